@@ -33,7 +33,6 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before the HIP runtime starts (diart_amd/__init__.py)
 from pathlib import Path
 
 import numpy as np
@@ -261,7 +260,52 @@ def parse():
                     help="run ONLY the serialised roofline pass (the command profiles/*_rocprofv3_kernel_stats_serial_*.csv are traces of)")
     ap.add_argument("--no-exact-f32", action="store_true",
                     help="skip the second, untimed-for-`value` pass on the exact-f32 MFMA path")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32 / float64, rank 0, at most 64 MB: a seeded sample of the streams beyond that); "
+                         "config 2 only")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.config != 2 or args.serial_only):
+        ap.error("--dump-outputs: the timed path of config 2 only (not --config 1 / 3 / 5 or --serial-only)")
+    return args
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, ticket, result):
+    """--dump-outputs: the arrays `StreamBatch.finish` handed back for the last timed step (segmentation, embeddings,
+    clustering scores and assignments) and, with the output tail on, the aggregated scores and speech turns of the region
+    that step finalised.  Rows past a stream's `rows` / `nturns` are unwritten buffer space and are zeroed.  Over
+    DUMP_BYTES, a fixed seeded sample of the streams is kept (its indices in `stream_index.npy`)."""
+    seg, emb, scores, assign = result
+    arrays = {"segmentation": np.asarray(seg, np.float32), "embeddings": np.asarray(emb, np.float32),
+              "scores": np.asarray(scores, np.float64), "assignments": np.asarray(assign, np.float64)}
+    if ticket.get("tail") is not None:
+        agg, rows, t0, res, turns, nturns = ticket["tail"]
+        n = len(seg)
+        rows, nturns = np.asarray(rows[:n], np.int64), np.asarray(nturns[:n], np.int64)
+        agg = np.array(agg[:n, :max(1, int(rows.max()))], np.float64)
+        turns = np.array(turns[:n, :max(1, int(nturns.max()))], np.float64)
+        agg[np.arange(agg.shape[1])[None, :] >= rows[:, None]] = 0.0
+        turns[np.arange(turns.shape[1])[None, :] >= nturns[:, None]] = 0.0
+        arrays.update(aggregated=agg, aggregated_rows=rows.astype(np.float64), region_start=np.asarray(t0[:n], np.float64),
+                      resolution=np.asarray(res[:n], np.float64), turns=turns, turn_count=nturns.astype(np.float64))
+    n = len(seg)
+    per_stream = sum(a.nbytes for a in arrays.values()) / n
+    if per_stream * n > DUMP_BYTES:
+        fit = int((DUMP_BYTES - (1 << 16)) // (per_stream + 8))      # (npy headers, stream_index)
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, fit), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["stream_index"] = keep.astype(np.float64)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+    log(f"outputs of the last timed step -> {out}/ ({', '.join(sorted(arrays))}; "
+        f"{sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB)")
 
 
 def kernel_table(lib, precision="f16x3"):
@@ -1054,15 +1098,19 @@ def main():
             inflight.append(pipe.launch(window(t)))
             h1 = time.perf_counter()
             if len(inflight) >= pipe.max_inflight:
-                pipe.finish(inflight.pop(0), want_scores=True)
+                tk = inflight.pop(0)
+                last[0] = (tk, pipe.finish(tk, want_scores=True))
             h2 = time.perf_counter()
             host["launch"] += h1 - h0
             host["finish"] += h2 - h1
             parts.append((h1 - h0, h2 - h1, pipe.host_seconds["wait"], pipe.host_seconds["work"]))
         while inflight:
-            pipe.finish(inflight.pop(0), want_scores=True)
+            tk = inflight.pop(0)
+            last[0] = (tk, pipe.finish(tk, want_scores=True))
 
     main_pipe = [pipe]
+    # (ticket, finish() result) of the newest finished step: views of the engine's buffers, valid until its next launch
+    last = [None]
     parts = []                     # per launched step: (launch s, finish s, cumulative wait s, cumulative work s)
 
     def barrier():
@@ -1216,6 +1264,8 @@ def main():
         return
 
     elapsed, table, n_sampled = timed_pass(pipe, f"timed region ({precision})")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last[0])        # before any later pass reuses the buffers
 
     def power_pass(p):
         """What the GPU draws while this pipeline runs: an UNTIMED pass of `--power-seconds` on the same engine, right behind

@@ -43,6 +43,8 @@ def gpu_local_cpus(device_index: int) -> list:
     """CPUs on the NUMA node the GPU hangs off (sysfs ``local_cpulist`` of its PCI function), [] if unknown."""
     try:
         import torch
+        if device_index >= torch.cuda.device_count():   # not visible here: asking would start the HIP runtime for nothing
+            return []
         p = torch.cuda.get_device_properties(device_index)
         bdf = "%04x:%02x:%02x.0" % (getattr(p, "pci_domain_id", 0), p.pci_bus_id, p.pci_device_id)
         return parse_cpulist(Path(f"/sys/bus/pci/devices/{bdf}/local_cpulist").read_text())

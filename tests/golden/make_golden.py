@@ -15,8 +15,7 @@ import numpy as np
 import torch
 
 HERE = Path(__file__).resolve().parent
-# --out DIR: write somewhere else (tests/test_oracle_golden.py regenerates into a scratch directory
-# and compares with the committed fixtures whenever /root/reference is present)
+# --out DIR: write somewhere else (to compare a regeneration with the committed fixtures)
 OUT = Path(sys.argv[sys.argv.index("--out") + 1]) if "--out" in sys.argv else HERE
 sys.path.insert(0, str(HERE.parent.parent))
 sys.path.insert(0, str(HERE))
@@ -97,6 +96,31 @@ def main():
                             assign=assign, active=active, score_sum=score_sum, raised=raised,
                             centers_trace=centers_trace, centers=clu.centers)
         print(name, "steps", T, "final speakers", int(active[-1].sum()), "raised", int(raised.sum()))
+
+
+def clustering_long_random(ref):
+    """blocks/clustering.py on the long random runs of scenarios.CLUSTERING_LONG_RANDOM: per case and step the digest
+    of the returned scores, whether the call raised, the active centroids as a bit mask; the final centroids."""
+    out = {}
+    for seed, K, D, G, tau, rho, delta in scenarios.CLUSTERING_LONG_RANDOM:
+        clu = ref.clustering.OnlineSpeakerClustering(tau, rho, delta, "cosine", G)
+        digest, raised, active = [], [], []
+        for seg, emb in scenarios.clustering_long_random_inputs(seed, K, D, G):
+            try:
+                res = clu(SlidingWindowFeature(seg, SlidingWindow(start=0.0, duration=0.1, step=0.1)), torch.from_numpy(emb))
+            except (AssertionError, ValueError):
+                digest.append(np.uint64(0))
+                raised.append(1)
+            else:
+                digest.append(scenarios.scores_digest(res.data))
+                raised.append(0)
+            active.append(sum(1 << int(g) for g in clu.active_centers))
+        out[f"s{seed}_digest"] = np.array(digest, dtype=np.uint64)
+        out[f"s{seed}_raised"] = np.array(raised, dtype=np.int8)
+        out[f"s{seed}_active"] = np.array(active, dtype=np.int64)
+        out[f"s{seed}_centers"] = np.asarray(clu.centers, dtype=np.float64)
+        print(f"long random s{seed}: steps {len(digest)}, raised {sum(raised)}")
+    np.savez_compressed(OUT / "clustering_long_random.npz", **out)
 
 
 def tail(ref):
@@ -227,8 +251,11 @@ if __name__ == "__main__":
         tail(load_reference())
     elif "--pipelines-only" in sys.argv:
         pipelines()
+    elif "--long-random-only" in sys.argv:
+        clustering_long_random(load_reference())
     else:
         main()
+        clustering_long_random(load_reference())
         tail(load_reference())
         pipelines()
         rttm_slice()

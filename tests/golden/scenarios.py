@@ -43,6 +43,45 @@ def clustering_inputs(name):
     return dict(seg=seg, emb=emb, tau=tau, rho=rho, delta=delta, G=G)
 
 
+# tests/test_clustering.py's long random runs: (seed, local speakers K, dim D, max_speakers G, tau, rho, delta); what the
+# reference's own clustering returned on them is in clustering_long_random.npz (one digest per step, see scores_digest)
+CLUSTERING_LONG_RANDOM = [(10, 3, 32, 20, 0.55, 0.25, 1.0), (11, 4, 16, 20, 0.507, 0.006, 1.057),
+                          (12, 3, 8, 3, 0.5, 0.2, 0.5), (13, 4, 12, 4, 0.6, 0.3, 0.9),
+                          (14, 3, 512, 20, 0.6, 0.3, 1.0)]
+
+
+def clustering_long_random_inputs(seed, K, D, G):
+    """(seg (F, K) f32, emb (K, D) f32) of every step: random activity from a pool of G + 6 voices, with NaN
+    embeddings, duplicated embeddings and silent chunks mixed in."""
+    rng = np.random.default_rng(seed)
+    T, F = (2500 if D < 100 else 400), 24
+    pool = rng.standard_normal((G + 6, D))
+    for t in range(T):
+        seg = (rng.random((F, K)) * (rng.random(K) < 0.8) * rng.choice([0.3, 0.8, 1.0], K)).astype(np.float32)
+        emb = (pool[rng.choice(len(pool), K, replace=False)] + 0.4 * rng.standard_normal((K, D))).astype(np.float32)
+        emb /= np.linalg.norm(emb, axis=1, keepdims=True)
+        r = rng.random()
+        if r < 0.05:
+            emb[rng.integers(K)] = np.nan
+        elif r < 0.1:
+            emb[1] = emb[0]
+        elif r < 0.13:
+            seg[:] = 0
+        if t == 0 and G < K:
+            seg[:, G:] = 0          # more first-chunk speakers than centroids: undefined in the reference
+        yield seg, emb
+
+
+def scores_digest(scores):
+    """64-bit digest of a score matrix: its shape and its values as f64 (-0.0 counted as 0.0), so two matrices have
+    the same digest exactly when np.array_equal holds for them (NaN-free)."""
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(scores, dtype=np.float64) + 0.0)
+    h = hashlib.blake2b(repr(a.shape).encode(), digest_size=8)
+    h.update(a.tobytes())
+    return np.uint64(int.from_bytes(h.digest(), "little"))
+
+
 def functional_inputs():
     rng = np.random.default_rng(123)
     seg = rng.random((4, 293, 3)).astype(np.float32)

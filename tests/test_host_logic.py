@@ -456,6 +456,9 @@ def test_eight_ranks_from_one_command_print_one_compact_line(tmp_path):
     script.write_text(EIGHT_RANK_SCRIPT)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["PYTHONDONTWRITEBYTECODE"] = "1"
+    # gloo ranks on the host: on a machine with a GPU, none of the 9 processes may open it (a device takes a few at most).
+    # No visible device, and torch's availability check counts visible devices instead of starting the HIP runtime.
+    env.update(HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="", PYTORCH_NVML_BASED_CUDA_CHECK="1")
     r = subprocess.run([sys.executable, str(script), str(ROOT), "8", str(ROOT / "profiles" / "r04_g_bench_driver_form.json")],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr

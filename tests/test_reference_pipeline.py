@@ -3,9 +3,7 @@
 ``tests/golden/pipeline_toy.npz`` holds what ``/root/reference/src/diart/blocks/diarization.py`` and
 ``blocks/vad.py`` (loaded by path, unmodified, around the toy models of ``golden/scenarios.py``)
 returned chunk by chunk for three (latency, batch size, timestamp shift, thresholds) cases, plus the
-segmentation / embeddings their blocks handed to the clustering (``make_golden.py::pipelines``; the
-fixture is regenerated from the reference and compared bit for bit by
-``test_oracle_golden.py`` whenever ``/root/reference`` is present).
+segmentation / embeddings their blocks handed to the clustering (``make_golden.py::pipelines``).
 
 * CPU (here): the HOST half of this package's pipelines (``finalise``: C++ clustering +
   aggregation + binarisation in one call, timestamps, buffers, shift) fed with the reference blocks'

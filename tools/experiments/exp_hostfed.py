@@ -6,7 +6,6 @@ C device ring fed from DEVICE blocks (no PCIe)
 D device ring fed from pinned HOST blocks (= bench `host_fed`)
 E as D with the push of step t+1 issued BEFORE finish(t - depth) (one step earlier)"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from pathlib import Path
 import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))

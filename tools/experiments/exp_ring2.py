@@ -3,7 +3,6 @@
  (a) a dense resident array view, (b) the ring window with NO pushes in between, (c) the ring with a push before every step
  on one stream, back to back."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from pathlib import Path
 import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))

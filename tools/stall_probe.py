@@ -10,7 +10,6 @@ import sys
 import time
 from pathlib import Path
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch  # noqa: E402
 
