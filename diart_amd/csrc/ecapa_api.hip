@@ -202,6 +202,8 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     if (lmax < MIN_NUM_SAMPLES) {       // "every signal is too short": all NaN
         for (int i = 0; i < N; ++i) h_short[i] = 1;
         DZ_HIP(hipMemcpyAsync(e->tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
+        DZ_HIP(hipMemsetAsync(e->nvalid, 0, sizeof(int) * N, st));     // (no frames: what peek 6 / 7 report)
+        DZ_HIP(hipMemsetAsync(e->nmask, 0, sizeof(int) * N, st));
         e->lastT = 0;
         return dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st);
     }
@@ -347,6 +349,8 @@ extern "C" int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long lo
         case 3: *d_ptr = e->mfa; *count = N * T * C3; return 0;
         case 4: *d_ptr = e->pooled; *count = N * 2 * C3; return 0;
         case 5: *d_ptr = e->lens; *count = N; return 0;
+        case 6: *d_ptr = e->nvalid; *count = N; return 0;
+        case 7: *d_ptr = e->nmask; *count = N; return 0;
     }
     dz_set_error("dz_ecapa_peek: unknown buffer %d", which);
     return 2;

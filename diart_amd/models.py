@@ -340,7 +340,7 @@ class HipEcapaEmbedding(_HipModule):
         ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
         _lib.check(_lib.load().dz_ecapa_peek(self._handles[num_samples][0], which, C.byref(ptr),
                                              C.byref(cnt), C.byref(frames)), "dz_ecapa_peek")
-        dtype = torch.int32 if which == 5 else torch.float32
+        dtype = torch.int32 if which in (5, 6, 7) else torch.float32
         out = torch.empty(cnt.value, dtype=dtype, device=self.device)
         torch.cuda.synchronize(self.device)
         import ctypes

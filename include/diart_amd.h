@@ -251,9 +251,13 @@ int dz_ecapa_create(dz_ctx* ctx, const dz_ecapa_weights* w, int max_rows, int nu
 int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
                      int n_rows, int mask_frames, float* d_out, void* stream);
 /* device pointer + element count of an intermediate of the LAST forward (parity tests):
- * 0 features (N,T,80)  1 block0 (N,T,1024)  2 cat (N,T,3072)  3 mfa (N,T,3072)
+ * 0 features (N,T,80)  1 block0 (N,T,1024)  2 ASP logits (N,T,3072; the concatenation's buffer,
+ * which holds the attention logits once a forward has returned)  3 mfa (N,T,3072)
  * 4 pooled (N,6144)    5 kept-sample counts (N) as int32, -(count + 1) for a row whose kept
- * samples hold a NaN / Inf (its embedding is NaN);  *frames receives T                   */
+ * samples hold a NaN / Inf (its embedding is NaN)  6 nvalid (N) as int32: frames of the sentence
+ * mean, round(float32(len / lmax) * T)  7 nmask (N) as int32: frames of the squeeze-excitation
+ * mean and the attentive pooling, #{t : t < float32(len / lmax) * T} (6 and 7 are 0 when every
+ * row is too short);  *frames receives T                                                  */
 int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long long* count, int* frames);
 int dz_ecapa_destroy(dz_ecapa* e);
 
