@@ -91,6 +91,7 @@ SIGNATURES = {
     "dz_ecapa_frames_for": (C.c_int, [C.c_int]),
     "dz_ecapa_create": (C.c_int, [vp, C.POINTER(EcapaWeights), C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_ecapa_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_ecapa_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_ecapa_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_ecapa_destroy": (C.c_int, [vp]),
     "dz_prof_enable": (C.c_int, [C.c_int]),
@@ -180,7 +181,7 @@ class ConvGemmDesc(C.Structure):
         ("ksplit", C.c_int), ("ysplit", C.c_longlong), ("agroup", C.c_int), ("pad", C.c_int),
         ("X2", vp), ("rowbias", vp), ("Wsplit", vp), ("Xsplit", vp), ("xplane", C.c_longlong),
         ("Ysplit", vp), ("yplane", C.c_longlong), ("npart", vp), ("ngamma", vp), ("nbeta", vp),
-        ("npart_tiles", C.c_int), ("npart_T", C.c_int), ("oflag", vp)]
+        ("npart_tiles", C.c_int), ("npart_T", C.c_int), ("oflag", vp), ("Tdev", vp)]
 
 
 (EPI_BIAS, EPI_BIAS_LEAKY, EPI_BIAS_SIGMOID, EPI_TDNN, EPI_POOL3, EPI_BIAS_RELU, EPI_RELU_BN,

@@ -301,6 +301,8 @@ int dz_launch_finalize_norm(const float* partials, int B, int ntile, int C, int 
 
 // k_convgemm.hip ------------------------------------------------------------
 typedef dz_convgemm_desc DzConvGemm;
+// internal epilogue flag of k_convgemm.hip / k_gemm_split.hip: the instance that reflects at DzConvGemm.Tdev
+constexpr int DZ_EPI_TG = 0x100;
 int dz_launch_convgemm(const DzConvGemm& p, hipStream_t st);
 // k_gemm_f32.hip: the exact-f32 kernel of the wide layers (dz_launch_convgemm routes to it when dz_gemm_f32_ok)
 bool dz_gemm_f32_ok(const DzConvGemm& p);
@@ -489,10 +491,14 @@ int dz_launch_cdist(const float* emb, const double* centers, int n, int k, int g
 
 // k_ecapa.hip ---------------------------------------------------------------
 int dz_launch_mask_compact(const float* wave, long long stride, int S, const float* masks, int Fw,
-                           int rows, float* sig, long long sig_stride, int* lens, hipStream_t st);
+                           int rows, float* sig, long long sig_stride, int* lens, hipStream_t st,
+                           int rows_per_wave = 1);
+// per-group geometry of dz_ecapa_forward_groups (k_ecapa.hip: ecapa_geometry_kernel)
+int dz_launch_ecapa_geometry(const int* lens, int G, int K, int Tc, int min_samples, int hop, int* nvalid,
+                             int* nmask, int* tooshort, int* tdev, int* rv, int* rm, int* rt, hipStream_t st);
 int dz_launch_power(const float* spec, int lds, long long rows, float* pw, hipStream_t st);
 int dz_launch_fbank_post(const float* melp, int T, int rows, const int* nvalid, float* feats,
-                         hipStream_t st);
+                         hipStream_t st, const int* tdev = nullptr);
 int dz_launch_se_mean(const float* x, int T, int C, int ldx, int rows, const int* nmask, float* s,
                       hipStream_t st);
 int dz_launch_se_apply(const float* x, int ldx, const float* gate, const float* resid, int ldr,

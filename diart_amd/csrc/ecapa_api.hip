@@ -38,7 +38,9 @@ struct dz_ecapa {
     // split-f16 precision: the inputs of the wide 1 x 1 layers as kb-major f16 planes (k_gemm_pre.hip), [2][C / 32][N T][32]
     unsigned short *b0s, *ress, *cats;
     int *lens, *nvalid, *nmask, *tooshort;
-    int lastN, lastT;
+    // groups forward: per-row frame count the kernels read, and the geometry dz_ecapa_peek 6 / 7 / 8 report
+    int *tdev, *rep_nvalid, *rep_nmask, *rep_T;
+    int lastN, lastT, lastGroups;
 };
 
 static void ecapa_carve(dz_ecapa* e, Carve& a) {
@@ -76,6 +78,10 @@ static void ecapa_carve(dz_ecapa* e, Carve& a) {
     e->nvalid = a.take<int>(N);
     e->nmask = a.take<int>(N);
     e->tooshort = a.take<int>(N);
+    e->tdev = a.take<int>(N);
+    e->rep_nvalid = a.take<int>(N);
+    e->rep_nmask = a.take<int>(N);
+    e->rep_T = a.take<int>(N);
 }
 
 extern "C" int dz_ecapa_frames_for(int num_samples) { return num_samples > 0 ? 1 + num_samples / HOP : 0; }
@@ -128,14 +134,14 @@ static int gemm(int tag, int rows_n, hipStream_t st, const float* X, int ldx, lo
                 int dil, int pad, const dz_layer& L, const float* bias, int Kpad, int Npad, int Nstore,
                 float* Y, int ldy, long long ybs, int epi, const float* X2 = nullptr,
                 const float* rowbias = nullptr, int ksplit = 0, long long ysplit = 0, void* Yplanes = nullptr,
-                long long yplane = 0) {
+                long long yplane = 0, const int* Tdev = nullptr) {
     DzConvGemm p;
     memset(&p, 0, sizeof(p));
     p.X = X; p.W = L.w; p.bias = bias ? bias : L.b; p.e0 = L.s; p.e1 = L.h; p.Y = Y;
     p.B = B; p.Tin = T; p.Tout = pad ? T : T - (taps - 1) * dil; p.Tstore = p.Tout;
     p.Cin = Cin; p.taps = taps; p.dil = dil; p.pad = pad; p.K = taps * Cin; p.Kpad = Kpad;
     p.Npad = Npad; p.Nstore = Nstore; p.ldx = ldx; p.ldy = ldy; p.xbs = xbs; p.ybs = ybs;
-    p.epi = epi; p.X2 = X2; p.rowbias = rowbias; p.ksplit = ksplit; p.ysplit = ysplit;
+    p.epi = epi; p.X2 = X2; p.rowbias = rowbias; p.ksplit = ksplit; p.ysplit = ysplit; p.Tdev = Tdev;
     // every layer that comes with split-f16 planes (default precision: block 0, the wide 1x1 layers, the
     // Res2Net convolutions with their reflect padding and second input, the attention's output
     // convolution, the DFT) runs the same contraction on the f16 matrix cores (k_gemm_split.hip)
@@ -165,6 +171,8 @@ static int gemm_pre(int tag, int rows_n, hipStream_t st, const void* Xplanes, lo
     return dz_launch_gemm_pre(p, st);
 }
 
+static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_out, hipStream_t st);
+
 extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave_stride,
                                 const float* d_masks, int N, int mask_frames, float* d_out,
                                 void* stream) {
@@ -176,7 +184,6 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     DzRangeScope range_scope(e->ctx->oflag_dev);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    const dz_ecapa_weights& w = e->w;
 
     // ---- 1. mask -> kept samples, zero padded rows (200 leading zeros = centred STFT) ---------
     DZ_HIP(hipMemsetAsync(e->sig, 0, sizeof(float) * (size_t)N * e->lstride, st));
@@ -199,6 +206,7 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     int lmax = 0;
     for (int i = 0; i < N; ++i) lmax = h_lens[i] > lmax ? h_lens[i] : lmax;
     e->lastN = N;
+    e->lastGroups = 0;
     if (lmax < MIN_NUM_SAMPLES) {       // "every signal is too short": all NaN
         for (int i = 0; i < N; ++i) h_short[i] = 1;
         DZ_HIP(hipMemcpyAsync(e->tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
@@ -225,6 +233,17 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     DZ_HIP(hipMemcpyAsync(e->nvalid, h_nvalid, sizeof(int) * N, hipMemcpyHostToDevice, st));
     DZ_HIP(hipMemcpyAsync(e->nmask, h_nmask, sizeof(int) * N, hipMemcpyHostToDevice, st));
     DZ_HIP(hipMemcpyAsync(e->tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
+    if ((rc = ecapa_network(e, N, T, nullptr, d_out, st))) return rc;
+    return dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st);
+}
+
+// Steps 2 - 3 of a forward (Fbank, ECAPA-TDNN, fc -> d_out, before the NaN rows) over the N rows of e->sig laid
+// out T frames apart, whose geometry (e->nvalid, e->nmask) is already on the device.  tdev: NULL (every row has
+// T frames) or the device [N] frame count of each row (the groups forward: T = the handle's Tc; a row reflects
+// and takes its top-dB maximum at its own count, and the frames past it are computed but read by no output).
+static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_out, hipStream_t st) {
+    int rc;
+    const dz_ecapa_weights& w = e->w;
     const long long NT = (long long)N * T;
 
     // ---- 2. Fbank: STFT as one GEMM over overlapping rows (hop 160 < window 400) ---------------
@@ -237,7 +256,7 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     if ((rc = gemm(DZ_T_ECAPA_FBANK, N, st, e->pw, 204, 0, 1, (int)NT, 204, 1, 1, 0, mel, nullptr, 224, 128, 80, e->melp, 80, 0,
                    DZ_EPI_BIAS)))
         return rc;
-    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->nvalid, e->feats, st))) return rc; }
+    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->nvalid, e->feats, st, tdev))) return rc; }
 
     // ---- 3. ECAPA-TDNN -------------------------------------------------------------------------
     // Split-f16 precision: the seven wide 1 x 1 layers (tdnn1 / tdnn2 of the three blocks, the MFA convolution: 84 % of
@@ -248,7 +267,7 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     const long long p1 = NT * C1, p3 = NT * C3;          // elements between the hi and lo planes
     // block 0: Conv1d(80 -> 1024, k5) -> ReLU -> BN
     if ((rc = gemm(DZ_T_ECAPA_BLOCK0, N, st, e->feats, 80, (long long)T * 80, N, T, 80, 5, 1, 2, w.block0, nullptr, 416, C1, C1,
-                   e->b0, C1, (long long)T * C1, DZ_EPI_RELU_BN, nullptr, nullptr, 0, 0, pre ? e->b0s : nullptr, p1)))
+                   e->b0, C1, (long long)T * C1, DZ_EPI_RELU_BN, nullptr, nullptr, 0, 0, pre ? e->b0s : nullptr, p1, tdev)))
         return rc;
     const int dil[3] = {2, 3, 4};
     for (int i = 0; i < 3; ++i) {
@@ -277,7 +296,7 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
             // (y7 has no f32 reader when tdnn2 takes the planes)
             if ((rc = gemm(DZ_T_ECAPA_RES2, N, st, e->t1 + j * 128, C1, (long long)T * C1, N, T, 128, 3, dil[i], dil[i], b.res[j - 1],
                            nullptr, 384, 128, 128, pre && j == 7 ? nullptr : e->res + j * 128, C1, (long long)T * C1, DZ_EPI_RELU_BN,
-                           x2, nullptr, 0, 0, pre ? e->ress + (size_t)j * 4 * NT * 32 : nullptr, p1)))
+                           x2, nullptr, 0, 0, pre ? e->ress + (size_t)j * 4 * NT * 32 : nullptr, p1, tdev)))
                 return rc;
         }
         // tdnn2 (1x1)
@@ -335,13 +354,57 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
                    0, DZ_EPI_BIAS, nullptr, nullptr, FC_SPLIT, ysplit)))
         return rc;
     { DzProfScope ps(DZ_T_ECAPA_FC, N); if ((rc = dz_launch_splitk_finish(e->parts, FC_SPLIT, ysplit, N, EMB, 0, d_out, st))) return rc; }
-    return dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st);
+    return 0;
+}
+
+// The forward of the rows of n_groups chunks, K (rows_per_group) speaker rows each, every group with its own
+// batch geometry — what dz_ecapa_forward computes for that group's K rows alone — in one launch sequence with
+// no host round trip: the geometry is derived on the device (dz_launch_ecapa_geometry) and every buffer is laid
+// out with the handle's Tc frames per row.  Row g K + k reads waveform row g and mask row g K + k ((G, K, Fw)
+// contiguous, the speaker-major OSP weights of dz_seg_forward_osp).
+extern "C" int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
+                                       int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                                       void* stream) {
+    DZ_REQUIRE(e && d_wave && d_masks && d_out, "dz_ecapa_forward_groups: NULL argument");
+    DZ_REQUIRE(n_groups >= 1 && rows_per_group >= 1 && (long long)n_groups * rows_per_group <= e->Nm,
+               "dz_ecapa_forward_groups: %d groups x %d rows outside [1, %d]", n_groups, rows_per_group, e->Nm);
+    DZ_REQUIRE(mask_frames >= 1, "dz_ecapa_forward_groups: mask_frames %d", mask_frames);
+    DZ_REQUIRE(wave_stride >= 0, "dz_ecapa_forward_groups: negative stride");
+    DZ_HIP(hipSetDevice(e->ctx->device));
+    DzRangeScope range_scope(e->ctx->oflag_dev);
+    hipStream_t st = (hipStream_t)stream;
+    const int N = n_groups * rows_per_group, Tc = e->Tc;
+    int rc;
+    DZ_HIP(hipMemsetAsync(e->sig, 0, sizeof(float) * (size_t)N * e->lstride, st));
+    { DzProfScope ps(DZ_T_ECAPA_FBANK, N);
+      if ((rc = dz_launch_mask_compact(d_wave, wave_stride, e->S, d_masks, mask_frames, N, e->sig, e->lstride, e->lens,
+                                       st, rows_per_group)))
+          return rc;
+      if ((rc = dz_launch_ecapa_geometry(e->lens, n_groups, rows_per_group, Tc, MIN_NUM_SAMPLES, HOP, e->nvalid, e->nmask,
+                                         e->tooshort, e->tdev, e->rep_nvalid, e->rep_nmask, e->rep_T, st)))
+          return rc; }
+    e->lastN = N;
+    e->lastT = Tc;
+    e->lastGroups = 1;
+    if ((rc = ecapa_network(e, N, Tc, e->tdev, d_out, st))) return rc;
+    if ((rc = dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st))) return rc;
+    return normalize ? dz_launch_l2norm(d_out, N, EMB, 1.0f, st) : 0;
 }
 
 extern "C" int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long long* count, int* frames) {
     DZ_REQUIRE(e && d_ptr && count, "dz_ecapa_peek: NULL argument");
     const long long N = e->lastN, T = e->lastT;
     if (frames) *frames = (int)T;
+    if (e->lastGroups) {        // the geometry a groups forward reports (ecapa_geometry_kernel)
+        switch (which) {
+            case 6: *d_ptr = e->rep_nvalid; *count = N; return 0;
+            case 7: *d_ptr = e->rep_nmask; *count = N; return 0;
+            case 8: *d_ptr = e->rep_T; *count = N; return 0;
+        }
+    } else if (which == 8) {
+        dz_set_error("dz_ecapa_peek: buffer 8 (per-row frames) exists after dz_ecapa_forward_groups only");
+        return 2;
+    }
     switch (which) {
         case 0: *d_ptr = e->feats; *count = N * T * 80; return 0;
         case 1: *d_ptr = e->b0; *count = N * T * C1; return 0;

@@ -36,8 +36,13 @@ struct Cfg {
 
 __device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : v * DZ_LEAKY_SLOPE; }
 
-template <int BN, bool PRO, int EPI>
+// EPIX = an epilogue DZ_EPI_* | DZ_EPI_TG: reflect "same" padding at each batch item's own frame count p.Tdev[b]
+// for the output frames below it (ECAPA's groups forward: rows of different lengths laid out with one stride);
+// frames at or past it keep Tin.  (The flag rides on the epilogue so that every other instance keeps its name.)
+template <int BN, bool PRO, int EPIX>
 __global__ __launch_bounds__(256) void convgemm_kernel(DzConvGemm p) {
+    constexpr int EPI = EPIX & ~DZ_EPI_TG;
+    constexpr bool TG = (EPIX & DZ_EPI_TG) != 0;
     using C = Cfg<BN>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -60,6 +65,12 @@ __global__ __launch_bounds__(256) void convgemm_kernel(DzConvGemm p) {
     for (int a = 0; a < C::A_F4; ++a) {
         const int t = t0 + lrow + 32 * a;
         trow[a] = t < p.Tout ? t : p.Tout - 1;
+    }
+    int trf[C::A_F4];          // (TG) where the reflection of row a happens
+    if (TG) {
+        const int tg = p.Tdev[b];
+#pragma unroll
+        for (int a = 0; a < C::A_F4; ++a) trf[a] = trow[a] < tg ? tg : p.Tin;
     }
     const float* Wt = p.W + (long long)(n0 + lrow) * p.Kpad + lkq * 4;
 
@@ -96,8 +107,9 @@ __global__ __launch_bounds__(256) void convgemm_kernel(DzConvGemm p) {
             if (kvalid) {
                 int tt = trow[a] + toff;
                 if (p.pad) {  // "same" convolution with reflect padding (ECAPA TDNN blocks)
+                    const int Tr = TG ? trf[a] : p.Tin;
                     tt = tt < 0 ? -tt : tt;
-                    tt = tt >= p.Tin ? 2 * (p.Tin - 1) - tt : tt;
+                    tt = tt >= Tr ? 2 * (Tr - 1) - tt : tt;
                 }
                 const long long off = (long long)tt * p.ldx + c;
                 v = *reinterpret_cast<const f32x4*>(Xb + off);
@@ -272,6 +284,9 @@ int dz_launch_convgemm(const DzConvGemm& p, hipStream_t st) {
                "convgemm: reflect 'same' padding needs 2*pad == (taps-1)*dil and pad < Tin");
     DZ_REQUIRE(p.ksplit <= 1 || (p.epi == DZ_EPI_BIAS && p.ksplit <= p.Kpad / KT),
                "convgemm: split-K needs the plain bias epilogue and ksplit <= k-tiles");
+    // (the caller guarantees pad < Tdev[b] for every batch item; Tdev is read on the device only)
+    DZ_REQUIRE(p.Tdev == nullptr || (p.pad > 0 && p.epi == DZ_EPI_RELU_BN && p.norm_on_load == 0),
+               "convgemm: per-item frame counts (Tdev) are built for the padded RELU_BN layers");
     const bool wide = (p.Npad % 128 == 0);
     DZ_REQUIRE(p.Npad % 64 == 0, "convgemm: Npad must be a multiple of 64");
     const bool pro = p.norm_on_load != 0;
@@ -303,6 +318,7 @@ int dz_launch_convgemm(const DzConvGemm& p, hipStream_t st) {
             DZ_CG(128, false, DZ_EPI_BIAS_RELU);
         case DZ_EPI_RELU_BN:
             DZ_REQUIRE(wide && !pro, "convgemm: RELU_BN is BN=128, no norm-on-load");
+            if (p.Tdev) DZ_CG(128, false, DZ_EPI_RELU_BN | DZ_EPI_TG);
             DZ_CG(128, false, DZ_EPI_RELU_BN);
         case DZ_EPI_RELU_BN_TANH:
             DZ_REQUIRE(wide && !pro, "convgemm: RELU_BN_TANH is BN=128, no norm-on-load");

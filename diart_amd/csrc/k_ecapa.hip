@@ -2,6 +2,7 @@
 // convolution / linear layer (those run on convgemm, k_convgemm.hip).
 //   mask_compact   PretrainedSpeakerEmbedding.__call__: nearest-resampled mask > 0.5 -> kept samples
 //   power          |STFT|^2 from the (re | im) GEMM output
+//   ecapa_geometry per-group batch geometry of the groups forward (frames, nvalid, nmask, flags) on the device
 //   fbank_post     10 log10 -> top_db clip against the row maximum -> sentence mean normalisation
 //   se_mean / se_apply     squeeze-excitation: masked time mean, gate * x + residual
 //   asp_gstats / asp_pool  attentive statistics pooling: global context stats, masked softmax stats
@@ -16,10 +17,11 @@ namespace {
 // mask_compact: one workgroup per row.  Sample s is kept iff
 // masks[min(floor(s * Fw / S), Fw - 1)] > 0.5  (F.interpolate(mode="nearest")); kept samples are
 // packed in order at sig[row][200 ...] (200 = the n_fft/2 zero padding of the centred STFT;
-// the buffer is zero-filled before, which also provides pad_sequence's zeros).
+// the buffer is zero-filled before, which also provides pad_sequence's zeros).  Row r reads waveform
+// row r / rows_per_wave (the groups forward: the K speaker rows of a chunk share its waveform).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void mask_compact_kernel(const float* __restrict__ wave,
-                                                           long long stride, int S,
+                                                           long long stride, int rows_per_wave, int S,
                                                            const float* __restrict__ masks, int Fw,
                                                            float* __restrict__ sig,
                                                            long long sig_stride,
@@ -27,7 +29,7 @@ __global__ __launch_bounds__(1024) void mask_compact_kernel(const float* __restr
     __shared__ int cnt[256];
     __shared__ int bad_s;                     // a kept sample is NaN / Inf: the row's length is reported as -(len + 1)
     const int row = blockIdx.x, tid = threadIdx.x;
-    const float* w = wave + (long long)row * stride;
+    const float* w = wave + (long long)(row / rows_per_wave) * stride;
     float* o = sig + (long long)row * sig_stride + 200;
     if (tid == 0) bad_s = 0;
     __syncthreads();
@@ -80,6 +82,56 @@ __global__ __launch_bounds__(1024) void mask_compact_kernel(const float* __restr
     if (tid == (int)blockDim.x - 1) lens[row] = bad_s ? -(total + 1) : total;
 }
 
+// ---------------------------------------------------------------------------
+// ecapa_geometry: one thread per group of K rows.  The host code of dz_ecapa_forward (ecapa_api.hip) on the
+// device, in the same float32 arithmetic: lmax over the group's kept-sample counts (a count -(len + 1) marks a
+// row with a NaN / Inf sample), T = 1 + lmax / 160, per row rel = len / lmax (1 for a too-short row), v = rel * T,
+// nvalid = round half to even (v), nmask = ceil(v), both clamped to [1, T].  Two sets of outputs:
+//   computation (nvalid, nmask, tdev): what the kernels read.  A group whose rows are all shorter than 640
+//     samples (NaN rows) is computed over all Tc frames with nvalid = nmask = Tc: finite, and read by no output;
+//   report (rv, rm, rt): what dz_ecapa_peek 6 / 7 / 8 return — dz_ecapa_forward's values, 0 for such a group.
+// ---------------------------------------------------------------------------
+__global__ void ecapa_geometry_kernel(const int* __restrict__ lens, int G, int K, int Tc, int min_samples, int hop,
+                                      int* __restrict__ nvalid, int* __restrict__ nmask, int* __restrict__ tooshort,
+                                      int* __restrict__ tdev, int* __restrict__ rv, int* __restrict__ rm,
+                                      int* __restrict__ rt) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int r0 = g * K;
+    int lmax = 0;
+    for (int k = 0; k < K; ++k) {
+        const int l = lens[r0 + k];
+        lmax = max(lmax, l < 0 ? -l - 1 : l);
+    }
+    if (lmax < min_samples) {                 // "every signal is too short": all NaN
+        for (int k = 0; k < K; ++k) {
+            const int r = r0 + k;
+            tooshort[r] = 1;
+            nvalid[r] = nmask[r] = tdev[r] = Tc;
+            rv[r] = rm[r] = rt[r] = 0;
+        }
+        return;
+    }
+    const int T = 1 + lmax / hop;
+    for (int k = 0; k < K; ++k) {
+        const int r = r0 + k;
+        const int l0 = lens[r];
+        const bool bad = l0 < 0;
+        const int len = bad ? -l0 - 1 : l0;
+        const bool too_short = len < min_samples;
+        tooshort[r] = too_short || bad;
+        const float rel = too_short ? 1.0f : __fdiv_rn((float)len, (float)lmax);
+        const float v = __fmul_rn(rel, (float)T);
+        int nv = (int)rintf(v);               // torch.round: half to even
+        nv = nv < 1 ? 1 : (nv > T ? T : nv);
+        int nm = (int)ceilf(v);               // #{t : (float)t < v}
+        nm = nm < 1 ? 1 : (nm > T ? T : nm);
+        nvalid[r] = rv[r] = nv;
+        nmask[r] = rm[r] = nm;
+        tdev[r] = rt[r] = T;
+    }
+}
+
 // spec [rows][lds] = (re[0..200] | im[0..200]) -> pw [rows][204] (cols 201..203 = 0)
 __global__ void power_kernel(const float* __restrict__ spec, int lds, long long rows,
                              float* __restrict__ pw) {
@@ -105,9 +157,11 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 
 // mel power [row][T][80] -> features [row][T][80]:
 //   x_db = 10 log10(max(x, 1e-10)); x_db = max(x_db, rowmax - 80); x_db -= mean over the first
-//   nvalid[row] frames (speechbrain Filterbank top_db + InputNormalization("sentence")).
+//   nvalid[row] frames (speechbrain Filterbank top_db + InputNormalization("sentence")).  Rows are T frames
+//   apart; the row maximum is taken over tdev[row] of them (the row's own frames), or all T if tdev is NULL.
 __global__ __launch_bounds__(256) void fbank_post_kernel(const float* __restrict__ melp, int T,
                                                          const int* __restrict__ nvalid,
+                                                         const int* __restrict__ tdev,
                                                          float* __restrict__ feats) {
     __shared__ float red[4];
     __shared__ float msum[3][80];
@@ -115,7 +169,8 @@ __global__ __launch_bounds__(256) void fbank_post_kernel(const float* __restrict
     const float* x = melp + (long long)row * T * 80;
     float* y = feats + (long long)row * T * 80;
     float mx = -INFINITY;
-    for (int i = tid; i < T * 80; i += 256) mx = fmaxf(mx, 10.f * log10f(fmaxf(x[i], 1e-10f)));
+    const int Tg = tdev ? tdev[row] : T;
+    for (int i = tid; i < Tg * 80; i += 256) mx = fmaxf(mx, 10.f * log10f(fmaxf(x[i], 1e-10f)));
     const float floor_db = block_max(mx, red) - 80.f;
     // per-mel mean over the valid frames: thread (m = tid % 80, part = tid / 80) for tid < 240
     const int nv = nvalid[row];
@@ -338,8 +393,9 @@ __global__ void nan_rows_kernel(float* __restrict__ out, int rows, int dim,
 }  // namespace
 
 int dz_launch_mask_compact(const float* wave, long long stride, int S, const float* masks, int Fw,
-                           int rows, float* sig, long long sig_stride, int* lens, hipStream_t st) {
-    DZ_LAUNCH(mask_compact_kernel, dim3(rows), dim3(1024), 0, st, wave, stride, S, masks, Fw,
+                           int rows, float* sig, long long sig_stride, int* lens, hipStream_t st, int rows_per_wave) {
+    DZ_REQUIRE(rows_per_wave >= 1, "mask_compact: rows_per_wave %d", rows_per_wave);
+    DZ_LAUNCH(mask_compact_kernel, dim3(rows), dim3(1024), 0, st, wave, stride, rows_per_wave, S, masks, Fw,
                        sig, sig_stride, lens);
     DZ_HIP(hipGetLastError());
     return 0;
@@ -351,9 +407,17 @@ int dz_launch_power(const float* spec, int lds, long long rows, float* pw, hipSt
     DZ_HIP(hipGetLastError());
     return 0;
 }
+int dz_launch_ecapa_geometry(const int* lens, int G, int K, int Tc, int min_samples, int hop, int* nvalid,
+                             int* nmask, int* tooshort, int* tdev, int* rv, int* rm, int* rt, hipStream_t st) {
+    DZ_REQUIRE(G >= 1 && K >= 1 && Tc >= 1 && hop >= 1, "ecapa_geometry: G %d, K %d, Tc %d", G, K, Tc);
+    DZ_LAUNCH(ecapa_geometry_kernel, dim3((G + 63) / 64), dim3(64), 0, st, lens, G, K, Tc, min_samples, hop, nvalid,
+              nmask, tooshort, tdev, rv, rm, rt);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}
 int dz_launch_fbank_post(const float* melp, int T, int rows, const int* nvalid, float* feats,
-                         hipStream_t st) {
-    DZ_LAUNCH(fbank_post_kernel, dim3(rows), dim3(256), 0, st, melp, T, nvalid, feats);
+                         hipStream_t st, const int* tdev) {
+    DZ_LAUNCH(fbank_post_kernel, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
     DZ_HIP(hipGetLastError());
     return 0;
 }

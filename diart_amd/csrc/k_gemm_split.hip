@@ -77,8 +77,12 @@ struct Cfg {
     static_assert(BN * 4 <= T, "one B chunk per thread at most");
 };
 
-template <int WM, int NB, bool PRO, int EPI>
+// EPIX = an epilogue DZ_EPI_* | DZ_EPI_TG: reflect padding at the batch item's own frame count p.Tdev[b] for the
+// rows below it (k_convgemm.hip)
+template <int WM, int NB, bool PRO, int EPIX>
 __global__ __launch_bounds__(128 * WM) void gemm_split_kernel(DzConvGemm p) {
+    constexpr int EPI = EPIX & ~DZ_EPI_TG;
+    constexpr bool TG = (EPIX & DZ_EPI_TG) != 0;
     using C = Cfg<WM, NB>;
     constexpr int BM = C::BM, BN = C::BN;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -103,6 +107,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_kernel(DzConvGemm p) {
         __syncthreads();
     }
     const int trow = (t0 + crow) < p.Tout ? (t0 + crow) : p.Tout - 1;
+    const int trf = TG && trow < p.Tdev[b] ? p.Tdev[b] : p.Tin;     // where this row's reflection happens
     const unsigned short* Whi = reinterpret_cast<const unsigned short*>(p.Wsplit);
     const unsigned short* Wlo = Whi + (long long)p.Npad * p.Kpad;
     const long long wofs = (long long)(n0 + (has_b ? crow : 0)) * p.Kpad + cidx * 8;
@@ -127,8 +132,9 @@ __global__ __launch_bounds__(128 * WM) void gemm_split_kernel(DzConvGemm p) {
             if (kvalid) {
                 int tt = trow + toff;
                 if (!PRO && p.pad) {   // "same" convolution with reflect padding (ECAPA TDNN blocks; k_convgemm.hip)
+                    const int Tr = TG ? trf : p.Tin;
                     tt = tt < 0 ? -tt : tt;
-                    tt = tt >= p.Tin ? 2 * (p.Tin - 1) - tt : tt;
+                    tt = tt >= Tr ? 2 * (Tr - 1) - tt : tt;
                 }
                 const long long xo = (long long)tt * p.ldx + c;
                 v0 = *reinterpret_cast<const f32x4*>(Xb + xo);
@@ -413,6 +419,8 @@ int dz_launch_gemm_split(const DzConvGemm& p_in, hipStream_t st) {
     DZ_REQUIRE(p.Ysplit == nullptr || (p.epi != DZ_EPI_POOL3 && p.ldy % 2 == 0 && p.yplane % 2 == 0 &&
                                        p.ybs % 2 == 0 && p.Npad <= p.ldy),
                "gemm_split: plane output needs even ldy / yplane / ybs, Npad <= ldy and no pooling");
+    DZ_REQUIRE(p.Tdev == nullptr || (p.pad > 0 && p.epi == DZ_EPI_RELU_BN && !p.norm_on_load),
+               "gemm_split: per-item frame counts (Tdev) are built for the padded RELU_BN layers");
     const bool pro = p.norm_on_load != 0;
 #define DZ_SP(WM, NB, PRO, EPI) return launch<WM, NB, PRO, EPI>(p, st)
     if (p.epi == DZ_EPI_POOL3) {
@@ -445,6 +453,7 @@ int dz_launch_gemm_split(const DzConvGemm& p_in, hipStream_t st) {
             DZ_SP(4, 2, false, DZ_EPI_BIAS_LEAKY);
         case DZ_EPI_RELU_BN:   // ECAPA-TDNN's 1x1 layers: conv -> ReLU -> folded BatchNorm
             DZ_REQUIRE(!pro, "gemm_split: RELU_BN has no norm-on-load instance");
+            if (p.Tdev) DZ_SP(4, 2, false, DZ_EPI_RELU_BN | DZ_EPI_TG);
             DZ_SP(4, 2, false, DZ_EPI_RELU_BN);
         case DZ_EPI_RELU_BN_TANH:   // ... and the attention TDNN of its pooling: -> tanh
             DZ_REQUIRE(!pro, "gemm_split: RELU_BN_TANH has no norm-on-load instance");

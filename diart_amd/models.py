@@ -327,6 +327,28 @@ class HipEcapaEmbedding(_HipModule):
                    "dz_ecapa_forward")
         return out
 
+    def forward_groups(self, waveform: torch.Tensor, masks: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """``waveform (G,1,S)``, ``masks (G,K,Fw)`` speaker-major -> ``(G,K,192)``: the ECAPA counterpart of
+        ``HipEmbedding.forward_multi``.  Each chunk's K rows are one call of their own, with the batch geometry
+        (padded frames, relative lengths) of those K rows alone, as the live reference embeds a chunk
+        (``StreamingInference`` at batch 1); all G groups run in one launch sequence whose geometry is derived on
+        the device — no synchronisation.  ``normalize``: L2-normalise every row (``EmbeddingNormalization(1)``)."""
+        if self.device is None:
+            self.to(waveform.device)
+        rows = _as_rows(waveform.to(self.device))
+        G, S = rows.shape
+        masks = masks.to(self.device, torch.float32).contiguous()
+        if masks.ndim != 3 or masks.shape[0] != G:
+            raise ValueError(f"masks must be (groups, speakers, frames), got {tuple(masks.shape)}")
+        K, fw = masks.shape[1], masks.shape[2]
+        handle = self._need(S, G * K)
+        out = torch.empty((G, K, self.dimension), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().dz_ecapa_forward_groups(handle, rows.data_ptr(), rows.stride(0) if G > 1 else S,
+                                                       masks.data_ptr(), G, K, fw, 1 if normalize else 0,
+                                                       out.data_ptr(), _stream_ptr(self.device)),
+                   "dz_ecapa_forward_groups")
+        return out
+
     def last_frames(self, num_samples: int) -> int:
         """Frames of the batch geometry of the last forward (= those of its longest kept row, what every row is
         padded to: ``dz_ecapa_peek``); no copy, no synchronisation.  ``bench.py --config 3`` prices its kernels with it."""
@@ -337,10 +359,15 @@ class HipEcapaEmbedding(_HipModule):
 
     def peek(self, num_samples: int, which: int) -> torch.Tensor:
         """Intermediate of the last forward (parity tests): see ``dz_ecapa_peek``."""
+        return self.peek_handle(self._handles[num_samples][0], which)
+
+    def peek_handle(self, handle, which: int) -> torch.Tensor:
+        """``peek`` of a handle this model created for someone else (``StreamBatch``'s per-lane handles);
+        synchronises the device."""
         ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
-        _lib.check(_lib.load().dz_ecapa_peek(self._handles[num_samples][0], which, C.byref(ptr),
-                                             C.byref(cnt), C.byref(frames)), "dz_ecapa_peek")
-        dtype = torch.int32 if which in (5, 6, 7) else torch.float32
+        _lib.check(_lib.load().dz_ecapa_peek(handle, which, C.byref(ptr), C.byref(cnt), C.byref(frames)),
+                   "dz_ecapa_peek")
+        dtype = torch.int32 if which in (5, 6, 7, 8) else torch.float32
         out = torch.empty(cnt.value, dtype=dtype, device=self.device)
         torch.cuda.synchronize(self.device)
         import ctypes

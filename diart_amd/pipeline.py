@@ -20,13 +20,19 @@ independent, only the host-side clustering is sequential per stream):
     stream B   : dz_emb_frames (SincNet -> 5 TDNN; independent of the segmentation, fills the
                  CUs the LSTM leaves idle)  <--wait all--  dz_emb_pool -> D2H (pinned)
     host       : clustering + output tail of step t-1 (C++ threads, fp64) while the GPU runs step t
+
+With a ``HipEcapaEmbedding`` (BASELINE.json config 3) stream B has nothing to run before the masks exist: it
+waits for the step's segmentation and runs ``dz_ecapa_forward_groups`` over the K speaker rows of every
+stream, each stream's rows with their own batch geometry (what the stream's own pipeline computes), then the
+D2H copy.  Nothing in the launch waits for the GPU, so with two lanes the ECAPA network of step t runs under
+the segmentation of step t + 1.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import time as _time
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -35,7 +41,7 @@ from . import _lib
 from .blocks.aggregation import BatchedOutputTail
 from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
-from .models import HipEmbedding, HipSegmentation, _as_rows
+from .models import HipEcapaEmbedding, HipEmbedding, HipSegmentation, _as_rows
 
 # lanes of a throughput engine (>= 64 streams per step on the matrix-core recurrence): profiles/r06*_lanes_grid.json
 THROUGHPUT_LANES = 6
@@ -158,7 +164,7 @@ class AudioRing:
 
 
 class StreamBatch:
-    def __init__(self, segmentation: HipSegmentation, embedding: HipEmbedding, num_streams: int,
+    def __init__(self, segmentation: HipSegmentation, embedding: Union[HipEmbedding, HipEcapaEmbedding], num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  normalize_embedding_weights: bool = False,
@@ -180,11 +186,18 @@ class StreamBatch:
         ``warmup``: warm steps on silence before the first real step of a window size (default 10, 0 = off);
         ``serial``: MEASUREMENT engine — one lane whose segmentation and embedding chains share ONE HIP stream, so
         that no two kernels ever overlap and a kernel's bracketed duration is its alone-time (what
-        ``rocprofv3 --kernel-trace --stats`` of the same run reports): ``bench.py``'s roofline pass."""
+        ``rocprofv3 --kernel-trace --stats`` of the same run reports): ``bench.py``'s roofline pass.
+
+        ``embedding`` may be a ``HipEcapaEmbedding`` (config 3: powerset segmentation + ECAPA-TDNN): each stream's K
+        speaker rows are embedded with the batch geometry of those rows alone (``forward_groups``), and the
+        embeddings are L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.  In that form
+        ``lanes`` defaults to 2 — one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s) carves
+        about 6.2 GB of device memory per lane — and ``emb_split`` must be 1."""
         from .config import setting
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)
         self.device = self.seg.device
+        self.ecapa = isinstance(self.emb, HipEcapaEmbedding)
         self.n = num_streams
         self.gamma, self.beta, self.norm_w = float(gamma), float(beta), bool(normalize_embedding_weights)
         self.clustering = BatchedSpeakerClustering(num_streams, tau_active, rho_update, delta_new,
@@ -202,6 +215,9 @@ class StreamBatch:
         # x-projection GEMM of one sub-batch runs under the latency-bound recurrence of another
         self.seg_split = max(1, min(int(_lib.exp_env("DZ_SEG_SPLIT", "1") if seg_split is None else seg_split), num_streams))
         self.emb_split = max(1, min(int(_lib.exp_env("DZ_EMB_SPLIT", "1") if emb_split is None else emb_split), num_streams))
+        if self.ecapa and self.emb_split != 1:
+            raise ValueError(f"StreamBatch: emb_split={self.emb_split} with an ECAPA embedding (its forward is one "
+                             "launch sequence over every stream's rows: emb_split must be 1)")
         # HIP stream priorities (0 normal, -1 high).  The segmentation chain is the long dependent one
         # (4 recurrences + their projections: ~2.2 ms in the pipeline, two lanes): its streams get the
         # high priority — round 3, two same-visit pairs: 1.215 vs 1.233 and 1.159 vs 1.180 ms per step
@@ -227,8 +243,10 @@ class StreamBatch:
         if depth is not None and lanes is not None and int(depth) != int(lanes):
             raise ValueError(f"StreamBatch: depth={depth} and lanes={lanes} name the same thing")
         matrix_core = self.recurrence not in (None, "valu")
+        # (an ECAPA engine keeps 2 lanes whatever the recurrence: ~6 GB of arena per lane at 64 streams)
+        many = (self.throughput or (matrix_core and num_streams >= 64)) and not self.ecapa
         self.depth = max(1, int(setting("lanes", lanes if lanes is not None else depth,
-                                        THROUGHPUT_LANES if (self.throughput or (matrix_core and num_streams >= 64)) else 2, int)))
+                                        THROUGHPUT_LANES if many else 2, int)))
         # How many launched-but-unfinished steps a throughput caller (bench.py, FileBatch) keeps: `depth` lanes
         # run concurrently, the steps beyond that wait IN THE STREAMS of their lane, so that a lane's next
         # step starts the moment the previous one ends instead of after the host has come back from
@@ -236,7 +254,7 @@ class StreamBatch:
         # lane's segmentation stream sat empty).
         # Round 6: a throughput engine keeps lanes + 2 (the second spare ticket covers the host's own launch + tail time of
         # a step: +3 % in the 20-step form, profiles/r06l_inflight_grid.json); the two-lane engines keep lanes + 1.
-        spare = 2 if (self.throughput or (matrix_core and num_streams >= 64)) else 1
+        spare = 2 if many else 1
         self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + spare, int)))
         self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
         # DZ_SHARED_EMB=1: ONE set of embedding streams serves every lane in step order and the
@@ -276,6 +294,9 @@ class StreamBatch:
         # recurrences of step t; on its own stream it runs under them and the lane's dependent chain is
         # the back half only (dz_seg_back: 4 recurrences, 3 projections, the MLP head).
         self.seg_front = _lib.exp_env("DZ_SEG_FRONT", "0") != "0"
+        if self.ecapa and (self.shared_emb or self.seg_front or self._ablate):
+            raise ValueError("StreamBatch: DZ_SHARED_EMB, DZ_SEG_FRONT and DZ_ABLATE are experiments of the x-vector "
+                             "engine; they have no meaning with an ECAPA embedding")
         pf = int(_lib.exp_env("DZ_PRIO_F", "0"))
         mk = lambda prio, k: [torch.cuda.Stream(self.device, priority=prio) for _ in range(k)]
         shared_b = mk(pb, self.emb_split) if self.shared_emb else None
@@ -368,7 +389,10 @@ class StreamBatch:
             sa, sb = self._ranges(self.n, self.seg_split), self._ranges(self.n, self.emb_split)
             hs = [self.seg._create(S, max(1, -(-self.n // self.seg_split)), throughput=self.throughput,
                                    recurrence=None if self.throughput else self.recurrence) for _ in sa]
-            he = [self.emb._create(S, max(1, -(-self.n // self.emb_split))) for _ in sb]
+            if self.ecapa:      # one handle over the K speaker rows of every stream (dz_ecapa_forward_groups)
+                he = [self.emb._create(S, self.n * self.seg.num_speakers)]
+            else:
+                he = [self.emb._create(S, max(1, -(-self.n // self.emb_split))) for _ in sb]
             got = self._sub[(S, lane)] = (hs, he, sa, sb)
         return got
 
@@ -514,7 +538,7 @@ class StreamBatch:
                 marks.append(("seg_forward_osp", _time.perf_counter()))
         for (i0, i1), h, b, ev in zip(sb, hembs, lane["b"], slot["ev_frames"]):
             b.wait_event(slot["ev_conv0"] if pair else slot["ev_in"])
-            if i1 > i0 and self._ablate != "noemb":
+            if i1 > i0 and self._ablate != "noemb" and not self.ecapa:   # (ECAPA: all of it after the segmentation)
                 if stats is not None:
                     _lib.check(lib.dz_emb_use_wave_stats(h, stats[i0:].data_ptr()), "dz_emb_use_wave_stats")
                 _lib.check(lib.dz_emb_frames(h, base + i0 * stride * esz, stride, i1 - i0, b.cuda_stream),
@@ -525,11 +549,15 @@ class StreamBatch:
         slot["rows"], slot["slots"] = N, None
         slot["keep"] = keep                              # keep the view alive until the GPU is done
         slot["pool"] = (lane, hembs, sa, sb, N, K, F)     # what _enqueue_pool needs
-        if ring is not None:                             # pushes `slack` steps from now wait for these
-            ring._read_by(list(lane["a"]) + list(lane["b"]) + list(front or []))
+        slot["wave"] = (base, stride)                    # (ECAPA reads the windows behind the segmentation)
+        readers = list(lane["a"]) + list(lane["b"]) + list(front or [])
+        if ring is not None and not self.ecapa:          # pushes `slack` steps from now wait for these
+            ring._read_by(readers)
         self._pending.append(slot)
         while len(self._pending) > self.lag:
             self._enqueue_pool(self._pending.pop(0))
+        if ring is not None and self.ecapa:              # (lag 0: its forward is enqueued by now)
+            ring._read_by(readers)
         if marks is not None:
             marks.append(("pool", _time.perf_counter()))
             if marks[-1][1] - marks[0][1] > 2e-3:           # a launch that took more than 2 ms: where
@@ -603,6 +631,12 @@ class StreamBatch:
             for (j0, j1), ev in zip(sa, slot["ev_seg"]):
                 if j0 < i1 and i0 < j1:
                     b.wait_event(ev)
+            if self.ecapa:      # the whole network, each stream's K rows with their own geometry, normalised
+                base, stride = slot["wave"]
+                _lib.check(lib.dz_ecapa_forward_groups(h, base + i0 * stride * 4, stride, slot["w"][i0:i1].data_ptr(),
+                                                       i1 - i0, K, F, 1, slot["emb"][i0:i1].data_ptr(), b.cuda_stream),
+                           "dz_ecapa_forward_groups")
+                continue
             if self._ablate == "noemb":
                 if not slot.get("_filled"):       # something the clustering accepts
                     with torch.cuda.stream(b):

@@ -10,7 +10,8 @@ that are ready *across streams* as one GPU batch: every ``step()`` takes at most
 window from each open stream, stacks them, runs segmentation / embedding once and steps each
 stream's own clustering and aggregation state.  Streams join and leave at any time and advance at
 their own pace; per stream the output is what a dedicated ``SpeakerDiarization`` pipeline with the
-same configuration produces.
+same configuration produces.  The model pair may be config 2's (x-vector) or config 3's (powerset segmentation +
+``HipEcapaEmbedding``, with ``normalize_embedding_weights=True``): see ``StreamBatch``.
 
 Audio reaches the GPU through per-stream device rings (``AudioRing.push_rows`` / ``gather``): a step
 uploads only the NEW 500 ms block of each stream that has one (32 KB instead of the 320 KB window the
@@ -53,7 +54,8 @@ class StreamServer:
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  device: Optional[torch.device] = None, patch_collar: float = 0.05,
-                 engine: Optional[Callable] = None, device_rings: bool = True):
+                 engine: Optional[Callable] = None, device_rings: bool = True,
+                 normalize_embedding_weights: bool = False):
         self.duration, self.step_seconds, self.sample_rate = float(duration), float(step), int(sample_rate)
         self.latency = self.step_seconds if latency is None else float(latency)
         self.chunk_samples = int(round(sample_rate * duration))
@@ -73,7 +75,8 @@ class StreamServer:
         # the default engine is a StreamBatch with the C++ output tail
         if engine is None:
             self.batch = StreamBatch(segmentation, embedding, self.max_streams, tau_active, rho_update,
-                                     delta_new, gamma, beta, max_speakers, device=device, tail=True,
+                                     delta_new, gamma, beta, max_speakers,
+                                     normalize_embedding_weights=normalize_embedding_weights, device=device, tail=True,
                                      duration=duration, step=step, latency=self.latency)
             self._dev = torch.empty((self.max_streams, self.chunk_samples), dtype=torch.float32,
                                     device=self.batch.device)

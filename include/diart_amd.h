@@ -250,6 +250,16 @@ int dz_ecapa_create(dz_ctx* ctx, const dz_ecapa_weights* w, int max_rows, int nu
                     dz_ecapa** out);
 int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
                      int n_rows, int mask_frames, float* d_out, void* stream);
+/* The same network over n_groups independent groups of rows_per_group (K) rows, each group with its own batch
+ * geometry: row r = g*K + k reads waveform row g (d_wave + g*wave_stride) and mask row r of d_masks (G,K,Fw)
+ * contiguous (the speaker-major layout of dz_seg_forward_osp's weights) -> d_out (G*K, 192); normalize = 1
+ * L2-normalises every row (NaN rows stay NaN).  A group's rows are what dz_ecapa_forward returns for those K
+ * rows alone (a group whose rows are all too short gives NaN rows; no other group is affected).  The
+ * geometry is derived on the device: the call does not synchronise, read device memory from the host or
+ * allocate.  G*K <= max_rows.                                                                   */
+int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
+                            int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                            void* stream);
 /* device pointer + element count of an intermediate of the LAST forward (parity tests):
  * 0 features (N,T,80)  1 block0 (N,T,1024)  2 ASP logits (N,T,3072; the concatenation's buffer,
  * which holds the attention logits once a forward has returned)  3 mfa (N,T,3072)
@@ -257,7 +267,12 @@ int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave_stride, co
  * samples hold a NaN / Inf (its embedding is NaN)  6 nvalid (N) as int32: frames of the sentence
  * mean, round(float32(len / lmax) * T)  7 nmask (N) as int32: frames of the squeeze-excitation
  * mean and the attentive pooling, #{t : t < float32(len / lmax) * T} (6 and 7 are 0 when every
- * row is too short);  *frames receives T                                                  */
+ * row is too short);  *frames receives T.
+ * After dz_ecapa_forward_groups: N = G*K, T = the handle's Tc = 1 + num_samples / 160 and buffers 0 - 3 are
+ * Tc-strided (frames at or past a row's own count are padding); 6 / 7 are each group's values as
+ * dz_ecapa_forward computes them for that group alone (0 for a group whose rows are all too short), and
+ * 8 is the per-row frame count of its group, 1 + lmax_g / 160, as int32 (N) (0 for such a group).
+ * Buffer 8 exists after a groups forward only.                                             */
 int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long long* count, int* frames);
 int dz_ecapa_destroy(dz_ecapa* e);
 
@@ -337,6 +352,10 @@ typedef struct {
     int* oflag;           /* device-visible int set to 1 when an operand of the split-f16 path lies
                              outside +-65504 (it is then clamped); NULL = the context's flag, read
                              with dz_range_check                                                 */
+    const int* Tdev;      /* optional device [B] frame count of each batch item (padded RELU_BN layers only):
+                             reflect padding of the output frames t < Tdev[b] happens at Tdev[b] instead of
+                             Tin (rows of different lengths laid out Tin frames apart; pad < Tdev[b]).  NULL:
+                             every item reflects at Tin                                           */
 } dz_convgemm_desc;
 int dz_k_convgemm(dz_ctx* ctx, const dz_convgemm_desc* desc, void* stream);
 /* the exact-f32 kernel of the wide layers alone (k_gemm_f32.hip; dz_k_convgemm routes to it by itself when the
