@@ -57,6 +57,14 @@ class EcapaWeights(C.Structure):
                 ("dft_split", vp)]
 
 
+class WspConv(C.Structure):
+    _fields_ = [("w", vp), ("b", vp), ("wsplit", vp)]
+
+
+class WspWeights(C.Structure):
+    _fields_ = [("mel", vp), ("conv1", WspConv), ("block", (WspConv * 3) * 16), ("seg_w", vp), ("seg_b", vp)]
+
+
 # name -> (restype, argtypes); must list every function of include/diart_amd.h
 SIGNATURES = {
     "dz_last_error": (C.c_char_p, []),
@@ -94,6 +102,13 @@ SIGNATURES = {
     "dz_ecapa_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_ecapa_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_ecapa_destroy": (C.c_int, [vp]),
+    "dz_wsp_abi_size": (C.c_int, []),
+    "dz_wsp_frames_for": (C.c_int, [C.c_int, C.c_int]),
+    "dz_wsp_create": (C.c_int, [vp, C.POINTER(WspWeights), C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_wsp_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_wsp_forward_multi": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_wsp_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "dz_wsp_destroy": (C.c_int, [vp]),
     "dz_prof_enable": (C.c_int, [C.c_int]),
     "dz_prof_pause": (C.c_int, [C.c_int]),
     "dz_prof_collect": (C.c_int, []),
@@ -222,6 +237,9 @@ def load() -> C.CDLL:
         if list(sizes) != mine:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
+        if lib.dz_wsp_abi_size() != C.sizeof(WspWeights):
+            raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof(dz_wsp_weights) "
+                                f"{lib.dz_wsp_abi_size()} (library) vs {C.sizeof(WspWeights)} (this binding); rebuild it")
         _lib = lib
     return _lib
 

@@ -511,6 +511,37 @@ int dz_launch_asp_pool(const float* x, const float* logit, int T, int C, int row
                        float* pooled, hipStream_t st);
 int dz_launch_nan_rows(float* out, int rows, int dim, const int* flags, hipStream_t st);
 
+// k_conv2d.hip ---------------------------------------------------------------
+// implicit-GEMM 2-D convolution over channels-last activations X [B][Fi][Ti][Cin] -> Y [B][Fo][To][Cout]:
+// taps 9 = 3x3 with zero padding 1, taps 1 = 1x1 without padding; stride 1 or 2.  W [Cout][taps Cin] with
+// k = (kh 3 + kw) Cin + c (exact-f32 MFMA), or Wsplit = its (hi, lo * 2^11) f16 planes [2][Cout][taps Cin]
+// (split-f16 MFMA, used whenever it is set).  Epilogue: + bias[n], + R[m][n] when R is set, ReLU when relu.
+struct DzConv2d {
+    const float* X;
+    const float* W;
+    const void* Wsplit;
+    const float* bias;
+    const float* R;
+    float* Y;
+    int B, Fi, Ti, Cin, Fo, To, Cout, taps, stride, relu;
+    int* oflag;
+};
+int dz_launch_conv2d(const DzConv2d& p, hipStream_t st);
+
+// k_wespeaker.hip -----------------------------------------------------------
+// kaldi fbank of N rows (T frames of 400 samples, hop 160) -> raw log-mel [N][80][T]; bad[row] = 1 when a sample a
+// frame reads is NaN / Inf (bad must be zeroed first)
+int dz_launch_wsp_fbank(const float* wave, long long stride, int N, int T, const float* mel, float* raw, int* bad,
+                        hipStream_t st);
+// per (row, bin) mean over the T frames subtracted; rows flagged bad are written as zeros
+int dz_launch_wsp_cmn(const float* raw, int N, int T, const int* bad, float* feats, hipStream_t st);
+// conv1 (3x3, 1 -> 32, pad 1) + folded BN + ReLU: feats [N][80][T] -> y [N][80][T][32], exact f32 FMAs
+int dz_launch_wsp_conv1(const float* feats, int N, int T, const float* w, const float* b, float* y, hipStream_t st);
+// TSTP statistics of x [B][10][T4][256] (pooled dim c 10 + f): K pool rows per trunk row, weights [B K][|Fw|]
+// (nearest-resampled to T4) or NULL -> out [B K][5120] = mean | std; rflag[B K] = bad[row / K]
+int dz_launch_wsp_pool(const float* x, int B, int T4, const float* weights, int Fw, int K, const int* bad,
+                       float* out, int* rflag, hipStream_t st);
+
 struct dz_ctx {
     int device;
     // "an operand left the f16 range" flag of the split-f16 kernels: one int in pinned, device-mapped

@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .weights import PackedEcapa, PackedEmbedding, PackedSegmentation
+from .weights import PackedEcapa, PackedEmbedding, PackedSegmentation, PackedWeSpeaker
 
 StateSource = Union[str, Path, Dict[str, torch.Tensor]]
 
@@ -378,6 +378,89 @@ class HipEcapaEmbedding(_HipModule):
         return out, frames.value
 
 
+class HipWeSpeakerEmbedding(_HipModule):
+    """pyannote.audio 3.1's ``WeSpeakerResNet34`` (pyannote/wespeaker-voxceleb-resnet34-LM): ``(waveform (N,1,S),
+    weights (N,Fw) | None) -> (N,256)`` — the callable the reference loads through ``PyannoteLoader`` (models.py:42-59)
+    and calls at blocks/embedding.py:56-65.  kaldi fbank, ResNet34 trunk on implicit-GEMM 2-D convolutions
+    (k_conv2d.hip), TSTP pooling with the 3.1 weighted statistics (nearest-resampled weights), ``seg_1``.  A row
+    with a NaN / Inf sample comes back NaN."""
+
+    dimension = 256
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None):
+        super().__init__(state, max_batch)
+        self.precision = default_precision(precision)
+
+    def _extra_state(self):
+        return {"precision": self.precision}
+
+    def _pack(self, device):
+        return PackedWeSpeaker(self._state, device, precision=self.precision)
+
+    def _create(self, num_samples, cap):
+        h = _lib.vp()
+        _lib.check(_lib.load().dz_wsp_create(_lib.context(self.device.index), C.byref(self._packed.struct), cap,
+                                             num_samples, C.byref(h)), "dz_wsp_create")
+        return h
+
+    def _destroy(self, h):
+        _lib.load().dz_wsp_destroy(h)
+
+    def num_frames(self, num_samples: int, stage: int = 0) -> int:
+        """Frames of the fbank (stage 0) or after layer 1 .. 4 (``dz_wsp_frames_for``)."""
+        return int(_lib.load().dz_wsp_frames_for(int(num_samples), int(stage)))
+
+    def __call__(self, waveform: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.device is None:
+            self.to(waveform.device)
+        rows = _as_rows(waveform.to(self.device))
+        N, S = rows.shape
+        wptr, fw = None, 0
+        if weights is not None:
+            weights = weights.to(self.device, torch.float32).contiguous()
+            if weights.ndim != 2 or weights.shape[0] != N:
+                raise ValueError(f"weights must be (batch, frames), got {tuple(weights.shape)}")
+            wptr, fw = weights.data_ptr(), weights.shape[1]
+        handle = self._need(S, N)
+        out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().dz_wsp_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S, wptr, N, fw,
+                                              out.data_ptr(), _stream_ptr(self.device)), "dz_wsp_forward")
+        return out
+
+    def forward_multi(self, waveform: torch.Tensor, weights: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """``waveform (B,1,S)``, ``weights (B,K,F)`` speaker-major -> ``(B,K,256)``: the reference's ``(B*K)``-row call
+        with the trunk (everything before the pooling) computed once per window.  No synchronisation."""
+        if self.device is None:
+            self.to(waveform.device)
+        rows = _as_rows(waveform.to(self.device))
+        B, S = rows.shape
+        weights = weights.to(self.device, torch.float32).contiguous()
+        if weights.ndim != 3 or weights.shape[0] != B:
+            raise ValueError(f"weights must be (batch, speakers, frames), got {tuple(weights.shape)}")
+        K, fw = weights.shape[1], weights.shape[2]
+        handle = self._need(S, B)
+        out = torch.empty((B, K, self.dimension), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().dz_wsp_forward_multi(handle, rows.data_ptr(), rows.stride(0) if B > 1 else S,
+                                                    weights.data_ptr(), B, K, fw, 1 if normalize else 0,
+                                                    out.data_ptr(), _stream_ptr(self.device)), "dz_wsp_forward_multi")
+        return out
+
+    def peek(self, num_samples: int, which: int):
+        """Intermediate of the last forward (parity tests; synchronises): ``(flat tensor, frames)``, see
+        ``dz_wsp_peek``."""
+        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
+        _lib.check(_lib.load().dz_wsp_peek(self._handles[num_samples][0], which, C.byref(ptr), C.byref(cnt),
+                                           C.byref(frames)), "dz_wsp_peek")
+        out = torch.empty(cnt.value, dtype=torch.float32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        import ctypes
+        hip = ctypes.CDLL("libamdhip64.so")
+        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(cnt.value * 4), 3)
+        if rc != 0:
+            raise _lib.DiartAmdError(f"hipMemcpy failed ({rc})")
+        return out, frames.value
+
+
 # --------------------------------------------------------------------------- #
 # loaders (picklable, no HIP state)
 # --------------------------------------------------------------------------- #
@@ -391,8 +474,9 @@ class SegmentationLoader:
 
 
 class EmbeddingLoader:
-    """``arch``: "xvector" (pyannote/embedding) or "ecapa" (speechbrain/spkrec-ecapa-voxceleb);
-    None = decide from the checkpoint keys."""
+    """``arch``: "xvector" (pyannote/embedding), "ecapa" (speechbrain/spkrec-ecapa-voxceleb) or "wespeaker"
+    (pyannote/wespeaker-voxceleb-resnet34-LM); None = decide from the checkpoint keys (``resnet.``: wespeaker,
+    ``asp.``: ecapa, otherwise xvector)."""
 
     def __init__(self, state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
                  precision: Optional[str] = None, weight_interp: Optional[str] = None):
@@ -404,6 +488,10 @@ class EmbeddingLoader:
     def __call__(self):
         sd = _read_state(self.state)
         arch = self.arch or ("ecapa" if any(k.startswith("asp.") for k in sd) else "xvector")
+        if self.arch is None and any(k.startswith("resnet.") for k in sd):
+            arch = "wespeaker"
+        if arch == "wespeaker":
+            return HipWeSpeakerEmbedding(sd, self.max_batch, self.precision)
         if arch == "ecapa":
             return HipEcapaEmbedding(sd, self.max_batch, self.precision)
         interp = self.weight_interp

@@ -41,7 +41,7 @@ from . import _lib
 from .blocks.aggregation import BatchedOutputTail
 from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
-from .models import HipEcapaEmbedding, HipEmbedding, HipSegmentation, _as_rows
+from .models import HipEcapaEmbedding, HipEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _as_rows
 
 # lanes of a throughput engine (>= 64 streams per step on the matrix-core recurrence): profiles/r06*_lanes_grid.json
 THROUGHPUT_LANES = 6
@@ -193,6 +193,10 @@ class StreamBatch:
         embeddings are L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.  In that form
         ``lanes`` defaults to 2 — one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s) carves
         about 6.2 GB of device memory per lane — and ``emb_split`` must be 1."""
+        if isinstance(embedding, HipWeSpeakerEmbedding):
+            raise ValueError("StreamBatch: the WeSpeaker ResNet34 embedding does not run on the N-stream engine; it runs "
+                             "HipEmbedding (pyannote/embedding) and HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb). "
+                             "Use the blocks API (SpeakerDiarization) for pyannote/wespeaker-voxceleb-resnet34-LM")
         from .config import setting
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)

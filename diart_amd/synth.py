@@ -245,3 +245,41 @@ def synth_ecapa_state(seed: int = 777, channels: int = 1024, lin_neurons: int = 
     bn("asp_bn", 6 * c)
     conv("fc", 6 * c, lin_neurons, 1)
     return sd
+
+
+def synth_wespeaker_state(seed: int = 4242, embed_dim: int = 256) -> Dict[str, torch.Tensor]:
+    """Random-init weights of pyannote.audio 3.1's ``WeSpeakerResNet34`` (feat_dim 80, embed_dim 256, TSTP pooling),
+    keyed like ``pyannote/wespeaker-voxceleb-resnet34-LM`` (``resnet.conv1.weight``, ``resnet.layer2.0.shortcut.1.
+    running_var``, ``resnet.seg_1.weight`` ...).  BatchNorm statistics are not the identity, so folding them is
+    exercised; the second convolution of every block is scaled down so the residual stream stays O(1)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(key, cin, cout, k, gain=1.0):
+        sd[key] = _u(g, (cout, cin, k, k), gain * math.sqrt(6.0 / (cin * k * k)))
+
+    def bn(prefix, n):
+        sd[prefix + ".weight"] = 1.0 + 0.2 * _u(g, (n,), 1.0)
+        sd[prefix + ".bias"] = 0.1 * _u(g, (n,), 1.0)
+        sd[prefix + ".running_mean"] = 0.2 * _u(g, (n,), 1.0)
+        sd[prefix + ".running_var"] = 0.5 + torch.rand((n,), generator=g)
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(1000)
+
+    conv("resnet.conv1.weight", 1, 32, 3, gain=0.5)
+    bn("resnet.bn1", 32)
+    cin = 32
+    for li, nb in enumerate((3, 4, 6, 3)):
+        c = 32 << li
+        for j in range(nb):
+            p = f"resnet.layer{li + 1}.{j}"
+            conv(p + ".conv1.weight", cin, c, 3, gain=0.8)
+            bn(p + ".bn1", c)
+            conv(p + ".conv2.weight", c, c, 3, gain=0.3)
+            bn(p + ".bn2", c)
+            if j == 0 and li > 0:
+                conv(p + ".shortcut.0.weight", cin, c, 1, gain=0.8)
+                bn(p + ".shortcut.1", c)
+            cin = c
+    sd["resnet.seg_1.weight"] = _u(g, (embed_dim, 5120), math.sqrt(6.0 / 5120))
+    sd["resnet.seg_1.bias"] = _u(g, (embed_dim,), 0.1)
+    return sd

@@ -534,3 +534,79 @@ def ecapa_mel_filterbank(n_mels: int = 80, n_fft: int = 400, sample_rate: int = 
     all_freqs = torch.linspace(0, sample_rate // 2, n_fft // 2 + 1)
     slope = (all_freqs.repeat(n_mels, 1) - f_central[:, None]) / band[:, None]
     return torch.max(torch.zeros(1), torch.min(slope + 1.0, -slope + 1.0)).t().contiguous()
+
+
+def kaldi_mel_banks(num_bins: int = 80, n_fft: int = 512, sample_rate: int = 16000, low_freq: float = 20.0) -> torch.Tensor:
+    """kaldi's triangular mel bank (torchaudio.compliance.kaldi.get_mel_banks with high_freq = Nyquist, no VTLN),
+    mel = 1127 ln(1 + f / 700), as the (num_bins, n_fft / 2 + 1) matrix kaldi.fbank multiplies the power spectrum
+    with: the n_fft / 2 FFT bins below Nyquist, then a zero column for the Nyquist bin.  Computed in float64."""
+    mel = lambda f: 1127.0 * torch.log1p(torch.as_tensor(f, dtype=torch.float64) / 700.0)
+    nyq = sample_rate / 2.0
+    lo, hi = mel(low_freq), mel(nyq)
+    delta = (hi - lo) / (num_bins + 1)
+    b = torch.arange(num_bins, dtype=torch.float64)[:, None]
+    left, center, right = lo + b * delta, lo + (b + 1) * delta, lo + (b + 2) * delta
+    m = mel(sample_rate / n_fft * torch.arange(n_fft // 2, dtype=torch.float64))[None, :]
+    up, down = (m - left) / (center - left), (right - m) / (right - center)
+    banks = torch.clamp(torch.minimum(up, down), min=0.0)
+    return torch.cat([banks, torch.zeros(num_bins, 1, dtype=torch.float64)], dim=1)
+
+
+# BasicBlocks per layer of ResNet34 and their channel counts
+WESPEAKER_BLOCKS = (3, 4, 6, 3)
+
+
+def fold_conv_bn(w: torch.Tensor, bn: Dict[str, torch.Tensor], eps: float = BN_EPS):
+    """Conv2d weight (Cout, Cin, kh, kw) without bias + BatchNorm2d (eval) -> (weight, bias) of the folded
+    convolution, in the dtype of ``w``."""
+    scale = bn["weight"] / torch.sqrt(bn["running_var"] + eps)
+    return w * scale[:, None, None, None], bn["bias"] - bn["running_mean"] * scale
+
+
+def wsp_conv_matrix(w: torch.Tensor) -> torch.Tensor:
+    """Conv2d weight (Cout, Cin, kh, kw) -> (Cout, kh kw Cin) with k = (kh 3 + kw) Cin + c: the tap-major K axis of
+    the implicit GEMM over channels-last activations (k_conv2d.hip)."""
+    co = w.shape[0]
+    return w.permute(0, 2, 3, 1).reshape(co, -1).contiguous()
+
+
+class PackedWeSpeaker:
+    """``dz_wsp_weights`` + the tensors behind it (pyannote.audio 3.1 ``WeSpeakerResNet34`` checkpoint keys:
+    ``resnet.conv1.weight``, ``resnet.bn1.*``, ``resnet.layer{1..4}.{i}.{conv1,bn1,conv2,bn2}.*``,
+    ``resnet.layer{2,3,4}.0.shortcut.{0,1}.*``, ``resnet.seg_1.*``).
+
+    * every BatchNorm2d (eval, eps 1e-5) is folded into the convolution before it: weight x scale, bias = shift;
+    * weights as ``[Cout][(kh 3 + kw) Cin + c]`` f32 and, for "f16x3", also as split-f16 planes (the 3x3 / 1x1
+      convolutions of the four layers; conv1 has Cin = 1 and runs on a direct f32 kernel);
+    * the kaldi mel bank (80, 257)."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], device: torch.device, precision: str = "f32"):
+        assert precision in PRECISIONS, precision
+        split = precision == "f16x3"
+        pk = _Packed(device)
+        g = lambda k: sd[k].detach().cpu().float()
+        bnd = lambda p: {n: g(f"{p}.{n}") for n in ("weight", "bias", "running_mean", "running_var")}
+        w = _lib.WspWeights()
+
+        def conv(dst, wkey, bnprefix, name, planes=True):
+            fw, fb = fold_conv_bn(g(wkey), bnd(bnprefix))
+            m = wsp_conv_matrix(fw)
+            dst.w, dst.b = pk.put(m), pk.put(fb)
+            if split and planes:
+                dst.wsplit = pk.put_split(m, name)
+
+        w.mel = pk.put(kaldi_mel_banks().float())
+        conv(w.conv1, "resnet.conv1.weight", "resnet.bn1", "conv1", planes=False)
+        bi = 0
+        for li, nb in enumerate(WESPEAKER_BLOCKS):
+            for j in range(nb):
+                p = f"resnet.layer{li + 1}.{j}"
+                blk = w.block[bi]
+                conv(blk[0], p + ".conv1.weight", p + ".bn1", p + ".conv1")
+                conv(blk[1], p + ".conv2.weight", p + ".bn2", p + ".conv2")
+                if p + ".shortcut.0.weight" in sd:
+                    conv(blk[2], p + ".shortcut.0.weight", p + ".shortcut.1", p + ".shortcut")
+                bi += 1
+        w.seg_w = pk.put(g("resnet.seg_1.weight"))
+        w.seg_b = pk.put(g("resnet.seg_1.bias"))
+        self.struct, self.pack = w, pk

@@ -276,6 +276,49 @@ int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_str
 int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long long* count, int* frames);
 int dz_ecapa_destroy(dz_ecapa* e);
 
+/* ---- WeSpeaker ResNet34 embedding (pyannote/wespeaker-voxceleb-resnet34-LM, pyannote.audio 3.1's
+ * WeSpeakerResNet34): the callable behind EmbeddingModel.__call__ for that checkpoint, reached in the reference
+ * through PyannoteLoader (diart src/diart/models.py:42-59) and called as
+ * model(waveform (N,1,S), weights (N,Fw)) (blocks/embedding.py:56-65).
+ * kaldi fbank (80 mel bins, 25 / 10 ms, waveform x 2^15, mean over frames subtracted per row) -> ResNet34 trunk
+ * (3x3 convolutions with folded BatchNorm, BasicBlocks [3, 4, 6, 3] at 32 / 64 / 128 / 256 channels, strides
+ * 1 / 2 / 2 / 2) -> TSTP statistics pooling of the (256 x 10) x T4 features -> Linear(5120, 256).  Activations are
+ * channels-last [row][f][t][c].  A row with a NaN / Inf sample in any of its frames comes back as a NaN row.  */
+typedef struct {
+    const float* w;      /* [Cout][taps * Cin], k = (kh * 3 + kw) * Cin + c (taps 9) or c (taps 1), BatchNorm folded */
+    const float* b;      /* [Cout] folded BatchNorm bias                                                  */
+    const void* wsplit;  /* split-f16 planes [2][Cout][taps * Cin] of w: the layer then runs on the f16 matrix cores
+                            (three products per pair); NULL: exact-f32 matrix cores                         */
+} dz_wsp_conv;
+typedef struct {
+    const float* mel;           /* [80][257] kaldi mel bank (the Nyquist column is zero)                      */
+    dz_wsp_conv conv1;          /* [32][9]: 3x3, 1 -> 32 (w / b only; direct f32 kernel)                      */
+    dz_wsp_conv block[16][3];   /* BasicBlocks of layers 1 - 4 in order: conv1 (3x3), conv2 (3x3), shortcut
+                                   (1x1, stride 2; w NULL where the shortcut is the identity)                */
+    const float* seg_w;         /* [256][5120] seg_1, input index c * 10 + f (mean) | 2560 + c * 10 + f (std) */
+    const float* seg_b;         /* [256]                                                                     */
+} dz_wsp_weights;
+typedef struct dz_wsp dz_wsp;
+/* sizeof(dz_wsp_weights): a binding checks its mirror against the library it loaded */
+int dz_wsp_abi_size(void);
+/* frames of stage `stage` for num_samples samples: 0 = fbank, 1 + (S - 400) / 160 (0 when S < 400); 1 .. 4 = the
+ * time axis after layer 1 .. 4 ((T - 1) / stride + 1 per strided layer); -1 on a bad stage                   */
+int dz_wsp_frames_for(int num_samples, int stage);
+int dz_wsp_create(dz_ctx* ctx, const dz_wsp_weights* w, int max_rows, int num_samples, dz_wsp** out);
+/* n_rows rows (d_wave + r * wave_stride) -> d_out (n_rows, 256); d_weights (n_rows, weight_frames) or NULL   */
+int dz_wsp_forward(dz_wsp* m, const float* d_wave, long long wave_stride, const float* d_weights, int n_rows,
+                   int weight_frames, float* d_out, void* stream);
+/* batch windows, num_speakers (K <= 8) weight rows each ((batch, K, weight_frames) speaker-major, contiguous) ->
+ * d_out (batch * K, 256): the trunk runs once per window and is pooled K times; normalize = 1 L2-normalises every
+ * row (NaN rows stay NaN).  Row b * K + k equals dz_wsp_forward of window b with weight row (b, k).           */
+int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wave_stride, const float* d_weights, int batch,
+                         int num_speakers, int weight_frames, int normalize, float* d_out, void* stream);
+/* device pointer + element count of an intermediate of the LAST forward (parity tests); *frames receives the
+ * buffer's time axis:  0 fbank (N,80,T) after the mean subtraction  1 conv1 (N,80,T,32)  2 .. 5 layer 1 .. 4
+ * (N,F,T_l,C_l)  6 pooled statistics (rows, 5120)                                                          */
+int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames);
+int dz_wsp_destroy(dz_wsp* m);
+
 /* ---- OverlappedSpeechPenalty: functional.py:6-13 + blocks/embedding.py:98-107
  * d_seg (B,F,K) -> weights.  speaker_major=0: (B,F,K) like the reference block;
  * speaker_major=1: (B,K,F), the layout dz_emb_forward_multi consumes.           */
