@@ -65,6 +65,11 @@ class WspWeights(C.Structure):
     _fields_ = [("mel", vp), ("conv1", WspConv), ("block", (WspConv * 3) * 16), ("seg_w", vp), ("seg_b", vp)]
 
 
+class SbxWeights(C.Structure):
+    _fields_ = [("dft", vp), ("dft_split", vp), ("mel", vp), ("tdnn", Layer * 5), ("lin_w", vp), ("lin_b", vp),
+                ("zeros", vp)]
+
+
 # name -> (restype, argtypes); must list every function of include/diart_amd.h
 SIGNATURES = {
     "dz_last_error": (C.c_char_p, []),
@@ -102,6 +107,12 @@ SIGNATURES = {
     "dz_ecapa_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_ecapa_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_ecapa_destroy": (C.c_int, [vp]),
+    "dz_sbx_abi_size": (C.c_int, []),
+    "dz_sbx_create": (C.c_int, [vp, C.POINTER(SbxWeights), C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_sbx_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_sbx_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_sbx_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "dz_sbx_destroy": (C.c_int, [vp]),
     "dz_wsp_abi_size": (C.c_int, []),
     "dz_wsp_frames_for": (C.c_int, [C.c_int, C.c_int]),
     "dz_wsp_create": (C.c_int, [vp, C.POINTER(WspWeights), C.c_int, C.c_int, C.POINTER(vp)]),
@@ -240,6 +251,9 @@ def load() -> C.CDLL:
         if lib.dz_wsp_abi_size() != C.sizeof(WspWeights):
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof(dz_wsp_weights) "
                                 f"{lib.dz_wsp_abi_size()} (library) vs {C.sizeof(WspWeights)} (this binding); rebuild it")
+        if lib.dz_sbx_abi_size() != C.sizeof(SbxWeights):
+            raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof(dz_sbx_weights) "
+                                f"{lib.dz_sbx_abi_size()} (library) vs {C.sizeof(SbxWeights)} (this binding); rebuild it")
         _lib = lib
     return _lib
 

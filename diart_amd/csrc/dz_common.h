@@ -510,6 +510,11 @@ int dz_launch_asp_gstats(const float* x, int T, int C, int rows, const int* nmas
 int dz_launch_asp_pool(const float* x, const float* logit, int T, int C, int rows, const int* nmask,
                        float* pooled, hipStream_t st);
 int dz_launch_nan_rows(float* out, int rows, int dim, const int* flags, hipStream_t st);
+// speechbrain x-vector (sbx_api.hip): fbank_post for n_mels (24) bins; StatisticsPooling over nvalid[row] frames
+int dz_launch_fbank_post_mels(const float* melp, int n_mels, int T, int rows, const int* nvalid, float* feats,
+                              hipStream_t st, const int* tdev = nullptr);
+int dz_launch_sb_stats_pool(const float* x, int T, int C, int ldx, int rows, const int* nvalid, float mean_bias,
+                            float std_bias, float* pooled, hipStream_t st);
 
 // k_conv2d.hip ---------------------------------------------------------------
 // implicit-GEMM 2-D convolution over channels-last activations X [B][Fi][Ti][Cin] -> Y [B][Fo][To][Cout]:

@@ -285,8 +285,8 @@ int dz_launch_convgemm(const DzConvGemm& p, hipStream_t st) {
     DZ_REQUIRE(p.ksplit <= 1 || (p.epi == DZ_EPI_BIAS && p.ksplit <= p.Kpad / KT),
                "convgemm: split-K needs the plain bias epilogue and ksplit <= k-tiles");
     // (the caller guarantees pad < Tdev[b] for every batch item; Tdev is read on the device only)
-    DZ_REQUIRE(p.Tdev == nullptr || (p.pad > 0 && p.epi == DZ_EPI_RELU_BN && p.norm_on_load == 0),
-               "convgemm: per-item frame counts (Tdev) are built for the padded RELU_BN layers");
+    DZ_REQUIRE(p.Tdev == nullptr || (p.pad > 0 && (p.epi == DZ_EPI_RELU_BN || p.epi == DZ_EPI_TDNN) && p.norm_on_load == 0),
+               "convgemm: per-item frame counts (Tdev) are built for the padded RELU_BN and TDNN layers");
     const bool wide = (p.Npad % 128 == 0);
     DZ_REQUIRE(p.Npad % 64 == 0, "convgemm: Npad must be a multiple of 64");
     const bool pro = p.norm_on_load != 0;
@@ -298,6 +298,7 @@ int dz_launch_convgemm(const DzConvGemm& p, hipStream_t st) {
         case DZ_EPI_TDNN:
             DZ_REQUIRE(wide, "convgemm: TDNN needs Npad %% 128 == 0");
             if (pro) DZ_CG(128, true, DZ_EPI_TDNN);
+            if (p.Tdev) DZ_CG(128, false, DZ_EPI_TDNN | DZ_EPI_TG);     // (speechbrain x-vector, groups forward)
             DZ_CG(128, false, DZ_EPI_TDNN);
         case DZ_EPI_BIAS:
             if (wide) {

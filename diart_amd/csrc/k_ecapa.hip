@@ -7,6 +7,7 @@
 //   se_mean / se_apply     squeeze-excitation: masked time mean, gate * x + residual
 //   asp_gstats / asp_pool  attentive statistics pooling: global context stats, masked softmax stats
 //   nan_rows       rows with fewer than min_num_samples kept samples -> NaN
+//   fbank_post_mels / sb_stats_pool   the speechbrain x-vector's 24-bin fbank tail and its statistics pooling
 // Third-party graph (speechbrain ECAPA_TDNN via pyannote's PretrainedSpeakerEmbedding) reached
 // from /root/reference/src/diart/models.py:59 and :262; SURVEY.md Appendix A.3.
 #include "dz_common.h"
@@ -383,6 +384,81 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const float* __restrict__
     }
 }
 
+// fbank_post_kernel for NM mel bins (speechbrain x-vector: 24): the same arithmetic over melp [row][T][NM]; the
+// per-mel sums over the nvalid frames are split over P = 240 / NM thread groups (frames part, part + P, ...) and
+// combined in the fixed order 0, 1, ..., P - 1.
+template <int NM>
+__global__ __launch_bounds__(256) void fbank_post_mels_kernel(const float* __restrict__ melp, int T,
+                                                              const int* __restrict__ nvalid,
+                                                              const int* __restrict__ tdev,
+                                                              float* __restrict__ feats) {
+    constexpr int P = 240 / NM;
+    __shared__ float red[4];
+    __shared__ float msum[P][NM];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* x = melp + (long long)row * T * NM;
+    float* y = feats + (long long)row * T * NM;
+    float mx = -INFINITY;
+    const int Tg = tdev ? tdev[row] : T;
+    for (int i = tid; i < Tg * NM; i += 256) mx = fmaxf(mx, 10.f * log10f(fmaxf(x[i], 1e-10f)));
+    const float floor_db = block_max(mx, red) - 80.f;
+    const int nv = nvalid[row];
+    if (tid < P * NM) {
+        const int m = tid % NM, part = tid / NM;
+        float s = 0.f;
+        for (int t = part; t < nv; t += P) s += fmaxf(10.f * log10f(fmaxf(x[t * NM + m], 1e-10f)), floor_db);
+        msum[part][m] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < T * NM; i += 256) {
+        const int m = i % NM;
+        float acc = 0.f;
+#pragma unroll
+        for (int q = 0; q < P; ++q) acc += msum[q][m];
+        y[i] = fmaxf(10.f * log10f(fmaxf(x[i], 1e-10f)), floor_db) - acc / (float)nv;
+    }
+}
+
+// speechbrain StatisticsPooling with relative lengths over x [row][T][ldx], C channels: n = nvalid[row] frames,
+//   pooled[row][c] = mean + mean_bias,  pooled[row][C + c] = sqrt(sum (x - mean)^2 / (n - 1)) + std_bias
+// (torch.std is unbiased: n = 1 gives 0 / 0 = NaN, as torch does).  Two passes over the frames (mean, then the
+// centred squares) in the layout of the reductions above: wave w of 4 takes frames [w n / 4, (w + 1) n / 4), the
+// partial sums are combined in the fixed order ((0 + 1) + 2) + 3 — nothing depends on the batch or the row's place.
+__global__ __launch_bounds__(256) void sb_stats_pool_kernel(const float* __restrict__ x, int T, int C, int ldx,
+                                                            const int* __restrict__ nvalid, float mean_bias,
+                                                            float std_bias, float* __restrict__ pooled) {
+    __shared__ f32x4 part[4][64];
+    const int row = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * 256 + lane * 4;
+    const bool ok = c < C;
+    const float* xr = x + (long long)row * T * ldx + c;
+    const int n = nvalid[row];
+    const int t0 = (int)((long long)w * n / 4), t1 = (int)((long long)(w + 1) * n / 4);
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    if (ok)
+        for (int t = t0; t < t1; ++t) a += *reinterpret_cast<const f32x4*>(xr + (long long)t * ldx);
+    part[w][lane] = a;
+    __syncthreads();
+    const f32x4 mean = dz_sum4(part, lane) / (float)n;
+    __syncthreads();
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (ok)
+        for (int t = t0; t < t1; ++t) {
+            const f32x4 d = *reinterpret_cast<const f32x4*>(xr + (long long)t * ldx) - mean;
+            v += d * d;
+        }
+    part[w][lane] = v;
+    __syncthreads();
+    if (w == 0 && ok) {
+        const f32x4 ss = dz_sum4(part, lane);
+        f32x4 sd;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sd[e] = sqrtf(ss[e] / (float)(n - 1)) + std_bias;
+        *reinterpret_cast<f32x4*>(pooled + (long long)row * 2 * C + c) = mean + mean_bias;
+        *reinterpret_cast<f32x4*>(pooled + (long long)row * 2 * C + C + c) = sd;
+    }
+}
+
 __global__ void nan_rows_kernel(float* __restrict__ out, int rows, int dim,
                                 const int* __restrict__ flags) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -418,6 +494,21 @@ int dz_launch_ecapa_geometry(const int* lens, int G, int K, int Tc, int min_samp
 int dz_launch_fbank_post(const float* melp, int T, int rows, const int* nvalid, float* feats,
                          hipStream_t st, const int* tdev) {
     DZ_LAUNCH(fbank_post_kernel, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}
+int dz_launch_fbank_post_mels(const float* melp, int n_mels, int T, int rows, const int* nvalid, float* feats,
+                              hipStream_t st, const int* tdev) {
+    DZ_REQUIRE(n_mels == 24, "fbank_post_mels: %d mel bins (built for 24; 80 is dz_launch_fbank_post)", n_mels);
+    DZ_LAUNCH(fbank_post_mels_kernel<24>, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}
+int dz_launch_sb_stats_pool(const float* x, int T, int C, int ldx, int rows, const int* nvalid, float mean_bias,
+                            float std_bias, float* pooled, hipStream_t st) {
+    DZ_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldx >= C, "sb_stats_pool: channels / ldx must be multiples of 4");
+    DZ_LAUNCH(sb_stats_pool_kernel, dim3((C + 255) / 256, rows), dim3(256), 0, st, x, T, C, ldx, nvalid, mean_bias,
+              std_bias, pooled);
     DZ_HIP(hipGetLastError());
     return 0;
 }

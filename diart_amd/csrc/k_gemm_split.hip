@@ -419,8 +419,8 @@ int dz_launch_gemm_split(const DzConvGemm& p_in, hipStream_t st) {
     DZ_REQUIRE(p.Ysplit == nullptr || (p.epi != DZ_EPI_POOL3 && p.ldy % 2 == 0 && p.yplane % 2 == 0 &&
                                        p.ybs % 2 == 0 && p.Npad <= p.ldy),
                "gemm_split: plane output needs even ldy / yplane / ybs, Npad <= ldy and no pooling");
-    DZ_REQUIRE(p.Tdev == nullptr || (p.pad > 0 && p.epi == DZ_EPI_RELU_BN && !p.norm_on_load),
-               "gemm_split: per-item frame counts (Tdev) are built for the padded RELU_BN layers");
+    DZ_REQUIRE(p.Tdev == nullptr || (p.pad > 0 && (p.epi == DZ_EPI_RELU_BN || p.epi == DZ_EPI_TDNN) && !p.norm_on_load),
+               "gemm_split: per-item frame counts (Tdev) are built for the padded RELU_BN and TDNN layers");
     const bool pro = p.norm_on_load != 0;
 #define DZ_SP(WM, NB, PRO, EPI) return launch<WM, NB, PRO, EPI>(p, st)
     if (p.epi == DZ_EPI_POOL3) {
@@ -443,6 +443,7 @@ int dz_launch_gemm_split(const DzConvGemm& p_in, hipStream_t st) {
         case DZ_EPI_TDNN:
             if (pro && small_wg) DZ_SP(2, 1, true, DZ_EPI_TDNN);
             if (pro) DZ_SP(4, 2, true, DZ_EPI_TDNN);
+            if (p.Tdev) DZ_SP(4, 2, false, DZ_EPI_TDNN | DZ_EPI_TG);   // (speechbrain x-vector, groups forward)
             DZ_SP(4, 2, false, DZ_EPI_TDNN);
         case DZ_EPI_BIAS:
             if (pro && small_wg) DZ_SP(2, 1, true, DZ_EPI_BIAS);

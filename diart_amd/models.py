@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .weights import PackedEcapa, PackedEmbedding, PackedSegmentation, PackedWeSpeaker
+from .weights import PackedEcapa, PackedEmbedding, PackedSbXvector, PackedSegmentation, PackedWeSpeaker
 
 StateSource = Union[str, Path, Dict[str, torch.Tensor]]
 
@@ -349,6 +349,15 @@ class HipEcapaEmbedding(_HipModule):
                    "dz_ecapa_forward_groups")
         return out
 
+    @staticmethod
+    def groups_launch(handle, wave_ptr: int, wave_stride: int, masks_ptr: int, G: int, K: int, mask_frames: int,
+                      normalize: bool, out_ptr: int, stream_ptr: int) -> None:
+        """``dz_ecapa_forward_groups`` on a handle of this model (``StreamBatch``'s lanes): raw device addresses,
+        masks (G,K,Fw) contiguous, out (G*K,192); no synchronisation."""
+        _lib.check(_lib.load().dz_ecapa_forward_groups(handle, wave_ptr, wave_stride, masks_ptr, G, K, mask_frames,
+                                                       1 if normalize else 0, out_ptr, stream_ptr),
+                   "dz_ecapa_forward_groups")
+
     def last_frames(self, num_samples: int) -> int:
         """Frames of the batch geometry of the last forward (= those of its longest kept row, what every row is
         padded to: ``dz_ecapa_peek``); no copy, no synchronisation.  ``bench.py --config 3`` prices its kernels with it."""
@@ -369,6 +378,96 @@ class HipEcapaEmbedding(_HipModule):
                    "dz_ecapa_peek")
         dtype = torch.int32 if which in (5, 6, 7, 8) else torch.float32
         out = torch.empty(cnt.value, dtype=dtype, device=self.device)
+        torch.cuda.synchronize(self.device)
+        import ctypes
+        hip = ctypes.CDLL("libamdhip64.so")
+        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(cnt.value * 4), 3)
+        if rc != 0:
+            raise _lib.DiartAmdError(f"hipMemcpy failed ({rc})")
+        return out, frames.value
+
+
+class HipSbXvectorEmbedding(_HipModule):
+    """speechbrain's x-vector (speechbrain/spkrec-xvect-voxceleb) behind pyannote's ``PretrainedSpeakerEmbedding``
+    contract, the wrapper the reference falls back to for it (models.py:59): ``(waveform (N,1,S), masks (N,F) |
+    None) -> (N,512)``; a row whose mask keeps fewer than 480 samples, or whose kept samples hold a NaN, is NaN.
+    The same call shape and batch geometry as ``HipEcapaEmbedding``, so the same engine forms take it."""
+
+    dimension = 512
+    min_num_samples = 480
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
+        super().__init__(state, max_batch)
+        self.precision = default_precision(precision)
+
+    def _extra_state(self):
+        return {"precision": self.precision}
+
+    def _pack(self, device):
+        return PackedSbXvector(self._state, device, precision=self.precision)
+
+    def _create(self, num_samples, cap):
+        h = _lib.vp()
+        _lib.check(_lib.load().dz_sbx_create(_lib.context(self.device.index), C.byref(self._packed.struct), cap,
+                                             num_samples, C.byref(h)), "dz_sbx_create")
+        return h
+
+    def _destroy(self, h):
+        _lib.load().dz_sbx_destroy(h)
+
+    def __call__(self, waveform: torch.Tensor, masks: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.device is None:
+            self.to(waveform.device)
+        rows = _as_rows(waveform.to(self.device))
+        N, S = rows.shape
+        mptr, fw = None, 0
+        if masks is not None:
+            masks = masks.to(self.device, torch.float32).contiguous()
+            if masks.ndim != 2 or masks.shape[0] != N:
+                raise ValueError(f"masks must be (batch, frames), got {tuple(masks.shape)}")
+            mptr, fw = masks.data_ptr(), masks.shape[1]
+        handle = self._need(S, N)
+        out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().dz_sbx_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S, mptr, N, fw,
+                                              out.data_ptr(), _stream_ptr(self.device)), "dz_sbx_forward")
+        return out
+
+    def forward_groups(self, waveform: torch.Tensor, masks: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """``waveform (G,1,S)``, ``masks (G,K,Fw)`` speaker-major -> ``(G,K,512)``: each chunk's K rows with the
+        batch geometry of those rows alone, all G groups in one launch sequence, no synchronisation (see
+        ``HipEcapaEmbedding.forward_groups``)."""
+        if self.device is None:
+            self.to(waveform.device)
+        rows = _as_rows(waveform.to(self.device))
+        G, S = rows.shape
+        masks = masks.to(self.device, torch.float32).contiguous()
+        if masks.ndim != 3 or masks.shape[0] != G:
+            raise ValueError(f"masks must be (groups, speakers, frames), got {tuple(masks.shape)}")
+        K = masks.shape[1]
+        handle = self._need(S, G * K)
+        out = torch.empty((G, K, self.dimension), dtype=torch.float32, device=self.device)
+        self.groups_launch(handle, rows.data_ptr(), rows.stride(0) if G > 1 else S, masks.data_ptr(), G, K,
+                           masks.shape[2], normalize, out.data_ptr(), _stream_ptr(self.device))
+        return out
+
+    @staticmethod
+    def groups_launch(handle, wave_ptr: int, wave_stride: int, masks_ptr: int, G: int, K: int, mask_frames: int,
+                      normalize: bool, out_ptr: int, stream_ptr: int) -> None:
+        """``dz_sbx_forward_groups`` on a handle of this model (``StreamBatch``'s lanes): raw device addresses,
+        masks (G,K,Fw) contiguous, out (G*K,512); no synchronisation."""
+        _lib.check(_lib.load().dz_sbx_forward_groups(handle, wave_ptr, wave_stride, masks_ptr, G, K, mask_frames,
+                                                     1 if normalize else 0, out_ptr, stream_ptr),
+                   "dz_sbx_forward_groups")
+
+    def peek(self, num_samples: int, which: int):
+        """Intermediate of the last forward (parity tests): see ``dz_sbx_peek``; -> (tensor, Tc)."""
+        return self.peek_handle(self._handles[num_samples][0], which)
+
+    def peek_handle(self, handle, which: int):
+        """``peek`` of a handle this model created for someone else (``StreamBatch``'s lanes); synchronises."""
+        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
+        _lib.check(_lib.load().dz_sbx_peek(handle, which, C.byref(ptr), C.byref(cnt), C.byref(frames)), "dz_sbx_peek")
+        out = torch.empty(cnt.value, dtype=torch.int32 if which >= 7 else torch.float32, device=self.device)
         torch.cuda.synchronize(self.device)
         import ctypes
         hip = ctypes.CDLL("libamdhip64.so")
@@ -474,9 +573,10 @@ class SegmentationLoader:
 
 
 class EmbeddingLoader:
-    """``arch``: "xvector" (pyannote/embedding), "ecapa" (speechbrain/spkrec-ecapa-voxceleb) or "wespeaker"
-    (pyannote/wespeaker-voxceleb-resnet34-LM); None = decide from the checkpoint keys (``resnet.``: wespeaker,
-    ``asp.``: ecapa, otherwise xvector)."""
+    """``arch``: "xvector" (pyannote/embedding), "ecapa" (speechbrain/spkrec-ecapa-voxceleb), "wespeaker"
+    (pyannote/wespeaker-voxceleb-resnet34-LM) or "sb-xvector" (speechbrain/spkrec-xvect-voxceleb); None = decide
+    from the checkpoint keys (``resnet.``: wespeaker, ``asp.``: ecapa, speechbrain ``Xvector`` keys
+    ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector, otherwise xvector)."""
 
     def __init__(self, state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
                  precision: Optional[str] = None, weight_interp: Optional[str] = None):
@@ -490,6 +590,10 @@ class EmbeddingLoader:
         arch = self.arch or ("ecapa" if any(k.startswith("asp.") for k in sd) else "xvector")
         if self.arch is None and any(k.startswith("resnet.") for k in sd):
             arch = "wespeaker"
+        if arch == "xvector" and self.arch is None and "blocks.0.conv.weight" in sd and "blocks.16.w.weight" in sd:
+            arch = "sb-xvector"     # (the pyannote x-vector packer has no ``blocks.`` keys: this state failed there)
+        if arch == "sb-xvector":
+            return HipSbXvectorEmbedding(sd, self.max_batch, self.precision)
         if arch == "wespeaker":
             return HipWeSpeakerEmbedding(sd, self.max_batch, self.precision)
         if arch == "ecapa":

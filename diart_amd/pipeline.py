@@ -41,7 +41,7 @@ from . import _lib
 from .blocks.aggregation import BatchedOutputTail
 from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
-from .models import HipEcapaEmbedding, HipEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _as_rows
+from .models import HipEcapaEmbedding, HipEmbedding, HipSbXvectorEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _as_rows
 
 # lanes of a throughput engine (>= 64 streams per step on the matrix-core recurrence): profiles/r06*_lanes_grid.json
 THROUGHPUT_LANES = 6
@@ -164,7 +164,8 @@ class AudioRing:
 
 
 class StreamBatch:
-    def __init__(self, segmentation: HipSegmentation, embedding: Union[HipEmbedding, HipEcapaEmbedding], num_streams: int,
+    def __init__(self, segmentation: HipSegmentation,
+                 embedding: Union[HipEmbedding, HipEcapaEmbedding, HipSbXvectorEmbedding], num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  normalize_embedding_weights: bool = False,
@@ -192,16 +193,20 @@ class StreamBatch:
         speaker rows are embedded with the batch geometry of those rows alone (``forward_groups``), and the
         embeddings are L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.  In that form
         ``lanes`` defaults to 2 — one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s) carves
-        about 6.2 GB of device memory per lane — and ``emb_split`` must be 1."""
+        about 6.2 GB of device memory per lane — and ``emb_split`` must be 1.  A ``HipSbXvectorEmbedding``
+        (speechbrain/spkrec-xvect-voxceleb) runs in the same form (about 1.7 GB of arena per lane at 192 rows of 5 s)."""
         if isinstance(embedding, HipWeSpeakerEmbedding):
             raise ValueError("StreamBatch: the WeSpeaker ResNet34 embedding does not run on the N-stream engine; it runs "
-                             "HipEmbedding (pyannote/embedding) and HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb). "
+                             "HipEmbedding (pyannote/embedding), HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb) and "
+                             "HipSbXvectorEmbedding (speechbrain/spkrec-xvect-voxceleb). "
                              "Use the blocks API (SpeakerDiarization) for pyannote/wespeaker-voxceleb-resnet34-LM")
         from .config import setting
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)
         self.device = self.seg.device
-        self.ecapa = isinstance(self.emb, HipEcapaEmbedding)
+        # the groups form (ECAPA, speechbrain x-vector): the whole embedding network behind the step's segmentation,
+        # each stream's K rows with their own batch geometry, through the model's groups_launch
+        self.ecapa = isinstance(self.emb, (HipEcapaEmbedding, HipSbXvectorEmbedding))
         self.n = num_streams
         self.gamma, self.beta, self.norm_w = float(gamma), float(beta), bool(normalize_embedding_weights)
         self.clustering = BatchedSpeakerClustering(num_streams, tau_active, rho_update, delta_new,
@@ -220,8 +225,8 @@ class StreamBatch:
         self.seg_split = max(1, min(int(_lib.exp_env("DZ_SEG_SPLIT", "1") if seg_split is None else seg_split), num_streams))
         self.emb_split = max(1, min(int(_lib.exp_env("DZ_EMB_SPLIT", "1") if emb_split is None else emb_split), num_streams))
         if self.ecapa and self.emb_split != 1:
-            raise ValueError(f"StreamBatch: emb_split={self.emb_split} with an ECAPA embedding (its forward is one "
-                             "launch sequence over every stream's rows: emb_split must be 1)")
+            raise ValueError(f"StreamBatch: emb_split={self.emb_split} with an ECAPA or speechbrain x-vector embedding "
+                             "(its forward is one launch sequence over every stream's rows: emb_split must be 1)")
         # HIP stream priorities (0 normal, -1 high).  The segmentation chain is the long dependent one
         # (4 recurrences + their projections: ~2.2 ms in the pipeline, two lanes): its streams get the
         # high priority — round 3, two same-visit pairs: 1.215 vs 1.233 and 1.159 vs 1.180 ms per step
@@ -300,7 +305,7 @@ class StreamBatch:
         self.seg_front = _lib.exp_env("DZ_SEG_FRONT", "0") != "0"
         if self.ecapa and (self.shared_emb or self.seg_front or self._ablate):
             raise ValueError("StreamBatch: DZ_SHARED_EMB, DZ_SEG_FRONT and DZ_ABLATE are experiments of the x-vector "
-                             "engine; they have no meaning with an ECAPA embedding")
+                             "engine; they have no meaning with an ECAPA or speechbrain x-vector embedding")
         pf = int(_lib.exp_env("DZ_PRIO_F", "0"))
         mk = lambda prio, k: [torch.cuda.Stream(self.device, priority=prio) for _ in range(k)]
         shared_b = mk(pb, self.emb_split) if self.shared_emb else None
@@ -637,9 +642,8 @@ class StreamBatch:
                     b.wait_event(ev)
             if self.ecapa:      # the whole network, each stream's K rows with their own geometry, normalised
                 base, stride = slot["wave"]
-                _lib.check(lib.dz_ecapa_forward_groups(h, base + i0 * stride * 4, stride, slot["w"][i0:i1].data_ptr(),
-                                                       i1 - i0, K, F, 1, slot["emb"][i0:i1].data_ptr(), b.cuda_stream),
-                           "dz_ecapa_forward_groups")
+                self.emb.groups_launch(h, base + i0 * stride * 4, stride, slot["w"][i0:i1].data_ptr(), i1 - i0, K, F,
+                                       True, slot["emb"][i0:i1].data_ptr(), b.cuda_stream)
                 continue
             if self._ablate == "noemb":
                 if not slot.get("_filled"):       # something the clustering accepts

@@ -11,7 +11,8 @@ window from each open stream, stacks them, runs segmentation / embedding once an
 stream's own clustering and aggregation state.  Streams join and leave at any time and advance at
 their own pace; per stream the output is what a dedicated ``SpeakerDiarization`` pipeline with the
 same configuration produces.  The model pair may be config 2's (x-vector) or config 3's (powerset segmentation +
-``HipEcapaEmbedding``, with ``normalize_embedding_weights=True``): see ``StreamBatch``.
+``HipEcapaEmbedding``, with ``normalize_embedding_weights=True``), or the same with the speechbrain x-vector
+(``HipSbXvectorEmbedding``): see ``StreamBatch``.
 
 Audio reaches the GPU through per-stream device rings (``AudioRing.push_rows`` / ``gather``): a step
 uploads only the NEW 500 ms block of each stream that has one (32 KB instead of the 320 KB window the

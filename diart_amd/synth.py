@@ -247,6 +247,28 @@ def synth_ecapa_state(seed: int = 777, channels: int = 1024, lin_neurons: int = 
     return sd
 
 
+def synth_sb_xvector_state(seed: int = 2024, lin_neurons: int = 512) -> Dict[str, torch.Tensor]:
+    """Random-init weights of speechbrain's ``Xvector`` (spkrec-xvect-voxceleb geometry: 24 mel bins, TDNN widths
+    512 x 4 then 1500, kernels 5 / 3 / 3 / 1 / 1), keyed like its ``embedding_model.ckpt`` (``blocks.0.conv.weight``,
+    ``blocks.2.norm.running_var``, ``blocks.16.w.weight``).  BatchNorm statistics are not the identity, so the
+    folding is exercised."""
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    layers = ((24, 512, 5, 0.08), (512, 512, 3, 0.55), (512, 512, 3, 0.55), (512, 512, 1, 0.55), (512, 1500, 1, 0.55))
+    for i, (cin, cout, k, gain) in enumerate(layers):
+        c, n = f"blocks.{3 * i}.conv", f"blocks.{3 * i + 2}.norm"
+        sd[c + ".weight"] = _u(g, (cout, cin, k), gain * math.sqrt(6.0 / (cin * k)))
+        sd[c + ".bias"] = _u(g, (cout,), 0.1)
+        sd[n + ".weight"] = 1.0 + 0.2 * _u(g, (cout,), 1.0)
+        sd[n + ".bias"] = 0.1 * _u(g, (cout,), 1.0)
+        sd[n + ".running_mean"] = 0.2 + 0.1 * _u(g, (cout,), 1.0)
+        sd[n + ".running_var"] = 0.5 + 0.8 * torch.rand((cout,), generator=g)
+        sd[n + ".num_batches_tracked"] = torch.tensor(1000)
+    sd["blocks.16.w.weight"] = _u(g, (lin_neurons, 3000), math.sqrt(6.0 / 3000))
+    sd["blocks.16.w.bias"] = _u(g, (lin_neurons,), 0.1)
+    return sd
+
+
 def synth_wespeaker_state(seed: int = 4242, embed_dim: int = 256) -> Dict[str, torch.Tensor]:
     """Random-init weights of pyannote.audio 3.1's ``WeSpeakerResNet34`` (feat_dim 80, embed_dim 256, TSTP pooling),
     keyed like ``pyannote/wespeaker-voxceleb-resnet34-LM`` (``resnet.conv1.weight``, ``resnet.layer2.0.shortcut.1.

@@ -524,6 +524,53 @@ class PackedEcapa:
         self.struct, self.pack = w, pk
 
 
+class PackedSbXvector:
+    """``dz_sbx_weights`` + the tensors behind it (speechbrain ``Xvector`` checkpoint keys of
+    spkrec-xvect-voxceleb: ``blocks.{0,3,6,9,12}.conv.{weight,bias}``, ``blocks.{2,5,8,11,14}.norm.{weight,bias,
+    running_mean,running_var}``, ``blocks.16.w.{weight,bias}``).
+
+    * the Fbank is ECAPA's (windowed DFT as one GEMM operand) with a 24-bin mel bank;
+    * TDNN weights as ``[Npad][Kpad]`` with ``k = tap * Cin + c`` (channels-last activations), layer 5 padded
+      1500 -> 1536 rows; BatchNorm1d (eval, eps 1e-5) after the LeakyReLU folded to scale / shift;
+    * for "f16x3" the DFT and the five TDNN layers also as row-major split-f16 planes (k_gemm_split.hip); the mel
+      bank and Linear(3000, 512) stay exact f32."""
+
+    CONV_KEYS = (0, 3, 6, 9, 12)
+    # (Cin, taps, Npad, Kpad) of the five TDNN layers
+    TDNN = ((24, 5, 512, 128), (512, 3, 512, 1536), (512, 3, 512, 1536), (512, 1, 512, 512), (512, 1, 1536, 512))
+
+    def __init__(self, sd: Dict[str, torch.Tensor], device: torch.device, precision: str = "f32"):
+        assert precision in PRECISIONS, precision
+        split = precision == "f16x3"
+        pk = _Packed(device)
+        g = lambda k: sd[k].detach().cpu().float()
+        w = _lib.SbxWeights()
+        w.dft = pk.put(_pad2(dft_matrices().float(), 448, 416))
+        if split:
+            w.dft_split = pk.put_split(_pad2(dft_matrices().float(), 512, 416), "windowed DFT")
+        w.mel = pk.put(_pad2(ecapa_mel_filterbank(n_mels=24).t().contiguous(), 64, 224))
+        for i, (cin, taps, npad, kpad) in enumerate(self.TDNN):
+            c, n = f"blocks.{self.CONV_KEYS[i]}.conv", f"blocks.{self.CONV_KEYS[i] + 2}.norm"
+            cw = g(c + ".weight")
+            if tuple(cw.shape[1:]) != (cin, taps):
+                raise ValueError(f"{c}.weight: shape {tuple(cw.shape)}, expected (Cout, {cin}, {taps}) "
+                                 "(speechbrain spkrec-xvect-voxceleb geometry)")
+            m = _conv_pack(cw, cin, npad, kpad)
+            L = w.tdnn[i]
+            L.w, L.b = pk.put(m), pk.put(_pad1(g(c + ".bias"), npad))
+            if split:
+                L.wsplit = pk.put_split(m, f"tdnn{i + 1}")
+            scale = g(n + ".weight") / torch.sqrt(g(n + ".running_var") + BN_EPS)
+            shift = g(n + ".bias") - g(n + ".running_mean") * scale
+            L.s, L.h = pk.put(_pad1(scale, npad)), pk.put(_pad1(shift, npad))
+        lw = g("blocks.16.w.weight")
+        if tuple(lw.shape) != (512, 3000):
+            raise ValueError(f"blocks.16.w.weight: shape {tuple(lw.shape)}, expected (512, 3000)")
+        w.lin_w, w.lin_b = pk.put(_pad2(lw, 512, 3008)), pk.put(g("blocks.16.w.bias"))
+        w.zeros = pk.put(torch.zeros(1536))
+        self.struct, self.pack = w, pk
+
+
 def ecapa_mel_filterbank(n_mels: int = 80, n_fft: int = 400, sample_rate: int = 16000) -> torch.Tensor:
     """speechbrain Filterbank (triangular, f_min = 0, f_max = sr / 2): (n_fft // 2 + 1, n_mels)."""
     to_mel = lambda hz: 2595.0 * math.log10(1.0 + hz / 700.0)

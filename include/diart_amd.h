@@ -319,6 +319,49 @@ int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wave_stride, 
 int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames);
 int dz_wsp_destroy(dz_wsp* m);
 
+/* ---- speechbrain x-vector embedding (speechbrain/spkrec-xvect-voxceleb) behind pyannote's
+ * PretrainedSpeakerEmbedding contract, like ECAPA: waveform (N,1,S), masks (N,Fw) or NULL -> (N,512).
+ * The mask selects samples (nearest resampling, > 0.5), rows are zero padded to the longest kept row of the
+ * call (of the group, for dz_sbx_forward_groups) and the relative lengths drive the sentence mean and the
+ * statistics pooling.  Fbank(24 mel bins) -> sentence mean normalisation -> 5 TDNN layers (Conv1d with reflect
+ * "same" padding -> LeakyReLU(0.01) -> BatchNorm1d) -> StatisticsPooling (mean + 5e-5, unbiased std + 1e-5 over
+ * round(rel * T) frames) -> Linear(3000, 512).  Rows that keep fewer than 480 samples, or whose kept samples hold
+ * a NaN / Inf, come back as NaN.  Activations are channels-last [row][t][c].                                  */
+typedef struct {
+    const float* dft;       /* [448][416] hamming-windowed DFT: rows 0..200 cos, 201..401 sin (as dz_ecapa_weights) */
+    const void* dft_split;  /* optional split-f16 planes [2][512][416] of dft                                      */
+    const float* mel;       /* [64][224] triangular mel bank, [mel][bin], 24 mel rows, zero padded                  */
+    dz_layer tdnn[5];       /* w [Npad][Kpad], k = tap * Cin + c: [512][128] (k5, Cin 24), [512][1536] (k3),
+                               [512][1536] (k3), [512][512], [1536][512]; b / s / h [Npad] (BatchNorm folded, after
+                               the LeakyReLU); wsplit: optional row-major split-f16 planes [2][Npad][Kpad]          */
+    const float* lin_w;     /* [512][3008] Linear(3000, 512), input (mean | std), zero padded columns               */
+    const float* lin_b;     /* [512]                                                                              */
+    const float* zeros;     /* [1536] zeros (the bias of the DFT and mel layers)                                  */
+} dz_sbx_weights;
+typedef struct dz_sbx dz_sbx;
+/* sizeof(dz_sbx_weights): a binding checks its mirror against the library it loaded */
+int dz_sbx_abi_size(void);
+int dz_sbx_create(dz_ctx* ctx, const dz_sbx_weights* w, int max_rows, int num_samples, dz_sbx** out);
+/* n_rows rows (d_wave + r * wave_stride), d_masks (n_rows, mask_frames) or NULL -> d_out (n_rows, 512): one batch
+ * geometry over all n_rows rows (pyannote's call).  Derived on the device: no synchronisation.                */
+int dz_sbx_forward(dz_sbx* m, const float* d_wave, long long wave_stride, const float* d_masks, int n_rows,
+                   int mask_frames, float* d_out, void* stream);
+/* n_groups groups of rows_per_group (K) rows, each group with its own batch geometry, as
+ * dz_ecapa_forward_groups: row g*K + k reads waveform row g and mask row g*K + k ((G,K,Fw) contiguous) ->
+ * d_out (G*K, 512); normalize = 1 L2-normalises every row (NaN rows stay NaN).  A group's rows are what
+ * dz_sbx_forward returns for those K rows alone.  No synchronisation, no allocation.  G*K <= max_rows.          */
+int dz_sbx_forward_groups(dz_sbx* m, const float* d_wave, long long wave_stride, const float* d_masks,
+                          int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                          void* stream);
+/* device pointer + element count of an intermediate of the LAST forward (parity tests); every buffer is laid out
+ * with the handle's Tc = 1 + num_samples / 160 frames per row (*frames receives Tc); frames at or past a row's own
+ * count (buffer 9) are padding:  0 features (N,Tc,24)  1 .. 4 TDNN layers 1 - 4 (N,Tc,512)  5 TDNN layer 5
+ * (N,Tc,1500)  6 pooled statistics (N,3000)  7 kept-sample counts (N) as int32, -(count + 1) for a row with a
+ * NaN / Inf sample  8 nvalid (N) as int32, round(float32(len / lmax) * T)  9 the row's frame count T =
+ * 1 + lmax / 160 of its group (N) as int32 (8 and 9 are 0 for a group whose rows are all too short).          */
+int dz_sbx_peek(dz_sbx* m, int which, const void** d_ptr, long long* count, int* frames);
+int dz_sbx_destroy(dz_sbx* m);
+
 /* ---- OverlappedSpeechPenalty: functional.py:6-13 + blocks/embedding.py:98-107
  * d_seg (B,F,K) -> weights.  speaker_major=0: (B,F,K) like the reference block;
  * speaker_major=1: (B,K,F), the layout dz_emb_forward_multi consumes.           */
