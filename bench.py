@@ -17,12 +17,12 @@ N > 1 (launched by torch.distributed.run): every rank owns 64 streams of its own
 streams are independent — no data-path collective); rank 0 synthesises the weights and broadcasts
 them over RCCL; timing is barrier + synchronize on both sides, max over ranks.
 
-Besides the contract's fields the JSON line carries: ``roofline`` (dominant MFMA-bound kernel) and
-``roofline_kernels`` (every kernel against its own bound) from per-kernel dispatch timestamps taken
-on every 10th timed step; ``exact_f32`` — the same job on the exact-f32 matrix path (the default
-arithmetic is "f16x3"); ``host_fed`` — the same job with each step's new audio
-uploaded from pinned host memory into the device ring (PCIe-inclusive); ``cpu_baseline`` — the
-oracle on the host cores (rank 0, N = 1).
+A plain run sets up, warms up, times its steps, writes --dump-outputs and prints the line.  With
+``--full`` the JSON line also carries: ``roofline`` (dominant kernel) and ``roofline_kernels`` (every
+kernel against its own bound) from a serialised pass of their own; ``power``; ``exact_f32`` — the same
+job on the exact-f32 matrix path (the default arithmetic is "f16x3"); ``host_fed`` — the
+same job with each step's new audio uploaded from pinned host memory into the device ring
+(PCIe-inclusive); ``host_rehearsal``; ``cpu_baseline`` — the oracle on the host cores (rank 0, N = 1).
 """
 from __future__ import annotations
 
@@ -220,10 +220,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--streams", type=int, default=64, help="concurrent streams per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-rehearsal", action="store_true", help="skip the 8-rank host-contention rehearsal (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure: the power pass, the serialised roofline pass, "
+                         "the host-fed and exact-f32 passes, the rocprofv3 --pmc children, the 8-rank host rehearsal and the CPU "
+                         "baseline (config 3: the host-phase and per-kernel passes).  The --no-* switches below take single "
+                         "ones out again.  Without it a run sets up, warms up, times its steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-rehearsal", action="store_true", help="--full: skip the 8-rank host-contention rehearsal (N = 1 only)")
     ap.add_argument("--power-seconds", type=float, default=float(os.environ.get("DZ_BENCH_POWER_S", "1.5")),
-                    help="N = 1: length of the untimed pass behind the timed region during which the card's hwmon files "
+                    help="--full, N = 1: length of the untimed pass behind the timed region during which the card's hwmon files "
                          "(package power, shader clock) are sampled -> `power` (0: off)")
     ap.add_argument("--no-tail", action="store_true",
                     help="stop after clustering (skip the C++ aggregation + binarisation tail)")
@@ -236,9 +241,9 @@ def parse():
     ap.add_argument("--lanes", type=int, default=0, help="StreamBatch(lanes=) (default: the engine's choice)")
     ap.add_argument("--inflight", type=int, default=0, help="StreamBatch(inflight=) (default: lanes + 1)")
     ap.add_argument("--no-host-pass", action="store_true",
-                    help="skip the extra pass that uploads each step's new audio from pinned host memory")
+                    help="--full: skip the extra pass that uploads each step's new audio from pinned host memory")
     ap.add_argument("--pmc", choices=["on", "all", "off"], default=os.environ.get("DZ_BENCH_PMC", "on"),
-                    help="N = 1: measure HBM traffic / matrix-core busy per kernel LIVE with rocprofv3 --pmc child "
+                    help="--full, N = 1: measure HBM traffic / matrix-core busy per kernel LIVE with rocprofv3 --pmc child "
                          "passes of this command (on: headline precision, ~2 min; all: also the exact-f32 pass; "
                          "off: use the committed passes under profiles/)")
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 5],
@@ -250,16 +255,17 @@ def parse():
                     help="side file for the full record (per-kernel tables, exact-f32 tables, rehearsal, notes); "
                          "stdout carries ONE compact JSON line (diart_amd/benchline.py)")
     ap.add_argument("--serial-steps", type=int, default=8,
-                    help="steps of the serialised roofline pass (one lane, one HIP stream, every launch bracketed: a kernel's "
-                         "duration there is its alone-time, what rocprofv3 --kernel-trace --stats of the same pass reports); 0 = off")
+                    help="steps of the serialised roofline pass of --full and --serial-only (one lane, one HIP stream, every launch "
+                         "bracketed: a kernel's duration there is its alone-time, what rocprofv3 --kernel-trace --stats of the same "
+                         "pass reports); 0 = off, and every 10th timed step carries the brackets instead")
     ap.add_argument("--overlap-brackets", action="store_true",
                     help="also bracket every 10th step of the TIMED passes (per-kernel durations while the lanes overlap -> "
                          "`roofline_kernels_overlapped` in the details file, --kernel-table); off by default: the roofline comes "
-                         "from the serialised pass, and event pairs on a timed step cost it ~15 %")
+                         "from the serialised pass, and event pairs on a timed step cost it ~15 %%")
     ap.add_argument("--serial-only", action="store_true",
                     help="run ONLY the serialised roofline pass (the command profiles/*_rocprofv3_kernel_stats_serial_*.csv are traces of)")
     ap.add_argument("--no-exact-f32", action="store_true",
-                    help="skip the second, untimed-for-`value` pass on the exact-f32 MFMA path")
+                    help="--full: skip the second, untimed-for-`value` pass on the exact-f32 MFMA path")
     ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
                          "(float32 / float64, rank 0, at most 64 MB: a seeded sample of the streams beyond that); "
@@ -511,7 +517,8 @@ def pmc_live(precision, args=None):
         return None
     t_start, budget = time.monotonic(), float(os.environ.get("DZ_PMC_BUDGET_S", "200"))
     work = Path(tempfile.mkdtemp(prefix="dz_pmc_"))
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    # (--full with every extra pass but the serialised one switched off: its launches are counted too, as they always were)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-exact-f32", "--no-host-pass", "--pmc", "off", "--no-rehearsal", "--power-seconds", "0", "--precision", precision,
            *(engine_args(args) if args is not None else [])]
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", TMPDIR="/tmp", DZ_SETTLE_STEPS="0")
@@ -735,6 +742,37 @@ def config3(args):
     T_FULL = 498                                         # frames of a full 5 s mask (ECAPA_MAC_PER_ROW is written for it)
     t_timed = sum(frames_timed) / max(1, len(frames_timed))
     gflop_chunk = 2.0 * (656_230_928 + 3 * ECAPA_MAC_PER_ROW * t_timed / T_FULL) / 1e9
+    phases, groups, T_ROW, tot, dom = (config3_passes(args, pipe, chunks, B, frames_of, precision, lib) if args.full
+                                       else (None, [], None, None, None))
+    out = {
+        "metric": "real-time-factor xRT streams/GPU @500ms step", "value": round(cps / 2, 2),
+        "unit": "xRT 16 kHz streams (chunks/s / 2)", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32" if precision == "f32" else "f16x3", "data": "synthetic",
+        "config": {"workload": "configs[2]: single MI355X, pyannote/segmentation-3.0 (powerset) + speechbrain ECAPA-TDNN "
+                               "architectures (random-init weights), 5 s window / 500 ms step, one synthetic stream through "
+                               "the blocks pipeline in batches of 32 consecutive windows (96 embedding rows per step)",
+                   "chunks_per_step": B, "speech_turns_emitted": turns, "host_phases_ms": phases,
+                   "ecapa_frames_per_row": {"timed_mean": round(t_timed, 1), "timed_min": min(frames_timed, default=0),
+                                            "timed_max": max(frames_timed, default=0),
+                                            "bracketed_mean": round(T_ROW, 1) if T_ROW is not None else None,
+                                            "full_mask": T_FULL}},
+        "roofline": dict(dom, traffic=None, whole_path_tflops=round(cps * gflop_chunk / 1e3, 2),
+                         alg_gflop_per_chunk=round(gflop_chunk, 2), kernel_time_ms_per_step=round(tot, 3),
+                         peak_note="f16 matrix peak / 3 for the layers on the split-f16 kernels (three MFMAs per "
+                                   "algorithmic product), exact-f32 matrix peak for the others; brackets = the "
+                                   "dispatches' own timestamps over %d steps after the timed region; algorithmic work "
+                                   "= 96 rows x the frames the step's batch was padded to (config.ecapa_frames_per_row), "
+                                   "not a full 5 s mask" % min(4, args.steps)) if args.full else None,
+        "roofline_kernels": groups,
+        "cpu_baseline": None,
+    }
+    emit(out, args.details)
+
+
+def config3_passes(args, pipe, chunks, B, frames_of, precision, lib):
+    """`--config 3 --full`: a few untimed steps after the timed region, clocked per phase, then a few more with per-kernel
+    brackets -> (phases, kernel groups, mean ECAPA frames of the bracketed steps, kernel ms per step, dominant group)."""
     # ---- where a step's wall time goes (a few extra untimed steps; every phase of the synchronous blocks API ends
     # in a `.cpu()`, so host clocks around the three calls of SpeakerDiarization.__call__ are honest) -------------
     phases = {"stack": 0.0, "segmentation": 0.0, "embedding": 0.0, "finalise": 0.0}
@@ -795,29 +833,7 @@ def config3(args):
         g["share_of_kernel_time"] = round(g["ms_per_step"] / tot, 4)
     groups.sort(key=lambda g: -g["ms_per_step"])
     dom = next((g for g in groups if g.get("bound") == "mfma"), groups[0] if groups else {})
-    out = {
-        "metric": "real-time-factor xRT streams/GPU @500ms step", "value": round(cps / 2, 2),
-        "unit": "xRT 16 kHz streams (chunks/s / 2)", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32" if precision == "f32" else "f16x3", "data": "synthetic",
-        "config": {"workload": "configs[2]: single MI355X, pyannote/segmentation-3.0 (powerset) + speechbrain ECAPA-TDNN "
-                               "architectures (random-init weights), 5 s window / 500 ms step, one synthetic stream through "
-                               "the blocks pipeline in batches of 32 consecutive windows (96 embedding rows per step)",
-                   "chunks_per_step": B, "speech_turns_emitted": turns, "host_phases_ms": phases,
-                   "ecapa_frames_per_row": {"timed_mean": round(t_timed, 1), "timed_min": min(frames_timed, default=0),
-                                            "timed_max": max(frames_timed, default=0), "bracketed_mean": round(T_ROW, 1),
-                                            "full_mask": T_FULL}},
-        "roofline": dict(dom, traffic=None, whole_path_tflops=round(cps * gflop_chunk / 1e3, 2),
-                         alg_gflop_per_chunk=round(gflop_chunk, 2), kernel_time_ms_per_step=round(tot, 3),
-                         peak_note="f16 matrix peak / 3 for the layers on the split-f16 kernels (three MFMAs per "
-                                   "algorithmic product), exact-f32 matrix peak for the others; brackets = the "
-                                   "dispatches' own timestamps over %d steps after the timed region; algorithmic work "
-                                   "= 96 rows x the frames the step's batch was padded to (config.ecapa_frames_per_row), "
-                                   "not a full 5 s mask" % nprof),
-        "roofline_kernels": groups,
-        "cpu_baseline": None,
-    }
-    emit(out, args.details)
+    return phases, groups, T_ROW, tot, dom
 
 
 def config5(args):
@@ -1309,7 +1325,7 @@ def main():
                           "40 ms by a side thread during an untimed pass behind the timed region; median of its last 60 %"}
 
     power = None
-    if world == 1 and rank == 0 and args.power_seconds > 0:
+    if args.full and world == 1 and rank == 0 and args.power_seconds > 0:
         try:
             power = power_pass(pipe)
         except Exception as exc:      # noqa: BLE001 — an unreadable hwmon tree must not cost the run its line
@@ -1317,7 +1333,7 @@ def main():
     if power:
         log(f"power pass: {power['package_w']} W at {power['sclk_mhz']} MHz over {power['steps']} steps "
             f"({power['ms_per_step']} ms / step, {power['joules_per_step']} J / step; idle {power['idle_w']} W)")
-    serial = serial_pass(precision) if args.serial_steps > 0 else None
+    serial = serial_pass(precision) if args.full and args.serial_steps > 0 else None
     host_line = {"cpu_ms_per_step": round(host["cpu_ms_per_step"], 3), "launch_ms_per_step": round(host["launch_ms_per_step"], 3),
                  "step_period_ms_in_timed_region": host["step_period_ms"],
                  "clustering_tail_wall_ms_per_step": round(host["work_ms_per_step"], 3), "threads": host_threads,
@@ -1332,7 +1348,7 @@ def main():
     # ---- the same job fed from HOST buffers: every step uploads the 500 ms of new audio of each
     # stream (pinned memory -> device ring, dz_ring_push) instead of finding it in HBM ------------
     host_fed = None
-    if not args.no_host_pass:
+    if args.full and not args.no_host_pass:
         from diart_amd.pipeline import AudioRing
         ring = AudioRing(n, S, hop, slack_blocks=2 * pipe.max_inflight + 2, device=device)   # >= steps in flight
         blocks = audio_cpu.unfold(1, hop, hop)                     # (n, nblocks, hop) view
@@ -1399,7 +1415,7 @@ def main():
     # ---- the same job on the exact-f32 MFMA path: the number at the reference's own arithmetic,
     # measured the same way (own per-kernel brackets, own roofline), not `value` ----------------------
     exact = None
-    if precision != "f32" and not args.no_exact_f32:
+    if args.full and precision != "f32" and not args.no_exact_f32:
         p32 = make_pipe("f32")
         prof_warm(p32)
         # the same settling as the headline pass, a third as many steps (they take twice as long): a timed region that
@@ -1425,7 +1441,7 @@ def main():
 
     if rank == 0:
         cps = D.whole_job_rate(n, args.steps, elapsed, world)
-        pmc = pmc_live(precision, args) if (world == 1 and args.pmc != "off") else None
+        pmc = pmc_live(precision, args) if (args.full and world == 1 and args.pmc != "off") else None
         pmc32 = pmc_live("f32", args) if (pmc is not None and exact is not None and args.pmc == "all") else None
         # per-kernel roofline from the SERIALISED pass (alone-times, reproducible from rocprofv3's kernel stats of
         # `--serial-only`); the brackets of the timed region — taken while `lanes` steps share the chip — go to the details
@@ -1434,14 +1450,17 @@ def main():
         if serial is not None:
             roof, per_kernel = build_roofline(serial[0], precision, serial[1], pmc)
             roof["serialised"], roof["serialised_ms_per_step"] = True, round(serial[2], 3)
-        else:
+        else:           # (a plain run without brackets on its timed steps has no roofline: roof None, per_kernel [])
             roof, per_kernel = build_roofline(table, precision, n_sampled, pmc)
-            roof["serialised"] = False
+            if roof is not None:
+                roof["serialised"] = False
         peak_path = PEAK_F32_MATRIX_TFLOPS if precision == "f32" else PEAK_F16_MATRIX_TFLOPS / SPLIT_PRODUCTS
-        roof["whole_path_tflops"] = round(cps / world * ALG_GFLOP_PER_CHUNK / 1e3, 2)
-        whole_path_frac = round(roof["whole_path_tflops"] / peak_path, 4)
-        roof["exact_f32_value"] = exact["value"] if exact else None
-        roof["host_fed_value"] = host_fed["value"] if host_fed else None
+        whole_path_tflops = round(cps / world * ALG_GFLOP_PER_CHUNK / 1e3, 2)
+        whole_path_frac = round(whole_path_tflops / peak_path, 4)
+        if roof is not None:
+            roof["whole_path_tflops"] = whole_path_tflops
+            roof["exact_f32_value"] = exact["value"] if exact else None
+            roof["host_fed_value"] = host_fed["value"] if host_fed else None
         whole_path_frac_f32 = None
         if exact is not None:
             ser32 = exact.pop("_serial")
@@ -1455,7 +1474,8 @@ def main():
             whole_path_frac_f32 = round(r32["whole_path_tflops"] / PEAK_F32_MATRIX_TFLOPS, 4)
             exact["roofline"], exact["roofline_kernels"] = r32, pk32
         # step-level utilisation: launches per step and PMC per-launch figures x the timed region's step time
-        mfma_step, hbm_step, roof_mfma = step_level(per_kernel, 1e3 * elapsed / args.steps, precision, roof.get("traffic_source"))
+        mfma_step, hbm_step, roof_mfma = (step_level(per_kernel, 1e3 * elapsed / args.steps, precision, roof.get("traffic_source"))
+                                          if per_kernel else (None, None, None))
         if exact is not None:
             exact["mfma_util_step"], exact["hbm_gbps_step"], exact["roofline_mfma"] = step_level(
                 exact["roofline_kernels"], exact["ms_per_step"], "f32", exact["roofline"].get("traffic_source"))
@@ -1473,7 +1493,7 @@ def main():
                            "(dz_range_check).  LSTM recurrence, classifier, pooling, Linear(3000,512): exact f32; "
                            "clustering / aggregation f64.  Error vs the f32 oracle equals the exact-f32 path's "
                            "(tests/test_gpu_models.py, tests/test_gpu_parity_r2.py: same gates for both).  The "
-                           "exact-f32 run of the same job is in `exact_f32`."),
+                           "exact-f32 run of the same job is in `exact_f32` (--full)."),
             "data": "synthetic",
             "config": {"workload": "configs[1]: single MI355X, 5 s window / 500 ms step, "
                                    "pyannote/segmentation + pyannote/embedding architectures "
@@ -1501,12 +1521,12 @@ def main():
             "host_fed": host_fed,
             "host": host_line,
         }
-        if world == 1 and not args.no_rehearsal:
+        if args.full and world == 1 and not args.no_rehearsal:
             out["host_rehearsal"] = host_rehearsal(args, precision, usable)
         if args.kernel_table:
             Path(args.kernel_table).parent.mkdir(parents=True, exist_ok=True)
             Path(args.kernel_table).write_text(json.dumps(table, indent=1))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_chunks)
         elif not args.no_cpu_baseline:
             out["cpu_baseline"] = None

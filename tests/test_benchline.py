@@ -61,6 +61,21 @@ def test_power_entry_reaches_the_line():
     assert len(json.dumps(d)) < 4096
 
 
+def test_plain_run_record_keeps_the_contract_fields():
+    """What bench.py records without --full: the headline pass alone; the fields of the other passes are null or absent."""
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "dtype_note", "data", "config", "host")
+    plain = {k: copy.deepcopy(FULL[k]) for k in keep}
+    plain.update(roofline=None, roofline_mfma=None, mfma_util_step=None, hbm_gbps_step=None, roofline_kernels=[],
+                 exact_f32=None, host_fed=None, power=None, cpu_baseline=None, whole_path_frac=0.27)
+    d = json.loads(benchline.line(plain, None))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert d[k] == FULL[k], k
+    assert d["roofline"] is None and d["roofline_mfma"] is None and d["cpu_baseline"] is None
+    assert d["value_exact_f32"] is None and d["value_host_fed"] is None and d["hbm_gbps_step"] is None
+    assert "power" not in d and "host_rehearsal" not in d and d["whole_path_frac"] == 0.27
+
+
 def test_missing_parts_do_not_break_the_line():
     d = json.loads(benchline.line({"metric": "m", "value": 1.0}, None))
     assert d["roofline"] is None and d["cpu_baseline"] is None and d["value"] == 1.0

@@ -3,7 +3,7 @@ OUT=gpurun_out/${TAG:-ab_multi}; mkdir -p $OUT
 for r in $(seq 1 ${ROUNDS:-2}); do
   for arm in $ARMS; do
     name=${arm%%:*}; envs=$(echo "${arm#*:}" | tr ',' ' ')
-    env $envs timeout -s KILL 300 python bench.py --steps ${STEPS:-200} --warmup 10 --pmc off --no-cpu-baseline --no-rehearsal --no-exact-f32 --no-host-pass \
+    env $envs timeout -s KILL 300 python bench.py --steps ${STEPS:-200} --warmup 10 --full --pmc off --no-cpu-baseline --no-rehearsal --no-exact-f32 --no-host-pass \
       --details $OUT/${name}_${r}_details.json > $OUT/${name}_$r.json 2> $OUT/${name}_$r.err
     python - <<PY
 import json

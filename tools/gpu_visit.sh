@@ -21,22 +21,22 @@ exp_tests)   # the experiments build: the never-default kernels against the same
   DZ_EXPERIMENTS=1 timeout -s KILL 900 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_parity_r2.py tests/test_abi.py -q -m "gpu or not gpu" -p no:cacheprovider 2>&1 | grep -v amdgpu.ids | tail -4 | tee $OUT/pytest_gpu_experiments.txt ;;
 smoke)
   timeout -s KILL 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
-driver)      # exactly what the driver runs
-  DZ_PMC_KEEP=$OUT/pmc_tables timeout -s KILL 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --pmc all --details $OUT/bench_driver_details.json > $OUT/bench_driver.json 2> $OUT/bench_driver.err
+driver)      # the headline command (--gpus 1 --steps 20 --warmup 5) with every extra pass (--full)
+  DZ_PMC_KEEP=$OUT/pmc_tables timeout -s KILL 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --pmc all --details $OUT/bench_driver_details.json > $OUT/bench_driver.json 2> $OUT/bench_driver.err
   echo "exit $? chars $(wc -c < $OUT/bench_driver.json)"; cut -c1-260 $OUT/bench_driver.json ;;
 driver2)     # twice more, short form (no PMC children, no CPU leg): run-to-run spread of the 20-step region
   for i in 1 2; do
-    timeout -s KILL 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --pmc off --no-cpu-baseline --no-rehearsal --details $OUT/bench_driver_short_${i}_details.json > $OUT/bench_driver_short_$i.json 2> $OUT/bench_driver_short_$i.err
+    timeout -s KILL 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --pmc off --no-cpu-baseline --no-rehearsal --details $OUT/bench_driver_short_${i}_details.json > $OUT/bench_driver_short_$i.json 2> $OUT/bench_driver_short_$i.err
     cut -c1-200 $OUT/bench_driver_short_$i.json
   done ;;
 long)        # 200 timed steps
-  timeout -s KILL 600 python bench.py --steps 200 --warmup 10 --pmc off --no-cpu-baseline --no-rehearsal --details $OUT/bench_200_details.json > $OUT/bench_200.json 2> $OUT/bench_200.err
+  timeout -s KILL 600 python bench.py --steps 200 --warmup 10 --full --pmc off --no-cpu-baseline --no-rehearsal --details $OUT/bench_200_details.json > $OUT/bench_200.json 2> $OUT/bench_200.err
   echo "exit $?"; cut -c1-260 $OUT/bench_200.json ;;
 rocprof)     # rocprofv3 --kernel-trace --stats of the bench command, both precisions
   cd /tmp
   for P in f16x3 f32; do
     DZ_PROF_EVERY=1 DZ_SETTLE_STEPS=0 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_$P -o prof -- \
-      python $REPO/bench.py --steps 10 --warmup 3 --precision $P --no-cpu-baseline --no-exact-f32 --no-host-pass --no-rehearsal --pmc off \
+      python $REPO/bench.py --steps 10 --warmup 3 --precision $P --full --no-cpu-baseline --no-exact-f32 --no-host-pass --no-rehearsal --pmc off \
       --kernel-table $REPO/$OUT/kernels_events_rocprof_run_$P.json --details $REPO/$OUT/bench_rocprof_${P}_details.json > $REPO/$OUT/prof_$P.log 2>&1
     echo "rocprof $P exit $?"
   done
@@ -62,7 +62,7 @@ rocprof_serial)   # rocprofv3 --kernel-trace --stats of the SERIALISED roofline 
   done
   find $OUT -name '*kernel_trace*' -size +3M -delete ;;
 config3)
-  timeout -s KILL 300 python bench.py --config 3 --steps 20 --warmup 3 --details $OUT/bench_config3_details.json > $OUT/bench_config3.json 2> $OUT/bench_config3.err
+  timeout -s KILL 300 python bench.py --config 3 --steps 20 --warmup 3 --full --details $OUT/bench_config3_details.json > $OUT/bench_config3.json 2> $OUT/bench_config3.err
   cut -c1-300 $OUT/bench_config3.json; grep "phases" $OUT/bench_config3.err | cut -c1-300 ;;
 config5)
   timeout -s KILL 300 python bench.py --config 5 --steps 400 --warmup 20 --details $OUT/bench_config5_details.json > $OUT/bench_config5.json 2> $OUT/bench_config5.err
