@@ -120,6 +120,12 @@ SIGNATURES = {
     "dz_wsp_forward_multi": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_wsp_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_wsp_destroy": (C.c_int, [vp]),
+    "dz_resample_geometry": (C.c_int, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "dz_resample_out_len": (C.c_longlong, [C.c_int, C.c_int, C.c_longlong]),
+    "dz_resample_table": (C.c_int, [C.c_int, C.c_int, c_float_p]),
+    "dz_resample_create": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_resample_forward": (C.c_int, [vp, vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_longlong, vp]),
+    "dz_resample_destroy": (C.c_int, [vp]),
     "dz_prof_enable": (C.c_int, [C.c_int]),
     "dz_prof_pause": (C.c_int, [C.c_int]),
     "dz_prof_collect": (C.c_int, []),

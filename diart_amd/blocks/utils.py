@@ -10,7 +10,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ..features import Annotation, Segment, SlidingWindowFeature
+from ..features import Annotation, Segment, SlidingWindowFeature, TemporalFeatureFormatter, TemporalFeatures
+from ..functional import resample, resampler
 
 
 def windows_batch(waveforms: Sequence[SlidingWindowFeature], device=None) -> torch.Tensor:
@@ -87,3 +88,24 @@ class Binarize:
             for a, b in zip(onsets, offsets):
                 annotation[Segment(ts[int(a)].middle, ts[int(b)].middle), int(spk)] = f"speaker{spk}"
         return annotation
+
+
+class Resample:
+    """Resample audio chunks (reference ``blocks/utils.py:62-89``, ``torchaudio.transforms.Resample``) on the GPU:
+    ``(batch, samples, channels)`` or ``(samples, channels)`` features in, the same kind out, each chunk resampled
+    on its own along the sample axis.  A ``SlidingWindowFeature`` keeps its start time and gets the resolution
+    duration / samples.  ``resample`` is the functional form for whole signals."""
+
+    def __init__(self, sample_rate: int, resample_rate: int, device: Optional[torch.device] = None):
+        self.sample_rate, self.resample_rate = int(sample_rate), int(resample_rate)
+        self.resample = resampler(self.sample_rate, self.resample_rate, device)
+        self.device = self.resample.device
+        self.formatter = TemporalFeatureFormatter()
+
+    def __call__(self, waveform: TemporalFeatures) -> TemporalFeatures:
+        wav = self.formatter.cast(waveform).to(self.device)  # (batch, samples, channels)
+        if self.sample_rate == self.resample_rate:
+            return self.formatter.restore_type(wav)
+        out = self.resample(wav.transpose(-1, -2)).transpose(-1, -2)
+        return self.formatter.restore_type(out)
+

@@ -547,6 +547,13 @@ int dz_launch_wsp_conv1(const float* feats, int N, int T, const float* w, const 
 int dz_launch_wsp_pool(const float* x, int B, int T4, const float* weights, int Fw, int K, const int* bad,
                        float* out, int* rflag, hipStream_t st);
 
+// k_resample.hip ------------------------------------------------------------
+// rows signals (in + r in_stride, in_len samples) -> out + r out_stride (out_len samples); table tap-major [T][n_pad]
+// (tap_major = 1, n >= 64) or phase-major [n][T]
+int dz_launch_resample(const float* in, long long in_stride, long long in_len, int rows, const float* table,
+                       int tap_major, int n, int n_pad, int o, int width, int T, float* out, long long out_stride,
+                       long long out_len, hipStream_t st);
+
 struct dz_ctx {
     int device;
     // "an operand left the f16 range" flag of the split-f16 kernels: one int in pinned, device-mapped

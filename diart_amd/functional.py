@@ -59,3 +59,77 @@ def normalize_embeddings(embeddings: torch.Tensor, norm: Union[float, torch.Tens
     elif norm != 1:
         out = norm * out
     return out if src == dev else out.to(src)
+
+
+class Resampler:
+    """``orig_freq`` -> ``new_freq`` on one GPU (``dz_resample_*``): torchaudio's ``sinc_interp_hann`` resampler with
+    its defaults, the filter built once in float64 and rounded to float32 (DESIGN.md "Resampling").  Each output is
+    one f32 fused-multiply-add chain over its taps, so a signal's outputs do not depend on the batch it comes in."""
+
+    def __init__(self, orig_freq: int, new_freq: int, device: Optional[torch.device] = None):
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.device = _gpu(device)
+        self._lib = _lib.load()
+        self._h = _lib.vp()
+        _lib.check(self._lib.dz_resample_create(_lib.context(self.device.index), self.orig_freq, self.new_freq,
+                                                _lib.C.byref(self._h)), "dz_resample_create")
+
+    def out_len(self, in_len: int) -> int:
+        n = self._lib.dz_resample_out_len(self.orig_freq, self.new_freq, int(in_len))
+        if n < 0:
+            raise ValueError(f"{in_len} samples at {self.orig_freq} Hz have no output length at {self.new_freq} Hz")
+        return int(n)
+
+    def rows(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``x`` (rows, L) float32 on this device, rows at any stride (a ring or window-batch view is read in
+        place) -> ``out`` (rows, out_len(L)), allocated when not given.  Enqueued on the current stream."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.ndim == 2 and x.stride(1) == 1
+        R, L = x.shape
+        M = self.out_len(L)
+        if out is None:
+            out = torch.empty((R, M), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (R, M) and out.stride(1) == 1
+        _lib.check(self._lib.dz_resample_forward(self._h, x.data_ptr(), x.stride(0), L, R, out.data_ptr(),
+                                                 out.stride(0), torch.cuda.current_stream(self.device).cuda_stream),
+                   "dz_resample_forward")
+        return out
+
+    def __call__(self, waveform: torch.Tensor) -> torch.Tensor:
+        """(..., L) on the host or the GPU -> (..., out_len(L)) on the device of the input."""
+        src = waveform.device
+        lead, L = waveform.shape[:-1], waveform.shape[-1]
+        x = waveform.to(self.device, torch.float32).reshape(-1, L)
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        y = self.rows(x).reshape(*lead, -1)
+        return y if src == self.device else y.to(src)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._lib.dz_resample_destroy(h)
+            self._h = None
+
+
+_resamplers = {}
+
+
+def resampler(orig_freq: int, new_freq: int, device: Optional[torch.device] = None) -> Resampler:
+    """The process's ``Resampler`` for (GPU, orig_freq, new_freq), created on first use."""
+    dev = _gpu(device)
+    key = (dev.index, int(orig_freq), int(new_freq))
+    if key not in _resamplers:
+        _resamplers[key] = Resampler(orig_freq, new_freq, dev)
+    return _resamplers[key]
+
+
+def resample(waveform, orig_freq: int, new_freq: int, device: Optional[torch.device] = None):
+    """``torchaudio.functional.resample(waveform, orig_freq, new_freq)`` over the last axis, on the GPU.  A tensor
+    comes back on its own device, a numpy array as a float32 array; equal rates return ``waveform`` itself."""
+    if int(orig_freq) == int(new_freq):
+        return waveform
+    if isinstance(waveform, torch.Tensor):
+        return resampler(orig_freq, new_freq, device if waveform.device.type != "cuda" else waveform.device)(waveform)
+    import numpy as np
+    x = torch.from_numpy(np.ascontiguousarray(waveform, dtype=np.float32))
+    return resampler(orig_freq, new_freq, device)(x).numpy()

@@ -56,7 +56,7 @@ def read_wav_into(path: FilePath, alloc, padding_of, block_duration: float = 0.5
 
 
 def read_wav(path: FilePath) -> Tuple[np.ndarray, int]:
-    """PCM WAV (8/16/32-bit integer) -> (mono float32 in [-1, 1], sample rate); channels are
+    """PCM WAV (8/16/24/32-bit integer) -> (mono float32 in [-1, 1], sample rate); channels are
     averaged like ``AudioLoader(mono=True)`` (reference ``audio.py:36-40``)."""
     with wave.open(str(path), "rb") as f:
         sr, nch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
@@ -67,10 +67,45 @@ def read_wav(path: FilePath) -> Tuple[np.ndarray, int]:
         x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
     elif width == 1:
         x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    elif width == 3:
+        # 24-bit little-endian PCM: the 3 bytes as the top of an int32 (what a 32-bit file of the same samples holds),
+        # so the decode is the 32-bit one (value / 2^31, exact)
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3)
+        w = np.zeros((b.shape[0], 4), dtype=np.uint8)
+        w[:, 1:] = b
+        x = w.view("<i4")[:, 0].astype(np.float32) / 2147483648.0
     else:
         raise ValueError(f"{path}: unsupported sample width {width}")
     x = x.reshape(-1, nch)
     return (x.mean(axis=1) if nch > 1 else x[:, 0]).astype(np.float32), sr
+
+
+def resample_file(waveform: np.ndarray, orig_freq: int, new_freq: int, device=None) -> np.ndarray:
+    """A whole mono signal at ``new_freq`` (float32 on the host), resampled on the GPU ``device`` (None: the current
+    one) by ``functional.resample``."""
+    from .functional import resample
+    return resample(np.asarray(waveform, dtype=np.float32).reshape(-1), orig_freq, new_freq, device)
+
+
+def read_wav_resampled_into(path: FilePath, alloc, padding_of, block_duration: float, sample_rate: int,
+                            device=None):
+    """``read_wav_into`` at the pipeline's rate: a file at another rate is decoded, resampled as a whole on the GPU,
+    then padded (``padding_of`` gets the file's own duration, as the reference's ``get_file_padding`` does) and
+    blocked at ``sample_rate`` into ``alloc``.  A file at ``sample_rate`` takes ``read_wav_into`` itself."""
+    with wave.open(str(path), "rb") as f:
+        sr = f.getframerate()
+    if sr == sample_rate:
+        return read_wav_into(path, alloc, padding_of, block_duration)
+    x, sr = read_wav(path)
+    padding = padding_of(len(x) / sr)
+    y = resample_file(x, sr, sample_rate, device)
+    left, right = (int(np.rint(p * sample_rate)) for p in padding)
+    size = int(np.rint(block_duration * sample_rate))
+    total = left + len(y) + right
+    out = alloc(-(-total // size) * size)
+    out[:] = 0.0
+    out[left:left + len(y)] = y
+    return out, sample_rate, padding
 
 
 def write_wav(path: FilePath, samples: np.ndarray, sample_rate: int = 16000) -> None:
@@ -179,8 +214,14 @@ class StreamingInference:
                  padding: Tuple[float, float] = (0, 0), batch_size: int = 1, hooks: Sequence = ()):
         cfg = pipeline.config
         if sample_rate != cfg.sample_rate:
-            raise ValueError(f"audio source has sample rate {sample_rate}, the pipeline's is "
-                             f"{cfg.sample_rate}; resample the file first")
+            # the whole file at the pipeline's rate, as FileAudioSource loads it (reference audio.py:31-37), on the
+            # pipeline's GPU; the padding (seconds) is applied after.  A pipeline without a GPU device has nowhere
+            # to resample.
+            if getattr(getattr(cfg, "device", None), "type", None) != "cuda":
+                raise ValueError(f"audio source has sample rate {sample_rate}, the pipeline's is {cfg.sample_rate} "
+                                 "and the pipeline has no GPU device to resample on; resample the file first")
+            waveform = resample_file(waveform, sample_rate, cfg.sample_rate, cfg.device)
+            sample_rate = cfg.sample_rate
         self.pipeline, self.batch_size, self.hooks = pipeline, max(1, int(batch_size)), list(hooks)
         self.accumulator = PredictionAccumulator(uri)
         self._windows = rolling_windows(file_blocks(waveform, sample_rate, padding, cfg.step),
@@ -297,10 +338,8 @@ class Benchmark:
         progress lines as ``run_single``, files read lazily as slots free up."""
         def feed():      # runs on the FileBatch's loader thread: decode straight into pinned memory
             for fp in paths:
-                padded, sr, padding = read_wav_into(fp, fb.host_buffer, config.get_padding, config.step)
-                if sr != config.sample_rate:
-                    raise ValueError(f"audio source has sample rate {sr}, the pipeline's is "
-                                     f"{config.sample_rate}; resample the file first")
+                padded, _, padding = read_wav_resampled_into(fp, fb.host_buffer, config.get_padding, config.step,
+                                                             config.sample_rate, config.device)
                 yield fp.stem, padded, -padding[0]
 
         got = fb.run(feed())

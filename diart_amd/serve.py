@@ -32,6 +32,7 @@ import torch
 
 from .blocks.aggregation import BatchedOutputTail
 from .features import Annotation
+from .functional import resampler
 from .pipeline import AudioRing, StreamBatch
 
 
@@ -56,11 +57,17 @@ class StreamServer:
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  device: Optional[torch.device] = None, patch_collar: float = 0.05,
                  engine: Optional[Callable] = None, device_rings: bool = True,
-                 normalize_embedding_weights: bool = False):
+                 normalize_embedding_weights: bool = False, input_sample_rate: Optional[int] = None):
         self.duration, self.step_seconds, self.sample_rate = float(duration), float(step), int(sample_rate)
         self.latency = self.step_seconds if latency is None else float(latency)
-        self.chunk_samples = int(round(sample_rate * duration))
-        self.step_samples = int(round(sample_rate * step))
+        # the rate clients push at.  Blocks and windows are cut at this rate; a window at another rate than the
+        # pipeline's is resampled on its own on the device before the models see it (the reference's per-window
+        # blocks.Resample, inference.py:101-122)
+        self.input_sample_rate = self.sample_rate if input_sample_rate is None else int(input_sample_rate)
+        self.model_chunk_samples = int(round(sample_rate * duration))
+        self.chunk_samples = int(round(self.input_sample_rate * duration))
+        self.step_samples = int(round(self.input_sample_rate * step))
+        self.resampler = None
         self.max_streams, self.patch_collar = int(max_streams), patch_collar
         self.blocks_per_window = -(-self.chunk_samples // self.step_samples)
         self._lock = threading.Lock()          # stream table, buffers, slot lists
@@ -79,8 +86,16 @@ class StreamServer:
                                      delta_new, gamma, beta, max_speakers,
                                      normalize_embedding_weights=normalize_embedding_weights, device=device, tail=True,
                                      duration=duration, step=step, latency=self.latency)
-            self._dev = torch.empty((self.max_streams, self.chunk_samples), dtype=torch.float32,
+            self._dev = torch.empty((self.max_streams, self.model_chunk_samples), dtype=torch.float32,
                                     device=self.batch.device)
+            # resampling: windows at the input rate land in _raw, their resampled rows in _dev
+            if self.input_sample_rate != self.sample_rate:
+                self.resampler = resampler(self.input_sample_rate, self.sample_rate, self.batch.device)
+                if self.resampler.out_len(self.chunk_samples) != self.model_chunk_samples:
+                    raise ValueError(f"a {duration} s window at {self.input_sample_rate} Hz resamples to "
+                                     f"{self.resampler.out_len(self.chunk_samples)} samples, not {self.model_chunk_samples}")
+                self._raw = torch.empty((self.max_streams, self.chunk_samples), dtype=torch.float32,
+                                        device=self.batch.device)
             self._engine, self._reset_slot = self._gpu_engine, self.batch.reset
             # per-stream device rings need whole blocks per window (and 16-byte aligned rows)
             self.rings: Optional[AudioRing] = None
@@ -96,6 +111,10 @@ class StreamServer:
         else:
             self.batch, self.rings = None, None
             self._engine, self._reset_slot = engine, getattr(engine, "reset", lambda slot: None)
+            if self.input_sample_rate != self.sample_rate:
+                # a custom engine gets its windows at the pipeline's rate, each resampled on its own (GPU)
+                self.resampler = resampler(self.input_sample_rate, self.sample_rate, device)
+                self._engine = self._resampling_engine(engine)
 
     # ------------------------------------------------------------------ stream life cycle
     def open(self, stream_id: Hashable) -> None:
@@ -222,7 +241,7 @@ class StreamServer:
                 if self.rings is None:
                     turns = self._engine(np.stack([w for _, _, w, _ in work]), starts, slots)
                 else:
-                    turns = self._gpu_engine(self.rings.gather(slots, self._dev), starts, slots)
+                    turns = self._gpu_engine(self.rings.gather(slots, self._window_buffer()), starts, slots)
             except BaseException as exc:
                 self._roll_back(undo, pushed, exc)
                 raise
@@ -313,6 +332,16 @@ class StreamServer:
     def shutdown(self) -> None:
         self._stop = True
 
+    def _window_buffer(self) -> torch.Tensor:
+        """Device rows the windows are assembled in, at the input rate."""
+        return self._dev if self.resampler is None else self._raw
+
+    def _resampling_engine(self, engine: Callable) -> Callable:
+        def run(windows, starts, slots):
+            x = torch.from_numpy(np.ascontiguousarray(windows, dtype=np.float32))
+            return engine(self.resampler(x).numpy(), starts, slots)
+        return run
+
     # ------------------------------------------------------------------ GPU engine
     def _gpu_engine(self, windows, starts: np.ndarray, slots: List[int]):
         """``windows``: (k, S) on the host (uploaded whole, like the reference) or already a device
@@ -320,7 +349,10 @@ class StreamServer:
         k = windows.shape[0]
         if not torch.is_tensor(windows):
             self._pinned[:k].copy_(torch.from_numpy(windows))
-            self._dev[:k].copy_(self._pinned[:k], non_blocking=True)
+            self._window_buffer()[:k].copy_(self._pinned[:k], non_blocking=True)
+        if self.resampler is not None:
+            with torch.cuda.device(self._dev.device):
+                self.resampler.rows(self._raw[:k], self._dev[:k])
         ticket = self.batch.launch(self._dev[:k], starts, slots=slots)
         self.batch.finish(ticket, want_scores=False)
         _, _, _, _, turns, nturns = ticket["tail"]

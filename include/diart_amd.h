@@ -362,6 +362,27 @@ int dz_sbx_forward_groups(dz_sbx* m, const float* d_wave, long long wave_stride,
 int dz_sbx_peek(dz_sbx* m, int which, const void** d_ptr, long long* count, int* frames);
 int dz_sbx_destroy(dz_sbx* m);
 
+/* ---- band-limited resampling: torchaudio's sinc_interp_hann (lowpass_filter_width 6, rolloff 0.99), the filter
+ * built in float64 and rounded to float32.  g = gcd(orig, new), o = orig / g, n = new / g, width =
+ * ceil(6 o / (0.99 min(o, n))), T = 2 width + o taps per phase; output m = j n + i is sum_k h[i][k] x[j o - width + k]
+ * (x = 0 outside the row), ceil(n L / o) outputs for L inputs.  Each output is one fused-multiply-add chain over
+ * its T taps in ascending k: a row's outputs do not depend on the batch it comes in.  Ratios whose table exceeds
+ * 16 MiB and rates <= 0 are refused (return 2).  Equal rates: the input unchanged.                           */
+typedef struct dz_resample dz_resample;
+/* host only: phases n, taps T, width and input step o of orig -> new                                           */
+int dz_resample_geometry(int orig_freq, int new_freq, int* phases, int* taps, int* width, int* in_step);
+/* host only: output length for in_len input samples (in_len at equal rates); -1 on bad rates or overflow       */
+long long dz_resample_out_len(int orig_freq, int new_freq, long long in_len);
+/* host only: the float32 filter table, phase-major [n][T]                                                      */
+int dz_resample_table(int orig_freq, int new_freq, float* out);
+/* uploads the table to the context's GPU                                                                       */
+int dz_resample_create(dz_ctx* ctx, int orig_freq, int new_freq, dz_resample** out);
+/* rows signals of in_len samples (d_in + r * in_stride) -> d_out + r * out_stride, dz_resample_out_len samples
+ * each.  Enqueued on `stream`; no synchronisation, no allocation.                                               */
+int dz_resample_forward(dz_resample* m, const float* d_in, long long in_stride, long long in_len, int rows,
+                        float* d_out, long long out_stride, void* stream);
+int dz_resample_destroy(dz_resample* m);
+
 /* ---- OverlappedSpeechPenalty: functional.py:6-13 + blocks/embedding.py:98-107
  * d_seg (B,F,K) -> weights.  speaker_major=0: (B,F,K) like the reference block;
  * speaker_major=1: (B,K,F), the layout dz_emb_forward_multi consumes.           */
