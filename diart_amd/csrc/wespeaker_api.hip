@@ -194,6 +194,23 @@ extern "C" int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wa
     return wsp_head(m, batch, num_speakers, d_weights, weight_frames, normalize, d_out, st);
 }
 
+// kernel-level entry point of k_conv2d.hip (parity tests): the launcher checks the operands
+extern "C" int dz_k_conv2d(dz_ctx* ctx, const float* d_x, const float* d_w, const void* d_wsplit, const float* d_bias,
+                           const float* d_r, float* d_y, int batch, int fi, int ti, int cin, int cout, int taps,
+                           int stride, int relu, void* stream) {
+    DZ_REQUIRE(ctx != nullptr, "dz_k_conv2d: NULL context");
+    DZ_HIP(hipSetDevice(ctx->device));
+    DzRangeScope range_scope(ctx->oflag_dev);
+    DzConv2d p;
+    memset(&p, 0, sizeof(p));
+    p.X = d_x; p.W = d_w; p.Wsplit = d_wsplit; p.bias = d_bias; p.R = d_r; p.Y = d_y;
+    p.B = batch; p.Fi = fi; p.Ti = ti; p.Cin = cin; p.Cout = cout; p.taps = taps; p.stride = stride; p.relu = relu;
+    // (a stride outside 1 / 2 is refused by the launcher before it reads Fo / To)
+    p.Fo = stride >= 1 ? (fi - 1) / stride + 1 : 0;
+    p.To = stride >= 1 ? (ti - 1) / stride + 1 : 0;
+    return dz_launch_conv2d(p, (hipStream_t)stream);
+}
+
 extern "C" int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames) {
     DZ_REQUIRE(m && d_ptr && count, "dz_wsp_peek: NULL argument");
     const long long N = m->lastN;
@@ -208,6 +225,7 @@ extern "C" int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* 
             break;
         }
         case 6: *d_ptr = m->pooled; T = m->T[4]; *count = (long long)m->lastRows * POOLED; break;
+        case 7: *d_ptr = m->raw; T = m->T[0]; *count = N * NMEL * T; break;
         default:
             dz_set_error("dz_wsp_peek: unknown buffer %d", which);
             return 2;

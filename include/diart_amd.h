@@ -315,9 +315,17 @@ int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wave_stride, 
                          int num_speakers, int weight_frames, int normalize, float* d_out, void* stream);
 /* device pointer + element count of an intermediate of the LAST forward (parity tests); *frames receives the
  * buffer's time axis:  0 fbank (N,80,T) after the mean subtraction  1 conv1 (N,80,T,32)  2 .. 5 layer 1 .. 4
- * (N,F,T_l,C_l)  6 pooled statistics (rows, 5120)                                                          */
+ * (N,F,T_l,C_l)  6 pooled statistics (rows, 5120)  7 fbank (N,80,T) before the mean subtraction             */
 int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames);
 int dz_wsp_destroy(dz_wsp* m);
+/* one 2-D convolution of the trunk alone (k_conv2d.hip; parity tests): channels-last d_x [batch][fi][ti][cin] ->
+ * d_y [batch][fo][to][cout], fo = (fi - 1) / stride + 1, to likewise; taps 9 = 3x3 with zero padding 1, taps 1 = 1x1
+ * without; d_w / d_wsplit as dz_wsp_conv (d_wsplit set: split-f16 matrix cores); epilogue + d_bias[n], + d_r[m][n]
+ * when d_r is set, ReLU when relu.  cin % 32 == 0, cout 32, 64 or a multiple of 128, stride 1 or 2; an operand of
+ * the split path outside +-65504 raises the context's range flag (dz_range_check)                        */
+int dz_k_conv2d(dz_ctx* ctx, const float* d_x, const float* d_w, const void* d_wsplit, const float* d_bias,
+                const float* d_r, float* d_y, int batch, int fi, int ti, int cin, int cout, int taps, int stride,
+                int relu, void* stream);
 
 /* ---- speechbrain x-vector embedding (speechbrain/spkrec-xvect-voxceleb) behind pyannote's
  * PretrainedSpeakerEmbedding contract, like ECAPA: waveform (N,1,S), masks (N,Fw) or NULL -> (N,512).

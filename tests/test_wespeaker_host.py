@@ -118,7 +118,7 @@ def test_odd_frames_at_every_stage_exist():
 def test_abi_symbols_and_struct_size():
     lib = C.CDLL(str(_lib.lib_path()))
     for n in ("dz_wsp_abi_size", "dz_wsp_frames_for", "dz_wsp_create", "dz_wsp_forward", "dz_wsp_forward_multi",
-              "dz_wsp_peek", "dz_wsp_destroy"):
+              "dz_wsp_peek", "dz_wsp_destroy", "dz_k_conv2d"):
         assert hasattr(lib, n), n
         assert n in _lib.SIGNATURES, n
     assert _lib.load().dz_wsp_abi_size() == C.sizeof(_lib.WspWeights) == 8 + 24 + 16 * 3 * 24 + 16
@@ -132,3 +132,83 @@ def test_stream_batch_refuses_wespeaker():
     emb = models.HipWeSpeakerEmbedding(synth_wespeaker_state())
     with pytest.raises(ValueError, match="HipEmbedding.*HipEcapaEmbedding"):
         StreamBatch(seg, emb, 2)
+
+
+# --------------------------------------------------------------------------- #
+# the GPU tests' own references, checked on the CPU
+# --------------------------------------------------------------------------- #
+def test_conv_restatement_equals_conv2d_in_float64():
+    """tests/test_gpu_conv2d.py's implicit GEMM (im2col rows in the kernels' k order times the test's own matrix, then
+    bias, residual, ReLU) is F.conv2d in float64 on every geometry the GPU test runs."""
+    from test_gpu_conv2d import CASES, EPI, _operands
+    for case in CASES:
+        B, Fi, Ti, cin, cout, taps, stride, epi = case
+        x, w4, m, b, r = _operands(case)
+        want, scale = R.conv_ref(x, w4, b, r, EPI[epi][1], stride)
+        y = R.im2col(x.double(), taps, stride) @ m.double().t() + b.double()
+        if r is not None:
+            y = y + r.double()
+        if EPI[epi][1]:
+            y = F.relu(y)
+        assert y.shape == want.shape, case
+        assert ((y - want).abs() / scale).max().item() < 1e-13, case
+
+
+def test_single_frame_pooling_denominator_is_negative_in_float32():
+    """pyannote.audio 3.1's StatsPool with one non-zero weight w: v1 = w + 1e-8, var = 0 / (v1 - w^2 / v1 + 1e-8).  In
+    float64 the denominator is 1e-8 + O(1e-16) > 0; in float32 w + 1e-8 rounds to w (for w > ~0.17) and w^2 / w may
+    round to w plus one ulp: the denominator is then 1e-8 - ulp(w) < 0 and sqrt gives NaN.  This happens for a few
+    percent of w; w = 1.0 (min-max normalised) is exact and gives std 0."""
+    w = torch.linspace(0.01, 1.0, 100000, dtype=torch.float32)
+    v1 = w + 1e-8
+    den = v1 - w * w / v1 + 1e-8
+    neg = den < 0
+    frac = neg.float().mean().item()
+    assert 0.005 < frac < 0.1, frac
+    w64 = w[neg].double()
+    v64 = w64 + 1e-8
+    assert (v64 - w64 * w64 / v64 + 1e-8 > 0).all()                    # float64: positive wherever float32 is negative
+    one = torch.tensor([1.0])
+    v1 = one + 1e-8
+    assert v1.item() == 1.0 and (v1 - one * one / v1 + 1e-8).item() > 0
+
+
+def test_gates_see_planted_mistakes():
+    """Each of three mistakes moves the float64 reference past the new gates: a periodic Hamming window (/ 400 instead of
+    / 399), the split-f16 cross products without their 2^-11, and the time padding shifted by one column."""
+    from test_gpu_conv2d import CASES, EPI, GATE, _operands
+    from test_gpu_wespeaker import ROW_GATES, case_inputs, rel
+    fb_gate = max(g["fbank"] for g in ROW_GATES.values())
+    # 1. window: the power-domain fbank measure, per row, on the stage test's 2 s rows
+    x, _ = case_inputs(32000, 293)
+    want, scale = R.fbank_raw(x)
+    bad, _ = R.fbank_raw(x, window_div=400)
+    err = ((bad.exp() - want.exp()).abs() / scale[..., None]).reshape(x.shape[0], -1).amax(dim=1)
+    old = rel(R.fbank(x, window_div=400), R.fbank(x))
+    print(f"periodic window: fbank {err.min().item():.2e} (gate {fb_gate:.1e}); old whole-tensor rel L2 {old:.2e}")
+    assert err.min().item() > fb_gate
+    c_gate = max(GATE.values())
+    for case in CASES[:4] + CASES[-4:]:
+        B, Fi, Ti, cin, cout, taps, stride, epi = case
+        xs, w4, m, b, r = _operands(case)
+        relu = EPI[epi][1]
+        want, scale = R.conv_ref(xs, w4, b, r, relu, stride)
+
+        def finish(y):
+            y = y + b.double() + (r.double() if r is not None else 0.0)
+            return F.relu(y) if relu else y
+        cols = R.im2col(xs.double(), taps, stride)
+        # 2. the (lo hi + hi lo) products added without their 2^-11
+        xh = cols.float().half().double()
+        xl = ((cols.float() - xh.float()) * 2048).half().double()
+        wp = R.split_planes(m).view(torch.float16).double()
+        y = finish(xh @ wp[0].t() + (xl @ wp[0].t() + xh @ wp[1].t()))
+        e2 = ((y - want).abs() / scale).max().item()
+        o2 = rel(y, want)
+        # 3. the time padding one column to the right (3x3 only)
+        e3 = o3 = float("inf")
+        if taps == 9:
+            y = finish(R.im2col(xs.double(), taps, stride, tpad=(0, 2)) @ m.double().t())
+            e3, o3 = ((y - want).abs() / scale).max().item(), rel(y, want)
+        print(f"{case}: no 2^-11 {e2:.2e} (old {o2:.2e}); shifted padding {e3:.2e} (old {o3:.2e})")
+        assert e2 > c_gate and e3 > c_gate, case
