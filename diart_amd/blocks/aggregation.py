@@ -199,10 +199,14 @@ class BatchedOutputTail:
         return self._agg, self._rows, self._t0, self._res, self._turns, self._nturns
 
     @staticmethod
-    def annotation(turns: np.ndarray, nturns: int, uri=None, shift: float = 0.0):
-        """Speech turns of one stream as the ``Annotation`` ``Binarize`` builds (utils.py:47-58)."""
+    def annotation(turns: np.ndarray, nturns: int, uri=None, shift: float = 0.0, label: Optional[str] = None):
+        """Speech turns of one stream as the ``Annotation`` ``Binarize`` builds (utils.py:47-58); ``label``: one label
+        for every turn (``"speech"``: VoiceActivityDetection, vad.py:183-189) instead of ``speaker{g}``."""
         from ..features import Annotation
         ann = Annotation(uri=uri, modality="speech")
-        for s, e, g in turns[:nturns]:
-            ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
+        for n, (s, e, g) in enumerate(turns[:nturns]):
+            if label is None:
+                ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
+            else:                       # one track per turn, like Timeline.to_annotation
+                ann[Segment(s + shift, e + shift), n] = label
         return ann

@@ -531,7 +531,8 @@ extern "C" int dz_seg_destroy(dz_seg* seg) {
 // phase 0: the whole network on one stream; 1: front half (SincNet + the first x-projection into gx0);
 // 2: back half (4 recurrences, projections 1..3, MLP head) of the chunks the last front half left
 static int seg_forward(dz_seg* s, const float* d_wave, long long wave_stride, int B, float* d_out,
-                       float* d_osp, float gamma, float beta, int normalize, void* stream, int phase = 0);
+                       float* d_osp, float gamma, float beta, int normalize, void* stream, int phase = 0,
+                       float* d_vad = nullptr);
 static bool mlp_head_enabled() {
     static const bool on = [] {
         const char* e = dz_exp_env("DZ_MLP_HEAD");
@@ -549,6 +550,18 @@ extern "C" int dz_seg_forward_osp(dz_seg* s, const float* d_wave, long long wave
     DZ_REQUIRE(d_weights != nullptr, "dz_seg_forward_osp: d_weights is NULL");
     return seg_forward(s, d_wave, wave_stride, B, d_out, d_weights, gamma, beta, normalize, stream);
 }
+// VoiceActivityDetection's hot path (reference blocks/vad.py:146-148): the forward pass whose head also
+// writes the speech track d_vad (B,F), the max over speakers of d_out (B,F,K) (dz_vad_frame), so that the
+// engine's step never reads the scores back for the reduction
+extern "C" int dz_seg_forward_vad(dz_seg* s, const float* d_wave, long long wave_stride, int B, float* d_out,
+                                  float* d_vad, void* stream) {
+    DZ_REQUIRE(d_out && d_vad, "dz_seg_forward_vad: NULL output");
+    DZ_REQUIRE(B >= 1, "dz_seg_forward_vad: batch %d < 1", B);
+    DZ_REQUIRE(wave_stride >= 0, "dz_seg_forward_vad: negative stride %lld", wave_stride);
+    DZ_REQUIRE(s != nullptr, "dz_seg_forward_vad: NULL handle");
+    DZ_REQUIRE(B <= s->Bm, "dz_seg_forward_vad: batch %d outside [1, %d]", B, s->Bm);
+    return seg_forward(s, d_wave, wave_stride, B, d_out, nullptr, 0.f, 0.f, 0, stream, 0, d_vad);
+}
 // The two halves of dz_seg_forward_osp for a caller that keeps the stateless front end of the NEXT step
 // off the long dependent chain of this one (StreamBatch): dz_seg_front(t + 2) — SincNet and the first
 // x-projection, on a stream of its own — runs under the recurrences of dz_seg_back(t) on the same handle.
@@ -565,7 +578,7 @@ extern "C" int dz_seg_back(dz_seg* s, int B, float* d_out, float gamma, float be
     return seg_forward(s, nullptr, 0, B, d_out, d_weights, gamma, beta, normalize, stream, 2);
 }
 static int seg_forward(dz_seg* s, const float* d_wave, long long wave_stride, int B, float* d_out,
-                       float* d_osp, float gamma, float beta, int normalize, void* stream, int phase) {
+                       float* d_osp, float gamma, float beta, int normalize, void* stream, int phase, float* d_vad) {
     DZ_REQUIRE(s && (d_out || phase == 1), "dz_seg_forward: NULL argument");
     DZ_REQUIRE(B >= 1 && B <= s->Bm, "dz_seg_forward: batch %d outside [1, %d]", B, s->Bm);
     int rc;
@@ -670,7 +683,7 @@ static int seg_forward(dz_seg* s, const float* d_wave, long long wave_stride, in
         m.W0split = s->w.lin0_split; m.W1split = s->w.lin1_split;
         m.b0 = s->w.lin0_b; m.b1 = s->w.lin1_b; m.cw = s->w.cls_w; m.cb = s->w.cls_b;
         m.rows = B * F; m.F = F; m.classes = s->w.num_classes; m.K = s->w.num_speakers; m.powerset = s->w.powerset;
-        m.gamma = gamma; m.beta = beta; m.seg = d_out; m.wout = d_osp;
+        m.gamma = gamma; m.beta = beta; m.seg = d_out; m.wout = d_osp; m.vad = d_vad;
         m.wave_mom = s->cur_stats;        // (split-f16 path: its clamps turn NaN into finite values)
         ProfScope ps(T_MLP, B);
         return dz_launch_mlp_head(m, st);
@@ -694,7 +707,8 @@ static int seg_forward(dz_seg* s, const float* d_wave, long long wave_stride, in
     // classifier + sigmoid / powerset decision (+ OverlappedSpeechPenalty weights): one launch
     ProfScope ps(T_CLS, B);
     return dz_launch_seg_head(s->m1, s->w.cls_w, s->w.cls_b, B, F, s->w.num_classes, s->w.num_speakers,
-                              s->w.powerset, d_out, gamma, beta, normalize, d_osp, st, s->pre ? s->cur_stats : nullptr);
+                              s->w.powerset, d_out, gamma, beta, normalize, d_osp, st, s->pre ? s->cur_stats : nullptr,
+                              d_vad);
 }
 
 // ---------------------------------------------------------------------------

@@ -445,6 +445,14 @@ __device__ __forceinline__ void dz_seg_decide(const float* lg, int classes, int 
         for (int k = 0; k < K; ++k) s[k] = 1.f / (1.f + expf(-lg[k]));
     }
 }
+// dz_vad_frame: the VoiceActivityDetection speech track of one frame, torch.max over the K speakers
+// (reference blocks/vad.py:146-148): NaN when any of them is NaN, as torch.max propagates it (fmaxf /
+// v_max_f32 would return the other operand)
+__device__ __forceinline__ float dz_vad_frame(const float* s, int K) {
+    float m = s[0];
+    for (int k = 1; k < K; ++k) m = (s[k] > m || s[k] != s[k]) ? s[k] : m;
+    return m;
+}
 __device__ __forceinline__ void dz_osp_frame(const float* s, int K, float gamma, float beta, float* w) {
     float e[8], m = -INFINITY;
     for (int k = 0; k < K; ++k) m = fmaxf(m, beta * s[k]);
@@ -461,9 +469,10 @@ __device__ __forceinline__ void dz_osp_frame(const float* s, int K, float gamma,
     }
 }
 
+// vad (optional): [B][F] speech track, dz_vad_frame of every frame's seg row
 int dz_launch_seg_head(const float* m1, const float* cw, const float* cb, int B, int F, int classes, int K,
                        int powerset, float* seg, float gamma, float beta, int normalize, float* wout,
-                       hipStream_t st, const float* wave_mom = nullptr);
+                       hipStream_t st, const float* wave_mom = nullptr, float* vad = nullptr);
 // lin0 (256 -> 128, LeakyReLU) -> lin1 (128 -> 128, LeakyReLU) -> classifier -> activation (-> OSP
 // weights, not normalised) in one launch: k_mlp_head.hip
 struct DzMlpHead {
@@ -477,6 +486,7 @@ struct DzMlpHead {
     float* wout;               // [rows / F][K][F] or NULL
     int* oflag;
     const float* wave_mom;     // wave_stats moments of the rows' chunks, or NULL: chunks with non-finite ones get NaN rows (dz_ws_bad)
+    float* vad;                // [rows] speech track (dz_vad_frame of each seg row) or NULL
 };
 int dz_launch_mlp_head(const DzMlpHead& p, hipStream_t st);
 int dz_launch_l2norm(float* x, int rows, int dim, float norm, hipStream_t st);

@@ -7,7 +7,8 @@
 //     -> lin0: 256 -> 128, LeakyReLU      f16x3 MFMA, operands by LDS-DMA (as k_gemm_pre.hip)
 //     -> lin1: 128 -> 128, LeakyReLU      f16x3 MFMA, A = lin0's tile re-split INTO LDS, B by LDS-DMA
 //     -> classifier 128 -> classes        f32 FMA chain per frame (the order of seg_head_kernel)
-//     -> sigmoid | powerset decision -> seg; OSP weights (not normalised) -> wout
+//     -> sigmoid | powerset decision -> seg; OSP weights (not normalised) -> wout; speech track
+//        (max over speakers, VoiceActivityDetection) -> vad
 //
 // It replaces three launches (two k_gemm_pre.hip GEMMs + seg_head_kernel) and the 2 x 9.6 MB round
 // trip of the hidden activations; the arithmetic per output is the same as theirs, statement by
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(256) void mlp_head_kernel(DzMlpHead p) {
         if (p.wave_mom && dz_ws_bad(p.wave_mom, b))          // a window with NaN / Inf samples: NaN rows, like the reference
             for (int k = 0; k < p.K; ++k) s[k] = __builtin_nanf("");
         for (int k = 0; k < p.K; ++k) p.seg[(long long)t * p.K + k] = s[k];
+        if (p.vad) p.vad[t] = dz_vad_frame(s, p.K);
         if (p.wout) {
             float wv[8];
             dz_osp_frame(s, p.K, p.gamma, p.beta, wv);

@@ -207,7 +207,8 @@ __global__ __launch_bounds__(256) void osp_kernel(const float* __restrict__ seg,
 // layout the pooling kernel reads.  One workgroup per chunk, thread = frame: the chunk's rows of the
 // MLP output (F x 128 f32) are staged through LDS in slices (coalesced loads, conflict-free row
 // reads at a 129-float pitch), the 128 x classes weights are wave-uniform scalar loads.  The OSP part
-// is the arithmetic of osp_kernel above, statement by statement.
+// is the arithmetic of osp_kernel above, statement by statement.  `vad` (optional) gets the speech
+// track of VoiceActivityDetection, the max over speakers of each frame (dz_vad_frame).
 // ---------------------------------------------------------------------------
 constexpr int SH_ROWS = 64;          // frames per LDS slice
 constexpr int SH_PITCH = 129;
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(256) void seg_head_kernel(const float* __restrict__
                                                        const float* __restrict__ cb, int F, int classes, int K,
                                                        int powerset, float* __restrict__ seg, float gamma,
                                                        float beta, int normalize, float* __restrict__ wout,
-                                                       const float* __restrict__ wave_mom) {
+                                                       const float* __restrict__ wave_mom, float* __restrict__ vad) {
     extern __shared__ float hbuf[];   // [SH_ROWS][SH_PITCH] slice | [F][K] weights | [2][K] min / max
     float* xs = hbuf;
     float* wbuf = hbuf + SH_ROWS * SH_PITCH;
@@ -249,6 +250,7 @@ __global__ __launch_bounds__(256) void seg_head_kernel(const float* __restrict__
                 for (int k = 0; k < K; ++k) s[k] = __builtin_nanf("");
             const int f = f0 + tid;
             for (int k = 0; k < K; ++k) sb[f * K + k] = s[k];
+            if (vad) vad[(long long)b * F + f] = dz_vad_frame(s, K);
             if (wout) {
                 float wv[8];
                 dz_osp_frame(s, K, gamma, beta, wv);
@@ -503,13 +505,13 @@ int dz_launch_osp(const float* seg, int B, int F, int K, float gamma, float beta
 // [B][K][F] OSP weights
 int dz_launch_seg_head(const float* m1, const float* cw, const float* cb, int B, int F, int classes, int K,
                        int powerset, float* seg, float gamma, float beta, int normalize, float* wout,
-                       hipStream_t st, const float* wave_mom) {
+                       hipStream_t st, const float* wave_mom, float* vad) {
     DZ_REQUIRE(classes >= 1 && classes <= 8 && K >= 1 && K <= 8 && (powerset || K == classes),
                "seg_head: classes %d / speakers %d", classes, K);
     const size_t lds = sizeof(float) * ((size_t)SH_ROWS * SH_PITCH + (size_t)F * K + 2 * K);
     DZ_REQUIRE(lds <= 64 * 1024, "seg_head: %d frames x %d speakers do not fit in LDS", F, K);
     DZ_LAUNCH(seg_head_kernel, dim3(B), dim3(256), lds, st, m1, cw, cb, F, classes, K, powerset, seg, gamma,
-              beta, normalize, wout, wave_mom);
+              beta, normalize, wout, wave_mom, vad);
     DZ_HIP(hipGetLastError());
     return 0;
 }

@@ -205,6 +205,28 @@ class HipSegmentation(_HipModule):
                    "dz_seg_forward")
         return out
 
+    def forward_vad(self, waveform: torch.Tensor, return_scores: bool = False):
+        """VoiceActivityDetection's hot path (reference blocks/vad.py:146-148): ``waveform (B,1,S) -> (B,F,1)``, the
+        max over speakers of ``__call__``'s scores (NaN where a row is NaN), computed by the kernel that writes the
+        scores (``dz_seg_forward_vad``).  ``return_scores``: ``(track, scores (B,F,K))``.  Enqueued on the current
+        stream; does not synchronise."""
+        if self.device is None:
+            self.to(waveform.device)
+        if waveform.device != self.device:
+            waveform = waveform.to(self.device)
+        rows = _as_rows(waveform)
+        B, S = rows.shape
+        if B < 1:
+            raise ValueError("empty batch")
+        handle = self._need(S, B)
+        F = self.num_frames(S)
+        scores = torch.empty((B, F, self.num_speakers), dtype=torch.float32, device=self.device)
+        track = torch.empty((B, F, 1), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().dz_seg_forward_vad(handle, rows.data_ptr(), rows.stride(0) if B > 1 else S, B,
+                                                  scores.data_ptr(), track.data_ptr(), _stream_ptr(self.device)),
+                   "dz_seg_forward_vad")
+        return (track, scores) if return_scores else track
+
 
 class HipEmbedding(_HipModule):
     """pyannote/embedding forward: ``(waveform (N,1,S), weights (N,F) | None) -> (N,512)`` — the

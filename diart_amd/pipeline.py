@@ -26,6 +26,9 @@ waits for the step's segmentation and runs ``dz_ecapa_forward_groups`` over the 
 stream, each stream's rows with their own batch geometry (what the stream's own pipeline computes), then the
 D2H copy.  Nothing in the launch waits for the GPU, so with two lanes the ECAPA network of step t runs under
 the segmentation of step t + 1.
+
+``VadBatch`` is the segmentation-only form for ``VoiceActivityDetection``: no embedding, no clustering; the head kernel
+writes each stream's speech track and only that track reaches the host's output tails.
 """
 from __future__ import annotations
 
@@ -737,6 +740,264 @@ class StreamBatch:
         self.finish(ticket, want_scores=False)
         _, _, _, _, turns, nturns = ticket["tail"]
         return [BatchedOutputTail.annotation(turns[i], int(nturns[i])) for i in range(self.n)]
+
+
+class VadBatch:
+    """``VoiceActivityDetection`` of N concurrent streams, one chunk each per step: the segmentation-only form of the
+    N-stream engine.  Per stream it produces what that stream's own ``VoiceActivityDetection`` (blocks/vad.py,
+    reference ``blocks/vad.py:136-191``) produces: the speech track ``max over speakers`` of the segmentation and the
+    ``"speech"`` turns of the region the step finalises (``DelayedAggregation(hamming, loose)`` + ``Binarize``).
+
+    GPU schedule per step, on the step's lane (one HIP stream):
+
+        dz_wave_stats -> dz_seg_forward_vad (the head kernel writes the (N,F) track beside the scores)
+                      -> dz_results_to_host (the track only) -> `done`
+        host          : aggregation + binarisation of step t-1 (C++ threads, fp64) while the GPU runs step t
+
+    No embedding network and no clustering: the step is the segmentation chain alone.  The engine choices are
+    ``StreamBatch``'s (``lanes``, ``recurrence``, ``inflight``, ``wait``, ``warmup``, ``DZ_ENGINE``): with >= 64
+    streams in the default precision the matrix-core recurrence on ``THROUGHPUT_LANES`` lanes.  ``host_threads``:
+    threads of the output tail."""
+
+    def __init__(self, segmentation: HipSegmentation, num_streams: int, tau_active: float = 0.6,
+                 duration: float = 5.0, step: float = 0.5, latency: Optional[float] = None,
+                 device: Optional[torch.device] = None, *, lanes: Optional[int] = None,
+                 recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
+                 warmup: Optional[int] = None, host_threads: int = 8, serial: bool = False):
+        from .blocks.diarization import _latency
+        from .config import setting
+        from .hostinfo import usable_cores
+        if serial:
+            raise ValueError("VadBatch: serial=True is the measurement engine of StreamBatch (bench.py's roofline "
+                             "pass); the VAD engine has no serial form")
+        for name in ("DZ_SEG_FRONT", "DZ_SHARED_EMB", "DZ_CONV0_PAIR"):
+            if _lib.exp_env(name, "0") != "0":
+                raise ValueError(f"VadBatch: {name} is an experiment of the x-vector engine; it has no meaning here")
+        if _lib.exp_env("DZ_ABLATE", ""):
+            raise ValueError("VadBatch: DZ_ABLATE is an experiment of the x-vector engine; it has no meaning here")
+        self.duration, self.step = float(duration), float(step)
+        self.latency = float(_latency(latency, self.step, self.duration))
+        if not self.step <= self.latency <= self.duration:
+            raise ValueError(f"VadBatch: latency should be in the range [{self.step}, {self.duration}], "
+                             f"got {self.latency}")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.seg = segmentation.to(self.device)
+        self.device = self.seg.device
+        self.n, self.tau_active, self.host_threads = int(num_streams), float(tau_active), max(1, int(host_threads))
+        # the engine StreamBatch would pick for these streams (see there): a throughput engine at >= 64 streams in
+        # the default precision runs the matrix-core recurrence on THROUGHPUT_LANES lanes
+        rec = setting("recurrence", recurrence, None)
+        split = getattr(self.seg, "precision", "f32") == "f16x3"
+        self.throughput = self.n >= 64 and rec is None and split and getattr(self.seg, "recurrence", "valu") == "valu"
+        self.recurrence = self.seg.throughput_recurrence() if self.throughput else (str(rec) if rec is not None and split else None)
+        many = self.throughput or (self.recurrence not in (None, "valu") and self.n >= 64)
+        self.depth = max(1, int(setting("lanes", lanes, THROUGHPUT_LANES if many else 2, int)))
+        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + (2 if many else 1), int)))
+        self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
+        try:
+            ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
+        except ValueError:
+            ranks_here = 1
+        self.cores_per_rank = usable_cores() / ranks_here
+        mode = str(setting("wait", wait, "auto"))
+        if mode not in ("auto", "spin", "block"):
+            raise ValueError(f"VadBatch: wait={mode!r} (expected auto | spin | block)")
+        self.blocking_wait = mode == "block" or (mode == "auto" and self.cores_per_rank < 4)
+        _lib.load().dz_host_pool_set_spin(0 if self.cores_per_rank < 4 else 40)
+        # the segmentation chain is the whole step: its streams get the high priority, as in StreamBatch
+        pa = int(_lib.exp_env("DZ_PRIO_A", "-1"))
+        self.lanes = [torch.cuda.Stream(self.device, priority=pa) for _ in range(self.depth)]
+        self.tail: Optional[BatchedOutputTail] = None
+        self._t = 0
+        self._steps = np.zeros(self.n, dtype=np.int64)
+        self.host_seconds = {"wait": 0.0, "work": 0.0}
+        self._sub: dict = {}
+        self._slots: List[dict] = []
+        self._warmed: set = set()
+        self._warming, self._real_launches = False, 0
+        self._lib = _lib.load()
+        self._ctx = _lib.context(self.device.index)
+
+    def set_host_threads(self, n: int) -> int:
+        """Host threads of the output tail (aggregation + binarisation) from now on."""
+        self.host_threads = max(1, int(n))
+        if self.tail is not None:
+            self.tail.num_threads = self.host_threads
+        return self.host_threads
+
+    def reset(self, slot: Optional[int] = None):
+        """Forget the aggregation state of every stream, or of one slot."""
+        if self.tail is not None:
+            self.tail.reset(slot)
+        if slot is None:
+            self._steps[:] = 0
+        else:
+            self._steps[slot] = 0
+
+    # ------------------------------------------------------------------ GPU half
+    def _handle(self, S: int, lane: int):
+        h = self._sub.get((S, lane))
+        if h is None:
+            h = self._sub[(S, lane)] = self.seg._create(S, self.n, throughput=self.throughput,
+                                                        recurrence=None if self.throughput else self.recurrence)
+        return h
+
+    def __del__(self):
+        try:
+            for h in self._sub.values():
+                self.seg._destroy(h)
+        except Exception:
+            pass
+
+    def _new_slot(self, F: int) -> dict:
+        n, dev, K = self.n, self.device, self.seg.num_speakers
+        s = dict(F=F, busy=False,
+                 seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
+                 vad=torch.empty((n, F), dtype=torch.float32, device=dev),
+                 stats=torch.empty((n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=dev),
+                 vad_h=torch.empty((n, F), dtype=torch.float32).pin_memory(),
+                 ev_in=torch.cuda.Event(), done=torch.cuda.Event(blocking=self.blocking_wait))
+        self._slots.append(s)
+        return s
+
+    def launch(self, waves, starts=None, slots: Optional[Sequence[int]] = None) -> dict:
+        """Enqueue the GPU work of one step; ``waves``, ``starts`` and ``slots`` as in ``StreamBatch.launch``.
+        Returns a ticket for ``finish``; does not wait for the GPU."""
+        ring = waves if isinstance(waves, AudioRing) else None
+        if ring is not None:
+            assert ring.filled == ring.window, "the ring does not hold a complete window yet"
+            rows, N, S = None, ring.n, ring.window
+            base, stride = ring.raw()
+        else:
+            rows = _as_rows(waves)
+            N, S = rows.shape
+            base, stride = rows.data_ptr(), (rows.stride(0) if N > 1 else S)
+        if slots is None:
+            assert N == self.n, f"expected {self.n} streams, got {N}"
+        else:
+            slots = [int(i) for i in slots]
+            assert N == len(slots) and 1 <= N <= self.n and len(set(slots)) == N, "bad slots"
+            assert all(0 <= i < self.n for i in slots), "slot out of range"
+        slot = self._launch_rows(base, stride, N, S, rows, ring)
+        slot["slots"] = slots
+        idx = np.arange(self.n) if slots is None else np.asarray(slots, dtype=np.int64)
+        slot["starts"] = self._steps[idx] * self.step if starts is None else starts
+        self._steps[idx] += 1
+        return slot
+
+    def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
+        assert 1 <= N <= self.n
+        F = self.seg.num_frames(S)
+        if (S, 0) not in self._sub:
+            # every lane's arena and the output tail's host state before the first kernel of this window size
+            # (allocations while kernels run stall the queues: StreamBatch._launch_rows)
+            for ln in range(self.depth):
+                self._handle(S, ln)
+            if self.tail is None:
+                self.tail = BatchedOutputTail(self.n, F, 1, self.step, self.latency, self.tau_active,
+                                              strategy="hamming", cropping_mode="loose", num_threads=self.host_threads)
+        if not any(s["F"] == F for s in self._slots):
+            for _ in range(self.max_inflight):
+                self._new_slot(F)
+        if S not in self._warmed:
+            self._warmed.add(S)
+            self._warm_up(S)
+        if not self._warming:
+            self._real_launches += 1
+        lane = self._t % self.depth
+        a, h = self.lanes[lane], self._handle(S, lane)
+        slot = next((s for s in self._slots if not s["busy"] and s["F"] == F), None) or self._new_slot(F)
+        slot["busy"] = True
+        lib = self._lib
+        slot["ev_in"].record(torch.cuda.current_stream(self.device))      # inputs produced on the caller's stream
+        a.wait_event(slot["ev_in"])
+        stats = slot["stats"]
+        _lib.check(lib.dz_wave_stats(self._ctx, base, stride, N, S, stats.data_ptr(), a.cuda_stream), "dz_wave_stats")
+        _lib.check(lib.dz_seg_use_wave_stats(h, stats.data_ptr()), "dz_seg_use_wave_stats")
+        _lib.check(lib.dz_seg_forward_vad(h, base, stride, N, slot["seg"].data_ptr(), slot["vad"].data_ptr(),
+                                          a.cuda_stream), "dz_seg_forward_vad")
+        _lib.check(lib.dz_results_to_host(self._ctx, slot["vad"].data_ptr(), slot["vad_h"].data_ptr(), N * F,
+                                          None, None, 0, a.cuda_stream), "dz_results_to_host")
+        slot["done"].record(a)
+        if ring is not None:                            # pushes `slack` steps from now wait for this forward
+            ring._read_by([a])
+        slot["rows"], slot["slots"], slot["keep"] = N, None, keep
+        self._t += 1
+        return slot
+
+    def _warm_up(self, S: int) -> None:
+        """Steps on silence before the first real one of this window size (StreamBatch._warm_up): complete steps
+        while no launch has been issued for a caller, GPU-only steps afterwards."""
+        steps = self.warmup_steps
+        if steps <= 0:
+            return
+        zeros = torch.zeros((self.n, S), dtype=torch.float32, device=self.device)
+        saved = dict(self.host_seconds)
+        inflight: List[dict] = []
+        t_saved = self._t
+        self._warming = True
+        try:
+            if self._real_launches == 0:
+                for _ in range(steps):
+                    inflight.append(self.launch(zeros))
+                    if len(inflight) >= self.max_inflight:
+                        self.finish(inflight.pop(0))
+                while inflight:
+                    self.finish(inflight.pop(0))
+            else:
+                for _ in range(steps):
+                    inflight.append(self._launch_rows(zeros.data_ptr(), zeros.stride(0), self.n, S, zeros))
+                    if len(inflight) >= self.max_inflight:
+                        t = inflight.pop(0)
+                        self._wait(t)
+                        t["busy"], t["keep"] = False, None
+                for t in inflight:
+                    self._wait(t)
+                    t["busy"], t["keep"] = False, None
+        finally:
+            self._warming = False
+        torch.cuda.synchronize(self.device)
+        if self._real_launches == 0:
+            self.reset()
+            self._t = 0
+        else:
+            self._t = t_saved
+        self.host_seconds.update(saved)
+
+    # ------------------------------------------------------------------ host half
+    def _wait(self, ticket: dict) -> None:
+        t0 = _time.perf_counter()
+        ticket["done"].synchronize()
+        self.host_seconds["wait"] += _time.perf_counter() - t0
+
+    def finish(self, ticket: dict) -> np.ndarray:
+        """Wait for the step's GPU work and run the N output tails -> the speech track (N,F,1) f32; the step's turns
+        are in ``ticket["tail"]`` (``BatchedOutputTail.__call__``'s tuple, indexed by row).  Both are views of
+        buffers that a later ``launch`` / ``finish`` reuses."""
+        self._wait(ticket)
+        t1 = _time.perf_counter()
+        try:
+            # a flagged step (an f16x3 operand out of range) never reaches the streams' state: StreamBatch.finish
+            _lib.range_check(self.device.index)
+            N, slots = ticket["rows"], ticket["slots"]
+            track = ticket["vad_h"].numpy()[:N, :, None]
+            ticket["tail"] = self.tail(track, ticket["starts"], self.duration / track.shape[1], slots=slots)
+        finally:
+            ticket["busy"] = False
+            ticket["keep"] = None
+            self.host_seconds["work"] += _time.perf_counter() - t1
+        return track
+
+    def __call__(self, waves):
+        return self.finish(self.launch(waves))
+
+    def detect(self, waves, starts=None) -> List[Annotation]:
+        """One step of every stream, end to end -> N ``Annotation``: the ``"speech"`` turns of the region this step
+        finalises (what ``VoiceActivityDetection.__call__`` returns per chunk, without the aggregated audio)."""
+        ticket = self.launch(waves, starts)
+        self.finish(ticket)
+        turns, nturns = ticket["tail"][4], ticket["tail"][5]
+        return [BatchedOutputTail.annotation(turns[i], int(nturns[i]), label="speech") for i in range(self.n)]
 
 
 class FileBatch:

@@ -12,7 +12,10 @@ stream's own clustering and aggregation state.  Streams join and leave at any ti
 their own pace; per stream the output is what a dedicated ``SpeakerDiarization`` pipeline with the
 same configuration produces.  The model pair may be config 2's (x-vector) or config 3's (powerset segmentation +
 ``HipEcapaEmbedding``, with ``normalize_embedding_weights=True``), or the same with the speechbrain x-vector
-(``HipSbXvectorEmbedding``): see ``StreamBatch``.
+(``HipSbXvectorEmbedding``): see ``StreamBatch``.  ``pipeline="vad"`` (no embedding) serves
+``VoiceActivityDetection`` instead (``diart.serve --pipeline VoiceActivityDetection``, reference
+``console/serve.py:19-22,99-102``) on a ``VadBatch``: every stream's turns are labelled ``"speech"``, and
+only the prediction is served, not the aggregated audio.
 
 Audio reaches the GPU through per-stream device rings (``AudioRing.push_rows`` / ``gather``): a step
 uploads only the NEW 500 ms block of each stream that has one (32 KB instead of the 320 KB window the
@@ -33,7 +36,9 @@ import torch
 from .blocks.aggregation import BatchedOutputTail
 from .features import Annotation
 from .functional import resampler
-from .pipeline import AudioRing, StreamBatch
+from .pipeline import AudioRing, StreamBatch, VadBatch
+
+PIPELINES = ("diarization", "vad")
 
 
 class _Stream:
@@ -57,7 +62,15 @@ class StreamServer:
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  device: Optional[torch.device] = None, patch_collar: float = 0.05,
                  engine: Optional[Callable] = None, device_rings: bool = True,
-                 normalize_embedding_weights: bool = False, input_sample_rate: Optional[int] = None):
+                 normalize_embedding_weights: bool = False, input_sample_rate: Optional[int] = None,
+                 pipeline: str = "diarization"):
+        if pipeline not in PIPELINES:
+            raise ValueError(f"StreamServer: pipeline={pipeline!r} (expected one of {PIPELINES})")
+        if pipeline == "vad" and embedding is not None:
+            raise ValueError("StreamServer: pipeline='vad' (VoiceActivityDetection) runs the segmentation only; "
+                             "pass embedding=None")
+        self.pipeline = pipeline
+        self._label = "speech" if pipeline == "vad" else None     # turn labels: speaker{g} | speech
         self.duration, self.step_seconds, self.sample_rate = float(duration), float(step), int(sample_rate)
         self.latency = self.step_seconds if latency is None else float(latency)
         # the rate clients push at.  Blocks and windows are cut at this rate; a window at another rate than the
@@ -80,12 +93,16 @@ class StreamServer:
         import collections
         self.step_errors = collections.deque(maxlen=64)   # (time, repr) of failed steps, newest last
         # `engine(windows (k, S) float32, starts (k,), slots [k]) -> list of k (turns (m, 3) array)`;
-        # the default engine is a StreamBatch with the C++ output tail
-        if engine is None:
+        # the default engine is a StreamBatch with the C++ output tail (a VadBatch for pipeline="vad")
+        if engine is None and pipeline == "vad":
+            self.batch = VadBatch(segmentation, self.max_streams, tau_active, duration=duration, step=step,
+                                  latency=self.latency, device=device)
+        elif engine is None:
             self.batch = StreamBatch(segmentation, embedding, self.max_streams, tau_active, rho_update,
                                      delta_new, gamma, beta, max_speakers,
                                      normalize_embedding_weights=normalize_embedding_weights, device=device, tail=True,
                                      duration=duration, step=step, latency=self.latency)
+        if engine is None:
             self._dev = torch.empty((self.max_streams, self.model_chunk_samples), dtype=torch.float32,
                                     device=self.batch.device)
             # resampling: windows at the input rate land in _raw, their resampled rows in _dev
@@ -256,7 +273,7 @@ class StreamServer:
                     if self._streams.get(sid) is not st:      # closed (or re-opened) mid-step: drop
                         continue
                     ann = BatchedOutputTail.annotation(np.asarray(tr, dtype=np.float64).reshape(-1, 3),
-                                                       len(tr), uri=str(sid))
+                                                       len(tr), uri=str(sid), label=self._label)
                     st.emitted += 1
                     if st.prediction is None:
                         st.prediction = ann
@@ -354,6 +371,9 @@ class StreamServer:
             with torch.cuda.device(self._dev.device):
                 self.resampler.rows(self._raw[:k], self._dev[:k])
         ticket = self.batch.launch(self._dev[:k], starts, slots=slots)
-        self.batch.finish(ticket, want_scores=False)
+        if isinstance(self.batch, VadBatch):
+            self.batch.finish(ticket)
+        else:
+            self.batch.finish(ticket, want_scores=False)
         _, _, _, _, turns, nturns = ticket["tail"]
         return [turns[i, :int(nturns[i])].copy() for i in range(k)]

@@ -154,6 +154,11 @@ int dz_seg_forward(dz_seg* seg, const float* d_wave, long long wave_stride, int 
  * dz_emb_pool consumes) — the N-stream driver's seg -> OSP hand-off without a launch of its own. */
 int dz_seg_forward_osp(dz_seg* seg, const float* d_wave, long long wave_stride, int batch, float* d_out,
                        float gamma, float beta, int normalize, float* d_weights, void* stream);
+/* dz_seg_forward that also writes the VoiceActivityDetection speech track: d_vad (B,F) = max over speakers of
+ * d_out (B,F,K), NaN where the row is NaN (reference blocks/vad.py:146-148).  Computed by the head kernel
+ * that writes d_out; honours dz_seg_use_wave_stats like dz_seg_forward_osp.                               */
+int dz_seg_forward_vad(dz_seg* seg, const float* d_wave, long long wave_stride, int batch,
+                       float* d_out, float* d_vad, void* stream);
 int dz_seg_destroy(dz_seg* seg);
 
 /* ---- embedding: replaces the callable behind EmbeddingModel.__call__ --------
