@@ -257,12 +257,11 @@ def load() -> C.CDLL:
         if list(sizes) != mine:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
-        if lib.dz_wsp_abi_size() != C.sizeof(WspWeights):
-            raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof(dz_wsp_weights) "
-                                f"{lib.dz_wsp_abi_size()} (library) vs {C.sizeof(WspWeights)} (this binding); rebuild it")
-        if lib.dz_sbx_abi_size() != C.sizeof(SbxWeights):
-            raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof(dz_sbx_weights) "
-                                f"{lib.dz_sbx_abi_size()} (library) vs {C.sizeof(SbxWeights)} (this binding); rebuild it")
+        for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights)):
+            size = getattr(lib, f"{name}_abi_size")()
+            if size != C.sizeof(struct):
+                raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({name}_weights) "
+                                    f"{size} (library) vs {C.sizeof(struct)} (this binding); rebuild it")
         _lib = lib
     return _lib
 
@@ -285,6 +284,20 @@ def get_option(name: str) -> int:
     v = C.c_int()
     check(load().dz_get_option(name.encode(), C.byref(v)), "dz_get_option")
     return v.value
+
+
+_hip: Optional[C.CDLL] = None
+
+
+def memcpy(dst: int, src, nbytes: int) -> None:
+    """``hipMemcpy`` of ``nbytes`` between two device addresses (a handle's buffer into a tensor: ``peek``); the caller
+    has synchronised the device."""
+    global _hip
+    if _hip is None:
+        _hip = C.CDLL("libamdhip64.so")
+    rc = _hip.hipMemcpy(vp(dst), src, C.c_size_t(nbytes), 3)     # hipMemcpyDeviceToDevice
+    if rc != 0:
+        raise DiartAmdError(f"hipMemcpy failed ({rc})")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -32,20 +32,8 @@ extern "C" int dz_abi_struct_sizes(int out[5]) {
 }
 
 // ---------------------------------------------------------------------------
-// context + scratch arena
+// context
 // ---------------------------------------------------------------------------
-struct Arena {
-    char* base = nullptr;
-    size_t size = 0, used = 0;
-    // first pass (base == nullptr) only measures
-    float* take(size_t nfloats) {
-        const size_t bytes = (nfloats * sizeof(float) + 255) & ~size_t(255);
-        float* p = base ? reinterpret_cast<float*>(base + used) : nullptr;
-        used += bytes;
-        return p;
-    }
-};
-
 extern "C" int dz_ctx_create(int hip_device, dz_ctx** out) {
     DZ_REQUIRE(out != nullptr, "dz_ctx_create: out is NULL");
     int n = 0;
@@ -496,23 +484,10 @@ extern "C" int dz_seg_create(dz_ctx* ctx, const dz_seg_weights* w, int max_batch
     DZ_HIP(hipEventCreateWithFlags(&s->ev_gx0_free, hipEventDisableTiming));
     s->pre = w->wih_split[1] && w->wih_split[2] && w->wih_split[3] &&
              w->lin0_split && w->lin1_split;
-    Arena measure;
-    seg_carve(s, measure);
-    hipError_t e = hipMalloc((void**)&s->arena, measure.used);
-    if (e != hipSuccess) {
-        dz_set_error("dz_seg_create: hipMalloc(%zu) failed: %s", measure.used, hipGetErrorString(e));
-        (void)hipEventDestroy(s->ev_gx0_free);
-        delete s;
-        return 1;
-    }
-    DZ_HIP(hipMemset(s->arena, 0, measure.used));
-    Arena real;
-    real.base = s->arena; real.size = measure.used;
-    seg_carve(s, real);
-    if (int rc = sinc_repack(w->sinc, s->ss)) {
-        (void)hipFree(s->arena);
-        (void)hipEventDestroy(s->ev_gx0_free);       // (the event leaked on this path)
-        delete s;
+    int rc = dz_arena_alloc("dz_seg_create", s, seg_carve);
+    if (!rc) rc = sinc_repack(w->sinc, s->ss);
+    if (rc) {
+        dz_seg_destroy(s);      // (the arena, the event)
         return rc;
     }
     *out = s;
@@ -775,19 +750,12 @@ extern "C" int dz_emb_create(dz_ctx* ctx, const dz_emb_weights* w, int max_batch
         t -= (kTdnnTaps[i] - 1) * kTdnnDil[i];
         e->T[i] = t;
     }
-    Arena measure;
-    emb_carve(e, measure);
-    hipError_t err = hipMalloc((void**)&e->arena, measure.used);
-    if (err != hipSuccess) {
-        dz_set_error("dz_emb_create: hipMalloc(%zu) failed: %s", measure.used, hipGetErrorString(err));
-        delete e;
-        return 1;
+    int rc = dz_arena_alloc("dz_emb_create", e, emb_carve);
+    if (!rc) rc = sinc_repack(w->sinc, e->ss);
+    if (rc) {
+        dz_emb_destroy(e);
+        return rc;
     }
-    DZ_HIP(hipMemset(e->arena, 0, measure.used));
-    Arena real;
-    real.base = e->arena; real.size = measure.used;
-    emb_carve(e, real);
-    if (int rc = sinc_repack(w->sinc, e->ss)) { (void)hipFree(e->arena); delete e; return rc; }
     *out = e;
     return 0;
 }

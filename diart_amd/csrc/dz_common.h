@@ -249,6 +249,81 @@ void dz_set_error(const char* fmt, ...);
     } while (0)
 
 // ---------------------------------------------------------------------------
+// scratch arenas and argument checks of the handles (host code)
+// ---------------------------------------------------------------------------
+// 256-byte aligned bump allocator; the first pass (base == nullptr) only measures
+struct Arena {
+    char* base = nullptr;
+    size_t used = 0;
+    template <typename T = float>
+    T* take(size_t n) {
+        const size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += bytes;
+        return p;
+    }
+};
+
+// The device arena of handle h (its `char* arena`): carve measures, one hipMalloc, the arena is zeroed, carve lays the
+// buffers out in it.  On failure the caller's destroy releases what was taken.
+template <typename H>
+int dz_arena_alloc(const char* who, H* h, void (*carve)(H*, Arena&)) {
+    Arena a;
+    carve(h, a);
+    const hipError_t err = hipMalloc((void**)&h->arena, a.used);
+    if (err != hipSuccess) {
+        h->arena = nullptr;
+        dz_set_error("%s: hipMalloc(%zu) failed: %s", who, a.used, hipGetErrorString(err));
+        return 1;
+    }
+    DZ_HIP(hipMemset(h->arena, 0, a.used));
+    a.base = h->arena;
+    a.used = 0;
+    carve(h, a);
+    return 0;
+}
+
+// The opening checks of a forward over n rows (dz_ecapa_forward, dz_sbx_forward, dz_wsp_forward; `frames` names the
+// argument that gives the masks' or weights' frame count) and of a groups forward (dz_*_forward_groups).
+inline int dz_check_rows_forward(const char* who, const void* h, int max_rows, const float* d_wave, long long wave_stride,
+                                 const float* d_masks, int n, int mask_frames, const float* d_out,
+                                 const char* frames = "mask_frames") {
+    DZ_REQUIRE(h && d_wave && d_out, "%s: NULL argument", who);
+    DZ_REQUIRE(n >= 1 && n <= max_rows, "%s: %d rows outside [1, %d]", who, n, max_rows);
+    DZ_REQUIRE(d_masks == nullptr || mask_frames >= 1, "%s: %s %d", who, frames, mask_frames);
+    DZ_REQUIRE(wave_stride >= 0, "%s: negative stride", who);
+    return 0;
+}
+inline int dz_check_groups_forward(const char* who, const void* h, int max_rows, const float* d_wave,
+                                   long long wave_stride, const float* d_masks, int n_groups, int rows_per_group,
+                                   int mask_frames, const float* d_out) {
+    DZ_REQUIRE(h && d_wave && d_masks && d_out, "%s: NULL argument", who);
+    DZ_REQUIRE(n_groups >= 1 && rows_per_group >= 1 && (long long)n_groups * rows_per_group <= max_rows,
+               "%s: %d groups x %d rows outside [1, %d]", who, n_groups, rows_per_group, max_rows);
+    DZ_REQUIRE(mask_frames >= 1, "%s: mask_frames %d", who, mask_frames);
+    DZ_REQUIRE(wave_stride >= 0, "%s: negative stride", who);
+    return 0;
+}
+
+// The batch geometry of ECAPA-TDNN and the speechbrain x-vector (ecapa_api.hip, sbx_api.hip): each row's kept samples
+// compacted into sig (lstride floats per row: the centred STFT's 200 leading zeros, padding), their count, and what
+// the device derives from it per group of rows (k_ecapa.hip: ecapa_geometry_kernel), with Tc frames per row at most.
+struct DzRowGeometry {
+    int S, Tc, min_samples;
+    long long lstride;
+    float* sig;
+    int *lens, *nvalid, *nmask, *tooshort;
+    // per-row frame count the kernels read, and the geometry a groups forward reports (peek)
+    int *tdev, *rep_nvalid, *rep_nmask, *rep_T;
+    void init(int num_samples, int min_num_samples);
+    void carve(Arena& a, size_t rows);
+    // zero sig, compact the kept samples of N = G K rows into it, derive each group's geometry on the device.  Row
+    // g K + k reads waveform row (g K + k) / rows_per_wave and mask row g K + k (or every sample when d_masks is NULL).
+    int prologue(const float* d_wave, long long wave_stride, const float* d_masks, int mask_frames, int G, int K,
+                 int rows_per_wave, hipStream_t st);
+};
+
+// ---------------------------------------------------------------------------
 // kernel launch wrappers (one per .hip file)
 // ---------------------------------------------------------------------------
 // k_front.hip ---------------------------------------------------------------

@@ -11,41 +11,57 @@ namespace {
 enum { MIN_NUM_SAMPLES = 640, HOP = 160, NFFT = 400, C1 = 1024, C3 = 3072, EMB = 192, FC_SPLIT = 16, SE_SPLIT = 8,
        PLANE_SLACK = 16384 };
 
-struct Carve {
-    char* base = nullptr;
-    size_t used = 0;
-    template <typename T>
-    T* take(size_t n) {
-        const size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += bytes;
-        return p;
-    }
-};
-
 }  // namespace
 
 struct dz_ecapa {
     dz_ctx* ctx;
     dz_ecapa_weights w;
-    int Nm, S, Tc;
-    long long lstride;
+    int Nm;
+    DzRowGeometry geo;
     char* arena;
     int* h_pin;  // pinned host: lens[Nm] | nvalid[Nm] | nmask[Nm] | tooshort[Nm]
     // device buffers
-    float *sig, *spec, *pw, *melp, *feats, *b0, *t1, *res, *t2, *cat, *mfa, *a1;
+    float *spec, *pw, *melp, *feats, *b0, *t1, *res, *t2, *cat, *mfa, *a1;
     float *smean, *sfc1, *gate, *gstat, *rb, *pooled, *parts;
     // split-f16 precision: the inputs of the wide 1 x 1 layers as kb-major f16 planes (k_gemm_pre.hip), [2][C / 32][N T][32]
     unsigned short *b0s, *ress, *cats;
-    int *lens, *nvalid, *nmask, *tooshort;
-    // groups forward: per-row frame count the kernels read, and the geometry dz_ecapa_peek 6 / 7 / 8 report
-    int *tdev, *rep_nvalid, *rep_nmask, *rep_T;
     int lastN, lastT, lastGroups;
 };
 
-static void ecapa_carve(dz_ecapa* e, Carve& a) {
-    const size_t N = e->Nm, NT = N * e->Tc;
-    e->sig = a.take<float>(N * e->lstride);
+// DzRowGeometry (dz_common.h): ECAPA's STFT layout and batch geometry, which sbx_api.hip shares
+void DzRowGeometry::init(int num_samples, int min_num_samples) {
+    S = num_samples;
+    Tc = 1 + num_samples / HOP;
+    min_samples = min_num_samples;
+    lstride = ((long long)num_samples + NFFT + 3) / 4 * 4;
+}
+
+void DzRowGeometry::carve(Arena& a, size_t rows) {
+    sig = a.take(rows * lstride);
+    lens = a.take<int>(rows);
+    nvalid = a.take<int>(rows);
+    nmask = a.take<int>(rows);
+    tooshort = a.take<int>(rows);
+    tdev = a.take<int>(rows);
+    rep_nvalid = a.take<int>(rows);
+    rep_nmask = a.take<int>(rows);
+    rep_T = a.take<int>(rows);
+}
+
+int DzRowGeometry::prologue(const float* d_wave, long long wave_stride, const float* d_masks, int mask_frames, int G,
+                            int K, int rows_per_wave, hipStream_t st) {
+    const int N = G * K;
+    int rc;
+    DZ_HIP(hipMemsetAsync(sig, 0, sizeof(float) * (size_t)N * lstride, st));
+    if ((rc = dz_launch_mask_compact(d_wave, wave_stride, S, d_masks, mask_frames, N, sig, lstride, lens, st,
+                                     rows_per_wave)))
+        return rc;
+    return dz_launch_ecapa_geometry(lens, G, K, Tc, min_samples, HOP, nvalid, nmask, tooshort, tdev, rep_nvalid,
+                                    rep_nmask, rep_T, st);
+}
+
+static void ecapa_carve(dz_ecapa* e, Arena& a) {
+    const size_t N = e->Nm, NT = N * e->geo.Tc;
     e->spec = a.take<float>(NT * 404);
     e->pw = a.take<float>(NT * 204);
     e->melp = a.take<float>(NT * 80);
@@ -74,14 +90,7 @@ static void ecapa_carve(dz_ecapa* e, Carve& a) {
         e->ress = a.take<unsigned short>(2 * NT * C1 + PLANE_SLACK);
         e->cats = a.take<unsigned short>(2 * NT * C3 + PLANE_SLACK);
     }
-    e->lens = a.take<int>(N);
-    e->nvalid = a.take<int>(N);
-    e->nmask = a.take<int>(N);
-    e->tooshort = a.take<int>(N);
-    e->tdev = a.take<int>(N);
-    e->rep_nvalid = a.take<int>(N);
-    e->rep_nmask = a.take<int>(N);
-    e->rep_T = a.take<int>(N);
+    e->geo.carve(a, N);
 }
 
 extern "C" int dz_ecapa_frames_for(int num_samples) { return num_samples > 0 ? 1 + num_samples / HOP : 0; }
@@ -95,27 +104,21 @@ extern "C" int dz_ecapa_create(dz_ctx* ctx, const dz_ecapa_weights* w, int max_r
     dz_ecapa* e = new (std::nothrow) dz_ecapa;
     DZ_REQUIRE(e != nullptr, "dz_ecapa_create: out of memory");
     memset(e, 0, sizeof(*e));
-    e->ctx = ctx; e->w = *w; e->Nm = max_rows; e->S = num_samples;
-    e->Tc = 1 + num_samples / HOP;
-    e->lstride = ((long long)num_samples + NFFT + 3) / 4 * 4;
-    Carve measure;
-    ecapa_carve(e, measure);
-    hipError_t err = hipMalloc((void**)&e->arena, measure.used);
-    if (err != hipSuccess) {
-        dz_set_error("dz_ecapa_create: hipMalloc(%zu) failed: %s", measure.used, hipGetErrorString(err));
-        delete e;
-        return 1;
+    e->ctx = ctx; e->w = *w; e->Nm = max_rows;
+    e->geo.init(num_samples, MIN_NUM_SAMPLES);
+    int rc = dz_arena_alloc("dz_ecapa_create", e, ecapa_carve);
+    if (!rc) {
+        const hipError_t err = hipHostMalloc((void**)&e->h_pin, sizeof(int) * 4 * max_rows, hipHostMallocDefault);
+        if (err != hipSuccess) {
+            e->h_pin = nullptr;
+            dz_set_error("dz_ecapa_create: hipHostMalloc failed: %s", hipGetErrorString(err));
+            rc = 1;
+        }
     }
-    err = hipHostMalloc((void**)&e->h_pin, sizeof(int) * 4 * max_rows, hipHostMallocDefault);
-    if (err != hipSuccess) {
-        dz_set_error("dz_ecapa_create: hipHostMalloc failed: %s", hipGetErrorString(err));
-        (void)hipFree(e->arena);
-        delete e;
-        return 1;
+    if (rc) {
+        dz_ecapa_destroy(e);
+        return rc;
     }
-    Carve real;
-    real.base = e->arena;
-    ecapa_carve(e, real);
     *out = e;
     return 0;
 }
@@ -176,26 +179,25 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
 extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave_stride,
                                 const float* d_masks, int N, int mask_frames, float* d_out,
                                 void* stream) {
-    DZ_REQUIRE(e && d_wave && d_out, "dz_ecapa_forward: NULL argument");
-    DZ_REQUIRE(N >= 1 && N <= e->Nm, "dz_ecapa_forward: %d rows outside [1, %d]", N, e->Nm);
-    DZ_REQUIRE(d_masks == nullptr || mask_frames >= 1, "dz_ecapa_forward: mask_frames %d", mask_frames);
-    DZ_REQUIRE(wave_stride >= 0, "dz_ecapa_forward: negative stride");
+    if (int rc = dz_check_rows_forward("dz_ecapa_forward", e, e ? e->Nm : 0, d_wave, wave_stride, d_masks, N,
+                                       mask_frames, d_out))
+        return rc;
     DZ_HIP(hipSetDevice(e->ctx->device));
     DzRangeScope range_scope(e->ctx->oflag_dev);
     hipStream_t st = (hipStream_t)stream;
     int rc;
 
     // ---- 1. mask -> kept samples, zero padded rows (200 leading zeros = centred STFT) ---------
-    DZ_HIP(hipMemsetAsync(e->sig, 0, sizeof(float) * (size_t)N * e->lstride, st));
+    DZ_HIP(hipMemsetAsync(e->geo.sig, 0, sizeof(float) * (size_t)N * e->geo.lstride, st));
     { DzProfScope ps(DZ_T_ECAPA_FBANK, N);
-      if ((rc = dz_launch_mask_compact(d_wave, wave_stride, e->S, d_masks, mask_frames, N, e->sig,
-                                       e->lstride, e->lens, st)))
+      if ((rc = dz_launch_mask_compact(d_wave, wave_stride, e->geo.S, d_masks, mask_frames, N, e->geo.sig,
+                                       e->geo.lstride, e->geo.lens, st)))
           return rc; }
     int* h_lens = e->h_pin;
     int* h_nvalid = h_lens + e->Nm;
     int* h_nmask = h_nvalid + e->Nm;
     int* h_short = h_nmask + e->Nm;
-    DZ_HIP(hipMemcpyAsync(h_lens, e->lens, sizeof(int) * N, hipMemcpyDeviceToHost, st));
+    DZ_HIP(hipMemcpyAsync(h_lens, e->geo.lens, sizeof(int) * N, hipMemcpyDeviceToHost, st));
     DZ_HIP(hipStreamSynchronize(st));   // the batch geometry (frames) depends on the longest row
     // a row whose kept samples hold a NaN / Inf comes back as -(len + 1): it keeps its place in the batch geometry
     // (speechbrain pads and normalises by the longest row whatever its values) and its embedding is NaN — what the
@@ -209,11 +211,11 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
     e->lastGroups = 0;
     if (lmax < MIN_NUM_SAMPLES) {       // "every signal is too short": all NaN
         for (int i = 0; i < N; ++i) h_short[i] = 1;
-        DZ_HIP(hipMemcpyAsync(e->tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
-        DZ_HIP(hipMemsetAsync(e->nvalid, 0, sizeof(int) * N, st));     // (no frames: what peek 6 / 7 report)
-        DZ_HIP(hipMemsetAsync(e->nmask, 0, sizeof(int) * N, st));
+        DZ_HIP(hipMemcpyAsync(e->geo.tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
+        DZ_HIP(hipMemsetAsync(e->geo.nvalid, 0, sizeof(int) * N, st));     // (no frames: what peek 6 / 7 report)
+        DZ_HIP(hipMemsetAsync(e->geo.nmask, 0, sizeof(int) * N, st));
         e->lastT = 0;
-        return dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st);
+        return dz_launch_nan_rows(d_out, N, EMB, e->geo.tooshort, st);
     }
     const int T = 1 + lmax / HOP;
     e->lastT = T;
@@ -230,15 +232,15 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
         nm = nm < 1 ? 1 : (nm > T ? T : nm);
         h_nmask[i] = nm;
     }
-    DZ_HIP(hipMemcpyAsync(e->nvalid, h_nvalid, sizeof(int) * N, hipMemcpyHostToDevice, st));
-    DZ_HIP(hipMemcpyAsync(e->nmask, h_nmask, sizeof(int) * N, hipMemcpyHostToDevice, st));
-    DZ_HIP(hipMemcpyAsync(e->tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
+    DZ_HIP(hipMemcpyAsync(e->geo.nvalid, h_nvalid, sizeof(int) * N, hipMemcpyHostToDevice, st));
+    DZ_HIP(hipMemcpyAsync(e->geo.nmask, h_nmask, sizeof(int) * N, hipMemcpyHostToDevice, st));
+    DZ_HIP(hipMemcpyAsync(e->geo.tooshort, h_short, sizeof(int) * N, hipMemcpyHostToDevice, st));
     if ((rc = ecapa_network(e, N, T, nullptr, d_out, st))) return rc;
-    return dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st);
+    return dz_launch_nan_rows(d_out, N, EMB, e->geo.tooshort, st);
 }
 
-// Steps 2 - 3 of a forward (Fbank, ECAPA-TDNN, fc -> d_out, before the NaN rows) over the N rows of e->sig laid
-// out T frames apart, whose geometry (e->nvalid, e->nmask) is already on the device.  tdev: NULL (every row has
+// Steps 2 - 3 of a forward (Fbank, ECAPA-TDNN, fc -> d_out, before the NaN rows) over the N rows of e->geo.sig
+// laid out T frames apart, whose geometry (geo.nvalid, geo.nmask) is already on the device.  tdev: NULL (every row has
 // T frames) or the device [N] frame count of each row (the groups forward: T = the handle's Tc; a row reflects
 // and takes its top-dB maximum at its own count, and the frames past it are computed but read by no output).
 static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_out, hipStream_t st) {
@@ -248,7 +250,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
 
     // ---- 2. Fbank: STFT as one GEMM over overlapping rows (hop 160 < window 400) ---------------
     dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
-    if ((rc = gemm(DZ_T_ECAPA_FBANK, N, st, e->sig, HOP, e->lstride, N, T, NFFT, 1, 1, 0, dft, nullptr, 416, 448, 402, e->spec,
+    if ((rc = gemm(DZ_T_ECAPA_FBANK, N, st, e->geo.sig, HOP, e->geo.lstride, N, T, NFFT, 1, 1, 0, dft, nullptr, 416, 448, 402, e->spec,
                    404, (long long)T * 404, DZ_EPI_BIAS)))
         return rc;
     { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_power(e->spec, 404, NT, e->pw, st))) return rc; }
@@ -256,7 +258,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     if ((rc = gemm(DZ_T_ECAPA_FBANK, N, st, e->pw, 204, 0, 1, (int)NT, 204, 1, 1, 0, mel, nullptr, 224, 128, 80, e->melp, 80, 0,
                    DZ_EPI_BIAS)))
         return rc;
-    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->nvalid, e->feats, st, tdev))) return rc; }
+    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->geo.nvalid, e->feats, st, tdev))) return rc; }
 
     // ---- 3. ECAPA-TDNN -------------------------------------------------------------------------
     // Split-f16 precision: the seven wide 1 x 1 layers (tdnn1 / tdnn2 of the three blocks, the MFA convolution: 84 % of
@@ -307,7 +309,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
                       DZ_EPI_RELU_BN);
         if (rc) return rc;
         // squeeze-excitation + residual, written straight into its slice of the concatenation
-        { DzProfScope ps(DZ_T_ECAPA_SE, N); if ((rc = dz_launch_se_mean(e->t2, T, C1, C1, N, e->nmask, e->smean, st))) return rc; }
+        { DzProfScope ps(DZ_T_ECAPA_SE, N); if ((rc = dz_launch_se_mean(e->t2, T, C1, C1, N, e->geo.nmask, e->smean, st))) return rc; }
         // squeeze (N rows x 1024 -> 128): one output tile, so the K loop is split 8 ways (a lone workgroup
         // walking 32 k-tiles took 90 us); the ReLU follows the fixed-order reduce
         if ((rc = gemm(DZ_T_ECAPA_SE, N, st, e->smean, C1, 0, 1, N, C1, 1, 1, 0, b.se1, nullptr, C1, 128, 128, e->parts, 128, 0,
@@ -333,7 +335,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
                   DZ_EPI_RELU_BN);
     if (rc) return rc;
     // attentive statistics pooling with global context: W [x; mean; std] = Wx x + Wms [mean; std]
-    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_asp_gstats(e->mfa, T, C3, N, e->nmask, e->gstat, st))) return rc; }
+    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_asp_gstats(e->mfa, T, C3, N, e->geo.nmask, e->gstat, st))) return rc; }
     dz_layer wms = {w.asp_wms, w.zeros, nullptr, nullptr};
     // (N rows x 6144 -> 128: one output tile and 192 k-tiles — 0.5 ms for a lone workgroup; split-K like fc)
     if ((rc = gemm(DZ_T_ECAPA_ASP, N, st, e->gstat, 2 * C3, 0, 1, N, 2 * C3, 1, 1, 0, wms, nullptr, 2 * C3, 128, 128, e->parts, 128, 0,
@@ -347,7 +349,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     if ((rc = gemm(DZ_T_ECAPA_ASP, N, st, e->a1, 128, 0, 1, (int)NT, 128, 1, 1, 0, w.asp_conv, nullptr, 128, C3, C3, logits, C3, 0,
                    DZ_EPI_BIAS)))
         return rc;
-    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_asp_pool(e->mfa, logits, T, C3, N, e->nmask, e->pooled, st))) return rc; }
+    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_asp_pool(e->mfa, logits, T, C3, N, e->geo.nmask, e->pooled, st))) return rc; }
     // asp_bn (folded) + fc, split-K with a fixed-order reduce
     const long long ysplit = (long long)N * EMB;
     if ((rc = gemm(DZ_T_ECAPA_FC, N, st, e->pooled, 2 * C3, 0, 1, N, 2 * C3, 1, 1, 0, w.fc, nullptr, 2 * C3, EMB, EMB, e->parts, EMB,
@@ -365,29 +367,21 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
 extern "C" int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
                                        int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
                                        void* stream) {
-    DZ_REQUIRE(e && d_wave && d_masks && d_out, "dz_ecapa_forward_groups: NULL argument");
-    DZ_REQUIRE(n_groups >= 1 && rows_per_group >= 1 && (long long)n_groups * rows_per_group <= e->Nm,
-               "dz_ecapa_forward_groups: %d groups x %d rows outside [1, %d]", n_groups, rows_per_group, e->Nm);
-    DZ_REQUIRE(mask_frames >= 1, "dz_ecapa_forward_groups: mask_frames %d", mask_frames);
-    DZ_REQUIRE(wave_stride >= 0, "dz_ecapa_forward_groups: negative stride");
+    int rc = dz_check_groups_forward("dz_ecapa_forward_groups", e, e ? e->Nm : 0, d_wave, wave_stride, d_masks,
+                                     n_groups, rows_per_group, mask_frames, d_out);
+    if (rc) return rc;
     DZ_HIP(hipSetDevice(e->ctx->device));
     DzRangeScope range_scope(e->ctx->oflag_dev);
     hipStream_t st = (hipStream_t)stream;
-    const int N = n_groups * rows_per_group, Tc = e->Tc;
-    int rc;
-    DZ_HIP(hipMemsetAsync(e->sig, 0, sizeof(float) * (size_t)N * e->lstride, st));
+    const int N = n_groups * rows_per_group, Tc = e->geo.Tc;
     { DzProfScope ps(DZ_T_ECAPA_FBANK, N);
-      if ((rc = dz_launch_mask_compact(d_wave, wave_stride, e->S, d_masks, mask_frames, N, e->sig, e->lstride, e->lens,
-                                       st, rows_per_group)))
-          return rc;
-      if ((rc = dz_launch_ecapa_geometry(e->lens, n_groups, rows_per_group, Tc, MIN_NUM_SAMPLES, HOP, e->nvalid, e->nmask,
-                                         e->tooshort, e->tdev, e->rep_nvalid, e->rep_nmask, e->rep_T, st)))
+      if ((rc = e->geo.prologue(d_wave, wave_stride, d_masks, mask_frames, n_groups, rows_per_group, rows_per_group, st)))
           return rc; }
     e->lastN = N;
     e->lastT = Tc;
     e->lastGroups = 1;
-    if ((rc = ecapa_network(e, N, Tc, e->tdev, d_out, st))) return rc;
-    if ((rc = dz_launch_nan_rows(d_out, N, EMB, e->tooshort, st))) return rc;
+    if ((rc = ecapa_network(e, N, Tc, e->geo.tdev, d_out, st))) return rc;
+    if ((rc = dz_launch_nan_rows(d_out, N, EMB, e->geo.tooshort, st))) return rc;
     return normalize ? dz_launch_l2norm(d_out, N, EMB, 1.0f, st) : 0;
 }
 
@@ -397,9 +391,9 @@ extern "C" int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long lo
     if (frames) *frames = (int)T;
     if (e->lastGroups) {        // the geometry a groups forward reports (ecapa_geometry_kernel)
         switch (which) {
-            case 6: *d_ptr = e->rep_nvalid; *count = N; return 0;
-            case 7: *d_ptr = e->rep_nmask; *count = N; return 0;
-            case 8: *d_ptr = e->rep_T; *count = N; return 0;
+            case 6: *d_ptr = e->geo.rep_nvalid; *count = N; return 0;
+            case 7: *d_ptr = e->geo.rep_nmask; *count = N; return 0;
+            case 8: *d_ptr = e->geo.rep_T; *count = N; return 0;
         }
     } else if (which == 8) {
         dz_set_error("dz_ecapa_peek: buffer 8 (per-row frames) exists after dz_ecapa_forward_groups only");
@@ -411,9 +405,9 @@ extern "C" int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long lo
         case 2: *d_ptr = e->cat; *count = N * T * C3; return 0;   // holds the logits after a forward
         case 3: *d_ptr = e->mfa; *count = N * T * C3; return 0;
         case 4: *d_ptr = e->pooled; *count = N * 2 * C3; return 0;
-        case 5: *d_ptr = e->lens; *count = N; return 0;
-        case 6: *d_ptr = e->nvalid; *count = N; return 0;
-        case 7: *d_ptr = e->nmask; *count = N; return 0;
+        case 5: *d_ptr = e->geo.lens; *count = N; return 0;
+        case 6: *d_ptr = e->geo.nvalid; *count = N; return 0;
+        case 7: *d_ptr = e->geo.nmask; *count = N; return 0;
     }
     dz_set_error("dz_ecapa_peek: unknown buffer %d", which);
     return 2;

@@ -20,34 +20,20 @@ constexpr float MEAN_NOISE = 5e-5f, STD_EPS = 1e-5f;
 constexpr int kTaps[5] = {5, 3, 3, 1, 1}, kDil[5] = {1, 2, 3, 1, 1}, kCin[5] = {NMEL, 512, 512, 512, 512},
               kNpad[5] = {512, 512, 512, 512, C5PAD}, kKpad[5] = {128, 1536, 1536, 512, 512};
 
-struct Carve {
-    char* base = nullptr;
-    size_t used = 0;
-    template <typename T>
-    T* take(size_t n) {
-        const size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += bytes;
-        return p;
-    }
-};
-
 }  // namespace
 
 struct dz_sbx {
     dz_ctx* ctx;
     dz_sbx_weights w;
-    int Nm, S, Tc;
-    long long lstride;
+    int Nm;
+    DzRowGeometry geo;
     char* arena;
-    float *sig, *spec, *pw, *melp, *feats, *x[5], *pooled, *parts;
-    int *lens, *nvalid, *nmask, *tooshort, *tdev, *rep_nvalid, *rep_nmask, *rep_T;
+    float *spec, *pw, *melp, *feats, *x[5], *pooled, *parts;
     int lastN;
 };
 
-static void sbx_carve(dz_sbx* m, Carve& a) {
-    const size_t N = m->Nm, NT = N * m->Tc;
-    m->sig = a.take<float>(N * m->lstride);
+static void sbx_carve(dz_sbx* m, Arena& a) {
+    const size_t N = m->Nm, NT = N * m->geo.Tc;
     m->spec = a.take<float>(NT * 404);
     m->pw = a.take<float>(NT * 204);
     m->melp = a.take<float>(NT * NMEL);
@@ -56,14 +42,7 @@ static void sbx_carve(dz_sbx* m, Carve& a) {
     m->x[4] = a.take<float>(NT * C5);
     m->pooled = a.take<float>(N * POOLED);
     m->parts = a.take<float>((size_t)FC_SPLIT * N * EMB);
-    m->lens = a.take<int>(N);
-    m->nvalid = a.take<int>(N);
-    m->nmask = a.take<int>(N);
-    m->tooshort = a.take<int>(N);
-    m->tdev = a.take<int>(N);
-    m->rep_nvalid = a.take<int>(N);
-    m->rep_nmask = a.take<int>(N);
-    m->rep_T = a.take<int>(N);
+    m->geo.carve(a, N);
 }
 
 extern "C" int dz_sbx_abi_size(void) { return (int)sizeof(dz_sbx_weights); }
@@ -76,20 +55,12 @@ extern "C" int dz_sbx_create(dz_ctx* ctx, const dz_sbx_weights* w, int max_rows,
     dz_sbx* m = new (std::nothrow) dz_sbx;
     DZ_REQUIRE(m != nullptr, "dz_sbx_create: out of memory");
     memset(m, 0, sizeof(*m));
-    m->ctx = ctx; m->w = *w; m->Nm = max_rows; m->S = num_samples;
-    m->Tc = 1 + num_samples / HOP;
-    m->lstride = ((long long)num_samples + NFFT + 3) / 4 * 4;
-    Carve measure;
-    sbx_carve(m, measure);
-    hipError_t err = hipMalloc((void**)&m->arena, measure.used);
-    if (err != hipSuccess) {
-        dz_set_error("dz_sbx_create: hipMalloc(%zu) failed: %s", measure.used, hipGetErrorString(err));
-        delete m;
-        return 1;
+    m->ctx = ctx; m->w = *w; m->Nm = max_rows;
+    m->geo.init(num_samples, MIN_NUM_SAMPLES);
+    if (int rc = dz_arena_alloc("dz_sbx_create", m, sbx_carve)) {
+        dz_sbx_destroy(m);
+        return rc;
     }
-    Carve real;
-    real.base = m->arena;
-    sbx_carve(m, real);
     *out = m;
     return 0;
 }
@@ -127,27 +98,22 @@ static int sbx_gemm(hipStream_t st, const float* X, int ldx, long long xbs, int 
 static int sbx_run(dz_sbx* m, const float* d_wave, long long wave_stride, const float* d_masks, int G, int K,
                    int rows_per_wave, int mask_frames, int normalize, float* d_out, hipStream_t st) {
     const dz_sbx_weights& w = m->w;
-    const int N = G * K, T = m->Tc;
+    DzRowGeometry& geo = m->geo;
+    const int N = G * K, T = geo.Tc;
     const long long NT = (long long)N * T;
     int rc;
-    DZ_HIP(hipMemsetAsync(m->sig, 0, sizeof(float) * (size_t)N * m->lstride, st));
-    if ((rc = dz_launch_mask_compact(d_wave, wave_stride, m->S, d_masks, mask_frames, N, m->sig, m->lstride, m->lens,
-                                     st, rows_per_wave)))
-        return rc;
-    if ((rc = dz_launch_ecapa_geometry(m->lens, G, K, T, MIN_NUM_SAMPLES, HOP, m->nvalid, m->nmask, m->tooshort,
-                                       m->tdev, m->rep_nvalid, m->rep_nmask, m->rep_T, st)))
-        return rc;
+    if ((rc = geo.prologue(d_wave, wave_stride, d_masks, mask_frames, G, K, rows_per_wave, st))) return rc;
     m->lastN = N;
     // ---- Fbank(n_mels = 24): STFT as one GEMM over the overlapping rows, |.|^2, mel GEMM, dB / top-dB / sentence mean
     const dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
-    if ((rc = sbx_gemm(st, m->sig, HOP, m->lstride, N, T, NFFT, 1, 1, 0, dft, 416, 448, 402, m->spec, 404,
+    if ((rc = sbx_gemm(st, geo.sig, HOP, geo.lstride, N, T, NFFT, 1, 1, 0, dft, 416, 448, 402, m->spec, 404,
                        (long long)T * 404, DZ_EPI_BIAS)))
         return rc;
     if ((rc = dz_launch_power(m->spec, 404, NT, m->pw, st))) return rc;
     const dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
     if ((rc = sbx_gemm(st, m->pw, 204, 0, 1, (int)NT, 204, 1, 1, 0, mel, 224, 64, NMEL, m->melp, NMEL, 0, DZ_EPI_BIAS)))
         return rc;
-    if ((rc = dz_launch_fbank_post_mels(m->melp, NMEL, T, N, m->nvalid, m->feats, st, m->tdev))) return rc;
+    if ((rc = dz_launch_fbank_post_mels(m->melp, NMEL, T, N, geo.nvalid, m->feats, st, geo.tdev))) return rc;
     // ---- TDNN 1 - 5: Conv1d (reflect "same" at the row's own frame count) -> LeakyReLU -> BatchNorm ------------
     const float* xin = m->feats;
     int ldin = NMEL;
@@ -155,7 +121,7 @@ static int sbx_run(dz_sbx* m, const float* d_wave, long long wave_stride, const 
         const int pad = kDil[l] * (kTaps[l] - 1) / 2, cout = l == 4 ? C5 : 512;
         if (pad)
             rc = sbx_gemm(st, xin, ldin, (long long)T * ldin, N, T, kCin[l], kTaps[l], kDil[l], pad, w.tdnn[l], kKpad[l],
-                          kNpad[l], cout, m->x[l], cout, (long long)T * cout, DZ_EPI_TDNN, m->tdev);
+                          kNpad[l], cout, m->x[l], cout, (long long)T * cout, DZ_EPI_TDNN, geo.tdev);
         else        // (1 x 1: every frame of every row is one GEMM row)
             rc = sbx_gemm(st, xin, ldin, 0, 1, (int)NT, kCin[l], 1, 1, 0, w.tdnn[l], kKpad[l], kNpad[l], cout, m->x[l],
                           cout, 0, DZ_EPI_TDNN);
@@ -164,23 +130,22 @@ static int sbx_run(dz_sbx* m, const float* d_wave, long long wave_stride, const 
         ldin = cout;
     }
     // ---- StatisticsPooling over round(rel T) frames, Linear(3000 -> 512) split-K + fixed-order finish --------------
-    if ((rc = dz_launch_sb_stats_pool(m->x[4], T, C5, C5, N, m->nvalid, MEAN_NOISE, STD_EPS, m->pooled, st))) return rc;
+    if ((rc = dz_launch_sb_stats_pool(m->x[4], T, C5, C5, N, geo.nvalid, MEAN_NOISE, STD_EPS, m->pooled, st))) return rc;
     const dz_layer lin = {w.lin_w, w.lin_b, nullptr, nullptr, nullptr};
     const long long ysplit = (long long)N * EMB;
     if ((rc = sbx_gemm(st, m->pooled, POOLED, 0, 1, N, POOLED, 1, 1, 0, lin, POOLED_KPAD, EMB, EMB, m->parts, EMB, 0,
                        DZ_EPI_BIAS, nullptr, FC_SPLIT, ysplit)))
         return rc;
     if ((rc = dz_launch_splitk_finish(m->parts, FC_SPLIT, ysplit, N, EMB, 0, d_out, st))) return rc;
-    if ((rc = dz_launch_nan_rows(d_out, N, EMB, m->tooshort, st))) return rc;
+    if ((rc = dz_launch_nan_rows(d_out, N, EMB, geo.tooshort, st))) return rc;
     return normalize ? dz_launch_l2norm(d_out, N, EMB, 1.0f, st) : 0;
 }
 
 extern "C" int dz_sbx_forward(dz_sbx* m, const float* d_wave, long long wave_stride, const float* d_masks, int N,
                               int mask_frames, float* d_out, void* stream) {
-    DZ_REQUIRE(m && d_wave && d_out, "dz_sbx_forward: NULL argument");
-    DZ_REQUIRE(N >= 1 && N <= m->Nm, "dz_sbx_forward: %d rows outside [1, %d]", N, m->Nm);
-    DZ_REQUIRE(d_masks == nullptr || mask_frames >= 1, "dz_sbx_forward: mask_frames %d", mask_frames);
-    DZ_REQUIRE(wave_stride >= 0, "dz_sbx_forward: negative stride");
+    if (int rc = dz_check_rows_forward("dz_sbx_forward", m, m ? m->Nm : 0, d_wave, wave_stride, d_masks, N, mask_frames,
+                                       d_out))
+        return rc;
     DZ_HIP(hipSetDevice(m->ctx->device));
     DzRangeScope range_scope(m->ctx->oflag_dev);
     return sbx_run(m, d_wave, wave_stride, d_masks, 1, N, 1, mask_frames, 0, d_out, (hipStream_t)stream);
@@ -189,11 +154,9 @@ extern "C" int dz_sbx_forward(dz_sbx* m, const float* d_wave, long long wave_str
 extern "C" int dz_sbx_forward_groups(dz_sbx* m, const float* d_wave, long long wave_stride, const float* d_masks,
                                      int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
                                      void* stream) {
-    DZ_REQUIRE(m && d_wave && d_masks && d_out, "dz_sbx_forward_groups: NULL argument");
-    DZ_REQUIRE(n_groups >= 1 && rows_per_group >= 1 && (long long)n_groups * rows_per_group <= m->Nm,
-               "dz_sbx_forward_groups: %d groups x %d rows outside [1, %d]", n_groups, rows_per_group, m->Nm);
-    DZ_REQUIRE(mask_frames >= 1, "dz_sbx_forward_groups: mask_frames %d", mask_frames);
-    DZ_REQUIRE(wave_stride >= 0, "dz_sbx_forward_groups: negative stride");
+    if (int rc = dz_check_groups_forward("dz_sbx_forward_groups", m, m ? m->Nm : 0, d_wave, wave_stride, d_masks,
+                                         n_groups, rows_per_group, mask_frames, d_out))
+        return rc;
     DZ_HIP(hipSetDevice(m->ctx->device));
     DzRangeScope range_scope(m->ctx->oflag_dev);
     return sbx_run(m, d_wave, wave_stride, d_masks, n_groups, rows_per_group, rows_per_group, mask_frames, normalize,
@@ -202,16 +165,16 @@ extern "C" int dz_sbx_forward_groups(dz_sbx* m, const float* d_wave, long long w
 
 extern "C" int dz_sbx_peek(dz_sbx* m, int which, const void** d_ptr, long long* count, int* frames) {
     DZ_REQUIRE(m && d_ptr && count, "dz_sbx_peek: NULL argument");
-    const long long N = m->lastN, NT = N * m->Tc;
-    if (frames) *frames = m->Tc;
+    const long long N = m->lastN, NT = N * m->geo.Tc;
+    if (frames) *frames = m->geo.Tc;
     switch (which) {
         case 0: *d_ptr = m->feats; *count = NT * NMEL; return 0;
         case 1: case 2: case 3: case 4: *d_ptr = m->x[which - 1]; *count = NT * 512; return 0;
         case 5: *d_ptr = m->x[4]; *count = NT * C5; return 0;
         case 6: *d_ptr = m->pooled; *count = N * POOLED; return 0;
-        case 7: *d_ptr = m->lens; *count = N; return 0;
-        case 8: *d_ptr = m->rep_nvalid; *count = N; return 0;
-        case 9: *d_ptr = m->rep_T; *count = N; return 0;
+        case 7: *d_ptr = m->geo.lens; *count = N; return 0;
+        case 8: *d_ptr = m->geo.rep_nvalid; *count = N; return 0;
+        case 9: *d_ptr = m->geo.rep_T; *count = N; return 0;
     }
     dz_set_error("dz_sbx_peek: unknown buffer %d", which);
     return 2;

@@ -9,18 +9,6 @@ namespace {
 enum { WIN = 400, HOP = 160, NMEL = 80, EMB = 256, POOLED = 5120, MAXK = 8, FC_SPLIT = 16 };
 constexpr int kBlocks[4] = {3, 4, 6, 3};
 
-struct Carve {
-    char* base = nullptr;
-    size_t used = 0;
-    template <typename T>
-    T* take(size_t n) {
-        const size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += bytes;
-        return p;
-    }
-};
-
 int frames_for(int S, int stage) {
     if (stage < 0 || stage > 4) return -1;
     int T = S >= WIN ? 1 + (S - WIN) / HOP : 0;
@@ -40,7 +28,7 @@ struct dz_wsp {
     int lastN, lastRows;
 };
 
-static void wsp_carve(dz_wsp* m, Carve& a) {
+static void wsp_carve(dz_wsp* m, Arena& a) {
     const size_t N = m->Nm, T = m->T[0];
     const size_t big = (size_t)NMEL * T * 32;                       // the largest activation: layer 1, per row
     m->raw = a.take<float>(N * NMEL * T);
@@ -75,17 +63,10 @@ extern "C" int dz_wsp_create(dz_ctx* ctx, const dz_wsp_weights* w, int max_rows,
     memset(m, 0, sizeof(*m));
     m->ctx = ctx; m->w = *w; m->Nm = max_rows; m->S = num_samples;
     for (int s = 0; s < 5; ++s) m->T[s] = frames_for(num_samples, s);
-    Carve measure;
-    wsp_carve(m, measure);
-    const hipError_t err = hipMalloc((void**)&m->arena, measure.used);
-    if (err != hipSuccess) {
-        dz_set_error("dz_wsp_create: hipMalloc(%zu) failed: %s", measure.used, hipGetErrorString(err));
-        delete m;
-        return 1;
+    if (int rc = dz_arena_alloc("dz_wsp_create", m, wsp_carve)) {
+        dz_wsp_destroy(m);
+        return rc;
     }
-    Carve real;
-    real.base = m->arena;
-    wsp_carve(m, real);
     *out = m;
     return 0;
 }
@@ -163,14 +144,12 @@ static int wsp_head(dz_wsp* m, int N, int K, const float* d_weights, int Fw, int
 
 extern "C" int dz_wsp_forward(dz_wsp* m, const float* d_wave, long long wave_stride, const float* d_weights, int n_rows,
                               int weight_frames, float* d_out, void* stream) {
-    DZ_REQUIRE(m && d_wave && d_out, "dz_wsp_forward: NULL argument");
-    DZ_REQUIRE(n_rows >= 1 && n_rows <= m->Nm, "dz_wsp_forward: %d rows outside [1, %d]", n_rows, m->Nm);
-    DZ_REQUIRE(d_weights == nullptr || weight_frames >= 1, "dz_wsp_forward: weight_frames %d", weight_frames);
-    DZ_REQUIRE(wave_stride >= 0, "dz_wsp_forward: negative stride");
+    int rc = dz_check_rows_forward("dz_wsp_forward", m, m ? m->Nm : 0, d_wave, wave_stride, d_weights, n_rows,
+                                   weight_frames, d_out, "weight_frames");
+    if (rc) return rc;
     DZ_HIP(hipSetDevice(m->ctx->device));
     DzRangeScope range_scope(m->ctx->oflag_dev);
     hipStream_t st = (hipStream_t)stream;
-    int rc;
     m->lastN = n_rows;
     if ((rc = wsp_trunk(m, d_wave, wave_stride, n_rows, st))) return rc;
     return wsp_head(m, n_rows, 1, d_weights, weight_frames, 0, d_out, st);

@@ -302,16 +302,18 @@ class HipEmbedding(_HipModule):
         return out
 
 
-class HipEcapaEmbedding(_HipModule):
-    """speechbrain ECAPA-TDNN behind pyannote's ``PretrainedSpeakerEmbedding`` contract
-    (BASELINE.json config 3): ``(waveform (N,1,S), masks (N,F) | None) -> (N,192)``; a row whose
-    mask keeps fewer than 640 samples is NaN.  The reference reaches this model through the
-    fallback at models.py:59 and calls it at :262; it returns numpy there, a device tensor here
-    (``EmbeddingModel`` accepts both, models.py:263-264)."""
+class _HipSpeakerEmbedding(_HipModule):
+    """The plumbing of the ECAPA-TDNN, speechbrain x-vector and WeSpeaker handles: one C prefix (``_c``: ``dz_ecapa``,
+    ``dz_sbx``, ``dz_wsp``) names their create / destroy / forward / peek functions; ``(waveform (N,1,S), masks or
+    weights (N,F) | None) -> (N,dimension)``."""
 
-    dimension = 192
+    dimension: int
+    _c: str                     # the C prefix
+    _packer: type               # weights.Packed*
+    _frames_arg = "masks"       # what the (N, F) matrix is called (error messages)
+    _int32_peeks = frozenset()  # peek buffers that hold int32
 
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int, precision: Optional[str] = None):
         super().__init__(state, max_batch)
         self.precision = default_precision(precision)
 
@@ -319,145 +321,64 @@ class HipEcapaEmbedding(_HipModule):
         return {"precision": self.precision}
 
     def _pack(self, device):
-        return PackedEcapa(self._state, device, precision=self.precision)
+        return self._packer(self._state, device, precision=self.precision)
+
+    def _fn(self, name: str):
+        return getattr(_lib.load(), f"{self._c}_{name}")
 
     def _create(self, num_samples, cap):
         h = _lib.vp()
-        _lib.check(_lib.load().dz_ecapa_create(_lib.context(self.device.index),
-                                               C.byref(self._packed.struct), cap, num_samples,
-                                               C.byref(h)), "dz_ecapa_create")
+        _lib.check(self._fn("create")(_lib.context(self.device.index), C.byref(self._packed.struct), cap, num_samples,
+                                      C.byref(h)), f"{self._c}_create")
         return h
 
     def _destroy(self, h):
-        _lib.load().dz_ecapa_destroy(h)
+        self._fn("destroy")(h)
 
-    def __call__(self, waveform: torch.Tensor, masks: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, waveform: torch.Tensor, masks_or_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.device is None:
             self.to(waveform.device)
         rows = _as_rows(waveform.to(self.device))
         N, S = rows.shape
         mptr, fw = None, 0
-        if masks is not None:
-            masks = masks.to(self.device, torch.float32).contiguous()
-            if masks.ndim != 2 or masks.shape[0] != N:
-                raise ValueError(f"masks must be (batch, frames), got {tuple(masks.shape)}")
-            mptr, fw = masks.data_ptr(), masks.shape[1]
+        if masks_or_weights is not None:
+            m = masks_or_weights.to(self.device, torch.float32).contiguous()
+            if m.ndim != 2 or m.shape[0] != N:
+                raise ValueError(f"{self._frames_arg} must be (batch, frames), got {tuple(m.shape)}")
+            mptr, fw = m.data_ptr(), m.shape[1]
         handle = self._need(S, N)
         out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_ecapa_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S,
-                                                mptr, N, fw, out.data_ptr(), _stream_ptr(self.device)),
-                   "dz_ecapa_forward")
+        _lib.check(self._fn("forward")(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S, mptr, N, fw,
+                                       out.data_ptr(), _stream_ptr(self.device)), f"{self._c}_forward")
         return out
 
+    def _peek_raw(self, handle, which: int):
+        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
+        _lib.check(self._fn("peek")(handle, which, C.byref(ptr), C.byref(cnt), C.byref(frames)), f"{self._c}_peek")
+        return ptr, cnt.value, frames.value
+
+    def peek(self, num_samples: int, which: int):
+        """Intermediate of the last forward (parity tests; synchronises): ``(flat tensor, frames)``, see ``<_c>_peek``."""
+        return self.peek_handle(self._handles[num_samples][0], which)
+
+    def peek_handle(self, handle, which: int):
+        """``peek`` of a handle this model created for someone else (``StreamBatch``'s per-lane handles)."""
+        ptr, cnt, frames = self._peek_raw(handle, which)
+        out = torch.empty(cnt, dtype=torch.int32 if which in self._int32_peeks else torch.float32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        _lib.memcpy(out.data_ptr(), ptr, cnt * 4)
+        return out, frames
+
+
+class _HipGroupsEmbedding(_HipSpeakerEmbedding):
+    """ECAPA-TDNN and the speechbrain x-vector: the same batch geometry, hence the same groups forward."""
+
     def forward_groups(self, waveform: torch.Tensor, masks: torch.Tensor, normalize: bool = False) -> torch.Tensor:
-        """``waveform (G,1,S)``, ``masks (G,K,Fw)`` speaker-major -> ``(G,K,192)``: the ECAPA counterpart of
+        """``waveform (G,1,S)``, ``masks (G,K,Fw)`` speaker-major -> ``(G,K,dimension)``: the counterpart of
         ``HipEmbedding.forward_multi``.  Each chunk's K rows are one call of their own, with the batch geometry
         (padded frames, relative lengths) of those K rows alone, as the live reference embeds a chunk
         (``StreamingInference`` at batch 1); all G groups run in one launch sequence whose geometry is derived on
         the device — no synchronisation.  ``normalize``: L2-normalise every row (``EmbeddingNormalization(1)``)."""
-        if self.device is None:
-            self.to(waveform.device)
-        rows = _as_rows(waveform.to(self.device))
-        G, S = rows.shape
-        masks = masks.to(self.device, torch.float32).contiguous()
-        if masks.ndim != 3 or masks.shape[0] != G:
-            raise ValueError(f"masks must be (groups, speakers, frames), got {tuple(masks.shape)}")
-        K, fw = masks.shape[1], masks.shape[2]
-        handle = self._need(S, G * K)
-        out = torch.empty((G, K, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_ecapa_forward_groups(handle, rows.data_ptr(), rows.stride(0) if G > 1 else S,
-                                                       masks.data_ptr(), G, K, fw, 1 if normalize else 0,
-                                                       out.data_ptr(), _stream_ptr(self.device)),
-                   "dz_ecapa_forward_groups")
-        return out
-
-    @staticmethod
-    def groups_launch(handle, wave_ptr: int, wave_stride: int, masks_ptr: int, G: int, K: int, mask_frames: int,
-                      normalize: bool, out_ptr: int, stream_ptr: int) -> None:
-        """``dz_ecapa_forward_groups`` on a handle of this model (``StreamBatch``'s lanes): raw device addresses,
-        masks (G,K,Fw) contiguous, out (G*K,192); no synchronisation."""
-        _lib.check(_lib.load().dz_ecapa_forward_groups(handle, wave_ptr, wave_stride, masks_ptr, G, K, mask_frames,
-                                                       1 if normalize else 0, out_ptr, stream_ptr),
-                   "dz_ecapa_forward_groups")
-
-    def last_frames(self, num_samples: int) -> int:
-        """Frames of the batch geometry of the last forward (= those of its longest kept row, what every row is
-        padded to: ``dz_ecapa_peek``); no copy, no synchronisation.  ``bench.py --config 3`` prices its kernels with it."""
-        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
-        _lib.check(_lib.load().dz_ecapa_peek(self._handles[num_samples][0], 5, C.byref(ptr),
-                                             C.byref(cnt), C.byref(frames)), "dz_ecapa_peek")
-        return frames.value
-
-    def peek(self, num_samples: int, which: int) -> torch.Tensor:
-        """Intermediate of the last forward (parity tests): see ``dz_ecapa_peek``."""
-        return self.peek_handle(self._handles[num_samples][0], which)
-
-    def peek_handle(self, handle, which: int) -> torch.Tensor:
-        """``peek`` of a handle this model created for someone else (``StreamBatch``'s per-lane handles);
-        synchronises the device."""
-        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
-        _lib.check(_lib.load().dz_ecapa_peek(handle, which, C.byref(ptr), C.byref(cnt), C.byref(frames)),
-                   "dz_ecapa_peek")
-        dtype = torch.int32 if which in (5, 6, 7, 8) else torch.float32
-        out = torch.empty(cnt.value, dtype=dtype, device=self.device)
-        torch.cuda.synchronize(self.device)
-        import ctypes
-        hip = ctypes.CDLL("libamdhip64.so")
-        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(cnt.value * 4), 3)
-        if rc != 0:
-            raise _lib.DiartAmdError(f"hipMemcpy failed ({rc})")
-        return out, frames.value
-
-
-class HipSbXvectorEmbedding(_HipModule):
-    """speechbrain's x-vector (speechbrain/spkrec-xvect-voxceleb) behind pyannote's ``PretrainedSpeakerEmbedding``
-    contract, the wrapper the reference falls back to for it (models.py:59): ``(waveform (N,1,S), masks (N,F) |
-    None) -> (N,512)``; a row whose mask keeps fewer than 480 samples, or whose kept samples hold a NaN, is NaN.
-    The same call shape and batch geometry as ``HipEcapaEmbedding``, so the same engine forms take it."""
-
-    dimension = 512
-    min_num_samples = 480
-
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
-        super().__init__(state, max_batch)
-        self.precision = default_precision(precision)
-
-    def _extra_state(self):
-        return {"precision": self.precision}
-
-    def _pack(self, device):
-        return PackedSbXvector(self._state, device, precision=self.precision)
-
-    def _create(self, num_samples, cap):
-        h = _lib.vp()
-        _lib.check(_lib.load().dz_sbx_create(_lib.context(self.device.index), C.byref(self._packed.struct), cap,
-                                             num_samples, C.byref(h)), "dz_sbx_create")
-        return h
-
-    def _destroy(self, h):
-        _lib.load().dz_sbx_destroy(h)
-
-    def __call__(self, waveform: torch.Tensor, masks: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if self.device is None:
-            self.to(waveform.device)
-        rows = _as_rows(waveform.to(self.device))
-        N, S = rows.shape
-        mptr, fw = None, 0
-        if masks is not None:
-            masks = masks.to(self.device, torch.float32).contiguous()
-            if masks.ndim != 2 or masks.shape[0] != N:
-                raise ValueError(f"masks must be (batch, frames), got {tuple(masks.shape)}")
-            mptr, fw = masks.data_ptr(), masks.shape[1]
-        handle = self._need(S, N)
-        out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_sbx_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S, mptr, N, fw,
-                                              out.data_ptr(), _stream_ptr(self.device)), "dz_sbx_forward")
-        return out
-
-    def forward_groups(self, waveform: torch.Tensor, masks: torch.Tensor, normalize: bool = False) -> torch.Tensor:
-        """``waveform (G,1,S)``, ``masks (G,K,Fw)`` speaker-major -> ``(G,K,512)``: each chunk's K rows with the
-        batch geometry of those rows alone, all G groups in one launch sequence, no synchronisation (see
-        ``HipEcapaEmbedding.forward_groups``)."""
         if self.device is None:
             self.to(waveform.device)
         rows = _as_rows(waveform.to(self.device))
@@ -472,34 +393,48 @@ class HipSbXvectorEmbedding(_HipModule):
                            masks.shape[2], normalize, out.data_ptr(), _stream_ptr(self.device))
         return out
 
-    @staticmethod
-    def groups_launch(handle, wave_ptr: int, wave_stride: int, masks_ptr: int, G: int, K: int, mask_frames: int,
+    def groups_launch(self, handle, wave_ptr: int, wave_stride: int, masks_ptr: int, G: int, K: int, mask_frames: int,
                       normalize: bool, out_ptr: int, stream_ptr: int) -> None:
-        """``dz_sbx_forward_groups`` on a handle of this model (``StreamBatch``'s lanes): raw device addresses,
-        masks (G,K,Fw) contiguous, out (G*K,512); no synchronisation."""
-        _lib.check(_lib.load().dz_sbx_forward_groups(handle, wave_ptr, wave_stride, masks_ptr, G, K, mask_frames,
-                                                     1 if normalize else 0, out_ptr, stream_ptr),
-                   "dz_sbx_forward_groups")
-
-    def peek(self, num_samples: int, which: int):
-        """Intermediate of the last forward (parity tests): see ``dz_sbx_peek``; -> (tensor, Tc)."""
-        return self.peek_handle(self._handles[num_samples][0], which)
-
-    def peek_handle(self, handle, which: int):
-        """``peek`` of a handle this model created for someone else (``StreamBatch``'s lanes); synchronises."""
-        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
-        _lib.check(_lib.load().dz_sbx_peek(handle, which, C.byref(ptr), C.byref(cnt), C.byref(frames)), "dz_sbx_peek")
-        out = torch.empty(cnt.value, dtype=torch.int32 if which >= 7 else torch.float32, device=self.device)
-        torch.cuda.synchronize(self.device)
-        import ctypes
-        hip = ctypes.CDLL("libamdhip64.so")
-        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(cnt.value * 4), 3)
-        if rc != 0:
-            raise _lib.DiartAmdError(f"hipMemcpy failed ({rc})")
-        return out, frames.value
+        """``<_c>_forward_groups`` on a handle of this model (``StreamBatch``'s lanes): raw device addresses,
+        masks (G,K,Fw) contiguous, out (G*K,dimension); no synchronisation."""
+        _lib.check(self._fn("forward_groups")(handle, wave_ptr, wave_stride, masks_ptr, G, K, mask_frames,
+                                              1 if normalize else 0, out_ptr, stream_ptr), f"{self._c}_forward_groups")
 
 
-class HipWeSpeakerEmbedding(_HipModule):
+class HipEcapaEmbedding(_HipGroupsEmbedding):
+    """speechbrain ECAPA-TDNN behind pyannote's ``PretrainedSpeakerEmbedding`` contract
+    (BASELINE.json config 3): ``(waveform (N,1,S), masks (N,F) | None) -> (N,192)``; a row whose
+    mask keeps fewer than 640 samples is NaN.  The reference reaches this model through the
+    fallback at models.py:59 and calls it at :262; it returns numpy there, a device tensor here
+    (``EmbeddingModel`` accepts both, models.py:263-264)."""
+
+    dimension = 192
+    _c, _packer, _int32_peeks = "dz_ecapa", PackedEcapa, frozenset((5, 6, 7, 8))
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
+        super().__init__(state, max_batch, precision)
+
+    def last_frames(self, num_samples: int) -> int:
+        """Frames of the batch geometry of the last forward (= those of its longest kept row, what every row is
+        padded to: ``dz_ecapa_peek``); no copy, no synchronisation.  ``bench.py --config 3`` prices its kernels with it."""
+        return self._peek_raw(self._handles[num_samples][0], 5)[2]
+
+
+class HipSbXvectorEmbedding(_HipGroupsEmbedding):
+    """speechbrain's x-vector (speechbrain/spkrec-xvect-voxceleb) behind pyannote's ``PretrainedSpeakerEmbedding``
+    contract, the wrapper the reference falls back to for it (models.py:59): ``(waveform (N,1,S), masks (N,F) |
+    None) -> (N,512)``; a row whose mask keeps fewer than 480 samples, or whose kept samples hold a NaN, is NaN.
+    The same call shape and batch geometry as ``HipEcapaEmbedding``, so the same engine forms take it."""
+
+    dimension = 512
+    min_num_samples = 480
+    _c, _packer, _int32_peeks = "dz_sbx", PackedSbXvector, frozenset((7, 8, 9))
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
+        super().__init__(state, max_batch, precision)
+
+
+class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
     """pyannote.audio 3.1's ``WeSpeakerResNet34`` (pyannote/wespeaker-voxceleb-resnet34-LM): ``(waveform (N,1,S),
     weights (N,Fw) | None) -> (N,256)`` — the callable the reference loads through ``PyannoteLoader`` (models.py:42-59)
     and calls at blocks/embedding.py:56-65.  kaldi fbank, ResNet34 trunk on implicit-GEMM 2-D convolutions
@@ -507,46 +442,14 @@ class HipWeSpeakerEmbedding(_HipModule):
     with a NaN / Inf sample comes back NaN."""
 
     dimension = 256
+    _c, _packer, _frames_arg = "dz_wsp", PackedWeSpeaker, "weights"
 
     def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None):
-        super().__init__(state, max_batch)
-        self.precision = default_precision(precision)
-
-    def _extra_state(self):
-        return {"precision": self.precision}
-
-    def _pack(self, device):
-        return PackedWeSpeaker(self._state, device, precision=self.precision)
-
-    def _create(self, num_samples, cap):
-        h = _lib.vp()
-        _lib.check(_lib.load().dz_wsp_create(_lib.context(self.device.index), C.byref(self._packed.struct), cap,
-                                             num_samples, C.byref(h)), "dz_wsp_create")
-        return h
-
-    def _destroy(self, h):
-        _lib.load().dz_wsp_destroy(h)
+        super().__init__(state, max_batch, precision)
 
     def num_frames(self, num_samples: int, stage: int = 0) -> int:
         """Frames of the fbank (stage 0) or after layer 1 .. 4 (``dz_wsp_frames_for``)."""
         return int(_lib.load().dz_wsp_frames_for(int(num_samples), int(stage)))
-
-    def __call__(self, waveform: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if self.device is None:
-            self.to(waveform.device)
-        rows = _as_rows(waveform.to(self.device))
-        N, S = rows.shape
-        wptr, fw = None, 0
-        if weights is not None:
-            weights = weights.to(self.device, torch.float32).contiguous()
-            if weights.ndim != 2 or weights.shape[0] != N:
-                raise ValueError(f"weights must be (batch, frames), got {tuple(weights.shape)}")
-            wptr, fw = weights.data_ptr(), weights.shape[1]
-        handle = self._need(S, N)
-        out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_wsp_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S, wptr, N, fw,
-                                              out.data_ptr(), _stream_ptr(self.device)), "dz_wsp_forward")
-        return out
 
     def forward_multi(self, waveform: torch.Tensor, weights: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         """``waveform (B,1,S)``, ``weights (B,K,F)`` speaker-major -> ``(B,K,256)``: the reference's ``(B*K)``-row call
@@ -565,21 +468,6 @@ class HipWeSpeakerEmbedding(_HipModule):
                                                     weights.data_ptr(), B, K, fw, 1 if normalize else 0,
                                                     out.data_ptr(), _stream_ptr(self.device)), "dz_wsp_forward_multi")
         return out
-
-    def peek(self, num_samples: int, which: int):
-        """Intermediate of the last forward (parity tests; synchronises): ``(flat tensor, frames)``, see
-        ``dz_wsp_peek``."""
-        ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
-        _lib.check(_lib.load().dz_wsp_peek(self._handles[num_samples][0], which, C.byref(ptr), C.byref(cnt),
-                                           C.byref(frames)), "dz_wsp_peek")
-        out = torch.empty(cnt.value, dtype=torch.float32, device=self.device)
-        torch.cuda.synchronize(self.device)
-        import ctypes
-        hip = ctypes.CDLL("libamdhip64.so")
-        rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(cnt.value * 4), 3)
-        if rc != 0:
-            raise _lib.DiartAmdError(f"hipMemcpy failed ({rc})")
-        return out, frames.value
 
 
 # --------------------------------------------------------------------------- #

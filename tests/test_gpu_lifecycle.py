@@ -1,8 +1,9 @@
 """Lifecycle of the engines on the GPU: a service creates and drops `StreamBatch` engines as stream groups come and go
 and runs for days (the reference's `StreamingInference` never ends, /root/reference/src/diart/inference.py:101-147).
 
-* engines give their device memory back: the library owns its scratch arenas (hipMalloc behind `dz_seg_create` /
-  `dz_emb_create`, not torch's allocator), so a leak would not show in `torch.cuda.memory_allocated`;
+* engines and the speaker-embedding handles give their device memory back: the library owns its scratch arenas
+  (hipMalloc behind `dz_seg_create`, `dz_emb_create`, `dz_ecapa_create`, ..., not torch's allocator), so a leak would
+  not show in `torch.cuda.memory_allocated`;
 * a long run neither grows nor drifts: after thousands of steps the free device memory is where it was after the first
   hundred, and the networks' outputs for a window are bit-identical to what a FRESH engine computes for it."""
 import gc
@@ -53,6 +54,41 @@ def test_engines_release_their_device_memory(gpu):
     print("free device memory after each engine, MB:", [round(a / MB) for a in after])
     assert max(after[5:]) - min(after[5:]) < 8 * MB, [round(a / MB) for a in after]
     assert after[0] - after[-1] < 512 * MB, [round(a / MB) for a in after]          # the pools themselves stay small
+
+
+_SPEAKER_MODELS = {"ecapa": ("HipEcapaEmbedding", "synth_ecapa_state", "dz_ecapa_create"),
+                   "sb-xvector": ("HipSbXvectorEmbedding", "synth_sb_xvector_state", "dz_sbx_create"),
+                   "wespeaker": ("HipWeSpeakerEmbedding", "synth_wespeaker_state", "dz_wsp_create")}
+
+
+@pytest.mark.parametrize("arch", list(_SPEAKER_MODELS))
+def test_speaker_embedding_handles_release_their_device_memory(gpu, arch):
+    """The ECAPA-TDNN, speechbrain x-vector and WeSpeaker handles own a hipMalloc arena each (tens of MB at 8 rows of
+    2 s): create one, run a forward on it and destroy it, ten times; after the first few the free device memory does
+    not move.  A create that its argument check refuses names the entry point and takes nothing."""
+    from diart_amd import models as M
+    from diart_amd import synth
+    from diart_amd._lib import DiartAmdError
+    cls, state, create = _SPEAKER_MODELS[arch]
+    emb = getattr(M, cls)(getattr(synth, state)(), max_batch=8).to(gpu)
+    S, N = 32000, 8
+    wave = torch.from_numpy(synth.synth_streams(N, 2.0, seed0=31)).to(gpu)[:, None, :S]
+    after = []
+    for _ in range(10):
+        h = emb._create(S, N)
+        emb._handles[S] = (h, N)
+        assert torch.isfinite(emb(wave)).all()
+        del emb._handles[S]
+        emb._destroy(h)
+        after.append(_free(gpu))
+    print(f"{arch}: free device memory after each handle, MB:", [round(a / MB) for a in after])
+    assert max(after[3:]) - min(after[3:]) < 8 * MB, [round(a / MB) for a in after]
+    before = _free(gpu)
+    for _ in range(10):
+        with pytest.raises(DiartAmdError, match=f"{create}: max_rows {N}, 100 samples"):
+            emb._create(100, N)
+    assert not emb._handles
+    assert abs(_free(gpu) - before) < 8 * MB
 
 
 def test_soak_memory_flat_and_no_drift(gpu):
