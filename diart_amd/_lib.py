@@ -119,6 +119,8 @@ SIGNATURES = {
     "dz_wsp_create": (C.c_int, [vp, C.POINTER(WspWeights), C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_wsp_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
     "dz_wsp_forward_multi": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_wsp_trunk": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp]),
+    "dz_wsp_pool": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_wsp_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_wsp_destroy": (C.c_int, [vp]),
     "dz_resample_geometry": (C.c_int, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]),

@@ -155,6 +155,30 @@ extern "C" int dz_wsp_forward(dz_wsp* m, const float* d_wave, long long wave_str
     return wsp_head(m, n_rows, 1, d_weights, weight_frames, 0, d_out, st);
 }
 
+extern "C" int dz_wsp_trunk(dz_wsp* m, const float* d_wave, long long wave_stride, int batch, void* stream) {
+    DZ_REQUIRE(m && d_wave, "dz_wsp_trunk: NULL argument");
+    DZ_REQUIRE(batch >= 1 && batch <= m->Nm, "dz_wsp_trunk: batch %d outside [1, %d]", batch, m->Nm);
+    DZ_REQUIRE(wave_stride >= 0, "dz_wsp_trunk: negative stride");
+    DZ_HIP(hipSetDevice(m->ctx->device));
+    DzRangeScope range_scope(m->ctx->oflag_dev);
+    m->lastN = batch;
+    return wsp_trunk(m, d_wave, wave_stride, batch, (hipStream_t)stream);
+}
+
+extern "C" int dz_wsp_pool(dz_wsp* m, const float* d_weights, int batch, int num_speakers, int weight_frames,
+                           int normalize, float* d_out, void* stream) {
+    DZ_REQUIRE(m && d_weights && d_out, "dz_wsp_pool: NULL argument");
+    DZ_REQUIRE(batch >= 1 && batch == m->lastN, "dz_wsp_pool: batch %d, the handle's last trunk ran %d", batch,
+               m->lastN);
+    DZ_REQUIRE(num_speakers >= 1 && num_speakers <= MAXK, "dz_wsp_pool: %d speakers outside [1, %d]", num_speakers,
+               (int)MAXK);
+    DZ_REQUIRE(weight_frames >= 1, "dz_wsp_pool: weight_frames %d", weight_frames);
+    DZ_HIP(hipSetDevice(m->ctx->device));
+    DzRangeScope range_scope(m->ctx->oflag_dev);
+    return wsp_head(m, batch, num_speakers, d_weights, weight_frames, normalize, d_out, (hipStream_t)stream);
+}
+
+// the two halves on one stream; every argument is checked before the first launch
 extern "C" int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wave_stride, const float* d_weights,
                                     int batch, int num_speakers, int weight_frames, int normalize, float* d_out,
                                     void* stream) {
@@ -164,13 +188,8 @@ extern "C" int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wa
                num_speakers, (int)MAXK);
     DZ_REQUIRE(weight_frames >= 1, "dz_wsp_forward_multi: weight_frames %d", weight_frames);
     DZ_REQUIRE(wave_stride >= 0, "dz_wsp_forward_multi: negative stride");
-    DZ_HIP(hipSetDevice(m->ctx->device));
-    DzRangeScope range_scope(m->ctx->oflag_dev);
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    m->lastN = batch;
-    if ((rc = wsp_trunk(m, d_wave, wave_stride, batch, st))) return rc;
-    return wsp_head(m, batch, num_speakers, d_weights, weight_frames, normalize, d_out, st);
+    if (int rc = dz_wsp_trunk(m, d_wave, wave_stride, batch, stream)) return rc;
+    return dz_wsp_pool(m, d_weights, batch, num_speakers, weight_frames, normalize, d_out, stream);
 }
 
 // kernel-level entry point of k_conv2d.hip (parity tests): the launcher checks the operands

@@ -469,6 +469,18 @@ class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
                                                     out.data_ptr(), _stream_ptr(self.device)), "dz_wsp_forward_multi")
         return out
 
+    def trunk_launch(self, handle, wave_ptr: int, wave_stride: int, batch: int, stream_ptr: int) -> None:
+        """``dz_wsp_trunk`` on a handle of this model (``WeSpeakerBatch``'s lanes): fbank + ResNet34 of ``batch``
+        windows at raw device addresses, into the handle; no synchronisation."""
+        _lib.check(_lib.load().dz_wsp_trunk(handle, wave_ptr, wave_stride, batch, stream_ptr), "dz_wsp_trunk")
+
+    def pool_launch(self, handle, weights_ptr: int, batch: int, K: int, weight_frames: int, normalize: bool,
+                    out_ptr: int, stream_ptr: int) -> None:
+        """``dz_wsp_pool`` of the handle's last ``trunk_launch``: weights (batch,K,Fw) contiguous, out
+        (batch*K,256); the caller has ordered ``stream_ptr`` behind the trunk's stream.  No synchronisation."""
+        _lib.check(_lib.load().dz_wsp_pool(handle, weights_ptr, batch, K, weight_frames, 1 if normalize else 0,
+                                           out_ptr, stream_ptr), "dz_wsp_pool")
+
 
 # --------------------------------------------------------------------------- #
 # loaders (picklable, no HIP state)

@@ -28,7 +28,8 @@ D2H copy.  Nothing in the launch waits for the GPU, so with two lanes the ECAPA 
 the segmentation of step t + 1.
 
 ``VadBatch`` is the segmentation-only form for ``VoiceActivityDetection``: no embedding, no clustering; the head kernel
-writes each stream's speech track and only that track reaches the host's output tails.
+writes each stream's speech track and only that track reaches the host's output tails.  ``WeSpeakerBatch`` is the form
+for the WeSpeaker ResNet34 embedding, whose trunk is the long chain of the step: the segmentation runs under it.
 """
 from __future__ import annotations
 
@@ -166,7 +167,206 @@ class AudioRing:
         return out
 
 
-class StreamBatch:
+class _StepEngine:
+    """What the N-stream engines (``StreamBatch``, ``VadBatch``, ``WeSpeakerBatch``) share: how the host waits for a
+    step, the front half of ``launch`` (rows, slots, start times) and the warm-up on silence.  A subclass provides
+    ``_launch_rows``, ``finish`` and ``reset``, and the state ``n``, ``step``, ``device``, ``max_inflight``,
+    ``warmup_steps``, ``_t``, ``_steps``, ``_warming``, ``_real_launches``, ``host_seconds``."""
+
+    def _host_wait(self, wait: Optional[str]) -> None:
+        """How the host waits.  With cores to spare the launching thread spins on the step's `done` event (lowest
+        latency) and the pool's workers poll 40 us for the next job; a rank that has ~2 cores for itself (8 ranks
+        on a node's 16 usable cores) cannot afford either: the event is then a blocking one (the thread sleeps in
+        the driver until the GPU signals) and the workers sleep at once.  ``wait`` = spin | block | auto."""
+        from .config import setting
+        from .hostinfo import usable_cores
+        try:
+            ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
+        except ValueError:
+            ranks_here = 1
+        self.cores_per_rank = usable_cores() / ranks_here
+        mode = str(setting("wait", wait, "auto"))
+        if mode not in ("auto", "spin", "block"):
+            raise ValueError(f"{type(self).__name__}: wait={mode!r} (expected auto | spin | block)")
+        self.blocking_wait = mode == "block" or (mode == "auto" and self.cores_per_rank < 4)
+        # idle pool workers poll 40 us for the next job when this rank has cores to spare, else they sleep at once
+        # (process-wide setting: the newest engine's situation decides, ADVICE r5)
+        _lib.load().dz_host_pool_set_spin(0 if self.cores_per_rank < 4 else 40)
+
+    def _refuse_xvector_experiments(self) -> None:
+        """The experiment switches of the x-vector engine (experiments build only) mean nothing to its siblings."""
+        who = type(self).__name__
+        for name in ("DZ_SEG_FRONT", "DZ_SHARED_EMB", "DZ_CONV0_PAIR"):
+            if _lib.exp_env(name, "0") != "0":
+                raise ValueError(f"{who}: {name} is an experiment of the x-vector engine; it has no meaning here")
+        if _lib.exp_env("DZ_ABLATE", ""):
+            raise ValueError(f"{who}: DZ_ABLATE is an experiment of the x-vector engine; it has no meaning here")
+
+    def launch(self, waves, starts=None, slots: Optional[Sequence[int]] = None) -> dict:
+        """Enqueue the GPU work for one step.  ``waves``: (N, S) or (N, 1, S) float32 on the GPU
+        (a strided rolling-window view is used in place) or an ``AudioRing`` holding a complete
+        window.  ``starts``: start time in seconds of each
+        stream's window (default: the number of windows that stream slot has seen since its last
+        ``reset`` x ``step``), used by the output tail only.
+        ``slots``: which of the ``num_streams`` clustering / tail states the rows belong to, for a
+        step in which only some streams have a new window (``len(slots)`` rows; default: all, in
+        order).  Returns a ticket for ``finish``; does not wait for the GPU."""
+        ring = waves if isinstance(waves, AudioRing) else None
+        if ring is not None:
+            assert ring.filled == ring.window, "the ring does not hold a complete window yet"
+            rows, N, S = None, ring.n, ring.window
+            base, stride = ring.raw()
+        else:
+            rows = _as_rows(waves)
+            N, S = rows.shape
+            base, stride = rows.data_ptr(), (rows.stride(0) if N > 1 else S)
+        if slots is None:
+            assert N == self.n, f"expected {self.n} streams, got {N}"
+        else:
+            slots = [int(i) for i in slots]
+            assert N == len(slots) and 1 <= N <= self.n and len(set(slots)) == N, "bad slots"
+            assert all(0 <= i < self.n for i in slots), "slot out of range"
+        slot = self._launch_rows(base, stride, N, S, rows, ring)
+        slot["slots"] = slots
+        idx = np.arange(self.n) if slots is None else np.asarray(slots, dtype=np.int64)
+        slot["starts"] = self._steps[idx] * self.step if starts is None else starts
+        self._steps[idx] += 1
+        return slot
+
+    def _warm_up(self, S: int) -> None:
+        """A few overlapped steps on silence before the first real one of this window size.  Besides the
+        start-up stall proper (the output tail's host buffers, allocated before the first launch: see
+        `StreamBatch._launch_rows`), a fresh process shows two 7 - 12 ms intervals within its first ~8 steps
+        (tools/stall_probe.py, no tracer; profiles/r03_f_stall_probe.txt): one-time set-up for the first
+        launches of each kernel on each queue — gone after warm steps, while warming the streams, the copy
+        path and the events alone did not move them.  Complete steps (GPU + host half: the worker pool's
+        threads start here too) while no stream has any state yet, GPU-only steps for a second window size
+        later on; ~0.1 s of construction time instead of latency spikes in a live stream.  ``warmup=<steps>``
+        (0 = off).
+
+        Complete steps (and the reset() that forgets them) only while NO launch has been issued for a caller:
+        counting finished steps instead (round 3) let a second window size, or a first finish() that comes
+        after several launches (FileBatch never calls finish), wipe the clustering / tail state and the
+        step counters under tickets that were still in flight."""
+        steps = self.warmup_steps
+        if steps <= 0:
+            return
+        zeros = torch.zeros((self.n, S), dtype=torch.float32, device=self.device)
+        saved = dict(self.host_seconds)
+        inflight: List[dict] = []
+        t_saved = self._t
+        self._warming = True
+        try:
+            if self._real_launches == 0:                     # complete steps, then forget them
+                for _ in range(steps):
+                    inflight.append(self.launch(zeros))
+                    if len(inflight) >= self.max_inflight:
+                        self.finish(inflight.pop(0))
+                while inflight:
+                    self.finish(inflight.pop(0))
+            else:                                            # GPU-only steps: no stream state is touched
+                for _ in range(steps):
+                    inflight.append(self._launch_rows(zeros.data_ptr(), zeros.stride(0), self.n, S, zeros))
+                    if len(inflight) >= self.max_inflight:
+                        t = inflight.pop(0)
+                        self._wait(t)
+                        t["busy"], t["keep"] = False, None
+                for t in inflight:
+                    self._wait(t)
+                    t["busy"], t["keep"] = False, None
+        finally:
+            self._warming = False
+        torch.cuda.synchronize(self.device)
+        if self._real_launches == 0:
+            self.reset()
+            self._t = 0
+        else:
+            self._t = t_saved
+        self.host_seconds.update(saved)
+
+    def _wait(self, ticket: dict) -> None:
+        """Block until the GPU half of the step is done and its results are in pinned host memory."""
+        t0 = _time.perf_counter()
+        ticket["done"].synchronize()
+        self.host_seconds["wait"] += _time.perf_counter() - t0
+
+    def __call__(self, waves):
+        return self.finish(self.launch(waves))
+
+
+class _DiarizationEngine(_StepEngine):
+    """The host half of the engines that diarize (``StreamBatch``, ``WeSpeakerBatch``): N clustering states and
+    (``tail=True``) N aggregation / binarisation states, stepped on the C++ workers from a ticket's pinned
+    segmentation scores and embeddings.  A subclass sets ``clustering``, ``tail``, ``with_tail``, ``cluster_threads``,
+    ``max_speakers``, ``tau_active``, ``duration``, ``latency`` and ``_real_steps``."""
+
+    def set_host_threads(self, n: int) -> int:
+        """Host threads of the per-stream CPU stages (clustering, aggregation + binarisation) from now on."""
+        n = max(1, int(n))
+        self.cluster_threads = self.clustering.num_threads = n
+        if self.tail is not None:
+            self.tail.num_threads = n
+        return n
+
+    def reset(self, slot: Optional[int] = None):
+        """Forget the clustering / aggregation state of every stream, or of one slot."""
+        self.clustering.reset(slot)
+        if self.tail is not None:
+            self.tail.reset(slot)
+        if slot is None:
+            self._steps[:] = 0
+        else:
+            self._steps[slot] = 0
+
+    def finish(self, ticket: dict, want_scores: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Wait for the step's GPU work, run the N clustering updates.
+        -> (segmentation (N,F,K) f32, embeddings (N,K,D) f32, scores (N,F,G) f64 | None, assign (N,K)).
+        The arrays (and ``ticket["tail"]``) are views of buffers that a later ``launch`` / ``finish``
+        reuses: copy what has to outlive the next step."""
+        self._wait(ticket)
+        if not self._warming:
+            self._real_steps += 1
+        t1 = _time.perf_counter()
+        # The ticket's slot is ALWAYS handed back (ADVICE r2): an exception between here and the end
+        # used to leak it, and every later launch then allocated a new pinned slot while kernels were
+        # running.  The range flag (an f16x3 operand beyond +-65504 is an error, not a clamp) is
+        # checked first: a flagged step's results are clamped garbage and must not reach the
+        # clustering state of the streams; the caller gets error 6 for THIS step and the streams
+        # skip one window.  The flag is one word per device: with `depth` steps in flight it may have
+        # been raised by a kernel of a later step, whose own finish() then passes — over-reporting by
+        # at most `depth - 1` steps, never under-reporting.
+        try:
+            _lib.range_check(self.device.index)
+            N, slots = ticket["rows"], ticket["slots"]
+            seg = ticket["seg_h"].numpy()[:N]
+            emb = ticket["emb_h"].numpy()[:N]
+            scores, assign = self.clustering(seg, emb, want_scores or self.with_tail, slots=slots)
+            if self.with_tail:
+                # diarization.py:190,203-232 for every stream: aggregate the overlapping windows of the
+                # region [t - latency, t - latency + step) and binarise it
+                if self.tail is None:
+                    self.tail = BatchedOutputTail(self.n, seg.shape[1], self.max_speakers, self.step,
+                                                  self.latency, self.tau_active,
+                                                  num_threads=self.cluster_threads)
+                ticket["tail"] = self.tail(scores, ticket["starts"], self.duration / seg.shape[1], slots=slots)
+        finally:
+            ticket["busy"] = False
+            ticket["keep"] = None
+            self.host_seconds["work"] += _time.perf_counter() - t1
+        return seg, emb, scores, assign
+
+    def diarize(self, waves: torch.Tensor, starts=None):
+        """One step of every stream, end to end: -> list of N ``Annotation`` (the speech turns of the
+        region this step finalises, what ``SpeakerDiarization.__call__`` returns per chunk) —
+        requires ``tail=True``."""
+        assert self.with_tail, f"construct {type(self).__name__}(tail=True)"
+        ticket = self.launch(waves, starts)
+        self.finish(ticket, want_scores=False)
+        _, _, _, _, turns, nturns = ticket["tail"]
+        return [BatchedOutputTail.annotation(turns[i], int(nturns[i])) for i in range(self.n)]
+
+
+class StreamBatch(_DiarizationEngine):
     def __init__(self, segmentation: HipSegmentation,
                  embedding: Union[HipEmbedding, HipEcapaEmbedding, HipSbXvectorEmbedding], num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
@@ -199,10 +399,10 @@ class StreamBatch:
         about 6.2 GB of device memory per lane — and ``emb_split`` must be 1.  A ``HipSbXvectorEmbedding``
         (speechbrain/spkrec-xvect-voxceleb) runs in the same form (about 1.7 GB of arena per lane at 192 rows of 5 s)."""
         if isinstance(embedding, HipWeSpeakerEmbedding):
-            raise ValueError("StreamBatch: the WeSpeaker ResNet34 embedding does not run on the N-stream engine; it runs "
+            raise ValueError("StreamBatch does not run the WeSpeaker ResNet34 embedding; it runs "
                              "HipEmbedding (pyannote/embedding), HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb) and "
                              "HipSbXvectorEmbedding (speechbrain/spkrec-xvect-voxceleb). "
-                             "Use the blocks API (SpeakerDiarization) for pyannote/wespeaker-voxceleb-resnet34-LM")
+                             "Use WeSpeakerBatch (the N-stream engine of pyannote/wespeaker-voxceleb-resnet34-LM)")
         from .config import setting
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)
@@ -280,23 +480,7 @@ class StreamBatch:
         # DZ_ABLATE=noemb | noseg: TIMING EXPERIMENT (results are wrong): one of the two networks is not launched,
         # to see what the step costs when the other one has the chip to itself
         self._ablate = _lib.exp_env("DZ_ABLATE", "")
-        # How the host waits.  With cores to spare the launching thread spins on the step's `done` event (lowest
-        # latency) and the pool's workers poll 40 us for the next job; a rank that has ~2 cores for itself (8 ranks
-        # on a node's 16 usable cores) cannot afford either: the event is then a blocking one (the thread sleeps in
-        # the driver until the GPU signals) and the workers sleep at once.  DZ_WAIT=spin | block, DZ_POOL_SPIN_US.
-        from .hostinfo import usable_cores
-        try:
-            ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
-        except ValueError:
-            ranks_here = 1
-        self.cores_per_rank = usable_cores() / ranks_here
-        mode = str(setting("wait", wait, "auto"))
-        if mode not in ("auto", "spin", "block"):
-            raise ValueError(f"StreamBatch: wait={mode!r} (expected auto | spin | block)")
-        self.blocking_wait = mode == "block" or (mode == "auto" and self.cores_per_rank < 4)
-        # idle pool workers poll 40 us for the next job when this rank has cores to spare, else they sleep at once
-        # (process-wide setting: the newest engine's situation decides)
-        _lib.load().dz_host_pool_set_spin(0 if self.cores_per_rank < 4 else 40)
+        self._host_wait(wait)
         self.shared_stats = _lib.exp_env("DZ_SHARED_STATS", "1") != "0"
         self.shared_emb = _lib.exp_env("DZ_SHARED_EMB", "0") != "0"
         self.lag = self.depth - 1 if self.shared_emb else 0
@@ -345,24 +529,6 @@ class StreamBatch:
         self._slots: List[dict] = []
         self._lib = _lib.load()
         self._ctx = _lib.context(self.device.index)
-
-    def set_host_threads(self, n: int) -> int:
-        """Host threads of the per-stream CPU stages (clustering, aggregation + binarisation) from now on."""
-        n = max(1, int(n))
-        self.cluster_threads = self.clustering.num_threads = n
-        if self.tail is not None:
-            self.tail.num_threads = n
-        return n
-
-    def reset(self, slot: Optional[int] = None):
-        """Forget the clustering / aggregation state of every stream, or of one slot."""
-        self.clustering.reset(slot)
-        if self.tail is not None:
-            self.tail.reset(slot)
-        if slot is None:
-            self._steps[:] = 0
-        else:
-            self._steps[slot] = 0
 
     # ------------------------------------------------------------------ GPU half
     def _slot(self, F: int, K: int, D: int) -> dict:
@@ -417,37 +583,6 @@ class StreamBatch:
                     self.emb._destroy(h)
         except Exception:
             pass
-
-    def launch(self, waves, starts=None, slots: Optional[Sequence[int]] = None) -> dict:
-        """Enqueue the GPU work for one step.  ``waves``: (N, S) or (N, 1, S) float32 on the GPU
-        (a strided rolling-window view is used in place) or an ``AudioRing`` holding a complete
-        window.  ``starts``: start time in seconds of each
-        stream's window (default: the number of windows that stream slot has seen since its last
-        ``reset`` x ``step``), used by the output tail only.
-        ``slots``: which of the ``num_streams`` clustering / tail states the rows belong to, for a
-        step in which only some streams have a new window (``len(slots)`` rows; default: all, in
-        order).  Returns a ticket for ``finish``."""
-        ring = waves if isinstance(waves, AudioRing) else None
-        if ring is not None:
-            assert ring.filled == ring.window, "the ring does not hold a complete window yet"
-            rows, N, S = None, ring.n, ring.window
-            base, stride = ring.raw()
-        else:
-            rows = _as_rows(waves)
-            N, S = rows.shape
-            base, stride = rows.data_ptr(), (rows.stride(0) if N > 1 else S)
-        if slots is None:
-            assert N == self.n, f"expected {self.n} streams, got {N}"
-        else:
-            slots = [int(i) for i in slots]
-            assert N == len(slots) and 1 <= N <= self.n and len(set(slots)) == N, "bad slots"
-            assert all(0 <= i < self.n for i in slots), "slot out of range"
-        slot = self._launch_rows(base, stride, N, S, rows, ring)
-        slot["slots"] = slots
-        idx = np.arange(self.n) if slots is None else np.asarray(slots, dtype=np.int64)
-        slot["starts"] = self._steps[idx] * self.step if starts is None else starts
-        self._steps[idx] += 1
-        return slot
 
     def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
         """The GPU half of a step for N <= num_streams rows of S samples at ``base + i * stride``
@@ -577,60 +712,6 @@ class StreamBatch:
         self._t += 1
         return slot
 
-    def _warm_up(self, S: int) -> None:
-        """A few overlapped steps on silence before the first real one of this window size.  Besides the
-        start-up stall proper (the output tail's host buffers, now allocated before the first launch: see
-        `_launch_rows`), a fresh process shows two 7 - 12 ms intervals within its first ~8 steps
-        (tools/stall_probe.py, no tracer; profiles/r03_f_stall_probe.txt): one-time set-up for the first
-        launches of each kernel on each queue — gone after warm steps, while warming the streams, the copy
-        path and the events alone did not move them.  Complete steps (GPU + host half: the worker pool's
-        threads start here too) while no stream has any state yet, GPU-only steps for a second window size
-        later on; ~0.1 s of construction time instead of latency spikes in a live stream.  ``warmup=<steps>``
-        (0 = off)."""
-        steps = self.warmup_steps
-        if steps <= 0:
-            return
-        zeros = torch.zeros((self.n, S), dtype=torch.float32, device=self.device)
-        saved = dict(self.host_seconds)
-        inflight: List[dict] = []
-        # Complete steps (and the reset() that forgets them) only while NO launch has been issued for a caller:
-        # counting finished steps instead (round 3) let a second window size, or a first finish() that comes
-        # after several launches (FileBatch never calls finish), wipe the clustering / tail state and the
-        # step counters under tickets that were still in flight (ADVICE r3).
-        if self._real_launches == 0:                     # complete steps, then forget them
-            self._warming = True
-            try:
-                for _ in range(steps):
-                    inflight.append(self.launch(zeros))
-                    if len(inflight) >= self.max_inflight:
-                        self.finish(inflight.pop(0))
-                while inflight:
-                    self.finish(inflight.pop(0))
-            finally:
-                self._warming = False
-            torch.cuda.synchronize(self.device)
-            self.reset()
-            self._t = 0
-        else:                                            # GPU-only steps: no stream state is touched
-            base, stride = zeros.data_ptr(), zeros.stride(0)
-            t_saved = self._t
-            self._warming = True
-            try:
-                for _ in range(steps):
-                    inflight.append(self._launch_rows(base, stride, self.n, S, zeros))
-                    if len(inflight) >= self.max_inflight:
-                        t = inflight.pop(0)
-                        self._wait(t)
-                        t["busy"], t["keep"] = False, None
-                for t in inflight:
-                    self._wait(t)
-                    t["busy"], t["keep"] = False, None
-            finally:
-                self._warming = False
-                self._t = t_saved
-            torch.cuda.synchronize(self.device)
-        self.host_seconds.update(saved)
-
     def _enqueue_pool(self, slot: dict):
         """Statistics pooling + Linear + normalisation of a launched step (they consume the OSP
         weights, i.e. wait for its segmentation), the copy of its results to pinned memory and its
@@ -681,44 +762,6 @@ class StreamBatch:
         slot["pool"] = None
 
     # ------------------------------------------------------------------ host half
-    def finish(self, ticket: dict, want_scores: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
-        """Wait for the step's GPU work, run the N clustering updates.
-        -> (segmentation (N,F,K) f32, embeddings (N,K,D) f32, scores (N,F,G) f64 | None, assign (N,K)).
-        The arrays (and ``ticket["tail"]``) are views of buffers that a later ``launch`` / ``finish``
-        reuses: copy what has to outlive the next step."""
-        import time as _time
-        self._wait(ticket)
-        if not self._warming:
-            self._real_steps += 1
-        t1 = _time.perf_counter()
-        # The ticket's slot is ALWAYS handed back (ADVICE r2): an exception between here and the end
-        # used to leak it, and every later launch then allocated a new pinned slot while kernels were
-        # running.  The range flag (an f16x3 operand beyond +-65504 is an error, not a clamp) is
-        # checked first: a flagged step's results are clamped garbage and must not reach the
-        # clustering state of the streams; the caller gets error 6 for THIS step and the streams
-        # skip one window.  The flag is one word per device: with `depth` steps in flight it may have
-        # been raised by a kernel of a later step, whose own finish() then passes — over-reporting by
-        # at most `depth - 1` steps, never under-reporting.
-        try:
-            _lib.range_check(self.device.index)
-            N, slots = ticket["rows"], ticket["slots"]
-            seg = ticket["seg_h"].numpy()[:N]
-            emb = ticket["emb_h"].numpy()[:N]
-            scores, assign = self.clustering(seg, emb, want_scores or self.with_tail, slots=slots)
-            if self.with_tail:
-                # diarization.py:190,203-232 for every stream: aggregate the overlapping windows of the
-                # region [t - latency, t - latency + step) and binarise it
-                if self.tail is None:
-                    self.tail = BatchedOutputTail(self.n, seg.shape[1], self.max_speakers, self.step,
-                                                  self.latency, self.tau_active,
-                                                  num_threads=self.cluster_threads)
-                ticket["tail"] = self.tail(scores, ticket["starts"], self.duration / seg.shape[1], slots=slots)
-        finally:
-            ticket["busy"] = False
-            ticket["keep"] = None
-            self.host_seconds["work"] += _time.perf_counter() - t1
-        return seg, emb, scores, assign
-
     def _wait(self, ticket: dict) -> None:
         """Block until the GPU half of the step is done and its results are in pinned host memory."""
         import time as _time
@@ -728,21 +771,8 @@ class StreamBatch:
         ticket["done"].synchronize()
         self.host_seconds["wait"] += _time.perf_counter() - t0
 
-    def __call__(self, waves: torch.Tensor):
-        return self.finish(self.launch(waves))
 
-    def diarize(self, waves: torch.Tensor, starts=None):
-        """One step of every stream, end to end: -> list of N ``Annotation`` (the speech turns of the
-        region this step finalises, what ``SpeakerDiarization.__call__`` returns per chunk) —
-        requires ``tail=True``."""
-        assert self.with_tail, "construct StreamBatch(tail=True)"
-        ticket = self.launch(waves, starts)
-        self.finish(ticket, want_scores=False)
-        _, _, _, _, turns, nturns = ticket["tail"]
-        return [BatchedOutputTail.annotation(turns[i], int(nturns[i])) for i in range(self.n)]
-
-
-class VadBatch:
+class VadBatch(_StepEngine):
     """``VoiceActivityDetection`` of N concurrent streams, one chunk each per step: the segmentation-only form of the
     N-stream engine.  Per stream it produces what that stream's own ``VoiceActivityDetection`` (blocks/vad.py,
     reference ``blocks/vad.py:136-191``) produces: the speech track ``max over speakers`` of the segmentation and the
@@ -766,15 +796,10 @@ class VadBatch:
                  warmup: Optional[int] = None, host_threads: int = 8, serial: bool = False):
         from .blocks.diarization import _latency
         from .config import setting
-        from .hostinfo import usable_cores
         if serial:
             raise ValueError("VadBatch: serial=True is the measurement engine of StreamBatch (bench.py's roofline "
                              "pass); the VAD engine has no serial form")
-        for name in ("DZ_SEG_FRONT", "DZ_SHARED_EMB", "DZ_CONV0_PAIR"):
-            if _lib.exp_env(name, "0") != "0":
-                raise ValueError(f"VadBatch: {name} is an experiment of the x-vector engine; it has no meaning here")
-        if _lib.exp_env("DZ_ABLATE", ""):
-            raise ValueError("VadBatch: DZ_ABLATE is an experiment of the x-vector engine; it has no meaning here")
+        self._refuse_xvector_experiments()
         self.duration, self.step = float(duration), float(step)
         self.latency = float(_latency(latency, self.step, self.duration))
         if not self.step <= self.latency <= self.duration:
@@ -794,16 +819,7 @@ class VadBatch:
         self.depth = max(1, int(setting("lanes", lanes, THROUGHPUT_LANES if many else 2, int)))
         self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + (2 if many else 1), int)))
         self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
-        try:
-            ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
-        except ValueError:
-            ranks_here = 1
-        self.cores_per_rank = usable_cores() / ranks_here
-        mode = str(setting("wait", wait, "auto"))
-        if mode not in ("auto", "spin", "block"):
-            raise ValueError(f"VadBatch: wait={mode!r} (expected auto | spin | block)")
-        self.blocking_wait = mode == "block" or (mode == "auto" and self.cores_per_rank < 4)
-        _lib.load().dz_host_pool_set_spin(0 if self.cores_per_rank < 4 else 40)
+        self._host_wait(wait)
         # the segmentation chain is the whole step: its streams get the high priority, as in StreamBatch
         pa = int(_lib.exp_env("DZ_PRIO_A", "-1"))
         self.lanes = [torch.cuda.Stream(self.device, priority=pa) for _ in range(self.depth)]
@@ -860,31 +876,6 @@ class VadBatch:
         self._slots.append(s)
         return s
 
-    def launch(self, waves, starts=None, slots: Optional[Sequence[int]] = None) -> dict:
-        """Enqueue the GPU work of one step; ``waves``, ``starts`` and ``slots`` as in ``StreamBatch.launch``.
-        Returns a ticket for ``finish``; does not wait for the GPU."""
-        ring = waves if isinstance(waves, AudioRing) else None
-        if ring is not None:
-            assert ring.filled == ring.window, "the ring does not hold a complete window yet"
-            rows, N, S = None, ring.n, ring.window
-            base, stride = ring.raw()
-        else:
-            rows = _as_rows(waves)
-            N, S = rows.shape
-            base, stride = rows.data_ptr(), (rows.stride(0) if N > 1 else S)
-        if slots is None:
-            assert N == self.n, f"expected {self.n} streams, got {N}"
-        else:
-            slots = [int(i) for i in slots]
-            assert N == len(slots) and 1 <= N <= self.n and len(set(slots)) == N, "bad slots"
-            assert all(0 <= i < self.n for i in slots), "slot out of range"
-        slot = self._launch_rows(base, stride, N, S, rows, ring)
-        slot["slots"] = slots
-        idx = np.arange(self.n) if slots is None else np.asarray(slots, dtype=np.int64)
-        slot["starts"] = self._steps[idx] * self.step if starts is None else starts
-        self._steps[idx] += 1
-        return slot
-
     def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
         assert 1 <= N <= self.n
         F = self.seg.num_frames(S)
@@ -925,51 +916,7 @@ class VadBatch:
         self._t += 1
         return slot
 
-    def _warm_up(self, S: int) -> None:
-        """Steps on silence before the first real one of this window size (StreamBatch._warm_up): complete steps
-        while no launch has been issued for a caller, GPU-only steps afterwards."""
-        steps = self.warmup_steps
-        if steps <= 0:
-            return
-        zeros = torch.zeros((self.n, S), dtype=torch.float32, device=self.device)
-        saved = dict(self.host_seconds)
-        inflight: List[dict] = []
-        t_saved = self._t
-        self._warming = True
-        try:
-            if self._real_launches == 0:
-                for _ in range(steps):
-                    inflight.append(self.launch(zeros))
-                    if len(inflight) >= self.max_inflight:
-                        self.finish(inflight.pop(0))
-                while inflight:
-                    self.finish(inflight.pop(0))
-            else:
-                for _ in range(steps):
-                    inflight.append(self._launch_rows(zeros.data_ptr(), zeros.stride(0), self.n, S, zeros))
-                    if len(inflight) >= self.max_inflight:
-                        t = inflight.pop(0)
-                        self._wait(t)
-                        t["busy"], t["keep"] = False, None
-                for t in inflight:
-                    self._wait(t)
-                    t["busy"], t["keep"] = False, None
-        finally:
-            self._warming = False
-        torch.cuda.synchronize(self.device)
-        if self._real_launches == 0:
-            self.reset()
-            self._t = 0
-        else:
-            self._t = t_saved
-        self.host_seconds.update(saved)
-
     # ------------------------------------------------------------------ host half
-    def _wait(self, ticket: dict) -> None:
-        t0 = _time.perf_counter()
-        ticket["done"].synchronize()
-        self.host_seconds["wait"] += _time.perf_counter() - t0
-
     def finish(self, ticket: dict) -> np.ndarray:
         """Wait for the step's GPU work and run the N output tails -> the speech track (N,F,1) f32; the step's turns
         are in ``ticket["tail"]`` (``BatchedOutputTail.__call__``'s tuple, indexed by row).  Both are views of
@@ -988,9 +935,6 @@ class VadBatch:
             self.host_seconds["work"] += _time.perf_counter() - t1
         return track
 
-    def __call__(self, waves):
-        return self.finish(self.launch(waves))
-
     def detect(self, waves, starts=None) -> List[Annotation]:
         """One step of every stream, end to end -> N ``Annotation``: the ``"speech"`` turns of the region this step
         finalises (what ``VoiceActivityDetection.__call__`` returns per chunk, without the aggregated audio)."""
@@ -998,6 +942,180 @@ class VadBatch:
         self.finish(ticket)
         turns, nturns = ticket["tail"][4], ticket["tail"][5]
         return [BatchedOutputTail.annotation(turns[i], int(nturns[i]), label="speech") for i in range(self.n)]
+
+
+class WeSpeakerBatch(_DiarizationEngine):
+    """``SpeakerDiarization`` of N concurrent streams with the WeSpeaker ResNet34 embedding
+    (pyannote/wespeaker-voxceleb-resnet34-LM, the embedding of pyannote.audio 3.1's pipeline): the sibling of
+    ``StreamBatch`` for the one model whose embedding trunk, not the segmentation, is the long chain of a step
+    (about 10.7 ms of fbank + ResNet34 per 64 windows against a 0.7 ms segmentation).  Per stream it produces what
+    that stream's own ``SpeakerDiarization`` produces; the public surface is ``StreamBatch``'s.
+
+    GPU schedule per step, on the step's lane (two HIP streams per lane):
+
+        stream A : dz_wave_stats -> dz_seg_forward_osp (scores + OSP weights)            -- ev_seg
+        stream B : dz_wsp_trunk (reads the same windows, in place from the ring)   <wait ev_seg>  dz_wsp_pool(normalize=1)
+                   -> dz_results_to_host (scores + embeddings) -> `done`
+        host     : clustering + output tail of step t-1 (C++ workers, fp64) while the GPU runs step t
+
+    The trunk does not depend on the segmentation, so the segmentation runs under it and only the pooling waits.  The
+    embeddings are bit for bit those of ``HipWeSpeakerEmbedding.forward_multi`` on the same windows and weights (a
+    row's result does not depend on the batch it is in).
+
+    ``lanes`` defaults to 2 for every stream count: one ``dz_wsp`` handle of ``num_streams`` rows per lane holds about
+    33 MB of activations per row at 5 s (four layer-1 sized buffers of 5.1 MB, the layer outputs, the fbank), i.e.
+    about 2.1 GB per lane at 64 streams and 8.4 GB at 256 (``tools/wespeaker_streams.py`` reports the measured
+    figure).  Two lanes are 4 HIP streams, what the runtime's 4 hardware queues carry.  ``recurrence``: what
+    ``StreamBatch`` picks (the matrix-core kernel at >= 64 streams in the default precision, else the model's own);
+    ``inflight`` defaults to lanes + 1; ``wait`` and ``warmup`` as in ``StreamBatch``; ``DZ_ENGINE`` overrides them.
+    No sub-batches, no serial form and none of the x-vector engine's experiment switches."""
+
+    def __init__(self, segmentation: HipSegmentation, embedding: HipWeSpeakerEmbedding, num_streams: int,
+                 tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
+                 gamma: float = 3, beta: float = 10, max_speakers: int = 20,
+                 normalize_embedding_weights: bool = False,
+                 device: Optional[torch.device] = None, cluster_threads: int = 8,
+                 tail: bool = False, duration: float = 5.0, step: float = 0.5,
+                 latency: Optional[float] = None, *, lanes: Optional[int] = None,
+                 recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
+                 warmup: Optional[int] = None):
+        from .blocks.diarization import _latency
+        from .config import setting
+        if not isinstance(embedding, HipWeSpeakerEmbedding):
+            raise ValueError(f"WeSpeakerBatch runs the WeSpeaker ResNet34 embedding (HipWeSpeakerEmbedding), not "
+                             f"{type(embedding).__name__}: use StreamBatch for HipEmbedding, HipEcapaEmbedding and "
+                             "HipSbXvectorEmbedding")
+        if not isinstance(segmentation, HipSegmentation):
+            raise ValueError(f"WeSpeakerBatch: segmentation must be a HipSegmentation, got {type(segmentation).__name__}")
+        self._refuse_xvector_experiments()
+        self.n = int(num_streams)
+        if self.n < 1:
+            raise ValueError(f"WeSpeakerBatch: num_streams={num_streams}")
+        self.duration, self.step = float(duration), float(step)
+        self.latency = float(_latency(latency, self.step, self.duration))
+        if not self.step <= self.latency <= self.duration:
+            raise ValueError(f"WeSpeakerBatch: latency should be in the range [{self.step}, {self.duration}], "
+                             f"got {self.latency}")
+        self._host_wait(wait)
+        # ---- from here on the device
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)
+        self.device = self.seg.device
+        self.gamma, self.beta, self.norm_w = float(gamma), float(beta), bool(normalize_embedding_weights)
+        self.clustering = BatchedSpeakerClustering(self.n, tau_active, rho_update, delta_new, max_speakers,
+                                                   cluster_threads)
+        self.max_speakers, self.tau_active, self.cluster_threads = max_speakers, tau_active, cluster_threads
+        self.with_tail = bool(tail)
+        self.tail: Optional[BatchedOutputTail] = None
+        # the recurrence StreamBatch would pick for these streams (see there); the lanes stay at 2 (memory, queues)
+        rec = setting("recurrence", recurrence, None)
+        split = getattr(self.seg, "precision", "f32") == "f16x3"
+        self.throughput = self.n >= 64 and rec is None and split and getattr(self.seg, "recurrence", "valu") == "valu"
+        self.recurrence = self.seg.throughput_recurrence() if self.throughput else (str(rec) if rec is not None and split else None)
+        self.depth = max(1, int(setting("lanes", lanes, 2, int)))
+        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + 1, int)))
+        self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
+        # The segmentation is the short chain here, but the step's last kernels (pooling, seg_1) wait for it: its stream
+        # keeps StreamBatch's high priority so that it is never queued behind the trunk's convolutions of both lanes.
+        self.lanes = [dict(a=torch.cuda.Stream(self.device, priority=-1), b=torch.cuda.Stream(self.device, priority=0))
+                      for _ in range(self.depth)]
+        self.num_hip_streams = 2 * self.depth
+        self._t = 0
+        self._steps = np.zeros(self.n, dtype=np.int64)
+        self.host_seconds = {"wait": 0.0, "work": 0.0}
+        self._sub: dict = {}                               # (S, lane) -> (segmentation handle, dz_wsp handle)
+        self._slots: List[dict] = []
+        self._warmed: set = set()
+        self._warming, self._real_steps, self._real_launches = False, 0, 0
+        self._lib = _lib.load()
+        self._ctx = _lib.context(self.device.index)
+
+    # ------------------------------------------------------------------ GPU half
+    def _handles(self, S: int, lane: int):
+        got = self._sub.get((S, lane))
+        if got is None:
+            hs = self.seg._create(S, self.n, throughput=self.throughput,
+                                  recurrence=None if self.throughput else self.recurrence)
+            try:
+                he = self.emb._create(S, self.n)
+            except Exception:
+                self.seg._destroy(hs)
+                raise
+            got = self._sub[(S, lane)] = (hs, he)
+        return got
+
+    def __del__(self):
+        try:
+            for hs, he in self._sub.values():
+                self.seg._destroy(hs)
+                self.emb._destroy(he)
+        except Exception:
+            pass
+
+    def _new_slot(self, F: int, K: int) -> dict:
+        n, dev, D = self.n, self.device, self.emb.dimension
+        s = dict(shape=(F, K), busy=False,
+                 seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
+                 w=torch.empty((n, K, F), dtype=torch.float32, device=dev),
+                 emb=torch.empty((n, K, D), dtype=torch.float32, device=dev),
+                 stats=torch.empty((n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=dev),
+                 seg_h=torch.empty((n, F, K), dtype=torch.float32).pin_memory(),
+                 emb_h=torch.empty((n, K, D), dtype=torch.float32).pin_memory(),
+                 ev_in=torch.cuda.Event(), ev_seg=torch.cuda.Event(),
+                 done=torch.cuda.Event(blocking=self.blocking_wait))
+        self._slots.append(s)
+        return s
+
+    def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
+        """The GPU half of a step for N <= num_streams rows of S samples at ``base + i * stride`` floats; nothing here
+        waits for the GPU."""
+        assert 1 <= N <= self.n
+        F, K, D = self.seg.num_frames(S), self.seg.num_speakers, self.emb.dimension
+        if (S, 0) not in self._sub:
+            # every lane's arenas and the output tail's host state before the first kernel of this window size
+            # (allocations while kernels run stall the queues: StreamBatch._launch_rows)
+            for ln in range(self.depth):
+                self._handles(S, ln)
+            if self.with_tail and self.tail is None:
+                self.tail = BatchedOutputTail(self.n, F, self.max_speakers, self.step, self.latency,
+                                              self.tau_active, num_threads=self.cluster_threads)
+        if not any(s["shape"] == (F, K) for s in self._slots):
+            for _ in range(self.max_inflight):
+                self._new_slot(F, K)
+        if S not in self._warmed:
+            self._warmed.add(S)
+            self._warm_up(S)
+        if not self._warming:
+            self._real_launches += 1
+        ln = self._t % self.depth
+        a, b = self.lanes[ln]["a"], self.lanes[ln]["b"]
+        hseg, hemb = self._handles(S, ln)
+        slot = next((s for s in self._slots if not s["busy"] and s["shape"] == (F, K)), None) or self._new_slot(F, K)
+        slot["busy"] = True
+        lib = self._lib
+        slot["ev_in"].record(torch.cuda.current_stream(self.device))      # inputs produced on the caller's stream
+        a.wait_event(slot["ev_in"])
+        b.wait_event(slot["ev_in"])
+        stats = slot["stats"]
+        _lib.check(lib.dz_wave_stats(self._ctx, base, stride, N, S, stats.data_ptr(), a.cuda_stream), "dz_wave_stats")
+        _lib.check(lib.dz_seg_use_wave_stats(hseg, stats.data_ptr()), "dz_seg_use_wave_stats")
+        _lib.check(lib.dz_seg_forward_osp(hseg, base, stride, N, slot["seg"].data_ptr(), self.gamma, self.beta,
+                                          int(self.norm_w), slot["w"].data_ptr(), a.cuda_stream), "dz_seg_forward_osp")
+        slot["ev_seg"].record(a)
+        # the lane's handle carries one trunk at a time: stream B orders this trunk behind the pooling of the lane's
+        # previous step
+        self.emb.trunk_launch(hemb, base, stride, N, b.cuda_stream)
+        b.wait_event(slot["ev_seg"])
+        self.emb.pool_launch(hemb, slot["w"].data_ptr(), N, K, F, True, slot["emb"].data_ptr(), b.cuda_stream)
+        _lib.check(lib.dz_results_to_host(self._ctx, slot["seg"].data_ptr(), slot["seg_h"].data_ptr(), N * F * K,
+                                          slot["emb"].data_ptr(), slot["emb_h"].data_ptr(), N * K * D,
+                                          b.cuda_stream), "dz_results_to_host")
+        slot["done"].record(b)
+        if ring is not None:                            # pushes `slack` steps from now wait for these forward passes
+            ring._read_by([a, b])
+        slot["rows"], slot["slots"], slot["keep"] = N, None, keep
+        self._t += 1
+        return slot
 
 
 class FileBatch:

@@ -12,7 +12,8 @@ stream's own clustering and aggregation state.  Streams join and leave at any ti
 their own pace; per stream the output is what a dedicated ``SpeakerDiarization`` pipeline with the
 same configuration produces.  The model pair may be config 2's (x-vector) or config 3's (powerset segmentation +
 ``HipEcapaEmbedding``, with ``normalize_embedding_weights=True``), or the same with the speechbrain x-vector
-(``HipSbXvectorEmbedding``): see ``StreamBatch``.  ``pipeline="vad"`` (no embedding) serves
+(``HipSbXvectorEmbedding``): see ``StreamBatch``; with a ``HipWeSpeakerEmbedding`` (pyannote.audio 3.1's embedding)
+the engine is a ``WeSpeakerBatch``.  ``pipeline="vad"`` (no embedding) serves
 ``VoiceActivityDetection`` instead (``diart.serve --pipeline VoiceActivityDetection``, reference
 ``console/serve.py:19-22,99-102``) on a ``VadBatch``: every stream's turns are labelled ``"speech"``, and
 only the prediction is served, not the aggregated audio.
@@ -36,7 +37,8 @@ import torch
 from .blocks.aggregation import BatchedOutputTail
 from .features import Annotation
 from .functional import resampler
-from .pipeline import AudioRing, StreamBatch, VadBatch
+from .models import HipWeSpeakerEmbedding
+from .pipeline import AudioRing, StreamBatch, VadBatch, WeSpeakerBatch
 
 PIPELINES = ("diarization", "vad")
 
@@ -98,10 +100,12 @@ class StreamServer:
             self.batch = VadBatch(segmentation, self.max_streams, tau_active, duration=duration, step=step,
                                   latency=self.latency, device=device)
         elif engine is None:
-            self.batch = StreamBatch(segmentation, embedding, self.max_streams, tau_active, rho_update,
-                                     delta_new, gamma, beta, max_speakers,
-                                     normalize_embedding_weights=normalize_embedding_weights, device=device, tail=True,
-                                     duration=duration, step=step, latency=self.latency)
+            # the WeSpeaker ResNet34 embedding has an engine of its own (its trunk is the long chain of a step)
+            batch_cls = WeSpeakerBatch if isinstance(embedding, HipWeSpeakerEmbedding) else StreamBatch
+            self.batch = batch_cls(segmentation, embedding, self.max_streams, tau_active, rho_update,
+                                   delta_new, gamma, beta, max_speakers,
+                                   normalize_embedding_weights=normalize_embedding_weights, device=device, tail=True,
+                                   duration=duration, step=step, latency=self.latency)
         if engine is None:
             self._dev = torch.empty((self.max_streams, self.model_chunk_samples), dtype=torch.float32,
                                     device=self.batch.device)

@@ -318,7 +318,19 @@ int dz_wsp_forward(dz_wsp* m, const float* d_wave, long long wave_stride, const 
  * row (NaN rows stay NaN).  Row b * K + k equals dz_wsp_forward of window b with weight row (b, k).           */
 int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wave_stride, const float* d_weights, int batch,
                          int num_speakers, int weight_frames, int normalize, float* d_out, void* stream);
-/* device pointer + element count of an intermediate of the LAST forward (parity tests); *frames receives the
+/* dz_wsp_forward_multi in two halves, for a caller whose weights come from a network that runs beside the trunk
+ * (the N-stream engine: the trunk does not depend on the segmentation, only the pooling does).  dz_wsp_forward_multi
+ * is exactly dz_wsp_trunk followed by dz_wsp_pool on one stream: the results are the same bits.
+ * fbank -> conv1 -> layers 1 - 4 of `batch` windows, into the handle; independent of any weights              */
+int dz_wsp_trunk(dz_wsp* m, const float* d_wave, long long wave_stride, int batch, void* stream);
+/* TSTP pooling (K weight rows per window) + seg_1 (+ L2 normalisation) of the handle's LAST trunk -> d_out
+ * (batch * K, 256); `batch` must be that trunk's batch, otherwise an error and no launch.  The two halves go on one
+ * HIP stream, or on two that the caller orders with an event (pool after trunk).  ONE handle carries ONE trunk at a
+ * time: its activations and its per-row NaN flags stay in the handle between the halves, so the next dz_wsp_trunk
+ * (or dz_wsp_forward / _multi) on the handle is enqueued behind the pooling of the previous one.               */
+int dz_wsp_pool(dz_wsp* m, const float* d_weights, int batch, int num_speakers, int weight_frames, int normalize,
+                float* d_out, void* stream);
+/* device pointer + element count of an intermediate of the LAST forward or half (parity tests); *frames receives the
  * buffer's time axis:  0 fbank (N,80,T) after the mean subtraction  1 conv1 (N,80,T,32)  2 .. 5 layer 1 .. 4
  * (N,F,T_l,C_l)  6 pooled statistics (rows, 5120)  7 fbank (N,80,T) before the mean subtraction             */
 int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames);
