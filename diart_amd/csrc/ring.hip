@@ -42,6 +42,10 @@ struct dz_ring {
     // per-row state (dz_ring_push_rows / dz_ring_gather); a lock-step dz_ring_push moves every row
     std::vector<int> rpos;
     std::vector<long long> rpushed;
+    // raw client blocks (dz_ring_push_rows_pcm) and rings whose hop is not a multiple of 4 samples
+    bool aligned;      // hop % 4 == 0: every block and every window starts on a 16-byte boundary
+    char* pstage;      // two landing blocks of `pstage_cap` bytes each for pageable host input, grown on demand
+    size_t pstage_cap;
 };
 
 // up to 64 (row, offset) pairs per launch, passed in the kernel-argument segment
@@ -53,15 +57,16 @@ struct DzRowList {
 extern "C" int dz_ring_create(dz_ctx* ctx, int n_streams, int window, int hop, int slack_blocks,
                               dz_ring** out) {
     DZ_REQUIRE(ctx && out, "dz_ring_create: NULL argument");
-    DZ_REQUIRE(n_streams >= 1 && window >= 4 && hop >= 4 && slack_blocks >= 0,
+    DZ_REQUIRE(n_streams >= 1 && window >= 1 && hop >= 1 && slack_blocks >= 0,
                "dz_ring_create: empty geometry");
-    DZ_REQUIRE(window % hop == 0 && hop % 4 == 0,
-               "dz_ring_create: window (%d) must be a multiple of hop (%d) and hop a multiple of 4 "
-               "samples (16-byte aligned rows)", window, hop);
+    // hop % 4 != 0 (44.1 kHz: 22 050 samples per 500 ms): blocks and windows start on 4-byte boundaries only; the
+    // per-row entry points then move 4-byte pieces where a piece is not 16-byte aligned, dz_ring_window refuses
+    DZ_REQUIRE(window % hop == 0, "dz_ring_create: window (%d) must be a multiple of hop (%d)", window, hop);
     DZ_HIP(hipSetDevice(ctx->device));
     dz_ring* r = new (std::nothrow) dz_ring;
     DZ_REQUIRE(r != nullptr, "dz_ring_create: out of memory");
     r->ctx = ctx; r->n = n_streams; r->W = window; r->hop = hop; r->buf = nullptr;
+    r->aligned = hop % 4 == 0; r->pstage = nullptr; r->pstage_cap = 0;
     r->P = window + slack_blocks * hop;
     r->pushed = 0; r->pos = 0;
     r->rpos.assign(n_streams, 0);
@@ -77,6 +82,10 @@ extern "C" int dz_ring_create(dz_ctx* ctx, int n_streams, int window, int hop, i
     }
     DZ_HIP(hipMemset(r->buf, 0, bytes));
     r->stage[0] = r->stage[1] = nullptr;
+    if (!r->aligned) {     // float blocks of such a ring land in `pstage` like raw client blocks
+        *out = r;
+        return 0;
+    }
     e = hipMalloc((void**)&r->stage[0], (size_t)2 * n_streams * hop * sizeof(float));
     if (e != hipSuccess) {
         dz_set_error("dz_ring_create: hipMalloc(stage) failed: %s", hipGetErrorString(e));
@@ -126,6 +135,115 @@ __global__ __launch_bounds__(256) void ring_gather_kernel(const float* __restric
     *reinterpret_cast<f32x4*>(out + (long long)jrow * ostride + 4 * j) = *reinterpret_cast<const f32x4*>(src);
 }
 
+// out row j <- W samples of ring row rows.row[j] from rows.off[j], where the window or the output row does not
+// start on a 16-byte boundary (a ring with hop % 4 != 0).  A block of 256 lanes moves 1024 samples: 16 bytes per
+// lane when this row's source and destination are aligned, else four 4-byte pieces per lane, 256 samples apart
+// (every load and store of a wave is then one contiguous 256-byte span).
+__global__ __launch_bounds__(256) void ring_gather_any_kernel(const float* __restrict__ buf, long long pitch,
+                                                              float* __restrict__ out, long long ostride, int W,
+                                                              int out_vec, DzRowList rows) {
+    const int jrow = blockIdx.y;
+    const int off = rows.off[jrow];
+    const float* src = buf + (long long)rows.row[jrow] * pitch + off;
+    float* dst = out + (long long)jrow * ostride;
+    const int e0 = blockIdx.x * 1024;
+    if (out_vec && (off & 3) == 0 && e0 + 1024 <= W) {
+        const int e = e0 + 4 * threadIdx.x;
+        *reinterpret_cast<f32x4*>(dst + e) = *reinterpret_cast<const f32x4*>(src + e);
+    } else {
+        for (int t = 0; t < 4; ++t) {
+            const int e = e0 + t * 256 + threadIdx.x;
+            if (e < W) dst[e] = src[e];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Raw client blocks -> ring (dz_ring_push_rows_pcm): load, convert, average the channels and store at `off` and
+// `off + P` in ONE kernel.  Replaces, for live streams, the channel average of the reference's loader
+// (reference audio.py:32-34, waveform.mean(dim=0)) and the int16 -> float conversion its clients
+// do before they send.  The arithmetic is the header's definition, operation for operation: nothing is
+// contracted (the sum is a chain of adds, the average one division), and one float channel is copied as bits.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float pcm_to_f32(float v) { return v; }
+__device__ __forceinline__ float pcm_to_f32(short v) { return (float)v * (1.0f / 32768.0f); }
+
+// e: the C values of one frame
+template <typename T, int C>
+__device__ __forceinline__ float pcm_frame(const T* e) {
+#pragma clang fp contract(off)
+    float s = pcm_to_f32(e[0]);
+    if (C == 1) return s;
+#pragma unroll
+    for (int c = 1; c < C; ++c) s = s + pcm_to_f32(e[c]);
+    return s / (float)C;
+}
+
+// Row j of `block` (rows `bstride` values apart): hop frames of C interleaved values of type T -> ring row
+// rows.row[j] at rows.off[j] and rows.off[j] + P.  A lane takes F = 16 / sizeof(T) frames, which are C 16-byte
+// loads whatever the format, and writes them with 16-byte stores; a block covers 256 F frames.  Where the input
+// rows (in_vec == 0), this row's ring position (off or P not a multiple of 4: a ring with hop % 4 != 0) or the
+// block's extent (the tail of a row) do not allow that, the lanes of the block take single frames, 256 apart:
+// 4-byte stores, a wave's stores one contiguous span.  Both paths do the same arithmetic per frame.
+template <typename T, int C>
+__global__ __launch_bounds__(256) void ring_scatter_pcm_kernel(const T* __restrict__ block, long long bstride,
+                                                               float* __restrict__ buf, long long pitch, int hop,
+                                                               int P, int in_vec, DzRowList rows) {
+    constexpr int F = 16 / sizeof(T);
+    const int jrow = blockIdx.y;
+    const int off = rows.off[jrow];
+    const T* in = block + (long long)jrow * bstride;
+    float* row = buf + (long long)rows.row[jrow] * pitch + off;
+    const int f0 = blockIdx.x * (F * 256);
+    if (in_vec && ((off | P) & 3) == 0 && f0 + F * 256 <= hop) {
+        const int f = f0 + F * threadIdx.x;
+        union {
+            f32x4 v[C];
+            T e[F * C];
+        } u;
+        const f32x4* src = reinterpret_cast<const f32x4*>(in + (long long)f * C);
+#pragma unroll
+        for (int c = 0; c < C; ++c) u.v[c] = src[c];
+#pragma unroll
+        for (int q = 0; q < F / 4; ++q) {
+            f32x4 o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = pcm_frame<T, C>(u.e + (4 * q + i) * C);
+            *reinterpret_cast<f32x4*>(row + f + 4 * q) = o;
+            *reinterpret_cast<f32x4*>(row + P + f + 4 * q) = o;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < F; ++t) {
+            const int f = f0 + t * 256 + threadIdx.x;
+            if (f < hop) {
+                T e[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) e[c] = in[(long long)f * C + c];
+                const float o = pcm_frame<T, C>(e);
+                row[f] = o;
+                row[P + f] = o;
+            }
+        }
+    }
+}
+
+template <typename T>
+static void launch_scatter_pcm(int channels, dim3 grid, hipStream_t st, const void* src, long long bstride,
+                               float* buf, long long pitch, int hop, int P, int in_vec, const DzRowList& rl) {
+    const T* b = reinterpret_cast<const T*>(src);
+#define DZ_PCM_CASE(C)                                                                                        \
+    case C:                                                                                                   \
+        hipLaunchKernelGGL((ring_scatter_pcm_kernel<T, C>), grid, dim3(256), 0, st, b, bstride, buf, pitch, hop, P, \
+                           in_vec, rl);                                                                       \
+        break;
+    switch (channels) {
+        DZ_PCM_CASE(1) DZ_PCM_CASE(2) DZ_PCM_CASE(3) DZ_PCM_CASE(4)
+        DZ_PCM_CASE(5) DZ_PCM_CASE(6) DZ_PCM_CASE(7) DZ_PCM_CASE(8)
+    }
+#undef DZ_PCM_CASE
+}
+
 // ---------------------------------------------------------------------------
 // A step's results -> pinned host memory with ONE kernel (stores over the host link; pinned memory is mapped at
 // its own address).  Why not hipMemcpyAsync: on this runtime a device-to-host copy call now and then blocks its
@@ -170,6 +288,7 @@ extern "C" int dz_ring_destroy(dz_ring* r) {
     if (r) {
         if (r->buf) (void)hipFree(r->buf);
         if (r->stage[0]) (void)hipFree(r->stage[0]);
+        if (r->pstage) (void)hipFree(r->pstage);
         delete r;
     }
     return 0;
@@ -191,6 +310,88 @@ extern "C" int dz_ring_reset_row(dz_ring* r, int row) {
     return 0;
 }
 
+// Rows of raw client audio -> the listed ring rows, each at its own write position (the body of
+// dz_ring_push_rows_pcm; float blocks of a ring with hop % 4 != 0 come here too).  The caller has checked `rows`.
+static int ring_push_pcm(dz_ring* r, const void* block, long long stride_bytes, int format, int channels,
+                         int on_device, const int* rows, int k, hipStream_t st) {
+    const long long esz = format == DZ_PCM_S16 ? 2 : 4;
+    const long long row_bytes = (long long)r->hop * channels * esz;
+    DZ_REQUIRE(stride_bytes >= row_bytes && stride_bytes % esz == 0 && (uintptr_t)block % esz == 0,
+               "ring push: rows of the block must be >= hop * channels values apart and aligned to one value");
+    const char* src = reinterpret_cast<const char*>(block);
+    long long sstride = stride_bytes;
+    if (on_device == 2) {
+        void* dptr = nullptr;
+        if (hipHostGetDevicePointer(&dptr, (void*)block, 0) == hipSuccess && dptr) {
+            src = reinterpret_cast<const char*>(dptr);
+        } else {
+            (void)hipGetLastError();
+            on_device = 0;
+        }
+    }
+    if (!on_device) {
+        // landing rows start on 16-byte boundaries whatever the caller's stride; the two landing blocks alternate as
+        // in dz_ring_push.  They grow to the largest format seen (hipFree waits for the kernels still reading them)
+        const long long spitch = (row_bytes + 15) & ~15LL;
+        const size_t full = (size_t)r->n * spitch;
+        if (r->pstage_cap < full) {
+            if (r->pstage) DZ_HIP(hipFree(r->pstage));
+            r->pstage = nullptr; r->pstage_cap = 0;
+            DZ_HIP(hipMalloc((void**)&r->pstage, 2 * full));
+            r->pstage_cap = full;
+        }
+        char* land = r->pstage + (size_t)(r->pushed & 1) * r->pstage_cap;
+        DZ_HIP(hipMemcpy2DAsync(land, (size_t)spitch, block, (size_t)stride_bytes, (size_t)row_bytes, k,
+                                hipMemcpyHostToDevice, st));
+        src = land;
+        sstride = spitch;
+    }
+    const int in_vec = ((uintptr_t)src & 15) == 0 && (sstride & 15) == 0;
+    const int per_block = 256 * (int)(16 / esz);
+    for (int j0 = 0; j0 < k; j0 += 64) {
+        const int m = k - j0 < 64 ? k - j0 : 64;
+        DzRowList rl;
+        for (int j = 0; j < m; ++j) {
+            rl.row[j] = rows[j0 + j];
+            rl.off[j] = r->rpos[rows[j0 + j]];
+        }
+        const dim3 grid((r->hop + per_block - 1) / per_block, m);
+        const char* s0 = src + (long long)j0 * sstride;
+        if (format == DZ_PCM_S16)
+            launch_scatter_pcm<short>(channels, grid, st, s0, sstride / esz, r->buf, r->pitch, r->hop, r->P, in_vec, rl);
+        else
+            launch_scatter_pcm<float>(channels, grid, st, s0, sstride / esz, r->buf, r->pitch, r->hop, r->P, in_vec, rl);
+        DZ_HIP(hipGetLastError());
+    }
+    for (int j = 0; j < k; ++j) {
+        r->rpos[rows[j]] = (r->rpos[rows[j]] + r->hop) % r->P;
+        r->rpushed[rows[j]] += 1;
+    }
+    r->pushed += 1;        // alternates the landing blocks
+    return 0;
+}
+
+static int ring_check_rows(const dz_ring* r, const int* rows, int k, const char* who) {
+    DZ_REQUIRE(k >= 1 && k <= r->n, "%s: %d rows for %d streams", who, k, r->n);
+    std::vector<char> seen(r->n, 0);
+    for (int j = 0; j < k; ++j) {
+        DZ_REQUIRE(rows[j] >= 0 && rows[j] < r->n && !seen[rows[j]], "%s: bad / repeated row %d", who, rows[j]);
+        seen[rows[j]] = 1;
+    }
+    return 0;
+}
+
+extern "C" int dz_ring_push_rows_pcm(dz_ring* r, const void* block, long long block_stride_bytes, int format,
+                                     int channels, int on_device, const int* rows, int k, void* stream) {
+    DZ_REQUIRE(r && block && rows, "dz_ring_push_rows_pcm: NULL argument");
+    DZ_REQUIRE(format == DZ_PCM_F32 || format == DZ_PCM_S16, "dz_ring_push_rows_pcm: unknown format %d", format);
+    DZ_REQUIRE(channels >= 1 && channels <= 8, "dz_ring_push_rows_pcm: %d channels (1 .. 8)", channels);
+    int rc = ring_check_rows(r, rows, k, "dz_ring_push_rows_pcm");
+    if (rc) return rc;
+    DZ_HIP(hipSetDevice(r->ctx->device));
+    return ring_push_pcm(r, block, block_stride_bytes, format, channels, on_device, rows, k, (hipStream_t)stream);
+}
+
 // block: [n][hop] floats with `block_stride` floats between rows; on the host (pinned memory makes
 // the copy asynchronous) when on_device == 0, in device memory otherwise.
 extern "C" int dz_ring_push(dz_ring* r, const float* block, long long block_stride, int on_device,
@@ -200,6 +401,15 @@ extern "C" int dz_ring_push(dz_ring* r, const float* block, long long block_stri
                r->hop);
     DZ_HIP(hipSetDevice(r->ctx->device));
     hipStream_t st = (hipStream_t)stream;
+    if (!r->aligned) {     // every row at the common position, through the 4-byte capable kernel
+        std::vector<int> all(r->n);
+        for (int i = 0; i < r->n; ++i) { all[i] = i; r->rpos[i] = r->pos; }
+        int rc = ring_push_pcm(r, block, block_stride * (long long)sizeof(float), DZ_PCM_F32, 1, on_device,
+                               all.data(), r->n, st);
+        if (rc) return rc;
+        r->pos = (r->pos + r->hop) % r->P;
+        return 0;
+    }
     DZ_REQUIRE(((uintptr_t)block & 15) == 0 && (block_stride & 3) == 0,
                "dz_ring_push: block rows must be 16-byte aligned");
     const float* src = block;
@@ -275,6 +485,13 @@ extern "C" int dz_ring_push_rows(dz_ring* r, const float* block, long long block
                                  const int* rows, int k, void* stream) {
     DZ_REQUIRE(r && block && rows, "dz_ring_push_rows: NULL argument");
     DZ_REQUIRE(k >= 1 && k <= r->n, "dz_ring_push_rows: %d rows for %d streams", k, r->n);
+    if (!r->aligned) {
+        int rc = ring_check_rows(r, rows, k, "dz_ring_push_rows");
+        if (rc) return rc;
+        DZ_HIP(hipSetDevice(r->ctx->device));
+        return ring_push_pcm(r, block, block_stride * (long long)sizeof(float), DZ_PCM_F32, 1, on_device, rows, k,
+                             (hipStream_t)stream);
+    }
     DZ_REQUIRE(block_stride >= r->hop && ((uintptr_t)block & 15) == 0 && (block_stride & 3) == 0,
                "dz_ring_push_rows: rows of the block must be >= hop floats apart and 16-byte aligned");
     std::vector<char> seen(r->n, 0);
@@ -322,8 +539,10 @@ extern "C" int dz_ring_filled_row(const dz_ring* r, int row, int* filled) {
 extern "C" int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d_out, long long out_stride,
                               void* stream) {
     DZ_REQUIRE(r && rows && d_out, "dz_ring_gather: NULL argument");
-    DZ_REQUIRE(k >= 1 && out_stride >= r->W && (out_stride & 3) == 0 && ((uintptr_t)d_out & 15) == 0,
-               "dz_ring_gather: output rows must be >= window floats apart and 16-byte aligned");
+    const bool out_vec = (out_stride & 3) == 0 && ((uintptr_t)d_out & 15) == 0;
+    DZ_REQUIRE(k >= 1 && out_stride >= r->W && (out_vec || !r->aligned) && ((uintptr_t)d_out & 3) == 0,
+               "dz_ring_gather: output rows must be >= window floats apart and 16-byte aligned (4-byte aligned "
+               "for a ring whose hop is not a multiple of 4)");
     for (int j = 0; j < k; ++j) {
         DZ_REQUIRE(rows[j] >= 0 && rows[j] < r->n, "dz_ring_gather: bad row %d", rows[j]);
         DZ_REQUIRE(r->rpushed[rows[j]] * r->hop >= r->W, "dz_ring_gather: the window of row %d is not complete",
@@ -338,8 +557,13 @@ extern "C" int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d
             rl.row[j] = rows[j0 + j];
             rl.off[j] = (r->rpos[rows[j0 + j]] + r->P - r->W) % r->P;
         }
-        hipLaunchKernelGGL(ring_gather_kernel, dim3((W4 + 255) / 256, m), dim3(256), 0, (hipStream_t)stream,
-                           r->buf, r->pitch, d_out + (long long)j0 * out_stride, out_stride, W4, rl);
+        if (r->aligned)
+            hipLaunchKernelGGL(ring_gather_kernel, dim3((W4 + 255) / 256, m), dim3(256), 0, (hipStream_t)stream,
+                               r->buf, r->pitch, d_out + (long long)j0 * out_stride, out_stride, W4, rl);
+        else
+            hipLaunchKernelGGL(ring_gather_any_kernel, dim3((r->W + 1023) / 1024, m), dim3(256), 0,
+                               (hipStream_t)stream, r->buf, r->pitch, d_out + (long long)j0 * out_stride, out_stride,
+                               r->W, (int)out_vec, rl);
         DZ_HIP(hipGetLastError());
     }
     return 0;
@@ -351,6 +575,8 @@ extern "C" int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d
 extern "C" int dz_ring_window(const dz_ring* r, const float** d_wave, long long* stride,
                               int* filled) {
     DZ_REQUIRE(r && d_wave && stride, "dz_ring_window: NULL argument");
+    DZ_REQUIRE(r->aligned, "dz_ring_window: the windows of a ring with hop %d (not a multiple of 4 samples) do not "
+               "start on 16-byte boundaries and cannot be read in place: use dz_ring_gather / dz_ring_read", r->hop);
     *d_wave = r->buf + (r->pos + r->P - r->W) % r->P;
     *stride = r->pitch;
     if (filled) {

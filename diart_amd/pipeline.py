@@ -47,6 +47,9 @@ from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
 from .models import HipEcapaEmbedding, HipEmbedding, HipSbXvectorEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _as_rows
 
+# sample formats of raw client audio (``dz_ring_push_rows_pcm``: DZ_PCM_F32 / DZ_PCM_S16, little-endian)
+PCM_F32, PCM_S16 = 0, 1
+
 # lanes of a throughput engine (>= 64 streams per step on the matrix-core recurrence): profiles/r06*_lanes_grid.json
 THROUGHPUT_LANES = 6
 
@@ -117,16 +120,32 @@ class AudioRing:
         self._readers.append(evs)
 
     # ---- streams that advance at their own pace (StreamServer) -------------------------------
-    def push_rows(self, block: torch.Tensor, rows: Sequence[int]) -> None:
-        """Row j of ``block`` (k, hop) is the next block of stream ``rows[j]`` (each row keeps its
-        own write position).  Enqueued on the current HIP stream; a pinned host block is read in
-        place by the GPU and must stay untouched until that stream has passed this point."""
+    def push_rows(self, block: torch.Tensor, rows: Sequence[int], channels: int = 1) -> None:
+        """Row j of ``block`` is the next block of stream ``rows[j]`` (each row keeps its own write position).
+        ``block``: (k, hop) float32 — or raw client audio, ``torch.float32`` / ``torch.int16`` of shape
+        (k, hop * channels) or (k, hop, channels) with interleaved frames, which the push kernel converts
+        (int16: ``v / 32768``) and averages over the channels (``dz_ring_push_rows_pcm``).  Enqueued on the current
+        HIP stream; a pinned host block is read in place by the GPU and must stay untouched until that stream has
+        passed this point."""
         k = len(rows)
-        assert block.dtype == torch.float32 and tuple(block.shape) == (k, self.hop) and block.stride(1) == 1
         mode = 1 if block.is_cuda else (2 if block.is_pinned() and _lib.exp_env("DZ_RING_ZERO_COPY", "1") != "0" else 0)
         arr = (C.c_int * k)(*[int(r) for r in rows])
-        _lib.check(self._lib.dz_ring_push_rows(self._h, block.data_ptr(), block.stride(0), mode, arr, k,
-                                               torch.cuda.current_stream(self.device).cuda_stream), "dz_ring_push_rows")
+        cur = torch.cuda.current_stream(self.device).cuda_stream
+        if block.dtype == torch.float32 and channels == 1 and block.dim() == 2 and self.hop % 4 == 0:
+            assert tuple(block.shape) == (k, self.hop) and block.stride(1) == 1
+            _lib.check(self._lib.dz_ring_push_rows(self._h, block.data_ptr(), block.stride(0), mode, arr, k, cur),
+                       "dz_ring_push_rows")
+        else:
+            fmt = {torch.float32: PCM_F32, torch.int16: PCM_S16}.get(block.dtype)
+            if fmt is None:
+                raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks (expected float32 or int16)")
+            if block.dim() == 3:
+                assert tuple(block.shape) == (k, self.hop, channels) and block.stride(2) == 1 \
+                    and block.stride(1) == channels, "frames of a (k, hop, channels) block must be contiguous"
+            else:
+                assert tuple(block.shape) == (k, self.hop * channels) and block.stride(1) == 1
+            _lib.check(self._lib.dz_ring_push_rows_pcm(self._h, block.data_ptr(), block.stride(0) * block.element_size(),
+                                                       fmt, int(channels), mode, arr, k, cur), "dz_ring_push_rows_pcm")
         self._keep = (self._keep + [block])[-4:]
 
     def filled_row(self, row: int) -> int:
@@ -154,6 +173,8 @@ class AudioRing:
 
     @property
     def filled(self) -> int:
+        if self.hop % 4:          # no in-place window (dz_ring_window); lock-step pushes advance every row alike
+            return self.filled_row(0)
         ptr, stride, f = _lib.vp(), C.c_longlong(), C.c_int()
         _lib.check(self._lib.dz_ring_window(self._h, C.byref(ptr), C.byref(stride), C.byref(f)), "dz_ring_window")
         return int(f.value)

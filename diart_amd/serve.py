@@ -23,6 +23,12 @@ uploads only the NEW 500 ms block of each stream that has one (32 KB instead of 
 reference moves per chunk, ``blocks/segmentation.py:47``) and assembles the batch of windows on the
 device.  ``device_rings=False`` (and any custom ``engine``) keeps the windows on the host instead.
 
+Clients may send what they have: ``input_format="s16"`` (16-bit PCM) and ``input_channels`` (interleaved frames,
+averaged like the reference's loader, ``audio.py:32-34``).  In ring mode the raw blocks are uploaded as they came
+and the push kernel converts and averages them (``dz_ring_push_rows_pcm``); the host modes do the same arithmetic
+in numpy (``pcm_to_mono``), so every mode hands the models identical float32 windows.  ``device_rings="all"``
+also uses rings where a block is not a multiple of 4 samples (44.1 kHz, 22.05 kHz).
+
 Transport (websocket, microphone) is out of scope: ``push`` is the seam a network front-end calls
 (thread-safe), ``step`` / ``serve_forever`` is the worker loop."""
 from __future__ import annotations
@@ -41,14 +47,32 @@ from .models import HipWeSpeakerEmbedding
 from .pipeline import AudioRing, StreamBatch, VadBatch, WeSpeakerBatch
 
 PIPELINES = ("diarization", "vad")
+INPUT_FORMATS = {"f32": np.dtype("<f4"), "s16": np.dtype("<i2")}      # name -> dtype of the values clients push
+MAX_INPUT_CHANNELS = 8
+
+
+def pcm_to_mono(values: np.ndarray, input_format: str = "f32", channels: int = 1) -> np.ndarray:
+    """Interleaved client audio -> mono float32, the arithmetic of ``dz_ring_push_rows_pcm`` operation for operation
+    (all in float32): int16 ``v -> float(v) * (1 / 32768)`` (exact, what ``read_wav`` does), then for several channels
+    ``((c0 + c1) + c2 ...) / channels``.  One float32 channel is returned as it is."""
+    x = np.asarray(values).reshape(-1)
+    if input_format == "s16":
+        x = x.astype(np.float32) * np.float32(1.0 / 32768.0)
+    if channels == 1:
+        return x
+    frames = x.reshape(-1, channels)
+    total = frames[:, 0].copy()
+    for c in range(1, channels):
+        total = total + frames[:, c]
+    return total / np.float32(channels)
 
 
 class _Stream:
     __slots__ = ("slot", "buffer", "blocks", "consumed", "chunk", "start", "emitted", "prediction")
 
-    def __init__(self, slot: int):
+    def __init__(self, slot: int, dtype=np.float32):
         self.slot = slot
-        self.buffer = np.zeros(0, dtype=np.float32)   # samples not yet a whole step block
+        self.buffer = np.zeros(0, dtype=dtype)        # values (input format, interleaved) not yet a whole step block
         self.blocks: List[np.ndarray] = []            # whole step blocks the worker has not taken yet
         self.consumed = 0                             # step blocks taken by the worker so far
         self.chunk: Optional[np.ndarray] = None       # host-window mode: the current (<= duration) window
@@ -63,14 +87,23 @@ class StreamServer:
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  device: Optional[torch.device] = None, patch_collar: float = 0.05,
-                 engine: Optional[Callable] = None, device_rings: bool = True,
+                 engine: Optional[Callable] = None, device_rings=True,
                  normalize_embedding_weights: bool = False, input_sample_rate: Optional[int] = None,
-                 pipeline: str = "diarization"):
+                 pipeline: str = "diarization", input_format: str = "f32", input_channels: int = 1):
         if pipeline not in PIPELINES:
             raise ValueError(f"StreamServer: pipeline={pipeline!r} (expected one of {PIPELINES})")
         if pipeline == "vad" and embedding is not None:
             raise ValueError("StreamServer: pipeline='vad' (VoiceActivityDetection) runs the segmentation only; "
                              "pass embedding=None")
+        if input_format not in INPUT_FORMATS:
+            raise ValueError(f"StreamServer: input_format={input_format!r} (expected one of {tuple(INPUT_FORMATS)})")
+        if not (isinstance(input_channels, (int, np.integer)) and 1 <= input_channels <= MAX_INPUT_CHANNELS):
+            raise ValueError(f"StreamServer: input_channels={input_channels!r} (expected 1 .. {MAX_INPUT_CHANNELS})")
+        if device_rings not in (True, False, "all"):
+            raise ValueError(f"StreamServer: device_rings={device_rings!r} (expected True, False or 'all')")
+        # what clients push: interleaved frames of `input_channels` values of `input_format`
+        self.input_format, self.input_channels = input_format, int(input_channels)
+        self._in_dtype = INPUT_FORMATS[input_format]
         self.pipeline = pipeline
         self._label = "speech" if pipeline == "vad" else None     # turn labels: speaker{g} | speech
         self.duration, self.step_seconds, self.sample_rate = float(duration), float(step), int(sample_rate)
@@ -82,6 +115,7 @@ class StreamServer:
         self.model_chunk_samples = int(round(sample_rate * duration))
         self.chunk_samples = int(round(self.input_sample_rate * duration))
         self.step_samples = int(round(self.input_sample_rate * step))
+        self._block_values = self.step_samples * self.input_channels      # values of one step block as pushed
         self.resampler = None
         self.max_streams, self.patch_collar = int(max_streams), patch_collar
         self.blocks_per_window = -(-self.chunk_samples // self.step_samples)
@@ -118,15 +152,20 @@ class StreamServer:
                 self._raw = torch.empty((self.max_streams, self.chunk_samples), dtype=torch.float32,
                                         device=self.batch.device)
             self._engine, self._reset_slot = self._gpu_engine, self.batch.reset
-            # per-stream device rings need whole blocks per window (and 16-byte aligned rows)
+            # per-stream device rings need whole blocks per window, and 16-byte aligned rows unless
+            # device_rings="all" (44.1 kHz: 22 050 samples per block; the ring then moves 4-byte pieces where it must)
             self.rings: Optional[AudioRing] = None
-            if device_rings and self.chunk_samples % self.step_samples == 0 and self.step_samples % 4 == 0:
+            if device_rings and self.chunk_samples % self.step_samples == 0 and \
+                    (self.step_samples % 4 == 0 or device_rings == "all"):
                 self.rings = AudioRing(self.max_streams, self.chunk_samples, self.step_samples, slack_blocks=0,
                                        device=self.batch.device)
                 # a stream takes at most blocks_per_window blocks in one step (its warm-up); round r of
-                # a step stages its blocks in plane r, so no plane is rewritten while the GPU reads it
-                self._stage = torch.empty((self.blocks_per_window, self.max_streams, self.step_samples),
-                                          dtype=torch.float32).pin_memory()
+                # a step stages its blocks in plane r, so no plane is rewritten while the GPU reads it.  The planes
+                # hold the blocks as the clients sent them (the push kernel converts), rows 16 bytes apart or a
+                # multiple: the kernel then loads 16 bytes per lane
+                per16 = 16 // self._in_dtype.itemsize
+                self._stage = torch.empty((self.blocks_per_window, self.max_streams, -(-self._block_values // per16) * per16),
+                                          dtype=torch.from_numpy(np.zeros(0, self._in_dtype)).dtype).pin_memory()
             else:
                 self._pinned = torch.empty((self.max_streams, self.chunk_samples), dtype=torch.float32).pin_memory()
         else:
@@ -150,7 +189,7 @@ class StreamServer:
             self._reset_slot(slot)
             if self.rings is not None:
                 self.rings.reset_row(slot)
-            self._streams[stream_id] = _Stream(slot)
+            self._streams[stream_id] = _Stream(slot, self._in_dtype)
 
     def close(self, stream_id: Hashable) -> Annotation:
         """Drop the stream (windows still pending are discarded: call ``drain`` first to flush them)
@@ -177,17 +216,31 @@ class StreamServer:
 
     # ------------------------------------------------------------------ audio in
     def push(self, stream_id: Hashable, samples) -> int:
-        """Append mono float samples (any length) to a stream; returns the number of windows now
-        pending for it.  The windowing is ``rearrange_audio_stream`` (``operators.py:44-100``): whole
-        ``step`` blocks, a window once ``duration`` seconds have arrived, then one per block."""
-        x = np.asarray(samples, dtype=np.float32).reshape(-1)
+        """Append audio (any length) to a stream; returns the number of windows now pending for it.  ``samples``:
+        values of the server's ``input_format`` — mono, or for ``input_channels > 1`` interleaved frames as a 1-D
+        array (a call may end in the middle of a frame) or an ``(n, channels)`` array.  The windowing is
+        ``rearrange_audio_stream`` (``operators.py:44-100``): whole ``step`` blocks, a window once ``duration``
+        seconds have arrived, then one per block."""
+        x = self._as_values(samples)
         with self._lock:
             st = self._streams[stream_id]
             st.buffer = np.concatenate([st.buffer, x]) if st.buffer.size else x.copy()
-            while st.buffer.size >= self.step_samples:
-                st.blocks.append(st.buffer[:self.step_samples].copy())
-                st.buffer = st.buffer[self.step_samples:]
+            while st.buffer.size >= self._block_values:
+                st.blocks.append(st.buffer[:self._block_values].copy())
+                st.buffer = st.buffer[self._block_values:]
             return self._pending(st)
+
+    def _as_values(self, samples) -> np.ndarray:
+        """``samples`` as a 1-D array of the input dtype; another kind of number is refused, not cast."""
+        x = np.asarray(samples)
+        if self.input_format == "s16":
+            if x.dtype != np.int16:
+                raise ValueError(f"push: {x.dtype} samples to a server with input_format='s16' (expected int16)")
+        elif x.dtype.kind != "f":
+            raise ValueError(f"push: {x.dtype} samples to a server with input_format='f32' (expected float32)")
+        if self.input_channels > 1 and not (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == self.input_channels)):
+            raise ValueError(f"push: samples of shape {x.shape} (expected interleaved 1-D or (n, {self.input_channels}))")
+        return np.ascontiguousarray(x, dtype=self._in_dtype).reshape(-1)
 
     def pending(self, stream_id: Hashable) -> int:
         """Windows of the stream still waiting for the worker (0 for an unknown / closed stream)."""
@@ -203,7 +256,7 @@ class StreamServer:
     def _take_host_window(self, st: _Stream):
         """Host-window mode: consume blocks until one completes a window -> (window copy, start)."""
         while st.blocks:
-            new = st.blocks.pop(0)
+            new = pcm_to_mono(st.blocks.pop(0), self.input_format, self.input_channels)
             st.consumed += 1
             st.chunk = new if st.chunk is None else np.concatenate([st.chunk, new])
             if st.chunk.size > self.chunk_samples:
@@ -324,9 +377,14 @@ class StreamServer:
             for r in range(max(len(b) for _, b in uploads)):
                 rows = [slot for slot, b in uploads if len(b) > r]
                 plane = self._stage[r]
+                if plane.shape[1] != self._block_values:        # rows padded to a multiple of 16 bytes
+                    plane = plane[:, :self._block_values]
                 for j, (slot, b) in enumerate((u for u in uploads if len(u[1]) > r)):
                     plane[j].copy_(torch.from_numpy(b[r]))
-                self.rings.push_rows(plane[:len(rows)], rows)
+                if self.input_channels == 1:
+                    self.rings.push_rows(plane[:len(rows)], rows)
+                else:
+                    self.rings.push_rows(plane[:len(rows)], rows, channels=self.input_channels)
                 if pushed is not None:
                     for slot in rows:
                         pushed[slot] = pushed.get(slot, 0) + 1

@@ -13,7 +13,8 @@ Only what that exchange needs of RFC 6455 is implemented, on the standard librar
 ``websocket-server`` dependency): the HTTP upgrade handshake, text / binary / continuation / ping /
 pong / close frames, client-to-server masking, payloads up to ``max_message`` bytes, no extensions,
 no TLS (terminate it in front).  Binary messages are accepted as raw little-endian float32 samples
-(no base64), which the reference's client does not send.
+(no base64), which the reference's client does not send.  A server built with ``input_format="s16"`` /
+``input_channels=2`` takes 16-bit PCM and interleaved frames in both kinds of message instead.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ from typing import Dict, Hashable, Optional
 
 import numpy as np
 
-from .serve import StreamServer
+from .serve import INPUT_FORMATS, StreamServer
 
 _GUID = b"258EAFA5-E914-47DA-95CA-C5AB0DC85B11"
 _OP_CONT, _OP_TEXT, _OP_BIN, _OP_CLOSE, _OP_PING, _OP_PONG = 0x0, 0x1, 0x2, 0x8, 0x9, 0xA
@@ -56,12 +57,17 @@ def encode_frame(opcode: int, payload: bytes, mask: Optional[bytes] = None) -> b
     return head + payload
 
 
-def decode_audio(message) -> np.ndarray:
-    """Text message: base64 of float32 bytes (``utils.decode_audio``); binary message: the bytes."""
+def decode_audio(message, input_format: str = "f32", channels: int = 1) -> np.ndarray:
+    """Text message: base64 of the raw bytes (``utils.decode_audio``; float32 with the defaults); binary message:
+    the bytes.  The bytes are little-endian values of ``input_format`` (``StreamServer``'s: "f32" | "s16"),
+    interleaved frames of ``channels`` values; a message holds whole frames."""
     raw = base64.decodebytes(message.encode("utf-8")) if isinstance(message, str) else bytes(message)
-    if len(raw) % 4:
-        raise ValueError(f"audio message of {len(raw)} bytes is not a whole number of float32 samples")
-    return np.frombuffer(raw, dtype="<f4")
+    dtype = INPUT_FORMATS[input_format]
+    if len(raw) % (dtype.itemsize * channels):
+        what = f"{channels}-channel {input_format} frames" if channels > 1 else \
+            ("float32 samples" if input_format == "f32" else f"{input_format} samples")
+        raise ValueError(f"audio message of {len(raw)} bytes is not a whole number of {what}")
+    return np.frombuffer(raw, dtype=dtype)
 
 
 class _ProtocolError(Exception):
@@ -80,6 +86,8 @@ class WebSocketFrontEnd:
                  backlog_timeout: float = 10.0):
         self.server, self.host, self.port = server, host, int(port)
         self.idle_sleep, self.max_message = idle_sleep, int(max_message)
+        # every connection sends what the server was built for (no per-connection negotiation)
+        self._format, self._channels = getattr(server, "input_format", "f32"), getattr(server, "input_channels", 1)
         # back-pressure: a connection whose stream holds more than this much unprocessed audio is not
         # read from (TCP flow control then slows the sender); if the backlog has not drained after
         # `backlog_timeout` seconds (stalled worker, or a client far ahead of real time) the
@@ -232,7 +240,8 @@ class WebSocketFrontEnd:
                 else:
                     raise _ProtocolError(f"unexpected opcode {op}")
                 if fin:
-                    samples = decode_audio(buf.decode("utf-8") if kind == _OP_TEXT else buf)
+                    samples = decode_audio(buf.decode("utf-8") if kind == _OP_TEXT else buf, self._format,
+                                           self._channels)
                     pending = self.server.push(sid, samples)
                     buf, kind = b"", None
                     waited = 0.0

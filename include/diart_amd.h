@@ -600,7 +600,10 @@ int dz_prof_get(int tag, const char** name, double* total_ms, long long* launche
  * per-chunk upload of the full window (blocks/segmentation.py:47, blocks/embedding.py:52) for the
  * N-stream driver: every step only the `hop` new samples of each stream are pushed (32 KB
  * instead of 320 KB per stream at 5 s / 500 ms); dz_ring_window returns the (pointer, row
- * stride) pair dz_seg_forward / dz_emb_frames read in place.  window % hop == 0, hop % 4 == 0.
+ * stride) pair dz_seg_forward / dz_emb_frames read in place.  window % hop == 0.  A ring whose
+ * hop is not a multiple of 4 samples (44.1 kHz: 22 050 per 500 ms) serves the per-row entry points,
+ * dz_ring_push and dz_ring_read only, at 4-byte granularity: dz_ring_window refuses it (its
+ * windows do not start on 16-byte boundaries, which the in-place readers need).
  * slack_blocks extra blocks of history are kept so that pushing block t+1 never overwrites a
  * sample of windows t-slack_blocks+1 .. t (forward passes of those may still be in flight).     */
 typedef struct dz_ring dz_ring;
@@ -623,6 +626,16 @@ int dz_ring_read(const dz_ring* r, float* d_out, void* stream);
  * dz_emb_frames — each must be complete (dz_ring_filled_row).  dz_ring_reset_row: the stream left. */
 int dz_ring_push_rows(dz_ring* r, const float* block, long long block_stride, int on_device,
                       const int* rows, int k, void* stream);
+/* Raw client audio: row j of `block` holds hop interleaved frames of `channels` (1 .. 8) values of
+ * `format`, rows block_stride_bytes apart.  One kernel converts, averages the channels and writes
+ * the block to the ring.  The float32 sample it writes, operation for operation:
+ *   DZ_PCM_S16 (little-endian): (float)v * (1.0f / 32768.0f), exact;
+ *   channels > 1: ((c0 + c1) + c2 ...) / (float)channels, one IEEE division;
+ *   DZ_PCM_F32 with one channel: the input bits (what dz_ring_push_rows writes).
+ * Non-finite float input passes through (a NaN in one channel makes that frame NaN).             */
+enum { DZ_PCM_F32 = 0, DZ_PCM_S16 = 1 };
+int dz_ring_push_rows_pcm(dz_ring* r, const void* block, long long block_stride_bytes, int format, int channels,
+                          int on_device, const int* rows, int k, void* stream);
 int dz_ring_filled_row(const dz_ring* r, int row, int* filled);
 int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d_out, long long out_stride, void* stream);
 int dz_ring_reset_row(dz_ring* r, int row);
