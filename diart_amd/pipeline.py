@@ -36,6 +36,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import time as _time
+from contextlib import contextmanager
 from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -189,10 +190,84 @@ class AudioRing:
 
 
 class _StepEngine:
-    """What the N-stream engines (``StreamBatch``, ``VadBatch``, ``WeSpeakerBatch``) share: how the host waits for a
-    step, the front half of ``launch`` (rows, slots, start times) and the warm-up on silence.  A subclass provides
-    ``_launch_rows``, ``finish`` and ``reset``, and the state ``n``, ``step``, ``device``, ``max_inflight``,
-    ``warmup_steps``, ``_t``, ``_steps``, ``_warming``, ``_real_launches``, ``host_seconds``."""
+    """What the N-stream engines (``StreamBatch``, ``VadBatch``, ``WeSpeakerBatch``) share: the engine choice and the
+    bookkeeping state (``_setup``), how the host waits for a step, the front half of ``launch`` (rows, slots, start
+    times), the prelude of a window size's first launch (``_prepare``), the pool of result slots, the warm-up on silence,
+    the guarded host half of ``finish`` and the teardown of the C handles.  A subclass provides its GPU schedule
+    (``_launch_rows``), ``finish`` and ``reset``, and the hooks ``_handles``, ``_new_slot`` and ``_make_tail``."""
+
+    xvector_experiments = False     # does this engine honour the x-vector engine's experiment switches?
+    lag = 0                         # slots beyond `max_inflight` (a StreamBatch with shared embedding streams)
+
+    def _timing(self, duration: float, step: float, latency) -> None:
+        """``duration``, ``step`` and ``latency`` as the blocks pipelines read them; a latency outside [step, duration]
+        is refused."""
+        from .blocks.diarization import _latency
+        self.duration, self.step = float(duration), float(step)
+        self.latency = float(_latency(latency, self.step, self.duration))
+        if not self.step <= self.latency <= self.duration:
+            raise ValueError(f"{type(self).__name__}: latency should be in the range [{self.step}, {self.duration}], "
+                             f"got {self.latency}")
+
+    def _setup(self, segmentation: HipSegmentation, embedding, num_streams: int, device: Optional[torch.device], *,
+               lanes: Optional[int], recurrence: Optional[str], inflight: Optional[int], wait: Optional[str],
+               warmup: Optional[int], lanes_follow_recurrence: bool, spare: int) -> None:
+        """The engine under a subclass: argument checks first (nothing has touched a device when one refuses), then the
+        models on the device, the engine choice and the bookkeeping state.  ``lanes_follow_recurrence``: a matrix-core
+        recurrence at >= 64 streams gets ``THROUGHPUT_LANES`` lanes (an engine whose lanes are heavy in memory stays at
+        2 whatever the recurrence); ``spare``: the tickets such a many-lane engine keeps beyond its lanes (a two-lane
+        engine keeps one)."""
+        from .config import setting
+        if not self.xvector_experiments:
+            self._refuse_xvector_experiments()
+        self._host_wait(wait)
+        # ---- from here on the device
+        self.n = int(num_streams)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.seg = segmentation.to(self.device)
+        if embedding is not None:
+            self.emb = embedding.to(self.device)
+        self.device = self.seg.device
+        # `depth` lanes, each with its own HIP streams and scratch arenas: step t runs on lane
+        # t % depth, so a caller that keeps `depth` tickets between launch() and finish() has that
+        # many steps on the GPU at once (the latency-bound recurrence of one step under the GEMMs
+        # of the others).  A lane is reused in stream order, which also orders its arenas.
+        # Round 5: with >= 64 streams per step the recurrence runs on the matrix cores (16 chains per workgroup: a
+        # seventh of the CU-time, twice the latency of a layer) and SIX steps are in flight instead of two — the longer
+        # dependent chain of a lane hides under five other steps, and the 128 CUs the one-chain-per-CU recurrence held
+        # for most of a step go to the GEMM-shaped kernels: 30 300 -> 33 500 xRT in same-visit pairs
+        # (profiles/r05u_recurrence_lanes_grid.json; in round 4, with the slower front end, the same pair measured
+        # equal).  Fewer streams (FileBatch's 32 windows per step lost 11 % with it), the exact-f32 precision and an
+        # explicit DZ_LSTM keep what they had; the synchronous blocks API always runs the low-latency recurrence.
+        rec = setting("recurrence", recurrence, None)
+        split = getattr(self.seg, "precision", "f32") == "f16x3"
+        self.throughput = self.n >= 64 and rec is None and split and getattr(self.seg, "recurrence", "valu") == "valu"
+        # the kernel this engine's handles run: None = the model's own struct
+        self.recurrence = self.seg.throughput_recurrence() if self.throughput else (str(rec) if rec is not None and split else None)
+        matrix_core = self.recurrence not in (None, "valu")
+        many = lanes_follow_recurrence and (self.throughput or (matrix_core and self.n >= 64))
+        self.depth = max(1, int(setting("lanes", lanes, THROUGHPUT_LANES if many else 2, int)))
+        # How many launched-but-unfinished steps a throughput caller (bench.py, FileBatch) keeps: `depth` lanes
+        # run concurrently, the steps beyond that wait IN THE STREAMS of their lane, so that a lane's next
+        # step starts the moment the previous one ends instead of after the host has come back from
+        # finish() (clustering of an older step + launch overhead: ~0.5 ms per step, during which the
+        # lane's segmentation stream sat empty).
+        # Round 6: a throughput engine keeps lanes + 2 (the second spare ticket covers the host's own launch + tail time of
+        # a step: +3 % in the 20-step form, profiles/r06l_inflight_grid.json); the two-lane engines keep lanes + 1.
+        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + (spare if many else 1), int)))
+        self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
+        self._t = 0                                        # launches so far (lane selection)
+        self._steps = np.zeros(self.n, dtype=np.int64)     # windows seen by each stream slot
+        # where finish() spends its time: waiting for the GPU vs clustering + output tail on the host
+        self.host_seconds = {"wait": 0.0, "work": 0.0}
+        self.tail: Optional[BatchedOutputTail] = None      # built at the first launch, when the frames per chunk are known
+        self._sub: dict = {}                               # (S, lane) -> (segmentation handles, embedding handles, ...)
+        self._slots: List[dict] = []
+        self._warmed: set = set()
+        self._warming, self._real_steps = False, 0       # (see _warm_up)
+        self._real_launches = 0                          # launches issued for a caller (not by _warm_up)
+        self._lib = _lib.load()
+        self._ctx = _lib.context(self.device.index)
 
     def _host_wait(self, wait: Optional[str]) -> None:
         """How the host waits.  With cores to spare the launching thread spins on the step's `done` event (lowest
@@ -254,10 +329,90 @@ class _StepEngine:
         self._steps[idx] += 1
         return slot
 
+    def _prepare(self, S: int, shape: tuple) -> int:
+        """The top of every ``_launch_rows`` -> the lane of this step.  Everything a window size allocates happens here,
+        at its first launch and before its first kernel is enqueued; ``shape``: the step's slot shape, frames first."""
+        if S not in self._warmed:
+            # The scratch arenas of EVERY lane before the first kernel of this window size is enqueued
+            # (~0.85 GB of hipMalloc + hipMemset per lane): no device allocation while kernels run.  (This
+            # did NOT remove the 21 - 39 ms start-up stall some runs show in their third step — it persisted
+            # with the arenas allocated up front; profiles/README.md, DESIGN.md 4.3.)
+            for lane in range(self.depth):
+                self._handles(S, lane)
+            # ... and the output tail's host state NOW, while the GPU is idle: built lazily in the first
+            # finish() — 64 aggregation states (30 MB of fresh host memory, mapped and first touched) + 7.5 MB
+            # of result buffers while two steps were on the GPU — it froze every resident kernel for 20 - 40 ms
+            # (tools/stall_probe.py: gone when only this is moved; the first clustering call, which starts the
+            # worker threads, is not the trigger).  This was the start-up stall of rounds 1 - 3.
+            if self.tail is None:
+                self.tail = self._make_tail(shape[0])
+            # ... and the slots (the first take of a shape allocates all of them), then the warm-up.  One order for
+            # every engine: the warm-up's own launches would allocate the slots anyway, before their first kernel.
+            self._release(self._take_slot(shape))
+            self._warmed.add(S)
+            self._warm_up(S)
+        if not self._warming:
+            self._real_launches += 1
+        return self._t % self.depth
+
+    def _take_slot(self, shape: tuple) -> dict:
+        """The first free slot of this shape, marked busy: a step's device and pinned result buffers and its events,
+        the ticket ``launch`` returns.  A subclass's ``_new_slot(shape)`` supplies its own tensors and events."""
+        pool = [s for s in self._slots if s["shape"] == shape]
+        if not pool:
+            # every in-flight slot up front: a pinned-memory allocation made while kernels are
+            # running stalls the queues for tens of milliseconds (seen as one 40 ms "kernel" in the
+            # rocprofv3 trace of the second step)
+            pool = [self._add_slot(shape) for _ in range(self.max_inflight + self.lag)]
+        slot = next((s for s in pool if not s["busy"]), None) or self._add_slot(shape)
+        slot["busy"] = True
+        return slot
+
+    def _add_slot(self, shape: tuple) -> dict:
+        stats = torch.empty((self.n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=self.device)
+        slot = dict(self._new_slot(shape), shape=shape, busy=False, stats=stats, ev_in=torch.cuda.Event(),
+                    done=torch.cuda.Event(blocking=self.blocking_wait))
+        self._slots.append(slot)
+        return slot
+
+    def _release(self, ticket: dict) -> None:
+        """Hand a ticket's slot back to the pool.  EVERY path out of a step ends here: a slot left busy makes each
+        later launch allocate a new pinned one while kernels are running."""
+        ticket["busy"] = False
+        ticket["keep"] = None
+
+    @contextmanager
+    def _host_half(self, ticket: dict):
+        """The guarded host half of a step: wait for its GPU half, then the body, then the slot is ALWAYS handed back
+        (an exception in the body used to leak it).  The range flag (an f16x3 operand beyond +-65504 is an error, not
+        a clamp) is checked first: a flagged step's results are clamped garbage and must not reach the
+        clustering state of the streams; the caller gets error 6 for THIS step and the streams
+        skip one window.  The flag is one word per device: with `depth` steps in flight it may have
+        been raised by a kernel of a later step, whose own finish() then passes — over-reporting by
+        at most `depth - 1` steps, never under-reporting."""
+        self._wait(ticket)
+        t1 = _time.perf_counter()
+        try:
+            _lib.range_check(self.device.index)
+            yield
+        finally:
+            self._release(ticket)
+            self.host_seconds["work"] += _time.perf_counter() - t1
+
+    def __del__(self):
+        try:
+            for hsegs, hembs, *_ in self._sub.values():
+                for h in hsegs:
+                    self.seg._destroy(h)
+                for h in hembs:
+                    self.emb._destroy(h)
+        except Exception:
+            pass
+
     def _warm_up(self, S: int) -> None:
         """A few overlapped steps on silence before the first real one of this window size.  Besides the
         start-up stall proper (the output tail's host buffers, allocated before the first launch: see
-        `StreamBatch._launch_rows`), a fresh process shows two 7 - 12 ms intervals within its first ~8 steps
+        `_prepare`), a fresh process shows two 7 - 12 ms intervals within its first ~8 steps
         (tools/stall_probe.py, no tracer; profiles/r03_f_stall_probe.txt): one-time set-up for the first
         launches of each kernel on each queue — gone after warm steps, while warming the streams, the copy
         path and the events alone did not move them.  Complete steps (GPU + host half: the worker pool's
@@ -289,12 +444,11 @@ class _StepEngine:
                 for _ in range(steps):
                     inflight.append(self._launch_rows(zeros.data_ptr(), zeros.stride(0), self.n, S, zeros))
                     if len(inflight) >= self.max_inflight:
-                        t = inflight.pop(0)
-                        self._wait(t)
-                        t["busy"], t["keep"] = False, None
+                        self._wait(inflight[0])
+                        self._release(inflight.pop(0))
                 for t in inflight:
                     self._wait(t)
-                    t["busy"], t["keep"] = False, None
+                    self._release(t)
         finally:
             self._warming = False
         torch.cuda.synchronize(self.device)
@@ -318,8 +472,24 @@ class _StepEngine:
 class _DiarizationEngine(_StepEngine):
     """The host half of the engines that diarize (``StreamBatch``, ``WeSpeakerBatch``): N clustering states and
     (``tail=True``) N aggregation / binarisation states, stepped on the C++ workers from a ticket's pinned
-    segmentation scores and embeddings.  A subclass sets ``clustering``, ``tail``, ``with_tail``, ``cluster_threads``,
-    ``max_speakers``, ``tau_active``, ``duration``, ``latency`` and ``_real_steps``."""
+    segmentation scores and embeddings."""
+
+    def _setup_host(self, tau_active, rho_update, delta_new, gamma, beta, max_speakers, normalize_embedding_weights,
+                    cluster_threads, tail, duration, step, latency) -> None:
+        """The N clustering states and the parameters of the output tail (DelayedAggregation + Binarize of every stream,
+        C++; built at the first launch, when the number of frames per chunk is known)."""
+        self.gamma, self.beta, self.norm_w = float(gamma), float(beta), bool(normalize_embedding_weights)
+        self.clustering = BatchedSpeakerClustering(self.n, tau_active, rho_update, delta_new, max_speakers,
+                                                   cluster_threads)
+        self.max_speakers, self.tau_active, self.cluster_threads = max_speakers, tau_active, cluster_threads
+        self.with_tail, self.duration, self.step = bool(tail), float(duration), float(step)
+        self.latency = self.step if latency is None else float(latency)
+
+    def _make_tail(self, F: int) -> Optional[BatchedOutputTail]:
+        if not self.with_tail:
+            return None
+        return BatchedOutputTail(self.n, F, self.max_speakers, self.step, self.latency, self.tau_active,
+                                 num_threads=self.cluster_threads)
 
     def set_host_threads(self, n: int) -> int:
         """Host threads of the per-stream CPU stages (clustering, aggregation + binarisation) from now on."""
@@ -344,20 +514,9 @@ class _DiarizationEngine(_StepEngine):
         -> (segmentation (N,F,K) f32, embeddings (N,K,D) f32, scores (N,F,G) f64 | None, assign (N,K)).
         The arrays (and ``ticket["tail"]``) are views of buffers that a later ``launch`` / ``finish``
         reuses: copy what has to outlive the next step."""
-        self._wait(ticket)
         if not self._warming:
             self._real_steps += 1
-        t1 = _time.perf_counter()
-        # The ticket's slot is ALWAYS handed back (ADVICE r2): an exception between here and the end
-        # used to leak it, and every later launch then allocated a new pinned slot while kernels were
-        # running.  The range flag (an f16x3 operand beyond +-65504 is an error, not a clamp) is
-        # checked first: a flagged step's results are clamped garbage and must not reach the
-        # clustering state of the streams; the caller gets error 6 for THIS step and the streams
-        # skip one window.  The flag is one word per device: with `depth` steps in flight it may have
-        # been raised by a kernel of a later step, whose own finish() then passes — over-reporting by
-        # at most `depth - 1` steps, never under-reporting.
-        try:
-            _lib.range_check(self.device.index)
+        with self._host_half(ticket):
             N, slots = ticket["rows"], ticket["slots"]
             seg = ticket["seg_h"].numpy()[:N]
             emb = ticket["emb_h"].numpy()[:N]
@@ -366,14 +525,8 @@ class _DiarizationEngine(_StepEngine):
                 # diarization.py:190,203-232 for every stream: aggregate the overlapping windows of the
                 # region [t - latency, t - latency + step) and binarise it
                 if self.tail is None:
-                    self.tail = BatchedOutputTail(self.n, seg.shape[1], self.max_speakers, self.step,
-                                                  self.latency, self.tau_active,
-                                                  num_threads=self.cluster_threads)
+                    self.tail = self._make_tail(seg.shape[1])
                 ticket["tail"] = self.tail(scores, ticket["starts"], self.duration / seg.shape[1], slots=slots)
-        finally:
-            ticket["busy"] = False
-            ticket["keep"] = None
-            self.host_seconds["work"] += _time.perf_counter() - t1
         return seg, emb, scores, assign
 
     def diarize(self, waves: torch.Tensor, starts=None):
@@ -388,6 +541,8 @@ class _DiarizationEngine(_StepEngine):
 
 
 class StreamBatch(_DiarizationEngine):
+    xvector_experiments = True
+
     def __init__(self, segmentation: HipSegmentation,
                  embedding: Union[HipEmbedding, HipEcapaEmbedding, HipSbXvectorEmbedding], num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
@@ -424,26 +579,9 @@ class StreamBatch(_DiarizationEngine):
                              "HipEmbedding (pyannote/embedding), HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb) and "
                              "HipSbXvectorEmbedding (speechbrain/spkrec-xvect-voxceleb). "
                              "Use WeSpeakerBatch (the N-stream engine of pyannote/wespeaker-voxceleb-resnet34-LM)")
-        from .config import setting
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)
-        self.device = self.seg.device
         # the groups form (ECAPA, speechbrain x-vector): the whole embedding network behind the step's segmentation,
         # each stream's K rows with their own batch geometry, through the model's groups_launch
-        self.ecapa = isinstance(self.emb, (HipEcapaEmbedding, HipSbXvectorEmbedding))
-        self.n = num_streams
-        self.gamma, self.beta, self.norm_w = float(gamma), float(beta), bool(normalize_embedding_weights)
-        self.clustering = BatchedSpeakerClustering(num_streams, tau_active, rho_update, delta_new,
-                                                   max_speakers, cluster_threads)
-        self.max_speakers = max_speakers
-        # optional output tail (DelayedAggregation + Binarize of every stream, C++): built on the
-        # first step, when the number of frames per chunk is known
-        self.with_tail, self.duration, self.step = bool(tail), float(duration), float(step)
-        self.latency = self.step if latency is None else float(latency)
-        self.tau_active, self.cluster_threads = tau_active, cluster_threads
-        self.tail: Optional[BatchedOutputTail] = None
-        self._t = 0                                        # launches so far (lane selection)
-        self._steps = np.zeros(num_streams, dtype=np.int64)   # windows seen by each stream slot
+        self.ecapa = isinstance(embedding, (HipEcapaEmbedding, HipSbXvectorEmbedding))
         # sub-batches per network, each on its own HIP stream with its own scratch arena: the
         # x-projection GEMM of one sub-batch runs under the latency-bound recurrence of another
         self.seg_split = max(1, min(int(_lib.exp_env("DZ_SEG_SPLIT", "1") if seg_split is None else seg_split), num_streams))
@@ -451,45 +589,20 @@ class StreamBatch(_DiarizationEngine):
         if self.ecapa and self.emb_split != 1:
             raise ValueError(f"StreamBatch: emb_split={self.emb_split} with an ECAPA or speechbrain x-vector embedding "
                              "(its forward is one launch sequence over every stream's rows: emb_split must be 1)")
+        if depth is not None and lanes is not None and int(depth) != int(lanes):
+            raise ValueError(f"StreamBatch: depth={depth} and lanes={lanes} name the same thing")
+        # (an ECAPA engine keeps 2 lanes whatever the recurrence: ~6 GB of arena per lane at 64 streams)
+        self._setup(segmentation, embedding, num_streams, device, lanes=lanes if lanes is not None else depth,
+                    recurrence=recurrence, inflight=inflight, wait=wait, warmup=warmup,
+                    lanes_follow_recurrence=not self.ecapa, spare=2)
+        self._setup_host(tau_active, rho_update, delta_new, gamma, beta, max_speakers, normalize_embedding_weights,
+                         cluster_threads, tail, duration, step, latency)
         # HIP stream priorities (0 normal, -1 high).  The segmentation chain is the long dependent one
         # (4 recurrences + their projections: ~2.2 ms in the pipeline, two lanes): its streams get the
         # high priority — round 3, two same-visit pairs: 1.215 vs 1.233 and 1.159 vs 1.180 ms per step
         # (gpurun_out/visit_r3l.log; in round 2, with longer small kernels in that chain, the effect was
         # inside the noise).  The embedding chain waits for the segmentation anyway and stays normal.
         pa, pb = int(_lib.exp_env("DZ_PRIO_A", "-1")), int(_lib.exp_env("DZ_PRIO_B", "0"))
-        # `depth` lanes, each with its own HIP streams and scratch arenas: step t runs on lane
-        # t % depth, so a caller that keeps `depth` tickets between launch() and finish() has that
-        # many steps on the GPU at once (the latency-bound recurrence of one step under the GEMMs
-        # of the others).  A lane is reused in stream order, which also orders its arenas.
-        # Round 5: with >= 64 streams per step the recurrence runs on the matrix cores (16 chains per workgroup: a
-        # seventh of the CU-time, twice the latency of a layer) and SIX steps are in flight instead of two — the longer
-        # dependent chain of a lane hides under five other steps, and the 128 CUs the one-chain-per-CU recurrence held
-        # for most of a step go to the GEMM-shaped kernels: 30 300 -> 33 500 xRT in same-visit pairs
-        # (profiles/r05u_recurrence_lanes_grid.json; in round 4, with the slower front end, the same pair measured
-        # equal).  Fewer streams (FileBatch's 32 windows per step lost 11 % with it), the exact-f32 precision and an
-        # explicit DZ_LSTM keep what they had; the synchronous blocks API always runs the low-latency recurrence.
-        rec = setting("recurrence", recurrence, None)
-        split = getattr(self.seg, "precision", "f32") == "f16x3"
-        self.throughput = num_streams >= 64 and rec is None and split and getattr(self.seg, "recurrence", "valu") == "valu"
-        # the kernel this engine's handles run: None = the model's own struct
-        self.recurrence = self.seg.throughput_recurrence() if self.throughput else (str(rec) if rec is not None and split else None)
-        if depth is not None and lanes is not None and int(depth) != int(lanes):
-            raise ValueError(f"StreamBatch: depth={depth} and lanes={lanes} name the same thing")
-        matrix_core = self.recurrence not in (None, "valu")
-        # (an ECAPA engine keeps 2 lanes whatever the recurrence: ~6 GB of arena per lane at 64 streams)
-        many = (self.throughput or (matrix_core and num_streams >= 64)) and not self.ecapa
-        self.depth = max(1, int(setting("lanes", lanes if lanes is not None else depth,
-                                        THROUGHPUT_LANES if many else 2, int)))
-        # How many launched-but-unfinished steps a throughput caller (bench.py, FileBatch) keeps: `depth` lanes
-        # run concurrently, the steps beyond that wait IN THE STREAMS of their lane, so that a lane's next
-        # step starts the moment the previous one ends instead of after the host has come back from
-        # finish() (clustering of an older step + launch overhead: ~0.5 ms per step, during which the
-        # lane's segmentation stream sat empty).
-        # Round 6: a throughput engine keeps lanes + 2 (the second spare ticket covers the host's own launch + tail time of
-        # a step: +3 % in the 20-step form, profiles/r06l_inflight_grid.json); the two-lane engines keep lanes + 1.
-        spare = 2 if many else 1
-        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + spare, int)))
-        self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
         # DZ_SHARED_EMB=1: ONE set of embedding streams serves every lane in step order and the
         # pooling of step t is enqueued `lag` = depth - 1 launches later, behind the frame features
         # of the following steps (only the last two kernels of the embedding network wait for the
@@ -501,7 +614,6 @@ class StreamBatch(_DiarizationEngine):
         # DZ_ABLATE=noemb | noseg: TIMING EXPERIMENT (results are wrong): one of the two networks is not launched,
         # to see what the step costs when the other one has the chip to itself
         self._ablate = _lib.exp_env("DZ_ABLATE", "")
-        self._host_wait(wait)
         self.shared_stats = _lib.exp_env("DZ_SHARED_STATS", "1") != "0"
         self.shared_emb = _lib.exp_env("DZ_SHARED_EMB", "0") != "0"
         self.lag = self.depth - 1 if self.shared_emb else 0
@@ -538,43 +650,23 @@ class StreamBatch(_DiarizationEngine):
                            and hasattr(self.emb, "_state") and type(self.emb).__name__ == "HipEmbedding")
         self._pair = None                                  # PackedConv0Pair, built at the first launch
         self._pending: List[dict] = []                     # launched, pooling not enqueued yet
-        # where finish() spends its time: waiting for the GPU vs clustering + output tail on the host
-        self.host_seconds = {"wait": 0.0, "work": 0.0}
         # measurement (bench.py sets it to a list): launches that took the host more than 2 ms, by the call they sat in
         self.slow_launches: Optional[list] = None
         self.d2h_by_kernel = True          # (False: the hipMemcpyAsync pair, kept for the A/B of profiles/r06z_launch_stalls.json)
-        self._sub: dict = {}
-        self._warmed: set = set()
-        self._warming, self._real_steps = False, 0       # (see _warm_up)
-        self._real_launches = 0                          # launches issued for a caller (not by _warm_up)
-        self._slots: List[dict] = []
-        self._lib = _lib.load()
-        self._ctx = _lib.context(self.device.index)
 
     # ------------------------------------------------------------------ GPU half
-    def _slot(self, F: int, K: int, D: int) -> dict:
-        for s in self._slots:
-            if not s["busy"] and s["shape"] == (F, K, D):
-                return s
-        return self._new_slot(F, K, D)
-
-    def _new_slot(self, F: int, K: int, D: int) -> dict:
-        n, dev = self.n, self.device
-        s = dict(shape=(F, K, D), busy=False,
-                 seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
-                 w=torch.empty((n, K, F), dtype=torch.float32, device=dev),
-                 emb=torch.empty((n, K, D), dtype=torch.float32, device=dev),
-                 stats=torch.empty((n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=dev),
-                 seg_h=torch.empty((n, F, K), dtype=torch.float32).pin_memory(),
-                 emb_h=torch.empty((n, K, D), dtype=torch.float32).pin_memory(),
-                 ev_seg=[torch.cuda.Event() for _ in range(self.seg_split)],
-                 ev_front=[torch.cuda.Event() for _ in range(self.seg_split)],
-                 ev_emb=[torch.cuda.Event() for _ in range(self.emb_split - 1)],
-                 ev_frames=[torch.cuda.Event() for _ in range(self.emb_split)],
-                 ev_in=torch.cuda.Event(), ev_conv0=torch.cuda.Event(),
-                 done=torch.cuda.Event(blocking=self.blocking_wait))
-        self._slots.append(s)
-        return s
+    def _new_slot(self, shape: tuple) -> dict:
+        (F, K, D), n, dev = shape, self.n, self.device
+        return dict(seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
+                    w=torch.empty((n, K, F), dtype=torch.float32, device=dev),
+                    emb=torch.empty((n, K, D), dtype=torch.float32, device=dev),
+                    seg_h=torch.empty((n, F, K), dtype=torch.float32).pin_memory(),
+                    emb_h=torch.empty((n, K, D), dtype=torch.float32).pin_memory(),
+                    ev_seg=[torch.cuda.Event() for _ in range(self.seg_split)],
+                    ev_front=[torch.cuda.Event() for _ in range(self.seg_split)],
+                    ev_emb=[torch.cuda.Event() for _ in range(self.emb_split - 1)],
+                    ev_frames=[torch.cuda.Event() for _ in range(self.emb_split)],
+                    ev_conv0=torch.cuda.Event())
 
     @staticmethod
     def _ranges(n: int, parts: int) -> List[Tuple[int, int]]:
@@ -595,57 +687,20 @@ class StreamBatch(_DiarizationEngine):
             got = self._sub[(S, lane)] = (hs, he, sa, sb)
         return got
 
-    def __del__(self):
-        try:
-            for hs, he, _, _ in self._sub.values():
-                for h in hs:
-                    self.seg._destroy(h)
-                for h in he:
-                    self.emb._destroy(h)
-        except Exception:
-            pass
-
     def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
         """The GPU half of a step for N <= num_streams rows of S samples at ``base + i * stride``
         floats: segmentation (+ OSP weights) and frame features on this step's lane, pooling behind
         them.  Knows nothing about which stream / file a row belongs to (``launch`` and ``FileBatch``
         decide that)."""
         assert 1 <= N <= self.n
-        F, K, D = self.seg.num_frames(S), None, self.emb.dimension
-        if (S, 0) not in self._sub:
-            # The scratch arenas of EVERY lane before the first kernel of this window size is enqueued
-            # (~0.85 GB of hipMalloc + hipMemset per lane): no device allocation while kernels run.  (This
-            # did NOT remove the 21 - 39 ms start-up stall some runs show in their third step — it persisted
-            # with the arenas allocated up front; profiles/README.md, DESIGN.md 4.3.)
-            for ln in range(self.depth):
-                self._handles(S, ln)
-            # ... and the output tail's host state NOW, while the GPU is idle: built lazily in the first
-            # finish() — 64 aggregation states (30 MB of fresh host memory, mapped and first touched) + 7.5 MB
-            # of result buffers while two steps were on the GPU — it froze every resident kernel for 20 - 40 ms
-            # (tools/stall_probe.py: gone when only this is moved; the first clustering call, which starts the
-            # worker threads, is not the trigger).  This was the start-up stall of rounds 1 - 3.
-            if self.with_tail and self.tail is None:
-                self.tail = BatchedOutputTail(self.n, F, self.max_speakers, self.step, self.latency,
-                                              self.tau_active, num_threads=self.cluster_threads)
-        if S not in self._warmed:
-            self._warmed.add(S)
-            self._warm_up(S)
-        if not self._warming:
-            self._real_launches += 1
-        lane = self.lanes[self._t % self.depth]
-        hsegs, hembs, _, _ = self._handles(S, self._t % self.depth)
+        F, K, D = self.seg.num_frames(S), self.seg.num_speakers, self.emb.dimension
+        ln = self._prepare(S, (F, K, D))
+        lane = self.lanes[ln]
+        hsegs, hembs, _, _ = self._handles(S, ln)
         marks = [("start", _time.perf_counter())] if self.slow_launches is not None else None
         # sub-batch ranges of THIS step's rows (each at most the capacity its handle was built for)
         sa, sb = self._ranges(N, self.seg_split), self._ranges(N, self.emb_split)
-        K = self.seg.num_speakers
-        if not any(s["shape"] == (F, K, D) for s in self._slots):
-            # every in-flight slot up front: a pinned-memory allocation made while kernels are
-            # running stalls the queues for tens of milliseconds (seen as one 40 ms "kernel" in the
-            # rocprofv3 trace of the second step)
-            for _ in range(self.max_inflight + self.lag):
-                self._new_slot(F, K, D)
-        slot = self._slot(F, K, D)
-        slot["busy"] = True
+        slot = self._take_slot((F, K, D))
         lib, esz = self._lib, 4
         cur = torch.cuda.current_stream(self.device)
         slot["ev_in"].record(cur)                       # inputs produced on the caller's stream
@@ -785,7 +840,6 @@ class StreamBatch(_DiarizationEngine):
     # ------------------------------------------------------------------ host half
     def _wait(self, ticket: dict) -> None:
         """Block until the GPU half of the step is done and its results are in pinned host memory."""
-        import time as _time
         t0 = _time.perf_counter()
         while ticket["pool"] is not None:               # its pooling is still held back: flush in order
             self._enqueue_pool(self._pending.pop(0))
@@ -815,45 +869,18 @@ class VadBatch(_StepEngine):
                  device: Optional[torch.device] = None, *, lanes: Optional[int] = None,
                  recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
                  warmup: Optional[int] = None, host_threads: int = 8, serial: bool = False):
-        from .blocks.diarization import _latency
-        from .config import setting
         if serial:
             raise ValueError("VadBatch: serial=True is the measurement engine of StreamBatch (bench.py's roofline "
                              "pass); the VAD engine has no serial form")
-        self._refuse_xvector_experiments()
-        self.duration, self.step = float(duration), float(step)
-        self.latency = float(_latency(latency, self.step, self.duration))
-        if not self.step <= self.latency <= self.duration:
-            raise ValueError(f"VadBatch: latency should be in the range [{self.step}, {self.duration}], "
-                             f"got {self.latency}")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.seg = segmentation.to(self.device)
-        self.device = self.seg.device
-        self.n, self.tau_active, self.host_threads = int(num_streams), float(tau_active), max(1, int(host_threads))
-        # the engine StreamBatch would pick for these streams (see there): a throughput engine at >= 64 streams in
-        # the default precision runs the matrix-core recurrence on THROUGHPUT_LANES lanes
-        rec = setting("recurrence", recurrence, None)
-        split = getattr(self.seg, "precision", "f32") == "f16x3"
-        self.throughput = self.n >= 64 and rec is None and split and getattr(self.seg, "recurrence", "valu") == "valu"
-        self.recurrence = self.seg.throughput_recurrence() if self.throughput else (str(rec) if rec is not None and split else None)
-        many = self.throughput or (self.recurrence not in (None, "valu") and self.n >= 64)
-        self.depth = max(1, int(setting("lanes", lanes, THROUGHPUT_LANES if many else 2, int)))
-        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + (2 if many else 1), int)))
-        self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
-        self._host_wait(wait)
+        self._timing(duration, step, latency)
+        # the engine StreamBatch would pick for these streams: a throughput engine at >= 64 streams in the default
+        # precision runs the matrix-core recurrence on THROUGHPUT_LANES lanes
+        self._setup(segmentation, None, num_streams, device, lanes=lanes, recurrence=recurrence, inflight=inflight,
+                    wait=wait, warmup=warmup, lanes_follow_recurrence=True, spare=2)
+        self.tau_active, self.host_threads = float(tau_active), max(1, int(host_threads))
         # the segmentation chain is the whole step: its streams get the high priority, as in StreamBatch
         pa = int(_lib.exp_env("DZ_PRIO_A", "-1"))
         self.lanes = [torch.cuda.Stream(self.device, priority=pa) for _ in range(self.depth)]
-        self.tail: Optional[BatchedOutputTail] = None
-        self._t = 0
-        self._steps = np.zeros(self.n, dtype=np.int64)
-        self.host_seconds = {"wait": 0.0, "work": 0.0}
-        self._sub: dict = {}
-        self._slots: List[dict] = []
-        self._warmed: set = set()
-        self._warming, self._real_launches = False, 0
-        self._lib = _lib.load()
-        self._ctx = _lib.context(self.device.index)
 
     def set_host_threads(self, n: int) -> int:
         """Host threads of the output tail (aggregation + binarisation) from now on."""
@@ -872,54 +899,29 @@ class VadBatch(_StepEngine):
             self._steps[slot] = 0
 
     # ------------------------------------------------------------------ GPU half
-    def _handle(self, S: int, lane: int):
-        h = self._sub.get((S, lane))
-        if h is None:
-            h = self._sub[(S, lane)] = self.seg._create(S, self.n, throughput=self.throughput,
-                                                        recurrence=None if self.throughput else self.recurrence)
-        return h
+    def _handles(self, S: int, lane: int):
+        got = self._sub.get((S, lane))
+        if got is None:
+            got = self._sub[(S, lane)] = ([self.seg._create(S, self.n, throughput=self.throughput,
+                                                            recurrence=None if self.throughput else self.recurrence)], [])
+        return got
 
-    def __del__(self):
-        try:
-            for h in self._sub.values():
-                self.seg._destroy(h)
-        except Exception:
-            pass
+    def _make_tail(self, F: int) -> BatchedOutputTail:
+        return BatchedOutputTail(self.n, F, 1, self.step, self.latency, self.tau_active,
+                                 strategy="hamming", cropping_mode="loose", num_threads=self.host_threads)
 
-    def _new_slot(self, F: int) -> dict:
-        n, dev, K = self.n, self.device, self.seg.num_speakers
-        s = dict(F=F, busy=False,
-                 seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
-                 vad=torch.empty((n, F), dtype=torch.float32, device=dev),
-                 stats=torch.empty((n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=dev),
-                 vad_h=torch.empty((n, F), dtype=torch.float32).pin_memory(),
-                 ev_in=torch.cuda.Event(), done=torch.cuda.Event(blocking=self.blocking_wait))
-        self._slots.append(s)
-        return s
+    def _new_slot(self, shape: tuple) -> dict:
+        (F,), n, dev, K = shape, self.n, self.device, self.seg.num_speakers
+        return dict(seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
+                    vad=torch.empty((n, F), dtype=torch.float32, device=dev),
+                    vad_h=torch.empty((n, F), dtype=torch.float32).pin_memory())
 
     def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
         assert 1 <= N <= self.n
         F = self.seg.num_frames(S)
-        if (S, 0) not in self._sub:
-            # every lane's arena and the output tail's host state before the first kernel of this window size
-            # (allocations while kernels run stall the queues: StreamBatch._launch_rows)
-            for ln in range(self.depth):
-                self._handle(S, ln)
-            if self.tail is None:
-                self.tail = BatchedOutputTail(self.n, F, 1, self.step, self.latency, self.tau_active,
-                                              strategy="hamming", cropping_mode="loose", num_threads=self.host_threads)
-        if not any(s["F"] == F for s in self._slots):
-            for _ in range(self.max_inflight):
-                self._new_slot(F)
-        if S not in self._warmed:
-            self._warmed.add(S)
-            self._warm_up(S)
-        if not self._warming:
-            self._real_launches += 1
-        lane = self._t % self.depth
-        a, h = self.lanes[lane], self._handle(S, lane)
-        slot = next((s for s in self._slots if not s["busy"] and s["F"] == F), None) or self._new_slot(F)
-        slot["busy"] = True
+        lane = self._prepare(S, (F,))
+        a, (h,) = self.lanes[lane], self._handles(S, lane)[0]
+        slot = self._take_slot((F,))
         lib = self._lib
         slot["ev_in"].record(torch.cuda.current_stream(self.device))      # inputs produced on the caller's stream
         a.wait_event(slot["ev_in"])
@@ -942,18 +944,10 @@ class VadBatch(_StepEngine):
         """Wait for the step's GPU work and run the N output tails -> the speech track (N,F,1) f32; the step's turns
         are in ``ticket["tail"]`` (``BatchedOutputTail.__call__``'s tuple, indexed by row).  Both are views of
         buffers that a later ``launch`` / ``finish`` reuses."""
-        self._wait(ticket)
-        t1 = _time.perf_counter()
-        try:
-            # a flagged step (an f16x3 operand out of range) never reaches the streams' state: StreamBatch.finish
-            _lib.range_check(self.device.index)
+        with self._host_half(ticket):
             N, slots = ticket["rows"], ticket["slots"]
             track = ticket["vad_h"].numpy()[:N, :, None]
             ticket["tail"] = self.tail(track, ticket["starts"], self.duration / track.shape[1], slots=slots)
-        finally:
-            ticket["busy"] = False
-            ticket["keep"] = None
-            self.host_seconds["work"] += _time.perf_counter() - t1
         return track
 
     def detect(self, waves, starts=None) -> List[Annotation]:
@@ -1000,56 +994,25 @@ class WeSpeakerBatch(_DiarizationEngine):
                  latency: Optional[float] = None, *, lanes: Optional[int] = None,
                  recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
                  warmup: Optional[int] = None):
-        from .blocks.diarization import _latency
-        from .config import setting
         if not isinstance(embedding, HipWeSpeakerEmbedding):
             raise ValueError(f"WeSpeakerBatch runs the WeSpeaker ResNet34 embedding (HipWeSpeakerEmbedding), not "
                              f"{type(embedding).__name__}: use StreamBatch for HipEmbedding, HipEcapaEmbedding and "
                              "HipSbXvectorEmbedding")
         if not isinstance(segmentation, HipSegmentation):
             raise ValueError(f"WeSpeakerBatch: segmentation must be a HipSegmentation, got {type(segmentation).__name__}")
-        self._refuse_xvector_experiments()
-        self.n = int(num_streams)
-        if self.n < 1:
+        if int(num_streams) < 1:
             raise ValueError(f"WeSpeakerBatch: num_streams={num_streams}")
-        self.duration, self.step = float(duration), float(step)
-        self.latency = float(_latency(latency, self.step, self.duration))
-        if not self.step <= self.latency <= self.duration:
-            raise ValueError(f"WeSpeakerBatch: latency should be in the range [{self.step}, {self.duration}], "
-                             f"got {self.latency}")
-        self._host_wait(wait)
-        # ---- from here on the device
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.seg, self.emb = segmentation.to(self.device), embedding.to(self.device)
-        self.device = self.seg.device
-        self.gamma, self.beta, self.norm_w = float(gamma), float(beta), bool(normalize_embedding_weights)
-        self.clustering = BatchedSpeakerClustering(self.n, tau_active, rho_update, delta_new, max_speakers,
-                                                   cluster_threads)
-        self.max_speakers, self.tau_active, self.cluster_threads = max_speakers, tau_active, cluster_threads
-        self.with_tail = bool(tail)
-        self.tail: Optional[BatchedOutputTail] = None
-        # the recurrence StreamBatch would pick for these streams (see there); the lanes stay at 2 (memory, queues)
-        rec = setting("recurrence", recurrence, None)
-        split = getattr(self.seg, "precision", "f32") == "f16x3"
-        self.throughput = self.n >= 64 and rec is None and split and getattr(self.seg, "recurrence", "valu") == "valu"
-        self.recurrence = self.seg.throughput_recurrence() if self.throughput else (str(rec) if rec is not None and split else None)
-        self.depth = max(1, int(setting("lanes", lanes, 2, int)))
-        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + 1, int)))
-        self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
+        self._timing(duration, step, latency)
+        # the recurrence StreamBatch would pick for these streams; the lanes stay at 2 (memory, queues)
+        self._setup(segmentation, embedding, num_streams, device, lanes=lanes, recurrence=recurrence, inflight=inflight,
+                    wait=wait, warmup=warmup, lanes_follow_recurrence=False, spare=1)
+        self._setup_host(tau_active, rho_update, delta_new, gamma, beta, max_speakers, normalize_embedding_weights,
+                         cluster_threads, tail, self.duration, self.step, self.latency)
         # The segmentation is the short chain here, but the step's last kernels (pooling, seg_1) wait for it: its stream
         # keeps StreamBatch's high priority so that it is never queued behind the trunk's convolutions of both lanes.
         self.lanes = [dict(a=torch.cuda.Stream(self.device, priority=-1), b=torch.cuda.Stream(self.device, priority=0))
                       for _ in range(self.depth)]
         self.num_hip_streams = 2 * self.depth
-        self._t = 0
-        self._steps = np.zeros(self.n, dtype=np.int64)
-        self.host_seconds = {"wait": 0.0, "work": 0.0}
-        self._sub: dict = {}                               # (S, lane) -> (segmentation handle, dz_wsp handle)
-        self._slots: List[dict] = []
-        self._warmed: set = set()
-        self._warming, self._real_steps, self._real_launches = False, 0, 0
-        self._lib = _lib.load()
-        self._ctx = _lib.context(self.device.index)
 
     # ------------------------------------------------------------------ GPU half
     def _handles(self, S: int, lane: int):
@@ -1062,57 +1025,27 @@ class WeSpeakerBatch(_DiarizationEngine):
             except Exception:
                 self.seg._destroy(hs)
                 raise
-            got = self._sub[(S, lane)] = (hs, he)
+            got = self._sub[(S, lane)] = ([hs], [he])
         return got
 
-    def __del__(self):
-        try:
-            for hs, he in self._sub.values():
-                self.seg._destroy(hs)
-                self.emb._destroy(he)
-        except Exception:
-            pass
-
-    def _new_slot(self, F: int, K: int) -> dict:
-        n, dev, D = self.n, self.device, self.emb.dimension
-        s = dict(shape=(F, K), busy=False,
-                 seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
-                 w=torch.empty((n, K, F), dtype=torch.float32, device=dev),
-                 emb=torch.empty((n, K, D), dtype=torch.float32, device=dev),
-                 stats=torch.empty((n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=dev),
-                 seg_h=torch.empty((n, F, K), dtype=torch.float32).pin_memory(),
-                 emb_h=torch.empty((n, K, D), dtype=torch.float32).pin_memory(),
-                 ev_in=torch.cuda.Event(), ev_seg=torch.cuda.Event(),
-                 done=torch.cuda.Event(blocking=self.blocking_wait))
-        self._slots.append(s)
-        return s
+    def _new_slot(self, shape: tuple) -> dict:
+        (F, K), n, dev, D = shape, self.n, self.device, self.emb.dimension
+        return dict(seg=torch.empty((n, F, K), dtype=torch.float32, device=dev),
+                    w=torch.empty((n, K, F), dtype=torch.float32, device=dev),
+                    emb=torch.empty((n, K, D), dtype=torch.float32, device=dev),
+                    seg_h=torch.empty((n, F, K), dtype=torch.float32).pin_memory(),
+                    emb_h=torch.empty((n, K, D), dtype=torch.float32).pin_memory(),
+                    ev_seg=torch.cuda.Event())
 
     def _launch_rows(self, base: int, stride: int, N: int, S: int, keep=None, ring: Optional[AudioRing] = None) -> dict:
         """The GPU half of a step for N <= num_streams rows of S samples at ``base + i * stride`` floats; nothing here
         waits for the GPU."""
         assert 1 <= N <= self.n
         F, K, D = self.seg.num_frames(S), self.seg.num_speakers, self.emb.dimension
-        if (S, 0) not in self._sub:
-            # every lane's arenas and the output tail's host state before the first kernel of this window size
-            # (allocations while kernels run stall the queues: StreamBatch._launch_rows)
-            for ln in range(self.depth):
-                self._handles(S, ln)
-            if self.with_tail and self.tail is None:
-                self.tail = BatchedOutputTail(self.n, F, self.max_speakers, self.step, self.latency,
-                                              self.tau_active, num_threads=self.cluster_threads)
-        if not any(s["shape"] == (F, K) for s in self._slots):
-            for _ in range(self.max_inflight):
-                self._new_slot(F, K)
-        if S not in self._warmed:
-            self._warmed.add(S)
-            self._warm_up(S)
-        if not self._warming:
-            self._real_launches += 1
-        ln = self._t % self.depth
+        ln = self._prepare(S, (F, K))
         a, b = self.lanes[ln]["a"], self.lanes[ln]["b"]
-        hseg, hemb = self._handles(S, ln)
-        slot = next((s for s in self._slots if not s["busy"] and s["shape"] == (F, K)), None) or self._new_slot(F, K)
-        slot["busy"] = True
+        (hseg,), (hemb,) = self._handles(S, ln)
+        slot = self._take_slot((F, K))
         lib = self._lib
         slot["ev_in"].record(torch.cuda.current_stream(self.device))      # inputs produced on the caller's stream
         a.wait_event(slot["ev_in"])
@@ -1392,9 +1325,7 @@ class FileBatch:
 
         def finish_step():
             ticket, plan, r = inflight.pop(0)
-            self.engine._wait(ticket)
-            try:
-                _lib.range_check(self.device.index)
+            with self.engine._host_half(ticket):
                 seg = ticket["seg_h"].numpy()[:r]
                 emb = ticket["emb_h"].numpy()[:r]
                 k = len(plan)
@@ -1408,9 +1339,6 @@ class FileBatch:
                     clus, tails, k, row0.ctypes.data, count.ctypes.data, seg.ctypes.data, seg.shape[1], seg.shape[2],
                     emb.ctypes.data, emb.shape[2], self.G, starts.ctypes.data, float(res), turns.ctypes.data,
                     self._max_turns, nturns.ctypes.data, None, self.threads), "dz_file_step_batch")
-            finally:
-                ticket["busy"] = False
-                ticket["keep"] = None
             for slot, f, r0, c, _ in plan:
                 for j in range(r0, r0 + c):
                     if nturns[j]:
@@ -1442,7 +1370,7 @@ class FileBatch:
                 try:
                     self.engine._wait(ticket)
                 finally:
-                    ticket["busy"], ticket["keep"] = False, None
+                    self.engine._release(ticket)
             # the open files' pinned buffers may still be the source of a non_blocking upload: only a finished
             # copy makes them safe to hand to the next run's loader thread
             try:
