@@ -590,7 +590,7 @@ def test_gemm_f32_wide_layers(gpu, monkeypatch, B, Tin, Cin, taps, dil, N, Nstor
 def test_lstm_recurrence(gpu, B, T, kernel):
     """k_lstm.hip (one chain per CU, exact f32) and k_lstm_mfma.hip (16 chains per workgroup on the
     f16 matrix cores, split operands; both gx column orders) against torch.nn.LSTM on the CPU —
-    the SAME tolerance for both."""
+    the SAME tolerance for both.  (Against float64, where the gates saturate: tests/test_gpu_lstm_f64.py.)"""
     from diart_amd.weights import lstm_whh_planes
     if kernel[:5] in ("mfma1", "mfma2") and not _lib.experiments():
         pytest.skip("matrix-core recurrence variants 1 / 2 exist in the experiments build only")
