@@ -171,6 +171,7 @@ SIGNATURES = {
                                      C.c_int, vp, C.c_int]),
     "dz_file_step_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int,
                                      C.c_int, vp, C.c_double, vp, C.c_int, vp, vp, C.c_int]),
+    "dz_rows_repeat": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, c_int_p]),
     # kernel-level entry points
     "dz_k_convgemm": (C.c_int, [vp, vp, vp]),
     "dz_k_gemm_f32": (C.c_int, [vp, vp, vp]),

@@ -7,7 +7,8 @@ themselves (the reference's ``Benchmark`` / ``StreamingInference`` build pipelin
 
     DZ_ENGINE="recurrence=3,lanes=6,inflight=7,wait=block,precision=f32,warmup=0,split_strict=0,affinity=0"
 
-Unknown keys are refused; every override that takes effect is logged once to stderr.
+``repeated_rows=share`` is how an unchanged reference CLI turns on the shared trunk of the embedding models' ``(batch
+spk)`` call (``models.repeated_rows_mode``).  Unknown keys are refused; every override that takes effect is logged once to stderr.
 """
 from __future__ import annotations
 
@@ -15,7 +16,8 @@ import os
 import sys
 from typing import Callable, Dict, Optional
 
-KEYS = ("recurrence", "lanes", "inflight", "wait", "precision", "warmup", "split_strict", "affinity", "concurrent_files")
+KEYS = ("recurrence", "lanes", "inflight", "wait", "precision", "warmup", "split_strict", "affinity", "concurrent_files",
+        "repeated_rows")
 _parsed: Dict[str, Dict[str, str]] = {}
 _logged: set = set()
 

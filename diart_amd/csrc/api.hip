@@ -53,10 +53,17 @@ extern "C" int dz_ctx_create(int hip_device, dz_ctx** out) {
     c->conv0_user = c->convp_user = nullptr;
     c->conv0_used = c->convp_used = false;
     c->convp_cin = c->convp_kpad = 0;
+    c->rr_flags = c->rr_host = c->rr_dev = nullptr;
+    c->rr_cap = 0;
+    c->rr_user = nullptr;
+    c->rr_dirty = false;
     DZ_HIP(hipSetDevice(hip_device));
     DZ_HIP(hipHostMalloc((void**)&c->oflag_host, sizeof(int), hipHostMallocMapped));
     *c->oflag_host = 0;
     DZ_HIP(hipHostGetDevicePointer((void**)&c->oflag_dev, c->oflag_host, 0));
+    DZ_HIP(hipHostMalloc((void**)&c->rr_host, sizeof(int), hipHostMallocMapped));
+    *c->rr_host = 0;
+    DZ_HIP(hipHostGetDevicePointer((void**)&c->rr_dev, c->rr_host, 0));
     *out = c;
     return 0;
 }
@@ -64,6 +71,8 @@ extern "C" int dz_ctx_destroy(dz_ctx* ctx) {
     if (ctx && ctx->oflag_host) (void)hipHostFree(ctx->oflag_host);
     if (ctx && ctx->conv0_frag) (void)hipFree(ctx->conv0_frag);
     if (ctx && ctx->convp_frag) (void)hipFree(ctx->convp_frag);
+    if (ctx && ctx->rr_host) (void)hipHostFree(ctx->rr_host);
+    if (ctx && ctx->rr_flags) (void)hipFree(ctx->rr_flags);
     delete ctx;
     return 0;
 }
@@ -1199,6 +1208,48 @@ extern "C" int dz_k_sinc_conv0_split(dz_ctx* ctx, const float* d_wave, long long
                                       d_filt_split, d_y0, g.P0, d_partials, g.nt0, (hipStream_t)stream, ctx->conv0_frag);
 }
 extern "C" int dz_k_conv0_split_ntile(int samples) { return sinc_geom(samples, true).nt0; }
+extern "C" int dz_rows_repeat(dz_ctx* ctx, const float* d_wave, long long wave_stride, int n_rows, int num_samples,
+                              void* stream, int* repeat_out) {
+    DZ_REQUIRE(ctx && d_wave && repeat_out, "dz_rows_repeat: NULL argument");
+    DZ_REQUIRE(((uintptr_t)d_wave & 3) == 0, "dz_rows_repeat: d_wave %p is not a float address", (const void*)d_wave);
+    DZ_REQUIRE(n_rows >= 1 && num_samples >= 1, "dz_rows_repeat: %d rows of %d samples", n_rows, num_samples);
+    DZ_REQUIRE(n_rows == 1 || wave_stride >= 0, "dz_rows_repeat: negative stride %lld", wave_stride);
+    if (n_rows == 1) {
+        *repeat_out = 1;
+        return 0;
+    }
+    DZ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    DZ_HIP(hipStreamIsCapturing(st, &capturing));
+    DZ_REQUIRE(capturing == hipStreamCaptureStatusNone,
+               "dz_rows_repeat: the stream is being captured; this call waits for its answer and cannot be part of a graph");
+    std::lock_guard<std::mutex> lock(ctx->rr_mu);
+    if (ctx->rr_dirty) {                          // the previous call's wait failed: its kernels may still own the flags
+        DZ_HIP(hipStreamSynchronize(ctx->rr_user));
+        if (ctx->rr_flags) DZ_HIP(hipMemsetAsync(ctx->rr_flags, 0, (size_t)ctx->rr_cap * sizeof(int), st));
+        ctx->rr_dirty = false;
+    }
+    if (n_rows > ctx->rr_cap) {                   // (no kernel of an earlier call is running: every call ends in a wait)
+        if (ctx->rr_flags) DZ_HIP(hipFree(ctx->rr_flags));
+        ctx->rr_flags = nullptr;
+        ctx->rr_cap = 0;
+        const int cap = n_rows < 1024 ? 1024 : n_rows;
+        DZ_HIP(hipMalloc((void**)&ctx->rr_flags, (size_t)cap * sizeof(int)));
+        ctx->rr_cap = cap;
+        DZ_HIP(hipMemsetAsync(ctx->rr_flags, 0, (size_t)cap * sizeof(int), st));
+    }
+    ctx->rr_user = st;
+    ctx->rr_dirty = true;
+    int rc;
+    if ((rc = dz_launch_rows_repeat(d_wave, wave_stride, n_rows, num_samples, ctx->rr_flags, ctx->rr_dev, st))) return rc;
+    DZ_HIP(hipStreamSynchronize(st));             // the one wait: four bytes of verdict
+    ctx->rr_dirty = false;
+    const int r = *(volatile int*)ctx->rr_host;
+    DZ_REQUIRE(r >= 1 && n_rows % r == 0, "dz_rows_repeat: the device answered %d for %d rows", r, n_rows);
+    *repeat_out = r;
+    return 0;
+}
 #ifdef DZ_EXPERIMENTS
 extern "C" int dz_k_sinc_conv0_pair(dz_ctx* ctx, const float* d_wave, long long stride, int batch, int samples,
                                     const float* d_moments, const void* d_pair_planes, const float* d_pair_bsum,

@@ -639,6 +639,12 @@ int dz_launch_resample(const float* in, long long in_stride, long long in_len, i
                        int tap_major, int n, int n_pad, int o, int width, int T, float* out, long long out_stride,
                        long long out_len, hipStream_t st);
 
+// k_rows_repeat.hip -------------------------------------------------------
+// *repeat_out = gcd(n_rows, lengths of the runs of bitwise-equal rows); differs[n_rows] must be zero and is zero again
+// when the second kernel has run; n_rows >= 2
+int dz_launch_rows_repeat(const float* wave, long long stride, int n_rows, int S, int* differs, int* repeat_out,
+                          hipStream_t st);
+
 struct dz_ctx {
     int device;
     // "an operand left the f16 range" flag of the split-f16 kernels: one int in pinned, device-mapped
@@ -655,4 +661,14 @@ struct dz_ctx {
     std::mutex frag_mu;
     hipStream_t conv0_user, convp_user;
     bool conv0_used, convp_used;
+    // dz_rows_repeat: one "differs" flag per row (grown on demand, zero between calls) and the verdict, one int in
+    // pinned, device-mapped host memory.  Guarded like the scratch above: rr_mu is held from the launch to the end of
+    // the wait, and a call that follows one whose wait failed first waits for that stream and zeroes the flags again
+    int* rr_flags;
+    int rr_cap;
+    int* rr_host;
+    int* rr_dev;
+    std::mutex rr_mu;
+    hipStream_t rr_user;
+    bool rr_dirty;
 };

@@ -48,6 +48,28 @@ def default_precision(given: Optional[str] = None) -> str:
     return p
 
 
+REPEATED_ROWS = ("each", "share")
+
+
+def repeated_rows_mode(given: Optional[str] = None, shares: bool = True, who: str = "") -> str:
+    """What a model does with the K copies of every waveform in the reference's ``(batch spk)`` call
+    (blocks/embedding.py:56-59): "each" (the default) runs the network on every row, "share" asks the device how often
+    the rows repeat (``dz_rows_repeat``) and runs everything before the pooling once per distinct window.
+    ``DZ_ENGINE=repeated_rows=...`` overrides the argument of the models that can share (config.py).  ``shares=False``:
+    a model whose rows are different inputs refuses "share" and ignores the override."""
+    if shares:
+        from .config import setting
+        given = setting("repeated_rows", given, "each")
+    mode = "each" if given is None else given
+    if mode not in REPEATED_ROWS:
+        raise ValueError(f"repeated_rows={mode!r}: expected one of {REPEATED_ROWS}")
+    if mode == "share" and not shares:
+        raise ValueError(f"repeated_rows='share': {who} has no trunk to share — its masks select the SAMPLES each row "
+                         "keeps, so the K rows of a chunk are K different inputs from the first layer on "
+                         "(use forward_groups, or repeated_rows='each')")
+    return mode
+
+
 def _read_state(src: StateSource) -> Dict[str, torch.Tensor]:
     """A state dict, or a file holding one: ``.safetensors``, a plain ``torch.save`` of a state dict (speechbrain's
     ``embedding_model.ckpt``) or a PyTorch-Lightning checkpoint (``pyannote/segmentation``, ``pyannote/embedding``:
@@ -117,6 +139,31 @@ class _HipModule:
             h = (self._create(num_samples, cap), cap)
             self._handles[num_samples] = h
         return h[0]
+
+    repeated_rows = "each"
+    last_shared: Optional[tuple] = None
+    MAX_MULTI = 8               # speakers per window of dz_emb_forward_multi / dz_wsp_forward_multi (kMaxSpk, MAXK)
+
+    def _shared_call(self, rows: torch.Tensor, weights: torch.Tensor) -> Optional[torch.Tensor]:
+        """``repeated_rows="share"``: ``__call__``'s rows (N,S) and weights (N,F) through ``forward_multi`` when every
+        window is there R >= 2 times in a row — B = N / R windows addressed in place (row stride x R), weights viewed as
+        (B,R,F) -> (N,D); None when nothing repeats.  ``dz_rows_repeat`` waits for the current stream once (four bytes
+        come back).  The detected repetition may exceed the caller's speaker count when neighbouring windows are
+        bit-identical (silence): identical waveforms have identical trunks.  ``forward_multi`` pools at most
+        ``MAX_MULTI`` rows per window, and every divisor of a repetition is a repetition too, so R is the largest
+        divisor of what the device found that fits (9 -> 3, 96 -> 8; a prime above the limit -> 1: nothing is shared).
+        ``last_shared`` = the (B, R) that ran, or None."""
+        N, S = rows.shape
+        r = C.c_int(0)
+        _lib.check(_lib.load().dz_rows_repeat(_lib.context(self.device.index), rows.data_ptr(), rows.stride(0), N, S,
+                                              _stream_ptr(self.device), C.byref(r)), "dz_rows_repeat")
+        R = max(d for d in range(1, self.MAX_MULTI + 1) if r.value % d == 0)
+        if R < 2:
+            return None
+        B = N // R
+        out = self.forward_multi(rows[::R, None, :], weights.view(B, R, weights.shape[1]))
+        self.last_shared = (B, R)
+        return out.view(N, self.dimension)
 
     def _release(self):
         for h, _ in self._handles.values():
@@ -235,16 +282,18 @@ class HipEmbedding(_HipModule):
     dimension = 512
 
     def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None,
-                 weight_interp: Optional[str] = None):
+                 weight_interp: Optional[str] = None, repeated_rows: Optional[str] = None):
         """``weight_interp``: StatsPool's resampling of the pooling weights to the feature frames — "linear"
         (pyannote.audio 2.x .. 3.0: ``F.interpolate(mode="linear")``; the default, setup.cfg pins ``>=2.1.1``) or
-        "nearest" (pyannote.audio >= 3.1).  ``EmbeddingLoader`` sets it from the version a checkpoint records."""
+        "nearest" (pyannote.audio >= 3.1).  ``EmbeddingLoader`` sets it from the version a checkpoint records.
+        ``repeated_rows``: "each" | "share" (``repeated_rows_mode``)."""
         super().__init__(state, max_batch)
         self.precision = default_precision(precision)
         self.weight_interp = weight_interp or "linear"
+        self.repeated_rows = repeated_rows_mode(repeated_rows)
 
     def _extra_state(self):
-        return {"precision": self.precision, "weight_interp": self.weight_interp}
+        return {"precision": self.precision, "weight_interp": self.weight_interp, "repeated_rows": self.repeated_rows}
 
     def _pack(self, device):
         return PackedEmbedding(self._state, device, precision=self.precision, weight_interp=self.weight_interp)
@@ -270,6 +319,11 @@ class HipEmbedding(_HipModule):
             if weights.ndim != 2 or weights.shape[0] != N:
                 raise ValueError(f"weights must be (batch, frames), got {tuple(weights.shape)}")
             wptr, fw = weights.data_ptr(), weights.shape[1]
+        self.last_shared = None
+        if self.repeated_rows == "share" and weights is not None and N >= 2:
+            shared = self._shared_call(rows, weights)
+            if shared is not None:
+                return shared
         handle = self._need(S, N)
         out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
         _lib.check(_lib.load().dz_emb_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S,
@@ -313,12 +367,16 @@ class _HipSpeakerEmbedding(_HipModule):
     _frames_arg = "masks"       # what the (N, F) matrix is called (error messages)
     _int32_peeks = frozenset()  # peek buffers that hold int32
 
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int, precision: Optional[str] = None):
+    _shares = False             # does ``repeated_rows="share"`` apply (is there a speaker-independent trunk)?
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None):
         super().__init__(state, max_batch)
         self.precision = default_precision(precision)
+        self.repeated_rows = repeated_rows_mode(repeated_rows, self._shares, type(self).__name__)
 
     def _extra_state(self):
-        return {"precision": self.precision}
+        return {"precision": self.precision, "repeated_rows": self.repeated_rows}
 
     def _pack(self, device):
         return self._packer(self._state, device, precision=self.precision)
@@ -346,6 +404,11 @@ class _HipSpeakerEmbedding(_HipModule):
             if m.ndim != 2 or m.shape[0] != N:
                 raise ValueError(f"{self._frames_arg} must be (batch, frames), got {tuple(m.shape)}")
             mptr, fw = m.data_ptr(), m.shape[1]
+        self.last_shared = None
+        if self.repeated_rows == "share" and masks_or_weights is not None and N >= 2:
+            shared = self._shared_call(rows, m)
+            if shared is not None:
+                return shared
         handle = self._need(S, N)
         out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
         _lib.check(self._fn("forward")(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S, mptr, N, fw,
@@ -411,8 +474,9 @@ class HipEcapaEmbedding(_HipGroupsEmbedding):
     dimension = 192
     _c, _packer, _int32_peeks = "dz_ecapa", PackedEcapa, frozenset((5, 6, 7, 8))
 
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
-        super().__init__(state, max_batch, precision)
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None):
+        super().__init__(state, max_batch, precision, repeated_rows)
 
     def last_frames(self, num_samples: int) -> int:
         """Frames of the batch geometry of the last forward (= those of its longest kept row, what every row is
@@ -430,8 +494,9 @@ class HipSbXvectorEmbedding(_HipGroupsEmbedding):
     min_num_samples = 480
     _c, _packer, _int32_peeks = "dz_sbx", PackedSbXvector, frozenset((7, 8, 9))
 
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None):
-        super().__init__(state, max_batch, precision)
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None):
+        super().__init__(state, max_batch, precision, repeated_rows)
 
 
 class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
@@ -442,10 +507,12 @@ class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
     with a NaN / Inf sample comes back NaN."""
 
     dimension = 256
-    _c, _packer, _frames_arg = "dz_wsp", PackedWeSpeaker, "weights"
+    _c, _packer, _frames_arg, _shares = "dz_wsp", PackedWeSpeaker, "weights", True
 
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None):
-        super().__init__(state, max_batch, precision)
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None):
+        """``repeated_rows``: "each" | "share" (``repeated_rows_mode``)."""
+        super().__init__(state, max_batch, precision, repeated_rows)
 
     def num_frames(self, num_samples: int, stage: int = 0) -> int:
         """Frames of the fbank (stage 0) or after layer 1 .. 4 (``dz_wsp_frames_for``)."""
@@ -501,11 +568,17 @@ class EmbeddingLoader:
     ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector, otherwise xvector)."""
 
     def __init__(self, state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
-                 precision: Optional[str] = None, weight_interp: Optional[str] = None):
+                 precision: Optional[str] = None, weight_interp: Optional[str] = None,
+                 repeated_rows: Optional[str] = None):
         """``weight_interp`` (x-vector only): "linear" | "nearest" | None = from the ``pyannote.audio`` version the
-        checkpoint file records (>= 3.1: "nearest"; older, absent, or a plain state dict: "linear")."""
+        checkpoint file records (>= 3.1: "nearest"; older, absent, or a plain state dict: "linear").
+        ``repeated_rows``: "each" | "share" (``repeated_rows_mode``: the reference-shaped ``(batch spk)`` call runs the
+        trunk once per window; xvector and wespeaker only — ecapa and sb-xvector refuse "share")."""
+        if repeated_rows is not None and repeated_rows not in REPEATED_ROWS:
+            raise ValueError(f"repeated_rows={repeated_rows!r}: expected one of {REPEATED_ROWS}")
         self.state, self.max_batch, self.arch, self.precision = state, max_batch, arch, precision
         self.weight_interp = weight_interp
+        self.repeated_rows = repeated_rows
 
     def __call__(self):
         sd = _read_state(self.state)
@@ -515,17 +588,17 @@ class EmbeddingLoader:
         if arch == "xvector" and self.arch is None and "blocks.0.conv.weight" in sd and "blocks.16.w.weight" in sd:
             arch = "sb-xvector"     # (the pyannote x-vector packer has no ``blocks.`` keys: this state failed there)
         if arch == "sb-xvector":
-            return HipSbXvectorEmbedding(sd, self.max_batch, self.precision)
+            return HipSbXvectorEmbedding(sd, self.max_batch, self.precision, self.repeated_rows)
         if arch == "wespeaker":
-            return HipWeSpeakerEmbedding(sd, self.max_batch, self.precision)
+            return HipWeSpeakerEmbedding(sd, self.max_batch, self.precision, self.repeated_rows)
         if arch == "ecapa":
-            return HipEcapaEmbedding(sd, self.max_batch, self.precision)
+            return HipEcapaEmbedding(sd, self.max_batch, self.precision, self.repeated_rows)
         interp = self.weight_interp
         if interp is None and not isinstance(self.state, dict):
             from .checkpoint import pyannote_version
             v = pyannote_version(self.state)
             interp = "nearest" if v is not None and v >= (3, 1) else "linear"
-        return HipEmbedding(sd, self.max_batch, self.precision, interp)
+        return HipEmbedding(sd, self.max_batch, self.precision, interp, self.repeated_rows)
 
 
 # --------------------------------------------------------------------------- #
@@ -607,24 +680,25 @@ class EmbeddingModel(LazyModel):
 
     @staticmethod
     def from_state(state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
-                   precision: Optional[str] = None, weight_interp: Optional[str] = None) -> "EmbeddingModel":
-        return EmbeddingModel(EmbeddingLoader(state, max_batch, arch, precision, weight_interp))
+                   precision: Optional[str] = None, weight_interp: Optional[str] = None,
+                   repeated_rows: Optional[str] = None) -> "EmbeddingModel":
+        return EmbeddingModel(EmbeddingLoader(state, max_batch, arch, precision, weight_interp, repeated_rows))
 
     @staticmethod
-    def from_pyannote(model, use_hf_token=True) -> "EmbeddingModel":
+    def from_pyannote(model, use_hf_token=True, repeated_rows: Optional[str] = None) -> "EmbeddingModel":
         if isinstance(model, (str, Path)) and Path(model).exists():
-            return EmbeddingModel.from_state(model)
+            return EmbeddingModel.from_state(model, repeated_rows=repeated_rows)
         raise FileNotFoundError(
             f"'{model}': pass a local pyannote checkpoint / state-dict file "
             "(gated HuggingFace downloads are not available here)")
 
     @staticmethod
-    def from_pretrained(model, use_hf_token=True) -> "EmbeddingModel":
+    def from_pretrained(model, use_hf_token=True, repeated_rows: Optional[str] = None) -> "EmbeddingModel":
         if isinstance(model, (str, Path)) and Path(model).name.endswith(".onnx"):
             return EmbeddingModel.from_onnx(model)
         if isinstance(model, dict):
-            return EmbeddingModel.from_state(model)
-        return EmbeddingModel.from_pyannote(model, use_hf_token)
+            return EmbeddingModel.from_state(model, repeated_rows=repeated_rows)
+        return EmbeddingModel.from_pyannote(model, use_hf_token, repeated_rows)
 
     def __call__(self, waveform: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = super().__call__(waveform, weights)

@@ -432,6 +432,18 @@ int dz_cdist_cosine(dz_ctx* ctx, const float* d_emb, const double* d_centers,
                     int n_streams, int k_local, int g_global, int dim,
                     double* d_out, void* stream);
 
+/* ---- repeated rows (csrc/k_rows_repeat.hip) ---------------------------------
+ * The reference's SpeakerEmbedding hands the model every waveform num_speakers times (blocks/embedding.py:56-59).
+ * repeat_out receives the largest R >= 1 that divides n_rows and for which every row i with i % R != 0 is BITWISE equal
+ * to row i - 1 (the gcd of n_rows and the lengths of the runs of equal rows; 1 = nothing to share): equal NaN patterns
+ * are equal, -0.0 and +0.0 are not.  Rows of num_samples floats, wave_stride floats apart (any stride >= 0 and any
+ * float address: 16-byte loads where the rows are 16-byte aligned, 4-byte loads elsewhere).
+ * SYNCHRONOUS BY DESIGN: two kernels are enqueued on `stream`, then the call waits for `stream` and reads the four
+ * bytes of the answer from pinned host memory; it cannot be captured into a graph.  The flags it works on belong to
+ * the context; concurrent callers are serialised by a lock held until the wait is over.                          */
+int dz_rows_repeat(dz_ctx* ctx, const float* d_wave, long long wave_stride, int n_rows, int num_samples,
+                   void* stream, int* repeat_out);
+
 /* ---- kernel-level entry points ---------------------------------------------
  * The building blocks of dz_seg_forward / dz_emb_forward, exported so that each HIP
  * kernel can be parity-tested on its own against a torch fp32 restatement of the same
