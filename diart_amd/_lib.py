@@ -70,6 +70,20 @@ class SbxWeights(C.Structure):
                 ("zeros", vp)]
 
 
+class TtnSep(C.Structure):
+    _fields_ = [("dw", vp), ("pw", Layer)]
+
+
+class TtnBlock(C.Structure):
+    _fields_ = [("rep", TtnSep * 3), ("se1", vp), ("se2t", vp), ("res", Layer)]
+
+
+class TtnWeights(C.Structure):
+    _fields_ = [("dft", vp), ("dft_split", vp), ("mel", vp), ("block", TtnBlock * 5), ("asp_tdnn", Layer),
+                ("asp_wms", vp), ("asp_conv", Layer), ("fc", Layer), ("zeros", vp), ("pad_reflect", C.c_int),
+                ("frame_pad", C.c_int), ("frame_nfft", C.c_int), ("min_num_samples", C.c_int)]
+
+
 # name -> (restype, argtypes); must list every function of include/diart_amd.h
 SIGNATURES = {
     "dz_last_error": (C.c_char_p, []),
@@ -114,6 +128,13 @@ SIGNATURES = {
     "dz_sbx_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_sbx_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_sbx_destroy": (C.c_int, [vp]),
+    "dz_ttn_abi_size": (C.c_int, []),
+    "dz_ttn_frames_for": (C.c_int, [C.c_int]),
+    "dz_ttn_create": (C.c_int, [vp, C.POINTER(TtnWeights), C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_ttn_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_ttn_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_ttn_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "dz_ttn_destroy": (C.c_int, [vp]),
     "dz_wsp_abi_size": (C.c_int, []),
     "dz_wsp_frames_for": (C.c_int, [C.c_int, C.c_int]),
     "dz_wsp_create": (C.c_int, [vp, C.POINTER(WspWeights), C.c_int, C.c_int, C.POINTER(vp)]),
@@ -198,6 +219,7 @@ SIGNATURES = {
     "dz_k_powerset": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_k_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, vp]),
+    "dz_k_ttn_depthwise": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
 }
 
 
@@ -261,7 +283,7 @@ def load() -> C.CDLL:
         if list(sizes) != mine:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
-        for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights)):
+        for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights), ("dz_ttn", TtnWeights)):
             size = getattr(lib, f"{name}_abi_size")()
             if size != C.sizeof(struct):
                 raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({name}_weights) "

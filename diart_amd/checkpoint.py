@@ -8,6 +8,8 @@ needs those packages to be importable and executes whatever the file's pickle as
 download; ``weights_only=True`` refuses the foreign classes.  This module extracts ONLY tensors:
 
 * ``.safetensors`` files through ``safetensors``;
+* NeMo ``.nemo`` archives (a tar file, possibly gzip-compressed, that holds ``model_weights.ckpt`` — a ``torch.save``
+  of the state dict — and ``model_config.yaml``): the weights member goes through the same unpickler;
 * ``torch.save`` archives, both the zip form (``<name>/data.pkl`` + ``<name>/data/<key>``) and the legacy stream
   (magic number, three header pickles, the object, then the storages), through a ``pickle.Unpickler`` whose
   ``find_class`` knows tensors, storages, dtypes, ``OrderedDict`` and a few builtins; EVERY other global becomes an
@@ -22,6 +24,8 @@ from __future__ import annotations
 import io
 import pickle
 import struct
+import tarfile
+import tempfile
 import zipfile
 from collections import OrderedDict
 from pathlib import Path
@@ -231,10 +235,70 @@ def _load_legacy(path: Path):
         return obj, up.stubbed
 
 
+def _is_nemo(path: Path) -> bool:
+    """A tar archive (an uncompressed one that ends with a ``torch.save`` zip also passes ``zipfile.is_zipfile``: the
+    first bytes decide)."""
+    with open(path, "rb") as f:
+        if f.read(2) == b"PK":
+            return False
+    return tarfile.is_tarfile(path)
+
+
+def _nemo_member(path: Path, name: str):
+    """Bytes of the archive member called ``name`` (at any depth: NeMo writes ``./model_weights.ckpt``) of a ``.nemo``
+    file, a tar archive that may be gzip-compressed, or None.  Only regular files are read; nothing is extracted to
+    disk and nothing from the archive is executed."""
+    with tarfile.open(path, "r:*") as tar:
+        for member in tar:
+            if member.isfile() and member.name.rsplit("/", 1)[-1] == name:
+                return tar.extractfile(member).read()
+    return None
+
+
+def nemo_frontend(path: Union[str, Path]) -> Dict[str, Any]:
+    """The front-end switches of ``weights.PackedTitaNet`` that a ``.nemo`` archive's ``model_config.yaml`` records, as
+    keyword arguments.  Only the top-level ``preprocessor:`` section is looked at (another module's ``pad_mode`` must
+    not switch the front end): ``pad_mode`` from its ``stft_pad_mode:`` / ``pad_mode:`` entry ("reflect" | "constant"),
+    ``frame_count`` from ``frame_count:`` ("floor_plus_one" | "padded").  The entry names themselves rest on a reading
+    of NeMo's configs; ``frame_count`` is this project's own name, for an archive annotated by
+    hand.  The yaml is scanned line by line for these scalar entries — it is never loaded as an object tree.  Not a
+    .nemo file, no yaml, no such entry: {}."""
+    path = Path(path)
+    if not path.is_file() or not _is_nemo(path):
+        return {}
+    raw = _nemo_member(path, "model_config.yaml")
+    out: Dict[str, Any] = {}
+    inside = False
+    for line in (raw or b"").decode("utf-8", "replace").splitlines():
+        if not line.strip() or line.lstrip().startswith("#"):
+            continue
+        if not line[0].isspace():                       # a top-level key opens or closes the section
+            inside = line.split("#", 1)[0].strip() == "preprocessor:"
+            continue
+        if not inside:
+            continue
+        key, _, value = line.strip().partition(":")
+        value = value.split("#", 1)[0].strip().strip("'\"")
+        if key in ("stft_pad_mode", "pad_mode") and value in ("reflect", "constant"):
+            out["pad_mode"] = value
+        elif key == "frame_count" and value in ("floor_plus_one", "padded"):
+            out["frame_count"] = value
+    return out
+
+
 def load_object(path: Union[str, Path]):
     """The unpickled top-level object of a ``torch.save`` file with every non-tensor class stubbed, and the set of
-    globals that were stubbed.  Tensors are CPU tensors."""
+    globals that were stubbed.  Tensors are CPU tensors.  A ``.nemo`` archive (tar, possibly gzip-compressed): the
+    same for its ``model_weights.ckpt`` member."""
     path = Path(path)
+    if _is_nemo(path):
+        raw = _nemo_member(path, "model_weights.ckpt")
+        if raw is None:
+            raise ValueError(f"{path}: a tar archive without model_weights.ckpt (not a .nemo model?)")
+        with tempfile.TemporaryDirectory() as tmp:
+            inner = Path(tmp) / "model_weights.ckpt"
+            inner.write_bytes(raw)
+            return load_object(inner)
     if zipfile.is_zipfile(path):
         return _load_zip(path)
     return _load_legacy(path)

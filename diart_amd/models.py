@@ -29,7 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .weights import PackedEcapa, PackedEmbedding, PackedSbXvector, PackedSegmentation, PackedWeSpeaker
+from .weights import (PackedEcapa, PackedEmbedding, PackedSbXvector, PackedSegmentation, PackedTitaNet, PackedWeSpeaker,
+                      TITANET_MARKERS, TITANET_MIN_NUM_SAMPLES)
 
 StateSource = Union[str, Path, Dict[str, torch.Tensor]]
 
@@ -499,6 +500,42 @@ class HipSbXvectorEmbedding(_HipGroupsEmbedding):
         super().__init__(state, max_batch, precision, repeated_rows)
 
 
+TITANET_OPTIONS = ("pad_mode", "frame_count", "min_num_samples", "attention_order")
+
+
+class HipTitaNetEmbedding(_HipGroupsEmbedding):
+    """NeMo's TitaNet-L (nvidia/speakerverification_en_titanet_large) behind pyannote's ``PretrainedSpeakerEmbedding``
+    contract, the NeMo wrapper the reference falls back to for it (models.py:59): ``(waveform (N,1,S), masks (N,F) |
+    None) -> (N,192)``, not normalised; a row whose mask keeps fewer than ``min_num_samples`` samples, or whose kept
+    samples hold a NaN, is NaN, and a call whose longest row is that short is all NaN.  The same call shape as
+    ``HipEcapaEmbedding``, so the same engine forms take it; masks select samples, so ``repeated_rows="share"`` is
+    refused.  ``pad_mode`` / ``frame_count`` / ``min_num_samples`` / ``attention_order``: the switches of
+    ``weights.PackedTitaNet``."""
+
+    dimension = 192
+    _c, _packer, _int32_peeks = "dz_ttn", PackedTitaNet, frozenset((7, 8, 9))
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None, pad_mode: str = "reflect", frame_count: str = "floor_plus_one",
+                 min_num_samples: int = TITANET_MIN_NUM_SAMPLES, attention_order: str = "relu_bn_tanh"):
+        super().__init__(state, max_batch, precision, repeated_rows)
+        self.pad_mode, self.frame_count, self.attention_order = pad_mode, frame_count, attention_order
+        self.min_num_samples = int(min_num_samples)
+
+    def _extra_state(self):
+        return dict(super()._extra_state(), pad_mode=self.pad_mode, frame_count=self.frame_count,
+                    min_num_samples=self.min_num_samples, attention_order=self.attention_order)
+
+    def _pack(self, device):
+        return PackedTitaNet(self._state, device, precision=self.precision, pad_mode=self.pad_mode,
+                             frame_count=self.frame_count, min_num_samples=self.min_num_samples,
+                             attention_order=self.attention_order)
+
+    def num_frames(self, num_samples: int) -> int:
+        """Frames every buffer lays a row of ``num_samples`` samples out with (``dz_ttn_frames_for``)."""
+        return int(_lib.load().dz_ttn_frames_for(int(num_samples)))
+
+
 class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
     """pyannote.audio 3.1's ``WeSpeakerResNet34`` (pyannote/wespeaker-voxceleb-resnet34-LM): ``(waveform (N,1,S),
     weights (N,Fw) | None) -> (N,256)`` — the callable the reference loads through ``PyannoteLoader`` (models.py:42-59)
@@ -563,22 +600,30 @@ class SegmentationLoader:
 
 class EmbeddingLoader:
     """``arch``: "xvector" (pyannote/embedding), "ecapa" (speechbrain/spkrec-ecapa-voxceleb), "wespeaker"
-    (pyannote/wespeaker-voxceleb-resnet34-LM) or "sb-xvector" (speechbrain/spkrec-xvect-voxceleb); None = decide
-    from the checkpoint keys (``resnet.``: wespeaker, ``asp.``: ecapa, speechbrain ``Xvector`` keys
-    ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector, otherwise xvector)."""
+    (pyannote/wespeaker-voxceleb-resnet34-LM), "sb-xvector" (speechbrain/spkrec-xvect-voxceleb) or "titanet"
+    (nvidia/speakerverification_en_titanet_large, a ``.nemo`` archive); None = decide from the checkpoint keys
+    (``encoder.encoder.0.mconv.0.conv.weight`` + ``decoder.emb_layers.0.1.weight``: titanet, ``resnet.``: wespeaker,
+    ``asp.``: ecapa, speechbrain ``Xvector`` keys ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector,
+    otherwise xvector)."""
 
     def __init__(self, state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
                  precision: Optional[str] = None, weight_interp: Optional[str] = None,
-                 repeated_rows: Optional[str] = None):
-        """``weight_interp`` (x-vector only): "linear" | "nearest" | None = from the ``pyannote.audio`` version the
+                 repeated_rows: Optional[str] = None, **arch_options):
+        """``arch_options`` (titanet only): ``pad_mode``, ``frame_count``, ``min_num_samples``, ``attention_order`` of
+        ``HipTitaNetEmbedding`` — the switches DESIGN.md 4.12 marks (R); they override what the archive's yaml records.
+        ``weight_interp`` (x-vector only): "linear" | "nearest" | None = from the ``pyannote.audio`` version the
         checkpoint file records (>= 3.1: "nearest"; older, absent, or a plain state dict: "linear").
         ``repeated_rows``: "each" | "share" (``repeated_rows_mode``: the reference-shaped ``(batch spk)`` call runs the
-        trunk once per window; xvector and wespeaker only — ecapa and sb-xvector refuse "share")."""
+        trunk once per window; xvector and wespeaker only — ecapa, sb-xvector and titanet refuse "share")."""
         if repeated_rows is not None and repeated_rows not in REPEATED_ROWS:
             raise ValueError(f"repeated_rows={repeated_rows!r}: expected one of {REPEATED_ROWS}")
         self.state, self.max_batch, self.arch, self.precision = state, max_batch, arch, precision
         self.weight_interp = weight_interp
         self.repeated_rows = repeated_rows
+        unknown = set(arch_options) - set(TITANET_OPTIONS)
+        if unknown:
+            raise TypeError(f"EmbeddingLoader: unknown option(s) {sorted(unknown)} (titanet takes {TITANET_OPTIONS})")
+        self.arch_options = arch_options
 
     def __call__(self):
         sd = _read_state(self.state)
@@ -587,6 +632,19 @@ class EmbeddingLoader:
             arch = "wespeaker"
         if arch == "xvector" and self.arch is None and "blocks.0.conv.weight" in sd and "blocks.16.w.weight" in sd:
             arch = "sb-xvector"     # (the pyannote x-vector packer has no ``blocks.`` keys: this state failed there)
+        if self.arch is None and all(k in sd for k in TITANET_MARKERS):
+            arch = "titanet"
+        if arch == "titanet":
+            # the front-end switches a .nemo archive's model_config.yaml records (checkpoint.nemo_frontend)
+            kw = {}
+            if not isinstance(self.state, dict):
+                from .checkpoint import nemo_frontend
+                kw = nemo_frontend(self.state)
+            kw.update(self.arch_options)
+            return HipTitaNetEmbedding(sd, self.max_batch, self.precision, self.repeated_rows, **kw)
+        if self.arch_options:
+            raise TypeError(f"EmbeddingLoader: {sorted(self.arch_options)} are options of the titanet architecture, "
+                            f"this state is {arch!r}")
         if arch == "sb-xvector":
             return HipSbXvectorEmbedding(sd, self.max_batch, self.precision, self.repeated_rows)
         if arch == "wespeaker":
@@ -681,24 +739,26 @@ class EmbeddingModel(LazyModel):
     @staticmethod
     def from_state(state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
                    precision: Optional[str] = None, weight_interp: Optional[str] = None,
-                   repeated_rows: Optional[str] = None) -> "EmbeddingModel":
-        return EmbeddingModel(EmbeddingLoader(state, max_batch, arch, precision, weight_interp, repeated_rows))
+                   repeated_rows: Optional[str] = None, **arch_options) -> "EmbeddingModel":
+        return EmbeddingModel(EmbeddingLoader(state, max_batch, arch, precision, weight_interp, repeated_rows,
+                                              **arch_options))
 
     @staticmethod
-    def from_pyannote(model, use_hf_token=True, repeated_rows: Optional[str] = None) -> "EmbeddingModel":
+    def from_pyannote(model, use_hf_token=True, repeated_rows: Optional[str] = None, **arch_options) -> "EmbeddingModel":
         if isinstance(model, (str, Path)) and Path(model).exists():
-            return EmbeddingModel.from_state(model, repeated_rows=repeated_rows)
+            return EmbeddingModel.from_state(model, repeated_rows=repeated_rows, **arch_options)
         raise FileNotFoundError(
             f"'{model}': pass a local pyannote checkpoint / state-dict file "
             "(gated HuggingFace downloads are not available here)")
 
     @staticmethod
-    def from_pretrained(model, use_hf_token=True, repeated_rows: Optional[str] = None) -> "EmbeddingModel":
+    def from_pretrained(model, use_hf_token=True, repeated_rows: Optional[str] = None, **arch_options) -> "EmbeddingModel":
+        """``arch_options``: the (R) switches of a TitaNet model (``EmbeddingLoader``)."""
         if isinstance(model, (str, Path)) and Path(model).name.endswith(".onnx"):
             return EmbeddingModel.from_onnx(model)
         if isinstance(model, dict):
-            return EmbeddingModel.from_state(model, repeated_rows=repeated_rows)
-        return EmbeddingModel.from_pyannote(model, use_hf_token, repeated_rows)
+            return EmbeddingModel.from_state(model, repeated_rows=repeated_rows, **arch_options)
+        return EmbeddingModel.from_pyannote(model, use_hf_token, repeated_rows, **arch_options)
 
     def __call__(self, waveform: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = super().__call__(waveform, weights)

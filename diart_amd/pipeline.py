@@ -46,7 +46,8 @@ from . import _lib
 from .blocks.aggregation import BatchedOutputTail
 from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
-from .models import HipEcapaEmbedding, HipEmbedding, HipSbXvectorEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _as_rows
+from .models import (HipEcapaEmbedding, HipEmbedding, HipSbXvectorEmbedding, HipSegmentation, HipTitaNetEmbedding,
+                     HipWeSpeakerEmbedding, _as_rows)
 
 # sample formats of raw client audio (``dz_ring_push_rows_pcm``: DZ_PCM_F32 / DZ_PCM_S16, little-endian)
 PCM_F32, PCM_S16 = 0, 1
@@ -544,7 +545,8 @@ class StreamBatch(_DiarizationEngine):
     xvector_experiments = True
 
     def __init__(self, segmentation: HipSegmentation,
-                 embedding: Union[HipEmbedding, HipEcapaEmbedding, HipSbXvectorEmbedding], num_streams: int,
+                 embedding: Union[HipEmbedding, HipEcapaEmbedding, HipSbXvectorEmbedding, HipTitaNetEmbedding],
+                 num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  normalize_embedding_weights: bool = False,
@@ -573,7 +575,9 @@ class StreamBatch(_DiarizationEngine):
         embeddings are L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.  In that form
         ``lanes`` defaults to 2 — one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s) carves
         about 6.2 GB of device memory per lane — and ``emb_split`` must be 1.  A ``HipSbXvectorEmbedding``
-        (speechbrain/spkrec-xvect-voxceleb) runs in the same form (about 1.7 GB of arena per lane at 192 rows of 5 s)."""
+        (speechbrain/spkrec-xvect-voxceleb) runs in the same form (about 1.7 GB of arena per lane at 192 rows of 5 s),
+        and so does a ``HipTitaNetEmbedding`` (NeMo TitaNet-L: 2 lanes, about 5.9 GB of arena per lane at 192 rows of
+        5 s with "f16x3"; the handle computes its arena from the rows and the window)."""
         if isinstance(embedding, HipWeSpeakerEmbedding):
             raise ValueError("StreamBatch does not run the WeSpeaker ResNet34 embedding; it runs "
                              "HipEmbedding (pyannote/embedding), HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb) and "
@@ -581,7 +585,7 @@ class StreamBatch(_DiarizationEngine):
                              "Use WeSpeakerBatch (the N-stream engine of pyannote/wespeaker-voxceleb-resnet34-LM)")
         # the groups form (ECAPA, speechbrain x-vector): the whole embedding network behind the step's segmentation,
         # each stream's K rows with their own batch geometry, through the model's groups_launch
-        self.ecapa = isinstance(embedding, (HipEcapaEmbedding, HipSbXvectorEmbedding))
+        self.ecapa = isinstance(embedding, (HipEcapaEmbedding, HipSbXvectorEmbedding, HipTitaNetEmbedding))
         # sub-batches per network, each on its own HIP stream with its own scratch arena: the
         # x-projection GEMM of one sub-batch runs under the latency-bound recurrence of another
         self.seg_split = max(1, min(int(_lib.exp_env("DZ_SEG_SPLIT", "1") if seg_split is None else seg_split), num_streams))

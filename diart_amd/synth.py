@@ -305,3 +305,46 @@ def synth_wespeaker_state(seed: int = 4242, embed_dim: int = 256) -> Dict[str, t
     sd["resnet.seg_1.weight"] = _u(g, (embed_dim, 5120), math.sqrt(6.0 / 5120))
     sd["resnet.seg_1.bias"] = _u(g, (embed_dim,), 0.1)
     return sd
+
+
+def synth_titanet_state(seed: int = 9091) -> Dict[str, torch.Tensor]:
+    """Random-init weights of NeMo's TitaNet-L (titanet-large geometry: 80 mel bins, separable blocks of 1024 channels
+    with kernels 3 / 7 / 11 / 15 / 1, epilog 3072, attentive pooling, 192-d embedding), keyed like the ``.nemo``
+    archive's ``model_weights.ckpt`` (``weights.TITANET_KEYS``).  BatchNorm statistics are not the identity, so the
+    folding is exercised; the classifier (``decoder.final``) is not part of the embedding and is left out."""
+    from .weights import TITANET_BLOCKS, TITANET_KEYS, titanet_key
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def bn(prefix, n, mean=0.1):
+        sd[prefix + ".weight"] = 1.0 + 0.2 * _u(g, (n,), 1.0)
+        sd[prefix + ".bias"] = 0.1 * _u(g, (n,), 1.0)
+        sd[prefix + ".running_mean"] = mean * _u(g, (n,), 1.0)
+        sd[prefix + ".running_var"] = 0.5 + 0.8 * torch.rand((n,), generator=g)
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(1000)
+
+    for i, (reps, k, cin, cout, residual) in enumerate(TITANET_BLOCKS):
+        c = cin
+        for j in range(reps):
+            co = cout if (j == reps - 1 or i == 0) else cin
+            sd[titanet_key("dw", i, j)] = _u(g, (c, 1, k), math.sqrt(3.0 / k))
+            sd[titanet_key("pw", i, j)] = _u(g, (co, c, 1), math.sqrt(6.0 / c))
+            bn(titanet_key("bn", i, j), co)
+            c = co
+        sd[titanet_key("se", i, l=0)] = _u(g, (cout // 8, cout), math.sqrt(6.0 / cout))
+        sd[titanet_key("se", i, l=2)] = _u(g, (cout, cout // 8), math.sqrt(6.0 / (cout // 8)))
+        if residual:
+            sd[titanet_key("res", i)] = _u(g, (cout, cin, 1), 0.7 * math.sqrt(6.0 / cin))
+            bn(titanet_key("res_bn", i), cout)
+    a = TITANET_KEYS["att_conv"]
+    sd[a + ".weight"] = _u(g, (128, 9216, 1), 0.3 * math.sqrt(6.0 / 9216))
+    sd[a + ".bias"] = _u(g, (128,), 0.1)
+    bn(TITANET_KEYS["att_bn"], 128)
+    a = TITANET_KEYS["att_out"]
+    sd[a + ".weight"] = _u(g, (3072, 128, 1), 1.5 * math.sqrt(6.0 / 128))
+    sd[a + ".bias"] = _u(g, (3072,), 0.1)
+    bn(TITANET_KEYS["emb_bn"], 6144, mean=0.3)
+    a = TITANET_KEYS["emb_fc"]
+    sd[a + ".weight"] = _u(g, (192, 6144, 1), math.sqrt(6.0 / 6144))
+    sd[a + ".bias"] = _u(g, (192,), 0.1)
+    return sd

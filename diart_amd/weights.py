@@ -657,3 +657,168 @@ class PackedWeSpeaker:
         w.seg_w = pk.put(g("resnet.seg_1.weight"))
         w.seg_b = pk.put(g("resnet.seg_1.bias"))
         self.struct, self.pack = w, pk
+
+
+# --------------------------------------------------------------------------- #
+# NeMo TitaNet-L
+# --------------------------------------------------------------------------- #
+# (repeats, kernel, C_in, C_out, residual) of encoder.encoder.{0..4} (titanet-large.yaml: prolog, three mega blocks, epilog)
+TITANET_BLOCKS = ((1, 3, 80, 1024, False), (3, 7, 1024, 1024, True), (3, 11, 1024, 1024, True), (3, 15, 1024, 1024, True),
+                  (1, 1, 1024, 3072, False))
+TITANET_BN_EPS = 1e-3
+TITANET_MIN_NUM_SAMPLES = 257      # n_fft / 2 + 1: the first length the reflect-padded centred STFT accepts (two frames)
+TITANET_PAD_MODES = ("reflect", "constant")
+TITANET_FRAME_COUNTS = {"floor_plus_one": (0, 0), "padded": (256, 512)}     # -> (frame_pad, frame_nfft) of dz_ttn_weights
+TITANET_ATTENTION_ORDERS = ("relu_bn_tanh", "bn_relu_tanh")
+# THE key map of a NeMo EncDecSpeakerLabelModel checkpoint (model_weights.ckpt): every name the packer, the synthetic
+# weights and the loader's recognition use comes from here.  {i}: encoder block, {m}: index inside its ``mconv``
+# ModuleList — repeat j holds depthwise 5 j, pointwise 5 j + 1, BatchNorm 5 j + 2 (ReLU and Dropout at 5 j + 3, 5 j + 4
+# except after the last repeat), the squeeze-excitation follows the last BatchNorm.
+TITANET_KEYS = {
+    "dw": "encoder.encoder.{i}.mconv.{m}.conv.weight",
+    "pw": "encoder.encoder.{i}.mconv.{m}.conv.weight",
+    "bn": "encoder.encoder.{i}.mconv.{m}",
+    "se": "encoder.encoder.{i}.mconv.{m}.fc.{l}.weight",
+    "res": "encoder.encoder.{i}.res.0.0.conv.weight",
+    "res_bn": "encoder.encoder.{i}.res.0.1",
+    "att_conv": "decoder._pooling.attention_layer.0.conv_layer",
+    "att_bn": "decoder._pooling.attention_layer.0.bn",
+    "att_out": "decoder._pooling.attention_layer.2",
+    "emb_bn": "decoder.emb_layers.0.0",
+    "emb_fc": "decoder.emb_layers.0.1",
+}
+# what the loader recognises a TitaNet state by
+TITANET_MARKERS = (TITANET_KEYS["dw"].format(i=0, m=0), TITANET_KEYS["emb_fc"] + ".weight")
+
+
+def titanet_key(kind: str, i: int = 0, j: int = 0, l: int = 0) -> str:
+    """Checkpoint key (or prefix) of ``kind`` (``TITANET_KEYS``) for repeat ``j`` of encoder block ``i``."""
+    m = {"dw": 5 * j, "pw": 5 * j + 1, "bn": 5 * j + 2, "se": 5 * (TITANET_BLOCKS[i][0] - 1) + 3}.get(kind, 0)
+    return TITANET_KEYS[kind].format(i=i, m=m, l=l)
+
+
+def titanet_dft_matrices() -> torch.Tensor:
+    """The STFT of NeMo's front end as ONE real GEMM operand, (2 * 257, 400) f64: n_fft = 512 with a symmetric Hann
+    window of 400 samples padded centrally (56 zeros each side), so a frame only reads the 400 samples under the
+    window: rows 0 .. 256 = cos(2 pi k (n + 56) / 512) w[n], rows 257 .. 513 = sin(...) w[n]."""
+    n = torch.arange(400, dtype=torch.float64)
+    win = torch.hann_window(400, periodic=False, dtype=torch.float64)
+    k = torch.arange(257, dtype=torch.float64)[:, None]
+    ang = 2.0 * math.pi * k * (n[None, :] + 56.0) / 512.0
+    return torch.cat([torch.cos(ang) * win, torch.sin(ang) * win], 0)
+
+
+def titanet_mel_filterbank() -> torch.Tensor:
+    """librosa.filters.mel(sr=16000, n_fft=512, n_mels=80, fmin=0, fmax=8000, htk=False, norm="slaney") as (80, 257)
+    f64: the slaney mel scale (linear below 1 kHz, logarithmic above), triangles normalised to unit area."""
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
+    top = min_log_mel + math.log(8000.0 / min_log_hz) / logstep
+    mels = torch.linspace(0.0, top, 82, dtype=torch.float64)
+    hz = torch.where(mels < min_log_mel, mels * f_sp, min_log_hz * torch.exp(logstep * (mels - min_log_mel)))
+    freqs = torch.linspace(0.0, 8000.0, 257, dtype=torch.float64)
+    lower = (freqs[None, :] - hz[:-2, None]) / (hz[1:-1] - hz[:-2])[:, None]
+    upper = (hz[2:, None] - freqs[None, :]) / (hz[2:] - hz[1:-1])[:, None]
+    return torch.clamp(torch.minimum(lower, upper), min=0.0) * (2.0 / (hz[2:] - hz[:-2]))[:, None]
+
+
+def fold_pointwise_bn(w: torch.Tensor, bn: Dict[str, torch.Tensor], eps: float):
+    """Conv1d weight (Cout, Cin, 1) without bias + BatchNorm1d (eval) -> (matrix (Cout, Cin), bias (Cout,)): the
+    ``fold_conv_bn`` pattern for a pointwise 1-D convolution, in the dtype of ``w``."""
+    scale = bn["weight"] / torch.sqrt(bn["running_var"] + eps)
+    return w[:, :, 0] * scale[:, None], bn["bias"] - bn["running_mean"] * scale
+
+
+class PackedTitaNet:
+    """``dz_ttn_weights`` + the tensors behind it (NeMo ``EncDecSpeakerLabelModel`` keys, ``TITANET_KEYS``).
+
+    * the Hann window is folded into the DFT matrix (``titanet_dft_matrices``); the slaney mel bank stays exact f32;
+    * depthwise taps as ``[taps][Cpad]``; every BatchNorm (eval, eps 1e-3) folded into the pointwise convolution in
+      front of it (``fold_pointwise_bn``), as ``[Cout][Cpad]`` f32 and, for "f16x3", kb-major split-f16 planes;
+    * the squeeze-excitation's second Linear transposed; the attention conv split into the columns that see x and the
+      columns that see (mean | std); ``emb_layers.0.0`` (BatchNorm1d(6144), eps 1e-5) folded into ``emb_layers.0.1``.
+
+    (R) switches, DESIGN.md 4.12: ``pad_mode`` "reflect" | "constant", ``frame_count`` "floor_plus_one" | "padded",
+    ``min_num_samples``, ``attention_order`` "relu_bn_tanh" | "bn_relu_tanh"."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], device: torch.device, precision: str = "f32",
+                 pad_mode: str = "reflect", frame_count: str = "floor_plus_one",
+                 min_num_samples: int = TITANET_MIN_NUM_SAMPLES, attention_order: str = "relu_bn_tanh"):
+        assert precision in PRECISIONS, precision
+        if pad_mode not in TITANET_PAD_MODES:
+            raise ValueError(f"pad_mode={pad_mode!r}: expected one of {TITANET_PAD_MODES}")
+        if frame_count not in TITANET_FRAME_COUNTS:
+            raise ValueError(f"frame_count={frame_count!r}: expected one of {tuple(TITANET_FRAME_COUNTS)}")
+        if attention_order not in TITANET_ATTENTION_ORDERS:
+            raise ValueError(f"attention_order={attention_order!r}: expected one of {TITANET_ATTENTION_ORDERS}")
+        if int(min_num_samples) <= 200:
+            raise ValueError(f"min_num_samples={min_num_samples}: the centred STFT reads 200 samples back (> 200)")
+        split = precision == "f16x3"
+        pk = _Packed(device)
+        f = titanet_fold(sd, attention_order, torch.float64)       # (folded in float64, rounded once by put)
+        w = _lib.TtnWeights()
+        w.dft = pk.put(_pad2(titanet_dft_matrices().float(), 640, 416))
+        if split:
+            w.dft_split = pk.put_split(_pad2(titanet_dft_matrices().float(), 640, 416), "windowed DFT (TitaNet)")
+        w.mel = pk.put(_pad2(titanet_mel_filterbank().float(), 128, 288))
+
+        def layer(dst, name, m, b, kb):
+            dst.w, dst.b = pk.put(m), pk.put(b)
+            if split:
+                dst.wsplit = pk.put_split(m, name, kb=kb)
+
+        for i, (reps, k, cin, cout, residual) in enumerate(TITANET_BLOCKS):
+            blk, cpad = w.block[i], 96 if i == 0 else cin
+            for j in range(reps):
+                blk.rep[j].dw = pk.put(_pad2(f[f"dw{i}.{j}"], k, cpad))
+                layer(blk.rep[j].pw, titanet_key("pw", i, j), _pad2(f[f"pw{i}.{j}.w"], cout, cpad), f[f"pw{i}.{j}.b"], True)
+            blk.se1, blk.se2t = pk.put(f[f"se{i}.1"]), pk.put(f[f"se{i}.2t"])
+            if residual:
+                layer(blk.res, titanet_key("res", i), f[f"res{i}.w"], f[f"res{i}.b"], True)
+        layer(w.asp_tdnn, TITANET_KEYS["att_conv"], f["att.w"], f["att.b"], False)
+        w.asp_tdnn.s, w.asp_tdnn.h = pk.put(f["att.s"]), pk.put(f["att.h"])
+        w.asp_wms = pk.put(f["att.wms"])
+        layer(w.asp_conv, TITANET_KEYS["att_out"], f["att_out.w"], f["att_out.b"], False)
+        w.fc.w, w.fc.b = pk.put(f["fc.w"]), pk.put(f["fc.b"])
+        w.zeros = pk.put(torch.zeros(6144))
+        w.pad_reflect = int(pad_mode == "reflect")
+        w.frame_pad, w.frame_nfft = TITANET_FRAME_COUNTS[frame_count]
+        w.min_num_samples = int(min_num_samples)
+        self.struct, self.pack, self.folded = w, pk, f
+
+
+def titanet_fold(sd: Dict[str, torch.Tensor], attention_order: str = "relu_bn_tanh", dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """Every matrix ``PackedTitaNet`` hands to the kernels, unpadded, in ``dtype`` (the packer folds in float64): ``dw{i}.{j}`` (taps, C), ``pw{i}.{j}.w|b``, ``se{i}.1|2t``, ``res{i}.w|b``,
+    ``att.w|b|s|h|wms``, ``att_out.w|b``, ``fc.w|b``."""
+    g = lambda k: sd[k].detach().cpu().to(dtype)
+    bnd = lambda p: {n: g(f"{p}.{n}") for n in ("weight", "bias", "running_mean", "running_var")}
+    out: Dict[str, torch.Tensor] = {}
+    for i, (reps, k, cin, cout, residual) in enumerate(TITANET_BLOCKS):
+        for j in range(reps):
+            dw, pw = g(titanet_key("dw", i, j)), g(titanet_key("pw", i, j))
+            if tuple(dw.shape) != (cin, 1, k) or pw.shape[1:] != (cin, 1):
+                raise ValueError(f"{titanet_key('dw', i, j)}: shapes {tuple(dw.shape)} / {tuple(pw.shape)}, expected "
+                                 f"({cin}, 1, {k}) / (Cout, {cin}, 1) (titanet-large geometry)")
+            out[f"dw{i}.{j}"] = dw[:, 0, :].t().contiguous()
+            out[f"pw{i}.{j}.w"], out[f"pw{i}.{j}.b"] = fold_pointwise_bn(pw, bnd(titanet_key("bn", i, j)), TITANET_BN_EPS)
+        out[f"se{i}.1"] = g(titanet_key("se", i, l=0)).contiguous()
+        out[f"se{i}.2t"] = g(titanet_key("se", i, l=2)).t().contiguous()
+        if residual:
+            out[f"res{i}.w"], out[f"res{i}.b"] = fold_pointwise_bn(g(titanet_key("res", i)), bnd(titanet_key("res_bn", i)),
+                                                                 TITANET_BN_EPS)
+    aw, ab = g(TITANET_KEYS["att_conv"] + ".weight")[:, :, 0], g(TITANET_KEYS["att_conv"] + ".bias")      # (128, 9216)
+    bn = bnd(TITANET_KEYS["att_bn"])
+    scale = bn["weight"] / torch.sqrt(bn["running_var"] + BN_EPS)
+    shift = bn["bias"] - bn["running_mean"] * scale
+    if attention_order == "bn_relu_tanh":       # BatchNorm in front of the ReLU: folded into the convolution
+        aw, ab = aw * scale[:, None], ab * scale + shift
+        scale, shift = torch.ones_like(scale), torch.zeros_like(shift)
+    out["att.w"], out["att.wms"], out["att.b"] = aw[:, :3072].contiguous(), aw[:, 3072:].contiguous(), ab
+    out["att.s"], out["att.h"] = scale, shift
+    out["att_out.w"], out["att_out.b"] = g(TITANET_KEYS["att_out"] + ".weight")[:, :, 0].contiguous(), g(TITANET_KEYS["att_out"] + ".bias")
+    bn = bnd(TITANET_KEYS["emb_bn"])
+    scale = bn["weight"] / torch.sqrt(bn["running_var"] + BN_EPS)
+    shift = bn["bias"] - bn["running_mean"] * scale
+    fw, fb = g(TITANET_KEYS["emb_fc"] + ".weight")[:, :, 0], g(TITANET_KEYS["emb_fc"] + ".bias")
+    out["fc.w"], out["fc.b"] = (fw * scale[None, :]).contiguous(), fb + fw @ shift
+    return out

@@ -387,6 +387,70 @@ int dz_sbx_forward_groups(dz_sbx* m, const float* d_wave, long long wave_stride,
 int dz_sbx_peek(dz_sbx* m, int which, const void** d_ptr, long long* count, int* frames);
 int dz_sbx_destroy(dz_sbx* m);
 
+/* ---- NeMo TitaNet-L (nvidia/speakerverification_en_titanet_large) behind pyannote's PretrainedSpeakerEmbedding
+ * contract (its NeMo wrapper): waveform (N,1,S), masks (N,Fw) or NULL -> (N,192), not normalised.  The mask
+ * selects samples (nearest resampling, > 0.5); a row's valid frames come from its OWN kept count and every layer
+ * masks its input at them, so a row depends on its group only through the reflect padding at the group's longest
+ * row and through the "too short" rules: rows below min_num_samples are NaN, a group whose longest row is below it
+ * is all NaN.  Pre-emphasis 0.97 -> STFT (n_fft 512, Hann 400, hop 160, centred) -> 80 slaney mel bins ->
+ * log(x + 2^-24) -> per-feature mean / unbiased std over the valid frames -> 5 separable Jasper blocks with masked
+ * squeeze-excitation (depthwise conv: k_titanet.hip; pointwise conv with its BatchNorm folded: the wide GEMMs) ->
+ * attentive statistics pooling -> BatchNorm1d(6144) folded into Conv1d(6144, 192, 1).  DESIGN.md 4.12.          */
+typedef struct {
+    const float* dw;        /* depthwise taps [taps][Cpad], tap-major; Cpad = 96 for block 0 (80 mel bins), else 1024 */
+    dz_layer pw;            /* pointwise conv x BatchNorm scale: w [Cout][Cpad], b [Cout] = BatchNorm shift; wsplit:
+                               optional kb-major split-f16 planes of w (k_gemm_pre)                                   */
+} dz_ttn_sep;
+typedef struct {
+    dz_ttn_sep rep[3];      /* the block's repeats (1 for blocks 0 and 4, 3 for blocks 1 .. 3)                      */
+    const float* se1;       /* [C / 8][C]  squeeze: Linear(C, C / 8).weight                                         */
+    const float* se2t;      /* [C / 8][C]  excite: Linear(C / 8, C).weight TRANSPOSED                               */
+    dz_layer res;           /* blocks 1 .. 3: residual 1 x 1 conv x BatchNorm, as pw                                */
+} dz_ttn_block;
+typedef struct {
+    const float* dft;       /* [640][416] Hann(400)-windowed 512-point DFT of the 400 samples a frame's window
+                               covers: rows 0..256 cos, 257..513 sin                                                */
+    const void* dft_split;  /* optional split-f16 planes [2][640][416] of dft                                       */
+    const float* mel;       /* [128][288] slaney mel bank, [mel][bin], 80 mel rows x 257 bins, zero padded          */
+    dz_ttn_block block[5];
+    dz_layer asp_tdnn;      /* [128][3072]: the columns of the 9216-wide attention conv that multiply x; s / h =
+                               its BatchNorm (after the ReLU)                                                       */
+    const float* asp_wms;   /* [128][6144]: the columns that multiply (mean | std)                                  */
+    dz_layer asp_conv;      /* [3072][128]                                                                          */
+    dz_layer fc;            /* [192][6144] with BatchNorm1d(6144) folded in                                         */
+    const float* zeros;     /* [6144] zeros                                                                         */
+    int pad_reflect;        /* centred STFT padding: 1 reflect (at the group's longest row), 0 zeros                */
+    int frame_pad, frame_nfft;   /* valid frames of len samples = (len + 2 frame_pad - frame_nfft) / 160 + 1        */
+    int min_num_samples;    /* >= 201 (the reflect padding reads 200 samples back)                                  */
+} dz_ttn_weights;
+typedef struct dz_ttn dz_ttn;
+int dz_ttn_abi_size(void);                    /* sizeof(dz_ttn_weights) */
+int dz_ttn_frames_for(int num_samples);       /* 1 + S / 160: frames every buffer lays a row out with */
+int dz_ttn_create(dz_ctx* ctx, const dz_ttn_weights* w, int max_rows, int num_samples, dz_ttn** out);
+/* n_rows rows as one group (pyannote's call), d_masks (n_rows, mask_frames) or NULL -> d_out (n_rows, 192).  The
+ * geometry is derived on the device: no synchronisation.                                                        */
+int dz_ttn_forward(dz_ttn* m, const float* d_wave, long long wave_stride, const float* d_masks, int n_rows,
+                   int mask_frames, float* d_out, void* stream);
+/* n_groups groups of rows_per_group (K) rows as dz_ecapa_forward_groups: row g*K + k reads waveform row g and mask
+ * row g*K + k -> d_out (G*K, 192); normalize = 1 L2-normalises every row.  A group's rows are bit-identical to
+ * dz_ttn_forward on those K rows alone.  No synchronisation, no allocation.  G*K <= max_rows.                  */
+int dz_ttn_forward_groups(dz_ttn* m, const float* d_wave, long long wave_stride, const float* d_masks,
+                          int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                          void* stream);
+/* intermediates of the LAST forward, rows laid out with Tc = dz_ttn_frames_for(num_samples) frames (*frames); frames
+ * at or past a row's own count (buffer 9) are padding:  0 features (N,Tc,80)  1 .. 4 blocks 0 - 3 (N,Tc,1024)
+ * 5 block 4 (N,Tc,3072)  6 pooled statistics (N,6144)  7 kept-sample counts (N) int32, -(count + 1) for a row with
+ * a NaN / Inf sample  8 the length the row is padded at (its group's longest row) (N) int32  9 valid frames (N) int32 */
+int dz_ttn_peek(dz_ttn* m, int which, const void** d_ptr, long long* count, int* frames);
+int dz_ttn_destroy(dz_ttn* m);
+/* the depthwise convolution alone (parity tests): x [rows][T][ldx] f32 channels-last with C channels (C % 32 == 0,
+ * ldx % 4 == 0, ldx >= C), taps in {1, 3, 7, 11, 15} as [taps][C], frames[rows] valid frames per row (input frames
+ * at or past them read as zero), relu = 1 applies ReLU to the input first -> y [rows][T][C] f32 when d_planes is
+ * NULL, else the kb-major split-f16 planes [2][C / 32][rows T][32] of the same values.  d_x, d_taps, d_y and
+ * d_planes are 16-byte aligned (the kernel moves 16 bytes per lane).                                                */
+int dz_k_ttn_depthwise(dz_ctx* ctx, const float* d_x, int ldx, const float* d_taps, int taps, const int* d_frames,
+                       int rows, int T, int C, int relu, float* d_y, void* d_planes, void* stream);
+
 /* ---- band-limited resampling: torchaudio's sinc_interp_hann (lowpass_filter_width 6, rolloff 0.99), the filter
  * built in float64 and rounded to float32.  g = gcd(orig, new), o = orig / g, n = new / g, width =
  * ceil(6 o / (0.99 min(o, n))), T = 2 width + o taps per phase; output m = j n + i is sum_k h[i][k] x[j o - width + k]
