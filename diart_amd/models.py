@@ -459,10 +459,21 @@ class _HipGroupsEmbedding(_HipSpeakerEmbedding):
 
     def groups_launch(self, handle, wave_ptr: int, wave_stride: int, masks_ptr: int, G: int, K: int, mask_frames: int,
                       normalize: bool, out_ptr: int, stream_ptr: int) -> None:
-        """``<_c>_forward_groups`` on a handle of this model (``StreamBatch``'s lanes): raw device addresses,
+        """``<_c>_forward_groups`` on a handle of this model (``GroupsBatch``'s lanes): raw device addresses,
         masks (G,K,Fw) contiguous, out (G*K,dimension); no synchronisation."""
         _lib.check(self._fn("forward_groups")(handle, wave_ptr, wave_stride, masks_ptr, G, K, mask_frames,
                                               1 if normalize else 0, out_ptr, stream_ptr), f"{self._c}_forward_groups")
+
+    # the two-chain engine's hooks: the whole network consumes the masks, so nothing runs before the segmentation
+    def engine_rows(self, n: int, K: int) -> int:
+        return n * K
+
+    def early_launch(self, handle, wave_ptr: int, wave_stride: int, N: int, stream_ptr: int) -> None:
+        pass
+
+    def late_launch(self, handle, wave_ptr: int, wave_stride: int, weights_ptr: int, N: int, K: int, F: int,
+                    out_ptr: int, stream_ptr: int) -> None:
+        self.groups_launch(handle, wave_ptr, wave_stride, weights_ptr, N, K, F, True, out_ptr, stream_ptr)
 
 
 class HipEcapaEmbedding(_HipGroupsEmbedding):
@@ -584,6 +595,16 @@ class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
         (batch*K,256); the caller has ordered ``stream_ptr`` behind the trunk's stream.  No synchronisation."""
         _lib.check(_lib.load().dz_wsp_pool(handle, weights_ptr, batch, K, weight_frames, 1 if normalize else 0,
                                            out_ptr, stream_ptr), "dz_wsp_pool")
+
+    # the two-chain engine's hooks: the trunk runs beside the segmentation, only the pooling waits for it
+    def engine_rows(self, n: int, K: int) -> int:
+        return n
+
+    early_launch = trunk_launch
+
+    def late_launch(self, handle, wave_ptr: int, wave_stride: int, weights_ptr: int, N: int, K: int, F: int,
+                    out_ptr: int, stream_ptr: int) -> None:
+        self.pool_launch(handle, weights_ptr, N, K, F, True, out_ptr, stream_ptr)
 
 
 # --------------------------------------------------------------------------- #

@@ -21,15 +21,11 @@ independent, only the host-side clustering is sequential per stream):
                  CUs the LSTM leaves idle)  <--wait all--  dz_emb_pool -> D2H (pinned)
     host       : clustering + output tail of step t-1 (C++ threads, fp64) while the GPU runs step t
 
-With a ``HipEcapaEmbedding`` (BASELINE.json config 3) stream B has nothing to run before the masks exist: it
-waits for the step's segmentation and runs ``dz_ecapa_forward_groups`` over the K speaker rows of every
-stream, each stream's rows with their own batch geometry (what the stream's own pipeline computes), then the
-D2H copy.  Nothing in the launch waits for the GPU, so with two lanes the ECAPA network of step t runs under
-the segmentation of step t + 1.
-
 ``VadBatch`` is the segmentation-only form for ``VoiceActivityDetection``: no embedding, no clustering; the head kernel
-writes each stream's speech track and only that track reaches the host's output tails.  ``WeSpeakerBatch`` is the form
-for the WeSpeaker ResNet34 embedding, whose trunk is the long chain of the step: the segmentation runs under it.
+writes each stream's speech track and only that track reaches the host's output tails.  The other embeddings share the
+two-chain engine: ``WeSpeakerBatch`` for the WeSpeaker ResNet34 embedding, whose trunk is the long chain of the step (the
+segmentation runs under it), and ``GroupsBatch`` for the groups form (``HipEcapaEmbedding``, BASELINE.json config 3,
+``HipSbXvectorEmbedding``, ``HipTitaNetEmbedding``), which ``StreamBatch(seg, emb, ...)`` constructs for them.
 """
 from __future__ import annotations
 
@@ -37,7 +33,7 @@ import ctypes as C
 import os
 import time as _time
 from contextlib import contextmanager
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -46,8 +42,7 @@ from . import _lib
 from .blocks.aggregation import BatchedOutputTail
 from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
-from .models import (HipEcapaEmbedding, HipEmbedding, HipSbXvectorEmbedding, HipSegmentation, HipTitaNetEmbedding,
-                     HipWeSpeakerEmbedding, _as_rows)
+from .models import HipEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _HipGroupsEmbedding, _as_rows
 
 # sample formats of raw client audio (``dz_ring_push_rows_pcm``: DZ_PCM_F32 / DZ_PCM_S16, little-endian)
 PCM_F32, PCM_S16 = 0, 1
@@ -212,12 +207,11 @@ class _StepEngine:
 
     def _setup(self, segmentation: HipSegmentation, embedding, num_streams: int, device: Optional[torch.device], *,
                lanes: Optional[int], recurrence: Optional[str], inflight: Optional[int], wait: Optional[str],
-               warmup: Optional[int], lanes_follow_recurrence: bool, spare: int) -> None:
+               warmup: Optional[int], lanes_follow_recurrence: bool) -> None:
         """The engine under a subclass: argument checks first (nothing has touched a device when one refuses), then the
         models on the device, the engine choice and the bookkeeping state.  ``lanes_follow_recurrence``: a matrix-core
         recurrence at >= 64 streams gets ``THROUGHPUT_LANES`` lanes (an engine whose lanes are heavy in memory stays at
-        2 whatever the recurrence); ``spare``: the tickets such a many-lane engine keeps beyond its lanes (a two-lane
-        engine keeps one)."""
+        2 whatever the recurrence)."""
         from .config import setting
         if not self.xvector_experiments:
             self._refuse_xvector_experiments()
@@ -255,7 +249,7 @@ class _StepEngine:
         # lane's segmentation stream sat empty).
         # Round 6: a throughput engine keeps lanes + 2 (the second spare ticket covers the host's own launch + tail time of
         # a step: +3 % in the 20-step form, profiles/r06l_inflight_grid.json); the two-lane engines keep lanes + 1.
-        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + (spare if many else 1), int)))
+        self.max_inflight = max(self.depth, int(setting("inflight", inflight, self.depth + (2 if many else 1), int)))
         self.warmup_steps = max(0, int(setting("warmup", warmup, 10, int)))
         self._t = 0                                        # launches so far (lane selection)
         self._steps = np.zeros(self.n, dtype=np.int64)     # windows seen by each stream slot
@@ -544,9 +538,14 @@ class _DiarizationEngine(_StepEngine):
 class StreamBatch(_DiarizationEngine):
     xvector_experiments = True
 
-    def __init__(self, segmentation: HipSegmentation,
-                 embedding: Union[HipEmbedding, HipEcapaEmbedding, HipSbXvectorEmbedding, HipTitaNetEmbedding],
-                 num_streams: int,
+    def __new__(cls, segmentation=None, embedding=None, *args, **kwargs):
+        # The front door of the groups form too: its callers construct ``StreamBatch(seg, emb, n, ...)``.  What comes
+        # back then is a GroupsBatch, no StreamBatch, so Python does not call StreamBatch.__init__ on it.
+        if cls is StreamBatch and isinstance(embedding, _HipGroupsEmbedding):
+            return GroupsBatch(segmentation, embedding, *args, **kwargs)
+        return super().__new__(cls)
+
+    def __init__(self, segmentation: HipSegmentation, embedding: HipEmbedding, num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  normalize_embedding_weights: bool = False,
@@ -570,35 +569,21 @@ class StreamBatch(_DiarizationEngine):
         that no two kernels ever overlap and a kernel's bracketed duration is its alone-time (what
         ``rocprofv3 --kernel-trace --stats`` of the same run reports): ``bench.py``'s roofline pass.
 
-        ``embedding`` may be a ``HipEcapaEmbedding`` (config 3: powerset segmentation + ECAPA-TDNN): each stream's K
-        speaker rows are embedded with the batch geometry of those rows alone (``forward_groups``), and the
-        embeddings are L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.  In that form
-        ``lanes`` defaults to 2 — one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s) carves
-        about 6.2 GB of device memory per lane — and ``emb_split`` must be 1.  A ``HipSbXvectorEmbedding``
-        (speechbrain/spkrec-xvect-voxceleb) runs in the same form (about 1.7 GB of arena per lane at 192 rows of 5 s),
-        and so does a ``HipTitaNetEmbedding`` (NeMo TitaNet-L: 2 lanes, about 5.9 GB of arena per lane at 192 rows of
-        5 s with "f16x3"; the handle computes its arena from the rows and the window)."""
+        With a groups-form ``embedding`` (ECAPA-TDNN, speechbrain x-vector, TitaNet-L) this call constructs a
+        ``GroupsBatch``: see there."""
         if isinstance(embedding, HipWeSpeakerEmbedding):
             raise ValueError("StreamBatch does not run the WeSpeaker ResNet34 embedding; it runs "
                              "HipEmbedding (pyannote/embedding), HipEcapaEmbedding (speechbrain/spkrec-ecapa-voxceleb) and "
                              "HipSbXvectorEmbedding (speechbrain/spkrec-xvect-voxceleb). "
                              "Use WeSpeakerBatch (the N-stream engine of pyannote/wespeaker-voxceleb-resnet34-LM)")
-        # the groups form (ECAPA, speechbrain x-vector): the whole embedding network behind the step's segmentation,
-        # each stream's K rows with their own batch geometry, through the model's groups_launch
-        self.ecapa = isinstance(embedding, (HipEcapaEmbedding, HipSbXvectorEmbedding, HipTitaNetEmbedding))
         # sub-batches per network, each on its own HIP stream with its own scratch arena: the
         # x-projection GEMM of one sub-batch runs under the latency-bound recurrence of another
         self.seg_split = max(1, min(int(_lib.exp_env("DZ_SEG_SPLIT", "1") if seg_split is None else seg_split), num_streams))
         self.emb_split = max(1, min(int(_lib.exp_env("DZ_EMB_SPLIT", "1") if emb_split is None else emb_split), num_streams))
-        if self.ecapa and self.emb_split != 1:
-            raise ValueError(f"StreamBatch: emb_split={self.emb_split} with an ECAPA or speechbrain x-vector embedding "
-                             "(its forward is one launch sequence over every stream's rows: emb_split must be 1)")
         if depth is not None and lanes is not None and int(depth) != int(lanes):
             raise ValueError(f"StreamBatch: depth={depth} and lanes={lanes} name the same thing")
-        # (an ECAPA engine keeps 2 lanes whatever the recurrence: ~6 GB of arena per lane at 64 streams)
         self._setup(segmentation, embedding, num_streams, device, lanes=lanes if lanes is not None else depth,
-                    recurrence=recurrence, inflight=inflight, wait=wait, warmup=warmup,
-                    lanes_follow_recurrence=not self.ecapa, spare=2)
+                    recurrence=recurrence, inflight=inflight, wait=wait, warmup=warmup, lanes_follow_recurrence=True)
         self._setup_host(tau_active, rho_update, delta_new, gamma, beta, max_speakers, normalize_embedding_weights,
                          cluster_threads, tail, duration, step, latency)
         # HIP stream priorities (0 normal, -1 high).  The segmentation chain is the long dependent one
@@ -627,9 +612,6 @@ class StreamBatch(_DiarizationEngine):
         # recurrences of step t; on its own stream it runs under them and the lane's dependent chain is
         # the back half only (dz_seg_back: 4 recurrences, 3 projections, the MLP head).
         self.seg_front = _lib.exp_env("DZ_SEG_FRONT", "0") != "0"
-        if self.ecapa and (self.shared_emb or self.seg_front or self._ablate):
-            raise ValueError("StreamBatch: DZ_SHARED_EMB, DZ_SEG_FRONT and DZ_ABLATE are experiments of the x-vector "
-                             "engine; they have no meaning with an ECAPA or speechbrain x-vector embedding")
         pf = int(_lib.exp_env("DZ_PRIO_F", "0"))
         mk = lambda prio, k: [torch.cuda.Stream(self.device, priority=prio) for _ in range(k)]
         shared_b = mk(pb, self.emb_split) if self.shared_emb else None
@@ -684,10 +666,7 @@ class StreamBatch(_DiarizationEngine):
             sa, sb = self._ranges(self.n, self.seg_split), self._ranges(self.n, self.emb_split)
             hs = [self.seg._create(S, max(1, -(-self.n // self.seg_split)), throughput=self.throughput,
                                    recurrence=None if self.throughput else self.recurrence) for _ in sa]
-            if self.ecapa:      # one handle over the K speaker rows of every stream (dz_ecapa_forward_groups)
-                he = [self.emb._create(S, self.n * self.seg.num_speakers)]
-            else:
-                he = [self.emb._create(S, max(1, -(-self.n // self.emb_split))) for _ in sb]
+            he = [self.emb._create(S, max(1, -(-self.n // self.emb_split))) for _ in sb]
             got = self._sub[(S, lane)] = (hs, he, sa, sb)
         return got
 
@@ -765,7 +744,7 @@ class StreamBatch(_DiarizationEngine):
                 marks.append(("seg_forward_osp", _time.perf_counter()))
         for (i0, i1), h, b, ev in zip(sb, hembs, lane["b"], slot["ev_frames"]):
             b.wait_event(slot["ev_conv0"] if pair else slot["ev_in"])
-            if i1 > i0 and self._ablate != "noemb" and not self.ecapa:   # (ECAPA: all of it after the segmentation)
+            if i1 > i0 and self._ablate != "noemb":
                 if stats is not None:
                     _lib.check(lib.dz_emb_use_wave_stats(h, stats[i0:].data_ptr()), "dz_emb_use_wave_stats")
                 _lib.check(lib.dz_emb_frames(h, base + i0 * stride * esz, stride, i1 - i0, b.cuda_stream),
@@ -776,15 +755,11 @@ class StreamBatch(_DiarizationEngine):
         slot["rows"], slot["slots"] = N, None
         slot["keep"] = keep                              # keep the view alive until the GPU is done
         slot["pool"] = (lane, hembs, sa, sb, N, K, F)     # what _enqueue_pool needs
-        slot["wave"] = (base, stride)                    # (ECAPA reads the windows behind the segmentation)
-        readers = list(lane["a"]) + list(lane["b"]) + list(front or [])
-        if ring is not None and not self.ecapa:          # pushes `slack` steps from now wait for these
-            ring._read_by(readers)
+        if ring is not None:                            # pushes `slack` steps from now wait for these
+            ring._read_by(list(lane["a"]) + list(lane["b"]) + list(front or []))
         self._pending.append(slot)
         while len(self._pending) > self.lag:
             self._enqueue_pool(self._pending.pop(0))
-        if ring is not None and self.ecapa:              # (lag 0: its forward is enqueued by now)
-            ring._read_by(readers)
         if marks is not None:
             marks.append(("pool", _time.perf_counter()))
             if marks[-1][1] - marks[0][1] > 2e-3:           # a launch that took more than 2 ms: where
@@ -804,11 +779,6 @@ class StreamBatch(_DiarizationEngine):
             for (j0, j1), ev in zip(sa, slot["ev_seg"]):
                 if j0 < i1 and i0 < j1:
                     b.wait_event(ev)
-            if self.ecapa:      # the whole network, each stream's K rows with their own geometry, normalised
-                base, stride = slot["wave"]
-                self.emb.groups_launch(h, base + i0 * stride * 4, stride, slot["w"][i0:i1].data_ptr(), i1 - i0, K, F,
-                                       True, slot["emb"][i0:i1].data_ptr(), b.cuda_stream)
-                continue
             if self._ablate == "noemb":
                 if not slot.get("_filled"):       # something the clustering accepts
                     with torch.cuda.stream(b):
@@ -880,7 +850,7 @@ class VadBatch(_StepEngine):
         # the engine StreamBatch would pick for these streams: a throughput engine at >= 64 streams in the default
         # precision runs the matrix-core recurrence on THROUGHPUT_LANES lanes
         self._setup(segmentation, None, num_streams, device, lanes=lanes, recurrence=recurrence, inflight=inflight,
-                    wait=wait, warmup=warmup, lanes_follow_recurrence=True, spare=2)
+                    wait=wait, warmup=warmup, lanes_follow_recurrence=True)
         self.tau_active, self.host_threads = float(tau_active), max(1, int(host_threads))
         # the segmentation chain is the whole step: its streams get the high priority, as in StreamBatch
         pa = int(_lib.exp_env("DZ_PRIO_A", "-1"))
@@ -963,59 +933,49 @@ class VadBatch(_StepEngine):
         return [BatchedOutputTail.annotation(turns[i], int(nturns[i]), label="speech") for i in range(self.n)]
 
 
-class WeSpeakerBatch(_DiarizationEngine):
-    """``SpeakerDiarization`` of N concurrent streams with the WeSpeaker ResNet34 embedding
-    (pyannote/wespeaker-voxceleb-resnet34-LM, the embedding of pyannote.audio 3.1's pipeline): the sibling of
-    ``StreamBatch`` for the one model whose embedding trunk, not the segmentation, is the long chain of a step
-    (about 10.7 ms of fbank + ResNet34 per 64 windows against a 0.7 ms segmentation).  Per stream it produces what
-    that stream's own ``SpeakerDiarization`` produces; the public surface is ``StreamBatch``'s.
-
-    GPU schedule per step, on the step's lane (two HIP streams per lane):
+class _TwoChainEngine(_DiarizationEngine):
+    """The engine of the embeddings that run as two chains per step, two HIP streams per lane:
 
         stream A : dz_wave_stats -> dz_seg_forward_osp (scores + OSP weights)            -- ev_seg
-        stream B : dz_wsp_trunk (reads the same windows, in place from the ring)   <wait ev_seg>  dz_wsp_pool(normalize=1)
-                   -> dz_results_to_host (scores + embeddings) -> `done`
+        stream B : the model's early launch (reads the windows)   <wait ev_seg>   its late launch (consumes the OSP
+                   weights, normalised) -> dz_results_to_host (scores + embeddings) -> `done`
         host     : clustering + output tail of step t-1 (C++ workers, fp64) while the GPU runs step t
 
-    The trunk does not depend on the segmentation, so the segmentation runs under it and only the pooling waits.  The
-    embeddings are bit for bit those of ``HipWeSpeakerEmbedding.forward_multi`` on the same windows and weights (a
-    row's result does not depend on the batch it is in).
+    The model says what the two launches are and how many rows its handle holds (``engine_rows``, ``early_launch``,
+    ``late_launch``).  Two lanes whatever the recurrence (an embedding handle per lane is gigabytes of arena; 4 HIP
+    streams are what the runtime's 4 hardware queues carry), ``inflight`` = lanes + 1; the other engine parameters are
+    ``StreamBatch``'s.  No sub-batches and none of the x-vector engine's experiment switches."""
 
-    ``lanes`` defaults to 2 for every stream count: one ``dz_wsp`` handle of ``num_streams`` rows per lane holds about
-    33 MB of activations per row at 5 s (four layer-1 sized buffers of 5.1 MB, the layer outputs, the fbank), i.e.
-    about 2.1 GB per lane at 64 streams and 8.4 GB at 256 (``tools/wespeaker_streams.py`` reports the measured
-    figure).  Two lanes are 4 HIP streams, what the runtime's 4 hardware queues carry.  ``recurrence``: what
-    ``StreamBatch`` picks (the matrix-core kernel at >= 64 streams in the default precision, else the model's own);
-    ``inflight`` defaults to lanes + 1; ``wait`` and ``warmup`` as in ``StreamBatch``; ``DZ_ENGINE`` overrides them.
-    No sub-batches, no serial form and none of the x-vector engine's experiment switches."""
-
-    def __init__(self, segmentation: HipSegmentation, embedding: HipWeSpeakerEmbedding, num_streams: int,
+    def __init__(self, segmentation: HipSegmentation, embedding, num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  normalize_embedding_weights: bool = False,
                  device: Optional[torch.device] = None, cluster_threads: int = 8,
+                 seg_split: Optional[int] = None, emb_split: Optional[int] = None,
                  tail: bool = False, duration: float = 5.0, step: float = 0.5,
-                 latency: Optional[float] = None, *, lanes: Optional[int] = None,
+                 latency: Optional[float] = None, depth: Optional[int] = None, *, lanes: Optional[int] = None,
                  recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
-                 warmup: Optional[int] = None):
-        if not isinstance(embedding, HipWeSpeakerEmbedding):
-            raise ValueError(f"WeSpeakerBatch runs the WeSpeaker ResNet34 embedding (HipWeSpeakerEmbedding), not "
-                             f"{type(embedding).__name__}: use StreamBatch for HipEmbedding, HipEcapaEmbedding and "
-                             "HipSbXvectorEmbedding")
-        if not isinstance(segmentation, HipSegmentation):
-            raise ValueError(f"WeSpeakerBatch: segmentation must be a HipSegmentation, got {type(segmentation).__name__}")
-        if int(num_streams) < 1:
-            raise ValueError(f"WeSpeakerBatch: num_streams={num_streams}")
-        self._timing(duration, step, latency)
+                 warmup: Optional[int] = None, serial: bool = False):
+        who = type(self).__name__
+        for name, split in (("seg_split", seg_split), ("emb_split", emb_split)):
+            if split not in (None, 1):
+                raise ValueError(f"{who}: {name}={split} (the embedding's forward is one launch sequence over every "
+                                 f"stream's rows: {name} must be 1)")
+        if depth is not None and lanes is not None and int(depth) != int(lanes):
+            raise ValueError(f"{who}: depth={depth} and lanes={lanes} name the same thing")
         # the recurrence StreamBatch would pick for these streams; the lanes stay at 2 (memory, queues)
-        self._setup(segmentation, embedding, num_streams, device, lanes=lanes, recurrence=recurrence, inflight=inflight,
-                    wait=wait, warmup=warmup, lanes_follow_recurrence=False, spare=1)
+        self._setup(segmentation, embedding, num_streams, device, lanes=lanes if lanes is not None else depth,
+                    recurrence=recurrence, inflight=inflight, wait=wait, warmup=warmup, lanes_follow_recurrence=False)
         self._setup_host(tau_active, rho_update, delta_new, gamma, beta, max_speakers, normalize_embedding_weights,
-                         cluster_threads, tail, self.duration, self.step, self.latency)
-        # The segmentation is the short chain here, but the step's last kernels (pooling, seg_1) wait for it: its stream
-        # keeps StreamBatch's high priority so that it is never queued behind the trunk's convolutions of both lanes.
+                         cluster_threads, tail, duration, step, latency)
+        if serial and self.depth != 1:
+            raise ValueError(f"{who}(serial=True) is one lane with one stream: lanes=1")
+        # the step's last kernels wait for the segmentation: its stream keeps StreamBatch's high priority, so that it is
+        # never queued behind the embedding networks of both lanes
         self.lanes = [dict(a=torch.cuda.Stream(self.device, priority=-1), b=torch.cuda.Stream(self.device, priority=0))
                       for _ in range(self.depth)]
+        if serial:                                      # the measurement form: no two kernels ever overlap
+            self.lanes[0]["b"] = self.lanes[0]["a"]
         self.num_hip_streams = 2 * self.depth
 
     # ------------------------------------------------------------------ GPU half
@@ -1025,7 +985,7 @@ class WeSpeakerBatch(_DiarizationEngine):
             hs = self.seg._create(S, self.n, throughput=self.throughput,
                                   recurrence=None if self.throughput else self.recurrence)
             try:
-                he = self.emb._create(S, self.n)
+                he = self.emb._create(S, self.emb.engine_rows(self.n, self.seg.num_speakers))
             except Exception:
                 self.seg._destroy(hs)
                 raise
@@ -1060,11 +1020,11 @@ class WeSpeakerBatch(_DiarizationEngine):
         _lib.check(lib.dz_seg_forward_osp(hseg, base, stride, N, slot["seg"].data_ptr(), self.gamma, self.beta,
                                           int(self.norm_w), slot["w"].data_ptr(), a.cuda_stream), "dz_seg_forward_osp")
         slot["ev_seg"].record(a)
-        # the lane's handle carries one trunk at a time: stream B orders this trunk behind the pooling of the lane's
-        # previous step
-        self.emb.trunk_launch(hemb, base, stride, N, b.cuda_stream)
+        # the lane's handle carries one forward at a time: stream B orders this step's early half behind the late half
+        # of the lane's previous step
+        self.emb.early_launch(hemb, base, stride, N, b.cuda_stream)
         b.wait_event(slot["ev_seg"])
-        self.emb.pool_launch(hemb, slot["w"].data_ptr(), N, K, F, True, slot["emb"].data_ptr(), b.cuda_stream)
+        self.emb.late_launch(hemb, base, stride, slot["w"].data_ptr(), N, K, F, slot["emb"].data_ptr(), b.cuda_stream)
         _lib.check(lib.dz_results_to_host(self._ctx, slot["seg"].data_ptr(), slot["seg_h"].data_ptr(), N * F * K,
                                           slot["emb"].data_ptr(), slot["emb_h"].data_ptr(), N * K * D,
                                           b.cuda_stream), "dz_results_to_host")
@@ -1074,6 +1034,63 @@ class WeSpeakerBatch(_DiarizationEngine):
         slot["rows"], slot["slots"], slot["keep"] = N, None, keep
         self._t += 1
         return slot
+
+
+class WeSpeakerBatch(_TwoChainEngine):
+    """``SpeakerDiarization`` of N concurrent streams with the WeSpeaker ResNet34 embedding
+    (pyannote/wespeaker-voxceleb-resnet34-LM, the embedding of pyannote.audio 3.1's pipeline): the sibling of
+    ``StreamBatch`` for the one model whose embedding trunk, not the segmentation, is the long chain of a step
+    (about 10.7 ms of fbank + ResNet34 per 64 windows against a 0.7 ms segmentation).  Per stream it produces what
+    that stream's own ``SpeakerDiarization`` produces; the public surface is ``StreamBatch``'s.
+
+    The two-chain schedule with ``dz_wsp_trunk`` (reads the windows, in place from the ring) as the early launch and
+    ``dz_wsp_pool(normalize=1)`` as the late one: the trunk does not depend on the segmentation, so the segmentation
+    runs under it and only the pooling waits.  The embeddings are bit for bit those of
+    ``HipWeSpeakerEmbedding.forward_multi`` on the same windows and weights (a row's result does not depend on the
+    batch it is in).
+
+    ``lanes`` defaults to 2 for every stream count: one ``dz_wsp`` handle of ``num_streams`` rows per lane holds about
+    33 MB of activations per row at 5 s (four layer-1 sized buffers of 5.1 MB, the layer outputs, the fbank), i.e.
+    about 2.1 GB per lane at 64 streams and 8.4 GB at 256 (``tools/wespeaker_streams.py`` reports the measured
+    figure).  No sub-batches and no serial form; a latency outside [step, duration] is refused."""
+
+    def __init__(self, segmentation: HipSegmentation, embedding: HipWeSpeakerEmbedding, num_streams: int,
+                 tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
+                 gamma: float = 3, beta: float = 10, max_speakers: int = 20,
+                 normalize_embedding_weights: bool = False,
+                 device: Optional[torch.device] = None, cluster_threads: int = 8,
+                 tail: bool = False, duration: float = 5.0, step: float = 0.5,
+                 latency: Optional[float] = None, *, lanes: Optional[int] = None,
+                 recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
+                 warmup: Optional[int] = None):
+        if not isinstance(embedding, HipWeSpeakerEmbedding):
+            raise ValueError(f"WeSpeakerBatch runs the WeSpeaker ResNet34 embedding (HipWeSpeakerEmbedding), not "
+                             f"{type(embedding).__name__}: use StreamBatch for HipEmbedding, HipEcapaEmbedding and "
+                             "HipSbXvectorEmbedding")
+        if not isinstance(segmentation, HipSegmentation):
+            raise ValueError(f"WeSpeakerBatch: segmentation must be a HipSegmentation, got {type(segmentation).__name__}")
+        if int(num_streams) < 1:
+            raise ValueError(f"WeSpeakerBatch: num_streams={num_streams}")
+        self._timing(duration, step, latency)
+        super().__init__(segmentation, embedding, num_streams, tau_active, rho_update, delta_new, gamma, beta,
+                         max_speakers, normalize_embedding_weights, device, cluster_threads, tail=tail,
+                         duration=self.duration, step=self.step, latency=self.latency, lanes=lanes,
+                         recurrence=recurrence, inflight=inflight, wait=wait, warmup=warmup)
+
+
+class GroupsBatch(_TwoChainEngine):
+    """``SpeakerDiarization`` of N concurrent streams with a groups-form embedding (``HipEcapaEmbedding``: config 3,
+    powerset segmentation + ECAPA-TDNN; ``HipSbXvectorEmbedding``; ``HipTitaNetEmbedding``): what ``StreamBatch(seg, emb,
+    n, ...)`` constructs for them, with ``StreamBatch``'s arguments.  The two-chain schedule with no early launch and
+    the model's ``groups_launch`` as the late one: each stream's K speaker rows are embedded with the batch geometry of
+    those rows alone (``forward_groups``) and L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.
+
+    ``lanes`` (= ``depth``) defaults to 2: one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s)
+    carves about 6.2 GB of device memory per lane, a speechbrain x-vector handle about 1.7 GB, a TitaNet-L handle about
+    5.9 GB with "f16x3" (the handle computes its arena from the rows and the window).  ``seg_split`` and ``emb_split``
+    must be None or 1; ``serial``: the measurement form, one lane (``lanes=1``) whose two chains share one HIP stream.
+    The experiments build's ``DZ_PRIO_A``, ``DZ_PRIO_B``, ``DZ_SHARED_STATS``, ``DZ_SEG_SPLIT`` and ``DZ_EMB_SPLIT`` do
+    not reach this engine."""
 
 
 class FileBatch:

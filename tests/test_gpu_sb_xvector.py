@@ -10,6 +10,7 @@ import torch
 
 import sb_xvector_ref as R
 from diart_amd import models as M
+from diart_amd.pipeline import GroupsBatch
 from diart_amd.synth import synth_sb_xvector_state, synth_segmentation_state, synth_streams
 
 pytestmark = pytest.mark.gpu
@@ -336,7 +337,7 @@ def test_engine_equals_per_stream_pipelines(gpu, states, precision):
     audio = synth_streams(n, (W + HOP * steps) / 16000.0, seed0=960)
     d_audio = torch.from_numpy(audio).to(gpu)
     pipe = engine(states, n, precision, gpu, tail=True)
-    assert pipe.depth == 2 and pipe.ecapa
+    assert pipe.depth == 2 and isinstance(pipe, GroupsBatch)
     refs = [blocks_pipeline(states, precision, gpu) for _ in range(n)]
     worst = 0.0
     for t in range(steps):
@@ -364,6 +365,29 @@ def test_engine_equals_per_stream_pipelines(gpu, states, precision):
         engine(states, n, precision, gpu, emb_split=2)
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_engine_adds_nothing_to_the_model_s_own_forward(gpu, states, precision):
+    """The groups-form counterpart of WeSpeaker's halves-equal-the-whole test: a ``GroupsBatch`` of 3 streams, two full
+    steps (one on each lane) and one ``slots=[2, 0]`` step (fewer rows than streams, on the first lane again).  After
+    ``finish`` the step's device embeddings equal the model's own ``forward_groups`` on the same windows and the step's
+    own OSP weights bit for bit, NaN rows included: the engine's schedule adds nothing to the forward."""
+    n = 3
+    seg_sd, emb_sd = states
+    audio = torch.from_numpy(synth_streams(n, (W + 3 * HOP) / 16000.0, seed0=965)).to(gpu)
+    pipe = GroupsBatch(M.HipSegmentation(seg_sd, max_batch=n, powerset=True, precision=precision),
+                       M.HipSbXvectorEmbedding(emb_sd, precision=precision), n, tau_active=0.5,
+                       normalize_embedding_weights=True, device=gpu)
+    assert pipe.depth == 2
+    for t, slots in enumerate((None, None, [2, 0])):
+        windows = audio[:, t * HOP:t * HOP + W] if slots is None else audio[slots, t * HOP:t * HOP + W]
+        ticket = pipe.launch(windows, slots=slots)
+        pipe.finish(ticket)
+        rows = len(windows)
+        want = pipe.emb.forward_groups(windows[:, None], ticket["w"][:rows], normalize=True)
+        assert want.shape == (rows, 3, 512)
+        assert same_nan(ticket["emb"][:rows], want), (precision, t, slots)
+
+
 def test_stream_server_equals_dedicated_pipelines(gpu, states):
     from diart_amd.inference import StreamingInference
     from diart_amd.serve import StreamServer
@@ -373,7 +397,7 @@ def test_stream_server_equals_dedicated_pipelines(gpu, states):
     srv = StreamServer(M.HipSegmentation(seg_sd, max_batch=2, powerset=True),
                        M.HipSbXvectorEmbedding(emb_sd), max_streams=2, tau_active=0.5,
                        normalize_embedding_weights=True, device=gpu)
-    assert srv.batch.ecapa
+    assert isinstance(srv.batch, GroupsBatch)
     rng = np.random.default_rng(6)
     pos = {k: 0 for k in audio}
     join_at = {"ana": 0, "ben": 2}

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from diart_amd import models as M
-from diart_amd.pipeline import StreamBatch
+from diart_amd.pipeline import GroupsBatch, StreamBatch
 from diart_amd.synth import synth_ecapa_state, synth_segmentation_state, synth_streams
 
 pytestmark = pytest.mark.gpu
@@ -62,7 +62,7 @@ def test_engine_equals_per_stream_pipelines(gpu, states, precision):
     audio = synth_streams(n, (W + HOP * steps) / 16000.0, seed0=950)
     d_audio = torch.from_numpy(audio).to(gpu)
     pipe = engine(states, n, precision, gpu, tail=True)
-    assert pipe.depth == 2 and pipe.ecapa
+    assert pipe.depth == 2 and isinstance(pipe, GroupsBatch)
     refs = [config3(states, precision, gpu) for _ in range(n)]
     nan_seen = 0
     for t in range(steps):
@@ -100,7 +100,7 @@ def test_stream_server_equals_dedicated_pipelines(gpu, states, precision):
     srv = StreamServer(M.HipSegmentation(seg_sd, max_batch=3, powerset=True, precision=precision),
                        M.HipEcapaEmbedding(emb_sd, precision=precision), max_streams=3, tau_active=0.5,
                        normalize_embedding_weights=True, device=gpu)
-    assert srv.batch.ecapa
+    assert isinstance(srv.batch, GroupsBatch)
     rng = np.random.default_rng(5)
     pos = {k: 0 for k in audio}
     join_at = {"ana": 0, "ben": 2, "cy": 5}
