@@ -1,9 +1,7 @@
 // dz_ecapa_*: launch sequence of the ECAPA-TDNN embedding (include/diart_amd.h).  Host code.
-#include "dz_common.h"
+#include "dz_embed.h"
 
 #include <math.h>
-#include <string.h>
-#include <new>
 #include <vector>
 
 namespace {
@@ -97,81 +95,32 @@ extern "C" int dz_ecapa_frames_for(int num_samples) { return num_samples > 0 ? 1
 
 extern "C" int dz_ecapa_create(dz_ctx* ctx, const dz_ecapa_weights* w, int max_rows, int num_samples,
                                dz_ecapa** out) {
-    DZ_REQUIRE(ctx && w && out, "dz_ecapa_create: NULL argument");
-    DZ_REQUIRE(max_rows >= 1 && num_samples >= MIN_NUM_SAMPLES, "dz_ecapa_create: max_rows %d, %d samples",
-               max_rows, num_samples);
-    DZ_HIP(hipSetDevice(ctx->device));
-    dz_ecapa* e = new (std::nothrow) dz_ecapa;
-    DZ_REQUIRE(e != nullptr, "dz_ecapa_create: out of memory");
-    memset(e, 0, sizeof(*e));
-    e->ctx = ctx; e->w = *w; e->Nm = max_rows;
-    e->geo.init(num_samples, MIN_NUM_SAMPLES);
-    int rc = dz_arena_alloc("dz_ecapa_create", e, ecapa_carve);
-    if (!rc) {
-        const hipError_t err = hipHostMalloc((void**)&e->h_pin, sizeof(int) * 4 * max_rows, hipHostMallocDefault);
-        if (err != hipSuccess) {
-            e->h_pin = nullptr;
-            dz_set_error("dz_ecapa_create: hipHostMalloc failed: %s", hipGetErrorString(err));
-            rc = 1;
-        }
-    }
-    if (rc) {
-        dz_ecapa_destroy(e);
+    dz_ecapa* e = nullptr;
+    if (int rc = dz_handle_create("dz_ecapa_create", ctx, w, max_rows, num_samples, MIN_NUM_SAMPLES, ecapa_carve, &e))
         return rc;
+    const hipError_t err = hipHostMalloc((void**)&e->h_pin, sizeof(int) * 4 * max_rows, hipHostMallocDefault);
+    if (err != hipSuccess) {
+        e->h_pin = nullptr;
+        dz_set_error("dz_ecapa_create: hipHostMalloc failed: %s", hipGetErrorString(err));
+        dz_ecapa_destroy(e);
+        return 1;
     }
     *out = e;
     return 0;
 }
 
 extern "C" int dz_ecapa_destroy(dz_ecapa* e) {
-    if (e) {
-        if (e->arena) (void)hipFree(e->arena);
-        if (e->h_pin) (void)hipHostFree(e->h_pin);
-        delete e;
-    }
-    return 0;
+    if (e && e->h_pin) (void)hipHostFree(e->h_pin);
+    return dz_handle_destroy(e);
 }
 
-// one convgemm launch; X is [B][Tin][ldx] with Cin channels used, Y [B][Tin or flat][ldy]
-static int gemm(int tag, int rows_n, hipStream_t st, const float* X, int ldx, long long xbs, int B, int T, int Cin, int taps,
-                int dil, int pad, const dz_layer& L, const float* bias, int Kpad, int Npad, int Nstore,
-                float* Y, int ldy, long long ybs, int epi, const float* X2 = nullptr,
-                const float* rowbias = nullptr, int ksplit = 0, long long ysplit = 0, void* Yplanes = nullptr,
-                long long yplane = 0, const int* Tdev = nullptr) {
-    DzConvGemm p;
-    memset(&p, 0, sizeof(p));
-    p.X = X; p.W = L.w; p.bias = bias ? bias : L.b; p.e0 = L.s; p.e1 = L.h; p.Y = Y;
-    p.B = B; p.Tin = T; p.Tout = pad ? T : T - (taps - 1) * dil; p.Tstore = p.Tout;
-    p.Cin = Cin; p.taps = taps; p.dil = dil; p.pad = pad; p.K = taps * Cin; p.Kpad = Kpad;
-    p.Npad = Npad; p.Nstore = Nstore; p.ldx = ldx; p.ldy = ldy; p.xbs = xbs; p.ybs = ybs;
-    p.epi = epi; p.X2 = X2; p.rowbias = rowbias; p.ksplit = ksplit; p.ysplit = ysplit; p.Tdev = Tdev;
-    // every layer that comes with split-f16 planes (default precision: block 0, the wide 1x1 layers, the
-    // Res2Net convolutions with their reflect padding and second input, the attention's output
-    // convolution, the DFT) runs the same contraction on the f16 matrix cores (k_gemm_split.hip)
-    if (L.wsplit && (epi == DZ_EPI_RELU_BN || epi == DZ_EPI_BIAS || epi == DZ_EPI_RELU_BN_TANH) && ksplit <= 1 && Cin % 8 == 0) {
-        p.Wsplit = L.wsplit;
-        p.Npad = (Npad + 127) / 128 * 128;       // (the DFT's planes are packed with 512 rows)
-        p.Ysplit = Yplanes;                      // the next wide layer's input, written by this epilogue
-        p.yplane = yplane;
-        DzProfScope ps(tag, rows_n);
-        return dz_launch_gemm_split(p, st);
-    }
-    DZ_REQUIRE(Yplanes == nullptr, "ecapa: plane output asked of a layer that is not on the split-f16 path");
-    DzProfScope ps(tag, rows_n);
-    return dz_launch_convgemm(p, st);
-}
-
-// a wide 1 x 1 layer with BOTH operands pre-split (k_gemm_pre.hip): rows x Cin -> rows x Npad, ReLU -> BN, f32 out.
-// Xplanes = the k-block of the layer's first input column inside planes of `pcols` columns (hi | lo, xplane apart)
-static int gemm_pre(int tag, int rows_n, hipStream_t st, const void* Xplanes, long long xplane, int pcols, long long rows,
-                    int Cin, const dz_layer& L, int Npad, float* Y) {
-    DzConvGemm p;
-    memset(&p, 0, sizeof(p));
-    p.Xsplit = Xplanes; p.xplane = xplane; p.ldx = pcols; p.Wsplit = L.wsplit; p.bias = L.b; p.e0 = L.s; p.e1 = L.h;
-    p.Y = Y; p.B = 1; p.Tin = p.Tout = p.Tstore = (int)rows; p.Cin = Cin; p.taps = 1; p.dil = 1; p.K = p.Kpad = Cin;
-    p.Npad = p.Nstore = Npad; p.ldy = Npad; p.epi = DZ_EPI_RELU_BN;
-    DzProfScope ps(tag, rows_n);
-    return dz_launch_gemm_pre(p, st);
+// a wide 1 x 1 layer (ReLU -> BN) over NT rows: both operands pre-split (k_gemm_pre.hip) when the producer wrote
+// `planes` — the k-block of the layer's first input column inside kb-major planes of ldx columns (hi | lo, xplane
+// apart) — else over the f32 rows X
+static int wide(const dz_layer& L, const float* X, int ldx, const void* planes, long long xplane, int N, long long NT,
+                int C, float* Y, hipStream_t st) {
+    return DzGemm::dense(L, planes ? nullptr : X, ldx, NT, C, Y, C, C, DZ_EPI_RELU_BN).xplanes(planes, xplane)
+        .prof(DZ_T_ECAPA_WIDE, N).run(st);
 }
 
 static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_out, hipStream_t st);
@@ -249,14 +198,10 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     const long long NT = (long long)N * T;
 
     // ---- 2. Fbank: STFT as one GEMM over overlapping rows (hop 160 < window 400) ---------------
-    dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
-    if ((rc = gemm(DZ_T_ECAPA_FBANK, N, st, e->geo.sig, HOP, e->geo.lstride, N, T, NFFT, 1, 1, 0, dft, nullptr, 416, 448, 402, e->spec,
-                   404, (long long)T * 404, DZ_EPI_BIAS)))
-        return rc;
-    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_power(e->spec, 404, NT, e->pw, st))) return rc; }
-    dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
-    if ((rc = gemm(DZ_T_ECAPA_FBANK, N, st, e->pw, 204, 0, 1, (int)NT, 204, 1, 1, 0, mel, nullptr, 224, 128, 80, e->melp, 80, 0,
-                   DZ_EPI_BIAS)))
+    const dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
+    const dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
+    if ((rc = dz_fbank_front(dft, mel, e->geo.sig, e->geo.lstride, N, T, e->spec, e->pw, 80, 128, e->melp, st,
+                             DZ_T_ECAPA_FBANK)))
         return rc;
     { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->geo.nvalid, e->feats, st, tdev))) return rc; }
 
@@ -268,8 +213,8 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     const bool pre = e->b0s != nullptr;
     const long long p1 = NT * C1, p3 = NT * C3;          // elements between the hi and lo planes
     // block 0: Conv1d(80 -> 1024, k5) -> ReLU -> BN
-    if ((rc = gemm(DZ_T_ECAPA_BLOCK0, N, st, e->feats, 80, (long long)T * 80, N, T, 80, 5, 1, 2, w.block0, nullptr, 416, C1, C1,
-                   e->b0, C1, (long long)T * C1, DZ_EPI_RELU_BN, nullptr, nullptr, 0, 0, pre ? e->b0s : nullptr, p1, tdev)))
+    if ((rc = DzGemm::conv1d(w.block0, e->feats, 80, N, T, 80, e->b0, C1, C1, DZ_EPI_RELU_BN).taps(5, 1, 2).padded(416, C1)
+                  .planes_out(pre ? e->b0s : nullptr, p1).tdev(tdev).prof(DZ_T_ECAPA_BLOCK0, N).run(st)))
         return rc;
     const int dil[3] = {2, 3, 4};
     for (int i = 0; i < 3; ++i) {
@@ -277,14 +222,9 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
         const float* xin = i == 0 ? e->b0 : e->cat + (size_t)(i - 1) * C1;
         const int ldin = i == 0 ? C1 : C3;
         // tdnn1 (1x1): block 0 reads block0's planes, blocks 1 / 2 columns [1024 (i - 1), 1024 i) of the concatenation's
-        if (pre)
-            rc = i == 0 ? gemm_pre(DZ_T_ECAPA_WIDE, N, st, e->b0s, p1, C1, NT, C1, b.tdnn1, C1, e->t1)
-                        : gemm_pre(DZ_T_ECAPA_WIDE, N, st, e->cats + (size_t)(i - 1) * (C1 / 32) * NT * 32, p3, C3, NT, C1, b.tdnn1,
-                                   C1, e->t1);
-        else
-            rc = gemm(DZ_T_ECAPA_WIDE, N, st, xin, ldin, 0, 1, (int)NT, C1, 1, 1, 0, b.tdnn1, nullptr, C1, C1, C1, e->t1, C1, 0,
-                      DZ_EPI_RELU_BN);
-        if (rc) return rc;
+        if ((rc = wide(b.tdnn1, xin, ldin, pre ? (i == 0 ? e->b0s : e->cats + (size_t)(i - 1) * (C1 / 32) * NT * 32) : nullptr,
+                       i == 0 ? p1 : p3, N, NT, C1, e->t1, st)))
+            return rc;
         // Res2Net: y0 = x0; y1 = f1(x1); yi = fi(xi + y(i-1))
         if (pre) {      // (y0 is only read by tdnn2: planes alone)
             DzProfScope ps(DZ_T_ECAPA_RES2, N);
@@ -296,28 +236,22 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
         for (int j = 1; j < 8; ++j) {
             const float* x2 = j >= 2 ? e->res + (j - 1) * 128 : nullptr;
             // (y7 has no f32 reader when tdnn2 takes the planes)
-            if ((rc = gemm(DZ_T_ECAPA_RES2, N, st, e->t1 + j * 128, C1, (long long)T * C1, N, T, 128, 3, dil[i], dil[i], b.res[j - 1],
-                           nullptr, 384, 128, 128, pre && j == 7 ? nullptr : e->res + j * 128, C1, (long long)T * C1, DZ_EPI_RELU_BN,
-                           x2, nullptr, 0, 0, pre ? e->ress + (size_t)j * 4 * NT * 32 : nullptr, p1, tdev)))
+            if ((rc = DzGemm::conv1d(b.res[j - 1], e->t1 + j * 128, C1, N, T, 128, pre && j == 7 ? nullptr : e->res + j * 128,
+                                     C1, 128, DZ_EPI_RELU_BN).taps(3, dil[i], dil[i]).padded(384, 128).x2(x2)
+                          .planes_out(pre ? e->ress + (size_t)j * 4 * NT * 32 : nullptr, p1).tdev(tdev)
+                          .prof(DZ_T_ECAPA_RES2, N).run(st)))
                 return rc;
         }
         // tdnn2 (1x1)
-        if (pre)
-            rc = gemm_pre(DZ_T_ECAPA_WIDE, N, st, e->ress, p1, C1, NT, C1, b.tdnn2, C1, e->t2);
-        else
-            rc = gemm(DZ_T_ECAPA_WIDE, N, st, e->res, C1, 0, 1, (int)NT, C1, 1, 1, 0, b.tdnn2, nullptr, C1, C1, C1, e->t2, C1, 0,
-                      DZ_EPI_RELU_BN);
-        if (rc) return rc;
+        if ((rc = wide(b.tdnn2, e->res, C1, e->ress, p1, N, NT, C1, e->t2, st))) return rc;
         // squeeze-excitation + residual, written straight into its slice of the concatenation
         { DzProfScope ps(DZ_T_ECAPA_SE, N); if ((rc = dz_launch_se_mean(e->t2, T, C1, C1, N, e->geo.nmask, e->smean, st))) return rc; }
         // squeeze (N rows x 1024 -> 128): one output tile, so the K loop is split 8 ways (a lone workgroup
         // walking 32 k-tiles took 90 us); the ReLU follows the fixed-order reduce
-        if ((rc = gemm(DZ_T_ECAPA_SE, N, st, e->smean, C1, 0, 1, N, C1, 1, 1, 0, b.se1, nullptr, C1, 128, 128, e->parts, 128, 0,
-                       DZ_EPI_BIAS, nullptr, nullptr, SE_SPLIT, (long long)N * 128)))
+        if ((rc = dz_splitk_linear(b.se1, e->smean, N, C1, C1, 128, SE_SPLIT, e->parts, 2, e->sfc1, st, DZ_T_ECAPA_SE)))
             return rc;
-        { DzProfScope ps(DZ_T_ECAPA_SE, N); if ((rc = dz_launch_splitk_finish(e->parts, SE_SPLIT, (long long)N * 128, N, 128, 2, e->sfc1, st))) return rc; }
-        if ((rc = gemm(DZ_T_ECAPA_SE, N, st, e->sfc1, 128, 0, 1, N, 128, 1, 1, 0, b.se2, nullptr, 128, C1, C1, e->gate, C1, 0,
-                       DZ_EPI_BIAS_SIGMOID)))
+        if ((rc = DzGemm::dense(b.se2, e->sfc1, 128, N, 128, e->gate, C1, C1, DZ_EPI_BIAS_SIGMOID).prof(DZ_T_ECAPA_SE, N)
+                      .run(st)))
             return rc;
         { DzProfScope ps(DZ_T_ECAPA_SE, N);
           if (pre)      // f32 for the next block's residual (the last block has none), planes for its tdnn1 and the MFA convolution
@@ -328,35 +262,12 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
           if (rc) return rc; }
     }
     // multi-layer feature aggregation
-    if (pre)
-        rc = gemm_pre(DZ_T_ECAPA_WIDE, N, st, e->cats, p3, C3, NT, C3, w.mfa, C3, e->mfa);
-    else
-        rc = gemm(DZ_T_ECAPA_WIDE, N, st, e->cat, C3, 0, 1, (int)NT, C3, 1, 1, 0, w.mfa, nullptr, C3, C3, C3, e->mfa, C3, 0,
-                  DZ_EPI_RELU_BN);
-    if (rc) return rc;
-    // attentive statistics pooling with global context: W [x; mean; std] = Wx x + Wms [mean; std]
-    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_asp_gstats(e->mfa, T, C3, N, e->geo.nmask, e->gstat, st))) return rc; }
-    dz_layer wms = {w.asp_wms, w.zeros, nullptr, nullptr};
-    // (N rows x 6144 -> 128: one output tile and 192 k-tiles — 0.5 ms for a lone workgroup; split-K like fc)
-    if ((rc = gemm(DZ_T_ECAPA_ASP, N, st, e->gstat, 2 * C3, 0, 1, N, 2 * C3, 1, 1, 0, wms, nullptr, 2 * C3, 128, 128, e->parts, 128, 0,
-                   DZ_EPI_BIAS, nullptr, nullptr, FC_SPLIT, (long long)N * 128)))
-        return rc;
-    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_splitk_finish(e->parts, FC_SPLIT, (long long)N * 128, N, 128, 0, e->rb, st))) return rc; }
-    if ((rc = gemm(DZ_T_ECAPA_ASP, N, st, e->mfa, C3, (long long)T * C3, N, T, C3, 1, 1, 0, w.asp_tdnn, nullptr, C3, 128, 128, e->a1,
-                   128, (long long)T * 128, DZ_EPI_RELU_BN_TANH, nullptr, e->rb)))
-        return rc;
-    float* logits = e->cat;   // the concatenation is dead once the MFA layer has consumed it
-    if ((rc = gemm(DZ_T_ECAPA_ASP, N, st, e->a1, 128, 0, 1, (int)NT, 128, 1, 1, 0, w.asp_conv, nullptr, 128, C3, C3, logits, C3, 0,
-                   DZ_EPI_BIAS)))
-        return rc;
-    { DzProfScope ps(DZ_T_ECAPA_ASP, N); if ((rc = dz_launch_asp_pool(e->mfa, logits, T, C3, N, e->geo.nmask, e->pooled, st))) return rc; }
-    // asp_bn (folded) + fc, split-K with a fixed-order reduce
-    const long long ysplit = (long long)N * EMB;
-    if ((rc = gemm(DZ_T_ECAPA_FC, N, st, e->pooled, 2 * C3, 0, 1, N, 2 * C3, 1, 1, 0, w.fc, nullptr, 2 * C3, EMB, EMB, e->parts, EMB,
-                   0, DZ_EPI_BIAS, nullptr, nullptr, FC_SPLIT, ysplit)))
-        return rc;
-    { DzProfScope ps(DZ_T_ECAPA_FC, N); if ((rc = dz_launch_splitk_finish(e->parts, FC_SPLIT, ysplit, N, EMB, 0, d_out, st))) return rc; }
-    return 0;
+    if ((rc = wide(w.mfa, e->cat, C3, e->cats, p3, N, NT, C3, e->mfa, st))) return rc;
+    // attentive statistics pooling with global context, asp_bn (folded) + fc (dz_asp_tail); the logits go where the
+    // concatenation is dead once the MFA layer has consumed it
+    const DzAspTail tail = {w.asp_wms, w.zeros, &w.asp_tdnn, &w.asp_conv, &w.fc, e->gstat, e->rb, e->a1, e->cat, e->pooled,
+                            e->parts, FC_SPLIT, DZ_T_ECAPA_ASP, DZ_T_ECAPA_FC};
+    return dz_asp_tail(tail, e->mfa, N, T, C3, EMB, e->geo.nmask, d_out, st);
 }
 
 // The forward of the rows of n_groups chunks, K (rows_per_group) speaker rows each, every group with its own
@@ -364,25 +275,25 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
 // no host round trip: the geometry is derived on the device (dz_launch_ecapa_geometry) and every buffer is laid
 // out with the handle's Tc frames per row.  Row g K + k reads waveform row g and mask row g K + k ((G, K, Fw)
 // contiguous, the speaker-major OSP weights of dz_seg_forward_osp).
-extern "C" int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
-                                       int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
-                                       void* stream) {
-    int rc = dz_check_groups_forward("dz_ecapa_forward_groups", e, e ? e->Nm : 0, d_wave, wave_stride, d_masks,
-                                     n_groups, rows_per_group, mask_frames, d_out);
-    if (rc) return rc;
-    DZ_HIP(hipSetDevice(e->ctx->device));
-    DzRangeScope range_scope(e->ctx->oflag_dev);
-    hipStream_t st = (hipStream_t)stream;
-    const int N = n_groups * rows_per_group, Tc = e->geo.Tc;
+static int ecapa_run_groups(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks, int G, int K,
+                            int rows_per_wave, int mask_frames, int normalize, float* d_out, hipStream_t st) {
+    const int N = G * K, Tc = e->geo.Tc;
+    int rc;
     { DzProfScope ps(DZ_T_ECAPA_FBANK, N);
-      if ((rc = e->geo.prologue(d_wave, wave_stride, d_masks, mask_frames, n_groups, rows_per_group, rows_per_group, st)))
-          return rc; }
+      if ((rc = e->geo.prologue(d_wave, wave_stride, d_masks, mask_frames, G, K, rows_per_wave, st))) return rc; }
     e->lastN = N;
     e->lastT = Tc;
     e->lastGroups = 1;
     if ((rc = ecapa_network(e, N, Tc, e->geo.tdev, d_out, st))) return rc;
     if ((rc = dz_launch_nan_rows(d_out, N, EMB, e->geo.tooshort, st))) return rc;
     return normalize ? dz_launch_l2norm(d_out, N, EMB, 1.0f, st) : 0;
+}
+
+extern "C" int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_stride, const float* d_masks,
+                                       int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                                       void* stream) {
+    return dz_handle_forward_groups("dz_ecapa_forward_groups", e, d_wave, wave_stride, d_masks, n_groups, rows_per_group,
+                                    mask_frames, normalize, d_out, stream, ecapa_run_groups);
 }
 
 extern "C" int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long long* count, int* frames) {

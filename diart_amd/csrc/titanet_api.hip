@@ -4,10 +4,7 @@
 // the pointwise convolutions (BatchNorm folded) are descriptor instances of the wide GEMMs: k_gemm_pre.hip over the
 // depthwise kernel's f16 planes ("f16x3"), k_gemm_f32.hip over its f32 rows ("f32").  A pointwise layer's ReLU is
 // applied by the depthwise kernel that reads it.
-#include "dz_common.h"
-
-#include <string.h>
-#include <new>
+#include "dz_embed.h"
 
 int dz_launch_ttn_geometry(const int* lens, int G, int K, int Tc, int S, int min_samples, int fpad, int fnfft,
                            int* tooshort, int* elen, int* plen, int* frames, hipStream_t st);
@@ -82,64 +79,19 @@ extern "C" int dz_ttn_create(dz_ctx* ctx, const dz_ttn_weights* w, int max_rows,
     DZ_REQUIRE(w->min_num_samples > 200 && w->frame_pad >= 0 && w->frame_nfft >= 0,
                "dz_ttn_create: min_num_samples %d (> 200: the reflect padding reads 200 samples back), frame_pad %d, "
                "frame_nfft %d", w->min_num_samples, w->frame_pad, w->frame_nfft);
-    DZ_REQUIRE(max_rows >= 1 && num_samples >= w->min_num_samples, "dz_ttn_create: max_rows %d, %d samples", max_rows,
-               num_samples);
     DZ_REQUIRE((long long)max_rows * (1 + num_samples / HOP) * C3 * 2 < (1ll << 31),
                "dz_ttn_create: %d rows x %d frames exceed the GEMM operands' 2 GiB offset range", max_rows,
                1 + num_samples / HOP);
-    DZ_HIP(hipSetDevice(ctx->device));
-    dz_ttn* m = new (std::nothrow) dz_ttn;
-    DZ_REQUIRE(m != nullptr, "dz_ttn_create: out of memory");
-    memset(m, 0, sizeof(*m));
-    m->ctx = ctx; m->w = *w; m->Nm = max_rows;
-    m->geo.init(num_samples, w->min_num_samples);
-    if (int rc = dz_arena_alloc("dz_ttn_create", m, ttn_carve)) {
-        dz_ttn_destroy(m);
-        return rc;
-    }
-    *out = m;
-    return 0;
+    return dz_handle_create("dz_ttn_create", ctx, w, max_rows, num_samples, w->min_num_samples, ttn_carve, out);
 }
 
-extern "C" int dz_ttn_destroy(dz_ttn* m) {
-    if (m) {
-        if (m->arena) (void)hipFree(m->arena);
-        delete m;
-    }
-    return 0;
-}
-
-// one GEMM launch of the front end / pooling (ECAPA's forms): split-f16 when the layer has row-major planes
-static int ttn_gemm(hipStream_t st, const float* X, int ldx, long long xbs, int B, int T, int Cin, const dz_layer& L,
-                    const float* bias, int Kpad, int Npad, int Nstore, float* Y, int ldy, long long ybs, int epi,
-                    const float* rowbias = nullptr, int ksplit = 0, long long ysplit = 0) {
-    DzConvGemm p;
-    memset(&p, 0, sizeof(p));
-    p.X = X; p.W = L.w; p.bias = bias ? bias : L.b; p.e0 = L.s; p.e1 = L.h; p.Y = Y;
-    p.B = B; p.Tin = p.Tout = p.Tstore = T; p.Cin = Cin; p.taps = 1; p.dil = 1; p.K = Cin; p.Kpad = Kpad;
-    p.Npad = Npad; p.Nstore = Nstore; p.ldx = ldx; p.ldy = ldy; p.xbs = xbs; p.ybs = ybs;
-    p.epi = epi; p.rowbias = rowbias; p.ksplit = ksplit; p.ysplit = ysplit;
-    if (L.wsplit && ksplit <= 1) {
-        p.Wsplit = L.wsplit;
-        return dz_launch_gemm_split(p, st);
-    }
-    return dz_launch_convgemm(p, st);
-}
+extern "C" int dz_ttn_destroy(dz_ttn* m) { return dz_handle_destroy(m); }
 
 // a pointwise convolution with its BatchNorm folded: rows x Cin -> rows x Cout, + bias.  "f16x3": both operands as
 // kb-major planes (k_gemm_pre.hip); "f32": f32 rows (k_gemm_f32.hip through dz_launch_convgemm)
 static int ttn_pointwise(hipStream_t st, const float* Xf, const void* Xs, long long rows, int Cin, const dz_layer& L,
                          int Cout, float* Y) {
-    DzConvGemm p;
-    memset(&p, 0, sizeof(p));
-    p.bias = L.b; p.Y = Y; p.B = 1; p.Tin = p.Tout = p.Tstore = (int)rows; p.Cin = Cin; p.taps = 1; p.dil = 1;
-    p.K = p.Kpad = Cin; p.Npad = p.Nstore = Cout; p.ldx = Cin; p.ldy = Cout; p.epi = DZ_EPI_BIAS;
-    if (Xs) {
-        p.Xsplit = Xs; p.xplane = rows * Cin; p.Wsplit = L.wsplit;
-        return dz_launch_gemm_pre(p, st);
-    }
-    p.X = Xf; p.W = L.w;
-    return dz_launch_convgemm(p, st);
+    return DzGemm::dense(L, Xf, Cin, rows, Cin, Y, Cout, Cout, DZ_EPI_BIAS).xplanes(Xs, rows * Cin).run(st);
 }
 
 // The forward of G groups of K rows, every row laid out with the handle's Tc frames.  Row g K + k reads waveform row
@@ -164,13 +116,12 @@ static int ttn_run(dz_ttn* m, const float* d_wave, long long wave_stride, const 
     if ((rc = dz_launch_ttn_prep(geo.sig, geo.lstride, N, m->elen, m->plen, w.pad_reflect, m->sig2, st))) return rc;
     // ---- front end: STFT as one GEMM over the overlapping rows, |.|^2, mel GEMM, log + normalisation ---------------
     const dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
-    if ((rc = ttn_gemm(st, m->sig2, HOP, geo.lstride, N, T, NWIN, dft, nullptr, 416, 640, 2 * NBIN, m->spec, SPEC_LD,
-                       (long long)T * SPEC_LD, DZ_EPI_BIAS)))
+    if ((rc = DzGemm::conv1d(dft, m->sig2, HOP, N, T, NWIN, m->spec, SPEC_LD, 2 * NBIN, DZ_EPI_BIAS)
+                  .xstride(geo.lstride, (long long)T * SPEC_LD).padded(416, 640).run(st)))
         return rc;
     if ((rc = dz_launch_ttn_power(m->spec, SPEC_LD, NT, m->pw, st))) return rc;
     const dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
-    if ((rc = ttn_gemm(st, m->pw, PW_LD, 0, 1, (int)NT, PW_LD, mel, nullptr, 288, 128, NMEL, m->melp, NMEL, 0,
-                       DZ_EPI_BIAS)))
+    if ((rc = DzGemm::dense(mel, m->pw, PW_LD, NT, PW_LD, m->melp, NMEL, NMEL, DZ_EPI_BIAS).padded(288, 128).run(st)))
         return rc;
     if ((rc = dz_launch_ttn_norm(m->melp, T, N, m->frames, m->feats, st))) return rc;
     // ---- encoder: five separable blocks -------------------------------------------------------------------------
@@ -203,50 +154,25 @@ static int ttn_run(dz_ttn* m, const float* d_wave, long long wave_stride, const 
         cin = ldin = cout;
     }
     // ---- decoder: attentive statistics pooling (ECAPA's form), BatchNorm + Conv1d(6144, 192) ------------------------
-    const float* x = m->blk[4];
-    if ((rc = dz_launch_asp_gstats(x, T, C3, N, m->frames, m->gstat, st))) return rc;
-    const dz_layer wms = {w.asp_wms, w.zeros, nullptr, nullptr, nullptr};
-    if ((rc = ttn_gemm(st, m->gstat, 2 * C3, 0, 1, N, 2 * C3, wms, nullptr, 2 * C3, 128, 128, m->parts, 128, 0, DZ_EPI_BIAS,
-                       nullptr, FC_SPLIT, (long long)N * 128)))
-        return rc;
-    if ((rc = dz_launch_splitk_finish(m->parts, FC_SPLIT, (long long)N * 128, N, 128, 0, m->rb, st))) return rc;
-    if ((rc = ttn_gemm(st, x, C3, (long long)T * C3, N, T, C3, w.asp_tdnn, nullptr, C3, 128, 128, m->a1, 128,
-                       (long long)T * 128, DZ_EPI_RELU_BN_TANH, m->rb)))
-        return rc;
-    float* logits = m->y[0];     // (block 4's pointwise output is dead behind its apply pass)
-    if ((rc = ttn_gemm(st, m->a1, 128, 0, 1, (int)NT, 128, w.asp_conv, nullptr, 128, C3, C3, logits, C3, 0, DZ_EPI_BIAS)))
-        return rc;
-    if ((rc = dz_launch_asp_pool(x, logits, T, C3, N, m->frames, m->pooled, st))) return rc;
-    const long long ysplit = (long long)N * EMB;
+    // (the logits go where block 4's pointwise output is dead behind its apply pass)
     const dz_layer fc = {w.fc.w, w.fc.b, nullptr, nullptr, nullptr};
-    if ((rc = ttn_gemm(st, m->pooled, 2 * C3, 0, 1, N, 2 * C3, fc, nullptr, 2 * C3, EMB, EMB, m->parts, EMB, 0, DZ_EPI_BIAS,
-                       nullptr, FC_SPLIT, ysplit)))
-        return rc;
-    if ((rc = dz_launch_splitk_finish(m->parts, FC_SPLIT, ysplit, N, EMB, 0, d_out, st))) return rc;
+    const DzAspTail tail = {w.asp_wms, w.zeros, &w.asp_tdnn, &w.asp_conv, &fc, m->gstat, m->rb, m->a1, m->y[0], m->pooled,
+                            m->parts, FC_SPLIT, -1, -1};
+    if ((rc = dz_asp_tail(tail, m->blk[4], N, T, C3, EMB, m->frames, d_out, st))) return rc;
     if ((rc = dz_launch_nan_rows(d_out, N, EMB, geo.tooshort, st))) return rc;
     return normalize ? dz_launch_l2norm(d_out, N, EMB, 1.0f, st) : 0;
 }
 
 extern "C" int dz_ttn_forward(dz_ttn* m, const float* d_wave, long long wave_stride, const float* d_masks, int N,
                               int mask_frames, float* d_out, void* stream) {
-    if (int rc = dz_check_rows_forward("dz_ttn_forward", m, m ? m->Nm : 0, d_wave, wave_stride, d_masks, N, mask_frames,
-                                       d_out))
-        return rc;
-    DZ_HIP(hipSetDevice(m->ctx->device));
-    DzRangeScope range_scope(m->ctx->oflag_dev);
-    return ttn_run(m, d_wave, wave_stride, d_masks, 1, N, 1, mask_frames, 0, d_out, (hipStream_t)stream);
+    return dz_handle_forward("dz_ttn_forward", m, d_wave, wave_stride, d_masks, N, mask_frames, d_out, stream, ttn_run);
 }
 
 extern "C" int dz_ttn_forward_groups(dz_ttn* m, const float* d_wave, long long wave_stride, const float* d_masks,
                                      int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
                                      void* stream) {
-    if (int rc = dz_check_groups_forward("dz_ttn_forward_groups", m, m ? m->Nm : 0, d_wave, wave_stride, d_masks,
-                                         n_groups, rows_per_group, mask_frames, d_out))
-        return rc;
-    DZ_HIP(hipSetDevice(m->ctx->device));
-    DzRangeScope range_scope(m->ctx->oflag_dev);
-    return ttn_run(m, d_wave, wave_stride, d_masks, n_groups, rows_per_group, rows_per_group, mask_frames, normalize,
-                   d_out, (hipStream_t)stream);
+    return dz_handle_forward_groups("dz_ttn_forward_groups", m, d_wave, wave_stride, d_masks, n_groups, rows_per_group,
+                                    mask_frames, normalize, d_out, stream, ttn_run);
 }
 
 extern "C" int dz_ttn_peek(dz_ttn* m, int which, const void** d_ptr, long long* count, int* frames) {

@@ -1,8 +1,5 @@
 // dz_wsp_*: launch sequence of the WeSpeaker ResNet34 embedding (include/diart_amd.h).  Host code.
-#include "dz_common.h"
-
-#include <string.h>
-#include <new>
+#include "dz_embed.h"
 
 namespace {
 
@@ -71,13 +68,7 @@ extern "C" int dz_wsp_create(dz_ctx* ctx, const dz_wsp_weights* w, int max_rows,
     return 0;
 }
 
-extern "C" int dz_wsp_destroy(dz_wsp* m) {
-    if (m) {
-        if (m->arena) (void)hipFree(m->arena);
-        delete m;
-    }
-    return 0;
-}
+extern "C" int dz_wsp_destroy(dz_wsp* m) { return dz_handle_destroy(m); }
 
 static int conv(const dz_wsp_conv& c, const float* X, int N, int Fi, int Ti, int Cin, int Cout, int taps, int stride,
                 const float* R, int relu, float* Y, hipStream_t st) {
@@ -129,14 +120,8 @@ static int wsp_head(dz_wsp* m, int N, int K, const float* d_weights, int Fw, int
     const int rows = N * K;
     if ((rc = dz_launch_wsp_pool(m->L[3], N, m->T[4], d_weights, Fw, K, m->bad, m->pooled, m->rflag, st))) return rc;
     // seg_1: rows x 5120 -> 256, split-K with a fixed-order reduce (k_pool.hip) on the exact-f32 GEMM
-    DzConvGemm p;
-    memset(&p, 0, sizeof(p));
-    p.X = m->pooled; p.W = m->w.seg_w; p.bias = m->w.seg_b; p.Y = m->parts;
-    p.B = 1; p.Tin = p.Tout = p.Tstore = rows; p.Cin = POOLED; p.taps = 1; p.dil = 1; p.K = p.Kpad = POOLED;
-    p.Npad = p.Nstore = EMB; p.ldx = POOLED; p.ldy = EMB; p.epi = DZ_EPI_BIAS; p.ksplit = FC_SPLIT;
-    p.ysplit = (long long)rows * EMB;
-    if ((rc = dz_launch_convgemm(p, st))) return rc;
-    if ((rc = dz_launch_splitk_finish(m->parts, FC_SPLIT, (long long)rows * EMB, rows, EMB, normalize ? 1 : 0, d_out, st)))
+    const dz_layer seg = {m->w.seg_w, m->w.seg_b, nullptr, nullptr, nullptr};
+    if ((rc = dz_splitk_linear(seg, m->pooled, rows, POOLED, POOLED, EMB, FC_SPLIT, m->parts, normalize ? 1 : 0, d_out, st)))
         return rc;
     m->lastRows = rows;
     return dz_launch_nan_rows(d_out, rows, EMB, m->rflag, st);

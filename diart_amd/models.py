@@ -276,90 +276,9 @@ class HipSegmentation(_HipModule):
         return (track, scores) if return_scores else track
 
 
-class HipEmbedding(_HipModule):
-    """pyannote/embedding forward: ``(waveform (N,1,S), weights (N,F) | None) -> (N,512)`` — the
-    callable behind ``EmbeddingModel.__call__`` (reference models.py:248-265)."""
-
-    dimension = 512
-
-    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None,
-                 weight_interp: Optional[str] = None, repeated_rows: Optional[str] = None):
-        """``weight_interp``: StatsPool's resampling of the pooling weights to the feature frames — "linear"
-        (pyannote.audio 2.x .. 3.0: ``F.interpolate(mode="linear")``; the default, setup.cfg pins ``>=2.1.1``) or
-        "nearest" (pyannote.audio >= 3.1).  ``EmbeddingLoader`` sets it from the version a checkpoint records.
-        ``repeated_rows``: "each" | "share" (``repeated_rows_mode``)."""
-        super().__init__(state, max_batch)
-        self.precision = default_precision(precision)
-        self.weight_interp = weight_interp or "linear"
-        self.repeated_rows = repeated_rows_mode(repeated_rows)
-
-    def _extra_state(self):
-        return {"precision": self.precision, "weight_interp": self.weight_interp, "repeated_rows": self.repeated_rows}
-
-    def _pack(self, device):
-        return PackedEmbedding(self._state, device, precision=self.precision, weight_interp=self.weight_interp)
-
-    def _create(self, num_samples, cap):
-        h = _lib.vp()
-        _lib.check(_lib.load().dz_emb_create(_lib.context(self.device.index),
-                                             C.byref(self._packed.struct), cap, num_samples,
-                                             C.byref(h)), "dz_emb_create")
-        return h
-
-    def _destroy(self, h):
-        _lib.load().dz_emb_destroy(h)
-
-    def __call__(self, waveform: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if self.device is None:
-            self.to(waveform.device)
-        rows = _as_rows(waveform.to(self.device))
-        N, S = rows.shape
-        wptr, fw = None, 0
-        if weights is not None:
-            weights = weights.to(self.device, torch.float32).contiguous()
-            if weights.ndim != 2 or weights.shape[0] != N:
-                raise ValueError(f"weights must be (batch, frames), got {tuple(weights.shape)}")
-            wptr, fw = weights.data_ptr(), weights.shape[1]
-        self.last_shared = None
-        if self.repeated_rows == "share" and weights is not None and N >= 2:
-            shared = self._shared_call(rows, weights)
-            if shared is not None:
-                return shared
-        handle = self._need(S, N)
-        out = torch.empty((N, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_emb_forward(handle, rows.data_ptr(), rows.stride(0) if N > 1 else S,
-                                              wptr, N, fw, out.data_ptr(), _stream_ptr(self.device)),
-                   "dz_emb_forward")
-        return out
-
-    def forward_multi(self, waveform: torch.Tensor, weights: torch.Tensor,
-                      normalize: bool = False) -> torch.Tensor:
-        """``waveform (B,1,S)``, ``weights (B,K,F)`` speaker-major -> ``(B,K,512)``.
-
-        Same result as the reference's ``(B*K)``-row call (blocks/embedding.py:56-65) with
-        the speaker-independent frame features computed once per chunk instead of K times.
-        """
-        if self.device is None:
-            self.to(waveform.device)
-        rows = _as_rows(waveform.to(self.device))
-        B, S = rows.shape
-        weights = weights.to(self.device, torch.float32).contiguous()
-        if weights.ndim != 3 or weights.shape[0] != B:
-            raise ValueError(f"weights must be (batch, speakers, frames), got {tuple(weights.shape)}")
-        K, fw = weights.shape[1], weights.shape[2]
-        handle = self._need(S, B)
-        out = torch.empty((B, K, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_emb_forward_multi(handle, rows.data_ptr(),
-                                                    rows.stride(0) if B > 1 else S,
-                                                    weights.data_ptr(), B, K, fw,
-                                                    1 if normalize else 0, out.data_ptr(),
-                                                    _stream_ptr(self.device)), "dz_emb_forward_multi")
-        return out
-
-
 class _HipSpeakerEmbedding(_HipModule):
-    """The plumbing of the ECAPA-TDNN, speechbrain x-vector and WeSpeaker handles: one C prefix (``_c``: ``dz_ecapa``,
-    ``dz_sbx``, ``dz_wsp``) names their create / destroy / forward / peek functions; ``(waveform (N,1,S), masks or
+    """The plumbing of every speaker-embedding handle: one C prefix (``_c``: ``dz_emb``, ``dz_ecapa``, ``dz_sbx``,
+    ``dz_ttn``, ``dz_wsp``) names their create / destroy / forward / peek functions; ``(waveform (N,1,S), masks or
     weights (N,F) | None) -> (N,dimension)``."""
 
     dimension: int
@@ -417,6 +336,9 @@ class _HipSpeakerEmbedding(_HipModule):
         return out
 
     def _peek_raw(self, handle, which: int):
+        if not hasattr(_lib.load(), f"{self._c}_peek"):
+            raise NotImplementedError(f"{type(self).__name__}: {self._c} handles expose no intermediate buffers (no "
+                                      f"{self._c}_peek)")
         ptr, cnt, frames = _lib.vp(), C.c_longlong(), C.c_int()
         _lib.check(self._fn("peek")(handle, which, C.byref(ptr), C.byref(cnt), C.byref(frames)), f"{self._c}_peek")
         return ptr, cnt.value, frames.value
@@ -432,6 +354,54 @@ class _HipSpeakerEmbedding(_HipModule):
         torch.cuda.synchronize(self.device)
         _lib.memcpy(out.data_ptr(), ptr, cnt * 4)
         return out, frames
+
+
+class _HipTrunkEmbedding(_HipSpeakerEmbedding):
+    """The pyannote x-vector and WeSpeaker: the (N, F) matrix is pooling weights, so everything before the pooling is
+    speaker-independent; ``blocks.SpeakerEmbedding`` takes ``forward_multi`` where a model has it."""
+
+    _frames_arg, _shares = "weights", True
+
+    def forward_multi(self, waveform: torch.Tensor, weights: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """``waveform (B,1,S)``, ``weights (B,K,F)`` speaker-major -> ``(B,K,dimension)`` the reference's ``(B*K)``-row call (blocks/embedding.py:56-65) with
+        everything before the pooling computed once per window instead of K times.  No synchronisation."""
+        if self.device is None:
+            self.to(waveform.device)
+        rows = _as_rows(waveform.to(self.device))
+        B, S = rows.shape
+        weights = weights.to(self.device, torch.float32).contiguous()
+        if weights.ndim != 3 or weights.shape[0] != B:
+            raise ValueError(f"weights must be (batch, speakers, frames), got {tuple(weights.shape)}")
+        K, fw = weights.shape[1], weights.shape[2]
+        handle = self._need(S, B)
+        out = torch.empty((B, K, self.dimension), dtype=torch.float32, device=self.device)
+        _lib.check(self._fn("forward_multi")(handle, rows.data_ptr(), rows.stride(0) if B > 1 else S, weights.data_ptr(),
+                                             B, K, fw, 1 if normalize else 0, out.data_ptr(), _stream_ptr(self.device)),
+                   f"{self._c}_forward_multi")
+        return out
+
+
+class HipEmbedding(_HipTrunkEmbedding):
+    """pyannote/embedding forward: ``(waveform (N,1,S), weights (N,F) | None) -> (N,512)`` — the
+    callable behind ``EmbeddingModel.__call__`` (reference models.py:248-265)."""
+
+    dimension = 512
+    _c = "dz_emb"
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None,
+                 weight_interp: Optional[str] = None, repeated_rows: Optional[str] = None):
+        """``weight_interp``: StatsPool's resampling of the pooling weights to the feature frames — "linear"
+        (pyannote.audio 2.x .. 3.0: ``F.interpolate(mode="linear")``; the default, setup.cfg pins ``>=2.1.1``) or
+        "nearest" (pyannote.audio >= 3.1).  ``EmbeddingLoader`` sets it from the version a checkpoint records.
+        ``repeated_rows``: "each" | "share" (``repeated_rows_mode``)."""
+        super().__init__(state, max_batch, precision, repeated_rows)
+        self.weight_interp = weight_interp or "linear"
+
+    def _extra_state(self):
+        return {"precision": self.precision, "weight_interp": self.weight_interp, "repeated_rows": self.repeated_rows}
+
+    def _pack(self, device):
+        return PackedEmbedding(self._state, device, precision=self.precision, weight_interp=self.weight_interp)
 
 
 class _HipGroupsEmbedding(_HipSpeakerEmbedding):
@@ -547,7 +517,7 @@ class HipTitaNetEmbedding(_HipGroupsEmbedding):
         return int(_lib.load().dz_ttn_frames_for(int(num_samples)))
 
 
-class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
+class HipWeSpeakerEmbedding(_HipTrunkEmbedding):
     """pyannote.audio 3.1's ``WeSpeakerResNet34`` (pyannote/wespeaker-voxceleb-resnet34-LM): ``(waveform (N,1,S),
     weights (N,Fw) | None) -> (N,256)`` — the callable the reference loads through ``PyannoteLoader`` (models.py:42-59)
     and calls at blocks/embedding.py:56-65.  kaldi fbank, ResNet34 trunk on implicit-GEMM 2-D convolutions
@@ -555,7 +525,7 @@ class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
     with a NaN / Inf sample comes back NaN."""
 
     dimension = 256
-    _c, _packer, _frames_arg, _shares = "dz_wsp", PackedWeSpeaker, "weights", True
+    _c, _packer = "dz_wsp", PackedWeSpeaker
 
     def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 64, precision: Optional[str] = None,
                  repeated_rows: Optional[str] = None):
@@ -565,24 +535,6 @@ class HipWeSpeakerEmbedding(_HipSpeakerEmbedding):
     def num_frames(self, num_samples: int, stage: int = 0) -> int:
         """Frames of the fbank (stage 0) or after layer 1 .. 4 (``dz_wsp_frames_for``)."""
         return int(_lib.load().dz_wsp_frames_for(int(num_samples), int(stage)))
-
-    def forward_multi(self, waveform: torch.Tensor, weights: torch.Tensor, normalize: bool = False) -> torch.Tensor:
-        """``waveform (B,1,S)``, ``weights (B,K,F)`` speaker-major -> ``(B,K,256)``: the reference's ``(B*K)``-row call
-        with the trunk (everything before the pooling) computed once per window.  No synchronisation."""
-        if self.device is None:
-            self.to(waveform.device)
-        rows = _as_rows(waveform.to(self.device))
-        B, S = rows.shape
-        weights = weights.to(self.device, torch.float32).contiguous()
-        if weights.ndim != 3 or weights.shape[0] != B:
-            raise ValueError(f"weights must be (batch, speakers, frames), got {tuple(weights.shape)}")
-        K, fw = weights.shape[1], weights.shape[2]
-        handle = self._need(S, B)
-        out = torch.empty((B, K, self.dimension), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().dz_wsp_forward_multi(handle, rows.data_ptr(), rows.stride(0) if B > 1 else S,
-                                                    weights.data_ptr(), B, K, fw, 1 if normalize else 0,
-                                                    out.data_ptr(), _stream_ptr(self.device)), "dz_wsp_forward_multi")
-        return out
 
     def trunk_launch(self, handle, wave_ptr: int, wave_stride: int, batch: int, stream_ptr: int) -> None:
         """``dz_wsp_trunk`` on a handle of this model (``WeSpeakerBatch``'s lanes): fbank + ResNet34 of ``batch``
