@@ -16,7 +16,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libdiart_amd.so"
 LIB_EXPERIMENTS = HERE / "libdiart_amd_exp.so"
-SOURCES = ["api.hip", "ecapa_api.hip", "k_front.hip", "k_convgemm.hip", "k_gemm_f32.hip", "k_gemm_split.hip", "k_gemm_pre.hip",
+SOURCES = ["api.hip", "seg_api.hip", "xvec_api.hip", "kernel_api.hip", "ecapa_api.hip", "k_front.hip", "k_convgemm.hip", "k_gemm_f32.hip", "k_gemm_split.hip", "k_gemm_pre.hip",
            "k_mlp_head.hip", "k_conv_pool.hip", "k_lstm.hip", "k_lstm_mfma.hip", "k_pool.hip",
            "k_ecapa.hip", "sbx_api.hip", "titanet_api.hip", "k_titanet.hip", "wespeaker_api.hip", "k_wespeaker.hip", "k_conv2d.hip", "k_resample.hip", "k_rows_repeat.hip", "resample_api.hip", "ring.hip", "cluster.cpp", "tail.cpp", "hostpool.cpp", "filebatch.cpp"]
 # -DDZ_EXPERIMENTS only (csrc/dz_common.h "build flavours"): the never-default GEMM generations
@@ -47,7 +47,7 @@ def build(force: bool = False, verbose: bool = False, experiments: bool = False)
     hipcc = _hipcc()
     objdir = HERE / "build" / ("exp" if experiments else "ship")
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [CSRC / "dz_common.h", CSRC / "dz_embed.h", CSRC / "hostpool.h", HERE.parent / "include" / "diart_amd.h",
+    headers = [CSRC / "dz_common.h", CSRC / "dz_embed.h", CSRC / "dz_sincnet.h", CSRC / "hostpool.h", HERE.parent / "include" / "diart_amd.h",
                HERE.parent / "include" / "diart_amd_experiments.h"]
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", f"-I{CSRC}"]
     sources, lib = list(SOURCES), LIB

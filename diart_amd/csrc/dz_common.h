@@ -66,8 +66,14 @@ struct DzProfScope {
     DzProfScope(int tag, int units);
     ~DzProfScope();
 };
-enum { DZ_T_ECAPA_FBANK = 21, DZ_T_ECAPA_BLOCK0, DZ_T_ECAPA_WIDE, DZ_T_ECAPA_RES2, DZ_T_ECAPA_SE, DZ_T_ECAPA_ASP,
-       DZ_T_ECAPA_FC };
+// The brackets' tags: one row each of bench.py's per-kernel table, named by kProfNames (api.hip) in this order.
+enum DzProfTag {
+    DZ_T_WAVE = 0, DZ_T_CONV0, DZ_T_FIN, DZ_T_CONV1, DZ_T_CONV2, DZ_T_PROJ, DZ_T_REC, DZ_T_MLP, DZ_T_CLS,
+    DZ_T_TDNN1, DZ_T_TDNN2, DZ_T_TDNN3, DZ_T_TDNN4, DZ_T_TDNN5, DZ_T_POOL, DZ_T_EMBLIN, DZ_T_L2, DZ_T_OSP, DZ_T_PSET,
+    DZ_T_CDIST, DZ_T_PROJ0,
+    DZ_T_ECAPA_FBANK, DZ_T_ECAPA_BLOCK0, DZ_T_ECAPA_WIDE, DZ_T_ECAPA_RES2, DZ_T_ECAPA_SE, DZ_T_ECAPA_ASP, DZ_T_ECAPA_FC,
+    DZ_T_CONV0_PAIR, DZ_T_NSPLIT, DZ_T_COUNT
+};
 // range flag (dz_ctx::oflag_dev) of the context whose forward pass is being enqueued on this host
 // thread: picked up by the split-f16 launchers when the descriptor does not name one
 extern thread_local int* dz_cur_oflag;

@@ -1,4 +1,4 @@
-// The launch vocabulary of the speaker-embedding handles (ecapa_api.hip, sbx_api.hip, titanet_api.hip,
+// The launch vocabulary of the handles (seg_api.hip, xvec_api.hip, ecapa_api.hip, sbx_api.hip, titanet_api.hip,
 // wespeaker_api.hip): one builder for the GEMM descriptor, the launch sequences two models share, and the entry
 // points of a handle that owns a DzRowGeometry and one arena.  Host code only.
 #pragma once
@@ -10,14 +10,22 @@
 // ---------------------------------------------------------------------------
 // DzGemm: a DzConvGemm filled by name.  Two constructors give the geometry, chained setters the rare fields, run()
 // picks the kernel:
-//   pre-split activations (xplanes)              -> k_gemm_pre.hip
-//   a layer with row-major planes, no split-K    -> k_gemm_split.hip, Npad rounded up to the planes' 128 rows
+//   pre-split activations (xplanes)              -> k_gemm_pre.hip (run_pooled(): its pooled-epilogue launch)
+//   a layer with row-major planes, no split-K,
+//     the POOL3 epilogue (SincNet stages 1 / 2)  -> k_conv_pool.hip with the weights' fragment copy (wfrag);
+//                                                   DZ_CONV_POOL=0 (experiments): k_gemm_split.hip, Npad as given
+//     any other epilogue                         -> k_gemm_split.hip, Npad rounded up to the planes' 128 rows
 //   everything else                              -> k_convgemm.hip / k_gemm_f32.hip (exact f32)
 // Kpad / Npad default to Cin / Nstore (an unpadded 1 x 1 layer); padded() names the packed sizes otherwise.
 // ---------------------------------------------------------------------------
+inline bool dz_conv_pool_enabled() {
+    const char* v = dz_exp_env("DZ_CONV_POOL");
+    return !(v && v[0] == '0');
+}
+
 struct DzGemm {
     DzConvGemm p;
-    const void* wsplit;
+    const void *wsplit, *wfrag;
     int tag, units;
 
     // rows x Cin (ldx floats apart) -> rows x Nstore (ldy apart): one flat batch
@@ -52,8 +60,28 @@ struct DzGemm {
     DzGemm& splitk(int n, long long ysplit) { p.ksplit = n; p.ysplit = ysplit; return *this; }
     // the input as kb-major f16 planes of ldx columns (hi | lo, xplane elements apart), X is then not read; NULL: no-op
     DzGemm& xplanes(const void* Xs, long long xplane) { p.Xsplit = Xs; p.xplane = Xs ? xplane : 0; return *this; }
-    // the output also as kb-major planes, for the next wide layer (split-f16 kernels only)
-    DzGemm& planes_out(void* Ys, long long yplane) { p.Ysplit = Ys; p.yplane = yplane; return *this; }
+    // the output also as kb-major planes, for the next wide layer (split-f16 kernels only); NULL: no-op
+    DzGemm& planes_out(void* Ys, long long yplane) { p.Ysplit = Ys; p.yplane = Ys ? yplane : 0; return *this; }
+    // InstanceNorm + LeakyReLU of the nld input channels as they are loaded: scale / shift derived by the kernel from the
+    // producer's tile partials [B][tiles][nld][2] over T values per channel (split-f16 kernels only) ...
+    DzGemm& norm_partials(const float* part, int tiles, int T, const float* gamma, const float* beta, int nld) {
+        p.npart = part; p.npart_tiles = tiles; p.npart_T = T; p.ngamma = gamma; p.nbeta = beta;
+        p.nld = nld; p.norm_on_load = 1;
+        return *this;
+    }
+    // ... or finalized by dz_launch_finalize_norm: nscale / nshift [B][nld]
+    DzGemm& norm_scaled(const float* nscale, const float* nshift, int nld) {
+        p.nscale = nscale; p.nshift = nshift; p.nld = nld; p.norm_on_load = 1;
+        return *this;
+    }
+    // the DZ_EPI_POOL3 epilogue (after taps()): MaxPool1d(3) of the output frames, Tout / 3 of them stored per item, and
+    // the tile partials [B][ntile][Npad][2] of the pooled rows for the next layer's norm
+    DzGemm& pool3(float* partials) {
+        p.partials = partials; p.Tstore = p.Tout / 3; p.ybs = (long long)p.Tstore * p.ldy;
+        return *this;
+    }
+    // the layer's planes in conv_pool_h's fragment order (dz_launch_conv_pool_wfrag)
+    DzGemm& frag(const void* f) { wfrag = f; return *this; }
     DzGemm& tdev(const int* T) { p.Tdev = T; return *this; }
     DzGemm& prof(int t, int u) { tag = t; units = u; return *this; }
 
@@ -66,11 +94,20 @@ struct DzGemm {
         }
         if (wsplit && p.ksplit <= 1) {
             p.Wsplit = wsplit;
+            if (p.epi == DZ_EPI_POOL3)      // (k_gemm_split.hip takes POOL3 with Npad == 64 only: no rounding)
+                return dz_conv_pool_enabled() ? dz_launch_conv_pool(p, st, wfrag) : dz_launch_gemm_split(p, st);
             p.Npad = (p.Npad + 127) / 128 * 128;       // (the DFT's planes are packed with 512 rows)
             return dz_launch_gemm_split(p, st);
         }
         DZ_REQUIRE(p.Ysplit == nullptr, "DzGemm: plane output asked of a layer that is not on the split-f16 path");
         return dz_launch_convgemm(p, st);
+    }
+    // the pre-split route with the x-vector's statistics pooling in the epilogue: pieces into q instead of an output
+    int run_pooled(const DzPoolFuse& q, hipStream_t st) {
+        DzProfScope ps(tag, units);
+        p.X = p.W = nullptr;
+        p.Wsplit = wsplit;
+        return dz_launch_gemm_pre_pool(p, q, st);
     }
 };
 
@@ -78,15 +115,19 @@ struct DzGemm {
 // launch sequences that more than one model runs.  `tag` (-1: none): the DzProfScope tag of every launch.
 // ---------------------------------------------------------------------------
 // Linear(Cin -> N) over `rows` rows with the K loop split nsplit ways into parts [nsplit][rows][N], then the
-// fixed-order reduce into out (finish: dz_launch_splitk_finish's mode — 0 plain, 1 L2-normalised, 2 ReLU)
+// fixed-order reduce into out (finish: dz_launch_splitk_finish's mode — 0 plain, 1 L2-normalised, 2 ReLU).  wave_mom /
+// rows_per_x: the finish writes NaN rows for the chunks (rows_per_x rows each) whose wave moments are not finite; the
+// brackets count chunks.  finish_tag: the finish launch's own tag (default: the GEMM's).
+constexpr int DZ_TAG_OF_GEMM = -2;
 inline int dz_splitk_linear(const dz_layer& L, const float* X, int rows, int Cin, int Kpad, int N, int nsplit,
-                            float* parts, int finish, float* out, hipStream_t st, int tag = -1) {
+                            float* parts, int finish, float* out, hipStream_t st, int tag = -1,
+                            int finish_tag = DZ_TAG_OF_GEMM, const float* wave_mom = nullptr, int rows_per_x = 1) {
     const long long ysplit = (long long)rows * N;
     if (int rc = DzGemm::dense(L, X, Cin, rows, Cin, parts, N, N, DZ_EPI_BIAS).padded(Kpad, N).splitk(nsplit, ysplit)
-                     .prof(tag, rows).run(st))
+                     .prof(tag, rows / rows_per_x).run(st))
         return rc;
-    DzProfScope ps(tag, rows);
-    return dz_launch_splitk_finish(parts, nsplit, ysplit, rows, N, finish, out, st);
+    DzProfScope ps(finish_tag == DZ_TAG_OF_GEMM ? tag : finish_tag, rows / rows_per_x);
+    return dz_launch_splitk_finish(parts, nsplit, ysplit, rows, N, finish, out, st, wave_mom, rows_per_x);
 }
 
 // speechbrain Fbank up to the mel energies: the STFT of N rows of `sig` (lstride apart, hop 160, window 400) as one

@@ -235,7 +235,7 @@ convgemm("tdnn2", B, 289, 512, 512, 3, 2, _lib.EPI_TDNN)
 convgemm("tdnn3", B, 285, 512, 512, 3, 3, _lib.EPI_TDNN)
 convgemm("tdnn4", B, 279, 512, 512, 1, 1, _lib.EPI_TDNN)
 convgemm("tdnn5", B, 279, 512, 1500, 1, 1, _lib.EPI_TDNN, Npad=1536)
-# the pipeline runs tdnn2..5 FLATTENED over all B * P rows (api.hip emb_frames): the form the exact-f32 kernels see
+# the pipeline runs tdnn2..5 FLATTENED over all B * P rows (xvec_api.hip emb_frames): the form the exact-f32 kernels see
 convgemm("tdnn2_flat", 1, B * 293, 512, 512, 3, 2, _lib.EPI_TDNN)
 convgemm("tdnn5_flat", 1, B * 293, 512, 1500, 1, 1, _lib.EPI_TDNN, Npad=1536)
 convgemm("emb_linear", 1, B * 3, 3008, 512, 1, 1, _lib.EPI_BIAS, ksplit=16)
