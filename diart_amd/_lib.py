@@ -84,6 +84,20 @@ class TtnWeights(C.Structure):
                 ("frame_pad", C.c_int), ("frame_nfft", C.c_int), ("min_num_samples", C.c_int)]
 
 
+class SbrBlock(C.Structure):
+    _fields_ = [("conv", WspConv * 3), ("se_w1t", vp), ("se_b1", vp), ("se_w2t", vp), ("se_b2", vp),
+                ("width", C.c_int), ("se_width", C.c_int), ("stride", C.c_int), ("layer", C.c_int)]
+
+
+SBR_MAX_BLOCKS = 32
+
+
+class SbrWeights(C.Structure):
+    _fields_ = [("dft", vp), ("dft_split", vp), ("mel", vp), ("stem_w", vp), ("stem_b", vp),
+                ("block", SbrBlock * SBR_MAX_BLOCKS), ("att1", Layer), ("att2", Layer), ("fc", Layer), ("zeros", vp),
+                ("n_blocks", C.c_int), ("stem_width", C.c_int), ("min_num_samples", C.c_int), ("rows_per_pass", C.c_int)]
+
+
 # name -> (restype, argtypes); must list every function of include/diart_amd.h
 SIGNATURES = {
     "dz_last_error": (C.c_char_p, []),
@@ -135,6 +149,12 @@ SIGNATURES = {
     "dz_ttn_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_ttn_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_ttn_destroy": (C.c_int, [vp]),
+    "dz_sbr_abi_size": (C.c_int, []),
+    "dz_sbr_create": (C.c_int, [vp, C.POINTER(SbrWeights), C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_sbr_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_sbr_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_sbr_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "dz_sbr_destroy": (C.c_int, [vp]),
     "dz_wsp_abi_size": (C.c_int, []),
     "dz_wsp_frames_for": (C.c_int, [C.c_int, C.c_int]),
     "dz_wsp_create": (C.c_int, [vp, C.POINTER(WspWeights), C.c_int, C.c_int, C.POINTER(vp)]),
@@ -219,6 +239,11 @@ SIGNATURES = {
     "dz_k_powerset": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_k_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, vp]),
+    "dz_k_conv2d_masked": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, vp]),
+    "dz_k_sbr_se_gate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dz_k_sbr_se_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "dz_k_sbr_att_pool": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "dz_k_ttn_depthwise": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
 }
 
@@ -283,7 +308,8 @@ def load() -> C.CDLL:
         if list(sizes) != mine:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
-        for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights), ("dz_ttn", TtnWeights)):
+        for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights), ("dz_ttn", TtnWeights),
+                             ("dz_sbr", SbrWeights)):
             size = getattr(lib, f"{name}_abi_size")()
             if size != C.sizeof(struct):
                 raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({name}_weights) "

@@ -612,6 +612,9 @@ int dz_launch_sb_stats_pool(const float* x, int T, int C, int ldx, int rows, con
 // taps 9 = 3x3 with zero padding 1, taps 1 = 1x1 without padding; stride 1 or 2.  W [Cout][taps Cin] with
 // k = (kh 3 + kw) Cin + c (exact-f32 MFMA), or Wsplit = its (hi, lo * 2^11) f16 planes [2][Cout][taps Cin]
 // (split-f16 MFMA, used whenever it is set).  Epilogue: + bias[n], + R[m][n] when R is set, ReLU when relu.
+// ext (device, [B]; NULL: every row is whole): the masked instances — row b is live for its first ext[b] <= Fo steps
+// of the F axis, every output at or past them is stored as exactly 0.0 (and X holds zeros at or past the row's
+// input extent, which the im2col load then reads as the row's own zero padding).
 struct DzConv2d {
     const float* X;
     const float* W;
@@ -621,8 +624,34 @@ struct DzConv2d {
     float* Y;
     int B, Fi, Ti, Cin, Fo, To, Cout, taps, stride, relu;
     int* oflag;
+    const int* ext;
 };
 int dz_launch_conv2d(const DzConv2d& p, hipStream_t st);
+
+// k_sb_resnet.hip -----------------------------------------------------------
+// The speechbrain ResNet's activations are channels-last [row][t][f][c] with Tb time steps per row in the buffer, of
+// which the first ext[row] are live and the rest hold zeros.  No reduction order depends on the batch or on a row's place.
+enum { DZ_SBR_SE_SLICES = 16 };
+// the rows' live steps at the stem and after each of the four layers: tdev [rows] -> ext [5][rows], ext[0] = tdev,
+// ext[l + 1] = (ext[l] - 1) / stride[l] + 1
+int dz_launch_sbr_extents(const int* tdev, int rows, int s0, int s1, int s2, int s3, int* ext, hipStream_t st);
+// the stem: feats [rows][Tb][F] -> y [rows][Tb][F][C], Conv2d(1, C, 3, pad 1) with folded BatchNorm (w [C][9], k = kt 3 +
+// kf; b [C]) -> ReLU, zero padded at ext[row] steps, exact f32 FMAs in tap order; C % 4 == 0
+int dz_launch_sbr_stem(const float* feats, int rows, int Tb, int F, int C, const float* w, const float* b,
+                       const int* ext, float* y, hipStream_t st);
+// sums over the ext[row] F live positions of y [rows][Tb][F][C] in DZ_SBR_SE_SLICES slices -> part [rows][slices][C]
+int dz_launch_sbr_se_sum(const float* y, int rows, int Tb, int F, int C, const int* ext, float* part, hipStream_t st);
+// mean = (slices in order) / (ext F) -> ReLU(w1 mean + b1) -> sigmoid(w2 h + b2) -> gate [rows][C];
+// w1t [C][Cr] and w2t [Cr][C] are the two Linear weights transposed; C, Cr <= 1024
+int dz_launch_sbr_se_fc(const float* part, int rows, int F, int C, int Cr, const int* ext, const float* w1t,
+                        const float* b1, const float* w2t, const float* b2, float* gate, hipStream_t st);
+// out = ReLU(gate[row][c] y + r) at the live positions, 0 elsewhere (out may be y)
+int dz_launch_sbr_se_apply(const float* y, const float* gate, const float* r, int rows, int Tb, int F, int C,
+                           const int* ext, float* out, hipStream_t st);
+// attention pooling over x / logits [rows][Tb][C] (ldl floats per logits frame): softmax over the row's ext[row] frames
+// per channel, mu = sum x w, sg = sqrt(max(sum x^2 w - mu^2, 1e-5)) -> pooled [rows][2 C] = mu | sg
+int dz_launch_sbr_att_pool(const float* x, const float* logits, int ldl, int rows, int Tb, int C, const int* ext,
+                           float* pooled, hipStream_t st);
 
 // k_wespeaker.hip -----------------------------------------------------------
 // kaldi fbank of N rows (T frames of 400 samples, hop 160) -> raw log-mel [N][80][T]; bad[row] = 1 when a sample a

@@ -194,6 +194,22 @@ extern "C" int dz_k_conv2d(dz_ctx* ctx, const float* d_x, const float* d_w, cons
     return dz_launch_conv2d(p, (hipStream_t)stream);
 }
 
+// the same with a row's live steps of the f axis (the masked instances; sbr_api.hip runs the trunk on them)
+extern "C" int dz_k_conv2d_masked(dz_ctx* ctx, const float* d_x, const float* d_w, const void* d_wsplit,
+                                  const float* d_bias, const float* d_r, const int* d_ext, float* d_y, int batch, int fi,
+                                  int ti, int cin, int cout, int taps, int stride, int relu, void* stream) {
+    DZ_REQUIRE(ctx != nullptr && d_ext != nullptr, "dz_k_conv2d_masked: NULL context or extents");
+    DZ_HIP(hipSetDevice(ctx->device));
+    DzRangeScope range_scope(ctx->oflag_dev);
+    DzConv2d p;
+    memset(&p, 0, sizeof(p));
+    p.X = d_x; p.W = d_w; p.Wsplit = d_wsplit; p.bias = d_bias; p.R = d_r; p.Y = d_y; p.ext = d_ext;
+    p.B = batch; p.Fi = fi; p.Ti = ti; p.Cin = cin; p.Cout = cout; p.taps = taps; p.stride = stride; p.relu = relu;
+    p.Fo = stride >= 1 ? (fi - 1) / stride + 1 : 0;
+    p.To = stride >= 1 ? (ti - 1) / stride + 1 : 0;
+    return dz_launch_conv2d(p, (hipStream_t)stream);
+}
+
 extern "C" int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames) {
     DZ_REQUIRE(m && d_ptr && count, "dz_wsp_peek: NULL argument");
     const long long N = m->lastN;

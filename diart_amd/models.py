@@ -29,8 +29,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .weights import (PackedEcapa, PackedEmbedding, PackedSbXvector, PackedSegmentation, PackedTitaNet, PackedWeSpeaker,
-                      TITANET_MARKERS, TITANET_MIN_NUM_SAMPLES)
+from .weights import (PackedEcapa, PackedEmbedding, PackedSbResNet, PackedSbXvector, PackedSegmentation, PackedTitaNet, PackedWeSpeaker,
+                      SB_RESNET_MARKERS, SB_RESNET_MIN_NUM_SAMPLES, SB_RESNET_STRIDES, TITANET_MARKERS,
+                      TITANET_MIN_NUM_SAMPLES)
 
 StateSource = Union[str, Path, Dict[str, torch.Tensor]]
 
@@ -517,6 +518,38 @@ class HipTitaNetEmbedding(_HipGroupsEmbedding):
         return int(_lib.load().dz_ttn_frames_for(int(num_samples)))
 
 
+SB_RESNET_OPTIONS = ("strides", "min_num_samples", "rows_per_pass")
+
+
+class HipSbResNetEmbedding(_HipGroupsEmbedding):
+    """speechbrain's ResNet (speechbrain/spkrec-resnet-voxceleb) behind pyannote's ``PretrainedSpeakerEmbedding``
+    contract, the wrapper the reference falls back to for it (models.py:59): ``(waveform (N,1,S), masks (N,F) |
+    None) -> (N,256)``, not normalised; a row whose mask keeps fewer than ``min_num_samples`` samples, or whose kept
+    samples hold a NaN, is NaN.  ECAPA's front end and batch geometry, a 2-D squeeze-excitation ResNet over every frame
+    of the padded batch, attentive statistics pooling.  The same call shape as ``HipEcapaEmbedding``,
+    so the same engine forms take it; masks select samples, so ``repeated_rows="share"`` is refused.  ``strides``: the
+    four layers' (not visible in the checkpoint's shapes); ``rows_per_pass``: rows the trunk runs over at a time (0:
+    the library's default, 16; a handle's arena grows with it, no result depends on it)."""
+
+    dimension = 256
+    _c, _packer, _int32_peeks = "dz_sbr", PackedSbResNet, frozenset((7, 8, 9))
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None, strides=SB_RESNET_STRIDES,
+                 min_num_samples: int = SB_RESNET_MIN_NUM_SAMPLES, rows_per_pass: int = 0):
+        super().__init__(state, max_batch, precision, repeated_rows)
+        self.strides = tuple(int(s) for s in strides)
+        self.min_num_samples, self.rows_per_pass = int(min_num_samples), int(rows_per_pass)
+
+    def _extra_state(self):
+        return dict(super()._extra_state(), strides=self.strides, min_num_samples=self.min_num_samples,
+                    rows_per_pass=self.rows_per_pass)
+
+    def _pack(self, device):
+        return PackedSbResNet(self._state, device, precision=self.precision, strides=self.strides,
+                              min_num_samples=self.min_num_samples, rows_per_pass=self.rows_per_pass)
+
+
 class HipWeSpeakerEmbedding(_HipTrunkEmbedding):
     """pyannote.audio 3.1's ``WeSpeakerResNet34`` (pyannote/wespeaker-voxceleb-resnet34-LM): ``(waveform (N,1,S),
     weights (N,Fw) | None) -> (N,256)`` — the callable the reference loads through ``PyannoteLoader`` (models.py:42-59)
@@ -573,17 +606,19 @@ class SegmentationLoader:
 
 class EmbeddingLoader:
     """``arch``: "xvector" (pyannote/embedding), "ecapa" (speechbrain/spkrec-ecapa-voxceleb), "wespeaker"
-    (pyannote/wespeaker-voxceleb-resnet34-LM), "sb-xvector" (speechbrain/spkrec-xvect-voxceleb) or "titanet"
-    (nvidia/speakerverification_en_titanet_large, a ``.nemo`` archive); None = decide from the checkpoint keys
-    (``encoder.encoder.0.mconv.0.conv.weight`` + ``decoder.emb_layers.0.1.weight``: titanet, ``resnet.``: wespeaker,
-    ``asp.``: ecapa, speechbrain ``Xvector`` keys ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector,
-    otherwise xvector)."""
+    (pyannote/wespeaker-voxceleb-resnet34-LM), "sb-xvector" (speechbrain/spkrec-xvect-voxceleb), "sb-resnet"
+    (speechbrain/spkrec-resnet-voxceleb) or "titanet" (nvidia/speakerverification_en_titanet_large, a ``.nemo``
+    archive); None = decide from the checkpoint keys (``encoder.encoder.0.mconv.0.conv.weight`` +
+    ``decoder.emb_layers.0.1.weight``: titanet, ``resnet.``: wespeaker, ``asp.``: ecapa, speechbrain ``Xvector`` keys
+    ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector, speechbrain ``ResNet`` keys
+    ``layer1.0.se.fc.0.weight`` + ``fc_embed.weight``: sb-resnet, otherwise xvector)."""
 
     def __init__(self, state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
                  precision: Optional[str] = None, weight_interp: Optional[str] = None,
                  repeated_rows: Optional[str] = None, **arch_options):
         """``arch_options`` (titanet only): ``pad_mode``, ``frame_count``, ``min_num_samples``, ``attention_order`` of
         ``HipTitaNetEmbedding`` — the switches DESIGN.md 4.12 marks (R); they override what the archive's yaml records.
+        ``arch_options`` (sb-resnet only): ``strides``, ``min_num_samples``, ``rows_per_pass`` of ``HipSbResNetEmbedding``.
         ``weight_interp`` (x-vector only): "linear" | "nearest" | None = from the ``pyannote.audio`` version the
         checkpoint file records (>= 3.1: "nearest"; older, absent, or a plain state dict: "linear").
         ``repeated_rows``: "each" | "share" (``repeated_rows_mode``: the reference-shaped ``(batch spk)`` call runs the
@@ -593,9 +628,10 @@ class EmbeddingLoader:
         self.state, self.max_batch, self.arch, self.precision = state, max_batch, arch, precision
         self.weight_interp = weight_interp
         self.repeated_rows = repeated_rows
-        unknown = set(arch_options) - set(TITANET_OPTIONS)
+        unknown = set(arch_options) - set(TITANET_OPTIONS) - set(SB_RESNET_OPTIONS)
         if unknown:
-            raise TypeError(f"EmbeddingLoader: unknown option(s) {sorted(unknown)} (titanet takes {TITANET_OPTIONS})")
+            raise TypeError(f"EmbeddingLoader: unknown option(s) {sorted(unknown)} (titanet takes {TITANET_OPTIONS}, "
+                            f"sb-resnet {SB_RESNET_OPTIONS})")
         self.arch_options = arch_options
 
     def __call__(self):
@@ -607,7 +643,18 @@ class EmbeddingLoader:
             arch = "sb-xvector"     # (the pyannote x-vector packer has no ``blocks.`` keys: this state failed there)
         if self.arch is None and all(k in sd for k in TITANET_MARKERS):
             arch = "titanet"
+        if arch == "xvector" and self.arch is None and all(k in sd for k in SB_RESNET_MARKERS):
+            arch = "sb-resnet"      # (the pyannote x-vector packer has no ``layer1.`` keys: this state failed there)
+        if arch == "sb-resnet":
+            other = sorted(set(self.arch_options) - set(SB_RESNET_OPTIONS))
+            if other:
+                raise TypeError(f"EmbeddingLoader: {other} are options of the titanet architecture, this state is {arch!r}")
+            return HipSbResNetEmbedding(sd, self.max_batch, self.precision, self.repeated_rows, **self.arch_options)
         if arch == "titanet":
+            other = sorted(set(self.arch_options) - set(TITANET_OPTIONS))
+            if other:
+                raise TypeError(f"EmbeddingLoader: {other} are options of the sb-resnet architecture, this state is "
+                                f"{arch!r}")
             # the front-end switches a .nemo archive's model_config.yaml records (checkpoint.nemo_frontend)
             kw = {}
             if not isinstance(self.state, dict):
@@ -616,8 +663,8 @@ class EmbeddingLoader:
             kw.update(self.arch_options)
             return HipTitaNetEmbedding(sd, self.max_batch, self.precision, self.repeated_rows, **kw)
         if self.arch_options:
-            raise TypeError(f"EmbeddingLoader: {sorted(self.arch_options)} are options of the titanet architecture, "
-                            f"this state is {arch!r}")
+            raise TypeError(f"EmbeddingLoader: {sorted(self.arch_options)} are options of the titanet or sb-resnet "
+                            f"architecture, this state is {arch!r}")
         if arch == "sb-xvector":
             return HipSbXvectorEmbedding(sd, self.max_batch, self.precision, self.repeated_rows)
         if arch == "wespeaker":
@@ -726,7 +773,7 @@ class EmbeddingModel(LazyModel):
 
     @staticmethod
     def from_pretrained(model, use_hf_token=True, repeated_rows: Optional[str] = None, **arch_options) -> "EmbeddingModel":
-        """``arch_options``: the (R) switches of a TitaNet model (``EmbeddingLoader``)."""
+        """``arch_options``: the (R) switches of a TitaNet or speechbrain ResNet model (``EmbeddingLoader``)."""
         if isinstance(model, (str, Path)) and Path(model).name.endswith(".onnx"):
             return EmbeddingModel.from_onnx(model)
         if isinstance(model, dict):

@@ -307,6 +307,58 @@ def synth_wespeaker_state(seed: int = 4242, embed_dim: int = 256) -> Dict[str, t
     return sd
 
 
+def synth_sb_resnet_state(channels=(128, 128, 256, 256), block_sizes=(3, 4, 6, 3), seed: int = 5150, strides=(1, 2, 2, 2),
+                          se_reduction: int = 1, lin_neurons: int = 256) -> Dict[str, torch.Tensor]:
+    """Random-init weights of speechbrain's ``ResNet`` (spkrec-resnet-voxceleb geometry by default: 80 mel bins, widths
+    128 / 128 / 256 / 256, SEBasicBlocks 3 / 4 / 6 / 3), keyed like its ``embedding_model.ckpt`` (``conv1.weight``,
+    ``layer2.0.downsample.1.running_var``, ``layer1.0.se.fc.0.weight``, ``attention.3.weight``, ``fc_embed.weight``).
+    BatchNorm statistics are not the identity, so the folding is exercised; the second convolution of every block is
+    scaled down so the residual stream stays O(1)."""
+    from .weights import sb_resnet_key as k
+    g = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(key, cin, cout, ks, gain=1.0):
+        sd[key + ".weight"] = _u(g, (cout, cin, ks, ks), gain * math.sqrt(6.0 / (cin * ks * ks)))
+
+    def lin(key, cin, cout, gain=1.0, shape=None):
+        sd[key + ".weight"] = _u(g, shape or (cout, cin), gain * math.sqrt(6.0 / cin))
+        sd[key + ".bias"] = _u(g, (cout,), 0.1)
+
+    def bn(prefix, n):
+        sd[prefix + ".weight"] = 1.0 + 0.2 * _u(g, (n,), 1.0)
+        sd[prefix + ".bias"] = 0.1 * _u(g, (n,), 1.0)
+        sd[prefix + ".running_mean"] = 0.2 * _u(g, (n,), 1.0)
+        sd[prefix + ".running_var"] = 0.5 + torch.rand((n,), generator=g)
+        sd[prefix + ".num_batches_tracked"] = torch.tensor(1000)
+
+    conv(k("stem"), 1, channels[0], 3, gain=0.1)            # the input is log-mel in dB (tens of units)
+    sd[k("stem") + ".bias"] = _u(g, (channels[0],), 0.1)
+    bn(k("stem_bn"), channels[0])
+    cin, f = channels[0], 80
+    for L, (c, nb, stride) in enumerate(zip(channels, block_sizes, strides), start=1):
+        for i in range(nb):
+            conv(k("conv1", L, i), cin, c, 3, gain=0.8)
+            bn(k("bn1", L, i), c)
+            conv(k("conv2", L, i), c, c, 3, gain=0.3)
+            bn(k("bn2", L, i), c)
+            lin(k("se1", L, i), c, c // se_reduction)
+            lin(k("se2", L, i), c // se_reduction, c)
+            if i == 0 and (stride != 1 or cin != c):
+                conv(k("down", L, i), cin, c, 1, gain=0.8)
+                bn(k("down_bn", L, i), c)
+            cin = c
+        f = (f - 1) // stride + 1
+    cf = cin * f
+    lin(k("att1"), cf, 128, gain=0.5, shape=(128, cf, 1))
+    bn(k("att_bn"), 128)
+    lin(k("att2"), 128, cf, gain=1.5, shape=(cf, 128, 1))
+    bn(k("norm_stats"), 2 * cf)
+    lin(k("fc"), 2 * cf, lin_neurons)
+    bn(k("norm_embed"), lin_neurons)
+    return sd
+
+
 def synth_titanet_state(seed: int = 9091) -> Dict[str, torch.Tensor]:
     """Random-init weights of NeMo's TitaNet-L (titanet-large geometry: 80 mel bins, separable blocks of 1024 channels
     with kernels 3 / 7 / 11 / 15 / 1, epilog 3072, attentive pooling, 192-d embedding), keyed like the ``.nemo``

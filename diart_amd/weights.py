@@ -660,6 +660,202 @@ class PackedWeSpeaker:
 
 
 # --------------------------------------------------------------------------- #
+# speechbrain ResNet (speechbrain/spkrec-resnet-voxceleb)
+# --------------------------------------------------------------------------- #
+# module prefixes of speechbrain.lobes.models.ResNet.ResNet's state dict
+SB_RESNET_KEYS = {
+    "stem": "conv1", "stem_bn": "bn1",
+    "conv1": "layer{L}.{i}.conv1", "bn1": "layer{L}.{i}.bn1", "conv2": "layer{L}.{i}.conv2", "bn2": "layer{L}.{i}.bn2",
+    "se1": "layer{L}.{i}.se.fc.0", "se2": "layer{L}.{i}.se.fc.2",
+    "down": "layer{L}.{i}.downsample.0", "down_bn": "layer{L}.{i}.downsample.1",
+    "att1": "attention.0", "att_bn": "attention.2", "att2": "attention.3",
+    "norm_stats": "norm_stats", "fc": "fc_embed", "norm_embed": "norm_embed",
+}
+# what the loader recognises the state by
+SB_RESNET_MARKERS = ("layer1.0.se.fc.0.weight", "fc_embed.weight")
+SB_RESNET_STRIDES = (1, 2, 2, 2)        # hyperparams.yaml; not visible in the shapes where the width changes too
+SB_RESNET_MIN_NUM_SAMPLES = 3           # what pyannote's bisection over [2, 8000] ends at when every length is accepted
+SB_RESNET_MAX_BLOCKS = _lib.SBR_MAX_BLOCKS
+_BN = ("weight", "bias", "running_mean", "running_var")
+
+
+def sb_resnet_key(kind: str, L: int = 0, i: int = 0) -> str:
+    return SB_RESNET_KEYS[kind].format(L=L, i=i)
+
+
+def sb_resnet_shape(sd: Dict[str, torch.Tensor], strides=SB_RESNET_STRIDES) -> dict:
+    """Widths, blocks per layer and squeeze-excitation widths read from the shapes of a speechbrain ResNet state;
+    every tensor the packer reads is checked against them and a mismatch is refused by its key."""
+    def need(key, shape):
+        if key not in sd:
+            raise ValueError(f"{key}: missing from the state (speechbrain ResNet)")
+        got = tuple(sd[key].shape)
+        if got != tuple(shape) and not (len(got) == len(shape) + 1 and got[-1] == 1 and got[:-1] == tuple(shape)):
+            raise ValueError(f"{key}: shape {got}, expected {tuple(shape)}")
+
+    def need_bn(prefix, n):
+        for f in _BN:
+            need(f"{prefix}.{f}", (n,))
+
+    def gemm_width(key, c):
+        if c not in (32, 64) and c % 128:
+            raise ValueError(f"{key}: {c} channels; the 2-D convolution kernels take 32, 64 or a multiple of 128")
+        if c > 1024:
+            raise ValueError(f"{key}: {c} channels; the squeeze-excitation kernels take at most 1024")
+
+    if len(strides) != 4 or any(s not in (1, 2) for s in strides):
+        raise ValueError(f"strides={strides!r}: four strides of 1 or 2")
+    k = sb_resnet_key
+    if k("stem") + ".weight" not in sd:
+        raise ValueError(f"{k('stem')}.weight: missing from the state (speechbrain ResNet)")
+    c0 = int(sd[k("stem") + ".weight"].shape[0])
+    need(k("stem") + ".weight", (c0, 1, 3, 3)); need(k("stem") + ".bias", (c0,)); need_bn(k("stem_bn"), c0)
+    gemm_width(k("stem") + ".weight", c0)
+    cin, f, widths, blocks, se = c0, 80, [], [], []
+    for L in range(1, 5):
+        n = 0
+        while k("conv1", L, n) + ".weight" in sd:
+            n += 1
+        if n == 0:
+            raise ValueError(f"{k('conv1', L, 0)}.weight: missing from the state (speechbrain ResNet)")
+        c = int(sd[k("conv1", L, 0) + ".weight"].shape[0])
+        gemm_width(k("conv1", L, 0) + ".weight", c)
+        se.append([])
+        for i in range(n):
+            stride = strides[L - 1] if i == 0 else 1
+            need(k("conv1", L, i) + ".weight", (c, cin, 3, 3)); need_bn(k("bn1", L, i), c)
+            need(k("conv2", L, i) + ".weight", (c, c, 3, 3)); need_bn(k("bn2", L, i), c)
+            if k("se1", L, i) + ".weight" not in sd:
+                raise ValueError(f"{k('se1', L, i)}.weight: missing from the state (speechbrain ResNet)")
+            cr = int(sd[k("se1", L, i) + ".weight"].shape[0])
+            need(k("se1", L, i) + ".weight", (cr, c))
+            if not 1 <= cr <= 1024:
+                raise ValueError(f"{k('se1', L, i)}.weight: {cr} rows; the squeeze-excitation kernels take 1 .. 1024")
+            need(k("se1", L, i) + ".bias", (cr,)); need(k("se2", L, i) + ".weight", (c, cr)); need(k("se2", L, i) + ".bias", (c,))
+            has_down = k("down", L, i) + ".weight" in sd
+            if (stride != 1 or cin != c) and not has_down:
+                raise ValueError(f"{k('down', L, i)}.weight: missing, but the block has stride {stride} and widths {cin} -> {c}")
+            if has_down:
+                need(k("down", L, i) + ".weight", (c, cin, 1, 1)); need_bn(k("down_bn", L, i), c)
+            se[-1].append(cr)
+            cin = c
+        f = (f - 1) // strides[L - 1] + 1
+        widths.append(c); blocks.append(n)
+    if sum(blocks) > SB_RESNET_MAX_BLOCKS:
+        raise ValueError(f"{sum(blocks)} blocks; dz_sbr_weights holds {SB_RESNET_MAX_BLOCKS}")
+    cf = f * cin
+    need(k("att1") + ".weight", (128, cf)); need(k("att1") + ".bias", (128,)); need_bn(k("att_bn"), 128)
+    need(k("att2") + ".weight", (cf, 128)); need(k("att2") + ".bias", (cf,))
+    need_bn(k("norm_stats"), 2 * cf)
+    need(k("fc") + ".weight", (256, 2 * cf)); need(k("fc") + ".bias", (256,)); need_bn(k("norm_embed"), 256)
+    return {"stem": c0, "channels": tuple(widths), "block_sizes": tuple(blocks), "se": se, "strides": tuple(strides),
+            "freq": f, "pooled": cf}
+
+
+def sb_resnet_fold(sd: Dict[str, torch.Tensor], strides=SB_RESNET_STRIDES, dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    """Every matrix ``PackedSbResNet`` hands to the kernels, folded in ``dtype`` (the packer: float64, rounded once):
+    ``stem.w|b`` ((C0, 9), k = kt 3 + kf), ``b{n}.conv1|conv2|down.w|b`` (``wsp_conv_matrix`` layout, time = kh),
+    ``b{n}.se.w1t|b1|w2t|b2``, ``att1.w|b|s|h``, ``att2.w|b``, ``fc.w|b``.  The head's 2560 channels are re-ordered from
+    speechbrain's c F4 + f (``transpose(2, 3).flatten(1, 2)``) to the activations' f C4 + c."""
+    shape = sb_resnet_shape(sd, strides)
+    g = lambda key: sd[key].detach().cpu().to(dtype)
+    bnd = lambda p: {n: g(f"{p}.{n}") for n in _BN}
+    k = sb_resnet_key
+    out: Dict[str, torch.Tensor] = {}
+    bn = bnd(k("stem_bn"))
+    scale = bn["weight"] / torch.sqrt(bn["running_var"] + BN_EPS)
+    out["stem.w"] = (g(k("stem") + ".weight") * scale[:, None, None, None]).reshape(shape["stem"], 9).contiguous()
+    out["stem.b"] = (g(k("stem") + ".bias") - bn["running_mean"]) * scale + bn["bias"]
+    n = 0
+    for L, nb in enumerate(shape["block_sizes"], start=1):
+        for i in range(nb):
+            for name, conv, norm in (("conv1", "conv1", "bn1"), ("conv2", "conv2", "bn2"), ("down", "down", "down_bn")):
+                if k(conv, L, i) + ".weight" in sd:
+                    fw, fb = fold_conv_bn(g(k(conv, L, i) + ".weight"), bnd(k(norm, L, i)))
+                    out[f"b{n}.{name}.w"], out[f"b{n}.{name}.b"] = wsp_conv_matrix(fw), fb
+            out[f"b{n}.se.w1t"] = g(k("se1", L, i) + ".weight").t().contiguous()
+            out[f"b{n}.se.b1"] = g(k("se1", L, i) + ".bias")
+            out[f"b{n}.se.w2t"] = g(k("se2", L, i) + ".weight").t().contiguous()
+            out[f"b{n}.se.b2"] = g(k("se2", L, i) + ".bias")
+            n += 1
+    c4, f4, cf = shape["channels"][3], shape["freq"], shape["pooled"]
+    perm = (torch.arange(c4)[None, :] * f4 + torch.arange(f4)[:, None]).reshape(-1)        # [f C4 + c] = c F4 + f
+    bn = bnd(k("att_bn"))
+    out["att1.w"] = g(k("att1") + ".weight").reshape(128, cf)[:, perm].contiguous()
+    out["att1.b"] = g(k("att1") + ".bias")
+    out["att1.s"] = bn["weight"] / torch.sqrt(bn["running_var"] + BN_EPS)
+    out["att1.h"] = bn["bias"] - bn["running_mean"] * out["att1.s"]
+    out["att2.w"] = g(k("att2") + ".weight").reshape(cf, 128)[perm].contiguous()
+    out["att2.b"] = g(k("att2") + ".bias")[perm].contiguous()
+    bs, be = bnd(k("norm_stats")), bnd(k("norm_embed"))
+    ss = bs["weight"] / torch.sqrt(bs["running_var"] + BN_EPS)
+    sh = bs["bias"] - bs["running_mean"] * ss
+    se = be["weight"] / torch.sqrt(be["running_var"] + BN_EPS)
+    he = be["bias"] - be["running_mean"] * se
+    fw, fb = g(k("fc") + ".weight"), g(k("fc") + ".bias")
+    perm2 = torch.cat([perm, cf + perm])
+    out["fc.w"] = (se[:, None] * fw * ss[None, :])[:, perm2].contiguous()
+    out["fc.b"] = se * (fw @ sh + fb) + he
+    return out
+
+
+class PackedSbResNet:
+    """``dz_sbr_weights`` + the tensors behind it (speechbrain ``ResNet`` checkpoint keys, ``SB_RESNET_KEYS``).
+
+    * the Fbank is ECAPA's (windowed DFT as one GEMM operand, 80-bin mel bank);
+    * every BatchNorm (eval, eps 1e-5) is folded in float64 (``sb_resnet_fold``): into the convolution before it, into
+      scale / shift after attention.0's ReLU, and ``norm_stats`` / ``norm_embed`` into ``fc_embed``;
+    * widths, blocks per layer and the squeeze-excitation reduction come from the shapes (``sb_resnet_shape``);
+      ``strides``, ``min_num_samples`` and ``rows_per_pass`` (0: the library's default) are the caller's;
+    * for "f16x3" the DFT, the 3x3 / 1x1 convolutions and the two attention convolutions also as split-f16 planes."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], device: torch.device, precision: str = "f32",
+                 strides=SB_RESNET_STRIDES, min_num_samples: int = SB_RESNET_MIN_NUM_SAMPLES, rows_per_pass: int = 0):
+        assert precision in PRECISIONS, precision
+        if int(min_num_samples) < 1 or int(rows_per_pass) < 0:
+            raise ValueError(f"min_num_samples={min_num_samples!r}, rows_per_pass={rows_per_pass!r}")
+        split = precision == "f16x3"
+        pk = _Packed(device)
+        self.shape = shape = sb_resnet_shape(sd, strides)
+        f = sb_resnet_fold(sd, strides, torch.float64)
+        w = _lib.SbrWeights()
+        w.dft = pk.put(_pad2(dft_matrices().float(), 448, 416))
+        if split:
+            w.dft_split = pk.put_split(_pad2(dft_matrices().float(), 512, 416), "windowed DFT")
+        w.mel = pk.put(_pad2(ecapa_mel_filterbank().t().contiguous(), 128, 224))
+        w.stem_w, w.stem_b = pk.put(f["stem.w"]), pk.put(f["stem.b"])
+        n = 0
+        for L, nb in enumerate(shape["block_sizes"]):
+            for i in range(nb):
+                b = w.block[n]
+                for j, name in enumerate(("conv1", "conv2", "down")):
+                    if f"b{n}.{name}.w" in f:
+                        m = f[f"b{n}.{name}.w"].float()
+                        b.conv[j].w, b.conv[j].b = pk.put(m), pk.put(f[f"b{n}.{name}.b"])
+                        if split:
+                            b.conv[j].wsplit = pk.put_split(m, sb_resnet_key(name, L + 1, i))
+                b.se_w1t, b.se_b1 = pk.put(f[f"b{n}.se.w1t"]), pk.put(f[f"b{n}.se.b1"])
+                b.se_w2t, b.se_b2 = pk.put(f[f"b{n}.se.w2t"]), pk.put(f[f"b{n}.se.b2"])
+                b.width, b.se_width = shape["channels"][L], shape["se"][L][i]
+                b.stride, b.layer = (shape["strides"][L] if i == 0 else 1), L
+                n += 1
+        cf = shape["pooled"]
+        cfpad = (cf + 127) // 128 * 128
+        a1, a2 = f["att1.w"].float(), _pad2(f["att2.w"].float(), cfpad, 128)
+        w.att1.w, w.att1.b = pk.put(a1), pk.put(f["att1.b"])
+        w.att1.s, w.att1.h = pk.put(f["att1.s"]), pk.put(f["att1.h"])
+        w.att2.w, w.att2.b = pk.put(a2), pk.put(_pad1(f["att2.b"].float(), cfpad))
+        if split:
+            w.att1.wsplit = pk.put_split(a1, "attention.0")
+            w.att2.wsplit = pk.put_split(a2, "attention.3")
+        w.fc.w, w.fc.b = pk.put(f["fc.w"]), pk.put(f["fc.b"])
+        w.zeros = pk.put(torch.zeros(512))
+        w.n_blocks, w.stem_width = n, shape["stem"]
+        w.min_num_samples, w.rows_per_pass = int(min_num_samples), int(rows_per_pass)
+        self.struct, self.pack = w, pk
+
+
+# --------------------------------------------------------------------------- #
 # NeMo TitaNet-L
 # --------------------------------------------------------------------------- #
 # (repeats, kernel, C_in, C_out, residual) of encoder.encoder.{0..4} (titanet-large.yaml: prolog, three mega blocks, epilog)

@@ -451,6 +451,82 @@ int dz_ttn_destroy(dz_ttn* m);
 int dz_k_ttn_depthwise(dz_ctx* ctx, const float* d_x, int ldx, const float* d_taps, int taps, const int* d_frames,
                        int rows, int T, int C, int relu, float* d_y, void* d_planes, void* stream);
 
+/* ---- speechbrain ResNet speaker embedding (speechbrain/spkrec-resnet-voxceleb) behind pyannote's
+ * PretrainedSpeakerEmbedding contract, like ECAPA and the speechbrain x-vector: waveform (N,1,S), masks (N,Fw) or
+ * NULL -> (N,256), not normalised.  The mask selects samples (nearest resampling, > 0.5), rows are zero padded to the
+ * longest kept row of the call (of the group, for dz_sbr_forward_groups): T_g = 1 + lmax / 160 frames.  ECAPA's
+ * Fbank(80) + sentence mean -> Conv2d(1, C0, 3) + BatchNorm + ReLU -> four layers of SEBasicBlocks (3x3 convolutions
+ * with folded BatchNorm, squeeze-excitation over every position of the padded batch, both axes strided) ->
+ * attentive statistics pooling over the T4_g frames of the F4 C4 channels -> BatchNorm1d -> Linear -> BatchNorm1d
+ * (both folded into the Linear).  The network does not use the relative lengths: a row depends on its group through
+ * T_g only.  Activations are channels-last [row][t][f][c]; every buffer lays a row out with the handle's
+ * Tc = 1 + num_samples / 160 steps (halved, rounding up, per strided layer) and holds zeros at or past the row's own.
+ * Rows that keep fewer than min_num_samples samples, or whose kept samples hold a NaN / Inf, come back as NaN; a
+ * group whose longest row is that short is all NaN.  DESIGN.md 4.14.                                              */
+enum { DZ_SBR_MAX_BLOCKS = 32 };
+typedef struct {
+    dz_wsp_conv conv[3];    /* conv1 (3x3, stride), conv2 (3x3), downsample (1x1, stride; w NULL: identity), BatchNorm folded */
+    const float* se_w1t;    /* [C][Cr]  se.fc.0.weight transposed                                                    */
+    const float* se_b1;     /* [Cr]                                                                                  */
+    const float* se_w2t;    /* [Cr][C]  se.fc.2.weight transposed                                                    */
+    const float* se_b2;     /* [C]                                                                                   */
+    int width, se_width;    /* C, Cr                                                                                 */
+    int stride;             /* of conv1 and the downsample, on both axes                                             */
+    int layer;              /* 0 .. 3                                                                                */
+} dz_sbr_block;
+typedef struct {
+    const float* dft;       /* [448][416] hamming-windowed DFT (as dz_ecapa_weights)                                 */
+    const void* dft_split;  /* optional split-f16 planes [2][512][416] of dft                                        */
+    const float* mel;       /* [128][224] triangular mel bank, 80 mel rows (as dz_ecapa_weights)                     */
+    const float* stem_w;    /* [C0][9], k = kt * 3 + kf: conv1 x bn1 scale                                           */
+    const float* stem_b;    /* [C0]: (conv1.bias - running_mean) x scale + bn1.bias                                  */
+    dz_sbr_block block[DZ_SBR_MAX_BLOCKS];
+    dz_layer att1;          /* attention.0 [128][F4 C4] with the columns in this layout's order f C4 + c; s / h =
+                               attention.2 (BatchNorm after the ReLU); wsplit: optional row-major split-f16 planes   */
+    dz_layer att2;          /* attention.3 [Npad][128], rows f C4 + c, Npad = F4 C4 rounded up to 128                */
+    dz_layer fc;            /* [256][2 F4 C4]: norm_stats, fc_embed and norm_embed folded; columns mu | sg           */
+    const float* zeros;     /* [512] zeros (the bias of the DFT and mel layers)                                      */
+    int n_blocks;
+    int stem_width;         /* C0                                                                                    */
+    int min_num_samples;    /* >= 1                                                                                  */
+    int rows_per_pass;      /* the trunk runs over at most this many rows at a time (0: 32); no result depends on it */
+} dz_sbr_weights;
+typedef struct dz_sbr dz_sbr;
+int dz_sbr_abi_size(void);                    /* sizeof(dz_sbr_weights) */
+int dz_sbr_create(dz_ctx* ctx, const dz_sbr_weights* w, int max_rows, int num_samples, dz_sbr** out);
+/* n_rows rows as one group (pyannote's call), d_masks (n_rows, mask_frames) or NULL -> d_out (n_rows, 256).  The
+ * geometry is derived on the device: no synchronisation.                                                        */
+int dz_sbr_forward(dz_sbr* m, const float* d_wave, long long wave_stride, const float* d_masks, int n_rows,
+                   int mask_frames, float* d_out, void* stream);
+/* n_groups groups of rows_per_group (K) rows as dz_ecapa_forward_groups: row g*K + k reads waveform row g and mask
+ * row g*K + k -> d_out (G*K, 256); normalize = 1 L2-normalises every row.  A group's rows are bit-identical to
+ * dz_sbr_forward on those K rows alone.  No synchronisation, no allocation.  G*K <= max_rows.                  */
+int dz_sbr_forward_groups(dz_sbr* m, const float* d_wave, long long wave_stride, const float* d_masks,
+                          int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                          void* stream);
+/* intermediates of the LAST forward (parity tests); *frames receives the buffer's steps per row.  0 features
+ * (N,Tc,80)  6 pooled statistics (N, 2 F4 C4) = mu | sg  7 kept-sample counts (N) int32, -(count + 1) for a row
+ * with a NaN / Inf sample  8 the group's frame count T_g (N) int32 (0 for a group whose rows are all too short)
+ * 9 live steps (5,N) int32 at the stem and after layers 1 .. 4.  The trunk's buffers hold the rows of the last pass
+ * (all N rows when N <= rows_per_pass): 1 the stem (n,Tc,80,C0)  2 .. 5 layers 1 .. 4 (n,T_l,F_l,C_l).            */
+int dz_sbr_peek(dz_sbr* m, int which, const void** d_ptr, long long* count, int* frames);
+int dz_sbr_destroy(dz_sbr* m);
+/* dz_k_conv2d's masked instances (k_conv2d.hip; parity tests): d_ext [batch] int32, row b is live for its first
+ * d_ext[b] <= fo steps of the f axis; every output at or past them is stored as exactly 0.0.                     */
+int dz_k_conv2d_masked(dz_ctx* ctx, const float* d_x, const float* d_w, const void* d_wsplit, const float* d_bias,
+                       const float* d_r, const int* d_ext, float* d_y, int batch, int fi, int ti, int cin, int cout,
+                       int taps, int stride, int relu, void* stream);
+/* the kernels of k_sb_resnet.hip alone (parity tests), activations [rows][tb][f][c], d_ext [rows] int32 live steps:
+ * squeeze-excitation gate of d_y -> d_gate (rows, c) through d_part (rows, 16, c) scratch; d_out = ReLU(gate y + r)
+ * masked (d_out may be d_y); attention pooling of d_x / d_logits (rows, tb, c) -> d_pooled (rows, 2 c)           */
+int dz_k_sbr_se_gate(dz_ctx* ctx, const float* d_y, int rows, int tb, int f, int c, int cr, const int* d_ext,
+                     const float* d_w1t, const float* d_b1, const float* d_w2t, const float* d_b2, float* d_part,
+                     float* d_gate, void* stream);
+int dz_k_sbr_se_apply(dz_ctx* ctx, const float* d_y, const float* d_gate, const float* d_r, int rows, int tb, int f,
+                      int c, const int* d_ext, float* d_out, void* stream);
+int dz_k_sbr_att_pool(dz_ctx* ctx, const float* d_x, const float* d_logits, int rows, int tb, int c, const int* d_ext,
+                      float* d_pooled, void* stream);
+
 /* ---- band-limited resampling: torchaudio's sinc_interp_hann (lowpass_filter_width 6, rolloff 0.99), the filter
  * built in float64 and rounded to float32.  g = gcd(orig, new), o = orig / g, n = new / g, width =
  * ceil(6 o / (0.99 min(o, n))), T = 2 width + o taps per phase; output m = j n + i is sum_k h[i][k] x[j o - width + k]
