@@ -57,6 +57,10 @@ class EcapaWeights(C.Structure):
                 ("dft_split", vp)]
 
 
+class EcmWeights(C.Structure):
+    _fields_ = [("net", EcapaWeights), ("dft", vp), ("dft_split", vp), ("mel", vp), ("min_num_samples", C.c_int)]
+
+
 class WspConv(C.Structure):
     _fields_ = [("w", vp), ("b", vp), ("wsplit", vp)]
 
@@ -136,6 +140,13 @@ SIGNATURES = {
     "dz_ecapa_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_ecapa_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_ecapa_destroy": (C.c_int, [vp]),
+    "dz_ecm_abi_size": (C.c_int, []),
+    "dz_ecm_frames_for": (C.c_int, [C.c_int]),
+    "dz_ecm_create": (C.c_int, [vp, C.POINTER(EcmWeights), C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_ecm_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_ecm_forward_groups": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_ecm_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "dz_ecm_destroy": (C.c_int, [vp]),
     "dz_sbx_abi_size": (C.c_int, []),
     "dz_sbx_create": (C.c_int, [vp, C.POINTER(SbxWeights), C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_sbx_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),
@@ -309,7 +320,7 @@ def load() -> C.CDLL:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
         for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights), ("dz_ttn", TtnWeights),
-                             ("dz_sbr", SbrWeights)):
+                             ("dz_sbr", SbrWeights), ("dz_ecm", EcmWeights)):
             size = getattr(lib, f"{name}_abi_size")()
             if size != C.sizeof(struct):
                 raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({name}_weights) "

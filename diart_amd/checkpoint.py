@@ -29,7 +29,7 @@ import tempfile
 import zipfile
 from collections import OrderedDict
 from pathlib import Path
-from typing import Any, Dict, Union
+from typing import Any, Dict, Optional, Union
 
 import torch
 
@@ -361,3 +361,42 @@ def read_state(path: Union[str, Path]) -> Dict[str, torch.Tensor]:
         state = stripped
     # own the memory (frombuffer views keep whole storages alive) and drop aliasing between entries
     return {k: v.clone() for k, v in state.items()}
+
+
+ECAPA_MEL_YAML_KEYS = ("sample_rate", "n_fft", "win_length", "hop_length", "f_min", "f_max", "n_mels", "power",
+                       "normalized", "norm", "mel_scale")
+# hyperparams.yaml spells some of torchaudio's names its own way
+_ECAPA_MEL_YAML_ALIASES = {"n_mel_channels": "n_mels", "mel_fmin": "f_min", "mel_fmax": "f_max", "mel_normalized": "normalized"}
+
+
+def ecapa_mel_hyperparams(state_path) -> Optional[dict]:
+    """The feature settings a speechbrain ``hyperparams.yaml`` beside ``state_path`` records for the mel-spectrogram
+    ECAPA (speechbrain/spkrec-ecapa-voxceleb-mel-spec), or None when there is no such file or its text does not name
+    ``mel_spectogram`` (speechbrain.lobes.models.HifiGAN.mel_spectogram, the bare function that model declares as its
+    features).  The file is read as TEXT: top-level ``key: scalar`` lines only — no yaml or hyperpyyaml loader, no tag is
+    resolved, nothing is imported or executed.  A value that refers to another key (``!ref <name>``) is followed once."""
+    import re
+    path = Path(state_path).parent / "hyperparams.yaml"
+    if not path.is_file():
+        return None
+    text = path.read_text(encoding="utf-8", errors="replace")
+    if "mel_spectogram" not in text:
+        return None
+    scalars = {}
+    for line in text.splitlines():
+        m = re.match(r"^\s*([A-Za-z_][A-Za-z0-9_]*)\s*:\s*([^#]*?)\s*(#.*)?$", line)
+        if m and m.group(2) and not m.group(2).startswith(("!new", "!name", "!apply", "&", "*", "|", ">")):
+            scalars.setdefault(m.group(1), m.group(2))
+    out = {}
+    for key, value in scalars.items():
+        name = _ECAPA_MEL_YAML_ALIASES.get(key, key)
+        if name not in ECAPA_MEL_YAML_KEYS:
+            continue
+        ref = re.match(r"^!ref\s*<([A-Za-z_][A-Za-z0-9_]*)>$", value)
+        if ref:
+            value = scalars.get(ref.group(1))
+            if value is None or value.startswith("!"):
+                continue
+        out.setdefault(name, value.strip("\"'"))
+    return out
+

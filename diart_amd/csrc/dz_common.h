@@ -314,14 +314,16 @@ inline int dz_check_groups_forward(const char* who, const void* h, int max_rows,
 // The batch geometry of ECAPA-TDNN and the speechbrain x-vector (ecapa_api.hip, sbx_api.hip): each row's kept samples
 // compacted into sig (lstride floats per row: the centred STFT's 200 leading zeros, padding), their count, and what
 // the device derives from it per group of rows (k_ecapa.hip: ecapa_geometry_kernel), with Tc frames per row at most.
+// hop / window: the front end's (the Fbank's 160 / 400; the mel-spectrogram ECAPA's 256 / 1024, ecm_api.hip) — Tc = 1 +
+// S / hop, a group has 1 + lmax / hop frames, and a row of sig leaves room for S + window samples.
 struct DzRowGeometry {
-    int S, Tc, min_samples;
+    int S, Tc, min_samples, hop;
     long long lstride;
     float* sig;
     int *lens, *nvalid, *nmask, *tooshort;
     // per-row frame count the kernels read, and the geometry a groups forward reports (peek)
     int *tdev, *rep_nvalid, *rep_nmask, *rep_T;
-    void init(int num_samples, int min_num_samples);
+    void init(int num_samples, int min_num_samples, int hop = 160, int window = 400);
     void carve(Arena& a, size_t rows);
     // zero sig, compact the kept samples of N = G K rows into it, derive each group's geometry on the device.  Row
     // g K + k reads waveform row (g K + k) / rows_per_wave and mask row g K + k (or every sample when d_masks is NULL).
@@ -606,6 +608,19 @@ int dz_launch_fbank_post_mels(const float* melp, int n_mels, int T, int rows, co
                               hipStream_t st, const int* tdev = nullptr);
 int dz_launch_sb_stats_pool(const float* x, int T, int C, int ldx, int rows, const int* nvalid, float mean_bias,
                             float std_bias, float* pooled, hipStream_t st);
+
+// k_ecapa_mel.hip -----------------------------------------------------------
+// the mel-spectrogram ECAPA's front end (ecm_api.hip): n_fft = window 1024, hop 256, centred with reflect padding.
+// Rows are K per group; lens [rows] as mask_compact leaves them (-(len + 1): a NaN / Inf sample).
+// sig [rows][sig_stride]: kept samples from column 200 on, zeros behind -> csig [rows][cstride]: column j = sample
+// j - 512 of the row zero-padded to its group's longest lmax and reflected there (i < 0 reads -i, i >= lmax reads
+// 2 (lmax - 1) - i), zeros from column lmax + 1024 on and for a group with lmax <= 512; lmax_out [rows] = lmax
+int dz_launch_ecm_prep(const float* sig, long long sig_stride, const int* lens, int rows, int K, float* csig,
+                       long long cstride, int* lmax_out, hipStream_t st);
+// spec [rows][1028] = (re[0..512] | im[0..512]) -> mag [rows][544] = sqrt(re^2 + im^2), columns 513.. = 0
+int dz_launch_ecm_magnitude(const float* spec, long long rows, float* mag, hipStream_t st);
+// melp [rows][T][80] -> feats = log(max(melp, 1e-5)) - mean over the row's first nvalid[row] frames
+int dz_launch_ecm_post(const float* melp, int T, int rows, const int* nvalid, float* feats, hipStream_t st);
 
 // k_conv2d.hip ---------------------------------------------------------------
 // implicit-GEMM 2-D convolution over channels-last activations X [B][Fi][Ti][Cin] -> Y [B][Fo][To][Cout]:

@@ -172,6 +172,18 @@ inline int dz_asp_tail(const DzAspTail& a, const float* x, int N, int T, int C, 
     return dz_splitk_linear(*a.fc, a.pooled, N, 2 * C, 2 * C, emb, a.nsplit, a.parts, 0, out, st, a.tag_fc);
 }
 
+// The buffers and the launch sequence of ECAPA-TDNN behind its features (ecapa_api.hip), for the two handles with that
+// network: dz_ecapa (Fbank front end) and dz_ecm (mel-spectrogram front end, ecm_api.hip).
+struct DzEcapaTrunk {
+    float *feats, *b0, *t1, *res, *t2, *cat, *mfa, *a1;
+    float *smean, *sfc1, *gate, *gstat, *rb, *pooled, *parts;
+    // split-f16 precision: the inputs of the wide 1 x 1 layers as kb-major f16 planes (k_gemm_pre.hip), [2][C / 32][N T][32]
+    unsigned short *b0s, *ress, *cats;
+    void carve(Arena& a, size_t N, size_t Tc, bool split);
+    int run(const dz_ecapa_weights& w, int N, int T, const int* nmask, const int* tdev, float* d_out,
+            hipStream_t st) const;
+};
+
 // ---------------------------------------------------------------------------
 // entry points of a handle H {dz_ctx* ctx; W w; int Nm; DzRowGeometry geo; char* arena; ...} (dz_sbx, dz_ttn,
 // dz_ecapa).  `who`: the public function, for the error strings.
@@ -186,7 +198,7 @@ int dz_handle_destroy(H* h) {
 }
 template <typename H, typename W>
 int dz_handle_create(const char* who, dz_ctx* ctx, const W* w, int max_rows, int num_samples, int min_samples,
-                     void (*carve)(H*, Arena&), H** out) {
+                     void (*carve)(H*, Arena&), H** out, int hop = 160, int window = 400) {
     DZ_REQUIRE(ctx && w && out, "%s: NULL argument", who);
     DZ_REQUIRE(max_rows >= 1 && num_samples >= min_samples, "%s: max_rows %d, %d samples", who, max_rows, num_samples);
     DZ_HIP(hipSetDevice(ctx->device));
@@ -194,7 +206,7 @@ int dz_handle_create(const char* who, dz_ctx* ctx, const W* w, int max_rows, int
     DZ_REQUIRE(h != nullptr, "%s: out of memory", who);
     memset(h, 0, sizeof(*h));
     h->ctx = ctx; h->w = *w; h->Nm = max_rows;
-    h->geo.init(num_samples, min_samples);
+    h->geo.init(num_samples, min_samples, hop, window);
     if (int rc = dz_arena_alloc(who, h, carve)) {
         dz_handle_destroy(h);
         return rc;

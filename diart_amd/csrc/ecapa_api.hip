@@ -19,19 +19,18 @@ struct dz_ecapa {
     char* arena;
     int* h_pin;  // pinned host: lens[Nm] | nvalid[Nm] | nmask[Nm] | tooshort[Nm]
     // device buffers
-    float *spec, *pw, *melp, *feats, *b0, *t1, *res, *t2, *cat, *mfa, *a1;
-    float *smean, *sfc1, *gate, *gstat, *rb, *pooled, *parts;
-    // split-f16 precision: the inputs of the wide 1 x 1 layers as kb-major f16 planes (k_gemm_pre.hip), [2][C / 32][N T][32]
-    unsigned short *b0s, *ress, *cats;
+    float *spec, *pw, *melp;
+    DzEcapaTrunk tr;    // features and everything behind them (dz_embed.h)
     int lastN, lastT, lastGroups;
 };
 
 // DzRowGeometry (dz_common.h): ECAPA's STFT layout and batch geometry, which sbx_api.hip shares
-void DzRowGeometry::init(int num_samples, int min_num_samples) {
+void DzRowGeometry::init(int num_samples, int min_num_samples, int hop_, int window) {
     S = num_samples;
-    Tc = 1 + num_samples / HOP;
+    hop = hop_;
+    Tc = 1 + num_samples / hop;
     min_samples = min_num_samples;
-    lstride = ((long long)num_samples + NFFT + 3) / 4 * 4;
+    lstride = ((long long)num_samples + window + 3) / 4 * 4;
 }
 
 void DzRowGeometry::carve(Arena& a, size_t rows) {
@@ -54,8 +53,38 @@ int DzRowGeometry::prologue(const float* d_wave, long long wave_stride, const fl
     if ((rc = dz_launch_mask_compact(d_wave, wave_stride, S, d_masks, mask_frames, N, sig, lstride, lens, st,
                                      rows_per_wave)))
         return rc;
-    return dz_launch_ecapa_geometry(lens, G, K, Tc, min_samples, HOP, nvalid, nmask, tooshort, tdev, rep_nvalid,
+    return dz_launch_ecapa_geometry(lens, G, K, Tc, min_samples, hop, nvalid, nmask, tooshort, tdev, rep_nvalid,
                                     rep_nmask, rep_T, st);
+}
+
+// DzEcapaTrunk (dz_embed.h): the buffers of ecapa_network's step 3 for N rows of Tc frames
+void DzEcapaTrunk::carve(Arena& a, size_t N, size_t Tc, bool split) {
+    const size_t NT = N * Tc;
+    feats = a.take<float>(NT * 80);
+    b0 = a.take<float>(NT * C1);
+    t1 = a.take<float>(NT * C1);
+    res = a.take<float>(NT * C1);
+    t2 = a.take<float>(NT * C1);
+    cat = a.take<float>(NT * C3);   // after the MFA convolution it is reused for the logits
+    mfa = a.take<float>(NT * C3);
+    a1 = a.take<float>(NT * 128);
+    smean = a.take<float>(N * C1);
+    sfc1 = a.take<float>(N * 128);
+    gate = a.take<float>(N * C1);
+    gstat = a.take<float>(N * 2 * C3);
+    rb = a.take<float>(N * 128);
+    pooled = a.take<float>(N * 2 * C3);
+    parts = a.take<float>((size_t)FC_SPLIT * N * EMB);
+    b0s = ress = cats = nullptr;
+    if (split) {
+        // (+ PLANE_SLACK: a 128-row tile that starts inside the last rows of a plane's last k-block reads up to 127
+        // rows x 64 bytes past it — zeros through the buffer bounds check when the resource ends there, but a
+        // consumer that reads a COLUMN SLICE of a plane (tdnn1 of blocks 1 and 2: k-blocks [32 (i - 1), 32 i) of
+        // the concatenation) has a resource that ends further on, so the bytes must exist)
+        b0s = a.take<unsigned short>(2 * NT * C1 + PLANE_SLACK);
+        ress = a.take<unsigned short>(2 * NT * C1 + PLANE_SLACK);
+        cats = a.take<unsigned short>(2 * NT * C3 + PLANE_SLACK);
+    }
 }
 
 static void ecapa_carve(dz_ecapa* e, Arena& a) {
@@ -63,31 +92,7 @@ static void ecapa_carve(dz_ecapa* e, Arena& a) {
     e->spec = a.take<float>(NT * 404);
     e->pw = a.take<float>(NT * 204);
     e->melp = a.take<float>(NT * 80);
-    e->feats = a.take<float>(NT * 80);
-    e->b0 = a.take<float>(NT * C1);
-    e->t1 = a.take<float>(NT * C1);
-    e->res = a.take<float>(NT * C1);
-    e->t2 = a.take<float>(NT * C1);
-    e->cat = a.take<float>(NT * C3);   // after the MFA convolution it is reused for the logits
-    e->mfa = a.take<float>(NT * C3);
-    e->a1 = a.take<float>(NT * 128);
-    e->smean = a.take<float>(N * C1);
-    e->sfc1 = a.take<float>(N * 128);
-    e->gate = a.take<float>(N * C1);
-    e->gstat = a.take<float>(N * 2 * C3);
-    e->rb = a.take<float>(N * 128);
-    e->pooled = a.take<float>(N * 2 * C3);
-    e->parts = a.take<float>((size_t)FC_SPLIT * N * EMB);
-    e->b0s = e->ress = e->cats = nullptr;
-    if (e->w.mfa.wsplit) {
-        // (+ PLANE_SLACK: a 128-row tile that starts inside the last rows of a plane's last k-block reads up to 127
-        // rows x 64 bytes past it — zeros through the buffer bounds check when the resource ends there, but a
-        // consumer that reads a COLUMN SLICE of a plane (tdnn1 of blocks 1 and 2: k-blocks [32 (i - 1), 32 i) of
-        // the concatenation) has a resource that ends further on, so the bytes must exist)
-        e->b0s = a.take<unsigned short>(2 * NT * C1 + PLANE_SLACK);
-        e->ress = a.take<unsigned short>(2 * NT * C1 + PLANE_SLACK);
-        e->cats = a.take<unsigned short>(2 * NT * C3 + PLANE_SLACK);
-    }
+    e->tr.carve(a, N, e->geo.Tc, e->w.mfa.wsplit != nullptr);
     e->geo.carve(a, N);
 }
 
@@ -195,7 +200,6 @@ extern "C" int dz_ecapa_forward(dz_ecapa* e, const float* d_wave, long long wave
 static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_out, hipStream_t st) {
     int rc;
     const dz_ecapa_weights& w = e->w;
-    const long long NT = (long long)N * T;
 
     // ---- 2. Fbank: STFT as one GEMM over overlapping rows (hop 160 < window 400) ---------------
     const dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
@@ -203,8 +207,19 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     if ((rc = dz_fbank_front(dft, mel, e->geo.sig, e->geo.lstride, N, T, e->spec, e->pw, 80, 128, e->melp, st,
                              DZ_T_ECAPA_FBANK)))
         return rc;
-    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->geo.nvalid, e->feats, st, tdev))) return rc; }
+    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->geo.nvalid, e->tr.feats, st, tdev))) return rc; }
 
+    return e->tr.run(w, N, T, e->geo.nmask, tdev, d_out, st);
+}
+
+// Step 3 of a forward, which the mel-spectrogram ECAPA (ecm_api.hip) shares: block 0 through dz_asp_tail over the
+// features [N][T][80] of this trunk -> d_out [N][192].  nmask [N]: the frames of the squeeze-excitation means and the
+// pooling; tdev as above.
+int DzEcapaTrunk::run(const dz_ecapa_weights& w, int N, int T, const int* nmask, const int* tdev, float* d_out,
+                      hipStream_t st) const {
+    const DzEcapaTrunk* e = this;
+    int rc;
+    const long long NT = (long long)N * T;
     // ---- 3. ECAPA-TDNN -------------------------------------------------------------------------
     // Split-f16 precision: the seven wide 1 x 1 layers (tdnn1 / tdnn2 of the three blocks, the MFA convolution: 84 % of
     // the network's MACs) run on k_gemm_pre.hip — both operands as ready f16 planes moved by LDS-DMA — so whatever
@@ -245,7 +260,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
         // tdnn2 (1x1)
         if ((rc = wide(b.tdnn2, e->res, C1, e->ress, p1, N, NT, C1, e->t2, st))) return rc;
         // squeeze-excitation + residual, written straight into its slice of the concatenation
-        { DzProfScope ps(DZ_T_ECAPA_SE, N); if ((rc = dz_launch_se_mean(e->t2, T, C1, C1, N, e->geo.nmask, e->smean, st))) return rc; }
+        { DzProfScope ps(DZ_T_ECAPA_SE, N); if ((rc = dz_launch_se_mean(e->t2, T, C1, C1, N, nmask, e->smean, st))) return rc; }
         // squeeze (N rows x 1024 -> 128): one output tile, so the K loop is split 8 ways (a lone workgroup
         // walking 32 k-tiles took 90 us); the ReLU follows the fixed-order reduce
         if ((rc = dz_splitk_linear(b.se1, e->smean, N, C1, C1, 128, SE_SPLIT, e->parts, 2, e->sfc1, st, DZ_T_ECAPA_SE)))
@@ -267,7 +282,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     // concatenation is dead once the MFA layer has consumed it
     const DzAspTail tail = {w.asp_wms, w.zeros, &w.asp_tdnn, &w.asp_conv, &w.fc, e->gstat, e->rb, e->a1, e->cat, e->pooled,
                             e->parts, FC_SPLIT, DZ_T_ECAPA_ASP, DZ_T_ECAPA_FC};
-    return dz_asp_tail(tail, e->mfa, N, T, C3, EMB, e->geo.nmask, d_out, st);
+    return dz_asp_tail(tail, e->mfa, N, T, C3, EMB, nmask, d_out, st);
 }
 
 // The forward of the rows of n_groups chunks, K (rows_per_group) speaker rows each, every group with its own
@@ -311,11 +326,11 @@ extern "C" int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long lo
         return 2;
     }
     switch (which) {
-        case 0: *d_ptr = e->feats; *count = N * T * 80; return 0;
-        case 1: *d_ptr = e->b0; *count = N * T * C1; return 0;
-        case 2: *d_ptr = e->cat; *count = N * T * C3; return 0;   // holds the logits after a forward
-        case 3: *d_ptr = e->mfa; *count = N * T * C3; return 0;
-        case 4: *d_ptr = e->pooled; *count = N * 2 * C3; return 0;
+        case 0: *d_ptr = e->tr.feats; *count = N * T * 80; return 0;
+        case 1: *d_ptr = e->tr.b0; *count = N * T * C1; return 0;
+        case 2: *d_ptr = e->tr.cat; *count = N * T * C3; return 0;   // holds the logits after a forward
+        case 3: *d_ptr = e->tr.mfa; *count = N * T * C3; return 0;
+        case 4: *d_ptr = e->tr.pooled; *count = N * 2 * C3; return 0;
         case 5: *d_ptr = e->geo.lens; *count = N; return 0;
         case 6: *d_ptr = e->geo.nvalid; *count = N; return 0;
         case 7: *d_ptr = e->geo.nmask; *count = N; return 0;

@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .weights import (PackedEcapa, PackedEmbedding, PackedSbResNet, PackedSbXvector, PackedSegmentation, PackedTitaNet, PackedWeSpeaker,
+from .weights import (ECAPA_MEL_FEATURES, ECAPA_MEL_MIN_NUM_SAMPLES, PackedEcapa, PackedEcapaMel, PackedEmbedding, PackedSbResNet, PackedSbXvector, PackedSegmentation, PackedTitaNet, PackedWeSpeaker,
                       SB_RESNET_MARKERS, SB_RESNET_MIN_NUM_SAMPLES, SB_RESNET_STRIDES, TITANET_MARKERS,
                       TITANET_MIN_NUM_SAMPLES)
 
@@ -467,6 +467,50 @@ class HipEcapaEmbedding(_HipGroupsEmbedding):
         return self._peek_raw(self._handles[num_samples][0], 5)[2]
 
 
+ECAPA_MEL_OPTIONS = ("min_num_samples",) + tuple(ECAPA_MEL_FEATURES)
+
+
+class HipEcapaMelEmbedding(_HipGroupsEmbedding):
+    """speechbrain's mel-spectrogram ECAPA-TDNN (speechbrain/spkrec-ecapa-voxceleb-mel-spec) behind pyannote's
+    ``PretrainedSpeakerEmbedding`` contract, the wrapper the reference falls back to for it (models.py:59):
+    ``(waveform (N,1,S), masks (N,F) | None) -> (N,192)``, not normalised; a row whose mask keeps fewer than
+    ``min_num_samples`` (1024) samples, or whose kept samples hold a NaN, is NaN, and a call whose longest row is that
+    short is all NaN.  ``HipEcapaEmbedding``'s network and checkpoint keys behind another front end: a centred,
+    reflect-padded STFT of 1024 samples at hop 256 over the padded batch, magnitude, 80 slaney mel bins,
+    ``log(max(x, 1e-5))``, sentence mean — 313 frames for 5 s instead of 501.  The same call shape as
+    ``HipEcapaEmbedding``, so the same engine forms take it; masks select samples, so ``repeated_rows="share"`` is
+    refused.  ``features``: the settings of ``weights.ECAPA_MEL_FEATURES``; a value the kernels are not built for is
+    refused by name."""
+
+    dimension = 192
+    _c, _packer, _int32_peeks = "dz_ecm", PackedEcapaMel, frozenset((5, 6, 7, 8, 9))
+
+    def __init__(self, state: Dict[str, torch.Tensor], max_batch: int = 192, precision: Optional[str] = None,
+                 repeated_rows: Optional[str] = None, min_num_samples: int = ECAPA_MEL_MIN_NUM_SAMPLES, **features):
+        super().__init__(state, max_batch, precision, repeated_rows)
+        from .weights import ecapa_mel_features
+        self.features = ecapa_mel_features(**features)
+        self.min_num_samples = int(min_num_samples)
+        if self.min_num_samples <= 512:
+            raise ValueError(f"ecapa-mel: min_num_samples={min_num_samples} — the centred STFT reflects 512 samples, "
+                             "which needs more than 512")
+
+    def _extra_state(self):
+        return dict(super()._extra_state(), min_num_samples=self.min_num_samples, **self.features)
+
+    def _pack(self, device):
+        return PackedEcapaMel(self._state, device, precision=self.precision, min_num_samples=self.min_num_samples,
+                              **self.features)
+
+    def num_frames(self, num_samples: int) -> int:
+        """Frames every buffer lays a row of ``num_samples`` samples out with (``dz_ecm_frames_for``: 1 + S // 256)."""
+        return int(_lib.load().dz_ecm_frames_for(int(num_samples)))
+
+    def last_frames(self, num_samples: int) -> int:
+        """Frames per row of the buffers of the last forward (``dz_ecm_peek``); no copy, no synchronisation."""
+        return self._peek_raw(self._handles[num_samples][0], 5)[2]
+
+
 class HipSbXvectorEmbedding(_HipGroupsEmbedding):
     """speechbrain's x-vector (speechbrain/spkrec-xvect-voxceleb) behind pyannote's ``PretrainedSpeakerEmbedding``
     contract, the wrapper the reference falls back to for it (models.py:59): ``(waveform (N,1,S), masks (N,F) |
@@ -607,11 +651,13 @@ class SegmentationLoader:
 class EmbeddingLoader:
     """``arch``: "xvector" (pyannote/embedding), "ecapa" (speechbrain/spkrec-ecapa-voxceleb), "wespeaker"
     (pyannote/wespeaker-voxceleb-resnet34-LM), "sb-xvector" (speechbrain/spkrec-xvect-voxceleb), "sb-resnet"
-    (speechbrain/spkrec-resnet-voxceleb) or "titanet" (nvidia/speakerverification_en_titanet_large, a ``.nemo``
-    archive); None = decide from the checkpoint keys (``encoder.encoder.0.mconv.0.conv.weight`` +
+    (speechbrain/spkrec-resnet-voxceleb), "ecapa-mel" (speechbrain/spkrec-ecapa-voxceleb-mel-spec) or "titanet"
+    (nvidia/speakerverification_en_titanet_large, a ``.nemo`` archive); None = decide from the checkpoint keys (``encoder.encoder.0.mconv.0.conv.weight`` +
     ``decoder.emb_layers.0.1.weight``: titanet, ``resnet.``: wespeaker, ``asp.``: ecapa, speechbrain ``Xvector`` keys
     ``blocks.0.conv.weight`` + ``blocks.16.w.weight``: sb-xvector, speechbrain ``ResNet`` keys
-    ``layer1.0.se.fc.0.weight`` + ``fc_embed.weight``: sb-resnet, otherwise xvector)."""
+    ``layer1.0.se.fc.0.weight`` + ``fc_embed.weight``: sb-resnet, otherwise xvector).  The mel-spectrogram ECAPA has
+    the fbank ECAPA's keys: a state FILE beside which a ``hyperparams.yaml`` names ``mel_spectogram`` is "ecapa-mel"
+    (``checkpoint.ecapa_mel_hyperparams``), a plain state dict with ``asp.`` keys stays "ecapa"."""
 
     def __init__(self, state: StateSource, max_batch: int = 64, arch: Optional[str] = None,
                  precision: Optional[str] = None, weight_interp: Optional[str] = None,
@@ -619,19 +665,21 @@ class EmbeddingLoader:
         """``arch_options`` (titanet only): ``pad_mode``, ``frame_count``, ``min_num_samples``, ``attention_order`` of
         ``HipTitaNetEmbedding`` — the switches DESIGN.md 4.12 marks (R); they override what the archive's yaml records.
         ``arch_options`` (sb-resnet only): ``strides``, ``min_num_samples``, ``rows_per_pass`` of ``HipSbResNetEmbedding``.
+        ``arch_options`` (ecapa-mel only): ``min_num_samples`` and the feature settings of ``HipEcapaMelEmbedding`` — the
+        points DESIGN.md 4.15 marks (R); they override what a ``hyperparams.yaml`` beside the state file records.
         ``weight_interp`` (x-vector only): "linear" | "nearest" | None = from the ``pyannote.audio`` version the
         checkpoint file records (>= 3.1: "nearest"; older, absent, or a plain state dict: "linear").
         ``repeated_rows``: "each" | "share" (``repeated_rows_mode``: the reference-shaped ``(batch spk)`` call runs the
-        trunk once per window; xvector and wespeaker only — ecapa, sb-xvector and titanet refuse "share")."""
+        trunk once per window; xvector and wespeaker only — ecapa, ecapa-mel, sb-xvector, sb-resnet and titanet refuse "share")."""
         if repeated_rows is not None and repeated_rows not in REPEATED_ROWS:
             raise ValueError(f"repeated_rows={repeated_rows!r}: expected one of {REPEATED_ROWS}")
         self.state, self.max_batch, self.arch, self.precision = state, max_batch, arch, precision
         self.weight_interp = weight_interp
         self.repeated_rows = repeated_rows
-        unknown = set(arch_options) - set(TITANET_OPTIONS) - set(SB_RESNET_OPTIONS)
+        unknown = set(arch_options) - set(TITANET_OPTIONS) - set(SB_RESNET_OPTIONS) - set(ECAPA_MEL_OPTIONS)
         if unknown:
             raise TypeError(f"EmbeddingLoader: unknown option(s) {sorted(unknown)} (titanet takes {TITANET_OPTIONS}, "
-                            f"sb-resnet {SB_RESNET_OPTIONS})")
+                            f"sb-resnet {SB_RESNET_OPTIONS}, ecapa-mel {ECAPA_MEL_OPTIONS})")
         self.arch_options = arch_options
 
     def __call__(self):
@@ -645,6 +693,22 @@ class EmbeddingLoader:
             arch = "titanet"
         if arch == "xvector" and self.arch is None and all(k in sd for k in SB_RESNET_MARKERS):
             arch = "sb-resnet"      # (the pyannote x-vector packer has no ``layer1.`` keys: this state failed there)
+        yaml_features = None
+        if arch == "ecapa" and self.arch is None and not isinstance(self.state, dict):
+            from .checkpoint import ecapa_mel_hyperparams
+            yaml_features = ecapa_mel_hyperparams(self.state)
+            if yaml_features is not None:
+                arch = "ecapa-mel"
+        if arch == "ecapa-mel":
+            other = sorted(set(self.arch_options) - set(ECAPA_MEL_OPTIONS))
+            if other:
+                raise TypeError(f"EmbeddingLoader: {other} are options of another architecture, this state is {arch!r}")
+            if yaml_features is None and not isinstance(self.state, dict):
+                from .checkpoint import ecapa_mel_hyperparams
+                yaml_features = ecapa_mel_hyperparams(self.state)
+            kw = dict(yaml_features or {})
+            kw.update(self.arch_options)
+            return HipEcapaMelEmbedding(sd, self.max_batch, self.precision, self.repeated_rows, **kw)
         if arch == "sb-resnet":
             other = sorted(set(self.arch_options) - set(SB_RESNET_OPTIONS))
             if other:
@@ -663,7 +727,7 @@ class EmbeddingLoader:
             kw.update(self.arch_options)
             return HipTitaNetEmbedding(sd, self.max_batch, self.precision, self.repeated_rows, **kw)
         if self.arch_options:
-            raise TypeError(f"EmbeddingLoader: {sorted(self.arch_options)} are options of the titanet or sb-resnet "
+            raise TypeError(f"EmbeddingLoader: {sorted(self.arch_options)} are options of the titanet, sb-resnet or ecapa-mel "
                             f"architecture, this state is {arch!r}")
         if arch == "sb-xvector":
             return HipSbXvectorEmbedding(sd, self.max_batch, self.precision, self.repeated_rows)
@@ -773,7 +837,8 @@ class EmbeddingModel(LazyModel):
 
     @staticmethod
     def from_pretrained(model, use_hf_token=True, repeated_rows: Optional[str] = None, **arch_options) -> "EmbeddingModel":
-        """``arch_options``: the (R) switches of a TitaNet or speechbrain ResNet model (``EmbeddingLoader``)."""
+        """``arch_options``: the (R) switches of a TitaNet, speechbrain ResNet or mel-spectrogram ECAPA model
+        (``EmbeddingLoader``)."""
         if isinstance(model, (str, Path)) and Path(model).name.endswith(".onnx"):
             return EmbeddingModel.from_onnx(model)
         if isinstance(model, dict):

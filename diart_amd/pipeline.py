@@ -25,7 +25,7 @@ independent, only the host-side clustering is sequential per stream):
 writes each stream's speech track and only that track reaches the host's output tails.  The other embeddings share the
 two-chain engine: ``WeSpeakerBatch`` for the WeSpeaker ResNet34 embedding, whose trunk is the long chain of the step (the
 segmentation runs under it), and ``GroupsBatch`` for the groups form (``HipEcapaEmbedding``, BASELINE.json config 3,
-``HipSbXvectorEmbedding``, ``HipTitaNetEmbedding``, ``HipSbResNetEmbedding``), which ``StreamBatch(seg, emb, ...)``
+``HipSbXvectorEmbedding``, ``HipTitaNetEmbedding``, ``HipSbResNetEmbedding``, ``HipEcapaMelEmbedding``), which ``StreamBatch(seg, emb, ...)``
 constructs for them.
 """
 from __future__ import annotations
@@ -570,7 +570,7 @@ class StreamBatch(_DiarizationEngine):
         that no two kernels ever overlap and a kernel's bracketed duration is its alone-time (what
         ``rocprofv3 --kernel-trace --stats`` of the same run reports): ``bench.py``'s roofline pass.
 
-        With a groups-form ``embedding`` (ECAPA-TDNN, speechbrain x-vector, TitaNet-L, speechbrain ResNet) this call constructs a
+        With a groups-form ``embedding`` (ECAPA-TDNN, speechbrain x-vector, TitaNet-L, speechbrain ResNet, mel-spectrogram ECAPA) this call constructs a
         ``GroupsBatch``: see there."""
         if isinstance(embedding, HipWeSpeakerEmbedding):
             raise ValueError("StreamBatch does not run the WeSpeaker ResNet34 embedding; it runs "
@@ -1081,14 +1081,16 @@ class WeSpeakerBatch(_TwoChainEngine):
 
 class GroupsBatch(_TwoChainEngine):
     """``SpeakerDiarization`` of N concurrent streams with a groups-form embedding (``HipEcapaEmbedding``: config 3,
-    powerset segmentation + ECAPA-TDNN; ``HipSbXvectorEmbedding``; ``HipTitaNetEmbedding``; ``HipSbResNetEmbedding``): what ``StreamBatch(seg, emb,
+    powerset segmentation + ECAPA-TDNN; ``HipSbXvectorEmbedding``; ``HipTitaNetEmbedding``; ``HipSbResNetEmbedding``;
+    ``HipEcapaMelEmbedding``): what ``StreamBatch(seg, emb,
     n, ...)`` constructs for them, with ``StreamBatch``'s arguments.  The two-chain schedule with no early launch and
     the model's ``groups_launch`` as the late one: each stream's K speaker rows are embedded with the batch geometry of
     those rows alone (``forward_groups``) and L2-normalised as the embedding block's ``EmbeddingNormalization(1)`` does.
 
     ``lanes`` (= ``depth``) defaults to 2: one ECAPA handle of 64 streams x 3 speakers = 192 rows x 501 frames (5 s)
     carves about 6.2 GB of device memory per lane, a speechbrain x-vector handle about 1.7 GB, a TitaNet-L handle about
-    5.9 GB with "f16x3", a speechbrain ResNet handle about 2.1 GB (the handle computes its arena from the rows and the
+    5.9 GB with "f16x3", a speechbrain ResNet handle about 2.1 GB, a mel-spectrogram ECAPA handle (192 rows x 313
+    frames) about 4.3 GB with "f16x3" and 3.0 GB with "f32" (the handle computes its arena from the rows and the
     window).  ``seg_split`` and ``emb_split``
     must be None or 1; ``serial``: the measurement form, one lane (``lanes=1``) whose two chains share one HIP stream.
     The experiments build's ``DZ_PRIO_A``, ``DZ_PRIO_B``, ``DZ_SHARED_STATS``, ``DZ_SEG_SPLIT`` and ``DZ_EMB_SPLIT`` do

@@ -12,7 +12,8 @@ stream's own clustering and aggregation state.  Streams join and leave at any ti
 their own pace; per stream the output is what a dedicated ``SpeakerDiarization`` pipeline with the
 same configuration produces.  The model pair may be config 2's (x-vector) or config 3's (powerset segmentation +
 ``HipEcapaEmbedding``, with ``normalize_embedding_weights=True``), or the same with the speechbrain x-vector
-(``HipSbXvectorEmbedding``) or the speechbrain ResNet (``HipSbResNetEmbedding``) on a ``GroupsBatch``; with a ``HipWeSpeakerEmbedding`` (pyannote.audio 3.1's embedding)
+(``HipSbXvectorEmbedding``), the speechbrain ResNet (``HipSbResNetEmbedding``) or the mel-spectrogram ECAPA
+(``HipEcapaMelEmbedding``) on a ``GroupsBatch``; with a ``HipWeSpeakerEmbedding`` (pyannote.audio 3.1's embedding)
 the engine is a ``WeSpeakerBatch``.  ``pipeline="vad"`` (no embedding) serves
 ``VoiceActivityDetection`` instead (``diart.serve --pipeline VoiceActivityDetection``, reference
 ``console/serve.py:19-22,99-102``) on a ``VadBatch``: every stream's turns are labelled ``"speech"``, and

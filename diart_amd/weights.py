@@ -463,6 +463,48 @@ class PackedEmbedding:
         self.struct, self.pack = w, pk
 
 
+def _pack_ecapa_network(sd: Dict[str, torch.Tensor], pk: "_Packed", w, split: bool) -> None:
+    """ECAPA_TDNN(80 -> 1024 x 4 -> 3072 -> 192) into ``w`` (a ``dz_ecapa_weights``: block0 .. fc, zeros), for the two
+    models with this network: ``PackedEcapa`` and ``PackedEcapaMel``."""
+    g = lambda k: sd[k].detach().cpu().float()
+
+    def bn(prefix, npad):
+        scale = g(prefix + ".norm.weight") / torch.sqrt(g(prefix + ".norm.running_var") + BN_EPS)
+        shift = g(prefix + ".norm.bias") - g(prefix + ".norm.running_mean") * scale
+        return _pad1(scale, npad), _pad1(shift, npad)
+
+    def layer(dst, prefix, cin_pad, npad, kpad, norm=True, weight=None, wide=False, kb=False):
+        cw = g(prefix + ".conv.weight") if weight is None else weight
+        dst.w = pk.put(_conv_pack(cw, cin_pad, npad, kpad))
+        if wide and split:   # also as split-f16 planes: the layer runs on k_gemm_split.hip, or (kb: planes in
+            #                  kb-major order) with pre-split activations on k_gemm_pre.hip
+            dst.wsplit = pk.put_split(_conv_pack(cw, cin_pad, npad, kpad), prefix, kb=kb)
+        dst.b = pk.put(_pad1(g(prefix + ".conv.bias"), npad))
+        if norm:
+            sc, sh = bn(prefix.rsplit(".conv", 1)[0] + ".norm", npad)
+            dst.s, dst.h = pk.put(sc), pk.put(sh)
+
+    layer(w.block0, "blocks.0.conv", 80, 1024, 416, wide=True)
+    for i in range(3):
+        p, b = f"blocks.{i + 1}", w.ser[i]
+        layer(b.tdnn1, p + ".tdnn1.conv", 1024, 1024, 1024, wide=True, kb=True)
+        for j in range(7):
+            layer(b.res[j], p + f".res2net_block.blocks.{j}.conv", 128, 128, 384, wide=True)
+        layer(b.tdnn2, p + ".tdnn2.conv", 1024, 1024, 1024, wide=True, kb=True)
+        layer(b.se1, p + ".se_block.conv1", 1024, 128, 1024, norm=False)
+        layer(b.se2, p + ".se_block.conv2", 128, 1024, 128, norm=False)
+    layer(w.mfa, "mfa.conv", 3072, 3072, 3072, wide=True, kb=True)
+    aw = g("asp.tdnn.conv.conv.weight")                           # (128, 9216, 1)
+    layer(w.asp_tdnn, "asp.tdnn.conv", 3072, 128, 3072, weight=aw[:, :3072], wide=True)
+    w.asp_wms = pk.put(aw[:, 3072:, 0].contiguous())             # (128, 6144)
+    layer(w.asp_conv, "asp.conv", 128, 3072, 128, norm=False, wide=True)
+    sc, sh = bn("asp_bn", 6144)
+    fw, fb = g("fc.conv.weight")[:, :, 0], g("fc.conv.bias")     # (192, 6144)
+    w.fc.w = pk.put((fw * sc[None, :]).contiguous())
+    w.fc.b = pk.put(fb + fw @ sh)
+    w.zeros = pk.put(torch.zeros(6144))
+
+
 class PackedEcapa:
     """``dz_ecapa_weights`` + the tensors behind it (speechbrain ECAPA_TDNN checkpoint keys:
     ``blocks.0.conv.conv.weight`` ... ``fc.conv.weight``).
@@ -477,50 +519,94 @@ class PackedEcapa:
         assert precision in PRECISIONS, precision
         split = precision == "f16x3"
         pk = _Packed(device)
-        g = lambda k: sd[k].detach().cpu().float()
         w = _lib.EcapaWeights()
-
-        def bn(prefix, npad):
-            scale = g(prefix + ".norm.weight") / torch.sqrt(g(prefix + ".norm.running_var") + BN_EPS)
-            shift = g(prefix + ".norm.bias") - g(prefix + ".norm.running_mean") * scale
-            return _pad1(scale, npad), _pad1(shift, npad)
-
-        def layer(dst, prefix, cin_pad, npad, kpad, norm=True, weight=None, wide=False, kb=False):
-            cw = g(prefix + ".conv.weight") if weight is None else weight
-            dst.w = pk.put(_conv_pack(cw, cin_pad, npad, kpad))
-            if wide and split:   # also as split-f16 planes: the layer runs on k_gemm_split.hip, or (kb: planes in
-                #                  kb-major order) with pre-split activations on k_gemm_pre.hip
-                dst.wsplit = pk.put_split(_conv_pack(cw, cin_pad, npad, kpad), prefix, kb=kb)
-            dst.b = pk.put(_pad1(g(prefix + ".conv.bias"), npad))
-            if norm:
-                sc, sh = bn(prefix.rsplit(".conv", 1)[0] + ".norm", npad)
-                dst.s, dst.h = pk.put(sc), pk.put(sh)
-
         # ---- features ------------------------------------------------------------------
         w.dft = pk.put(_pad2(dft_matrices().float(), 448, 416))
         if split:
             w.dft_split = pk.put_split(_pad2(dft_matrices().float(), 512, 416), "windowed DFT")
         w.mel = pk.put(_pad2(ecapa_mel_filterbank().t().contiguous(), 128, 224))
         # ---- network -------------------------------------------------------------------
-        layer(w.block0, "blocks.0.conv", 80, 1024, 416, wide=True)
-        for i in range(3):
-            p, b = f"blocks.{i + 1}", w.ser[i]
-            layer(b.tdnn1, p + ".tdnn1.conv", 1024, 1024, 1024, wide=True, kb=True)
-            for j in range(7):
-                layer(b.res[j], p + f".res2net_block.blocks.{j}.conv", 128, 128, 384, wide=True)
-            layer(b.tdnn2, p + ".tdnn2.conv", 1024, 1024, 1024, wide=True, kb=True)
-            layer(b.se1, p + ".se_block.conv1", 1024, 128, 1024, norm=False)
-            layer(b.se2, p + ".se_block.conv2", 128, 1024, 128, norm=False)
-        layer(w.mfa, "mfa.conv", 3072, 3072, 3072, wide=True, kb=True)
-        aw = g("asp.tdnn.conv.conv.weight")                           # (128, 9216, 1)
-        layer(w.asp_tdnn, "asp.tdnn.conv", 3072, 128, 3072, weight=aw[:, :3072], wide=True)
-        w.asp_wms = pk.put(aw[:, 3072:, 0].contiguous())             # (128, 6144)
-        layer(w.asp_conv, "asp.conv", 128, 3072, 128, norm=False, wide=True)
-        sc, sh = bn("asp_bn", 6144)
-        fw, fb = g("fc.conv.weight")[:, :, 0], g("fc.conv.bias")     # (192, 6144)
-        w.fc.w = pk.put((fw * sc[None, :]).contiguous())
-        w.fc.b = pk.put(fb + fw @ sh)
-        w.zeros = pk.put(torch.zeros(6144))
+        _pack_ecapa_network(sd, pk, w, split)
+        self.struct, self.pack = w, pk
+
+
+# The feature settings of speechbrain/spkrec-ecapa-voxceleb-mel-spec (its hyperparams.yaml, recalled: DESIGN.md 4.15
+# (R)) in torchaudio.transforms.MelSpectrogram's names.  f_min / f_max only shape the packed mel bank and may differ;
+# the kernels and the packer are built for the values of ECAPA_MEL_BUILT and every other value of those is refused by name.
+ECAPA_MEL_FEATURES = {"sample_rate": 16000, "n_fft": 1024, "win_length": 1024, "hop_length": 256, "f_min": 0.0,
+                      "f_max": 8000.0, "n_mels": 80, "power": 1, "normalized": False, "norm": "slaney",
+                      "mel_scale": "slaney"}
+ECAPA_MEL_BUILT = ("sample_rate", "n_fft", "win_length", "hop_length", "n_mels", "power", "normalized", "norm",
+                   "mel_scale")
+ECAPA_MEL_MIN_NUM_SAMPLES = 1024
+
+
+def ecapa_mel_features(**given) -> dict:
+    """``ECAPA_MEL_FEATURES`` with ``given`` laid over it; ValueError naming the setting for an unknown one or a value
+    the kernels are not built for."""
+    out = dict(ECAPA_MEL_FEATURES)
+    for k, v in given.items():
+        if k not in out:
+            raise ValueError(f"ecapa-mel: unknown feature setting {k!r} (known: {sorted(out)})")
+        want = out[k]
+        if isinstance(want, bool):
+            v = v if isinstance(v, bool) else str(v).strip().lower() in ("true", "1", "yes")
+        elif isinstance(want, (int, float)):
+            v = type(want)(float(v))
+        else:
+            v = None if v is None or str(v).strip().lower() in ("none", "null", "~") else str(v).strip().strip("\"'")
+        if k in ECAPA_MEL_BUILT and v != want:
+            raise ValueError(f"ecapa-mel: {k}={v!r} — the HIP front end is built for {k}={want!r} only")
+        out[k] = v
+    if not 0.0 <= out["f_min"] < out["f_max"] <= out["sample_rate"] / 2:
+        raise ValueError(f"ecapa-mel: f_min={out['f_min']!r} / f_max={out['f_max']!r} outside 0 <= f_min < f_max <= Nyquist")
+    return out
+
+
+def ecapa_mel_spec_dft() -> torch.Tensor:
+    """The STFT of the mel-spectrogram ECAPA as ONE real GEMM operand, (2 * 513, 1024) f64: rows 0 .. 512 =
+    cos(2 pi k n / 1024) w[n], rows 513 .. 1025 = sin(...) w[n], w the periodic Hann window of 1024 samples:
+    frame @ rows.T = (Re, -Im) of rfft(frame * w).  k n is reduced modulo 1024 in integers first, so the angle is exact
+    to its last bit, and the zeros of the sine and the cosine (multiples of a quarter turn) are exact zeros."""
+    n = torch.arange(1024, dtype=torch.int64)
+    k = torch.arange(513, dtype=torch.int64)[:, None]
+    r = torch.remainder(k * n[None, :], 1024)
+    ang = 2.0 * math.pi * r.to(torch.float64) / 1024.0
+    cos = torch.where(r % 512 == 256, torch.zeros((), dtype=torch.float64), torch.cos(ang))
+    sin = torch.where(r % 512 == 0, torch.zeros((), dtype=torch.float64), torch.sin(ang))
+    win = torch.hann_window(1024, periodic=True, dtype=torch.float64)
+    return torch.cat([cos * win, sin * win], 0)
+
+
+def ecapa_mel_spec_filterbank(f_min: float = 0.0, f_max: float = 8000.0) -> torch.Tensor:
+    """torchaudio's melscale_fbanks(513, f_min, f_max, 80, 16000, "slaney", "slaney") as (80, 513) f64
+    (``slaney_mel_filterbank``)."""
+    return slaney_mel_filterbank(80, 1024, 16000, float(f_min), float(f_max))
+
+
+class PackedEcapaMel:
+    """``dz_ecm_weights`` + the tensors behind it: ``PackedEcapa``'s network (the same checkpoint keys, packed by the
+    same code), the Hann-windowed DFT of 1024 samples built in float64 as one GEMM operand (1152 x 1024, for "f16x3"
+    also as split-f16 planes) and the slaney mel bank (128 x 544, exact f32).  ``features``: ``ecapa_mel_features``."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], device: torch.device, precision: str = "f32",
+                 min_num_samples: int = ECAPA_MEL_MIN_NUM_SAMPLES, **features):
+        assert precision in PRECISIONS, precision
+        split = precision == "f16x3"
+        self.features = ecapa_mel_features(**features)
+        if int(min_num_samples) <= 512:
+            raise ValueError(f"ecapa-mel: min_num_samples={min_num_samples} — the centred STFT reflects 512 samples, "
+                             "which needs more than 512")
+        pk = _Packed(device)
+        w = _lib.EcmWeights()
+        dft = _pad2(ecapa_mel_spec_dft().float(), 1152, 1024)
+        w.dft = pk.put(dft)
+        if split:
+            w.dft_split = pk.put_split(dft, "Hann-windowed DFT (1024)")
+        bank = ecapa_mel_spec_filterbank(self.features["f_min"], self.features["f_max"])
+        w.mel = pk.put(_pad2(bank.float(), 128, 544))
+        w.min_num_samples = int(min_num_samples)
+        _pack_ecapa_network(sd, pk, w.net, split)
         self.struct, self.pack = w, pk
 
 
@@ -904,18 +990,26 @@ def titanet_dft_matrices() -> torch.Tensor:
     return torch.cat([torch.cos(ang) * win, torch.sin(ang) * win], 0)
 
 
-def titanet_mel_filterbank() -> torch.Tensor:
-    """librosa.filters.mel(sr=16000, n_fft=512, n_mels=80, fmin=0, fmax=8000, htk=False, norm="slaney") as (80, 257)
-    f64: the slaney mel scale (linear below 1 kHz, logarithmic above), triangles normalised to unit area."""
+def slaney_mel_filterbank(n_mels: int, n_fft: int, sample_rate: int, f_min: float, f_max: float) -> torch.Tensor:
+    """The slaney mel bank — librosa.filters.mel(htk=False, norm="slaney"), torchaudio's melscale_fbanks(norm="slaney",
+    mel_scale="slaney") — as (n_mels, n_fft // 2 + 1) f64: a mel scale linear below 1 kHz (200 / 3 Hz per mel) and
+    logarithmic above (27 mels per factor 6.4), n_mels + 2 points equally spaced on it between f_min and f_max,
+    triangles between them over the bin frequencies, each scaled to unit area (2 / its width in Hz)."""
     f_sp, min_log_hz = 200.0 / 3.0, 1000.0
     min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
-    top = min_log_mel + math.log(8000.0 / min_log_hz) / logstep
-    mels = torch.linspace(0.0, top, 82, dtype=torch.float64)
+    to_mel = lambda f: f / f_sp if f < min_log_hz else min_log_mel + math.log(f / min_log_hz) / logstep
+    mels = torch.linspace(to_mel(f_min), to_mel(f_max), n_mels + 2, dtype=torch.float64)
     hz = torch.where(mels < min_log_mel, mels * f_sp, min_log_hz * torch.exp(logstep * (mels - min_log_mel)))
-    freqs = torch.linspace(0.0, 8000.0, 257, dtype=torch.float64)
+    freqs = torch.linspace(0.0, sample_rate / 2, n_fft // 2 + 1, dtype=torch.float64)
     lower = (freqs[None, :] - hz[:-2, None]) / (hz[1:-1] - hz[:-2])[:, None]
     upper = (hz[2:, None] - freqs[None, :]) / (hz[2:] - hz[1:-1])[:, None]
     return torch.clamp(torch.minimum(lower, upper), min=0.0) * (2.0 / (hz[2:] - hz[:-2]))[:, None]
+
+
+def titanet_mel_filterbank() -> torch.Tensor:
+    """librosa.filters.mel(sr=16000, n_fft=512, n_mels=80, fmin=0, fmax=8000, htk=False, norm="slaney") as (80, 257)
+    f64 (``slaney_mel_filterbank``)."""
+    return slaney_mel_filterbank(80, 512, 16000, 0.0, 8000.0)
 
 
 def fold_pointwise_bn(w: torch.Tensor, bn: Dict[str, torch.Tensor], eps: float):

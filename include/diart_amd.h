@@ -281,6 +281,41 @@ int dz_ecapa_forward_groups(dz_ecapa* e, const float* d_wave, long long wave_str
 int dz_ecapa_peek(dz_ecapa* e, int which, const void** d_ptr, long long* count, int* frames);
 int dz_ecapa_destroy(dz_ecapa* e);
 
+/* ---- mel-spectrogram ECAPA-TDNN (speechbrain/spkrec-ecapa-voxceleb-mel-spec) behind the same masked call:
+ * waveform (N,1,S), masks (N,Fw) or NULL -> (N,192), not normalised.  The network is dz_ecapa's (net); the front
+ * end is torchaudio's MelSpectrogram as speechbrain's HifiGAN mel_spectogram sets it up — n_fft = win_length = 1024,
+ * hop 256, periodic Hann, centred with reflect padding of the batch zero-padded to the longest kept row lmax of the
+ * call (of the group, for dz_ecm_forward_groups), magnitude, 80 slaney mel bins — then log(max(x, 1e-5)) and the
+ * sentence mean over round(float32(len / lmax) * T) frames, T = 1 + lmax / 256.  Rows below min_num_samples (or with
+ * a NaN / Inf kept sample) are NaN, a group whose longest row is below it is all NaN.  DESIGN.md 4.15.             */
+typedef struct {
+    dz_ecapa_weights net;   /* block0 .. fc and zeros as dz_ecapa_weights; its dft / mel / dft_split are not read */
+    const float* dft;       /* [1152][1024] Hann-windowed DFT: rows 0..512 cos, 513..1025 sin, zero rows behind   */
+    const void* dft_split;  /* optional split-f16 planes [2][1152][1024] of dft: the STFT then runs on dz_k_gemm_split */
+    const float* mel;       /* [128][544] slaney mel bank [mel][bin], zero padded                                  */
+    int min_num_samples;    /* > 512 (the reflect padding of the STFT)                                             */
+} dz_ecm_weights;
+typedef struct dz_ecm dz_ecm;
+int dz_ecm_abi_size(void);                /* sizeof(dz_ecm_weights) of the library */
+int dz_ecm_frames_for(int num_samples);   /* 1 + S / 256 */
+int dz_ecm_create(dz_ctx* ctx, const dz_ecm_weights* w, int max_rows, int num_samples, dz_ecm** out);
+/* one call of n_rows rows = one group: no synchronisation, the geometry is derived on the device */
+int dz_ecm_forward(dz_ecm* m, const float* d_wave, long long wave_stride, const float* d_masks, int n_rows,
+                   int mask_frames, float* d_out, void* stream);
+/* n_groups groups of rows_per_group (K) rows as dz_ecapa_forward_groups: row g*K + k reads waveform row g and mask
+ * row g*K + k -> d_out (G*K, 192).  A group's rows are what dz_ecm_forward returns for those K rows alone.         */
+int dz_ecm_forward_groups(dz_ecm* m, const float* d_wave, long long wave_stride, const float* d_masks,
+                          int n_groups, int rows_per_group, int mask_frames, int normalize, float* d_out,
+                          void* stream);
+/* intermediates of the LAST forward, every buffer laid out with the handle's Tc = 1 + num_samples / 256 frames per
+ * row (*frames receives Tc; frames at or past a row's own count, buffer 8, are padding):  0 features (N,Tc,80)
+ * 1 block0 (N,Tc,1024)  2 ASP logits (N,Tc,3072)  3 mfa (N,Tc,3072)  4 pooled (N,6144)  5 kept-sample counts (N)
+ * int32, -(count + 1) for a row with a NaN / Inf sample  6 nvalid (N) int32  7 nmask (N) int32  8 the row's frame
+ * count 1 + lmax / 256 of its group (N) int32 (6 - 8 are 0 for a group whose rows are all too short)  9 lmax of
+ * the row's group (N) int32  10 the magnitude spectrum (N,Tc,544), bins 0..512, zeros behind.                    */
+int dz_ecm_peek(dz_ecm* m, int which, const void** d_ptr, long long* count, int* frames);
+int dz_ecm_destroy(dz_ecm* m);
+
 /* ---- WeSpeaker ResNet34 embedding (pyannote/wespeaker-voxceleb-resnet34-LM, pyannote.audio 3.1's
  * WeSpeakerResNet34): the callable behind EmbeddingModel.__call__ for that checkpoint, reached in the reference
  * through PyannoteLoader (diart src/diart/models.py:42-59) and called as

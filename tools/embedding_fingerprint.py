@@ -1,9 +1,9 @@
-"""SHA-256 fingerprints of the six speaker embeddings and the segmentation: the proof that a change to host code left
+"""SHA-256 fingerprints of the seven speaker embeddings and the segmentation: the proof that a change to host code left
 every bit alone.
 
-    python tools/embedding_fingerprint.py [--models ecapa,sbx,sbr,titanet,wespeaker,xvector,segmentation] [--precisions f16x3,f32] [--out FILE]
+    python tools/embedding_fingerprint.py [--models ecapa,ecapa-mel,sbx,sbr,titanet,wespeaker,xvector,segmentation] [--precisions f16x3,f32] [--out FILE]
 
-For each of ``HipEcapaEmbedding``, ``HipSbXvectorEmbedding``, ``HipSbResNetEmbedding``, ``HipTitaNetEmbedding``, ``HipWeSpeakerEmbedding`` and
+For each of ``HipEcapaEmbedding``, ``HipEcapaMelEmbedding``, ``HipSbXvectorEmbedding``, ``HipSbResNetEmbedding``, ``HipTitaNetEmbedding``, ``HipWeSpeakerEmbedding`` and
 ``HipEmbedding`` on ``diart_amd.synth``'s synthetic state, in both precisions, three calls on fixed inputs:
 
 * ``rows_masked``: the rows forward with masks / weights, N = 5 rows of 16000 samples, Fw = 50.  Row 0 is all ones,
@@ -47,6 +47,7 @@ def models():
     from diart_amd import models as M, synth
     # name -> (class, synthetic state, samples the masks must keep (0: the matrix is pooling weights), forward_multi?)
     return {"ecapa": (M.HipEcapaEmbedding, synth.synth_ecapa_state, 640, False),
+            "ecapa-mel": (M.HipEcapaMelEmbedding, synth.synth_ecapa_state, 1024, False),
             "sbx": (M.HipSbXvectorEmbedding, synth.synth_sb_xvector_state, 480, False),
             "sbr": (M.HipSbResNetEmbedding, synth.synth_sb_resnet_state, 3, False),
             "titanet": (M.HipTitaNetEmbedding, synth.synth_titanet_state, 257, False),
@@ -166,7 +167,7 @@ def fingerprint_segmentation(prec: str, dev) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--models", default="ecapa,sbx,sbr,titanet,wespeaker,xvector,segmentation")
+    ap.add_argument("--models", default="ecapa,ecapa-mel,sbx,sbr,titanet,wespeaker,xvector,segmentation")
     ap.add_argument("--precisions", default="f16x3,f32")
     ap.add_argument("--out", default="")
     a = ap.parse_args()

@@ -116,7 +116,10 @@ def main():
                                        "a8 XVectorSincNet forward": "pinned on real weights" if green else "FAILED on real weights",
                                        "a9 ECAPA (config 3)": "not covered by this tool (needs speechbrain's checkpoint: tests/test_gpu_ecapa.py)",
                                        "NeMo TitaNet-L": "not covered by this tool (needs the .nemo archive: synthetic-weight parity in "
-                                                         "tests/test_gpu_titanet.py; the (R) switches of DESIGN.md 4.12 are unpinned)"}
+                                                         "tests/test_gpu_titanet.py; the (R) switches of DESIGN.md 4.12 are unpinned)",
+                                       "mel-spectrogram ECAPA": "not covered by this tool (needs speechbrain's checkpoint and hyperparams.yaml: "
+                                                                "synthetic-weight parity in tests/test_gpu_ecapa_mel.py; the (R) points of "
+                                                                "DESIGN.md 4.15 are unpinned)"}
             print(f"[verify_real] coverage rows: {report['coverage_rows']}", flush=True)
         if not args.ami:
             print(json.dumps(report, indent=1))
