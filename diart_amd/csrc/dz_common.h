@@ -589,8 +589,10 @@ int dz_launch_mask_compact(const float* wave, long long stride, int S, const flo
 // per-group geometry of dz_ecapa_forward_groups (k_ecapa.hip: ecapa_geometry_kernel)
 int dz_launch_ecapa_geometry(const int* lens, int G, int K, int Tc, int min_samples, int hop, int* nvalid,
                              int* nmask, int* tooshort, int* tdev, int* rv, int* rm, int* rt, hipStream_t st);
-int dz_launch_power(const float* spec, int lds, long long rows, float* pw, hipStream_t st);
-int dz_launch_fbank_post(const float* melp, int T, int rows, const int* nvalid, float* feats,
+// spec [rows][lds] = (re | im) of `bins` (201 or 257) bins each -> pw [rows][bins rounded up to 4]
+int dz_launch_power(const float* spec, int lds, int bins, long long rows, float* pw, hipStream_t st);
+// n_mels: 80 (ECAPA, the speechbrain ResNet) or 24 (the speechbrain x-vector)
+int dz_launch_fbank_post(const float* melp, int n_mels, int T, int rows, const int* nvalid, float* feats,
                          hipStream_t st, const int* tdev = nullptr);
 int dz_launch_se_mean(const float* x, int T, int C, int ldx, int rows, const int* nmask, float* s,
                       hipStream_t st);
@@ -603,9 +605,7 @@ int dz_launch_asp_gstats(const float* x, int T, int C, int rows, const int* nmas
 int dz_launch_asp_pool(const float* x, const float* logit, int T, int C, int rows, const int* nmask,
                        float* pooled, hipStream_t st);
 int dz_launch_nan_rows(float* out, int rows, int dim, const int* flags, hipStream_t st);
-// speechbrain x-vector (sbx_api.hip): fbank_post for n_mels (24) bins; StatisticsPooling over nvalid[row] frames
-int dz_launch_fbank_post_mels(const float* melp, int n_mels, int T, int rows, const int* nvalid, float* feats,
-                              hipStream_t st, const int* tdev = nullptr);
+// speechbrain x-vector (sbx_api.hip): StatisticsPooling over nvalid[row] frames
 int dz_launch_sb_stats_pool(const float* x, int T, int C, int ldx, int rows, const int* nvalid, float mean_bias,
                             float std_bias, float* pooled, hipStream_t st);
 
@@ -641,6 +641,17 @@ struct DzConv2d {
     int* oflag;
     const int* ext;
 };
+// the descriptor of one layer: Fi x Ti are X's two spatial extents (slow, fast).  (A stride below 1 leaves Fo = To =
+// 0; the launcher refuses a stride outside 1 / 2 before it reads them.)
+inline DzConv2d dz_conv2d(const float* W, const void* Wsplit, const float* bias, const float* X, int B, int Fi, int Ti,
+                          int Cin, int Cout, int taps, int stride, const float* R, int relu, const int* ext, float* Y) {
+    DzConv2d p = {};
+    p.X = X; p.W = W; p.Wsplit = Wsplit; p.bias = bias; p.R = R; p.Y = Y; p.ext = ext;
+    p.B = B; p.Fi = Fi; p.Ti = Ti; p.Cin = Cin; p.Cout = Cout; p.taps = taps; p.stride = stride; p.relu = relu;
+    p.Fo = stride >= 1 ? (Fi - 1) / stride + 1 : 0;
+    p.To = stride >= 1 ? (Ti - 1) / stride + 1 : 0;
+    return p;
+}
 int dz_launch_conv2d(const DzConv2d& p, hipStream_t st);
 
 // k_sb_resnet.hip -----------------------------------------------------------

@@ -1,6 +1,6 @@
-// The launch vocabulary of the handles (seg_api.hip, xvec_api.hip, ecapa_api.hip, sbx_api.hip, titanet_api.hip,
-// wespeaker_api.hip): one builder for the GEMM descriptor, the launch sequences two models share, and the entry
-// points of a handle that owns a DzRowGeometry and one arena.  Host code only.
+// The launch vocabulary of the handles (seg_api.hip, xvec_api.hip, ecapa_api.hip, ecm_api.hip, sbx_api.hip,
+// sbr_api.hip, titanet_api.hip, wespeaker_api.hip): one builder for the GEMM descriptor, the launch sequences two
+// models share, and the entry points of a handle that owns a DzRowGeometry and one arena.  Host code only.
 #pragma once
 #include "dz_common.h"
 
@@ -140,7 +140,7 @@ inline int dz_fbank_front(const dz_layer& dft, const dz_layer& mel, const float*
     if ((rc = DzGemm::conv1d(dft, sig, 160, N, T, 400, spec, 404, 402, DZ_EPI_BIAS).xstride(lstride, (long long)T * 404)
                   .padded(416, 448).prof(tag, N).run(st)))
         return rc;
-    { DzProfScope ps(tag, N); if ((rc = dz_launch_power(spec, 404, NT, pw, st))) return rc; }
+    { DzProfScope ps(tag, N); if ((rc = dz_launch_power(spec, 404, 201, NT, pw, st))) return rc; }
     return DzGemm::dense(mel, pw, 204, NT, 204, melp, nmel, nmel, DZ_EPI_BIAS).padded(224, mel_npad).prof(tag, N).run(st);
 }
 
@@ -185,8 +185,8 @@ struct DzEcapaTrunk {
 };
 
 // ---------------------------------------------------------------------------
-// entry points of a handle H {dz_ctx* ctx; W w; int Nm; DzRowGeometry geo; char* arena; ...} (dz_sbx, dz_ttn,
-// dz_ecapa).  `who`: the public function, for the error strings.
+// entry points of a handle H {dz_ctx* ctx; W w; int Nm; DzRowGeometry geo; char* arena; ...} (dz_sbx, dz_sbr,
+// dz_ttn, dz_ecapa, dz_ecm).  `who`: the public function, for the error strings.
 // ---------------------------------------------------------------------------
 template <typename H>
 int dz_handle_destroy(H* h) {

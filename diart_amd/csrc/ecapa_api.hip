@@ -207,7 +207,7 @@ static int ecapa_network(dz_ecapa* e, int N, int T, const int* tdev, float* d_ou
     if ((rc = dz_fbank_front(dft, mel, e->geo.sig, e->geo.lstride, N, T, e->spec, e->pw, 80, 128, e->melp, st,
                              DZ_T_ECAPA_FBANK)))
         return rc;
-    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, T, N, e->geo.nvalid, e->tr.feats, st, tdev))) return rc; }
+    { DzProfScope ps(DZ_T_ECAPA_FBANK, N); if ((rc = dz_launch_fbank_post(e->melp, 80, T, N, e->geo.nvalid, e->tr.feats, st, tdev))) return rc; }
 
     return e->tr.run(w, N, T, e->geo.nmask, tdev, d_out, st);
 }

@@ -1,15 +1,17 @@
 // Kernels around the ECAPA-TDNN embedding (BASELINE.json config 3): everything that is not a
 // convolution / linear layer (those run on convgemm, k_convgemm.hip).
 //   mask_compact   PretrainedSpeakerEmbedding.__call__: nearest-resampled mask > 0.5 -> kept samples
-//   power          |STFT|^2 from the (re | im) GEMM output
+//   power          |STFT|^2 from the (re | im) GEMM output, 201 bins (n_fft 400) or 257 (TitaNet's n_fft 512)
 //   ecapa_geometry per-group batch geometry of the groups forward (frames, nvalid, nmask, flags) on the device
-//   fbank_post     10 log10 -> top_db clip against the row maximum -> sentence mean normalisation
+//   fbank_post_mels        10 log10 -> top_db clip against the row maximum -> sentence mean normalisation, for 80 mel
+//                          bins (ECAPA, the speechbrain ResNet) or 24 (the speechbrain x-vector)
 //   se_mean / se_apply     squeeze-excitation: masked time mean, gate * x + residual
+//   se_apply_planes        se_apply (or a plain copy) that also writes the f16 planes k_gemm_pre.hip reads
 //   asp_gstats / asp_pool  attentive statistics pooling: global context stats, masked softmax stats
+//   sb_stats_pool  the speechbrain x-vector's statistics pooling
 //   nan_rows       rows with fewer than min_num_samples kept samples -> NaN
-//   fbank_post_mels / sb_stats_pool   the speechbrain x-vector's 24-bin fbank tail and its statistics pooling
 // Third-party graph (speechbrain ECAPA_TDNN via pyannote's PretrainedSpeakerEmbedding) reached
-// from /root/reference/src/diart/models.py:59 and :262; SURVEY.md Appendix A.3.
+// from the reference's src/diart/models.py:59 and :262; SURVEY.md Appendix A.3.
 #include "dz_common.h"
 
 namespace {
@@ -133,16 +135,19 @@ __global__ void ecapa_geometry_kernel(const int* __restrict__ lens, int G, int K
     }
 }
 
-// spec [rows][lds] = (re[0..200] | im[0..200]) -> pw [rows][204] (cols 201..203 = 0)
+// spec [rows][lds] = (re[0..BINS-1] | im[0..BINS-1]) -> pw [rows][PITCH], PITCH = BINS rounded up to 4 (the columns
+// from BINS on = 0): 201 -> 204, 257 -> 260
+template <int BINS>
 __global__ void power_kernel(const float* __restrict__ spec, int lds, long long rows,
                              float* __restrict__ pw) {
+    constexpr int PITCH = (BINS + 3) / 4 * 4;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * 204) return;
-    const long long r = idx / 204;
-    const int j = (int)(idx - r * 204);
+    if (idx >= rows * PITCH) return;
+    const long long r = idx / PITCH;
+    const int j = (int)(idx - r * PITCH);
     float v = 0.f;
-    if (j < 201) {
-        const float re = spec[r * lds + j], im = spec[r * lds + 201 + j];
+    if (j < BINS) {
+        const float re = spec[r * lds + j], im = spec[r * lds + BINS + j];
         v = re * re + im * im;
     }
     pw[idx] = v;
@@ -156,36 +161,41 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// mel power [row][T][80] -> features [row][T][80]:
+// mel power [row][T][NM] -> features [row][T][NM], NM = 80 (ECAPA, the speechbrain ResNet) or 24 (x-vector):
 //   x_db = 10 log10(max(x, 1e-10)); x_db = max(x_db, rowmax - 80); x_db -= mean over the first
 //   nvalid[row] frames (speechbrain Filterbank top_db + InputNormalization("sentence")).  Rows are T frames
 //   apart; the row maximum is taken over tdev[row] of them (the row's own frames), or all T if tdev is NULL.
-__global__ __launch_bounds__(256) void fbank_post_kernel(const float* __restrict__ melp, int T,
-                                                         const int* __restrict__ nvalid,
-                                                         const int* __restrict__ tdev,
-                                                         float* __restrict__ feats) {
+// The per-mel sums over the nvalid frames are split over P = 240 / NM thread groups (frames part, part + P, ...) and
+// combined in the fixed order 0, 1, ..., P - 1.
+template <int NM>
+__global__ __launch_bounds__(256) void fbank_post_mels_kernel(const float* __restrict__ melp, int T,
+                                                              const int* __restrict__ nvalid,
+                                                              const int* __restrict__ tdev,
+                                                              float* __restrict__ feats) {
+    constexpr int P = 240 / NM;
     __shared__ float red[4];
-    __shared__ float msum[3][80];
+    __shared__ float msum[P][NM];
     const int row = blockIdx.x, tid = threadIdx.x;
-    const float* x = melp + (long long)row * T * 80;
-    float* y = feats + (long long)row * T * 80;
+    const float* x = melp + (long long)row * T * NM;
+    float* y = feats + (long long)row * T * NM;
     float mx = -INFINITY;
     const int Tg = tdev ? tdev[row] : T;
-    for (int i = tid; i < Tg * 80; i += 256) mx = fmaxf(mx, 10.f * log10f(fmaxf(x[i], 1e-10f)));
+    for (int i = tid; i < Tg * NM; i += 256) mx = fmaxf(mx, 10.f * log10f(fmaxf(x[i], 1e-10f)));
     const float floor_db = block_max(mx, red) - 80.f;
-    // per-mel mean over the valid frames: thread (m = tid % 80, part = tid / 80) for tid < 240
     const int nv = nvalid[row];
-    if (tid < 240) {
-        const int m = tid % 80, part = tid / 80;
+    if (tid < P * NM) {
+        const int m = tid % NM, part = tid / NM;
         float s = 0.f;
-        for (int t = part; t < nv; t += 3) s += fmaxf(10.f * log10f(fmaxf(x[t * 80 + m], 1e-10f)), floor_db);
+        for (int t = part; t < nv; t += P) s += fmaxf(10.f * log10f(fmaxf(x[t * NM + m], 1e-10f)), floor_db);
         msum[part][m] = s;
     }
     __syncthreads();
-    for (int i = tid; i < T * 80; i += 256) {
-        const int m = i % 80;
-        const float mean = ((msum[0][m] + msum[1][m]) + msum[2][m]) / (float)nv;
-        y[i] = fmaxf(10.f * log10f(fmaxf(x[i], 1e-10f)), floor_db) - mean;
+    for (int i = tid; i < T * NM; i += 256) {
+        const int m = i % NM;
+        float acc = msum[0][m];
+#pragma unroll
+        for (int q = 1; q < P; ++q) acc += msum[q][m];
+        y[i] = fmaxf(10.f * log10f(fmaxf(x[i], 1e-10f)), floor_db) - acc / (float)nv;
     }
 }
 
@@ -384,41 +394,6 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const float* __restrict__
     }
 }
 
-// fbank_post_kernel for NM mel bins (speechbrain x-vector: 24): the same arithmetic over melp [row][T][NM]; the
-// per-mel sums over the nvalid frames are split over P = 240 / NM thread groups (frames part, part + P, ...) and
-// combined in the fixed order 0, 1, ..., P - 1.
-template <int NM>
-__global__ __launch_bounds__(256) void fbank_post_mels_kernel(const float* __restrict__ melp, int T,
-                                                              const int* __restrict__ nvalid,
-                                                              const int* __restrict__ tdev,
-                                                              float* __restrict__ feats) {
-    constexpr int P = 240 / NM;
-    __shared__ float red[4];
-    __shared__ float msum[P][NM];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const float* x = melp + (long long)row * T * NM;
-    float* y = feats + (long long)row * T * NM;
-    float mx = -INFINITY;
-    const int Tg = tdev ? tdev[row] : T;
-    for (int i = tid; i < Tg * NM; i += 256) mx = fmaxf(mx, 10.f * log10f(fmaxf(x[i], 1e-10f)));
-    const float floor_db = block_max(mx, red) - 80.f;
-    const int nv = nvalid[row];
-    if (tid < P * NM) {
-        const int m = tid % NM, part = tid / NM;
-        float s = 0.f;
-        for (int t = part; t < nv; t += P) s += fmaxf(10.f * log10f(fmaxf(x[t * NM + m], 1e-10f)), floor_db);
-        msum[part][m] = s;
-    }
-    __syncthreads();
-    for (int i = tid; i < T * NM; i += 256) {
-        const int m = i % NM;
-        float acc = 0.f;
-#pragma unroll
-        for (int q = 0; q < P; ++q) acc += msum[q][m];
-        y[i] = fmaxf(10.f * log10f(fmaxf(x[i], 1e-10f)), floor_db) - acc / (float)nv;
-    }
-}
-
 // speechbrain StatisticsPooling with relative lengths over x [row][T][ldx], C channels: n = nvalid[row] frames,
 //   pooled[row][c] = mean + mean_bias,  pooled[row][C + c] = sqrt(sum (x - mean)^2 / (n - 1)) + std_bias
 // (torch.std is unbiased: n = 1 gives 0 / 0 = NaN, as torch does).  Two passes over the frames (mean, then the
@@ -476,10 +451,11 @@ int dz_launch_mask_compact(const float* wave, long long stride, int S, const flo
     DZ_HIP(hipGetLastError());
     return 0;
 }
-int dz_launch_power(const float* spec, int lds, long long rows, float* pw, hipStream_t st) {
-    const long long n = rows * 204;
-    DZ_LAUNCH(power_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, spec, lds,
-                       rows, pw);
+int dz_launch_power(const float* spec, int lds, int bins, long long rows, float* pw, hipStream_t st) {
+    DZ_REQUIRE(bins == 201 || bins == 257, "power: %d bins (built for 201 and 257)", bins);
+    const dim3 grid((unsigned)((rows * ((bins + 3) / 4 * 4) + 255) / 256));
+    if (bins == 201) DZ_LAUNCH(power_kernel<201>, grid, dim3(256), 0, st, spec, lds, rows, pw);
+    else DZ_LAUNCH(power_kernel<257>, grid, dim3(256), 0, st, spec, lds, rows, pw);
     DZ_HIP(hipGetLastError());
     return 0;
 }
@@ -491,16 +467,11 @@ int dz_launch_ecapa_geometry(const int* lens, int G, int K, int Tc, int min_samp
     DZ_HIP(hipGetLastError());
     return 0;
 }
-int dz_launch_fbank_post(const float* melp, int T, int rows, const int* nvalid, float* feats,
+int dz_launch_fbank_post(const float* melp, int n_mels, int T, int rows, const int* nvalid, float* feats,
                          hipStream_t st, const int* tdev) {
-    DZ_LAUNCH(fbank_post_kernel, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
-    DZ_HIP(hipGetLastError());
-    return 0;
-}
-int dz_launch_fbank_post_mels(const float* melp, int n_mels, int T, int rows, const int* nvalid, float* feats,
-                              hipStream_t st, const int* tdev) {
-    DZ_REQUIRE(n_mels == 24, "fbank_post_mels: %d mel bins (built for 24; 80 is dz_launch_fbank_post)", n_mels);
-    DZ_LAUNCH(fbank_post_mels_kernel<24>, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
+    DZ_REQUIRE(n_mels == 24 || n_mels == 80, "fbank_post: %d mel bins (built for 24 and 80)", n_mels);
+    if (n_mels == 24) DZ_LAUNCH(fbank_post_mels_kernel<24>, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
+    else DZ_LAUNCH(fbank_post_mels_kernel<80>, dim3(rows), dim3(256), 0, st, melp, T, nvalid, tdev, feats);
     DZ_HIP(hipGetLastError());
     return 0;
 }

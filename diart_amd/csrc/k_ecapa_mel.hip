@@ -60,7 +60,7 @@ __global__ void ecm_magnitude_kernel(const float* __restrict__ spec, long long r
 
 // mel magnitudes [row][T][80] -> features [row][T][80]: x = log(max(x, 1e-5)), minus the per-mel mean over the first
 // nvalid[row] frames (InputNormalization("sentence", std_norm = False)).  The sums are split over 3 thread groups
-// (frames part, part + 3, ...) and combined in the fixed order (0 + 1) + 2, as fbank_post_kernel does.
+// (frames part, part + 3, ...) and combined in the fixed order (0 + 1) + 2, as fbank_post_mels_kernel<80> does.
 __global__ __launch_bounds__(256) void ecm_post_kernel(const float* __restrict__ melp, int T,
                                                        const int* __restrict__ nvalid, float* __restrict__ feats) {
     __shared__ float msum[3][NMEL];

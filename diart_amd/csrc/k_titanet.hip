@@ -1,9 +1,9 @@
 // Kernels around the NeMo TitaNet-L embedding (include/diart_amd.h: dz_ttn_*): everything that is not
 // a GEMM.  The pointwise convolutions, the DFT, the mel bank and the pooling's attention run on the wide GEMMs
-// (k_gemm_pre.hip / k_gemm_f32.hip / k_gemm_split.hip / k_convgemm.hip), the pooling itself on k_ecapa.hip.
+// (k_gemm_pre.hip / k_gemm_f32.hip / k_gemm_split.hip / k_convgemm.hip), the pooling itself and the power spectrum
+// (power_kernel<257>) on k_ecapa.hip.
 //   ttn_geometry   per-group geometry on the device: NaN flags, each row's valid frames and padded length
 //   ttn_prep       pre-emphasis, masked at the row's length, + the centred STFT's padding (reflect | zeros)
-//   ttn_power      |STFT|^2 from the (re | im) GEMM output, 257 bins
 //   ttn_norm       log(mel + 2^-24) -> per-feature mean / unbiased std over the row's valid frames, zeros past them
 //   ttn_depthwise  masked depthwise convolution, written as the next pointwise GEMM's operand
 //   ttn_se_fc      squeeze-excitation: Linear(C, C / 8) -> ReLU -> Linear(C / 8, C) -> sigmoid
@@ -67,20 +67,6 @@ __global__ __launch_bounds__(256) void ttn_prep_kernel(const float* __restrict__
     float v = 0.f;
     if (j >= 0 && j < len) v = j > 0 ? x[j] - PREEMPH * x[j - 1] : x[0];
     out[(long long)row * stride + p] = v;
-}
-
-// spec [rows][lds] = (re[0..256] | im[0..256]) -> pw [rows][260] (columns 257 .. 259 = 0)
-__global__ void ttn_power_kernel(const float* __restrict__ spec, int lds, long long rows, float* __restrict__ pw) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * 260) return;
-    const long long r = idx / 260;
-    const int j = (int)(idx - r * 260);
-    float v = 0.f;
-    if (j < 257) {
-        const float re = spec[r * lds + j], im = spec[r * lds + 257 + j];
-        v = re * re + im * im;
-    }
-    pw[idx] = v;
 }
 
 // mel power [row][T][80] -> features [row][T][80]: log(x + 2^-24), minus the feature's mean over the row's n valid
@@ -309,13 +295,6 @@ int dz_launch_ttn_prep(const float* sig, long long stride, int rows, const int* 
                        float* out, hipStream_t st) {
     DZ_LAUNCH(ttn_prep_kernel, dim3((unsigned)((stride + 255) / 256), rows), dim3(256), 0, st, sig, stride, elen, plen,
               reflect, out);
-    DZ_HIP(hipGetLastError());
-    return 0;
-}
-
-int dz_launch_ttn_power(const float* spec, int lds, long long rows, float* pw, hipStream_t st) {
-    const long long n = rows * 260;
-    DZ_LAUNCH(ttn_power_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, spec, lds, rows, pw);
     DZ_HIP(hipGetLastError());
     return 0;
 }

@@ -122,14 +122,9 @@ extern "C" int dz_sbr_destroy(dz_sbr* m) { return dz_handle_destroy(m); }
 
 static int sbr_conv(const dz_wsp_conv& c, const float* X, int n, int Ti, int Fi, int Cin, int Cout, int taps, int stride,
                     int relu, const int* ext_out, float* Y, hipStream_t st) {
-    DzConv2d p;
-    memset(&p, 0, sizeof(p));
     // (time in DzConv2d's F slot, the slow spatial axis; frequency in its T slot)
-    p.X = X; p.W = c.w; p.Wsplit = c.wsplit; p.bias = c.b; p.Y = Y; p.ext = ext_out;
-    p.B = n; p.Fi = Ti; p.Ti = Fi; p.Cin = Cin; p.Cout = Cout; p.taps = taps; p.stride = stride; p.relu = relu;
-    p.Fo = down(Ti, stride);
-    p.To = down(Fi, stride);
-    return dz_launch_conv2d(p, st);
+    return dz_launch_conv2d(dz_conv2d(c.w, c.wsplit, c.b, X, n, Ti, Fi, Cin, Cout, taps, stride, nullptr, relu, ext_out, Y),
+                            st);
 }
 
 // the stem, the four layers and the attention pooling of rows [r0, r0 + n) -> pooled rows [r0, r0 + n)
@@ -190,7 +185,7 @@ static int sbr_run(dz_sbr* m, const float* d_wave, long long wave_stride, const 
     const dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
     const dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
     if ((rc = dz_fbank_front(dft, mel, geo.sig, geo.lstride, N, T, m->spec, m->pw, NMEL, 128, m->melp, st))) return rc;
-    if ((rc = dz_launch_fbank_post(m->melp, T, N, geo.nvalid, m->feats, st, geo.tdev))) return rc;
+    if ((rc = dz_launch_fbank_post(m->melp, NMEL, T, N, geo.nvalid, m->feats, st, geo.tdev))) return rc;
     // ---- the trunk and the pooling, rows_per_pass rows at a time ---------------------------------------------------------
     for (int r0 = 0; r0 < N; r0 += m->P) {
         m->lastPass = N - r0 < m->P ? N - r0 : m->P;

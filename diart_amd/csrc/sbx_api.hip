@@ -66,7 +66,7 @@ static int sbx_run(dz_sbx* m, const float* d_wave, long long wave_stride, const 
     const dz_layer dft = {w.dft, w.zeros, nullptr, nullptr, w.dft_split};
     const dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
     if ((rc = dz_fbank_front(dft, mel, geo.sig, geo.lstride, N, T, m->spec, m->pw, NMEL, 64, m->melp, st))) return rc;
-    if ((rc = dz_launch_fbank_post_mels(m->melp, NMEL, T, N, geo.nvalid, m->feats, st, geo.tdev))) return rc;
+    if ((rc = dz_launch_fbank_post(m->melp, NMEL, T, N, geo.nvalid, m->feats, st, geo.tdev))) return rc;
     // ---- TDNN 1 - 5: Conv1d (reflect "same" at the row's own frame count) -> LeakyReLU -> BatchNorm ------------
     const float* xin = m->feats;
     int ldin = NMEL;

@@ -10,7 +10,6 @@ int dz_launch_ttn_geometry(const int* lens, int G, int K, int Tc, int S, int min
                            int* tooshort, int* elen, int* plen, int* frames, hipStream_t st);
 int dz_launch_ttn_prep(const float* sig, long long stride, int rows, const int* elen, const int* plen, int reflect,
                        float* out, hipStream_t st);
-int dz_launch_ttn_power(const float* spec, int lds, long long rows, float* pw, hipStream_t st);
 int dz_launch_ttn_norm(const float* melp, int T, int rows, const int* frames, float* feats, hipStream_t st);
 int dz_launch_ttn_depthwise(const float* x, int ldx, int Cin, const float* taps, int ktaps, const int* frames, int rows,
                             int T, int C, int relu, float* y, void* planes, long long plane, hipStream_t st);
@@ -119,7 +118,7 @@ static int ttn_run(dz_ttn* m, const float* d_wave, long long wave_stride, const 
     if ((rc = DzGemm::conv1d(dft, m->sig2, HOP, N, T, NWIN, m->spec, SPEC_LD, 2 * NBIN, DZ_EPI_BIAS)
                   .xstride(geo.lstride, (long long)T * SPEC_LD).padded(416, 640).run(st)))
         return rc;
-    if ((rc = dz_launch_ttn_power(m->spec, SPEC_LD, NT, m->pw, st))) return rc;
+    if ((rc = dz_launch_power(m->spec, SPEC_LD, 257, NT, m->pw, st))) return rc;
     const dz_layer mel = {w.mel, w.zeros, nullptr, nullptr, nullptr};
     if ((rc = DzGemm::dense(mel, m->pw, PW_LD, NT, PW_LD, m->melp, NMEL, NMEL, DZ_EPI_BIAS).padded(288, 128).run(st)))
         return rc;

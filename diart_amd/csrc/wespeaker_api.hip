@@ -72,13 +72,8 @@ extern "C" int dz_wsp_destroy(dz_wsp* m) { return dz_handle_destroy(m); }
 
 static int conv(const dz_wsp_conv& c, const float* X, int N, int Fi, int Ti, int Cin, int Cout, int taps, int stride,
                 const float* R, int relu, float* Y, hipStream_t st) {
-    DzConv2d p;
-    memset(&p, 0, sizeof(p));
-    p.X = X; p.W = c.w; p.Wsplit = c.wsplit; p.bias = c.b; p.R = R; p.Y = Y;
-    p.B = N; p.Fi = Fi; p.Ti = Ti; p.Cin = Cin; p.Cout = Cout; p.taps = taps; p.stride = stride; p.relu = relu;
-    p.Fo = (Fi - 1) / stride + 1;
-    p.To = (Ti - 1) / stride + 1;
-    return dz_launch_conv2d(p, st);
+    return dz_launch_conv2d(dz_conv2d(c.w, c.wsplit, c.b, X, N, Fi, Ti, Cin, Cout, taps, stride, R, relu, nullptr, Y),
+                            st);
 }
 
 // fbank -> trunk -> layer 4 output in m->L[3] for N rows
@@ -177,21 +172,23 @@ extern "C" int dz_wsp_forward_multi(dz_wsp* m, const float* d_wave, long long wa
     return dz_wsp_pool(m, d_weights, batch, num_speakers, weight_frames, normalize, d_out, stream);
 }
 
-// kernel-level entry point of k_conv2d.hip (parity tests): the launcher checks the operands
+// kernel-level entry points of k_conv2d.hip (parity tests): the launcher checks the operands
+static int k_conv2d(dz_ctx* ctx, const float* d_x, const float* d_w, const void* d_wsplit, const float* d_bias,
+                    const float* d_r, const int* d_ext, float* d_y, int batch, int fi, int ti, int cin, int cout,
+                    int taps, int stride, int relu, void* stream) {
+    DZ_HIP(hipSetDevice(ctx->device));
+    DzRangeScope range_scope(ctx->oflag_dev);
+    return dz_launch_conv2d(
+        dz_conv2d(d_w, d_wsplit, d_bias, d_x, batch, fi, ti, cin, cout, taps, stride, d_r, relu, d_ext, d_y),
+        (hipStream_t)stream);
+}
+
 extern "C" int dz_k_conv2d(dz_ctx* ctx, const float* d_x, const float* d_w, const void* d_wsplit, const float* d_bias,
                            const float* d_r, float* d_y, int batch, int fi, int ti, int cin, int cout, int taps,
                            int stride, int relu, void* stream) {
     DZ_REQUIRE(ctx != nullptr, "dz_k_conv2d: NULL context");
-    DZ_HIP(hipSetDevice(ctx->device));
-    DzRangeScope range_scope(ctx->oflag_dev);
-    DzConv2d p;
-    memset(&p, 0, sizeof(p));
-    p.X = d_x; p.W = d_w; p.Wsplit = d_wsplit; p.bias = d_bias; p.R = d_r; p.Y = d_y;
-    p.B = batch; p.Fi = fi; p.Ti = ti; p.Cin = cin; p.Cout = cout; p.taps = taps; p.stride = stride; p.relu = relu;
-    // (a stride outside 1 / 2 is refused by the launcher before it reads Fo / To)
-    p.Fo = stride >= 1 ? (fi - 1) / stride + 1 : 0;
-    p.To = stride >= 1 ? (ti - 1) / stride + 1 : 0;
-    return dz_launch_conv2d(p, (hipStream_t)stream);
+    return k_conv2d(ctx, d_x, d_w, d_wsplit, d_bias, d_r, nullptr, d_y, batch, fi, ti, cin, cout, taps, stride, relu,
+                    stream);
 }
 
 // the same with a row's live steps of the f axis (the masked instances; sbr_api.hip runs the trunk on them)
@@ -199,15 +196,8 @@ extern "C" int dz_k_conv2d_masked(dz_ctx* ctx, const float* d_x, const float* d_
                                   const float* d_bias, const float* d_r, const int* d_ext, float* d_y, int batch, int fi,
                                   int ti, int cin, int cout, int taps, int stride, int relu, void* stream) {
     DZ_REQUIRE(ctx != nullptr && d_ext != nullptr, "dz_k_conv2d_masked: NULL context or extents");
-    DZ_HIP(hipSetDevice(ctx->device));
-    DzRangeScope range_scope(ctx->oflag_dev);
-    DzConv2d p;
-    memset(&p, 0, sizeof(p));
-    p.X = d_x; p.W = d_w; p.Wsplit = d_wsplit; p.bias = d_bias; p.R = d_r; p.Y = d_y; p.ext = d_ext;
-    p.B = batch; p.Fi = fi; p.Ti = ti; p.Cin = cin; p.Cout = cout; p.taps = taps; p.stride = stride; p.relu = relu;
-    p.Fo = stride >= 1 ? (fi - 1) / stride + 1 : 0;
-    p.To = stride >= 1 ? (ti - 1) / stride + 1 : 0;
-    return dz_launch_conv2d(p, (hipStream_t)stream);
+    return k_conv2d(ctx, d_x, d_w, d_wsplit, d_bias, d_r, d_ext, d_y, batch, fi, ti, cin, cout, taps, stride, relu,
+                    stream);
 }
 
 extern "C" int dz_wsp_peek(dz_wsp* m, int which, const void** d_ptr, long long* count, int* frames) {
