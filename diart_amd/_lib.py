@@ -102,6 +102,12 @@ class SbrWeights(C.Structure):
                 ("n_blocks", C.c_int), ("stem_width", C.c_int), ("min_num_samples", C.c_int), ("rows_per_pass", C.c_int)]
 
 
+class TuneDesc(C.Structure):
+    _fields_ = [(n, vp) for n in ("seg", "emb", "pre_max", "pre_mean", "pre_flags", "chunk_off", "plan", "row_off",
+                                  "row_chunk", "hamming")] + [
+        (n, C.c_int) for n in ("N", "F", "K", "D", "G", "nwin", "total_chunks", "total_rows")]
+
+
 # name -> (restype, argtypes); must list every function of include/diart_amd.h
 SIGNATURES = {
     "dz_last_error": (C.c_char_p, []),
@@ -223,6 +229,13 @@ SIGNATURES = {
                                      C.c_int, vp, C.c_int]),
     "dz_file_step_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int,
                                      C.c_int, vp, C.c_double, vp, C.c_int, vp, vp, C.c_int]),
+    "dz_tune_abi_size": (C.c_int, []),
+    "dz_tune_plan": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp]),
+    "dz_tune_replay": (C.c_int, [vp, C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "dz_tune_replay_host": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp,
+                                      C.c_int, C.c_int]),
+    "dz_tune_score": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp,
+                                C.c_int]),
     "dz_rows_repeat": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, c_int_p]),
     # kernel-level entry points
     "dz_k_convgemm": (C.c_int, [vp, vp, vp]),
@@ -320,10 +333,11 @@ def load() -> C.CDLL:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
         for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights), ("dz_ttn", TtnWeights),
-                             ("dz_sbr", SbrWeights), ("dz_ecm", EcmWeights)):
+                             ("dz_sbr", SbrWeights), ("dz_ecm", EcmWeights), ("dz_tune", TuneDesc)):
             size = getattr(lib, f"{name}_abi_size")()
             if size != C.sizeof(struct):
-                raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({name}_weights) "
+                what = "dz_tune_desc" if struct is TuneDesc else f"{name}_weights"
+                raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({what}) "
                                     f"{size} (library) vs {C.sizeof(struct)} (this binding); rebuild it")
         _lib = lib
     return _lib

@@ -128,6 +128,13 @@ class SpeakerDiarization(base.Pipeline):
         got = waveforms[0].data.shape[0]
         assert all(w.data.shape[0] == got for w in waveforms), "chunks of different lengths in one batch"
         assert got == expected, f"Expected {expected} samples per chunk, but got {got}"
+        segmentations, embeddings = self.model_outputs(waveforms)
+        return self.finalise(waveforms, segmentations, embeddings)
+
+    def model_outputs(self, waveforms: Sequence[SlidingWindowFeature]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The model half of ``__call__``: segmentation ``(batch, frames, speakers)`` and overlap-aware embeddings
+        ``(batch, speakers, dim)`` of the chunks, on the host.  Nothing here depends on ``tau_active``, ``rho_update``
+        or ``delta_new``: ``optim.TuneCache`` keeps these outputs and replays ``finalise``'s half per trial."""
         # (batch, samples, channels) on the device, uploaded once for both blocks (blocks/utils.py)
         batch = windows_batch(waveforms, self.config.device)
 
@@ -140,7 +147,7 @@ class SpeakerDiarization(base.Pipeline):
         else:
             segmentations = self.segmentation(batch)
             embeddings = self.embedding(batch, segmentations)
-        return self.finalise(waveforms, segmentations, embeddings)
+        return segmentations, embeddings
 
     def finalise(self, waveforms: Sequence[SlidingWindowFeature], segmentations: torch.Tensor,
                  embeddings: torch.Tensor) -> Sequence[Tuple[Annotation, SlidingWindowFeature]]:

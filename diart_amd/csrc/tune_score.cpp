@@ -1,0 +1,349 @@
+// Host side of the hyper-parameter tuner:
+//
+//   dz_tune_plan         what the output tail (tail.cpp: Hamming aggregation, "loose" cropping) does at every step of a
+//                        file that does not depend on the scores: rows, buffers, cropped rows, the first-chunk prepend
+//   dz_tune_replay_host  T x N (trial, file) chains on host threads, either through the existing handles (dz_clu_step ->
+//                        dz_tail_step: the yardstick of the GPU kernels and the backend of a machine without a GPU) or
+//                        through tune_core.h, the text the kernels are compiled from
+//   dz_tune_score        diarization error rate components of every pair from the packed frame masks
+//                        (diart_amd/metrics.py DiarizationErrorRate, collar 0, overlap included; PredictionAccumulator's
+//                        gap merging), without building an Annotation
+#include "tune_core.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "hostpool.h"
+
+void dz_set_error(const char* fmt, ...);
+extern "C" const char* dz_last_error(void);
+
+namespace {
+
+// tail.cpp crop_range / samples_for, "loose"
+inline double seg_duration(double s, double e) { return e > s ? e - s : 0.0; }
+inline void crop_loose(double fs, double fe, double start, double res, long* first, long* count) {
+    *first = (long)ceil((fs - res - start) / res);
+    *count = (long)floor((seg_duration(fs, fe) + res) / res);
+}
+
+struct NoBarrier {
+    void operator()() const {}
+};
+
+struct Turn {
+    double s, e;
+    int is, ie;   // the cells that start at s and at e
+};
+
+}  // namespace
+
+extern "C" int dz_tune_plan(int chunks, int frames, double step, double latency, const double* starts,
+                            const double* resolution, int* plan, double* t0_out, double* res_out) {
+    if (chunks < 1 || frames < 1 || !(step > 0.0) || !(latency >= step) || !starts || !resolution || !plan || !t0_out ||
+        !res_out) {
+        dz_set_error("dz_tune_plan: bad arguments (latency must be >= step)");
+        return 2;
+    }
+    const int F = frames, nwin = (int)nearbyint(latency / step), stride = 4 + nwin;
+    for (int c = 0; c < chunks; ++c) {
+        if (!(resolution[c] > 0.0)) {
+            dz_set_error("dz_tune_plan: chunk %d has resolution %g", c, resolution[c]);
+            return 2;
+        }
+        int* p = plan + (size_t)c * stride;
+        const int nbuf = c + 1 < nwin ? c + 1 : nwin, b0 = c - nbuf + 1;
+        const double ext_end = starts[c] + (F - 1) * resolution[c] + resolution[c];
+        const double rs = ext_end - latency;
+        const double re = rs + step;
+        long first0, count;
+        crop_loose(rs, re, starts[b0], resolution[b0], &first0, &count);
+        bool ok = count >= 1 && count <= F + 2;
+        for (int b = 0; b < nwin; ++b) p[4 + b] = 0;
+        for (int b = 0; ok && b < nbuf; ++b) {
+            long first, cnt;
+            crop_loose(rs, re, starts[b0 + b], resolution[b0 + b], &first, &cnt);
+            ok = cnt == count && first > -(1l << 30) && first < (1l << 30);
+            p[4 + b] = (int)first;
+        }
+        int rows = (int)count, pre = 0, f1 = 0;
+        double out_start = rs, out_res = ok ? seg_duration(rs, re) / rows : 0.0;
+        if (ok && nbuf == 1 && starts[b0] == 0.0) {
+            long lf1, c1;
+            crop_loose(0.0, re, starts[b0], resolution[b0], &lf1, &c1);
+            ok = c1 >= rows && c1 <= F + 2 && lf1 > -(1l << 30) && lf1 < (1l << 30);
+            pre = (int)c1 - rows;
+            f1 = (int)lf1;
+            out_start = 0.0;
+            out_res = re / (double)(int)c1;
+        }
+        if (!ok) {
+            dz_set_error("dz_tune_plan: the output region of step %d does not map onto the frame grid of every buffer", c);
+            return 4;
+        }
+        p[0] = rows;
+        p[1] = pre;
+        p[2] = f1;
+        p[3] = nbuf;
+        t0_out[c] = out_start;
+        res_out[c] = out_res;
+    }
+    return 0;
+}
+
+extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams, int trials, double step, double latency,
+                                   const double* starts, const double* resolution, signed char* assign, int* status,
+                                   unsigned* bits, int use_core, int num_threads) {
+    if (!d || !hparams || !assign || !status || !bits || trials < 1 || (!use_core && (!starts || !resolution))) {
+        dz_set_error("dz_tune_replay_host: bad arguments");
+        return 2;
+    }
+    if (d->K < 1 || d->K > TC_KMAX || d->G < 1 || d->G > TC_GMAX || d->N < 1 || d->F < 1 || d->D < 1 || d->nwin < 1) {
+        dz_set_error("dz_tune_replay_host: %d local / %d global speakers (at most %d / %d), %d files", d->K, d->G, TC_KMAX,
+                     TC_GMAX, d->N);
+        return 2;
+    }
+    const int N = d->N, F = d->F, K = d->K, D = d->D, G = d->G;
+    const int pairs = trials * N;
+    int nt = num_threads < 1 ? 1 : num_threads;
+    if (nt > pairs) nt = pairs;
+    std::memset(assign, 0xff, (size_t)trials * d->total_chunks * K);
+    std::vector<int> rcs(nt, 0);
+    std::vector<std::string> msgs(nt);
+    struct Scratch {
+        std::vector<double> a, b;
+        std::vector<int> ia;
+        TcStep s;
+    };
+    std::vector<Scratch> scratch(nt);
+    auto fail = [&](int w, int rc, const char* what) {
+        if (!rcs[w]) {
+            rcs[w] = rc;
+            msgs[w] = what;
+        }
+    };
+    auto run_handles = [&](int w, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        const double tau = hparams[3 * t], rho = hparams[3 * t + 1], delta = hparams[3 * t + 2];
+        signed char* A = assign + (size_t)t * d->total_chunks * K;
+        unsigned* B = bits + (size_t)t * d->total_rows;
+        Scratch& sc = scratch[w];
+        sc.a.assign((size_t)F * G, 0.0);
+        sc.b.resize((size_t)(F + 2) * G);
+        sc.ia.resize(K);
+        dz_clu* clu = nullptr;
+        dz_tail* tail = nullptr;
+        if (dz_clu_create(tau, rho, delta, G, &clu) ||
+            dz_tail_create(F, G, step, latency, tau, DZ_AGG_HAMMING, DZ_CROP_LOOSE, d->hamming, &tail)) {
+            fail(w, 2, dz_last_error());
+            dz_clu_destroy(clu);
+            return;
+        }
+        int stat = -1;
+        for (int c = d->chunk_off[n]; c < d->chunk_off[n + 1] && !rcs[w]; ++c) {
+            if (stat < 0) {
+                const int rc = dz_clu_step(clu, d->seg + (size_t)c * F * K, F, K, d->emb + (size_t)c * K * D, D, sc.a.data(),
+                                           sc.ia.data());
+                if (rc) {   // the chain stops: its remaining chunks map nobody
+                    stat = c - d->chunk_off[n];
+                    std::fill(sc.a.begin(), sc.a.end(), 0.0);
+                } else {
+                    for (int k = 0; k < K; ++k) A[(size_t)c * K + k] = (signed char)sc.ia[k];
+                }
+            }
+            int rows = 0;
+            double t0 = 0.0, res = 0.0;
+            const int rc = dz_tail_step(tail, sc.a.data(), starts[c], resolution[c], sc.b.data(), &rows, &t0, &res, nullptr, 0,
+                                        nullptr);
+            if (rc) {
+                fail(w, rc, dz_last_error());
+                break;
+            }
+            const int* p = d->plan + (size_t)c * (4 + d->nwin);
+            if (rows != p[0] + p[1] || rows != d->row_off[c + 1] - d->row_off[c]) {
+                fail(w, 4, "dz_tune_replay_host: dz_tail_step and the plan disagree on the rows of a step");
+                break;
+            }
+            for (int r = 0; r < rows; ++r) {
+                unsigned m = 0;
+                for (int g = 0; g < G; ++g)
+                    if (sc.b[(size_t)r * G + g] > tau) m |= 1u << g;
+                B[d->row_off[c] + r] = m;
+            }
+        }
+        status[pair] = stat;
+        dz_clu_destroy(clu);
+        dz_tail_destroy(tail);
+    };
+    auto run_core = [&](int w, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        signed char* A = assign + (size_t)t * d->total_chunks * K;
+        unsigned* B = bits + (size_t)t * d->total_rows;
+        Scratch& sc = scratch[w];
+        sc.a.assign((size_t)D * G, std::nan(""));   // (and its work buffer: a centroid is written before it is read)
+        // the device's LDS starts with whatever was there: nothing in the step's state may be read before it is written
+        std::memset(&sc.s, (pair & 1) ? 0x7f : 0xff, sizeof(sc.s));
+        status[pair] = tc_chain(*d, n, hparams[3 * t], hparams[3 * t + 1], hparams[3 * t + 2], A, sc.a.data(), sc.s, 0, 1,
+                                NoBarrier());
+        const int c0 = d->chunk_off[n], c1 = d->chunk_off[n + 1];
+        for (int p = d->row_off[c0]; p < d->row_off[c1]; ++p) B[p] = tc_row_mask(*d, p, hparams[3 * t], A);
+    };
+    auto run = [&](int w, int pair) {
+        if (use_core) run_core(w, pair);
+        else run_handles(w, pair);
+    };
+    if (nt == 1)
+        for (int i = 0; i < pairs; ++i) run(0, i);
+    else
+        dz_host_parallel(pairs, nt, run);
+    for (int w = 0; w < nt; ++w)
+        if (rcs[w]) {
+            dz_set_error("dz_tune_replay_host: %s", msgs[w].c_str());
+            return rcs[w];
+        }
+    return 0;
+}
+
+extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_row_off,
+                             const int* file_chunk_off, const int* step_rows, const double* mids, const int* mid_cell,
+                             const int* file_cell_off, const double* cell_dur, const unsigned long long* cell_ref,
+                             int max_speakers, double collar, double* out, int num_threads) {
+    if (trials < 1 || n_files < 1 || !bits || !file_row_off || !file_chunk_off || !step_rows || !mids || !mid_cell ||
+        !file_cell_off || !cell_dur || !cell_ref || !out || max_speakers < 1 || max_speakers > TC_GMAX) {
+        dz_set_error("dz_tune_score: bad arguments");
+        return 2;
+    }
+    const int N = n_files, G = max_speakers, pairs = trials * N;
+    int nt = num_threads < 1 ? 1 : num_threads;
+    if (nt > pairs) nt = pairs;
+    struct Scratch {
+        std::vector<Turn> turns[TC_GMAX];
+        std::vector<unsigned> hyp;
+    };
+    std::vector<Scratch> scratch(nt);
+    std::vector<int> rcs(nt, 0);
+    auto run = [&](int w, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        Scratch& sc = scratch[w];
+        const unsigned* B = bits + (size_t)t * total_rows;
+        for (int g = 0; g < G; ++g) sc.turns[g].clear();
+        // ---- Binarize: per step and speaker, [middle(onset), middle(first inactive row)); the row after the last closes
+        int p = file_row_off[n];
+        for (int c = file_chunk_off[n]; c < file_chunk_off[n + 1]; ++c) {
+            const int rows = step_rows[c];
+            const double* mid = mids + (size_t)p + c;      // rows + 1 values
+            const int* cell = mid_cell + (size_t)p + c;
+            unsigned any = 0;
+            for (int r = 0; r < rows; ++r) any |= B[p + r];
+            for (unsigned m = any; m; m &= m - 1) {
+                const int g = __builtin_ctz(m);
+                if (g >= G) break;
+                int onset = -1;
+                for (int r = 0; r <= rows; ++r) {
+                    const bool on = r < rows && ((B[p + r] >> g) & 1u);
+                    if (on && onset < 0) onset = r;
+                    if (!on && onset >= 0) {
+                        if (mid[r] - mid[onset] > 1e-6)   // Segment.__bool__: shorter segments are not stored
+                            sc.turns[g].push_back(Turn{mid[onset], mid[r], cell[onset], cell[r]});
+                        onset = -1;
+                    }
+                }
+            }
+            p += rows;
+        }
+        // ---- Annotation.support(collar) per speaker, then the cells each merged turn covers
+        const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
+        sc.hyp.assign((size_t)ncell, 0u);
+        for (int g = 0; g < G; ++g) {
+            std::vector<Turn>& tv = sc.turns[g];
+            if (tv.empty()) continue;
+            std::sort(tv.begin(), tv.end(), [](const Turn& a, const Turn& b) { return a.s < b.s || (a.s == b.s && a.e < b.e); });
+            Turn cur = tv[0];
+            auto flush = [&](const Turn& u) {
+                if (u.is < 0 || u.ie > ncell || u.is > u.ie) {
+                    rcs[w] = 4;
+                    return;
+                }
+                for (int i = u.is; i < u.ie; ++i) sc.hyp[i] |= 1u << g;
+            };
+            for (size_t i = 1; i < tv.size(); ++i) {
+                const double gap = tv[i].s - cur.e;
+                if (gap <= 1e-6 || gap < collar) {
+                    if (tv[i].e > cur.e) {
+                        cur.e = tv[i].e;
+                        cur.ie = tv[i].ie;
+                    }
+                } else {
+                    flush(cur);
+                    cur = tv[i];
+                }
+            }
+            flush(cur);
+        }
+        // ---- the components over the cells
+        double total = 0.0, missed = 0.0, fa = 0.0, both = 0.0;
+        double cooc[TC_GMAX][64];
+        unsigned hseen = 0;
+        unsigned long long rseen = 0;
+        for (int g = 0; g < G; ++g)
+            for (int r = 0; r < 64; ++r) cooc[g][r] = 0.0;
+        for (int i = 0; i < ncell; ++i) {
+            const unsigned h = sc.hyp[i];
+            const unsigned long long rm = cell_ref[cell0 + i];
+            if (!h && !rm) continue;
+            const double dur = cell_dur[cell0 + i];
+            const int nref = __builtin_popcountll(rm), nhyp = __builtin_popcount(h);
+            total += dur * nref;
+            missed += dur * (nref > nhyp ? nref - nhyp : 0);
+            fa += dur * (nhyp > nref ? nhyp - nref : 0);
+            both += dur * (nref < nhyp ? nref : nhyp);
+            hseen |= h;
+            rseen |= rm;
+            for (unsigned m = h; m; m &= m - 1) {
+                const int g = __builtin_ctz(m);
+                for (unsigned long long q = rm; q; q &= q - 1) cooc[g][__builtin_ctzll(q)] += dur;
+            }
+        }
+        // ---- metrics.optimal_mapping: hypothesis labels "speaker<g>" and reference labels in str order, LSAP on -cooc
+        double correct = 0.0;
+        int hl[TC_GMAX], nh = 0, rl[64], nr = 0;
+        for (int g = 0; g < G; ++g)
+            if ((hseen >> g) & 1u) hl[nh++] = g;
+        std::sort(hl, hl + nh, [](int a, int b) { return std::to_string(a) < std::to_string(b); });
+        for (int r = 0; r < 64; ++r)
+            if ((rseen >> r) & 1ull) rl[nr++] = r;   // the bit order IS the label order (the cache sorts them)
+        if (nh > 0 && nr > 0) {
+            std::vector<double> cost((size_t)nh * nr);
+            std::vector<int> col(nh);
+            for (int a = 0; a < nh; ++a)
+                for (int b = 0; b < nr; ++b) cost[(size_t)a * nr + b] = -cooc[hl[a]][rl[b]];
+            if (dz_lsap(cost.data(), nh, nr, col.data())) {
+                rcs[w] = 3;
+                return;
+            }
+            for (int a = 0; a < nh; ++a)
+                if (col[a] >= 0 && cooc[hl[a]][rl[col[a]]] > 0.0) correct += cooc[hl[a]][rl[col[a]]];
+        }
+        double* o = out + (size_t)pair * 5;   // metrics.COMPONENTS order
+        o[0] = total;
+        o[1] = correct;
+        o[2] = fa;
+        o[3] = missed;
+        o[4] = both - correct;
+    };
+    if (nt == 1)
+        for (int i = 0; i < pairs; ++i) run(0, i);
+    else
+        dz_host_parallel(pairs, nt, run);
+    for (int w = 0; w < nt; ++w)
+        if (rcs[w]) {
+            dz_set_error(rcs[w] == 4 ? "dz_tune_score: a speech turn does not start and end on the file's scoring cells"
+                                     : "dz_tune_score: the mapping's assignment problem failed");
+            return rcs[w];
+        }
+    return 0;
+}

@@ -1,0 +1,527 @@
+"""Hyper-parameter tuning (reference: ``/root/reference/src/diart/optim.py``) by replaying cached model outputs.
+
+``tau_active``, ``rho_update`` and ``delta_new`` — what ``SpeakerDiarization.hyper_parameters()`` returns — act only
+after the networks: the segmentation scores, the overlapped-speech-penalty weights and the embeddings do not depend on
+them.  The reference runs the whole pipeline over the whole dataset once per trial; here ``TuneCache.collect`` runs
+the model half (``SpeakerDiarization.model_outputs``) once per file, and a trial is a replay of the cached
+``(chunks, F, K)`` scores and ``(chunks, K, D)`` embeddings: clustering -> permutation -> Hamming aggregation ->
+binarisation -> diarization error rate.  The ``T x N`` chains of T trials over N files are independent:
+
+* ``backend="gpu"``: two HIP kernels (``csrc/k_tune.hip``): one wavefront per chain for the clustering, one thread per
+  output frame for the aggregation, giving one 32-bit speaker mask per output frame;
+* ``backend="host"``: the existing C ABI (``dz_clu_step`` / ``dz_tail_step``), chains on host threads — the same masks,
+  bit for bit (``tests/test_gpu_tune.py``); what a machine without a GPU runs.
+
+Either way ``dz_tune_score`` turns the masks into the error-rate components on host threads.  DESIGN.md 4.16.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import json
+from pathlib import Path
+from typing import Dict, List, NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .blocks import base
+from .features import Annotation, Segment
+from .metrics import DiarizationErrorRate, _turns
+
+TUNABLE = ("tau_active", "rho_update", "delta_new")
+MAX_SPEAKERS = 32          # the hypothesis of a frame is one 32-bit mask
+MAX_LOCAL_SPEAKERS = 8
+PATCH_COLLAR = 0.05        # PredictionAccumulator's default
+
+
+class TuneResult(NamedTuple):
+    rate: np.ndarray          # (T,)   NaN for a trial with a non-negative status anywhere
+    components: np.ndarray    # (T, 5) metrics.COMPONENTS summed over the files
+    per_file: np.ndarray      # (T, N, 5)
+    status: np.ndarray        # (T, N) -1, or the chunk at which the clustering would raise
+
+
+def _config_meta(config) -> Dict[str, float]:
+    get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+    meta = {k: float(get(k)) for k in ("step", "latency") + TUNABLE}
+    meta["max_speakers"] = int(get("max_speakers"))
+    return meta
+
+
+def _reference_turns(reference) -> List[tuple]:
+    """(start, end, label) of the reference as the metric sees it: same-label turns that touch are one turn."""
+    if isinstance(reference, Annotation):
+        return _turns(reference)
+    ann = Annotation()
+    for n, (s, e, label) in enumerate(reference):
+        ann[Segment(float(s), float(e)), n] = str(label)
+    return _turns(ann)
+
+
+class TuneCache:
+    """The trial-independent half of a tuning run: per file the model outputs, the window start times, the frame
+    resolution ``finalise`` was given, the timestamp shift and the reference turns — and, computed once from them on
+    the host, what every trial shares: what ``identify`` derives from ``seg`` (float32 max, float32 sequential mean, NaN
+    flags), the output tail's plan (rows, buffers and cropped rows of every step, first-chunk prepend included) and the
+    file's scoring cells (the sorted union of every time at which a hypothesis turn can start or end and of the
+    reference's turn boundaries, each with its duration and the reference speakers active in it)."""
+
+    def __init__(self, files: Sequence[dict], config):
+        self.meta = _config_meta(config)
+        G = self.meta["max_speakers"]
+        if G > MAX_SPEAKERS:
+            raise ValueError(f"max_speakers = {G}: the replay keeps one 32-bit mask per frame, at most {MAX_SPEAKERS} speakers")
+        if not files:
+            raise ValueError("TuneCache needs at least one file")
+        self.files = []
+        for i, f in enumerate(files):
+            seg = np.ascontiguousarray(f["seg"], dtype=np.float32)
+            emb = np.ascontiguousarray(f["emb"], dtype=np.float32)
+            starts = np.ascontiguousarray(f["starts"], dtype=np.float64)
+            C_ = seg.shape[0]
+            if seg.ndim != 3 or emb.ndim != 3 or emb.shape[:2] != (C_, seg.shape[2]) or starts.shape != (C_,) or C_ < 1:
+                raise ValueError(f"file {i}: seg (C, F, K), emb (C, K, D), starts (C) expected, got {seg.shape}, "
+                                 f"{emb.shape}, {starts.shape}")
+            res = np.ascontiguousarray(np.broadcast_to(np.asarray(f["res"], dtype=np.float64), (C_,)))
+            self.files.append(dict(uri=str(f.get("uri", f"file{i}")), seg=seg, emb=emb, starts=starts, res=res,
+                                   shift=float(f.get("shift", 0.0)), turns=_reference_turns(f["reference"])))
+        shapes = {(f["seg"].shape[1:], f["emb"].shape[2]) for f in self.files}
+        if len(shapes) != 1:
+            raise ValueError(f"the files of one cache share frames, local speakers and dimension, got {sorted(shapes)}")
+        (self.F, self.K), self.D = next(iter(shapes))
+        if self.K > MAX_LOCAL_SPEAKERS:
+            raise ValueError(f"{self.K} local speakers per chunk (at most {MAX_LOCAL_SPEAKERS})")
+        self.G, self.N = G, len(self.files)
+        self._prepare()
+        self._dev = {}
+
+    # ------------------------------------------------------------------------------------------ construction
+    @classmethod
+    def from_arrays(cls, files: Sequence[dict], config) -> "TuneCache":
+        """``files``: dicts with ``seg (C, F, K)``, ``emb (C, K, D)``, ``starts (C)``, ``res`` (the frame resolution
+        ``finalise`` computes, one value or one per chunk), ``shift``, ``reference`` (an ``Annotation`` or
+        ``(start, end, label)`` tuples) and optionally ``uri``.  ``config``: anything with ``step``, ``latency``,
+        ``max_speakers`` and the three hyper-parameters (attributes or keys)."""
+        return cls(files, config)
+
+    @classmethod
+    def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32) -> "TuneCache":
+        """Run the model half of ``SpeakerDiarization`` once per WAV of ``speech_path`` (no ``finalise``, no
+        clustering), with ``Benchmark.run_single``'s file handling."""
+        from .features import load_rttm
+        from .inference import file_blocks, read_wav, resample_file, rolling_windows
+        _check_pipeline_class(pipeline_class)
+        if int(base_config.max_speakers) > MAX_SPEAKERS:
+            raise ValueError(f"max_speakers = {base_config.max_speakers}: the replay keeps one 32-bit mask per frame, "
+                             f"at most {MAX_SPEAKERS} speakers")
+        speech_path, reference_path = Path(speech_path).expanduser(), Path(reference_path).expanduser()
+        assert speech_path.is_dir(), "Speech path must be a directory"
+        assert reference_path.is_dir(), "Reference path must be a directory"
+        pipeline = pipeline_class(base_config)
+        cfg = pipeline.config
+        files = []
+        for fp in sorted(p for p in speech_path.iterdir() if p.suffix.lower() == ".wav"):
+            waveform, sr = read_wav(fp)
+            padding = cfg.get_padding(len(waveform) / sr)
+            if sr != cfg.sample_rate:
+                if getattr(getattr(cfg, "device", None), "type", None) != "cuda":
+                    raise ValueError(f"{fp} has sample rate {sr}, the pipeline's is {cfg.sample_rate} and the pipeline "
+                                     "has no GPU device to resample on; resample the file first")
+                waveform, sr = resample_file(waveform, sr, cfg.sample_rate, cfg.device), cfg.sample_rate
+            seg, emb, starts, res, batch = [], [], [], [], []
+
+            def flush():
+                s, e = pipeline.model_outputs(batch)
+                s = s.detach().cpu().numpy().astype(np.float32, copy=False)
+                e = e.detach().cpu().numpy().astype(np.float32, copy=False)
+                seg.append(s)
+                emb.append(e if e.ndim == 3 else e[None])
+                starts.extend(w.extent.start for w in batch)
+                res.extend([batch[0].extent.duration / s.shape[1]] * len(batch))     # finalise's seg_resolution
+                batch.clear()
+
+            for window in rolling_windows(file_blocks(waveform, sr, padding, cfg.step), cfg.duration, cfg.step, sr):
+                batch.append(window)
+                if len(batch) == max(1, int(batch_size)):
+                    flush()
+            if batch:
+                flush()
+            if not seg:
+                raise ValueError(f"{fp} is shorter than one chunk")
+            files.append(dict(uri=fp.stem, seg=np.concatenate(seg), emb=np.concatenate(emb), starts=np.array(starts),
+                              res=np.array(res), shift=-padding[0],
+                              reference=load_rttm(reference_path / f"{fp.stem}.rttm").popitem()[1]))
+        return cls(files, cfg)
+
+    def save(self, path) -> None:
+        out = {"meta": np.array(json.dumps(self.meta)), "uris": np.array([f["uri"] for f in self.files])}
+        for i, f in enumerate(self.files):
+            for k in ("seg", "emb", "starts", "res"):
+                out[f"{k}_{i}"] = f[k]
+            out[f"shift_{i}"] = np.array(f["shift"])
+            out[f"ref_times_{i}"] = np.array([[s, e] for s, e, _ in f["turns"]], dtype=np.float64).reshape(-1, 2)
+            out[f"ref_labels_{i}"] = np.array([str(l) for _, _, l in f["turns"]], dtype=str)
+        with open(path, "wb") as fh:
+            np.savez(fh, **out)
+
+    @classmethod
+    def load(cls, path) -> "TuneCache":
+        with np.load(path, allow_pickle=False) as z:
+            meta = json.loads(str(z["meta"]))
+            files = []
+            for i, uri in enumerate(z["uris"]):
+                ref = [(s, e, str(l)) for (s, e), l in zip(z[f"ref_times_{i}"], z[f"ref_labels_{i}"])]
+                files.append(dict(uri=str(uri), seg=z[f"seg_{i}"], emb=z[f"emb_{i}"], starts=z[f"starts_{i}"],
+                                  res=z[f"res_{i}"], shift=float(z[f"shift_{i}"]), reference=ref))
+        return cls(files, meta)
+
+    # ------------------------------------------------------------------------------------------ trial-independent parts
+    def _prepare(self) -> None:
+        lib = _lib.load()
+        F, K, m = self.F, self.K, self.meta
+        self.nwin = int(round(m["latency"] / m["step"]))
+        self.seg = np.concatenate([f["seg"] for f in self.files])
+        self.emb = np.concatenate([f["emb"] for f in self.files])
+        self.starts = np.concatenate([f["starts"] for f in self.files])
+        self.res = np.concatenate([f["res"] for f in self.files])
+        counts = [f["seg"].shape[0] for f in self.files]
+        self.chunk_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        total = int(self.chunk_off[-1])
+        # what identify derives from seg: NaN flag, max, and the float32 mean summed over the frames in order
+        seg_nan = np.isnan(self.seg).any(axis=1)
+        with np.errstate(invalid="ignore"):
+            self.pre_max = np.ascontiguousarray(np.where(seg_nan, np.float32(0), self.seg.max(axis=1)), dtype=np.float32)
+            acc = np.zeros((total, K), dtype=np.float32)
+            for f in range(F):
+                acc += self.seg[:, f, :]
+            self.pre_mean = np.ascontiguousarray(acc / np.float32(F), dtype=np.float32)
+        self.pre_flags = np.ascontiguousarray(seg_nan.astype(np.uint8) | (np.isnan(self.emb).any(axis=2).astype(np.uint8) << 1))
+        self.hamming = np.ascontiguousarray(np.hamming(F), dtype=np.float64)
+        # the tail's plan, file by file
+        self.plan = np.zeros((total, 4 + self.nwin), dtype=np.int32)
+        self.t0, self.out_res = np.zeros(total), np.zeros(total)
+        for n in range(self.N):
+            a, b = int(self.chunk_off[n]), int(self.chunk_off[n + 1])
+            plan, t0, res = self.plan[a:b], self.t0[a:b], self.out_res[a:b]
+            _lib.check(lib.dz_tune_plan(b - a, F, m["step"], m["latency"], self.starts[a:b].ctypes.data,
+                                        self.res[a:b].ctypes.data, plan.ctypes.data, t0.ctypes.data, res.ctypes.data),
+                       "dz_tune_plan")
+        self.step_rows = np.ascontiguousarray(self.plan[:, 0] + self.plan[:, 1], dtype=np.int32)
+        self.row_off = np.concatenate([[0], np.cumsum(self.step_rows)]).astype(np.int32)
+        self.total_rows = int(self.row_off[-1])
+        self.row_chunk = np.repeat(np.arange(total, dtype=np.int32), self.step_rows)
+        self.file_row_off = np.ascontiguousarray(self.row_off[self.chunk_off], dtype=np.int32)
+        # frame middles of every step's output grid (rows + 1 per step: the row after the last closes open turns),
+        # with Binarize's expression, plus the shift
+        per = self.step_rows.astype(np.int64) + 1
+        step_of = np.repeat(np.arange(total), per)
+        first = np.concatenate([[0], np.cumsum(per)])[:-1]
+        i = (np.arange(int(per.sum())) - first[step_of]).astype(np.float64)
+        s = self.t0[step_of] + i * self.out_res[step_of]
+        shift = np.repeat(np.array([f["shift"] for f in self.files]), np.diff(self.chunk_off))[step_of]
+        self.mids = np.ascontiguousarray(0.5 * (s + (s + self.out_res[step_of])) + shift)
+        # scoring cells
+        self.mid_cell = np.zeros(self.mids.shape[0], dtype=np.int32)
+        durs, refs, cell_off = [], [], [0]
+        self.ref_labels = []
+        for n, f in enumerate(self.files):
+            a = int(self.file_row_off[n] + self.chunk_off[n])
+            b = int(self.file_row_off[n + 1] + self.chunk_off[n + 1]) if n + 1 < self.N else self.mids.shape[0]
+            labels = sorted({l for _, _, l in f["turns"]}, key=str)
+            if len(labels) > 64:
+                raise ValueError(f"{f['uri']}: {len(labels)} reference speakers (at most 64)")
+            self.ref_labels.append(labels)
+            rs = np.array([t[0] for t in f["turns"]], dtype=np.float64)
+            re = np.array([t[1] for t in f["turns"]], dtype=np.float64)
+            bounds = np.unique(np.concatenate([self.mids[a:b], rs, re]))
+            self.mid_cell[a:b] = np.searchsorted(bounds, self.mids[a:b])
+            mask = np.zeros(bounds.shape[0] - 1, dtype=np.uint64)
+            for (s_, e_, l) in f["turns"]:
+                i0, i1 = np.searchsorted(bounds, s_), np.searchsorted(bounds, e_)
+                mask[i0:i1] |= np.uint64(1) << np.uint64(labels.index(l))
+            durs.append(np.diff(bounds))
+            refs.append(mask)
+            cell_off.append(cell_off[-1] + mask.shape[0])
+        self.cell_dur = np.ascontiguousarray(np.concatenate(durs), dtype=np.float64)
+        self.cell_ref = np.ascontiguousarray(np.concatenate(refs), dtype=np.uint64)
+        self.file_cell_off = np.array(cell_off, dtype=np.int32)
+
+    def _desc(self, ptr) -> _lib.TuneDesc:
+        d = _lib.TuneDesc()
+        for name in ("seg", "emb", "pre_max", "pre_mean", "pre_flags", "chunk_off", "plan", "row_off", "row_chunk", "hamming"):
+            setattr(d, name, ptr(name))
+        d.N, d.F, d.K, d.D, d.G, d.nwin = self.N, self.F, self.K, self.D, self.G, self.nwin
+        d.total_chunks, d.total_rows = int(self.chunk_off[-1]), self.total_rows
+        return d
+
+    @property
+    def bytes_per_trial(self) -> int:
+        """Device (and host) memory one trial's results take: the assignments, the frame masks, the statuses."""
+        return int(self.chunk_off[-1]) * self.K + 4 * self.total_rows + 4 * self.N
+
+    # ------------------------------------------------------------------------------------------ replay
+    @staticmethod
+    def _hparams(hparams) -> np.ndarray:
+        hp = np.ascontiguousarray(np.atleast_2d(np.asarray(hparams, dtype=np.float64)))
+        if hp.ndim != 2 or hp.shape[1] != 3 or hp.shape[0] < 1:
+            raise ValueError(f"hparams (T, 3) = (tau_active, rho_update, delta_new) per trial expected, got {hp.shape}")
+        return hp
+
+    @staticmethod
+    def default_backend() -> str:
+        return "gpu" if torch.cuda.is_available() else "host"
+
+    def replay(self, hparams, backend: Optional[str] = None, num_threads: int = 8):
+        """``(assign (T, chunks, K) int8, status (T, N) int32, bits (T, rows) uint32)`` of T trials: the global speaker
+        of every local one (-1: none), the chunk at which a chain stopped (-1: it ran to the end) and one speaker mask
+        per packed output frame.  ``backend``: "gpu" | "host" | "core" (the kernels' text on the host)."""
+        hp = self._hparams(hparams)
+        backend = backend or self.default_backend()
+        if backend == "gpu":
+            a, s, b = self._replay_gpu(hp)
+            torch.cuda.synchronize(a.device)
+            return a.cpu().numpy(), s.cpu().numpy(), b.cpu().numpy().view(np.uint32)
+        if backend not in ("host", "core"):
+            raise ValueError(f"backend '{backend}': gpu, host or core")
+        T, total = hp.shape[0], int(self.chunk_off[-1])
+        assign = np.empty((T, total, self.K), dtype=np.int8)
+        status = np.empty((T, self.N), dtype=np.int32)
+        bits = np.empty((T, self.total_rows), dtype=np.uint32)
+        d = self._desc(lambda name: getattr(self, name).ctypes.data)
+        _lib.check(_lib.load().dz_tune_replay_host(C.byref(d), hp.ctypes.data, T, self.meta["step"], self.meta["latency"],
+                                                   self.starts.ctypes.data, self.res.ctypes.data, assign.ctypes.data,
+                                                   status.ctypes.data, bits.ctypes.data, int(backend == "core"),
+                                                   int(num_threads)), "dz_tune_replay_host")
+        return assign, status, bits
+
+    def _device(self, device: torch.device):
+        key = str(device)
+        if key not in self._dev:
+            tensors = {name: torch.from_numpy(getattr(self, name)).to(device)
+                       for name in ("seg", "emb", "pre_max", "pre_mean", "pre_flags", "chunk_off", "plan", "row_off",
+                                    "row_chunk", "hamming")}
+            self._dev[key] = (tensors, self._desc(lambda name: tensors[name].data_ptr()))
+        return self._dev[key]
+
+    WORK_BLOCKS = 2048          # resident chains: 256 CUs x 8 one-wave workgroups
+
+    def _replay_gpu(self, hp: np.ndarray, device: Optional[torch.device] = None, phases: int = 3, into=None):
+        if not torch.cuda.is_available():
+            raise _lib.DiartAmdError("backend='gpu' needs a GPU; backend='host' replays on the host")
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        _, desc = self._device(device)
+        T, total = hp.shape[0], int(self.chunk_off[-1])
+        d_hp = torch.from_numpy(hp).to(device)
+        if into is not None:                     # (measurements: one phase on the arrays of an earlier call)
+            assign, status, bits = into
+        else:
+            assign = torch.empty((T, total, self.K), dtype=torch.int8, device=device)
+            status = torch.empty((T, self.N), dtype=torch.int32, device=device)
+            bits = torch.empty((T, self.total_rows), dtype=torch.int32, device=device)
+        blocks = min(T * self.N, self.WORK_BLOCKS)
+        work = torch.empty((blocks, self.D * self.G), dtype=torch.float64, device=device)
+        _lib.check(_lib.load().dz_tune_replay(_lib.context(device.index), C.byref(desc), d_hp.data_ptr(), T,
+                                              assign.data_ptr(), status.data_ptr(), bits.data_ptr(), work.data_ptr(), blocks, int(phases),
+                                              torch.cuda.current_stream(device).cuda_stream), "dz_tune_replay")
+        return assign, status, bits
+
+    def score(self, bits: np.ndarray, num_threads: int = 8) -> np.ndarray:
+        """``(T, N, 5)`` error-rate components (``metrics.COMPONENTS``) of the masks of ``replay``."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        T = bits.shape[0]
+        out = np.zeros((T, self.N, 5), dtype=np.float64)
+        _lib.check(_lib.load().dz_tune_score(T, self.N, bits.ctypes.data, self.total_rows, self.file_row_off.ctypes.data,
+                                             self.chunk_off.ctypes.data, self.step_rows.ctypes.data, self.mids.ctypes.data,
+                                             self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
+                                             self.cell_dur.ctypes.data, self.cell_ref.ctypes.data, self.G, PATCH_COLLAR,
+                                             out.ctypes.data, int(num_threads)), "dz_tune_score")
+        return out
+
+    def evaluate(self, hparams, backend: Optional[str] = None, memory_budget: int = 1 << 30,
+                 num_threads: int = 8) -> TuneResult:
+        """The error rate of every trial of ``hparams (T, 3)``, trials in batches whose results fit ``memory_budget``
+        bytes."""
+        hp = self._hparams(hparams)
+        backend = backend or self.default_backend()
+        per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
+        per_file, status = [], []
+        for a in range(0, hp.shape[0], per_batch):
+            _, st, bits = self.replay(hp[a:a + per_batch], backend, num_threads)
+            per_file.append(self.score(bits, num_threads))
+            status.append(st)
+        per_file, status = np.concatenate(per_file), np.concatenate(status)
+        comp = per_file.sum(axis=1)
+        err = comp[:, 2] + comp[:, 3] + comp[:, 4]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rate = np.where(comp[:, 0] > 0, err / comp[:, 0], np.where(err == 0, 0.0, 1.0))
+        rate = np.where((status >= 0).any(axis=1), np.nan, rate)
+        return TuneResult(rate, comp, per_file, status)
+
+    def hypothesis(self, bits_row: np.ndarray, n: int) -> Annotation:
+        """File n's hypothesis under one trial as the ``Annotation`` ``PredictionAccumulator`` ends with (tests and
+        RTTM output): the speech turns of the masks, same-speaker turns closer than the patch collar merged."""
+        ann = Annotation(uri=self.files[n]["uri"], modality="speech")
+        p, m = int(self.file_row_off[n]), int(self.file_row_off[n] + self.chunk_off[n])
+        for c in range(int(self.chunk_off[n]), int(self.chunk_off[n + 1])):
+            rows = int(self.step_rows[c])
+            b = bits_row[p:p + rows]
+            for g in range(self.G):
+                on = np.concatenate([[False], (b >> np.uint32(g)) & np.uint32(1) > 0, [False]])
+                edges = np.flatnonzero(on[1:] != on[:-1])
+                for s, e in zip(edges[::2], edges[1::2]):
+                    ann[Segment(self.mids[m + s], self.mids[m + e]), g] = f"speaker{g}"
+            p, m = p + rows, m + rows + 1
+        return ann.support(PATCH_COLLAR)
+
+
+def _check_pipeline_class(pipeline_class) -> None:
+    from .blocks.diarization import SpeakerDiarization
+    if pipeline_class is not SpeakerDiarization:
+        name = getattr(pipeline_class, "__name__", repr(pipeline_class))
+        raise ValueError(f"pipeline class {name}: only SpeakerDiarization is tuned by replaying cached model outputs")
+
+
+def trial_config(base_config, values: Dict[str, float]):
+    """``base_config`` with the tuned hyper-parameters of one trial (the models are shared, not copied)."""
+    cfg = copy.copy(base_config)
+    for name, v in values.items():
+        setattr(cfg, name, float(v))
+    return cfg
+
+
+class Optimizer:
+    """The reference's ``Optimizer`` (``optim.py:17-141``) on a ``TuneCache``: same constructor, ``objective`` value
+    (the metric in percent), ``__call__(num_iter, show_progress)``, ``best_performance`` and ``best_hparams``.  optuna
+    is replaced by a directory: ``<path>/<stem>.json`` holds every trial and is loaded if it exists, a second call
+    continues the numbering and never evaluates a stored trial again.  ``sampler``: "random" (uniform over each
+    parameter's range, from ``seed``) or "grid" (``num_iter`` as a total: the largest cube not above it).  Trials are
+    evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run)."""
+
+    def __init__(self, pipeline_class: type, speech_path, reference_path, study_or_path, batch_size: int = 32,
+                 hparams: Optional[Sequence[base.HyperParameter]] = None, base_config=None,
+                 do_kickstart_hparams: bool = True, metric=None, direction: str = "minimize", sampler: str = "random",
+                 seed: int = 0, trials_per_batch: int = 256, cache: Optional[TuneCache] = None,
+                 backend: Optional[str] = None):
+        _check_pipeline_class(pipeline_class)
+        self.pipeline_class = pipeline_class
+        self.speech_path, self.reference_path, self.batch_size = speech_path, reference_path, batch_size
+        if metric is not None and not isinstance(metric, DiarizationErrorRate):
+            raise ValueError(f"metric {type(metric).__name__}: the replay scores the diarization error rate only")
+        if direction not in ("minimize", "maximize"):
+            raise ValueError(f"direction '{direction}': minimize or maximize")
+        if sampler not in ("random", "grid"):
+            raise ValueError(f"sampler '{sampler}': random or grid")
+        self.metric, self.direction, self.sampler, self.seed = metric, direction, sampler, int(seed)
+        self.trials_per_batch, self.backend = max(1, int(trials_per_batch)), backend
+        self.base_config, self.do_kickstart_hparams = base_config, do_kickstart_hparams
+        if self.base_config is None:
+            self.base_config = pipeline_class.get_config_class()()
+            self.do_kickstart_hparams = False
+        self.hparams = list(pipeline_class.hyper_parameters() if hparams is None else hparams)
+        possible = vars(self.base_config)
+        for param in self.hparams:
+            if param.name not in TUNABLE:
+                raise ValueError(f"hyper-parameter {param.name} changes the model outputs: only {', '.join(TUNABLE)} "
+                                 "are tuned by replaying them")
+            assert param.name in possible, (f"Hyper-parameter {param.name} not found in configuration "
+                                            f"{self.base_config.__class__.__name__}")
+        if int(self.base_config.max_speakers) > MAX_SPEAKERS:
+            raise ValueError(f"max_speakers = {self.base_config.max_speakers}: the replay keeps one 32-bit mask per "
+                             f"frame, at most {MAX_SPEAKERS} speakers")
+        if not isinstance(study_or_path, (str, Path)):
+            raise TypeError(f"Expected a path-like study directory, but got {type(study_or_path).__name__}: optuna "
+                            "studies are not supported, trials are kept in <path>/<stem>.json")
+        self.study_path = Path(study_or_path)
+        self.study_file = self.study_path / f"{self.study_path.stem}.json"
+        self.trials: List[dict] = []
+        if self.study_file.exists():
+            stored = json.loads(self.study_file.read_text())
+            names = [p.name for p in self.hparams]
+            if stored.get("direction") != self.direction or stored.get("hparams") != names:
+                raise ValueError(f"{self.study_file} holds a study of {stored.get('hparams')} ({stored.get('direction')}), "
+                                 f"not of {names} ({self.direction}): its trials cannot be continued with other "
+                                 "hyper-parameters or the other direction")
+            self.trials = stored["trials"]
+        self._cache = cache
+
+    @property
+    def cache(self) -> TuneCache:
+        if self._cache is None:
+            self._cache = TuneCache.collect(self.pipeline_class, self.base_config, self.speech_path, self.reference_path,
+                                            self.batch_size)
+        return self._cache
+
+    def _complete(self) -> List[dict]:
+        return [t for t in self.trials if t["value"] is not None]
+
+    @property
+    def best_trial(self) -> dict:
+        done = self._complete()
+        if not done:
+            raise ValueError("no completed trial yet")
+        pick = min if self.direction == "minimize" else max
+        return pick(done, key=lambda t: t["value"])
+
+    @property
+    def best_performance(self) -> float:
+        return self.best_trial["value"]
+
+    @property
+    def best_hparams(self) -> Dict[str, float]:
+        return dict(self.best_trial["params"])
+
+    def _values(self, params: Dict[str, float]) -> List[float]:
+        """(tau, rho, delta) of a trial: the sampled parameters, the base config's value for the others."""
+        return [float(params.get(name, getattr(self.base_config, name))) for name in TUNABLE]
+
+    def objective(self, params: Sequence[Dict[str, float]]) -> np.ndarray:
+        """The metric in percent of every trial of ``params`` (NaN where the clustering would raise)."""
+        hp = np.array([self._values(p) for p in params], dtype=np.float64)
+        return 100.0 * self.cache.evaluate(hp, backend=self.backend).rate
+
+    def _grid(self, total: int) -> List[Dict[str, float]]:
+        """The largest cube of at most ``total`` points: the same number of equally spaced interior values per axis."""
+        side = 1
+        while (side + 1) ** len(self.hparams) <= total:
+            side += 1
+        axes = [np.linspace(p.low, p.high, side + 2)[1:-1] for p in self.hparams]
+        mesh = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, len(self.hparams))
+        return [{p.name: float(v) for p, v in zip(self.hparams, row)} for row in mesh]
+
+    def _random(self, number: int) -> Dict[str, float]:
+        """The draw of trial ``number`` depends on (seed, number) only, so a resumed study continues the sequence."""
+        rng = np.random.default_rng([self.seed, number])
+        return {p.name: float(rng.uniform(p.low, p.high)) for p in self.hparams}
+
+    def _store(self) -> None:
+        self.study_path.mkdir(parents=True, exist_ok=True)
+        payload = dict(direction=self.direction, hparams=[p.name for p in self.hparams], trials=self.trials)
+        tmp = self.study_file.with_suffix(".json.tmp")
+        tmp.write_text(json.dumps(payload, indent=1))
+        tmp.replace(self.study_file)
+
+    def __call__(self, num_iter: int, show_progress: bool = True):
+        queue: List[Dict[str, float]] = []
+        if self.do_kickstart_hparams:
+            kick = {p.name: float(getattr(self.base_config, p.name)) for p in self.hparams}
+            if not any(t["params"] == kick for t in self.trials):
+                queue.append(kick)
+        if self.sampler == "grid":
+            stored = [t["params"] for t in self.trials]
+            queue += [p for p in self._grid(int(num_iter)) if p not in stored and p not in queue]
+        else:
+            first = len(self.trials)
+            queue += [self._random(first + j) for j in range(len(queue), int(num_iter))]
+        for a in range(0, len(queue), self.trials_per_batch):
+            batch = queue[a:a + self.trials_per_batch]
+            values = self.objective(batch)
+            for params, v in zip(batch, values):
+                self.trials.append(dict(number=len(self.trials), params=params, value=None if np.isnan(v) else float(v)))
+            self._store()
+            if show_progress:
+                done = self._complete()
+                best = f"best {self.best_performance:.3f}" if done else "no completed trial"
+                print(f"[tune] trial {len(self.trials)}: {best}", flush=True)
+        return self

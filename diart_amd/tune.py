@@ -1,0 +1,78 @@
+"""``python -m diart_amd.tune``: tune tau_active, rho_update and delta_new of ``SpeakerDiarization`` on a directory of
+WAV files against RTTM references (reference: ``/root/reference/src/diart/console/tune.py``).  The models run once
+over the dataset (``optim.TuneCache.collect``; ``--cache FILE`` saves that pass, or loads it when the file is there),
+then every trial is a replay of their outputs — on the GPU when there is one.  The study is a directory: ``--output
+DIR`` holds ``DIR/<stem>.json`` with every trial, and a second run continues it."""
+from __future__ import annotations
+
+import argparse
+from pathlib import Path
+
+from . import models as m
+from .blocks.base import HyperParameter
+from .blocks.diarization import SpeakerDiarization, SpeakerDiarizationConfig
+from .optim import Optimizer, TuneCache
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m diart_amd.tune", description=__doc__.split("\n\n")[0])
+    ap.add_argument("root", type=str, help="Directory with audio files CONVERSATION.wav")
+    ap.add_argument("--reference", required=True, type=str,
+                    help="Directory with RTTM files CONVERSATION.rttm. Names must match audio files")
+    ap.add_argument("--segmentation", default="pyannote/segmentation", type=str, help="Segmentation checkpoint file")
+    ap.add_argument("--embedding", default="pyannote/embedding", type=str, help="Embedding checkpoint file")
+    ap.add_argument("--duration", type=float, default=5, help="Chunk duration in seconds. Defaults to 5")
+    ap.add_argument("--step", default=0.5, type=float, help="Sliding window step in seconds. Defaults to 0.5")
+    ap.add_argument("--latency", default=0.5, type=float, help="System latency in seconds. Defaults to 0.5")
+    ap.add_argument("--tau-active", default=0.5, type=float, help="Base value of tau_active. Defaults to 0.5")
+    ap.add_argument("--rho-update", default=0.3, type=float, help="Base value of rho_update. Defaults to 0.3")
+    ap.add_argument("--delta-new", default=1, type=float, help="Base value of delta_new. Defaults to 1")
+    ap.add_argument("--gamma", default=3, type=float, help="Overlapped-speech-penalty gamma. Defaults to 3")
+    ap.add_argument("--beta", default=10, type=float, help="Overlapped-speech-penalty beta. Defaults to 10")
+    ap.add_argument("--max-speakers", default=20, type=int, help="Maximum number of speakers (at most 32). Defaults to 20")
+    ap.add_argument("--batch-size", default=32, type=int, help="Chunks per model call while collecting. Defaults to 32")
+    ap.add_argument("--normalize-embedding-weights", action="store_true")
+    ap.add_argument("--cpu", action="store_true",
+                    help="Replay the trials on the host even if a GPU is there; the models keep their GPU device")
+    ap.add_argument("--hparams", nargs="+", default=("tau_active", "rho_update", "delta_new"),
+                    help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three)")
+    ap.add_argument("--num-iter", default=100, type=int, help="Number of optimization trials")
+    ap.add_argument("--output", type=str, required=True, help="Study directory: holds <stem>.json with every trial")
+    ap.add_argument("--sampler", default="random", choices=("random", "grid"),
+                    help="random: uniform over each range; grid: the largest cube of at most --num-iter points")
+    ap.add_argument("--seed", default=0, type=int, help="Seed of the random sampler. Defaults to 0")
+    ap.add_argument("--trials-per-batch", default=256, type=int, help="Trials evaluated at a time. Defaults to 256")
+    ap.add_argument("--cache", type=str, help="File of the collected model outputs: loaded if it exists, written if not")
+    return ap
+
+
+def run(args: argparse.Namespace, models=None) -> Optimizer:
+    """``models``: (segmentation, embedding) to use in place of the checkpoints the arguments name."""
+    seg, emb = models if models is not None else (m.SegmentationModel.from_pretrained(args.segmentation),
+                                                  m.EmbeddingModel.from_pretrained(args.embedding))
+    base_config = SpeakerDiarizationConfig(
+        segmentation=seg, embedding=emb, duration=args.duration, step=args.step, latency=args.latency,
+        tau_active=args.tau_active, rho_update=args.rho_update, delta_new=args.delta_new, gamma=args.gamma,
+        beta=args.beta, max_speakers=args.max_speakers, normalize_embedding_weights=args.normalize_embedding_weights,
+        device=None)
+    possible = SpeakerDiarization.hyper_parameters()
+    hparams = [hp for hp in (HyperParameter.from_name(name) for name in args.hparams) if hp in possible]
+    if not hparams:
+        raise SystemExit("No hyper-parameters to optimize. Make sure to select one of: "
+                         + ", ".join(hp.name for hp in possible))
+    cache = None
+    if args.cache and Path(args.cache).exists():
+        cache = TuneCache.load(args.cache)
+    opt = Optimizer(SpeakerDiarization, args.root, args.reference, Path(args.output).expanduser(),
+                    batch_size=args.batch_size, hparams=hparams, base_config=base_config, sampler=args.sampler,
+                    seed=args.seed, trials_per_batch=args.trials_per_batch, cache=cache,
+                    backend="host" if args.cpu else None)
+    if args.cache and cache is None:
+        opt.cache.save(args.cache)
+    opt(num_iter=args.num_iter, show_progress=True)
+    print(f"[tune] best {opt.best_performance:.3f} % at {opt.best_hparams}", flush=True)
+    return opt
+
+
+if __name__ == "__main__":
+    run(parser().parse_args())

@@ -875,6 +875,70 @@ int dz_file_step_batch(dz_clu** clus, dz_tail** tails, int n_files, const int* r
                        double* turns_out, int max_turns, int* nturns_out, int* assign_out,
                        int num_threads);
 
+/* ---- hyper-parameter tuning: replay cached model outputs --------------------
+ * tau_active, rho_update and delta_new act only after the networks, so a trial is a replay of the
+ * cached segmentation (chunks, frames, k_local) and embeddings (chunks, k_local, dim) of every file:
+ * clustering -> Hamming aggregation -> binarisation -> error rate.  The chunks of the N files are
+ * concatenated (file n: chunk_off[n] .. chunk_off[n + 1]); everything in dz_tune_desc is the same for
+ * every trial and is computed once, on the host, when the cache is collected:
+ *   pre_max / pre_mean / pre_flags (chunks, k_local)  what identify derives from seg: the float32 max, the
+ *       float32 sequential mean, bit 0 = a NaN score, bit 1 = a NaN in the embedding row
+ *   plan (chunks, 4 + nwin)  dz_tune_plan: per step {aggregated rows, prepended rows of a first chunk, their
+ *       first cropped row, buffers, first cropped row of each buffer}; buffer b of step c is chunk c - buffers + 1 + b
+ *   row_off (chunks + 1), row_chunk (total_rows)  the packed output rows: a prefix sum of the rows per step
+ *       and each row's step
+ * max_speakers <= 32 (a frame's hypothesis is one 32-bit mask) and k_local <= 8.                         */
+typedef struct dz_tune_desc {
+    const float* seg;
+    const float* emb;
+    const float* pre_max;
+    const float* pre_mean;
+    const unsigned char* pre_flags;
+    const int* chunk_off;
+    const int* plan;
+    const int* row_off;
+    const int* row_chunk;
+    const double* hamming; /* [frames] */
+    int N, F, K, D, G, nwin, total_chunks, total_rows;
+} dz_tune_desc;
+int dz_tune_abi_size(void);
+/* The tail's plan of one file (Hamming aggregation, "loose" cropping) with tail.cpp's own expressions:
+ * starts, resolution (chunks) as dz_tail_step gets them.  plan (chunks, 4 + nwin) with
+ * nwin = round(latency / step); t0_out, res_out (chunks): the output grid of every step.  4 = the output
+ * region does not map onto the frame grid of every buffer.                                              */
+int dz_tune_plan(int chunks, int frames, double step, double latency, const double* starts,
+                 const double* resolution, int* plan, double* t0_out, double* res_out);
+/* T trials (hparams (T, 3): tau, rho, delta) x N files on the GPU: every pointer of `d` and every array here
+ * is device memory.  assign (T, chunks, k_local) int8: the global speaker of every local one or -1;
+ * status (T, N): -1, or the first chunk of the file at which dz_clu_step would return non-zero (the chain
+ * stops there); bits (T, total_rows): bit g = the aggregated score of global speaker g is > tau.
+ * One wavefront walks one (trial, file) chain; its centroids live in work (work_blocks, dim * max_speakers)
+ * doubles, one slice per resident workgroup.  phases: 3 = both kernels; 1 = the clustering alone, 2 = the masks
+ * alone, from the assignments d_assign holds (measurements).  Enqueued on `stream`, no synchronisation.  */
+int dz_tune_replay(dz_ctx* ctx, const dz_tune_desc* d, const double* d_hparams, int trials,
+                   signed char* d_assign, int* d_status, unsigned* d_bits, double* d_work, int work_blocks,
+                   int phases, void* stream);
+/* The same three arrays from host memory.  use_core = 0: with dz_clu_step and dz_tail_step, one handle pair
+ * per (trial, file), pairs on host threads (starts, resolution (chunks), step, latency as dz_tail_step gets
+ * them).  use_core = 1: the text the kernels are compiled from, run on the host (tests hold it against the
+ * former without a GPU).                                                                                */
+int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams, int trials, double step, double latency,
+                        const double* starts, const double* resolution, signed char* assign, int* status,
+                        unsigned* bits, int use_core, int num_threads);
+/* Diarization error rate components (collar 0, overlap included) of every (trial, file) pair from the packed
+ * frame masks, without building annotations: speech turns as Binarize forms them, same-speaker turns closer
+ * than `collar` merged as Annotation.support does, then total / correct / false alarm / missed detection /
+ * confusion over the file's scoring cells under the optimal one-to-one mapping.
+ *   file_row_off, file_chunk_off, file_cell_off (N + 1); step_rows (chunks)
+ *   mids (total_rows + chunks): per step its rows + 1 frame middles, timestamp shift added; mid_cell: the cell
+ *       that starts at that time
+ *   cell_dur, cell_ref (cells): duration and bit mask of the reference speakers of every cell
+ * out (T, N, 5).                                                                                        */
+int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_row_off,
+                  const int* file_chunk_off, const int* step_rows, const double* mids, const int* mid_cell,
+                  const int* file_cell_off, const double* cell_dur, const unsigned long long* cell_ref,
+                  int max_speakers, double collar, double* out, int num_threads);
+
 /* sizeof() of the five structs that cross this boundary, in declaration order
  * (dz_sincnet_weights, dz_seg_weights, dz_emb_weights, dz_ecapa_weights, dz_convgemm_desc): a
  * binding checks its own mirror of the layouts against the library it loaded.            */
