@@ -1,9 +1,9 @@
 // Hyper-parameter tuning on cached model outputs (dz_tune_replay): T trials x N files replayed on the GPU.
 //
-//   tune_cluster_kernel   one wavefront per (trial, file) chain walks the file's chunks in order: cluster.cpp's identify
-//                         + step in fp64 with the same decisions (tune_core.h is the text; the host compiles it too).  The
+//   tune_cluster_kernel   one wavefront per (trial, file) chain walks the file's chunks in order: dz_clu_step in fp64, its
+//                         decisions compiled from the text cluster.cpp compiles (clu_core.h, here on the fixed store).  The
 //                         K x G distances and the norms are spread over the lanes, each dot product summed by ONE lane in
-//                         dot2's order; lane 0 solves the assignment problems while the others wait at the barrier.  A
+//                         the core's order; lane 0 solves the assignment problems while the others wait at the barrier.  A
 //                         workgroup is one wavefront and takes chains blockIdx.x, blockIdx.x + gridDim.x, ...; its centroids
 //                         (G x D doubles, 80 KiB at 20 x 512) live in its own slice of a global work buffer that stays in
 //                         L2 — LDS would hold one such chain per CU, and the lanes that wait for lane 0 need no bandwidth.
@@ -28,7 +28,7 @@ struct TuneBarrier {
 __global__ __launch_bounds__(TUNE_WAVE) void tune_cluster_kernel(dz_tune_desc d, const double* __restrict__ hp, int trials,
                                                                  signed char* __restrict__ assign, int* __restrict__ status,
                                                                  double* __restrict__ work) {
-    __shared__ TcStep s;
+    __shared__ TcStep<CluFixed> s;
     const int lane = threadIdx.x;
     double* ctr = work + (size_t)blockIdx.x * d.D * d.G;
     const int chains = trials * d.N;

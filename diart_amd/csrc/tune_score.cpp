@@ -4,7 +4,8 @@
 //                        file that does not depend on the scores: rows, buffers, cropped rows, the first-chunk prepend
 //   dz_tune_replay_host  T x N (trial, file) chains on host threads, either through the existing handles (dz_clu_step ->
 //                        dz_tail_step: the yardstick of the GPU kernels and the backend of a machine without a GPU) or
-//                        through tune_core.h, the text the kernels are compiled from
+//                        through tune_core.h, the text the kernels are compiled from (the clustering decisions are
+//                        clu_core.h's either way: on the handles' heap store or on the kernels' fixed one)
 //   dz_tune_score        diarization error rate components of every pair from the packed frame masks
 //                        (diart_amd/metrics.py DiarizationErrorRate, collar 0, overlap included; PredictionAccumulator's
 //                        gap merging), without building an Annotation
@@ -117,7 +118,7 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
     struct Scratch {
         std::vector<double> a, b;
         std::vector<int> ia;
-        TcStep s;
+        TcStep<CluFixed> s;
     };
     std::vector<Scratch> scratch(nt);
     auto fail = [&](int w, int rc, const char* what) {

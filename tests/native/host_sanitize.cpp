@@ -34,19 +34,19 @@ extern "C" const char* dz_last_error(void) { return g_err; }
         }                                                                             \
     } while (0)
 
-namespace {
 constexpr int F = 293, K = 3, D = 64, G = 20;
+namespace {
 
 struct Streams {
     int n;
     std::vector<dz_clu*> clu;
     std::vector<dz_tail*> tail;
-    explicit Streams(int n_) : n(n_), clu(n_), tail(n_) {
+    explicit Streams(int n_, int g = G) : n(n_), clu(n_), tail(n_) {
         std::vector<double> ham(F);
         for (int i = 0; i < F; ++i) ham[i] = 0.54 - 0.46 * std::cos(2.0 * M_PI * i / (F - 1));
         for (int i = 0; i < n; ++i) {
-            CHECK(dz_clu_create(0.5, 0.3, 1.0, G, &clu[i]) == 0);
-            CHECK(dz_tail_create(F, G, 0.5, 2.5, 0.5, DZ_AGG_HAMMING, DZ_CROP_LOOSE, ham.data(), &tail[i]) == 0);
+            CHECK(dz_clu_create(0.5, 0.3, 1.0, g, &clu[i]) == 0);
+            CHECK(dz_tail_create(F, g, 0.5, 2.5, 0.5, DZ_AGG_HAMMING, DZ_CROP_LOOSE, ham.data(), &tail[i]) == 0);
         }
     }
     ~Streams() {
@@ -57,7 +57,7 @@ struct Streams {
     }
 };
 
-void fill(std::mt19937& rng, int n, int step, std::vector<float>& seg, std::vector<float>& emb) {
+void fill(std::mt19937& rng, int n, int step, std::vector<float>& seg, std::vector<float>& emb, int K = ::K, int G = ::G) {
     std::uniform_real_distribution<float> u(0.f, 1.f);
     std::normal_distribution<float> g(0.f, 1.f);
     seg.resize((size_t)n * F * K);
@@ -72,7 +72,7 @@ void fill(std::mt19937& rng, int n, int step, std::vector<float>& seg, std::vect
                 seg[((size_t)i * F + f) * K + k] = v;
             }
         for (int k = 0; k < K; ++k) {
-            const int spk = (int)(rng() % 30);           // up to 30 identities for 20 centroids
+            const int spk = (int)(rng() % (G + 10));     // ten identities more than centroids
             for (int d = 0; d < D; ++d)
                 emb[((size_t)i * K + k) * D + d] = std::sin(0.37f * (float)(spk + 1) * (float)(d + 1)) + 0.05f * g(rng);
         }
@@ -80,15 +80,17 @@ void fill(std::mt19937& rng, int n, int step, std::vector<float>& seg, std::vect
     }
 }
 
-void run_streams(unsigned seed, int n, int steps, int threads) {
+// K, G: beyond 8 local and 32 global speakers only the heap-backed store of the decision core runs
+void run_streams(unsigned seed, int n, int steps, int threads, int K = ::K, int G = ::G) {
     std::mt19937 rng(seed);
-    Streams s(n), one(n);
+    const int max_turns = 64 * G;
+    Streams s(n, G), one(n, G);
     std::vector<float> seg, emb;
-    std::vector<double> scores((size_t)n * F * G), scores1((size_t)F * G), agg((size_t)n * (F + 2) * G), turns((size_t)n * 256 * 3);
+    std::vector<double> scores((size_t)n * F * G), scores1((size_t)F * G), agg((size_t)n * (F + 2) * G), turns((size_t)n * max_turns * 3);
     std::vector<double> start(n), res(n, 5.0 / F), t0(n), rout(n);
     std::vector<int> assign((size_t)n * K), assign1(K), rows(n), nturns(n);
     for (int t = 0; t < steps; ++t) {
-        fill(rng, n, t, seg, emb);
+        fill(rng, n, t, seg, emb, K, G);
         CHECK(dz_clu_step_batch(s.clu.data(), n, seg.data(), F, K, emb.data(), D, scores.data(), assign.data(), threads) == 0);
         for (int i = 0; i < n; ++i) {                    // the batch on the pool == one stream at a time on this thread
             CHECK(dz_clu_step(one.clu[i], &seg[(size_t)i * F * K], F, K, &emb[(size_t)i * K * D], D, scores1.data(), assign1.data()) == 0);
@@ -99,8 +101,8 @@ void run_streams(unsigned seed, int n, int steps, int threads) {
         }
         for (double v : scores) CHECK(std::isfinite(v));
         CHECK(dz_tail_step_batch(s.tail.data(), n, scores.data(), start.data(), res.data(), agg.data(), rows.data(), t0.data(),
-                                 rout.data(), turns.data(), 256, nturns.data(), threads) == 0);
-        for (int i = 0; i < n; ++i) CHECK(rows[i] >= 0 && rows[i] <= F + 2 && nturns[i] >= 0 && nturns[i] <= 256);
+                                 rout.data(), turns.data(), max_turns, nturns.data(), threads) == 0);
+        for (int i = 0; i < n; ++i) CHECK(rows[i] >= 0 && rows[i] <= F + 2 && nturns[i] >= 0 && nturns[i] <= max_turns);
         if (t % 17 == 16) {                              // a stream that ends and starts again
             CHECK(dz_clu_reset(s.clu[t % n]) == 0 && dz_clu_reset(one.clu[t % n]) == 0);
             CHECK(dz_tail_reset(s.tail[t % n]) == 0);
@@ -138,7 +140,7 @@ void run_lsap(unsigned seed) {
     std::mt19937 rng(seed);
     std::uniform_real_distribution<double> u(0.0, 2.0);
     for (int it = 0; it < 300; ++it) {
-        const int nr = 1 + (int)(rng() % 6), nc = 1 + (int)(rng() % 24);
+        const int nr = 1 + (int)(rng() % 12), nc = 1 + (int)(rng() % 40);
         std::vector<double> cost((size_t)nr * nc);
         for (double& c : cost) c = rng() % 5 == 0 ? 1e10 : u(rng);
         std::vector<int> col(nr, -2);
@@ -151,6 +153,7 @@ void run_lsap(unsigned seed) {
 int main(int argc, char** argv) {
     const int steps = argc > 1 ? atoi(argv[1]) : 60;
     run_lsap(1);
+    run_streams(5, 4, steps, 2, 10, 40);
     for (int threads : {1, 3, 8}) {
         run_streams(10u + threads, 16, steps, threads);
         run_files(20u + threads, 5, steps / 2, threads);

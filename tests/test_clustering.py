@@ -16,6 +16,7 @@ from oracle.clustering_ref import OnlineSpeakerClusteringRef
 GOLD = Path(__file__).resolve().parent / "golden"
 sys.path.insert(0, str(GOLD))
 import scenarios  # noqa: E402
+import tune_cases  # noqa: E402
 
 
 def _swf(a):
@@ -59,12 +60,15 @@ def test_oracle_matches_reference_golden(name):
 
 
 @pytest.mark.parametrize("seed,K,D,G,delta", [(0, 3, 32, 20, 1.0), (1, 4, 16, 20, 0.8), (2, 3, 8, 3, 0.5),
-                                               (3, 4, 12, 4, 0.9), (4, 3, 512, 20, 1.057)])
+                                               (3, 4, 12, 4, 0.9), (4, 3, 512, 20, 1.057),
+                                               (5, 10, 32, 40, 0.5), (6, 12, 8, 9, 0.7)])
 def test_cpp_matches_oracle_long_random(seed, K, D, G, delta):
     """>= 10k steps in total across the parametrisations, with NaN embeddings, silent chunks,
-    duplicated embeddings (ties) and more speakers than centroids."""
+    duplicated embeddings (ties) and more speakers than centroids.  Seeds 5 and 6 lie beyond what the tuner's
+    fixed store holds (K <= 8, G <= 32), where only the handles' heap store runs: all 40 centroids in use, and
+    the transposed assignment problem with K = 12 (600 steps each: the oracle is slow at these sizes)."""
     rng = np.random.default_rng(seed)
-    T, F = (2500 if D < 100 else 400), 24
+    T, F = (600 if K > 8 else 2500 if D < 100 else 400), 24
     pool = rng.standard_normal((G + 6, D))
     cpp = OnlineSpeakerClustering(0.55, 0.25, delta, "cosine", G)
     ref = OnlineSpeakerClusteringRef(0.55, 0.25, delta, "cosine", G)
@@ -84,6 +88,54 @@ def test_cpp_matches_oracle_long_random(seed, K, D, G, delta):
         assert np.array_equal(got, want), (seed, t)
         assert cpp.active_centers == ref.active_centers
     assert np.allclose(cpp.centers, ref.centers, rtol=0, atol=1e-9)
+    if seed == 5:
+        assert len(cpp.active_centers) == G
+
+
+def failing_step_case(seed):
+    """tune_cases.failing_step_inputs(seed) up to and including the first step at which the oracle raises:
+    (K, G, [(seg, emb), ...], the oracle after them, its exception or None)."""
+    K, G, seg, emb = tune_cases.failing_step_inputs(seed)
+    ref = OnlineSpeakerClusteringRef(0.55, 0.25, 1e11, "cosine", G)
+    steps, err = [], None
+    for t in range(len(seg)):
+        steps.append((seg[t], emb[t]))
+        try:
+            ref(seg[t], emb[t])
+        except (AssertionError, ValueError) as e:
+            err = e
+            break
+    return K, G, steps, ref, err
+
+
+def test_state_after_a_failing_step_is_the_oracles():
+    """The reference updates centroids pair by pair and asserts mid-loop ("Cannot update unknown centers"), so a
+    step that raises has already added the embeddings of the pairs before the failing one.  dz_clu_step decides
+    first (csrc/clu_core.h) and applies afterwards: after a failing step its centroids and active set must be the
+    oracle's.  200 short streams; at the commit before the handles moved onto the core, 163 of them reached a failing
+    step, 47 of those after that step had changed a centroid, and the state was the oracle's in all 163."""
+    failed = changed_first = 0
+    for seed in range(200):
+        K, G, steps, ref, err = failing_step_case(seed)
+        cpp = OnlineSpeakerClustering(0.55, 0.25, 1e11, "cosine", G)
+        for seg, emb in steps[:-1] if err is not None else steps:
+            cpp(_swf(seg), torch.from_numpy(emb))
+        if err is None:
+            assert cpp.active_centers == ref.active_centers, seed
+            assert np.allclose(cpp.centers, ref.centers, rtol=0, atol=1e-12), seed
+            continue
+        failed += 1
+        before = cpp.centers
+        seg, emb = steps[-1]
+        with pytest.raises(AssertionError) as got:      # the C++ returns non-zero exactly when the oracle raises
+            cpp(_swf(seg), torch.from_numpy(emb))
+        if "Cannot update unknown centers" in str(err):
+            assert str(got.value) == "Cannot update unknown centers", seed
+        assert cpp.active_centers == ref.active_centers, seed
+        assert np.allclose(cpp.centers, ref.centers, rtol=0, atol=1e-12), seed
+        changed_first += not np.array_equal(before, ref.centers)
+    print(f"failing steps: {failed} of 200 seeds, {changed_first} after changing a centroid")
+    assert failed >= 100 and changed_first >= 20
 
 
 @pytest.mark.parametrize("seed,K,D,G,tau,rho,delta", scenarios.CLUSTERING_LONG_RANDOM)

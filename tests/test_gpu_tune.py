@@ -65,7 +65,8 @@ def test_long_random(gpu, seed, K, D, G, tau, rho, delta):
 @pytest.mark.parametrize("name", list(tc.EDGES))
 def test_edges(gpu, name):
     """D = 1 and D = 15 (dot2's odd tail), K = 1, G = 1, F = 1, 1 < G < K (K = 4 with G = 3, K = 8 with G = 5: the
-    transposed assignment problem), a file of one chunk beside one of 61, T = 1 and T = 67, latency = step, 2.5 and 5.0."""
+    transposed assignment problem), a file of one chunk beside one of 61, T = 1 and T = 67, latency = step, 2.5 and 5.0;
+    `raises`: a chain that stops at the chunk where the reference raises "Cannot update unknown centers"."""
     cache, hp = tc.edge_cache(name)
     assert hp.shape[0] == tc.EDGES[name][5]
     host, dev = _both(cache, hp)

@@ -99,10 +99,30 @@ def long_random(seed, K, D, G, steps: int = 300):
     return np.stack(seg), np.stack(emb)
 
 
+def failing_step_inputs(seed: int):
+    """Six steps of a short stream with more local than global speakers (K 5..8, G 3..4; D 8, 12 frames), two of them
+    at most active in the first: (K, G, seg, emb).  Under tau 0.55, rho 0.25 and a delta_new that unmaps nobody (1e11)
+    most seeds reach a step at which the reference raises "Cannot update unknown centers", many of them after that
+    step has updated a centroid (tests/test_clustering.py test_state_after_a_failing_step_is_the_oracles)."""
+    rng = np.random.default_rng(1000 + seed)
+    K, G, D, F = int(rng.integers(5, 9)), int(rng.integers(3, 5)), 8, 12
+    seg = np.zeros((6, F, K), dtype=np.float32)
+    emb = np.zeros((6, K, D), dtype=np.float32)
+    for t in range(6):
+        seg[t] = rng.random((F, K)) * (rng.random(K) < 0.5) * rng.choice([0.3, 0.8, 1.0], K)
+        emb[t] = rng.standard_normal((K, D))
+        if t == 0:
+            seg[t, :, 0] = 0.9
+            seg[t, :, 2:] = 0
+    return K, G, seg, emb
+
+
 # name -> (F, K, D, G, latency, trials): D = 1 and 15 (dot2's odd tail), one local / one global speaker, one frame,
 # one trial and 67, fewer centroids than local speakers with more than one of them (1 < G < K: the transposed
 # assignment problem whose pairs have to be sorted by row, and `valid` enumerating a column list shorter than K; K = 8
-# is the capacity of the fixed arrays); every case is a file of one chunk beside one of 61
+# is the capacity of the fixed arrays); every case is a file of one chunk beside one of 61.  "raises": beside the one
+# chunk, failing_step_inputs(RAISES_SEED), whose chunk 3 makes dz_clu_step return non-zero ("Cannot update unknown
+# centers") under the first trial, after it has decided a centroid update; the other trials are uniform draws
 EDGES = {
     "D1": (16, 3, 1, 4, 2.5, 67),
     "D15": (16, 3, 15, 4, 0.5, 67),
@@ -115,16 +135,23 @@ EDGES = {
     "lat_step": (32, 4, 24, 20, 0.5, 9),
     "lat_mid": (32, 4, 24, 20, 2.5, 9),
     "lat_max": (32, 4, 24, 20, 5.0, 9),
+    "raises": (12, 8, 8, 4, 2.5, 9),
 }
+RAISES_SEED, RAISES_OWN = 17, (0.55, 0.25, 1e11)
 
-EDGE_SEEDS = sorted(n for n in EDGES if n not in ("K4G3", "K8G5")) + ["K4G3", "K8G5"]
+EDGE_SEEDS = sorted(n for n in EDGES if n not in ("K4G3", "K8G5", "raises")) + ["K4G3", "K8G5", "raises"]
 
 
 def edge_cache(name):
     from diart_amd.optim import TuneCache
     F, K, D, G, latency, T = EDGES[name]
     seed = EDGE_SEEDS.index(name)
-    files = [file_of(*random_outputs(100 + seed, 1, F, K, D), shift=0.0, uri="one"),
-             file_of(*random_outputs(200 + seed, 61, F, K, D), shift=-1.25, uri="sixty-one")]
-    cache = TuneCache.from_arrays(files, config_of(0.5, 0.3, 1.0, G, latency))
-    return cache, random_trials((0.5, 0.3, 1.0), T, seed=seed) if T > 1 else np.array([[0.5, 0.3, 1.0]])
+    own = RAISES_OWN if name == "raises" else (0.5, 0.3, 1.0)
+    if name == "raises":
+        assert failing_step_inputs(RAISES_SEED)[:2] == (K, G)
+        second = file_of(*failing_step_inputs(RAISES_SEED)[2:], shift=-1.25, uri="six")
+    else:
+        second = file_of(*random_outputs(200 + seed, 61, F, K, D), shift=-1.25, uri="sixty-one")
+    files = [file_of(*random_outputs(100 + seed, 1, F, K, D), shift=0.0, uri="one"), second]
+    cache = TuneCache.from_arrays(files, config_of(*own, G, latency))
+    return cache, random_trials(own, T, seed=seed) if T > 1 else np.array([own])
