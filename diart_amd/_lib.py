@@ -236,6 +236,11 @@ SIGNATURES = {
                                       C.c_int, C.c_int]),
     "dz_tune_score": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp,
                                 C.c_int]),
+    "dz_tune_vad_rows": (C.c_int, [vp, C.POINTER(TuneDesc), vp, vp]),
+    "dz_tune_vad_score": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp,
+                                    vp]),
+    "dz_tune_vad_host": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp,
+                                   C.c_int]),
     "dz_rows_repeat": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, c_int_p]),
     # kernel-level entry points
     "dz_k_convgemm": (C.c_int, [vp, vp, vp]),

@@ -95,6 +95,13 @@ class VoiceActivityDetection(base.Pipeline):
         batch = windows_batch(waveforms, self.config.device)
         return self.finalise(waveforms, self.segmentation(batch))
 
+    def model_outputs(self, waveforms: Sequence[SlidingWindowFeature]) -> torch.Tensor:
+        """The model half of ``__call__``: what ``finalise`` computes as ``voice_detection``, ``(batch, frames, 1)``
+        float32 on the host.  Nothing here depends on ``tau_active``: ``optim.VadTuneCache`` keeps these tracks and
+        replays the aggregation and the binarisation per trial."""
+        batch = windows_batch(waveforms, self.config.device)
+        return torch.max(self.segmentation(batch), dim=-1, keepdim=True)[0].float().cpu()
+
     def finalise(self, waveforms: Sequence[SlidingWindowFeature], segmentations: torch.Tensor):
         """The host half of ``__call__`` (reference vad.py:146-191) for given segmentation scores."""
         voice_detection = torch.max(segmentations, dim=-1, keepdim=True)[0]   # (batch, frames, 1)

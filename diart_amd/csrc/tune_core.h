@@ -4,7 +4,8 @@
 // G <= TC_GMAX, the whole state in LDS); what this file adds is how the lanes of a wavefront share the arithmetic that
 // feeds them (each norm and each of the K x G distances summed by ONE lane in the core's order).  Host and device
 // compile this text: k_tune.hip for the kernels, tune_score.cpp for backend="core", which tests/test_tune_host.py
-// holds against dz_clu_step + dz_tail_step.
+// holds against dz_clu_step + dz_tail_step.  The VoiceActivityDetection half (tc_vad_*, at the end) is k_tune_vad.hip's
+// and dz_tune_vad_host's in the same way.
 #pragma once
 #include "../../include/diart_amd.h"
 #include "clu_core.h"
@@ -131,3 +132,97 @@ TC_HD unsigned tc_row_mask(const dz_tune_desc& d, int p, double tau, const signe
     if (0.0 > tau) out |= all & ~seen;   // a speaker nobody was mapped to scores 0.0
     return out;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// VoiceActivityDetection (one track per chunk: K = G = 1, seg is (chunks, F), no clustering).
+//
+// tc_vad_row: the aggregated speech score of packed output row p, the value tc_row_mask compares with tau when
+// the one local speaker of every buffer is mapped.  It does not depend on tau: computed once per cache.
+// ---------------------------------------------------------------------------------------------------------
+TC_HD double tc_vad_row(const dz_tune_desc& d, int p) {
+    const int F = d.F;
+    const int c = d.row_chunk[p], r = p - d.row_off[c];
+    const int* plan = d.plan + (long)c * (4 + d.nwin);
+    const int pre = plan[1], nbuf = plan[3];
+    if (r < pre) return (double)d.seg[(long)c * F + tc_clip(plan[2] + r, F - 1)];
+    const int ra = r - pre;
+    const long cb0 = c - nbuf + 1;
+    double den = 0.0, num = 0.0;
+    for (int b = 0; b < nbuf; ++b) {
+        const int row = tc_clip(plan[4 + b] + ra, F - 1);
+        const double h = d.hamming[row];
+        const double term = h * (double)d.seg[(cb0 + b) * F + row];
+        den = b == 0 ? h : den + h;
+        num = b == 0 ? term : num + term;
+    }
+    return tc_div(num, den);
+}
+
+// What the detection error rate of one (trial, file) needs besides the file's constants: the duration the merged
+// speech turns cover, and the part of it in which the reference is active.
+struct TcVadSum {
+    double hyp, both;
+};
+// The end of the latest-ending turn so far and the scoring cell that starts there (-infinity: no turn yet).
+struct TcVadEnd {
+    double e;
+    int cell;
+};
+
+// Steps [c_lo, c_hi) of one file under one tau, in order.  Row r of a step is speech when agg > tau; a turn runs
+// from mid[onset] to mid[first inactive row] (the row after the step's last closes an open turn; mids holds rows + 1
+// values per step), turns no longer than 1e-6 are dropped (Segment.__bool__).  Turns arrive sorted by start (the
+// cache checks that the steps' grids are), so Annotation.support(collar) is a running maximum: a turn whose gap to
+// `end` is <= 1e-6 or < collar extends the covered span from `end` to its own end (if that is later), any other
+// turn opens a new span.  Every turn therefore adds the cells [from, its end cell) with from = the cell of `end`
+// or its own start cell: nothing is covered twice.  Durations are differences of the file's prefix sums
+// (dur_prefix / ref_prefix: ncell + 1 values, cell_dur and cell_dur where the reference is active, summed in order).
+TC_HD TcVadEnd tc_vad_walk(const double* agg, const int* row_off, const double* mids, const int* mid_cell,
+                           const double* dur_prefix, const double* ref_prefix, double tau, double collar, int c_lo,
+                           int c_hi, TcVadEnd end, TcVadSum* sum) {
+    for (int c = c_lo; c < c_hi; ++c) {
+        const int p = row_off[c], rows = row_off[c + 1] - p;
+        const double* mid = mids + (long)p + c;
+        const int* cell = mid_cell + (long)p + c;
+        int onset = -1;
+        for (int r = 0; r <= rows; ++r) {
+            const bool on = r < rows && agg[p + r] > tau;
+            if (on && onset < 0) onset = r;
+            if (!on && onset >= 0) {
+                const double s = mid[onset], e = mid[r];
+                if (e - s > 1e-6) {
+                    const double gap = s - end.e;
+                    int from = cell[onset];
+                    bool adds = true;
+                    if (gap <= 1e-6 || gap < collar) {
+                        from = end.cell;
+                        adds = e > end.e;
+                    }
+                    if (adds) {
+                        const int to = cell[r];
+                        sum->hyp += dur_prefix[to] - dur_prefix[from];
+                        sum->both += ref_prefix[to] - ref_prefix[from];
+                        end.e = e;
+                        end.cell = to;
+                    }
+                }
+                onset = -1;
+            }
+        }
+    }
+    return end;
+}
+
+// The five components (metrics.COMPONENTS) of DetectionErrorRate as dz_tune_score builds them for one hypothesis
+// label and one reference label: the confusion is 0.
+TC_HD void tc_vad_components(double total, TcVadSum s, double* o) {
+    const double fa = s.hyp - s.both, missed = total - s.both;
+    o[0] = total;
+    o[1] = s.both;
+    o[2] = fa > 0.0 ? fa : 0.0;
+    o[3] = missed > 0.0 ? missed : 0.0;
+    o[4] = 0.0;
+}
+
+// How a workgroup of nl lanes shares a file of `chunks` steps: lane i walks steps [i * per, (i + 1) * per).
+TC_HD int tc_vad_steps_per_lane(int chunks, int nl) { return (chunks + nl - 1) / nl; }

@@ -9,6 +9,8 @@
 //   dz_tune_score        diarization error rate components of every pair from the packed frame masks
 //                        (diart_amd/metrics.py DiarizationErrorRate, collar 0, overlap included; PredictionAccumulator's
 //                        gap merging), without building an Annotation
+//   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
+//                        scoring of k_tune_vad.hip, from the text those kernels compile
 #include "tune_core.h"
 
 #include <algorithm>
@@ -346,5 +348,73 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
                                      : "dz_tune_score: the mapping's assignment problem failed");
             return rcs[w];
         }
+    return 0;
+}
+
+// VoiceActivityDetection on the host, from the text k_tune_vad.hip compiles: agg (total_rows) once,
+// bits (T, total_rows) = agg > tau, and — where `out` is given — the components as tune_vad_score_kernel forms them,
+// `lanes` lanes of a workgroup played one after the other (backend="core"; backend="host" scores the bits with
+// dz_tune_score instead, the yardstick of the device scoring).
+extern "C" int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+                                const double* mids, const int* mid_cell, const int* file_cell_off,
+                                const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
+                                int num_threads) {
+    if (!d || !taus || !agg || trials < 1 || !d->seg || !d->chunk_off || !d->plan || !d->row_off || !d->row_chunk ||
+        !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->nwin < 1 || d->total_rows < 1 ||
+        (out && (!mids || !mid_cell || !file_cell_off || !dur_prefix || !ref_prefix || lanes < 1))) {
+        dz_set_error("dz_tune_vad_host: bad arguments (one track per chunk expected)");
+        return 2;
+    }
+    const int N = d->N, rows = d->total_rows;
+    int nt = num_threads < 1 ? 1 : num_threads;
+    {   // the rows, in slices
+        const int slices = rows < nt ? rows : nt;
+        auto run = [&](int, int s) {
+            const int a = (int)((long long)rows * s / slices), b = (int)((long long)rows * (s + 1) / slices);
+            for (int p = a; p < b; ++p) agg[p] = tc_vad_row(*d, p);
+        };
+        if (slices == 1) run(0, 0);
+        else dz_host_parallel(slices, slices, run);
+    }
+    if (bits) {
+        auto run = [&](int, int t) {
+            unsigned* B = bits + (size_t)t * rows;
+            const double tau = taus[t];
+            for (int p = 0; p < rows; ++p) B[p] = agg[p] > tau ? 1u : 0u;
+        };
+        if (nt == 1 || trials == 1)
+            for (int t = 0; t < trials; ++t) run(0, t);
+        else
+            dz_host_parallel(trials, nt < trials ? nt : trials, run);
+    }
+    if (out) {
+        const int pairs = trials * N;
+        if (nt > pairs) nt = pairs;
+        auto run = [&](int, int pair) {
+            const int t = pair / N, n = pair - t * N;
+            const int c0 = d->chunk_off[n], c1 = d->chunk_off[n + 1];
+            const int per = tc_vad_steps_per_lane(c1 - c0, lanes);
+            const double* dp = dur_prefix + (size_t)file_cell_off[n] + n;
+            const double* rp = ref_prefix + (size_t)file_cell_off[n] + n;
+            const TcVadEnd none = {-INFINITY, 0};
+            TcVadEnd before = none;
+            TcVadSum all = {0.0, 0.0};
+            for (int lane = 0; lane < lanes; ++lane) {
+                const int lo = c0 + ((long long)lane * per < c1 - c0 ? lane * per : c1 - c0);
+                const int hi = lo + per < c1 ? lo + per : c1;
+                TcVadSum scratch = {0.0, 0.0}, s = {0.0, 0.0};
+                const TcVadEnd own = tc_vad_walk(agg, d->row_off, mids, mid_cell, dp, rp, taus[t], collar, lo, hi, none, &scratch);
+                tc_vad_walk(agg, d->row_off, mids, mid_cell, dp, rp, taus[t], collar, lo, hi, before, &s);
+                all.hyp += s.hyp;
+                all.both += s.both;
+                if (own.e > before.e) before = own;
+            }
+            tc_vad_components(rp[file_cell_off[n + 1] - file_cell_off[n]], all, out + (size_t)pair * 5);
+        };
+        if (nt == 1)
+            for (int i = 0; i < pairs; ++i) run(0, i);
+        else
+            dz_host_parallel(pairs, nt, run);
+    }
     return 0;
 }

@@ -13,6 +13,11 @@ binarisation -> diarization error rate.  The ``T x N`` chains of T trials over N
   bit for bit (``tests/test_gpu_tune.py``); what a machine without a GPU runs.
 
 Either way ``dz_tune_score`` turns the masks into the error-rate components on host threads.  DESIGN.md 4.16.
+
+``VoiceActivityDetection`` has ``tau_active`` alone and no clustering: ``VadTuneCache`` keeps one track per chunk (the
+max over the local speakers), its aggregated speech score per output frame is computed once per cache, and a trial is
+one comparison per frame plus the detection error rate — on the GPU both in HIP kernels (``csrc/k_tune_vad.hip``), so
+that a batch of trials returns ``T x N x 5`` doubles and nothing else.
 """
 from __future__ import annotations
 
@@ -28,9 +33,10 @@ import torch
 from . import _lib
 from .blocks import base
 from .features import Annotation, Segment
-from .metrics import DiarizationErrorRate, _turns
+from .metrics import DetectionErrorRate, DiarizationErrorRate, _turns
 
 TUNABLE = ("tau_active", "rho_update", "delta_new")
+VAD_TUNABLE = ("tau_active",)
 MAX_SPEAKERS = 32          # the hypothesis of a frame is one 32-bit mask
 MAX_LOCAL_SPEAKERS = 8
 PATCH_COLLAR = 0.05        # PredictionAccumulator's default
@@ -60,7 +66,153 @@ def _reference_turns(reference) -> List[tuple]:
     return _turns(ann)
 
 
-class TuneCache:
+class _ReplayCache:
+    """What ``TuneCache`` and ``VadTuneCache`` share: the file handling of ``collect``, and the trial-independent
+    preparation — the output tail's plan (rows, buffers and cropped rows of every step, first-chunk prepend included),
+    the frame middles of every step's output grid and the file's scoring cells (the sorted union of every time at
+    which a hypothesis turn can start or end and of the reference's turn boundaries, each with its duration and the
+    reference bits active in it).  A subclass sets ``files`` (dicts with ``uri``, ``starts``, ``res``, ``shift``,
+    ``turns``), ``meta`` (``step``, ``latency``), ``F`` and ``N``, and says which bit a reference label is."""
+
+    def _reference_bits(self, f: dict) -> Dict[object, int]:
+        raise NotImplementedError
+
+    @staticmethod
+    def _collect_files(pipeline, speech_path, reference_path, batch_size: int, outputs) -> List[dict]:
+        """Every WAV of ``speech_path`` with ``Benchmark.run_single``'s file handling: ``outputs(batch)`` gives the
+        model outputs of a batch of chunks as numpy arrays (the first one ``(batch, frames, ...)``); per file their
+        concatenation over the chunks, the window starts, ``finalise``'s frame resolution, the shift, the reference."""
+        from .features import load_rttm
+        from .inference import file_blocks, read_wav, resample_file, rolling_windows
+        speech_path, reference_path = Path(speech_path).expanduser(), Path(reference_path).expanduser()
+        assert speech_path.is_dir(), "Speech path must be a directory"
+        assert reference_path.is_dir(), "Reference path must be a directory"
+        cfg = pipeline.config
+        files = []
+        for fp in sorted(p for p in speech_path.iterdir() if p.suffix.lower() == ".wav"):
+            waveform, sr = read_wav(fp)
+            padding = cfg.get_padding(len(waveform) / sr)
+            if sr != cfg.sample_rate:
+                if getattr(getattr(cfg, "device", None), "type", None) != "cuda":
+                    raise ValueError(f"{fp} has sample rate {sr}, the pipeline's is {cfg.sample_rate} and the pipeline "
+                                     "has no GPU device to resample on; resample the file first")
+                waveform, sr = resample_file(waveform, sr, cfg.sample_rate, cfg.device), cfg.sample_rate
+            outs, starts, res, batch = [], [], [], []
+
+            def flush():
+                arrays = outputs(batch)
+                outs.append(arrays)
+                starts.extend(w.extent.start for w in batch)
+                res.extend([batch[0].extent.duration / arrays[0].shape[1]] * len(batch))     # finalise's seg_resolution
+                batch.clear()
+
+            for window in rolling_windows(file_blocks(waveform, sr, padding, cfg.step), cfg.duration, cfg.step, sr):
+                batch.append(window)
+                if len(batch) == max(1, int(batch_size)):
+                    flush()
+            if batch:
+                flush()
+            if not outs:
+                raise ValueError(f"{fp} is shorter than one chunk")
+            files.append(dict(uri=fp.stem, outputs=[np.concatenate(a) for a in zip(*outs)], starts=np.array(starts),
+                              res=np.array(res), shift=-padding[0],
+                              reference=load_rttm(reference_path / f"{fp.stem}.rttm").popitem()[1]))
+        return files
+
+    def _prepare_plan(self) -> None:
+        lib = _lib.load()
+        F, m = self.F, self.meta
+        self.nwin = int(round(m["latency"] / m["step"]))
+        self.starts = np.concatenate([f["starts"] for f in self.files])
+        self.res = np.concatenate([f["res"] for f in self.files])
+        counts = [f["starts"].shape[0] for f in self.files]
+        self.chunk_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        total = int(self.chunk_off[-1])
+        self.hamming = np.ascontiguousarray(np.hamming(F), dtype=np.float64)
+        # the tail's plan, file by file
+        self.plan = np.zeros((total, 4 + self.nwin), dtype=np.int32)
+        self.t0, self.out_res = np.zeros(total), np.zeros(total)
+        for n in range(self.N):
+            a, b = int(self.chunk_off[n]), int(self.chunk_off[n + 1])
+            plan, t0, res = self.plan[a:b], self.t0[a:b], self.out_res[a:b]
+            _lib.check(lib.dz_tune_plan(b - a, F, m["step"], m["latency"], self.starts[a:b].ctypes.data,
+                                        self.res[a:b].ctypes.data, plan.ctypes.data, t0.ctypes.data, res.ctypes.data),
+                       "dz_tune_plan")
+        self.step_rows = np.ascontiguousarray(self.plan[:, 0] + self.plan[:, 1], dtype=np.int32)
+        self.row_off = np.concatenate([[0], np.cumsum(self.step_rows)]).astype(np.int32)
+        self.total_rows = int(self.row_off[-1])
+        self.row_chunk = np.repeat(np.arange(total, dtype=np.int32), self.step_rows)
+        self.file_row_off = np.ascontiguousarray(self.row_off[self.chunk_off], dtype=np.int32)
+        # frame middles of every step's output grid (rows + 1 per step: the row after the last closes open turns),
+        # with Binarize's expression, plus the shift
+        per = self.step_rows.astype(np.int64) + 1
+        step_of = np.repeat(np.arange(total), per)
+        first = np.concatenate([[0], np.cumsum(per)])[:-1]
+        i = (np.arange(int(per.sum())) - first[step_of]).astype(np.float64)
+        s = self.t0[step_of] + i * self.out_res[step_of]
+        shift = np.repeat(np.array([f["shift"] for f in self.files]), np.diff(self.chunk_off))[step_of]
+        self.mids = np.ascontiguousarray(0.5 * (s + (s + self.out_res[step_of])) + shift)
+        # scoring cells
+        self.mid_cell = np.zeros(self.mids.shape[0], dtype=np.int32)
+        durs, refs, cell_off = [], [], [0]
+        self.ref_labels = []
+        for n, f in enumerate(self.files):
+            a = int(self.file_row_off[n] + self.chunk_off[n])
+            b = int(self.file_row_off[n + 1] + self.chunk_off[n + 1]) if n + 1 < self.N else self.mids.shape[0]
+            bit = self._reference_bits(f)
+            rs = np.array([t[0] for t in f["turns"]], dtype=np.float64)
+            re = np.array([t[1] for t in f["turns"]], dtype=np.float64)
+            bounds = np.unique(np.concatenate([self.mids[a:b], rs, re]))
+            self.mid_cell[a:b] = np.searchsorted(bounds, self.mids[a:b])
+            mask = np.zeros(bounds.shape[0] - 1, dtype=np.uint64)
+            for (s_, e_, l) in f["turns"]:
+                i0, i1 = np.searchsorted(bounds, s_), np.searchsorted(bounds, e_)
+                mask[i0:i1] |= np.uint64(1) << np.uint64(bit[l])
+            durs.append(np.diff(bounds))
+            refs.append(mask)
+            cell_off.append(cell_off[-1] + mask.shape[0])
+        self.cell_dur = np.ascontiguousarray(np.concatenate(durs), dtype=np.float64)
+        self.cell_ref = np.ascontiguousarray(np.concatenate(refs), dtype=np.uint64)
+        self.file_cell_off = np.array(cell_off, dtype=np.int32)
+
+    @staticmethod
+    def default_backend() -> str:
+        return "gpu" if torch.cuda.is_available() else "host"
+
+    def _score_bits(self, bits: np.ndarray, max_speakers: int, num_threads: int) -> np.ndarray:
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        T = bits.shape[0]
+        out = np.zeros((T, self.N, 5), dtype=np.float64)
+        _lib.check(_lib.load().dz_tune_score(T, self.N, bits.ctypes.data, self.total_rows, self.file_row_off.ctypes.data,
+                                             self.chunk_off.ctypes.data, self.step_rows.ctypes.data, self.mids.ctypes.data,
+                                             self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
+                                             self.cell_dur.ctypes.data, self.cell_ref.ctypes.data, max_speakers, PATCH_COLLAR,
+                                             out.ctypes.data, int(num_threads)), "dz_tune_score")
+        return out
+
+    def _hypothesis(self, bits_row: np.ndarray, n: int, speakers: int, label) -> Annotation:
+        ann = Annotation(uri=self.files[n]["uri"], modality="speech")
+        p, m = int(self.file_row_off[n]), int(self.file_row_off[n] + self.chunk_off[n])
+        for c in range(int(self.chunk_off[n]), int(self.chunk_off[n + 1])):
+            rows = int(self.step_rows[c])
+            b = bits_row[p:p + rows]
+            for g in range(speakers):
+                on = np.concatenate([[False], (b >> np.uint32(g)) & np.uint32(1) > 0, [False]])
+                edges = np.flatnonzero(on[1:] != on[:-1])
+                for s, e in zip(edges[::2], edges[1::2]):
+                    ann[Segment(self.mids[m + s], self.mids[m + e]), g] = label(g)
+            p, m = p + rows, m + rows + 1
+        return ann.support(PATCH_COLLAR)
+
+
+def _rates(comp: np.ndarray) -> np.ndarray:
+    """``_Accumulating._rate`` of ``(T, 5)`` components."""
+    err = comp[:, 2] + comp[:, 3] + comp[:, 4]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(comp[:, 0] > 0, err / comp[:, 0], np.where(err == 0, 0.0, 1.0))
+
+
+class TuneCache(_ReplayCache):
     """The trial-independent half of a tuning run: per file the model outputs, the window start times, the frame
     resolution ``finalise`` was given, the timestamp shift and the reference turns — and, computed once from them on
     the host, what every trial shares: what ``identify`` derives from ``seg`` (float32 max, float32 sequential mean, NaN
@@ -110,50 +262,22 @@ class TuneCache:
     def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32) -> "TuneCache":
         """Run the model half of ``SpeakerDiarization`` once per WAV of ``speech_path`` (no ``finalise``, no
         clustering), with ``Benchmark.run_single``'s file handling."""
-        from .features import load_rttm
-        from .inference import file_blocks, read_wav, resample_file, rolling_windows
         _check_pipeline_class(pipeline_class)
         if int(base_config.max_speakers) > MAX_SPEAKERS:
             raise ValueError(f"max_speakers = {base_config.max_speakers}: the replay keeps one 32-bit mask per frame, "
                              f"at most {MAX_SPEAKERS} speakers")
-        speech_path, reference_path = Path(speech_path).expanduser(), Path(reference_path).expanduser()
-        assert speech_path.is_dir(), "Speech path must be a directory"
-        assert reference_path.is_dir(), "Reference path must be a directory"
         pipeline = pipeline_class(base_config)
-        cfg = pipeline.config
-        files = []
-        for fp in sorted(p for p in speech_path.iterdir() if p.suffix.lower() == ".wav"):
-            waveform, sr = read_wav(fp)
-            padding = cfg.get_padding(len(waveform) / sr)
-            if sr != cfg.sample_rate:
-                if getattr(getattr(cfg, "device", None), "type", None) != "cuda":
-                    raise ValueError(f"{fp} has sample rate {sr}, the pipeline's is {cfg.sample_rate} and the pipeline "
-                                     "has no GPU device to resample on; resample the file first")
-                waveform, sr = resample_file(waveform, sr, cfg.sample_rate, cfg.device), cfg.sample_rate
-            seg, emb, starts, res, batch = [], [], [], [], []
 
-            def flush():
-                s, e = pipeline.model_outputs(batch)
-                s = s.detach().cpu().numpy().astype(np.float32, copy=False)
-                e = e.detach().cpu().numpy().astype(np.float32, copy=False)
-                seg.append(s)
-                emb.append(e if e.ndim == 3 else e[None])
-                starts.extend(w.extent.start for w in batch)
-                res.extend([batch[0].extent.duration / s.shape[1]] * len(batch))     # finalise's seg_resolution
-                batch.clear()
+        def outputs(batch):
+            s, e = pipeline.model_outputs(batch)
+            s = s.detach().cpu().numpy().astype(np.float32, copy=False)
+            e = e.detach().cpu().numpy().astype(np.float32, copy=False)
+            return s, (e if e.ndim == 3 else e[None])
 
-            for window in rolling_windows(file_blocks(waveform, sr, padding, cfg.step), cfg.duration, cfg.step, sr):
-                batch.append(window)
-                if len(batch) == max(1, int(batch_size)):
-                    flush()
-            if batch:
-                flush()
-            if not seg:
-                raise ValueError(f"{fp} is shorter than one chunk")
-            files.append(dict(uri=fp.stem, seg=np.concatenate(seg), emb=np.concatenate(emb), starts=np.array(starts),
-                              res=np.array(res), shift=-padding[0],
-                              reference=load_rttm(reference_path / f"{fp.stem}.rttm").popitem()[1]))
-        return cls(files, cfg)
+        files = cls._collect_files(pipeline, speech_path, reference_path, batch_size, outputs)
+        for f in files:
+            f["seg"], f["emb"] = f.pop("outputs")
+        return cls(files, pipeline.config)
 
     def save(self, path) -> None:
         out = {"meta": np.array(json.dumps(self.meta)), "uris": np.array([f["uri"] for f in self.files])}
@@ -169,6 +293,8 @@ class TuneCache:
     @classmethod
     def load(cls, path) -> "TuneCache":
         with np.load(path, allow_pickle=False) as z:
+            if "kind" in z.files:
+                raise ValueError(f"{path} holds a {str(z['kind'])}, not a TuneCache (SpeakerDiarization)")
             meta = json.loads(str(z["meta"]))
             files = []
             for i, uri in enumerate(z["uris"]):
@@ -178,16 +304,18 @@ class TuneCache:
         return cls(files, meta)
 
     # ------------------------------------------------------------------------------------------ trial-independent parts
+    def _reference_bits(self, f: dict) -> Dict[object, int]:
+        labels = sorted({l for _, _, l in f["turns"]}, key=str)
+        if len(labels) > 64:
+            raise ValueError(f"{f['uri']}: {len(labels)} reference speakers (at most 64)")
+        self.ref_labels.append(labels)
+        return {l: i for i, l in enumerate(labels)}
+
     def _prepare(self) -> None:
-        lib = _lib.load()
-        F, K, m = self.F, self.K, self.meta
-        self.nwin = int(round(m["latency"] / m["step"]))
+        F, K = self.F, self.K
+        self._prepare_plan()
         self.seg = np.concatenate([f["seg"] for f in self.files])
         self.emb = np.concatenate([f["emb"] for f in self.files])
-        self.starts = np.concatenate([f["starts"] for f in self.files])
-        self.res = np.concatenate([f["res"] for f in self.files])
-        counts = [f["seg"].shape[0] for f in self.files]
-        self.chunk_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         total = int(self.chunk_off[-1])
         # what identify derives from seg: NaN flag, max, and the float32 mean summed over the frames in order
         seg_nan = np.isnan(self.seg).any(axis=1)
@@ -198,55 +326,6 @@ class TuneCache:
                 acc += self.seg[:, f, :]
             self.pre_mean = np.ascontiguousarray(acc / np.float32(F), dtype=np.float32)
         self.pre_flags = np.ascontiguousarray(seg_nan.astype(np.uint8) | (np.isnan(self.emb).any(axis=2).astype(np.uint8) << 1))
-        self.hamming = np.ascontiguousarray(np.hamming(F), dtype=np.float64)
-        # the tail's plan, file by file
-        self.plan = np.zeros((total, 4 + self.nwin), dtype=np.int32)
-        self.t0, self.out_res = np.zeros(total), np.zeros(total)
-        for n in range(self.N):
-            a, b = int(self.chunk_off[n]), int(self.chunk_off[n + 1])
-            plan, t0, res = self.plan[a:b], self.t0[a:b], self.out_res[a:b]
-            _lib.check(lib.dz_tune_plan(b - a, F, m["step"], m["latency"], self.starts[a:b].ctypes.data,
-                                        self.res[a:b].ctypes.data, plan.ctypes.data, t0.ctypes.data, res.ctypes.data),
-                       "dz_tune_plan")
-        self.step_rows = np.ascontiguousarray(self.plan[:, 0] + self.plan[:, 1], dtype=np.int32)
-        self.row_off = np.concatenate([[0], np.cumsum(self.step_rows)]).astype(np.int32)
-        self.total_rows = int(self.row_off[-1])
-        self.row_chunk = np.repeat(np.arange(total, dtype=np.int32), self.step_rows)
-        self.file_row_off = np.ascontiguousarray(self.row_off[self.chunk_off], dtype=np.int32)
-        # frame middles of every step's output grid (rows + 1 per step: the row after the last closes open turns),
-        # with Binarize's expression, plus the shift
-        per = self.step_rows.astype(np.int64) + 1
-        step_of = np.repeat(np.arange(total), per)
-        first = np.concatenate([[0], np.cumsum(per)])[:-1]
-        i = (np.arange(int(per.sum())) - first[step_of]).astype(np.float64)
-        s = self.t0[step_of] + i * self.out_res[step_of]
-        shift = np.repeat(np.array([f["shift"] for f in self.files]), np.diff(self.chunk_off))[step_of]
-        self.mids = np.ascontiguousarray(0.5 * (s + (s + self.out_res[step_of])) + shift)
-        # scoring cells
-        self.mid_cell = np.zeros(self.mids.shape[0], dtype=np.int32)
-        durs, refs, cell_off = [], [], [0]
-        self.ref_labels = []
-        for n, f in enumerate(self.files):
-            a = int(self.file_row_off[n] + self.chunk_off[n])
-            b = int(self.file_row_off[n + 1] + self.chunk_off[n + 1]) if n + 1 < self.N else self.mids.shape[0]
-            labels = sorted({l for _, _, l in f["turns"]}, key=str)
-            if len(labels) > 64:
-                raise ValueError(f"{f['uri']}: {len(labels)} reference speakers (at most 64)")
-            self.ref_labels.append(labels)
-            rs = np.array([t[0] for t in f["turns"]], dtype=np.float64)
-            re = np.array([t[1] for t in f["turns"]], dtype=np.float64)
-            bounds = np.unique(np.concatenate([self.mids[a:b], rs, re]))
-            self.mid_cell[a:b] = np.searchsorted(bounds, self.mids[a:b])
-            mask = np.zeros(bounds.shape[0] - 1, dtype=np.uint64)
-            for (s_, e_, l) in f["turns"]:
-                i0, i1 = np.searchsorted(bounds, s_), np.searchsorted(bounds, e_)
-                mask[i0:i1] |= np.uint64(1) << np.uint64(labels.index(l))
-            durs.append(np.diff(bounds))
-            refs.append(mask)
-            cell_off.append(cell_off[-1] + mask.shape[0])
-        self.cell_dur = np.ascontiguousarray(np.concatenate(durs), dtype=np.float64)
-        self.cell_ref = np.ascontiguousarray(np.concatenate(refs), dtype=np.uint64)
-        self.file_cell_off = np.array(cell_off, dtype=np.int32)
 
     def _desc(self, ptr) -> _lib.TuneDesc:
         d = _lib.TuneDesc()
@@ -268,10 +347,6 @@ class TuneCache:
         if hp.ndim != 2 or hp.shape[1] != 3 or hp.shape[0] < 1:
             raise ValueError(f"hparams (T, 3) = (tau_active, rho_update, delta_new) per trial expected, got {hp.shape}")
         return hp
-
-    @staticmethod
-    def default_backend() -> str:
-        return "gpu" if torch.cuda.is_available() else "host"
 
     def replay(self, hparams, backend: Optional[str] = None, num_threads: int = 8):
         """``(assign (T, chunks, K) int8, status (T, N) int32, bits (T, rows) uint32)`` of T trials: the global speaker
@@ -329,15 +404,7 @@ class TuneCache:
 
     def score(self, bits: np.ndarray, num_threads: int = 8) -> np.ndarray:
         """``(T, N, 5)`` error-rate components (``metrics.COMPONENTS``) of the masks of ``replay``."""
-        bits = np.ascontiguousarray(bits, dtype=np.uint32)
-        T = bits.shape[0]
-        out = np.zeros((T, self.N, 5), dtype=np.float64)
-        _lib.check(_lib.load().dz_tune_score(T, self.N, bits.ctypes.data, self.total_rows, self.file_row_off.ctypes.data,
-                                             self.chunk_off.ctypes.data, self.step_rows.ctypes.data, self.mids.ctypes.data,
-                                             self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
-                                             self.cell_dur.ctypes.data, self.cell_ref.ctypes.data, self.G, PATCH_COLLAR,
-                                             out.ctypes.data, int(num_threads)), "dz_tune_score")
-        return out
+        return self._score_bits(bits, self.G, num_threads)
 
     def evaluate(self, hparams, backend: Optional[str] = None, memory_budget: int = 1 << 30,
                  num_threads: int = 8) -> TuneResult:
@@ -353,34 +420,259 @@ class TuneCache:
             status.append(st)
         per_file, status = np.concatenate(per_file), np.concatenate(status)
         comp = per_file.sum(axis=1)
-        err = comp[:, 2] + comp[:, 3] + comp[:, 4]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            rate = np.where(comp[:, 0] > 0, err / comp[:, 0], np.where(err == 0, 0.0, 1.0))
-        rate = np.where((status >= 0).any(axis=1), np.nan, rate)
+        rate = np.where((status >= 0).any(axis=1), np.nan, _rates(comp))
         return TuneResult(rate, comp, per_file, status)
 
     def hypothesis(self, bits_row: np.ndarray, n: int) -> Annotation:
         """File n's hypothesis under one trial as the ``Annotation`` ``PredictionAccumulator`` ends with (tests and
         RTTM output): the speech turns of the masks, same-speaker turns closer than the patch collar merged."""
-        ann = Annotation(uri=self.files[n]["uri"], modality="speech")
-        p, m = int(self.file_row_off[n]), int(self.file_row_off[n] + self.chunk_off[n])
-        for c in range(int(self.chunk_off[n]), int(self.chunk_off[n + 1])):
-            rows = int(self.step_rows[c])
-            b = bits_row[p:p + rows]
-            for g in range(self.G):
-                on = np.concatenate([[False], (b >> np.uint32(g)) & np.uint32(1) > 0, [False]])
-                edges = np.flatnonzero(on[1:] != on[:-1])
-                for s, e in zip(edges[::2], edges[1::2]):
-                    ann[Segment(self.mids[m + s], self.mids[m + e]), g] = f"speaker{g}"
-            p, m = p + rows, m + rows + 1
-        return ann.support(PATCH_COLLAR)
+        return self._hypothesis(bits_row, n, self.G, lambda g: f"speaker{g}")
+
+
+class VadTuneCache(_ReplayCache):
+    """``TuneCache``'s sibling for ``VoiceActivityDetection``: per file the track ``(C, F)`` (the max of the segmentation
+    over the local speakers, what ``finalise`` aggregates), the window starts, the frame resolution, the shift and the
+    reference turns.  The reference is collapsed to speech / non-speech: a scoring cell's one reference bit is "any
+    reference speaker active".  The aggregated speech score of every packed output frame (``agg``) does not depend on
+    ``tau_active``; it is computed once per cache (and once per device), a trial compares it with its tau."""
+
+    SCORE_LANES = 256           # the lanes of tune_vad_score_kernel's workgroup (backend="core" plays them in order)
+
+    def __init__(self, files: Sequence[dict], config):
+        get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+        self.meta = {k: float(get(k)) for k in ("step", "latency", "tau_active")}
+        if not files:
+            raise ValueError("VadTuneCache needs at least one file")
+        self.files = []
+        for i, f in enumerate(files):
+            track = np.ascontiguousarray(f["track"], dtype=np.float32)
+            if track.ndim == 3 and track.shape[2] == 1:
+                track = np.ascontiguousarray(track[:, :, 0])
+            starts = np.ascontiguousarray(f["starts"], dtype=np.float64)
+            C_ = track.shape[0]
+            if track.ndim != 2 or starts.shape != (C_,) or C_ < 1 or track.shape[1] < 1:
+                raise ValueError(f"file {i}: track (C, F), starts (C) expected, got {track.shape}, {starts.shape}")
+            res = np.ascontiguousarray(np.broadcast_to(np.asarray(f["res"], dtype=np.float64), (C_,)))
+            self.files.append(dict(uri=str(f.get("uri", f"file{i}")), track=track, starts=starts, res=res,
+                                   shift=float(f.get("shift", 0.0)), turns=_reference_turns(f["reference"])))
+        frames = {f["track"].shape[1] for f in self.files}
+        if len(frames) != 1:
+            raise ValueError(f"the files of one cache share the frames per chunk, got {sorted(frames)}")
+        self.F, self.N = next(iter(frames)), len(self.files)
+        self._prepare()
+        self._dev = {}
+        self._agg = None
+
+    # ------------------------------------------------------------------------------------------ construction
+    @classmethod
+    def from_arrays(cls, files: Sequence[dict], config) -> "VadTuneCache":
+        """``files``: dicts with ``track (C, F)`` (or ``(C, F, 1)``), ``starts (C)``, ``res``, ``shift``, ``reference``
+        and optionally ``uri``, as ``TuneCache.from_arrays`` takes them.  ``config``: anything with ``step``,
+        ``latency`` and ``tau_active`` (attributes or keys)."""
+        return cls(files, config)
+
+    @classmethod
+    def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32) -> "VadTuneCache":
+        """Run the model half of ``VoiceActivityDetection`` (``model_outputs``) once per WAV of ``speech_path``."""
+        if _pipeline_kind(pipeline_class) != "vad":
+            raise ValueError(f"pipeline class {pipeline_class.__name__}: VadTuneCache collects VoiceActivityDetection; "
+                             "TuneCache collects SpeakerDiarization")
+        pipeline = pipeline_class(base_config)
+        files = cls._collect_files(pipeline, speech_path, reference_path, batch_size,
+                                   lambda batch: (pipeline.model_outputs(batch).detach().cpu().numpy()
+                                                  .astype(np.float32, copy=False),))
+        for f in files:
+            f["track"] = f.pop("outputs")[0]
+        return cls(files, pipeline.config)
+
+    def save(self, path) -> None:
+        out = {"kind": np.array("VadTuneCache"), "meta": np.array(json.dumps(self.meta)),
+               "uris": np.array([f["uri"] for f in self.files])}
+        for i, f in enumerate(self.files):
+            for k in ("track", "starts", "res"):
+                out[f"{k}_{i}"] = f[k]
+            out[f"shift_{i}"] = np.array(f["shift"])
+            out[f"ref_times_{i}"] = np.array([[s, e] for s, e, _ in f["turns"]], dtype=np.float64).reshape(-1, 2)
+            out[f"ref_labels_{i}"] = np.array([str(l) for _, _, l in f["turns"]], dtype=str)
+        with open(path, "wb") as fh:
+            np.savez(fh, **out)
+
+    @classmethod
+    def load(cls, path) -> "VadTuneCache":
+        with np.load(path, allow_pickle=False) as z:
+            if "kind" not in z.files or str(z["kind"]) != "VadTuneCache":
+                raise ValueError(f"{path} holds a TuneCache (SpeakerDiarization), not a VadTuneCache")
+            meta = json.loads(str(z["meta"]))
+            files = []
+            for i, uri in enumerate(z["uris"]):
+                ref = [(s, e, str(l)) for (s, e), l in zip(z[f"ref_times_{i}"], z[f"ref_labels_{i}"])]
+                files.append(dict(uri=str(uri), track=z[f"track_{i}"], starts=z[f"starts_{i}"], res=z[f"res_{i}"],
+                                  shift=float(z[f"shift_{i}"]), reference=ref))
+        return cls(files, meta)
+
+    # ------------------------------------------------------------------------------------------ trial-independent parts
+    def _reference_bits(self, f: dict) -> Dict[object, int]:
+        self.ref_labels.append(["speech"] if f["turns"] else [])
+        return {l: 0 for _, _, l in f["turns"]}
+
+    def _prepare(self) -> None:
+        self._prepare_plan()
+        self.seg = np.concatenate([f["track"] for f in self.files])                 # (chunks, F): one local speaker
+        # prefix sums of the cells' durations, and of the durations where the reference is active: cells + 1 per file
+        dur, ref = [], []
+        for n in range(self.N):
+            a, b = int(self.file_cell_off[n]), int(self.file_cell_off[n + 1])
+            d = self.cell_dur[a:b]
+            dur.append(np.concatenate([[0.0], np.cumsum(d)]))
+            ref.append(np.concatenate([[0.0], np.cumsum(np.where(self.cell_ref[a:b] != 0, d, 0.0))]))
+        self.dur_prefix = np.ascontiguousarray(np.concatenate(dur), dtype=np.float64)
+        self.ref_prefix = np.ascontiguousarray(np.concatenate(ref), dtype=np.float64)
+        # the scoring kernel takes the turns of a file in step order: that is their order by start time when every
+        # step's grid starts behind the last row of the step before it (any file the file loop produces)
+        first = (self.row_off[:-1] + np.arange(self.row_off.shape[0] - 1))[1:]
+        last = (self.row_off[1:] + np.arange(self.row_off.shape[0] - 1) - 1)[:-1]
+        inner = np.ones(first.shape[0], dtype=bool)
+        inner[self.chunk_off[1:-1] - 1] = False                                        # the first step of a file
+        self.sorted_steps = bool((self.mids[first] > self.mids[last])[inner].all())
+
+    def _desc(self, ptr) -> _lib.TuneDesc:
+        d = _lib.TuneDesc()
+        for name in ("seg", "chunk_off", "plan", "row_off", "row_chunk", "hamming"):
+            setattr(d, name, ptr(name))
+        d.N, d.F, d.K, d.D, d.G, d.nwin = self.N, self.F, 1, 1, 1, self.nwin
+        d.total_chunks, d.total_rows = int(self.chunk_off[-1]), self.total_rows
+        return d
+
+    @property
+    def bytes_per_trial(self) -> int:
+        """Host memory one trial's masks take (backend="host"); the GPU backend keeps 40 bytes per (trial, file)."""
+        return 4 * self.total_rows
+
+    # ------------------------------------------------------------------------------------------ replay
+    @staticmethod
+    def _taus(taus) -> np.ndarray:
+        t = np.asarray(taus, dtype=np.float64)
+        if t.ndim == 2 and t.shape[1] == 1:
+            t = t[:, 0]
+        if t.ndim != 1 or t.shape[0] < 1:
+            raise ValueError(f"taus (T,) or (T, 1) = tau_active per trial expected, got {np.shape(taus)}")
+        return np.ascontiguousarray(t)
+
+    def _check_sorted(self, backend: str) -> None:
+        if not self.sorted_steps:
+            raise ValueError(f"backend '{backend}' scores the turns of a file in step order, and the output grids of "
+                             "this cache's steps are not sorted by time; backend='host' sorts them")
+
+    def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int):
+        T = taus.shape[0]
+        agg = np.empty(self.total_rows, dtype=np.float64)
+        b = np.empty((T, self.total_rows), dtype=np.uint32) if bits else None
+        out = np.zeros((T, self.N, 5), dtype=np.float64) if components else None
+        d = self._desc(lambda name: getattr(self, name).ctypes.data)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _lib.check(_lib.load().dz_tune_vad_host(C.byref(d), taus.ctypes.data, T, agg.ctypes.data, ptr(b), self.mids.ctypes.data,
+                                                self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
+                                                self.dur_prefix.ctypes.data, self.ref_prefix.ctypes.data, PATCH_COLLAR,
+                                                self.SCORE_LANES, ptr(out), int(num_threads)), "dz_tune_vad_host")
+        return agg, b, out
+
+    def _device(self, device: torch.device):
+        """The cache's device tensors, ``agg`` among them: tune_vad_rows_kernel runs once per cache and device."""
+        key = str(device)
+        if key not in self._dev:
+            tensors = {name: torch.from_numpy(getattr(self, name)).to(device)
+                       for name in ("seg", "chunk_off", "plan", "row_off", "row_chunk", "hamming", "mids", "mid_cell",
+                                    "file_cell_off", "dur_prefix", "ref_prefix")}
+            tensors["agg"] = torch.empty(self.total_rows, dtype=torch.float64, device=device)
+            desc = self._desc(lambda name: tensors[name].data_ptr())
+            _lib.check(_lib.load().dz_tune_vad_rows(_lib.context(device.index), C.byref(desc), tensors["agg"].data_ptr(),
+                                                    torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_rows")
+            self._dev[key] = (tensors, desc)
+        return self._dev[key]
+
+    def _gpu(self, taus: np.ndarray, bits: bool, components: bool, device: Optional[torch.device] = None):
+        if not torch.cuda.is_available():
+            raise _lib.DiartAmdError("backend='gpu' needs a GPU; backend='host' replays on the host")
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        t, _ = self._device(device)
+        T = taus.shape[0]
+        d_taus = torch.from_numpy(taus).to(device)
+        b = torch.empty((T, self.total_rows), dtype=torch.int32, device=device) if bits else None
+        out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device) if components else None
+        ptr = lambda a: None if a is None else a.data_ptr()
+        _lib.check(_lib.load().dz_tune_vad_score(_lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(),
+                                                 d_taus.data_ptr(), t["chunk_off"].data_ptr(), t["row_off"].data_ptr(),
+                                                 t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
+                                                 t["file_cell_off"].data_ptr(), t["dur_prefix"].data_ptr(),
+                                                 t["ref_prefix"].data_ptr(), PATCH_COLLAR, ptr(out), ptr(b),
+                                                 torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_score")
+        return t["agg"], b, out
+
+    def replay(self, taus, backend: Optional[str] = None, num_threads: int = 8):
+        """``(agg (rows,) float64, bits (T, rows) uint32)``: the aggregated speech score of every packed output frame
+        and, per trial, whether it is above the trial's tau.  ``backend``: "gpu" | "host"."""
+        taus = self._taus(taus)
+        backend = backend or self.default_backend()
+        if backend == "gpu":
+            agg, bits, _ = self._gpu(taus, True, False)
+            torch.cuda.synchronize(agg.device)
+            return agg.cpu().numpy(), bits.cpu().numpy().view(np.uint32)
+        if backend != "host":
+            raise ValueError(f"backend '{backend}': gpu or host")
+        agg, bits, _ = self._host(taus, True, False, num_threads)
+        return agg, bits
+
+    def score(self, bits: np.ndarray, num_threads: int = 8) -> np.ndarray:
+        """``(T, N, 5)`` detection error rate components of the masks of ``replay``, by ``dz_tune_score`` with one
+        hypothesis speaker on the collapsed reference cells."""
+        return self._score_bits(bits, 1, num_threads)
+
+    def evaluate(self, taus, backend: Optional[str] = None, memory_budget: int = 1 << 30,
+                 num_threads: int = 8) -> TuneResult:
+        """The detection error rate of every trial of ``taus``.  ``backend``: "gpu" (the two kernels; only the
+        components come back), "host" (the same aggregation on host threads, then ``dz_tune_score``; trials in batches
+        whose masks fit ``memory_budget`` bytes) or "core" (the scoring kernel's text on host threads)."""
+        taus = self._taus(taus)
+        backend = backend or self.default_backend()
+        if backend == "gpu":
+            self._check_sorted(backend)
+            out = self._gpu(taus, False, True)[2]
+            per_file = out.cpu().numpy()
+        elif backend == "core":
+            self._check_sorted(backend)
+            per_file = self._host(taus, False, True, num_threads)[2]
+        elif backend == "host":
+            per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
+            per_file = np.concatenate([self.score(self._host(taus[a:a + per_batch], True, False, num_threads)[1], num_threads)
+                                       for a in range(0, taus.shape[0], per_batch)])
+        else:
+            raise ValueError(f"backend '{backend}': gpu, host or core")
+        comp = per_file.sum(axis=1)
+        return TuneResult(_rates(comp), comp, per_file, np.full((taus.shape[0], self.N), -1, dtype=np.int32))
+
+    def hypothesis(self, bits_row: np.ndarray, n: int) -> Annotation:
+        """File n's hypothesis under one trial as ``PredictionAccumulator`` ends with it: turns labelled "speech"."""
+        return self._hypothesis(bits_row, n, 1, lambda g: "speech")
+
+
+def _pipeline_kind(pipeline_class) -> str:
+    """"dia" for ``SpeakerDiarization``, "vad" for ``VoiceActivityDetection``; nothing else is tuned by replay (a
+    subclass may change what the cached outputs mean)."""
+    from .blocks.diarization import SpeakerDiarization
+    from .blocks.vad import VoiceActivityDetection
+    if pipeline_class is SpeakerDiarization:
+        return "dia"
+    if pipeline_class is VoiceActivityDetection:
+        return "vad"
+    name = getattr(pipeline_class, "__name__", repr(pipeline_class))
+    raise ValueError(f"pipeline class {name}: only SpeakerDiarization and VoiceActivityDetection are tuned by replaying "
+                     "cached model outputs")
 
 
 def _check_pipeline_class(pipeline_class) -> None:
-    from .blocks.diarization import SpeakerDiarization
-    if pipeline_class is not SpeakerDiarization:
-        name = getattr(pipeline_class, "__name__", repr(pipeline_class))
-        raise ValueError(f"pipeline class {name}: only SpeakerDiarization is tuned by replaying cached model outputs")
+    if _pipeline_kind(pipeline_class) != "dia":
+        raise ValueError(f"pipeline class {pipeline_class.__name__}: TuneCache replays SpeakerDiarization; "
+                         "VadTuneCache is the cache of VoiceActivityDetection")
 
 
 def trial_config(base_config, values: Dict[str, float]):
@@ -397,18 +689,27 @@ class Optimizer:
     is replaced by a directory: ``<path>/<stem>.json`` holds every trial and is loaded if it exists, a second call
     continues the numbering and never evaluates a stored trial again.  ``sampler``: "random" (uniform over each
     parameter's range, from ``seed``) or "grid" (``num_iter`` as a total: the largest cube not above it).  Trials are
-    evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run)."""
+    evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run).
+    ``pipeline_class``: ``SpeakerDiarization``, or ``VoiceActivityDetection`` — then ``tau_active`` alone is tuned, the
+    metric is the detection error rate and the cache a ``VadTuneCache``."""
 
     def __init__(self, pipeline_class: type, speech_path, reference_path, study_or_path, batch_size: int = 32,
                  hparams: Optional[Sequence[base.HyperParameter]] = None, base_config=None,
                  do_kickstart_hparams: bool = True, metric=None, direction: str = "minimize", sampler: str = "random",
-                 seed: int = 0, trials_per_batch: int = 256, cache: Optional[TuneCache] = None,
-                 backend: Optional[str] = None):
-        _check_pipeline_class(pipeline_class)
+                 seed: int = 0, trials_per_batch: int = 256, cache=None, backend: Optional[str] = None):
+        self.kind = _pipeline_kind(pipeline_class)
+        vad = self.kind == "vad"
+        self.cache_class = VadTuneCache if vad else TuneCache
+        self.tunable = VAD_TUNABLE if vad else TUNABLE
+        if cache is not None and not isinstance(cache, self.cache_class):
+            raise ValueError(f"pipeline class {pipeline_class.__name__}: cache must be a {self.cache_class.__name__}, "
+                             f"got a {type(cache).__name__}")
         self.pipeline_class = pipeline_class
         self.speech_path, self.reference_path, self.batch_size = speech_path, reference_path, batch_size
-        if metric is not None and not isinstance(metric, DiarizationErrorRate):
-            raise ValueError(f"metric {type(metric).__name__}: the replay scores the diarization error rate only")
+        wanted = DetectionErrorRate if vad else DiarizationErrorRate
+        if metric is not None and not isinstance(metric, wanted):
+            raise ValueError(f"metric {type(metric).__name__}: the replay of {pipeline_class.__name__} scores the "
+                             f"{wanted.name} ({wanted.__name__}) only")
         if direction not in ("minimize", "maximize"):
             raise ValueError(f"direction '{direction}': minimize or maximize")
         if sampler not in ("random", "grid"):
@@ -422,12 +723,12 @@ class Optimizer:
         self.hparams = list(pipeline_class.hyper_parameters() if hparams is None else hparams)
         possible = vars(self.base_config)
         for param in self.hparams:
-            if param.name not in TUNABLE:
-                raise ValueError(f"hyper-parameter {param.name} changes the model outputs: only {', '.join(TUNABLE)} "
-                                 "are tuned by replaying them")
+            if param.name not in self.tunable:
+                raise ValueError(f"hyper-parameter {param.name} changes the model outputs: only "
+                                 f"{', '.join(self.tunable)} are tuned by replaying them")
             assert param.name in possible, (f"Hyper-parameter {param.name} not found in configuration "
                                             f"{self.base_config.__class__.__name__}")
-        if int(self.base_config.max_speakers) > MAX_SPEAKERS:
+        if not vad and int(self.base_config.max_speakers) > MAX_SPEAKERS:
             raise ValueError(f"max_speakers = {self.base_config.max_speakers}: the replay keeps one 32-bit mask per "
                              f"frame, at most {MAX_SPEAKERS} speakers")
         if not isinstance(study_or_path, (str, Path)):
@@ -447,9 +748,9 @@ class Optimizer:
         self._cache = cache
 
     @property
-    def cache(self) -> TuneCache:
+    def cache(self):
         if self._cache is None:
-            self._cache = TuneCache.collect(self.pipeline_class, self.base_config, self.speech_path, self.reference_path,
+            self._cache = self.cache_class.collect(self.pipeline_class, self.base_config, self.speech_path, self.reference_path,
                                             self.batch_size)
         return self._cache
 
@@ -473,8 +774,9 @@ class Optimizer:
         return dict(self.best_trial["params"])
 
     def _values(self, params: Dict[str, float]) -> List[float]:
-        """(tau, rho, delta) of a trial: the sampled parameters, the base config's value for the others."""
-        return [float(params.get(name, getattr(self.base_config, name))) for name in TUNABLE]
+        """(tau, rho, delta) of a trial ((tau) of VoiceActivityDetection): the sampled parameters, the base config's
+        value for the others."""
+        return [float(params.get(name, getattr(self.base_config, name))) for name in self.tunable]
 
     def objective(self, params: Sequence[Dict[str, float]]) -> np.ndarray:
         """The metric in percent of every trial of ``params`` (NaN where the clustering would raise)."""

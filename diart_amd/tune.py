@@ -2,7 +2,9 @@
 WAV files against RTTM references (reference: ``/root/reference/src/diart/console/tune.py``).  The models run once
 over the dataset (``optim.TuneCache.collect``; ``--cache FILE`` saves that pass, or loads it when the file is there),
 then every trial is a replay of their outputs — on the GPU when there is one.  The study is a directory: ``--output
-DIR`` holds ``DIR/<stem>.json`` with every trial, and a second run continues it."""
+DIR`` holds ``DIR/<stem>.json`` with every trial, and a second run continues it.  ``--pipeline
+VoiceActivityDetection`` tunes tau_active of that pipeline against the detection error rate (``optim.VadTuneCache``;
+the embedding and the clustering arguments are ignored)."""
 from __future__ import annotations
 
 import argparse
@@ -11,7 +13,8 @@ from pathlib import Path
 from . import models as m
 from .blocks.base import HyperParameter
 from .blocks.diarization import SpeakerDiarization, SpeakerDiarizationConfig
-from .optim import Optimizer, TuneCache
+from .blocks.vad import VoiceActivityDetection, VoiceActivityDetectionConfig
+from .optim import Optimizer, TuneCache, VadTuneCache
 
 
 def parser() -> argparse.ArgumentParser:
@@ -19,6 +22,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("root", type=str, help="Directory with audio files CONVERSATION.wav")
     ap.add_argument("--reference", required=True, type=str,
                     help="Directory with RTTM files CONVERSATION.rttm. Names must match audio files")
+    ap.add_argument("--pipeline", default="SpeakerDiarization", choices=("SpeakerDiarization", "VoiceActivityDetection"),
+                    help="Pipeline to tune. Defaults to SpeakerDiarization")
     ap.add_argument("--segmentation", default="pyannote/segmentation", type=str, help="Segmentation checkpoint file")
     ap.add_argument("--embedding", default="pyannote/embedding", type=str, help="Embedding checkpoint file")
     ap.add_argument("--duration", type=float, default=5, help="Chunk duration in seconds. Defaults to 5")
@@ -34,8 +39,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--normalize-embedding-weights", action="store_true")
     ap.add_argument("--cpu", action="store_true",
                     help="Replay the trials on the host even if a GPU is there; the models keep their GPU device")
-    ap.add_argument("--hparams", nargs="+", default=("tau_active", "rho_update", "delta_new"),
-                    help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three)")
+    ap.add_argument("--hparams", nargs="+", default=None,
+                    help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three); "
+                         "tau_active alone with --pipeline VoiceActivityDetection")
     ap.add_argument("--num-iter", default=100, type=int, help="Number of optimization trials")
     ap.add_argument("--output", type=str, required=True, help="Study directory: holds <stem>.json with every trial")
     ap.add_argument("--sampler", default="random", choices=("random", "grid"),
@@ -47,23 +53,35 @@ def parser() -> argparse.ArgumentParser:
 
 
 def run(args: argparse.Namespace, models=None) -> Optimizer:
-    """``models``: (segmentation, embedding) to use in place of the checkpoints the arguments name."""
-    seg, emb = models if models is not None else (m.SegmentationModel.from_pretrained(args.segmentation),
-                                                  m.EmbeddingModel.from_pretrained(args.embedding))
-    base_config = SpeakerDiarizationConfig(
-        segmentation=seg, embedding=emb, duration=args.duration, step=args.step, latency=args.latency,
-        tau_active=args.tau_active, rho_update=args.rho_update, delta_new=args.delta_new, gamma=args.gamma,
-        beta=args.beta, max_speakers=args.max_speakers, normalize_embedding_weights=args.normalize_embedding_weights,
-        device=None)
-    possible = SpeakerDiarization.hyper_parameters()
-    hparams = [hp for hp in (HyperParameter.from_name(name) for name in args.hparams) if hp in possible]
+    """``models``: (segmentation, embedding) to use in place of the checkpoints the arguments name (the embedding is
+    not used, and may be None, with ``--pipeline VoiceActivityDetection``)."""
+    vad = args.pipeline == "VoiceActivityDetection"
+    if models is not None:
+        seg, emb = models
+    else:
+        seg = m.SegmentationModel.from_pretrained(args.segmentation)
+        emb = None if vad else m.EmbeddingModel.from_pretrained(args.embedding)
+    if vad:
+        pipeline_class, cache_class = VoiceActivityDetection, VadTuneCache
+        base_config = VoiceActivityDetectionConfig(segmentation=seg, duration=args.duration, step=args.step,
+                                                   latency=args.latency, tau_active=args.tau_active, device=None)
+    else:
+        pipeline_class, cache_class = SpeakerDiarization, TuneCache
+        base_config = SpeakerDiarizationConfig(
+            segmentation=seg, embedding=emb, duration=args.duration, step=args.step, latency=args.latency,
+            tau_active=args.tau_active, rho_update=args.rho_update, delta_new=args.delta_new, gamma=args.gamma,
+            beta=args.beta, max_speakers=args.max_speakers, normalize_embedding_weights=args.normalize_embedding_weights,
+            device=None)
+    possible = pipeline_class.hyper_parameters()
+    names = args.hparams or [hp.name for hp in possible]
+    hparams = [hp for hp in (HyperParameter.from_name(name) for name in names) if hp in possible]
     if not hparams:
         raise SystemExit("No hyper-parameters to optimize. Make sure to select one of: "
                          + ", ".join(hp.name for hp in possible))
     cache = None
     if args.cache and Path(args.cache).exists():
-        cache = TuneCache.load(args.cache)
-    opt = Optimizer(SpeakerDiarization, args.root, args.reference, Path(args.output).expanduser(),
+        cache = cache_class.load(args.cache)
+    opt = Optimizer(pipeline_class, args.root, args.reference, Path(args.output).expanduser(),
                     batch_size=args.batch_size, hparams=hparams, base_config=base_config, sampler=args.sampler,
                     seed=args.seed, trials_per_batch=args.trials_per_batch, cache=cache,
                     backend="host" if args.cpu else None)

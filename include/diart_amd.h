@@ -938,6 +938,32 @@ int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows,
                   const int* file_chunk_off, const int* step_rows, const double* mids, const int* mid_cell,
                   const int* file_cell_off, const double* cell_dur, const unsigned long long* cell_ref,
                   int max_speakers, double collar, double* out, int num_threads);
+/* Tuning VoiceActivityDetection (tau_active alone): one track per chunk, so dz_tune_desc has k_local = 1,
+ * seg (chunks, frames) = the max over the local speakers, and emb / pre_* unused (may be NULL).  The
+ * aggregated speech score of a packed output row does not depend on tau: dz_tune_vad_rows writes
+ * d_agg (total_rows) doubles once per cache (the value dz_tune_replay compares with tau when the one
+ * local speaker of every buffer is mapped).  Device memory throughout, enqueued on `stream`.            */
+int dz_tune_vad_rows(dz_ctx* ctx, const dz_tune_desc* d, double* d_agg, void* stream);
+/* T trials (d_taus (T)) x N files from d_agg: row r is speech when agg > tau; the turns, their merging and the
+ * scoring cells are dz_tune_score's for one hypothesis label against a reference collapsed to one label
+ * (detection error rate: the confusion is 0).  One workgroup per (trial, file); d_out (T, N, 5) is all that a
+ * trial leaves.  file_chunk_off, file_cell_off (N + 1), row_off (chunks + 1), mids / mid_cell as in
+ * dz_tune_score, sorted by time over the steps of a file; dur_prefix / ref_prefix (cells + N): per file its
+ * cells + 1 prefix sums of cell_dur and of cell_dur where the reference is active (file n starts at
+ * file_cell_off[n] + n).  d_bits (T, total_rows), if not NULL: agg > tau as 0 / 1 masks; d_out may be NULL
+ * then.                                                                                                   */
+int dz_tune_vad_score(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
+                      const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
+                      const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
+                      const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
+                      unsigned* d_bits, void* stream);
+/* The same from host memory, compiled from the text of the kernels: agg (total_rows); bits (T, total_rows)
+ * if not NULL; out (T, N, 5) if not NULL, the workgroup's `lanes` lanes played in order (the other
+ * arguments may be NULL where out is).                                                                    */
+int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+                     const double* mids, const int* mid_cell, const int* file_cell_off,
+                     const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
+                     int num_threads);
 
 /* sizeof() of the five structs that cross this boundary, in declaration order
  * (dz_sincnet_weights, dz_seg_weights, dz_emb_weights, dz_ecapa_weights, dz_convgemm_desc): a

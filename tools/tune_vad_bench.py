@@ -1,0 +1,118 @@
+"""What a VoiceActivityDetection tuning trial costs: `VadTuneCache.evaluate` on the GPU and on the host against
+`Benchmark` calls.
+
+Synthetic dataset (no checkpoint): `--files` files of `--seconds` seconds, the segmentation with synthetic weights, and
+as references the pipeline's own output at the base configuration.  Records the collect time once, the one-time rows
+kernel (device events), then for every T of `--trials` the wall time of `evaluate` on the GPU backend and on the host
+backend with `--threads` threads (warm runs first, medians of `--reps`), the score kernel alone (device events), and
+the wall time of a `Benchmark` call on the blocks path — what a trial costs without the cache — measured
+`--benchmark-calls` times and stated per trial (T such calls are T times that: extrapolated, not run).  One JSON line,
+`--out FILE`."""
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+
+from tune_bench import events_ms, median_ms  # noqa: E402
+
+from diart_amd import _lib  # noqa: E402
+from diart_amd import models as M  # noqa: E402
+from diart_amd.blocks.vad import VoiceActivityDetection, VoiceActivityDetectionConfig  # noqa: E402
+from diart_amd.inference import Benchmark, write_wav  # noqa: E402
+from diart_amd.optim import VadTuneCache  # noqa: E402
+from diart_amd.synth import synth_segmentation_state, synth_stream  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--files", type=int, default=16)
+    ap.add_argument("--seconds", type=float, default=600.0)
+    ap.add_argument("--trials", type=int, nargs="+", default=[1, 64, 1024])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--benchmark-calls", type=int, default=1)
+    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--latency", type=float, default=5.0)
+    ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "r20a_tune_vad.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tune_vad_bench.py measures on a GPU; there is none")
+    device = torch.device("cuda", 0)
+    out = dict(tool="tools/tune_vad_bench.py", files=args.files, seconds=args.seconds, latency=args.latency,
+               batch_size=args.batch_size, host_threads=args.threads, gpu=torch.cuda.get_device_name(0))
+    with tempfile.TemporaryDirectory() as tmp:
+        speech, refs = Path(tmp) / "wav", Path(tmp) / "rttm"
+        speech.mkdir()
+        for i in range(args.files):
+            write_wav(speech / f"f{i:02d}.wav", synth_stream(5000 + i, args.seconds, num_speakers=3 + i % 3), 16000)
+        config = VoiceActivityDetectionConfig(
+            segmentation=M.SegmentationModel.from_state(synth_segmentation_state(), max_batch=args.batch_size),
+            latency=args.latency, device=device)
+        # ---- a Benchmark call on the blocks path: what the reference's Optimizer pays per trial; the first call also
+        # writes the references (and warms the model up)
+        Benchmark(speech, None, refs, show_report=False, batch_size=args.batch_size, concurrent_files=0)(
+            VoiceActivityDetection, config)
+        scored = Benchmark(speech, refs, show_report=False, batch_size=args.batch_size, concurrent_files=0)
+        calls = []
+        for _ in range(args.benchmark_calls):
+            torch.cuda.synchronize(device)
+            t = time.perf_counter()
+            metric = scored(VoiceActivityDetection, config)
+            calls.append(time.perf_counter() - t)
+        out["benchmark_call_s"] = dict(median=statistics.median(calls), runs=calls, rate_percent=100.0 * abs(metric),
+                                       note="per trial: one call is one trial")
+        # ---- the model once
+        torch.cuda.synchronize(device)
+        t = time.perf_counter()
+        cache = VadTuneCache.collect(VoiceActivityDetection, config, speech, refs, batch_size=args.batch_size)
+        torch.cuda.synchronize(device)
+        out["collect_s"] = time.perf_counter() - t
+    out["cache"] = dict(chunks=int(cache.chunk_off[-1]), frames=cache.F, output_rows=cache.total_rows,
+                        cells=int(cache.file_cell_off[-1]), sorted_steps=cache.sorted_steps)
+    # ---- the rows kernel: once per cache and device (the upload of the cache's arrays is in the first figure only)
+    t = time.perf_counter()
+    tensors, desc = cache._device(device)
+    torch.cuda.synchronize(device)
+    out["upload_and_rows_ms"] = 1e3 * (time.perf_counter() - t)
+    lib, ctx = _lib.load(), _lib.context(device.index)
+    out["kernel_rows"] = events_ms(lambda: _lib.check(lib.dz_tune_vad_rows(
+        ctx, C.byref(desc), tensors["agg"].data_ptr(), torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_rows"),
+        device, args.reps)
+    rng = np.random.default_rng(0)
+    rows = []
+    for T in args.trials:
+        taus = np.concatenate([[0.6], rng.uniform(0, 1, size=T - 1)])
+        row = dict(trials=T)
+        gpu = cache.evaluate(taus, backend="gpu")
+        row["gpu_evaluate"] = median_ms(lambda: cache.evaluate(taus, backend="gpu"), args.reps)
+        row["kernel_score"] = events_ms(lambda: cache._gpu(taus, False, True, device), device, args.reps)
+        host = cache.evaluate(taus, backend="host", num_threads=args.threads)
+        row["host_evaluate"] = median_ms(lambda: cache.evaluate(taus, backend="host", num_threads=args.threads), args.reps,
+                                         warm=0)      # (the call above was the warm run)
+        total = np.maximum(host.per_file[..., :1], 1e-300)
+        row["largest_component_error_over_total"] = float((np.abs(gpu.per_file - host.per_file) / total).max())
+        row["best_rate_percent"] = float(100.0 * host.rate.min())
+        row["gpu_over_host"] = row["host_evaluate"]["median_ms"] / row["gpu_evaluate"]["median_ms"]
+        row["benchmark_calls_s_extrapolated"] = T * out["benchmark_call_s"]["median"]      # T x one call: not measured
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    out["rows"] = rows
+    line = json.dumps(out)
+    print(line, flush=True)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
