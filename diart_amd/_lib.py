@@ -236,6 +236,10 @@ SIGNATURES = {
                                       C.c_int, C.c_int]),
     "dz_tune_score": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp,
                                 C.c_int]),
+    "dz_tune_score_gpu": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int,
+                                    C.c_double, vp, vp, C.c_int, vp, vp]),
+    "dz_tune_score_core": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double,
+                                     C.c_int, C.c_int, vp, C.c_int]),
     "dz_tune_vad_rows": (C.c_int, [vp, C.POINTER(TuneDesc), vp, vp]),
     "dz_tune_vad_score": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp,
                                     vp]),

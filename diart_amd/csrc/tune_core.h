@@ -4,8 +4,9 @@
 // G <= TC_GMAX, the whole state in LDS); what this file adds is how the lanes of a wavefront share the arithmetic that
 // feeds them (each norm and each of the K x G distances summed by ONE lane in the core's order).  Host and device
 // compile this text: k_tune.hip for the kernels, tune_score.cpp for backend="core", which tests/test_tune_host.py
-// holds against dz_clu_step + dz_tail_step.  The VoiceActivityDetection half (tc_vad_*, at the end) is k_tune_vad.hip's
-// and dz_tune_vad_host's in the same way.
+// holds against dz_clu_step + dz_tail_step.  The VoiceActivityDetection half (tc_vad_*, behind the replay) is
+// k_tune_vad.hip's and dz_tune_vad_host's in the same way, and the scoring of the diarization masks (tc_score_*, at the
+// end) is k_tune_score.hip's and dz_tune_score_core's.
 #pragma once
 #include "../../include/diart_amd.h"
 #include "clu_core.h"
@@ -169,24 +170,23 @@ struct TcVadEnd {
     int cell;
 };
 
-// Steps [c_lo, c_hi) of one file under one tau, in order.  Row r of a step is speech when agg > tau; a turn runs
+// Steps [c_lo, c_hi) of one file, in order.  Row p of the packed rows is active when on(p); a turn runs
 // from mid[onset] to mid[first inactive row] (the row after the step's last closes an open turn; mids holds rows + 1
 // values per step), turns no longer than 1e-6 are dropped (Segment.__bool__).  Turns arrive sorted by start (the
 // cache checks that the steps' grids are), so Annotation.support(collar) is a running maximum: a turn whose gap to
 // `end` is <= 1e-6 or < collar extends the covered span from `end` to its own end (if that is later), any other
 // turn opens a new span.  Every turn therefore adds the cells [from, its end cell) with from = the cell of `end`
-// or its own start cell: nothing is covered twice.  Durations are differences of the file's prefix sums
-// (dur_prefix / ref_prefix: ncell + 1 values, cell_dur and cell_dur where the reference is active, summed in order).
-TC_HD TcVadEnd tc_vad_walk(const double* agg, const int* row_off, const double* mids, const int* mid_cell,
-                           const double* dur_prefix, const double* ref_prefix, double tau, double collar, int c_lo,
-                           int c_hi, TcVadEnd end, TcVadSum* sum) {
+// or its own start cell, handed to add(from, to): nothing is covered twice.
+template <typename On, typename Add>
+TC_HD TcVadEnd tc_turn_walk(On on_row, Add add, const int* row_off, const double* mids, const int* mid_cell, double collar,
+                            int c_lo, int c_hi, TcVadEnd end) {
     for (int c = c_lo; c < c_hi; ++c) {
         const int p = row_off[c], rows = row_off[c + 1] - p;
         const double* mid = mids + (long)p + c;
         const int* cell = mid_cell + (long)p + c;
         int onset = -1;
         for (int r = 0; r <= rows; ++r) {
-            const bool on = r < rows && agg[p + r] > tau;
+            const bool on = r < rows && on_row(p + r);
             if (on && onset < 0) onset = r;
             if (!on && onset >= 0) {
                 const double s = mid[onset], e = mid[r];
@@ -200,8 +200,7 @@ TC_HD TcVadEnd tc_vad_walk(const double* agg, const int* row_off, const double* 
                     }
                     if (adds) {
                         const int to = cell[r];
-                        sum->hyp += dur_prefix[to] - dur_prefix[from];
-                        sum->both += ref_prefix[to] - ref_prefix[from];
+                        add(from, to);
                         end.e = e;
                         end.cell = to;
                     }
@@ -211,6 +210,29 @@ TC_HD TcVadEnd tc_vad_walk(const double* agg, const int* row_off, const double* 
         }
     }
     return end;
+}
+
+// VoiceActivityDetection's walk under one tau: row r is speech when agg > tau, and the durations a turn adds are
+// differences of the file's prefix sums (dur_prefix / ref_prefix: ncell + 1 values, cell_dur and cell_dur where the
+// reference is active, summed in order).
+struct TcVadOn {
+    const double* agg;
+    double tau;
+    TC_HD bool operator()(int p) const { return agg[p] > tau; }
+};
+struct TcVadAdd {
+    const double *dur_prefix, *ref_prefix;
+    TcVadSum* sum;
+    TC_HD void operator()(int from, int to) const {
+        sum->hyp += dur_prefix[to] - dur_prefix[from];
+        sum->both += ref_prefix[to] - ref_prefix[from];
+    }
+};
+TC_HD TcVadEnd tc_vad_walk(const double* agg, const int* row_off, const double* mids, const int* mid_cell,
+                           const double* dur_prefix, const double* ref_prefix, double tau, double collar, int c_lo,
+                           int c_hi, TcVadEnd end, TcVadSum* sum) {
+    return tc_turn_walk(TcVadOn{agg, tau}, TcVadAdd{dur_prefix, ref_prefix, sum}, row_off, mids, mid_cell, collar, c_lo, c_hi,
+                        end);
 }
 
 // The five components (metrics.COMPONENTS) of DetectionErrorRate as dz_tune_score builds them for one hypothesis
@@ -226,3 +248,304 @@ TC_HD void tc_vad_components(double total, TcVadSum s, double* o) {
 
 // How a workgroup of nl lanes shares a file of `chunks` steps: lane i walks steps [i * per, (i + 1) * per).
 TC_HD int tc_vad_steps_per_lane(int chunks, int nl) { return (chunks + nl - 1) / nl; }
+
+// ---------------------------------------------------------------------------------------------------------
+// SpeakerDiarization: the diarization error rate components of one (trial, file) from the trial's packed masks
+// (bit g of a row = global speaker g is active), as dz_tune_score forms them, by the `nl` lanes of one workgroup.
+//
+// Turns and their merging are tc_turn_walk's, per label: lane i walks steps [i * per, (i + 1) * per) twice, as
+// tune_vad_score_kernel does (alone for the end of its latest-ending turn, then from the running maximum of the
+// lanes before it).  The covered ranges of one label are disjoint, so a range [from, to) is recorded by toggling
+// bit g of words `from` and `to` of the pair's scratch slice (ncell + 1 words, integer atomic XOR); a prefix XOR
+// over the words then IS the hypothesis mask of every scoring cell.  Every sum over the cells is formed per lane
+// (lane l takes cells l, l + nl, ...) and the lanes' sums are added in lane order by one lane: the same doubles on
+// every run, and no floating-point atomic anywhere.  The co-occurrence matrix is formed TC_SCORE_SWEEP entries at
+// a time (that many accumulators per lane, statically indexed); lane 0 solves the mapping (tc_lsap on -cooc).
+// What differs from dz_tune_score is the order of these sums, nothing else.
+//
+// The text is written as phases over the lanes: lanes(f) runs f(lane) for every lane and ends with the workgroup's
+// barrier (k_tune_score.hip), or plays the lanes one after the other (dz_tune_score_core).  Nothing in
+// TcScoreShared or in the scratch slice is read before this pair has written it: LDS holds whatever was there, and
+// the slice holds the hypothesis of the pair this workgroup took before.
+// ---------------------------------------------------------------------------------------------------------
+struct CluMapping {   // the store of the mapping problem: up to TC_GMAX hypothesis x 64 reference labels
+    template <typename T> using PerK = T[TC_GMAX];
+    template <typename T> using PerG = T[64];
+    template <typename T> using PerKG = T[TC_GMAX * 64];
+    using Active = CluMask32;
+    using Index = int;
+    static constexpr int err(int) { return 3; }
+};
+
+constexpr int TC_SCORE_LANES = 256;   // the workgroup of tune_score_kernel; dz_tune_score_core plays at most as many
+constexpr int TC_SCORE_SWEEP = 8;     // co-occurrence entries per pass over the cells
+// dz_tune_score's return codes
+constexpr int TC_SCORE_ERR_ARGS = 2;    // a file with more cells than a scratch slice holds
+constexpr int TC_SCORE_ERR_MAP = 3;     // the mapping's assignment problem failed
+constexpr int TC_SCORE_ERR_CELLS = 4;   // a speech turn does not start and end on the file's scoring cells
+
+// The words of a scratch slice are toggled with device-scope atomics, which act in L2: every other access to them
+// goes there too (relaxed, device scope), so that no lane reads a line its CU cached before the toggles.
+TC_HD unsigned tc_word_load(const unsigned* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_load(const_cast<unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    return *p;
+#endif
+}
+TC_HD void tc_word_store(unsigned* p, unsigned v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    *p = v;
+#endif
+}
+TC_HD void tc_word_xor(unsigned* p, unsigned v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_fetch_xor(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    *p ^= v;
+#endif
+}
+TC_HD void tc_err_raise(int* err, int code) {   // the call's error word: the largest code any pair met
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_fetch_max(err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    if (*err < code) *err = code;
+#endif
+}
+
+struct TcScoreIn {
+    const unsigned* bits;                 // this trial's masks (total_rows)
+    const int* row_off;                   // (chunks + 1) the packed rows of every step
+    const double* mids;                   // rows + 1 frame middles per step
+    const int* mid_cell;                  // the file's cell that starts at each of them
+    const double* cell_dur;               // the file's cells: duration
+    const unsigned long long* cell_ref;   //                   reference speakers
+    int c0, c1, ncell, G;
+    double collar;
+};
+
+struct TcScoreShared {
+    double cost[TC_GMAX * 64];            // -cooc of (hypothesis label a, reference label b) at a * nr + b
+    TcLsapWork<CluMapping> work;
+    double part[TC_SCORE_SWEEP][TC_SCORE_LANES];   // the lanes' partial sums
+    double end_e[TC_SCORE_LANES];
+    unsigned long long lane_ref[TC_SCORE_LANES];
+    int end_cell[TC_SCORE_LANES];
+    unsigned lane_any[TC_SCORE_LANES];    // the labels in a lane's steps
+    unsigned lane_x[TC_SCORE_LANES];      // the XOR of a lane's block of words; then the labels in a lane's cells
+    double sums[4];                       // total, missed, false alarm, sum dur x min(Nref, Nhyp)
+    int hl[TC_GMAX], rl[64], raw[64], col[TC_GMAX];
+    int nh, nr, err;
+};
+
+struct TcBitOn {
+    const unsigned* bits;
+    int g;
+    TC_HD bool operator()(int p) const { return (bits[p] >> g) & 1u; }
+};
+struct TcNoAdd {
+    TC_HD void operator()(int, int) const {}
+};
+struct TcToggle {
+    unsigned* scratch;
+    unsigned bit;
+    int ncell;
+    int* err;
+    TC_HD void operator()(int from, int to) const {
+        if (from < 0 || to > ncell || from > to) {   // dz_tune_score's rc 4, before any word is touched
+            *err = TC_SCORE_ERR_CELLS;
+            return;
+        }
+        tc_word_xor(scratch + from, bit);
+        tc_word_xor(scratch + to, bit);
+    }
+};
+
+// str(a) < str(b) for label numbers below 100: "10" < "2" (metrics.optimal_mapping sorts the labels as strings)
+TC_HD bool tc_str_less(int a, int b) {
+    const int a0 = a >= 10 ? a / 10 : a, b0 = b >= 10 ? b / 10 : b;
+    if (a0 != b0) return a0 < b0;
+    const int a1 = a >= 10 ? a % 10 : -1, b1 = b >= 10 ? b % 10 : -1;   // -1: the string ends here
+    return a1 < b1;
+}
+
+template <typename Lanes>
+TC_HD void tc_score_pair(const TcScoreIn& in, TcScoreShared& sh, unsigned* scratch, double* out /* 5 */, int* err,
+                         Lanes lanes) {
+    const int nl = lanes.nl, ncell = in.ncell, chunks = in.c1 - in.c0;
+    const int per = tc_vad_steps_per_lane(chunks, nl);
+    const unsigned gmask = in.G >= 32 ? 0xffffffffu : ((1u << in.G) - 1u);   // dz_tune_score ignores bits >= G
+    const TcVadEnd none = {-INFINITY, 0};
+    auto lo_of = [&](int lane) { return in.c0 + ((long long)lane * per < chunks ? lane * per : chunks); };
+    auto hi_of = [&](int lane) {
+        const int lo = lo_of(lane);
+        return lo + per < in.c1 ? lo + per : in.c1;
+    };
+    // ---- the slice starts from zeros; the labels of every lane's steps
+    lanes([&](int lane) {
+        for (int i = lane; i <= ncell; i += nl) tc_word_store(scratch + i, 0u);
+        unsigned any = 0;
+        for (int p = in.row_off[lo_of(lane)], p1 = in.row_off[hi_of(lane)]; p < p1; ++p) any |= in.bits[p];
+        sh.lane_any[lane] = any & gmask;
+        if (lane == 0) sh.err = 0;
+    });
+    unsigned any = 0;
+    for (int j = 0; j < nl; ++j) any |= sh.lane_any[j];
+    // ---- per label: the merged turns toggle the words at which they start and end
+    for (unsigned m = any; m; m &= m - 1) {
+        const int g = __builtin_ctz(m);
+        lanes([&](int lane) {
+            TcVadEnd own = none;
+            if ((sh.lane_any[lane] >> g) & 1u)
+                own = tc_turn_walk(TcBitOn{in.bits, g}, TcNoAdd{}, in.row_off, in.mids, in.mid_cell, in.collar, lo_of(lane),
+                                   hi_of(lane), none);
+            sh.end_e[lane] = own.e;
+            sh.end_cell[lane] = own.cell;
+        });
+        lanes([&](int lane) {
+            if (!((sh.lane_any[lane] >> g) & 1u)) return;   // no turn of g in this lane's steps: nothing to add
+            TcVadEnd before = none;
+            for (int j = 0; j < lane; ++j)
+                if (sh.end_e[j] > before.e) {
+                    before.e = sh.end_e[j];
+                    before.cell = sh.end_cell[j];
+                }
+            tc_turn_walk(TcBitOn{in.bits, g}, TcToggle{scratch, 1u << g, ncell, &sh.err}, in.row_off, in.mids, in.mid_cell,
+                         in.collar, lo_of(lane), hi_of(lane), before);
+        });
+    }
+    // ---- prefix XOR: word i becomes the hypothesis mask of cell i (lane l scans the block [l * blk, (l + 1) * blk))
+    const int blk = (ncell + nl - 1) / nl;
+    auto b0_of = [&](int lane) { return (long long)lane * blk < ncell ? lane * blk : ncell; };
+    auto b1_of = [&](int lane) {
+        const int b0 = b0_of(lane);
+        return b0 + blk < ncell ? b0 + blk : ncell;
+    };
+    lanes([&](int lane) {
+        unsigned x = 0;
+        for (int i = b0_of(lane), b1 = b1_of(lane); i < b1; ++i) x ^= tc_word_load(scratch + i);
+        sh.lane_x[lane] = x;
+    });
+    lanes([&](int lane) {
+        unsigned carry = 0;
+        for (int j = 0; j < lane; ++j) carry ^= sh.lane_x[j];
+        for (int i = b0_of(lane), b1 = b1_of(lane); i < b1; ++i) {
+            carry ^= tc_word_load(scratch + i);
+            tc_word_store(scratch + i, carry);
+        }
+    });
+    // ---- the components over the cells, per lane
+    lanes([&](int lane) {
+        double total = 0.0, missed = 0.0, fa = 0.0, both = 0.0;
+        unsigned hseen = 0;
+        unsigned long long rseen = 0;
+        for (int i = lane; i < ncell; i += nl) {
+            const unsigned h = tc_word_load(scratch + i);
+            const unsigned long long rm = in.cell_ref[i];
+            if (!h && !rm) continue;
+            const double dur = in.cell_dur[i];
+            const int nref = __builtin_popcountll(rm), nhyp = __builtin_popcount(h);
+            total += dur * nref;
+            missed += dur * (nref > nhyp ? nref - nhyp : 0);
+            fa += dur * (nhyp > nref ? nhyp - nref : 0);
+            both += dur * (nref < nhyp ? nref : nhyp);
+            hseen |= h;
+            rseen |= rm;
+        }
+        sh.part[0][lane] = total;
+        sh.part[1][lane] = missed;
+        sh.part[2][lane] = fa;
+        sh.part[3][lane] = both;
+        sh.lane_x[lane] = hseen;
+        sh.lane_ref[lane] = rseen;
+    });
+    // ---- lane 0: the lanes' sums in lane order; the labels (hypothesis in str order, reference in bit order)
+    lanes([&](int lane) {
+        if (lane != 0) return;
+        unsigned hseen = 0;
+        unsigned long long rseen = 0;
+        for (int q = 0; q < 4; ++q) {
+            double s = 0.0;
+            for (int j = 0; j < nl; ++j) s += sh.part[q][j];
+            sh.sums[q] = s;
+        }
+        for (int j = 0; j < nl; ++j) {
+            hseen |= sh.lane_x[j];
+            rseen |= sh.lane_ref[j];
+        }
+        int nh = 0, nr = 0;
+        for (int g = 0; g < in.G; ++g)
+            if ((hseen >> g) & 1u) {
+                int p = nh++;
+                while (p > 0 && tc_str_less(g, sh.hl[p - 1])) {
+                    sh.hl[p] = sh.hl[p - 1];
+                    --p;
+                }
+                sh.hl[p] = g;
+            }
+        for (int r = 0; r < 64; ++r)
+            if ((rseen >> r) & 1ull) sh.rl[nr++] = r;
+        sh.nh = nh;
+        sh.nr = nr;
+    });
+    // ---- cooc[a][b] = the duration in which hypothesis label hl[a] and reference label rl[b] are both active
+    const int nh = sh.nh, nr = sh.nr, nent = nh * nr;
+    for (int e0 = 0; e0 < nent; e0 += TC_SCORE_SWEEP) {
+        lanes([&](int lane) {
+            unsigned hm[TC_SCORE_SWEEP];
+            unsigned long long rk[TC_SCORE_SWEEP];
+            double acc[TC_SCORE_SWEEP];
+#pragma unroll
+            for (int j = 0; j < TC_SCORE_SWEEP; ++j) {
+                const int e = e0 + j < nent ? e0 + j : 0;
+                hm[j] = e0 + j < nent ? 1u << sh.hl[e / nr] : 0u;
+                rk[j] = e0 + j < nent ? 1ull << sh.rl[e - (e / nr) * nr] : 0ull;
+                acc[j] = 0.0;
+            }
+            for (int i = lane; i < ncell; i += nl) {
+                const unsigned h = tc_word_load(scratch + i);
+                const unsigned long long rm = in.cell_ref[i];
+                if (!h || !rm) continue;
+                const double dur = in.cell_dur[i];
+#pragma unroll
+                for (int j = 0; j < TC_SCORE_SWEEP; ++j) acc[j] += ((h & hm[j]) && (rm & rk[j])) ? dur : 0.0;   // (x + 0.0 is x)
+            }
+#pragma unroll
+            for (int j = 0; j < TC_SCORE_SWEEP; ++j) sh.part[j][lane] = acc[j];
+        });
+        lanes([&](int lane) {
+            if (lane >= TC_SCORE_SWEEP || e0 + lane >= nent) return;
+            double s = 0.0;
+            for (int j = 0; j < nl; ++j) s += sh.part[lane][j];
+            sh.cost[e0 + lane] = -s;
+        });
+    }
+    // ---- lane 0: metrics.optimal_mapping (LSAP on -cooc, pairs with cooc > 0 kept), the five components
+    lanes([&](int lane) {
+        if (lane != 0) return;
+        double correct = 0.0;
+        if (nh > 0 && nr > 0) {
+            int nraw = 0;
+            if (tc_lsap(sh.cost, nh, nr, sh.raw, &nraw, sh.work)) {
+                sh.err = TC_SCORE_ERR_MAP;
+            } else {
+                // raw holds the columns of the pairs sorted by row: every row has one, or (nr < nh) their rows are work.pr
+                for (int a = 0; a < nh; ++a) sh.col[a] = -1;
+                for (int i = 0; i < nraw; ++i) sh.col[nr < nh ? sh.work.pr[i] : i] = sh.raw[i];
+                for (int a = 0; a < nh; ++a)
+                    if (sh.col[a] >= 0 && -sh.cost[a * nr + sh.col[a]] > 0.0) correct += -sh.cost[a * nr + sh.col[a]];
+            }
+        }
+        if (sh.err) {
+            tc_err_raise(err, sh.err);
+            return;
+        }
+        out[0] = sh.sums[0];   // metrics.COMPONENTS order
+        out[1] = correct;
+        out[2] = sh.sums[2];
+        out[3] = sh.sums[1];
+        out[4] = sh.sums[3] - correct;
+    });
+}

@@ -9,6 +9,8 @@
 //   dz_tune_score        diarization error rate components of every pair from the packed frame masks
 //                        (diart_amd/metrics.py DiarizationErrorRate, collar 0, overlap included; PredictionAccumulator's
 //                        gap merging), without building an Annotation
+//   dz_tune_score_core   the same components from the text tune_score_kernel compiles (k_tune_score.hip), the lanes of its
+//                        workgroup played one after the other: scoring="device" on backend="core"
 //   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
 //                        scoring of k_tune_vad.hip, from the text those kernels compile
 #include "tune_core.h"
@@ -36,6 +38,14 @@ inline void crop_loose(double fs, double fe, double start, double res, long* fir
 
 struct NoBarrier {
     void operator()() const {}
+};
+
+struct LanesInTurn {   // the lanes of a workgroup, one after the other: a phase ends when the last lane has run it
+    int nl;
+    template <typename F>
+    void operator()(F f) const {
+        for (int lane = 0; lane < nl; ++lane) f(lane);
+    }
 };
 
 struct Turn {
@@ -348,6 +358,57 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
                                      : "dz_tune_score: the mapping's assignment problem failed");
             return rcs[w];
         }
+    return 0;
+}
+
+// dz_tune_score's components from the text of tune_score_kernel (tune_core.h: tc_score_pair), on host memory.  As on
+// the device, "workgroup" b of score_blocks takes pairs b, b + score_blocks, ... on one scratch slice of max_cells + 1
+// words, which every pair finds as the pair before left it; the shared state starts from a pattern, as LDS starts
+// from whatever was there.
+extern "C" int dz_tune_score_core(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
+                                  const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
+                                  const double* cell_dur, const unsigned long long* cell_ref, int max_cells, int max_speakers,
+                                  double collar, int lanes, int score_blocks, double* out, int num_threads) {
+    if (trials < 1 || n_files < 1 || !bits || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off ||
+        !cell_dur || !cell_ref || !out || max_speakers < 1 || max_speakers > TC_GMAX || max_cells < 0 || lanes < 1 ||
+        lanes > TC_SCORE_LANES || score_blocks < 1) {
+        dz_set_error("dz_tune_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
+        return 2;
+    }
+    const long long pairs = (long long)trials * n_files;
+    const int blocks = (int)(pairs < score_blocks ? pairs : score_blocks);
+    int nt = num_threads < 1 ? 1 : num_threads;
+    if (nt > blocks) nt = blocks;
+    std::vector<int> errs(blocks, 0);
+    auto run = [&](int, int b) {
+        std::vector<unsigned> slice((size_t)max_cells + 1, 0xa5a5a5a5u);
+        std::vector<TcScoreShared> sh(1);
+        for (long long pair = b; pair < pairs; pair += blocks) {
+            const int t = (int)(pair / n_files), n = (int)(pair - (long long)t * n_files);
+            const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
+            if (ncell < 0 || ncell > max_cells) {
+                tc_err_raise(&errs[b], TC_SCORE_ERR_ARGS);
+                continue;
+            }
+            std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(TcScoreShared));
+            const TcScoreIn in = {bits + (size_t)t * total_rows, row_off, mids, mid_cell, cell_dur + cell0, cell_ref + cell0,
+                                  file_chunk_off[n], file_chunk_off[n + 1], ncell, max_speakers, collar};
+            tc_score_pair(in, sh[0], slice.data(), out + (size_t)pair * 5, &errs[b], LanesInTurn{lanes});
+        }
+    };
+    if (nt == 1)
+        for (int b = 0; b < blocks; ++b) run(0, b);
+    else
+        dz_host_parallel(blocks, nt, run);
+    int rc = 0;
+    for (int b = 0; b < blocks; ++b)
+        if (errs[b] > rc) rc = errs[b];
+    if (rc) {
+        dz_set_error(rc == TC_SCORE_ERR_CELLS ? "dz_tune_score: a speech turn does not start and end on the file's scoring cells"
+                     : rc == TC_SCORE_ERR_MAP ? "dz_tune_score: the mapping's assignment problem failed"
+                                              : "dz_tune_score_core: a file has more scoring cells than a scratch slice holds");
+        return rc;
+    }
     return 0;
 }
 

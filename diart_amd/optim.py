@@ -12,7 +12,9 @@ binarisation -> diarization error rate.  The ``T x N`` chains of T trials over N
 * ``backend="host"``: the existing C ABI (``dz_clu_step`` / ``dz_tail_step``), chains on host threads — the same masks,
   bit for bit (``tests/test_gpu_tune.py``); what a machine without a GPU runs.
 
-Either way ``dz_tune_score`` turns the masks into the error-rate components on host threads.  DESIGN.md 4.16.
+Either way ``dz_tune_score`` turns the masks into the error-rate components on host threads; with
+``scoring="device"`` the GPU backend scores them where they are (``csrc/k_tune_score.hip``) and a batch of trials returns
+``T x N x 5`` doubles and the statuses.  DESIGN.md 4.16.
 
 ``VoiceActivityDetection`` has ``tau_active`` alone and no clustering: ``VadTuneCache`` keeps one track per chunk (the
 max over the local speakers), its aggregated speech score per output frame is computed once per cache, and a trial is
@@ -174,6 +176,19 @@ class _ReplayCache:
         self.cell_dur = np.ascontiguousarray(np.concatenate(durs), dtype=np.float64)
         self.cell_ref = np.ascontiguousarray(np.concatenate(refs), dtype=np.uint64)
         self.file_cell_off = np.array(cell_off, dtype=np.int32)
+        self.max_cells = int(np.diff(self.file_cell_off).max())
+        # the scoring kernels take the turns of a file in step order: that is their order by start time when every
+        # step's grid starts behind the last row of the step before it (any file the file loop produces)
+        first = (self.row_off[:-1] + np.arange(self.row_off.shape[0] - 1))[1:]
+        last = (self.row_off[1:] + np.arange(self.row_off.shape[0] - 1) - 1)[:-1]
+        inner = np.ones(first.shape[0], dtype=bool)
+        inner[self.chunk_off[1:-1] - 1] = False                                        # the first step of a file
+        self.sorted_steps = bool((self.mids[first] > self.mids[last])[inner].all())
+
+    def _check_sorted(self, what: str, instead: str = "backend='host'") -> None:
+        if not self.sorted_steps:
+            raise ValueError(f"{what} scores the turns of a file in step order, and the output grids of "
+                             f"this cache's steps are not sorted by time; {instead} sorts them")
 
     @staticmethod
     def default_backend() -> str:
@@ -376,7 +391,8 @@ class TuneCache(_ReplayCache):
         if key not in self._dev:
             tensors = {name: torch.from_numpy(getattr(self, name)).to(device)
                        for name in ("seg", "emb", "pre_max", "pre_mean", "pre_flags", "chunk_off", "plan", "row_off",
-                                    "row_chunk", "hamming")}
+                                    "row_chunk", "hamming", "mids", "mid_cell", "file_cell_off", "cell_dur")}
+            tensors["cell_ref"] = torch.from_numpy(self.cell_ref.view(np.int64)).to(device)      # (the 64 bits as they are)
             self._dev[key] = (tensors, self._desc(lambda name: tensors[name].data_ptr()))
         return self._dev[key]
 
@@ -402,21 +418,108 @@ class TuneCache(_ReplayCache):
                                               torch.cuda.current_stream(device).cuda_stream), "dz_tune_replay")
         return assign, status, bits
 
-    def score(self, bits: np.ndarray, num_threads: int = 8) -> np.ndarray:
-        """``(T, N, 5)`` error-rate components (``metrics.COMPONENTS``) of the masks of ``replay``."""
-        return self._score_bits(bits, self.G, num_threads)
+    SCORE_LANES = 256           # the lanes of tune_score_kernel's workgroup (backend="core" plays them in order)
+    SCORE_BLOCKS = 512          # resident scoring workgroups: 256 CUs x 2 (60 KB of LDS each), one scratch slice each
+    _SCORE_ERRORS = {4: "dz_tune_score: a speech turn does not start and end on the file's scoring cells",
+                     3: "dz_tune_score: the mapping's assignment problem failed",
+                     2: "dz_tune_score_gpu: a file has more scoring cells than a scratch slice holds"}
+
+    @staticmethod
+    def _check_scoring(scoring: Optional[str], backend: str) -> str:
+        if scoring not in (None, "host", "device"):
+            raise ValueError(f"scoring '{scoring}': host or device")
+        if scoring == "device" and backend not in ("gpu", "core"):
+            raise ValueError(f"scoring='device' runs on backend='gpu' (the scoring kernel) or backend='core' (its text on "
+                             f"host threads), not on backend '{backend}'")
+        return scoring or "host"
+
+    def _score_gpu(self, bits: torch.Tensor, score_blocks: Optional[int] = None):
+        """``(out (T, N, 5) float64, err (1,) int32)`` on the device of ``bits (T, rows)``: tune_score_kernel, enqueued."""
+        device = bits.device
+        t, _ = self._device(device)
+        T = bits.shape[0]
+        blocks = max(1, min(T * self.N, int(score_blocks or self.SCORE_BLOCKS)))
+        out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device)
+        scratch = torch.empty((blocks, self.max_cells + 1), dtype=torch.int32, device=device)
+        err = torch.empty(1, dtype=torch.int32, device=device)
+        _lib.check(_lib.load().dz_tune_score_gpu(_lib.context(device.index), T, self.N, bits.data_ptr(), self.total_rows,
+                                                 t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(),
+                                                 t["mid_cell"].data_ptr(), t["file_cell_off"].data_ptr(),
+                                                 t["cell_dur"].data_ptr(), t["cell_ref"].data_ptr(), self.max_cells, self.G,
+                                                 PATCH_COLLAR, out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(),
+                                                 torch.cuda.current_stream(device).cuda_stream), "dz_tune_score_gpu")
+        return out, err
+
+    def _score_fetch(self, out: torch.Tensor, err: torch.Tensor) -> np.ndarray:
+        per_file, rc = out.cpu().numpy(), int(err.cpu()[0])
+        if rc:
+            raise _lib.DiartAmdError(f"dz_tune_score_gpu failed (code {rc}): {self._SCORE_ERRORS.get(rc, 'unknown')}")
+        return per_file
+
+    def _score_core(self, bits: np.ndarray, num_threads: int, score_blocks: Optional[int] = None) -> np.ndarray:
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        T = bits.shape[0]
+        out = np.zeros((T, self.N, 5), dtype=np.float64)
+        _lib.check(_lib.load().dz_tune_score_core(T, self.N, bits.ctypes.data, self.total_rows, self.chunk_off.ctypes.data,
+                                                  self.row_off.ctypes.data, self.mids.ctypes.data, self.mid_cell.ctypes.data,
+                                                  self.file_cell_off.ctypes.data, self.cell_dur.ctypes.data,
+                                                  self.cell_ref.ctypes.data, self.max_cells, self.G, PATCH_COLLAR,
+                                                  self.SCORE_LANES, int(score_blocks or self.SCORE_BLOCKS), out.ctypes.data,
+                                                  int(num_threads)), "dz_tune_score_core")
+        return out
+
+    def score(self, bits, num_threads: int = 8, scoring: Optional[str] = None, backend: Optional[str] = None,
+              score_blocks: Optional[int] = None) -> np.ndarray:
+        """``(T, N, 5)`` error-rate components (``metrics.COMPONENTS``) of the masks of ``replay``.  ``scoring``: None or
+        "host" (``dz_tune_score`` on host threads) or "device": the scoring kernel on ``backend="gpu"`` (``bits`` a
+        device tensor, or a numpy array that is uploaded), its text on host threads on ``backend="core"`` (the default
+        without a GPU).  ``score_blocks``: the workgroups that share the pairs, each with one scratch slice."""
+        if scoring == "device" and backend is None:
+            backend = "gpu" if isinstance(bits, torch.Tensor) or torch.cuda.is_available() else "core"
+        if self._check_scoring(scoring, backend or "host") == "host":
+            if isinstance(bits, torch.Tensor):
+                bits = bits.cpu().numpy().view(np.uint32)
+            return self._score_bits(bits, self.G, num_threads)
+        self._check_sorted("scoring 'device'", "scoring='host'")
+        if backend == "core":
+            if isinstance(bits, torch.Tensor):
+                bits = bits.cpu().numpy().view(np.uint32)
+            return self._score_core(bits, num_threads, score_blocks)
+        if not torch.cuda.is_available():
+            raise _lib.DiartAmdError("backend='gpu' needs a GPU; backend='core' scores with the kernel's text on the host")
+        if not isinstance(bits, torch.Tensor):
+            bits = torch.from_numpy(np.ascontiguousarray(bits, dtype=np.uint32).view(np.int32)).to(
+                torch.device("cuda", torch.cuda.current_device()))
+        if bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[1] != self.total_rows or not bits.is_cuda:
+            raise ValueError(f"bits (T, {self.total_rows}) int32 on a GPU expected, got {tuple(bits.shape)} {bits.dtype} on "
+                             f"{bits.device}")
+        return self._score_fetch(*self._score_gpu(bits.contiguous(), score_blocks))
 
     def evaluate(self, hparams, backend: Optional[str] = None, memory_budget: int = 1 << 30,
-                 num_threads: int = 8) -> TuneResult:
+                 num_threads: int = 8, scoring: Optional[str] = None) -> TuneResult:
         """The error rate of every trial of ``hparams (T, 3)``, trials in batches whose results fit ``memory_budget``
-        bytes."""
+        bytes (``bytes_per_trial`` each: host and device bytes with host scoring; with ``scoring="device"`` on the GPU
+        backend the masks never reach the host and the budget counts device bytes — the scratch of the scoring kernel,
+        ``SCORE_BLOCKS`` slices of one word per scoring cell of the largest file, does not grow with the trials and is
+        not counted).  ``scoring``: None or "host": the masks are copied to the host and scored by ``dz_tune_score``;
+        "device": scored where they are (``backend="gpu"``: only the components and the statuses come back;
+        ``backend="core"``: the kernel's text on host threads)."""
         hp = self._hparams(hparams)
         backend = backend or self.default_backend()
+        device_scoring = self._check_scoring(scoring, backend) == "device"
+        if device_scoring:
+            self._check_sorted("scoring 'device'", "scoring='host'")
         per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
         per_file, status = [], []
         for a in range(0, hp.shape[0], per_batch):
+            if device_scoring and backend == "gpu":
+                _, st, bits = self._replay_gpu(hp[a:a + per_batch])
+                out, err = self._score_gpu(bits)
+                per_file.append(self._score_fetch(out, err))
+                status.append(st.cpu().numpy())
+                continue
             _, st, bits = self.replay(hp[a:a + per_batch], backend, num_threads)
-            per_file.append(self.score(bits, num_threads))
+            per_file.append(self._score_core(bits, num_threads) if device_scoring else self.score(bits, num_threads))
             status.append(st)
         per_file, status = np.concatenate(per_file), np.concatenate(status)
         comp = per_file.sum(axis=1)
@@ -527,13 +630,6 @@ class VadTuneCache(_ReplayCache):
             ref.append(np.concatenate([[0.0], np.cumsum(np.where(self.cell_ref[a:b] != 0, d, 0.0))]))
         self.dur_prefix = np.ascontiguousarray(np.concatenate(dur), dtype=np.float64)
         self.ref_prefix = np.ascontiguousarray(np.concatenate(ref), dtype=np.float64)
-        # the scoring kernel takes the turns of a file in step order: that is their order by start time when every
-        # step's grid starts behind the last row of the step before it (any file the file loop produces)
-        first = (self.row_off[:-1] + np.arange(self.row_off.shape[0] - 1))[1:]
-        last = (self.row_off[1:] + np.arange(self.row_off.shape[0] - 1) - 1)[:-1]
-        inner = np.ones(first.shape[0], dtype=bool)
-        inner[self.chunk_off[1:-1] - 1] = False                                        # the first step of a file
-        self.sorted_steps = bool((self.mids[first] > self.mids[last])[inner].all())
 
     def _desc(self, ptr) -> _lib.TuneDesc:
         d = _lib.TuneDesc()
@@ -557,11 +653,6 @@ class VadTuneCache(_ReplayCache):
         if t.ndim != 1 or t.shape[0] < 1:
             raise ValueError(f"taus (T,) or (T, 1) = tau_active per trial expected, got {np.shape(taus)}")
         return np.ascontiguousarray(t)
-
-    def _check_sorted(self, backend: str) -> None:
-        if not self.sorted_steps:
-            raise ValueError(f"backend '{backend}' scores the turns of a file in step order, and the output grids of "
-                             "this cache's steps are not sorted by time; backend='host' sorts them")
 
     def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int):
         T = taus.shape[0]
@@ -635,11 +726,11 @@ class VadTuneCache(_ReplayCache):
         taus = self._taus(taus)
         backend = backend or self.default_backend()
         if backend == "gpu":
-            self._check_sorted(backend)
+            self._check_sorted(f"backend '{backend}'")
             out = self._gpu(taus, False, True)[2]
             per_file = out.cpu().numpy()
         elif backend == "core":
-            self._check_sorted(backend)
+            self._check_sorted(f"backend '{backend}'")
             per_file = self._host(taus, False, True, num_threads)[2]
         elif backend == "host":
             per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
@@ -689,16 +780,24 @@ class Optimizer:
     is replaced by a directory: ``<path>/<stem>.json`` holds every trial and is loaded if it exists, a second call
     continues the numbering and never evaluates a stored trial again.  ``sampler``: "random" (uniform over each
     parameter's range, from ``seed``) or "grid" (``num_iter`` as a total: the largest cube not above it).  Trials are
-    evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run).
+    evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run);
+    ``scoring``: ``TuneCache.evaluate``'s (None and "host": on host threads, "device": on the replay's backend).
     ``pipeline_class``: ``SpeakerDiarization``, or ``VoiceActivityDetection`` — then ``tau_active`` alone is tuned, the
     metric is the detection error rate and the cache a ``VadTuneCache``."""
 
     def __init__(self, pipeline_class: type, speech_path, reference_path, study_or_path, batch_size: int = 32,
                  hparams: Optional[Sequence[base.HyperParameter]] = None, base_config=None,
                  do_kickstart_hparams: bool = True, metric=None, direction: str = "minimize", sampler: str = "random",
-                 seed: int = 0, trials_per_batch: int = 256, cache=None, backend: Optional[str] = None):
+                 seed: int = 0, trials_per_batch: int = 256, cache=None, backend: Optional[str] = None,
+                 scoring: Optional[str] = None):
         self.kind = _pipeline_kind(pipeline_class)
         vad = self.kind == "vad"
+        if scoring not in (None, "host", "device"):
+            raise ValueError(f"scoring '{scoring}': host or device")
+        if vad and scoring is not None:
+            raise ValueError("scoring: VoiceActivityDetection is scored where it is replayed (backend); only "
+                             "SpeakerDiarization takes scoring='host' or 'device'")
+        self.scoring = scoring
         self.cache_class = VadTuneCache if vad else TuneCache
         self.tunable = VAD_TUNABLE if vad else TUNABLE
         if cache is not None and not isinstance(cache, self.cache_class):
@@ -781,7 +880,8 @@ class Optimizer:
     def objective(self, params: Sequence[Dict[str, float]]) -> np.ndarray:
         """The metric in percent of every trial of ``params`` (NaN where the clustering would raise)."""
         hp = np.array([self._values(p) for p in params], dtype=np.float64)
-        return 100.0 * self.cache.evaluate(hp, backend=self.backend).rate
+        kw = {} if self.scoring is None else dict(scoring=self.scoring)
+        return 100.0 * self.cache.evaluate(hp, backend=self.backend, **kw).rate
 
     def _grid(self, total: int) -> List[Dict[str, float]]:
         """The largest cube of at most ``total`` points: the same number of equally spaced interior values per axis."""

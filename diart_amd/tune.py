@@ -39,6 +39,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--normalize-embedding-weights", action="store_true")
     ap.add_argument("--cpu", action="store_true",
                     help="Replay the trials on the host even if a GPU is there; the models keep their GPU device")
+    ap.add_argument("--scoring", default=None, choices=("host", "device"),
+                    help="Where SpeakerDiarization trials are scored: host (dz_tune_score on host threads, the default) or "
+                         "device (on the GPU, beside the replay; not with --cpu)")
     ap.add_argument("--hparams", nargs="+", default=None,
                     help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three); "
                          "tau_active alone with --pipeline VoiceActivityDetection")
@@ -84,7 +87,7 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
     opt = Optimizer(pipeline_class, args.root, args.reference, Path(args.output).expanduser(),
                     batch_size=args.batch_size, hparams=hparams, base_config=base_config, sampler=args.sampler,
                     seed=args.seed, trials_per_batch=args.trials_per_batch, cache=cache,
-                    backend="host" if args.cpu else None)
+                    backend="host" if args.cpu else None, scoring=args.scoring)
     if args.cache and cache is None:
         opt.cache.save(args.cache)
     opt(num_iter=args.num_iter, show_progress=True)

@@ -938,6 +938,28 @@ int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows,
                   const int* file_chunk_off, const int* step_rows, const double* mids, const int* mid_cell,
                   const int* file_cell_off, const double* cell_dur, const unsigned long long* cell_ref,
                   int max_speakers, double collar, double* out, int num_threads);
+/* dz_tune_score on the device: d_bits (T, total_rows) as dz_tune_replay wrote them stay there, and d_out
+ * (T, N, 5) is all that a call leaves.  One workgroup per (trial, file) pair, score_blocks of them resident,
+ * each on its own slice of d_scratch (score_blocks, max_cells + 1) uint32, max_cells = the cells of the
+ * largest file; row_off (chunks + 1) is the prefix sum of step_rows, the other arrays are dz_tune_score's,
+ * in device memory, the steps of a file sorted by time.  What differs from dz_tune_score is the order in
+ * which the durations are summed (per lane, the lanes in order: the same doubles on every call).  d_err: one
+ * int, 0 after the call, or dz_tune_score's return code (4 = a turn off the file's cells, 3 = the assignment
+ * problem failed, 2 = a file with more than max_cells cells) of some pair; d_out is then not to be used.
+ * Enqueued on `stream`, no synchronisation.                                                              */
+int dz_tune_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits, int total_rows,
+                      const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
+                      const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
+                      const unsigned long long* d_cell_ref, int max_cells, int max_speakers, double collar,
+                      double* d_out, unsigned* d_scratch, int score_blocks, int* d_err, void* stream);
+/* The same from host memory, compiled from the text of the kernel: the `lanes` (at most 256) lanes of a
+ * workgroup played in order, "workgroup" b of score_blocks taking pairs b, b + score_blocks, ... on one
+ * scratch slice, workgroups on num_threads host threads.  Returns dz_tune_score's codes.                */
+int dz_tune_score_core(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
+                       const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
+                       const double* cell_dur, const unsigned long long* cell_ref, int max_cells,
+                       int max_speakers, double collar, int lanes, int score_blocks, double* out,
+                       int num_threads);
 /* Tuning VoiceActivityDetection (tau_active alone): one track per chunk, so dz_tune_desc has k_local = 1,
  * seg (chunks, frames) = the max over the local speakers, and emb / pre_* unused (may be NULL).  The
  * aggregated speech score of a packed output row does not depend on tau: dz_tune_vad_rows writes
