@@ -187,6 +187,8 @@ SIGNATURES = {
     "dz_resample_create": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_resample_forward": (C.c_int, [vp, vp, C.c_longlong, C.c_longlong, C.c_int, vp, C.c_longlong, vp]),
     "dz_resample_destroy": (C.c_int, [vp]),
+    "dz_adjust_volume": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_double,
+                                   vp]),
     "dz_prof_enable": (C.c_int, [C.c_int]),
     "dz_prof_pause": (C.c_int, [C.c_int]),
     "dz_prof_collect": (C.c_int, []),

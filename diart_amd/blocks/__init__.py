@@ -7,13 +7,13 @@ from .diarization import SpeakerDiarization, SpeakerDiarizationConfig
 from .embedding import (EmbeddingNormalization, OverlapAwareSpeakerEmbedding,
                         OverlappedSpeechPenalty, SpeakerEmbedding)
 from .segmentation import SpeakerSegmentation
-from .utils import Binarize, Resample, resample
+from .utils import AdjustVolume, Binarize, Resample, adjust_volume, resample
 from .vad import VoiceActivityDetection, VoiceActivityDetectionConfig
 
 __all__ = ["SpeakerSegmentation", "SpeakerEmbedding", "OverlappedSpeechPenalty",
            "EmbeddingNormalization", "OverlapAwareSpeakerEmbedding", "OnlineSpeakerClustering",
            "IncrementalSpeakerClustering", "BatchedSpeakerClustering", "DelayedAggregation",
            "AggregationStrategy", "HammingWeightedAverageStrategy", "AverageStrategy", "FirstOnlyStrategy",
-           "BatchedOutputTail", "Binarize", "Resample", "resample", "Pipeline", "PipelineConfig", "HyperParameter",
+           "BatchedOutputTail", "Binarize", "Resample", "resample", "AdjustVolume", "adjust_volume", "Pipeline", "PipelineConfig", "HyperParameter",
            "SpeakerDiarization", "SpeakerDiarizationConfig", "VoiceActivityDetection",
            "VoiceActivityDetectionConfig"]

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..features import Annotation, Segment, SlidingWindowFeature, TemporalFeatureFormatter, TemporalFeatures
-from ..functional import resample, resampler
+from ..functional import _gpu, _target_db, adjust_volume, adjust_volume_rows, resample, resampler  # noqa: F401
 
 
 def windows_batch(waveforms: Sequence[SlidingWindowFeature], device=None) -> torch.Tensor:
@@ -109,3 +109,30 @@ class Resample:
         out = self.resample(wav.transpose(-1, -2)).transpose(-1, -2)
         return self.formatter.restore_type(out)
 
+
+
+class AdjustVolume:
+    """Change the volume of audio chunks (reference ``blocks/utils.py:92-137``) on the GPU: ``(batch, samples,
+    channels)`` or ``(samples, channels)`` features in, the same kind out, every (chunk, channel) signal scaled to
+    ``volume_in_db`` dB on its own and, where that would exceed full scale, divided by its scaled peak — so the output
+    volume may be lower than asked for.  As in the reference a chunk of zero energy, or with a NaN / Inf sample, comes
+    out all NaN.  A ``SlidingWindowFeature`` keeps its sliding window.  ``adjust_volume`` is the functional form."""
+
+    def __init__(self, volume_in_db: float, device: Optional[torch.device] = None):
+        self.target_db = _target_db(volume_in_db)
+        self.device = None if device is None else torch.device(device)
+        self.formatter = TemporalFeatureFormatter()
+
+    @staticmethod
+    def get_volumes(waveforms: torch.Tensor) -> torch.Tensor:
+        """Volumes in dB of audio chunks ``(batch, samples, channels)``, per channel: ``(batch, 1, channels)``."""
+        return 10 * torch.log10(waveforms.square().mean(dim=1, keepdim=True))
+
+    def __call__(self, waveform: TemporalFeatures) -> TemporalFeatures:
+        wav = self.formatter.cast(waveform)          # (batch, samples, channels)
+        src = wav.device
+        dev = _gpu(src if src.type == "cuda" else self.device)
+        B, S, C = wav.shape
+        x = wav.to(dev).contiguous().reshape(B, S * C)
+        out = adjust_volume_rows(x, self.target_db, channels=C).reshape(B, S, C)
+        return self.formatter.restore_type(out if src == dev else out.to(src))

@@ -1,7 +1,8 @@
 """Tensor functions of the hot path, computed by HIP kernels.
 
 Same names and results as ``/root/reference/src/diart/functional.py`` (:6-13
-``overlapped_speech_penalty``, :16-27 ``normalize_embeddings``).  Inputs may live on the host
+``overlapped_speech_penalty``, :16-27 ``normalize_embeddings``), plus ``resample`` and ``adjust_volume``, the
+functional forms of the ``Resample`` and ``AdjustVolume`` blocks.  Inputs may live on the host
 (the reference runs these on CPU tensors) or on the GPU; the result comes back on the device
 of the input.  There is no torch fallback: without ``libdiart_amd.so`` and a GPU they raise.
 """
@@ -133,3 +134,58 @@ def resample(waveform, orig_freq: int, new_freq: int, device: Optional[torch.dev
     import numpy as np
     x = torch.from_numpy(np.ascontiguousarray(waveform, dtype=np.float32))
     return resampler(orig_freq, new_freq, device)(x).numpy()
+
+
+def _target_db(volume_in_db) -> float:
+    """``volume_in_db`` as a finite float, or ``ValueError`` (before anything touches a device)."""
+    import math
+    import numbers
+    if isinstance(volume_in_db, bool) or not isinstance(volume_in_db, numbers.Real) or not math.isfinite(volume_in_db):
+        raise ValueError(f"volume_in_db={volume_in_db!r} (expected a finite number of dB)")
+    return float(volume_in_db)
+
+
+def adjust_volume_rows(x: torch.Tensor, volume_in_db: float, out: Optional[torch.Tensor] = None,
+                       channels: int = 1) -> torch.Tensor:
+    """``x`` (rows, samples * channels) float32 on a GPU, a row's channels interleaved, rows at any stride (a ring or
+    window-batch view is read in place) -> ``out`` of the same shape (allocated when not given; ``out is x``: in
+    place), every (row, channel) signal brought to ``volume_in_db`` on its own (``dz_adjust_volume``, DESIGN.md
+    "Volume adjustment").  Enqueued on the current stream."""
+    target = _target_db(volume_in_db)
+    assert x.is_cuda and x.dtype == torch.float32 and x.ndim == 2 and x.stride(1) == 1
+    R, L = x.shape
+    if not (1 <= channels <= 8) or L % channels or R < 1 or L < 1:
+        raise ValueError(f"adjust_volume_rows: {R} rows of {L} values in {channels} channels")
+    if out is None:
+        out = torch.empty((R, L), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.device == x.device and out.dtype == torch.float32 and tuple(out.shape) == (R, L) \
+        and out.stride(1) == 1
+    # one row: its stride is never used (and torch reports any number for it)
+    xs, os_ = (L, L) if R == 1 else (x.stride(0), out.stride(0))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dz_adjust_volume(_lib.context(x.device.index), x.data_ptr(), xs, out.data_ptr(), os_, R,
+                                                L // channels, int(channels), target,
+                                                torch.cuda.current_stream(x.device).cuda_stream), "dz_adjust_volume")
+    return out
+
+
+def adjust_volume(waveform, volume_in_db: float, device: Optional[torch.device] = None):
+    """The ``AdjustVolume`` block's arithmetic over the last axis of ``(..., samples)``, on the GPU: each signal is
+    scaled to ``volume_in_db`` dB (``10 log10`` of its mean square) and, where the scaled peak exceeds 1, divided by
+    it.  A tensor comes back on its own device, a numpy array as a float32 array.  As in the reference a signal of
+    zero energy, or with a NaN / Inf sample, comes out all NaN."""
+    target = _target_db(volume_in_db)
+    if not isinstance(waveform, torch.Tensor):
+        import numpy as np
+        x = torch.from_numpy(np.ascontiguousarray(waveform, dtype=np.float32))
+        return adjust_volume(x, target, device).numpy()
+    if waveform.ndim == 0 or waveform.numel() == 0:
+        raise ValueError(f"adjust_volume: empty waveform of shape {tuple(waveform.shape)}")
+    src = waveform.device
+    dev = _gpu(src if src.type == "cuda" or device is None else torch.device(device))
+    lead, L = waveform.shape[:-1], waveform.shape[-1]
+    x = waveform.to(dev, torch.float32).reshape(-1, L)
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    y = adjust_volume_rows(x, target).reshape(*lead, L)
+    return y if src == dev else y.to(src)

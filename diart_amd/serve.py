@@ -30,6 +30,13 @@ and the push kernel converts and averages them (``dz_ring_push_rows_pcm``); the 
 in numpy (``pcm_to_mono``), so every mode hands the models identical float32 windows.  ``device_rings="all"``
 also uses rings where a block is not a multiple of 4 samples (44.1 kHz, 22.05 kHz).
 
+Clients differ in level by tens of dB.  ``volume_in_db`` (default ``None``: off, no kernel, today's windows) brings
+every window of every stream to that volume on its own before the models see it — the reference's per-window
+``blocks.AdjustVolume``: gain to the target, then division by the scaled peak where it exceeds 1.  With the default
+engines it runs in place on the staged device rows, behind the resampler and on its stream; a custom ``engine`` gets
+windows adjusted by the same kernel, so every mode sees identical bits.  As in the reference a digitally silent
+window (all zeros) becomes a NaN window, and its scores are NaN rows.
+
 Transport (websocket, microphone) is out of scope: ``push`` is the seam a network front-end calls
 (thread-safe), ``step`` / ``serve_forever`` is the worker loop."""
 from __future__ import annotations
@@ -43,7 +50,7 @@ import torch
 
 from .blocks.aggregation import BatchedOutputTail
 from .features import Annotation
-from .functional import resampler
+from .functional import _target_db, adjust_volume, adjust_volume_rows, resampler
 from .models import HipWeSpeakerEmbedding
 from .pipeline import AudioRing, StreamBatch, VadBatch, WeSpeakerBatch
 
@@ -90,7 +97,8 @@ class StreamServer:
                  device: Optional[torch.device] = None, patch_collar: float = 0.05,
                  engine: Optional[Callable] = None, device_rings=True,
                  normalize_embedding_weights: bool = False, input_sample_rate: Optional[int] = None,
-                 pipeline: str = "diarization", input_format: str = "f32", input_channels: int = 1):
+                 pipeline: str = "diarization", input_format: str = "f32", input_channels: int = 1,
+                 volume_in_db: Optional[float] = None):
         if pipeline not in PIPELINES:
             raise ValueError(f"StreamServer: pipeline={pipeline!r} (expected one of {PIPELINES})")
         if pipeline == "vad" and embedding is not None:
@@ -102,6 +110,8 @@ class StreamServer:
             raise ValueError(f"StreamServer: input_channels={input_channels!r} (expected 1 .. {MAX_INPUT_CHANNELS})")
         if device_rings not in (True, False, "all"):
             raise ValueError(f"StreamServer: device_rings={device_rings!r} (expected True, False or 'all')")
+        # per-window volume adjustment (None: off); a non-finite or non-numeric target is refused here
+        self.volume_in_db = None if volume_in_db is None else _target_db(volume_in_db)
         # what clients push: interleaved frames of `input_channels` values of `input_format`
         self.input_format, self.input_channels = input_format, int(input_channels)
         self._in_dtype = INPUT_FORMATS[input_format]
@@ -172,10 +182,13 @@ class StreamServer:
         else:
             self.batch, self.rings = None, None
             self._engine, self._reset_slot = engine, getattr(engine, "reset", lambda slot: None)
+            if self.volume_in_db is not None:
+                # a custom engine gets its windows adjusted, each on its own (GPU), behind the resampler
+                self._engine = self._adjusting_engine(engine, device)
             if self.input_sample_rate != self.sample_rate:
                 # a custom engine gets its windows at the pipeline's rate, each resampled on its own (GPU)
                 self.resampler = resampler(self.input_sample_rate, self.sample_rate, device)
-                self._engine = self._resampling_engine(engine)
+                self._engine = self._resampling_engine(self._engine)
 
     # ------------------------------------------------------------------ stream life cycle
     def open(self, stream_id: Hashable) -> None:
@@ -422,6 +435,12 @@ class StreamServer:
             return engine(self.resampler(x).numpy(), starts, slots)
         return run
 
+    def _adjusting_engine(self, engine: Callable, device) -> Callable:
+        def run(windows, starts, slots):
+            x = torch.from_numpy(np.ascontiguousarray(windows, dtype=np.float32))
+            return engine(adjust_volume(x, self.volume_in_db, device).numpy(), starts, slots)
+        return run
+
     # ------------------------------------------------------------------ GPU engine
     def _gpu_engine(self, windows, starts: np.ndarray, slots: List[int]):
         """``windows``: (k, S) on the host (uploaded whole, like the reference) or already a device
@@ -433,6 +452,9 @@ class StreamServer:
         if self.resampler is not None:
             with torch.cuda.device(self._dev.device):
                 self.resampler.rows(self._raw[:k], self._dev[:k])
+        if self.volume_in_db is not None:
+            rows = self._dev[:k]
+            adjust_volume_rows(rows, self.volume_in_db, out=rows)       # in place, on the current stream
         ticket = self.batch.launch(self._dev[:k], starts, slots=slots)
         if isinstance(self.batch, VadBatch):
             self.batch.finish(ticket)

@@ -583,6 +583,16 @@ int dz_resample_forward(dz_resample* m, const float* d_in, long long in_stride, 
                         float* d_out, long long out_stride, void* stream);
 int dz_resample_destroy(dz_resample* m);
 
+/* ---- volume adjustment: the reference's AdjustVolume block (blocks/utils.py:92-137; csrc/k_volume.hip).  A row is
+ * samples * channels interleaved float32 values; rows at any float address, any stride >= that size.  Per (row,
+ * channel) signal x: volume = 10 log10(mean(x^2)) (squares in f32, summed in f64), gain = fl32(10^((target_db - volume)
+ * / 20)), m = max(fl32(gain max|x|), 1), out = fl32(fl32(gain x) / m).  As in the reference a signal of zero energy, or
+ * with a NaN / Inf sample, comes out all NaN.  A signal's bits do not depend on its alignment, its place in the call or
+ * the other rows; no atomics.  d_out == d_in with equal strides is in place.  rows, samples >= 1, 1 <= channels <= 8,
+ * finite target_db (else return 2, nothing launched).  Enqueued on `stream`; no handle, no allocation.                */
+int dz_adjust_volume(dz_ctx* ctx, const float* d_in, long long in_row_stride, float* d_out, long long out_row_stride,
+                     int rows, long long samples, int channels, double target_db, void* stream);
+
 /* ---- OverlappedSpeechPenalty: functional.py:6-13 + blocks/embedding.py:98-107
  * d_seg (B,F,K) -> weights.  speaker_major=0: (B,F,K) like the reference block;
  * speaker_major=1: (B,K,F), the layout dz_emb_forward_multi consumes.           */
