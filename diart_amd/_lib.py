@@ -218,6 +218,7 @@ SIGNATURES = {
     "dz_ring_read": (C.c_int, [vp, vp, vp]),
     "dz_ring_push_rows": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_int, vp]),
     "dz_ring_push_rows_pcm": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, vp]),
+    "dz_pcm_decode": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp]),
     "dz_ring_filled_row": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
     "dz_ring_gather": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, vp, C.c_longlong, vp]),
     "dz_ring_reset_row": (C.c_int, [vp, C.c_int]),

@@ -165,8 +165,31 @@ __global__ __launch_bounds__(256) void ring_gather_any_kernel(const float* __res
 // do before they send.  The arithmetic is the header's definition, operation for operation: nothing is
 // contracted (the sum is a chain of adds, the average one division), and one float channel is copied as bits.
 // ---------------------------------------------------------------------------
+// the three 1-byte formats share a storage type: a tag type each selects the conversion
+struct pcm_u8 { unsigned char v; };
+struct pcm_ulaw { unsigned char v; };
+struct pcm_alaw { unsigned char v; };
+
 __device__ __forceinline__ float pcm_to_f32(float v) { return v; }
 __device__ __forceinline__ float pcm_to_f32(short v) { return (float)v * (1.0f / 32768.0f); }
+__device__ __forceinline__ float pcm_to_f32(int v) { return (float)v * (1.0f / 2147483648.0f); }   // the conversion rounds
+__device__ __forceinline__ float pcm_to_f32(pcm_u8 b) { return ((float)b.v - 128.0f) * (1.0f / 128.0f); }
+// G.711 expansion in integer ALU (a dozen operations per byte, selects instead of branches: no table to stage, no
+// LDS, nothing a wave could diverge on), then one exact int -> float conversion and one exact scaling
+__device__ __forceinline__ float pcm_to_f32(pcm_ulaw b) {
+    const int u = ~(int)b.v & 0xFF;
+    const int t = (((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7);
+    const int L = (u & 0x80) ? 0x84 - t : t - 0x84;
+    return (float)L * (1.0f / 32768.0f);
+}
+__device__ __forceinline__ float pcm_to_f32(pcm_alaw b) {
+    const int a = (int)b.v ^ 0x55;
+    const int m = (a & 0x0F) << 4;
+    const int s = (a >> 4) & 7;
+    const int t = (s == 0) ? m + 8 : (m + 0x108) << ((s - 1) & 7);     // (& 7: the shift of the unselected side stays defined)
+    const int L = (a & 0x80) ? t : -t;
+    return (float)L * (1.0f / 32768.0f);
+}
 
 // e: the C values of one frame
 template <typename T, int C>
@@ -179,62 +202,101 @@ __device__ __forceinline__ float pcm_frame(const T* e) {
     return s / (float)C;
 }
 
+// F = 16 / sizeof(T) frames of C interleaved values at `src` (16-byte aligned): C 16-byte loads, the frames'
+// samples to o0 and, with TWICE, to o1 (both 16-byte aligned) with 16-byte stores
+template <typename T, int C, bool TWICE>
+__device__ __forceinline__ void pcm_lane_frames(const T* src, float* o0, float* o1) {
+    constexpr int F = 16 / sizeof(T);
+    union {
+        f32x4 v[C];
+        T e[F * C];
+    } u;
+    const f32x4* s = reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+    for (int c = 0; c < C; ++c) u.v[c] = s[c];
+#pragma unroll
+    for (int q = 0; q < F / 4; ++q) {
+        f32x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = pcm_frame<T, C>(u.e + (4 * q + i) * C);
+        *reinterpret_cast<f32x4*>(o0 + 4 * q) = o;
+        if (TWICE) *reinterpret_cast<f32x4*>(o1 + 4 * q) = o;
+    }
+}
+
+// one frame at `src` (aligned to one value)
+template <typename T, int C>
+__device__ __forceinline__ float pcm_one_frame(const T* src) {
+    T e[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) e[c] = src[c];
+    return pcm_frame<T, C>(e);
+}
+
+// lanes of a block of the push kernel: a 1-byte format's lane takes 16 frames, so one wave already covers 1 024
+template <typename T>
+constexpr int pcm_block_lanes() { return sizeof(T) == 1 ? 64 : 256; }
+
 // Row j of `block` (rows `bstride` values apart): hop frames of C interleaved values of type T -> ring row
 // rows.row[j] at rows.off[j] and rows.off[j] + P.  A lane takes F = 16 / sizeof(T) frames, which are C 16-byte
-// loads whatever the format, and writes them with 16-byte stores; a block covers 256 F frames.  Where the input
-// rows (in_vec == 0), this row's ring position (off or P not a multiple of 4: a ring with hop % 4 != 0) or the
-// block's extent (the tail of a row) do not allow that, the lanes of the block take single frames, 256 apart:
-// 4-byte stores, a wave's stores one contiguous span.  Both paths do the same arithmetic per frame.
+// loads whatever the format, and writes them with 16-byte stores; a block of L lanes covers L F frames.  Where the
+// input rows (in_vec == 0) or this row's ring position (off or P not a multiple of 4: a ring with hop % 4 != 0) do
+// not allow that, the lanes of the block take single frames, L apart: 4-byte stores, a wave's stores one contiguous
+// span.  So does, for the 2- and 4-byte formats, the block at the tail of a row (f0 + F L > hop).  A 1-byte format has
+// F = 16 and the telephone hop is 4 000 frames: a per-block rule would send every frame of that workload down the
+// single-frame path, so there each LANE decides: 16 frames inside the row -> the vector path, and only the lane
+// that holds the ragged end (hop % 16 frames) takes them one by one.  Both paths do the same arithmetic per frame.
 template <typename T, int C>
 __global__ __launch_bounds__(256) void ring_scatter_pcm_kernel(const T* __restrict__ block, long long bstride,
                                                                float* __restrict__ buf, long long pitch, int hop,
                                                                int P, int in_vec, DzRowList rows) {
     constexpr int F = 16 / sizeof(T);
+    constexpr int L = pcm_block_lanes<T>();
     const int jrow = blockIdx.y;
     const int off = rows.off[jrow];
     const T* in = block + (long long)jrow * bstride;
     float* row = buf + (long long)rows.row[jrow] * pitch + off;
-    const int f0 = blockIdx.x * (F * 256);
-    if (in_vec && ((off | P) & 3) == 0 && f0 + F * 256 <= hop) {
-        const int f = f0 + F * threadIdx.x;
-        union {
-            f32x4 v[C];
-            T e[F * C];
-        } u;
-        const f32x4* src = reinterpret_cast<const f32x4*>(in + (long long)f * C);
-#pragma unroll
-        for (int c = 0; c < C; ++c) u.v[c] = src[c];
-#pragma unroll
-        for (int q = 0; q < F / 4; ++q) {
-            f32x4 o;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = pcm_frame<T, C>(u.e + (4 * q + i) * C);
-            *reinterpret_cast<f32x4*>(row + f + 4 * q) = o;
-            *reinterpret_cast<f32x4*>(row + P + f + 4 * q) = o;
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < F; ++t) {
-            const int f = f0 + t * 256 + threadIdx.x;
-            if (f < hop) {
-                T e[C];
-#pragma unroll
-                for (int c = 0; c < C; ++c) e[c] = in[(long long)f * C + c];
-                const float o = pcm_frame<T, C>(e);
-                row[f] = o;
-                row[P + f] = o;
+    const int f0 = blockIdx.x * (F * L);
+    if constexpr (sizeof(T) == 1) {
+        if (in_vec && ((off | P) & 3) == 0) {
+            const int f = f0 + F * threadIdx.x;
+            if (f + F <= hop) {
+                pcm_lane_frames<T, C, true>(in + (long long)f * C, row + f, row + P + f);
+            } else {
+                for (int g = f; g < hop; ++g) {
+                    const float o = pcm_one_frame<T, C>(in + (long long)g * C);
+                    row[g] = o;
+                    row[P + g] = o;
+                }
             }
+            return;
+        }
+    } else if (in_vec && ((off | P) & 3) == 0 && f0 + F * L <= hop) {
+        const int f = f0 + F * threadIdx.x;
+        pcm_lane_frames<T, C, true>(in + (long long)f * C, row + f, row + P + f);
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < F; ++t) {
+        const int f = f0 + t * L + threadIdx.x;
+        if (f < hop) {
+            const float o = pcm_one_frame<T, C>(in + (long long)f * C);
+            row[f] = o;
+            row[P + f] = o;
         }
     }
 }
 
 template <typename T>
-static void launch_scatter_pcm(int channels, dim3 grid, hipStream_t st, const void* src, long long bstride,
+static void launch_scatter_pcm(int channels, int rows, hipStream_t st, const void* src, long long bstride,
                                float* buf, long long pitch, int hop, int P, int in_vec, const DzRowList& rl) {
     const T* b = reinterpret_cast<const T*>(src);
+    constexpr int L = pcm_block_lanes<T>();
+    constexpr int per_block = L * (int)(16 / sizeof(T));
+    const dim3 grid((hop + per_block - 1) / per_block, rows);
 #define DZ_PCM_CASE(C)                                                                                        \
     case C:                                                                                                   \
-        hipLaunchKernelGGL((ring_scatter_pcm_kernel<T, C>), grid, dim3(256), 0, st, b, bstride, buf, pitch, hop, P, \
+        hipLaunchKernelGGL((ring_scatter_pcm_kernel<T, C>), grid, dim3(L), 0, st, b, bstride, buf, pitch, hop, P, \
                            in_vec, rl);                                                                       \
         break;
     switch (channels) {
@@ -242,6 +304,71 @@ static void launch_scatter_pcm(int channels, dim3 grid, hipStream_t st, const vo
         DZ_PCM_CASE(5) DZ_PCM_CASE(6) DZ_PCM_CASE(7) DZ_PCM_CASE(8)
     }
 #undef DZ_PCM_CASE
+}
+
+static long long pcm_value_bytes(int format) {
+    return format == DZ_PCM_F32 || format == DZ_PCM_S32 ? 4 : format == DZ_PCM_S16 ? 2 : 1;
+}
+
+static bool pcm_format_known(int format) { return format >= DZ_PCM_F32 && format <= DZ_PCM_ALAW; }
+
+// ---------------------------------------------------------------------------
+// dz_pcm_decode: the push kernel's per-frame function over ONE contiguous device buffer, without a ring (files,
+// tests, functional.decode_pcm).  A lane takes F frames with 16-byte loads and stores where both buffers are
+// 16-byte aligned and its frames lie inside the buffer, single frames otherwise: the same bits either way.
+// ---------------------------------------------------------------------------
+template <typename T, int C>
+__global__ __launch_bounds__(256) void pcm_decode_kernel(const T* __restrict__ src, float* __restrict__ dst,
+                                                         long long n, int vec) {
+    constexpr int F = 16 / sizeof(T);
+    const long long f = ((long long)blockIdx.x * 256 + threadIdx.x) * F;
+    if (f >= n) return;
+    if (vec && f + F <= n) {
+        pcm_lane_frames<T, C, false>(src + f * C, dst + f, nullptr);
+    } else {
+        const long long end = f + F < n ? f + F : n;
+        for (long long g = f; g < end; ++g) dst[g] = pcm_one_frame<T, C>(src + g * C);
+    }
+}
+
+template <typename T>
+static void launch_pcm_decode(int channels, hipStream_t st, const void* src, float* dst, long long n, int vec) {
+    const T* b = reinterpret_cast<const T*>(src);
+    constexpr long long per_block = 256 * (16 / sizeof(T));
+    const dim3 grid((unsigned)((n + per_block - 1) / per_block));
+#define DZ_PCM_CASE(C)                                                                                        \
+    case C:                                                                                                   \
+        hipLaunchKernelGGL((pcm_decode_kernel<T, C>), grid, dim3(256), 0, st, b, dst, n, vec);                \
+        break;
+    switch (channels) {
+        DZ_PCM_CASE(1) DZ_PCM_CASE(2) DZ_PCM_CASE(3) DZ_PCM_CASE(4)
+        DZ_PCM_CASE(5) DZ_PCM_CASE(6) DZ_PCM_CASE(7) DZ_PCM_CASE(8)
+    }
+#undef DZ_PCM_CASE
+}
+
+extern "C" int dz_pcm_decode(dz_ctx* ctx, const void* d_src, long long n_frames, int format, int channels,
+                             float* d_dst, void* stream) {
+    DZ_REQUIRE(ctx && d_src && d_dst, "dz_pcm_decode: NULL argument");
+    DZ_REQUIRE(pcm_format_known(format), "dz_pcm_decode: unknown format %d", format);
+    DZ_REQUIRE(channels >= 1 && channels <= 8, "dz_pcm_decode: %d channels (1 .. 8)", channels);
+    DZ_REQUIRE(n_frames >= 1 && n_frames <= (1LL << 40), "dz_pcm_decode: %lld frames", n_frames);
+    const long long esz = pcm_value_bytes(format);
+    DZ_REQUIRE((uintptr_t)d_src % esz == 0 && ((uintptr_t)d_dst & 3) == 0,
+               "dz_pcm_decode: buffers must be aligned to one value");
+    DZ_HIP(hipSetDevice(ctx->device));
+    const int vec = (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+        case DZ_PCM_F32: launch_pcm_decode<float>(channels, st, d_src, d_dst, n_frames, vec); break;
+        case DZ_PCM_S16: launch_pcm_decode<short>(channels, st, d_src, d_dst, n_frames, vec); break;
+        case DZ_PCM_U8: launch_pcm_decode<pcm_u8>(channels, st, d_src, d_dst, n_frames, vec); break;
+        case DZ_PCM_S32: launch_pcm_decode<int>(channels, st, d_src, d_dst, n_frames, vec); break;
+        case DZ_PCM_ULAW: launch_pcm_decode<pcm_ulaw>(channels, st, d_src, d_dst, n_frames, vec); break;
+        default: launch_pcm_decode<pcm_alaw>(channels, st, d_src, d_dst, n_frames, vec); break;
+    }
+    DZ_HIP(hipGetLastError());
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -314,7 +441,7 @@ extern "C" int dz_ring_reset_row(dz_ring* r, int row) {
 // dz_ring_push_rows_pcm; float blocks of a ring with hop % 4 != 0 come here too).  The caller has checked `rows`.
 static int ring_push_pcm(dz_ring* r, const void* block, long long stride_bytes, int format, int channels,
                          int on_device, const int* rows, int k, hipStream_t st) {
-    const long long esz = format == DZ_PCM_S16 ? 2 : 4;
+    const long long esz = pcm_value_bytes(format);
     const long long row_bytes = (long long)r->hop * channels * esz;
     DZ_REQUIRE(stride_bytes >= row_bytes && stride_bytes % esz == 0 && (uintptr_t)block % esz == 0,
                "ring push: rows of the block must be >= hop * channels values apart and aligned to one value");
@@ -347,7 +474,6 @@ static int ring_push_pcm(dz_ring* r, const void* block, long long stride_bytes, 
         sstride = spitch;
     }
     const int in_vec = ((uintptr_t)src & 15) == 0 && (sstride & 15) == 0;
-    const int per_block = 256 * (int)(16 / esz);
     for (int j0 = 0; j0 < k; j0 += 64) {
         const int m = k - j0 < 64 ? k - j0 : 64;
         DzRowList rl;
@@ -355,12 +481,16 @@ static int ring_push_pcm(dz_ring* r, const void* block, long long stride_bytes, 
             rl.row[j] = rows[j0 + j];
             rl.off[j] = r->rpos[rows[j0 + j]];
         }
-        const dim3 grid((r->hop + per_block - 1) / per_block, m);
         const char* s0 = src + (long long)j0 * sstride;
-        if (format == DZ_PCM_S16)
-            launch_scatter_pcm<short>(channels, grid, st, s0, sstride / esz, r->buf, r->pitch, r->hop, r->P, in_vec, rl);
-        else
-            launch_scatter_pcm<float>(channels, grid, st, s0, sstride / esz, r->buf, r->pitch, r->hop, r->P, in_vec, rl);
+        const long long bs = sstride / esz;
+        switch (format) {
+            case DZ_PCM_F32: launch_scatter_pcm<float>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
+            case DZ_PCM_S16: launch_scatter_pcm<short>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
+            case DZ_PCM_U8: launch_scatter_pcm<pcm_u8>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
+            case DZ_PCM_S32: launch_scatter_pcm<int>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
+            case DZ_PCM_ULAW: launch_scatter_pcm<pcm_ulaw>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
+            default: launch_scatter_pcm<pcm_alaw>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
+        }
         DZ_HIP(hipGetLastError());
     }
     for (int j = 0; j < k; ++j) {
@@ -384,7 +514,7 @@ static int ring_check_rows(const dz_ring* r, const int* rows, int k, const char*
 extern "C" int dz_ring_push_rows_pcm(dz_ring* r, const void* block, long long block_stride_bytes, int format,
                                      int channels, int on_device, const int* rows, int k, void* stream) {
     DZ_REQUIRE(r && block && rows, "dz_ring_push_rows_pcm: NULL argument");
-    DZ_REQUIRE(format == DZ_PCM_F32 || format == DZ_PCM_S16, "dz_ring_push_rows_pcm: unknown format %d", format);
+    DZ_REQUIRE(pcm_format_known(format), "dz_ring_push_rows_pcm: unknown format %d", format);
     DZ_REQUIRE(channels >= 1 && channels <= 8, "dz_ring_push_rows_pcm: %d channels (1 .. 8)", channels);
     int rc = ring_check_rows(r, rows, k, "dz_ring_push_rows_pcm");
     if (rc) return rc;

@@ -2,7 +2,8 @@
 
 Same names and results as ``/root/reference/src/diart/functional.py`` (:6-13
 ``overlapped_speech_penalty``, :16-27 ``normalize_embeddings``), plus ``resample`` and ``adjust_volume``, the
-functional forms of the ``Resample`` and ``AdjustVolume`` blocks.  Inputs may live on the host
+functional forms of the ``Resample`` and ``AdjustVolume`` blocks, and ``decode_pcm``, the push kernel's sample
+conversion over one buffer.  Inputs may live on the host
 (the reference runs these on CPU tensors) or on the GPU; the result comes back on the device
 of the input.  There is no torch fallback: without ``libdiart_amd.so`` and a GPU they raise.
 """
@@ -189,3 +190,42 @@ def adjust_volume(waveform, volume_in_db: float, device: Optional[torch.device] 
         x = x.contiguous()
     y = adjust_volume_rows(x, target).reshape(*lead, L)
     return y if src == dev else y.to(src)
+
+
+def decode_pcm(raw, input_format: str, channels: int = 1, device: Optional[torch.device] = None) -> torch.Tensor:
+    """Interleaved frames of ``channels`` values of ``input_format`` (``diart_amd.pcm``: "f32" | "s16" | "u8" | "s32" |
+    "ulaw" | "alaw") -> mono float32 on the GPU, by the push kernel's per-frame function (``dz_pcm_decode``): the bits
+    a ``StreamServer`` with that format hands its models.  ``raw``: a numpy array or tensor of the format's dtype, 1-D
+    or ``(n, channels)``, or a bytes-like object of little-endian values; whole frames."""
+    import numpy as np
+    from .pcm import PCM_FORMATS
+    if input_format not in PCM_FORMATS:
+        raise ValueError(f"decode_pcm: input_format={input_format!r} (expected one of {tuple(PCM_FORMATS)})")
+    if not (isinstance(channels, int) and 1 <= channels <= 8):
+        raise ValueError(f"decode_pcm: channels={channels!r} (expected 1 .. 8)")
+    code, dtype = PCM_FORMATS[input_format]
+    tdtype = torch.from_numpy(np.zeros(0, dtype)).dtype
+    if isinstance(raw, torch.Tensor):
+        x = raw
+    elif isinstance(raw, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(raw))
+    else:
+        view = memoryview(raw).cast("B")
+        if len(view) % dtype.itemsize:
+            raise ValueError(f"decode_pcm: {len(view)} bytes are not whole {input_format} values")
+        x = torch.from_numpy(np.frombuffer(view, dtype=dtype).copy())
+    if x.dtype != tdtype:
+        raise ValueError(f"decode_pcm: {x.dtype} values for input_format={input_format!r} (expected {dtype.name})")
+    if not (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == channels)):
+        raise ValueError(f"decode_pcm: values of shape {tuple(x.shape)} (expected 1-D or (n, {channels}))")
+    if x.numel() == 0 or x.numel() % channels:
+        raise ValueError(f"decode_pcm: {x.numel()} values are not a whole number (>= 1) of {channels}-channel frames")
+    dev = _gpu(x.device if x.device.type == "cuda" or device is None else torch.device(device))
+    x = x.to(dev).contiguous().reshape(-1)
+    frames = x.numel() // channels
+    out = torch.empty(frames, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().dz_pcm_decode(_lib.context(dev.index), x.data_ptr(), frames, code, int(channels),
+                                             out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dz_pcm_decode")
+        # `x` may be a temporary copy: its memory is reused in stream order by the caching allocator
+    return out

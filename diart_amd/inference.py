@@ -31,37 +31,64 @@ FilePath = Union[str, Path]
 
 
 # ------------------------------------------------------------------------------------- audio
-def read_wav_into(path: FilePath, alloc, padding_of, block_duration: float = 0.5):
-    """``padded_file(read_wav(path))`` in ONE pass: decode the PCM samples straight into
-    ``alloc(n_total)`` (e.g. a pinned upload buffer) at their padded position.  ``padding_of(duration
-    seconds) -> (left, right)`` seconds.  -> (array, sample rate, (left, right)); same samples as the
-    two-step form (the 2^-15 / 2^-31 / 2^-7 scalings are exact in float32)."""
-    with wave.open(str(path), "rb") as f:
-        sr, nch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-        raw = f.readframes(n)
-    padding = padding_of(n / sr)
-    left, right = (int(np.rint(p * sr)) for p in padding)
-    size = int(np.rint(block_duration * sr))
-    total = left + n + right
-    out = alloc(-(-total // size) * size)
-    out[:left] = 0.0
-    out[left + n:] = 0.0
-    dst = out[left:left + n]
-    if nch == 1 and width == 2:
-        np.multiply(np.frombuffer(raw, dtype="<i2"), np.float32(1.0 / 32768.0), out=dst, dtype=np.float32, casting="unsafe")
-    else:
-        x, _ = read_wav(path)
-        dst[:] = x
-    return out, sr, padding
+_WAVE_TAGS = {1: "integer PCM", 3: "IEEE float", 6: "A-law", 7: "mu-law"}
 
 
-def read_wav(path: FilePath) -> Tuple[np.ndarray, int]:
-    """PCM WAV (8/16/24/32-bit integer) -> (mono float32 in [-1, 1], sample rate); channels are
-    averaged like ``AudioLoader(mono=True)`` (reference ``audio.py:36-40``)."""
-    with wave.open(str(path), "rb") as f:
-        sr, nch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-        raw = f.readframes(n)
-    if width == 2:
+def _riff(path: FilePath, with_data: bool = True) -> dict:
+    """The ``fmt `` and ``data`` chunks of a RIFF/WAVE file: format tag (the sub-format's of an extensible header),
+    channels, rate, bits per value, the number of whole frames and, ``with_data``, their bytes.  Unknown chunks are
+    skipped, an odd-sized chunk is followed by its pad byte.  ``ValueError`` names the file and what is wrong with it;
+    the file is only ever read as data."""
+    import struct
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise ValueError(f"{path}: not a RIFF/WAVE file")
+        end = f.seek(0, 2)
+        pos, fmt = 12, None
+        while pos + 8 <= end:
+            f.seek(pos)
+            cid, size = struct.unpack("<4sI", f.read(8))
+            if cid == b"fmt ":
+                body = f.read(min(size, 40))
+                if len(body) < 16:
+                    raise ValueError(f"{path}: fmt chunk of {len(body)} bytes")
+                tag, nch, sr, _, _, bits = struct.unpack("<HHIIHH", body[:16])
+                if tag == 0xFFFE:                      # extensible: the tag is the first two bytes of the sub-format
+                    if len(body) < 26:
+                        raise ValueError(f"{path}: extensible fmt chunk of {len(body)} bytes")
+                    tag, = struct.unpack("<H", body[24:26])
+                fmt = (tag, nch, sr, bits)
+            elif cid == b"data":
+                if fmt is None:
+                    raise ValueError(f"{path}: data chunk before the fmt chunk")
+                tag, nch, sr, bits = fmt
+                if tag not in _WAVE_TAGS:
+                    raise ValueError(f"{path}: unsupported WAVE format tag {tag} (0x{tag:04x}); supported: "
+                                     + ", ".join(f"{t} ({n})" for t, n in _WAVE_TAGS.items()))
+                if bits not in {1: (8, 16, 24, 32), 3: (32, 64), 6: (8,), 7: (8,)}[tag]:
+                    raise ValueError(f"{path}: {bits}-bit {_WAVE_TAGS[tag]} (format tag {tag}) is not supported")
+                if nch < 1 or sr < 1:
+                    raise ValueError(f"{path}: {nch} channels at {sr} Hz")
+                frame = nch * (bits // 8)
+                n = min(size, end - pos - 8) // frame          # (a streamed file's size field may exceed the file)
+                info = {"tag": tag, "channels": nch, "rate": sr, "width": bits // 8, "frames": n}
+                if with_data:
+                    info["data"] = f.read(n * frame)
+                return info
+            pos += 8 + size + (size & 1)
+    raise ValueError(f"{path}: no data chunk")
+
+
+def _decode_wav(path: FilePath, info: dict) -> np.ndarray:
+    """The samples of ``_riff(path)`` as mono float32."""
+    raw, nch, width, tag = info["data"], info["channels"], info["width"], info["tag"]
+    if tag == 3:
+        x = np.frombuffer(raw, dtype="<f4" if width == 4 else "<f8").astype(np.float32)
+    elif tag in (6, 7):
+        from .pcm import pcm_to_float
+        x = pcm_to_float(np.frombuffer(raw, dtype=np.uint8), "alaw" if tag == 6 else "ulaw")
+    elif width == 2:
         x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
     elif width == 4:
         x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
@@ -77,7 +104,40 @@ def read_wav(path: FilePath) -> Tuple[np.ndarray, int]:
     else:
         raise ValueError(f"{path}: unsupported sample width {width}")
     x = x.reshape(-1, nch)
-    return (x.mean(axis=1) if nch > 1 else x[:, 0]).astype(np.float32), sr
+    return (x.mean(axis=1) if nch > 1 else x[:, 0]).astype(np.float32)
+
+
+def read_wav_into(path: FilePath, alloc, padding_of, block_duration: float = 0.5):
+    """``padded_file(read_wav(path))`` in ONE pass: decode the samples straight into
+    ``alloc(n_total)`` (e.g. a pinned upload buffer) at their padded position.  ``padding_of(duration
+    seconds) -> (left, right)`` seconds.  -> (array, sample rate, (left, right)); same samples as the
+    two-step form (the 2^-15 / 2^-31 / 2^-7 scalings are exact in float32)."""
+    info = _riff(path)
+    sr, nch, width, n = info["rate"], info["channels"], info["width"], info["frames"]
+    padding = padding_of(n / sr)
+    left, right = (int(np.rint(p * sr)) for p in padding)
+    size = int(np.rint(block_duration * sr))
+    total = left + n + right
+    out = alloc(-(-total // size) * size)
+    out[:left] = 0.0
+    out[left + n:] = 0.0
+    dst = out[left:left + n]
+    if nch == 1 and width == 2 and info["tag"] == 1:
+        np.multiply(np.frombuffer(info["data"], dtype="<i2"), np.float32(1.0 / 32768.0), out=dst, dtype=np.float32,
+                    casting="unsafe")
+    else:
+        dst[:] = _decode_wav(path, info)
+    return out, sr, padding
+
+
+def read_wav(path: FilePath) -> Tuple[np.ndarray, int]:
+    """WAV -> (mono float32, sample rate): integer PCM (8/16/24/32-bit, in [-1, 1)), IEEE float (32-bit; 64-bit cast to
+    float32), G.711 A-law and mu-law (``diart_amd.pcm``), plain or in an extensible header; another format tag is a
+    ``ValueError`` that names it.  Channels are averaged like ``AudioLoader(mono=True)`` (reference
+    ``audio.py:36-40``).  A RIFF reader of the project's own (``_riff``): the standard library's ``wave`` refuses
+    everything but integer PCM."""
+    info = _riff(path)
+    return _decode_wav(path, info), info["rate"]
 
 
 def resample_file(waveform: np.ndarray, orig_freq: int, new_freq: int, device=None) -> np.ndarray:
@@ -92,8 +152,7 @@ def read_wav_resampled_into(path: FilePath, alloc, padding_of, block_duration: f
     """``read_wav_into`` at the pipeline's rate: a file at another rate is decoded, resampled as a whole on the GPU,
     then padded (``padding_of`` gets the file's own duration, as the reference's ``get_file_padding`` does) and
     blocked at ``sample_rate`` into ``alloc``.  A file at ``sample_rate`` takes ``read_wav_into`` itself."""
-    with wave.open(str(path), "rb") as f:
-        sr = f.getframerate()
+    sr = _riff(path, with_data=False)["rate"]
     if sr == sample_rate:
         return read_wav_into(path, alloc, padding_of, block_duration)
     x, sr = read_wav(path)
@@ -119,8 +178,8 @@ def write_wav(path: FilePath, samples: np.ndarray, sample_rate: int = 16000) -> 
 
 
 def wav_duration(path: FilePath) -> float:
-    with wave.open(str(path), "rb") as f:
-        return f.getnframes() / float(f.getframerate())
+    info = _riff(path, with_data=False)
+    return info["frames"] / float(info["rate"])
 
 
 def file_blocks(waveform: np.ndarray, sample_rate: int, padding: Tuple[float, float] = (0, 0),

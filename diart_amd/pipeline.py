@@ -43,10 +43,12 @@ from . import _lib
 from .blocks.aggregation import BatchedOutputTail
 from .blocks.clustering import BatchedSpeakerClustering
 from .features import Annotation, Segment
+from .pcm import PCM_FORMATS
 from .models import HipEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _HipGroupsEmbedding, _as_rows
 
-# sample formats of raw client audio (``dz_ring_push_rows_pcm``: DZ_PCM_F32 / DZ_PCM_S16, little-endian)
-PCM_F32, PCM_S16 = 0, 1
+# sample formats of raw client audio (``dz_ring_push_rows_pcm``: the DZ_PCM_* constants; definitions in diart_amd.pcm)
+PCM_F32, PCM_S16, PCM_U8, PCM_S32, PCM_ULAW, PCM_ALAW = range(6)
+_PCM_OF_DTYPE = {torch.float32: "f32", torch.int16: "s16", torch.int32: "s32"}      # what push_rows infers
 
 # lanes of a throughput engine (>= 64 streams per step on the matrix-core recurrence): profiles/r06*_lanes_grid.json
 THROUGHPUT_LANES = 6
@@ -118,25 +120,34 @@ class AudioRing:
         self._readers.append(evs)
 
     # ---- streams that advance at their own pace (StreamServer) -------------------------------
-    def push_rows(self, block: torch.Tensor, rows: Sequence[int], channels: int = 1) -> None:
+    def push_rows(self, block: torch.Tensor, rows: Sequence[int], channels: int = 1, format: Optional[str] = None) -> None:
         """Row j of ``block`` is the next block of stream ``rows[j]`` (each row keeps its own write position).
-        ``block``: (k, hop) float32 — or raw client audio, ``torch.float32`` / ``torch.int16`` of shape
-        (k, hop * channels) or (k, hop, channels) with interleaved frames, which the push kernel converts
-        (int16: ``v / 32768``) and averages over the channels (``dz_ring_push_rows_pcm``).  Enqueued on the current
-        HIP stream; a pinned host block is read in place by the GPU and must stay untouched until that stream has
-        passed this point."""
+        ``block``: (k, hop) float32 — or raw client audio of shape (k, hop * channels) or (k, hop, channels) with
+        interleaved frames, which the push kernel converts (int16: ``v / 32768``; every format: ``diart_amd.pcm``)
+        and averages over the channels (``dz_ring_push_rows_pcm``).  ``format=None`` infers the format from the dtype
+        (``torch.float32``, ``torch.int16``, ``torch.int32``); a ``torch.uint8`` block means nothing by itself and
+        needs ``format="u8" | "ulaw" | "alaw"``.  Enqueued on the current HIP stream; a pinned host block is read in
+        place by the GPU and must stay untouched until that stream has passed this point."""
         k = len(rows)
         mode = 1 if block.is_cuda else (2 if block.is_pinned() and _lib.exp_env("DZ_RING_ZERO_COPY", "1") != "0" else 0)
         arr = (C.c_int * k)(*[int(r) for r in rows])
         cur = torch.cuda.current_stream(self.device).cuda_stream
-        if block.dtype == torch.float32 and channels == 1 and block.dim() == 2 and self.hop % 4 == 0:
+        if block.dtype == torch.float32 and channels == 1 and block.dim() == 2 and self.hop % 4 == 0 \
+                and format in (None, "f32"):
             assert tuple(block.shape) == (k, self.hop) and block.stride(1) == 1
             _lib.check(self._lib.dz_ring_push_rows(self._h, block.data_ptr(), block.stride(0), mode, arr, k, cur),
                        "dz_ring_push_rows")
         else:
-            fmt = {torch.float32: PCM_F32, torch.int16: PCM_S16}.get(block.dtype)
-            if fmt is None:
-                raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks (expected float32 or int16)")
+            if format is None:
+                format = _PCM_OF_DTYPE.get(block.dtype)
+                if format is None:
+                    raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks (expected float32, int16 or int32; "
+                                    "uint8 blocks need format='u8' | 'ulaw' | 'alaw')")
+            if format not in PCM_FORMATS:
+                raise ValueError(f"AudioRing.push_rows: format={format!r} (expected one of {tuple(PCM_FORMATS)})")
+            fmt, dtype = PCM_FORMATS[format]
+            if torch.from_numpy(np.zeros(0, dtype)).dtype != block.dtype:
+                raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks for format={format!r} (expected {dtype.name})")
             if block.dim() == 3:
                 assert tuple(block.shape) == (k, self.hop, channels) and block.stride(2) == 1 \
                     and block.stride(1) == channels, "frames of a (k, hop, channels) block must be contiguous"

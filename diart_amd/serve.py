@@ -24,8 +24,10 @@ uploads only the NEW 500 ms block of each stream that has one (32 KB instead of 
 reference moves per chunk, ``blocks/segmentation.py:47``) and assembles the batch of windows on the
 device.  ``device_rings=False`` (and any custom ``engine``) keeps the windows on the host instead.
 
-Clients may send what they have: ``input_format="s16"`` (16-bit PCM) and ``input_channels`` (interleaved frames,
-averaged like the reference's loader, ``audio.py:32-34``).  In ring mode the raw blocks are uploaded as they came
+Clients may send what they have: ``input_format`` ``"s16"`` (16-bit PCM), ``"u8"``, ``"s32"``, ``"ulaw"`` or ``"alaw"``
+(G.711, one byte per sample: telephone audio, usually with ``input_sample_rate=8000``; the definitions are in
+``diart_amd.pcm``) and ``input_channels`` (interleaved frames, averaged like the reference's loader,
+``audio.py:32-34``).  In ring mode the raw blocks are uploaded as they came
 and the push kernel converts and averages them (``dz_ring_push_rows_pcm``); the host modes do the same arithmetic
 in numpy (``pcm_to_mono``), so every mode hands the models identical float32 windows.  ``device_rings="all"``
 also uses rings where a block is not a multiple of 4 samples (44.1 kHz, 22.05 kHz).
@@ -52,27 +54,11 @@ from .blocks.aggregation import BatchedOutputTail
 from .features import Annotation
 from .functional import _target_db, adjust_volume, adjust_volume_rows, resampler
 from .models import HipWeSpeakerEmbedding
+from .pcm import INPUT_FORMATS, pcm_to_mono  # noqa: F401  (INPUT_FORMATS: name -> dtype of the values clients push)
 from .pipeline import AudioRing, StreamBatch, VadBatch, WeSpeakerBatch
 
 PIPELINES = ("diarization", "vad")
-INPUT_FORMATS = {"f32": np.dtype("<f4"), "s16": np.dtype("<i2")}      # name -> dtype of the values clients push
 MAX_INPUT_CHANNELS = 8
-
-
-def pcm_to_mono(values: np.ndarray, input_format: str = "f32", channels: int = 1) -> np.ndarray:
-    """Interleaved client audio -> mono float32, the arithmetic of ``dz_ring_push_rows_pcm`` operation for operation
-    (all in float32): int16 ``v -> float(v) * (1 / 32768)`` (exact, what ``read_wav`` does), then for several channels
-    ``((c0 + c1) + c2 ...) / channels``.  One float32 channel is returned as it is."""
-    x = np.asarray(values).reshape(-1)
-    if input_format == "s16":
-        x = x.astype(np.float32) * np.float32(1.0 / 32768.0)
-    if channels == 1:
-        return x
-    frames = x.reshape(-1, channels)
-    total = frames[:, 0].copy()
-    for c in range(1, channels):
-        total = total + frames[:, c]
-    return total / np.float32(channels)
 
 
 class _Stream:
@@ -247,11 +233,12 @@ class StreamServer:
     def _as_values(self, samples) -> np.ndarray:
         """``samples`` as a 1-D array of the input dtype; another kind of number is refused, not cast."""
         x = np.asarray(samples)
-        if self.input_format == "s16":
-            if x.dtype != np.int16:
-                raise ValueError(f"push: {x.dtype} samples to a server with input_format='s16' (expected int16)")
-        elif x.dtype.kind != "f":
-            raise ValueError(f"push: {x.dtype} samples to a server with input_format='f32' (expected float32)")
+        if self.input_format == "f32":
+            if x.dtype.kind != "f":
+                raise ValueError(f"push: {x.dtype} samples to a server with input_format='f32' (expected float32)")
+        elif x.dtype != self._in_dtype:
+            raise ValueError(f"push: {x.dtype} samples to a server with input_format={self.input_format!r} "
+                             f"(expected {self._in_dtype.name})")
         if self.input_channels > 1 and not (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == self.input_channels)):
             raise ValueError(f"push: samples of shape {x.shape} (expected interleaved 1-D or (n, {self.input_channels}))")
         return np.ascontiguousarray(x, dtype=self._in_dtype).reshape(-1)
@@ -395,10 +382,10 @@ class StreamServer:
                     plane = plane[:, :self._block_values]
                 for j, (slot, b) in enumerate((u for u in uploads if len(u[1]) > r)):
                     plane[j].copy_(torch.from_numpy(b[r]))
-                if self.input_channels == 1:
+                if self.input_channels == 1 and self.input_format == "f32":
                     self.rings.push_rows(plane[:len(rows)], rows)
                 else:
-                    self.rings.push_rows(plane[:len(rows)], rows, channels=self.input_channels)
+                    self.rings.push_rows(plane[:len(rows)], rows, channels=self.input_channels, format=self.input_format)
                 if pushed is not None:
                     for slot in rows:
                         pushed[slot] = pushed.get(slot, 0) + 1

@@ -14,7 +14,8 @@ Only what that exchange needs of RFC 6455 is implemented, on the standard librar
 pong / close frames, client-to-server masking, payloads up to ``max_message`` bytes, no extensions,
 no TLS (terminate it in front).  Binary messages are accepted as raw little-endian float32 samples
 (no base64), which the reference's client does not send.  A server built with ``input_format="s16"`` /
-``input_channels=2`` takes 16-bit PCM and interleaved frames in both kinds of message instead.
+``input_channels=2`` takes 16-bit PCM and interleaved frames in both kinds of message instead; likewise ``"u8"``,
+``"s32"`` and G.711 (``"ulaw"``, ``"alaw"``: the bytes as a telephone gateway has them).
 """
 from __future__ import annotations
 
@@ -59,8 +60,9 @@ def encode_frame(opcode: int, payload: bytes, mask: Optional[bytes] = None) -> b
 
 def decode_audio(message, input_format: str = "f32", channels: int = 1) -> np.ndarray:
     """Text message: base64 of the raw bytes (``utils.decode_audio``; float32 with the defaults); binary message:
-    the bytes.  The bytes are little-endian values of ``input_format`` (``StreamServer``'s: "f32" | "s16"),
-    interleaved frames of ``channels`` values; a message holds whole frames."""
+    the bytes.  The bytes are little-endian values of ``input_format`` (``StreamServer``'s: "f32" | "s16" | "u8" |
+    "s32" | "ulaw" | "alaw": 4, 2, 1, 4, 1 and 1 bytes per value), interleaved frames of ``channels`` values; a message
+    holds whole frames."""
     raw = base64.decodebytes(message.encode("utf-8")) if isinstance(message, str) else bytes(message)
     dtype = INPUT_FORMATS[input_format]
     if len(raw) % (dtype.itemsize * channels):

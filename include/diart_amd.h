@@ -825,14 +825,28 @@ int dz_ring_push_rows(dz_ring* r, const float* block, long long block_stride, in
                       const int* rows, int k, void* stream);
 /* Raw client audio: row j of `block` holds hop interleaved frames of `channels` (1 .. 8) values of
  * `format`, rows block_stride_bytes apart.  One kernel converts, averages the channels and writes
- * the block to the ring.  The float32 sample it writes, operation for operation:
- *   DZ_PCM_S16 (little-endian): (float)v * (1.0f / 32768.0f), exact;
+ * the block to the ring.  The float32 sample it writes, operation for operation (every format is
+ * exact in float32 but for the one rounding named for DZ_PCM_S32):
+ *   DZ_PCM_S16 (int16, little-endian): (float)v * (1.0f / 32768.0f);
+ *   DZ_PCM_U8 (uint8): ((float)v - 128.0f) * (1.0f / 128.0f);
+ *   DZ_PCM_S32 (int32, little-endian): (float)v * (1.0f / 2147483648.0f); the int-to-float conversion
+ *     rounds to nearest even (0x7fffffc0 gives 1.0f), the scaling is exact;
+ *   DZ_PCM_ULAW (uint8, G.711 mu-law): (float)L * (1.0f / 32768.0f) with
+ *     u = ~b & 0xFF; t = (((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7); L = (u & 0x80) ? 0x84 - t : t - 0x84;
+ *   DZ_PCM_ALAW (uint8, G.711 A-law): (float)L * (1.0f / 32768.0f) with
+ *     a = b ^ 0x55; m = (a & 0x0F) << 4; s = (a >> 4) & 7; t = (s == 0) ? m + 8 : (m + 0x108) << (s - 1);
+ *     L = (a & 0x80) ? t : -t;
  *   channels > 1: ((c0 + c1) + c2 ...) / (float)channels, one IEEE division;
  *   DZ_PCM_F32 with one channel: the input bits (what dz_ring_push_rows writes).
- * Non-finite float input passes through (a NaN in one channel makes that frame NaN).             */
-enum { DZ_PCM_F32 = 0, DZ_PCM_S16 = 1 };
+ * Non-finite float input passes through (a NaN in one channel makes that frame NaN).  Another
+ * format value is refused.
+ * dz_pcm_decode: the same per-frame function over one contiguous device buffer of n_frames
+ * interleaved frames (d_src aligned to one value), mono float32 to d_dst, without a ring.        */
+enum { DZ_PCM_F32 = 0, DZ_PCM_S16 = 1, DZ_PCM_U8 = 2, DZ_PCM_S32 = 3, DZ_PCM_ULAW = 4, DZ_PCM_ALAW = 5 };
 int dz_ring_push_rows_pcm(dz_ring* r, const void* block, long long block_stride_bytes, int format, int channels,
                           int on_device, const int* rows, int k, void* stream);
+int dz_pcm_decode(dz_ctx* ctx, const void* d_src, long long n_frames, int format, int channels, float* d_dst,
+                  void* stream);
 int dz_ring_filled_row(const dz_ring* r, int row, int* filled);
 int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d_out, long long out_stride, void* stream);
 int dz_ring_reset_row(dz_ring* r, int row);
