@@ -43,6 +43,13 @@ class EmbWeights(C.Structure):
                 ("tw_split", vp * 5), ("tw0_split_kb", vp), ("pool_nearest", C.c_int)]
 
 
+GATHER_MAX_RUNS = 64            # DZ_GATHER_MAX_RUNS: runs one launch of dz_gather_windows carries
+
+
+class WindowRun(C.Structure):   # dz_window_run
+    _fields_ = [("src", vp), ("row0", C.c_int), ("count", C.c_int)]
+
+
 class Layer(C.Structure):
     _fields_ = [("w", vp), ("b", vp), ("s", vp), ("h", vp), ("wsplit", vp)]
 
@@ -227,11 +234,15 @@ SIGNATURES = {
     "dz_tail_reset": (C.c_int, [vp]),
     "dz_tail_destroy": (C.c_int, [vp]),
     "dz_tail_max_rows": (C.c_int, [vp]),
+    "dz_tail_speakers": (C.c_int, [vp]),
     "dz_tail_step": (C.c_int, [vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp, C.c_int, vp]),
     "dz_tail_step_batch": (C.c_int, [C.POINTER(vp), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                      C.c_int, vp, C.c_int]),
     "dz_file_step_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int,
                                      C.c_int, vp, C.c_double, vp, C.c_int, vp, vp, C.c_int]),
+    "dz_file_vad_step_batch": (C.c_int, [C.POINTER(vp), C.c_int, vp, vp, vp, C.c_int, vp, C.c_double, vp, C.c_int, vp,
+                                         C.c_int]),
+    "dz_gather_windows": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, C.c_int, vp]),
     "dz_tune_abi_size": (C.c_int, []),
     "dz_tune_plan": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp]),
     "dz_tune_replay": (C.c_int, [vp, C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),

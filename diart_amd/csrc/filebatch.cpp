@@ -76,3 +76,59 @@ extern "C" int dz_file_step_batch(dz_clu** clus, dz_tail** tails, int n_files, c
         }
     return 0;
 }
+
+// The VoiceActivityDetection sibling: no clustering, the (frames,) speech track of a window is the one "speaker" of its
+// file's aggregation state (built with speakers = 1).  Same rows, same walk, same error report.
+extern "C" int dz_file_vad_step_batch(dz_tail** tails, int n_files, const int* row0, const int* count,
+                                      const float* track, int frames, const double* chunk_start, double resolution,
+                                      double* turns_out, int max_turns, int* nturns_out, int num_threads) {
+    if (!tails || n_files < 1 || !row0 || !count || !track || !chunk_start || !turns_out || !nturns_out) {
+        dz_set_error("dz_file_vad_step_batch: NULL argument");
+        return 2;
+    }
+    if (frames < 1 || max_turns < 1) {
+        dz_set_error("dz_file_vad_step_batch: empty shape");
+        return 2;
+    }
+    for (int i = 0; i < n_files; ++i)
+        if (!tails[i] || count[i] < 0 || row0[i] < 0 || dz_tail_max_rows(tails[i]) != frames + 2 ||
+            dz_tail_speakers(tails[i]) != 1) {
+            dz_set_error("dz_file_vad_step_batch: bad handle / row range of file %d", i);
+            return 2;
+        }
+    int nt = num_threads < 1 ? 1 : num_threads;
+    if (nt > n_files) nt = n_files;
+    const size_t F = (size_t)frames;
+    // per worker: the current window's track in fp64 and the aggregated region (discarded, as above)
+    std::vector<std::vector<double>> scores(nt, std::vector<double>(F)), agg(nt, std::vector<double>(F + 2));
+    std::vector<int> rcs(nt, 0), who(nt, -1);
+    std::vector<std::string> msgs(nt);
+    auto run = [&](int worker, int i) {
+        int rows = 0;
+        double t0 = 0.0, res = 0.0;
+        for (int t = 0; t < count[i] && !rcs[worker]; ++t) {
+            const size_t r = (size_t)row0[i] + t;
+            double* s = scores[worker].data();
+            for (size_t f = 0; f < F; ++f) s[f] = (double)track[r * F + f];
+            const int rc = dz_tail_step(tails[i], s, chunk_start[r], resolution, agg[worker].data(), &rows, &t0, &res,
+                                        turns_out + r * (size_t)max_turns * 3, max_turns, nturns_out + r);
+            if (rc) {
+                rcs[worker] = rc;
+                who[worker] = i;
+                msgs[worker] = dz_last_error();
+            }
+        }
+    };
+    if (nt == 1) {
+        for (int i = 0; i < n_files && !rcs[0]; ++i) run(0, i);
+    } else {
+        dz_host_parallel(n_files, nt, run);
+    }
+    for (int t = 0; t < nt; ++t)
+        if (rcs[t]) {
+            dz_set_error("dz_file_vad_step_batch: file %d of %d failed (code %d): %s", who[t], n_files, rcs[t],
+                         msgs[t].c_str());
+            return rcs[t];
+        }
+    return 0;
+}

@@ -220,6 +220,7 @@ extern "C" int dz_tail_destroy(dz_tail* t) {
     return 0;
 }
 extern "C" int dz_tail_max_rows(const dz_tail* t) { return t ? t->F + 2 : 0; }
+extern "C" int dz_tail_speakers(const dz_tail* t) { return t ? t->G : 0; }
 
 static int tail_fail(const char* who, int rc) {
     if (rc == 4)

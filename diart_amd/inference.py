@@ -309,11 +309,62 @@ class StreamingInference:
         return self.accumulator.get_prediction()
 
 
+# Which forms of the file batch `Benchmark` takes WITHOUT being asked (``concurrent_files=None``): a form whose file batch
+# measured slower than its loop stays on the loop unless ``concurrent_files`` is given (profiles/r24a_file_batch_models.json,
+# README "File batches for every model").
+FILE_BATCH_BY_DEFAULT = {"xvector": True, "wespeaker": True, "groups": True, "vad": True}
+
+
+def file_batch_kind(pipeline_class: type, segmentation_type: type, embedding_type: Optional[type], batch_size: int,
+                    concurrent_files: int = 16, device_type: str = "cuda", explicit: bool = True) -> Optional[str]:
+    """Which ``FileBatch`` form runs (pipeline class, model classes, batch size), or None for the one-file-at-a-time
+    loop.  No device is touched: the arguments are classes, numbers and a device TYPE.
+
+        SpeakerDiarization   HipSegmentation + HipEmbedding (pyannote/embedding)            "xvector"
+        SpeakerDiarization   HipSegmentation + HipWeSpeakerEmbedding                        "wespeaker"
+        SpeakerDiarization   HipSegmentation + a groups-form embedding, batch_size == 1     "groups"
+        VoiceActivityDetection   HipSegmentation                                            "vad"
+
+    A groups-form model (ECAPA, speechbrain x-vector, TitaNet-L, speechbrain ResNet, mel-spectrogram ECAPA) pads and
+    normalises a row by the geometry of the rows it is batched with: at ``batch_size=32`` the loop's embeddings depend on
+    the batch, as the reference's do, while ``GroupsBatch`` embeds each chunk's K rows alone — the loop at
+    ``batch_size=1``.  Only there do the two agree, so only there is the file batch taken; any other batch size keeps the
+    numbers it gives today.
+
+    None as well for ``concurrent_files <= 0``, a device that is not "cuda", a SUBCLASS of either pipeline (it may
+    override any stage), models that are not exactly these classes, and — when ``concurrent_files`` was not given
+    (``explicit=False``) — a form that ``FILE_BATCH_BY_DEFAULT`` leaves on the loop."""
+    from .blocks.diarization import SpeakerDiarization
+    from .blocks.vad import VoiceActivityDetection
+    from .models import HipEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _HipGroupsEmbedding
+    if int(concurrent_files) <= 0 or device_type != "cuda" or segmentation_type is not HipSegmentation:
+        return None
+    kind = None
+    if pipeline_class is VoiceActivityDetection:
+        kind = "vad"
+    elif pipeline_class is SpeakerDiarization and isinstance(embedding_type, type):
+        if embedding_type is HipEmbedding:
+            kind = "xvector"
+        elif embedding_type is HipWeSpeakerEmbedding:
+            kind = "wespeaker"
+        elif issubclass(embedding_type, _HipGroupsEmbedding) and int(batch_size) == 1:
+            kind = "groups"
+    if kind is not None and not explicit and not FILE_BATCH_BY_DEFAULT[kind]:
+        return None
+    return kind
+
+
 class Benchmark:
     """Run a pipeline class on every WAV of ``speech_path``; write ``<uri>.rttm`` files to
     ``output_path`` and / or score against ``reference_path/<uri>.rttm``.  Same constructor and call
     as the reference's; the report is the metric object (``abs(metric)`` = aggregate rate,
-    ``metric.report()`` = the per-file table) instead of a pandas frame of pyannote.metrics."""
+    ``metric.report()`` = the per-file table) instead of a pandas frame of pyannote.metrics.
+
+    ``concurrent_files`` files of this process share one GPU batch (``FileBatch``) where ``file_batch_kind`` names a
+    form for the pipeline and its models: ``SpeakerDiarization`` with pyannote/embedding, with the WeSpeaker ResNet34, or
+    (at ``batch_size=1`` only) with a groups-form embedding, and ``VoiceActivityDetection``.  Everything else — and
+    everything at ``concurrent_files=0`` — runs the reference's loop, one file at a time in batches of ``batch_size``
+    windows.  The RTTM files are the same either way; ``last_path`` says which path ran."""
 
     def __init__(self, speech_path: FilePath, reference_path: Optional[FilePath] = None,
                  output_path: Optional[FilePath] = None, show_progress: bool = False,
@@ -332,10 +383,14 @@ class Benchmark:
             self.output_path.mkdir(parents=True, exist_ok=True)
         self.show_progress, self.show_report, self.batch_size = show_progress, show_report, batch_size
         # files of this process that share one GPU batch (``FileBatch``); None = 16, 0 = the reference's
-        # one-file-at-a-time loop.  Only the HIP x-vector diarization pipeline has the batched path; anything else
-        # falls back to the loop.
-        from .config import setting
+        # one-file-at-a-time loop.  `file_batch_kind` says which pipelines and models have the batched path; anything
+        # else falls back to the loop.
+        from .config import overrides, setting
         self.concurrent_files = int(setting("concurrent_files", concurrent_files, 16, int))
+        self._files_given = concurrent_files is not None or overrides().get("concurrent_files") is not None
+        # windows per GPU step of the file batch (at least `batch_size`).  An attribute, not an argument: the engine under
+        # the files allocates by it (a 64-row ECAPA engine holds about 6 GB per lane), so a small job may lower it
+        self.file_batch_rows = 64
         self.last_path = None      # "file_batch" | "one_file_at_a_time": which path the last call took
 
     def get_file_paths(self) -> List[Path]:
@@ -358,39 +413,47 @@ class Benchmark:
         return pred
 
     def file_batch(self, pipeline_class: type, config):
-        """A ``FileBatch`` for (pipeline_class, config), or None when this combination has to go
-        through the one-file-at-a-time loop (custom pipeline classes, non-HIP or ECAPA models, CPU)."""
+        """A ``FileBatch`` for (pipeline_class, config), or None when this combination has to go through the
+        one-file-at-a-time loop: the rule is ``file_batch_kind`` (custom pipeline classes, non-HIP models, CPU devices,
+        groups-form embeddings at a batch size other than 1, ``concurrent_files=0``)."""
         from .blocks.diarization import SpeakerDiarization
-        from .models import HipEmbedding, HipSegmentation
-        if self.concurrent_files <= 0 or pipeline_class is not SpeakerDiarization:
+        from .blocks.vad import VoiceActivityDetection
+        if self.concurrent_files <= 0 or pipeline_class not in (SpeakerDiarization, VoiceActivityDetection):
+            return None                 # (a custom pipeline's config may have neither models nor a device)
+        if getattr(getattr(config, "device", None), "type", "cpu") != "cuda":
             return None
-        if getattr(config.device, "type", "cpu") != "cuda":
-            return None
-        seg, emb = config.segmentation, config.embedding
+        seg, emb = config.segmentation, getattr(config, "embedding", None)
         seg.load()
-        emb.load()
-        if type(seg.model) is not HipSegmentation or type(emb.model) is not HipEmbedding:
+        if emb is not None:
+            emb.load()
+        kind = file_batch_kind(pipeline_class, type(seg.model), None if emb is None else type(emb.model),
+                               self.batch_size, self.concurrent_files, config.device.type, self._files_given)
+        if kind is None:
             return None
         from .pipeline import FileBatch
-        # one engine per (models, hyper-parameters): its scratch arenas (~1 GB) and pinned slots are
+        # one engine per (form, models, hyper-parameters): its scratch arenas (1 - 12 GB) and pinned slots are
         # allocated once, not per call
-        key = (id(seg.model), id(emb.model), config.tau_active, config.rho_update, config.delta_new, config.gamma,
-               config.beta, config.max_speakers, config.normalize_embedding_weights, config.duration, config.step,
-               config.latency, config.sample_rate, str(config.device), self.batch_size, self.concurrent_files)
+        hyper = () if kind == "vad" else (config.rho_update, config.delta_new, config.gamma, config.beta,
+                                          config.max_speakers, config.normalize_embedding_weights)
+        key = (kind, id(seg.model), None if kind == "vad" else id(emb.model), config.tau_active, hyper, config.duration,
+               config.step, config.latency, config.sample_rate, str(config.device), self.batch_size,
+               self.concurrent_files, self.file_batch_rows)
         cached = getattr(self, "_fb_cache", None)
         if cached is not None and cached[0] == key:
             return cached[1]
-        fb = self._new_file_batch(FileBatch, seg, emb, config)
+        fb = self._new_file_batch(FileBatch, seg, None if kind == "vad" else emb, config)
         self._fb_cache = (key, fb)
         return fb
 
     def _new_file_batch(self, FileBatch, seg, emb, config):
-        return FileBatch(seg.model, emb.model, rows=max(64, self.batch_size), max_files=self.concurrent_files,
-                         tau_active=config.tau_active, rho_update=config.rho_update, delta_new=config.delta_new,
+        common = dict(rows=max(int(self.file_batch_rows), self.batch_size), max_files=self.concurrent_files, tau_active=config.tau_active,
+                      duration=config.duration, step=config.step, latency=config.latency,
+                      sample_rate=config.sample_rate, device=config.device)
+        if emb is None:
+            return FileBatch(seg.model, None, pipeline="vad", **common)
+        return FileBatch(seg.model, emb.model, rho_update=config.rho_update, delta_new=config.delta_new,
                          gamma=config.gamma, beta=config.beta, max_speakers=config.max_speakers,
-                         normalize_embedding_weights=config.normalize_embedding_weights,
-                         duration=config.duration, step=config.step, latency=config.latency,
-                         sample_rate=config.sample_rate, device=config.device)
+                         normalize_embedding_weights=config.normalize_embedding_weights, **common)
 
     def run_batched(self, fb, config, paths: Sequence[Path]) -> List[Annotation]:
         """``paths`` through one ``FileBatch``: same padding, timestamp shift, RTTM files and

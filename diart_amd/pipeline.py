@@ -1117,11 +1117,24 @@ class FileBatch:
     (``blocks/diarization.py:193-232``) then runs clustering, aggregation and binarisation.  Only
     that loop is sequential, and only within a file.  Here one GPU step carries ``rows`` windows:
     the next ``rows // k`` CONSECUTIVE windows of each of the ``k`` files that are open (file-major
-    rows, copied device to device from the file's resident audio); the host half hands every file
+    rows, gathered device to device from the file's resident audio); the host half hands every file
     to a thread that walks its windows in order through that file's own clustering / aggregation
-    state (``dz_file_step_batch``), ``depth`` GPU steps in flight.  A file that ends frees its slot
-    for the next one.  Per file the speech turns — hence the RTTM — are those of the
-    one-file-at-a-time path (``tests/test_gpu_der.py``).
+    state (``dz_file_step_batch``; ``dz_file_vad_step_batch`` for the VAD form), ``depth`` GPU steps in
+    flight.  A file that ends frees its slot for the next one.  Per file the speech turns — hence the
+    RTTM — are those of the one-file-at-a-time path (``tests/test_gpu_der.py``,
+    ``tests/test_gpu_file_batch_models.py``).
+
+    The engine under the files follows the models, as ``StreamServer``'s does (``self.kind``):
+
+        HipEmbedding (pyannote/embedding)            "xvector"    StreamBatch
+        HipWeSpeakerEmbedding                        "wespeaker"  WeSpeakerBatch
+        a groups-form embedding (ECAPA, speechbrain  "groups"     what StreamBatch(seg, emb, ...) constructs: GroupsBatch
+          x-vector, TitaNet-L, speechbrain ResNet,                (each chunk's K rows embedded alone: the blocks path at
+          mel-spectrogram ECAPA)                                  batch_size = 1, see Benchmark.file_batch)
+        None with pipeline="vad"                     "vad"        VadBatch; every turn is labelled "speech"
+
+    Everything ``run`` does with its engine goes through ``_launch_rows`` and the ticket's pinned results
+    (``seg_h`` / ``emb_h``, or ``vad_h``).
 
     ``run(files)``: ``files`` = iterable of ``(uri, padded waveform float32 (samples,), shift)``;
     the waveform already carries ``config.get_padding`` and a zero-filled last block (what
@@ -1129,31 +1142,65 @@ class FileBatch:
     ``{uri: Annotation}`` (``PredictionAccumulator`` semantics: every chunk's turns, then
     ``support(patch_collar)``)."""
 
-    def __init__(self, segmentation: HipSegmentation, embedding: HipEmbedding, *, rows: int = 64,
+    # Is a step's stage filled by ONE dz_gather_windows launch (True) or by one torch copy per open file?  The kernel takes
+    # 6.7 us where the 16 copies take 112 us of GPU time, but the pyannote/embedding form, measured against the parent
+    # commit, showed no gain from it (profiles/r24a_file_batch_models.json; README "File batches for every model"): the
+    # form that existed keeps the copies it had, the new forms start with the kernel.
+    GATHER_DEFAULT = {"xvector": False, "wespeaker": True, "groups": True, "vad": True}
+
+    def __init__(self, segmentation: HipSegmentation, embedding=None, *, rows: int = 64,
                  max_files: int = 16, tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
                  gamma: float = 3, beta: float = 10, max_speakers: int = 20,
                  normalize_embedding_weights: bool = False, duration: float = 5.0, step: float = 0.5,
                  latency: Optional[float] = None, sample_rate: int = 16000,
                  device: Optional[torch.device] = None, threads: int = 8, patch_collar: float = 0.05,
-                 recurrence: Optional[str] = "valu", lanes: Optional[int] = 2):
+                 recurrence: Optional[str] = "valu", lanes: Optional[int] = 2, pipeline: str = "diarization",
+                 gather: Optional[bool] = None):
         """``recurrence`` / ``lanes``: the engine under the files.  A file job is short and its files end at different
         times: the latency-form recurrence on two lanes finishes 16 ten-minute files 13 - 40 % sooner than the
         throughput engine a 64-row ``StreamBatch`` would pick for itself (profiles/r06q_file_batch_engine.json:
-        25 800 - 26 700 vs 17 900 - 23 600 chunks/s); None = let ``StreamBatch`` choose."""
+        25 800 - 26 700 vs 17 900 - 23 600 chunks/s); None = let the engine choose.  The other forms keep the same
+        pair for another reason too: the blocks path always runs the "valu" recurrence, a matrix-core recurrence rounds
+        the segmentation scores differently, and the RTTM files have to be those of the one-file-at-a-time loop byte for
+        byte; two lanes are what the two-chain engines run anyway (gigabytes of arena per lane).
+
+        ``pipeline``: "diarization" | "vad" (``embedding`` must then be None).  ``gather``: fill a step's stage with one
+        ``dz_gather_windows`` launch instead of one torch copy per open file (None = the form's default)."""
         self.rows, self.max_files = int(rows), max(1, min(int(max_files), int(rows)))
-        self.engine = StreamBatch(segmentation, embedding, self.rows, tau_active, rho_update, delta_new, gamma,
-                                  beta, max_speakers, normalize_embedding_weights, device=device,
-                                  cluster_threads=threads, tail=False, duration=duration, step=step,
-                                  latency=latency, recurrence=recurrence, lanes=lanes)
+        if pipeline not in ("diarization", "vad"):
+            raise ValueError(f"FileBatch: pipeline={pipeline!r} (expected diarization | vad)")
+        if pipeline == "vad":
+            if embedding is not None:
+                raise ValueError("FileBatch(pipeline='vad') takes no embedding")
+            self.kind = "vad"
+            self.engine = VadBatch(segmentation, self.rows, tau_active, duration, step, latency, device, lanes=lanes,
+                                   recurrence=recurrence, host_threads=threads)
+        else:
+            if isinstance(embedding, HipWeSpeakerEmbedding):
+                self.kind, engine = "wespeaker", WeSpeakerBatch
+            elif isinstance(embedding, _HipGroupsEmbedding):
+                self.kind, engine = "groups", StreamBatch          # -> GroupsBatch
+            elif isinstance(embedding, HipEmbedding):
+                self.kind, engine = "xvector", StreamBatch
+            else:
+                raise ValueError(f"FileBatch: no engine runs the embedding {type(embedding).__name__}")
+            self.engine = engine(segmentation, embedding, self.rows, tau_active, rho_update, delta_new, gamma,
+                                 beta, max_speakers, normalize_embedding_weights, device=device,
+                                 cluster_threads=threads, tail=False, duration=duration, step=step,
+                                 latency=latency, recurrence=recurrence, lanes=lanes)
+        self.gather = FileBatch.GATHER_DEFAULT[self.kind] if gather is None else bool(gather)
         self.device = self.engine.device
         self.duration, self.step, self.sr = float(duration), float(step), int(sample_rate)
         self.latency = self.step if latency is None else float(latency)
         self.S, self.hop = int(round(sample_rate * duration)), int(round(sample_rate * step))
         assert self.hop % 4 == 0, "the step must be a multiple of 4 samples (16-byte aligned windows)"
-        self.tau, self.rho, self.delta, self.G = tau_active, rho_update, delta_new, int(max_speakers)
+        self.tau, self.rho, self.delta = tau_active, rho_update, delta_new
+        self.G = 1 if self.kind == "vad" else int(max_speakers)
         self.threads, self.patch_collar = int(threads), patch_collar
         self._lib = _lib.load()
-        self._clu: List = []          # per file slot: dz_clu handle
+        self._ctx = _lib.context(self.device.index)
+        self._runs = (_lib.WindowRun * self.max_files)()
+        self._clu: List = []          # per file slot: dz_clu handle (none for the VAD form)
         self._tails: Optional[BatchedOutputTail] = None
         self._stage: List[torch.Tensor] = []
         self._pool, self._lent = FileBatch._PinnedPool(), {}
@@ -1163,10 +1210,11 @@ class FileBatch:
     def _ensure_state(self, F: int) -> None:
         if self._tails is not None:
             return
-        for _ in range(self.max_files):
+        for _ in range(0 if self.kind == "vad" else self.max_files):
             h = _lib.vp()
             _lib.check(self._lib.dz_clu_create(self.tau, self.rho, self.delta, self.G, C.byref(h)), "dz_clu_create")
             self._clu.append(h)
+        # DelayedAggregation(hamming, loose) + Binarize: what both pipelines build (the VAD form: one "speaker")
         self._tails = BatchedOutputTail(self.max_files, F, self.G, self.step, self.latency, self.tau,
                                         num_threads=self.threads)
         self._F = F
@@ -1293,7 +1341,7 @@ class FileBatch:
         files = FileBatch._Loader(files, self)
         F = self.engine.seg.to(self.device).num_frames(self.S)
         self._ensure_state(F)
-        K, D = None, self.engine.emb.dimension
+        vad = self.kind == "vad"
         res = self.duration / F
         open_files: List[Optional[dict]] = [None] * self.max_files
         done: dict = {}
@@ -1320,7 +1368,8 @@ class FileBatch:
                         self._pool.release(pinned)
                         raise ValueError(f"FileBatch.run: two files share the uri {uri!r}; the results are keyed by it")
                     nwin = (nsamp - self.S) // self.hop + 1 if nsamp >= self.S else 0
-                    _lib.check(self._lib.dz_clu_reset(self._clu[slot]), "dz_clu_reset")
+                    if not vad:
+                        _lib.check(self._lib.dz_clu_reset(self._clu[slot]), "dz_clu_reset")
                     self._tails.reset(slot)
                     if nwin <= 0:
                         done[uri] = []
@@ -1342,9 +1391,13 @@ class FileBatch:
                 if c <= 0:
                     break
                 w0 = f["sent"]
-                # c consecutive windows of this file: a strided view of its resident audio -> dense rows
-                view = f["audio"][w0 * self.hop: w0 * self.hop + (c - 1) * self.hop + self.S].unfold(0, self.S, self.hop)
-                stage[r:r + c].copy_(view, non_blocking=True)
+                # c consecutive windows of this file, `hop` apart in its resident audio -> dense rows
+                if self.gather:
+                    run = self._runs[len(plan)]
+                    run.src, run.row0, run.count = f["audio"].data_ptr() + 4 * w0 * self.hop, r, c
+                else:
+                    view = f["audio"][w0 * self.hop: w0 * self.hop + (c - 1) * self.hop + self.S].unfold(0, self.S, self.hop)
+                    stage[r:r + c].copy_(view, non_blocking=True)
                 # window start times by repeated addition, exactly as rearrange_audio_stream counts them
                 # (`start += step`, operators.py:82-84): bit-identical for steps that are not dyadic
                 starts = np.empty(c, dtype=np.float64)
@@ -1354,6 +1407,11 @@ class FileBatch:
                 plan.append((slot, f, r, c, starts))
                 f["sent"] += c
                 r += c
+            if self.gather:
+                # one launch for every open file, on the stream the files' uploads were queued on
+                _lib.check(self._lib.dz_gather_windows(
+                    self._ctx, self._runs, len(plan), self.S, self.hop, stage.data_ptr(), stage.stride(0), self.rows,
+                    torch.cuda.current_stream(self.device).cuda_stream), "dz_gather_windows")
             ticket = self.engine._launch_rows(stage.data_ptr(), stage.stride(0), r, self.S, keep=stage)
             inflight.append((ticket, plan, r))
             step_no += 1
@@ -1362,19 +1420,26 @@ class FileBatch:
         def finish_step():
             ticket, plan, r = inflight.pop(0)
             with self.engine._host_half(ticket):
-                seg = ticket["seg_h"].numpy()[:r]
-                emb = ticket["emb_h"].numpy()[:r]
                 k = len(plan)
-                clus = (_lib.vp * k)(*[self._clu[slot] for slot, *_ in plan])
                 tails = (_lib.vp * k)(*[self._tails._hs[slot] for slot, *_ in plan])
                 row0 = np.array([p[2] for p in plan], dtype=np.int32)
                 count = np.array([p[3] for p in plan], dtype=np.int32)
                 starts = np.concatenate([p[4] for p in plan]).astype(np.float64)
                 turns, nturns = self._turns[0], self._nturns[0]
-                _lib.check(self._lib.dz_file_step_batch(
-                    clus, tails, k, row0.ctypes.data, count.ctypes.data, seg.ctypes.data, seg.shape[1], seg.shape[2],
-                    emb.ctypes.data, emb.shape[2], self.G, starts.ctypes.data, float(res), turns.ctypes.data,
-                    self._max_turns, nturns.ctypes.data, None, self.threads), "dz_file_step_batch")
+                if vad:
+                    track = ticket["vad_h"].numpy()[:r]
+                    _lib.check(self._lib.dz_file_vad_step_batch(
+                        tails, k, row0.ctypes.data, count.ctypes.data, track.ctypes.data, track.shape[1],
+                        starts.ctypes.data, float(res), turns.ctypes.data, self._max_turns, nturns.ctypes.data,
+                        self.threads), "dz_file_vad_step_batch")
+                else:
+                    seg = ticket["seg_h"].numpy()[:r]
+                    emb = ticket["emb_h"].numpy()[:r]
+                    clus = (_lib.vp * k)(*[self._clu[slot] for slot, *_ in plan])
+                    _lib.check(self._lib.dz_file_step_batch(
+                        clus, tails, k, row0.ctypes.data, count.ctypes.data, seg.ctypes.data, seg.shape[1], seg.shape[2],
+                        emb.ctypes.data, emb.shape[2], self.G, starts.ctypes.data, float(res), turns.ctypes.data,
+                        self._max_turns, nturns.ctypes.data, None, self.threads), "dz_file_step_batch")
             for slot, f, r0, c, _ in plan:
                 for j in range(r0, r0 + c):
                     if nturns[j]:
@@ -1424,7 +1489,10 @@ class FileBatch:
             if rec:
                 chunks, shift = rec
                 for arr in chunks:
-                    for s, e, g in arr:
-                        ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
+                    for n, (s, e, g) in enumerate(arr):
+                        if vad:                 # one track per turn of a chunk, like Timeline.to_annotation
+                            ann[Segment(s + shift, e + shift), n] = "speech"
+                        else:
+                            ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
             out[uri] = ann.support(self.patch_collar)
         return out

@@ -873,6 +873,7 @@ int dz_tail_create(int frames, int speakers, double step, double latency, double
 int dz_tail_reset(dz_tail* t);
 int dz_tail_destroy(dz_tail* t);
 int dz_tail_max_rows(const dz_tail* t);
+int dz_tail_speakers(const dz_tail* t);      /* the `speakers` it was created with */
 int dz_tail_step(dz_tail* t, const double* scores, double chunk_start, double resolution,
                  double* agg_out, int* rows_out, double* t0_out, double* res_out,
                  double* turns_out, int max_turns, int* nturns_out);
@@ -898,6 +899,28 @@ int dz_file_step_batch(dz_clu** clus, dz_tail** tails, int n_files, const int* r
                        int max_speakers, const double* chunk_start, double resolution,
                        double* turns_out, int max_turns, int* nturns_out, int* assign_out,
                        int num_threads);
+
+/* The VoiceActivityDetection sibling (blocks/vad.py:136-191 of the reference, driven the same way): no clustering.
+ * track (rows, frames) float32 = the speech track of every window (max over speakers of the segmentation, what
+ * dz_seg_forward_vad writes); tails: per file, built for ONE speaker and `frames` frames.  Per file, in window order:
+ * dz_tail_step on that file's own handle (the track widened to fp64); files run in parallel on host threads.  A failing
+ * file is reported with its index and the worker's own message; bad arguments return 2 and touch nothing.           */
+int dz_file_vad_step_batch(dz_tail** tails, int n_files, const int* row0, const int* count, const float* track,
+                           int frames, const double* chunk_start, double resolution, double* turns_out,
+                           int max_turns, int* nturns_out, int num_threads);
+
+/* ---- the rows of a file-batch step in one launch (csrc/k_gather.hip) ------------------------
+ * rows row0 .. row0+count-1 of d_out receive the windows src + j*hop .. + num_samples of run i (consecutive windows of
+ * one file's resident audio).  The runs are passed to the kernel by value, DZ_GATHER_MAX_RUNS per launch (more runs:
+ * more launches on the same stream).  No synchronisation, no allocation, nothing read from device memory by the host.
+ * A run with count == 0 is skipped.  Errors (code 2, nothing launched): row0 < 0, row0 + count > out_rows,
+ * out_stride < num_samples, hop < 1, n_runs < 1, a NULL src with count > 0.  A pure copy: 16-byte loads / stores where
+ * a window and its row are both 16-byte aligned, one float at a time otherwise; nothing outside the rows and the
+ * first num_samples columns asked for is written.                                                                  */
+#define DZ_GATHER_MAX_RUNS 64
+typedef struct { const float* src; int row0; int count; } dz_window_run;   /* host array */
+int dz_gather_windows(dz_ctx* ctx, const dz_window_run* runs, int n_runs, int num_samples, int hop,
+                      float* d_out, long long out_stride, int out_rows, void* stream);
 
 /* ---- hyper-parameter tuning: replay cached model outputs --------------------
  * tau_active, rho_update and delta_new act only after the networks, so a trial is a replay of the
