@@ -721,7 +721,17 @@ int dz_k_convgemm_ntile(int t_out);
  * point runs the slice kernel plus the merge and synchronises the stream.                     */
 int dz_k_wave_stats(dz_ctx* ctx, const float* d_wave, long long stride, int batch, int samples,
                     float* d_stats, void* stream);
-/* y0 (B, P0, 80) with P0 = ((S-251)/10+1)/3; partials (B, ntile0, 80, 2), ntile0 = ceil(F0/192);
+/* Waveform rows of dz_k_wave_stats, dz_k_sinc_conv0* and every handle (d_wave + b * stride): the first row 16-byte
+ * aligned, stride a multiple of 4 floats and >= 0 (checked).  That is ALL: no kernel needs readable zeros —
+ * or readable memory at all — behind sample S of a row, and no output depends on what lies there.  wave_stats reads
+ * float4s and a < 4-sample tail inside [0, S) of each slice; sinc_conv0 tests every index against S; the split kernels
+ * (sinc_conv0_split, sinc_conv0_pair) fetch through a buffer descriptor of S * 4 bytes per row (out-of-range dwords
+ * come back as zeros) and test the index against S again when they normalise.  So rows may lie roundup4(S) apart (the
+ * dense (k, W) batch of dz_ring_gather: row b + 1 starts right behind row b), or be windows into a longer signal whose
+ * next samples follow (the rolling window of ring.hip, addressed in place: [q, q + W) of a row of 2 P live samples).
+ * A window with a NaN / Inf sample changes no bit of another row's statistics, y0 or partials
+ * (tests/test_gpu_front_f64.py: NaN behind every row, a non-finite neighbour).
+ * y0 (B, P0, 80) with P0 = ((S-251)/10+1)/3; partials (B, ntile0, 80, 2), ntile0 = ceil(F0/192);
  * d_filt (128, 96): the folded symmetric bank, see dz_sincnet_weights.filt */
 int dz_k_sinc_conv0(dz_ctx* ctx, const float* d_wave, long long stride, int batch, int samples,
                     const float* d_stats, float gamma, float beta, const float* d_filt,
