@@ -11,20 +11,28 @@
 // W samples are ALWAYS one contiguous span [q, q + W) of the row, q = (p + slack*hop) mod P: the
 // segmentation / embedding kernels read the rolling window in place through (base pointer +
 // offset, row stride 2*P) with their usual coalesced 16-byte loads — no wrap-around logic in any
-// kernel, nothing is copied or repeated.  Only the new samples cross PCIe: ONE contiguous
-// asynchronous H2D copy into a staging block, then one small kernel writes the block to both
-// positions (the 2-D runtime copies this replaced cost the step ~0.3 ms of host and queue time).  The slack keeps a push from overwriting samples a forward
+// kernel, nothing is copied or repeated.  The slack keeps a push from overwriting samples a forward
 // pass of the previous `slack` windows may still be reading: block t+1 lands on the slot of
 // block t+1-W/hop-slack, which belongs to windows <= t-slack only.
 //
-// Streams that do NOT advance in lock step (StreamServer: every stream has its own pace) use the
-// per-row entry points: every row keeps its own write position (dz_ring_push_rows advances only the
-// listed rows) and dz_ring_gather copies the current windows of the listed rows, device to device,
-// into the dense (k, W) batch the forward passes take — 320 KB per window at HBM speed instead of
-// 320 KB per window over PCIe.
+// ONE push path (ring_push) behind the three entry points.  dz_ring_push (lock step: every row at the
+// common position, one launch whatever n), dz_ring_push_rows (float rows, each listed row at its own
+// position: StreamServer, where every stream has its own pace) and dz_ring_push_rows_pcm (the same
+// for raw client audio) check their arguments and call it.  It resolves the source once — pinned
+// host memory read in place over PCIe, device memory, or ONE asynchronous H2D copy of the new samples
+// into one of two landing blocks used alternately (the 2-D runtime copies into the ring this replaced
+// cost the step ~0.3 ms of host and queue time) — launches ONE kernel template
+// (ring_scatter_kernel<T, C>: load, convert, average the channels, store at both positions;
+// <float, 1> copies bits) and does the position bookkeeping.  Only the new samples cross PCIe.
+//
+// dz_ring_gather copies the current windows of the listed rows, device to device, into the dense
+// (k, W) batch the forward passes take — 320 KB per window at HBM speed instead of 320 KB per window
+// over PCIe — with ONE kernel, 16 bytes per lane wherever that lane's piece allows it.
 #include "dz_common.h"
 
 #include <new>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 struct dz_ring {
@@ -36,16 +44,14 @@ struct dz_ring {
                        // set and the front-end kernels ran 25 % slower reading the ring than a
                        // dense stream array)
     float* buf;        // [n][2P]
-    float* stage[2];   // [n][hop] landing blocks of the H2D copies, used alternately
-    long long pushed;  // blocks pushed so far
+    char* land;        // two landing blocks of `land_cap` bytes each for the H2D copies of pageable blocks, used
+    size_t land_cap;   // alternately; a mono float32 block of all n rows fits from create on, wider formats grow it
+    long long pushed;  // push calls so far, lock-step and per-row alike (dz_ring_window's `filled`, the landing blocks' turn)
     int pos;           // write position of the NEXT block, in [0, P)
-    // per-row state (dz_ring_push_rows / dz_ring_gather); a lock-step dz_ring_push moves every row
+    // per-row state (the per-row pushes / dz_ring_gather); a lock-step dz_ring_push moves every row
     std::vector<int> rpos;
     std::vector<long long> rpushed;
-    // raw client blocks (dz_ring_push_rows_pcm) and rings whose hop is not a multiple of 4 samples
     bool aligned;      // hop % 4 == 0: every block and every window starts on a 16-byte boundary
-    char* pstage;      // two landing blocks of `pstage_cap` bytes each for pageable host input, grown on demand
-    size_t pstage_cap;
 };
 
 // up to 64 (row, offset) pairs per launch, passed in the kernel-argument segment
@@ -53,6 +59,8 @@ struct DzRowList {
     int row[64];
     int off[64];
 };
+
+static long long round16(long long bytes) { return (bytes + 15) & ~15LL; }
 
 extern "C" int dz_ring_create(dz_ctx* ctx, int n_streams, int window, int hop, int slack_blocks,
                               dz_ring** out) {
@@ -66,7 +74,7 @@ extern "C" int dz_ring_create(dz_ctx* ctx, int n_streams, int window, int hop, i
     dz_ring* r = new (std::nothrow) dz_ring;
     DZ_REQUIRE(r != nullptr, "dz_ring_create: out of memory");
     r->ctx = ctx; r->n = n_streams; r->W = window; r->hop = hop; r->buf = nullptr;
-    r->aligned = hop % 4 == 0; r->pstage = nullptr; r->pstage_cap = 0;
+    r->aligned = hop % 4 == 0; r->land = nullptr;
     r->P = window + slack_blocks * hop;
     r->pushed = 0; r->pos = 0;
     r->rpos.assign(n_streams, 0);
@@ -81,85 +89,20 @@ extern "C" int dz_ring_create(dz_ctx* ctx, int n_streams, int window, int hop, i
         return 1;
     }
     DZ_HIP(hipMemset(r->buf, 0, bytes));
-    r->stage[0] = r->stage[1] = nullptr;
-    if (!r->aligned) {     // float blocks of such a ring land in `pstage` like raw client blocks
-        *out = r;
-        return 0;
-    }
-    e = hipMalloc((void**)&r->stage[0], (size_t)2 * n_streams * hop * sizeof(float));
+    r->land_cap = (size_t)n_streams * round16((long long)hop * sizeof(float));
+    e = hipMalloc((void**)&r->land, 2 * r->land_cap);
     if (e != hipSuccess) {
-        dz_set_error("dz_ring_create: hipMalloc(stage) failed: %s", hipGetErrorString(e));
+        dz_set_error("dz_ring_create: hipMalloc(landing blocks) failed: %s", hipGetErrorString(e));
         (void)hipFree(r->buf);
         delete r;
         return 1;
     }
-    r->stage[1] = r->stage[0] + (size_t)n_streams * hop;
     *out = r;
     return 0;
 }
 
-// block [n][hop] (rows `bstride` floats apart) -> ring rows at `pos` and `pos + P`; 16 bytes per lane
-__global__ __launch_bounds__(256) void ring_scatter_kernel(const float* __restrict__ block, long long bstride,
-                                                           float* __restrict__ buf, long long pitch, int n,
-                                                           int hop4, int P, int pos) {
-    const int i = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= hop4) return;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(block + (long long)i * bstride + 4 * j);
-    float* row = buf + (long long)i * pitch + pos + 4 * j;
-    *reinterpret_cast<f32x4*>(row) = v;
-    *reinterpret_cast<f32x4*>(row + P) = v;
-}
-
-// row j of the block -> ring row rows.row[j] at rows.off[j] and rows.off[j] + P
-__global__ __launch_bounds__(256) void ring_scatter_rows_kernel(const float* __restrict__ block, long long bstride,
-                                                                float* __restrict__ buf, long long pitch,
-                                                                int hop4, int P, DzRowList rows) {
-    const int jrow = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= hop4) return;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(block + (long long)jrow * bstride + 4 * j);
-    float* row = buf + (long long)rows.row[jrow] * pitch + rows.off[jrow] + 4 * j;
-    *reinterpret_cast<f32x4*>(row) = v;
-    *reinterpret_cast<f32x4*>(row + P) = v;
-}
-
-// out row j <- the W samples of ring row rows.row[j] starting at rows.off[j]
-__global__ __launch_bounds__(256) void ring_gather_kernel(const float* __restrict__ buf, long long pitch,
-                                                          float* __restrict__ out, long long ostride, int W4,
-                                                          DzRowList rows) {
-    const int jrow = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= W4) return;
-    const float* src = buf + (long long)rows.row[jrow] * pitch + rows.off[jrow] + 4 * j;
-    *reinterpret_cast<f32x4*>(out + (long long)jrow * ostride + 4 * j) = *reinterpret_cast<const f32x4*>(src);
-}
-
-// out row j <- W samples of ring row rows.row[j] from rows.off[j], where the window or the output row does not
-// start on a 16-byte boundary (a ring with hop % 4 != 0).  A block of 256 lanes moves 1024 samples: 16 bytes per
-// lane when this row's source and destination are aligned, else four 4-byte pieces per lane, 256 samples apart
-// (every load and store of a wave is then one contiguous 256-byte span).
-__global__ __launch_bounds__(256) void ring_gather_any_kernel(const float* __restrict__ buf, long long pitch,
-                                                              float* __restrict__ out, long long ostride, int W,
-                                                              int out_vec, DzRowList rows) {
-    const int jrow = blockIdx.y;
-    const int off = rows.off[jrow];
-    const float* src = buf + (long long)rows.row[jrow] * pitch + off;
-    float* dst = out + (long long)jrow * ostride;
-    const int e0 = blockIdx.x * 1024;
-    if (out_vec && (off & 3) == 0 && e0 + 1024 <= W) {
-        const int e = e0 + 4 * threadIdx.x;
-        *reinterpret_cast<f32x4*>(dst + e) = *reinterpret_cast<const f32x4*>(src + e);
-    } else {
-        for (int t = 0; t < 4; ++t) {
-            const int e = e0 + t * 256 + threadIdx.x;
-            if (e < W) dst[e] = src[e];
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------
-// Raw client blocks -> ring (dz_ring_push_rows_pcm): load, convert, average the channels and store at `off` and
+// Blocks -> ring (every push): load, convert, average the channels and store at `off` and
 // `off + P` in ONE kernel.  Replaces, for live streams, the channel average of the reference's loader
 // (reference audio.py:32-34, waveform.mean(dim=0)) and the int16 -> float conversion its clients
 // do before they send.  The arithmetic is the header's definition, operation for operation: nothing is
@@ -202,28 +145,6 @@ __device__ __forceinline__ float pcm_frame(const T* e) {
     return s / (float)C;
 }
 
-// F = 16 / sizeof(T) frames of C interleaved values at `src` (16-byte aligned): C 16-byte loads, the frames'
-// samples to o0 and, with TWICE, to o1 (both 16-byte aligned) with 16-byte stores
-template <typename T, int C, bool TWICE>
-__device__ __forceinline__ void pcm_lane_frames(const T* src, float* o0, float* o1) {
-    constexpr int F = 16 / sizeof(T);
-    union {
-        f32x4 v[C];
-        T e[F * C];
-    } u;
-    const f32x4* s = reinterpret_cast<const f32x4*>(src);
-#pragma unroll
-    for (int c = 0; c < C; ++c) u.v[c] = s[c];
-#pragma unroll
-    for (int q = 0; q < F / 4; ++q) {
-        f32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = pcm_frame<T, C>(u.e + (4 * q + i) * C);
-        *reinterpret_cast<f32x4*>(o0 + 4 * q) = o;
-        if (TWICE) *reinterpret_cast<f32x4*>(o1 + 4 * q) = o;
-    }
-}
-
 // one frame at `src` (aligned to one value)
 template <typename T, int C>
 __device__ __forceinline__ float pcm_one_frame(const T* src) {
@@ -233,47 +154,69 @@ __device__ __forceinline__ float pcm_one_frame(const T* src) {
     return pcm_frame<T, C>(e);
 }
 
+// One lane's share of a row: the F = 16 / sizeof(T) frames at `src`, of which `left` lie inside the row, to o0 and,
+// with TWICE, to o1.  With `vec` (all three 16-byte aligned) and left >= F: C 16-byte loads whatever the format, F / 4
+// 16-byte stores per destination.  Otherwise (unaligned, or the lane that holds the ragged end of the row) the
+// min(left, F) frames one by one.  The same arithmetic per frame either way.
+template <typename T, int C, bool TWICE>
+__device__ __forceinline__ void pcm_lane(const T* src, float* o0, float* o1, long long left, bool vec) {
+    constexpr int F = 16 / sizeof(T);
+    if (__builtin_expect(vec && left >= F, 1)) {      // (laid out first: the instructions of the usual lane are contiguous)
+        union {
+            f32x4 v[C];
+            T e[F * C];
+        } u;
+        const f32x4* s = reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+        for (int c = 0; c < C; ++c) u.v[c] = s[c];
+#pragma unroll
+        for (int q = 0; q < F / 4; ++q) {
+            f32x4 o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = pcm_frame<T, C>(u.e + (4 * q + i) * C);
+            *reinterpret_cast<f32x4*>(o0 + 4 * q) = o;
+            if (TWICE) *reinterpret_cast<f32x4*>(o1 + 4 * q) = o;
+        }
+    } else {
+#pragma nounroll
+        for (int g = 0; g < F && g < left; ++g) {
+            const float o = pcm_one_frame<T, C>(src + g * C);
+            o0[g] = o;
+            if (TWICE) o1[g] = o;
+        }
+    }
+}
+
 // lanes of a block of the push kernel: a 1-byte format's lane takes 16 frames, so one wave already covers 1 024
 template <typename T>
 constexpr int pcm_block_lanes() { return sizeof(T) == 1 ? 64 : 256; }
 
-// Row j of `block` (rows `bstride` values apart): hop frames of C interleaved values of type T -> ring row
-// rows.row[j] at rows.off[j] and rows.off[j] + P.  A lane takes F = 16 / sizeof(T) frames, which are C 16-byte
-// loads whatever the format, and writes them with 16-byte stores; a block of L lanes covers L F frames.  Where the
-// input rows (in_vec == 0) or this row's ring position (off or P not a multiple of 4: a ring with hop % 4 != 0) do
-// not allow that, the lanes of the block take single frames, L apart: 4-byte stores, a wave's stores one contiguous
-// span.  So does, for the 2- and 4-byte formats, the block at the tail of a row (f0 + F L > hop).  A 1-byte format has
-// F = 16 and the telephone hop is 4 000 frames: a per-block rule would send every frame of that workload down the
-// single-frame path, so there each LANE decides: 16 frames inside the row -> the vector path, and only the lane
-// that holds the ragged end (hop % 16 frames) takes them one by one.  Both paths do the same arithmetic per frame.
+// THE push kernel.  Row j of `block` (rows `bstride` values apart): hop frames of C interleaved values of type T ->
+// ring row rows.row[j] at rows.off[j] and rows.off[j] + P; with uni >= 0 (a lock-step push: one launch for any number
+// of rows) -> ring row j at `uni`.  A block of L lanes covers L F frames, F = 16 / sizeof(T).  Where the input rows
+// (in_vec) and this row's ring position (off and P multiples of 4) allow 16-byte access each LANE decides
+// (pcm_lane): its F frames lie inside the row -> C 16-byte loads and 16-byte stores, and only the lane that holds
+// the ragged end (hop % F frames) takes those one by one.  So the telephone hop of 4 000 one-byte frames is 250
+// vector lanes per row, and the 832 frames behind the last full block of a float32 hop of 8 000 are read 16 bytes
+// at a time (over PCIe when the block is mapped pinned memory).  Where they do not (a ring with hop % 4 != 0, input
+// rows off the 16-byte boundary) the lanes of the block take single frames, L apart: 4-byte stores, a wave's stores
+// one contiguous span.  Every path does the same arithmetic per frame; <float, 1> copies bits.
 template <typename T, int C>
-__global__ __launch_bounds__(256) void ring_scatter_pcm_kernel(const T* __restrict__ block, long long bstride,
-                                                               float* __restrict__ buf, long long pitch, int hop,
-                                                               int P, int in_vec, DzRowList rows) {
+__global__ __launch_bounds__(256) void ring_scatter_kernel(const T* __restrict__ block, long long bstride,
+                                                           float* __restrict__ buf, long long pitch, int hop, int P,
+                                                           int in_vec, int uni, DzRowList rows) {
     constexpr int F = 16 / sizeof(T);
     constexpr int L = pcm_block_lanes<T>();
     const int jrow = blockIdx.y;
-    const int off = rows.off[jrow];
+    // (the list is read whatever the mode, so that every kernel argument is fetched in one round trip)
+    const int lrow = rows.row[jrow & 63], loff = rows.off[jrow & 63];
+    const int off = uni >= 0 ? uni : loff;
     const T* in = block + (long long)jrow * bstride;
-    float* row = buf + (long long)rows.row[jrow] * pitch + off;
+    float* row = buf + (long long)(uni >= 0 ? jrow : lrow) * pitch + off;
     const int f0 = blockIdx.x * (F * L);
-    if constexpr (sizeof(T) == 1) {
-        if (in_vec && ((off | P) & 3) == 0) {
-            const int f = f0 + F * threadIdx.x;
-            if (f + F <= hop) {
-                pcm_lane_frames<T, C, true>(in + (long long)f * C, row + f, row + P + f);
-            } else {
-                for (int g = f; g < hop; ++g) {
-                    const float o = pcm_one_frame<T, C>(in + (long long)g * C);
-                    row[g] = o;
-                    row[P + g] = o;
-                }
-            }
-            return;
-        }
-    } else if (in_vec && ((off | P) & 3) == 0 && f0 + F * L <= hop) {
+    if (__builtin_expect(in_vec && ((off | P) & 3) == 0, 1)) {
         const int f = f0 + F * threadIdx.x;
-        pcm_lane_frames<T, C, true>(in + (long long)f * C, row + f, row + P + f);
+        pcm_lane<T, C, true>(in + (long long)f * C, row + f, row + P + f, hop - f, true);
         return;
     }
 #pragma unroll
@@ -287,64 +230,42 @@ __global__ __launch_bounds__(256) void ring_scatter_pcm_kernel(const T* __restri
     }
 }
 
-template <typename T>
-static void launch_scatter_pcm(int channels, int rows, hipStream_t st, const void* src, long long bstride,
-                               float* buf, long long pitch, int hop, int P, int in_vec, const DzRowList& rl) {
-    const T* b = reinterpret_cast<const T*>(src);
-    constexpr int L = pcm_block_lanes<T>();
-    constexpr int per_block = L * (int)(16 / sizeof(T));
-    const dim3 grid((hop + per_block - 1) / per_block, rows);
-#define DZ_PCM_CASE(C)                                                                                        \
-    case C:                                                                                                   \
-        hipLaunchKernelGGL((ring_scatter_pcm_kernel<T, C>), grid, dim3(L), 0, st, b, bstride, buf, pitch, hop, P, \
-                           in_vec, rl);                                                                       \
-        break;
-    switch (channels) {
-        DZ_PCM_CASE(1) DZ_PCM_CASE(2) DZ_PCM_CASE(3) DZ_PCM_CASE(4)
-        DZ_PCM_CASE(5) DZ_PCM_CASE(6) DZ_PCM_CASE(7) DZ_PCM_CASE(8)
-    }
-#undef DZ_PCM_CASE
-}
-
 static long long pcm_value_bytes(int format) {
     return format == DZ_PCM_F32 || format == DZ_PCM_S32 ? 4 : format == DZ_PCM_S16 ? 2 : 1;
 }
 
 static bool pcm_format_known(int format) { return format >= DZ_PCM_F32 && format <= DZ_PCM_ALAW; }
 
+// f(T(), integral_constant<int, C>()) for the value type of `format` and C = channels (both checked by the caller):
+// the one format x channel dispatch, of the push and of dz_pcm_decode
+template <typename T, typename Fn, int... I>
+static void pcm_with_channels(int channels, Fn& f, std::integer_sequence<int, I...>) {
+    ((channels == I + 1 ? f(T(), std::integral_constant<int, I + 1>()) : void()), ...);
+}
+
+template <typename Fn>
+static void pcm_dispatch(int format, int channels, Fn f) {
+    const std::make_integer_sequence<int, 8> c8;
+    switch (format) {
+        case DZ_PCM_F32: pcm_with_channels<float>(channels, f, c8); break;
+        case DZ_PCM_S16: pcm_with_channels<short>(channels, f, c8); break;
+        case DZ_PCM_U8: pcm_with_channels<pcm_u8>(channels, f, c8); break;
+        case DZ_PCM_S32: pcm_with_channels<int>(channels, f, c8); break;
+        case DZ_PCM_ULAW: pcm_with_channels<pcm_ulaw>(channels, f, c8); break;
+        default: pcm_with_channels<pcm_alaw>(channels, f, c8); break;
+    }
+}
+
 // ---------------------------------------------------------------------------
-// dz_pcm_decode: the push kernel's per-frame function over ONE contiguous device buffer, without a ring (files,
-// tests, functional.decode_pcm).  A lane takes F frames with 16-byte loads and stores where both buffers are
-// 16-byte aligned and its frames lie inside the buffer, single frames otherwise: the same bits either way.
+// dz_pcm_decode: the push kernel's lane (pcm_lane) over ONE contiguous device buffer, without a ring (files, tests,
+// functional.decode_pcm): F frames with 16-byte loads and stores where both buffers are 16-byte aligned and the
+// frames lie inside the buffer, single frames otherwise: the same bits either way.
 // ---------------------------------------------------------------------------
 template <typename T, int C>
 __global__ __launch_bounds__(256) void pcm_decode_kernel(const T* __restrict__ src, float* __restrict__ dst,
                                                          long long n, int vec) {
-    constexpr int F = 16 / sizeof(T);
-    const long long f = ((long long)blockIdx.x * 256 + threadIdx.x) * F;
-    if (f >= n) return;
-    if (vec && f + F <= n) {
-        pcm_lane_frames<T, C, false>(src + f * C, dst + f, nullptr);
-    } else {
-        const long long end = f + F < n ? f + F : n;
-        for (long long g = f; g < end; ++g) dst[g] = pcm_one_frame<T, C>(src + g * C);
-    }
-}
-
-template <typename T>
-static void launch_pcm_decode(int channels, hipStream_t st, const void* src, float* dst, long long n, int vec) {
-    const T* b = reinterpret_cast<const T*>(src);
-    constexpr long long per_block = 256 * (16 / sizeof(T));
-    const dim3 grid((unsigned)((n + per_block - 1) / per_block));
-#define DZ_PCM_CASE(C)                                                                                        \
-    case C:                                                                                                   \
-        hipLaunchKernelGGL((pcm_decode_kernel<T, C>), grid, dim3(256), 0, st, b, dst, n, vec);                \
-        break;
-    switch (channels) {
-        DZ_PCM_CASE(1) DZ_PCM_CASE(2) DZ_PCM_CASE(3) DZ_PCM_CASE(4)
-        DZ_PCM_CASE(5) DZ_PCM_CASE(6) DZ_PCM_CASE(7) DZ_PCM_CASE(8)
-    }
-#undef DZ_PCM_CASE
+    const long long f = ((long long)blockIdx.x * 256 + threadIdx.x) * (16 / sizeof(T));
+    pcm_lane<T, C, false>(src + f * C, dst + f, nullptr, n - f, vec);
 }
 
 extern "C" int dz_pcm_decode(dz_ctx* ctx, const void* d_src, long long n_frames, int format, int channels,
@@ -358,15 +279,12 @@ extern "C" int dz_pcm_decode(dz_ctx* ctx, const void* d_src, long long n_frames,
                "dz_pcm_decode: buffers must be aligned to one value");
     DZ_HIP(hipSetDevice(ctx->device));
     const int vec = (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) == 0;
-    hipStream_t st = (hipStream_t)stream;
-    switch (format) {
-        case DZ_PCM_F32: launch_pcm_decode<float>(channels, st, d_src, d_dst, n_frames, vec); break;
-        case DZ_PCM_S16: launch_pcm_decode<short>(channels, st, d_src, d_dst, n_frames, vec); break;
-        case DZ_PCM_U8: launch_pcm_decode<pcm_u8>(channels, st, d_src, d_dst, n_frames, vec); break;
-        case DZ_PCM_S32: launch_pcm_decode<int>(channels, st, d_src, d_dst, n_frames, vec); break;
-        case DZ_PCM_ULAW: launch_pcm_decode<pcm_ulaw>(channels, st, d_src, d_dst, n_frames, vec); break;
-        default: launch_pcm_decode<pcm_alaw>(channels, st, d_src, d_dst, n_frames, vec); break;
-    }
+    pcm_dispatch(format, channels, [&](auto tag, auto c) {
+        using T = decltype(tag);
+        constexpr long long per_block = 256 * (16 / sizeof(T));
+        hipLaunchKernelGGL((pcm_decode_kernel<T, decltype(c)::value>), dim3((unsigned)((n_frames + per_block - 1) / per_block)),
+                           dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const T*>(d_src), d_dst, n_frames, vec);
+    });
     DZ_HIP(hipGetLastError());
     return 0;
 }
@@ -414,8 +332,7 @@ extern "C" int dz_results_to_host(dz_ctx* ctx, const float* d_a, float* h_a, lon
 extern "C" int dz_ring_destroy(dz_ring* r) {
     if (r) {
         if (r->buf) (void)hipFree(r->buf);
-        if (r->stage[0]) (void)hipFree(r->stage[0]);
-        if (r->pstage) (void)hipFree(r->pstage);
+        if (r->land) (void)hipFree(r->land);
         delete r;
     }
     return 0;
@@ -437,17 +354,23 @@ extern "C" int dz_ring_reset_row(dz_ring* r, int row) {
     return 0;
 }
 
-// Rows of raw client audio -> the listed ring rows, each at its own write position (the body of
-// dz_ring_push_rows_pcm; float blocks of a ring with hop % 4 != 0 come here too).  The caller has checked `rows`.
-static int ring_push_pcm(dz_ring* r, const void* block, long long stride_bytes, int format, int channels,
-                         int on_device, const int* rows, int k, hipStream_t st) {
+// The push path.  k rows of `block` (stride_bytes apart; hop frames of `channels` interleaved values of `format`
+// each): row j -> ring row rows[j] at THAT row's own write position (the caller has checked `rows`), 64 rows per
+// launch; or, rows == nullptr and k == n, the lock-step push: row j -> ring row j at the common position, one launch.
+static int ring_push(dz_ring* r, const void* block, long long stride_bytes, int format, int channels, int on_device,
+                     const int* rows, int k, hipStream_t st) {
     const long long esz = pcm_value_bytes(format);
     const long long row_bytes = (long long)r->hop * channels * esz;
     DZ_REQUIRE(stride_bytes >= row_bytes && stride_bytes % esz == 0 && (uintptr_t)block % esz == 0,
                "ring push: rows of the block must be >= hop * channels values apart and aligned to one value");
+    DZ_HIP(hipSetDevice(r->ctx->device));
     const char* src = reinterpret_cast<const char*>(block);
     long long sstride = stride_bytes;
     if (on_device == 2) {
+        // pinned host memory: ask the runtime for its device-side address and let the scatter kernel
+        // read it in place over PCIe (32 KB per stream).  That keeps the upload off the copy queues,
+        // where it was seen to wait behind the D2H copy of a step whose results were not ready yet
+        // (-17 % with one embedding stream per lane).  Not mappable -> staged copy below.
         void* dptr = nullptr;
         if (hipHostGetDevicePointer(&dptr, (void*)block, 0) == hipSuccess && dptr) {
             src = reinterpret_cast<const char*>(dptr);
@@ -457,47 +380,52 @@ static int ring_push_pcm(dz_ring* r, const void* block, long long stride_bytes, 
         }
     }
     if (!on_device) {
-        // landing rows start on 16-byte boundaries whatever the caller's stride; the two landing blocks alternate as
-        // in dz_ring_push.  They grow to the largest format seen (hipFree waits for the kernels still reading them)
-        const long long spitch = (row_bytes + 15) & ~15LL;
+        // landing rows start on 16-byte boundaries whatever the caller's stride.  Pushes of one ring are issued in
+        // stream order, so two landing blocks used alternately are never overwritten before the scatter that reads
+        // them has run.  They grow to the largest format seen (hipFree waits for the kernels still reading them)
+        const long long spitch = round16(row_bytes);
         const size_t full = (size_t)r->n * spitch;
-        if (r->pstage_cap < full) {
-            if (r->pstage) DZ_HIP(hipFree(r->pstage));
-            r->pstage = nullptr; r->pstage_cap = 0;
-            DZ_HIP(hipMalloc((void**)&r->pstage, 2 * full));
-            r->pstage_cap = full;
+        if (r->land_cap < full) {
+            DZ_HIP(hipFree(r->land));
+            r->land = nullptr; r->land_cap = 0;
+            DZ_HIP(hipMalloc((void**)&r->land, 2 * full));
+            r->land_cap = full;
         }
-        char* land = r->pstage + (size_t)(r->pushed & 1) * r->pstage_cap;
-        DZ_HIP(hipMemcpy2DAsync(land, (size_t)spitch, block, (size_t)stride_bytes, (size_t)row_bytes, k,
-                                hipMemcpyHostToDevice, st));
+        char* land = r->land + (size_t)(r->pushed & 1) * r->land_cap;
+        if (stride_bytes == row_bytes && row_bytes == spitch) {
+            DZ_HIP(hipMemcpyAsync(land, block, (size_t)k * row_bytes, hipMemcpyHostToDevice, st));
+        } else {
+            DZ_HIP(hipMemcpy2DAsync(land, (size_t)spitch, block, (size_t)stride_bytes, (size_t)row_bytes, k,
+                                    hipMemcpyHostToDevice, st));
+        }
         src = land;
         sstride = spitch;
     }
     const int in_vec = ((uintptr_t)src & 15) == 0 && (sstride & 15) == 0;
-    for (int j0 = 0; j0 < k; j0 += 64) {
-        const int m = k - j0 < 64 ? k - j0 : 64;
-        DzRowList rl;
-        for (int j = 0; j < m; ++j) {
+    const int per_launch = rows ? 64 : k;
+    for (int j0 = 0; j0 < k; j0 += per_launch) {
+        const int m = k - j0 < per_launch ? k - j0 : per_launch;
+        DzRowList rl = {};
+        for (int j = 0; rows && j < m; ++j) {
             rl.row[j] = rows[j0 + j];
             rl.off[j] = r->rpos[rows[j0 + j]];
         }
-        const char* s0 = src + (long long)j0 * sstride;
-        const long long bs = sstride / esz;
-        switch (format) {
-            case DZ_PCM_F32: launch_scatter_pcm<float>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
-            case DZ_PCM_S16: launch_scatter_pcm<short>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
-            case DZ_PCM_U8: launch_scatter_pcm<pcm_u8>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
-            case DZ_PCM_S32: launch_scatter_pcm<int>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
-            case DZ_PCM_ULAW: launch_scatter_pcm<pcm_ulaw>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
-            default: launch_scatter_pcm<pcm_alaw>(channels, m, st, s0, bs, r->buf, r->pitch, r->hop, r->P, in_vec, rl); break;
-        }
+        pcm_dispatch(format, channels, [&](auto tag, auto c) {
+            using T = decltype(tag);
+            constexpr int L = pcm_block_lanes<T>(), per_block = L * (int)(16 / sizeof(T));
+            hipLaunchKernelGGL((ring_scatter_kernel<T, decltype(c)::value>), dim3((r->hop + per_block - 1) / per_block, m),
+                               dim3(L), 0, st, reinterpret_cast<const T*>(src + (long long)j0 * sstride), sstride / esz,
+                               r->buf, r->pitch, r->hop, r->P, in_vec, rows ? -1 : r->pos, rl);
+        });
         DZ_HIP(hipGetLastError());
     }
+    if (!rows) r->pos = (r->pos + r->hop) % r->P;
     for (int j = 0; j < k; ++j) {
-        r->rpos[rows[j]] = (r->rpos[rows[j]] + r->hop) % r->P;
-        r->rpushed[rows[j]] += 1;
+        const int i = rows ? rows[j] : j;
+        r->rpos[i] = rows ? (r->rpos[i] + r->hop) % r->P : r->pos;
+        r->rpushed[i] += 1;
     }
-    r->pushed += 1;        // alternates the landing blocks
+    r->pushed += 1;        // also alternates the landing blocks
     return 0;
 }
 
@@ -518,95 +446,20 @@ extern "C" int dz_ring_push_rows_pcm(dz_ring* r, const void* block, long long bl
     DZ_REQUIRE(channels >= 1 && channels <= 8, "dz_ring_push_rows_pcm: %d channels (1 .. 8)", channels);
     int rc = ring_check_rows(r, rows, k, "dz_ring_push_rows_pcm");
     if (rc) return rc;
-    DZ_HIP(hipSetDevice(r->ctx->device));
-    return ring_push_pcm(r, block, block_stride_bytes, format, channels, on_device, rows, k, (hipStream_t)stream);
+    return ring_push(r, block, block_stride_bytes, format, channels, on_device, rows, k, (hipStream_t)stream);
 }
 
 // block: [n][hop] floats with `block_stride` floats between rows; on the host (pinned memory makes
-// the copy asynchronous) when on_device == 0, in device memory otherwise.
+// the copy asynchronous) when on_device == 0, in device memory otherwise.  Every row at the common position.
 extern "C" int dz_ring_push(dz_ring* r, const float* block, long long block_stride, int on_device,
                             void* stream) {
     DZ_REQUIRE(r && block, "dz_ring_push: NULL argument");
     DZ_REQUIRE(block_stride >= r->hop, "dz_ring_push: block_stride %lld < hop %d", block_stride,
                r->hop);
-    DZ_HIP(hipSetDevice(r->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!r->aligned) {     // every row at the common position, through the 4-byte capable kernel
-        std::vector<int> all(r->n);
-        for (int i = 0; i < r->n; ++i) { all[i] = i; r->rpos[i] = r->pos; }
-        int rc = ring_push_pcm(r, block, block_stride * (long long)sizeof(float), DZ_PCM_F32, 1, on_device,
-                               all.data(), r->n, st);
-        if (rc) return rc;
-        r->pos = (r->pos + r->hop) % r->P;
-        return 0;
-    }
-    DZ_REQUIRE(((uintptr_t)block & 15) == 0 && (block_stride & 3) == 0,
+    DZ_REQUIRE(!r->aligned || (((uintptr_t)block & 15) == 0 && (block_stride & 3) == 0),
                "dz_ring_push: block rows must be 16-byte aligned");
-    const float* src = block;
-    long long sstride = block_stride;
-    if (on_device == 2) {
-        // pinned host memory: ask the runtime for its device-side address and let the scatter kernel
-        // read it in place over PCIe (32 KB per stream).  That keeps the upload off the copy queues,
-        // where it was seen to wait behind the D2H copy of a step whose results were not ready yet
-        // (-17 % with one embedding stream per lane).  Not mappable -> staged copy below.
-        void* dptr = nullptr;
-        if (hipHostGetDevicePointer(&dptr, (void*)block, 0) == hipSuccess && dptr) {
-            src = reinterpret_cast<const float*>(dptr);
-        } else {
-            (void)hipGetLastError();
-            on_device = 0;
-        }
-    }
-    if (!on_device) {
-        // pushes of one ring are issued in stream order, so two landing blocks used alternately
-        // are never overwritten before the scatter that reads them has run
-        float* land = r->stage[r->pushed & 1];
-        if (block_stride == r->hop) {
-            DZ_HIP(hipMemcpyAsync(land, block, (size_t)r->n * r->hop * sizeof(float),
-                                  hipMemcpyHostToDevice, st));
-        } else {
-            DZ_HIP(hipMemcpy2DAsync(land, (size_t)r->hop * sizeof(float), block,
-                                    (size_t)block_stride * sizeof(float), (size_t)r->hop * sizeof(float),
-                                    r->n, hipMemcpyHostToDevice, st));
-        }
-        src = land;
-        sstride = r->hop;
-    }
-    const int hop4 = r->hop / 4;
-    hipLaunchKernelGGL(ring_scatter_kernel, dim3((hop4 + 255) / 256, r->n), dim3(256), 0, st, src, sstride,
-                       r->buf, r->pitch, r->n, hop4, r->P, r->pos);
-    DZ_HIP(hipGetLastError());
-    r->pos = (r->pos + r->hop) % r->P;
-    r->pushed += 1;
-    for (int i = 0; i < r->n; ++i) {
-        r->rpos[i] = r->pos;
-        r->rpushed[i] += 1;
-    }
-    return 0;
-}
-
-// resolve a host block for the scatter kernels: mapped pinned memory (mode 2) or a staged copy
-static int ring_source(dz_ring* r, const float* block, long long block_stride, int rows, int& on_device,
-                       const float*& src, long long& sstride, hipStream_t st) {
-    src = block;
-    sstride = block_stride;
-    if (on_device == 2) {
-        void* dptr = nullptr;
-        if (hipHostGetDevicePointer(&dptr, (void*)block, 0) == hipSuccess && dptr) {
-            src = reinterpret_cast<const float*>(dptr);
-        } else {
-            (void)hipGetLastError();
-            on_device = 0;
-        }
-    }
-    if (!on_device) {
-        float* land = r->stage[r->pushed & 1];
-        DZ_HIP(hipMemcpy2DAsync(land, (size_t)r->hop * sizeof(float), block, (size_t)block_stride * sizeof(float),
-                                (size_t)r->hop * sizeof(float), rows, hipMemcpyHostToDevice, st));
-        src = land;
-        sstride = r->hop;
-    }
-    return 0;
+    return ring_push(r, block, block_stride * (long long)sizeof(float), DZ_PCM_F32, 1, on_device, nullptr, r->n,
+                     (hipStream_t)stream);
 }
 
 // One new block for each of the `k` listed streams: row j of `block` (k, hop) goes to ring row
@@ -614,46 +467,12 @@ static int ring_source(dz_ring* r, const float* block, long long block_stride, i
 extern "C" int dz_ring_push_rows(dz_ring* r, const float* block, long long block_stride, int on_device,
                                  const int* rows, int k, void* stream) {
     DZ_REQUIRE(r && block && rows, "dz_ring_push_rows: NULL argument");
-    DZ_REQUIRE(k >= 1 && k <= r->n, "dz_ring_push_rows: %d rows for %d streams", k, r->n);
-    if (!r->aligned) {
-        int rc = ring_check_rows(r, rows, k, "dz_ring_push_rows");
-        if (rc) return rc;
-        DZ_HIP(hipSetDevice(r->ctx->device));
-        return ring_push_pcm(r, block, block_stride * (long long)sizeof(float), DZ_PCM_F32, 1, on_device, rows, k,
-                             (hipStream_t)stream);
-    }
-    DZ_REQUIRE(block_stride >= r->hop && ((uintptr_t)block & 15) == 0 && (block_stride & 3) == 0,
+    DZ_REQUIRE(!r->aligned || (block_stride >= r->hop && ((uintptr_t)block & 15) == 0 && (block_stride & 3) == 0),
                "dz_ring_push_rows: rows of the block must be >= hop floats apart and 16-byte aligned");
-    std::vector<char> seen(r->n, 0);
-    for (int j = 0; j < k; ++j) {
-        DZ_REQUIRE(rows[j] >= 0 && rows[j] < r->n && !seen[rows[j]], "dz_ring_push_rows: bad / repeated row %d",
-                   rows[j]);
-        seen[rows[j]] = 1;
-    }
-    DZ_HIP(hipSetDevice(r->ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const float* src;
-    long long sstride;
-    int rc = ring_source(r, block, block_stride, k, on_device, src, sstride, st);
+    int rc = ring_check_rows(r, rows, k, "dz_ring_push_rows");
     if (rc) return rc;
-    const int hop4 = r->hop / 4;
-    for (int j0 = 0; j0 < k; j0 += 64) {
-        const int m = k - j0 < 64 ? k - j0 : 64;
-        DzRowList rl;
-        for (int j = 0; j < m; ++j) {
-            rl.row[j] = rows[j0 + j];
-            rl.off[j] = r->rpos[rows[j0 + j]];
-        }
-        hipLaunchKernelGGL(ring_scatter_rows_kernel, dim3((hop4 + 255) / 256, m), dim3(256), 0, st,
-                           src + (long long)j0 * sstride, sstride, r->buf, r->pitch, hop4, r->P, rl);
-        DZ_HIP(hipGetLastError());
-    }
-    for (int j = 0; j < k; ++j) {
-        r->rpos[rows[j]] = (r->rpos[rows[j]] + r->hop) % r->P;
-        r->rpushed[rows[j]] += 1;
-    }
-    r->pushed += 1;        // alternates the landing blocks
-    return 0;
+    return ring_push(r, block, block_stride * (long long)sizeof(float), DZ_PCM_F32, 1, on_device, rows, k,
+                     (hipStream_t)stream);
 }
 
 // samples received by one row so far, capped at the window
@@ -662,6 +481,34 @@ extern "C" int dz_ring_filled_row(const dz_ring* r, int row, int* filled) {
     const long long got = r->rpushed[row] * r->hop;
     *filled = got >= r->W ? r->W : (int)got;
     return 0;
+}
+
+// out row j <- the W samples of ring row rows.row[j] starting at rows.off[j].  A block of 256 lanes moves 1024
+// samples.  Where this row's source and destination are 16-byte aligned each lane moves its 4 samples with one
+// 16-byte load and store (the lane at the end of a W that is no multiple of 4: what is left, one by one); else (a ring
+// with hop % 4 != 0) four 4-byte pieces per lane, 256 samples apart (every load and store of a wave is then one
+// contiguous 256-byte span).
+__global__ __launch_bounds__(256) void ring_gather_kernel(const float* __restrict__ buf, long long pitch,
+                                                          float* __restrict__ out, long long ostride, int W,
+                                                          int out_vec, DzRowList rows) {
+    const int jrow = blockIdx.y;
+    const int off = rows.off[jrow];
+    const float* src = buf + (long long)rows.row[jrow] * pitch + off;
+    float* dst = out + (long long)jrow * ostride;
+    const int e0 = blockIdx.x * 1024;
+    if (out_vec && (off & 3) == 0) {
+        const int e = e0 + 4 * threadIdx.x;
+        if (e + 4 <= W) {
+            *reinterpret_cast<f32x4*>(dst + e) = *reinterpret_cast<const f32x4*>(src + e);
+        } else {
+            for (int g = e; g < W; ++g) dst[g] = src[g];
+        }
+    } else {
+        for (int t = 0; t < 4; ++t) {
+            const int e = e0 + t * 256 + threadIdx.x;
+            if (e < W) dst[e] = src[e];
+        }
+    }
 }
 
 // d_out row j (out_stride floats apart) <- the current window of ring row rows[j]; every listed row
@@ -679,7 +526,6 @@ extern "C" int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d
                    rows[j]);
     }
     DZ_HIP(hipSetDevice(r->ctx->device));
-    const int W4 = r->W / 4;
     for (int j0 = 0; j0 < k; j0 += 64) {
         const int m = k - j0 < 64 ? k - j0 : 64;
         DzRowList rl;
@@ -687,13 +533,8 @@ extern "C" int dz_ring_gather(const dz_ring* r, const int* rows, int k, float* d
             rl.row[j] = rows[j0 + j];
             rl.off[j] = (r->rpos[rows[j0 + j]] + r->P - r->W) % r->P;
         }
-        if (r->aligned)
-            hipLaunchKernelGGL(ring_gather_kernel, dim3((W4 + 255) / 256, m), dim3(256), 0, (hipStream_t)stream,
-                               r->buf, r->pitch, d_out + (long long)j0 * out_stride, out_stride, W4, rl);
-        else
-            hipLaunchKernelGGL(ring_gather_any_kernel, dim3((r->W + 1023) / 1024, m), dim3(256), 0,
-                               (hipStream_t)stream, r->buf, r->pitch, d_out + (long long)j0 * out_stride, out_stride,
-                               r->W, (int)out_vec, rl);
+        hipLaunchKernelGGL(ring_gather_kernel, dim3((r->W + 1023) / 1024, m), dim3(256), 0, (hipStream_t)stream, r->buf,
+                           r->pitch, d_out + (long long)j0 * out_stride, out_stride, r->W, (int)out_vec, rl);
         DZ_HIP(hipGetLastError());
     }
     return 0;

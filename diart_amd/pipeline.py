@@ -81,6 +81,17 @@ class AudioRing:
         _lib.check(self._lib.dz_ring_reset(self._h), "dz_ring_reset")
         self._readers = []
 
+    @staticmethod
+    def _mode(block: torch.Tensor) -> int:
+        """Where a push finds ``block``: 1 = device memory, 0 = host memory (a staged copy), 2 = pinned host memory.
+        Pinned host memory is mapped into the GPU's address space: the scatter kernel reads it IN PLACE over PCIe
+        (32 KB per stream per step; if the runtime cannot map it, a staged copy), which keeps the upload off the SDMA
+        queue — there it can queue behind the D2H copy of a step whose results are not ready yet, and the next step's
+        forward passes then wait for the previous step's (measured: -17 %)."""
+        if block.is_cuda:
+            return 1
+        return 2 if block.is_pinned() and _lib.exp_env("DZ_RING_ZERO_COPY", "1") != "0" else 0
+
     def push(self, block) -> bool:
         """``block``: (N, hop) float32 — a CPU tensor / ndarray (pinned memory makes the copy
         asynchronous) or a tensor on the ring's GPU.  Enqueued on the current HIP stream, after the
@@ -96,13 +107,7 @@ class AudioRing:
         if len(self._readers) == self.slack + 1:
             for ev in self._readers[0]:
                 cur.wait_event(ev)
-        # Pinned host memory is mapped into the GPU's address space: the scatter kernel reads it in
-        # place over PCIe (32 KB per stream per step), which keeps the upload off the SDMA queue —
-        # there it can queue behind the D2H copy of a step whose results are not ready yet, and
-        # the next step's forward passes then wait for the previous step's (measured: -17 %).
-        # mode 2 = pinned host memory read IN PLACE by the scatter kernel (if the runtime can map it)
-        mode = 1 if block.is_cuda else (2 if block.is_pinned() and _lib.exp_env("DZ_RING_ZERO_COPY", "1") != "0" else 0)
-        _lib.check(self._lib.dz_ring_push(self._h, block.data_ptr(), block.stride(0), mode,
+        _lib.check(self._lib.dz_ring_push(self._h, block.data_ptr(), block.stride(0), self._mode(block),
                                           cur.cuda_stream), "dz_ring_push")
         self._keep = (self._keep + [block])[-4:]
         return self.filled == self.window
@@ -129,32 +134,26 @@ class AudioRing:
         needs ``format="u8" | "ulaw" | "alaw"``.  Enqueued on the current HIP stream; a pinned host block is read in
         place by the GPU and must stay untouched until that stream has passed this point."""
         k = len(rows)
-        mode = 1 if block.is_cuda else (2 if block.is_pinned() and _lib.exp_env("DZ_RING_ZERO_COPY", "1") != "0" else 0)
-        arr = (C.c_int * k)(*[int(r) for r in rows])
-        cur = torch.cuda.current_stream(self.device).cuda_stream
-        if block.dtype == torch.float32 and channels == 1 and block.dim() == 2 and self.hop % 4 == 0 \
-                and format in (None, "f32"):
-            assert tuple(block.shape) == (k, self.hop) and block.stride(1) == 1
-            _lib.check(self._lib.dz_ring_push_rows(self._h, block.data_ptr(), block.stride(0), mode, arr, k, cur),
-                       "dz_ring_push_rows")
-        else:
+        if format is None:
+            format = _PCM_OF_DTYPE.get(block.dtype)
             if format is None:
-                format = _PCM_OF_DTYPE.get(block.dtype)
-                if format is None:
-                    raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks (expected float32, int16 or int32; "
-                                    "uint8 blocks need format='u8' | 'ulaw' | 'alaw')")
-            if format not in PCM_FORMATS:
-                raise ValueError(f"AudioRing.push_rows: format={format!r} (expected one of {tuple(PCM_FORMATS)})")
-            fmt, dtype = PCM_FORMATS[format]
-            if torch.from_numpy(np.zeros(0, dtype)).dtype != block.dtype:
-                raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks for format={format!r} (expected {dtype.name})")
-            if block.dim() == 3:
-                assert tuple(block.shape) == (k, self.hop, channels) and block.stride(2) == 1 \
-                    and block.stride(1) == channels, "frames of a (k, hop, channels) block must be contiguous"
-            else:
-                assert tuple(block.shape) == (k, self.hop * channels) and block.stride(1) == 1
-            _lib.check(self._lib.dz_ring_push_rows_pcm(self._h, block.data_ptr(), block.stride(0) * block.element_size(),
-                                                       fmt, int(channels), mode, arr, k, cur), "dz_ring_push_rows_pcm")
+                raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks (expected float32, int16 or int32; "
+                                "uint8 blocks need format='u8' | 'ulaw' | 'alaw')")
+        if format not in PCM_FORMATS:
+            raise ValueError(f"AudioRing.push_rows: format={format!r} (expected one of {tuple(PCM_FORMATS)})")
+        fmt, dtype = PCM_FORMATS[format]
+        if torch.from_numpy(np.zeros(0, dtype)).dtype != block.dtype:
+            raise TypeError(f"AudioRing.push_rows: {block.dtype} blocks for format={format!r} (expected {dtype.name})")
+        if block.dim() == 3:
+            assert tuple(block.shape) == (k, self.hop, channels) and block.stride(2) == 1 \
+                and block.stride(1) == channels, "frames of a (k, hop, channels) block must be contiguous"
+        else:
+            assert tuple(block.shape) == (k, self.hop * channels) and block.stride(1) == 1
+        arr = (C.c_int * k)(*[int(r) for r in rows])
+        _lib.check(self._lib.dz_ring_push_rows_pcm(self._h, block.data_ptr(), block.stride(0) * block.element_size(), fmt,
+                                                   int(channels), self._mode(block), arr, k,
+                                                   torch.cuda.current_stream(self.device).cuda_stream),
+                   "dz_ring_push_rows_pcm")
         self._keep = (self._keep + [block])[-4:]
 
     def filled_row(self, row: int) -> int:

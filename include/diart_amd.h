@@ -817,7 +817,14 @@ typedef struct dz_ring dz_ring;
 int dz_ring_create(dz_ctx* ctx, int n_streams, int window, int hop, int slack_blocks, dz_ring** out);
 int dz_ring_reset(dz_ring* r);
 int dz_ring_destroy(dz_ring* r);
-/* block (n_streams, hop) with block_stride floats between rows; host memory (on_device = 0;
+/* The three push entry points check their arguments and share ONE path: the block is read where it
+ * lies (device memory, or pinned host memory mapped into the GPU) or lands through one asynchronous
+ * copy in one of the ring's two landing blocks, used alternately (allocated by dz_ring_create for a
+ * mono float32 block of every stream, so the default workload allocates nothing later; they grow on
+ * demand for wider client formats), and ONE kernel writes it to the ring.
+ * dz_ring_push, the lock-step push: block (n_streams, hop) with block_stride floats between rows,
+ * every stream at the common write position, one launch; afterwards every row's own position (below)
+ * is that position.  Host memory (on_device = 0;
  * pinned memory makes the copy asynchronous), device memory (on_device = 1), or pinned host memory
  * to be read in place by the GPU when the runtime can map it (on_device = 2; falls back to 0).   */
 int dz_ring_push(dz_ring* r, const float* block, long long block_stride, int on_device, void* stream);
@@ -830,7 +837,8 @@ int dz_ring_read(const dz_ring* r, float* d_out, void* stream);
  * every row has its own write position.  dz_ring_push_rows: row j of block (k, hop) is the next
  * block of stream rows[j] (distinct rows; on_device as for dz_ring_push).  dz_ring_gather: the
  * current windows of the listed streams as a dense (k, window) device batch for dz_seg_forward /
- * dz_emb_frames — each must be complete (dz_ring_filled_row).  dz_ring_reset_row: the stream left. */
+ * dz_emb_frames — each must be complete (dz_ring_filled_row); d_out rows 16-byte aligned (4-byte
+ * aligned for a ring whose hop is not a multiple of 4).  dz_ring_reset_row: the stream left. */
 int dz_ring_push_rows(dz_ring* r, const float* block, long long block_stride, int on_device,
                       const int* rows, int k, void* stream);
 /* Raw client audio: row j of `block` holds hop interleaved frames of `channels` (1 .. 8) values of
@@ -847,9 +855,12 @@ int dz_ring_push_rows(dz_ring* r, const float* block, long long block_stride, in
  *     a = b ^ 0x55; m = (a & 0x0F) << 4; s = (a >> 4) & 7; t = (s == 0) ? m + 8 : (m + 0x108) << (s - 1);
  *     L = (a & 0x80) ? t : -t;
  *   channels > 1: ((c0 + c1) + c2 ...) / (float)channels, one IEEE division;
- *   DZ_PCM_F32 with one channel: the input bits (what dz_ring_push_rows writes).
+ *   DZ_PCM_F32 with one channel: the input bits (what dz_ring_push_rows and dz_ring_push write:
+ *     the same kernel).
  * Non-finite float input passes through (a NaN in one channel makes that frame NaN).  Another
  * format value is refused.
+ * Rows and ring positions on 16-byte boundaries are moved 16 bytes per lane, others value by value;
+ * the samples do not depend on it.
  * dz_pcm_decode: the same per-frame function over one contiguous device buffer of n_frames
  * interleaved frames (d_src aligned to one value), mono float32 to d_dst, without a ring.        */
 enum { DZ_PCM_F32 = 0, DZ_PCM_S16 = 1, DZ_PCM_U8 = 2, DZ_PCM_S32 = 3, DZ_PCM_ULAW = 4, DZ_PCM_ALAW = 5 };

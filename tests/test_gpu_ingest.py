@@ -123,15 +123,20 @@ def test_lock_step_push_and_snapshot_on_an_unaligned_ring(gpu, hop):
 
 def test_mono_float_equals_the_plain_push_on_an_aligned_ring(gpu):
     """``dz_ring_push_rows_pcm`` with one float32 channel writes the bits ``dz_ring_push_rows`` writes — any bits:
-    the block is random 32-bit patterns (NaNs with payloads, denormals)."""
+    the block is random 32-bit patterns (NaNs with payloads, denormals).  The two entry points share their push path,
+    so both rings are also held against the block history in numpy."""
     n, hop = 4, 8000
     W = 10 * hop
     plain, pcm = AudioRing(n, W, hop, slack_blocks=0, device=gpu), AudioRing(n, W, hop, slack_blocks=0, device=gpu)
     rng = np.random.default_rng(2)
     out = torch.empty(n, W, device=gpu)
+    hist = [np.zeros(0, dtype=np.float32) for _ in range(n)]
     for it in range(23):
         rows = rng.permutation(n)[:int(rng.integers(1, n + 1))].tolist()
-        blk = torch.from_numpy(rng.integers(0, 2 ** 32, size=(len(rows), hop), dtype=np.uint32).view(np.float32))
+        bits = rng.integers(0, 2 ** 32, size=(len(rows), hop), dtype=np.uint32).view(np.float32)
+        for j, r in enumerate(rows):
+            hist[r] = np.concatenate([hist[r], bits[j]])[-W:]
+        blk = torch.from_numpy(bits)
         blk = blk.to(gpu) if it % 2 else blk
         plain.push_rows(blk, rows)
         arr = (C.c_int * len(rows))(*rows)
@@ -143,6 +148,7 @@ def test_mono_float_equals_the_plain_push_on_an_aligned_ring(gpu):
         if full:
             a = plain.gather(full, out).clone()
             assert torch.equal(a.view(torch.int32), pcm.gather(full, out).view(torch.int32))
+            assert same_bits(a, np.stack([hist[r] for r in full]))          # and both hold the blocks' bits
     assert full
 
 

@@ -169,6 +169,17 @@ def test_decode_pcm_of_every_code(gpu):
             # a view one frame in: the source is not 16-byte aligned, every frame takes the single-frame path
             assert same_bits(decode_pcm(dev[1:], fmt, ch), want[1:])
     rng = np.random.default_rng(0)
+    # the lane body the decode shares with the push: a lane's F = 16 / itemsize frames, one short, one over, one alone,
+    # and 256 F + 3 (a second block whose only lane holds a ragged end), against the host definition
+    for fmt, dtype in INPUT_FORMATS.items():
+        F = 16 // dtype.itemsize
+        for ch in (1, 3):
+            for n_frames in (1, F - 1, F, F + 1, 256 * F + 3):
+                v = rng.integers(0, 2 ** (8 * dtype.itemsize), size=n_frames * ch, dtype=np.uint64)
+                v = v.astype(f"<u{dtype.itemsize}").view(dtype)
+                if fmt == "f32" and ch > 1:
+                    v = rng.uniform(-1, 1, size=n_frames * ch).astype(np.float32)     # (a sum of NaNs has no one payload)
+                assert same_bits(decode_pcm(v, fmt, ch, device=gpu), pcm_to_mono(v, fmt, ch)), (fmt, ch, n_frames)
     s32 = raw_blocks(rng, "s32", 2, 1, 1, frames)[0, 0]
     assert same_bits(decode_pcm(s32, "s32", 2, device=gpu), restate(s32, "s32", 2))
     assert same_bits(decode_pcm(s32[:, :1].copy(), "s32", 1, device=gpu), restate(s32[:, :1], "s32", 1))
@@ -194,6 +205,7 @@ def test_s16_and_plain_float_pushes_write_what_they_wrote(gpu):
     rng = np.random.default_rng(7)
     s16, plain, pcm = (AudioRing(n, W, hop, slack_blocks=0, device=gpu) for _ in range(3))
     hist = np.zeros((n, 0), dtype=np.float32)
+    fhist = np.zeros((n, 0), dtype=np.float32)
     for t in range(11):
         a = rng.integers(-32768, 32768, size=(n, hop, 2), dtype=np.int16)
         a[0, 0], a[1, -1] = -32768, 32767
@@ -201,7 +213,9 @@ def test_s16_and_plain_float_pushes_write_what_they_wrote(gpu):
         s16.push_rows(blk.to(gpu) if t % 2 else blk, [1, 0], channels=2)
         hist = np.concatenate([hist, np.stack([pcm_to_mono(a[1].reshape(-1), "s16", 2),
                                                pcm_to_mono(a[0].reshape(-1), "s16", 2)])], axis=1)[:, -W:]
-        f = torch.from_numpy(rng.integers(0, 2 ** 32, size=(n, hop), dtype=np.uint32).view(np.float32))
+        bits = rng.integers(0, 2 ** 32, size=(n, hop), dtype=np.uint32).view(np.float32)
+        fhist = np.concatenate([fhist, bits], axis=1)[:, -W:]
+        f = torch.from_numpy(bits)
         f = f.to(gpu) if t % 2 else f
         plain.push_rows(f, [0, 1])
         arr = (C.c_int * n)(0, 1)
@@ -211,6 +225,7 @@ def test_s16_and_plain_float_pushes_write_what_they_wrote(gpu):
     assert same_bits(s16.gather([0, 1], out), hist)          # (block row 0 went to ring row 1)
     a = plain.gather([0, 1], out).clone()
     assert torch.equal(a.view(torch.int32), pcm.gather([0, 1], out).view(torch.int32))
+    assert same_bits(a, fhist)                               # the two entry points share their push path: numpy too
 
 
 # ---------------------------------------------------------------------------------------------- StreamServer

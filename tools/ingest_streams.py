@@ -10,13 +10,15 @@ steps after a warm-up.  Prints one JSON object; ``--out`` also writes it.
 ``--rows 0,3`` runs a subset (rows 0 and 3 use nothing but ``input_sample_rate``).  Rows 7 - 11 are the telephone
 forms: 8 kHz float32, 16-bit, mu-law, stereo A-law, and 8-bit at 16 kHz.
 
-``--kernel`` adds the push alone: 64 rows of 4 000 frames (500 ms at 8 kHz) already on the device, as mu-law bytes
-(``dz_ring_push_rows_pcm``) and as float32 (``dz_ring_push_rows``), ``--calls`` pushes between two device events that
-wait behind a long matrix product, so the launches are queued before the first one runs and the interval is the GPU's;
-microseconds per push (median of 5) and the bytes read and written over that time.
+``--kernel`` adds the ring kernels alone: per-row pushes of 64 rows of 4 000 frames (500 ms at 8 kHz) already on the
+device, as mu-law bytes and as float32; the lock-step push of 64 x 8 000 float32 from device memory and from mapped
+pinned memory; the gather of 64 windows of 80 000.  ``--calls`` calls between two device events that wait behind a long
+matrix product, so the launches are queued before the first one runs and the interval is the GPU's; microseconds per
+call (median of 5) and the bytes read and written over that time.
 
 ``--parent-tree DIR`` (a checkout of the parent commit with its library built) adds row 0 alone in a child process,
-this tree's and that tree's in turn, twice, in the same visit (``--tree`` is the checkout a child imports from).
+this tree's and that tree's in turn, twice, in the same visit (``--tree`` is the checkout a child imports from); with
+``--kernel`` the children time the ring kernels too.
 """
 from __future__ import annotations
 
@@ -99,19 +101,18 @@ def run_row(dev, rate, fmt, channels, rings, steps, runs, streams=64):
 
 
 def push_kernel(dev, calls, rows=64, hop=4000):
-    """The push alone, from device memory: mu-law bytes through the PCM kernel, float32 through the plain one."""
+    """The ring kernels alone.  Per-row pushes of ``rows`` x ``hop`` frames from device memory, as mu-law bytes and as
+    float32; the lock-step push of ``rows`` x 8 000 float32 from device memory and from mapped pinned memory; the gather
+    of ``rows`` windows of 80 000.  Each: ``calls`` calls queued behind a long matrix product, between two device
+    events, microseconds per call, 5 runs."""
     from diart_amd.pipeline import AudioRing
     rng = np.random.default_rng(1)
-    blocks = {"ulaw": torch.from_numpy(rng.integers(0, 256, (rows, hop), dtype=np.uint8)).to(dev),
-              "f32": torch.from_numpy(rng.uniform(-1, 1, (rows, hop)).astype(np.float32)).to(dev)}
     big = torch.randn(8192, 8192, device=dev)
-    out = {}
-    for fmt, blk in blocks.items():
-        ring = AudioRing(rows, 10 * hop, hop, slack_blocks=0, device=dev)
-        kw = {} if fmt == "f32" else {"format": fmt}
-        idx = list(range(rows))
+    idx = list(range(rows))
+
+    def timed(call, bytes_read, bytes_written):
         for _ in range(20):
-            ring.push_rows(blk, idx, **kw)
+            call()
         us = []
         for _ in range(5):
             torch.cuda.synchronize()
@@ -120,15 +121,30 @@ def push_kernel(dev, calls, rows=64, hop=4000):
                 big @ big                       # the launches below are queued while this runs
             e0.record()
             for _ in range(calls):
-                ring.push_rows(blk, idx, **kw)
+                call()
             e1.record()
             torch.cuda.synchronize()
             us.append(e0.elapsed_time(e1) * 1e3 / calls)
-        moved = rows * hop * (blk.element_size() + 8)          # the block read once, every sample written twice
         t = float(np.median(us))
-        out[fmt] = {"us_per_push": round(t, 3), "us_runs": [round(u, 3) for u in us], "bytes_read": rows * hop * blk.element_size(),
-                    "bytes_written": rows * hop * 8, "bytes_per_s": round(moved / (t * 1e-6), 1)}
-    return {"rows": rows, "frames_per_row": hop, "calls": calls, **out}
+        return {"us_per_call": round(t, 3), "us_runs": [round(u, 3) for u in us], "bytes_read": bytes_read,
+                "bytes_written": bytes_written, "bytes_per_s": round((bytes_read + bytes_written) / (t * 1e-6), 1)}
+
+    out = {}
+    blocks = {"ulaw": torch.from_numpy(rng.integers(0, 256, (rows, hop), dtype=np.uint8)).to(dev),
+              "f32": torch.from_numpy(rng.uniform(-1, 1, (rows, hop)).astype(np.float32)).to(dev)}
+    for fmt, blk in blocks.items():
+        ring = AudioRing(rows, 10 * hop, hop, slack_blocks=0, device=dev)
+        kw = {} if fmt == "f32" else {"format": fmt}
+        # the block read once, every sample written twice
+        out[fmt] = timed(lambda: ring.push_rows(blk, idx, **kw), rows * hop * blk.element_size(), rows * hop * 8)
+    W, step = 80000, 8000
+    host = torch.from_numpy(rng.uniform(-1, 1, (rows, step)).astype(np.float32))
+    for name, blk in (("lock_step_device", host.to(dev)), ("lock_step_pinned", host.pin_memory())):
+        ring = AudioRing(rows, W, step, device=dev)
+        out[name] = timed(lambda: ring.push(blk), rows * step * 4, rows * step * 8)
+    batch = torch.empty(rows, W, device=dev)
+    out["gather"] = timed(lambda: ring.gather(idx, batch), rows * W * 4, rows * W * 4)      # (the ring is full by now)
+    return {"rows": rows, "frames_per_row": hop, "lock_step_hop": step, "gather_window": W, "calls": calls, **out}
 
 
 def main():
@@ -136,7 +152,7 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--rows", type=str, default=None, help="comma-separated row numbers (default: all)")
-    ap.add_argument("--kernel", action="store_true", help="also time the push alone (ulaw and f32 rows on the device)")
+    ap.add_argument("--kernel", action="store_true", help="also time the ring kernels alone")
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--tree", type=str, default=str(Path(__file__).resolve().parent.parent),
                     help="the checkout diart_amd is imported from")
@@ -154,18 +170,22 @@ def main():
         # keeps its GPU state), this tree and the parent's in turn, twice; a child's last line is its JSON object
         def alone(tree):
             r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--tree", tree, "--rows", "0",
-                                "--steps", str(a.steps), "--runs", str(a.runs)], capture_output=True, text=True,
-                               timeout=600)
+                                "--steps", str(a.steps), "--runs", str(a.runs), "--calls", str(a.calls)]
+                               + (["--kernel"] if a.kernel else []), capture_output=True, text=True, timeout=600)
             if r.returncode != 0:
                 raise RuntimeError(f"the run of {tree} failed ({r.returncode}):\n{r.stderr[-2000:]}")
-            return json.loads(r.stdout.strip().splitlines()[-1])["rows"][0]
+            return json.loads(r.stdout.strip().splitlines()[-1])
 
         here, parent = [], []
         for _ in range(2):
             here.append(alone(a.tree))
             parent.append(alone(a.parent_tree))
-        res["default_row_alone"] = {"this_tree": here, "parent_tree": parent, "xrt_runs": {
-            "this_tree": [x for r in here for x in r["xrt_runs"]], "parent_tree": [x for r in parent for x in r["xrt_runs"]]}}
+        rows_of = {"this_tree": [r["rows"][0] for r in here], "parent_tree": [r["rows"][0] for r in parent]}
+        res["default_row_alone"] = {**rows_of, "xrt_runs": {k: [x for r in v for x in r["xrt_runs"]]
+                                                            for k, v in rows_of.items()}}
+        if a.kernel:
+            res["ring_kernels_alone"] = {"this_tree": [r["push_kernel"] for r in here],
+                                         "parent_tree": [r["push_kernel"] for r in parent]}
     print(json.dumps(res))
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
