@@ -47,7 +47,7 @@ def build(force: bool = False, verbose: bool = False, experiments: bool = False)
     hipcc = _hipcc()
     objdir = HERE / "build" / ("exp" if experiments else "ship")
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [CSRC / "dz_common.h", CSRC / "dz_embed.h", CSRC / "dz_sincnet.h", CSRC / "hostpool.h", CSRC / "tune_core.h", CSRC / "clu_core.h", HERE.parent / "include" / "diart_amd.h",
+    headers = [CSRC / "dz_common.h", CSRC / "dz_embed.h", CSRC / "dz_sincnet.h", CSRC / "hostpool.h", CSRC / "tune_core.h", CSRC / "clu_core.h", CSRC / "tail_core.h", HERE.parent / "include" / "diart_amd.h",
                HERE.parent / "include" / "diart_amd_experiments.h"]
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", f"-I{CSRC}"]
     sources, lib = list(SOURCES), LIB

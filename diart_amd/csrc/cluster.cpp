@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <cstring>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "clu_core.h"
@@ -18,7 +17,6 @@
 #pragma clang fp contract(off)
 
 void dz_set_error(const char* fmt, ...);
-extern "C" const char* dz_last_error(void);
 
 namespace {
 
@@ -233,45 +231,18 @@ extern "C" int dz_clu_step_batch(dz_clu** clus, int n, const float* seg, int fra
             dz_set_error("dz_clu_step_batch: handles must share max_speakers");
             return 2;
         }
-    auto run = [&](int i) -> int {
+    // Streams are independent, so on the pool the ones that succeeded HAVE been stepped; the caller decides what to
+    // do with the failed ones.  On one thread the first failure ends the call with the step's own message.
+    const dz_host_failure f = dz_host_parallel_rc(n, num_threads, [&](int, int i) {
         return step(clus[i], seg + (size_t)i * frames * k_local, frames, k_local,
                     emb + (size_t)i * k_local * dim, dim,
                     scores_out ? scores_out + (size_t)i * frames * G : nullptr,
                     assign_out ? assign_out + (size_t)i * k_local : nullptr);
-    };
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > n) nt = n;
-    if (nt == 1) {
-        for (int i = 0; i < n; ++i) {
-            const int rc = run(i);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    // the error text is thread local: a failing worker copies its own message (and which stream
-    // it was) before another stream's overwrites it.  Streams are independent, so the ones that
-    // succeeded HAVE been stepped; the caller decides what to do with the failed ones.
-    std::vector<int> rcs(nt, 0), who(nt, -1);
-    std::vector<std::string> msgs(nt);
-    dz_host_parallel(n, nt, [&](int t, int i) {
-        const int rc = run(i);
-        if (rc && (!rcs[t] || i < who[t])) {
-            rcs[t] = rc;
-            who[t] = i;
-            msgs[t] = dz_last_error();
-        }
     });
-    int first = -1;
-    for (int t = 0; t < nt; ++t)
-        if (rcs[t] && (first < 0 || who[t] < who[first])) first = t;
-    if (first >= 0) {
-        int failed = 0;
-        for (int rc : rcs) failed += rc != 0;
-        dz_set_error("dz_clu_step_batch: stream %d of %d failed (code %d): %s%s", who[first], n, rcs[first],
-                     msgs[first].c_str(), failed > 1 ? " (other streams failed too)" : "");
-        return rcs[first];
-    }
-    return 0;
+    if (f.code && dz_host_threads(num_threads, n) > 1)
+        dz_set_error("dz_clu_step_batch: stream %d of %d failed (code %d): %s%s", f.index, n, f.code, f.message.c_str(),
+                     f.failed > 1 ? " (other streams failed too)" : "");
+    return f.code;
 }
 extern "C" int dz_clu_get_centers(dz_clu* c, double* out, int dim) {
     if (!c) return 2;

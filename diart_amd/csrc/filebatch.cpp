@@ -9,13 +9,19 @@
 // count[i] consecutive windows starting at row row0[i]; a host thread takes a whole file and walks
 // its windows in order (dz_clu_step -> dz_tail_step), files run in parallel.  No barrier per window.
 #include <cstddef>
-#include <string>
 #include <vector>
 
 #include "../../include/diart_amd.h"
 #include "hostpool.h"
 
 void dz_set_error(const char* fmt, ...);
+
+// A file stops at its first failing window.  On the pool the other files are walked to the end of their rows
+// all the same; on one thread the call ends there.  The lowest failing file is reported with its own message.
+static int file_fail(const char* who, int n_files, const dz_host_failure& f) {
+    if (f.code) dz_set_error("%s: file %d of %d failed (code %d): %s", who, f.index, n_files, f.code, f.message.c_str());
+    return f.code;
+}
 
 extern "C" int dz_file_step_batch(dz_clu** clus, dz_tail** tails, int n_files, const int* row0,
                                   const int* count, const float* seg, int frames, int k_local,
@@ -36,45 +42,25 @@ extern "C" int dz_file_step_batch(dz_clu** clus, dz_tail** tails, int n_files, c
             dz_set_error("dz_file_step_batch: bad handle / row range of file %d", i);
             return 2;
         }
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > n_files) nt = n_files;
+    const int nt = dz_host_threads(num_threads, n_files);
     const size_t F = (size_t)frames, G = (size_t)max_speakers;
     // per worker: the permuted scores of the current window and the aggregated region (discarded:
     // the RTTM needs the speech turns only)
     std::vector<std::vector<double>> scores(nt, std::vector<double>(F * G)), agg(nt, std::vector<double>((F + 2) * G));
-    // the error text is thread local: a failing worker keeps its own message and which file it was
-    std::vector<int> rcs(nt, 0), who(nt, -1);
-    std::vector<std::string> msgs(nt);
-    auto run = [&](int worker, int i) {
-        int rows = 0;
+    return file_fail("dz_file_step_batch", n_files, dz_host_parallel_rc(n_files, nt, [&](int worker, int i) {
+        int rows = 0, rc = 0;
         double t0 = 0.0, res = 0.0;
         std::vector<int> assign((size_t)k_local);
-        for (int t = 0; t < count[i] && !rcs[worker]; ++t) {
+        for (int t = 0; t < count[i] && !rc; ++t) {
             const size_t r = (size_t)row0[i] + t;
-            int rc = dz_clu_step(clus[i], seg + r * F * k_local, frames, k_local, emb + r * (size_t)k_local * dim, dim,
-                                 scores[worker].data(), assign_out ? assign_out + r * k_local : assign.data());
+            rc = dz_clu_step(clus[i], seg + r * F * k_local, frames, k_local, emb + r * (size_t)k_local * dim, dim,
+                             scores[worker].data(), assign_out ? assign_out + r * k_local : assign.data());
             if (!rc)
                 rc = dz_tail_step(tails[i], scores[worker].data(), chunk_start[r], resolution, agg[worker].data(), &rows,
                                   &t0, &res, turns_out + r * (size_t)max_turns * 3, max_turns, nturns_out + r);
-            if (rc) {
-                rcs[worker] = rc;
-                who[worker] = i;
-                msgs[worker] = dz_last_error();
-            }
         }
-    };
-    if (nt == 1) {
-        for (int i = 0; i < n_files && !rcs[0]; ++i) run(0, i);
-    } else {
-        dz_host_parallel(n_files, nt, run);
-    }
-    for (int t = 0; t < nt; ++t)
-        if (rcs[t]) {
-            dz_set_error("dz_file_step_batch: file %d of %d failed (code %d): %s", who[t], n_files, rcs[t],
-                         msgs[t].c_str());
-            return rcs[t];
-        }
-    return 0;
+        return rc;
+    }));
 }
 
 // The VoiceActivityDetection sibling: no clustering, the (frames,) speech track of a window is the one "speaker" of its
@@ -96,39 +82,20 @@ extern "C" int dz_file_vad_step_batch(dz_tail** tails, int n_files, const int* r
             dz_set_error("dz_file_vad_step_batch: bad handle / row range of file %d", i);
             return 2;
         }
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > n_files) nt = n_files;
+    const int nt = dz_host_threads(num_threads, n_files);
     const size_t F = (size_t)frames;
     // per worker: the current window's track in fp64 and the aggregated region (discarded, as above)
     std::vector<std::vector<double>> scores(nt, std::vector<double>(F)), agg(nt, std::vector<double>(F + 2));
-    std::vector<int> rcs(nt, 0), who(nt, -1);
-    std::vector<std::string> msgs(nt);
-    auto run = [&](int worker, int i) {
-        int rows = 0;
+    return file_fail("dz_file_vad_step_batch", n_files, dz_host_parallel_rc(n_files, nt, [&](int worker, int i) {
+        int rows = 0, rc = 0;
         double t0 = 0.0, res = 0.0;
-        for (int t = 0; t < count[i] && !rcs[worker]; ++t) {
+        for (int t = 0; t < count[i] && !rc; ++t) {
             const size_t r = (size_t)row0[i] + t;
             double* s = scores[worker].data();
             for (size_t f = 0; f < F; ++f) s[f] = (double)track[r * F + f];
-            const int rc = dz_tail_step(tails[i], s, chunk_start[r], resolution, agg[worker].data(), &rows, &t0, &res,
-                                        turns_out + r * (size_t)max_turns * 3, max_turns, nturns_out + r);
-            if (rc) {
-                rcs[worker] = rc;
-                who[worker] = i;
-                msgs[worker] = dz_last_error();
-            }
+            rc = dz_tail_step(tails[i], s, chunk_start[r], resolution, agg[worker].data(), &rows, &t0, &res,
+                              turns_out + r * (size_t)max_turns * 3, max_turns, nturns_out + r);
         }
-    };
-    if (nt == 1) {
-        for (int i = 0; i < n_files && !rcs[0]; ++i) run(0, i);
-    } else {
-        dz_host_parallel(n_files, nt, run);
-    }
-    for (int t = 0; t < nt; ++t)
-        if (rcs[t]) {
-            dz_set_error("dz_file_vad_step_batch: file %d of %d failed (code %d): %s", who[t], n_files, rcs[t],
-                         msgs[t].c_str());
-            return rcs[t];
-        }
-    return 0;
+        return rc;
+    }));
 }

@@ -11,6 +11,8 @@
 #include <thread>
 #include <vector>
 
+extern "C" const char* dz_last_error(void);
+
 namespace {
 
 constexpr int MAX_WORKERS = 63;
@@ -127,6 +129,33 @@ void dz_host_parallel(int n, int threads, const std::function<void(int, int)>& f
         std::lock_guard<std::mutex> lk(p->mu);
         p->cur.reset();
     }
+}
+
+dz_host_failure dz_host_parallel_rc(int n, int threads, const std::function<int(int, int)>& fn) {
+    threads = dz_host_threads(threads, n);
+    std::vector<dz_host_failure> per(threads > 1 ? threads : 1);
+    auto run = [&](int worker, int i) {
+        const int rc = fn(worker, i);
+        dz_host_failure& f = per[worker];
+        if (rc && (!f.failed++ || i < f.index)) {
+            f.index = i;
+            f.code = rc;
+            f.message = dz_last_error();
+        }
+        return rc;
+    };
+    if (threads <= 1) {
+        for (int i = 0; i < n && !run(0, i); ++i) {}
+    } else {
+        dz_host_parallel(n, threads, run);
+    }
+    int first = 0, failed = 0;
+    for (int w = 0; w < (int)per.size(); ++w) {
+        failed += per[w].failed;
+        if (per[w].failed && (!per[first].failed || per[w].index < per[first].index)) first = w;
+    }
+    per[first].failed = failed;
+    return std::move(per[first]);
 }
 
 extern "C" int dz_host_pool_set_spin(int microseconds) {

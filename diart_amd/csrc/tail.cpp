@@ -16,16 +16,19 @@
 // first / last row, and the sums run in the buffer order numpy's axis-0 reduction uses, so the
 // aggregated scores are bit-identical to the reference's and the speech turns come out of one
 // pass over rising / falling edges of `score > threshold`.
-#include <math.h>
+//
+// The crop rule, the geometry of a step and the edge walk are tail_core.h's, the text the tuner's
+// plan and its GPU kernels compile too.  What is here is what a handle adds: the buffers of a
+// stream, the strategies over them, the speech turns as (start, end, speaker), the C entry points.
 #include <stddef.h>
 #include <string.h>
 
 #include <deque>
 #include <new>
-#include "hostpool.h"
 #include <vector>
 
-#include "../../include/diart_amd.h"
+#include "hostpool.h"
+#include "tail_core.h"
 
 void dz_set_error(const char* fmt, ...);
 
@@ -36,33 +39,6 @@ struct Buffer {
     double start, res;         // frame grid: frame i covers [start + i*res, start + (i+1)*res)
 };
 
-inline double seg_duration(double s, double e) { return e > s ? e - s : 0.0; }
-
-// pyannote.core SlidingWindow.samples(from_duration, mode)
-inline long samples_for(double from_duration, double dur, double step, int mode) {
-    if (mode == DZ_CROP_STRICT) return (long)floor((from_duration - dur) / step) + 1;
-    if (mode == DZ_CROP_LOOSE) return (long)floor((from_duration + dur) / step);
-    return (long)nearbyint(from_duration / step);  // center; np.rint = round half to even
-}
-inline long closest_frame(double t, double start, double dur, double step) {
-    return (long)nearbyint((t - start - 0.5 * dur) / step);
-}
-// first frame index and frame count of focus [fs, fe) on the grid (start, res) for a crop with
-// fixed = focus duration
-inline void crop_range(double fs, double fe, double start, double res, int mode, long* first,
-                       long* count) {
-    long i;
-    if (mode == DZ_CROP_LOOSE)
-        i = (long)ceil((fs - res - start) / res);
-    else if (mode == DZ_CROP_STRICT)
-        i = (long)ceil((fs - start) / res);
-    else
-        i = closest_frame(fs, start, res, res);
-    *first = i;
-    *count = samples_for(seg_duration(fs, fe), res, res, mode);
-}
-inline int clip(long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
-
 }  // namespace
 
 struct dz_tail {
@@ -71,6 +47,7 @@ struct dz_tail {
     std::vector<double> hamming;  // [F]
     std::deque<Buffer> buffers;
     std::vector<double> num, den;  // scratch
+    std::vector<long> first;       // the region's first row in every buffer
 };
 
 namespace {
@@ -85,33 +62,32 @@ int tail_step(dz_tail* t, const double* scores, double chunk_start, double res, 
     nb.data.assign(scores, scores + (size_t)F * G);
     nb.start = chunk_start;
     nb.res = res;
-    // buffers[-1].extent.end - latency  (aggregation.py:214-216); extent = start + (n-1)*step + duration
-    const double ext_end = nb.start + (F - 1) * nb.res + nb.res;
-    const double rs = ext_end - t->latency;
-    const double re = rs + t->step;
     const int nbuf = (int)t->buffers.size();
-    const int max_rows = F + 2;
-
-    long first0, count;
-    crop_range(rs, re, t->buffers[0].start, t->buffers[0].res, t->mode, &first0, &count);
-    if (count < 1 || count > max_rows) return 4;
-    int rows = (int)count;
+    if (t->first.size() < (size_t)nbuf) t->first.resize(nbuf);  // (nwin; more only after a step that failed)
+    TailGeometry geo;
+    // "first" reads buffer 0 alone; for the others np.stack would raise in the reference on unequal crops
+    if (tail_geometry(F, t->step, t->latency, t->mode, nbuf, t->strategy != DZ_AGG_FIRST,
+                      [&](int b, double* start, double* r) {
+                          *start = t->buffers[b].start;
+                          *r = t->buffers[b].res;
+                      },
+                      &geo, t->first.data()))
+        return 4;
+    int rows = geo.rows;
     // ---- aggregate the region over the buffers ---------------------------------------
     if (t->strategy == DZ_AGG_FIRST) {
         const Buffer& b = t->buffers[0];
         for (int r = 0; r < rows; ++r)
-            memcpy(agg_out + (size_t)r * G, b.data.data() + (size_t)clip(first0 + r, F - 1) * G,
+            memcpy(agg_out + (size_t)r * G, b.data.data() + (size_t)tail_clip(t->first[0] + r, F - 1) * G,
                    sizeof(double) * G);
     } else {
         t->num.assign((size_t)rows * G, 0.0);
         t->den.assign(rows, 0.0);
         for (int bi = 0; bi < nbuf; ++bi) {
             const Buffer& b = t->buffers[bi];
-            long first, cnt;
-            crop_range(rs, re, b.start, b.res, t->mode, &first, &cnt);
-            if (cnt != count) return 4;  // np.stack would raise in the reference
+            const long first = t->first[bi];
             for (int r = 0; r < rows; ++r) {
-                const int row = clip(first + r, F - 1);
+                const int row = tail_clip(first + r, F - 1);
                 const double* src = b.data.data() + (size_t)row * G;
                 double* dst = t->num.data() + (size_t)r * G;
                 if (t->strategy == DZ_AGG_HAMMING) {
@@ -136,29 +112,22 @@ int tail_step(dz_tail* t, const double* scores, double chunk_start, double res, 
             for (int g = 0; g < G; ++g) agg_out[(size_t)r * G + g] = t->num[(size_t)r * G + g] / d;
         }
     }
-    double out_start = rs;
-    double out_res = seg_duration(rs, re) / rows;
     // ---- first buffer of a stream: everything up to the end of the region (aggregation.py:188-211)
-    if (nbuf == 1 && t->buffers[0].start == 0.0) {
+    if (geo.pre > 0) {
         const Buffer& b = t->buffers[0];
-        long f1, c1;
-        crop_range(0.0, re, b.start, b.res, t->mode, &f1, &c1);
-        if (c1 < rows || c1 > max_rows) return 4;
-        const int all = (int)c1;
         // the aggregated rows become the LAST `rows` rows; move them first (ranges may overlap)
-        memmove(agg_out + (size_t)(all - rows) * G, agg_out, sizeof(double) * (size_t)rows * G);
-        for (int r = 0; r < all - rows; ++r)
-            memcpy(agg_out + (size_t)r * G, b.data.data() + (size_t)clip(f1 + r, F - 1) * G,
+        memmove(agg_out + (size_t)geo.pre * G, agg_out, sizeof(double) * (size_t)rows * G);
+        for (int r = 0; r < geo.pre; ++r)
+            memcpy(agg_out + (size_t)r * G, b.data.data() + (size_t)tail_clip(geo.pre_first + r, F - 1) * G,
                    sizeof(double) * G);
-        rows = all;
-        out_start = 0.0;
-        out_res = re / rows;
+        rows += geo.pre;
     }
+    const double out_start = geo.out_start, out_res = geo.out_res;
     *rows_out = rows;
     *t0_out = out_start;
     *res_out = out_res;
     // ---- Binarize (utils.py:43-59): strict `>`; a turn spans [middle(first active frame),
-    // middle(first inactive frame after it)), the frame after the last one closing open turns
+    // middle(first inactive frame after it))
     int nt = 0;
     if (turns_out) {
         auto middle = [&](int i) {
@@ -166,19 +135,17 @@ int tail_step(dz_tail* t, const double* scores, double chunk_start, double res, 
             return 0.5 * (s + (s + out_res));
         };
         for (int g = 0; g < G; ++g) {
-            int onset = -1;
-            for (int r = 0; r <= rows; ++r) {
-                const bool on = r < rows && agg_out[(size_t)r * G + g] > t->threshold;
-                if (on && onset < 0) onset = r;
-                if (!on && onset >= 0) {
-                    if (nt >= max_turns) return 5;
+            const bool room = tail_edge_walk(
+                rows, [&](int r) { return agg_out[(size_t)r * G + g] > t->threshold; },
+                [&](int onset, int r) {
+                    if (nt >= max_turns) return false;
                     turns_out[3 * nt + 0] = middle(onset);
                     turns_out[3 * nt + 1] = middle(r);
                     turns_out[3 * nt + 2] = (double)g;
                     ++nt;
-                    onset = -1;
-                }
-            }
+                    return true;
+                });
+            if (!room) return 5;
         }
     }
     if (nturns_out) *nturns_out = nt;
@@ -260,24 +227,10 @@ extern "C" int dz_tail_step_batch(dz_tail** tails, int n, const double* scores,
             return 2;
         }
     const size_t mr = (size_t)F + 2;
-    auto run = [&](int i) -> int {
+    return tail_fail("dz_tail_step_batch", dz_host_parallel_rc(n, num_threads, [&](int, int i) {
         return tail_step(tails[i], scores + (size_t)i * F * G, chunk_start[i], resolution[i],
                          agg_out + (size_t)i * mr * G, rows_out + i, t0_out + i, res_out + i,
                          turns_out ? turns_out + (size_t)i * max_turns * 3 : nullptr, max_turns,
                          nturns_out ? nturns_out + i : nullptr);
-    };
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > n) nt = n;
-    std::vector<int> rcs(nt, 0);
-    if (nt == 1) {
-        for (int i = 0; i < n && !rcs[0]; ++i) rcs[0] = run(i);
-    } else {
-        dz_host_parallel(n, nt, [&](int k, int i) {
-            const int rc = run(i);
-            if (rc && !rcs[k]) rcs[k] = rc;
-        });
-    }
-    for (int rc : rcs)
-        if (rc) return tail_fail("dz_tail_step_batch", rc);
-    return 0;
+    }).code);
 }

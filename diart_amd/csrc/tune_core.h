@@ -2,7 +2,9 @@
 // chain of clustering steps, tc_row_mask turns the assignments into one packed output row of the tail.  The
 // decisions of a step are clu_core.h's, the text dz_clu_step runs too, here on its fixed store (K <= TC_KMAX,
 // G <= TC_GMAX, the whole state in LDS); what this file adds is how the lanes of a wavefront share the arithmetic that
-// feeds them (each norm and each of the K x G distances summed by ONE lane in the core's order).  Host and device
+// feeds them (each norm and each of the K x G distances summed by ONE lane in the core's order).  The rules of the
+// tail are tail_core.h's, the text dz_tail_step runs too: the clipped rows, the Hamming-weighted sum of a row, the
+// edge walk of Binarize; what this file adds there is the plan's layout and the merging of the turns.  Host and device
 // compile this text: k_tune.hip for the kernels, tune_score.cpp for backend="core", which tests/test_tune_host.py
 // holds against dz_clu_step + dz_tail_step.  The VoiceActivityDetection half (tc_vad_*, behind the replay) is
 // k_tune_vad.hip's and dz_tune_vad_host's in the same way, and the scoring of the diarization masks (tc_score_*, at the
@@ -10,6 +12,7 @@
 #pragma once
 #include "../../include/diart_amd.h"
 #include "clu_core.h"
+#include "tail_core.h"
 
 #pragma clang fp contract(off)
 
@@ -80,12 +83,9 @@ TC_HD int tc_chain(const dz_tune_desc& d, int n, double tau, double rho, double 
     return -1;
 }
 
-TC_HD int tc_clip(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // The hypothesis of packed output row p under one trial: bit g = the aggregated score of global speaker g is
-// > tau (tail.cpp: Hamming-weighted sum over the step's buffers in order, divided by the sum of the weights; the
-// first chunk's prepended rows are that chunk's own scores).  A buffer in which g has no local speaker adds
-// h * 0.0 on the host: leaving that addition out changes at most the sign of a zero, which no comparison sees.
+// > tau (the tail's Hamming-weighted sum over the step's buffers divided by the sum of the weights, both
+// tail_core.h's; the first chunk's prepended rows are that chunk's own scores).
 TC_HD unsigned tc_row_mask(const dz_tune_desc& d, int p, double tau, const signed char* assign /* this trial's */) {
     const int K = d.K, F = d.F, G = d.G;
     const int c = d.row_chunk[p], r = p - d.row_off[c];
@@ -94,7 +94,7 @@ TC_HD unsigned tc_row_mask(const dz_tune_desc& d, int p, double tau, const signe
     const unsigned all = G >= 32 ? 0xffffffffu : ((1u << G) - 1u);
     unsigned out = 0, seen = 0;
     if (r < pre) {
-        const int row = tc_clip(plan[2] + r, F - 1);
+        const int row = tail_clip(plan[2] + r, F - 1);
         for (int k = 0; k < K; ++k) {
             const int g = assign[(long)c * K + k];
             if (g < 0) continue;
@@ -104,29 +104,21 @@ TC_HD unsigned tc_row_mask(const dz_tune_desc& d, int p, double tau, const signe
     } else {
         const int ra = r - pre, cb0 = c - nbuf + 1;
         double den = 0.0;
-        for (int b = 0; b < nbuf; ++b) {
-            const double h = d.hamming[tc_clip(plan[4 + b] + ra, F - 1)];
-            den = b == 0 ? h : den + h;
+        tail_hamming_num(d.seg, d.hamming, F, K, plan + 4, cb0, nbuf, ra, [](long) { return -1; }, &den);
+        for (int b = 0; b < nbuf; ++b)
             for (int k = 0; k < K; ++k) {
                 const int g = assign[(long)(cb0 + b) * K + k];
                 if (g >= 0) seen |= 1u << g;
             }
-        }
         for (unsigned m = seen; m; m &= m - 1) {
             const int g = __builtin_ctz(m);
-            double num = 0.0;
-            bool first = true;
-            for (int b = 0; b < nbuf; ++b) {
-                const long cb = cb0 + b;
+            auto local = [&](long cb) {
                 int ks = -1;
                 for (int k = 0; k < K; ++k)
                     if (assign[cb * K + k] == g) ks = k;
-                if (ks < 0) continue;
-                const int row = tc_clip(plan[4 + b] + ra, F - 1);
-                const double term = d.hamming[row] * (double)d.seg[(cb * F + row) * K + ks];
-                num = first ? term : num + term;
-                first = false;
-            }
+                return ks;
+            };
+            const double num = tail_hamming_num(d.seg, d.hamming, F, K, plan + 4, cb0, nbuf, ra, local, nullptr);
             if (tc_div(num, den) > tau) out |= 1u << g;
         }
     }
@@ -145,17 +137,10 @@ TC_HD double tc_vad_row(const dz_tune_desc& d, int p) {
     const int c = d.row_chunk[p], r = p - d.row_off[c];
     const int* plan = d.plan + (long)c * (4 + d.nwin);
     const int pre = plan[1], nbuf = plan[3];
-    if (r < pre) return (double)d.seg[(long)c * F + tc_clip(plan[2] + r, F - 1)];
-    const int ra = r - pre;
-    const long cb0 = c - nbuf + 1;
-    double den = 0.0, num = 0.0;
-    for (int b = 0; b < nbuf; ++b) {
-        const int row = tc_clip(plan[4 + b] + ra, F - 1);
-        const double h = d.hamming[row];
-        const double term = h * (double)d.seg[(cb0 + b) * F + row];
-        den = b == 0 ? h : den + h;
-        num = b == 0 ? term : num + term;
-    }
+    if (r < pre) return (double)d.seg[(long)c * F + tail_clip(plan[2] + r, F - 1)];
+    double den = 0.0;
+    const double num =
+        tail_hamming_num(d.seg, d.hamming, F, 1, plan + 4, c - nbuf + 1, nbuf, r - pre, [](long) { return 0; }, &den);
     return tc_div(num, den);
 }
 
@@ -171,8 +156,8 @@ struct TcVadEnd {
 };
 
 // Steps [c_lo, c_hi) of one file, in order.  Row p of the packed rows is active when on(p); a turn runs
-// from mid[onset] to mid[first inactive row] (the row after the step's last closes an open turn; mids holds rows + 1
-// values per step), turns no longer than 1e-6 are dropped (Segment.__bool__).  Turns arrive sorted by start (the
+// from mid[onset] to mid[first inactive row] (tail_edge_walk: the row after the step's last closes an open turn; mids
+// holds rows + 1 values per step), turns no longer than 1e-6 are dropped (Segment.__bool__).  Turns arrive sorted by start (the
 // cache checks that the steps' grids are), so Annotation.support(collar) is a running maximum: a turn whose gap to
 // `end` is <= 1e-6 or < collar extends the covered span from `end` to its own end (if that is later), any other
 // turn opens a new span.  Every turn therefore adds the cells [from, its end cell) with from = the cell of `end`
@@ -184,30 +169,25 @@ TC_HD TcVadEnd tc_turn_walk(On on_row, Add add, const int* row_off, const double
         const int p = row_off[c], rows = row_off[c + 1] - p;
         const double* mid = mids + (long)p + c;
         const int* cell = mid_cell + (long)p + c;
-        int onset = -1;
-        for (int r = 0; r <= rows; ++r) {
-            const bool on = r < rows && on_row(p + r);
-            if (on && onset < 0) onset = r;
-            if (!on && onset >= 0) {
-                const double s = mid[onset], e = mid[r];
-                if (e - s > 1e-6) {
-                    const double gap = s - end.e;
-                    int from = cell[onset];
-                    bool adds = true;
-                    if (gap <= 1e-6 || gap < collar) {
-                        from = end.cell;
-                        adds = e > end.e;
-                    }
-                    if (adds) {
-                        const int to = cell[r];
-                        add(from, to);
-                        end.e = e;
-                        end.cell = to;
-                    }
+        tail_edge_walk(rows, [&](int r) { return on_row(p + r); }, [&](int onset, int r) {
+            const double s = mid[onset], e = mid[r];
+            if (e - s > 1e-6) {
+                const double gap = s - end.e;
+                int from = cell[onset];
+                bool adds = true;
+                if (gap <= 1e-6 || gap < collar) {
+                    from = end.cell;
+                    adds = e > end.e;
                 }
-                onset = -1;
+                if (adds) {
+                    const int to = cell[r];
+                    add(from, to);
+                    end.e = e;
+                    end.cell = to;
+                }
             }
-        }
+            return true;
+        });
     }
     return end;
 }

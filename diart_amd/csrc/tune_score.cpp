@@ -1,7 +1,8 @@
 // Host side of the hyper-parameter tuner:
 //
-//   dz_tune_plan         what the output tail (tail.cpp: Hamming aggregation, "loose" cropping) does at every step of a
-//                        file that does not depend on the scores: rows, buffers, cropped rows, the first-chunk prepend
+//   dz_tune_plan         what the output tail (Hamming aggregation, "loose" cropping) does at every step of a file that
+//                        does not depend on the scores: rows, buffers, cropped rows, the first-chunk prepend.  A loop
+//                        over tail_core.h's tail_geometry, the function dz_tail_step calls over its own buffers
 //   dz_tune_replay_host  T x N (trial, file) chains on host threads, either through the existing handles (dz_clu_step ->
 //                        dz_tail_step: the yardstick of the GPU kernels and the backend of a machine without a GPU) or
 //                        through tune_core.h, the text the kernels are compiled from (the clustering decisions are
@@ -25,16 +26,8 @@
 #include "hostpool.h"
 
 void dz_set_error(const char* fmt, ...);
-extern "C" const char* dz_last_error(void);
 
 namespace {
-
-// tail.cpp crop_range / samples_for, "loose"
-inline double seg_duration(double s, double e) { return e > s ? e - s : 0.0; }
-inline void crop_loose(double fs, double fe, double start, double res, long* first, long* count) {
-    *first = (long)ceil((fs - res - start) / res);
-    *count = (long)floor((seg_duration(fs, fe) + res) / res);
-}
 
 struct NoBarrier {
     void operator()() const {}
@@ -62,48 +55,40 @@ extern "C" int dz_tune_plan(int chunks, int frames, double step, double latency,
         dz_set_error("dz_tune_plan: bad arguments (latency must be >= step)");
         return 2;
     }
-    const int F = frames, nwin = (int)nearbyint(latency / step), stride = 4 + nwin;
+    const int nwin = (int)nearbyint(latency / step), stride = 4 + nwin;
+    std::vector<long> first(nwin);
+    auto fits = [](long row) { return row > -(1l << 30) && row < (1l << 30); };   // the plan holds rows as int
     for (int c = 0; c < chunks; ++c) {
         if (!(resolution[c] > 0.0)) {
             dz_set_error("dz_tune_plan: chunk %d has resolution %g", c, resolution[c]);
             return 2;
         }
-        int* p = plan + (size_t)c * stride;
+        // the buffers a handle holds at step c: the last nwin chunks
         const int nbuf = c + 1 < nwin ? c + 1 : nwin, b0 = c - nbuf + 1;
-        const double ext_end = starts[c] + (F - 1) * resolution[c] + resolution[c];
-        const double rs = ext_end - latency;
-        const double re = rs + step;
-        long first0, count;
-        crop_loose(rs, re, starts[b0], resolution[b0], &first0, &count);
-        bool ok = count >= 1 && count <= F + 2;
+        TailGeometry geo;
+        bool ok = !tail_geometry(frames, step, latency, DZ_CROP_LOOSE, nbuf, true,
+                                 [&](int b, double* start, double* res) {
+                                     *start = starts[b0 + b];
+                                     *res = resolution[b0 + b];
+                                 },
+                                 &geo, first.data()) &&
+                  fits(geo.pre_first);
+        int* p = plan + (size_t)c * stride;
         for (int b = 0; b < nwin; ++b) p[4 + b] = 0;
         for (int b = 0; ok && b < nbuf; ++b) {
-            long first, cnt;
-            crop_loose(rs, re, starts[b0 + b], resolution[b0 + b], &first, &cnt);
-            ok = cnt == count && first > -(1l << 30) && first < (1l << 30);
-            p[4 + b] = (int)first;
-        }
-        int rows = (int)count, pre = 0, f1 = 0;
-        double out_start = rs, out_res = ok ? seg_duration(rs, re) / rows : 0.0;
-        if (ok && nbuf == 1 && starts[b0] == 0.0) {
-            long lf1, c1;
-            crop_loose(0.0, re, starts[b0], resolution[b0], &lf1, &c1);
-            ok = c1 >= rows && c1 <= F + 2 && lf1 > -(1l << 30) && lf1 < (1l << 30);
-            pre = (int)c1 - rows;
-            f1 = (int)lf1;
-            out_start = 0.0;
-            out_res = re / (double)(int)c1;
+            ok = fits(first[b]);
+            p[4 + b] = (int)first[b];
         }
         if (!ok) {
             dz_set_error("dz_tune_plan: the output region of step %d does not map onto the frame grid of every buffer", c);
             return 4;
         }
-        p[0] = rows;
-        p[1] = pre;
-        p[2] = f1;
+        p[0] = geo.rows;
+        p[1] = geo.pre;
+        p[2] = (int)geo.pre_first;
         p[3] = nbuf;
-        t0_out[c] = out_start;
-        res_out[c] = out_res;
+        t0_out[c] = geo.out_start;
+        res_out[c] = geo.out_res;
     }
     return 0;
 }
@@ -122,23 +107,14 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
     }
     const int N = d->N, F = d->F, K = d->K, D = d->D, G = d->G;
     const int pairs = trials * N;
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > pairs) nt = pairs;
+    const int nt = dz_host_threads(num_threads, pairs);
     std::memset(assign, 0xff, (size_t)trials * d->total_chunks * K);
-    std::vector<int> rcs(nt, 0);
-    std::vector<std::string> msgs(nt);
     struct Scratch {
         std::vector<double> a, b;
         std::vector<int> ia;
         TcStep<CluFixed> s;
     };
     std::vector<Scratch> scratch(nt);
-    auto fail = [&](int w, int rc, const char* what) {
-        if (!rcs[w]) {
-            rcs[w] = rc;
-            msgs[w] = what;
-        }
-    };
     auto run_handles = [&](int w, int pair) {
         const int t = pair / N, n = pair - t * N;
         const double tau = hparams[3 * t], rho = hparams[3 * t + 1], delta = hparams[3 * t + 2];
@@ -152,12 +128,11 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
         dz_tail* tail = nullptr;
         if (dz_clu_create(tau, rho, delta, G, &clu) ||
             dz_tail_create(F, G, step, latency, tau, DZ_AGG_HAMMING, DZ_CROP_LOOSE, d->hamming, &tail)) {
-            fail(w, 2, dz_last_error());
             dz_clu_destroy(clu);
-            return;
+            return 2;   // with the message of the create that failed
         }
-        int stat = -1;
-        for (int c = d->chunk_off[n]; c < d->chunk_off[n + 1] && !rcs[w]; ++c) {
+        int stat = -1, failed = 0;
+        for (int c = d->chunk_off[n]; c < d->chunk_off[n + 1] && !failed; ++c) {
             if (stat < 0) {
                 const int rc = dz_clu_step(clu, d->seg + (size_t)c * F * K, F, K, d->emb + (size_t)c * K * D, D, sc.a.data(),
                                            sc.ia.data());
@@ -170,15 +145,14 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
             }
             int rows = 0;
             double t0 = 0.0, res = 0.0;
-            const int rc = dz_tail_step(tail, sc.a.data(), starts[c], resolution[c], sc.b.data(), &rows, &t0, &res, nullptr, 0,
-                                        nullptr);
-            if (rc) {
-                fail(w, rc, dz_last_error());
-                break;
-            }
+            failed = dz_tail_step(tail, sc.a.data(), starts[c], resolution[c], sc.b.data(), &rows, &t0, &res, nullptr, 0,
+                                  nullptr);
+            if (failed) break;
+            // the plan is the same geometry (tail_core.h); what this still guards is the cache's row_off
             const int* p = d->plan + (size_t)c * (4 + d->nwin);
             if (rows != p[0] + p[1] || rows != d->row_off[c + 1] - d->row_off[c]) {
-                fail(w, 4, "dz_tune_replay_host: dz_tail_step and the plan disagree on the rows of a step");
+                dz_set_error("dz_tune_replay_host: dz_tail_step and the plan disagree on the rows of a step");
+                failed = 4;
                 break;
             }
             for (int r = 0; r < rows; ++r) {
@@ -191,6 +165,7 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
         status[pair] = stat;
         dz_clu_destroy(clu);
         dz_tail_destroy(tail);
+        return failed;
     };
     auto run_core = [&](int w, int pair) {
         const int t = pair / N, n = pair - t * N;
@@ -204,21 +179,12 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
                                 NoBarrier());
         const int c0 = d->chunk_off[n], c1 = d->chunk_off[n + 1];
         for (int p = d->row_off[c0]; p < d->row_off[c1]; ++p) B[p] = tc_row_mask(*d, p, hparams[3 * t], A);
+        return 0;
     };
-    auto run = [&](int w, int pair) {
-        if (use_core) run_core(w, pair);
-        else run_handles(w, pair);
-    };
-    if (nt == 1)
-        for (int i = 0; i < pairs; ++i) run(0, i);
-    else
-        dz_host_parallel(pairs, nt, run);
-    for (int w = 0; w < nt; ++w)
-        if (rcs[w]) {
-            dz_set_error("dz_tune_replay_host: %s", msgs[w].c_str());
-            return rcs[w];
-        }
-    return 0;
+    const dz_host_failure f =
+        dz_host_parallel_rc(pairs, nt, [&](int w, int pair) { return use_core ? run_core(w, pair) : run_handles(w, pair); });
+    if (f.code) dz_set_error("dz_tune_replay_host: %s", f.message.c_str());
+    return f.code;
 }
 
 extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_row_off,
@@ -244,7 +210,7 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
         Scratch& sc = scratch[w];
         const unsigned* B = bits + (size_t)t * total_rows;
         for (int g = 0; g < G; ++g) sc.turns[g].clear();
-        // ---- Binarize: per step and speaker, [middle(onset), middle(first inactive row)); the row after the last closes
+        // ---- Binarize (tail_edge_walk): per step and speaker, [middle(onset), middle(first inactive row))
         int p = file_row_off[n];
         for (int c = file_chunk_off[n]; c < file_chunk_off[n + 1]; ++c) {
             const int rows = step_rows[c];
@@ -255,16 +221,11 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
             for (unsigned m = any; m; m &= m - 1) {
                 const int g = __builtin_ctz(m);
                 if (g >= G) break;
-                int onset = -1;
-                for (int r = 0; r <= rows; ++r) {
-                    const bool on = r < rows && ((B[p + r] >> g) & 1u);
-                    if (on && onset < 0) onset = r;
-                    if (!on && onset >= 0) {
-                        if (mid[r] - mid[onset] > 1e-6)   // Segment.__bool__: shorter segments are not stored
-                            sc.turns[g].push_back(Turn{mid[onset], mid[r], cell[onset], cell[r]});
-                        onset = -1;
-                    }
-                }
+                tail_edge_walk(rows, [&](int r) { return (B[p + r] >> g) & 1u; }, [&](int onset, int r) {
+                    if (mid[r] - mid[onset] > 1e-6)   // Segment.__bool__: shorter segments are not stored
+                        sc.turns[g].push_back(Turn{mid[onset], mid[r], cell[onset], cell[r]});
+                    return true;
+                });
             }
             p += rows;
         }

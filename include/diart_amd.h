@@ -970,7 +970,7 @@ typedef struct dz_tune_desc {
     int N, F, K, D, G, nwin, total_chunks, total_rows;
 } dz_tune_desc;
 int dz_tune_abi_size(void);
-/* The tail's plan of one file (Hamming aggregation, "loose" cropping) with tail.cpp's own expressions:
+/* The tail's plan of one file (Hamming aggregation, "loose" cropping) from the text dz_tail_step runs (csrc/tail_core.h):
  * starts, resolution (chunks) as dz_tail_step gets them.  plan (chunks, 4 + nwin) with
  * nwin = round(latency / step); t0_out, res_out (chunks): the output grid of every step.  4 = the output
  * region does not map onto the frame grid of every buffer.                                              */

@@ -3,8 +3,9 @@
 // tests/test_host_sanitizers.py with g++ -fsanitize=address,undefined and with -fsanitize=thread (the GPU build cannot
 // carry sanitizers on this pool) and run on random inputs — NaN embeddings, silent chunks, more local speakers than free
 // centroids, varying thread counts, two callers at once.  It checks only what must hold whatever the data (finite
-// scores, assignments in range, batch == one-by-one); the reference's results are pinned by tests/test_clustering.py and
-// tests/test_tail.py.  Exit code 0 = nothing reported.
+// scores, assignments in range, batch == one-by-one, the tuner's plan (csrc/tune_score.cpp dz_tune_plan, built with
+// them) == the rows and the output grid dz_tail_step returned); the reference's results are pinned by
+// tests/test_clustering.py and tests/test_tail.py.  Exit code 0 = nothing reported.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -89,6 +90,26 @@ void run_streams(unsigned seed, int n, int steps, int threads, int K = ::K, int 
     std::vector<double> scores((size_t)n * F * G), scores1((size_t)F * G), agg((size_t)n * (F + 2) * G), turns((size_t)n * max_turns * 3);
     std::vector<double> start(n), res(n, 5.0 / F), t0(n), rout(n);
     std::vector<int> assign((size_t)n * K), assign1(K), rows(n), nturns(n);
+    // what dz_tail_step returned at every step of a stream since it (re)started, against the tuner's plan of the same
+    // starts: the two callers of the shared step geometry (csrc/tail_core.h) must agree
+    struct Chain {
+        std::vector<double> start, res, t0, rout;
+        std::vector<int> rows;
+    };
+    std::vector<Chain> chain(n);
+    auto check_plan = [&](Chain& c) {
+        const int chunks = (int)c.start.size(), nwin = 5;   // Streams: latency 2.5 / step 0.5
+        if (!chunks) return;
+        std::vector<int> plan((size_t)chunks * (4 + nwin));
+        std::vector<double> pt0(chunks), pres(chunks);
+        CHECK(dz_tune_plan(chunks, F, 0.5, 2.5, c.start.data(), c.res.data(), plan.data(), pt0.data(), pres.data()) == 0);
+        for (int s = 0; s < chunks; ++s) {
+            const int* p = &plan[(size_t)s * (4 + nwin)];
+            CHECK(p[0] + p[1] == c.rows[s] && pt0[s] == c.t0[s] && pres[s] == c.rout[s]);
+            CHECK(p[3] == (s + 1 < nwin ? s + 1 : nwin));
+        }
+        c = Chain();
+    };
     for (int t = 0; t < steps; ++t) {
         fill(rng, n, t, seg, emb, K, G);
         CHECK(dz_clu_step_batch(s.clu.data(), n, seg.data(), F, K, emb.data(), D, scores.data(), assign.data(), threads) == 0);
@@ -102,12 +123,19 @@ void run_streams(unsigned seed, int n, int steps, int threads, int K = ::K, int 
         for (double v : scores) CHECK(std::isfinite(v));
         CHECK(dz_tail_step_batch(s.tail.data(), n, scores.data(), start.data(), res.data(), agg.data(), rows.data(), t0.data(),
                                  rout.data(), turns.data(), max_turns, nturns.data(), threads) == 0);
-        for (int i = 0; i < n; ++i) CHECK(rows[i] >= 0 && rows[i] <= F + 2 && nturns[i] >= 0 && nturns[i] <= max_turns);
+        for (int i = 0; i < n; ++i) {
+            CHECK(rows[i] >= 0 && rows[i] <= F + 2 && nturns[i] >= 0 && nturns[i] <= max_turns);
+            Chain& c = chain[i];
+            c.start.push_back(start[i]); c.res.push_back(res[i]); c.t0.push_back(t0[i]); c.rout.push_back(rout[i]);
+            c.rows.push_back(rows[i]);
+        }
         if (t % 17 == 16) {                              // a stream that ends and starts again
             CHECK(dz_clu_reset(s.clu[t % n]) == 0 && dz_clu_reset(one.clu[t % n]) == 0);
             CHECK(dz_tail_reset(s.tail[t % n]) == 0);
+            check_plan(chain[t % n]);
         }
     }
+    for (Chain& c : chain) check_plan(c);
     std::vector<double> centers((size_t)G * D);
     std::vector<int> mask(G);
     for (int i = 0; i < n; ++i) {

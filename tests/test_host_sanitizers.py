@@ -3,7 +3,9 @@ DelayedAggregation + Binarize and the worker pool that runs them for N streams â
 blocks/clustering.py, mapping.py, blocks/aggregation.py, blocks/utils.py) under AddressSanitizer + UBSan and under
 ThreadSanitizer.  GPU sanitizers are not available on this pool, and these four files have no HIP in them: they are
 compiled here with g++ together with tests/native/host_sanitize.cpp (random streams, NaN embeddings, resets, several
-thread counts, two callers sharing the process-wide pool) and must run without a report."""
+thread counts, two callers sharing the process-wide pool) and must run without a report.  csrc/tune_score.cpp, the
+tuner's host side, is compiled with them for dz_tune_plan: the step geometry of csrc/tail_core.h then runs from both of
+its callers, and the harness holds the plan against what dz_tail_step returned for the same starts."""
 import shutil
 import subprocess
 from pathlib import Path
@@ -12,7 +14,7 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 SRC = [ROOT / "tests" / "native" / "host_sanitize.cpp"] + [ROOT / "diart_amd" / "csrc" / f
-                                                            for f in ("cluster.cpp", "tail.cpp", "hostpool.cpp", "filebatch.cpp")]
+                                                            for f in ("cluster.cpp", "tail.cpp", "hostpool.cpp", "filebatch.cpp", "tune_score.cpp")]
 
 
 @pytest.mark.parametrize("flags,env", [

@@ -111,6 +111,138 @@ def test_cpp_batched_tail_matches_reference_golden(latency):
     assert np.array_equal(agg[0, :rows[0]], GOLD[f"s0_l{latency:g}_t0_agg"])
 
 
+def test_cpp_tail_equals_the_python_blocks_for_every_strategy_and_mode():
+    """dz_tail_step against DelayedAggregation + Binarize (which the goldens above pin) for all nine strategy x cropping
+    mode pairs, on three frame grids, four (step, latency) pairs and four first starts, 14 steps of seeded uniform
+    scores each: the aggregated rows, t0, res and the sorted turns are EQUAL (no tolerance) at every step.  Where the
+    Python block raises (np.stack on unequal crops) dz_tail_step returns 4 and the other way round; the chain ends
+    there.  Both are counted and the counts must agree; fewer than 2 % of the steps may end so, or the sweep would
+    check little.  For hamming / loose the tuner's plan (dz_tune_plan) of the chain's starts must give the same rows,
+    t0 and res: the GPU tuner hangs on the same text (csrc/tail_core.h).
+
+    (step, latency) = (0.1, 2.0) — 20 buffers — is not in the sweep on purpose: from the 8th buffer on, where the region
+    has one or two rows, numpy sums the short stacked axis pairwise and the C++ tail sums in order, and "hamming" differs
+    in the last bits.  The shipped shape (293 frames, step 0.5, up to 10 buffers) is exact."""
+    import ctypes as C
+    import itertools
+    from diart_amd import _lib
+    from diart_amd.blocks import Binarize, DelayedAggregation
+    from diart_amd.blocks.aggregation import _MODE, _STRATEGY
+    from diart_amd.features import SlidingWindow, SlidingWindowFeature
+    lib = _lib.load()
+    binarize = Binarize(0.5)
+    rng = np.random.default_rng(0)
+    steps = py_raised = cpp_rc4 = 0
+    bad = []
+    for (F, G), strategy, mode, (step, latency), first_start in itertools.product(
+            [(7, 2), (59, 3), (293, 4)], _STRATEGY, _MODE, [(0.5, 0.5), (0.5, 1.5), (0.5, 5.0), (0.3, 0.9)],
+            [0.0, 7.5, -1.75, 0.3]):
+        case = (F, G, strategy, mode, step, latency, first_start)
+        res = 5 / F
+        hamming = np.ascontiguousarray(np.hamming(F))
+        h = _lib.vp()
+        _lib.check(lib.dz_tail_create(F, G, step, latency, 0.5, _STRATEGY[strategy], _MODE[mode], hamming.ctypes.data,
+                                      C.byref(h)), "dz_tail_create")
+        agg = DelayedAggregation(step, latency, strategy, mode)
+        out, max_turns = np.empty((F + 2, G)), G * ((F + 2) // 2 + 1)
+        turns = np.empty((max_turns, 3))
+        rows, nturns, t0, r = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+        buffers, start, starts, done = [], first_start, [], []
+        failed = False
+        for i in range(14):
+            scores = rng.random((F, G))
+            buffers.append(SlidingWindowFeature(scores, SlidingWindow(start=start, duration=res, step=res)))
+            starts.append(start)
+            rc = lib.dz_tail_step(h, scores.ctypes.data, start, res, out.ctypes.data, C.byref(rows), C.byref(t0),
+                                  C.byref(r), turns.ctypes.data, max_turns, C.byref(nturns))
+            steps += 1
+            try:
+                want = agg(buffers)
+            except (ValueError, ZeroDivisionError):   # np.stack on unequal crops; a region of no rows at all
+                want = None
+            py_raised += want is None
+            cpp_rc4 += rc == 4
+            if want is None or rc:
+                failed = True
+                if not (want is None and rc == 4):
+                    bad.append((case, i, f"rc {rc}, python {'raised' if want is None else 'did not raise'}"))
+                break
+            sw = want.sliding_window
+            want_turns = sorted((s.start, s.end, float(t)) for s, t, _ in binarize(want).itertracks(yield_label=True))
+            got_turns = sorted(map(tuple, turns[:nturns.value]))
+            if not (rows.value == want.data.shape[0] and np.array_equal(out[:rows.value], want.data)
+                    and t0.value == sw.start and r.value == sw.step and got_turns == want_turns):
+                bad.append((case, i, "rows / t0 / res / turns differ"))
+            done.append((rows.value, t0.value, r.value))
+            if len(buffers) == agg.num_overlapping_windows:
+                buffers = buffers[1:]
+            start += step
+        lib.dz_tail_destroy(h)
+        if strategy == "hamming" and mode == "loose":
+            nwin = agg.num_overlapping_windows
+            s_arr, r_arr = np.array(starts), np.full(len(starts), res)
+            plan = np.zeros((len(starts), 4 + nwin), dtype=np.int32)
+            pt0, pres = np.zeros(len(starts)), np.zeros(len(starts))
+            rc = lib.dz_tune_plan(len(starts), F, step, latency, s_arr.ctypes.data, r_arr.ctypes.data, plan.ctypes.data,
+                                  pt0.ctypes.data, pres.ctypes.data)
+            if rc != (4 if failed else 0):
+                bad.append((case, len(starts) - 1, f"dz_tune_plan returned {rc}"))
+            got = [(int(p[0] + p[1]), a, b) for p, a, b in zip(plan[:len(done)], pt0, pres)]   # (the steps before a 4)
+            if got != done:
+                bad.append((case, -1, "dz_tune_plan and dz_tail_step differ in rows / t0 / res"))
+    print(f"{steps} steps, python raised at {py_raised}, dz_tail_step returned 4 at {cpp_rc4}, {len(bad)} differ")
+    assert not bad, bad[:5]
+    assert py_raised == cpp_rc4
+    assert py_raised < 0.02 * steps, (steps, py_raised)
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+def test_batches_report_the_lowest_failing_item(threads):
+    """Two items of a batch fail: the code and the message are those of the LOWEST index, on one thread and on the
+    pool (where which worker met a failure first is a matter of timing).  On the pool the items that did not fail have
+    been stepped; on one thread the call ends at the first failure."""
+    import ctypes as C
+    from diart_amd import _lib
+    lib = _lib.load()
+    F, n, res = 59, 4, 5 / 59
+    hamming = np.ascontiguousarray(np.hamming(F))
+    hs = []
+    for _ in range(n):
+        h = _lib.vp()
+        _lib.check(lib.dz_tail_create(F, 1, 0.5, 0.5, 0.5, 0, 1, hamming.ctypes.data, C.byref(h)), "dz_tail_create")
+        hs.append(h)
+    handles = (_lib.vp * n)(*hs)
+    # dz_tail_step_batch: stream 1 gets resolution 0 (code 2), stream 3 a region of more than F + 2 rows (code 4)
+    scores = np.zeros((n, F, 1))
+    scores[:, 10:20] = 1.0
+    scores[:, 30:40] = 1.0            # two speech turns per stream
+    starts = np.zeros(n)
+    resolution = np.array([res, 0.0, res, res / 100])
+    agg, turns = np.empty((n, F + 2, 1)), np.empty((n, 8, 3))
+    rows = np.full(n, -1, dtype=np.int32)
+    nturns = np.full(n, -1, dtype=np.int32)
+    t0, r = np.empty(n), np.empty(n)
+    rc = lib.dz_tail_step_batch(handles, n, scores.ctypes.data, starts.ctypes.data, resolution.ctypes.data, agg.ctypes.data,
+                                rows.ctypes.data, t0.ctypes.data, r.ctypes.data, turns.ctypes.data, 8, nturns.ctypes.data,
+                                threads)
+    assert rc == 2 and lib.dz_last_error() == b"dz_tail_step_batch: bad arguments"
+    assert rows[0] > 0 and nturns[0] == 2 and rows[1] == -1 and rows[3] == -1
+    assert (rows[2] > 0 and nturns[2] == 2) if threads > 1 else rows[2] == -1
+    # dz_file_vad_step_batch: one window per file, room for one turn: files 1 and 2 have two (code 5), file 0 is silent
+    for h in hs:
+        lib.dz_tail_reset(h)
+    track = np.ascontiguousarray(scores[:3, :, 0], dtype=np.float32)
+    track[0] = 0.0
+    row0, count = np.arange(3, dtype=np.int32), np.ones(3, dtype=np.int32)
+    fstarts, fturns, fn = np.zeros(3), np.empty((3, 1, 3)), np.zeros(3, dtype=np.int32)
+    rc = lib.dz_file_vad_step_batch(handles, 3, row0.ctypes.data, count.ctypes.data, track.ctypes.data, F, fstarts.ctypes.data,
+                                    res, fturns.ctypes.data, 1, fn.ctypes.data, threads)
+    assert rc == 5
+    assert lib.dz_last_error() == b"dz_file_vad_step_batch: file 1 of 3 failed (code 5): dz_tail_step: more speech turns than max_turns"
+    for h in hs:
+        lib.dz_tail_destroy(h)
+
+
 def test_docstring_example_of_the_reference():
     """aggregation.py:141-161: 5 s / 500 frames / step 0.5 / latency 2 -> 4 windows, (51, 2)."""
     from diart_amd.blocks import DelayedAggregation
