@@ -43,6 +43,7 @@ class EmbWeights(C.Structure):
                 ("tw_split", vp * 5), ("tw0_split_kb", vp), ("pool_nearest", C.c_int)]
 
 
+TRACK_SPEECH, TRACK_OVERLAP = 0, 1   # DZ_TRACK_*: the track dz_seg_forward_track's head writes beside the scores
 GATHER_MAX_RUNS = 64            # DZ_GATHER_MAX_RUNS: runs one launch of dz_gather_windows carries
 
 
@@ -133,6 +134,8 @@ SIGNATURES = {
     "dz_seg_forward": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp]),
     "dz_seg_forward_osp": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, C.c_float, C.c_float, C.c_int, vp, vp]),
     "dz_seg_forward_vad": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, vp]),
+    "dz_seg_forward_track": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_int, vp]),
+    "dz_overlap_track": (C.c_int, [vp, C.c_longlong, C.c_longlong, C.c_int, vp, vp]),
     "dz_seg_destroy": (C.c_int, [vp]),
     "dz_emb_create": (C.c_int, [vp, C.POINTER(EmbWeights), C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_emb_forward": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, C.c_int, vp, vp]),

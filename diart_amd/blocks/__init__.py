@@ -6,6 +6,7 @@ from .clustering import (BatchedSpeakerClustering, IncrementalSpeakerClustering,
 from .diarization import SpeakerDiarization, SpeakerDiarizationConfig
 from .embedding import (EmbeddingNormalization, OverlapAwareSpeakerEmbedding,
                         OverlappedSpeechPenalty, SpeakerEmbedding)
+from .osd import OverlappedSpeechDetection, OverlappedSpeechDetectionConfig
 from .segmentation import SpeakerSegmentation
 from .utils import AdjustVolume, Binarize, Resample, adjust_volume, resample
 from .vad import VoiceActivityDetection, VoiceActivityDetectionConfig
@@ -16,4 +17,4 @@ __all__ = ["SpeakerSegmentation", "SpeakerEmbedding", "OverlappedSpeechPenalty",
            "AggregationStrategy", "HammingWeightedAverageStrategy", "AverageStrategy", "FirstOnlyStrategy",
            "BatchedOutputTail", "Binarize", "Resample", "resample", "AdjustVolume", "adjust_volume", "Pipeline", "PipelineConfig", "HyperParameter",
            "SpeakerDiarization", "SpeakerDiarizationConfig", "VoiceActivityDetection",
-           "VoiceActivityDetectionConfig"]
+           "VoiceActivityDetectionConfig", "OverlappedSpeechDetection", "OverlappedSpeechDetectionConfig"]

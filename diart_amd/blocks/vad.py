@@ -49,9 +49,16 @@ class VoiceActivityDetectionConfig(base.PipelineConfig):
         return self._sample_rate
 
 
-class VoiceActivityDetection(base.Pipeline):
-    def __init__(self, config: Optional[VoiceActivityDetectionConfig] = None):
-        self._config = VoiceActivityDetectionConfig() if config is None else config
+class _TrackDetection(base.Pipeline):
+    """What the pipelines that binarise ONE track of the segmentation share (``VoiceActivityDetection``: the max over
+    speakers; ``OverlappedSpeechDetection``, blocks/osd.py: the second largest): the blocks, the buffers and the host
+    half behind the track (reference vad.py:150-191).  A private base, not a pipeline: the two are siblings."""
+
+    LABEL: str                  # what every turn is called
+    CONFIG: type                # the pipeline's configuration class
+
+    def __init__(self, config=None):
+        self._config = self.CONFIG() if config is None else config
         c = self._config
         msg = f"Latency should be in the range [{c.step}, {c.duration}]"
         assert c.step <= c.latency <= c.duration, msg
@@ -63,20 +70,11 @@ class VoiceActivityDetection(base.Pipeline):
         self.chunk_buffer, self.pred_buffer = [], []
 
     @staticmethod
-    def get_config_class() -> type:
-        return VoiceActivityDetectionConfig
-
-    @staticmethod
-    def suggest_metric():
-        from ..metrics import DetectionErrorRate
-        return DetectionErrorRate(collar=0, skip_overlap=False)
-
-    @staticmethod
     def hyper_parameters() -> Sequence[base.HyperParameter]:
         return [base.TauActive]
 
     @property
-    def config(self) -> VoiceActivityDetectionConfig:
+    def config(self):
         return self._config
 
     def reset(self):
@@ -86,14 +84,57 @@ class VoiceActivityDetection(base.Pipeline):
     def set_timestamp_shift(self, shift: float):
         self.timestamp_shift = shift
 
-    def __call__(self, waveforms: Sequence[SlidingWindowFeature]) -> Sequence[Tuple[Annotation, SlidingWindowFeature]]:
+    def _windows(self, waveforms: Sequence[SlidingWindowFeature]) -> torch.Tensor:
+        """``__call__``'s checks of its chunks, then their batch on the device."""
         assert len(waveforms) >= 1, "Pipeline expected at least 1 input"
         expected = int(np.rint(self.config.duration * self.config.sample_rate))
         got = waveforms[0].data.shape[0]
         assert all(w.data.shape[0] == got for w in waveforms), "chunks of different lengths in one batch"
         assert got == expected, f"Expected {expected} samples per chunk, but got {got}"
-        batch = windows_batch(waveforms, self.config.device)
-        return self.finalise(waveforms, self.segmentation(batch))
+        return windows_batch(waveforms, self.config.device)
+
+    def _finalise_track(self, waveforms: Sequence[SlidingWindowFeature], track: torch.Tensor):
+        """Aggregation, binarisation and labelling of the chunks' track ``(batch, frames, 1)``."""
+        seg_resolution = waveforms[0].extent.duration / track.shape[1]
+        outputs = []
+        for wav, row in zip(waveforms, track):
+            sw = SlidingWindow(start=wav.extent.start, duration=seg_resolution, step=seg_resolution)
+            row = SlidingWindowFeature(row.cpu().numpy(), sw)
+            self.chunk_buffer.append(wav)
+            self.pred_buffer.append(row)
+            agg_waveform = self.audio_aggregation(self.chunk_buffer)
+            timeline = self.binarize(self.pred_aggregation(self.pred_buffer)).get_timeline(copy=False)
+            if self.timestamp_shift != 0:
+                shifted = Timeline(uri=timeline.uri)
+                for segment in timeline:
+                    shifted.add(Segment(segment.start + self.timestamp_shift, segment.end + self.timestamp_shift))
+                timeline = shifted
+            outputs.append((timeline.to_annotation(_repeat_label(self.LABEL)), agg_waveform))
+            if len(self.chunk_buffer) == self.pred_aggregation.num_overlapping_windows:
+                self.chunk_buffer = self.chunk_buffer[1:]
+                self.pred_buffer = self.pred_buffer[1:]
+        return outputs
+
+
+class VoiceActivityDetection(_TrackDetection):
+    LABEL = "speech"
+    CONFIG = VoiceActivityDetectionConfig
+
+    @staticmethod
+    def get_config_class() -> type:
+        return VoiceActivityDetectionConfig
+
+    @staticmethod
+    def suggest_metric():
+        from ..metrics import DetectionErrorRate
+        return DetectionErrorRate(collar=0, skip_overlap=False)
+
+    @property
+    def config(self) -> VoiceActivityDetectionConfig:
+        return self._config
+
+    def __call__(self, waveforms: Sequence[SlidingWindowFeature]) -> Sequence[Tuple[Annotation, SlidingWindowFeature]]:
+        return self.finalise(waveforms, self.segmentation(self._windows(waveforms)))
 
     def model_outputs(self, waveforms: Sequence[SlidingWindowFeature]) -> torch.Tensor:
         """The model half of ``__call__``: what ``finalise`` computes as ``voice_detection``, ``(batch, frames, 1)``
@@ -104,23 +145,4 @@ class VoiceActivityDetection(base.Pipeline):
 
     def finalise(self, waveforms: Sequence[SlidingWindowFeature], segmentations: torch.Tensor):
         """The host half of ``__call__`` (reference vad.py:146-191) for given segmentation scores."""
-        voice_detection = torch.max(segmentations, dim=-1, keepdim=True)[0]   # (batch, frames, 1)
-        seg_resolution = waveforms[0].extent.duration / segmentations.shape[1]
-        outputs = []
-        for wav, vad in zip(waveforms, voice_detection):
-            sw = SlidingWindow(start=wav.extent.start, duration=seg_resolution, step=seg_resolution)
-            vad = SlidingWindowFeature(vad.cpu().numpy(), sw)
-            self.chunk_buffer.append(wav)
-            self.pred_buffer.append(vad)
-            agg_waveform = self.audio_aggregation(self.chunk_buffer)
-            timeline = self.binarize(self.pred_aggregation(self.pred_buffer)).get_timeline(copy=False)
-            if self.timestamp_shift != 0:
-                shifted = Timeline(uri=timeline.uri)
-                for segment in timeline:
-                    shifted.add(Segment(segment.start + self.timestamp_shift, segment.end + self.timestamp_shift))
-                timeline = shifted
-            outputs.append((timeline.to_annotation(_repeat_label("speech")), agg_waveform))
-            if len(self.chunk_buffer) == self.pred_aggregation.num_overlapping_windows:
-                self.chunk_buffer = self.chunk_buffer[1:]
-                self.pred_buffer = self.pred_buffer[1:]
-        return outputs
+        return self._finalise_track(waveforms, torch.max(segmentations, dim=-1, keepdim=True)[0])   # (batch, frames, 1)

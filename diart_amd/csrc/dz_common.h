@@ -539,6 +539,24 @@ __device__ __forceinline__ float dz_vad_frame(const float* s, int K) {
     for (int k = 1; k < K; ++k) m = (s[k] > m || s[k] != s[k]) ? s[k] : m;
     return m;
 }
+// dz_overlap_frame: the OverlappedSpeechDetection track of one frame, the second-largest of the K >= 2 speaker scores
+// counted with multiplicity: torch.sort(s, descending=True)[1], NaN ordered above every number as torch.sort orders
+// it.  Plain compares only (v_max_f32 drops a NaN operand); the values travel unchanged, a NaN with its payload.
+__device__ __forceinline__ bool dz_sort_above(float a, float b) { return a != a ? b == b : a > b; }
+__device__ __forceinline__ float dz_overlap_frame(const float* s, int K) {
+    float m1 = s[0], m2 = s[1];
+    if (dz_sort_above(m2, m1)) { m1 = s[1]; m2 = s[0]; }
+    for (int k = 2; k < K; ++k) {
+        const float v = s[k];
+        if (dz_sort_above(v, m1)) { m2 = m1; m1 = v; }
+        else if (dz_sort_above(v, m2)) m2 = v;
+    }
+    return m2;
+}
+// the track a head writes beside its scores (include/diart_amd.h: DZ_TRACK_SPEECH | DZ_TRACK_OVERLAP)
+__device__ __forceinline__ float dz_track_frame(const float* s, int K, int track) {
+    return track ? dz_overlap_frame(s, K) : dz_vad_frame(s, K);
+}
 __device__ __forceinline__ void dz_osp_frame(const float* s, int K, float gamma, float beta, float* w) {
     float e[8], m = -INFINITY;
     for (int k = 0; k < K; ++k) m = fmaxf(m, beta * s[k]);
@@ -555,10 +573,14 @@ __device__ __forceinline__ void dz_osp_frame(const float* s, int K, float gamma,
     }
 }
 
-// vad (optional): [B][F] speech track, dz_vad_frame of every frame's seg row
+// vad (optional): [B][F] track of every frame's seg row: dz_vad_frame (track 0, the speech track) or dz_overlap_frame
+// (track 1, K >= 2)
 int dz_launch_seg_head(const float* m1, const float* cw, const float* cb, int B, int F, int classes, int K,
                        int powerset, float* seg, float gamma, float beta, int normalize, float* wout,
-                       hipStream_t st, const float* wave_mom = nullptr, float* vad = nullptr);
+                       hipStream_t st, const float* wave_mom = nullptr, float* vad = nullptr, int track = 0);
+// scores [rows] x K floats, `row_stride` floats apart -> out [rows] = dz_overlap_frame of each row (k_pool.hip)
+int dz_launch_overlap_track(const float* scores, long long row_stride, long long rows, int K, float* out,
+                            hipStream_t st);
 // lin0 (256 -> 128, LeakyReLU) -> lin1 (128 -> 128, LeakyReLU) -> classifier -> activation (-> OSP
 // weights, not normalised) in one launch: k_mlp_head.hip
 struct DzMlpHead {
@@ -573,6 +595,7 @@ struct DzMlpHead {
     int* oflag;
     const float* wave_mom;     // wave_stats moments of the rows' chunks, or NULL: chunks with non-finite ones get NaN rows (dz_ws_bad)
     float* vad;                // [rows] speech track (dz_vad_frame of each seg row) or NULL
+    int track;                 // what `vad` gets: 0 the speech track, 1 the overlap track (dz_overlap_frame, K >= 2)
 };
 int dz_launch_mlp_head(const DzMlpHead& p, hipStream_t st);
 int dz_launch_l2norm(float* x, int rows, int dim, float norm, hipStream_t st);

@@ -8,7 +8,8 @@
 //     -> lin1: 128 -> 128, LeakyReLU      f16x3 MFMA, A = lin0's tile re-split INTO LDS, B by LDS-DMA
 //     -> classifier 128 -> classes        f32 FMA chain per frame (the order of seg_head_kernel)
 //     -> sigmoid | powerset decision -> seg; OSP weights (not normalised) -> wout; speech track
-//        (max over speakers, VoiceActivityDetection) -> vad
+//        (max over speakers, VoiceActivityDetection) or overlap track (second largest,
+//        OverlappedSpeechDetection; p.track) -> vad
 //
 // It replaces three launches (two k_gemm_pre.hip GEMMs + seg_head_kernel) and the 2 x 9.6 MB round
 // trip of the hidden activations; the arithmetic per output is the same as theirs, statement by
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256) void mlp_head_kernel(DzMlpHead p) {
         if (p.wave_mom && dz_ws_bad(p.wave_mom, b))          // a window with NaN / Inf samples: NaN rows, like the reference
             for (int k = 0; k < p.K; ++k) s[k] = __builtin_nanf("");
         for (int k = 0; k < p.K; ++k) p.seg[(long long)t * p.K + k] = s[k];
-        if (p.vad) p.vad[t] = dz_vad_frame(s, p.K);
+        if (p.vad) p.vad[t] = dz_track_frame(s, p.K, p.track);
         if (p.wout) {
             float wv[8];
             dz_osp_frame(s, p.K, p.gamma, p.beta, wv);
@@ -233,6 +234,7 @@ int dz_launch_mlp_head(const DzMlpHead& p_in, hipStream_t st) {
     DZ_REQUIRE(p.rows > 0 && p.F > 0 && p.rows % p.F == 0, "mlp_head: %d rows are not whole chunks of %d frames", p.rows, p.F);
     DZ_REQUIRE(p.classes >= 1 && p.classes <= 8 && p.K >= 1 && p.K <= 8 && (p.powerset || p.K == p.classes),
                "mlp_head: classes %d / speakers %d", p.classes, p.K);
+    DZ_REQUIRE(!p.vad || p.track == 0 || (p.track == 1 && p.K >= 2), "mlp_head: track %d of %d speakers", p.track, p.K);
     DZ_REQUIRE((long long)p.rows * 256 * 2 < (1ll << 31), "mlp_head: plane exceeds the buffer range");
     DZ_REQUIRE(p.xplane == (long long)p.rows * 256, "mlp_head: kb-major input planes of exactly `rows` rows (xplane = rows * 256)");
     static DzAttrOnce attr_once;

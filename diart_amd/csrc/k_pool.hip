@@ -208,7 +208,8 @@ __global__ __launch_bounds__(256) void osp_kernel(const float* __restrict__ seg,
 // MLP output (F x 128 f32) are staged through LDS in slices (coalesced loads, conflict-free row
 // reads at a 129-float pitch), the 128 x classes weights are wave-uniform scalar loads.  The OSP part
 // is the arithmetic of osp_kernel above, statement by statement.  `vad` (optional) gets the speech
-// track of VoiceActivityDetection, the max over speakers of each frame (dz_vad_frame).
+// track of VoiceActivityDetection, the max over speakers of each frame (dz_vad_frame), or with
+// track = 1 the overlap track of OverlappedSpeechDetection (dz_overlap_frame).
 // ---------------------------------------------------------------------------
 constexpr int SH_ROWS = 64;          // frames per LDS slice
 constexpr int SH_PITCH = 129;
@@ -217,7 +218,8 @@ __global__ __launch_bounds__(256) void seg_head_kernel(const float* __restrict__
                                                        const float* __restrict__ cb, int F, int classes, int K,
                                                        int powerset, float* __restrict__ seg, float gamma,
                                                        float beta, int normalize, float* __restrict__ wout,
-                                                       const float* __restrict__ wave_mom, float* __restrict__ vad) {
+                                                       const float* __restrict__ wave_mom, float* __restrict__ vad,
+                                                       int track) {
     extern __shared__ float hbuf[];   // [SH_ROWS][SH_PITCH] slice | [F][K] weights | [2][K] min / max
     float* xs = hbuf;
     float* wbuf = hbuf + SH_ROWS * SH_PITCH;
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(256) void seg_head_kernel(const float* __restrict__
                 for (int k = 0; k < K; ++k) s[k] = __builtin_nanf("");
             const int f = f0 + tid;
             for (int k = 0; k < K; ++k) sb[f * K + k] = s[k];
-            if (vad) vad[(long long)b * F + f] = dz_vad_frame(s, K);
+            if (vad) vad[(long long)b * F + f] = dz_track_frame(s, K, track);
             if (wout) {
                 float wv[8];
                 dz_osp_frame(s, K, gamma, beta, wv);
@@ -505,15 +507,81 @@ int dz_launch_osp(const float* seg, int B, int F, int K, float gamma, float beta
 // [B][K][F] OSP weights
 int dz_launch_seg_head(const float* m1, const float* cw, const float* cb, int B, int F, int classes, int K,
                        int powerset, float* seg, float gamma, float beta, int normalize, float* wout,
-                       hipStream_t st, const float* wave_mom, float* vad) {
+                       hipStream_t st, const float* wave_mom, float* vad, int track) {
     DZ_REQUIRE(classes >= 1 && classes <= 8 && K >= 1 && K <= 8 && (powerset || K == classes),
                "seg_head: classes %d / speakers %d", classes, K);
+    DZ_REQUIRE(!vad || track == 0 || (track == 1 && K >= 2), "seg_head: track %d of %d speakers", track, K);
     const size_t lds = sizeof(float) * ((size_t)SH_ROWS * SH_PITCH + (size_t)F * K + 2 * K);
     DZ_REQUIRE(lds <= 64 * 1024, "seg_head: %d frames x %d speakers do not fit in LDS", F, K);
     DZ_LAUNCH(seg_head_kernel, dim3(B), dim3(256), lds, st, m1, cw, cb, F, classes, K, powerset, seg, gamma,
-              beta, normalize, wout, wave_mom, vad);
+              beta, normalize, wout, wave_mom, vad, track);
     DZ_HIP(hipGetLastError());
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// overlap_track: scores (rows, K), rows `stride` floats apart -> out (rows), the overlap track of
+// OverlappedSpeechDetection (dz_overlap_frame: the second largest of each row, NaN above every number).
+// Thread = row, 256 rows per workgroup.  Packed rows (stride == K): the workgroup's 256 * K consecutive
+// floats come in as whole-wave coalesced loads through LDS, and each thread reads its row from there (rows
+// at an odd pitch K | 1, so that the K reads of a wave meet no bank twice); any other stride: K loads per
+// thread straight from its row.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int OT_ROWS = 256;
+
+template <int K>
+__global__ __launch_bounds__(OT_ROWS) void overlap_track_kernel(const float* __restrict__ scores, long long stride,
+                                                                long long rows, float* __restrict__ out) {
+    constexpr int PITCH = K | 1;
+    __shared__ float tile[OT_ROWS * PITCH];
+    const int tid = threadIdx.x;
+    const long long r0 = (long long)blockIdx.x * OT_ROWS, r = r0 + tid;
+    float s[K];
+    if (stride == K) {
+        const long long left = (rows - r0) * K;                  // floats from this workgroup's first row to the end
+        const int n = left < (long long)OT_ROWS * K ? (int)left : OT_ROWS * K;
+        const float* src = scores + r0 * K;
+        for (int i = tid; i < n; i += OT_ROWS) tile[(i / K) * PITCH + i % K] = src[i];      // i / K < OT_ROWS
+        __syncthreads();
+        if (r >= rows) return;
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] = tile[tid * PITCH + k];
+    } else {
+        if (r >= rows) return;
+        const float* src = scores + r * stride;
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] = src[k];
+    }
+    out[r] = dz_overlap_frame(s, K);
+}
+
+template <int K>
+int launch_overlap_track(const float* scores, long long stride, long long rows, float* out, hipStream_t st) {
+    DZ_LAUNCH(overlap_track_kernel<K>, dim3((unsigned)((rows + OT_ROWS - 1) / OT_ROWS)), dim3(OT_ROWS), 0, st, scores,
+              stride, rows, out);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+int dz_launch_overlap_track(const float* scores, long long row_stride, long long rows, int K, float* out,
+                            hipStream_t st) {
+    DZ_REQUIRE(scores && out, "overlap_track: NULL argument");
+    DZ_REQUIRE(K >= 2 && K <= 8, "overlap_track: 2 <= speakers <= 8 (got %d)", K);
+    DZ_REQUIRE(rows >= 1 && rows <= (long long)OT_ROWS * 0x7fffffff, "overlap_track: %lld rows", rows);
+    DZ_REQUIRE(row_stride >= K, "overlap_track: rows %lld floats apart hold no %d scores", row_stride, K);
+    switch (K) {
+        case 2: return launch_overlap_track<2>(scores, row_stride, rows, out, st);
+        case 3: return launch_overlap_track<3>(scores, row_stride, rows, out, st);
+        case 4: return launch_overlap_track<4>(scores, row_stride, rows, out, st);
+        case 5: return launch_overlap_track<5>(scores, row_stride, rows, out, st);
+        case 6: return launch_overlap_track<6>(scores, row_stride, rows, out, st);
+        case 7: return launch_overlap_track<7>(scores, row_stride, rows, out, st);
+        default: return launch_overlap_track<8>(scores, row_stride, rows, out, st);
+    }
 }
 
 int dz_launch_l2norm(float* x, int rows, int dim, float norm, hipStream_t st) {

@@ -131,7 +131,7 @@ static int seg_front_half(dz_seg* s, const float* d_wave, long long wave_stride,
 // With s->pre the hidden states travel as f16 (hi, lo) planes (same bytes as f32, same buffers)
 // and the projections of layers 1..3 and the MLP run on k_gemm_pre.hip.
 static int seg_back_half(dz_seg* s, int B, float* d_out, float* d_osp, float gamma, float beta, int normalize,
-                         float* d_vad, hipStream_t st) {
+                         float* d_vad, hipStream_t st, int track = DZ_TRACK_SPEECH) {
     const dz_seg_weights& w = s->w;
     const int F = s->g.P2;
     const long long rows = (long long)B * F;
@@ -169,7 +169,7 @@ static int seg_back_half(dz_seg* s, int B, float* d_out, float* d_osp, float gam
         m.W0split = w.lin0_split; m.W1split = w.lin1_split;
         m.b0 = w.lin0_b; m.b1 = w.lin1_b; m.cw = w.cls_w; m.cb = w.cls_b;
         m.rows = B * F; m.F = F; m.classes = w.num_classes; m.K = w.num_speakers; m.powerset = w.powerset;
-        m.gamma = gamma; m.beta = beta; m.seg = d_out; m.wout = d_osp; m.vad = d_vad;
+        m.gamma = gamma; m.beta = beta; m.seg = d_out; m.wout = d_osp; m.vad = d_vad; m.track = track;
         m.wave_mom = s->cur_stats;        // (split-f16 path: its clamps turn NaN into finite values)
         DzProfScope ps(DZ_T_MLP, B);
         return dz_launch_mlp_head(m, st);
@@ -187,16 +187,16 @@ static int seg_back_half(dz_seg* s, int B, float* d_out, float* d_osp, float gam
     // classifier + sigmoid / powerset decision (+ OverlappedSpeechPenalty weights): one launch
     DzProfScope ps(DZ_T_CLS, B);
     return dz_launch_seg_head(s->m1, w.cls_w, w.cls_b, B, F, w.num_classes, w.num_speakers, w.powerset, d_out, gamma,
-                              beta, normalize, d_osp, st, s->pre ? s->cur_stats : nullptr, d_vad);
+                              beta, normalize, d_osp, st, s->pre ? s->cur_stats : nullptr, d_vad, track);
 }
 
 // the whole network on one stream
 static int seg_forward(dz_seg* s, const float* d_wave, long long wave_stride, int B, float* d_out, float* d_osp,
-                       float gamma, float beta, int normalize, float* d_vad, void* stream) {
+                       float gamma, float beta, int normalize, float* d_vad, void* stream, int track = DZ_TRACK_SPEECH) {
     if (int rc = seg_open(s, d_out != nullptr, B, true, d_wave, wave_stride)) return rc;
     DzRangeScope range_scope(s->ctx->oflag_dev);
     if (int rc = seg_front_half(s, d_wave, wave_stride, B, (hipStream_t)stream)) return rc;
-    return seg_back_half(s, B, d_out, d_osp, gamma, beta, normalize, d_vad, (hipStream_t)stream);
+    return seg_back_half(s, B, d_out, d_osp, gamma, beta, normalize, d_vad, (hipStream_t)stream, track);
 }
 extern "C" int dz_seg_forward(dz_seg* s, const float* d_wave, long long wave_stride, int B,
                               float* d_out, void* stream) {
@@ -219,6 +219,31 @@ extern "C" int dz_seg_forward_vad(dz_seg* s, const float* d_wave, long long wave
     DZ_REQUIRE(s != nullptr, "dz_seg_forward_vad: NULL handle");
     DZ_REQUIRE(B <= s->Bm, "dz_seg_forward_vad: batch %d outside [1, %d]", B, s->Bm);
     return seg_forward(s, d_wave, wave_stride, B, d_out, nullptr, 0.f, 0.f, 0, d_vad, stream);
+}
+// dz_seg_forward_vad with the track chosen by the caller: DZ_TRACK_SPEECH is that function, DZ_TRACK_OVERLAP makes the
+// head write OverlappedSpeechDetection's track, the second largest of each frame's K >= 2 scores (dz_overlap_frame)
+extern "C" int dz_seg_forward_track(dz_seg* s, const float* d_wave, long long wave_stride, int B, float* d_out,
+                                    float* d_track, int track, void* stream) {
+    DZ_REQUIRE(d_out && d_track, "dz_seg_forward_track: NULL output");
+    DZ_REQUIRE(B >= 1, "dz_seg_forward_track: batch %d < 1", B);
+    DZ_REQUIRE(wave_stride >= 0, "dz_seg_forward_track: negative stride %lld", wave_stride);
+    DZ_REQUIRE(track == DZ_TRACK_SPEECH || track == DZ_TRACK_OVERLAP, "dz_seg_forward_track: unknown track %d", track);
+    DZ_REQUIRE(s != nullptr, "dz_seg_forward_track: NULL handle");
+    DZ_REQUIRE(B <= s->Bm, "dz_seg_forward_track: batch %d outside [1, %d]", B, s->Bm);
+    DZ_REQUIRE(track != DZ_TRACK_OVERLAP || (s->w.num_speakers >= 2 && s->w.num_speakers <= 8),
+               "dz_seg_forward_track: the overlap track needs 2 <= speakers <= 8 (got %d)", s->w.num_speakers);
+    return seg_forward(s, d_wave, wave_stride, B, d_out, nullptr, 0.f, 0.f, 0, d_track, stream, track);
+}
+// OverlappedSpeechDetection's reduction alone, for scores that are already on the device (the blocks pipeline):
+// d_out (rows) = the second largest of each of the `rows` rows of K scores, `row_stride` floats apart
+extern "C" int dz_overlap_track(const float* d_scores, long long row_stride, long long rows, int K, float* d_out,
+                                void* stream) {
+    DZ_REQUIRE(d_scores && d_out, "dz_overlap_track: NULL argument");
+    DZ_REQUIRE(K >= 2 && K <= 8, "dz_overlap_track: 2 <= speakers <= 8 (got %d)", K);
+    DZ_REQUIRE(rows >= 1, "dz_overlap_track: rows %lld < 1", rows);
+    DZ_REQUIRE(row_stride >= 0, "dz_overlap_track: negative stride %lld", row_stride);
+    DZ_REQUIRE(row_stride >= K, "dz_overlap_track: rows %lld floats apart hold no %d scores", row_stride, K);
+    return dz_launch_overlap_track(d_scores, row_stride, rows, K, d_out, (hipStream_t)stream);
 }
 // The two halves of dz_seg_forward_osp for a caller that keeps the stateless front end of the NEXT step
 // off the long dependent chain of this one (StreamBatch): dz_seg_front(t + 2) — SincNet and the first

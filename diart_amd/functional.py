@@ -3,7 +3,8 @@
 Same names and results as ``/root/reference/src/diart/functional.py`` (:6-13
 ``overlapped_speech_penalty``, :16-27 ``normalize_embeddings``), plus ``resample`` and ``adjust_volume``, the
 functional forms of the ``Resample`` and ``AdjustVolume`` blocks, and ``decode_pcm``, the push kernel's sample
-conversion over one buffer.  Inputs may live on the host
+conversion over one buffer, and ``overlap_track``, the per-frame reduction of ``OverlappedSpeechDetection`` (the one
+function here that answers a host tensor on the host: its definition is a torch statement).  Inputs may live on the host
 (the reference runs these on CPU tensors) or on the GPU; the result comes back on the device
 of the input.  There is no torch fallback: without ``libdiart_amd.so`` and a GPU they raise.
 """
@@ -229,3 +230,43 @@ def decode_pcm(raw, input_format: str, channels: int = 1, device: Optional[torch
                                              out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dz_pcm_decode")
         # `x` may be a temporary copy: its memory is reused in stream order by the caching allocator
     return out
+
+
+def overlap_track(scores):
+    """The OverlappedSpeechDetection track of ``scores (..., K)``, ``K`` speakers last: per row the second largest
+    value counted with multiplicity, NaN ordered above every number, shaped ``(..., 1)``, of the scores' dtype and on
+    their device.  The definition is
+
+        torch.sort(scores, dim=-1, descending=True).values[..., 1:2]
+
+    and that statement is what a CPU tensor or a numpy array gets (the array comes back as an array).  A CUDA tensor
+    runs ``overlap_track_kernel`` (``dz_overlap_track``) on the current stream: rows packed or at one common stride
+    are read in place, anything else is copied first.  The kernel is float32 with 2 <= K <= 8, and nothing is
+    converted behind the caller's back: a CUDA tensor of another dtype or with more speakers is a ``ValueError``.
+    ``K < 2`` (one speaker has no overlap) and empty scores are a ``ValueError`` on every path."""
+    if not isinstance(scores, torch.Tensor):
+        import numpy as np
+        return overlap_track(torch.from_numpy(np.asarray(scores))).numpy()
+    if scores.ndim < 1 or scores.shape[-1] < 2:
+        raise ValueError(f"overlap_track: scores of shape {tuple(scores.shape)} (at least 2 speakers on the last axis: "
+                         "one speaker has no overlap)")
+    if scores.numel() == 0:
+        raise ValueError(f"overlap_track: empty scores of shape {tuple(scores.shape)}")
+    if not scores.is_cuda:
+        return torch.sort(scores, dim=-1, descending=True).values[..., 1:2]
+    K = scores.shape[-1]
+    if K > 8:
+        raise ValueError(f"overlap_track: {K} speakers (the kernel takes 2 .. 8)")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"overlap_track: {scores.dtype} scores on the GPU (the kernel takes float32)")
+    x = scores
+    if x.ndim != 2 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < K):
+        x = x.reshape(-1, K)
+        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < K):
+            x = x.contiguous()
+    rows = x.shape[0]
+    out = torch.empty(rows, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dz_overlap_track(x.data_ptr(), x.stride(0) if rows > 1 else K, rows, K, out.data_ptr(),
+                                                torch.cuda.current_stream(x.device).cuda_stream), "dz_overlap_track")
+    return out.reshape(*scores.shape[:-1], 1)

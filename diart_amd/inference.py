@@ -312,7 +312,7 @@ class StreamingInference:
 # Which forms of the file batch `Benchmark` takes WITHOUT being asked (``concurrent_files=None``): a form whose file batch
 # measured slower than its loop stays on the loop unless ``concurrent_files`` is given (profiles/r24a_file_batch_models.json,
 # README "File batches for every model").
-FILE_BATCH_BY_DEFAULT = {"xvector": True, "wespeaker": True, "groups": True, "vad": True}
+FILE_BATCH_BY_DEFAULT = {"xvector": True, "wespeaker": True, "groups": True, "vad": True, "osd": True}
 
 
 def file_batch_kind(pipeline_class: type, segmentation_type: type, embedding_type: Optional[type], batch_size: int,
@@ -324,6 +324,7 @@ def file_batch_kind(pipeline_class: type, segmentation_type: type, embedding_typ
         SpeakerDiarization   HipSegmentation + HipWeSpeakerEmbedding                        "wespeaker"
         SpeakerDiarization   HipSegmentation + a groups-form embedding, batch_size == 1     "groups"
         VoiceActivityDetection   HipSegmentation                                            "vad"
+        OverlappedSpeechDetection   HipSegmentation                                         "osd"
 
     A groups-form model (ECAPA, speechbrain x-vector, TitaNet-L, speechbrain ResNet, mel-spectrogram ECAPA) pads and
     normalises a row by the geometry of the rows it is batched with: at ``batch_size=32`` the loop's embeddings depend on
@@ -331,10 +332,11 @@ def file_batch_kind(pipeline_class: type, segmentation_type: type, embedding_typ
     ``batch_size=1``.  Only there do the two agree, so only there is the file batch taken; any other batch size keeps the
     numbers it gives today.
 
-    None as well for ``concurrent_files <= 0``, a device that is not "cuda", a SUBCLASS of either pipeline (it may
+    None as well for ``concurrent_files <= 0``, a device that is not "cuda", a SUBCLASS of any of the pipelines (it may
     override any stage), models that are not exactly these classes, and — when ``concurrent_files`` was not given
     (``explicit=False``) — a form that ``FILE_BATCH_BY_DEFAULT`` leaves on the loop."""
     from .blocks.diarization import SpeakerDiarization
+    from .blocks.osd import OverlappedSpeechDetection
     from .blocks.vad import VoiceActivityDetection
     from .models import HipEmbedding, HipSegmentation, HipWeSpeakerEmbedding, _HipGroupsEmbedding
     if int(concurrent_files) <= 0 or device_type != "cuda" or segmentation_type is not HipSegmentation:
@@ -342,6 +344,8 @@ def file_batch_kind(pipeline_class: type, segmentation_type: type, embedding_typ
     kind = None
     if pipeline_class is VoiceActivityDetection:
         kind = "vad"
+    elif pipeline_class is OverlappedSpeechDetection:
+        kind = "osd"
     elif pipeline_class is SpeakerDiarization and isinstance(embedding_type, type):
         if embedding_type is HipEmbedding:
             kind = "xvector"
@@ -362,7 +366,7 @@ class Benchmark:
 
     ``concurrent_files`` files of this process share one GPU batch (``FileBatch``) where ``file_batch_kind`` names a
     form for the pipeline and its models: ``SpeakerDiarization`` with pyannote/embedding, with the WeSpeaker ResNet34, or
-    (at ``batch_size=1`` only) with a groups-form embedding, and ``VoiceActivityDetection``.  Everything else — and
+    (at ``batch_size=1`` only) with a groups-form embedding, ``VoiceActivityDetection`` and ``OverlappedSpeechDetection``.  Everything else — and
     everything at ``concurrent_files=0`` — runs the reference's loop, one file at a time in batches of ``batch_size``
     windows.  The RTTM files are the same either way; ``last_path`` says which path ran."""
 
@@ -417,8 +421,10 @@ class Benchmark:
         one-file-at-a-time loop: the rule is ``file_batch_kind`` (custom pipeline classes, non-HIP models, CPU devices,
         groups-form embeddings at a batch size other than 1, ``concurrent_files=0``)."""
         from .blocks.diarization import SpeakerDiarization
+        from .blocks.osd import OverlappedSpeechDetection
         from .blocks.vad import VoiceActivityDetection
-        if self.concurrent_files <= 0 or pipeline_class not in (SpeakerDiarization, VoiceActivityDetection):
+        if self.concurrent_files <= 0 or pipeline_class not in (SpeakerDiarization, VoiceActivityDetection,
+                                                                OverlappedSpeechDetection):
             return None                 # (a custom pipeline's config may have neither models nor a device)
         if getattr(getattr(config, "device", None), "type", "cpu") != "cuda":
             return None
@@ -433,24 +439,25 @@ class Benchmark:
         from .pipeline import FileBatch
         # one engine per (form, models, hyper-parameters): its scratch arenas (1 - 12 GB) and pinned slots are
         # allocated once, not per call
-        hyper = () if kind == "vad" else (config.rho_update, config.delta_new, config.gamma, config.beta,
+        one_track = kind in ("vad", "osd")
+        hyper = () if one_track else (config.rho_update, config.delta_new, config.gamma, config.beta,
                                           config.max_speakers, config.normalize_embedding_weights)
-        key = (kind, id(seg.model), None if kind == "vad" else id(emb.model), config.tau_active, hyper, config.duration,
+        key = (kind, id(seg.model), None if one_track else id(emb.model), config.tau_active, hyper, config.duration,
                config.step, config.latency, config.sample_rate, str(config.device), self.batch_size,
                self.concurrent_files, self.file_batch_rows)
         cached = getattr(self, "_fb_cache", None)
         if cached is not None and cached[0] == key:
             return cached[1]
-        fb = self._new_file_batch(FileBatch, seg, None if kind == "vad" else emb, config)
+        fb = self._new_file_batch(FileBatch, seg, None if one_track else emb, config, kind)
         self._fb_cache = (key, fb)
         return fb
 
-    def _new_file_batch(self, FileBatch, seg, emb, config):
+    def _new_file_batch(self, FileBatch, seg, emb, config, kind: Optional[str] = None):
         common = dict(rows=max(int(self.file_batch_rows), self.batch_size), max_files=self.concurrent_files, tau_active=config.tau_active,
                       duration=config.duration, step=config.step, latency=config.latency,
                       sample_rate=config.sample_rate, device=config.device)
         if emb is None:
-            return FileBatch(seg.model, None, pipeline="vad", **common)
+            return FileBatch(seg.model, None, pipeline="osd" if kind == "osd" else "vad", **common)
         return FileBatch(seg.model, emb.model, rho_update=config.rho_update, delta_new=config.delta_new,
                          gamma=config.gamma, beta=config.beta, max_speakers=config.max_speakers,
                          normalize_embedding_weights=config.normalize_embedding_weights, **common)

@@ -135,3 +135,41 @@ class DetectionErrorRate(_Accumulating):
             comp["missed detection"] += dur * (bool(r) and not h)
             comp["false alarm"] += dur * (bool(h) and not r)
         return comp
+
+
+def overlap_reference(annotation: Annotation) -> Annotation:
+    """The overlapped-speech regions of ``annotation`` as an annotation of ``"overlap"`` turns: the support of the
+    places where at least two turns with DIFFERENT labels are active.  Two overlapping turns of one label are one
+    speaker and no overlap; touching regions are merged; three speakers at once are one region."""
+    from .features import Segment
+    regions: List[Tuple[float, float]] = []
+    for lo, hi, labels in _bounded_regions(_turns(annotation)):
+        if len(labels) < 2:
+            continue
+        if regions and regions[-1][1] == lo:
+            regions[-1] = (regions[-1][0], hi)
+        else:
+            regions.append((lo, hi))
+    out = Annotation(uri=annotation.uri)
+    for i, (lo, hi) in enumerate(regions):
+        out[Segment(lo, hi), i] = "overlap"
+    return out
+
+
+def _bounded_regions(turns):
+    """Elementary regions of one annotation's turns -> (start, end, distinct active labels)."""
+    bounds = sorted({t for s, e, _ in turns for t in (s, e)})
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        labels = {label for s, e, label in turns if s <= lo and e >= hi}
+        if labels:
+            yield lo, hi, labels
+
+
+class OverlapDetectionErrorRate(DetectionErrorRate):
+    """``DetectionErrorRate(collar=0, skip_overlap=False)`` of an ``OverlappedSpeechDetection`` hypothesis against the
+    reference's OVERLAP regions (``overlap_reference``): the reference is an ordinary speaker annotation, the
+    hypothesis holds ``"overlap"`` turns.  ``total`` is the duration of overlapped speech in the reference."""
+    name = "overlap detection error rate"
+
+    def components(self, reference: Annotation, hypothesis: Annotation) -> Dict[str, float]:
+        return super().components(overlap_reference(reference), hypothesis)

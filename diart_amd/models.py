@@ -276,6 +276,32 @@ class HipSegmentation(_HipModule):
                    "dz_seg_forward_vad")
         return (track, scores) if return_scores else track
 
+    def forward_overlap(self, waveform: torch.Tensor, return_scores: bool = False):
+        """OverlappedSpeechDetection's hot path: ``waveform (B,1,S) -> (B,F,1)``, per frame the second largest of
+        ``__call__``'s scores counted with multiplicity, NaN ordered above every number (``torch.sort(scores, -1,
+        descending=True).values[..., 1:2]``), computed by the kernel that writes the scores (``dz_seg_forward_track``
+        with ``DZ_TRACK_OVERLAP``).  ``return_scores``: ``(track, scores (B,F,K))``.  A model with one speaker has no
+        overlap: ``ValueError``.  Enqueued on the current stream; does not synchronise."""
+        if self.device is None:
+            self.to(waveform.device)
+        if self.num_speakers < 2:                # (known once the weights are packed)
+            raise ValueError(f"forward_overlap: a model with {self.num_speakers} speaker has no overlap track "
+                             "(at least 2 speakers)")
+        if waveform.device != self.device:
+            waveform = waveform.to(self.device)
+        rows = _as_rows(waveform)
+        B, S = rows.shape
+        if B < 1:
+            raise ValueError("empty batch")
+        handle = self._need(S, B)
+        F = self.num_frames(S)
+        scores = torch.empty((B, F, self.num_speakers), dtype=torch.float32, device=self.device)
+        track = torch.empty((B, F, 1), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().dz_seg_forward_track(handle, rows.data_ptr(), rows.stride(0) if B > 1 else S, B,
+                                                    scores.data_ptr(), track.data_ptr(), _lib.TRACK_OVERLAP,
+                                                    _stream_ptr(self.device)), "dz_seg_forward_track")
+        return (track, scores) if return_scores else track
+
 
 class _HipSpeakerEmbedding(_HipModule):
     """The plumbing of every speaker-embedding handle: one C prefix (``_c``: ``dz_emb``, ``dz_ecapa``, ``dz_sbx``,

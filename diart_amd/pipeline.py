@@ -22,7 +22,8 @@ independent, only the host-side clustering is sequential per stream):
     host       : clustering + output tail of step t-1 (C++ threads, fp64) while the GPU runs step t
 
 ``VadBatch`` is the segmentation-only form for ``VoiceActivityDetection``: no embedding, no clustering; the head kernel
-writes each stream's speech track and only that track reaches the host's output tails.  The other embeddings share the
+writes each stream's speech track and only that track reaches the host's output tails; ``OverlapBatch`` is the same step
+for ``OverlappedSpeechDetection``, the head writing the overlap track (the second largest score).  The other embeddings share the
 two-chain engine: ``WeSpeakerBatch`` for the WeSpeaker ResNet34 embedding, whose trunk is the long chain of the step (the
 segmentation runs under it), and ``GroupsBatch`` for the groups form (``HipEcapaEmbedding``, BASELINE.json config 3,
 ``HipSbXvectorEmbedding``, ``HipTitaNetEmbedding``, ``HipSbResNetEmbedding``, ``HipEcapaMelEmbedding``), which ``StreamBatch(seg, emb, ...)``
@@ -849,6 +850,8 @@ class VadBatch(_StepEngine):
     streams in the default precision the matrix-core recurrence on ``THROUGHPUT_LANES`` lanes.  ``host_threads``:
     threads of the output tail."""
 
+    LABEL = "speech"            # what the turns of `detect` are called (OverlapBatch: "overlap")
+
     def __init__(self, segmentation: HipSegmentation, num_streams: int, tau_active: float = 0.6,
                  duration: float = 5.0, step: float = 0.5, latency: Optional[float] = None,
                  device: Optional[torch.device] = None, *, lanes: Optional[int] = None,
@@ -913,8 +916,7 @@ class VadBatch(_StepEngine):
         stats = slot["stats"]
         _lib.check(lib.dz_wave_stats(self._ctx, base, stride, N, S, stats.data_ptr(), a.cuda_stream), "dz_wave_stats")
         _lib.check(lib.dz_seg_use_wave_stats(h, stats.data_ptr()), "dz_seg_use_wave_stats")
-        _lib.check(lib.dz_seg_forward_vad(h, base, stride, N, slot["seg"].data_ptr(), slot["vad"].data_ptr(),
-                                          a.cuda_stream), "dz_seg_forward_vad")
+        self._forward_track(h, base, stride, N, slot, a)
         _lib.check(lib.dz_results_to_host(self._ctx, slot["vad"].data_ptr(), slot["vad_h"].data_ptr(), N * F,
                                           None, None, 0, a.cuda_stream), "dz_results_to_host")
         slot["done"].record(a)
@@ -923,6 +925,11 @@ class VadBatch(_StepEngine):
         slot["rows"], slot["slots"], slot["keep"] = N, None, keep
         self._t += 1
         return slot
+
+    def _forward_track(self, h, base: int, stride: int, N: int, slot: dict, a) -> None:
+        """The step's forward pass on lane stream ``a``: scores -> slot["seg"], the (N,F) track -> slot["vad"]."""
+        _lib.check(self._lib.dz_seg_forward_vad(h, base, stride, N, slot["seg"].data_ptr(), slot["vad"].data_ptr(),
+                                                a.cuda_stream), "dz_seg_forward_vad")
 
     # ------------------------------------------------------------------ host half
     def finish(self, ticket: dict) -> np.ndarray:
@@ -941,7 +948,28 @@ class VadBatch(_StepEngine):
         ticket = self.launch(waves, starts)
         self.finish(ticket)
         turns, nturns = ticket["tail"][4], ticket["tail"][5]
-        return [BatchedOutputTail.annotation(turns[i], int(nturns[i]), label="speech") for i in range(self.n)]
+        return [BatchedOutputTail.annotation(turns[i], int(nturns[i]), label=self.LABEL) for i in range(self.n)]
+
+
+class OverlapBatch(VadBatch):
+    """``OverlappedSpeechDetection`` of N concurrent streams: ``VadBatch``'s step with the head kernel writing the
+    overlap track — per frame the second largest of the speaker scores, NaN ordered above every number
+    (``dz_seg_forward_track`` with ``DZ_TRACK_OVERLAP``) — in place of the max, and turns labelled ``"overlap"``.
+    Per stream it produces what that stream's own ``OverlappedSpeechDetection`` (blocks/osd.py) produces.  Only the
+    (N,F) track travels to the host; ``launch`` / ``finish`` / ``reset`` / ``detect``, the rings, ``slots=`` and the
+    lane choices are ``VadBatch``'s.  A model with one speaker has no overlap: ``ValueError``."""
+
+    LABEL = "overlap"
+
+    def __init__(self, segmentation: HipSegmentation, num_streams: int, tau_active: float = 0.5, *args, **kwargs):
+        super().__init__(segmentation, num_streams, tau_active, *args, **kwargs)
+        if int(self.seg.num_speakers) < 2:       # (known once the weights are on the device; no handle exists yet)
+            raise ValueError(f"OverlapBatch: a segmentation model with {self.seg.num_speakers} speaker has no overlap "
+                             "track (at least 2 speakers)")
+
+    def _forward_track(self, h, base: int, stride: int, N: int, slot: dict, a) -> None:
+        _lib.check(self._lib.dz_seg_forward_track(h, base, stride, N, slot["seg"].data_ptr(), slot["vad"].data_ptr(),
+                                                  _lib.TRACK_OVERLAP, a.cuda_stream), "dz_seg_forward_track")
 
 
 class _TwoChainEngine(_DiarizationEngine):
@@ -1131,6 +1159,7 @@ class FileBatch:
           x-vector, TitaNet-L, speechbrain ResNet,                (each chunk's K rows embedded alone: the blocks path at
           mel-spectrogram ECAPA)                                  batch_size = 1, see Benchmark.file_batch)
         None with pipeline="vad"                     "vad"        VadBatch; every turn is labelled "speech"
+        None with pipeline="osd"                     "osd"        OverlapBatch; every turn is labelled "overlap"
 
     Everything ``run`` does with its engine goes through ``_launch_rows`` and the ticket's pinned results
     (``seg_h`` / ``emb_h``, or ``vad_h``).
@@ -1145,7 +1174,7 @@ class FileBatch:
     # 6.7 us where the 16 copies take 112 us of GPU time, but the pyannote/embedding form, measured against the parent
     # commit, showed no gain from it (profiles/r24a_file_batch_models.json; README "File batches for every model"): the
     # form that existed keeps the copies it had, the new forms start with the kernel.
-    GATHER_DEFAULT = {"xvector": False, "wespeaker": True, "groups": True, "vad": True}
+    GATHER_DEFAULT = {"xvector": False, "wespeaker": True, "groups": True, "vad": True, "osd": True}
 
     def __init__(self, segmentation: HipSegmentation, embedding=None, *, rows: int = 64,
                  max_files: int = 16, tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
@@ -1163,17 +1192,18 @@ class FileBatch:
         the segmentation scores differently, and the RTTM files have to be those of the one-file-at-a-time loop byte for
         byte; two lanes are what the two-chain engines run anyway (gigabytes of arena per lane).
 
-        ``pipeline``: "diarization" | "vad" (``embedding`` must then be None).  ``gather``: fill a step's stage with one
+        ``pipeline``: "diarization" | "vad" | "osd" (``embedding`` must be None for the last two).  ``gather``: fill a step's stage with one
         ``dz_gather_windows`` launch instead of one torch copy per open file (None = the form's default)."""
         self.rows, self.max_files = int(rows), max(1, min(int(max_files), int(rows)))
-        if pipeline not in ("diarization", "vad"):
-            raise ValueError(f"FileBatch: pipeline={pipeline!r} (expected diarization | vad)")
-        if pipeline == "vad":
+        if pipeline not in ("diarization", "vad", "osd"):
+            raise ValueError(f"FileBatch: pipeline={pipeline!r} (expected diarization | vad | osd)")
+        if pipeline in ("vad", "osd"):
             if embedding is not None:
-                raise ValueError("FileBatch(pipeline='vad') takes no embedding")
-            self.kind = "vad"
-            self.engine = VadBatch(segmentation, self.rows, tau_active, duration, step, latency, device, lanes=lanes,
-                                   recurrence=recurrence, host_threads=threads)
+                raise ValueError(f"FileBatch(pipeline={pipeline!r}) takes no embedding")
+            self.kind = pipeline
+            engine = VadBatch if pipeline == "vad" else OverlapBatch
+            self.engine = engine(segmentation, self.rows, tau_active, duration, step, latency, device, lanes=lanes,
+                                 recurrence=recurrence, host_threads=threads)
         else:
             if isinstance(embedding, HipWeSpeakerEmbedding):
                 self.kind, engine = "wespeaker", WeSpeakerBatch
@@ -1194,7 +1224,7 @@ class FileBatch:
         self.S, self.hop = int(round(sample_rate * duration)), int(round(sample_rate * step))
         assert self.hop % 4 == 0, "the step must be a multiple of 4 samples (16-byte aligned windows)"
         self.tau, self.rho, self.delta = tau_active, rho_update, delta_new
-        self.G = 1 if self.kind == "vad" else int(max_speakers)
+        self.G = 1 if self.kind in ("vad", "osd") else int(max_speakers)
         self.threads, self.patch_collar = int(threads), patch_collar
         self._lib = _lib.load()
         self._ctx = _lib.context(self.device.index)
@@ -1209,7 +1239,7 @@ class FileBatch:
     def _ensure_state(self, F: int) -> None:
         if self._tails is not None:
             return
-        for _ in range(0 if self.kind == "vad" else self.max_files):
+        for _ in range(0 if self.kind in ("vad", "osd") else self.max_files):
             h = _lib.vp()
             _lib.check(self._lib.dz_clu_create(self.tau, self.rho, self.delta, self.G, C.byref(h)), "dz_clu_create")
             self._clu.append(h)
@@ -1340,7 +1370,7 @@ class FileBatch:
         files = FileBatch._Loader(files, self)
         F = self.engine.seg.to(self.device).num_frames(self.S)
         self._ensure_state(F)
-        vad = self.kind == "vad"
+        vad = self.kind in ("vad", "osd")         # the one-track forms: no clustering, one label for every turn
         res = self.duration / F
         open_files: List[Optional[dict]] = [None] * self.max_files
         done: dict = {}
@@ -1490,7 +1520,7 @@ class FileBatch:
                 for arr in chunks:
                     for n, (s, e, g) in enumerate(arr):
                         if vad:                 # one track per turn of a chunk, like Timeline.to_annotation
-                            ann[Segment(s + shift, e + shift), n] = "speech"
+                            ann[Segment(s + shift, e + shift), n] = self.engine.LABEL
                         else:
                             ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
             out[uri] = ann.support(self.patch_collar)

@@ -17,7 +17,9 @@ same configuration produces.  The model pair may be config 2's (x-vector) or con
 the engine is a ``WeSpeakerBatch``.  ``pipeline="vad"`` (no embedding) serves
 ``VoiceActivityDetection`` instead (``diart.serve --pipeline VoiceActivityDetection``, reference
 ``console/serve.py:19-22,99-102``) on a ``VadBatch``: every stream's turns are labelled ``"speech"``, and
-only the prediction is served, not the aggregated audio.
+only the prediction is served, not the aggregated audio.  ``pipeline="osd"`` (no embedding either) serves
+``OverlappedSpeechDetection`` the same way on an ``OverlapBatch``: the turns are the regions where two or more people
+talk at once, labelled ``"overlap"``.
 
 Audio reaches the GPU through per-stream device rings (``AudioRing.push_rows`` / ``gather``): a step
 uploads only the NEW 500 ms block of each stream that has one (32 KB instead of the 320 KB window the
@@ -55,9 +57,12 @@ from .features import Annotation
 from .functional import _target_db, adjust_volume, adjust_volume_rows, resampler
 from .models import HipWeSpeakerEmbedding
 from .pcm import INPUT_FORMATS, pcm_to_mono  # noqa: F401  (INPUT_FORMATS: name -> dtype of the values clients push)
-from .pipeline import AudioRing, StreamBatch, VadBatch, WeSpeakerBatch
+from .pipeline import AudioRing, OverlapBatch, StreamBatch, VadBatch, WeSpeakerBatch
 
-PIPELINES = ("diarization", "vad")
+PIPELINES = ("diarization", "vad", "osd")
+# the segmentation-only pipelines: (what it is, its engine, the label of every turn)
+_ONE_TRACK = {"vad": ("VoiceActivityDetection", VadBatch, "speech"),
+              "osd": ("OverlappedSpeechDetection", OverlapBatch, "overlap")}
 MAX_INPUT_CHANNELS = 8
 
 
@@ -87,9 +92,9 @@ class StreamServer:
                  volume_in_db: Optional[float] = None):
         if pipeline not in PIPELINES:
             raise ValueError(f"StreamServer: pipeline={pipeline!r} (expected one of {PIPELINES})")
-        if pipeline == "vad" and embedding is not None:
-            raise ValueError("StreamServer: pipeline='vad' (VoiceActivityDetection) runs the segmentation only; "
-                             "pass embedding=None")
+        if pipeline in _ONE_TRACK and embedding is not None:
+            raise ValueError(f"StreamServer: pipeline={pipeline!r} ({_ONE_TRACK[pipeline][0]}) runs the segmentation "
+                             "only; pass embedding=None")
         if input_format not in INPUT_FORMATS:
             raise ValueError(f"StreamServer: input_format={input_format!r} (expected one of {tuple(INPUT_FORMATS)})")
         if not (isinstance(input_channels, (int, np.integer)) and 1 <= input_channels <= MAX_INPUT_CHANNELS):
@@ -102,7 +107,7 @@ class StreamServer:
         self.input_format, self.input_channels = input_format, int(input_channels)
         self._in_dtype = INPUT_FORMATS[input_format]
         self.pipeline = pipeline
-        self._label = "speech" if pipeline == "vad" else None     # turn labels: speaker{g} | speech
+        self._label = _ONE_TRACK[pipeline][2] if pipeline in _ONE_TRACK else None   # turn labels: speaker{g} | speech | overlap
         self.duration, self.step_seconds, self.sample_rate = float(duration), float(step), int(sample_rate)
         self.latency = self.step_seconds if latency is None else float(latency)
         # the rate clients push at.  Blocks and windows are cut at this rate; a window at another rate than the
@@ -126,10 +131,12 @@ class StreamServer:
         import collections
         self.step_errors = collections.deque(maxlen=64)   # (time, repr) of failed steps, newest last
         # `engine(windows (k, S) float32, starts (k,), slots [k]) -> list of k (turns (m, 3) array)`;
-        # the default engine is a StreamBatch with the C++ output tail (a VadBatch for pipeline="vad")
-        if engine is None and pipeline == "vad":
-            self.batch = VadBatch(segmentation, self.max_streams, tau_active, duration=duration, step=step,
-                                  latency=self.latency, device=device)
+        # the default engine is a StreamBatch with the C++ output tail (a VadBatch for pipeline="vad", an OverlapBatch
+        # for pipeline="osd")
+        if engine is None and pipeline in _ONE_TRACK:
+            batch_cls = _ONE_TRACK[pipeline][1]
+            self.batch = batch_cls(segmentation, self.max_streams, tau_active, duration=duration, step=step,
+                                   latency=self.latency, device=device)
         elif engine is None:
             # the WeSpeaker ResNet34 embedding has an engine of its own (its trunk is the long chain of a step)
             batch_cls = WeSpeakerBatch if isinstance(embedding, HipWeSpeakerEmbedding) else StreamBatch

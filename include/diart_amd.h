@@ -159,6 +159,23 @@ int dz_seg_forward_osp(dz_seg* seg, const float* d_wave, long long wave_stride, 
  * that writes d_out; honours dz_seg_use_wave_stats like dz_seg_forward_osp.                               */
 int dz_seg_forward_vad(dz_seg* seg, const float* d_wave, long long wave_stride, int batch,
                        float* d_out, float* d_vad, void* stream);
+/* dz_seg_forward_vad with the track chosen by the caller.  DZ_TRACK_SPEECH: d_track is dz_seg_forward_vad's d_vad,
+ * from the same code.  DZ_TRACK_OVERLAP: the OverlappedSpeechDetection track (pyannote's pipeline of that name on
+ * the (frames, speakers) scores), d_track (B,F) = the SECOND LARGEST of each frame's K scores counted with
+ * multiplicity, torch.sort(d_out, -1, descending=True).values[..., 1]: NaN is ordered above every number, so a frame
+ * with one NaN score gets its largest number and a frame with two gets NaN; a window with non-finite samples has NaN
+ * rows and a NaN track.  For a powerset model d_out is the hard 0/1 decision, and the track is 1 exactly where a
+ * two-speaker class wins.  Refused (status 2, the message names the function, nothing is launched): NULL handle or
+ * outputs, batch < 1 or > max_batch, negative stride, a track that is neither of the two, and for DZ_TRACK_OVERLAP a
+ * model with fewer than 2 (or more than 8) speakers: one speaker has no overlap, and it is not answered with zeros. */
+enum { DZ_TRACK_SPEECH = 0, DZ_TRACK_OVERLAP = 1 };
+int dz_seg_forward_track(dz_seg* seg, const float* d_wave, long long wave_stride, int batch,
+                         float* d_out, float* d_track, int track, void* stream);
+/* The reduction of DZ_TRACK_OVERLAP alone, for scores already on the device: d_scores holds `rows` rows of K scores,
+ * `row_stride` >= K floats apart; d_out (rows) gets each row's second largest as above.  One thread per row; packed
+ * rows (row_stride == K) are loaded by whole waves.  Refused like the above: NULL pointers, K < 2 or K > 8, rows < 1,
+ * a negative stride or one below K.                                                                               */
+int dz_overlap_track(const float* d_scores, long long row_stride, long long rows, int K, float* d_out, void* stream);
 int dz_seg_destroy(dz_seg* seg);
 
 /* ---- embedding: replaces the callable behind EmbeddingModel.__call__ --------
