@@ -286,6 +286,9 @@ SIGNATURES = {
     "dz_k_lstm_planes": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_int, vp]),
     "dz_k_stats_pool": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
                                   C.c_int, vp, C.c_int, vp]),
+    "dz_k_pool_pieces": (C.c_int, [C.c_int]),
+    "dz_k_tdnn_pool": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                 C.c_int, vp]),
     "dz_k_powerset": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "dz_k_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, vp]),

@@ -478,7 +478,9 @@ __global__ __launch_bounds__(256) void pool_combine_kernel(const float* __restri
         v2 += (double)so[1];
     }
     float* o = out + (long long)row * ldo;
-    o[c] = (float)mean;
+    // (a row without any weight: 0 / 0 like pyannote and stats_pool_reg_kernel — every piece was skipped above and the
+    // std below is NaN already)
+    o[c] = v1 > 0.0 ? (float)mean : __builtin_nanf("");
     o[C + c] = (float)sqrt(M2 / (v1 - v2 / v1));
 }
 }  // namespace

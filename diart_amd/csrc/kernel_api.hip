@@ -220,6 +220,38 @@ extern "C" int dz_k_stats_pool(dz_ctx* ctx, const float* d_x, int frames, int ch
                                 d_weights ? weight_frames : frames, rows, rows_per_x, d_out, ldo,
                                 (hipStream_t)stream);
 }
+extern "C" int dz_k_pool_pieces(int pitch) { return dz_pool_pieces(pitch); }
+// tdnn5 + statistics pooling on the caller's buffers, the two ways emb_head (xvec_api.hip) runs them: the pooled
+// epilogue + pool_combine, or the plain layer + stats_pool at the handle's chunk stride (pitch rows, not frames)
+extern "C" int dz_k_tdnn_pool(dz_ctx* ctx, const dz_convgemm_desc* d, const float* d_weights, int weight_frames,
+                              int speakers, int pitch, int frames, int channels, int fused, float* d_part,
+                              float* d_s0, float* d_out, int ldo, void* stream) {
+    DZ_REQUIRE(ctx && d && d_out, "dz_k_tdnn_pool: NULL argument");
+    DZ_REQUIRE(d->epi == DZ_EPI_TDNN && d->taps == 1 && d->B == 1, "dz_k_tdnn_pool: built for the flattened 1 x 1 TDNN layer");
+    DZ_REQUIRE(speakers >= 1 && pitch >= 1 && frames >= 2 && frames <= pitch && d->Tout >= pitch && d->Tout % pitch == 0,
+               "dz_k_tdnn_pool: %d speakers, %d frames of a pitch of %d rows, %d rows in all", speakers, frames, pitch, d->Tout);
+    DZ_REQUIRE(channels >= 1 && channels <= d->Nstore && d->Nstore <= d->Npad && ldo >= 2 * channels,
+               "dz_k_tdnn_pool: %d channels of %d stored columns, out rows of %d floats", channels, d->Nstore, ldo);
+    DZ_REQUIRE(!d_weights || weight_frames >= 2 || weight_frames <= -2, "dz_k_tdnn_pool: weight_frames %d", weight_frames);
+    DZ_HIP(hipSetDevice(ctx->device));
+    DzRangeScope range_scope(ctx->oflag_dev);
+    hipStream_t st = (hipStream_t)stream;
+    const int nx = d->Tout / pitch, Fw = d_weights ? weight_frames : frames;
+    int rc;
+    if (fused) {
+        DZ_REQUIRE(d_part && d_s0, "dz_k_tdnn_pool: the pooled epilogue needs part and s0");
+        DzPoolFuse q;
+        q.w = d_weights; q.Fw = Fw; q.K = speakers; q.P = pitch; q.T = frames; q.np = dz_pool_pieces(pitch);
+        q.part = d_part; q.s0 = d_s0;
+        if ((rc = dz_launch_gemm_pre_pool(*d, q, st))) return rc;
+        return dz_launch_pool_combine(d_part, d_s0, nx, speakers, q.np, pitch, frames, channels, d->Npad, d_out, ldo, st);
+    }
+    DZ_REQUIRE(d->Y && d->ldy >= channels, "dz_k_tdnn_pool: the stand-alone pooling reads the layer's f32 output Y");
+    DZ_REQUIRE(frames <= 640, "dz_k_tdnn_pool: %d frames per chunk (stats_pool: at most 640)", frames);
+    if ((rc = dz_launch_gemm_pre(*d, st))) return rc;
+    return dz_launch_stats_pool(d->Y, (long long)pitch * d->ldy, frames, channels, d->ldy, d_weights, Fw, nx * speakers,
+                                speakers, d_out, ldo, st);
+}
 extern "C" int dz_k_powerset(dz_ctx* ctx, const float* d_logits, int rows, int classes,
                              int speakers, float* d_out, void* stream) {
     DZ_REQUIRE(ctx && d_logits && d_out, "dz_k_powerset: NULL argument");

@@ -781,6 +781,19 @@ int dz_k_lstm_planes(dz_ctx* ctx, const float* d_gx, const float* d_whh, const v
 int dz_k_stats_pool(dz_ctx* ctx, const float* d_x, int frames, int channels, int ldx,
                     const float* d_weights, int weight_frames, int rows, int rows_per_x,
                     float* d_out, int ldo, void* stream);
+/* The last x-vector layer with its statistics pooling, both ways the embedding handle runs them, on the caller's
+ * buffers.  desc: the flattened 1 x 1 TDNN layer over Tout = chunks * pitch rows (DZ_EPI_TDNN, taps = 1, B = 1, kb-major
+ * planes, as dz_k_gemm_pre); chunk b owns rows b * pitch .., of which the first `frames` are pooled, each with the
+ * `speakers` weight rows b * speakers .. of d_weights (weight_frames and NULL as at dz_k_stats_pool).
+ * fused != 0: the pooled epilogue of the layer, then the merge of its tile pieces (speakers <= 4, pitch >= 128);
+ *   d_part [chunks][np][speakers][Npad][2] and d_s0 [chunks][np][speakers][2] floats, np = dz_k_pool_pieces(pitch);
+ *   desc->Y is not written.
+ * fused == 0: the layer writes desc->Y, the stand-alone kernel pools it, chunks pitch * ldy floats apart.
+ * d_out [chunks * speakers][ldo]: mean in columns 0 .. channels - 1, std in channels .. 2 channels - 1.           */
+int dz_k_pool_pieces(int pitch);
+int dz_k_tdnn_pool(dz_ctx* ctx, const dz_convgemm_desc* desc, const float* d_weights, int weight_frames, int speakers,
+                   int pitch, int frames, int channels, int fused, float* d_part, float* d_s0, float* d_out, int ldo,
+                   void* stream);
 int dz_k_powerset(dz_ctx* ctx, const float* d_logits, int rows, int classes, int speakers,
                   float* d_out, void* stream);
 
