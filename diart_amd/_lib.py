@@ -263,6 +263,11 @@ SIGNATURES = {
     "dz_tune_vad_host": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp,
                                    C.c_int]),
     "dz_rows_repeat": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, c_int_p]),
+    "dz_gallery_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
+    "dz_gallery_destroy": (C.c_int, [vp]),
+    "dz_gallery_size": (C.c_int, [vp]),
+    "dz_gallery_dim": (C.c_int, [vp]),
+    "dz_gallery_match": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, vp, vp]),
     # kernel-level entry points
     "dz_k_convgemm": (C.c_int, [vp, vp, vp]),
     "dz_k_gemm_f32": (C.c_int, [vp, vp, vp]),

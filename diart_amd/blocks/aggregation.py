@@ -199,14 +199,18 @@ class BatchedOutputTail:
         return self._agg, self._rows, self._t0, self._res, self._turns, self._nturns
 
     @staticmethod
-    def annotation(turns: np.ndarray, nturns: int, uri=None, shift: float = 0.0, label: Optional[str] = None):
+    def annotation(turns: np.ndarray, nturns: int, uri=None, shift: float = 0.0, label: Optional[str] = None,
+                   names=None):
         """Speech turns of one stream as the ``Annotation`` ``Binarize`` builds (utils.py:47-58); ``label``: one label
-        for every turn (``"speech"``: VoiceActivityDetection, vad.py:183-189) instead of ``speaker{g}``."""
+        for every turn (``"speech"``: VoiceActivityDetection, vad.py:183-189) instead of ``speaker{g}``; ``names``: a
+        mapping g -> name for the global speakers a gallery has named (``gallery.SpeakerNames``), the others stay
+        ``speaker{g}``."""
         from ..features import Annotation
         ann = Annotation(uri=uri, modality="speech")
         for n, (s, e, g) in enumerate(turns[:nturns]):
             if label is None:
-                ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
+                name = names.get(int(g)) if names else None
+                ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}" if name is None else name
             else:                       # one track per turn, like Timeline.to_annotation
                 ann[Segment(s + shift, e + shift), n] = label
         return ann

@@ -732,6 +732,14 @@ int dz_launch_resample(const float* in, long long in_stride, long long in_len, i
 int dz_launch_rows_repeat(const float* wave, long long stride, int n_rows, int S, int* differs, int* repeat_out,
                           hipStream_t st);
 
+// k_gallery.hip -----------------------------------------------------------
+// gallery tiles of E voiceprints (the second axis of the partial results)
+int dz_gallery_tiles(int E);
+// norm: R floats; p_*: R x dz_gallery_tiles(E) each; index / dist / second: R each, device or mapped pinned memory
+int dz_launch_gallery_match(const float* X, long long stride, int R, int D, const float* G, int E, float* norm,
+                            int* p_idx, float* p_best, float* p_second, int* index, float* dist, float* second,
+                            hipStream_t st);
+
 struct dz_ctx {
     int device;
     // "an operand left the f16 range" flag of the split-f16 kernels: one int in pinned, device-mapped

@@ -270,3 +270,43 @@ def overlap_track(scores):
         _lib.check(_lib.load().dz_overlap_track(x.data_ptr(), x.stride(0) if rows > 1 else K, rows, K, out.data_ptr(),
                                                 torch.cuda.current_stream(x.device).cuda_stream), "dz_overlap_track")
     return out.reshape(*scores.shape[:-1], 1)
+
+
+def gallery_match(embeddings, voiceprints):
+    """The nearest voiceprint of every row of ``embeddings (..., D)`` among ``voiceprints (E, D)`` by the clustering's
+    cosine distance -> ``(index int32, distance f32, second f32)`` shaped ``(...)``.  The definition is, on float64,
+
+        d = 1 - (x @ g.T) / (x.norm(dim=1, keepdim=True) * g.norm(dim=1)[None])
+        index = d.argmin(dim=1)          # the lowest index among equal distances
+
+    with ``distance`` that minimum and ``second`` the smallest distance among the other voiceprints (+inf when E == 1);
+    a row with a NaN / Inf element or of zero norm gets -1 / NaN / NaN.  A CPU tensor or a numpy array gets exactly that
+    statement, rounded to float32 (the array comes back as arrays).  A CUDA tensor runs ``gallery_match`` of
+    ``csrc/k_gallery.hip`` (``dz_gallery_match``; float32, D a multiple of 64 from 64 to 512, E <= 65 536) against a
+    gallery built from ``voiceprints`` for this call; to match step after step keep a ``gallery.SpeakerGallery``."""
+    import numpy as np
+    if not isinstance(embeddings, torch.Tensor):
+        out = gallery_match(torch.from_numpy(np.asarray(embeddings)), voiceprints)
+        return tuple(t.numpy() for t in out)
+    g = voiceprints if isinstance(voiceprints, torch.Tensor) else torch.from_numpy(np.asarray(voiceprints))
+    if g.ndim != 2 or g.shape[0] < 1 or embeddings.ndim < 1 or embeddings.shape[-1] != g.shape[1] or embeddings.numel() == 0:
+        raise ValueError(f"gallery_match: embeddings of shape {tuple(embeddings.shape)} against voiceprints of shape "
+                         f"{tuple(g.shape)}")
+    if embeddings.is_cuda:
+        from .gallery import SpeakerGallery
+        names = [f"voiceprint {e}" for e in range(g.shape[0])]
+        return SpeakerGallery(names, g, embeddings.device).match(embeddings)
+    lead = embeddings.shape[:-1]
+    x = embeddings.reshape(-1, g.shape[1]).to(torch.float64)
+    g = g.detach().cpu().to(torch.float64)
+    norm = x.norm(dim=1, keepdim=True)
+    bad = ~torch.isfinite(x).all(dim=1) | (norm[:, 0] == 0) | ~torch.isfinite(norm[:, 0])
+    x = torch.where(bad[:, None], torch.ones_like(x), x)
+    d = 1 - (x @ g.T) / (x.norm(dim=1, keepdim=True) * g.norm(dim=1)[None])
+    index = d.argmin(dim=1)
+    dist = d.gather(1, index[:, None])[:, 0]
+    second = d.scatter(1, index[:, None], float("inf")).min(dim=1).values
+    nan = torch.full_like(dist, float("nan"))
+    index = torch.where(bad, torch.full_like(index, -1), index).to(torch.int32)
+    return (index.reshape(lead), torch.where(bad, nan, dist).to(torch.float32).reshape(lead),
+            torch.where(bad, nan, second).to(torch.float32).reshape(lead))

@@ -379,6 +379,8 @@ class _StepEngine:
         stats = torch.empty((self.n, self._lib.dz_wave_stats_floats()), dtype=torch.float32, device=self.device)
         slot = dict(self._new_slot(shape), shape=shape, busy=False, stats=stats, ev_in=torch.cuda.Event(),
                     done=torch.cuda.Event(blocking=self.blocking_wait))
+        if getattr(self, "_gallery", None) is not None:
+            self._match_buffers(slot)
         self._slots.append(slot)
         return slot
 
@@ -491,6 +493,7 @@ class _DiarizationEngine(_StepEngine):
         self.max_speakers, self.tau_active, self.cluster_threads = max_speakers, tau_active, cluster_threads
         self.with_tail, self.duration, self.step = bool(tail), float(duration), float(step)
         self.latency = self.step if latency is None else float(latency)
+        self._gallery, self._names, self._gallery_handles = None, None, []     # (set_gallery)
 
     def _make_tail(self, F: int) -> Optional[BatchedOutputTail]:
         if not self.with_tail:
@@ -511,10 +514,67 @@ class _DiarizationEngine(_StepEngine):
         self.clustering.reset(slot)
         if self.tail is not None:
             self.tail.reset(slot)
+        if self._names is not None:
+            self._names.reset(slot)
         if slot is None:
             self._steps[:] = 0
         else:
             self._steps[slot] = 0
+
+    # ------------------------------------------------------------------ speaker gallery
+    def set_gallery(self, gallery, delta_id=None) -> None:
+        """Name the speakers against ``gallery`` (a ``gallery.SpeakerGallery``) from the next launch on; ``None``
+        removes it.  ``delta_id``: the largest cosine distance at which a match counts (no default: it depends on the
+        embedding model).  With a gallery every launch enqueues one ``dz_gallery_match`` over the step's (N * K, D)
+        embeddings, behind the embedding on the stream that carries the results to the host, its answers written to
+        pinned memory by the kernel itself; ``finish`` adds ``ticket["match"] = (index, distance, second)``, each
+        (N, K), and ``ticket["names"]``, per row a dict g -> name (``gallery.SpeakerNames`` after this step's
+        assignment); ``diarize`` labels its turns with them.  Each lane gets a handle of its own (a device copy of the
+        voiceprints + the scratch of one match).  Refused by name: a gallery of another dimension than the embedding's,
+        or on another device.  Setting another gallery (or None) forgets every stream's names; call it with no step
+        between ``launch`` and ``finish``."""
+        who = type(self).__name__
+        if gallery is not None:
+            from .gallery import SpeakerGallery, SpeakerNames, check_delta_id
+            if not isinstance(gallery, SpeakerGallery):
+                raise ValueError(f"{who}.set_gallery: expected a SpeakerGallery or None, got {type(gallery).__name__}")
+            delta = check_delta_id(delta_id, f"{who}.set_gallery")
+            if gallery.dimension != self.emb.dimension:
+                raise ValueError(f"{who}.set_gallery: the gallery's voiceprints have dimension {gallery.dimension}, the "
+                                 f"embedding model's embeddings {self.emb.dimension}")
+            if gallery.device is not None and torch.device(gallery.device) != self.device:
+                raise ValueError(f"{who}.set_gallery: the gallery is on {gallery.device}, the engine on {self.device}")
+        if any(s["busy"] for s in self._slots):
+            raise RuntimeError(f"{who}.set_gallery: a step is between launch and finish")
+        torch.cuda.synchronize(self.device)               # no kernel of an older step reads the handles dropped here
+        self._gallery, self._names, self._gallery_handles = None, None, []
+        for s in self._slots:
+            s.pop("match_h", None)
+            s.pop("match", None)
+            s.pop("names", None)
+            s["matched"] = False
+        if gallery is None:
+            return
+        handles = [gallery.new_handle(self.device) for _ in range(self.depth)]
+        self._names = SpeakerNames(self.n, self.max_speakers, delta)
+        self._gallery, self._gallery_handles = gallery, handles
+        for s in self._slots:
+            self._match_buffers(s)
+
+    def _match_buffers(self, slot: dict) -> None:
+        """A slot's pinned (index | distance | second) rows, (3, N, K) of 4-byte values."""
+        n, K = slot["emb"].shape[:2]
+        slot["match_h"] = torch.empty((3, n, K), dtype=torch.int32).pin_memory()
+        slot["matched"] = False
+
+    def _enqueue_match(self, slot: dict, ln: int, N: int, stream) -> None:
+        """One nearest-voiceprint search over the step's N * K embeddings on ``stream``, behind the embedding; the
+        kernel writes its answers to the slot's pinned rows (no copy call: csrc/ring.hip, dz_results_to_host)."""
+        K, D = slot["emb"].shape[1:]
+        m = slot["match_h"]
+        self._gallery_handles[ln].match(slot["emb"].data_ptr(), D, N * K, m[0].data_ptr(), m[1].data_ptr(),
+                                        m[2].data_ptr(), stream.cuda_stream)
+        slot["matched"] = True
 
     def finish(self, ticket: dict, want_scores: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """Wait for the step's GPU work, run the N clustering updates.
@@ -534,6 +594,11 @@ class _DiarizationEngine(_StepEngine):
                 if self.tail is None:
                     self.tail = self._make_tail(seg.shape[1])
                 ticket["tail"] = self.tail(scores, ticket["starts"], self.duration / seg.shape[1], slots=slots)
+            if self._gallery is not None and ticket.get("matched"):
+                m = ticket["match_h"].numpy()
+                ticket["match"] = (m[0, :N], m[1, :N].view(np.float32), m[2, :N].view(np.float32))
+                self._names.update(assign, ticket["match"][0], ticket["match"][1], slots)
+                ticket["names"] = self._names.labels(self._gallery.names, slots)
         return seg, emb, scores, assign
 
     def diarize(self, waves: torch.Tensor, starts=None):
@@ -544,7 +609,8 @@ class _DiarizationEngine(_StepEngine):
         ticket = self.launch(waves, starts)
         self.finish(ticket, want_scores=False)
         _, _, _, _, turns, nturns = ticket["tail"]
-        return [BatchedOutputTail.annotation(turns[i], int(nturns[i])) for i in range(self.n)]
+        names = ticket["names"] if self._gallery is not None else [None] * self.n
+        return [BatchedOutputTail.annotation(turns[i], int(nturns[i]), names=names[i]) for i in range(self.n)]
 
 
 class StreamBatch(_DiarizationEngine):
@@ -767,6 +833,7 @@ class StreamBatch(_DiarizationEngine):
         slot["rows"], slot["slots"] = N, None
         slot["keep"] = keep                              # keep the view alive until the GPU is done
         slot["pool"] = (lane, hembs, sa, sb, N, K, F)     # what _enqueue_pool needs
+        slot["ln"] = ln
         if ring is not None:                            # pushes `slack` steps from now wait for these
             ring._read_by(list(lane["a"]) + list(lane["b"]) + list(front or []))
         self._pending.append(slot)
@@ -808,6 +875,8 @@ class StreamBatch(_DiarizationEngine):
         # Results -> pinned memory by a kernel of our own.  The two hipMemcpyAsync (tensor.copy_) that stood here
         # blocked the launching thread for a whole step's latency about once per 150 steps (csrc/ring.hip).
         D = slot["emb"].shape[2]
+        if self._gallery is not None:
+            self._enqueue_match(slot, slot["ln"], N, b0)
         if self.d2h_by_kernel:
             _lib.check(lib.dz_results_to_host(self._ctx, slot["seg"].data_ptr(), slot["seg_h"].data_ptr(), N * F * K,
                                               slot["emb"].data_ptr(), slot["emb_h"].data_ptr(), N * K * D,
@@ -1064,6 +1133,8 @@ class _TwoChainEngine(_DiarizationEngine):
         self.emb.early_launch(hemb, base, stride, N, b.cuda_stream)
         b.wait_event(slot["ev_seg"])
         self.emb.late_launch(hemb, base, stride, slot["w"].data_ptr(), N, K, F, slot["emb"].data_ptr(), b.cuda_stream)
+        if self._gallery is not None:
+            self._enqueue_match(slot, ln, N, b)
         _lib.check(lib.dz_results_to_host(self._ctx, slot["seg"].data_ptr(), slot["seg_h"].data_ptr(), N * F * K,
                                           slot["emb"].data_ptr(), slot["emb_h"].data_ptr(), N * K * D,
                                           b.cuda_stream), "dz_results_to_host")

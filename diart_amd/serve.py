@@ -128,6 +128,7 @@ class StreamServer:
         self._inflight: set = set()            # slots whose window the worker is processing now
         self._deferred: List[int] = []         # slots closed while in flight: freed after the step
         self._stop = False
+        self._step_names = None                # per row of the step's batch: {g: name} (a gallery is attached), else None
         import collections
         self.step_errors = collections.deque(maxlen=64)   # (time, repr) of failed steps, newest last
         # `engine(windows (k, S) float32, starts (k,), slots [k]) -> list of k (turns (m, 3) array)`;
@@ -182,6 +183,22 @@ class StreamServer:
                 # a custom engine gets its windows at the pipeline's rate, each resampled on its own (GPU)
                 self.resampler = resampler(self.input_sample_rate, self.sample_rate, device)
                 self._engine = self._resampling_engine(self._engine)
+
+    # ------------------------------------------------------------------ speaker gallery
+    def set_gallery(self, gallery, delta_id=None) -> None:
+        """Name the speakers of every stream against ``gallery`` (``gallery.SpeakerGallery``; ``None`` removes it):
+        the engine's ``set_gallery``, between two steps.  From the next ``step()`` on the Annotations carry the names
+        where a voiceprint is within ``delta_id`` (no default), and so does everything derived from them: ``close()``
+        and the websocket messages.  A stream that joins later starts with no names (``open`` resets its slot).  The
+        diarization pipeline only: ``"vad"`` and ``"osd"`` have no speakers to name."""
+        if self.pipeline in _ONE_TRACK:
+            raise ValueError(f"StreamServer.set_gallery: pipeline={self.pipeline!r} ({_ONE_TRACK[self.pipeline][0]}) has "
+                             "no speakers to name; a gallery needs pipeline='diarization'")
+        if self.batch is None:
+            raise ValueError("StreamServer.set_gallery: a custom engine runs its own embedding; the gallery needs the "
+                             "default engine")
+        with self._step_lock:
+            self.batch.set_gallery(gallery, delta_id)
 
     # ------------------------------------------------------------------ stream life cycle
     def open(self, stream_id: Hashable) -> None:
@@ -320,6 +337,7 @@ class StreamServer:
                     return {}
                 starts = np.array([t for _, _, _, t in work], dtype=np.float64)
                 slots = [st.slot for _, st, _, _ in work]
+                self._step_names = None
                 if self.rings is None:
                     turns = self._engine(np.stack([w for _, _, w, _ in work]), starts, slots)
                 else:
@@ -333,12 +351,13 @@ class StreamServer:
                     self._free.extend(self._deferred)     # slots closed while they were in flight
                     self._deferred = []
             out = {}
+            names = self._step_names if self._step_names is not None else [None] * len(work)
             with self._lock:
-                for (sid, st, _, _), tr in zip(work, turns):
+                for (sid, st, _, _), tr, nm in zip(work, turns, names):
                     if self._streams.get(sid) is not st:      # closed (or re-opened) mid-step: drop
                         continue
                     ann = BatchedOutputTail.annotation(np.asarray(tr, dtype=np.float64).reshape(-1, 3),
-                                                       len(tr), uri=str(sid), label=self._label)
+                                                       len(tr), uri=str(sid), label=self._label, names=nm)
                     st.emitted += 1
                     if st.prediction is None:
                         st.prediction = ann
@@ -455,4 +474,6 @@ class StreamServer:
         else:
             self.batch.finish(ticket, want_scores=False)
         _, _, _, _, turns, nturns = ticket["tail"]
+        if getattr(self.batch, "_gallery", None) is not None:
+            self._step_names = ticket["names"]
         return [turns[i, :int(nturns[i])].copy() for i in range(k)]

@@ -514,7 +514,7 @@ int dz_k_ttn_depthwise(dz_ctx* ctx, const float* d_x, int ldx, const float* d_ta
  * T_g only.  Activations are channels-last [row][t][f][c]; every buffer lays a row out with the handle's
  * Tc = 1 + num_samples / 160 steps (halved, rounding up, per strided layer) and holds zeros at or past the row's own.
  * Rows that keep fewer than min_num_samples samples, or whose kept samples hold a NaN / Inf, come back as NaN; a
- * group whose longest row is that short is all NaN.  DESIGN.md 4.14.                                              */
+ * group whose longest row is that short is all NaN.  DESIGN.md 4.18.                                              */
 enum { DZ_SBR_MAX_BLOCKS = 32 };
 typedef struct {
     dz_wsp_conv conv[3];    /* conv1 (3x3, stride), conv2 (3x3), downsample (1x1, stride; w NULL: identity), BatchNorm folded */
@@ -633,6 +633,34 @@ int dz_l2_normalize(dz_ctx* ctx, float* d_emb, int rows, int dim, float norm, vo
 int dz_cdist_cosine(dz_ctx* ctx, const float* d_emb, const double* d_centers,
                     int n_streams, int k_local, int g_global, int dim,
                     double* d_out, void* stream);
+
+/* ---- speaker gallery: the nearest enrolled voiceprint of embedding rows (csrc/k_gallery.hip).
+ * The reference has no such step.  A gallery is E voiceprints of D floats, STORED NORMALISED: dz_gallery_create divides
+ * each host row by its float64 norm, rounds to float32 once and uploads.  dz_gallery_match takes R rows of D floats on
+ * the device, row_stride >= D floats apart at any 4-byte address (16-byte loads where base and stride allow, single
+ * floats otherwise; the same bits either way), and writes per row
+ *     index_out  (int32) the voiceprint of the smallest cosine distance 1 - x.g / (|x| |g|), the LOWEST index among
+ *                equal distances; dist_out (f32) that distance; second_out (f32) the smallest distance among the other
+ *                voiceprints (+inf when E == 1).
+ * A row with a NaN / Inf element, of zero norm or of a norm beyond float32 gets -1 / NaN / NaN and touches no other row.
+ * The dot products run on the exact-f32 matrix instructions, every (row, voiceprint) pair in one fixed k order, and the
+ * division is by the row's norm (summed in float64) alone: the distance bits of a pair depend on the two vectors only,
+ * not on R, E, the voiceprint's place in the gallery, the row's alignment or the rows it is batched with.  Each
+ * distance is within (D + 8) 2^-24 of the float64 value.  No atomics: (row tile, gallery tile) partial results go to
+ * the handle's scratch and a second kernel folds them.  The three outputs may be device memory or pinned host memory
+ * mapped into the device (plain stores from the kernel; complete when an event recorded on `stream` behind the call has
+ * fired).  D: a multiple of 64 from 64 to 512; E: 1 .. 65536; R: 1 .. 4096.  Refused (status 2, the message names the
+ * function, nothing is launched): NULL handle, rows or outputs; R, E or D out of range; a stride below D; a voiceprint
+ * that is not finite or of zero norm.  The handle owns the scratch of ONE match (sized for R = 4096): two streams must
+ * not run dz_gallery_match on the same handle at once; give each stream its own handle.  Enqueued on `stream`; no
+ * synchronisation, no allocation.                                                                                    */
+typedef struct dz_gallery dz_gallery;
+int dz_gallery_create(dz_ctx* ctx, const float* voiceprints, int E, int D, dz_gallery** out);
+int dz_gallery_destroy(dz_gallery* g);
+int dz_gallery_size(dz_gallery* g);   /* E (0 for NULL) */
+int dz_gallery_dim(dz_gallery* g);    /* D (0 for NULL) */
+int dz_gallery_match(dz_gallery* g, const float* d_rows, long long row_stride, int R, int* index_out, float* dist_out,
+                     float* second_out, void* stream);
 
 /* ---- repeated rows (csrc/k_rows_repeat.hip) ---------------------------------
  * The reference's SpeakerEmbedding hands the model every waveform num_speakers times (blocks/embedding.py:56-59).
