@@ -1,6 +1,8 @@
 // Tuning VoiceActivityDetection on cached model outputs: there is no clustering and the Hamming
 // aggregation does not depend on tau_active, so the aggregated speech score of every packed output row is computed
 // once per cache and a trial is one comparison per row plus the detection error rate's bookkeeping.
+// These kernels serve both track pipelines: OverlappedSpeechDetection (OsdTuneCache) feeds them the overlap track and
+// the prefix sums of the reference's overlap regions.
 //
 //   tune_vad_rows_kernel    one thread per packed output row: agg[row] in fp64 (tc_vad_row), once per cache and device
 //   tune_vad_score_kernel   one workgroup per (trial, file).  Lane i walks steps [i * per, (i + 1) * per) of the file

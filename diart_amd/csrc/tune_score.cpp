@@ -13,7 +13,8 @@
 //   dz_tune_score_core   the same components from the text tune_score_kernel compiles (k_tune_score.hip), the lanes of its
 //                        workgroup played one after the other: scoring="device" on backend="core"
 //   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
-//                        scoring of k_tune_vad.hip, from the text those kernels compile
+//                        scoring of k_tune_vad.hip, from the text those kernels compile; OverlappedSpeechDetection
+//                        too (both track pipelines: another track, other reference prefix sums)
 #include "tune_core.h"
 
 #include <algorithm>

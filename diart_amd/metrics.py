@@ -173,3 +173,46 @@ class OverlapDetectionErrorRate(DetectionErrorRate):
 
     def components(self, reference: Annotation, hypothesis: Annotation) -> Dict[str, float]:
         return super().components(overlap_reference(reference), hypothesis)
+
+
+def detection_prf(components) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(precision, recall, F)`` of detection components ``(..., 5)`` in ``COMPONENTS`` order (a dict of them is one
+    row), vectorised over the leading axes.  (R) — read from pyannote.metrics' published detection precision, recall
+    and F-measure (beta = 1), not run against the package:
+
+        retrieved = correct + false alarm,  relevant = total,
+        precision = 1 if retrieved == 0 else correct / retrieved,
+        recall    = 1 if relevant == 0 else correct / relevant,
+        F         = 0 if precision + recall == 0 else 2 precision recall / (precision + recall).
+
+    Over several files the components are summed first (pyannote accumulates the components, not the rates)."""
+    if isinstance(components, dict):
+        components = [components[c] for c in COMPONENTS]
+    comp = np.asarray(components, dtype=np.float64)
+    if comp.shape[-1] != len(COMPONENTS):
+        raise ValueError(f"detection_prf: components (..., {len(COMPONENTS)}) expected, got {comp.shape}")
+    relevant, correct = comp[..., 0], comp[..., 1]
+    retrieved = correct + comp[..., 2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        precision = np.where(retrieved == 0, 1.0, correct / retrieved)
+        recall = np.where(relevant == 0, 1.0, correct / relevant)
+        f = np.where(precision + recall == 0, 0.0, 2.0 * precision * recall / (precision + recall))
+    return precision, recall, f
+
+
+class OverlapDetectionFMeasure(_Accumulating):
+    """The detection F-measure of an ``OverlappedSpeechDetection`` hypothesis against the reference's overlap regions
+    (``detection_prf`` of ``OverlapDetectionErrorRate``'s components), what pyannote tunes this task on: overlap is
+    rare, and a hypothesis without a turn has an error rate of exactly 100 %.  Accumulates the components like
+    ``OverlapDetectionErrorRate``; ``abs()`` and ``report()`` give F of the sums — larger is better."""
+    name = "overlap detection f-measure"
+
+    def __init__(self, collar: float = 0.0, skip_overlap: bool = False):
+        self._rater = OverlapDetectionErrorRate(collar, skip_overlap)
+        super().__init__()
+
+    def components(self, reference: Annotation, hypothesis: Annotation) -> Dict[str, float]:
+        return self._rater.components(reference, hypothesis)
+
+    def _rate(self, comp: Dict[str, float]) -> float:
+        return float(detection_prf(comp)[2])

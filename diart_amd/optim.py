@@ -20,6 +20,11 @@ Either way ``dz_tune_score`` turns the masks into the error-rate components on h
 max over the local speakers), its aggregated speech score per output frame is computed once per cache, and a trial is
 one comparison per frame plus the detection error rate — on the GPU both in HIP kernels (``csrc/k_tune_vad.hip``), so
 that a batch of trials returns ``T x N x 5`` doubles and nothing else.
+
+``OverlappedSpeechDetection`` is the same pipeline behind another track (the second largest over the local speakers)
+and is scored against another reference (the regions where two different speakers are active): ``OsdTuneCache`` feeds
+the VAD tuner's kernels and host code that track and the prefix sums of those regions.  A collected ``TuneCache`` holds
+the raw scores both tracks are made of: ``VadTuneCache.from_tune_cache`` / ``OsdTuneCache.from_tune_cache``.
 """
 from __future__ import annotations
 
@@ -35,7 +40,8 @@ import torch
 from . import _lib
 from .blocks import base
 from .features import Annotation, Segment
-from .metrics import DetectionErrorRate, DiarizationErrorRate, _turns
+from .metrics import (DetectionErrorRate, DiarizationErrorRate, OverlapDetectionErrorRate, OverlapDetectionFMeasure,
+                      _turns, detection_prf, overlap_reference)
 
 TUNABLE = ("tau_active", "rho_update", "delta_new")
 VAD_TUNABLE = ("tau_active",)
@@ -532,20 +538,24 @@ class TuneCache(_ReplayCache):
         return self._hypothesis(bits_row, n, self.G, lambda g: f"speaker{g}")
 
 
-class VadTuneCache(_ReplayCache):
-    """``TuneCache``'s sibling for ``VoiceActivityDetection``: per file the track ``(C, F)`` (the max of the segmentation
-    over the local speakers, what ``finalise`` aggregates), the window starts, the frame resolution, the shift and the
-    reference turns.  The reference is collapsed to speech / non-speech: a scoring cell's one reference bit is "any
-    reference speaker active".  The aggregated speech score of every packed output frame (``agg``) does not depend on
-    ``tau_active``; it is computed once per cache (and once per device), a trial compares it with its tau."""
+class _TrackTuneCache(_ReplayCache):
+    """What ``VadTuneCache`` and ``OsdTuneCache`` share, which is everything behind the track: per file a track
+    ``(C, F)`` (what ``finalise`` aggregates), the window starts, the frame resolution, the shift and a reference; the
+    meta fields ``step``, ``latency`` and ``tau_active``.  A scoring cell has one reference bit.  The aggregated score of
+    every packed output frame (``agg``) does not depend on ``tau_active``; it is computed once per cache (and once per
+    device), a trial compares it with its tau.  A subclass names its pipeline (``KIND``, ``REPLAY``, ``PIPELINE``,
+    ``LABEL``), says which turns of a reference are stored and which build the scoring cells (``_reference``), and
+    what a file of another kind is told (``_check_kind``)."""
 
     SCORE_LANES = 256           # the lanes of tune_vad_score_kernel's workgroup (backend="core" plays them in order)
+    KIND = REPLAY = PIPELINE = LABEL = ELSEWHERE = None
 
     def __init__(self, files: Sequence[dict], config):
         get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
         self.meta = {k: float(get(k)) for k in ("step", "latency", "tau_active")}
+        name = type(self).__name__
         if not files:
-            raise ValueError("VadTuneCache needs at least one file")
+            raise ValueError(f"{name} needs at least one file")
         self.files = []
         for i, f in enumerate(files):
             track = np.ascontiguousarray(f["track"], dtype=np.float32)
@@ -556,8 +566,9 @@ class VadTuneCache(_ReplayCache):
             if track.ndim != 2 or starts.shape != (C_,) or C_ < 1 or track.shape[1] < 1:
                 raise ValueError(f"file {i}: track (C, F), starts (C) expected, got {track.shape}, {starts.shape}")
             res = np.ascontiguousarray(np.broadcast_to(np.asarray(f["res"], dtype=np.float64), (C_,)))
+            stored, turns = self._reference(f["reference"])
             self.files.append(dict(uri=str(f.get("uri", f"file{i}")), track=track, starts=starts, res=res,
-                                   shift=float(f.get("shift", 0.0)), turns=_reference_turns(f["reference"])))
+                                   shift=float(f.get("shift", 0.0)), stored=stored, turns=turns))
         frames = {f["track"].shape[1] for f in self.files}
         if len(frames) != 1:
             raise ValueError(f"the files of one cache share the frames per chunk, got {sorted(frames)}")
@@ -566,20 +577,43 @@ class VadTuneCache(_ReplayCache):
         self._dev = {}
         self._agg = None
 
+    @staticmethod
+    def _reference(reference):
+        """``(stored, turns)``: the turns ``save`` writes (``load`` hands them back as the reference) and the turns whose
+        boundaries and activity make the scoring cells."""
+        raise NotImplementedError
+
+    @classmethod
+    def _check_kind(cls, path, kind: Optional[str]) -> None:
+        """Raise the ValueError of a file whose kind tag (None: no tag, a ``TuneCache``) is not this class's."""
+        raise NotImplementedError
+
     # ------------------------------------------------------------------------------------------ construction
     @classmethod
-    def from_arrays(cls, files: Sequence[dict], config) -> "VadTuneCache":
+    def from_arrays(cls, files: Sequence[dict], config):
         """``files``: dicts with ``track (C, F)`` (or ``(C, F, 1)``), ``starts (C)``, ``res``, ``shift``, ``reference``
         and optionally ``uri``, as ``TuneCache.from_arrays`` takes them.  ``config``: anything with ``step``,
         ``latency`` and ``tau_active`` (attributes or keys)."""
         return cls(files, config)
 
     @classmethod
-    def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32) -> "VadTuneCache":
-        """Run the model half of ``VoiceActivityDetection`` (``model_outputs``) once per WAV of ``speech_path``."""
-        if _pipeline_kind(pipeline_class) != "vad":
-            raise ValueError(f"pipeline class {pipeline_class.__name__}: VadTuneCache collects VoiceActivityDetection; "
-                             "TuneCache collects SpeakerDiarization")
+    def _from_scores(cls, cache: "TuneCache", tau_active: Optional[float], track):
+        """A collected ``TuneCache`` as this class's cache: ``track(scores)`` turns a file's raw segmentation scores
+        ``(C, F, K)`` (a float32 tensor) into the track ``(C, F)`` or ``(C, F, 1)``; the starts, the resolutions, the
+        shift and the reference turns are the diarization cache's own."""
+        if not isinstance(cache, TuneCache):
+            raise ValueError(f"{cls.__name__}.from_tune_cache takes a TuneCache, got a {type(cache).__name__}")
+        files = [dict(uri=f["uri"], track=track(torch.from_numpy(f["seg"])).cpu().numpy(), starts=f["starts"], res=f["res"],
+                      shift=f["shift"], reference=f["turns"]) for f in cache.files]
+        tau = cache.meta["tau_active"] if tau_active is None else float(tau_active)
+        return cls(files, dict(step=cache.meta["step"], latency=cache.meta["latency"], tau_active=tau))
+
+    @classmethod
+    def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32):
+        """Run the model half of the class's pipeline (``model_outputs``) once per WAV of ``speech_path``."""
+        if _replay_kind(pipeline_class) != cls.REPLAY:
+            raise ValueError(f"pipeline class {pipeline_class.__name__}: {cls.KIND} collects {cls.PIPELINE}; "
+                             f"{cls.ELSEWHERE}")
         pipeline = pipeline_class(base_config)
         files = cls._collect_files(pipeline, speech_path, reference_path, batch_size,
                                    lambda batch: (pipeline.model_outputs(batch).detach().cpu().numpy()
@@ -589,22 +623,23 @@ class VadTuneCache(_ReplayCache):
         return cls(files, pipeline.config)
 
     def save(self, path) -> None:
-        out = {"kind": np.array("VadTuneCache"), "meta": np.array(json.dumps(self.meta)),
+        out = {"kind": np.array(self.KIND), "meta": np.array(json.dumps(self.meta)),
                "uris": np.array([f["uri"] for f in self.files])}
         for i, f in enumerate(self.files):
             for k in ("track", "starts", "res"):
                 out[f"{k}_{i}"] = f[k]
             out[f"shift_{i}"] = np.array(f["shift"])
-            out[f"ref_times_{i}"] = np.array([[s, e] for s, e, _ in f["turns"]], dtype=np.float64).reshape(-1, 2)
-            out[f"ref_labels_{i}"] = np.array([str(l) for _, _, l in f["turns"]], dtype=str)
+            out[f"ref_times_{i}"] = np.array([[s, e] for s, e, _ in f["stored"]], dtype=np.float64).reshape(-1, 2)
+            out[f"ref_labels_{i}"] = np.array([str(l) for _, _, l in f["stored"]], dtype=str)
         with open(path, "wb") as fh:
             np.savez(fh, **out)
 
     @classmethod
-    def load(cls, path) -> "VadTuneCache":
+    def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            if "kind" not in z.files or str(z["kind"]) != "VadTuneCache":
-                raise ValueError(f"{path} holds a TuneCache (SpeakerDiarization), not a VadTuneCache")
+            kind = str(z["kind"]) if "kind" in z.files else None
+            if kind != cls.KIND:
+                cls._check_kind(path, kind)
             meta = json.loads(str(z["meta"]))
             files = []
             for i, uri in enumerate(z["uris"]):
@@ -615,7 +650,7 @@ class VadTuneCache(_ReplayCache):
 
     # ------------------------------------------------------------------------------------------ trial-independent parts
     def _reference_bits(self, f: dict) -> Dict[object, int]:
-        self.ref_labels.append(["speech"] if f["turns"] else [])
+        self.ref_labels.append([self.LABEL] if f["turns"] else [])
         return {l: 0 for _, _, l in f["turns"]}
 
     def _prepare(self) -> None:
@@ -742,13 +777,79 @@ class VadTuneCache(_ReplayCache):
         return TuneResult(_rates(comp), comp, per_file, np.full((taus.shape[0], self.N), -1, dtype=np.int32))
 
     def hypothesis(self, bits_row: np.ndarray, n: int) -> Annotation:
-        """File n's hypothesis under one trial as ``PredictionAccumulator`` ends with it: turns labelled "speech"."""
-        return self._hypothesis(bits_row, n, 1, lambda g: "speech")
+        """File n's hypothesis under one trial as ``PredictionAccumulator`` ends with it: turns labelled "speech"
+        (``VadTuneCache``) or "overlap" (``OsdTuneCache``)."""
+        return self._hypothesis(bits_row, n, 1, lambda g: self.LABEL)
+
+
+class VadTuneCache(_TrackTuneCache):
+    """``TuneCache``'s sibling for ``VoiceActivityDetection``: the track is the max of the segmentation over the local
+    speakers.  The reference is collapsed to speech / non-speech: a scoring cell's one reference bit is "any reference
+    speaker active"."""
+
+    KIND, REPLAY, PIPELINE, LABEL = "VadTuneCache", "vad", "VoiceActivityDetection", "speech"
+    ELSEWHERE = "TuneCache collects SpeakerDiarization"
+
+    @staticmethod
+    def _reference(reference):
+        turns = _reference_turns(reference)
+        return turns, turns
+
+    @classmethod
+    def _check_kind(cls, path, kind: Optional[str]) -> None:
+        raise ValueError(f"{path} holds a TuneCache (SpeakerDiarization), not a VadTuneCache")
+
+    @classmethod
+    def from_tune_cache(cls, cache: "TuneCache", tau_active: Optional[float] = None) -> "VadTuneCache":
+        """The ``VadTuneCache`` of a collected ``TuneCache``, whose raw scores are the same model's: the track is their
+        float32 max over the speakers (NaN propagates), what ``VoiceActivityDetection.model_outputs`` returns.
+        ``tau_active``: the base value; None takes the diarization cache's."""
+        return cls._from_scores(cache, tau_active, lambda scores: torch.max(scores, dim=-1)[0])
+
+
+class OsdTuneCache(_TrackTuneCache):
+    """``VadTuneCache``'s sibling for ``OverlappedSpeechDetection``: the track is the second largest of the segmentation
+    over the local speakers (``functional.overlap_track``).  The reference is an ordinary speaker annotation; a scoring
+    cell's one reference bit is "at least two DIFFERENT reference speakers active" — the cells are built from
+    ``metrics.overlap_reference`` of it (touching regions merged), what ``OverlapDetectionErrorRate`` scores against.
+    ``save`` keeps the speaker turns as given, so that ``load`` builds the same cells.  The replay, both kernels and the
+    host backends are the VAD tuner's: they see another track and other reference prefix sums."""
+
+    KIND, REPLAY, PIPELINE, LABEL = "OsdTuneCache", "osd", "OverlappedSpeechDetection", "overlap"
+    ELSEWHERE = "VadTuneCache collects VoiceActivityDetection, TuneCache collects SpeakerDiarization"
+
+    @staticmethod
+    def _reference(reference):
+        if isinstance(reference, Annotation):
+            reference = [(seg.start, seg.end, label) for seg, _, label in reference.itertracks(yield_label=True)]
+        stored = [(float(s), float(e), str(label)) for s, e, label in reference]
+        ann = Annotation()
+        for n, (s, e, label) in enumerate(stored):
+            ann[Segment(s, e), n] = label
+        return stored, _turns(overlap_reference(ann))
+
+    @classmethod
+    def _check_kind(cls, path, kind: Optional[str]) -> None:
+        holds = "TuneCache (SpeakerDiarization)" if kind is None else f"{kind}"
+        raise ValueError(f"{path} holds a {holds}, not an OsdTuneCache (OverlappedSpeechDetection)")
+
+    @classmethod
+    def from_tune_cache(cls, cache: "TuneCache", tau_active: float = 0.5, device=None) -> "OsdTuneCache":
+        """The ``OsdTuneCache`` of a collected ``TuneCache``: the track is ``functional.overlap_track`` of its raw scores
+        — the defining torch statement on the host, ``overlap_track_kernel`` with ``device`` a GPU (the same values:
+        a selection, no arithmetic).  ``tau_active``: the base value, this pipeline's default."""
+        if isinstance(cache, TuneCache) and cache.K < 2:
+            raise ValueError(f"OsdTuneCache.from_tune_cache: a cache of {cache.K} local speaker per chunk has no overlap "
+                             "track (at least 2 speakers)")
+        from .functional import overlap_track
+        return cls._from_scores(cache, tau_active,
+                                lambda scores: overlap_track(scores if device is None else scores.to(device)))
 
 
 def _pipeline_kind(pipeline_class) -> str:
-    """"dia" for ``SpeakerDiarization``, "vad" for ``VoiceActivityDetection``; nothing else is tuned by replay (a
-    subclass may change what the cached outputs mean)."""
+    """Which of the two original caches: "dia" for ``SpeakerDiarization`` (``TuneCache``), "vad" for
+    ``VoiceActivityDetection`` (``VadTuneCache``), a ValueError for anything else.  ``_replay_kind`` is the question
+    "is this class tuned by replay, and how"."""
     from .blocks.diarization import SpeakerDiarization
     from .blocks.vad import VoiceActivityDetection
     if pipeline_class is SpeakerDiarization:
@@ -756,14 +857,31 @@ def _pipeline_kind(pipeline_class) -> str:
     if pipeline_class is VoiceActivityDetection:
         return "vad"
     name = getattr(pipeline_class, "__name__", repr(pipeline_class))
-    raise ValueError(f"pipeline class {name}: only SpeakerDiarization and VoiceActivityDetection are tuned by replaying "
-                     "cached model outputs")
+    raise ValueError(f"pipeline class {name}: neither SpeakerDiarization (TuneCache) nor VoiceActivityDetection "
+                     "(VadTuneCache)")
+
+
+def _replay_kind(pipeline_class) -> str:
+    """"dia" for ``SpeakerDiarization``, "vad" for ``VoiceActivityDetection``, "osd" for
+    ``OverlappedSpeechDetection``; nothing else is tuned by replay (a subclass may change what the cached outputs
+    mean)."""
+    from .blocks.osd import OverlappedSpeechDetection
+    if pipeline_class is OverlappedSpeechDetection:
+        return "osd"
+    try:
+        return _pipeline_kind(pipeline_class)
+    except ValueError:
+        name = getattr(pipeline_class, "__name__", repr(pipeline_class))
+        raise ValueError(f"pipeline class {name}: only SpeakerDiarization, VoiceActivityDetection and "
+                         "OverlappedSpeechDetection are tuned by replaying cached model outputs") from None
 
 
 def _check_pipeline_class(pipeline_class) -> None:
-    if _pipeline_kind(pipeline_class) != "dia":
+    kind = _replay_kind(pipeline_class)
+    if kind != "dia":
+        other = "VadTuneCache" if kind == "vad" else "OsdTuneCache"
         raise ValueError(f"pipeline class {pipeline_class.__name__}: TuneCache replays SpeakerDiarization; "
-                         "VadTuneCache is the cache of VoiceActivityDetection")
+                         f"{other} is the cache of {pipeline_class.__name__}")
 
 
 def trial_config(base_config, values: Dict[str, float]):
@@ -783,34 +901,42 @@ class Optimizer:
     evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run);
     ``scoring``: ``TuneCache.evaluate``'s (None and "host": on host threads, "device": on the replay's backend).
     ``pipeline_class``: ``SpeakerDiarization``, or ``VoiceActivityDetection`` — then ``tau_active`` alone is tuned, the
-    metric is the detection error rate and the cache a ``VadTuneCache``."""
+    metric is the detection error rate and the cache a ``VadTuneCache`` — or ``OverlappedSpeechDetection``:
+    ``tau_active`` alone, an ``OsdTuneCache``, and as the metric ``OverlapDetectionErrorRate`` (the default) or, with
+    ``direction="maximize"``, ``OverlapDetectionFMeasure``: the objective is then ``100 * F`` of the components summed
+    over the files (``metrics.detection_prf``)."""
 
     def __init__(self, pipeline_class: type, speech_path, reference_path, study_or_path, batch_size: int = 32,
                  hparams: Optional[Sequence[base.HyperParameter]] = None, base_config=None,
                  do_kickstart_hparams: bool = True, metric=None, direction: str = "minimize", sampler: str = "random",
                  seed: int = 0, trials_per_batch: int = 256, cache=None, backend: Optional[str] = None,
                  scoring: Optional[str] = None):
-        self.kind = _pipeline_kind(pipeline_class)
-        vad = self.kind == "vad"
+        self.kind = _replay_kind(pipeline_class)
+        track = self.kind != "dia"                 # a track pipeline: tau_active alone, scored where it is replayed
         if scoring not in (None, "host", "device"):
             raise ValueError(f"scoring '{scoring}': host or device")
-        if vad and scoring is not None:
-            raise ValueError("scoring: VoiceActivityDetection is scored where it is replayed (backend); only "
+        if track and scoring is not None:
+            raise ValueError(f"scoring: {pipeline_class.__name__} is scored where it is replayed (backend); only "
                              "SpeakerDiarization takes scoring='host' or 'device'")
         self.scoring = scoring
-        self.cache_class = VadTuneCache if vad else TuneCache
-        self.tunable = VAD_TUNABLE if vad else TUNABLE
+        self.cache_class = {"dia": TuneCache, "vad": VadTuneCache, "osd": OsdTuneCache}[self.kind]
+        self.tunable = VAD_TUNABLE if track else TUNABLE
         if cache is not None and not isinstance(cache, self.cache_class):
             raise ValueError(f"pipeline class {pipeline_class.__name__}: cache must be a {self.cache_class.__name__}, "
                              f"got a {type(cache).__name__}")
         self.pipeline_class = pipeline_class
         self.speech_path, self.reference_path, self.batch_size = speech_path, reference_path, batch_size
-        wanted = DetectionErrorRate if vad else DiarizationErrorRate
-        if metric is not None and not isinstance(metric, wanted):
+        wanted = {"dia": DiarizationErrorRate, "vad": DetectionErrorRate, "osd": OverlapDetectionErrorRate}[self.kind]
+        self.fmeasure = self.kind == "osd" and isinstance(metric, OverlapDetectionFMeasure)
+        if metric is not None and not isinstance(metric, wanted) and not self.fmeasure:
             raise ValueError(f"metric {type(metric).__name__}: the replay of {pipeline_class.__name__} scores the "
-                             f"{wanted.name} ({wanted.__name__}) only")
+                             f"{wanted.name} ({wanted.__name__}) only"
+                             + (", or OverlapDetectionFMeasure with direction='maximize'" if self.kind == "osd" else ""))
         if direction not in ("minimize", "maximize"):
             raise ValueError(f"direction '{direction}': minimize or maximize")
+        if self.fmeasure and direction != "maximize":
+            raise ValueError(f"metric OverlapDetectionFMeasure with direction '{direction}': an F-measure is maximised "
+                             "(direction='maximize')")
         if sampler not in ("random", "grid"):
             raise ValueError(f"sampler '{sampler}': random or grid")
         self.metric, self.direction, self.sampler, self.seed = metric, direction, sampler, int(seed)
@@ -827,7 +953,7 @@ class Optimizer:
                                  f"{', '.join(self.tunable)} are tuned by replaying them")
             assert param.name in possible, (f"Hyper-parameter {param.name} not found in configuration "
                                             f"{self.base_config.__class__.__name__}")
-        if not vad and int(self.base_config.max_speakers) > MAX_SPEAKERS:
+        if not track and int(self.base_config.max_speakers) > MAX_SPEAKERS:
             raise ValueError(f"max_speakers = {self.base_config.max_speakers}: the replay keeps one 32-bit mask per "
                              f"frame, at most {MAX_SPEAKERS} speakers")
         if not isinstance(study_or_path, (str, Path)):
@@ -873,15 +999,17 @@ class Optimizer:
         return dict(self.best_trial["params"])
 
     def _values(self, params: Dict[str, float]) -> List[float]:
-        """(tau, rho, delta) of a trial ((tau) of VoiceActivityDetection): the sampled parameters, the base config's
+        """(tau, rho, delta) of a trial ((tau) of a track pipeline): the sampled parameters, the base config's
         value for the others."""
         return [float(params.get(name, getattr(self.base_config, name))) for name in self.tunable]
 
     def objective(self, params: Sequence[Dict[str, float]]) -> np.ndarray:
-        """The metric in percent of every trial of ``params`` (NaN where the clustering would raise)."""
+        """The metric in percent of every trial of ``params`` (NaN where the clustering would raise); with an
+        ``OverlapDetectionFMeasure``, 100 x F of the components summed over the files."""
         hp = np.array([self._values(p) for p in params], dtype=np.float64)
         kw = {} if self.scoring is None else dict(scoring=self.scoring)
-        return 100.0 * self.cache.evaluate(hp, backend=self.backend, **kw).rate
+        result = self.cache.evaluate(hp, backend=self.backend, **kw)
+        return 100.0 * (detection_prf(result.components)[2] if self.fmeasure else result.rate)
 
     def _grid(self, total: int) -> List[Dict[str, float]]:
         """The largest cube of at most ``total`` points: the same number of equally spaced interior values per axis."""

@@ -4,7 +4,9 @@ over the dataset (``optim.TuneCache.collect``; ``--cache FILE`` saves that pass,
 then every trial is a replay of their outputs — on the GPU when there is one.  The study is a directory: ``--output
 DIR`` holds ``DIR/<stem>.json`` with every trial, and a second run continues it.  ``--pipeline
 VoiceActivityDetection`` tunes tau_active of that pipeline against the detection error rate (``optim.VadTuneCache``;
-the embedding and the clustering arguments are ignored)."""
+the embedding and the clustering arguments are ignored).  ``--pipeline OverlappedSpeechDetection`` tunes tau_active of
+that pipeline (``optim.OsdTuneCache``, the same arguments ignored) against the overlap detection error rate, or with
+``--objective fmeasure`` for the largest detection F-measure, the objective pyannote tunes this task on."""
 from __future__ import annotations
 
 import argparse
@@ -13,8 +15,10 @@ from pathlib import Path
 from . import models as m
 from .blocks.base import HyperParameter
 from .blocks.diarization import SpeakerDiarization, SpeakerDiarizationConfig
-from .blocks.vad import VoiceActivityDetection, VoiceActivityDetectionConfig
-from .optim import Optimizer, TuneCache, VadTuneCache
+from .blocks.osd import OverlappedSpeechDetection
+from .blocks.vad import VoiceActivityDetection
+from .metrics import OverlapDetectionFMeasure
+from .optim import Optimizer, OsdTuneCache, TuneCache, VadTuneCache
 
 
 def parser() -> argparse.ArgumentParser:
@@ -22,7 +26,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("root", type=str, help="Directory with audio files CONVERSATION.wav")
     ap.add_argument("--reference", required=True, type=str,
                     help="Directory with RTTM files CONVERSATION.rttm. Names must match audio files")
-    ap.add_argument("--pipeline", default="SpeakerDiarization", choices=("SpeakerDiarization", "VoiceActivityDetection"),
+    ap.add_argument("--pipeline", default="SpeakerDiarization",
+                    choices=("SpeakerDiarization", "VoiceActivityDetection", "OverlappedSpeechDetection"),
                     help="Pipeline to tune. Defaults to SpeakerDiarization")
     ap.add_argument("--segmentation", default="pyannote/segmentation", type=str, help="Segmentation checkpoint file")
     ap.add_argument("--embedding", default="pyannote/embedding", type=str, help="Embedding checkpoint file")
@@ -44,7 +49,10 @@ def parser() -> argparse.ArgumentParser:
                          "device (on the GPU, beside the replay; not with --cpu)")
     ap.add_argument("--hparams", nargs="+", default=None,
                     help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three); "
-                         "tau_active alone with --pipeline VoiceActivityDetection")
+                         "tau_active alone with --pipeline VoiceActivityDetection or OverlappedSpeechDetection")
+    ap.add_argument("--objective", default="der", choices=("der", "fmeasure"),
+                    help="der: minimise the pipeline's error rate (the default); fmeasure: maximise the detection "
+                         "F-measure (--pipeline OverlappedSpeechDetection only)")
     ap.add_argument("--num-iter", default=100, type=int, help="Number of optimization trials")
     ap.add_argument("--output", type=str, required=True, help="Study directory: holds <stem>.json with every trial")
     ap.add_argument("--sampler", default="random", choices=("random", "grid"),
@@ -57,17 +65,22 @@ def parser() -> argparse.ArgumentParser:
 
 def run(args: argparse.Namespace, models=None) -> Optimizer:
     """``models``: (segmentation, embedding) to use in place of the checkpoints the arguments name (the embedding is
-    not used, and may be None, with ``--pipeline VoiceActivityDetection``)."""
-    vad = args.pipeline == "VoiceActivityDetection"
+    not used, and may be None, with ``--pipeline VoiceActivityDetection`` or ``OverlappedSpeechDetection``)."""
+    vad = args.pipeline != "SpeakerDiarization"          # a track pipeline: no embedding, no clustering
+    osd = args.pipeline == "OverlappedSpeechDetection"
+    if args.objective == "fmeasure" and not osd:
+        raise SystemExit(f"--objective fmeasure is the detection F-measure of OverlappedSpeechDetection; --pipeline "
+                         f"{args.pipeline} is tuned on its error rate (--objective der)")
     if models is not None:
         seg, emb = models
     else:
         seg = m.SegmentationModel.from_pretrained(args.segmentation)
         emb = None if vad else m.EmbeddingModel.from_pretrained(args.embedding)
     if vad:
-        pipeline_class, cache_class = VoiceActivityDetection, VadTuneCache
-        base_config = VoiceActivityDetectionConfig(segmentation=seg, duration=args.duration, step=args.step,
-                                                   latency=args.latency, tau_active=args.tau_active, device=None)
+        pipeline_class, cache_class = ((OverlappedSpeechDetection, OsdTuneCache) if osd else
+                                       (VoiceActivityDetection, VadTuneCache))
+        base_config = pipeline_class.get_config_class()(segmentation=seg, duration=args.duration, step=args.step,
+                                                        latency=args.latency, tau_active=args.tau_active, device=None)
     else:
         pipeline_class, cache_class = SpeakerDiarization, TuneCache
         base_config = SpeakerDiarizationConfig(
@@ -84,10 +97,11 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
     cache = None
     if args.cache and Path(args.cache).exists():
         cache = cache_class.load(args.cache)
+    objective = dict(metric=OverlapDetectionFMeasure(), direction="maximize") if args.objective == "fmeasure" else {}
     opt = Optimizer(pipeline_class, args.root, args.reference, Path(args.output).expanduser(),
                     batch_size=args.batch_size, hparams=hparams, base_config=base_config, sampler=args.sampler,
                     seed=args.seed, trials_per_batch=args.trials_per_batch, cache=cache,
-                    backend="host" if args.cpu else None, scoring=args.scoring)
+                    backend="host" if args.cpu else None, scoring=args.scoring, **objective)
     if args.cache and cache is None:
         opt.cache.save(args.cache)
     opt(num_iter=args.num_iter, show_progress=True)

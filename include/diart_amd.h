@@ -1090,7 +1090,10 @@ int dz_tune_score_core(int trials, int n_files, const unsigned* bits, int total_
  * seg (chunks, frames) = the max over the local speakers, and emb / pre_* unused (may be NULL).  The
  * aggregated speech score of a packed output row does not depend on tau: dz_tune_vad_rows writes
  * d_agg (total_rows) doubles once per cache (the value dz_tune_replay compares with tau when the one
- * local speaker of every buffer is mapped).  Device memory throughout, enqueued on `stream`.            */
+ * local speaker of every buffer is mapped).  Device memory throughout, enqueued on `stream`.
+ * The three dz_tune_vad_* calls serve both track pipelines: for OverlappedSpeechDetection seg is the
+ * second largest over the local speakers and ref_prefix sums the cells where two different reference
+ * speakers are active; nothing in the arithmetic knows which of the two it is given.                   */
 int dz_tune_vad_rows(dz_ctx* ctx, const dz_tune_desc* d, double* d_agg, void* stream);
 /* T trials (d_taus (T)) x N files from d_agg: row r is speech when agg > tau; the turns, their merging and the
  * scoring cells are dz_tune_score's for one hypothesis label against a reference collapsed to one label

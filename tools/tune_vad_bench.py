@@ -7,7 +7,11 @@ kernel (device events), then for every T of `--trials` the wall time of `evaluat
 backend with `--threads` threads (warm runs first, medians of `--reps`), the score kernel alone (device events), and
 the wall time of a `Benchmark` call on the blocks path — what a trial costs without the cache — measured
 `--benchmark-calls` times and stated per trial (T such calls are T times that: extrapolated, not run).  One JSON line,
-`--out FILE`."""
+`--out FILE`.
+
+`--pipeline osd` measures the OverlappedSpeechDetection tuner (`OsdTuneCache`: the same kernels behind the overlap track)
+and the VAD tuner beside it, in one process on the same files: the references are then three made-up speakers whose
+turns overlap, `collect` is timed once per cache and every `evaluate` figure is taken for both caches in turn."""
 import argparse
 import ctypes as C
 import json
@@ -30,12 +34,83 @@ from diart_amd import _lib  # noqa: E402
 from diart_amd import models as M  # noqa: E402
 from diart_amd.blocks.vad import VoiceActivityDetection, VoiceActivityDetectionConfig  # noqa: E402
 from diart_amd.inference import Benchmark, write_wav  # noqa: E402
-from diart_amd.optim import VadTuneCache  # noqa: E402
+from diart_amd.optim import VadTuneCache  # noqa: E402  (OsdTuneCache: imported where --pipeline osd needs it)
 from diart_amd.synth import synth_segmentation_state, synth_stream  # noqa: E402
+
+
+def speaker_reference(uri: str, seconds: float) -> str:
+    """Three speakers taking turns of different periods over the file (two and three of them at once): an RTTM text."""
+    from diart_amd.features import Annotation, Segment
+    ann, n = Annotation(uri=uri), 0
+    for s in range(3):
+        t = 0.37 * s
+        while t < seconds:
+            ann[Segment(t, min(seconds, t + 2.9 + 0.61 * s)), n] = f"ref{s}"
+            t, n = t + 4.3 + 0.83 * s, n + 1
+    return ann.to_rttm()
+
+
+def evaluate_rows(cache, trials, reps: int, threads: int, device, rng) -> list:
+    rows = []
+    for T in trials:
+        taus = np.concatenate([[0.6], rng.uniform(0, 1, size=T - 1)])
+        row = dict(trials=T)
+        gpu = cache.evaluate(taus, backend="gpu")
+        row["gpu_evaluate"] = median_ms(lambda: cache.evaluate(taus, backend="gpu"), reps)
+        row["kernel_score"] = events_ms(lambda: cache._gpu(taus, False, True, device), device, reps)
+        host = cache.evaluate(taus, backend="host", num_threads=threads)
+        row["host_evaluate"] = median_ms(lambda: cache.evaluate(taus, backend="host", num_threads=threads), reps,
+                                         warm=0)      # (the call above was the warm run)
+        total = np.maximum(host.per_file[..., :1], 1e-300)
+        row["largest_component_error_over_total"] = float((np.abs(gpu.per_file - host.per_file) / total).max())
+        row["best_rate_percent"] = float(100.0 * host.rate.min())
+        row["gpu_over_host"] = row["host_evaluate"]["median_ms"] / row["gpu_evaluate"]["median_ms"]
+        rows.append(row)
+    return rows
+
+
+def both_pipelines(args, device) -> dict:
+    """--pipeline osd: the two detection caches collected from the same files, measured side by side."""
+    from diart_amd.blocks.osd import OverlappedSpeechDetection, OverlappedSpeechDetectionConfig
+    from diart_amd.optim import OsdTuneCache
+    out, caches = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        speech, refs = Path(tmp) / "wav", Path(tmp) / "rttm"
+        speech.mkdir()
+        refs.mkdir()
+        for i in range(args.files):
+            write_wav(speech / f"f{i:02d}.wav", synth_stream(5000 + i, args.seconds, num_speakers=3 + i % 3), 16000)
+            (refs / f"f{i:02d}.rttm").write_text(speaker_reference(f"f{i:02d}", args.seconds))
+        seg = M.SegmentationModel.from_state(synth_segmentation_state(), max_batch=args.batch_size)
+        kinds = (("vad", VadTuneCache, VoiceActivityDetection, VoiceActivityDetectionConfig),
+                 ("osd", OsdTuneCache, OverlappedSpeechDetection, OverlappedSpeechDetectionConfig))
+        for warm in (True, False):                # the first pass warms the model and the file cache up
+            for name, cache_class, pipeline, config_class in kinds:
+                config = config_class(segmentation=seg, latency=args.latency, device=device)
+                torch.cuda.synchronize(device)
+                t = time.perf_counter()
+                caches[name] = cache_class.collect(pipeline, config, speech, refs, batch_size=args.batch_size)
+                torch.cuda.synchronize(device)
+                out.setdefault(name, {})["collect_warm_s" if warm else "collect_s"] = time.perf_counter() - t
+    for name, cache in caches.items():
+        out[name]["cache"] = dict(chunks=int(cache.chunk_off[-1]), frames=cache.F, output_rows=cache.total_rows,
+                                  cells=int(cache.file_cell_off[-1]), sorted_steps=cache.sorted_steps)
+        t = time.perf_counter()
+        cache._device(device)
+        torch.cuda.synchronize(device)
+        out[name]["upload_and_rows_ms"] = 1e3 * (time.perf_counter() - t)
+    for name, cache in caches.items():
+        out[name]["rows"] = evaluate_rows(cache, args.trials, args.reps, args.threads, device, np.random.default_rng(0))
+        for row in out[name]["rows"]:
+            print(name, json.dumps(row), flush=True)
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--pipeline", default="vad", choices=("vad", "osd"),
+                    help="vad: the VoiceActivityDetection tuner (the default); osd: the OverlappedSpeechDetection tuner "
+                         "with the VAD tuner beside it")
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=600.0)
     ap.add_argument("--trials", type=int, nargs="+", default=[1, 64, 1024])
@@ -44,11 +119,22 @@ def main():
     ap.add_argument("--benchmark-calls", type=int, default=1)
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--latency", type=float, default=5.0)
-    ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "r20a_tune_vad.json"))
+    ap.add_argument("--out", type=str, default=None,
+                    help="profiles/r20a_tune_vad.json, profiles/r29a_tune_osd.json with --pipeline osd")
     args = ap.parse_args()
+    args.out = args.out or str(ROOT / "profiles" / ("r29a_tune_osd.json" if args.pipeline == "osd" else "r20a_tune_vad.json"))
     if not torch.cuda.is_available():
         raise SystemExit("tune_vad_bench.py measures on a GPU; there is none")
     device = torch.device("cuda", 0)
+    if args.pipeline == "osd":
+        out = dict(tool="tools/tune_vad_bench.py --pipeline osd", files=args.files, seconds=args.seconds, latency=args.latency,
+                   batch_size=args.batch_size, host_threads=args.threads, reps=args.reps, gpu=torch.cuda.get_device_name(0))
+        out.update(both_pipelines(args, device))
+        line = json.dumps(out)
+        print(line, flush=True)
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(line + "\n")
+        return
     out = dict(tool="tools/tune_vad_bench.py", files=args.files, seconds=args.seconds, latency=args.latency,
                batch_size=args.batch_size, host_threads=args.threads, gpu=torch.cuda.get_device_name(0))
     with tempfile.TemporaryDirectory() as tmp:
@@ -89,23 +175,9 @@ def main():
     out["kernel_rows"] = events_ms(lambda: _lib.check(lib.dz_tune_vad_rows(
         ctx, C.byref(desc), tensors["agg"].data_ptr(), torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_rows"),
         device, args.reps)
-    rng = np.random.default_rng(0)
-    rows = []
-    for T in args.trials:
-        taus = np.concatenate([[0.6], rng.uniform(0, 1, size=T - 1)])
-        row = dict(trials=T)
-        gpu = cache.evaluate(taus, backend="gpu")
-        row["gpu_evaluate"] = median_ms(lambda: cache.evaluate(taus, backend="gpu"), args.reps)
-        row["kernel_score"] = events_ms(lambda: cache._gpu(taus, False, True, device), device, args.reps)
-        host = cache.evaluate(taus, backend="host", num_threads=args.threads)
-        row["host_evaluate"] = median_ms(lambda: cache.evaluate(taus, backend="host", num_threads=args.threads), args.reps,
-                                         warm=0)      # (the call above was the warm run)
-        total = np.maximum(host.per_file[..., :1], 1e-300)
-        row["largest_component_error_over_total"] = float((np.abs(gpu.per_file - host.per_file) / total).max())
-        row["best_rate_percent"] = float(100.0 * host.rate.min())
-        row["gpu_over_host"] = row["host_evaluate"]["median_ms"] / row["gpu_evaluate"]["median_ms"]
-        row["benchmark_calls_s_extrapolated"] = T * out["benchmark_call_s"]["median"]      # T x one call: not measured
-        rows.append(row)
+    rows = evaluate_rows(cache, args.trials, args.reps, args.threads, device, np.random.default_rng(0))
+    for row in rows:
+        row["benchmark_calls_s_extrapolated"] = row["trials"] * out["benchmark_call_s"]["median"]   # T x one call: not measured
         print(json.dumps(row), flush=True)
     out["rows"] = rows
     line = json.dumps(out)
