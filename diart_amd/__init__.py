@@ -11,7 +11,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # `from diart_amd import Optimizer, TuneCache` without importing the tuner (and torch) with the package
-    if name in ("Optimizer", "TuneCache", "VadTuneCache", "OsdTuneCache"):
+    if name in ("Optimizer", "TuneCache", "VadTuneCache", "OsdTuneCache", "IdentTuneCache"):
         from . import optim
         return getattr(optim, name)
     raise AttributeError(f"module 'diart_amd' has no attribute '{name}'")

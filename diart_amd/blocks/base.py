@@ -18,7 +18,7 @@ class HyperParameter:
 
     @staticmethod
     def from_name(name: str) -> "HyperParameter":
-        for hp in (TauActive, RhoUpdate, DeltaNew):
+        for hp in (TauActive, RhoUpdate, DeltaNew, DeltaId):
             if hp.name == name:
                 return hp
         raise ValueError(f"Hyper-parameter '{name}' not recognized")
@@ -27,6 +27,8 @@ class HyperParameter:
 TauActive = HyperParameter("tau_active", low=0, high=1)
 RhoUpdate = HyperParameter("rho_update", low=0, high=1)
 DeltaNew = HyperParameter("delta_new", low=0, high=2)
+# the identification distance of a speaker gallery (optim.IdentTuneCache): the cosine distance's range, as delta_new
+DeltaId = HyperParameter("delta_id", low=0, high=2)
 
 
 class PipelineConfig(ABC):

@@ -1,0 +1,144 @@
+// Tuning delta_id by replay (dz_tune_name, dz_tune_ident_score_gpu): the names a gallery gives the
+// global speakers of every trial, and the identification error rate of every (trial, file) pair, from the assignments and
+// masks that dz_tune_replay left on the device.
+//
+//   tune_name_kernel          one wavefront per (trial, file) chain, sequential over the file's chunks.  Lane g < G holds
+//                             speaker g's closest match so far (best_d, best_e) in registers; a step reads the chunk's K
+//                             assignments and its stored match (the same addresses for every lane), and the holder
+//                             conflicts are settled by G shuffles.  It writes one byte per (chunk, g): the reference bit
+//                             of the name g carries in that step, or "other"; and the holder itself where asked.  Chunks
+//                             from the chain's status on change nothing (their assignments are -1 anyway).
+//   tune_ident_score_kernel   one workgroup of 256 lanes per pair, pairs blockIdx.x, blockIdx.x + gridDim.x, ...: the
+//                             toggle and prefix-XOR phases of tune_score_kernel (tc_score_cells) on a scratch slice, then
+//                             per cell the identities of the step that owns it, popcounts, five sums per lane added in
+//                             lane order by lane 0.  No assignment problem, no co-occurrence sweep, 15 KB of LDS.
+//
+// Both are latency-sized (a chain is a dependent walk; a pair is a few thousand cells).  Vector stores only, no
+// floating-point atomics: two calls give the same doubles.  The arithmetic is tune_ident_core.h's, which the host
+// compiles too.  No contraction, as in k_tune.hip.
+#pragma clang fp contract(off)
+#include "dz_common.h"
+#include "tune_ident_core.h"
+
+namespace {
+
+constexpr int NAME_WAVE = 64;
+
+struct IdentLanes {
+    int nl;
+    template <typename F>
+    __device__ void operator()(F f) const {
+        f((int)threadIdx.x);
+        __syncthreads();
+    }
+};
+
+__global__ __launch_bounds__(NAME_WAVE) void tune_name_kernel(
+    int trials, int n_files, int total_chunks, int K, int G, int V, const int* __restrict__ file_chunk_off,
+    const signed char* __restrict__ assign, const int* __restrict__ status, const int* __restrict__ match_index,
+    const float* __restrict__ match_distance, const signed char* __restrict__ vp_ref, const double* __restrict__ delta_id,
+    signed char* __restrict__ ident, int* __restrict__ hold) {
+    const int g = threadIdx.x;
+    const long long chains = (long long)trials * n_files;
+    for (long long chain = blockIdx.x; chain < chains; chain += gridDim.x) {
+        const int t = (int)(chain / n_files), n = (int)(chain - (long long)t * n_files);
+        const int c0 = file_chunk_off[n], c1 = file_chunk_off[n + 1];
+        const int st = status[chain];
+        const int stop = st < 0 ? c1 : (c0 + st < c1 ? c0 + st : c1);
+        const double delta = delta_id[t];
+        const signed char* A = assign + (size_t)t * total_chunks * K;
+        signed char* I = ident + (size_t)t * total_chunks * G;
+        int* H = hold ? hold + (size_t)t * total_chunks * G : nullptr;
+        float best_d = INFINITY;
+        int best_e = -1;
+        for (int c = c0; c < c1; ++c) {
+            if (c < stop)
+                ti_update(best_d, best_e, g, A + (size_t)c * K, match_index + (size_t)c * K, match_distance + (size_t)c * K, K,
+                          delta);
+            const int h = ti_hold(best_d, best_e, g, G, [&](int g2, float* d2, int* e2) {
+                *d2 = __shfl(best_d, g2, NAME_WAVE);
+                *e2 = __shfl(best_e, g2, NAME_WAVE);
+            });
+            if (g < G) {
+                I[(size_t)c * G + g] = ti_identity(h, vp_ref + (size_t)n * V, V);
+                if (H) H[(size_t)c * G + g] = h;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(TC_SCORE_LANES) void tune_ident_score_kernel(
+    const unsigned* __restrict__ bits, const signed char* __restrict__ ident, int trials, int n_files, int total_rows,
+    int total_chunks, const int* __restrict__ file_chunk_off, const int* __restrict__ row_off,
+    const double* __restrict__ mids, const int* __restrict__ mid_cell, const int* __restrict__ file_cell_off,
+    const double* __restrict__ cell_dur, const unsigned long long* __restrict__ cell_ref, const int* __restrict__ cell_step,
+    int max_cells, int max_speakers, double collar, double* __restrict__ out, unsigned* scratch, int* err) {
+    __shared__ TiScoreShared sh;
+    unsigned* slice = scratch + (size_t)blockIdx.x * ((size_t)max_cells + 1);
+    const long long pairs = (long long)trials * n_files;
+    for (long long pair = blockIdx.x; pair < pairs; pair += gridDim.x) {
+        const int t = (int)(pair / n_files), n = (int)(pair - (long long)t * n_files);
+        const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
+        if (ncell < 0 || ncell > max_cells) {   // (the same for every lane) the file does not fit a slice
+            if (threadIdx.x == 0) tc_err_raise(err, TC_SCORE_ERR_ARGS);
+            continue;
+        }
+        const TiScoreIn in = {{bits + (size_t)t * total_rows, row_off, mids, mid_cell, cell_dur + cell0, cell_ref + cell0,
+                               file_chunk_off[n], file_chunk_off[n + 1], ncell, max_speakers, collar},
+                              ident + (size_t)t * total_chunks * max_speakers, cell_step + cell0};
+        ti_score_pair(in, sh, slice, out + (size_t)pair * 5, err, IdentLanes{TC_SCORE_LANES});
+    }
+}
+
+}  // namespace
+
+extern "C" int dz_tune_name(dz_ctx* ctx, int trials, int n_files, int total_chunks, int k_local, int max_speakers,
+                            int voiceprints, const int* d_file_chunk_off, const signed char* d_assign, const int* d_status,
+                            const int* d_match_index, const float* d_match_distance, const signed char* d_vp_ref,
+                            const double* d_delta_id, signed char* d_ident, int* d_hold, int name_blocks, void* stream) {
+    DZ_REQUIRE(ctx && d_file_chunk_off && d_assign && d_status && d_match_index && d_match_distance && d_vp_ref &&
+                   d_delta_id && d_ident, "dz_tune_name: NULL argument");
+    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_chunks >= n_files && k_local >= 1 && k_local <= TC_KMAX &&
+                   max_speakers >= 1 && max_speakers <= TC_GMAX && voiceprints >= 1 && name_blocks >= 1,
+               "dz_tune_name: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at most %d / %d), "
+               "%d voiceprints, %d workgroups)",
+               trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints, name_blocks);
+    const long long chains = (long long)trials * n_files;
+    DZ_REQUIRE(chains < (1ll << 31), "dz_tune_name: %lld chains in one call; evaluate fewer trials per batch", chains);
+    DZ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = (int)(chains < name_blocks ? chains : name_blocks);
+    DZ_LAUNCH(tune_name_kernel, dim3(grid), dim3(NAME_WAVE), 0, st, trials, n_files, total_chunks, k_local, max_speakers,
+              voiceprints, d_file_chunk_off, d_assign, d_status, d_match_index, d_match_distance, d_vp_ref, d_delta_id, d_ident,
+              d_hold);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int dz_tune_ident_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits,
+                                       const signed char* d_ident, int total_rows, int total_chunks,
+                                       const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
+                                       const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
+                                       const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
+                                       int max_speakers, double collar, double* d_out, unsigned* d_scratch, int score_blocks,
+                                       int* d_err, void* stream) {
+    DZ_REQUIRE(ctx && d_bits && d_ident && d_file_chunk_off && d_row_off && d_mids && d_mid_cell && d_file_cell_off &&
+                   d_cell_dur && d_cell_ref && d_cell_step && d_out && d_scratch && d_err,
+               "dz_tune_ident_score_gpu: NULL argument");
+    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_rows >= 1 && total_chunks >= n_files && max_cells >= 0 &&
+                   score_blocks >= 1 && max_speakers >= 1 && max_speakers <= TC_GMAX,
+               "dz_tune_ident_score_gpu: bad arguments (%d trials, %d files, %d rows, %d chunks, %d cells per slice, %d slices, "
+               "%d speakers (at most %d))",
+               trials, n_files, total_rows, total_chunks, max_cells, score_blocks, max_speakers, TC_GMAX);
+    const long long pairs = (long long)trials * n_files;
+    DZ_REQUIRE(pairs < (1ll << 31), "dz_tune_ident_score_gpu: %lld pairs in one call; evaluate fewer trials per batch", pairs);
+    DZ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    DZ_HIP(hipMemsetAsync(d_err, 0, sizeof(int), st));
+    const int grid = (int)(pairs < score_blocks ? pairs : score_blocks);
+    DZ_LAUNCH(tune_ident_score_kernel, dim3(grid), dim3(TC_SCORE_LANES), 0, st, d_bits, d_ident, trials, n_files, total_rows,
+              total_chunks, d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_cell_dur, d_cell_ref,
+              d_cell_step, max_cells, max_speakers, collar, d_out, d_scratch, d_err);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}

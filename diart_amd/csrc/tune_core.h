@@ -351,9 +351,11 @@ TC_HD bool tc_str_less(int a, int b) {
     return a1 < b1;
 }
 
-template <typename Lanes>
-TC_HD void tc_score_pair(const TcScoreIn& in, TcScoreShared& sh, unsigned* scratch, double* out /* 5 */, int* err,
-                         Lanes lanes) {
+// The first half of a pair, which the identification scoring shares (tune_ident_core.h): after it word i of the slice
+// is the hypothesis mask of scoring cell i, and sh.err says whether a turn left the file's cells.  `Shared` has
+// lane_any, lane_x, end_e, end_cell (one per lane) and err.
+template <typename Shared, typename Lanes>
+TC_HD void tc_score_cells(const TcScoreIn& in, Shared& sh, unsigned* scratch, Lanes lanes) {
     const int nl = lanes.nl, ncell = in.ncell, chunks = in.c1 - in.c0;
     const int per = tc_vad_steps_per_lane(chunks, nl);
     const unsigned gmask = in.G >= 32 ? 0xffffffffu : ((1u << in.G) - 1u);   // dz_tune_score ignores bits >= G
@@ -416,6 +418,13 @@ TC_HD void tc_score_pair(const TcScoreIn& in, TcScoreShared& sh, unsigned* scrat
             tc_word_store(scratch + i, carry);
         }
     });
+}
+
+template <typename Lanes>
+TC_HD void tc_score_pair(const TcScoreIn& in, TcScoreShared& sh, unsigned* scratch, double* out /* 5 */, int* err,
+                         Lanes lanes) {
+    const int nl = lanes.nl, ncell = in.ncell;
+    tc_score_cells(in, sh, scratch, lanes);
     // ---- the components over the cells, per lane
     lanes([&](int lane) {
         double total = 0.0, missed = 0.0, fa = 0.0, both = 0.0;

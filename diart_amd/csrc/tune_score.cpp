@@ -15,7 +15,12 @@
 //   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
 //                        scoring of k_tune_vad.hip, from the text those kernels compile; OverlappedSpeechDetection
 //                        too (both track pipelines: another track, other reference prefix sums)
+//   dz_tune_name_host    the names a gallery gives the global speakers of every (trial, file) chain, step by step, from
+//                        the text tune_name_kernel compiles (tune_ident_core.h)
+//   dz_tune_ident_score  identification error rate components of every pair: dz_tune_score's cells, the labels compared
+//                        as they are;  dz_tune_ident_score_core: the same from the text of tune_ident_score_kernel
 #include "tune_core.h"
+#include "tune_ident_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -46,6 +51,68 @@ struct Turn {
     double s, e;
     int is, ie;   // the cells that start at s and at e
 };
+
+struct ScoreScratch {
+    std::vector<Turn> turns[TC_GMAX];
+    std::vector<unsigned> hyp;
+};
+
+// The hypothesis mask of every scoring cell of file n from one trial's masks B (dz_tune_score and
+// dz_tune_ident_score): Binarize's turns per step and speaker, Annotation.support(collar) per speaker, then the cells
+// each merged turn covers.  Returns 4 when a turn does not start and end on the file's cells.
+int hyp_cells(ScoreScratch& sc, const unsigned* B, int n, const int* file_row_off, const int* file_chunk_off,
+              const int* step_rows, const double* mids, const int* mid_cell, int ncell, int G, double collar) {
+    int rc = 0;
+    for (int g = 0; g < G; ++g) sc.turns[g].clear();
+    // ---- Binarize (tail_edge_walk): per step and speaker, [middle(onset), middle(first inactive row))
+    int p = file_row_off[n];
+    for (int c = file_chunk_off[n]; c < file_chunk_off[n + 1]; ++c) {
+        const int rows = step_rows[c];
+        const double* mid = mids + (size_t)p + c;      // rows + 1 values
+        const int* cell = mid_cell + (size_t)p + c;
+        unsigned any = 0;
+        for (int r = 0; r < rows; ++r) any |= B[p + r];
+        for (unsigned m = any; m; m &= m - 1) {
+            const int g = __builtin_ctz(m);
+            if (g >= G) break;
+            tail_edge_walk(rows, [&](int r) { return (B[p + r] >> g) & 1u; }, [&](int onset, int r) {
+                if (mid[r] - mid[onset] > 1e-6)   // Segment.__bool__: shorter segments are not stored
+                    sc.turns[g].push_back(Turn{mid[onset], mid[r], cell[onset], cell[r]});
+                return true;
+            });
+        }
+        p += rows;
+    }
+    // ---- Annotation.support(collar) per speaker, then the cells each merged turn covers
+    sc.hyp.assign((size_t)ncell, 0u);
+    for (int g = 0; g < G; ++g) {
+        std::vector<Turn>& tv = sc.turns[g];
+        if (tv.empty()) continue;
+        std::sort(tv.begin(), tv.end(), [](const Turn& a, const Turn& b) { return a.s < b.s || (a.s == b.s && a.e < b.e); });
+        Turn cur = tv[0];
+        auto flush = [&](const Turn& u) {
+            if (u.is < 0 || u.ie > ncell || u.is > u.ie) {
+                rc = 4;
+                return;
+            }
+            for (int i = u.is; i < u.ie; ++i) sc.hyp[i] |= 1u << g;
+        };
+        for (size_t i = 1; i < tv.size(); ++i) {
+            const double gap = tv[i].s - cur.e;
+            if (gap <= 1e-6 || gap < collar) {
+                if (tv[i].e > cur.e) {
+                    cur.e = tv[i].e;
+                    cur.ie = tv[i].ie;
+                }
+            } else {
+                flush(cur);
+                cur = tv[i];
+            }
+        }
+        flush(cur);
+    }
+    return rc;
+}
 
 }  // namespace
 
@@ -200,65 +267,15 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
     const int N = n_files, G = max_speakers, pairs = trials * N;
     int nt = num_threads < 1 ? 1 : num_threads;
     if (nt > pairs) nt = pairs;
-    struct Scratch {
-        std::vector<Turn> turns[TC_GMAX];
-        std::vector<unsigned> hyp;
-    };
-    std::vector<Scratch> scratch(nt);
+    std::vector<ScoreScratch> scratch(nt);
     std::vector<int> rcs(nt, 0);
     auto run = [&](int w, int pair) {
         const int t = pair / N, n = pair - t * N;
-        Scratch& sc = scratch[w];
-        const unsigned* B = bits + (size_t)t * total_rows;
-        for (int g = 0; g < G; ++g) sc.turns[g].clear();
-        // ---- Binarize (tail_edge_walk): per step and speaker, [middle(onset), middle(first inactive row))
-        int p = file_row_off[n];
-        for (int c = file_chunk_off[n]; c < file_chunk_off[n + 1]; ++c) {
-            const int rows = step_rows[c];
-            const double* mid = mids + (size_t)p + c;      // rows + 1 values
-            const int* cell = mid_cell + (size_t)p + c;
-            unsigned any = 0;
-            for (int r = 0; r < rows; ++r) any |= B[p + r];
-            for (unsigned m = any; m; m &= m - 1) {
-                const int g = __builtin_ctz(m);
-                if (g >= G) break;
-                tail_edge_walk(rows, [&](int r) { return (B[p + r] >> g) & 1u; }, [&](int onset, int r) {
-                    if (mid[r] - mid[onset] > 1e-6)   // Segment.__bool__: shorter segments are not stored
-                        sc.turns[g].push_back(Turn{mid[onset], mid[r], cell[onset], cell[r]});
-                    return true;
-                });
-            }
-            p += rows;
-        }
-        // ---- Annotation.support(collar) per speaker, then the cells each merged turn covers
+        ScoreScratch& sc = scratch[w];
         const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
-        sc.hyp.assign((size_t)ncell, 0u);
-        for (int g = 0; g < G; ++g) {
-            std::vector<Turn>& tv = sc.turns[g];
-            if (tv.empty()) continue;
-            std::sort(tv.begin(), tv.end(), [](const Turn& a, const Turn& b) { return a.s < b.s || (a.s == b.s && a.e < b.e); });
-            Turn cur = tv[0];
-            auto flush = [&](const Turn& u) {
-                if (u.is < 0 || u.ie > ncell || u.is > u.ie) {
-                    rcs[w] = 4;
-                    return;
-                }
-                for (int i = u.is; i < u.ie; ++i) sc.hyp[i] |= 1u << g;
-            };
-            for (size_t i = 1; i < tv.size(); ++i) {
-                const double gap = tv[i].s - cur.e;
-                if (gap <= 1e-6 || gap < collar) {
-                    if (tv[i].e > cur.e) {
-                        cur.e = tv[i].e;
-                        cur.ie = tv[i].ie;
-                    }
-                } else {
-                    flush(cur);
-                    cur = tv[i];
-                }
-            }
-            flush(cur);
-        }
+        if (hyp_cells(sc, bits + (size_t)t * total_rows, n, file_row_off, file_chunk_off, step_rows, mids, mid_cell, ncell, G,
+                      collar))
+            rcs[w] = 4;
         // ---- the components over the cells
         double total = 0.0, missed = 0.0, fa = 0.0, both = 0.0;
         double cooc[TC_GMAX][64];
@@ -438,6 +455,168 @@ extern "C" int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int t
             for (int i = 0; i < pairs; ++i) run(0, i);
         else
             dz_host_parallel(pairs, nt, run);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Tuning delta_id
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int dz_tune_name_host(int trials, int n_files, int total_chunks, int k_local, int max_speakers, int voiceprints,
+                                 const int* file_chunk_off, const signed char* assign, const int* status,
+                                 const int* match_index, const float* match_distance, const signed char* vp_ref,
+                                 const double* delta_id, signed char* ident, int* hold, int num_threads) {
+    if (!file_chunk_off || !assign || !status || !match_index || !match_distance || !vp_ref || !delta_id || !ident) {
+        dz_set_error("dz_tune_name_host: NULL argument");
+        return 2;
+    }
+    if (trials < 1 || n_files < 1 || total_chunks < n_files || k_local < 1 || k_local > TC_KMAX || max_speakers < 1 ||
+        max_speakers > TC_GMAX || voiceprints < 1) {
+        dz_set_error("dz_tune_name_host: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at most "
+                     "%d / %d), %d voiceprints)",
+                     trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints);
+        return 2;
+    }
+    const int N = n_files, K = k_local, G = max_speakers, V = voiceprints, pairs = trials * N;
+    auto run = [&](int, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        const int c0 = file_chunk_off[n], c1 = file_chunk_off[n + 1];
+        const int stop = status[pair] < 0 ? c1 : std::min(c0 + status[pair], c1);
+        const signed char* A = assign + (size_t)t * total_chunks * K;
+        signed char* I = ident + (size_t)t * total_chunks * G;
+        int* H = hold ? hold + (size_t)t * total_chunks * G : nullptr;
+        float best_d[TC_GMAX];
+        int best_e[TC_GMAX];
+        for (int g = 0; g < G; ++g) {
+            best_d[g] = INFINITY;
+            best_e[g] = -1;
+        }
+        for (int c = c0; c < c1; ++c) {
+            if (c < stop)
+                for (int g = 0; g < G; ++g)
+                    ti_update(best_d[g], best_e[g], g, A + (size_t)c * K, match_index + (size_t)c * K,
+                              match_distance + (size_t)c * K, K, delta_id[t]);
+            for (int g = 0; g < G; ++g) {
+                const int h = ti_hold(best_d[g], best_e[g], g, G, [&](int g2, float* d2, int* e2) {
+                    *d2 = best_d[g2];
+                    *e2 = best_e[g2];
+                });
+                I[(size_t)c * G + g] = ti_identity(h, vp_ref + (size_t)n * V, V);
+                if (H) H[(size_t)c * G + g] = h;
+            }
+        }
+    };
+    const int nt = std::max(1, std::min(num_threads, pairs));
+    if (nt == 1)
+        for (int i = 0; i < pairs; ++i) run(0, i);
+    else
+        dz_host_parallel(pairs, nt, run);
+    return 0;
+}
+
+extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
+                                   int total_chunks, const int* file_row_off, const int* file_chunk_off,
+                                   const int* step_rows, const double* mids, const int* mid_cell, const int* file_cell_off,
+                                   const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
+                                   int max_speakers, double collar, double* out, int num_threads) {
+    if (!bits || !ident || !file_row_off || !file_chunk_off || !step_rows || !mids || !mid_cell || !file_cell_off ||
+        !cell_dur || !cell_ref || !cell_step || !out) {
+        dz_set_error("dz_tune_ident_score: NULL argument");
+        return 2;
+    }
+    if (trials < 1 || n_files < 1 || total_rows < 1 || total_chunks < n_files || max_speakers < 1 || max_speakers > TC_GMAX) {
+        dz_set_error("dz_tune_ident_score: bad arguments (%d trials, %d files, %d rows, %d chunks, %d speakers (at most %d))",
+                     trials, n_files, total_rows, total_chunks, max_speakers, TC_GMAX);
+        return 2;
+    }
+    const int N = n_files, G = max_speakers, pairs = trials * N;
+    const int nt = std::max(1, std::min(num_threads, pairs));
+    std::vector<ScoreScratch> scratch(nt);
+    std::vector<int> rcs(nt, 0);
+    auto run = [&](int w, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        ScoreScratch& sc = scratch[w];
+        const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
+        if (hyp_cells(sc, bits + (size_t)t * total_rows, n, file_row_off, file_chunk_off, step_rows, mids, mid_cell, ncell, G,
+                      collar))
+            rcs[w] = 4;
+        const signed char* I = ident + (size_t)t * total_chunks * G;
+        double* o = out + (size_t)pair * 5;   // metrics.COMPONENTS order
+        for (int q = 0; q < 5; ++q) o[q] = 0.0;
+        for (int i = 0; i < ncell; ++i) {
+            const unsigned h = sc.hyp[i];
+            const unsigned long long rm = cell_ref[cell0 + i];
+            if (!h && !rm) continue;
+            const int c = cell_step[cell0 + i];
+            if (c < file_chunk_off[n] || c >= file_chunk_off[n + 1]) {
+                rcs[w] = 4;
+                continue;
+            }
+            int cnt[5];
+            ti_cell_counts(h, rm, I + (size_t)c * G, cnt);
+            for (int q = 0; q < 5; ++q) o[q] += cell_dur[cell0 + i] * cnt[q];
+        }
+    };
+    if (nt == 1)
+        for (int i = 0; i < pairs; ++i) run(0, i);
+    else
+        dz_host_parallel(pairs, nt, run);
+    for (int w = 0; w < nt; ++w)
+        if (rcs[w]) {
+            dz_set_error("dz_tune_ident_score: a speech turn or a step does not lie on the file's scoring cells");
+            return rcs[w];
+        }
+    return 0;
+}
+
+extern "C" int dz_tune_ident_score_core(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
+                                        int total_chunks, const int* file_chunk_off, const int* row_off, const double* mids,
+                                        const int* mid_cell, const int* file_cell_off, const double* cell_dur,
+                                        const unsigned long long* cell_ref, const int* cell_step, int max_cells,
+                                        int max_speakers, double collar, int lanes, int score_blocks, double* out,
+                                        int num_threads) {
+    if (!bits || !ident || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off || !cell_dur || !cell_ref ||
+        !cell_step || !out) {
+        dz_set_error("dz_tune_ident_score_core: NULL argument");
+        return 2;
+    }
+    if (trials < 1 || n_files < 1 || total_rows < 1 || total_chunks < n_files || max_speakers < 1 || max_speakers > TC_GMAX ||
+        max_cells < 0 || lanes < 1 || lanes > TC_SCORE_LANES || score_blocks < 1) {
+        dz_set_error("dz_tune_ident_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
+        return 2;
+    }
+    const long long pairs = (long long)trials * n_files;
+    const int blocks = (int)(pairs < score_blocks ? pairs : score_blocks);
+    const int nt = std::max(1, std::min(num_threads, blocks));
+    std::vector<int> errs(blocks, 0);
+    auto run = [&](int, int b) {
+        std::vector<unsigned> slice((size_t)max_cells + 1, 0xa5a5a5a5u);
+        std::vector<TiScoreShared> sh(1);
+        for (long long pair = b; pair < pairs; pair += blocks) {
+            const int t = (int)(pair / n_files), n = (int)(pair - (long long)t * n_files);
+            const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
+            if (ncell < 0 || ncell > max_cells) {
+                tc_err_raise(&errs[b], TC_SCORE_ERR_ARGS);
+                continue;
+            }
+            std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(TiScoreShared));
+            const TiScoreIn in = {{bits + (size_t)t * total_rows, row_off, mids, mid_cell, cell_dur + cell0, cell_ref + cell0,
+                                   file_chunk_off[n], file_chunk_off[n + 1], ncell, max_speakers, collar},
+                                  ident + (size_t)t * total_chunks * max_speakers, cell_step + cell0};
+            ti_score_pair(in, sh[0], slice.data(), out + (size_t)pair * 5, &errs[b], LanesInTurn{lanes});
+        }
+    };
+    if (nt == 1)
+        for (int b = 0; b < blocks; ++b) run(0, b);
+    else
+        dz_host_parallel(blocks, nt, run);
+    int rc = 0;
+    for (int b = 0; b < blocks; ++b)
+        if (errs[b] > rc) rc = errs[b];
+    if (rc) {
+        dz_set_error(rc == TC_SCORE_ERR_ARGS ? "dz_tune_ident_score_core: a file has more scoring cells than a scratch slice holds"
+                                             : "dz_tune_ident_score: a speech turn or a step does not lie on the file's scoring cells");
+        return rc;
     }
     return 0;
 }

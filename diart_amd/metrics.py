@@ -216,3 +216,34 @@ class OverlapDetectionFMeasure(_Accumulating):
 
     def _rate(self, comp: Dict[str, float]) -> float:
         return float(detection_prf(comp)[2])
+
+
+class IdentificationErrorRate(_Accumulating):
+    """The identification error rate: hypothesis labels are NAMES and are compared with the reference labels as they
+    are — there is no mapping.  (R) — read from pyannote.metrics' published ``IdentificationErrorRate`` with unit
+    weights (confusion, miss and false alarm each count 1), not run against the package, which is not installable
+    here.  Over every elementary region with reference labels R and hypothesis labels H:
+
+        total += dur |R|,  correct += dur |R & H|,
+        missed detection += dur max(0, |R| - |H|),  false alarm += dur max(0, |H| - |R|),
+        confusion += dur (min(|R|, |H|) - |R & H|),   IER = sum(miss + fa + conf) / sum(|R|)
+
+    A reference speaker nobody names can only be missed or confused; a hypothesis label no reference has (an unnamed
+    ``speaker3``, say) can only be a false alarm or a confusion.  No collar, overlapped speech included."""
+    name = "identification error rate"
+
+    def __init__(self, collar: float = 0.0, skip_overlap: bool = False):
+        if collar != 0.0 or skip_overlap:
+            raise NotImplementedError("only collar=0, skip_overlap=False is built")
+        super().__init__()
+
+    def components(self, reference: Annotation, hypothesis: Annotation) -> Dict[str, float]:
+        comp = {c: 0.0 for c in COMPONENTS}
+        for dur, r, h in _regions(_turns(reference), _turns(hypothesis)):
+            nref, nhyp, both = len(r), len(h), len(set(r) & set(h))
+            comp["total"] += dur * nref
+            comp["correct"] += dur * both
+            comp["missed detection"] += dur * max(0, nref - nhyp)
+            comp["false alarm"] += dur * max(0, nhyp - nref)
+            comp["confusion"] += dur * (min(nref, nhyp) - both)
+        return comp

@@ -25,12 +25,19 @@ that a batch of trials returns ``T x N x 5`` doubles and nothing else.
 and is scored against another reference (the regions where two different speakers are active): ``OsdTuneCache`` feeds
 the VAD tuner's kernels and host code that track and the prefix sums of those regions.  A collected ``TuneCache`` holds
 the raw scores both tracks are made of: ``VadTuneCache.from_tune_cache`` / ``OsdTuneCache.from_tune_cache``.
+
+``delta_id``, the distance under which a speaker takes the name of an enrolled voiceprint (``gallery.py``), is tuned
+on the same cache: ``TuneCache.with_gallery`` matches the cached embeddings against a ``SpeakerGallery`` once (the match
+depends on no hyper-parameter) and returns an ``IdentTuneCache``, whose trials replay ``SpeakerNames`` over the
+clustering's assignments and are scored by the identification error rate — names compared as they are, no mapping
+(``csrc/k_tune_ident.hip``).
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
 import json
+import re
 from pathlib import Path
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
@@ -40,10 +47,11 @@ import torch
 from . import _lib
 from .blocks import base
 from .features import Annotation, Segment
-from .metrics import (DetectionErrorRate, DiarizationErrorRate, OverlapDetectionErrorRate, OverlapDetectionFMeasure,
-                      _turns, detection_prf, overlap_reference)
+from .metrics import (DetectionErrorRate, DiarizationErrorRate, IdentificationErrorRate, OverlapDetectionErrorRate,
+                      OverlapDetectionFMeasure, _turns, detection_prf, overlap_reference)
 
 TUNABLE = ("tau_active", "rho_update", "delta_new")
+IDENT_TUNABLE = TUNABLE + ("delta_id",)
 VAD_TUNABLE = ("tau_active",)
 MAX_SPEAKERS = 32          # the hypothesis of a frame is one 32-bit mask
 MAX_LOCAL_SPEAKERS = 8
@@ -300,7 +308,7 @@ class TuneCache(_ReplayCache):
             f["seg"], f["emb"] = f.pop("outputs")
         return cls(files, pipeline.config)
 
-    def save(self, path) -> None:
+    def _payload(self) -> dict:
         out = {"meta": np.array(json.dumps(self.meta)), "uris": np.array([f["uri"] for f in self.files])}
         for i, f in enumerate(self.files):
             for k in ("seg", "emb", "starts", "res"):
@@ -308,21 +316,35 @@ class TuneCache(_ReplayCache):
             out[f"shift_{i}"] = np.array(f["shift"])
             out[f"ref_times_{i}"] = np.array([[s, e] for s, e, _ in f["turns"]], dtype=np.float64).reshape(-1, 2)
             out[f"ref_labels_{i}"] = np.array([str(l) for _, _, l in f["turns"]], dtype=str)
+        return out
+
+    def save(self, path) -> None:
         with open(path, "wb") as fh:
-            np.savez(fh, **out)
+            np.savez(fh, **self._payload())
+
+    @staticmethod
+    def _stored(z) -> "TuneCache":
+        meta = json.loads(str(z["meta"]))
+        files = []
+        for i, uri in enumerate(z["uris"]):
+            ref = [(s, e, str(l)) for (s, e), l in zip(z[f"ref_times_{i}"], z[f"ref_labels_{i}"])]
+            files.append(dict(uri=str(uri), seg=z[f"seg_{i}"], emb=z[f"emb_{i}"], starts=z[f"starts_{i}"],
+                              res=z[f"res_{i}"], shift=float(z[f"shift_{i}"]), reference=ref))
+        return TuneCache(files, meta)
 
     @classmethod
     def load(cls, path) -> "TuneCache":
         with np.load(path, allow_pickle=False) as z:
             if "kind" in z.files:
                 raise ValueError(f"{path} holds a {str(z['kind'])}, not a TuneCache (SpeakerDiarization)")
-            meta = json.loads(str(z["meta"]))
-            files = []
-            for i, uri in enumerate(z["uris"]):
-                ref = [(s, e, str(l)) for (s, e), l in zip(z[f"ref_times_{i}"], z[f"ref_labels_{i}"])]
-                files.append(dict(uri=str(uri), seg=z[f"seg_{i}"], emb=z[f"emb_{i}"], starts=z[f"starts_{i}"],
-                                  res=z[f"res_{i}"], shift=float(z[f"shift_{i}"]), reference=ref))
-        return cls(files, meta)
+            return cls._stored(z)
+
+    def with_gallery(self, gallery, device=None) -> "IdentTuneCache":
+        """This cache with the match of every cached embedding against ``gallery`` (a ``SpeakerGallery``): an
+        ``IdentTuneCache``, which tunes ``delta_id`` beside the three.  The files, the plan and the device copies are
+        shared, not copied.  The match is ``gallery.match`` on the GPU when there is one (``device``: which), else
+        ``functional.gallery_match``'s float64 statement rounded to float32."""
+        return IdentTuneCache(self, gallery, device=device)
 
     # ------------------------------------------------------------------------------------------ trial-independent parts
     def _reference_bits(self, f: dict) -> Dict[object, int]:
@@ -536,6 +558,274 @@ class TuneCache(_ReplayCache):
         """File n's hypothesis under one trial as the ``Annotation`` ``PredictionAccumulator`` ends with (tests and
         RTTM output): the speech turns of the masks, same-speaker turns closer than the patch collar merged."""
         return self._hypothesis(bits_row, n, self.G, lambda g: f"speaker{g}")
+
+
+_RESERVED_LABEL = re.compile(r"speaker\d+")          # gallery.py: what unnamed speakers are called
+
+
+class IdentTuneCache(TuneCache):
+    """A ``TuneCache`` plus a gallery: ``delta_id`` is tuned beside ``tau_active``, ``rho_update`` and ``delta_new``.
+    Three arrays are added, the same for every trial and read by every backend (two backends can never disagree about a
+    distance next to ``delta_id``): ``match_index (chunks, K) int32`` and ``match_distance (chunks, K) float32``, the
+    nearest voiceprint of every cached embedding row and its cosine distance (-1 / NaN for a NaN or zero row), and
+    ``vp_ref (N, V) int8``, per file the bit of the reference label that equals voiceprint v's name, or -1.
+
+    A trial's names are ``gallery.SpeakerNames(1, G, delta_id)`` run over the file's chunks on the trial's assignments:
+    ``hold[c][g]`` is the voiceprint whose name global speaker g carries in step c, or -1.  The named hypothesis is
+    ``TuneCache.hypothesis`` with every turn of g cut at the steps' first frame middles ``b_c`` and each piece in
+    ``[b_c, b_{c+1})`` labelled ``names[hold[c][g]]``, or ``speaker{g}`` where g holds none (the first step of a file
+    also owns what lies before its ``b_c``, the last what lies behind).  It is scored by
+    ``metrics.IdentificationErrorRate``: labels compared as they are.  This needs the steps' grids sorted by time
+    (``sorted_steps``); a cache without is refused on every backend.  A reference label of the form ``speaker<digits>``
+    is refused, as the gallery refuses such names."""
+
+    KIND = "IdentTuneCache"
+    NAME_BLOCKS = 8192          # resident naming chains: 256 CUs x 32 one-wave workgroups
+    IDENT_BLOCKS = 1024         # resident ident-scoring workgroups (15 KB of LDS each), one scratch slice each
+    _IDENT_ERRORS = {4: "a speech turn or a step does not lie on the file's scoring cells",
+                     2: "a file has more scoring cells than a scratch slice holds"}
+
+    def __init__(self, cache: TuneCache, gallery, device=None, match=None):
+        if not isinstance(cache, TuneCache):
+            raise ValueError(f"IdentTuneCache takes a TuneCache, got a {type(cache).__name__}")
+        if gallery.dimension != cache.D:
+            raise ValueError(f"IdentTuneCache: a gallery of dimension {gallery.dimension} against cached embeddings of "
+                             f"dimension {cache.D}")
+        for f in cache.files:
+            bad = [l for _, _, l in f["turns"] if _RESERVED_LABEL.fullmatch(str(l))]
+            if bad:
+                raise ValueError(f"IdentTuneCache: {f['uri']}: reference label {bad[0]!r} is what an unnamed speaker is "
+                                 "called (speaker<digits>)")
+        self.__dict__.update(cache.__dict__)                 # the files, the plan, the device copies: shared
+        self.names = tuple(gallery.names)
+        self.voiceprints = gallery.voiceprints
+        total = int(self.chunk_off[-1])
+        if match is None:
+            if torch.cuda.is_available():
+                if device is not None:
+                    gallery._resolve(device)
+                index, distance, _ = gallery.match(self.emb)
+            else:
+                from .functional import gallery_match
+                index, distance, _ = gallery_match(self.emb, gallery.voiceprints)
+        else:
+            index, distance = match
+        self.match_index = np.ascontiguousarray(index, dtype=np.int32).reshape(total, self.K)
+        self.match_distance = np.ascontiguousarray(distance, dtype=np.float32).reshape(total, self.K)
+        V = len(self.names)
+        if ((self.match_index < -1) | (self.match_index >= V)).any():
+            raise ValueError(f"IdentTuneCache: a stored match names a voiceprint outside 0 .. {V - 1}")
+        self.vp_ref = np.full((self.N, V), -1, dtype=np.int8)
+        for n, labels in enumerate(self.ref_labels):
+            bit = {str(l): i for i, l in enumerate(labels)}
+            for v, name in enumerate(self.names):
+                self.vp_ref[n, v] = bit.get(name, -1)
+        # the step that owns every scoring cell: step c owns the cells from the one that starts at its first frame
+        # middle to the next step's (the first step of a file everything before, the last everything behind)
+        self.cell_step = np.zeros(int(self.file_cell_off[-1]), dtype=np.int32)
+        if self.sorted_steps:
+            for n in range(self.N):
+                c0, c1 = int(self.chunk_off[n]), int(self.chunk_off[n + 1])
+                first = self.mid_cell[self.row_off[c0:c1] + np.arange(c0, c1)]
+                a, b = int(self.file_cell_off[n]), int(self.file_cell_off[n + 1])
+                own = np.searchsorted(first, np.arange(b - a), side="right") - 1
+                self.cell_step[a:b] = c0 + np.clip(own, 0, c1 - c0 - 1)
+        self._ident_dev = {}
+
+    # ------------------------------------------------------------------------------------------ construction
+    @classmethod
+    def from_arrays(cls, files, config):
+        raise TypeError("IdentTuneCache: TuneCache.from_arrays(files, config).with_gallery(gallery)")
+
+    @classmethod
+    def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32, gallery=None,
+                device=None) -> "IdentTuneCache":
+        if gallery is None:
+            raise ValueError("IdentTuneCache.collect needs gallery= (a SpeakerGallery)")
+        return TuneCache.collect(pipeline_class, base_config, speech_path, reference_path, batch_size).with_gallery(
+            gallery, device)
+
+    def save(self, path) -> None:
+        out = self._payload()
+        out.update(kind=np.array(self.KIND), gallery_names=np.asarray(self.names, dtype=np.str_),
+                   gallery_voiceprints=self.voiceprints, match_index=self.match_index, match_distance=self.match_distance)
+        with open(path, "wb") as fh:
+            np.savez(fh, **out)
+
+    @classmethod
+    def load(cls, path) -> "IdentTuneCache":
+        from .gallery import SpeakerGallery
+        with np.load(path, allow_pickle=False) as z:
+            kind = str(z["kind"]) if "kind" in z.files else None
+            if kind != cls.KIND:
+                holds = "TuneCache (SpeakerDiarization)" if kind is None else kind
+                raise ValueError(f"{path} holds a {holds}, not an IdentTuneCache (SpeakerDiarization with a gallery)")
+            gallery = SpeakerGallery([str(n) for n in z["gallery_names"]], z["gallery_voiceprints"])
+            return cls(cls._stored(z), gallery, match=(z["match_index"], z["match_distance"]))
+
+    # ------------------------------------------------------------------------------------------ replay
+    @property
+    def bytes_per_trial(self) -> int:
+        """``TuneCache.bytes_per_trial`` plus a trial's names: one byte per (chunk, global speaker)."""
+        return TuneCache.bytes_per_trial.fget(self) + int(self.chunk_off[-1]) * self.G
+
+    @staticmethod
+    def _hparams4(hparams) -> np.ndarray:
+        hp = np.ascontiguousarray(np.atleast_2d(np.asarray(hparams, dtype=np.float64)))
+        if hp.ndim != 2 or hp.shape[1] != 4 or hp.shape[0] < 1:
+            raise ValueError(f"hparams (T, 4) = (tau_active, rho_update, delta_new, delta_id) per trial expected, got "
+                             f"{hp.shape}")
+        bad = np.flatnonzero(~np.isfinite(hp[:, 3]) | (hp[:, 3] < 0))
+        if bad.size:
+            raise ValueError(f"trial {int(bad[0])}: delta_id={hp[bad[0], 3]!r} (a finite distance >= 0)")
+        return hp
+
+    def _check_steps(self) -> None:
+        if not self.sorted_steps:
+            raise ValueError("IdentTuneCache: a step owns the time from its first output frame to the next step's, and the "
+                             "output grids of this cache's steps are not sorted by time")
+
+    def _ident_device(self, device: torch.device):
+        key = str(device)
+        if key not in self._ident_dev:
+            self._ident_dev[key] = {name: torch.from_numpy(getattr(self, name)).to(device)
+                                    for name in ("match_index", "match_distance", "vp_ref", "cell_step")}
+        return self._ident_dev[key]
+
+    def _names_gpu(self, assign: torch.Tensor, status: torch.Tensor, delta_id: np.ndarray, want_hold: bool = False):
+        """``(ident (T, chunks, G) int8, hold (T, chunks, G) int32 or None)`` on the device: tune_name_kernel, enqueued."""
+        device = assign.device
+        t, i = self._device(device)[0], self._ident_device(device)
+        T, total = assign.shape[0], int(self.chunk_off[-1])
+        d_delta = torch.from_numpy(np.ascontiguousarray(delta_id)).to(device)
+        ident = torch.empty((T, total, self.G), dtype=torch.int8, device=device)
+        hold = torch.empty((T, total, self.G), dtype=torch.int32, device=device) if want_hold else None
+        _lib.check(_lib.load().dz_tune_name(_lib.context(device.index), T, self.N, total, self.K, self.G, len(self.names),
+                                            t["chunk_off"].data_ptr(), assign.data_ptr(), status.data_ptr(),
+                                            i["match_index"].data_ptr(), i["match_distance"].data_ptr(),
+                                            i["vp_ref"].data_ptr(), d_delta.data_ptr(), ident.data_ptr(),
+                                            None if hold is None else hold.data_ptr(), self.NAME_BLOCKS,
+                                            torch.cuda.current_stream(device).cuda_stream), "dz_tune_name")
+        return ident, hold
+
+    def _names_host(self, assign: np.ndarray, status: np.ndarray, delta_id: np.ndarray, want_hold: bool, num_threads: int):
+        T, total = assign.shape[0], int(self.chunk_off[-1])
+        delta_id = np.ascontiguousarray(delta_id)
+        ident = np.empty((T, total, self.G), dtype=np.int8)
+        hold = np.empty((T, total, self.G), dtype=np.int32) if want_hold else None
+        _lib.check(_lib.load().dz_tune_name_host(T, self.N, total, self.K, self.G, len(self.names), self.chunk_off.ctypes.data,
+                                                 assign.ctypes.data, status.ctypes.data, self.match_index.ctypes.data,
+                                                 self.match_distance.ctypes.data, self.vp_ref.ctypes.data,
+                                                 delta_id.ctypes.data, ident.ctypes.data,
+                                                 None if hold is None else hold.ctypes.data, int(num_threads)),
+                   "dz_tune_name_host")
+        return ident, hold
+
+    def replay_names(self, hparams, backend: Optional[str] = None, num_threads: int = 8):
+        """``(assign, status, bits, hold (T, chunks, G) int32)``: ``TuneCache.replay`` of the first three columns of
+        ``hparams (T, 4)``, and the voiceprint whose name every global speaker carries in every step under the
+        trial's ``delta_id`` (-1: none).  ``backend``: "gpu" | "host" | "core"; the naming rule has one text, which
+        "host" and "core" both run on host threads."""
+        hp = self._hparams4(hparams)
+        backend = backend or self.default_backend()
+        if backend == "gpu":
+            a, s, b = self._replay_gpu(np.ascontiguousarray(hp[:, :3]))
+            _, hold = self._names_gpu(a, s, hp[:, 3], want_hold=True)
+            torch.cuda.synchronize(a.device)
+            return a.cpu().numpy(), s.cpu().numpy(), b.cpu().numpy().view(np.uint32), hold.cpu().numpy()
+        a, s, b = TuneCache.replay(self, hp[:, :3], backend, num_threads)
+        return a, s, b, self._names_host(a, s, hp[:, 3], True, num_threads)[1]
+
+    def _ident_score_gpu(self, bits: torch.Tensor, ident: torch.Tensor):
+        device = bits.device
+        t, i = self._device(device)[0], self._ident_device(device)
+        T = bits.shape[0]
+        blocks = max(1, min(T * self.N, self.IDENT_BLOCKS))
+        out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device)
+        scratch = torch.empty((blocks, self.max_cells + 1), dtype=torch.int32, device=device)
+        err = torch.empty(1, dtype=torch.int32, device=device)
+        _lib.check(_lib.load().dz_tune_ident_score_gpu(
+            _lib.context(device.index), T, self.N, bits.data_ptr(), ident.data_ptr(), self.total_rows, int(self.chunk_off[-1]),
+            t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
+            t["file_cell_off"].data_ptr(), t["cell_dur"].data_ptr(), t["cell_ref"].data_ptr(), i["cell_step"].data_ptr(),
+            self.max_cells, self.G, PATCH_COLLAR, out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(),
+            torch.cuda.current_stream(device).cuda_stream), "dz_tune_ident_score_gpu")
+        return out, err
+
+    def _ident_score_host(self, bits: np.ndarray, ident: np.ndarray, core: bool, num_threads: int) -> np.ndarray:
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        T, total = bits.shape[0], int(self.chunk_off[-1])
+        out = np.zeros((T, self.N, 5), dtype=np.float64)
+        lib, p = _lib.load(), lambda name: getattr(self, name).ctypes.data
+        if core:
+            _lib.check(lib.dz_tune_ident_score_core(T, self.N, bits.ctypes.data, ident.ctypes.data, self.total_rows, total,
+                                                    p("chunk_off"), p("row_off"), p("mids"), p("mid_cell"), p("file_cell_off"),
+                                                    p("cell_dur"), p("cell_ref"), p("cell_step"), self.max_cells, self.G,
+                                                    PATCH_COLLAR, self.SCORE_LANES, self.IDENT_BLOCKS, out.ctypes.data,
+                                                    int(num_threads)), "dz_tune_ident_score_core")
+        else:
+            _lib.check(lib.dz_tune_ident_score(T, self.N, bits.ctypes.data, ident.ctypes.data, self.total_rows, total,
+                                               p("file_row_off"), p("chunk_off"), p("step_rows"), p("mids"), p("mid_cell"),
+                                               p("file_cell_off"), p("cell_dur"), p("cell_ref"), p("cell_step"), self.G,
+                                               PATCH_COLLAR, out.ctypes.data, int(num_threads)), "dz_tune_ident_score")
+        return out
+
+    def evaluate(self, hparams, backend: Optional[str] = None, memory_budget: int = 1 << 30,
+                 num_threads: int = 8) -> TuneResult:
+        """The identification error rate of every trial of ``hparams (T, 4)`` = (tau_active, rho_update, delta_new,
+        delta_id), trials in batches whose results fit ``memory_budget`` bytes (``bytes_per_trial`` each).  Scored
+        where it is replayed: ``backend="gpu"`` leaves ``T x N x 5`` doubles and the statuses; "host": the clustering
+        and the tail through their handles, the names and the score on host threads; "core": the kernels' text on host
+        threads.  A trial whose chain stopped has rate NaN."""
+        hp = self._hparams4(hparams)
+        backend = backend or self.default_backend()
+        if backend not in ("gpu", "host", "core"):
+            raise ValueError(f"backend '{backend}': gpu, host or core")
+        self._check_steps()
+        per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
+        per_file, status = [], []
+        for a in range(0, hp.shape[0], per_batch):
+            h3, delta = np.ascontiguousarray(hp[a:a + per_batch, :3]), hp[a:a + per_batch, 3]
+            if backend == "gpu":
+                assign, st, bits = self._replay_gpu(h3)
+                ident, _ = self._names_gpu(assign, st, delta)
+                out, err = self._ident_score_gpu(bits, ident)
+                rc = int(err.cpu()[0])
+                if rc:
+                    raise _lib.DiartAmdError(f"dz_tune_ident_score_gpu failed (code {rc}): "
+                                             f"{self._IDENT_ERRORS.get(rc, 'unknown')}")
+                per_file.append(out.cpu().numpy())
+                status.append(st.cpu().numpy())
+                continue
+            assign, st, bits = TuneCache.replay(self, h3, backend, num_threads)
+            ident, _ = self._names_host(assign, st, delta, False, num_threads)
+            per_file.append(self._ident_score_host(bits, ident, backend == "core", num_threads))
+            status.append(st)
+        per_file, status = np.concatenate(per_file), np.concatenate(status)
+        comp = per_file.sum(axis=1)
+        rate = np.where((status >= 0).any(axis=1), np.nan, _rates(comp))
+        return TuneResult(rate, comp, per_file, status)
+
+    def score(self, *args, **kw):
+        raise TypeError("IdentTuneCache scores names, not an optimal mapping: evaluate(hparams (T, 4)); the diarization "
+                        "error rate of the same outputs is the TuneCache's it was made from")
+
+    def hypothesis(self, bits_row: np.ndarray, hold_row: np.ndarray, n: int) -> Annotation:
+        """File n's NAMED hypothesis under one trial (``bits_row``, ``hold_row (chunks, G)`` of ``replay_names``): the
+        turns of ``TuneCache.hypothesis`` cut at the steps' first frame middles, every piece labelled with the name its
+        speaker carries in the step that owns it, or ``speaker{g}``."""
+        self._check_steps()
+        c0, c1 = int(self.chunk_off[n]), int(self.chunk_off[n + 1])
+        b = self.mids[self.row_off[c0:c1] + np.arange(c0, c1)]
+        ann = Annotation(uri=self.files[n]["uri"], modality="speech")
+        for i, (seg, _, label) in enumerate(TuneCache.hypothesis(self, bits_row, n).itertracks(yield_label=True)):
+            g = int(label[len("speaker"):])
+            cuts = [seg.start] + [float(x) for x in b[1:] if seg.start < x < seg.end] + [seg.end]
+            for j, (s, e) in enumerate(zip(cuts[:-1], cuts[1:])):
+                c = min(max(int(np.searchsorted(b, s, side="right")) - 1, 0), c1 - c0 - 1)
+                v = int(hold_row[c0 + c][g])
+                ann[Segment(s, e), f"{i}_{j}"] = self.names[v] if v >= 0 else label
+        return ann
 
 
 class _TrackTuneCache(_ReplayCache):
@@ -797,7 +1087,8 @@ class VadTuneCache(_TrackTuneCache):
 
     @classmethod
     def _check_kind(cls, path, kind: Optional[str]) -> None:
-        raise ValueError(f"{path} holds a TuneCache (SpeakerDiarization), not a VadTuneCache")
+        holds = "TuneCache (SpeakerDiarization)" if kind is None else kind
+        raise ValueError(f"{path} holds a {holds}, not a VadTuneCache")
 
     @classmethod
     def from_tune_cache(cls, cache: "TuneCache", tau_active: Optional[float] = None) -> "VadTuneCache":
@@ -904,32 +1195,61 @@ class Optimizer:
     metric is the detection error rate and the cache a ``VadTuneCache`` — or ``OverlappedSpeechDetection``:
     ``tau_active`` alone, an ``OsdTuneCache``, and as the metric ``OverlapDetectionErrorRate`` (the default) or, with
     ``direction="maximize"``, ``OverlapDetectionFMeasure``: the objective is then ``100 * F`` of the components summed
-    over the files (``metrics.detection_prf``)."""
+    over the files (``metrics.detection_prf``).  ``gallery``: a ``SpeakerGallery`` (``SpeakerDiarization`` only) — then
+    ``delta_id`` is tuned beside the three (``blocks.base.DeltaId``), the cache is an ``IdentTuneCache`` (a ``TuneCache``
+    is matched against the gallery on first use), the metric is the ``IdentificationErrorRate`` and ``delta_id=`` is
+    required: the value of the kick-start trial, and of every trial when ``DeltaId`` is not among ``hparams``.  There is
+    no default."""
 
     def __init__(self, pipeline_class: type, speech_path, reference_path, study_or_path, batch_size: int = 32,
                  hparams: Optional[Sequence[base.HyperParameter]] = None, base_config=None,
                  do_kickstart_hparams: bool = True, metric=None, direction: str = "minimize", sampler: str = "random",
                  seed: int = 0, trials_per_batch: int = 256, cache=None, backend: Optional[str] = None,
-                 scoring: Optional[str] = None):
+                 scoring: Optional[str] = None, gallery=None, delta_id=None):
         self.kind = _replay_kind(pipeline_class)
         track = self.kind != "dia"                 # a track pipeline: tau_active alone, scored where it is replayed
         if scoring not in (None, "host", "device"):
             raise ValueError(f"scoring '{scoring}': host or device")
+        self.gallery, self.delta_id = gallery, None
+        if gallery is not None:
+            if track:
+                raise ValueError(f"gallery=: {pipeline_class.__name__} has no speakers to name; only SpeakerDiarization is "
+                                 "tuned against a gallery")
+            if scoring is not None:
+                raise ValueError("scoring: with gallery= the trials are scored where they are replayed (backend), like the "
+                                 "track pipelines")
+            from .gallery import check_delta_id
+            self.delta_id = check_delta_id(delta_id, "Optimizer(gallery=...)")
+            self.kind = "ident"
+        elif delta_id is not None:
+            raise ValueError("delta_id= is the identification distance of gallery=, which is not given")
+        elif isinstance(metric, IdentificationErrorRate):
+            raise ValueError("metric IdentificationErrorRate compares names: it needs gallery= (a SpeakerGallery) and "
+                             "delta_id=")
         if track and scoring is not None:
             raise ValueError(f"scoring: {pipeline_class.__name__} is scored where it is replayed (backend); only "
                              "SpeakerDiarization takes scoring='host' or 'device'")
         self.scoring = scoring
-        self.cache_class = {"dia": TuneCache, "vad": VadTuneCache, "osd": OsdTuneCache}[self.kind]
-        self.tunable = VAD_TUNABLE if track else TUNABLE
-        if cache is not None and not isinstance(cache, self.cache_class):
+        self.cache_class = {"dia": TuneCache, "ident": IdentTuneCache, "vad": VadTuneCache, "osd": OsdTuneCache}[self.kind]
+        self.tunable = VAD_TUNABLE if track else IDENT_TUNABLE if gallery is not None else TUNABLE
+        if gallery is not None and type(cache) is TuneCache:
+            pass                                   # matched against the gallery on first use (the cache property)
+        elif gallery is not None and isinstance(cache, IdentTuneCache) and cache.names != tuple(gallery.names):
+            raise ValueError("cache: this IdentTuneCache was matched against another gallery (other names) than gallery=")
+        elif gallery is None and isinstance(cache, IdentTuneCache):
+            raise ValueError("cache: an IdentTuneCache is tuned with gallery= and delta_id=; the TuneCache it was made "
+                             "from tunes the diarization error rate")
+        elif cache is not None and not isinstance(cache, self.cache_class):
             raise ValueError(f"pipeline class {pipeline_class.__name__}: cache must be a {self.cache_class.__name__}, "
                              f"got a {type(cache).__name__}")
         self.pipeline_class = pipeline_class
         self.speech_path, self.reference_path, self.batch_size = speech_path, reference_path, batch_size
-        wanted = {"dia": DiarizationErrorRate, "vad": DetectionErrorRate, "osd": OverlapDetectionErrorRate}[self.kind]
+        wanted = {"dia": DiarizationErrorRate, "ident": IdentificationErrorRate, "vad": DetectionErrorRate,
+                  "osd": OverlapDetectionErrorRate}[self.kind]
         self.fmeasure = self.kind == "osd" and isinstance(metric, OverlapDetectionFMeasure)
         if metric is not None and not isinstance(metric, wanted) and not self.fmeasure:
-            raise ValueError(f"metric {type(metric).__name__}: the replay of {pipeline_class.__name__} scores the "
+            raise ValueError(f"metric {type(metric).__name__}: the replay of {pipeline_class.__name__} "
+                             f"{'with a gallery ' if gallery is not None else ''}scores the "
                              f"{wanted.name} ({wanted.__name__}) only"
                              + (", or OverlapDetectionFMeasure with direction='maximize'" if self.kind == "osd" else ""))
         if direction not in ("minimize", "maximize"):
@@ -945,13 +1265,17 @@ class Optimizer:
         if self.base_config is None:
             self.base_config = pipeline_class.get_config_class()()
             self.do_kickstart_hparams = False
-        self.hparams = list(pipeline_class.hyper_parameters() if hparams is None else hparams)
+        default = list(pipeline_class.hyper_parameters()) + ([base.DeltaId] if gallery is not None else [])
+        self.hparams = list(default if hparams is None else hparams)
         possible = vars(self.base_config)
         for param in self.hparams:
+            if param.name == "delta_id" and gallery is None:
+                raise ValueError("hyper-parameter delta_id is the identification distance of a gallery: gallery= and "
+                                 "delta_id= are not given")
             if param.name not in self.tunable:
                 raise ValueError(f"hyper-parameter {param.name} changes the model outputs: only "
                                  f"{', '.join(self.tunable)} are tuned by replaying them")
-            assert param.name in possible, (f"Hyper-parameter {param.name} not found in configuration "
+            assert param.name in possible or param.name == "delta_id", (f"Hyper-parameter {param.name} not found in configuration "
                                             f"{self.base_config.__class__.__name__}")
         if not track and int(self.base_config.max_speakers) > MAX_SPEAKERS:
             raise ValueError(f"max_speakers = {self.base_config.max_speakers}: the replay keeps one 32-bit mask per "
@@ -975,8 +1299,11 @@ class Optimizer:
     @property
     def cache(self):
         if self._cache is None:
+            kw = {} if self.gallery is None else dict(gallery=self.gallery)
             self._cache = self.cache_class.collect(self.pipeline_class, self.base_config, self.speech_path, self.reference_path,
-                                            self.batch_size)
+                                            self.batch_size, **kw)
+        if self.gallery is not None and type(self._cache) is TuneCache:
+            self._cache = self._cache.with_gallery(self.gallery)
         return self._cache
 
     def _complete(self) -> List[dict]:
@@ -1001,7 +1328,11 @@ class Optimizer:
     def _values(self, params: Dict[str, float]) -> List[float]:
         """(tau, rho, delta) of a trial ((tau) of a track pipeline): the sampled parameters, the base config's
         value for the others."""
-        return [float(params.get(name, getattr(self.base_config, name))) for name in self.tunable]
+        return [float(params.get(name, self._base_value(name))) for name in self.tunable]
+
+    def _base_value(self, name: str) -> float:
+        """The base configuration's value; delta_id is no field of a configuration: the constructor's."""
+        return self.delta_id if name == "delta_id" else getattr(self.base_config, name)
 
     def objective(self, params: Sequence[Dict[str, float]]) -> np.ndarray:
         """The metric in percent of every trial of ``params`` (NaN where the clustering would raise); with an
@@ -1035,7 +1366,7 @@ class Optimizer:
     def __call__(self, num_iter: int, show_progress: bool = True):
         queue: List[Dict[str, float]] = []
         if self.do_kickstart_hparams:
-            kick = {p.name: float(getattr(self.base_config, p.name)) for p in self.hparams}
+            kick = {p.name: float(self._base_value(p.name)) for p in self.hparams}
             if not any(t["params"] == kick for t in self.trials):
                 queue.append(kick)
         if self.sampler == "grid":

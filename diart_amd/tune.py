@@ -6,7 +6,11 @@ DIR`` holds ``DIR/<stem>.json`` with every trial, and a second run continues it.
 VoiceActivityDetection`` tunes tau_active of that pipeline against the detection error rate (``optim.VadTuneCache``;
 the embedding and the clustering arguments are ignored).  ``--pipeline OverlappedSpeechDetection`` tunes tau_active of
 that pipeline (``optim.OsdTuneCache``, the same arguments ignored) against the overlap detection error rate, or with
-``--objective fmeasure`` for the largest detection F-measure, the objective pyannote tunes this task on."""
+``--objective fmeasure`` for the largest detection F-measure, the objective pyannote tunes this task on.
+``--gallery FILE --delta-id VALUE`` (``SpeakerDiarization`` only) tunes ``delta_id``, the distance under which a speaker
+takes the name of a voiceprint of the ``SpeakerGallery`` in FILE, beside the three, against the identification error rate
+(``optim.IdentTuneCache``): the RTTM labels are then compared with the gallery's names as they are.  ``--delta-id`` has no
+default: it is the kick-start trial's value and, when ``--hparams`` leaves ``delta_id`` out, every trial's."""
 from __future__ import annotations
 
 import argparse
@@ -18,7 +22,7 @@ from .blocks.diarization import SpeakerDiarization, SpeakerDiarizationConfig
 from .blocks.osd import OverlappedSpeechDetection
 from .blocks.vad import VoiceActivityDetection
 from .metrics import OverlapDetectionFMeasure
-from .optim import Optimizer, OsdTuneCache, TuneCache, VadTuneCache
+from .optim import IdentTuneCache, Optimizer, OsdTuneCache, TuneCache, VadTuneCache
 
 
 def parser() -> argparse.ArgumentParser:
@@ -49,7 +53,12 @@ def parser() -> argparse.ArgumentParser:
                          "device (on the GPU, beside the replay; not with --cpu)")
     ap.add_argument("--hparams", nargs="+", default=None,
                     help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three); "
-                         "tau_active alone with --pipeline VoiceActivityDetection or OverlappedSpeechDetection")
+                         "tau_active alone with --pipeline VoiceActivityDetection or OverlappedSpeechDetection; with --gallery "
+                         "also delta_id (the default is then all four)")
+    ap.add_argument("--gallery", type=str, default=None,
+                    help="A SpeakerGallery file (.npz): tune delta_id too, against the identification error rate")
+    ap.add_argument("--delta-id", type=float, default=None,
+                    help="Base value of delta_id; required with --gallery, there is no default")
     ap.add_argument("--objective", default="der", choices=("der", "fmeasure"),
                     help="der: minimise the pipeline's error rate (the default); fmeasure: maximise the detection "
                          "F-measure (--pipeline OverlappedSpeechDetection only)")
@@ -71,6 +80,16 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
     if args.objective == "fmeasure" and not osd:
         raise SystemExit(f"--objective fmeasure is the detection F-measure of OverlappedSpeechDetection; --pipeline "
                          f"{args.pipeline} is tuned on its error rate (--objective der)")
+    gallery = None
+    if args.gallery is not None or args.delta_id is not None:
+        if vad:
+            raise SystemExit(f"--gallery names the speakers of SpeakerDiarization; --pipeline {args.pipeline} has none")
+        if args.gallery is None or args.delta_id is None:
+            raise SystemExit("--gallery FILE and --delta-id VALUE go together (delta_id has no default)")
+        if args.scoring is not None:
+            raise SystemExit("--scoring: with --gallery the trials are scored where they are replayed")
+        from .gallery import SpeakerGallery
+        gallery = SpeakerGallery.load(args.gallery)
     if models is not None:
         seg, emb = models
     else:
@@ -88,7 +107,10 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
             tau_active=args.tau_active, rho_update=args.rho_update, delta_new=args.delta_new, gamma=args.gamma,
             beta=args.beta, max_speakers=args.max_speakers, normalize_embedding_weights=args.normalize_embedding_weights,
             device=None)
-    possible = pipeline_class.hyper_parameters()
+    possible = list(pipeline_class.hyper_parameters())
+    if gallery is not None:
+        from .blocks.base import DeltaId
+        possible, cache_class = possible + [DeltaId], IdentTuneCache
     names = args.hparams or [hp.name for hp in possible]
     hparams = [hp for hp in (HyperParameter.from_name(name) for name in names) if hp in possible]
     if not hparams:
@@ -98,6 +120,8 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
     if args.cache and Path(args.cache).exists():
         cache = cache_class.load(args.cache)
     objective = dict(metric=OverlapDetectionFMeasure(), direction="maximize") if args.objective == "fmeasure" else {}
+    if gallery is not None:
+        objective = dict(gallery=gallery, delta_id=args.delta_id)
     opt = Optimizer(pipeline_class, args.root, args.reference, Path(args.output).expanduser(),
                     batch_size=args.batch_size, hparams=hparams, base_config=base_config, sampler=args.sampler,
                     seed=args.seed, trials_per_batch=args.trials_per_batch, cache=cache,

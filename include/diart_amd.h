@@ -1115,6 +1115,59 @@ int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, doub
                      const double* mids, const int* mid_cell, const int* file_cell_off,
                      const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
                      int num_threads);
+/* Tuning delta_id, the identification distance of a speaker gallery.  A trial's names are the
+ * rule of the live engines replayed over the assignments dz_tune_replay wrote: per global speaker the closest
+ * match so far, a step's local speaker k with assign = g, match_index = e >= 0 and
+ * (double)match_distance <= delta_id replacing it when match_distance < best (float32, strictly); g carries the
+ * name of its voiceprint unless another speaker holds the same one with a lower best distance (ties: the lower
+ * g).  match_index / match_distance (chunks, k_local): the stored match of every embedding row against the
+ * gallery (-1 / NaN: none), the same for every trial; vp_ref (N, voiceprints) int8: the reference bit of file n
+ * whose label is voiceprint v's name, or -1; delta_id (T).  ident (T, chunks, max_speakers) int8: the reference
+ * bit of the name speaker g carries in that step, or -1 (no name, or a name no reference label of the file has);
+ * hold (T, chunks, max_speakers) int32, if not NULL: the voiceprint itself, or -1.  A chain takes nothing from
+ * its status chunk on.  dz_tune_name: device memory, one wavefront per (trial, file) chain, name_blocks
+ * workgroups resident; enqueued on `stream`, no synchronisation.  Refused with 2 before anything runs: a NULL
+ * pointer (d_hold excepted), trials < 1, max_speakers > 32, voiceprints < 1.                              */
+int dz_tune_name(dz_ctx* ctx, int trials, int n_files, int total_chunks, int k_local, int max_speakers,
+                 int voiceprints, const int* d_file_chunk_off, const signed char* d_assign, const int* d_status,
+                 const int* d_match_index, const float* d_match_distance, const signed char* d_vp_ref,
+                 const double* d_delta_id, signed char* d_ident, int* d_hold, int name_blocks, void* stream);
+/* The same from host memory, compiled from the text of the kernel, chains on num_threads host threads.     */
+int dz_tune_name_host(int trials, int n_files, int total_chunks, int k_local, int max_speakers, int voiceprints,
+                      const int* file_chunk_off, const signed char* assign, const int* status,
+                      const int* match_index, const float* match_distance, const signed char* vp_ref,
+                      const double* delta_id, signed char* ident, int* hold, int num_threads);
+/* Identification error rate components of every (trial, file) pair: dz_tune_score's turns, merging and cells,
+ * but the labels are compared as they are (no mapping).  cell_step (cells): the step (chunk of the cache) that
+ * owns each cell (step c owns the cells from its first frame middle to the next step's); a set bit g of a cell's
+ * hypothesis mask stands for ident[step][g].  Per cell with Nref reference labels, Nhyp hypothesis labels and
+ * Nboth in both: total += dur Nref, correct += dur Nboth, false alarm += dur max(0, Nhyp - Nref),
+ * missed detection += dur max(0, Nref - Nhyp), confusion += dur (min(Nref, Nhyp) - Nboth).  out (T, N, 5).
+ * 4 = a turn or a step off the file's cells.                                                              */
+int dz_tune_ident_score(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
+                        int total_chunks, const int* file_row_off, const int* file_chunk_off,
+                        const int* step_rows, const double* mids, const int* mid_cell, const int* file_cell_off,
+                        const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
+                        int max_speakers, double collar, double* out, int num_threads);
+/* dz_tune_ident_score on the device, as dz_tune_score_gpu is dz_tune_score's: one workgroup per pair,
+ * score_blocks of them resident on their slices of d_scratch (score_blocks, max_cells + 1) uint32; the sums
+ * per lane, the lanes in order (the same doubles on every call).  d_err: one int, 0 after the call, or 4 / 2 as
+ * dz_tune_score_gpu.  Enqueued on `stream`, no synchronisation.                                            */
+int dz_tune_ident_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits,
+                            const signed char* d_ident, int total_rows, int total_chunks,
+                            const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
+                            const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
+                            const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
+                            int max_speakers, double collar, double* d_out, unsigned* d_scratch, int score_blocks,
+                            int* d_err, void* stream);
+/* The same from host memory, compiled from the text of the kernel (the lanes of a workgroup played in order,
+ * as dz_tune_score_core).                                                                                  */
+int dz_tune_ident_score_core(int trials, int n_files, const unsigned* bits, const signed char* ident,
+                             int total_rows, int total_chunks, const int* file_chunk_off, const int* row_off,
+                             const double* mids, const int* mid_cell, const int* file_cell_off,
+                             const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
+                             int max_cells, int max_speakers, double collar, int lanes, int score_blocks,
+                             double* out, int num_threads);
 
 /* sizeof() of the five structs that cross this boundary, in declaration order
  * (dz_sincnet_weights, dz_seg_weights, dz_emb_weights, dz_ecapa_weights, dz_convgemm_desc): a
