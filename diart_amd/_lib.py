@@ -278,6 +278,11 @@ SIGNATURES = {
     "dz_gallery_size": (C.c_int, [vp]),
     "dz_gallery_dim": (C.c_int, [vp]),
     "dz_gallery_match": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, vp, vp]),
+    "dz_gallery_set_cohort": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+    "dz_gallery_cohort_size": (C.c_int, [vp]),
+    "dz_gallery_cohort_stats": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, vp]),
+    "dz_gallery_entry_stats": (C.c_int, [vp, vp, vp]),
+    "dz_gallery_match_norm": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, vp, vp]),
     # kernel-level entry points
     "dz_k_convgemm": (C.c_int, [vp, vp, vp]),
     "dz_k_gemm_f32": (C.c_int, [vp, vp, vp]),

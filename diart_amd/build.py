@@ -19,7 +19,7 @@ LIB_EXPERIMENTS = HERE / "libdiart_amd_exp.so"
 SOURCES = ["api.hip", "seg_api.hip", "xvec_api.hip", "kernel_api.hip", "ecapa_api.hip", "k_front.hip", "k_convgemm.hip", "k_gemm_f32.hip", "k_gemm_split.hip", "k_gemm_pre.hip",
            "k_mlp_head.hip", "k_conv_pool.hip", "k_lstm.hip", "k_lstm_mfma.hip", "k_pool.hip",
            "k_ecapa.hip", "ecm_api.hip", "k_ecapa_mel.hip", "sbx_api.hip", "titanet_api.hip", "k_titanet.hip", "sbr_api.hip", "k_sb_resnet.hip", "wespeaker_api.hip", "k_wespeaker.hip", "k_conv2d.hip", "k_resample.hip", "k_volume.hip", "k_rows_repeat.hip", "k_gather.hip", "resample_api.hip", "ring.hip", "cluster.cpp", "tail.cpp", "hostpool.cpp", "filebatch.cpp", "k_tune.hip", "k_tune_vad.hip", "k_tune_score.hip", "k_tune_ident.hip", "tune_score.cpp",
-           "gallery_api.hip", "k_gallery.hip"]
+           "gallery_api.hip", "k_gallery.hip", "k_cohort.hip"]
 # -DDZ_EXPERIMENTS only (csrc/dz_common.h "build flavours"): the never-default GEMM generations
 EXPERIMENT_SOURCES = ["experiments/k_gemm_g2.hip", "experiments/k_gemm_g3.hip"]
 ARCH = "gfx950"

@@ -739,6 +739,18 @@ int dz_gallery_tiles(int E);
 int dz_launch_gallery_match(const float* X, long long stride, int R, int D, const float* G, int E, float* norm,
                             int* p_idx, float* p_best, float* p_second, int* index, float* dist, float* second,
                             hipStream_t st);
+int dz_launch_gallery_norm(const float* X, long long stride, int R, int D, float* norm, hipStream_t st);
+int dz_launch_gallery_reduce(const float* norm, int R, int E, const int* p_idx, const float* p_best,
+                             const float* p_second, int* index, float* dist, float* second, hipStream_t st);
+// k_cohort.hip: the statistics of R rows against a cohort C (M, D) of unit rows, in passes of DZ_COHORT_PASS rows over a
+// scratch of DZ_COHORT_PASS x dz_cohort_ld(M) floats, and the gallery's tile launch with the normalising epilogue
+constexpr int DZ_COHORT_PASS = 256;
+int dz_cohort_ld(int M);
+int dz_launch_cohort_stats(const float* X, long long stride, int R, int D, const float* C, int M, int top_n,
+                           const float* norm, float* dist, float* mean, float* sd, float* inv, hipStream_t st);
+int dz_launch_gallery_tile_norm(const float* X, long long stride, int R, int D, const float* G, int E,
+                                const float* norm, const float* mu_g, const float* inv_g, const float* mu_x,
+                                const float* inv_x, int* p_idx, float* p_best, float* p_second, hipStream_t st);
 
 struct dz_ctx {
     int device;

@@ -266,3 +266,18 @@ int dz_launch_gallery_match(const float* X, long long stride, int R, int D, cons
     DZ_HIP(hipGetLastError());
     return 0;
 }
+
+// the first and the last launch alone, for the normalised match (k_cohort.hip), whose tile kernel lies between them
+int dz_launch_gallery_norm(const float* X, long long stride, int R, int D, float* norm, hipStream_t st) {
+    DZ_LAUNCH(gallery_norm_kernel, dim3((R + 3) / 4), dim3(256), 0, st, X, stride, R, D, norm);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}
+
+int dz_launch_gallery_reduce(const float* norm, int R, int E, const int* p_idx, const float* p_best,
+                             const float* p_second, int* index, float* dist, float* second, hipStream_t st) {
+    DZ_LAUNCH(gallery_reduce_kernel, dim3((R + 3) / 4), dim3(256), 0, st, norm, R, dz_gallery_tiles(E), p_idx, p_best,
+              p_second, index, dist, second);
+    DZ_HIP(hipGetLastError());
+    return 0;
+}

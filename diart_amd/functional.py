@@ -310,3 +310,105 @@ def gallery_match(embeddings, voiceprints):
     index = torch.where(bad, torch.full_like(index, -1), index).to(torch.int32)
     return (index.reshape(lead), torch.where(bad, nan, dist).to(torch.float32).reshape(lead),
             torch.where(bad, nan, second).to(torch.float32).reshape(lead))
+
+
+SIGMA_FLOOR = 1e-3      # a guard against dividing by zero (top_n == 1, a degenerate cohort), not a tuned value
+
+
+def _cohort_stats64(x, c, top_n):
+    """x (R, D), c (M, D) float64 -> (mean, std) of the top_n NEAREST cohort members of every row."""
+    d = 1 - (x @ c.T) / (x.norm(dim=1, keepdim=True) * c.norm(dim=1)[None])
+    near = d.topk(top_n, dim=1, largest=False).values
+    return near.mean(dim=1), near.std(dim=1, unbiased=False).clamp_min(SIGMA_FLOOR)
+
+
+def _cohort_args(embeddings, cohort, top_n, who, voiceprints=None):
+    import numpy as np
+    c = cohort if isinstance(cohort, torch.Tensor) else torch.from_numpy(np.asarray(cohort))
+    g = voiceprints
+    if g is not None and not isinstance(g, torch.Tensor):
+        g = torch.from_numpy(np.asarray(g))
+    D = embeddings.shape[-1] if embeddings.ndim >= 1 else -1
+    if (c.ndim != 2 or c.shape[0] < 1 or c.shape[1] != D or embeddings.numel() == 0
+            or (g is not None and (g.ndim != 2 or g.shape[0] < 1 or g.shape[1] != D))):
+        raise ValueError(f"{who}: embeddings of shape {tuple(embeddings.shape)} against "
+                         + (f"voiceprints of shape {tuple(g.shape)} and " if g is not None else "")
+                         + f"a cohort of shape {tuple(c.shape)}")
+    if int(top_n) != top_n or not 1 <= int(top_n) <= c.shape[0]:
+        raise ValueError(f"{who}: top_n={top_n!r} (1 .. the cohort's {c.shape[0]} rows)")
+    return c, g, int(top_n)
+
+
+def _unusable(x):
+    """x (R, D) float64 -> (bad (R,), x with the unusable rows replaced by ones): the gallery's rule."""
+    norm = x.norm(dim=1)
+    bad = ~torch.isfinite(x).all(dim=1) | (norm == 0) | ~torch.isfinite(norm)
+    return bad, torch.where(bad[:, None], torch.ones_like(x), x)
+
+
+def cohort_stats(embeddings, cohort, top_n):
+    """Mean and population standard deviation of the cosine distances of every row of ``embeddings (..., D)`` to its
+    ``top_n`` NEAREST rows of ``cohort (M, D)`` -> ``(mean f32, std f32)`` shaped ``(...)``.  On float64:
+
+        d = 1 - (x @ c.T) / (x.norm(dim=1, keepdim=True) * c.norm(dim=1)[None])
+        near = d.topk(top_n, dim=1, largest=False).values
+        mean, std = near.mean(dim=1), near.std(dim=1, unbiased=False).clamp_min(1e-3)
+
+    (the floor guards a division, it is no tuned value); a row with a NaN / Inf element or of zero norm gets NaN.  A CPU
+    tensor or a numpy array gets exactly that statement, rounded to float32.  A CUDA tensor runs the kernels of
+    ``csrc/k_cohort.hip`` (``dz_gallery_cohort_stats``; M <= 8 192) on a gallery built for this call."""
+    import numpy as np
+    if not isinstance(embeddings, torch.Tensor):
+        return tuple(t.numpy() for t in cohort_stats(torch.from_numpy(np.asarray(embeddings)), cohort, top_n))
+    c, _, top_n = _cohort_args(embeddings, cohort, top_n, "cohort_stats")
+    if embeddings.is_cuda:
+        from .gallery import SpeakerGallery
+        c = c.detach().cpu()
+        return SpeakerGallery(["voiceprint 0"], c[:1], embeddings.device, cohort=c, top_n=top_n).cohort_stats(embeddings)
+    lead = embeddings.shape[:-1]
+    bad, x = _unusable(embeddings.reshape(-1, c.shape[1]).to(torch.float64))
+    mean, std = _cohort_stats64(x, c.detach().cpu().to(torch.float64), top_n)
+    nan = torch.full_like(mean, float("nan"))
+    return (torch.where(bad, nan, mean).to(torch.float32).reshape(lead),
+            torch.where(bad, nan, std).to(torch.float32).reshape(lead))
+
+
+def gallery_match_normalised(embeddings, voiceprints, cohort, top_n=300):
+    """``gallery_match`` by the distance normalised against a cohort of impostors (adaptive s-norm) ->
+    ``(index int32, distance f32, second f32)`` shaped ``(...)``.  On float64, with ``cohort_stats`` as above,
+
+        mu_x, sd_x = cohort_stats(x, c, top_n)              # per embedding row
+        mu_g, sd_g = cohort_stats(g, c, top_n)              # per voiceprint
+        d  = 1 - (x @ g.T) / (x.norm(dim=1, keepdim=True) * g.norm(dim=1)[None])
+        dn = 0.5 * ((d - mu_g[None]) / sd_g[None] + (d - mu_x[:, None]) / sd_x[:, None])
+        index = dn.argmin(dim=1)                            # the lowest index among equal values
+
+    ``dn`` is minus the AS-norm score of the similarity ``1 - d``: signed, lower is closer; a true match is typically
+    several units below zero, an impostor near or above zero.  ``distance`` is ``dn`` at ``index``, ``second`` the
+    smallest ``dn`` among the other voiceprints (+inf when E == 1); an unusable row gets -1 / NaN / NaN.  ``top_n``
+    = 300 is the value of the published recipes, not measured here.  A CPU tensor or a numpy array gets exactly that
+    statement, rounded to float32; a CUDA tensor runs ``dz_gallery_match_norm`` (``csrc/k_cohort.hip``) on a gallery
+    built for this call; to match step after step keep a ``gallery.SpeakerGallery`` with a cohort."""
+    import numpy as np
+    if not isinstance(embeddings, torch.Tensor):
+        out = gallery_match_normalised(torch.from_numpy(np.asarray(embeddings)), voiceprints, cohort, top_n)
+        return tuple(t.numpy() for t in out)
+    c, g, top_n = _cohort_args(embeddings, cohort, top_n, "gallery_match_normalised", voiceprints)
+    if embeddings.is_cuda:
+        from .gallery import SpeakerGallery
+        names = [f"voiceprint {e}" for e in range(g.shape[0])]
+        return SpeakerGallery(names, g, embeddings.device, cohort=c.detach().cpu(), top_n=top_n).match_normalised(embeddings)
+    lead = embeddings.shape[:-1]
+    bad, x = _unusable(embeddings.reshape(-1, g.shape[1]).to(torch.float64))
+    g, c = g.detach().cpu().to(torch.float64), c.detach().cpu().to(torch.float64)
+    mu_x, sd_x = _cohort_stats64(x, c, top_n)
+    mu_g, sd_g = _cohort_stats64(g, c, top_n)
+    d = 1 - (x @ g.T) / (x.norm(dim=1, keepdim=True) * g.norm(dim=1)[None])
+    dn = 0.5 * ((d - mu_g[None]) / sd_g[None] + (d - mu_x[:, None]) / sd_x[:, None])
+    index = dn.argmin(dim=1)
+    dist = dn.gather(1, index[:, None])[:, 0]
+    second = dn.scatter(1, index[:, None], float("inf")).min(dim=1).values
+    nan = torch.full_like(dist, float("nan"))
+    index = torch.where(bad, torch.full_like(index, -1), index).to(torch.int32)
+    return (index.reshape(lead), torch.where(bad, nan, dist).to(torch.float32).reshape(lead),
+            torch.where(bad, nan, second).to(torch.float32).reshape(lead))

@@ -9,7 +9,13 @@ global speaker it keeps the closest match seen so far and hands out each voicepr
 ``StreamServer.set_gallery`` attach a gallery to live streams.
 
 There is no default identification threshold: the right ``delta_id`` depends on the embedding model and has not been
-measured on real checkpoints here, so every caller gives it."""
+measured on real checkpoints here, so every caller gives it.
+
+A gallery may carry a COHORT of impostor voiceprints (``cohort=``, ``with_cohort``).  ``match_normalised`` then
+expresses every distance in standard deviations of the distances that its two sides get against their ``top_n`` nearest
+cohort members (adaptive s-norm: ``dz_gallery_match_norm``, ``csrc/k_cohort.hip``), a signed quantity
+whose threshold transfers across models and channels far better than a raw distance; the engines use it for a gallery
+with a cohort.  The cohort should not contain the enrolled speakers: that is the caller's business and is not checked."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,34 +28,80 @@ import torch
 from . import _lib
 
 MAX_ROWS, MAX_ENTRIES, MIN_DIM, MAX_DIM = 4096, 65536, 64, 512     # dz_gallery_match's domain (include/diart_amd.h)
+MAX_COHORT, TOP_N = 8192, 300           # dz_gallery_set_cohort's domain; top_n of the published AS-norm recipes
 _RESERVED = re.compile(r"speaker\d+")                               # the labels of speakers nobody has named
 
 
-def check_delta_id(delta_id, who: str) -> float:
+def check_delta_id(delta_id, who: str, signed: bool = False) -> float:
+    """``signed``: the threshold of a normalised distance (a gallery with a cohort), any finite value."""
+    what = "a finite normalised distance" if signed else "a finite distance >= 0"
     try:
         d = float(delta_id)
     except (TypeError, ValueError):
-        raise ValueError(f"{who}: delta_id={delta_id!r} (a finite distance >= 0; there is no default)") from None
-    if not np.isfinite(d) or d < 0:
-        raise ValueError(f"{who}: delta_id={delta_id!r} (a finite distance >= 0; there is no default)")
+        raise ValueError(f"{who}: delta_id={delta_id!r} ({what}; there is no default)") from None
+    if not np.isfinite(d) or (d < 0 and not signed):
+        raise ValueError(f"{who}: delta_id={delta_id!r} ({what}; there is no default)")
     return d
+
+
+def check_cohort(cohort, top_n, D: int, who: str) -> Tuple[np.ndarray, int]:
+    """``cohort`` (M, D) as contiguous float32 rows and ``top_n`` as an int, or a ``ValueError`` by name: what
+    ``dz_gallery_set_cohort`` refuses, before anything touches the GPU."""
+    if isinstance(cohort, torch.Tensor):
+        cohort = cohort.detach().cpu().numpy()
+    rows = np.ascontiguousarray(cohort, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] != D:
+        raise ValueError(f"{who}: a cohort of shape {rows.shape} (expected (M, {D}), the voiceprints' dimension)")
+    M = rows.shape[0]
+    if not 1 <= M <= MAX_COHORT:
+        raise ValueError(f"{who}: a cohort of {M} rows (1 .. {MAX_COHORT})")
+    try:
+        n = int(top_n)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: top_n={top_n!r} (1 .. the cohort's {M} rows)") from None
+    if n != top_n or not 1 <= n <= M:
+        raise ValueError(f"{who}: top_n={top_n!r} (1 .. the cohort's {M} rows)")
+    finite = np.isfinite(rows).all(axis=1)
+    if not finite.all():
+        raise ValueError(f"{who}: cohort row {int(np.argmin(finite))} is not finite")
+    norms = np.sqrt((rows.astype(np.float64) ** 2).sum(axis=1))
+    if not (norms > 0).all():
+        raise ValueError(f"{who}: cohort row {int(np.argmin(norms > 0))} has zero norm")
+    return rows, n
 
 
 class _Handle:
     """One ``dz_gallery`` handle: the voiceprints on the device and the scratch of ONE match at a time (a handle per
     HIP stream that matches)."""
 
-    def __init__(self, rows: np.ndarray, device: torch.device):
+    def __init__(self, rows: np.ndarray, device: torch.device, cohort: Optional[np.ndarray] = None, top_n: int = TOP_N):
         self._lib = _lib.load()
         self.h = _lib.vp()
-        E, D = rows.shape
-        _lib.check(self._lib.dz_gallery_create(_lib.context(device.index), rows.ctypes.data, E, D, C.byref(self.h)),
+        self.E, D = rows.shape
+        _lib.check(self._lib.dz_gallery_create(_lib.context(device.index), rows.ctypes.data, self.E, D, C.byref(self.h)),
                    "dz_gallery_create")
+        if cohort is not None:           # uploads it and computes the voiceprints' statistics (synchronous)
+            _lib.check(self._lib.dz_gallery_set_cohort(self.h, cohort.ctypes.data, cohort.shape[0], int(top_n)),
+                       "dz_gallery_set_cohort")
 
     def match(self, rows_ptr: int, stride: int, R: int, index_ptr: int, dist_ptr: int, second_ptr: int,
               stream: int) -> None:
         _lib.check(self._lib.dz_gallery_match(self.h, rows_ptr, stride, R, index_ptr, dist_ptr, second_ptr, stream),
                    "dz_gallery_match")
+
+    def match_norm(self, rows_ptr: int, stride: int, R: int, index_ptr: int, dist_ptr: int, second_ptr: int,
+                   stream: int) -> None:
+        _lib.check(self._lib.dz_gallery_match_norm(self.h, rows_ptr, stride, R, index_ptr, dist_ptr, second_ptr, stream),
+                   "dz_gallery_match_norm")
+
+    def cohort_stats(self, rows_ptr: int, stride: int, R: int, mean_ptr: int, std_ptr: int, stream: int) -> None:
+        _lib.check(self._lib.dz_gallery_cohort_stats(self.h, rows_ptr, stride, R, mean_ptr, std_ptr, stream),
+                   "dz_gallery_cohort_stats")
+
+    def entry_stats(self) -> Tuple[np.ndarray, np.ndarray]:
+        mean, std = np.empty(self.E, dtype=np.float32), np.empty(self.E, dtype=np.float32)
+        _lib.check(self._lib.dz_gallery_entry_stats(self.h, mean.ctypes.data, std.ctypes.data), "dz_gallery_entry_stats")
+        return mean, std
 
     def __del__(self):
         try:
@@ -58,7 +110,7 @@ class _Handle:
             pass
 
 
-def _match_rows(handle: _Handle, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def _match_rows(handle: _Handle, x: torch.Tensor, normalised: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``x`` (R, D) float32 on the handle's GPU, rows at any stride >= D -> (index int32, distance, second) on that
     GPU, ``MAX_ROWS`` rows per launch, on the current stream."""
     R, D = x.shape
@@ -66,13 +118,28 @@ def _match_rows(handle: _Handle, x: torch.Tensor) -> Tuple[torch.Tensor, torch.T
     dist = torch.empty(R, dtype=torch.float32, device=x.device)
     second = torch.empty(R, dtype=torch.float32, device=x.device)
     stride = x.stride(0) if R > 1 else D
+    match = handle.match_norm if normalised else handle.match
     with torch.cuda.device(x.device):
         st = torch.cuda.current_stream(x.device).cuda_stream
         for r0 in range(0, R, MAX_ROWS):
             n = min(MAX_ROWS, R - r0)
-            handle.match(x.data_ptr() + 4 * r0 * stride, stride, n, index[r0:].data_ptr(), dist[r0:].data_ptr(),
-                         second[r0:].data_ptr(), st)
+            match(x.data_ptr() + 4 * r0 * stride, stride, n, index[r0:].data_ptr(), dist[r0:].data_ptr(),
+                  second[r0:].data_ptr(), st)
     return index, dist, second
+
+
+def _stats_rows(handle: _Handle, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``_match_rows`` for the cohort statistics alone -> (mean, std) float32 on the handle's GPU."""
+    R, D = x.shape
+    mean = torch.empty(R, dtype=torch.float32, device=x.device)
+    std = torch.empty(R, dtype=torch.float32, device=x.device)
+    stride = x.stride(0) if R > 1 else D
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        for r0 in range(0, R, MAX_ROWS):
+            n = min(MAX_ROWS, R - r0)
+            handle.cohort_stats(x.data_ptr() + 4 * r0 * stride, stride, n, mean[r0:].data_ptr(), std[r0:].data_ptr(), st)
+    return mean, std
 
 
 def _rows_2d(embeddings: torch.Tensor, D: int, who: str) -> torch.Tensor:
@@ -92,9 +159,16 @@ class SpeakerGallery:
     is normalised, each voiceprint divided by its float64 norm and rounded to float32 once.  Refused with a
     ``ValueError``: duplicate names, names of the form ``speaker<digits>`` (what unnamed speakers are called),
     non-finite or zero voiceprints, a bad D or E.  Nothing touches the GPU before the first ``match`` (or an engine's
-    ``set_gallery``); ``device=None`` is the current GPU then."""
+    ``set_gallery``); ``device=None`` is the current GPU then.
 
-    def __init__(self, names: Sequence[str], voiceprints, device: Optional[torch.device] = None):
+    ``cohort``: (M, D) impostor voiceprints, 1 <= M <= 8 192, validated and stored like voiceprints, with ``top_n`` in
+    1 .. M (300: the value of the published AS-norm recipes, not measured here) -> ``match_normalised``,
+    ``cohort_stats``, ``entry_stats``; ``match`` stays the raw match.  A cohort is built like a gallery, for example
+    ``SpeakerGallery.enrol(model, impostor_audio).voiceprints``; it should not contain the enrolled speakers (not
+    checked)."""
+
+    def __init__(self, names: Sequence[str], voiceprints, device: Optional[torch.device] = None, cohort=None,
+                 top_n: int = TOP_N):
         if isinstance(voiceprints, torch.Tensor):
             voiceprints = voiceprints.detach().cpu().numpy()
         rows = np.ascontiguousarray(voiceprints, dtype=np.float32)
@@ -128,6 +202,7 @@ class SpeakerGallery:
         norms = np.sqrt((rows.astype(np.float64) ** 2).sum(axis=1))
         if not (norms > 0).all():
             raise ValueError(f"SpeakerGallery: the voiceprint of {names[int(np.argmin(norms > 0))]!r} has zero norm")
+        self._cohort, self._top_n = (None, top_n) if cohort is None else check_cohort(cohort, top_n, D, "SpeakerGallery")
         self._names: Tuple[str, ...] = tuple(names)
         self._rows = rows
         self.device = None if device is None else torch.device(device)
@@ -150,14 +225,30 @@ class SpeakerGallery:
     def __len__(self) -> int:
         return int(self._rows.shape[0])
 
+    @property
+    def cohort(self) -> Optional[np.ndarray]:
+        """The cohort's float32 rows as given (not normalised), or ``None``."""
+        return self._cohort
+
+    @property
+    def top_n(self) -> int:
+        return self._top_n
+
+    def with_cohort(self, cohort, top_n: int = TOP_N) -> "SpeakerGallery":
+        """A new gallery of the same names and voiceprints with this cohort (``None``: without one)."""
+        return SpeakerGallery(self._names, self._rows, self.device, cohort, top_n)
+
     def save(self, path) -> None:
-        """An ``.npz`` of the names and the float32 rows as given."""
+        """An ``.npz`` of the names and the float32 rows as given; with a cohort also its rows and ``top_n``."""
+        extra = {} if self._cohort is None else dict(cohort=self._cohort, top_n=np.asarray(self._top_n, dtype=np.int64))
         with open(path, "wb") as f:
-            np.savez(f, names=np.asarray(self._names, dtype=np.str_), voiceprints=self._rows)
+            np.savez(f, names=np.asarray(self._names, dtype=np.str_), voiceprints=self._rows, **extra)
 
     @staticmethod
     def load(path, device: Optional[torch.device] = None) -> "SpeakerGallery":
         with np.load(path, allow_pickle=False) as z:
+            if "cohort" in z.files:
+                return SpeakerGallery([str(n) for n in z["names"]], z["voiceprints"], device, z["cohort"], int(z["top_n"]))
             return SpeakerGallery([str(n) for n in z["names"]], z["voiceprints"], device)
 
     # ------------------------------------------------------------------ on the device
@@ -174,7 +265,55 @@ class SpeakerGallery:
 
     def new_handle(self, device: Optional[torch.device] = None) -> _Handle:
         """A device copy with scratch of its own (an engine takes one per lane)."""
-        return _Handle(self._rows, self._resolve(device))
+        return _Handle(self._rows, self._resolve(device), self._cohort, self._top_n)
+
+    def _on_device(self, embeddings, who: str):
+        """-> (rows (R, D) on the gallery's GPU, the leading shape, back): ``back`` gives tensors on the GPU their
+        leading shape and the caller's kind (a CPU tensor or numpy array was uploaded and gets its own kind back)."""
+        as_numpy = not isinstance(embeddings, torch.Tensor)
+        x = torch.from_numpy(np.ascontiguousarray(embeddings)) if as_numpy else embeddings
+        src = x.device
+        dev = self._resolve(src if src.type == "cuda" else None)
+        if src.type == "cuda" and src != dev:
+            raise ValueError(f"{who}: embeddings on {src}, the gallery on {dev}")
+        lead = tuple(x.shape[:-1])
+        rows = _rows_2d(x.to(dev), self.dimension, who)
+        if self._handle is None:
+            self._handle = self.new_handle()
+
+        def back(tensors):
+            out = [t.reshape(lead) for t in tensors]
+            if src.type != "cuda":
+                out = [t.cpu() for t in out]                       # (synchronises)
+            return tuple(t.numpy() for t in out) if as_numpy else tuple(out)
+        return rows, back
+
+    def _need_cohort(self, who: str) -> None:
+        if self._cohort is None:
+            raise ValueError(f"{who}: the gallery has no cohort (SpeakerGallery(..., cohort=...) or with_cohort)")
+
+    def match_normalised(self, embeddings):
+        """``match`` by the normalised distance (adaptive s-norm against the cohort; ``functional.
+        gallery_match_normalised`` states it): ``(index int32, distance f32, second f32)`` shaped ``(...)``, the
+        distances signed, lower is closer; -1 / NaN / NaN for an unusable row.  Always the kernels, as ``match``."""
+        self._need_cohort("SpeakerGallery.match_normalised")
+        rows, back = self._on_device(embeddings, "SpeakerGallery.match_normalised")
+        return back(_match_rows(self._handle, rows, normalised=True))
+
+    def cohort_stats(self, embeddings):
+        """``(mean f32, std f32)`` shaped ``(...)``: mean and population standard deviation (never below 1e-3) of the
+        distances of every row of ``embeddings (..., D)`` to its ``top_n`` nearest cohort members; NaN for an unusable
+        row.  The bits of a row's pair depend on the row, the cohort and ``top_n`` only."""
+        self._need_cohort("SpeakerGallery.cohort_stats")
+        rows, back = self._on_device(embeddings, "SpeakerGallery.cohort_stats")
+        return back(_stats_rows(self._handle, rows))
+
+    def entry_stats(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(mean, std)`` of the E voiceprints against the cohort, float32 arrays: computed once per device copy."""
+        self._need_cohort("SpeakerGallery.entry_stats")
+        if self._handle is None:
+            self._handle = self.new_handle()
+        return self._handle.entry_stats()
 
     def match(self, embeddings):
         """The nearest voiceprint of every row of ``embeddings (..., D)`` float32 -> ``(index int32, distance f32,
@@ -182,20 +321,8 @@ class SpeakerGallery:
         distance and the runner-up's (+inf for a gallery of one); -1 / NaN / NaN for a row with a NaN or Inf element or
         of zero norm.  Always the kernel, on the gallery's GPU: a CUDA tensor there gets tensors back (current stream,
         rows at a common stride read in place), a CPU tensor or numpy array is uploaded and gets its own kind back."""
-        as_numpy = not isinstance(embeddings, torch.Tensor)
-        x = torch.from_numpy(np.ascontiguousarray(embeddings)) if as_numpy else embeddings
-        src = x.device
-        dev = self._resolve(src if src.type == "cuda" else None)
-        if src.type == "cuda" and src != dev:
-            raise ValueError(f"SpeakerGallery.match: embeddings on {src}, the gallery on {dev}")
-        lead = tuple(x.shape[:-1])
-        rows = _rows_2d(x.to(dev), self.dimension, "SpeakerGallery.match")
-        if self._handle is None:
-            self._handle = self.new_handle()
-        out = [t.reshape(lead) for t in _match_rows(self._handle, rows)]
-        if src.type != "cuda":
-            out = [t.cpu() for t in out]                       # (synchronises)
-        return tuple(t.numpy() for t in out) if as_numpy else tuple(out)
+        rows, back = self._on_device(embeddings, "SpeakerGallery.match")
+        return back(_match_rows(self._handle, rows))
 
     # ------------------------------------------------------------------ enrolment
     @staticmethod
@@ -248,10 +375,11 @@ class SpeakerNames:
     ``index[k] = e >= 0`` and a distance ``d <= delta_id`` replaces it when ``d < best_d[g]`` (local speakers in
     ascending k).  A stream's labels are ``names[best_e[g]]`` where set; if several g of a stream hold the same
     voiceprint, the one with the lowest ``best_d`` keeps the name (ties: the lowest g) and the others read
-    ``speaker{g}`` for that step, keeping their state.  ``delta_id`` has no default."""
+    ``speaker{g}`` for that step, keeping their state.  ``delta_id`` has no default.  ``signed=True``: the distances
+    are normalised ones (a gallery with a cohort) and any finite ``delta_id`` is a threshold; the rule is the same."""
 
-    def __init__(self, num_streams: int, max_speakers: int, delta_id: float):
-        self.delta_id = check_delta_id(delta_id, "SpeakerNames")
+    def __init__(self, num_streams: int, max_speakers: int, delta_id: float, signed: bool = False):
+        self.delta_id = check_delta_id(delta_id, "SpeakerNames", signed)
         self.n, self.g = int(num_streams), int(max_speakers)
         if self.n < 1 or self.g < 1:
             raise ValueError(f"SpeakerNames: {num_streams} streams of {max_speakers} speakers")

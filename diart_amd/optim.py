@@ -343,7 +343,13 @@ class TuneCache(_ReplayCache):
         """This cache with the match of every cached embedding against ``gallery`` (a ``SpeakerGallery``): an
         ``IdentTuneCache``, which tunes ``delta_id`` beside the three.  The files, the plan and the device copies are
         shared, not copied.  The match is ``gallery.match`` on the GPU when there is one (``device``: which), else
-        ``functional.gallery_match``'s float64 statement rounded to float32."""
+        ``functional.gallery_match``'s float64 statement rounded to float32.  A gallery with a cohort is refused: the
+        live engines match it by the normalised distance, while ``DeltaId``'s range, the replays and the stored
+        ``match_distance`` are all for raw distances."""
+        if getattr(gallery, "cohort", None) is not None:
+            raise ValueError("TuneCache.with_gallery: the gallery has a cohort, so the live engines match it by the "
+                             "normalised distance, and delta_id is tuned on raw distances only; tune gallery."
+                             "with_cohort(None), or set the normalised threshold by hand")
         return IdentTuneCache(self, gallery, device=device)
 
     # ------------------------------------------------------------------------------------------ trial-independent parts

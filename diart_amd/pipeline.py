@@ -494,6 +494,7 @@ class _DiarizationEngine(_StepEngine):
         self.with_tail, self.duration, self.step = bool(tail), float(duration), float(step)
         self.latency = self.step if latency is None else float(latency)
         self._gallery, self._names, self._gallery_handles = None, None, []     # (set_gallery)
+        self._match_norm = False                # the gallery has a cohort: dz_gallery_match_norm, a signed delta_id
 
     def _make_tail(self, F: int) -> Optional[BatchedOutputTail]:
         if not self.with_tail:
@@ -532,13 +533,19 @@ class _DiarizationEngine(_StepEngine):
         assignment); ``diarize`` labels its turns with them.  Each lane gets a handle of its own (a device copy of the
         voiceprints + the scratch of one match).  Refused by name: a gallery of another dimension than the embedding's,
         or on another device.  Setting another gallery (or None) forgets every stream's names; call it with no step
-        between ``launch`` and ``finish``."""
+        between ``launch`` and ``finish``.
+
+        A gallery WITH A COHORT (``SpeakerGallery(..., cohort=...)``) is matched by ``dz_gallery_match_norm`` instead:
+        ``ticket["match"]`` then carries the normalised distances (adaptive s-norm, ``csrc/k_cohort.hip``: signed, lower
+        is closer), ``ticket["match_normalised"]`` is ``True`` and ``delta_id`` is a threshold on that quantity, any
+        finite value.  The rule is the same; a gallery without a cohort takes the raw path and refuses a negative
+        ``delta_id`` as before."""
         who = type(self).__name__
         if gallery is not None:
             from .gallery import SpeakerGallery, SpeakerNames, check_delta_id
             if not isinstance(gallery, SpeakerGallery):
                 raise ValueError(f"{who}.set_gallery: expected a SpeakerGallery or None, got {type(gallery).__name__}")
-            delta = check_delta_id(delta_id, f"{who}.set_gallery")
+            delta = check_delta_id(delta_id, f"{who}.set_gallery", signed=gallery.cohort is not None)
             if gallery.dimension != self.emb.dimension:
                 raise ValueError(f"{who}.set_gallery: the gallery's voiceprints have dimension {gallery.dimension}, the "
                                  f"embedding model's embeddings {self.emb.dimension}")
@@ -547,7 +554,7 @@ class _DiarizationEngine(_StepEngine):
         if any(s["busy"] for s in self._slots):
             raise RuntimeError(f"{who}.set_gallery: a step is between launch and finish")
         torch.cuda.synchronize(self.device)               # no kernel of an older step reads the handles dropped here
-        self._gallery, self._names, self._gallery_handles = None, None, []
+        self._gallery, self._names, self._gallery_handles, self._match_norm = None, None, [], False
         for s in self._slots:
             s.pop("match_h", None)
             s.pop("match", None)
@@ -556,7 +563,8 @@ class _DiarizationEngine(_StepEngine):
         if gallery is None:
             return
         handles = [gallery.new_handle(self.device) for _ in range(self.depth)]
-        self._names = SpeakerNames(self.n, self.max_speakers, delta)
+        self._match_norm = gallery.cohort is not None
+        self._names = SpeakerNames(self.n, self.max_speakers, delta, signed=self._match_norm)
         self._gallery, self._gallery_handles = gallery, handles
         for s in self._slots:
             self._match_buffers(s)
@@ -572,8 +580,9 @@ class _DiarizationEngine(_StepEngine):
         kernel writes its answers to the slot's pinned rows (no copy call: csrc/ring.hip, dz_results_to_host)."""
         K, D = slot["emb"].shape[1:]
         m = slot["match_h"]
-        self._gallery_handles[ln].match(slot["emb"].data_ptr(), D, N * K, m[0].data_ptr(), m[1].data_ptr(),
-                                        m[2].data_ptr(), stream.cuda_stream)
+        h = self._gallery_handles[ln]
+        (h.match_norm if self._match_norm else h.match)(slot["emb"].data_ptr(), D, N * K, m[0].data_ptr(),
+                                                        m[1].data_ptr(), m[2].data_ptr(), stream.cuda_stream)
         slot["matched"] = True
 
     def finish(self, ticket: dict, want_scores: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
@@ -597,6 +606,7 @@ class _DiarizationEngine(_StepEngine):
             if self._gallery is not None and ticket.get("matched"):
                 m = ticket["match_h"].numpy()
                 ticket["match"] = (m[0, :N], m[1, :N].view(np.float32), m[2, :N].view(np.float32))
+                ticket["match_normalised"] = self._match_norm
                 self._names.update(assign, ticket["match"][0], ticket["match"][1], slots)
                 ticket["names"] = self._names.labels(self._gallery.names, slots)
         return seg, emb, scores, assign

@@ -188,7 +188,8 @@ class StreamServer:
     def set_gallery(self, gallery, delta_id=None) -> None:
         """Name the speakers of every stream against ``gallery`` (``gallery.SpeakerGallery``; ``None`` removes it):
         the engine's ``set_gallery``, between two steps.  From the next ``step()`` on the Annotations carry the names
-        where a voiceprint is within ``delta_id`` (no default), and so does everything derived from them: ``close()``
+        where a voiceprint is within ``delta_id`` (no default; a gallery with a cohort is matched by the normalised
+        distance and takes a signed threshold), and so does everything derived from them: ``close()``
         and the websocket messages.  A stream that joins later starts with no names (``open`` resets its slot).  The
         diarization pipeline only: ``"vad"`` and ``"osd"`` have no speakers to name."""
         if self.pipeline in _ONE_TRACK:

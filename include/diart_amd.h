@@ -662,6 +662,35 @@ int dz_gallery_dim(dz_gallery* g);    /* D (0 for NULL) */
 int dz_gallery_match(dz_gallery* g, const float* d_rows, long long row_stride, int R, int* index_out, float* dist_out,
                      float* second_out, void* stream);
 
+/* ---- the match normalised against a cohort of impostors: adaptive s-norm (csrc/k_cohort.hip).
+ * A cohort is M rows of D floats (1 <= M <= 8192), validated and stored like voiceprints (finite, of non-zero norm,
+ * divided by the float64 norm, rounded to float32 once), and top_n in 1 .. M.  For a vector v, (mean, std)(v) are the
+ * mean and the population standard deviation (never below 1e-3) of the top_n SMALLEST of its M cosine distances to the
+ * cohort.  The normalised distance of row x and voiceprint g at raw distance d is
+ *     dn = 0.5 ((d - mean(g)) / std(g) + (d - mean(x)) / std(x))
+ * signed, lower is closer: minus the AS-norm score of the similarity 1 - d.
+ *   dz_gallery_set_cohort    validates, uploads and computes the E voiceprints' statistics (synchronous; no match of
+ *                            the handle may be in flight).  rows == NULL or M == 0 removes the cohort.
+ *   dz_gallery_cohort_size   M (0: no cohort, or NULL).
+ *   dz_gallery_cohort_stats  (mean, std) of R rows, rows and outputs as dz_gallery_match takes them.
+ *   dz_gallery_entry_stats   the E voiceprints' (mean, std) to host memory (synchronous).
+ *   dz_gallery_match_norm    dz_gallery_match with dn in the distance's place: index (lowest among equals), dn there,
+ *                            the smallest dn among the other voiceprints (+inf when E == 1); -1 / NaN / NaN and NaN
+ *                            statistics for an unusable row.  Same domain, outputs and one-match-per-handle rule.
+ * dz_gallery_match stays the raw match on a handle with a cohort.  The bits of (mean, std) depend on the vector, the
+ * stored cohort and top_n only; those of dn on the two vectors, the cohort and top_n only.  Each mean and std is
+ * within (D + 8) 2^-24 + 2^-22 of the float64 value.  Scratch: at most 8 MiB beside the cohort (rows go in passes of
+ * 256).  Status 2 (the message names the function, nothing is launched): NULL arguments; M outside 1 .. 8192; top_n
+ * outside 1 .. M; a cohort row that is not finite or of zero norm (named by index); cohort_stats, entry_stats or
+ * match_norm on a handle without a cohort; the row, stride and alignment checks of dz_gallery_match.              */
+int dz_gallery_set_cohort(dz_gallery* g, const float* rows, int M, int top_n);
+int dz_gallery_cohort_size(dz_gallery* g);
+int dz_gallery_cohort_stats(dz_gallery* g, const float* d_rows, long long row_stride, int R, float* mean_out,
+                            float* std_out, void* stream);
+int dz_gallery_entry_stats(dz_gallery* g, float* mean_host, float* std_host);
+int dz_gallery_match_norm(dz_gallery* g, const float* d_rows, long long row_stride, int R, int* index_out,
+                          float* dist_out, float* second_out, void* stream);
+
 /* ---- repeated rows (csrc/k_rows_repeat.hip) ---------------------------------
  * The reference's SpeakerEmbedding hands the model every waveform num_speakers times (blocks/embedding.py:56-59).
  * repeat_out receives the largest R >= 1 that divides n_rows and for which every row i with i % R != 0 is BITWISE equal
