@@ -235,6 +235,7 @@ SIGNATURES = {
     "dz_tail_create": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                  C.c_int, vp, C.POINTER(vp)]),
     "dz_tail_reset": (C.c_int, [vp]),
+    "dz_tail_set_offset": (C.c_int, [vp, C.c_double]),
     "dz_tail_destroy": (C.c_int, [vp]),
     "dz_tail_max_rows": (C.c_int, [vp]),
     "dz_tail_speakers": (C.c_int, [vp]),
@@ -262,6 +263,11 @@ SIGNATURES = {
                                     vp]),
     "dz_tune_vad_host": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp,
                                    C.c_int]),
+    "dz_tune_vad_score_hyst": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp,
+                                         vp, vp]),
+    "dz_tune_vad_host_hyst": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int,
+                                        vp, C.c_int]),
+    "dz_tune_vad_replay_tails": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.c_int]),
     "dz_tune_name": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                C.c_int, vp]),
     "dz_tune_name_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,

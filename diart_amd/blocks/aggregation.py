@@ -135,13 +135,19 @@ class BatchedOutputTail:
 
     ``__call__(scores (N,F,G) f64, chunk_start (N,), resolution (N,) | float)`` ->
     ``(aggregated, rows, t0, res, turns, nturns)``: ``aggregated[i, :rows[i]]`` are the scores of the
-    region ``[t0[i], t0[i] + rows[i] * res[i])``; ``turns[i, :nturns[i]]`` = (start, end, speaker)."""
+    region ``[t0[i], t0[i] + rows[i] * res[i])``; ``turns[i, :nturns[i]]`` = (start, end, speaker).
+
+    ``offset``: the offset threshold of ``Binarize(threshold, offset=)``, per stream and speaker column in the
+    handles; ``reset(slot)`` clears that stream's states.  None: the single threshold, the handles as they were."""
 
     def __init__(self, num_streams: int, frames: int, speakers: int, step: float,
                  latency: Optional[float] = None, threshold: float = 0.5, strategy: str = "hamming",
-                 cropping_mode: str = "loose", num_threads: int = 8, max_turns: Optional[int] = None):
+                 cropping_mode: str = "loose", num_threads: int = 8, max_turns: Optional[int] = None,
+                 offset: Optional[float] = None):
         from .. import _lib
+        from .base import check_tau_offset
         import ctypes as C
+        self.offset = check_tau_offset(offset, "BatchedOutputTail(offset=)")
         self._lib, self._C = _lib, C
         latency = step if latency is None else latency
         assert step <= latency, "Invalid latency requested"
@@ -158,6 +164,8 @@ class BatchedOutputTail:
                                           _STRATEGY[strategy], _MODE[cropping_mode],
                                           hamming.ctypes.data, C.byref(h)), "dz_tail_create")
             hs.append(h)
+            if self.offset is not None:     # hysteresis: the state of every stream lives in its handle
+                _lib.check(lib.dz_tail_set_offset(h, self.offset), "dz_tail_set_offset")
         self._hs = hs
         self._handles = (_lib.vp * num_streams)(*hs)
         self.max_rows = frames + 2

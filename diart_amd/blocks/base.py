@@ -18,7 +18,7 @@ class HyperParameter:
 
     @staticmethod
     def from_name(name: str) -> "HyperParameter":
-        for hp in (TauActive, RhoUpdate, DeltaNew, DeltaId):
+        for hp in (TauActive, RhoUpdate, DeltaNew, DeltaId, TauOffset):
             if hp.name == name:
                 return hp
         raise ValueError(f"Hyper-parameter '{name}' not recognized")
@@ -29,6 +29,22 @@ RhoUpdate = HyperParameter("rho_update", low=0, high=1)
 DeltaNew = HyperParameter("delta_new", low=0, high=2)
 # the identification distance of a speaker gallery (optim.IdentTuneCache): the cosine distance's range, as delta_new
 DeltaId = HyperParameter("delta_id", low=0, high=2)
+# the offset threshold of the track pipelines' hysteresis (VoiceActivityDetection, OverlappedSpeechDetection)
+TauOffset = HyperParameter("tau_offset", 0, 1)
+
+
+def check_tau_offset(value, who: str):
+    """``None`` (no hysteresis: the offset is ``tau_active``) or the finite float of ``value``; anything else is a
+    ``ValueError`` that names ``who``."""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: tau_offset must be a finite number or None, got {value!r}") from None
+    if isinstance(value, bool) or v != v or v in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: tau_offset must be a finite number or None, got {value!r}")
+    return v
 
 
 class PipelineConfig(ABC):

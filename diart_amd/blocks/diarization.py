@@ -32,6 +32,14 @@ def _latency(latency, step, duration):
     return latency
 
 
+def refuse_tau_offset(kwargs, who: str) -> None:
+    """Hysteresis is VoiceActivityDetection's and OverlappedSpeechDetection's: pyannote's diarization has no offset
+    threshold, and a live setting the tuner cannot replay would be worse than a refusal."""
+    if "tau_offset" in kwargs:
+        raise ValueError(f"{who}: tau_offset is not a parameter of SpeakerDiarization; hysteresis is "
+                         "VoiceActivityDetection's and OverlappedSpeechDetection's")
+
+
 class SpeakerDiarizationConfig(base.PipelineConfig):
     def __init__(self, segmentation: Optional[m.SegmentationModel] = None,
                  embedding: Optional[m.EmbeddingModel] = None, duration: float = 5, step: float = 0.5,
@@ -39,6 +47,7 @@ class SpeakerDiarizationConfig(base.PipelineConfig):
                  rho_update: float = 0.3, delta_new: float = 1, gamma: float = 3, beta: float = 10,
                  max_speakers: int = 20, normalize_embedding_weights: bool = False,
                  device: Optional[torch.device] = None, sample_rate: int = 16000, **kwargs):
+        refuse_tau_offset(kwargs, "SpeakerDiarizationConfig")
         # the reference downloads pyannote/segmentation + pyannote/embedding here; offline the
         # models must be given (state dicts / checkpoints, see diart_amd.models)
         self.segmentation = segmentation or m.SegmentationModel.from_pyannote("pyannote/segmentation")
@@ -78,6 +87,8 @@ class SpeakerDiarization(base.Pipeline):
     def __init__(self, config: Optional[SpeakerDiarizationConfig] = None):
         self._config = SpeakerDiarizationConfig() if config is None else config
         c = self._config
+        if hasattr(c, "tau_offset"):
+            refuse_tau_offset({"tau_offset": c.tau_offset}, "SpeakerDiarization")
         msg = f"Latency should be in the range [{c.step}, {c.duration}]"
         assert c.step <= c.latency <= c.duration, msg
         self.segmentation = SpeakerSegmentation(c.segmentation, c.device)

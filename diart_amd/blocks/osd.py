@@ -28,8 +28,10 @@ class OverlappedSpeechDetectionConfig(VoiceActivityDetectionConfig):
 
     def __init__(self, segmentation: Optional[m.SegmentationModel] = None, duration: float = 5,
                  step: float = 0.5, latency: Union[float, str, None] = None, tau_active: float = 0.5,
-                 device: Optional[torch.device] = None, sample_rate: int = 16000, **kwargs):
-        super().__init__(segmentation, duration, step, latency, tau_active, device, sample_rate, **kwargs)
+                 device: Optional[torch.device] = None, sample_rate: int = 16000, tau_offset: Optional[float] = None,
+                 **kwargs):
+        super().__init__(segmentation, duration, step, latency, tau_active, device, sample_rate, tau_offset=tau_offset,
+                         **kwargs)
 
 
 class OverlappedSpeechDetection(_TrackDetection):

@@ -72,14 +72,44 @@ def _common_span(datas):
 
 
 class Binarize:
-    def __init__(self, threshold: float, uri: Optional[str] = None):
+    """Frame scores -> speech turns.  ``offset=None``: ``score > threshold`` (the reference).  ``offset``: hysteresis,
+    pyannote's onset / offset — a frame of a column is on when its score is > ``threshold`` while the column is off and
+    > ``offset`` while it is on.  The state is kept per column, starts off, crosses from one call into the next (a
+    call is one step of one stream, so the column count may not change between calls) and is cleared by ``reset()``; a NaN frame is off and leaves the state off.  The
+    turns are formed from the frames as before: a turn open at the last frame is closed there."""
+
+    def __init__(self, threshold: float, uri: Optional[str] = None, offset: Optional[float] = None):
+        from .base import check_tau_offset
         self.uri, self.threshold = uri, threshold
+        self.offset = check_tau_offset(offset, "Binarize(offset=)")
+        self._state: Optional[np.ndarray] = None
+
+    def reset(self):
+        self._state = None
+
+    def _active(self, data: np.ndarray) -> np.ndarray:
+        if self.offset is None:
+            return data > self.threshold                         # strict, utils.py:45
+        num_frames, num_speakers = data.shape
+        if self._state is None:
+            self._state = np.zeros(num_speakers, dtype=bool)
+        elif self._state.shape != (num_speakers,):
+            raise ValueError(f"Binarize(offset=): {num_speakers} columns, but the state carried from the call before has "
+                             f"{self._state.shape[0]}; reset() starts another stream")
+        data = np.asarray(data, dtype=np.float64)
+        on = np.empty((num_frames, num_speakers), dtype=bool)
+        state = self._state
+        for r in range(num_frames):
+            state = data[r] > np.where(state, self.offset, self.threshold)
+            on[r] = state
+        self._state = state
+        return on
 
     def __call__(self, segmentation: SlidingWindowFeature) -> Annotation:
         num_frames, num_speakers = segmentation.data.shape
         ts = segmentation.sliding_window
         active = np.zeros((num_frames + 2, num_speakers), dtype=np.int8)
-        active[1:-1] = segmentation.data > self.threshold       # strict, utils.py:45
+        active[1:-1] = self._active(segmentation.data)
         edges = np.diff(active, axis=0)                          # (num_frames + 1, speakers)
         annotation = Annotation(uri=self.uri, modality="speech")
         for spk in np.nonzero(edges.any(axis=0))[0]:

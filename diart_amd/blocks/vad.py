@@ -25,11 +25,14 @@ def _repeat_label(label):
 class VoiceActivityDetectionConfig(base.PipelineConfig):
     def __init__(self, segmentation: Optional[m.SegmentationModel] = None, duration: float = 5,
                  step: float = 0.5, latency: Union[float, str, None] = None, tau_active: float = 0.6,
-                 device: Optional[torch.device] = None, sample_rate: int = 16000, **kwargs):
+                 device: Optional[torch.device] = None, sample_rate: int = 16000, tau_offset: Optional[float] = None,
+                 **kwargs):
         self.segmentation = segmentation or m.SegmentationModel.from_pyannote("pyannote/segmentation")
         self._duration, self._step, self._sample_rate = duration, step, sample_rate
         self._latency = _latency(latency, step, duration)
         self.tau_active = tau_active
+        # hysteresis: a frame stays on while its score is > tau_offset; None = tau_active, the single threshold
+        self.tau_offset = base.check_tau_offset(tau_offset, f"{type(self).__name__}")
         self.device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
     @property
@@ -65,7 +68,7 @@ class _TrackDetection(base.Pipeline):
         self.segmentation = SpeakerSegmentation(c.segmentation, c.device)
         self.pred_aggregation = DelayedAggregation(c.step, c.latency, strategy="hamming", cropping_mode="loose")
         self.audio_aggregation = DelayedAggregation(c.step, c.latency, strategy="first", cropping_mode="center")
-        self.binarize = Binarize(c.tau_active)
+        self.binarize = Binarize(c.tau_active, offset=getattr(c, "tau_offset", None))
         self.timestamp_shift = 0
         self.chunk_buffer, self.pred_buffer = [], []
 
@@ -80,6 +83,7 @@ class _TrackDetection(base.Pipeline):
     def reset(self):
         self.set_timestamp_shift(0)
         self.chunk_buffer, self.pred_buffer = [], []
+        self.binarize.reset()
 
     def set_timestamp_shift(self, shift: float):
         self.timestamp_shift = shift

@@ -13,6 +13,11 @@
 //                           sums in lane order and writes the five components.  No mask leaves the device.
 //   tune_vad_bits_kernel    one thread per (trial, row): agg > tau as the uint32 masks of the diarization replay
 //                           (VadTuneCache.replay; the tests compare them with the host's)
+//   tune_vad_hyst_kernel    with an offset threshold (taus (T, 2)): one workgroup per (trial, file) for the components
+//                           AND for the masks, because a row's state depends on the row before it.  Each lane first
+//                           runs the two-state machine from both states over its rows; the lanes' state maps, composed
+//                           in lane order, give every lane the state its first row finds (tc_hyst_pair, DESIGN.md
+//                           4.21), and the two walks above then run on the stateful `on`.  (T,) input never comes here.
 //
 // The arithmetic is tune_core.h's, which the host compiles too (dz_tune_vad_host).  No contraction, as in k_tune.hip.
 #pragma clang fp contract(off)
@@ -86,6 +91,32 @@ __global__ __launch_bounds__(VAD_SCORE_THREADS) void tune_vad_score_kernel(
     }
 }
 
+struct HystLanes {
+    int nl;
+    template <typename F>
+    __device__ void operator()(F f) const {
+        f((int)threadIdx.x);
+        __syncthreads();
+    }
+};
+
+// taus (T, 2) = (tau_active, tau_offset); out (T, N, 5) and bits (T, total_rows) may each be NULL (tc_hyst_pair)
+__global__ __launch_bounds__(TC_HYST_LANES) void tune_vad_hyst_kernel(
+    const double* __restrict__ agg, const double* __restrict__ taus, int n_files, int total_rows,
+    const int* __restrict__ file_chunk_off, const int* __restrict__ row_off, const double* __restrict__ mids,
+    const int* __restrict__ mid_cell, const int* __restrict__ file_cell_off, const double* __restrict__ dur_prefix,
+    const double* __restrict__ ref_prefix, double collar, double* __restrict__ out, unsigned* __restrict__ bits) {
+    __shared__ TcHystShared sh;
+    const int pair = blockIdx.x;
+    const int t = pair / n_files, n = pair - t * n_files;
+    const long pre = (long)file_cell_off[n] + n;          // ncell + 1 prefix values per file
+    const TcHystIn in = {agg, row_off, mids, mid_cell, dur_prefix + pre, ref_prefix + pre, file_chunk_off[n],
+                         file_chunk_off[n + 1], file_cell_off[n + 1] - file_cell_off[n], taus[2 * (size_t)t],
+                         taus[2 * (size_t)t + 1], collar};
+    tc_hyst_pair(in, sh, out ? out + (size_t)pair * 5 : nullptr, bits ? bits + (size_t)t * total_rows : nullptr,
+                 HystLanes{TC_HYST_LANES});
+}
+
 }  // namespace
 
 extern "C" int dz_tune_vad_rows(dz_ctx* ctx, const dz_tune_desc* d, double* d_agg, void* stream) {
@@ -127,5 +158,25 @@ extern "C" int dz_tune_vad_score(dz_ctx* ctx, int trials, int n_files, int total
                   total_rows, d_bits);
         DZ_HIP(hipGetLastError());
     }
+    return 0;
+}
+
+// With hysteresis: d_taus (T, 2) = (tau_active, tau_offset) per trial; everything else is dz_tune_vad_score's.
+extern "C" int dz_tune_vad_score_hyst(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
+                                      const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
+                                      const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
+                                      const double* d_dur_prefix, const double* d_ref_prefix, double collar,
+                                      double* d_out, unsigned* d_bits, void* stream) {
+    DZ_REQUIRE(ctx && d_agg && d_taus && d_file_chunk_off && d_row_off && d_mids && d_mid_cell && d_file_cell_off &&
+                   d_dur_prefix && d_ref_prefix && (d_out || d_bits), "dz_tune_vad_score_hyst: NULL argument");
+    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_rows >= 1,
+               "dz_tune_vad_score_hyst: empty shape (%d trials, %d files, %d rows)", trials, n_files, total_rows);
+    const long long pairs = (long long)trials * n_files;
+    DZ_REQUIRE(pairs < (1ll << 31), "dz_tune_vad_score_hyst: %lld pairs in one call; evaluate fewer trials per batch", pairs);
+    DZ_HIP(hipSetDevice(ctx->device));
+    DZ_LAUNCH(tune_vad_hyst_kernel, dim3((unsigned)pairs), dim3(TC_HYST_LANES), 0, (hipStream_t)stream, d_agg, d_taus,
+              n_files, total_rows, d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix,
+              d_ref_prefix, collar, d_out, d_bits);
+    DZ_HIP(hipGetLastError());
     return 0;
 }

@@ -23,6 +23,7 @@
 #include <stddef.h>
 #include <string.h>
 
+#include <cmath>
 #include <deque>
 #include <new>
 #include <vector>
@@ -48,6 +49,10 @@ struct dz_tail {
     std::deque<Buffer> buffers;
     std::vector<double> num, den;  // scratch
     std::vector<long> first;       // the region's first row in every buffer
+    // hysteresis (dz_tail_set_offset): off until it is called, and then today's walk runs
+    bool has_offset = false;
+    double offset = 0.0;
+    std::vector<unsigned char> active;   // [G] the state every speaker column's last row left
 };
 
 namespace {
@@ -134,18 +139,39 @@ int tail_step(dz_tail* t, const double* scores, double chunk_start, double res, 
             const double s = out_start + i * out_res;
             return 0.5 * (s + (s + out_res));
         };
+        bool full = false;   // hysteresis: more turns than max_turns — the walk goes on without storing, so that the
+                             // state of EVERY column has seen the whole step when 5 is returned
         for (int g = 0; g < G; ++g) {
-            const bool room = tail_edge_walk(
-                rows, [&](int r) { return agg_out[(size_t)r * G + g] > t->threshold; },
-                [&](int onset, int r) {
-                    if (nt >= max_turns) return false;
-                    turns_out[3 * nt + 0] = middle(onset);
-                    turns_out[3 * nt + 1] = middle(r);
-                    turns_out[3 * nt + 2] = (double)g;
-                    ++nt;
-                    return true;
-                });
+            auto emit = [&](int onset, int r) {
+                if (nt >= max_turns) {
+                    full = true;
+                    return t->has_offset;
+                }
+                turns_out[3 * nt + 0] = middle(onset);
+                turns_out[3 * nt + 1] = middle(r);
+                turns_out[3 * nt + 2] = (double)g;
+                ++nt;
+                return true;
+            };
+            bool room;
+            if (t->has_offset) {
+                bool state = t->active[g] != 0;
+                room = tail_edge_walk_hyst(
+                    rows, [&](int r) { return agg_out[(size_t)r * G + g]; }, t->threshold, t->offset, &state, emit);
+                t->active[g] = state;
+            } else {
+                room = tail_edge_walk(rows, [&](int r) { return agg_out[(size_t)r * G + g] > t->threshold; }, emit);
+            }
             if (!room) return 5;
+        }
+        if (full) return 5;
+    } else if (t->has_offset) {   // no turns asked for: the states still follow the rows
+        for (int g = 0; g < G; ++g) {
+            bool state = t->active[g] != 0;
+            tail_edge_walk_hyst(
+                rows, [&](int r) { return agg_out[(size_t)r * G + g]; }, t->threshold, t->offset, &state,
+                [](int, int) { return true; });
+            t->active[g] = state;
         }
     }
     if (nturns_out) *nturns_out = nt;
@@ -180,6 +206,21 @@ extern "C" int dz_tail_create(int frames, int speakers, double step, double late
 extern "C" int dz_tail_reset(dz_tail* t) {
     if (!t) return 2;
     t->buffers.clear();
+    t->active.assign(t->active.size(), 0);   // the states; the offset stays
+    return 0;
+}
+extern "C" int dz_tail_set_offset(dz_tail* t, double offset) {
+    if (!t) {
+        dz_set_error("dz_tail_set_offset: NULL handle");
+        return 2;
+    }
+    if (!std::isfinite(offset)) {
+        dz_set_error("dz_tail_set_offset: the offset threshold must be finite, got %g", offset);
+        return 2;
+    }
+    if (!t->has_offset) t->active.assign(t->G, 0);
+    t->has_offset = true;
+    t->offset = offset;
     return 0;
 }
 extern "C" int dz_tail_destroy(dz_tail* t) {

@@ -9,6 +9,7 @@
 //   tail_geometry      what a step does that does not depend on the scores: the output region, its cropped rows in
 //                      every buffer, the first-chunk prepend, the output grid
 //   tail_edge_walk     Binarize: the rising and falling edges of "row r is on"
+//   tail_edge_walk_hyst  the same with an offset threshold: the on/off state is taken from and handed to the caller
 //   tail_hamming_num   the Hamming-weighted sum of one output row of the tuner, one speaker at a time
 //
 // Arithmetic and control flow only: no allocation, nothing of the standard library; the callers own the memory.
@@ -120,6 +121,28 @@ TC_HD bool tail_edge_walk(int rows, On on, Emit emit) {
         }
     }
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Binarize with hysteresis (two thresholds, pyannote's onset / offset): a row is on when its score is > tau_active
+// while the track is off and > tau_offset while it is on.  Plain compares: a NaN row is off and leaves the state off.
+// tau_offset == tau_active is `y > tau`, row for row; any finite pair is defined by this line, tau_offset above
+// tau_active included.
+// ---------------------------------------------------------------------------------------------------------
+TC_HD bool tail_hyst_on(double y, double tau_active, double tau_offset, bool active) {
+    return y > (active ? tau_offset : tau_active);
+}
+// tail_edge_walk's stateful sibling: score(r) is the aggregated score of row r, *state the state the step before left
+// (off at the start of a stream and after a reset) and, on return, the state after the last row walked.  The turns are
+// formed from `on` as tail_edge_walk forms them: within the step, the row after the last closes an open turn — the
+// state, not the turn, crosses into the next step.
+template <typename Score, typename Emit>
+TC_HD bool tail_edge_walk_hyst(int rows, Score score, double tau_active, double tau_offset, bool* state, Emit emit) {
+    bool active = *state;
+    const bool room = tail_edge_walk(
+        rows, [&](int r) { return active = tail_hyst_on(score(r), tau_active, tau_offset, active); }, emit);
+    *state = active;
+    return room;
 }
 
 // ---------------------------------------------------------------------------------------------------------

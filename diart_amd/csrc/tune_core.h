@@ -7,7 +7,8 @@
 // edge walk of Binarize; what this file adds there is the plan's layout and the merging of the turns.  Host and device
 // compile this text: k_tune.hip for the kernels, tune_score.cpp for backend="core", which tests/test_tune_host.py
 // holds against dz_clu_step + dz_tail_step.  The VoiceActivityDetection half (tc_vad_*, behind the replay) is
-// k_tune_vad.hip's and dz_tune_vad_host's in the same way, and the scoring of the diarization masks (tc_score_*, at the
+// k_tune_vad.hip's and dz_tune_vad_host's in the same way — with its hysteresis form (tc_hyst_*: the lanes' state maps,
+// DESIGN.md 4.21), tune_vad_hyst_kernel's and dz_tune_vad_host_hyst's — and the scoring of the diarization masks (tc_score_*, at the
 // end) is k_tune_score.hip's and dz_tune_score_core's.
 #pragma once
 #include "../../include/diart_amd.h"
@@ -228,6 +229,119 @@ TC_HD void tc_vad_components(double total, TcVadSum s, double* o) {
 
 // How a workgroup of nl lanes shares a file of `chunks` steps: lane i walks steps [i * per, (i + 1) * per).
 TC_HD int tc_vad_steps_per_lane(int chunks, int nl) { return (chunks + nl - 1) / nl; }
+
+// ---------------------------------------------------------------------------------------------------------
+// The track pipelines with hysteresis (tail_hyst_on: a row is on when agg > tau_active while the track is off and
+// > tau_offset while it is on; the state is off at a file's first row and is carried across its steps).  A row now
+// depends on the row before it, and a lane that walks steps [i * per, (i + 1) * per) does not know the state its first
+// row finds.  It does know what its rows make of either state: tc_hyst_map runs the machine from "off" and from "on"
+// at once over the lane's rows and returns both out-states, two bits.  These maps compose (tc_hyst_apply), a lane
+// without rows is the identity, and the state lane i starts from is the lanes 0 .. i - 1 applied in order to "off".
+// Nothing is approximated: the rule is a function of (state, score), every lane applies that function to exactly the
+// rows the sequential walk would, in their order, and composing functions is associative; the `on` of every row is
+// therefore the sequential machine's, bit for bit.  From there the two walks are tune_vad_score_kernel's.
+//
+// Written as phases over the lanes, as tc_score_cells is: lanes(f) runs f(lane) for every lane and ends with the
+// workgroup's barrier (k_tune_vad.hip), or plays the lanes in order (dz_tune_vad_host_hyst).  `out` (5 components) and
+// `bits` (this trial's masks, indexed by packed row) may each be NULL.  No atomics, plain compares.
+// ---------------------------------------------------------------------------------------------------------
+TC_HD unsigned tc_hyst_map(const double* agg, int p0, int p1, double tau_active, double tau_offset) {
+    bool from_off = false, from_on = true;
+    for (int p = p0; p < p1; ++p) {
+        const double y = agg[p];
+        from_off = tail_hyst_on(y, tau_active, tau_offset, from_off);
+        from_on = tail_hyst_on(y, tau_active, tau_offset, from_on);
+    }
+    return (from_off ? 1u : 0u) | (from_on ? 2u : 0u);
+}
+TC_HD bool tc_hyst_apply(unsigned map, bool active) { return (map >> (active ? 1 : 0)) & 1u; }
+
+struct TcHystOn {   // tc_turn_walk asks for the rows of its steps once each and in order
+    const double* agg;
+    double tau_active, tau_offset;
+    bool* active;
+    TC_HD bool operator()(int p) const { return *active = tail_hyst_on(agg[p], tau_active, tau_offset, *active); }
+};
+
+constexpr int TC_HYST_LANES = 256;   // the workgroup of tune_vad_hyst_kernel; the host plays at most as many
+
+struct TcHystIn {
+    const double* agg;                        // (total_rows)
+    const int* row_off;                       // (chunks + 1)
+    const double* mids;                       // rows + 1 frame middles per step
+    const int* mid_cell;
+    const double *dur_prefix, *ref_prefix;    // THIS file's ncell + 1 prefix sums
+    int c0, c1, ncell;
+    double tau_active, tau_offset, collar;
+};
+struct TcHystShared {
+    double end_e[TC_HYST_LANES];
+    double sum_hyp[TC_HYST_LANES], sum_both[TC_HYST_LANES];
+    int end_cell[TC_HYST_LANES];
+    unsigned char map[TC_HYST_LANES];         // tc_hyst_map of every lane's rows
+    unsigned char start[TC_HYST_LANES];       // the state every lane's first row finds
+};
+
+template <typename Lanes>
+TC_HD void tc_hyst_pair(const TcHystIn& in, TcHystShared& sh, double* out, unsigned* bits, Lanes lanes) {
+    const int nl = lanes.nl, chunks = in.c1 - in.c0;
+    const int per = tc_vad_steps_per_lane(chunks, nl);
+    const double ta = in.tau_active, to = in.tau_offset;
+    const TcVadEnd none = {-INFINITY, 0};
+    auto lo_of = [&](int lane) { return in.c0 + ((long long)lane * per < chunks ? lane * per : chunks); };
+    auto hi_of = [&](int lane) {
+        const int lo = lo_of(lane);
+        return lo + per < in.c1 ? lo + per : in.c1;
+    };
+    // ---- every lane's state map
+    lanes([&](int lane) {
+        sh.map[lane] = (unsigned char)tc_hyst_map(in.agg, in.row_off[lo_of(lane)], in.row_off[hi_of(lane)], ta, to);
+    });
+    // ---- the maps composed in lane order; the masks; alone, the end of the lane's latest-ending turn
+    lanes([&](int lane) {
+        bool start = false;
+        for (int j = 0; j < lane; ++j) start = tc_hyst_apply(sh.map[j], start);
+        sh.start[lane] = start ? 1 : 0;
+        if (bits) {
+            bool active = start;
+            for (int p = in.row_off[lo_of(lane)], p1 = in.row_off[hi_of(lane)]; p < p1; ++p) {
+                active = tail_hyst_on(in.agg[p], ta, to, active);
+                bits[p] = active ? 1u : 0u;
+            }
+        }
+        if (!out) return;
+        bool active = start;
+        const TcVadEnd own = tc_turn_walk(TcHystOn{in.agg, ta, to, &active}, [](int, int) {}, in.row_off, in.mids,
+                                          in.mid_cell, in.collar, lo_of(lane), hi_of(lane), none);
+        sh.end_e[lane] = own.e;
+        sh.end_cell[lane] = own.cell;
+    });
+    if (!out) return;
+    // ---- again from the end of the last turn before the lane, summing what its turns add
+    lanes([&](int lane) {
+        TcVadEnd before = none;
+        for (int j = 0; j < lane; ++j)
+            if (sh.end_e[j] > before.e) {
+                before.e = sh.end_e[j];
+                before.cell = sh.end_cell[j];
+            }
+        TcVadSum s = {0.0, 0.0};
+        bool active = sh.start[lane] != 0;
+        tc_turn_walk(TcHystOn{in.agg, ta, to, &active}, TcVadAdd{in.dur_prefix, in.ref_prefix, &s}, in.row_off, in.mids,
+                     in.mid_cell, in.collar, lo_of(lane), hi_of(lane), before);
+        sh.sum_hyp[lane] = s.hyp;
+        sh.sum_both[lane] = s.both;
+    });
+    lanes([&](int lane) {
+        if (lane != 0) return;
+        TcVadSum all = {0.0, 0.0};
+        for (int j = 0; j < nl; ++j) {
+            all.hyp += sh.sum_hyp[j];
+            all.both += sh.sum_both[j];
+        }
+        tc_vad_components(in.ref_prefix[in.ncell], all, out);
+    });
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // SpeakerDiarization: the diarization error rate components of one (trial, file) from the trial's packed masks

@@ -15,6 +15,8 @@
 //   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
 //                        scoring of k_tune_vad.hip, from the text those kernels compile; OverlappedSpeechDetection
 //                        too (both track pipelines: another track, other reference prefix sums)
+//   dz_tune_vad_host_hyst     the same with an offset threshold (hysteresis), from the text of tune_vad_hyst_kernel;
+//   dz_tune_vad_replay_tails  its yardstick: the masks through dz_tail_create + dz_tail_set_offset + dz_tail_step
 //   dz_tune_name_host    the names a gallery gives the global speakers of every (trial, file) chain, step by step, from
 //                        the text tune_name_kernel compiles (tune_ident_core.h)
 //   dz_tune_ident_score  identification error rate components of every pair: dz_tune_score's cells, the labels compared
@@ -457,6 +459,120 @@ extern "C" int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int t
             dz_host_parallel(pairs, nt, run);
     }
     return 0;
+}
+
+// The track pipelines with hysteresis, from the text tune_vad_hyst_kernel compiles (tc_hyst_pair): taus
+// (T, 2) = (tau_active, tau_offset) per trial, everything else as dz_tune_vad_host.  bits and out both come from the
+// lanes' state maps, `lanes` lanes of a workgroup played one after the other; lanes is needed for either.
+extern "C" int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+                                     const double* mids, const int* mid_cell, const int* file_cell_off,
+                                     const double* dur_prefix, const double* ref_prefix, double collar, int lanes,
+                                     double* out, int num_threads) {
+    if (!d || !taus || !agg || trials < 1 || !d->seg || !d->chunk_off || !d->plan || !d->row_off || !d->row_chunk ||
+        !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->nwin < 1 || d->total_rows < 1 || lanes < 1 ||
+        lanes > TC_HYST_LANES || !mids || !mid_cell || !file_cell_off || !dur_prefix || !ref_prefix) {
+        dz_set_error("dz_tune_vad_host_hyst: bad arguments (one track per chunk, 1 .. %d lanes expected)", TC_HYST_LANES);
+        return 2;
+    }
+    for (int t = 0; t < trials; ++t)
+        if (!std::isfinite(taus[2 * (size_t)t + 1])) {
+            dz_set_error("dz_tune_vad_host_hyst: tau_offset of trial %d is %g, not a finite number", t, taus[2 * (size_t)t + 1]);
+            return 2;
+        }
+    const int N = d->N, rows = d->total_rows;
+    int nt = num_threads < 1 ? 1 : num_threads;
+    {   // the rows, in slices
+        const int slices = rows < nt ? rows : nt;
+        auto run = [&](int, int s) {
+            const int a = (int)((long long)rows * s / slices), b = (int)((long long)rows * (s + 1) / slices);
+            for (int p = a; p < b; ++p) agg[p] = tc_vad_row(*d, p);
+        };
+        if (slices == 1) run(0, 0);
+        else dz_host_parallel(slices, slices, run);
+    }
+    if (!bits && !out) return 0;
+    const int pairs = trials * N;
+    if (nt > pairs) nt = pairs;
+    auto run = [&](int, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        const size_t pre = (size_t)file_cell_off[n] + n;
+        std::vector<TcHystShared> sh(1);
+        // LDS starts with whatever was there: nothing in it may be read before this pair has written it
+        std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(TcHystShared));
+        const TcHystIn in = {agg, d->row_off, mids, mid_cell, dur_prefix + pre, ref_prefix + pre, d->chunk_off[n],
+                             d->chunk_off[n + 1], file_cell_off[n + 1] - file_cell_off[n], taus[2 * (size_t)t],
+                             taus[2 * (size_t)t + 1], collar};
+        tc_hyst_pair(in, sh[0], out ? out + (size_t)pair * 5 : nullptr, bits ? bits + (size_t)t * rows : nullptr,
+                     LanesInTurn{lanes});
+    };
+    if (nt == 1)
+        for (int i = 0; i < pairs; ++i) run(0, i);
+    else
+        dz_host_parallel(pairs, nt, run);
+    return 0;
+}
+
+// The same masks from an independent text: one dz_tail handle per (trial, file) with dz_tail_set_offset, the file's
+// track fed step by step (what a live stream or a file batch does), pairs on host threads.  The masks are read back from
+// the turns dz_tail_step returns: a turn [middle(onset), middle(r)) covers rows onset .. r - 1 of its step.  taus (T, 2);
+// starts, resolution (chunks), step, latency as dz_tail_step gets them; bits (T, total_rows).  backend="host".
+extern "C" int dz_tune_vad_replay_tails(const dz_tune_desc* d, const double* taus, int trials, double step, double latency,
+                                        const double* starts, const double* resolution, unsigned* bits, int num_threads) {
+    if (!d || !taus || !starts || !resolution || !bits || trials < 1 || !d->seg || !d->chunk_off || !d->row_off ||
+        !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->total_rows < 1) {
+        dz_set_error("dz_tune_vad_replay_tails: bad arguments (one track per chunk expected)");
+        return 2;
+    }
+    for (int t = 0; t < trials; ++t)
+        if (!std::isfinite(taus[2 * (size_t)t + 1])) {
+            dz_set_error("dz_tune_vad_replay_tails: tau_offset of trial %d is %g, not a finite number", t,
+                         taus[2 * (size_t)t + 1]);
+            return 2;
+        }
+    const int N = d->N, F = d->F, pairs = trials * N;
+    const int max_turns = (F + 2) / 2 + 1;
+    const dz_host_failure f = dz_host_parallel_rc(pairs, dz_host_threads(num_threads, pairs), [&](int, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        unsigned* B = bits + (size_t)t * d->total_rows;
+        std::vector<double> in(F), agg((size_t)F + 2), turns((size_t)max_turns * 3);
+        dz_tail* tail = nullptr;
+        if (dz_tail_create(F, 1, step, latency, taus[2 * (size_t)t], DZ_AGG_HAMMING, DZ_CROP_LOOSE, d->hamming, &tail)) return 2;
+        int rc = dz_tail_set_offset(tail, taus[2 * (size_t)t + 1]);
+        for (int c = d->chunk_off[n]; c < d->chunk_off[n + 1] && !rc; ++c) {
+            for (int i = 0; i < F; ++i) in[i] = (double)d->seg[(size_t)c * F + i];
+            int rows = 0, nturns = 0;
+            double t0 = 0.0, res = 0.0;
+            rc = dz_tail_step(tail, in.data(), starts[c], resolution[c], agg.data(), &rows, &t0, &res, turns.data(), max_turns,
+                              &nturns);
+            if (rc) break;
+            if (rows != d->row_off[c + 1] - d->row_off[c]) {
+                dz_set_error("dz_tune_vad_replay_tails: dz_tail_step and the plan disagree on the rows of a step");
+                rc = 4;
+                break;
+            }
+            unsigned* row = B + d->row_off[c];
+            for (int r = 0; r < rows; ++r) row[r] = 0u;
+            for (int k = 0; k < nturns; ++k) {   // middle(i) = t0 + (i + 0.5) * res
+                const long a = (long)nearbyint((turns[3 * k] - t0) / res - 0.5), b = (long)nearbyint((turns[3 * k + 1] - t0) / res - 0.5);
+                // the rounding finds the rows only while t0 / res is far below 2^52 / rows; rather than trust that, the
+                // rows must give back the turn's own times through dz_tail_step's expression for a frame's middle
+                auto middle = [&](long i) {
+                    const double s = t0 + (int)i * res;
+                    return 0.5 * (s + (s + res));
+                };
+                if (a < 0 || b > rows || a >= b || middle(a) != turns[3 * k] || middle(b) != turns[3 * k + 1]) {
+                    dz_set_error("dz_tune_vad_replay_tails: a turn of step %d does not map back onto the step's rows", c);
+                    rc = 4;
+                    break;
+                }
+                for (long r = a; r < b; ++r) row[r] = 1u;
+            }
+        }
+        dz_tail_destroy(tail);
+        return rc;
+    });
+    if (f.code) dz_set_error("dz_tune_vad_replay_tails: %s", f.message.c_str());
+    return f.code;
 }
 
 // ---------------------------------------------------------------------------------------------------------

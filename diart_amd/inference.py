@@ -442,7 +442,8 @@ class Benchmark:
         one_track = kind in ("vad", "osd")
         hyper = () if one_track else (config.rho_update, config.delta_new, config.gamma, config.beta,
                                           config.max_speakers, config.normalize_embedding_weights)
-        key = (kind, id(seg.model), None if one_track else id(emb.model), config.tau_active, hyper, config.duration,
+        key = (kind, id(seg.model), None if one_track else id(emb.model), config.tau_active,
+               getattr(config, "tau_offset", None) if one_track else None, hyper, config.duration,
                config.step, config.latency, config.sample_rate, str(config.device), self.batch_size,
                self.concurrent_files, self.file_batch_rows)
         cached = getattr(self, "_fb_cache", None)
@@ -457,7 +458,8 @@ class Benchmark:
                       duration=config.duration, step=config.step, latency=config.latency,
                       sample_rate=config.sample_rate, device=config.device)
         if emb is None:
-            return FileBatch(seg.model, None, pipeline="osd" if kind == "osd" else "vad", **common)
+            return FileBatch(seg.model, None, pipeline="osd" if kind == "osd" else "vad",
+                             tau_offset=getattr(config, "tau_offset", None), **common)
         return FileBatch(seg.model, emb.model, rho_update=config.rho_update, delta_new=config.delta_new,
                          gamma=config.gamma, beta=config.beta, max_speakers=config.max_speakers,
                          normalize_embedding_weights=config.normalize_embedding_weights, **common)

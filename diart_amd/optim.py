@@ -53,6 +53,8 @@ from .metrics import (DetectionErrorRate, DiarizationErrorRate, IdentificationEr
 TUNABLE = ("tau_active", "rho_update", "delta_new")
 IDENT_TUNABLE = TUNABLE + ("delta_id",)
 VAD_TUNABLE = ("tau_active",)
+# with hysteresis (blocks.base.TauOffset): the track pipelines' second threshold, replayed by tune_vad_hyst_kernel
+TRACK_TUNABLE = ("tau_active", "tau_offset")
 MAX_SPEAKERS = 32          # the hypothesis of a frame is one 32-bit mask
 MAX_LOCAL_SPEAKERS = 8
 PATCH_COLLAR = 0.05        # PredictionAccumulator's default
@@ -978,11 +980,22 @@ class _TrackTuneCache(_ReplayCache):
     # ------------------------------------------------------------------------------------------ replay
     @staticmethod
     def _taus(taus) -> np.ndarray:
-        t = np.asarray(taus, dtype=np.float64)
+        """``(T,)`` — ``(T, 1)`` too — = tau_active per trial: the single threshold, today's kernels.  ``(T, 2)`` =
+        (tau_active, tau_offset) per trial: hysteresis, and the array stays two-dimensional."""
+        try:
+            t = np.asarray(taus, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("taus (T,), (T, 1) = tau_active or (T, 2) = (tau_active, tau_offset) per trial expected: "
+                             "numbers") from None
         if t.ndim == 2 and t.shape[1] == 1:
             t = t[:, 0]
+        if t.ndim == 2 and t.shape[1] == 2 and t.shape[0] >= 1:
+            if not np.isfinite(t[:, 1]).all():
+                raise ValueError("taus (T, 2): tau_offset must be finite in every trial")
+            return np.ascontiguousarray(t)
         if t.ndim != 1 or t.shape[0] < 1:
-            raise ValueError(f"taus (T,) or (T, 1) = tau_active per trial expected, got {np.shape(taus)}")
+            raise ValueError(f"taus (T,) or (T, 1) = tau_active per trial, or (T, 2) = (tau_active, tau_offset) per trial "
+                             f"expected, got {np.shape(taus)}")
         return np.ascontiguousarray(t)
 
     def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int):
@@ -997,6 +1010,36 @@ class _TrackTuneCache(_ReplayCache):
                                                 self.dur_prefix.ctypes.data, self.ref_prefix.ctypes.data, PATCH_COLLAR,
                                                 self.SCORE_LANES, ptr(out), int(num_threads)), "dz_tune_vad_host")
         return agg, b, out
+
+    def _host_hyst(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int, core: bool):
+        """``_host`` for ``taus (T, 2)``.  ``core``: masks and components from the kernel's text, the lanes' state maps
+        included (``dz_tune_vad_host_hyst``).  Otherwise the masks come from an independent text — one ``dz_tail``
+        handle with ``dz_tail_set_offset`` per (trial, file), fed the track step by step — and no components."""
+        T = taus.shape[0]
+        agg = np.empty(self.total_rows, dtype=np.float64)
+        b = np.empty((T, self.total_rows), dtype=np.uint32) if bits else None
+        out = np.zeros((T, self.N, 5), dtype=np.float64) if components else None
+        d = self._desc(lambda name: getattr(self, name).ctypes.data)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        lib = _lib.load()
+        if core:
+            _lib.check(lib.dz_tune_vad_host_hyst(C.byref(d), taus.ctypes.data, T, agg.ctypes.data, ptr(b),
+                                                 self.mids.ctypes.data, self.mid_cell.ctypes.data,
+                                                 self.file_cell_off.ctypes.data, self.dur_prefix.ctypes.data,
+                                                 self.ref_prefix.ctypes.data, PATCH_COLLAR, self.SCORE_LANES, ptr(out),
+                                                 int(num_threads)), "dz_tune_vad_host_hyst")
+            return agg, b, out
+        assert not components
+        onsets = np.ascontiguousarray(taus[:, 0])
+        _lib.check(lib.dz_tune_vad_host(C.byref(d), onsets.ctypes.data, T, agg.ctypes.data, None, None, None, None, None,
+                                        None, PATCH_COLLAR, self.SCORE_LANES, None, int(num_threads)), "dz_tune_vad_host")
+        if bits:
+            starts = np.ascontiguousarray(self.starts, dtype=np.float64)
+            res = np.ascontiguousarray(self.res, dtype=np.float64)
+            _lib.check(lib.dz_tune_vad_replay_tails(C.byref(d), taus.ctypes.data, T, self.meta["step"], self.meta["latency"],
+                                                    starts.ctypes.data, res.ctypes.data, b.ctypes.data, int(num_threads)),
+                       "dz_tune_vad_replay_tails")
+        return agg, b, None
 
     def _device(self, device: torch.device):
         """The cache's device tensors, ``agg`` among them: tune_vad_rows_kernel runs once per cache and device."""
@@ -1022,25 +1065,34 @@ class _TrackTuneCache(_ReplayCache):
         b = torch.empty((T, self.total_rows), dtype=torch.int32, device=device) if bits else None
         out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device) if components else None
         ptr = lambda a: None if a is None else a.data_ptr()
-        _lib.check(_lib.load().dz_tune_vad_score(_lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(),
-                                                 d_taus.data_ptr(), t["chunk_off"].data_ptr(), t["row_off"].data_ptr(),
-                                                 t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
-                                                 t["file_cell_off"].data_ptr(), t["dur_prefix"].data_ptr(),
-                                                 t["ref_prefix"].data_ptr(), PATCH_COLLAR, ptr(out), ptr(b),
-                                                 torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_score")
+        # (T, 2): tune_vad_hyst_kernel, one workgroup per (trial, file) for the masks too; (T,): today's kernels
+        entry, name = ((_lib.load().dz_tune_vad_score_hyst, "dz_tune_vad_score_hyst") if taus.ndim == 2 else
+                       (_lib.load().dz_tune_vad_score, "dz_tune_vad_score"))
+        _lib.check(entry(_lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(),
+                         d_taus.data_ptr(), t["chunk_off"].data_ptr(), t["row_off"].data_ptr(),
+                         t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
+                         t["file_cell_off"].data_ptr(), t["dur_prefix"].data_ptr(),
+                         t["ref_prefix"].data_ptr(), PATCH_COLLAR, ptr(out), ptr(b),
+                         torch.cuda.current_stream(device).cuda_stream), name)
         return t["agg"], b, out
 
     def replay(self, taus, backend: Optional[str] = None, num_threads: int = 8):
         """``(agg (rows,) float64, bits (T, rows) uint32)``: the aggregated speech score of every packed output frame
-        and, per trial, whether it is above the trial's tau.  ``backend``: "gpu" | "host"."""
+        and, per trial, whether it is above the trial's tau.  ``backend``: "gpu" | "host".  ``taus (T, 2)`` =
+        (tau_active, tau_offset): whether the frame is on under the hysteresis rule, the state off at every file's first
+        frame; then "core" too, the kernel's text on host threads ("host" goes through ``dz_tail_set_offset``)."""
         taus = self._taus(taus)
         backend = backend or self.default_backend()
+        hyst = taus.ndim == 2
         if backend == "gpu":
             agg, bits, _ = self._gpu(taus, True, False)
             torch.cuda.synchronize(agg.device)
             return agg.cpu().numpy(), bits.cpu().numpy().view(np.uint32)
+        if hyst and backend in ("host", "core"):
+            agg, bits, _ = self._host_hyst(taus, True, False, num_threads, core=backend == "core")
+            return agg, bits
         if backend != "host":
-            raise ValueError(f"backend '{backend}': gpu or host")
+            raise ValueError(f"backend '{backend}': gpu or host" + (" or core" if hyst else ""))
         agg, bits, _ = self._host(taus, True, False, num_threads)
         return agg, bits
 
@@ -1053,7 +1105,10 @@ class _TrackTuneCache(_ReplayCache):
                  num_threads: int = 8) -> TuneResult:
         """The detection error rate of every trial of ``taus``.  ``backend``: "gpu" (the two kernels; only the
         components come back), "host" (the same aggregation on host threads, then ``dz_tune_score``; trials in batches
-        whose masks fit ``memory_budget`` bytes) or "core" (the scoring kernel's text on host threads)."""
+        whose masks fit ``memory_budget`` bytes) or "core" (the scoring kernel's text on host threads).  ``taus (T, 2)``
+        = (tau_active, tau_offset) per trial: hysteresis — "gpu" runs ``tune_vad_hyst_kernel``, "core" its text, "host"
+        one ``dz_tail`` handle with ``dz_tail_set_offset`` per (trial, file), then ``dz_tune_score``.  ``(T,)`` runs what
+        it always ran."""
         taus = self._taus(taus)
         backend = backend or self.default_backend()
         if backend == "gpu":
@@ -1062,10 +1117,13 @@ class _TrackTuneCache(_ReplayCache):
             per_file = out.cpu().numpy()
         elif backend == "core":
             self._check_sorted(f"backend '{backend}'")
-            per_file = self._host(taus, False, True, num_threads)[2]
+            per_file = (self._host_hyst(taus, False, True, num_threads, core=True) if taus.ndim == 2 else
+                        self._host(taus, False, True, num_threads))[2]
         elif backend == "host":
             per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
-            per_file = np.concatenate([self.score(self._host(taus[a:a + per_batch], True, False, num_threads)[1], num_threads)
+            masks = ((lambda t: self._host_hyst(t, True, False, num_threads, core=False)[1]) if taus.ndim == 2 else
+                     (lambda t: self._host(t, True, False, num_threads)[1]))
+            per_file = np.concatenate([self.score(masks(taus[a:a + per_batch]), num_threads)
                                        for a in range(0, taus.shape[0], per_batch)])
         else:
             raise ValueError(f"backend '{backend}': gpu, host or core")
@@ -1237,7 +1295,7 @@ class Optimizer:
                              "SpeakerDiarization takes scoring='host' or 'device'")
         self.scoring = scoring
         self.cache_class = {"dia": TuneCache, "ident": IdentTuneCache, "vad": VadTuneCache, "osd": OsdTuneCache}[self.kind]
-        self.tunable = VAD_TUNABLE if track else IDENT_TUNABLE if gallery is not None else TUNABLE
+        self.tunable = TRACK_TUNABLE if track else IDENT_TUNABLE if gallery is not None else TUNABLE
         if gallery is not None and type(cache) is TuneCache:
             pass                                   # matched against the gallery on first use (the cache property)
         elif gallery is not None and isinstance(cache, IdentTuneCache) and cache.names != tuple(gallery.names):
@@ -1274,6 +1332,11 @@ class Optimizer:
         default = list(pipeline_class.hyper_parameters()) + ([base.DeltaId] if gallery is not None else [])
         self.hparams = list(default if hparams is None else hparams)
         possible = vars(self.base_config)
+        if not track and (hasattr(self.base_config, "tau_offset") or any(p.name == "tau_offset" for p in self.hparams)):
+            from .blocks.diarization import refuse_tau_offset
+            refuse_tau_offset({"tau_offset": None}, f"Optimizer({pipeline_class.__name__})")
+        if track:
+            base.check_tau_offset(getattr(self.base_config, "tau_offset", None), "Optimizer: base_config")
         for param in self.hparams:
             if param.name == "delta_id" and gallery is None:
                 raise ValueError("hyper-parameter delta_id is the identification distance of a gallery: gallery= and "
@@ -1334,10 +1397,26 @@ class Optimizer:
     def _values(self, params: Dict[str, float]) -> List[float]:
         """(tau, rho, delta) of a trial ((tau) of a track pipeline): the sampled parameters, the base config's
         value for the others."""
+        if self.kind in ("vad", "osd"):
+            # (tau_active,) — today's kernels — unless tau_offset is tuned or the base configuration sets one; an offset
+            # that is not tuned is the base configuration's in every trial, and the trial's own tau_active without one
+            tau = float(params.get("tau_active", self.base_config.tau_active))
+            fixed = getattr(self.base_config, "tau_offset", None)
+            if "tau_offset" not in params and fixed is None:
+                return [tau] if not self._hysteresis() else [tau, tau]
+            return [tau, float(params.get("tau_offset", fixed))]
         return [float(params.get(name, self._base_value(name))) for name in self.tunable]
 
+    def _hysteresis(self) -> bool:
+        """Does a trial of this study carry (tau_active, tau_offset)?"""
+        return (any(p.name == "tau_offset" for p in self.hparams) or
+                getattr(self.base_config, "tau_offset", None) is not None)
+
     def _base_value(self, name: str) -> float:
-        """The base configuration's value; delta_id is no field of a configuration: the constructor's."""
+        """The base configuration's value; delta_id is no field of a configuration: the constructor's.  A tau_offset of
+        None is the configuration's tau_active."""
+        if name == "tau_offset" and getattr(self.base_config, "tau_offset", None) is None:
+            return self.base_config.tau_active
         return self.delta_id if name == "delta_id" else getattr(self.base_config, name)
 
     def objective(self, params: Sequence[Dict[str, float]]) -> np.ndarray:

@@ -483,6 +483,15 @@ class _DiarizationEngine(_StepEngine):
     (``tail=True``) N aggregation / binarisation states, stepped on the C++ workers from a ticket's pinned
     segmentation scores and embeddings."""
 
+    def __new__(cls, *args, **kwargs):
+        # ``tau_offset=`` is refused by name by every engine that diarizes (StreamBatch, its GroupsBatch front door,
+        # WeSpeakerBatch): hysteresis is VadBatch's and OverlapBatch's.  Here and not as a keyword of the ``__init__``s,
+        # whose parameter lists are held equal to one another name by name (tests/test_wespeaker_engine_host.py): a
+        # parameter that exists only to be refused does not belong in them.
+        from .blocks.diarization import refuse_tau_offset
+        refuse_tau_offset(kwargs, cls.__name__)
+        return super().__new__(cls)
+
     def _setup_host(self, tau_active, rho_update, delta_new, gamma, beta, max_speakers, normalize_embedding_weights,
                     cluster_threads, tail, duration, step, latency) -> None:
         """The N clustering states and the parameters of the output tail (DelayedAggregation + Binarize of every stream,
@@ -631,7 +640,7 @@ class StreamBatch(_DiarizationEngine):
         # back then is a GroupsBatch, no StreamBatch, so Python does not call StreamBatch.__init__ on it.
         if cls is StreamBatch and isinstance(embedding, _HipGroupsEmbedding):
             return GroupsBatch(segmentation, embedding, *args, **kwargs)
-        return super().__new__(cls)
+        return super().__new__(cls, **kwargs)     # (_DiarizationEngine.__new__ looks at the keywords)
 
     def __init__(self, segmentation: HipSegmentation, embedding: HipEmbedding, num_streams: int,
                  tau_active: float = 0.6, rho_update: float = 0.3, delta_new: float = 1.0,
@@ -927,7 +936,9 @@ class VadBatch(_StepEngine):
     No embedding network and no clustering: the step is the segmentation chain alone.  The engine choices are
     ``StreamBatch``'s (``lanes``, ``recurrence``, ``inflight``, ``wait``, ``warmup``, ``DZ_ENGINE``): with >= 64
     streams in the default precision the matrix-core recurrence on ``THROUGHPUT_LANES`` lanes.  ``host_threads``:
-    threads of the output tail."""
+    threads of the output tail.  ``tau_offset``: hysteresis (``dz_tail_set_offset``) — a frame of a stream stays on while
+    its aggregated score is > ``tau_offset``; the state is per stream, crosses the steps and is cleared by
+    ``reset(slot)``.  None: the single threshold."""
 
     LABEL = "speech"            # what the turns of `detect` are called (OverlapBatch: "overlap")
 
@@ -935,7 +946,10 @@ class VadBatch(_StepEngine):
                  duration: float = 5.0, step: float = 0.5, latency: Optional[float] = None,
                  device: Optional[torch.device] = None, *, lanes: Optional[int] = None,
                  recurrence: Optional[str] = None, inflight: Optional[int] = None, wait: Optional[str] = None,
-                 warmup: Optional[int] = None, host_threads: int = 8, serial: bool = False):
+                 warmup: Optional[int] = None, host_threads: int = 8, serial: bool = False,
+                 tau_offset: Optional[float] = None):
+        from .blocks.base import check_tau_offset
+        self.tau_offset = check_tau_offset(tau_offset, type(self).__name__)      # (before the GPU is touched)
         if serial:
             raise ValueError("VadBatch: serial=True is the measurement engine of StreamBatch (bench.py's roofline "
                              "pass); the VAD engine has no serial form")
@@ -975,7 +989,8 @@ class VadBatch(_StepEngine):
 
     def _make_tail(self, F: int) -> BatchedOutputTail:
         return BatchedOutputTail(self.n, F, 1, self.step, self.latency, self.tau_active,
-                                 strategy="hamming", cropping_mode="loose", num_threads=self.host_threads)
+                                 strategy="hamming", cropping_mode="loose", num_threads=self.host_threads,
+                                 offset=self.tau_offset)
 
     def _new_slot(self, shape: tuple) -> dict:
         (F,), n, dev, K = shape, self.n, self.device, self.seg.num_speakers
@@ -1264,7 +1279,7 @@ class FileBatch:
                  latency: Optional[float] = None, sample_rate: int = 16000,
                  device: Optional[torch.device] = None, threads: int = 8, patch_collar: float = 0.05,
                  recurrence: Optional[str] = "valu", lanes: Optional[int] = 2, pipeline: str = "diarization",
-                 gather: Optional[bool] = None):
+                 gather: Optional[bool] = None, tau_offset: Optional[float] = None):
         """``recurrence`` / ``lanes``: the engine under the files.  A file job is short and its files end at different
         times: the latency-form recurrence on two lanes finishes 16 ten-minute files 13 - 40 % sooner than the
         throughput engine a 64-row ``StreamBatch`` would pick for itself (profiles/r06q_file_batch_engine.json:
@@ -1274,10 +1289,17 @@ class FileBatch:
         byte; two lanes are what the two-chain engines run anyway (gigabytes of arena per lane).
 
         ``pipeline``: "diarization" | "vad" | "osd" (``embedding`` must be None for the last two).  ``gather``: fill a step's stage with one
-        ``dz_gather_windows`` launch instead of one torch copy per open file (None = the form's default)."""
+        ``dz_gather_windows`` launch instead of one torch copy per open file (None = the form's default).
+        ``tau_offset``: the hysteresis of the "vad" and "osd" forms (every file's tail starts with the state off);
+        ``pipeline="diarization"`` refuses it."""
         self.rows, self.max_files = int(rows), max(1, min(int(max_files), int(rows)))
         if pipeline not in ("diarization", "vad", "osd"):
             raise ValueError(f"FileBatch: pipeline={pipeline!r} (expected diarization | vad | osd)")
+        if tau_offset is not None and pipeline == "diarization":
+            from .blocks.diarization import refuse_tau_offset
+            refuse_tau_offset({"tau_offset": tau_offset}, "FileBatch(pipeline='diarization')")
+        from .blocks.base import check_tau_offset
+        self.tau_offset = check_tau_offset(tau_offset, "FileBatch")
         if pipeline in ("vad", "osd"):
             if embedding is not None:
                 raise ValueError(f"FileBatch(pipeline={pipeline!r}) takes no embedding")
@@ -1326,7 +1348,7 @@ class FileBatch:
             self._clu.append(h)
         # DelayedAggregation(hamming, loose) + Binarize: what both pipelines build (the VAD form: one "speaker")
         self._tails = BatchedOutputTail(self.max_files, F, self.G, self.step, self.latency, self.tau,
-                                        num_threads=self.threads)
+                                        num_threads=self.threads, offset=self.tau_offset)
         self._F = F
         self._max_turns = self._tails.max_turns
         n = self.engine.max_inflight + 1

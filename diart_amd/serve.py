@@ -89,9 +89,19 @@ class StreamServer:
                  engine: Optional[Callable] = None, device_rings=True,
                  normalize_embedding_weights: bool = False, input_sample_rate: Optional[int] = None,
                  pipeline: str = "diarization", input_format: str = "f32", input_channels: int = 1,
-                 volume_in_db: Optional[float] = None):
+                 volume_in_db: Optional[float] = None, tau_offset: Optional[float] = None):
         if pipeline not in PIPELINES:
             raise ValueError(f"StreamServer: pipeline={pipeline!r} (expected one of {PIPELINES})")
+        # hysteresis of the one-track pipelines (VadBatch / OverlapBatch keep the state per slot; a stream that joins
+        # gets a reset slot, so it starts with the state off); refused before anything touches the GPU
+        if tau_offset is not None and pipeline not in _ONE_TRACK:
+            from .blocks.diarization import refuse_tau_offset
+            refuse_tau_offset({"tau_offset": tau_offset}, "StreamServer(pipeline='diarization')")
+        from .blocks.base import check_tau_offset
+        self.tau_offset = check_tau_offset(tau_offset, "StreamServer")
+        if self.tau_offset is not None and engine is not None:
+            raise ValueError("StreamServer: tau_offset is the default engine's (VadBatch / OverlapBatch); a custom "
+                             "engine= binarises on its own")
         if pipeline in _ONE_TRACK and embedding is not None:
             raise ValueError(f"StreamServer: pipeline={pipeline!r} ({_ONE_TRACK[pipeline][0]}) runs the segmentation "
                              "only; pass embedding=None")
@@ -137,7 +147,7 @@ class StreamServer:
         if engine is None and pipeline in _ONE_TRACK:
             batch_cls = _ONE_TRACK[pipeline][1]
             self.batch = batch_cls(segmentation, self.max_streams, tau_active, duration=duration, step=step,
-                                   latency=self.latency, device=device)
+                                   latency=self.latency, device=device, tau_offset=self.tau_offset)
         elif engine is None:
             # the WeSpeaker ResNet34 embedding has an engine of its own (its trunk is the long chain of a step)
             batch_cls = WeSpeakerBatch if isinstance(embedding, HipWeSpeakerEmbedding) else StreamBatch

@@ -39,6 +39,10 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--step", default=0.5, type=float, help="Sliding window step in seconds. Defaults to 0.5")
     ap.add_argument("--latency", default=0.5, type=float, help="System latency in seconds. Defaults to 0.5")
     ap.add_argument("--tau-active", default=0.5, type=float, help="Base value of tau_active. Defaults to 0.5")
+    ap.add_argument("--tau-offset", default=None, type=float,
+                    help="Base value of tau_offset, the offset threshold of the hysteresis of VoiceActivityDetection and "
+                         "OverlappedSpeechDetection (a frame stays on while its score is above it). Defaults to none: the "
+                         "single threshold tau_active")
     ap.add_argument("--rho-update", default=0.3, type=float, help="Base value of rho_update. Defaults to 0.3")
     ap.add_argument("--delta-new", default=1, type=float, help="Base value of delta_new. Defaults to 1")
     ap.add_argument("--gamma", default=3, type=float, help="Overlapped-speech-penalty gamma. Defaults to 3")
@@ -53,7 +57,8 @@ def parser() -> argparse.ArgumentParser:
                          "device (on the GPU, beside the replay; not with --cpu)")
     ap.add_argument("--hparams", nargs="+", default=None,
                     help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three); "
-                         "tau_active alone with --pipeline VoiceActivityDetection or OverlappedSpeechDetection; with --gallery "
+                         "tau_active alone with --pipeline VoiceActivityDetection or OverlappedSpeechDetection, where tau_offset "
+                         "can be named beside it (hysteresis); with --gallery "
                          "also delta_id (the default is then all four)")
     ap.add_argument("--gallery", type=str, default=None,
                     help="A SpeakerGallery file (.npz): tune delta_id too, against the identification error rate")
@@ -99,8 +104,12 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
         pipeline_class, cache_class = ((OverlappedSpeechDetection, OsdTuneCache) if osd else
                                        (VoiceActivityDetection, VadTuneCache))
         base_config = pipeline_class.get_config_class()(segmentation=seg, duration=args.duration, step=args.step,
-                                                        latency=args.latency, tau_active=args.tau_active, device=None)
+                                                        latency=args.latency, tau_active=args.tau_active, device=None,
+                                                        tau_offset=getattr(args, "tau_offset", None))
     else:
+        if getattr(args, "tau_offset", None) is not None or "tau_offset" in (args.hparams or []):
+            raise SystemExit("tau_offset is not a parameter of SpeakerDiarization: hysteresis is tuned with --pipeline "
+                             "VoiceActivityDetection or OverlappedSpeechDetection")
         pipeline_class, cache_class = SpeakerDiarization, TuneCache
         base_config = SpeakerDiarizationConfig(
             segmentation=seg, embedding=emb, duration=args.duration, step=args.step, latency=args.latency,
@@ -108,10 +117,15 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
             beta=args.beta, max_speakers=args.max_speakers, normalize_embedding_weights=args.normalize_embedding_weights,
             device=None)
     possible = list(pipeline_class.hyper_parameters())
+    default = [hp.name for hp in possible]
+    if vad:
+        from .blocks.base import TauOffset
+        possible = possible + [TauOffset]            # tuned on request (--hparams tau_active tau_offset), never by default
     if gallery is not None:
         from .blocks.base import DeltaId
         possible, cache_class = possible + [DeltaId], IdentTuneCache
-    names = args.hparams or [hp.name for hp in possible]
+        default = [hp.name for hp in possible]
+    names = args.hparams or default
     hparams = [hp for hp in (HyperParameter.from_name(name) for name in names) if hp in possible]
     if not hparams:
         raise SystemExit("No hyper-parameters to optimize. Make sure to select one of: "

@@ -978,7 +978,16 @@ typedef struct dz_tail dz_tail;
 int dz_tail_create(int frames, int speakers, double step, double latency, double threshold,
                    int strategy, int cropping_mode, const double* hamming /* [frames] */,
                    dz_tail** out);
-int dz_tail_reset(dz_tail* t);
+int dz_tail_reset(dz_tail* t);                 /* forgets the buffers and the hysteresis states; keeps the offset */
+/* Hysteresis (pyannote's onset / offset): from the next step on a row of a speaker column is on when its score is
+ * > threshold while the column is off and > offset while it is on.  The state is kept per speaker column, starts off,
+ * crosses from a step into the next one and is cleared by dz_tail_reset; a NaN row is off and leaves the state off.
+ * The turns are formed from `on` as before (the row after a step's last closes an open turn).  Valid for any speaker
+ * count; any finite offset is accepted, offset == threshold being `score > threshold` row for row, and a non-finite one
+ * is status 2.  A tail on which this was never called runs the stateless walk.  A step that returns 5 (more turns
+ * than max_turns) has still moved every column's state over all of its rows; like any failed step it leaves its buffer
+ * in the handle, so reset the handle before the stream goes on.                                                     */
+int dz_tail_set_offset(dz_tail* t, double offset);
 int dz_tail_destroy(dz_tail* t);
 int dz_tail_max_rows(const dz_tail* t);
 int dz_tail_speakers(const dz_tail* t);      /* the `speakers` it was created with */
@@ -1144,6 +1153,27 @@ int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, doub
                      const double* mids, const int* mid_cell, const int* file_cell_off,
                      const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
                      int num_threads);
+/* The track pipelines with hysteresis: d_taus / taus are (T, 2) = (tau_active, tau_offset) per trial,
+ * a row is on when agg > tau_active while the track is off and > tau_offset while it is on (dz_tail_set_offset's rule),
+ * the state off at every file's first step and carried across its steps.  All other arguments are those of
+ * dz_tune_vad_score / dz_tune_vad_host.  One workgroup per (trial, file) for the components and for the masks: the
+ * lanes compose the state maps of their steps before they walk them, so every row's `on` is the sequential rule's.
+ * The host form needs mids .. ref_prefix and lanes (1 .. 256) for the masks too, and returns 2 for a non-finite
+ * tau_offset; the device form cannot read d_taus: its callers check them first.                                     */
+int dz_tune_vad_score_hyst(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
+                           const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
+                           const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
+                           const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
+                           unsigned* d_bits, void* stream);
+int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+                          const double* mids, const int* mid_cell, const int* file_cell_off,
+                          const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
+                          int num_threads);
+/* The masks of the same trials from an independent text: one dz_tail handle per (trial, file) with dz_tail_set_offset,
+ * fed the file's track step by step (starts, resolution (chunks), step, latency as dz_tail_step gets them), the
+ * masks read back from the turns it returns.  bits (T, total_rows).                                                  */
+int dz_tune_vad_replay_tails(const dz_tune_desc* d, const double* taus, int trials, double step, double latency,
+                             const double* starts, const double* resolution, unsigned* bits, int num_threads);
 /* Tuning delta_id, the identification distance of a speaker gallery.  A trial's names are the
  * rule of the live engines replayed over the assignments dz_tune_replay wrote: per global speaker the closest
  * match so far, a step's local speaker k with assign = g, match_index = e >= 0 and

@@ -11,7 +11,16 @@ the wall time of a `Benchmark` call on the blocks path — what a trial costs wi
 
 `--pipeline osd` measures the OverlappedSpeechDetection tuner (`OsdTuneCache`: the same kernels behind the overlap track)
 and the VAD tuner beside it, in one process on the same files: the references are then three made-up speakers whose
-turns overlap, `collect` is timed once per cache and every `evaluate` figure is taken for both caches in turn."""
+turns overlap, `collect` is timed once per cache and every `evaluate` figure is taken for both caches in turn.
+
+`--hysteresis` measures the two-threshold path beside the single threshold, for both caches on the dataset of
+`--pipeline osd`: per T the wall time of `evaluate` and the device time of the scoring kernel for `(T,)` taus
+(tune_vad_score_kernel, what the parent commit runs: its own `--pipeline osd` rows on the same files are the yardstick,
+taken in a child process of their own) and for `(T, 2)` taus (tune_vad_hyst_kernel), with a band of 0.2 under every
+tau and with equal columns.  EXPECTATION, written before the first run: the new kernel adds one pass over a lane's
+rows (two compares per row, no time stamps read) and a fold over at most 255 bytes of LDS to two walks that read the
+time stamps and the prefix sums, so its device time should stay well under twice the plain kernel's at every T — a
+supposition; the tool reports the ratio whichever way it falls."""
 import argparse
 import ctypes as C
 import json
@@ -69,6 +78,26 @@ def evaluate_rows(cache, trials, reps: int, threads: int, device, rng) -> list:
     return rows
 
 
+def hysteresis_rows(cache, trials, reps: int, device, rng) -> list:
+    """Per T: (T,) taus on today's kernel, (T, 2) taus with a band and with equal columns on the hysteresis kernel."""
+    rows = []
+    for T in trials:
+        taus = np.concatenate([[0.6], rng.uniform(0, 1, size=T - 1)])
+        forms = dict(plain=taus, band=np.stack([taus, taus - 0.2], axis=1), equal=np.stack([taus, taus], axis=1))
+        row = dict(trials=T)
+        for name, t in forms.items():
+            cache.evaluate(t, backend="gpu")
+            row[f"{name}_evaluate"] = median_ms(lambda: cache.evaluate(t, backend="gpu"), reps)
+            row[f"{name}_kernel"] = events_ms(lambda: cache._gpu(cache._taus(t), False, True, device), device, reps)
+        a, b = cache.evaluate(forms["plain"], backend="gpu"), cache.evaluate(forms["equal"], backend="gpu")
+        row["equal_columns_are_plain_bit_for_bit"] = bool(np.array_equal(a.per_file, b.per_file))
+        for name in ("band", "equal"):
+            row[f"{name}_kernel_over_plain"] = row[f"{name}_kernel"]["median_ms"] / row["plain_kernel"]["median_ms"]
+            row[f"{name}_evaluate_over_plain"] = row[f"{name}_evaluate"]["median_ms"] / row["plain_evaluate"]["median_ms"]
+        rows.append(row)
+    return rows
+
+
 def both_pipelines(args, device) -> dict:
     """--pipeline osd: the two detection caches collected from the same files, measured side by side."""
     from diart_amd.blocks.osd import OverlappedSpeechDetection, OverlappedSpeechDetectionConfig
@@ -100,7 +129,10 @@ def both_pipelines(args, device) -> dict:
         torch.cuda.synchronize(device)
         out[name]["upload_and_rows_ms"] = 1e3 * (time.perf_counter() - t)
     for name, cache in caches.items():
-        out[name]["rows"] = evaluate_rows(cache, args.trials, args.reps, args.threads, device, np.random.default_rng(0))
+        if args.hysteresis:
+            out[name]["rows"] = hysteresis_rows(cache, args.trials, args.reps, device, np.random.default_rng(0))
+        else:
+            out[name]["rows"] = evaluate_rows(cache, args.trials, args.reps, args.threads, device, np.random.default_rng(0))
         for row in out[name]["rows"]:
             print(name, json.dumps(row), flush=True)
     return out
@@ -111,6 +143,8 @@ def main():
     ap.add_argument("--pipeline", default="vad", choices=("vad", "osd"),
                     help="vad: the VoiceActivityDetection tuner (the default); osd: the OverlappedSpeechDetection tuner "
                          "with the VAD tuner beside it")
+    ap.add_argument("--hysteresis", action="store_true",
+                    help="(T, 2) taus = (tau_active, tau_offset) beside (T,) taus, for both caches (implies --pipeline osd)")
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=600.0)
     ap.add_argument("--trials", type=int, nargs="+", default=[1, 64, 1024])
@@ -122,12 +156,15 @@ def main():
     ap.add_argument("--out", type=str, default=None,
                     help="profiles/r20a_tune_vad.json, profiles/r29a_tune_osd.json with --pipeline osd")
     args = ap.parse_args()
-    args.out = args.out or str(ROOT / "profiles" / ("r29a_tune_osd.json" if args.pipeline == "osd" else "r20a_tune_vad.json"))
+    if args.hysteresis:
+        args.pipeline = "osd"
+    args.out = args.out or str(ROOT / "profiles" / ("r32a_tune_hysteresis.json" if args.hysteresis else
+                                                     "r29a_tune_osd.json" if args.pipeline == "osd" else "r20a_tune_vad.json"))
     if not torch.cuda.is_available():
         raise SystemExit("tune_vad_bench.py measures on a GPU; there is none")
     device = torch.device("cuda", 0)
     if args.pipeline == "osd":
-        out = dict(tool="tools/tune_vad_bench.py --pipeline osd", files=args.files, seconds=args.seconds, latency=args.latency,
+        out = dict(tool="tools/tune_vad_bench.py " + ("--hysteresis" if args.hysteresis else "--pipeline osd"), files=args.files, seconds=args.seconds, latency=args.latency,
                    batch_size=args.batch_size, host_threads=args.threads, reps=args.reps, gpu=torch.cuda.get_device_name(0))
         out.update(both_pipelines(args, device))
         line = json.dumps(out)

@@ -9,6 +9,7 @@ of the stream counts, steps and precisions asked for.  One JSON line:
 xRT = windows per second x step (a stream needs 1 / step windows per second of audio).
 
     python tools/vad_streams.py [--streams 64,256] [--step 0.5,0.25] [--precision both] [--steps 40] [--warmup 10]
+                                [--tau-offset 0.4]
 """
 import argparse
 import json
@@ -25,12 +26,12 @@ from diart_amd.pipeline import VadBatch  # noqa: E402
 from diart_amd.synth import synth_segmentation_state, synth_streams  # noqa: E402
 
 
-def one(n, step, precision, args, audio, device, state):
+def one(n, step, precision, args, audio, device, state, tau_offset=None):
     hop, S = int(round(16000 * step)), 80000
     torch.cuda.synchronize(device)
     free0 = torch.cuda.mem_get_info(device)[0]
     pipe = VadBatch(HipSegmentation(state, max_batch=n, precision=precision), n, step=step, device=device,
-                    lanes=args.lanes or None)
+                    lanes=args.lanes or None, **({} if tau_offset is None else dict(tau_offset=tau_offset)))
 
     def run(t0, count):
         inflight = []
@@ -51,7 +52,7 @@ def one(n, step, precision, args, audio, device, state):
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
     host = dict(pipe.host_seconds)
-    out = {"streams": n, "step_s": step, "precision": precision, "xrt": round(n * args.steps / elapsed * step, 1),
+    out = {"streams": n, "step_s": step, "precision": precision, "tau_offset": tau_offset, "xrt": round(n * args.steps / elapsed * step, 1),
            "ms_per_step": round(1e3 * elapsed / args.steps, 3), "steps": args.steps, "warmup": args.warmup,
            "lanes": pipe.depth, "inflight": pipe.max_inflight, "recurrence": pipe.recurrence or "model",
            "host_wait_s": round(host["wait"], 4), "host_work_s": round(host["work"], 4),
@@ -69,6 +70,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--lanes", type=int, default=0, help="VadBatch(lanes=) (default: the engine's choice)")
     ap.add_argument("--precision", default="both", choices=["both", "f16x3", "f32"])
+    ap.add_argument("--tau-offset", type=float, default=None,
+                    help="hysteresis: measure every combination without and with this offset threshold, in this process, "
+                         "in both build orders (without, with, with, without)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("vad_streams.py needs an MI355X GPU (the HIP path has no CPU fallback)")
@@ -85,8 +89,10 @@ def main():
     for n in counts:
         for step in steps:
             for p in precs:
-                runs.append(one(n, step, p, args, audio, device, state))
-                print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+                offsets = [None] if args.tau_offset is None else [None, args.tau_offset, args.tau_offset, None]
+                for off in offsets:
+                    runs.append(one(n, step, p, args, audio, device, state, off))
+                    print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
     print(json.dumps({"tool": "vad_streams", "window_s": 5.0, "gpu": torch.cuda.get_device_name(device),
                       "runs": runs}))
 
