@@ -17,18 +17,10 @@
 // from dz_tune_score is the order of the sums.  No contraction, as in k_tune.hip.
 #pragma clang fp contract(off)
 #include "dz_common.h"
+#define TC_KERNEL_UNIT 1   // tune_core.h: TcDeviceLanes
 #include "tune_core.h"
 
 namespace {
-
-struct ScoreLanes {
-    int nl;
-    template <typename F>
-    __device__ void operator()(F f) const {
-        f((int)threadIdx.x);
-        __syncthreads();
-    }
-};
 
 __global__ __launch_bounds__(TC_SCORE_LANES) void tune_score_kernel(
     const unsigned* __restrict__ bits, int trials, int n_files, int total_rows, const int* __restrict__ file_chunk_off,
@@ -38,18 +30,11 @@ __global__ __launch_bounds__(TC_SCORE_LANES) void tune_score_kernel(
     double* __restrict__ out, unsigned* scratch, int* err) {
     __shared__ TcScoreShared sh;
     unsigned* slice = scratch + (size_t)blockIdx.x * ((size_t)max_cells + 1);
-    const long long pairs = (long long)trials * n_files;
-    for (long long pair = blockIdx.x; pair < pairs; pair += gridDim.x) {
-        const int t = (int)(pair / n_files), n = (int)(pair - (long long)t * n_files);
-        const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
-        if (ncell < 0 || ncell > max_cells) {   // (the same for every lane) the file does not fit a slice
-            if (threadIdx.x == 0) tc_err_raise(err, TC_SCORE_ERR_ARGS);
-            continue;
-        }
-        const TcScoreIn in = {bits + (size_t)t * total_rows, row_off, mids, mid_cell, cell_dur + cell0, cell_ref + cell0,
-                              file_chunk_off[n], file_chunk_off[n + 1], ncell, max_speakers, collar};
-        tc_score_pair(in, sh, slice, out + (size_t)pair * 5, err, ScoreLanes{TC_SCORE_LANES});
-    }
+    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
+                              cell_dur, cell_ref, max_cells, max_speakers, collar};
+    tc_score_pairs(call, blockIdx.x, gridDim.x, threadIdx.x == 0, err, [&](long long pair, int, int, const TcScoreIn& in) {
+        tc_score_pair(in, sh, slice, out + (size_t)pair * 5, err, TcDeviceLanes{TC_SCORE_LANES});
+    });
 }
 
 }  // namespace

@@ -6,10 +6,12 @@
 // tail are tail_core.h's, the text dz_tail_step runs too: the clipped rows, the Hamming-weighted sum of a row, the
 // edge walk of Binarize; what this file adds there is the plan's layout and the merging of the turns.  Host and device
 // compile this text: k_tune.hip for the kernels, tune_score.cpp for backend="core", which tests/test_tune_host.py
-// holds against dz_clu_step + dz_tail_step.  The VoiceActivityDetection half (tc_vad_*, behind the replay) is
-// k_tune_vad.hip's and dz_tune_vad_host's in the same way — with its hysteresis form (tc_hyst_*: the lanes' state maps,
-// DESIGN.md 4.21), tune_vad_hyst_kernel's and dz_tune_vad_host_hyst's — and the scoring of the diarization masks (tc_score_*, at the
-// end) is k_tune_score.hip's and dz_tune_score_core's.
+// holds against dz_clu_step + dz_tail_step.  The track pipelines' half (tc_vad_row and tc_track_pair<Rule>, behind the
+// replay: one pair routine for the single threshold and for hysteresis, whose lanes' state maps are DESIGN.md 4.21) is
+// k_tune_vad.hip's and dz_tune_vad_host's / dz_tune_vad_host_hyst's in the same way, and the scoring of the diarization
+// masks (tc_score_*, at the end) is k_tune_score.hip's and dz_tune_score_core's.  Three things are said once for all
+// of them: how lanes share a range (tc_lane_steps), how workgroups share the pairs of a scoring call (tc_score_pairs),
+// and what a phase over the lanes is on the device (TcDeviceLanes; the host's LanesInTurn is tune_score.cpp's).
 #pragma once
 #include "../../include/diart_amd.h"
 #include "clu_core.h"
@@ -193,14 +195,8 @@ TC_HD TcVadEnd tc_turn_walk(On on_row, Add add, const int* row_off, const double
     return end;
 }
 
-// VoiceActivityDetection's walk under one tau: row r is speech when agg > tau, and the durations a turn adds are
-// differences of the file's prefix sums (dur_prefix / ref_prefix: ncell + 1 values, cell_dur and cell_dur where the
-// reference is active, summed in order).
-struct TcVadOn {
-    const double* agg;
-    double tau;
-    TC_HD bool operator()(int p) const { return agg[p] > tau; }
-};
+// The durations a turn of a track adds are differences of the file's prefix sums (dur_prefix / ref_prefix: ncell + 1
+// values, cell_dur and cell_dur where the reference is active, summed in order).
 struct TcVadAdd {
     const double *dur_prefix, *ref_prefix;
     TcVadSum* sum;
@@ -209,12 +205,9 @@ struct TcVadAdd {
         sum->both += ref_prefix[to] - ref_prefix[from];
     }
 };
-TC_HD TcVadEnd tc_vad_walk(const double* agg, const int* row_off, const double* mids, const int* mid_cell,
-                           const double* dur_prefix, const double* ref_prefix, double tau, double collar, int c_lo,
-                           int c_hi, TcVadEnd end, TcVadSum* sum) {
-    return tc_turn_walk(TcVadOn{agg, tau}, TcVadAdd{dur_prefix, ref_prefix, sum}, row_off, mids, mid_cell, collar, c_lo, c_hi,
-                        end);
-}
+struct TcNoAdd {
+    TC_HD void operator()(int, int) const {}
+};
 
 // The five components (metrics.COMPONENTS) of DetectionErrorRate as dz_tune_score builds them for one hypothesis
 // label and one reference label: the confusion is 0.
@@ -227,98 +220,138 @@ TC_HD void tc_vad_components(double total, TcVadSum s, double* o) {
     o[4] = 0.0;
 }
 
-// How a workgroup of nl lanes shares a file of `chunks` steps: lane i walks steps [i * per, (i + 1) * per).
-TC_HD int tc_vad_steps_per_lane(int chunks, int nl) { return (chunks + nl - 1) / nl; }
+// How a workgroup of nl lanes shares a file of `chunks` steps from c0 on: lane i walks steps [i * per, (i + 1) * per),
+// clipped to the file (a lane behind the last step has lo == hi).  In long long: lane * per passes 2^31 for a file that
+// itself fits an int.
+struct TcSteps {
+    int lo, hi;
+};
+TC_HD TcSteps tc_lane_steps(int c0, int chunks, int lane, int nl) {
+    const long long per = ((unsigned)chunks + (unsigned)nl - 1u) / (unsigned)nl, at = lane * per;   // (a 32-bit quotient)
+    const long long lo = at < chunks ? at : chunks, hi = lo + per < chunks ? lo + per : chunks;
+    return {c0 + (int)lo, c0 + (int)hi};
+}
 
 // ---------------------------------------------------------------------------------------------------------
-// The track pipelines with hysteresis (tail_hyst_on: a row is on when agg > tau_active while the track is off and
-// > tau_offset while it is on; the state is off at a file's first row and is carried across its steps).  A row now
-// depends on the row before it, and a lane that walks steps [i * per, (i + 1) * per) does not know the state its first
-// row finds.  It does know what its rows make of either state: tc_hyst_map runs the machine from "off" and from "on"
-// at once over the lane's rows and returns both out-states, two bits.  These maps compose (tc_hyst_apply), a lane
-// without rows is the identity, and the state lane i starts from is the lanes 0 .. i - 1 applied in order to "off".
-// Nothing is approximated: the rule is a function of (state, score), every lane applies that function to exactly the
-// rows the sequential walk would, in their order, and composing functions is associative; the `on` of every row is
-// therefore the sequential machine's, bit for bit.  From there the two walks are tune_vad_score_kernel's.
+// One (trial, file) pair of a track pipeline, by the `nl` lanes of one workgroup: tc_track_pair<Rule>.
+//
+// The rule says whether a row is on: TcPlainRule, agg > tau, or TcHystRule (tail_hyst_on: agg > tau_active while the
+// track is off and > tau_offset while it is on; the state is off at a file's first row and is carried across its
+// steps).  Under the stateful rule a row depends on the row before it, and a lane that walks steps [i * per,
+// (i + 1) * per) does not know the state its first row finds.  It does know what its rows make of either state:
+// tc_state_map runs the machine from "off" and from "on" at once over the lane's rows and returns both out-states, two
+// bits.  These maps compose (tc_state_apply), a lane without rows is the identity, and the state lane i starts from is
+// the lanes 0 .. i - 1 applied in order to "off".  Nothing is approximated: the rule is a function of (state, score),
+// every lane applies that function to exactly the rows the sequential walk would, in their order, and composing
+// functions is associative; the `on` of every row is therefore the sequential machine's, bit for bit.  The stateless
+// rule has no such phase (if constexpr) and no map and start arrays in its shared struct.  With tau_offset ==
+// tau_active the stateful rule IS the stateless one, and the two give the same doubles.
+//
+// Then, for either rule, every lane walks its steps twice (tc_turn_walk): first alone, for the end of its
+// latest-ending turn; an exclusive running maximum of those ends over the lanes, strictly greater in lane order
+// (-infinity for a lane without a turn, so it carries across any number of empty steps), is "the end of the last turn
+// before this lane"; then again from that end, summing the durations its turns add.  Lane 0 adds the lanes' sums in
+// lane order and writes the five components.
 //
 // Written as phases over the lanes, as tc_score_cells is: lanes(f) runs f(lane) for every lane and ends with the
-// workgroup's barrier (k_tune_vad.hip), or plays the lanes in order (dz_tune_vad_host_hyst).  `out` (5 components) and
-// `bits` (this trial's masks, indexed by packed row) may each be NULL.  No atomics, plain compares.
+// workgroup's barrier (k_tune_vad.hip), or plays the lanes in order (tune_score.cpp).  `out` (5 components) and `bits`
+// (this trial's masks, indexed by packed row) may each be NULL, not both.  No atomics, plain compares.
 // ---------------------------------------------------------------------------------------------------------
-TC_HD unsigned tc_hyst_map(const double* agg, int p0, int p1, double tau_active, double tau_offset) {
+struct TcPlainRule {   // taus (T,)
+    static constexpr bool stateful = false;
+    double tau;
+    static TC_HD TcPlainRule of(const double* taus, int t) { return {taus[t]}; }
+    TC_HD bool operator()(double y, bool) const { return y > tau; }
+};
+struct TcHystRule {    // taus (T, 2) = (tau_active, tau_offset)
+    static constexpr bool stateful = true;
+    double tau_active, tau_offset;
+    static TC_HD TcHystRule of(const double* taus, int t) { return {taus[2 * (long)t], taus[2 * (long)t + 1]}; }
+    TC_HD bool operator()(double y, bool active) const { return tail_hyst_on(y, tau_active, tau_offset, active); }
+};
+
+template <typename Rule>
+TC_HD unsigned tc_state_map(const Rule& rule, const double* agg, int p0, int p1) {
     bool from_off = false, from_on = true;
     for (int p = p0; p < p1; ++p) {
         const double y = agg[p];
-        from_off = tail_hyst_on(y, tau_active, tau_offset, from_off);
-        from_on = tail_hyst_on(y, tau_active, tau_offset, from_on);
+        from_off = rule(y, from_off);
+        from_on = rule(y, from_on);
     }
     return (from_off ? 1u : 0u) | (from_on ? 2u : 0u);
 }
-TC_HD bool tc_hyst_apply(unsigned map, bool active) { return (map >> (active ? 1 : 0)) & 1u; }
+TC_HD bool tc_state_apply(unsigned map, bool active) { return (map >> (active ? 1 : 0)) & 1u; }
 
-struct TcHystOn {   // tc_turn_walk asks for the rows of its steps once each and in order
+template <typename Rule>
+struct TcTrackOn {   // tc_turn_walk asks for the rows of its steps once each and in order
     const double* agg;
-    double tau_active, tau_offset;
+    Rule rule;
     bool* active;
-    TC_HD bool operator()(int p) const { return *active = tail_hyst_on(agg[p], tau_active, tau_offset, *active); }
+    TC_HD bool operator()(int p) const { return *active = rule(agg[p], *active); }
 };
 
-constexpr int TC_HYST_LANES = 256;   // the workgroup of tune_vad_hyst_kernel; the host plays at most as many
+constexpr int TC_TRACK_LANES = 256;   // the workgroup of tune_vad_score_kernel; the host plays at most as many
 
-struct TcHystIn {
+struct TcTrackIn {
     const double* agg;                        // (total_rows)
     const int* row_off;                       // (chunks + 1)
     const double* mids;                       // rows + 1 frame middles per step
     const int* mid_cell;
     const double *dur_prefix, *ref_prefix;    // THIS file's ncell + 1 prefix sums
     int c0, c1, ncell;
-    double tau_active, tau_offset, collar;
+    double collar;
 };
-struct TcHystShared {
-    double end_e[TC_HYST_LANES];
-    double sum_hyp[TC_HYST_LANES], sum_both[TC_HYST_LANES];
-    int end_cell[TC_HYST_LANES];
-    unsigned char map[TC_HYST_LANES];         // tc_hyst_map of every lane's rows
-    unsigned char start[TC_HYST_LANES];       // the state every lane's first row finds
+template <bool Stateful>
+struct TcTrackStates {                        // what the stateful rule keeps per lane; the stateless form carries none
+    unsigned char map[TC_TRACK_LANES];        // tc_state_map of every lane's rows
+    unsigned char start[TC_TRACK_LANES];      // the state every lane's first row finds
+};
+template <>
+struct TcTrackStates<false> {};
+template <bool Stateful>
+struct TcTrackShared : TcTrackStates<Stateful> {
+    double end_e[TC_TRACK_LANES];
+    double sum_hyp[TC_TRACK_LANES], sum_both[TC_TRACK_LANES];
+    int end_cell[TC_TRACK_LANES];
 };
 
-template <typename Lanes>
-TC_HD void tc_hyst_pair(const TcHystIn& in, TcHystShared& sh, double* out, unsigned* bits, Lanes lanes) {
+template <typename Rule, typename Lanes>
+TC_HD void tc_track_pair(const TcTrackIn& in, const Rule rule, TcTrackShared<Rule::stateful>& sh, double* out, unsigned* bits,
+                         Lanes lanes) {
     const int nl = lanes.nl, chunks = in.c1 - in.c0;
-    const int per = tc_vad_steps_per_lane(chunks, nl);
-    const double ta = in.tau_active, to = in.tau_offset;
     const TcVadEnd none = {-INFINITY, 0};
-    auto lo_of = [&](int lane) { return in.c0 + ((long long)lane * per < chunks ? lane * per : chunks); };
-    auto hi_of = [&](int lane) {
-        const int lo = lo_of(lane);
-        return lo + per < in.c1 ? lo + per : in.c1;
-    };
     // ---- every lane's state map
-    lanes([&](int lane) {
-        sh.map[lane] = (unsigned char)tc_hyst_map(in.agg, in.row_off[lo_of(lane)], in.row_off[hi_of(lane)], ta, to);
-    });
+    if constexpr (Rule::stateful)
+        lanes([&](int lane) {
+            const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
+            sh.map[lane] = (unsigned char)tc_state_map(rule, in.agg, in.row_off[my.lo], in.row_off[my.hi]);
+        });
     // ---- the maps composed in lane order; the masks; alone, the end of the lane's latest-ending turn
     lanes([&](int lane) {
+        const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
         bool start = false;
-        for (int j = 0; j < lane; ++j) start = tc_hyst_apply(sh.map[j], start);
-        sh.start[lane] = start ? 1 : 0;
+        if constexpr (Rule::stateful) {
+            for (int j = 0; j < lane; ++j) start = tc_state_apply(sh.map[j], start);
+            sh.start[lane] = start ? 1 : 0;
+        }
         if (bits) {
             bool active = start;
-            for (int p = in.row_off[lo_of(lane)], p1 = in.row_off[hi_of(lane)]; p < p1; ++p) {
-                active = tail_hyst_on(in.agg[p], ta, to, active);
+            for (int p = in.row_off[my.lo], p1 = in.row_off[my.hi]; p < p1; ++p) {
+                active = rule(in.agg[p], active);
                 bits[p] = active ? 1u : 0u;
             }
         }
         if (!out) return;
         bool active = start;
-        const TcVadEnd own = tc_turn_walk(TcHystOn{in.agg, ta, to, &active}, [](int, int) {}, in.row_off, in.mids,
-                                          in.mid_cell, in.collar, lo_of(lane), hi_of(lane), none);
+        const TcVadEnd own = tc_turn_walk(TcTrackOn<Rule>{in.agg, rule, &active}, TcNoAdd{}, in.row_off, in.mids, in.mid_cell,
+                                          in.collar, my.lo, my.hi, none);
         sh.end_e[lane] = own.e;
         sh.end_cell[lane] = own.cell;
     });
     if (!out) return;
     // ---- again from the end of the last turn before the lane, summing what its turns add
     lanes([&](int lane) {
+        const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
         TcVadEnd before = none;
         for (int j = 0; j < lane; ++j)
             if (sh.end_e[j] > before.e) {
@@ -326,9 +359,10 @@ TC_HD void tc_hyst_pair(const TcHystIn& in, TcHystShared& sh, double* out, unsig
                 before.cell = sh.end_cell[j];
             }
         TcVadSum s = {0.0, 0.0};
-        bool active = sh.start[lane] != 0;
-        tc_turn_walk(TcHystOn{in.agg, ta, to, &active}, TcVadAdd{in.dur_prefix, in.ref_prefix, &s}, in.row_off, in.mids,
-                     in.mid_cell, in.collar, lo_of(lane), hi_of(lane), before);
+        bool active = false;
+        if constexpr (Rule::stateful) active = sh.start[lane] != 0;
+        tc_turn_walk(TcTrackOn<Rule>{in.agg, rule, &active}, TcVadAdd{in.dur_prefix, in.ref_prefix, &s}, in.row_off, in.mids,
+                     in.mid_cell, in.collar, my.lo, my.hi, before);
         sh.sum_hyp[lane] = s.hyp;
         sh.sum_both[lane] = s.both;
     });
@@ -348,7 +382,7 @@ TC_HD void tc_hyst_pair(const TcHystIn& in, TcHystShared& sh, double* out, unsig
 // (bit g of a row = global speaker g is active), as dz_tune_score forms them, by the `nl` lanes of one workgroup.
 //
 // Turns and their merging are tc_turn_walk's, per label: lane i walks steps [i * per, (i + 1) * per) twice, as
-// tune_vad_score_kernel does (alone for the end of its latest-ending turn, then from the running maximum of the
+// tc_track_pair does (alone for the end of its latest-ending turn, then from the running maximum of the
 // lanes before it).  The covered ranges of one label are disjoint, so a range [from, to) is recorded by toggling
 // bit g of words `from` and `to` of the pair's scratch slice (ncell + 1 words, integer atomic XOR); a prefix XOR
 // over the words then IS the hypothesis mask of every scoring cell.  Every sum over the cells is formed per lane
@@ -434,13 +468,52 @@ struct TcScoreShared {
     int nh, nr, err;
 };
 
+// The pairs of one scoring call as its `blocks` workgroups share them: workgroup `block` takes pairs block,
+// block + blocks, ... and hands score(pair, t, cell0, in) each of them with the pair's slice of the call's arrays.  A
+// file with more cells than a scratch slice holds is skipped and raises TC_SCORE_ERR_ARGS (`raises`: one lane's job).
+struct TcScoreCall {
+    const unsigned* bits;                 // (trials, total_rows)
+    int trials, n_files, total_rows;
+    const int *file_chunk_off, *row_off;
+    const double* mids;
+    const int *mid_cell, *file_cell_off;
+    const double* cell_dur;
+    const unsigned long long* cell_ref;
+    int max_cells, max_speakers;
+    double collar;
+};
+template <typename Score>
+TC_HD void tc_score_pairs(const TcScoreCall& c, int block, int blocks, bool raises, int* err, Score score) {
+    const long long pairs = (long long)c.trials * c.n_files;
+    for (long long pair = block; pair < pairs; pair += blocks) {
+        const int t = (int)(pair / c.n_files), n = (int)(pair - (long long)t * c.n_files);
+        const int cell0 = c.file_cell_off[n], ncell = c.file_cell_off[n + 1] - cell0;
+        if (ncell < 0 || ncell > c.max_cells) {   // (the same for every lane) the file does not fit a slice
+            if (raises) tc_err_raise(err, TC_SCORE_ERR_ARGS);
+            continue;
+        }
+        const TcScoreIn in = {c.bits + (long long)t * c.total_rows, c.row_off, c.mids, c.mid_cell, c.cell_dur + cell0,
+                              c.cell_ref + cell0, c.file_chunk_off[n], c.file_chunk_off[n + 1], ncell, c.max_speakers, c.collar};
+        score(pair, t, cell0, in);
+    }
+}
+
+#if defined(TC_KERNEL_UNIT)   // the kernels' translation units define it before this header: threadIdx, the barrier
+// The lanes of a phase on the device: every thread of the workgroup is one, and the phase ends with the barrier.
+struct TcDeviceLanes {
+    int nl;
+    template <typename F>
+    __device__ void operator()(F f) const {
+        f((int)threadIdx.x);
+        __syncthreads();
+    }
+};
+#endif
+
 struct TcBitOn {
     const unsigned* bits;
     int g;
     TC_HD bool operator()(int p) const { return (bits[p] >> g) & 1u; }
-};
-struct TcNoAdd {
-    TC_HD void operator()(int, int) const {}
 };
 struct TcToggle {
     unsigned* scratch;
@@ -471,19 +544,14 @@ TC_HD bool tc_str_less(int a, int b) {
 template <typename Shared, typename Lanes>
 TC_HD void tc_score_cells(const TcScoreIn& in, Shared& sh, unsigned* scratch, Lanes lanes) {
     const int nl = lanes.nl, ncell = in.ncell, chunks = in.c1 - in.c0;
-    const int per = tc_vad_steps_per_lane(chunks, nl);
     const unsigned gmask = in.G >= 32 ? 0xffffffffu : ((1u << in.G) - 1u);   // dz_tune_score ignores bits >= G
     const TcVadEnd none = {-INFINITY, 0};
-    auto lo_of = [&](int lane) { return in.c0 + ((long long)lane * per < chunks ? lane * per : chunks); };
-    auto hi_of = [&](int lane) {
-        const int lo = lo_of(lane);
-        return lo + per < in.c1 ? lo + per : in.c1;
-    };
     // ---- the slice starts from zeros; the labels of every lane's steps
     lanes([&](int lane) {
         for (int i = lane; i <= ncell; i += nl) tc_word_store(scratch + i, 0u);
+        const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
         unsigned any = 0;
-        for (int p = in.row_off[lo_of(lane)], p1 = in.row_off[hi_of(lane)]; p < p1; ++p) any |= in.bits[p];
+        for (int p = in.row_off[my.lo], p1 = in.row_off[my.hi]; p < p1; ++p) any |= in.bits[p];
         sh.lane_any[lane] = any & gmask;
         if (lane == 0) sh.err = 0;
     });
@@ -493,15 +561,17 @@ TC_HD void tc_score_cells(const TcScoreIn& in, Shared& sh, unsigned* scratch, La
     for (unsigned m = any; m; m &= m - 1) {
         const int g = __builtin_ctz(m);
         lanes([&](int lane) {
+            const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
             TcVadEnd own = none;
             if ((sh.lane_any[lane] >> g) & 1u)
-                own = tc_turn_walk(TcBitOn{in.bits, g}, TcNoAdd{}, in.row_off, in.mids, in.mid_cell, in.collar, lo_of(lane),
-                                   hi_of(lane), none);
+                own = tc_turn_walk(TcBitOn{in.bits, g}, TcNoAdd{}, in.row_off, in.mids, in.mid_cell, in.collar, my.lo, my.hi,
+                                   none);
             sh.end_e[lane] = own.e;
             sh.end_cell[lane] = own.cell;
         });
         lanes([&](int lane) {
             if (!((sh.lane_any[lane] >> g) & 1u)) return;   // no turn of g in this lane's steps: nothing to add
+            const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
             TcVadEnd before = none;
             for (int j = 0; j < lane; ++j)
                 if (sh.end_e[j] > before.e) {
@@ -509,25 +579,21 @@ TC_HD void tc_score_cells(const TcScoreIn& in, Shared& sh, unsigned* scratch, La
                     before.cell = sh.end_cell[j];
                 }
             tc_turn_walk(TcBitOn{in.bits, g}, TcToggle{scratch, 1u << g, ncell, &sh.err}, in.row_off, in.mids, in.mid_cell,
-                         in.collar, lo_of(lane), hi_of(lane), before);
+                         in.collar, my.lo, my.hi, before);
         });
     }
     // ---- prefix XOR: word i becomes the hypothesis mask of cell i (lane l scans the block [l * blk, (l + 1) * blk))
-    const int blk = (ncell + nl - 1) / nl;
-    auto b0_of = [&](int lane) { return (long long)lane * blk < ncell ? lane * blk : ncell; };
-    auto b1_of = [&](int lane) {
-        const int b0 = b0_of(lane);
-        return b0 + blk < ncell ? b0 + blk : ncell;
-    };
     lanes([&](int lane) {
+        const TcSteps my = tc_lane_steps(0, ncell, lane, nl);
         unsigned x = 0;
-        for (int i = b0_of(lane), b1 = b1_of(lane); i < b1; ++i) x ^= tc_word_load(scratch + i);
+        for (int i = my.lo; i < my.hi; ++i) x ^= tc_word_load(scratch + i);
         sh.lane_x[lane] = x;
     });
     lanes([&](int lane) {
         unsigned carry = 0;
         for (int j = 0; j < lane; ++j) carry ^= sh.lane_x[j];
-        for (int i = b0_of(lane), b1 = b1_of(lane); i < b1; ++i) {
+        const TcSteps my = tc_lane_steps(0, ncell, lane, nl);
+        for (int i = my.lo; i < my.hi; ++i) {
             carry ^= tc_word_load(scratch + i);
             tc_word_store(scratch + i, carry);
         }

@@ -15,7 +15,7 @@
 //   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
 //                        scoring of k_tune_vad.hip, from the text those kernels compile; OverlappedSpeechDetection
 //                        too (both track pipelines: another track, other reference prefix sums)
-//   dz_tune_vad_host_hyst     the same with an offset threshold (hysteresis), from the text of tune_vad_hyst_kernel;
+//   dz_tune_vad_host_hyst     the same with an offset threshold (hysteresis): one implementation, another row rule;
 //   dz_tune_vad_replay_tails  its yardstick: the masks through dz_tail_create + dz_tail_set_offset + dz_tail_step
 //   dz_tune_name_host    the names a gallery gives the global speakers of every (trial, file) chain, step by step, from
 //                        the text tune_name_kernel compiles (tune_ident_core.h)
@@ -48,6 +48,37 @@ struct LanesInTurn {   // the lanes of a workgroup, one after the other: a phase
         for (int lane = 0; lane < nl; ++lane) f(lane);
     }
 };
+
+// fn(worker, i) for i in [0, n) on at most `threads` threads (1 .. n of them); in order, on the caller's, when that is one
+template <typename F>
+void each_item(int n, int threads, F fn) {
+    const int nt = dz_host_threads(threads, n);
+    if (nt == 1)
+        for (int i = 0; i < n; ++i) fn(0, i);
+    else
+        dz_host_parallel(n, nt, fn);
+}
+
+// The workgroups of a scoring call on the host (dz_tune_score_core, dz_tune_ident_score_core).  As on the device,
+// "workgroup" b of score_blocks takes pairs b, b + score_blocks, ... (tc_score_pairs) on one scratch slice of
+// max_cells + 1 words, which every pair finds as the pair before left it; the shared state starts from a pattern, as
+// LDS starts from whatever was there.  score(in, shared, slice, pair, t, cell0, err) scores one pair; returns the
+// largest code a workgroup's error word holds.
+template <typename Shared, typename Score>
+int score_core(const TcScoreCall& call, int score_blocks, int num_threads, Score score) {
+    const long long pairs = (long long)call.trials * call.n_files;
+    const int blocks = (int)(pairs < score_blocks ? pairs : score_blocks);
+    std::vector<int> errs(blocks, 0);
+    each_item(blocks, num_threads, [&](int, int b) {
+        std::vector<unsigned> slice((size_t)call.max_cells + 1, 0xa5a5a5a5u);
+        std::vector<Shared> sh(1);
+        tc_score_pairs(call, b, blocks, true, &errs[b], [&](long long pair, int t, int cell0, const TcScoreIn& in) {
+            std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(Shared));
+            score(in, sh[0], slice.data(), pair, t, cell0, &errs[b]);
+        });
+    });
+    return *std::max_element(errs.begin(), errs.end());
+}
 
 struct Turn {
     double s, e;
@@ -267,11 +298,10 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
         return 2;
     }
     const int N = n_files, G = max_speakers, pairs = trials * N;
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > pairs) nt = pairs;
+    const int nt = dz_host_threads(num_threads, pairs);
     std::vector<ScoreScratch> scratch(nt);
     std::vector<int> rcs(nt, 0);
-    auto run = [&](int w, int pair) {
+    each_item(pairs, nt, [&](int w, int pair) {
         const int t = pair / N, n = pair - t * N;
         ScoreScratch& sc = scratch[w];
         const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
@@ -328,11 +358,7 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
         o[2] = fa;
         o[3] = missed;
         o[4] = both - correct;
-    };
-    if (nt == 1)
-        for (int i = 0; i < pairs; ++i) run(0, i);
-    else
-        dz_host_parallel(pairs, nt, run);
+    });
     for (int w = 0; w < nt; ++w)
         if (rcs[w]) {
             dz_set_error(rcs[w] == 4 ? "dz_tune_score: a speech turn does not start and end on the file's scoring cells"
@@ -342,10 +368,8 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
     return 0;
 }
 
-// dz_tune_score's components from the text of tune_score_kernel (tune_core.h: tc_score_pair), on host memory.  As on
-// the device, "workgroup" b of score_blocks takes pairs b, b + score_blocks, ... on one scratch slice of max_cells + 1
-// words, which every pair finds as the pair before left it; the shared state starts from a pattern, as LDS starts
-// from whatever was there.
+// dz_tune_score's components from the text of tune_score_kernel (tune_core.h: tc_score_pair), on host memory
+// (score_core above).
 extern "C" int dz_tune_score_core(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
                                   const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
                                   const double* cell_dur, const unsigned long long* cell_ref, int max_cells, int max_speakers,
@@ -356,34 +380,13 @@ extern "C" int dz_tune_score_core(int trials, int n_files, const unsigned* bits,
         dz_set_error("dz_tune_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
         return 2;
     }
-    const long long pairs = (long long)trials * n_files;
-    const int blocks = (int)(pairs < score_blocks ? pairs : score_blocks);
-    int nt = num_threads < 1 ? 1 : num_threads;
-    if (nt > blocks) nt = blocks;
-    std::vector<int> errs(blocks, 0);
-    auto run = [&](int, int b) {
-        std::vector<unsigned> slice((size_t)max_cells + 1, 0xa5a5a5a5u);
-        std::vector<TcScoreShared> sh(1);
-        for (long long pair = b; pair < pairs; pair += blocks) {
-            const int t = (int)(pair / n_files), n = (int)(pair - (long long)t * n_files);
-            const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
-            if (ncell < 0 || ncell > max_cells) {
-                tc_err_raise(&errs[b], TC_SCORE_ERR_ARGS);
-                continue;
-            }
-            std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(TcScoreShared));
-            const TcScoreIn in = {bits + (size_t)t * total_rows, row_off, mids, mid_cell, cell_dur + cell0, cell_ref + cell0,
-                                  file_chunk_off[n], file_chunk_off[n + 1], ncell, max_speakers, collar};
-            tc_score_pair(in, sh[0], slice.data(), out + (size_t)pair * 5, &errs[b], LanesInTurn{lanes});
-        }
-    };
-    if (nt == 1)
-        for (int b = 0; b < blocks; ++b) run(0, b);
-    else
-        dz_host_parallel(blocks, nt, run);
-    int rc = 0;
-    for (int b = 0; b < blocks; ++b)
-        if (errs[b] > rc) rc = errs[b];
+    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
+                              cell_dur, cell_ref, max_cells, max_speakers, collar};
+    const int rc = score_core<TcScoreShared>(
+        call, score_blocks, num_threads,
+        [&](const TcScoreIn& in, TcScoreShared& sh, unsigned* slice, long long pair, int, int, int* err) {
+            tc_score_pair(in, sh, slice, out + (size_t)pair * 5, err, LanesInTurn{lanes});
+        });
     if (rc) {
         dz_set_error(rc == TC_SCORE_ERR_CELLS ? "dz_tune_score: a speech turn does not start and end on the file's scoring cells"
                      : rc == TC_SCORE_ERR_MAP ? "dz_tune_score: the mapping's assignment problem failed"
@@ -393,123 +396,74 @@ extern "C" int dz_tune_score_core(int trials, int n_files, const unsigned* bits,
     return 0;
 }
 
-// VoiceActivityDetection on the host, from the text k_tune_vad.hip compiles: agg (total_rows) once,
-// bits (T, total_rows) = agg > tau, and — where `out` is given — the components as tune_vad_score_kernel forms them,
-// `lanes` lanes of a workgroup played one after the other (backend="core"; backend="host" scores the bits with
-// dz_tune_score instead, the yardstick of the device scoring).
+// The track pipelines on the host, from the text k_tune_vad.hip compiles; what dz_tune_vad_host
+// (TcPlainRule: taus (T,)) and dz_tune_vad_host_hyst (TcHystRule: taus (T, 2) = (tau_active, tau_offset)) share, `name`
+// the one that was called.  agg (total_rows) once; then the pairs as tune_vad_score_kernel<Rule> runs them
+// (tc_track_pair), `lanes` lanes of a workgroup played one after the other: the components where `out` is given
+// (backend="core"; backend="host" scores the bits with dz_tune_score instead, the yardstick of the device scoring) and,
+// under the stateful rule, the masks, which come from the lanes' state maps.  The stateless masks are agg > tau row by
+// row, as on the device.
+namespace {
+template <typename Rule>
+int track_host(const char* name, const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+               const double* mids, const int* mid_cell, const int* file_cell_off, const double* dur_prefix,
+               const double* ref_prefix, double collar, int lanes, double* out, int num_threads) {
+    const bool pair_call = Rule::stateful || out;   // (whether anything goes through tc_track_pair)
+    if (!d || !taus || !agg || trials < 1 || !d->seg || !d->chunk_off || !d->plan || !d->row_off || !d->row_chunk ||
+        !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->nwin < 1 || d->total_rows < 1 || lanes > TC_TRACK_LANES ||
+        (pair_call && (!mids || !mid_cell || !file_cell_off || !dur_prefix || !ref_prefix || lanes < 1))) {
+        dz_set_error("%s: bad arguments (one track per chunk, 1 .. %d lanes expected)", name, TC_TRACK_LANES);
+        return 2;
+    }
+    if constexpr (Rule::stateful)
+        for (int t = 0; t < trials; ++t)
+            if (!std::isfinite(taus[2 * (size_t)t + 1])) {
+                dz_set_error("%s: tau_offset of trial %d is %g, not a finite number", name, t, taus[2 * (size_t)t + 1]);
+                return 2;
+            }
+    const int N = d->N, rows = d->total_rows;
+    const int slices = dz_host_threads(num_threads, rows);   // the rows, in slices
+    each_item(slices, slices, [&](int, int s) {
+        const int a = (int)((long long)rows * s / slices), b = (int)((long long)rows * (s + 1) / slices);
+        for (int p = a; p < b; ++p) agg[p] = tc_vad_row(*d, p);
+    });
+    unsigned* pair_bits = Rule::stateful ? bits : nullptr;
+    if (bits && !pair_bits)
+        each_item(trials, num_threads, [&](int, int t) {
+            unsigned* B = bits + (size_t)t * rows;
+            const Rule rule = Rule::of(taus, t);
+            for (int p = 0; p < rows; ++p) B[p] = rule(agg[p], false) ? 1u : 0u;
+        });
+    if (!out && !pair_bits) return 0;
+    each_item(trials * N, num_threads, [&](int, int pair) {
+        const int t = pair / N, n = pair - t * N;
+        const size_t pre = (size_t)file_cell_off[n] + n;
+        std::vector<TcTrackShared<Rule::stateful>> sh(1);
+        // LDS starts with whatever was there: nothing in it may be read before this pair has written it
+        std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(sh[0]));
+        const TcTrackIn in = {agg, d->row_off, mids, mid_cell, dur_prefix + pre, ref_prefix + pre, d->chunk_off[n],
+                              d->chunk_off[n + 1], file_cell_off[n + 1] - file_cell_off[n], collar};
+        tc_track_pair(in, Rule::of(taus, t), sh[0], out ? out + (size_t)pair * 5 : nullptr,
+                      pair_bits ? pair_bits + (size_t)t * rows : nullptr, LanesInTurn{lanes});
+    });
+    return 0;
+}
+}  // namespace
+
 extern "C" int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
                                 const double* mids, const int* mid_cell, const int* file_cell_off,
                                 const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
                                 int num_threads) {
-    if (!d || !taus || !agg || trials < 1 || !d->seg || !d->chunk_off || !d->plan || !d->row_off || !d->row_chunk ||
-        !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->nwin < 1 || d->total_rows < 1 ||
-        (out && (!mids || !mid_cell || !file_cell_off || !dur_prefix || !ref_prefix || lanes < 1))) {
-        dz_set_error("dz_tune_vad_host: bad arguments (one track per chunk expected)");
-        return 2;
-    }
-    const int N = d->N, rows = d->total_rows;
-    int nt = num_threads < 1 ? 1 : num_threads;
-    {   // the rows, in slices
-        const int slices = rows < nt ? rows : nt;
-        auto run = [&](int, int s) {
-            const int a = (int)((long long)rows * s / slices), b = (int)((long long)rows * (s + 1) / slices);
-            for (int p = a; p < b; ++p) agg[p] = tc_vad_row(*d, p);
-        };
-        if (slices == 1) run(0, 0);
-        else dz_host_parallel(slices, slices, run);
-    }
-    if (bits) {
-        auto run = [&](int, int t) {
-            unsigned* B = bits + (size_t)t * rows;
-            const double tau = taus[t];
-            for (int p = 0; p < rows; ++p) B[p] = agg[p] > tau ? 1u : 0u;
-        };
-        if (nt == 1 || trials == 1)
-            for (int t = 0; t < trials; ++t) run(0, t);
-        else
-            dz_host_parallel(trials, nt < trials ? nt : trials, run);
-    }
-    if (out) {
-        const int pairs = trials * N;
-        if (nt > pairs) nt = pairs;
-        auto run = [&](int, int pair) {
-            const int t = pair / N, n = pair - t * N;
-            const int c0 = d->chunk_off[n], c1 = d->chunk_off[n + 1];
-            const int per = tc_vad_steps_per_lane(c1 - c0, lanes);
-            const double* dp = dur_prefix + (size_t)file_cell_off[n] + n;
-            const double* rp = ref_prefix + (size_t)file_cell_off[n] + n;
-            const TcVadEnd none = {-INFINITY, 0};
-            TcVadEnd before = none;
-            TcVadSum all = {0.0, 0.0};
-            for (int lane = 0; lane < lanes; ++lane) {
-                const int lo = c0 + ((long long)lane * per < c1 - c0 ? lane * per : c1 - c0);
-                const int hi = lo + per < c1 ? lo + per : c1;
-                TcVadSum scratch = {0.0, 0.0}, s = {0.0, 0.0};
-                const TcVadEnd own = tc_vad_walk(agg, d->row_off, mids, mid_cell, dp, rp, taus[t], collar, lo, hi, none, &scratch);
-                tc_vad_walk(agg, d->row_off, mids, mid_cell, dp, rp, taus[t], collar, lo, hi, before, &s);
-                all.hyp += s.hyp;
-                all.both += s.both;
-                if (own.e > before.e) before = own;
-            }
-            tc_vad_components(rp[file_cell_off[n + 1] - file_cell_off[n]], all, out + (size_t)pair * 5);
-        };
-        if (nt == 1)
-            for (int i = 0; i < pairs; ++i) run(0, i);
-        else
-            dz_host_parallel(pairs, nt, run);
-    }
-    return 0;
+    return track_host<TcPlainRule>("dz_tune_vad_host", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off, dur_prefix,
+                                   ref_prefix, collar, lanes, out, num_threads);
 }
 
-// The track pipelines with hysteresis, from the text tune_vad_hyst_kernel compiles (tc_hyst_pair): taus
-// (T, 2) = (tau_active, tau_offset) per trial, everything else as dz_tune_vad_host.  bits and out both come from the
-// lanes' state maps, `lanes` lanes of a workgroup played one after the other; lanes is needed for either.
 extern "C" int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
                                      const double* mids, const int* mid_cell, const int* file_cell_off,
                                      const double* dur_prefix, const double* ref_prefix, double collar, int lanes,
                                      double* out, int num_threads) {
-    if (!d || !taus || !agg || trials < 1 || !d->seg || !d->chunk_off || !d->plan || !d->row_off || !d->row_chunk ||
-        !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->nwin < 1 || d->total_rows < 1 || lanes < 1 ||
-        lanes > TC_HYST_LANES || !mids || !mid_cell || !file_cell_off || !dur_prefix || !ref_prefix) {
-        dz_set_error("dz_tune_vad_host_hyst: bad arguments (one track per chunk, 1 .. %d lanes expected)", TC_HYST_LANES);
-        return 2;
-    }
-    for (int t = 0; t < trials; ++t)
-        if (!std::isfinite(taus[2 * (size_t)t + 1])) {
-            dz_set_error("dz_tune_vad_host_hyst: tau_offset of trial %d is %g, not a finite number", t, taus[2 * (size_t)t + 1]);
-            return 2;
-        }
-    const int N = d->N, rows = d->total_rows;
-    int nt = num_threads < 1 ? 1 : num_threads;
-    {   // the rows, in slices
-        const int slices = rows < nt ? rows : nt;
-        auto run = [&](int, int s) {
-            const int a = (int)((long long)rows * s / slices), b = (int)((long long)rows * (s + 1) / slices);
-            for (int p = a; p < b; ++p) agg[p] = tc_vad_row(*d, p);
-        };
-        if (slices == 1) run(0, 0);
-        else dz_host_parallel(slices, slices, run);
-    }
-    if (!bits && !out) return 0;
-    const int pairs = trials * N;
-    if (nt > pairs) nt = pairs;
-    auto run = [&](int, int pair) {
-        const int t = pair / N, n = pair - t * N;
-        const size_t pre = (size_t)file_cell_off[n] + n;
-        std::vector<TcHystShared> sh(1);
-        // LDS starts with whatever was there: nothing in it may be read before this pair has written it
-        std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(TcHystShared));
-        const TcHystIn in = {agg, d->row_off, mids, mid_cell, dur_prefix + pre, ref_prefix + pre, d->chunk_off[n],
-                             d->chunk_off[n + 1], file_cell_off[n + 1] - file_cell_off[n], taus[2 * (size_t)t],
-                             taus[2 * (size_t)t + 1], collar};
-        tc_hyst_pair(in, sh[0], out ? out + (size_t)pair * 5 : nullptr, bits ? bits + (size_t)t * rows : nullptr,
-                     LanesInTurn{lanes});
-    };
-    if (nt == 1)
-        for (int i = 0; i < pairs; ++i) run(0, i);
-    else
-        dz_host_parallel(pairs, nt, run);
-    return 0;
+    return track_host<TcHystRule>("dz_tune_vad_host_hyst", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off,
+                                  dur_prefix, ref_prefix, collar, lanes, out, num_threads);
 }
 
 // The same masks from an independent text: one dz_tail handle per (trial, file) with dz_tail_set_offset, the file's
@@ -594,7 +548,7 @@ extern "C" int dz_tune_name_host(int trials, int n_files, int total_chunks, int 
         return 2;
     }
     const int N = n_files, K = k_local, G = max_speakers, V = voiceprints, pairs = trials * N;
-    auto run = [&](int, int pair) {
+    each_item(pairs, num_threads, [&](int, int pair) {
         const int t = pair / N, n = pair - t * N;
         const int c0 = file_chunk_off[n], c1 = file_chunk_off[n + 1];
         const int stop = status[pair] < 0 ? c1 : std::min(c0 + status[pair], c1);
@@ -621,12 +575,7 @@ extern "C" int dz_tune_name_host(int trials, int n_files, int total_chunks, int 
                 if (H) H[(size_t)c * G + g] = h;
             }
         }
-    };
-    const int nt = std::max(1, std::min(num_threads, pairs));
-    if (nt == 1)
-        for (int i = 0; i < pairs; ++i) run(0, i);
-    else
-        dz_host_parallel(pairs, nt, run);
+    });
     return 0;
 }
 
@@ -646,10 +595,10 @@ extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits
         return 2;
     }
     const int N = n_files, G = max_speakers, pairs = trials * N;
-    const int nt = std::max(1, std::min(num_threads, pairs));
+    const int nt = dz_host_threads(num_threads, pairs);
     std::vector<ScoreScratch> scratch(nt);
     std::vector<int> rcs(nt, 0);
-    auto run = [&](int w, int pair) {
+    each_item(pairs, nt, [&](int w, int pair) {
         const int t = pair / N, n = pair - t * N;
         ScoreScratch& sc = scratch[w];
         const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
@@ -672,11 +621,7 @@ extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits
             ti_cell_counts(h, rm, I + (size_t)c * G, cnt);
             for (int q = 0; q < 5; ++q) o[q] += cell_dur[cell0 + i] * cnt[q];
         }
-    };
-    if (nt == 1)
-        for (int i = 0; i < pairs; ++i) run(0, i);
-    else
-        dz_host_parallel(pairs, nt, run);
+    });
     for (int w = 0; w < nt; ++w)
         if (rcs[w]) {
             dz_set_error("dz_tune_ident_score: a speech turn or a step does not lie on the file's scoring cells");
@@ -701,34 +646,14 @@ extern "C" int dz_tune_ident_score_core(int trials, int n_files, const unsigned*
         dz_set_error("dz_tune_ident_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
         return 2;
     }
-    const long long pairs = (long long)trials * n_files;
-    const int blocks = (int)(pairs < score_blocks ? pairs : score_blocks);
-    const int nt = std::max(1, std::min(num_threads, blocks));
-    std::vector<int> errs(blocks, 0);
-    auto run = [&](int, int b) {
-        std::vector<unsigned> slice((size_t)max_cells + 1, 0xa5a5a5a5u);
-        std::vector<TiScoreShared> sh(1);
-        for (long long pair = b; pair < pairs; pair += blocks) {
-            const int t = (int)(pair / n_files), n = (int)(pair - (long long)t * n_files);
-            const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
-            if (ncell < 0 || ncell > max_cells) {
-                tc_err_raise(&errs[b], TC_SCORE_ERR_ARGS);
-                continue;
-            }
-            std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(TiScoreShared));
-            const TiScoreIn in = {{bits + (size_t)t * total_rows, row_off, mids, mid_cell, cell_dur + cell0, cell_ref + cell0,
-                                   file_chunk_off[n], file_chunk_off[n + 1], ncell, max_speakers, collar},
-                                  ident + (size_t)t * total_chunks * max_speakers, cell_step + cell0};
-            ti_score_pair(in, sh[0], slice.data(), out + (size_t)pair * 5, &errs[b], LanesInTurn{lanes});
-        }
-    };
-    if (nt == 1)
-        for (int b = 0; b < blocks; ++b) run(0, b);
-    else
-        dz_host_parallel(blocks, nt, run);
-    int rc = 0;
-    for (int b = 0; b < blocks; ++b)
-        if (errs[b] > rc) rc = errs[b];
+    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
+                              cell_dur, cell_ref, max_cells, max_speakers, collar};
+    const int rc = score_core<TiScoreShared>(
+        call, score_blocks, num_threads,
+        [&](const TcScoreIn& cells, TiScoreShared& sh, unsigned* slice, long long pair, int t, int cell0, int* err) {
+            const TiScoreIn in = {cells, ident + (size_t)t * total_chunks * max_speakers, cell_step + cell0};
+            ti_score_pair(in, sh, slice, out + (size_t)pair * 5, err, LanesInTurn{lanes});
+        });
     if (rc) {
         dz_set_error(rc == TC_SCORE_ERR_ARGS ? "dz_tune_ident_score_core: a file has more scoring cells than a scratch slice holds"
                                              : "dz_tune_ident_score: a speech turn or a step does not lie on the file's scoring cells");

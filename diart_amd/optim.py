@@ -53,7 +53,7 @@ from .metrics import (DetectionErrorRate, DiarizationErrorRate, IdentificationEr
 TUNABLE = ("tau_active", "rho_update", "delta_new")
 IDENT_TUNABLE = TUNABLE + ("delta_id",)
 VAD_TUNABLE = ("tau_active",)
-# with hysteresis (blocks.base.TauOffset): the track pipelines' second threshold, replayed by tune_vad_hyst_kernel
+# with hysteresis (blocks.base.TauOffset): the track pipelines' second threshold, replayed by tune_vad_score_kernel<TcHystRule>
 TRACK_TUNABLE = ("tau_active", "tau_offset")
 MAX_SPEAKERS = 32          # the hypothesis of a frame is one 32-bit mask
 MAX_LOCAL_SPEAKERS = 8
@@ -998,48 +998,33 @@ class _TrackTuneCache(_ReplayCache):
                              f"expected, got {np.shape(taus)}")
         return np.ascontiguousarray(t)
 
-    def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int):
+    def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int, core: bool = True):
+        """``(agg, bits, components)`` on host threads, from the kernels' text: ``dz_tune_vad_host`` for ``taus (T,)``,
+        ``dz_tune_vad_host_hyst`` — the lanes' state maps included — for ``taus (T, 2)``.  ``core=False`` with
+        ``(T, 2)`` (backend="host"): the masks come from an independent text instead — one ``dz_tail`` handle with
+        ``dz_tail_set_offset`` per (trial, file), fed the track step by step — and there are no components."""
         T = taus.shape[0]
-        agg = np.empty(self.total_rows, dtype=np.float64)
-        b = np.empty((T, self.total_rows), dtype=np.uint32) if bits else None
-        out = np.zeros((T, self.N, 5), dtype=np.float64) if components else None
-        d = self._desc(lambda name: getattr(self, name).ctypes.data)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        _lib.check(_lib.load().dz_tune_vad_host(C.byref(d), taus.ctypes.data, T, agg.ctypes.data, ptr(b), self.mids.ctypes.data,
-                                                self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
-                                                self.dur_prefix.ctypes.data, self.ref_prefix.ctypes.data, PATCH_COLLAR,
-                                                self.SCORE_LANES, ptr(out), int(num_threads)), "dz_tune_vad_host")
-        return agg, b, out
-
-    def _host_hyst(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int, core: bool):
-        """``_host`` for ``taus (T, 2)``.  ``core``: masks and components from the kernel's text, the lanes' state maps
-        included (``dz_tune_vad_host_hyst``).  Otherwise the masks come from an independent text — one ``dz_tail``
-        handle with ``dz_tail_set_offset`` per (trial, file), fed the track step by step — and no components."""
-        T = taus.shape[0]
+        tails = taus.ndim == 2 and not core
+        assert not (tails and components)
         agg = np.empty(self.total_rows, dtype=np.float64)
         b = np.empty((T, self.total_rows), dtype=np.uint32) if bits else None
         out = np.zeros((T, self.N, 5), dtype=np.float64) if components else None
         d = self._desc(lambda name: getattr(self, name).ctypes.data)
         ptr = lambda a: None if a is None else a.ctypes.data
         lib = _lib.load()
-        if core:
-            _lib.check(lib.dz_tune_vad_host_hyst(C.byref(d), taus.ctypes.data, T, agg.ctypes.data, ptr(b),
-                                                 self.mids.ctypes.data, self.mid_cell.ctypes.data,
-                                                 self.file_cell_off.ctypes.data, self.dur_prefix.ctypes.data,
-                                                 self.ref_prefix.ctypes.data, PATCH_COLLAR, self.SCORE_LANES, ptr(out),
-                                                 int(num_threads)), "dz_tune_vad_host_hyst")
-            return agg, b, out
-        assert not components
-        onsets = np.ascontiguousarray(taus[:, 0])
-        _lib.check(lib.dz_tune_vad_host(C.byref(d), onsets.ctypes.data, T, agg.ctypes.data, None, None, None, None, None,
-                                        None, PATCH_COLLAR, self.SCORE_LANES, None, int(num_threads)), "dz_tune_vad_host")
-        if bits:
+        name = "dz_tune_vad_host_hyst" if taus.ndim == 2 and core else "dz_tune_vad_host"
+        thresholds = np.ascontiguousarray(taus[:, 0]) if tails else taus          # (the aggregation reads none of them)
+        _lib.check(getattr(lib, name)(C.byref(d), thresholds.ctypes.data, T, agg.ctypes.data, None if tails else ptr(b),
+                                      self.mids.ctypes.data, self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
+                                      self.dur_prefix.ctypes.data, self.ref_prefix.ctypes.data, PATCH_COLLAR,
+                                      self.SCORE_LANES, ptr(out), int(num_threads)), name)
+        if tails and bits:
             starts = np.ascontiguousarray(self.starts, dtype=np.float64)
             res = np.ascontiguousarray(self.res, dtype=np.float64)
             _lib.check(lib.dz_tune_vad_replay_tails(C.byref(d), taus.ctypes.data, T, self.meta["step"], self.meta["latency"],
                                                     starts.ctypes.data, res.ctypes.data, b.ctypes.data, int(num_threads)),
                        "dz_tune_vad_replay_tails")
-        return agg, b, None
+        return agg, b, out
 
     def _device(self, device: torch.device):
         """The cache's device tensors, ``agg`` among them: tune_vad_rows_kernel runs once per cache and device."""
@@ -1065,7 +1050,7 @@ class _TrackTuneCache(_ReplayCache):
         b = torch.empty((T, self.total_rows), dtype=torch.int32, device=device) if bits else None
         out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device) if components else None
         ptr = lambda a: None if a is None else a.data_ptr()
-        # (T, 2): tune_vad_hyst_kernel, one workgroup per (trial, file) for the masks too; (T,): today's kernels
+        # (T, 2): the stateful instantiation of tune_vad_score_kernel, one workgroup per (trial, file) for the masks too
         entry, name = ((_lib.load().dz_tune_vad_score_hyst, "dz_tune_vad_score_hyst") if taus.ndim == 2 else
                        (_lib.load().dz_tune_vad_score, "dz_tune_vad_score"))
         _lib.check(entry(_lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(),
@@ -1088,12 +1073,9 @@ class _TrackTuneCache(_ReplayCache):
             agg, bits, _ = self._gpu(taus, True, False)
             torch.cuda.synchronize(agg.device)
             return agg.cpu().numpy(), bits.cpu().numpy().view(np.uint32)
-        if hyst and backend in ("host", "core"):
-            agg, bits, _ = self._host_hyst(taus, True, False, num_threads, core=backend == "core")
-            return agg, bits
-        if backend != "host":
+        if backend != "host" and not (hyst and backend == "core"):
             raise ValueError(f"backend '{backend}': gpu or host" + (" or core" if hyst else ""))
-        agg, bits, _ = self._host(taus, True, False, num_threads)
+        agg, bits, _ = self._host(taus, True, False, num_threads, core=backend == "core")
         return agg, bits
 
     def score(self, bits: np.ndarray, num_threads: int = 8) -> np.ndarray:
@@ -1106,9 +1088,9 @@ class _TrackTuneCache(_ReplayCache):
         """The detection error rate of every trial of ``taus``.  ``backend``: "gpu" (the two kernels; only the
         components come back), "host" (the same aggregation on host threads, then ``dz_tune_score``; trials in batches
         whose masks fit ``memory_budget`` bytes) or "core" (the scoring kernel's text on host threads).  ``taus (T, 2)``
-        = (tau_active, tau_offset) per trial: hysteresis — "gpu" runs ``tune_vad_hyst_kernel``, "core" its text, "host"
-        one ``dz_tail`` handle with ``dz_tail_set_offset`` per (trial, file), then ``dz_tune_score``.  ``(T,)`` runs what
-        it always ran."""
+        = (tau_active, tau_offset) per trial: hysteresis — "gpu" runs ``tune_vad_score_kernel`` under the stateful rule,
+        "core" its text, "host" one ``dz_tail`` handle with ``dz_tail_set_offset`` per (trial, file), then
+        ``dz_tune_score``.  ``(T,)`` is the same pair routine under the stateless rule."""
         taus = self._taus(taus)
         backend = backend or self.default_backend()
         if backend == "gpu":
@@ -1117,14 +1099,11 @@ class _TrackTuneCache(_ReplayCache):
             per_file = out.cpu().numpy()
         elif backend == "core":
             self._check_sorted(f"backend '{backend}'")
-            per_file = (self._host_hyst(taus, False, True, num_threads, core=True) if taus.ndim == 2 else
-                        self._host(taus, False, True, num_threads))[2]
+            per_file = self._host(taus, False, True, num_threads)[2]
         elif backend == "host":
             per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
-            masks = ((lambda t: self._host_hyst(t, True, False, num_threads, core=False)[1]) if taus.ndim == 2 else
-                     (lambda t: self._host(t, True, False, num_threads)[1]))
-            per_file = np.concatenate([self.score(masks(taus[a:a + per_batch]), num_threads)
-                                       for a in range(0, taus.shape[0], per_batch)])
+            per_file = np.concatenate([self.score(self._host(taus[a:a + per_batch], True, False, num_threads, core=False)[1],
+                                                  num_threads) for a in range(0, taus.shape[0], per_batch)])
         else:
             raise ValueError(f"backend '{backend}': gpu, host or core")
         comp = per_file.sum(axis=1)

@@ -1148,7 +1148,8 @@ int dz_tune_vad_score(dz_ctx* ctx, int trials, int n_files, int total_rows, cons
                       unsigned* d_bits, void* stream);
 /* The same from host memory, compiled from the text of the kernels: agg (total_rows); bits (T, total_rows)
  * if not NULL; out (T, N, 5) if not NULL, the workgroup's `lanes` lanes played in order (the other
- * arguments may be NULL where out is).                                                                    */
+ * arguments may be NULL where out is).  lanes is at most 256, the workgroup of the kernel and the bound of
+ * every sibling *_core entry point (the Python side only ever passes 256); more returns 2.                */
 int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
                      const double* mids, const int* mid_cell, const int* file_cell_off,
                      const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
@@ -1156,7 +1157,11 @@ int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, doub
 /* The track pipelines with hysteresis: d_taus / taus are (T, 2) = (tau_active, tau_offset) per trial,
  * a row is on when agg > tau_active while the track is off and > tau_offset while it is on (dz_tail_set_offset's rule),
  * the state off at every file's first step and carried across its steps.  All other arguments are those of
- * dz_tune_vad_score / dz_tune_vad_host.  One workgroup per (trial, file) for the components and for the masks: the
+ * dz_tune_vad_score / dz_tune_vad_host, and so is the implementation (one pair routine, tc_track_pair in
+ * csrc/tune_core.h, under another row rule: with tau_offset == tau_active these calls return the doubles of those).
+ * (The device form bounds trials x files below 2^31; dz_tune_vad_score also bounds trials x total_rows, the grid of
+ * its one-thread-per-row mask kernel, which the hysteresis form never launches.)
+ * One workgroup per (trial, file) for the components and for the masks: the
  * lanes compose the state maps of their steps before they walk them, so every row's `on` is the sequential rule's.
  * The host form needs mids .. ref_prefix and lanes (1 .. 256) for the masks too, and returns 2 for a non-finite
  * tau_offset; the device form cannot read d_taus: its callers check them first.                                     */

@@ -4,7 +4,8 @@
 // carry sanitizers on this pool) and run on random inputs — NaN embeddings, silent chunks, more local speakers than free
 // centroids, varying thread counts, two callers at once.  It checks only what must hold whatever the data (finite
 // scores, assignments in range, batch == one-by-one, the tuner's plan (csrc/tune_score.cpp dz_tune_plan, built with
-// them) == the rows and the output grid dz_tail_step returned); the reference's results are pinned by
+// them) == the rows and the output grid dz_tail_step returned, the track tuners' host entry points on 1, 3 and 256
+// lanes); the reference's results are pinned by
 // tests/test_clustering.py and tests/test_tail.py.  Exit code 0 = nothing reported.
 #include <cmath>
 #include <cstdarg>
@@ -164,6 +165,84 @@ void run_files(unsigned seed, int files, int steps, int threads) {
     }
 }
 
+// The track tuners' host entry points (csrc/tune_score.cpp: one implementation under two row rules): files of 7 and 2
+// steps on 1, 3 and 256 lanes — fewer lanes than steps, and more — with and without the masks and the components.
+// Whatever the lanes: masks of 0 / 1, finite components, and (T, 2) taus with equal columns give what (T,) taus give.
+void run_track(unsigned seed, int threads) {
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<float> u(0.f, 1.f);
+    constexpr int Ft = 16, nwin = 5, N = 2, T = 3, ncell = 40;
+    const int chunk_off[N + 1] = {0, 7, 9}, chunks = chunk_off[N];
+    std::vector<float> seg((size_t)chunks * Ft);
+    for (float& v : seg) v = u(rng);
+    seg[3 * Ft + 5] = NAN;
+    std::vector<double> ham(Ft), start(chunks), res(chunks, 5.0 / Ft), t0(chunks), rout(chunks);
+    for (int i = 0; i < Ft; ++i) ham[i] = 0.54 - 0.46 * std::cos(2.0 * M_PI * i / (Ft - 1));
+    std::vector<int> plan((size_t)chunks * (4 + nwin)), row_off(chunks + 1, 0), row_chunk;
+    for (int n = 0; n < N; ++n) {
+        const int c0 = chunk_off[n], count = chunk_off[n + 1] - c0;
+        for (int c = 0; c < count; ++c) start[c0 + c] = 0.5 * c;
+        CHECK(dz_tune_plan(count, Ft, 0.5, 2.5, &start[c0], &res[c0], &plan[(size_t)c0 * (4 + nwin)], &t0[c0], &rout[c0]) == 0);
+    }
+    for (int c = 0; c < chunks; ++c) {
+        const int rows = plan[(size_t)c * (4 + nwin)] + plan[(size_t)c * (4 + nwin) + 1];
+        row_off[c + 1] = row_off[c] + rows;
+        row_chunk.insert(row_chunk.end(), rows, c);
+    }
+    const int total_rows = row_off[chunks];
+    // rows + 1 frame middles per step and the scoring cell each lies in: cells of 0.25 s, the reference on in every third
+    std::vector<double> mids((size_t)total_rows + chunks), dur_prefix(N * (ncell + 1)), ref_prefix(N * (ncell + 1));
+    std::vector<int> mid_cell(mids.size()), file_cell_off = {0, ncell, 2 * ncell};
+    for (int c = 0; c < chunks; ++c)
+        for (int i = 0; i <= row_off[c + 1] - row_off[c]; ++i) {
+            const double m = t0[c] + (i + 0.5) * rout[c];
+            mids[(size_t)row_off[c] + c + i] = m;
+            mid_cell[(size_t)row_off[c] + c + i] = m < 0.0 ? 0 : (m / 0.25 > ncell ? ncell : (int)(m / 0.25));
+        }
+    for (int n = 0; n < N; ++n)
+        for (int i = 0; i <= ncell; ++i) {
+            dur_prefix[(size_t)n * (ncell + 1) + i] = 0.25 * i;
+            ref_prefix[(size_t)n * (ncell + 1) + i] = 0.25 * ((i + 2) / 3);
+        }
+    dz_tune_desc d = {};
+    d.seg = seg.data();
+    d.chunk_off = chunk_off;
+    d.plan = plan.data();
+    d.row_off = row_off.data();
+    d.row_chunk = row_chunk.data();
+    d.hamming = ham.data();
+    d.N = N, d.F = Ft, d.K = d.D = d.G = 1, d.nwin = nwin, d.total_chunks = chunks, d.total_rows = total_rows;
+    const double taus[T] = {0.3, 0.5, 0.8};
+    double pairs[T][2];
+    for (int t = 0; t < T; ++t) pairs[t][0] = pairs[t][1] = taus[t];
+    std::vector<double> agg(total_rows), agg2(total_rows), out((size_t)T * N * 5), out2(out.size());
+    std::vector<unsigned> bits((size_t)T * total_rows), bits2(bits.size());
+    for (int lanes : {1, 3, 256}) {
+        CHECK(dz_tune_vad_host(&d, taus, T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
+                               dur_prefix.data(), ref_prefix.data(), 0.05, lanes, out.data(), threads) == 0);
+        CHECK(dz_tune_vad_host_hyst(&d, &pairs[0][0], T, agg2.data(), bits2.data(), mids.data(), mid_cell.data(),
+                                    file_cell_off.data(), dur_prefix.data(), ref_prefix.data(), 0.05, lanes, out2.data(),
+                                    threads) == 0);
+        CHECK(memcmp(agg.data(), agg2.data(), sizeof(double) * agg.size()) == 0);
+        CHECK(memcmp(bits.data(), bits2.data(), sizeof(unsigned) * bits.size()) == 0);
+        CHECK(memcmp(out.data(), out2.data(), sizeof(double) * out.size()) == 0);
+        for (unsigned b : bits) CHECK(b <= 1u);
+        for (double v : out) CHECK(std::isfinite(v));
+        // the masks alone, the components alone (the stateless masks need none of the scoring arrays)
+        CHECK(dz_tune_vad_host(&d, taus, T, agg.data(), bits.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0.05, lanes,
+                               nullptr, threads) == 0);
+        CHECK(dz_tune_vad_host_hyst(&d, &pairs[0][0], T, agg2.data(), bits2.data(), mids.data(), mid_cell.data(),
+                                    file_cell_off.data(), dur_prefix.data(), ref_prefix.data(), 0.05, lanes, nullptr, threads) == 0);
+        CHECK(memcmp(bits.data(), bits2.data(), sizeof(unsigned) * bits.size()) == 0);
+        CHECK(dz_tune_vad_host_hyst(&d, &pairs[0][0], T, agg2.data(), nullptr, mids.data(), mid_cell.data(),
+                                    file_cell_off.data(), dur_prefix.data(), ref_prefix.data(), 0.05, lanes, out2.data(),
+                                    threads) == 0);
+        CHECK(memcmp(out.data(), out2.data(), sizeof(double) * out.size()) == 0);
+    }
+    CHECK(dz_tune_vad_host(&d, taus, T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
+                           dur_prefix.data(), ref_prefix.data(), 0.05, 257, out.data(), threads) == 2);
+}
+
 void run_lsap(unsigned seed) {
     std::mt19937 rng(seed);
     std::uniform_real_distribution<double> u(0.0, 2.0);
@@ -185,6 +264,7 @@ int main(int argc, char** argv) {
     for (int threads : {1, 3, 8}) {
         run_streams(10u + threads, 16, steps, threads);
         run_files(20u + threads, 5, steps / 2, threads);
+        run_track(60u + threads, threads);
     }
     // two engines' host halves at once (two StreamBatch objects on two Python threads share the process-wide pool)
     dz_host_pool_set_spin(40);

@@ -1,5 +1,5 @@
-"""Hysteresis (tau_offset) on the GPU: the tuner's kernel with the lanes' state maps (tune_vad_hyst_kernel) against the
-kernel's text on the host and the host tail; VadBatch, OverlapBatch, StreamServer and the file batch with tau_offset
+"""Hysteresis (tau_offset) on the GPU: the tuner's kernel with the lanes' state maps (tune_vad_score_kernel<TcHystRule>)
+against the kernel's text on the host and the host tail; VadBatch, OverlapBatch, StreamServer and the file batch with tau_offset
 against each stream's / file's own blocks pipeline.  The rule and the tuner's cases are tests/hysteresis_cases.py's."""
 import gc
 import sys

@@ -16,8 +16,8 @@ turns overlap, `collect` is timed once per cache and every `evaluate` figure is 
 `--hysteresis` measures the two-threshold path beside the single threshold, for both caches on the dataset of
 `--pipeline osd`: per T the wall time of `evaluate` and the device time of the scoring kernel for `(T,)` taus
 (tune_vad_score_kernel, what the parent commit runs: its own `--pipeline osd` rows on the same files are the yardstick,
-taken in a child process of their own) and for `(T, 2)` taus (tune_vad_hyst_kernel), with a band of 0.2 under every
-tau and with equal columns.  EXPECTATION, written before the first run: the new kernel adds one pass over a lane's
+taken in a child process of their own) and for `(T, 2)` taus (the kernel's stateful form), with a band of 0.2 under
+every tau and with equal columns.  EXPECTATION, written before the first run: the new kernel adds one pass over a lane's
 rows (two compares per row, no time stamps read) and a fold over at most 255 bytes of LDS to two walks that read the
 time stamps and the prefix sums, so its device time should stay well under twice the plain kernel's at every T — a
 supposition; the tool reports the ratio whichever way it falls."""
