@@ -267,6 +267,12 @@ SIGNATURES = {
                                          vp, vp]),
     "dz_tune_vad_host_hyst": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int,
                                         vp, C.c_int]),
+    "dz_tune_vad_score_dur": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp,
+                                        vp, vp]),
+    "dz_tune_vad_host_dur": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int,
+                                       vp, C.c_int]),
+    "dz_tune_track_score_dur": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp,
+                                          C.c_int]),
     "dz_tune_vad_replay_tails": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.c_int]),
     "dz_tune_name": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                C.c_int, vp]),

@@ -18,7 +18,7 @@ class HyperParameter:
 
     @staticmethod
     def from_name(name: str) -> "HyperParameter":
-        for hp in (TauActive, RhoUpdate, DeltaNew, DeltaId, TauOffset):
+        for hp in (TauActive, RhoUpdate, DeltaNew, DeltaId, TauOffset, MinDurationOn, MinDurationOff):
             if hp.name == name:
                 return hp
         raise ValueError(f"Hyper-parameter '{name}' not recognized")
@@ -31,6 +31,11 @@ DeltaNew = HyperParameter("delta_new", low=0, high=2)
 DeltaId = HyperParameter("delta_id", low=0, high=2)
 # the offset threshold of the track pipelines' hysteresis (VoiceActivityDetection, OverlappedSpeechDetection)
 TauOffset = HyperParameter("tau_offset", 0, 1)
+# the minimum durations of the track pipelines, where a whole file is known (file batches, the accumulated prediction, the
+# tuner): gaps shorter than min_duration_off are filled, then turns shorter than min_duration_on are dropped.  The range
+# is pyannote's Uniform(0, 1) for both, in seconds
+MinDurationOn = HyperParameter("min_duration_on", 0, 1)
+MinDurationOff = HyperParameter("min_duration_off", 0, 1)
 
 
 def check_tau_offset(value, who: str):
@@ -45,6 +50,27 @@ def check_tau_offset(value, who: str):
     if isinstance(value, bool) or v != v or v in (float("inf"), float("-inf")):
         raise ValueError(f"{who}: tau_offset must be a finite number or None, got {value!r}")
     return v
+
+
+def check_min_duration(value, name: str, who: str) -> float:
+    """The finite float >= 0 of ``value`` (``name``: min_duration_on | min_duration_off, in seconds); anything else is a
+    ``ValueError`` that names ``who``."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {name} must be a finite number >= 0, got {value!r}") from None
+    if isinstance(value, bool) or not (0.0 <= v < float("inf")):
+        raise ValueError(f"{who}: {name} must be a finite number >= 0, got {value!r}")
+    return v
+
+
+def refuse_min_duration(kwargs: dict, who: str) -> None:
+    """``SpeakerDiarization`` and everything that serves it take no minimum duration (they would be per speaker): a
+    ``ValueError`` if ``kwargs`` names one."""
+    for name in ("min_duration_on", "min_duration_off"):
+        if name in kwargs:
+            raise ValueError(f"{who}: {name} is not a parameter of SpeakerDiarization; the minimum durations are "
+                             "VoiceActivityDetection's and OverlappedSpeechDetection's, where a whole file is known")
 
 
 class PipelineConfig(ABC):

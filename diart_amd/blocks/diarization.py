@@ -48,6 +48,7 @@ class SpeakerDiarizationConfig(base.PipelineConfig):
                  max_speakers: int = 20, normalize_embedding_weights: bool = False,
                  device: Optional[torch.device] = None, sample_rate: int = 16000, **kwargs):
         refuse_tau_offset(kwargs, "SpeakerDiarizationConfig")
+        base.refuse_min_duration(kwargs, "SpeakerDiarizationConfig")
         # the reference downloads pyannote/segmentation + pyannote/embedding here; offline the
         # models must be given (state dicts / checkpoints, see diart_amd.models)
         self.segmentation = segmentation or m.SegmentationModel.from_pyannote("pyannote/segmentation")
@@ -89,6 +90,7 @@ class SpeakerDiarization(base.Pipeline):
         c = self._config
         if hasattr(c, "tau_offset"):
             refuse_tau_offset({"tau_offset": c.tau_offset}, "SpeakerDiarization")
+        base.refuse_min_duration(vars(c), "SpeakerDiarization")
         msg = f"Latency should be in the range [{c.step}, {c.duration}]"
         assert c.step <= c.latency <= c.duration, msg
         self.segmentation = SpeakerSegmentation(c.segmentation, c.device)

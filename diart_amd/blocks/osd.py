@@ -24,7 +24,9 @@ from .vad import VoiceActivityDetectionConfig, _TrackDetection
 
 
 class OverlappedSpeechDetectionConfig(VoiceActivityDetectionConfig):
-    """``VoiceActivityDetectionConfig``'s fields; ``tau_active`` defaults to 0.5, pyannote's onset for this task."""
+    """``VoiceActivityDetectionConfig``'s fields; ``tau_active`` defaults to 0.5, pyannote's onset for this task.
+    ``min_duration_on`` / ``min_duration_off`` (through ``**kwargs``) are the base class's too: they act where a whole
+    file is known, never in a live step."""
 
     def __init__(self, segmentation: Optional[m.SegmentationModel] = None, duration: float = 5,
                  step: float = 0.5, latency: Union[float, str, None] = None, tau_active: float = 0.5,

@@ -26,13 +26,19 @@ class VoiceActivityDetectionConfig(base.PipelineConfig):
     def __init__(self, segmentation: Optional[m.SegmentationModel] = None, duration: float = 5,
                  step: float = 0.5, latency: Union[float, str, None] = None, tau_active: float = 0.6,
                  device: Optional[torch.device] = None, sample_rate: int = 16000, tau_offset: Optional[float] = None,
-                 **kwargs):
+                 min_duration_on: float = 0.0, min_duration_off: float = 0.0, **kwargs):
         self.segmentation = segmentation or m.SegmentationModel.from_pyannote("pyannote/segmentation")
         self._duration, self._step, self._sample_rate = duration, step, sample_rate
         self._latency = _latency(latency, step, duration)
         self.tau_active = tau_active
         # hysteresis: a frame stays on while its score is > tau_offset; None = tau_active, the single threshold
         self.tau_offset = base.check_tau_offset(tau_offset, f"{type(self).__name__}")
+        # minimum durations, in seconds: gaps shorter than min_duration_off are filled, then turns shorter than
+        # min_duration_on are dropped.  They act where a whole file is known (the accumulated prediction of
+        # StreamingInference and Benchmark, the file batch, the tuner); a live step has no look-ahead, so the pipeline's
+        # per-chunk __call__ and the N-stream engines neither take nor apply them
+        self.min_duration_on = base.check_min_duration(min_duration_on, "min_duration_on", f"{type(self).__name__}")
+        self.min_duration_off = base.check_min_duration(min_duration_off, "min_duration_off", f"{type(self).__name__}")
         self.device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
     @property

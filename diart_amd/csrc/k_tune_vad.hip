@@ -10,7 +10,7 @@
 //                                 workgroup's barrier between its phases.  Every lane walks its steps of the file
 //                                 twice; the ends of the lanes' latest turns, as an exclusive running maximum in lane
 //                                 order, join the lanes' walks; lane 0 adds the lanes' sums in lane order and writes the
-//                                 five components.  Instantiated twice:
+//                                 five components.  Instantiated three times:
 //                                   TcPlainRule  taus (T,), a row is on when agg > tau.  No mask leaves the device:
 //                                                this instantiation is launched for the components only.
 //                                   TcHystRule   taus (T, 2) = (tau_active, tau_offset), DESIGN.md 4.21: a row's state
@@ -18,10 +18,17 @@
 //                                                machine from both states over its rows and the lanes' state maps,
 //                                                composed in lane order, give every lane the state its first row finds.
 //                                                The masks come from this kernel too, for the same reason.
+//                                   TcDurRule    taus (T, 4) = (tau_active, tau_offset, min_duration_on,
+//                                                min_duration_off), DESIGN.md 4.22: TcHystRule's rows and masks; the
+//                                                collar is max(collar, min_duration_off) and a merged span shorter than
+//                                                min_duration_on does not count.  A span may cross any number of lanes:
+//                                                every lane walks its steps once and leaves a summary (first span, last
+//                                                span, the sums between), one lane composes the 256 summaries in order.
 //   tune_vad_bits_kernel          one thread per (trial, row): agg > tau as the uint32 masks of the diarization replay
 //                                 (VadTuneCache.replay with taus (T,); the tests compare them with the host's)
 //
-// The arithmetic is tune_core.h's, which the host compiles too (dz_tune_vad_host, dz_tune_vad_host_hyst).  No
+// The arithmetic is tune_core.h's, which the host compiles too (dz_tune_vad_host, dz_tune_vad_host_hyst,
+// dz_tune_vad_host_dur).  No
 // contraction, as in k_tune.hip.
 #pragma clang fp contract(off)
 #include "dz_common.h"
@@ -54,7 +61,7 @@ __global__ __launch_bounds__(TC_TRACK_LANES) void tune_vad_score_kernel(
     const int* __restrict__ file_chunk_off, const int* __restrict__ row_off, const double* __restrict__ mids,
     const int* __restrict__ mid_cell, const int* __restrict__ file_cell_off, const double* __restrict__ dur_prefix,
     const double* __restrict__ ref_prefix, double collar, double* __restrict__ out, unsigned* __restrict__ bits) {
-    __shared__ TcTrackShared<Rule::stateful> sh;
+    __shared__ TcTrackSharedOf<Rule> sh;
     const int pair = blockIdx.x;
     const int t = pair / n_files, n = pair - t * n_files;
     const long pre = (long)file_cell_off[n] + n;          // ncell + 1 prefix values per file
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(TC_TRACK_LANES) void tune_vad_score_kernel(
                   Rule::stateful && bits ? bits + (size_t)t * total_rows : nullptr, TcDeviceLanes{TC_TRACK_LANES});
 }
 
-// What dz_tune_vad_score and dz_tune_vad_score_hyst (`name`) share: the checks and the launches.  The stateful rule
+// What dz_tune_vad_score, dz_tune_vad_score_hyst and dz_tune_vad_score_dur (`name`) share: the checks and the launches.  The stateful rule
 // takes its masks from the pair kernel; the stateless one keeps them one thread per (trial, row).
 template <typename Rule>
 int track_score(const char* name, dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
@@ -137,4 +144,25 @@ extern "C" int dz_tune_vad_score_hyst(dz_ctx* ctx, int trials, int n_files, int 
     return track_score<TcHystRule>("dz_tune_vad_score_hyst", ctx, trials, n_files, total_rows, d_agg, d_taus,
                                    d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix, d_ref_prefix,
                                    collar, d_out, d_bits, stream);
+}
+
+// With minimum durations: d_taus (T, 4) = (tau_active, tau_offset, min_duration_on, min_duration_off)
+// per trial, and `taus` the same values in host memory: the device form cannot read d_taus, and a duration that is
+// negative or not finite is refused here, before the device is touched.  Everything else is dz_tune_vad_score_hyst's.
+extern "C" int dz_tune_vad_score_dur(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
+                                     const double* taus, const double* d_taus, const int* d_file_chunk_off,
+                                     const int* d_row_off, const double* d_mids, const int* d_mid_cell,
+                                     const int* d_file_cell_off, const double* d_dur_prefix, const double* d_ref_prefix,
+                                     double collar, double* d_out, unsigned* d_bits, void* stream) {
+    DZ_REQUIRE(taus, "dz_tune_vad_score_dur: NULL argument");
+    DZ_REQUIRE(trials >= 1, "dz_tune_vad_score_dur: empty shape (%d trials)", trials);
+    for (int t = 0; t < trials; ++t)
+        for (int k = 2; k < 4; ++k) {
+            const double v = taus[4 * (size_t)t + k];
+            DZ_REQUIRE(v >= 0.0 && v <= 1.7976931348623157e308, "dz_tune_vad_score_dur: %s of trial %d is %g, not a finite number >= 0",
+                       k == 2 ? "min_duration_on" : "min_duration_off", t, v);
+        }
+    return track_score<TcDurRule>("dz_tune_vad_score_dur", ctx, trials, n_files, total_rows, d_agg, d_taus, d_file_chunk_off,
+                                  d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix, d_ref_prefix, collar, d_out,
+                                  d_bits, stream);
 }

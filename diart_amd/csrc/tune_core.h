@@ -251,23 +251,39 @@ TC_HD TcSteps tc_lane_steps(int c0, int chunks, int lane, int nl) {
 // latest-ending turn; an exclusive running maximum of those ends over the lanes, strictly greater in lane order
 // (-infinity for a lane without a turn, so it carries across any number of empty steps), is "the end of the last turn
 // before this lane"; then again from that end, summing the durations its turns add.  Lane 0 adds the lanes' sums in
-// lane order and writes the five components.
+// lane order and writes the five components.  (TcDurRule, the hysteresis rows with minimum durations, replaces these
+// two walks by one walk per lane and a composition of the lanes' summaries: further down, before the routine.)
 //
 // Written as phases over the lanes, as tc_score_cells is: lanes(f) runs f(lane) for every lane and ends with the
 // workgroup's barrier (k_tune_vad.hip), or plays the lanes in order (tune_score.cpp).  `out` (5 components) and `bits`
 // (this trial's masks, indexed by packed row) may each be NULL, not both.  No atomics, plain compares.
 // ---------------------------------------------------------------------------------------------------------
 struct TcPlainRule {   // taus (T,)
-    static constexpr bool stateful = false;
+    static constexpr bool stateful = false, durations = false;
     double tau;
     static TC_HD TcPlainRule of(const double* taus, int t) { return {taus[t]}; }
     TC_HD bool operator()(double y, bool) const { return y > tau; }
 };
 struct TcHystRule {    // taus (T, 2) = (tau_active, tau_offset)
-    static constexpr bool stateful = true;
+    static constexpr bool stateful = true, durations = false;
     double tau_active, tau_offset;
     static TC_HD TcHystRule of(const double* taus, int t) { return {taus[2 * (long)t], taus[2 * (long)t + 1]}; }
     TC_HD bool operator()(double y, bool active) const { return tail_hyst_on(y, tau_active, tau_offset, active); }
+};
+// taus (T, 4) = (tau_active, tau_offset, min_duration_on, min_duration_off), DESIGN.md 4.22: the rows are TcHystRule's
+// (a trial without hysteresis passes tau_offset == tau_active); the durations act on the file's merged spans
+struct TcDurRule : TcHystRule {
+    static constexpr bool durations = true;
+    double min_on, min_off;
+    static TC_HD TcDurRule of(const double* taus, int t) {
+        const double* q = taus + 4 * (long)t;
+        TcDurRule r;
+        r.tau_active = q[0];
+        r.tau_offset = q[1];
+        r.min_on = q[2];
+        r.min_off = q[3];
+        return r;
+    }
 };
 
 template <typename Rule>
@@ -315,11 +331,176 @@ struct TcTrackShared : TcTrackStates<Stateful> {
     int end_cell[TC_TRACK_LANES];
 };
 
+// ---------------------------------------------------------------------------------------------------------
+// Minimum durations (TcDurRule).  The file's turns are merged with the collar max(collar, min_off)
+// into spans — Annotation.support: a turn whose gap to the running maximum of the ends is <= 1e-6 or < collar extends
+// the span — and a span counts towards hyp / both unless end - start < min_on, both taken from `mids`.  Whether a span
+// counts is known only when both its ends are, and a span may cross any number of lanes, so the two walks of the other
+// rules do not serve.  Instead every lane reduces its steps, walked alone from "no span", to a summary: no span; or
+// its first span, its last span (the same one when it has one) and the sums of the spans strictly between them, which
+// no other lane can change.  One lane then composes the summaries in lane order (below, at tc_track_pair's end).
+// ---------------------------------------------------------------------------------------------------------
+struct TcSpan {
+    double s, e;
+    int cs, ce;   // the scoring cells that start at s and at e
+};
+
+// tc_turn_walk's sibling for whole spans: steps [c_lo, c_hi) from the open span `cur` (if `have`); close(span) for every
+// span that a later turn does not join, in order.  Returns whether a span is open at the end, in `cur`.
+template <typename On, typename Close>
+TC_HD bool tc_span_walk(On on_row, Close close, const int* row_off, const double* mids, const int* mid_cell, double collar,
+                        int c_lo, int c_hi, TcSpan& cur, bool have) {
+    for (int c = c_lo; c < c_hi; ++c) {
+        const int p = row_off[c], rows = row_off[c + 1] - p;
+        const double* mid = mids + (long)p + c;
+        const int* cell = mid_cell + (long)p + c;
+        tail_edge_walk(rows, [&](int r) { return on_row(p + r); }, [&](int onset, int r) {
+            const double s = mid[onset], e = mid[r];
+            if (e - s > 1e-6) {
+                bool joins = false;
+                if (have) {
+                    const double gap = s - cur.e;
+                    joins = gap <= 1e-6 || gap < collar;
+                }
+                if (joins) {
+                    if (e > cur.e) {
+                        cur.e = e;
+                        cur.ce = cell[r];
+                    }
+                } else {
+                    if (have) close(cur);
+                    cur.s = s;
+                    cur.e = e;
+                    cur.cs = cell[onset];
+                    cur.ce = cell[r];
+                    have = true;
+                }
+            }
+            return true;
+        });
+    }
+    return have;
+}
+
+struct TcSpanCount {   // a closed span counts unless it is shorter than min_on (strictly)
+    const double *dur_prefix, *ref_prefix;
+    double min_on;
+    TcVadSum* sum;
+    TC_HD void operator()(const TcSpan& u) const {
+        if (u.e - u.s < min_on) return;
+        sum->hyp += dur_prefix[u.ce] - dur_prefix[u.cs];
+        sum->both += ref_prefix[u.ce] - ref_prefix[u.cs];
+    }
+};
+
+struct TcDurShared : TcTrackStates<true> {    // the lanes' summaries (17.5 KB)
+    double first_s[TC_TRACK_LANES], first_e[TC_TRACK_LANES], last_s[TC_TRACK_LANES], last_e[TC_TRACK_LANES];
+    double mid_hyp[TC_TRACK_LANES], mid_both[TC_TRACK_LANES];
+    int first_cs[TC_TRACK_LANES], first_ce[TC_TRACK_LANES], last_cs[TC_TRACK_LANES], last_ce[TC_TRACK_LANES];
+    int spans[TC_TRACK_LANES];                // 0, 1, or 2: two or more
+};
+template <typename Rule, bool Durations = Rule::durations>
+struct TcTrackSharedFor {
+    using type = TcTrackShared<Rule::stateful>;
+};
+template <typename Rule>
+struct TcTrackSharedFor<Rule, true> {
+    using type = TcDurShared;
+};
+template <typename Rule>
+using TcTrackSharedOf = typename TcTrackSharedFor<Rule>::type;
+
+// One lane's steps, walked alone, as a summary.
+template <typename Rule>
+TC_HD void tc_span_summary(const TcTrackIn& in, const Rule& rule, double collar, TcSteps my, bool start, TcDurShared& sh,
+                           int lane) {
+    TcVadSum mid = {0.0, 0.0};
+    const TcSpanCount count = {in.dur_prefix, in.ref_prefix, rule.min_on, &mid};
+    TcSpan first = {0.0, 0.0, 0, 0}, cur = {0.0, 0.0, 0, 0};
+    int closed = 0;
+    bool active = start;
+    const bool open = tc_span_walk(TcTrackOn<Rule>{in.agg, rule, &active}, [&](const TcSpan& u) {
+        if (closed++ == 0)
+            first = u;
+        else
+            count(u);
+    }, in.row_off, in.mids, in.mid_cell, collar, my.lo, my.hi, cur, false);
+    if (closed == 0) first = cur;   // (a span closes only because another opens: with none open, none closed either)
+    sh.spans[lane] = !open ? 0 : closed == 0 ? 1 : 2;
+    sh.first_s[lane] = first.s;
+    sh.first_e[lane] = first.e;
+    sh.first_cs[lane] = first.cs;
+    sh.first_ce[lane] = first.ce;
+    sh.last_s[lane] = cur.s;
+    sh.last_e[lane] = cur.e;
+    sh.last_cs[lane] = cur.cs;
+    sh.last_ce[lane] = cur.ce;
+    sh.mid_hyp[lane] = mid.hyp;
+    sh.mid_both[lane] = mid.both;
+}
+
+// The summaries composed in lane order by one lane: the sequential walk of the whole file, lane by lane.  `cur` is the
+// open span — its end is the running maximum of every end so far.  Lane j's summary was formed from "no span"; the
+// sequential walk enters lane j with `cur`.  The lane's first span consists of turns that join each other against the
+// lane's own running maximum; against a maximum that is no smaller they join all the more, so the sequential walk
+// merges them too, into `cur` if the first of them joins it and into a span of their own otherwise, and leaves the
+// maximum at max(cur.e, first.e).  Where that is first.e, the walk goes on exactly as the lane did alone: the spans
+// between count as summed, the last stays open.  Where cur.e is greater — a turn of an earlier lane ends behind the
+// lane's whole first span — and the lane has further spans, those may join `cur` as well: that lane is walked again
+// here, from `cur` and the state its first row finds.  (Step grids sorted by time and of one resolution never get
+// there.)  The sums are added in this order on every run; compares are the walk's own.
+template <typename Rule>
+TC_HD TcVadSum tc_span_compose(const TcTrackIn& in, const Rule& rule, double collar, const TcDurShared& sh, int nl) {
+    TcVadSum all = {0.0, 0.0};
+    const TcSpanCount count = {in.dur_prefix, in.ref_prefix, rule.min_on, &all};
+    const int chunks = in.c1 - in.c0;
+    TcSpan cur = {0.0, 0.0, 0, 0};
+    bool have = false;
+    for (int j = 0; j < nl; ++j) {
+        const int n = sh.spans[j];
+        if (!n) continue;
+        const TcSpan first = {sh.first_s[j], sh.first_e[j], sh.first_cs[j], sh.first_ce[j]};
+        bool joins = false;
+        if (have) {
+            const double gap = first.s - cur.e;
+            joins = gap <= 1e-6 || gap < collar;
+        }
+        if (joins && n > 1 && cur.e > first.e) {
+            const TcSteps my = tc_lane_steps(in.c0, chunks, j, nl);
+            bool active = sh.start[j] != 0;
+            have = tc_span_walk(TcTrackOn<Rule>{in.agg, rule, &active}, count, in.row_off, in.mids, in.mid_cell, collar, my.lo,
+                                my.hi, cur, true);
+            continue;
+        }
+        if (joins) {
+            if (first.e > cur.e) {
+                cur.e = first.e;
+                cur.ce = first.ce;
+            }
+        } else {
+            if (have) count(cur);
+            cur = first;
+            have = true;
+        }
+        if (n > 1) {
+            count(cur);
+            all.hyp += sh.mid_hyp[j];
+            all.both += sh.mid_both[j];
+            cur.s = sh.last_s[j];
+            cur.e = sh.last_e[j];
+            cur.cs = sh.last_cs[j];
+            cur.ce = sh.last_ce[j];
+        }
+    }
+    if (have) count(cur);
+    return all;
+}
+
 template <typename Rule, typename Lanes>
-TC_HD void tc_track_pair(const TcTrackIn& in, const Rule rule, TcTrackShared<Rule::stateful>& sh, double* out, unsigned* bits,
+TC_HD void tc_track_pair(const TcTrackIn& in, const Rule rule, TcTrackSharedOf<Rule>& sh, double* out, unsigned* bits,
                          Lanes lanes) {
     const int nl = lanes.nl, chunks = in.c1 - in.c0;
-    const TcVadEnd none = {-INFINITY, 0};
+    [[maybe_unused]] const TcVadEnd none = {-INFINITY, 0};
     // ---- every lane's state map
     if constexpr (Rule::stateful)
         lanes([&](int lane) {
@@ -342,13 +523,25 @@ TC_HD void tc_track_pair(const TcTrackIn& in, const Rule rule, TcTrackShared<Rul
             }
         }
         if (!out) return;
-        bool active = start;
-        const TcVadEnd own = tc_turn_walk(TcTrackOn<Rule>{in.agg, rule, &active}, TcNoAdd{}, in.row_off, in.mids, in.mid_cell,
-                                          in.collar, my.lo, my.hi, none);
-        sh.end_e[lane] = own.e;
-        sh.end_cell[lane] = own.cell;
+        if constexpr (Rule::durations) {
+            tc_span_summary(in, rule, in.collar > rule.min_off ? in.collar : rule.min_off, my, start, sh, lane);
+        } else {
+            bool active = start;
+            const TcVadEnd own = tc_turn_walk(TcTrackOn<Rule>{in.agg, rule, &active}, TcNoAdd{}, in.row_off, in.mids,
+                                              in.mid_cell, in.collar, my.lo, my.hi, none);
+            sh.end_e[lane] = own.e;
+            sh.end_cell[lane] = own.cell;
+        }
     });
     if (!out) return;
+    if constexpr (Rule::durations) {
+        // ---- one lane composes the summaries in lane order and writes the five components
+        lanes([&](int lane) {
+            if (lane != 0) return;
+            const double collar = in.collar > rule.min_off ? in.collar : rule.min_off;
+            tc_vad_components(in.ref_prefix[in.ncell], tc_span_compose(in, rule, collar, sh, nl), out);
+        });
+    } else {
     // ---- again from the end of the last turn before the lane, summing what its turns add
     lanes([&](int lane) {
         const TcSteps my = tc_lane_steps(in.c0, chunks, lane, nl);
@@ -375,6 +568,7 @@ TC_HD void tc_track_pair(const TcTrackIn& in, const Rule rule, TcTrackShared<Rul
         }
         tc_vad_components(in.ref_prefix[in.ncell], all, out);
     });
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

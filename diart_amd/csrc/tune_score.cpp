@@ -415,12 +415,22 @@ int track_host(const char* name, const dz_tune_desc* d, const double* taus, int 
         dz_set_error("%s: bad arguments (one track per chunk, 1 .. %d lanes expected)", name, TC_TRACK_LANES);
         return 2;
     }
-    if constexpr (Rule::stateful)
-        for (int t = 0; t < trials; ++t)
-            if (!std::isfinite(taus[2 * (size_t)t + 1])) {
-                dz_set_error("%s: tau_offset of trial %d is %g, not a finite number", name, t, taus[2 * (size_t)t + 1]);
+    if constexpr (Rule::stateful) {
+        const int cols = Rule::durations ? 4 : 2;
+        for (int t = 0; t < trials; ++t) {
+            const double* q = taus + (size_t)cols * t;
+            if (!std::isfinite(q[1])) {
+                dz_set_error("%s: tau_offset of trial %d is %g, not a finite number", name, t, q[1]);
                 return 2;
             }
+            for (int k = 2; k < cols; ++k)
+                if (!(std::isfinite(q[k]) && q[k] >= 0.0)) {
+                    dz_set_error("%s: %s of trial %d is %g, not a finite number >= 0", name,
+                                 k == 2 ? "min_duration_on" : "min_duration_off", t, q[k]);
+                    return 2;
+                }
+        }
+    }
     const int N = d->N, rows = d->total_rows;
     const int slices = dz_host_threads(num_threads, rows);   // the rows, in slices
     each_item(slices, slices, [&](int, int s) {
@@ -438,7 +448,7 @@ int track_host(const char* name, const dz_tune_desc* d, const double* taus, int 
     each_item(trials * N, num_threads, [&](int, int pair) {
         const int t = pair / N, n = pair - t * N;
         const size_t pre = (size_t)file_cell_off[n] + n;
-        std::vector<TcTrackShared<Rule::stateful>> sh(1);
+        std::vector<TcTrackSharedOf<Rule>> sh(1);
         // LDS starts with whatever was there: nothing in it may be read before this pair has written it
         std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(sh[0]));
         const TcTrackIn in = {agg, d->row_off, mids, mid_cell, dur_prefix + pre, ref_prefix + pre, d->chunk_off[n],
@@ -464,6 +474,106 @@ extern "C" int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, 
                                      double* out, int num_threads) {
     return track_host<TcHystRule>("dz_tune_vad_host_hyst", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off,
                                   dur_prefix, ref_prefix, collar, lanes, out, num_threads);
+}
+
+// Minimum durations: taus (T, 4) = (tau_active, tau_offset, min_duration_on, min_duration_off), the
+// text of tune_vad_score_kernel<TcDurRule>.  backend="core".
+extern "C" int dz_tune_vad_host_dur(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+                                    const double* mids, const int* mid_cell, const int* file_cell_off,
+                                    const double* dur_prefix, const double* ref_prefix, double collar, int lanes,
+                                    double* out, int num_threads) {
+    return track_host<TcDurRule>("dz_tune_vad_host_dur", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off,
+                                 dur_prefix, ref_prefix, collar, lanes, out, num_threads);
+}
+
+// The same components from an independent sequential text, behind masks that were made elsewhere (backend="host": the
+// dz_tail handles of dz_tune_vad_replay_tails).  One host thread per pair and no lanes: the turns of the file's steps
+// from the masks, sorted by start; Annotation.support(max(collar, min_duration_off)); the spans shorter than
+// min_duration_on dropped; the cells of the others summed one by one, from cell_dur and cell_ref and not from prefix
+// sums.  bits (T, total_rows), bit 0; taus (T, 4), of which the two durations are read; out (T, N, 5).
+extern "C" int dz_tune_track_score_dur(int trials, int n_files, const unsigned* bits, int total_rows,
+                                       const int* file_chunk_off, const int* row_off, const double* mids,
+                                       const int* mid_cell, const int* file_cell_off, const double* cell_dur,
+                                       const unsigned long long* cell_ref, const double* taus, double collar, double* out,
+                                       int num_threads) {
+    if (!bits || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off || !cell_dur || !cell_ref || !taus ||
+        !out) {
+        dz_set_error("dz_tune_track_score_dur: NULL argument");
+        return 2;
+    }
+    if (trials < 1 || n_files < 1 || total_rows < 1) {
+        dz_set_error("dz_tune_track_score_dur: empty shape (%d trials, %d files, %d rows)", trials, n_files, total_rows);
+        return 2;
+    }
+    for (int t = 0; t < trials; ++t)
+        for (int k = 2; k < 4; ++k) {
+            const double v = taus[4 * (size_t)t + k];
+            if (!(std::isfinite(v) && v >= 0.0)) {
+                dz_set_error("dz_tune_track_score_dur: %s of trial %d is %g, not a finite number >= 0",
+                             k == 2 ? "min_duration_on" : "min_duration_off", t, v);
+                return 2;
+            }
+        }
+    const dz_host_failure f = dz_host_parallel_rc(trials * n_files, dz_host_threads(num_threads, trials * n_files), [&](int, int pair) {
+        const int t = pair / n_files, n = pair - t * n_files;
+        const unsigned* B = bits + (size_t)t * total_rows;
+        const double min_on = taus[4 * (size_t)t + 2], min_off = taus[4 * (size_t)t + 3];
+        const double join = collar > min_off ? collar : min_off;
+        const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
+        std::vector<Turn> turns;
+        for (int c = file_chunk_off[n]; c < file_chunk_off[n + 1]; ++c) {
+            const int p = row_off[c], rows = row_off[c + 1] - p;
+            const double* mid = mids + (size_t)p + c;
+            const int* cell = mid_cell + (size_t)p + c;
+            for (int r = 0; r < rows;) {
+                if (!(B[p + r] & 1u)) {
+                    ++r;
+                    continue;
+                }
+                int e = r;
+                while (e < rows && (B[p + e] & 1u)) ++e;
+                if (mid[e] - mid[r] > 1e-6) turns.push_back(Turn{mid[r], mid[e], cell[r], cell[e]});
+                r = e;
+            }
+        }
+        std::stable_sort(turns.begin(), turns.end(), [](const Turn& a, const Turn& b) { return a.s < b.s; });
+        std::vector<Turn> spans;
+        for (const Turn& u : turns) {
+            if (!spans.empty()) {
+                Turn& last = spans.back();
+                const double gap = u.s - last.e;
+                if (gap <= 1e-6 || gap < join) {
+                    if (u.e > last.e) {
+                        last.e = u.e;
+                        last.ie = u.ie;
+                    }
+                    continue;
+                }
+            }
+            spans.push_back(u);
+        }
+        double total = 0.0, hyp = 0.0, both = 0.0;
+        for (int i = 0; i < ncell; ++i)
+            if (cell_ref[cell0 + i]) total += cell_dur[cell0 + i];
+        for (const Turn& u : spans) {
+            if (u.e - u.s < min_on) continue;
+            if (u.is < 0 || u.ie > ncell || u.is > u.ie) return 4;
+            for (int i = u.is; i < u.ie; ++i) {
+                hyp += cell_dur[cell0 + i];
+                if (cell_ref[cell0 + i]) both += cell_dur[cell0 + i];
+            }
+        }
+        double* o = out + (size_t)pair * 5;
+        const double fa = hyp - both, missed = total - both;
+        o[0] = total;
+        o[1] = both;
+        o[2] = fa > 0.0 ? fa : 0.0;
+        o[3] = missed > 0.0 ? missed : 0.0;
+        o[4] = 0.0;
+        return 0;
+    });
+    if (f.code) dz_set_error("dz_tune_track_score_dur: a speech turn does not start and end on the file's scoring cells");
+    return f.code;
 }
 
 // The same masks from an independent text: one dz_tail handle per (trial, file) with dz_tail_set_offset, the file's

@@ -4,7 +4,9 @@ Same names and results as ``/root/reference/src/diart/functional.py`` (:6-13
 ``overlapped_speech_penalty``, :16-27 ``normalize_embeddings``), plus ``resample`` and ``adjust_volume``, the
 functional forms of the ``Resample`` and ``AdjustVolume`` blocks, and ``decode_pcm``, the push kernel's sample
 conversion over one buffer, and ``overlap_track``, the per-frame reduction of ``OverlappedSpeechDetection`` (the one
-function here that answers a host tensor on the host: its definition is a torch statement).  Inputs may live on the host
+function here that answers a host tensor on the host: its definition is a torch statement), and ``min_duration``,
+which is no tensor function at all: the rule of the track pipelines' minimum durations on an annotation, host
+bookkeeping at the end of a file.  Inputs may live on the host
 (the reference runs these on CPU tensors) or on the GPU; the result comes back on the device
 of the input.  There is no torch fallback: without ``libdiart_amd.so`` and a GPU they raise.
 """
@@ -412,3 +414,24 @@ def gallery_match_normalised(embeddings, voiceprints, cohort, top_n=300):
     index = torch.where(bad, torch.full_like(index, -1), index).to(torch.int32)
     return (index.reshape(lead), torch.where(bad, nan, dist).to(torch.float32).reshape(lead),
             torch.where(bad, nan, second).to(torch.float32).reshape(lead))
+
+
+def min_duration(annotation, min_duration_on: float = 0.0, min_duration_off: float = 0.0, patch_collar: float = 0.05):
+    """The minimum durations of ``VoiceActivityDetection`` and ``OverlappedSpeechDetection`` on a file's accumulated
+    turns, per label: the gaps are filled first — ``annotation.support(max(patch_collar, min_duration_off))``, which is
+    ``support(patch_collar)`` followed by ``support(min_duration_off)`` — then every merged turn with
+    ``end - start < min_duration_on`` (strictly) is dropped.  A turn that will be dropped still bridges gaps.  This is
+    ``PredictionAccumulator``'s stitching followed by the tail of pyannote's ``Binarize``.  ``annotation``: the project's
+    ``Annotation`` or pyannote's; a new one of the same class comes back.  Both durations 0:
+    ``annotation.support(patch_collar)``.  It needs the whole file: a live step has no look-ahead, and no engine calls it."""
+    from .blocks.base import check_min_duration
+    on = check_min_duration(min_duration_on, "min_duration_on", "min_duration")
+    off = check_min_duration(min_duration_off, "min_duration_off", "min_duration")
+    merged = annotation.support(max(float(patch_collar), off))
+    if on == 0.0:
+        return merged
+    out = type(merged)(uri=merged.uri, modality=merged.modality)
+    for segment, track, label in merged.itertracks(yield_label=True):
+        if not (segment.end - segment.start < on):
+            out[segment, track] = label
+    return out

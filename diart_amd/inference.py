@@ -245,10 +245,17 @@ def rolling_windows(blocks: Iterable[np.ndarray], duration: float = 5.0, step: f
 # -------------------------------------------------------------------------------- inference
 class PredictionAccumulator:
     """Joins the per-chunk annotations of one stream; same-speaker turns closer than
-    ``patch_collar`` are stitched (``Annotation.support``)."""
+    ``patch_collar`` are stitched (``Annotation.support``).  ``min_duration_on`` / ``min_duration_off`` (the track
+    pipelines' configuration; seconds): ``functional.min_duration`` in ``get_prediction``, where the whole stream is
+    known — gaps shorter than ``min_duration_off`` filled, then turns shorter than ``min_duration_on`` dropped.  Both 0:
+    the stitching alone."""
 
-    def __init__(self, uri: Optional[str] = None, patch_collar: float = 0.05):
+    def __init__(self, uri: Optional[str] = None, patch_collar: float = 0.05, min_duration_on: float = 0.0,
+                 min_duration_off: float = 0.0):
+        from .blocks.base import check_min_duration
         self.uri, self.patch_collar = uri, patch_collar
+        self.min_duration_on = check_min_duration(min_duration_on, "min_duration_on", "PredictionAccumulator")
+        self.min_duration_off = check_min_duration(min_duration_off, "min_duration_off", "PredictionAccumulator")
         self._prediction: Optional[Annotation] = None
 
     def on_next(self, value):
@@ -260,9 +267,14 @@ class PredictionAccumulator:
             self._prediction.update(prediction)
 
     def get_prediction(self) -> Optional[Annotation]:
-        if self._prediction is not None:
-            self._prediction = self._prediction.support(self.patch_collar)
-        return self._prediction
+        if self._prediction is None:
+            return None
+        self._prediction = self._prediction.support(self.patch_collar)
+        if self.min_duration_on == 0.0 and self.min_duration_off == 0.0:
+            return self._prediction
+        # the accumulated turns stay as they are (a later on_next may still bridge a gap); the durations act on a copy
+        from .functional import min_duration
+        return min_duration(self._prediction, self.min_duration_on, self.min_duration_off, self.patch_collar)
 
 
 class StreamingInference:
@@ -282,7 +294,9 @@ class StreamingInference:
             waveform = resample_file(waveform, sample_rate, cfg.sample_rate, cfg.device)
             sample_rate = cfg.sample_rate
         self.pipeline, self.batch_size, self.hooks = pipeline, max(1, int(batch_size)), list(hooks)
-        self.accumulator = PredictionAccumulator(uri)
+        # the track pipelines' minimum durations act on the accumulated prediction, never on a step's output
+        self.accumulator = PredictionAccumulator(uri, min_duration_on=getattr(cfg, "min_duration_on", 0.0),
+                                                 min_duration_off=getattr(cfg, "min_duration_off", 0.0))
         self._windows = rolling_windows(file_blocks(waveform, sample_rate, padding, cfg.step),
                                         cfg.duration, cfg.step, sample_rate)
         total = padding[0] + len(waveform) / sample_rate + padding[1]
@@ -443,7 +457,9 @@ class Benchmark:
         hyper = () if one_track else (config.rho_update, config.delta_new, config.gamma, config.beta,
                                           config.max_speakers, config.normalize_embedding_weights)
         key = (kind, id(seg.model), None if one_track else id(emb.model), config.tau_active,
-               getattr(config, "tau_offset", None) if one_track else None, hyper, config.duration,
+               getattr(config, "tau_offset", None) if one_track else None,
+               (getattr(config, "min_duration_on", 0.0), getattr(config, "min_duration_off", 0.0)) if one_track else None,
+               hyper, config.duration,
                config.step, config.latency, config.sample_rate, str(config.device), self.batch_size,
                self.concurrent_files, self.file_batch_rows)
         cached = getattr(self, "_fb_cache", None)
@@ -459,7 +475,9 @@ class Benchmark:
                       sample_rate=config.sample_rate, device=config.device)
         if emb is None:
             return FileBatch(seg.model, None, pipeline="osd" if kind == "osd" else "vad",
-                             tau_offset=getattr(config, "tau_offset", None), **common)
+                             tau_offset=getattr(config, "tau_offset", None),
+                             min_duration_on=getattr(config, "min_duration_on", 0.0),
+                             min_duration_off=getattr(config, "min_duration_off", 0.0), **common)
         return FileBatch(seg.model, emb.model, rho_update=config.rho_update, delta_new=config.delta_new,
                          gamma=config.gamma, beta=config.beta, max_speakers=config.max_speakers,
                          normalize_embedding_weights=config.normalize_embedding_weights, **common)

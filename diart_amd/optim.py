@@ -54,7 +54,9 @@ TUNABLE = ("tau_active", "rho_update", "delta_new")
 IDENT_TUNABLE = TUNABLE + ("delta_id",)
 VAD_TUNABLE = ("tau_active",)
 # with hysteresis (blocks.base.TauOffset): the track pipelines' second threshold, replayed by tune_vad_score_kernel<TcHystRule>
-TRACK_TUNABLE = ("tau_active", "tau_offset")
+# and the minimum durations (blocks.base.MinDurationOn / MinDurationOff), which act on a file's merged turns: <TcDurRule>
+TRACK_TUNABLE = ("tau_active", "tau_offset", "min_duration_on", "min_duration_off")
+DURATIONS = ("min_duration_on", "min_duration_off")
 MAX_SPEAKERS = 32          # the hypothesis of a frame is one 32-bit mask
 MAX_LOCAL_SPEAKERS = 8
 PATCH_COLLAR = 0.05        # PredictionAccumulator's default
@@ -978,41 +980,56 @@ class _TrackTuneCache(_ReplayCache):
         return 4 * self.total_rows
 
     # ------------------------------------------------------------------------------------------ replay
-    @staticmethod
-    def _taus(taus) -> np.ndarray:
+    SHAPES = ("(T,) or (T, 1) = tau_active per trial, (T, 2) = (tau_active, tau_offset) per trial or (T, 4) = "
+              "(tau_active, tau_offset, min_duration_on, min_duration_off) per trial")
+
+    @classmethod
+    def _taus(cls, taus) -> np.ndarray:
         """``(T,)`` — ``(T, 1)`` too — = tau_active per trial: the single threshold, today's kernels.  ``(T, 2)`` =
-        (tau_active, tau_offset) per trial: hysteresis, and the array stays two-dimensional."""
+        (tau_active, tau_offset) per trial: hysteresis, and the array stays two-dimensional.  ``(T, 4)`` = (tau_active,
+        tau_offset, min_duration_on, min_duration_off): the minimum durations (seconds) on the hysteresis rows; a trial
+        without hysteresis passes tau_offset == tau_active."""
         try:
             t = np.asarray(taus, dtype=np.float64)
         except (TypeError, ValueError):
-            raise ValueError("taus (T,), (T, 1) = tau_active or (T, 2) = (tau_active, tau_offset) per trial expected: "
-                             "numbers") from None
+            raise ValueError(f"taus {cls.SHAPES} expected: numbers") from None
         if t.ndim == 2 and t.shape[1] == 1:
             t = t[:, 0]
         if t.ndim == 2 and t.shape[1] == 2 and t.shape[0] >= 1:
             if not np.isfinite(t[:, 1]).all():
                 raise ValueError("taus (T, 2): tau_offset must be finite in every trial")
             return np.ascontiguousarray(t)
+        if t.ndim == 2 and t.shape[1] == 4 and t.shape[0] >= 1:
+            if not np.isfinite(t[:, 1]).all():
+                raise ValueError("taus (T, 4): tau_offset must be finite in every trial")
+            for k, name in ((2, "min_duration_on"), (3, "min_duration_off")):
+                bad = np.flatnonzero(~(np.isfinite(t[:, k]) & (t[:, k] >= 0)))
+                if len(bad):
+                    raise ValueError(f"taus (T, 4): {name} of trial {int(bad[0])} is {t[bad[0], k]}: a duration is a "
+                                     "finite number >= 0")
+            return np.ascontiguousarray(t)
         if t.ndim != 1 or t.shape[0] < 1:
-            raise ValueError(f"taus (T,) or (T, 1) = tau_active per trial, or (T, 2) = (tau_active, tau_offset) per trial "
-                             f"expected, got {np.shape(taus)}")
+            raise ValueError(f"taus {cls.SHAPES} expected, got {np.shape(taus)}")
         return np.ascontiguousarray(t)
 
     def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int, core: bool = True):
         """``(agg, bits, components)`` on host threads, from the kernels' text: ``dz_tune_vad_host`` for ``taus (T,)``,
-        ``dz_tune_vad_host_hyst`` — the lanes' state maps included — for ``taus (T, 2)``.  ``core=False`` with
-        ``(T, 2)`` (backend="host"): the masks come from an independent text instead — one ``dz_tail`` handle with
-        ``dz_tail_set_offset`` per (trial, file), fed the track step by step — and there are no components."""
+        ``dz_tune_vad_host_hyst`` — the lanes' state maps included — for ``taus (T, 2)``, ``dz_tune_vad_host_dur`` — the
+        lanes' span summaries too — for ``taus (T, 4)``.  ``core=False`` with ``(T, 2)`` or ``(T, 4)`` (backend="host"):
+        the masks come from an independent text instead — one ``dz_tail`` handle with ``dz_tail_set_offset`` per (trial,
+        file), fed the track step by step, which reads the first two columns — and there are no components."""
         T = taus.shape[0]
         tails = taus.ndim == 2 and not core
         assert not (tails and components)
+        pairs = np.ascontiguousarray(taus[:, :2]) if tails else None
         agg = np.empty(self.total_rows, dtype=np.float64)
         b = np.empty((T, self.total_rows), dtype=np.uint32) if bits else None
         out = np.zeros((T, self.N, 5), dtype=np.float64) if components else None
         d = self._desc(lambda name: getattr(self, name).ctypes.data)
         ptr = lambda a: None if a is None else a.ctypes.data
         lib = _lib.load()
-        name = "dz_tune_vad_host_hyst" if taus.ndim == 2 and core else "dz_tune_vad_host"
+        name = ("dz_tune_vad_host" if taus.ndim == 1 or not core else
+                "dz_tune_vad_host_dur" if taus.shape[1] == 4 else "dz_tune_vad_host_hyst")
         thresholds = np.ascontiguousarray(taus[:, 0]) if tails else taus          # (the aggregation reads none of them)
         _lib.check(getattr(lib, name)(C.byref(d), thresholds.ctypes.data, T, agg.ctypes.data, None if tails else ptr(b),
                                       self.mids.ctypes.data, self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
@@ -1021,7 +1038,7 @@ class _TrackTuneCache(_ReplayCache):
         if tails and bits:
             starts = np.ascontiguousarray(self.starts, dtype=np.float64)
             res = np.ascontiguousarray(self.res, dtype=np.float64)
-            _lib.check(lib.dz_tune_vad_replay_tails(C.byref(d), taus.ctypes.data, T, self.meta["step"], self.meta["latency"],
+            _lib.check(lib.dz_tune_vad_replay_tails(C.byref(d), pairs.ctypes.data, T, self.meta["step"], self.meta["latency"],
                                                     starts.ctypes.data, res.ctypes.data, b.ctypes.data, int(num_threads)),
                        "dz_tune_vad_replay_tails")
         return agg, b, out
@@ -1050,6 +1067,15 @@ class _TrackTuneCache(_ReplayCache):
         b = torch.empty((T, self.total_rows), dtype=torch.int32, device=device) if bits else None
         out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device) if components else None
         ptr = lambda a: None if a is None else a.data_ptr()
+        if taus.ndim == 2 and taus.shape[1] == 4:
+            # (T, 4): the third instantiation, which takes the trials in host memory too and checks the durations there
+            _lib.check(_lib.load().dz_tune_vad_score_dur(
+                _lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(), taus.ctypes.data,
+                d_taus.data_ptr(), t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(),
+                t["mid_cell"].data_ptr(), t["file_cell_off"].data_ptr(), t["dur_prefix"].data_ptr(),
+                t["ref_prefix"].data_ptr(), PATCH_COLLAR, ptr(out), ptr(b), torch.cuda.current_stream(device).cuda_stream),
+                "dz_tune_vad_score_dur")
+            return t["agg"], b, out
         # (T, 2): the stateful instantiation of tune_vad_score_kernel, one workgroup per (trial, file) for the masks too
         entry, name = ((_lib.load().dz_tune_vad_score_hyst, "dz_tune_vad_score_hyst") if taus.ndim == 2 else
                        (_lib.load().dz_tune_vad_score, "dz_tune_vad_score"))
@@ -1065,7 +1091,11 @@ class _TrackTuneCache(_ReplayCache):
         """``(agg (rows,) float64, bits (T, rows) uint32)``: the aggregated speech score of every packed output frame
         and, per trial, whether it is above the trial's tau.  ``backend``: "gpu" | "host".  ``taus (T, 2)`` =
         (tau_active, tau_offset): whether the frame is on under the hysteresis rule, the state off at every file's first
-        frame; then "core" too, the kernel's text on host threads ("host" goes through ``dz_tail_set_offset``)."""
+        frame; then "core" too, the kernel's text on host threads ("host" goes through ``dz_tail_set_offset``).
+        ``taus (T, 4)`` = (tau_active, tau_offset, min_duration_on, min_duration_off): the masks BEFORE the durations
+        act, which are the ``(T, 2)`` masks of the first two columns — a mask says which frames are on, and a gap that
+        ``min_duration_off`` fills lies between two steps' rows as often as inside one: a filled gap is not a row, and
+        a dropped turn keeps its rows.  ``hypothesis(bits_row, n, min_duration_on, min_duration_off)`` applies them."""
         taus = self._taus(taus)
         backend = backend or self.default_backend()
         hyst = taus.ndim == 2
@@ -1090,7 +1120,11 @@ class _TrackTuneCache(_ReplayCache):
         whose masks fit ``memory_budget`` bytes) or "core" (the scoring kernel's text on host threads).  ``taus (T, 2)``
         = (tau_active, tau_offset) per trial: hysteresis — "gpu" runs ``tune_vad_score_kernel`` under the stateful rule,
         "core" its text, "host" one ``dz_tail`` handle with ``dz_tail_set_offset`` per (trial, file), then
-        ``dz_tune_score``.  ``(T,)`` is the same pair routine under the stateless rule."""
+        ``dz_tune_score``.  ``(T,)`` is the same pair routine under the stateless rule.  ``taus (T, 4)`` = (tau_active,
+        tau_offset, min_duration_on, min_duration_off): the file's turns merged with the collar ``max(PATCH_COLLAR,
+        min_duration_off)``, then the merged turns shorter than ``min_duration_on`` dropped
+        (``functional.min_duration``) — "gpu" runs the pair routine's third instantiation, "core" its text, "host" the
+        ``dz_tail`` masks and then ``dz_tune_track_score_dur``, one sequential walk per (trial, file)."""
         taus = self._taus(taus)
         backend = backend or self.default_backend()
         if backend == "gpu":
@@ -1102,17 +1136,39 @@ class _TrackTuneCache(_ReplayCache):
             per_file = self._host(taus, False, True, num_threads)[2]
         elif backend == "host":
             per_batch = max(1, int(memory_budget) // max(1, self.bytes_per_trial))
-            per_file = np.concatenate([self.score(self._host(taus[a:a + per_batch], True, False, num_threads, core=False)[1],
-                                                  num_threads) for a in range(0, taus.shape[0], per_batch)])
+            durations = taus.ndim == 2 and taus.shape[1] == 4
+            score = (lambda bits, t: self._score_durations(bits, t, num_threads)) if durations else \
+                (lambda bits, t: self.score(bits, num_threads))
+            per_file = np.concatenate([score(self._host(taus[a:a + per_batch], True, False, num_threads, core=False)[1],
+                                             taus[a:a + per_batch]) for a in range(0, taus.shape[0], per_batch)])
         else:
             raise ValueError(f"backend '{backend}': gpu, host or core")
         comp = per_file.sum(axis=1)
         return TuneResult(_rates(comp), comp, per_file, np.full((taus.shape[0], self.N), -1, dtype=np.int32))
 
-    def hypothesis(self, bits_row: np.ndarray, n: int) -> Annotation:
+    def _score_durations(self, bits: np.ndarray, taus: np.ndarray, num_threads: int = 8) -> np.ndarray:
+        """``(T, N, 5)`` components of the masks of ``replay`` under the durations of ``taus (T, 4)``, by
+        ``dz_tune_track_score_dur``: one sequential walk per (trial, file), no lanes."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        taus = np.ascontiguousarray(taus, dtype=np.float64)
+        out = np.zeros((bits.shape[0], self.N, 5), dtype=np.float64)
+        _lib.check(_lib.load().dz_tune_track_score_dur(bits.shape[0], self.N, bits.ctypes.data, self.total_rows,
+                                                       self.chunk_off.ctypes.data, self.row_off.ctypes.data,
+                                                       self.mids.ctypes.data, self.mid_cell.ctypes.data,
+                                                       self.file_cell_off.ctypes.data, self.cell_dur.ctypes.data,
+                                                       self.cell_ref.ctypes.data, taus.ctypes.data, PATCH_COLLAR,
+                                                       out.ctypes.data, int(num_threads)), "dz_tune_track_score_dur")
+        return out
+
+    def hypothesis(self, bits_row: np.ndarray, n: int, min_duration_on: float = 0.0,
+                   min_duration_off: float = 0.0) -> Annotation:
         """File n's hypothesis under one trial as ``PredictionAccumulator`` ends with it: turns labelled "speech"
-        (``VadTuneCache``) or "overlap" (``OsdTuneCache``)."""
-        return self._hypothesis(bits_row, n, 1, lambda g: self.LABEL)
+        (``VadTuneCache``) or "overlap" (``OsdTuneCache``); with durations, filtered by ``functional.min_duration``."""
+        ann = self._hypothesis(bits_row, n, 1, lambda g: self.LABEL)
+        if min_duration_on == 0.0 and min_duration_off == 0.0:
+            return ann
+        from .functional import min_duration
+        return min_duration(ann, min_duration_on, min_duration_off, PATCH_COLLAR)
 
 
 class VadTuneCache(_TrackTuneCache):
@@ -1234,7 +1290,8 @@ class Optimizer:
     parameter's range, from ``seed``) or "grid" (``num_iter`` as a total: the largest cube not above it).  Trials are
     evaluated ``trials_per_batch`` at a time; ``cache``: a collected ``TuneCache`` (the models then never run);
     ``scoring``: ``TuneCache.evaluate``'s (None and "host": on host threads, "device": on the replay's backend).
-    ``pipeline_class``: ``SpeakerDiarization``, or ``VoiceActivityDetection`` — then ``tau_active`` alone is tuned, the
+    ``pipeline_class``: ``SpeakerDiarization``, or ``VoiceActivityDetection`` — then ``tau_active`` alone is tuned (the
+    default; ``hparams=`` may name ``TauOffset``, ``MinDurationOn`` and ``MinDurationOff`` beside or instead of it), the
     metric is the detection error rate and the cache a ``VadTuneCache`` — or ``OverlappedSpeechDetection``:
     ``tau_active`` alone, an ``OsdTuneCache``, and as the metric ``OverlapDetectionErrorRate`` (the default) or, with
     ``direction="maximize"``, ``OverlapDetectionFMeasure``: the objective is then ``100 * F`` of the components summed
@@ -1314,8 +1371,13 @@ class Optimizer:
         if not track and (hasattr(self.base_config, "tau_offset") or any(p.name == "tau_offset" for p in self.hparams)):
             from .blocks.diarization import refuse_tau_offset
             refuse_tau_offset({"tau_offset": None}, f"Optimizer({pipeline_class.__name__})")
+        if not track:
+            base.refuse_min_duration({name: None for name in DURATIONS if hasattr(self.base_config, name) or
+                                      any(p.name == name for p in self.hparams)}, f"Optimizer({pipeline_class.__name__})")
         if track:
             base.check_tau_offset(getattr(self.base_config, "tau_offset", None), "Optimizer: base_config")
+            for name in DURATIONS:
+                base.check_min_duration(getattr(self.base_config, name, 0.0), name, "Optimizer: base_config")
         for param in self.hparams:
             if param.name == "delta_id" and gallery is None:
                 raise ValueError("hyper-parameter delta_id is the identification distance of a gallery: gallery= and "
@@ -1381,15 +1443,27 @@ class Optimizer:
             # that is not tuned is the base configuration's in every trial, and the trial's own tau_active without one
             tau = float(params.get("tau_active", self.base_config.tau_active))
             fixed = getattr(self.base_config, "tau_offset", None)
+            offset = tau if "tau_offset" not in params and fixed is None else float(params.get("tau_offset", fixed))
+            if self._durations():
+                # four columns: a duration that is not tuned is the base configuration's in every trial, and a trial
+                # without hysteresis carries its own tau_active as the offset
+                return [tau, offset] + [float(params.get(name, getattr(self.base_config, name, 0.0))) for name in DURATIONS]
             if "tau_offset" not in params and fixed is None:
                 return [tau] if not self._hysteresis() else [tau, tau]
-            return [tau, float(params.get("tau_offset", fixed))]
+            return [tau, offset]
         return [float(params.get(name, self._base_value(name))) for name in self.tunable]
 
     def _hysteresis(self) -> bool:
         """Does a trial of this study carry (tau_active, tau_offset)?"""
         return (any(p.name == "tau_offset" for p in self.hparams) or
                 getattr(self.base_config, "tau_offset", None) is not None)
+
+    def _durations(self) -> bool:
+        """Does a trial of this study carry (tau_active, tau_offset, min_duration_on, min_duration_off)?  Only when a
+        duration is tuned or the base configuration sets one non-zero: otherwise the kernels launched are those of a
+        study without them."""
+        return any(p.name in DURATIONS for p in self.hparams) or \
+            any(float(getattr(self.base_config, name, 0.0)) != 0.0 for name in DURATIONS)
 
     def _base_value(self, name: str) -> float:
         """The base configuration's value; delta_id is no field of a configuration: the constructor's.  A tau_offset of

@@ -1231,6 +1231,11 @@ class GroupsBatch(_TwoChainEngine):
     not reach this engine."""
 
 
+def _is_zero(value) -> bool:
+    """Is ``value`` the number 0 (the default of an argument that a form does not take)?"""
+    return isinstance(value, (int, float)) and not isinstance(value, bool) and value == 0
+
+
 class FileBatch:
     """Several FILES of one rank through the hot path at once — the file-parallel evaluation
     (BASELINE.json configs 1 / 4) at the batcher's rate.
@@ -1279,7 +1284,8 @@ class FileBatch:
                  latency: Optional[float] = None, sample_rate: int = 16000,
                  device: Optional[torch.device] = None, threads: int = 8, patch_collar: float = 0.05,
                  recurrence: Optional[str] = "valu", lanes: Optional[int] = 2, pipeline: str = "diarization",
-                 gather: Optional[bool] = None, tau_offset: Optional[float] = None):
+                 gather: Optional[bool] = None, tau_offset: Optional[float] = None, min_duration_on: float = 0.0,
+                 min_duration_off: float = 0.0):
         """``recurrence`` / ``lanes``: the engine under the files.  A file job is short and its files end at different
         times: the latency-form recurrence on two lanes finishes 16 ten-minute files 13 - 40 % sooner than the
         throughput engine a 64-row ``StreamBatch`` would pick for itself (profiles/r06q_file_batch_engine.json:
@@ -1291,7 +1297,10 @@ class FileBatch:
         ``pipeline``: "diarization" | "vad" | "osd" (``embedding`` must be None for the last two).  ``gather``: fill a step's stage with one
         ``dz_gather_windows`` launch instead of one torch copy per open file (None = the form's default).
         ``tau_offset``: the hysteresis of the "vad" and "osd" forms (every file's tail starts with the state off);
-        ``pipeline="diarization"`` refuses it."""
+        ``pipeline="diarization"`` refuses it.  ``min_duration_on`` / ``min_duration_off`` (seconds): the minimum
+        durations of the "vad" and "osd" forms, ``functional.min_duration`` on a file's turns at its end, where
+        ``support(patch_collar)`` stitches them — the engine under the files is a live engine, has no look-ahead and never
+        sees them; ``pipeline="diarization"`` refuses them by name."""
         self.rows, self.max_files = int(rows), max(1, min(int(max_files), int(rows)))
         if pipeline not in ("diarization", "vad", "osd"):
             raise ValueError(f"FileBatch: pipeline={pipeline!r} (expected diarization | vad | osd)")
@@ -1300,6 +1309,14 @@ class FileBatch:
             refuse_tau_offset({"tau_offset": tau_offset}, "FileBatch(pipeline='diarization')")
         from .blocks.base import check_tau_offset
         self.tau_offset = check_tau_offset(tau_offset, "FileBatch")
+        if pipeline == "diarization":
+            from .blocks.base import refuse_min_duration
+            refuse_min_duration({k: v for k, v in (("min_duration_on", min_duration_on),
+                                                   ("min_duration_off", min_duration_off)) if not _is_zero(v)},
+                                "FileBatch(pipeline='diarization')")
+        from .blocks.base import check_min_duration
+        self.min_duration_on = check_min_duration(min_duration_on, "min_duration_on", "FileBatch")
+        self.min_duration_off = check_min_duration(min_duration_off, "min_duration_off", "FileBatch")
         if pipeline in ("vad", "osd"):
             if embedding is not None:
                 raise ValueError(f"FileBatch(pipeline={pipeline!r}) takes no embedding")
@@ -1626,5 +1643,9 @@ class FileBatch:
                             ann[Segment(s + shift, e + shift), n] = self.engine.LABEL
                         else:
                             ann[Segment(s + shift, e + shift), int(g)] = f"speaker{int(g)}"
-            out[uri] = ann.support(self.patch_collar)
+            if self.min_duration_on == 0.0 and self.min_duration_off == 0.0:
+                out[uri] = ann.support(self.patch_collar)
+            else:
+                from .functional import min_duration
+                out[uri] = min_duration(ann, self.min_duration_on, self.min_duration_off, self.patch_collar)
         return out

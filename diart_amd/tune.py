@@ -43,6 +43,12 @@ def parser() -> argparse.ArgumentParser:
                     help="Base value of tau_offset, the offset threshold of the hysteresis of VoiceActivityDetection and "
                          "OverlappedSpeechDetection (a frame stays on while its score is above it). Defaults to none: the "
                          "single threshold tau_active")
+    ap.add_argument("--min-duration-on", default=0.0, type=float,
+                    help="Base value of min_duration_on in seconds (VoiceActivityDetection and OverlappedSpeechDetection): "
+                         "turns of a file shorter than this are dropped, after the gaps are filled. Defaults to 0")
+    ap.add_argument("--min-duration-off", default=0.0, type=float,
+                    help="Base value of min_duration_off in seconds (VoiceActivityDetection and OverlappedSpeechDetection): "
+                         "gaps of a file shorter than this are filled. Defaults to 0")
     ap.add_argument("--rho-update", default=0.3, type=float, help="Base value of rho_update. Defaults to 0.3")
     ap.add_argument("--delta-new", default=1, type=float, help="Base value of delta_new. Defaults to 1")
     ap.add_argument("--gamma", default=3, type=float, help="Overlapped-speech-penalty gamma. Defaults to 3")
@@ -58,7 +64,7 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--hparams", nargs="+", default=None,
                     help="Hyper-parameters to optimize: tau_active, rho_update, delta_new (the default is all three); "
                          "tau_active alone with --pipeline VoiceActivityDetection or OverlappedSpeechDetection, where tau_offset "
-                         "can be named beside it (hysteresis); with --gallery "
+                         "(hysteresis), min_duration_on and min_duration_off can be named beside it; with --gallery "
                          "also delta_id (the default is then all four)")
     ap.add_argument("--gallery", type=str, default=None,
                     help="A SpeakerGallery file (.npz): tune delta_id too, against the identification error rate")
@@ -105,8 +111,14 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
                                        (VoiceActivityDetection, VadTuneCache))
         base_config = pipeline_class.get_config_class()(segmentation=seg, duration=args.duration, step=args.step,
                                                         latency=args.latency, tau_active=args.tau_active, device=None,
-                                                        tau_offset=getattr(args, "tau_offset", None))
+                                                        tau_offset=getattr(args, "tau_offset", None),
+                                                        min_duration_on=getattr(args, "min_duration_on", 0.0),
+                                                        min_duration_off=getattr(args, "min_duration_off", 0.0))
     else:
+        for name in ("min_duration_on", "min_duration_off"):
+            if getattr(args, name, 0.0) != 0.0 or name in (args.hparams or []):
+                raise SystemExit(f"{name} is not a parameter of SpeakerDiarization: the minimum durations are tuned with "
+                                 "--pipeline VoiceActivityDetection or OverlappedSpeechDetection")
         if getattr(args, "tau_offset", None) is not None or "tau_offset" in (args.hparams or []):
             raise SystemExit("tau_offset is not a parameter of SpeakerDiarization: hysteresis is tuned with --pipeline "
                              "VoiceActivityDetection or OverlappedSpeechDetection")
@@ -119,8 +131,9 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
     possible = list(pipeline_class.hyper_parameters())
     default = [hp.name for hp in possible]
     if vad:
-        from .blocks.base import TauOffset
-        possible = possible + [TauOffset]            # tuned on request (--hparams tau_active tau_offset), never by default
+        from .blocks.base import MinDurationOff, MinDurationOn, TauOffset
+        # tuned on request (--hparams tau_active tau_offset min_duration_on min_duration_off), never by default
+        possible = possible + [TauOffset, MinDurationOn, MinDurationOff]
     if gallery is not None:
         from .blocks.base import DeltaId
         possible, cache_class = possible + [DeltaId], IdentTuneCache

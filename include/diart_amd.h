@@ -1174,6 +1174,33 @@ int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, int trials,
                           const double* mids, const int* mid_cell, const int* file_cell_off,
                           const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
                           int num_threads);
+/* The track pipelines with minimum durations, where a whole file is known: d_taus / taus are (T, 4) =
+ * (tau_active, tau_offset, min_duration_on, min_duration_off) per trial.  The rows and the masks are the hysteresis
+ * form's (no hysteresis: tau_offset == tau_active) — the masks are taken BEFORE the durations act; a filled gap is no
+ * row.  The file's turns are merged with the collar max(collar, min_duration_off) (Annotation.support), then a merged
+ * span counts unless end - start < min_duration_on, strictly, both from `mids`.  The same pair routine under a third
+ * rule (TcDurRule): every lane leaves a summary of its steps, one lane composes the summaries in lane order.
+ * dz_tune_vad_score_dur takes the trials twice: `taus` in host memory, which it checks before the device is touched,
+ * and d_taus; its other arguments are dz_tune_vad_score_hyst's, and dz_tune_vad_host_dur's are dz_tune_vad_host_hyst's.
+ * All three return 2, with a message that names the function, for a NULL pointer, trials < 1 and a duration that is
+ * negative or not finite.                                                                                            */
+int dz_tune_vad_score_dur(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
+                          const double* taus, const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
+                          const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
+                          const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
+                          unsigned* d_bits, void* stream);
+int dz_tune_vad_host_dur(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
+                         const double* mids, const int* mid_cell, const int* file_cell_off,
+                         const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
+                         int num_threads);
+/* The components of the same trials from an independent sequential text, behind masks made elsewhere: one host thread
+ * per (trial, file) walks the file's turns from bits (T, total_rows; bit 0) in order, merges, drops and sums the
+ * cells one by one (cell_dur, cell_ref as in dz_tune_score).  Of taus (T, 4) the two durations are read.  Returns 4
+ * when a turn does not start and end on the file's cells.                                                           */
+int dz_tune_track_score_dur(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
+                            const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
+                            const double* cell_dur, const unsigned long long* cell_ref, const double* taus,
+                            double collar, double* out, int num_threads);
 /* The masks of the same trials from an independent text: one dz_tail handle per (trial, file) with dz_tail_set_offset,
  * fed the file's track step by step (starts, resolution (chunks), step, latency as dz_tail_step gets them), the
  * masks read back from the turns it returns.  bits (T, total_rows).                                                  */

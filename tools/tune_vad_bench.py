@@ -20,7 +20,21 @@ taken in a child process of their own) and for `(T, 2)` taus (the kernel's state
 every tau and with equal columns.  EXPECTATION, written before the first run: the new kernel adds one pass over a lane's
 rows (two compares per row, no time stamps read) and a fold over at most 255 bytes of LDS to two walks that read the
 time stamps and the prefix sums, so its device time should stay well under twice the plain kernel's at every T — a
-supposition; the tool reports the ratio whichever way it falls."""
+supposition; the tool reports the ratio whichever way it falls.
+
+`--min-duration` measures the four-column path — `(T, 4)` = (tau_active, tau_offset, min_duration_on, min_duration_off),
+tune_vad_score_kernel<TcDurRule> — beside `(T,)` and `(T, 2)` on the same dataset and in the same form as `--hysteresis`
+(whose `plain` and `band` rows of the parent commit, taken in a child process of their own, are the yardstick): per T
+the wall time of `evaluate` and the device time of the scoring kernel with both durations zero and with durations
+drawn from U(0, 1), the range the Optimizer draws from.  EXPECTATION, written before the first run: against the `(T, 2)`
+kernel the new one walks a lane's steps once instead of twice (the time stamps and the cells of a turn are read once),
+keeps the pass of the state maps, stores eleven words per lane instead of four, and ends with ONE lane composing 256
+summaries from LDS — a serial loop of some 256 x 11 LDS reads, a few microseconds during which the other 255 lanes wait —
+where the `(T, 2)` kernel has every lane fold up to 255 ends and one lane add 256 sums.  The two should cost about the
+same: a device-time ratio between 0.8 and 1.3 at 64 and 1 024 trials, where the kernel is a few hundred workgroups or
+more per CU wave, and nearer 1.3 - 1.5 at one trial, where 16 workgroups leave the serial tail exposed.  Large
+min_duration_off merges more turns per span and so touches the prefix sums less: random durations should not cost more
+than zeros.  A supposition; the tool reports the ratios whichever way they fall."""
 import argparse
 import ctypes as C
 import json
@@ -98,6 +112,32 @@ def hysteresis_rows(cache, trials, reps: int, device, rng) -> list:
     return rows
 
 
+def min_duration_rows(cache, trials, reps: int, device, rng) -> list:
+    """Per T: hysteresis_rows' plain and band forms — (T,) and (T, 2), which must not move — and (T, 4) with both
+    durations zero and with durations from U(0, 1), all under the band's thresholds."""
+    rows = []
+    for T in trials:
+        taus = np.concatenate([[0.6], rng.uniform(0, 1, size=T - 1)])
+        band = np.stack([taus, taus - 0.2], axis=1)
+        forms = dict(plain=taus, band=band, zero=np.concatenate([band, np.zeros((T, 2))], axis=1),
+                     drawn=np.concatenate([band, rng.uniform(0, 1, size=(T, 2))], axis=1))
+        row = dict(trials=T)
+        for name, t in forms.items():
+            cache.evaluate(t, backend="gpu")
+            row[f"{name}_evaluate"] = median_ms(lambda: cache.evaluate(t, backend="gpu"), reps)
+            row[f"{name}_kernel"] = events_ms(lambda: cache._gpu(cache._taus(t), False, True, device), device, reps)
+        two, four = cache.evaluate(forms["band"], backend="gpu"), cache.evaluate(forms["zero"], backend="gpu")
+        total = np.maximum(two.per_file[..., :1], 1e-300)
+        row["zero_durations_against_two_columns_over_total"] = float((np.abs(two.per_file - four.per_file) / total).max())
+        row["best_rate_percent"] = {name: float(100.0 * cache.evaluate(forms[name], backend="gpu").rate.min())
+                                    for name in ("band", "drawn")}
+        for name in ("zero", "drawn"):
+            row[f"{name}_kernel_over_band"] = row[f"{name}_kernel"]["median_ms"] / row["band_kernel"]["median_ms"]
+            row[f"{name}_evaluate_over_band"] = row[f"{name}_evaluate"]["median_ms"] / row["band_evaluate"]["median_ms"]
+        rows.append(row)
+    return rows
+
+
 def both_pipelines(args, device) -> dict:
     """--pipeline osd: the two detection caches collected from the same files, measured side by side."""
     from diart_amd.blocks.osd import OverlappedSpeechDetection, OverlappedSpeechDetectionConfig
@@ -129,7 +169,9 @@ def both_pipelines(args, device) -> dict:
         torch.cuda.synchronize(device)
         out[name]["upload_and_rows_ms"] = 1e3 * (time.perf_counter() - t)
     for name, cache in caches.items():
-        if args.hysteresis:
+        if args.min_duration:
+            out[name]["rows"] = min_duration_rows(cache, args.trials, args.reps, device, np.random.default_rng(0))
+        elif args.hysteresis:
             out[name]["rows"] = hysteresis_rows(cache, args.trials, args.reps, device, np.random.default_rng(0))
         else:
             out[name]["rows"] = evaluate_rows(cache, args.trials, args.reps, args.threads, device, np.random.default_rng(0))
@@ -145,6 +187,9 @@ def main():
                          "with the VAD tuner beside it")
     ap.add_argument("--hysteresis", action="store_true",
                     help="(T, 2) taus = (tau_active, tau_offset) beside (T,) taus, for both caches (implies --pipeline osd)")
+    ap.add_argument("--min-duration", action="store_true",
+                    help="(T, 4) taus = (tau_active, tau_offset, min_duration_on, min_duration_off) beside (T,) and (T, 2) "
+                         "taus, for both caches (implies --pipeline osd)")
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=600.0)
     ap.add_argument("--trials", type=int, nargs="+", default=[1, 64, 1024])
@@ -154,17 +199,22 @@ def main():
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--latency", type=float, default=5.0)
     ap.add_argument("--out", type=str, default=None,
-                    help="profiles/r20a_tune_vad.json, profiles/r29a_tune_osd.json with --pipeline osd")
+                    help="profiles/r20a_tune_vad.json, profiles/r29a_tune_osd.json with --pipeline osd, r32a_tune_hysteresis.json with "
+                         "--hysteresis, r34a_tune_min_duration.json with --min-duration")
     args = ap.parse_args()
-    if args.hysteresis:
+    if args.hysteresis and args.min_duration:
+        raise SystemExit("--hysteresis and --min-duration are two runs")
+    if args.hysteresis or args.min_duration:
         args.pipeline = "osd"
-    args.out = args.out or str(ROOT / "profiles" / ("r32a_tune_hysteresis.json" if args.hysteresis else
+    args.out = args.out or str(ROOT / "profiles" / ("r34a_tune_min_duration.json" if args.min_duration else
+                                                     "r32a_tune_hysteresis.json" if args.hysteresis else
                                                      "r29a_tune_osd.json" if args.pipeline == "osd" else "r20a_tune_vad.json"))
     if not torch.cuda.is_available():
         raise SystemExit("tune_vad_bench.py measures on a GPU; there is none")
     device = torch.device("cuda", 0)
     if args.pipeline == "osd":
-        out = dict(tool="tools/tune_vad_bench.py " + ("--hysteresis" if args.hysteresis else "--pipeline osd"), files=args.files, seconds=args.seconds, latency=args.latency,
+        out = dict(tool="tools/tune_vad_bench.py " + ("--min-duration" if args.min_duration else
+                                                      "--hysteresis" if args.hysteresis else "--pipeline osd"), files=args.files, seconds=args.seconds, latency=args.latency,
                    batch_size=args.batch_size, host_threads=args.threads, reps=args.reps, gpu=torch.cuda.get_device_name(0))
         out.update(both_pipelines(args, device))
         line = json.dumps(out)
