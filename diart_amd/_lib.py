@@ -284,6 +284,14 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, vp, vp]),
     "dz_tune_ident_score_core": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                            C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, C.c_int]),
+    "dz_tune_name_sweep": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                     vp, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "dz_tune_name_sweep_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                          vp, vp, vp, vp, vp, vp, C.c_int]),
+    "dz_tune_ident_score_sweep_gpu": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, vp, vp]),
+    "dz_tune_ident_score_sweep_core": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
+                                                 vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, C.c_int]),
     "dz_rows_repeat": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, c_int_p]),
     "dz_gallery_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_gallery_destroy": (C.c_int, [vp]),

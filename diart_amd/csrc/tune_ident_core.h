@@ -11,12 +11,20 @@
 // every set bit g of a cell is looked up in the identities of the step that owns the cell: a reference bit 0..63 of
 // the file, or "other" (an unnamed speaker, or a name no reference label of the file has).  Labels are compared as they
 // are: no mapping, no co-occurrence sweep.
+//
+// Both halves take several (plane, threshold) points per clustering trial: a chain per (trial, point,
+// file) for the names (ti_chain), and for the score the cells once and then every point's components (ti_score_pair
+// over ti_score_point).  One point is the case points = 1 of the same text.
 #pragma once
 #include "tune_core.h"
 
 #pragma clang fp contract(off)
 
 constexpr int TI_OTHER = -1;   // an identity that is no reference label of the file
+// A sweep evaluates one clustering trial at `points` (plane, threshold) points: a plane is one stored
+// match of the cache (one top_n of a normalised gallery), and the points are plane-major.
+constexpr int TI_MAX_POINTS = 256;
+constexpr int TI_MAX_PLANES = 8;
 
 // One step of speaker g's state.  A NaN distance passes neither comparison.
 TC_HD void ti_update(float& best_d, int& best_e, int g, const signed char* assign, const int* index, const float* dist, int K,
@@ -84,14 +92,16 @@ TC_HD void ti_cell_counts(unsigned h, unsigned long long rm, const signed char* 
     n[4] = (nref < nhyp ? nref : nhyp) - both;
 }
 
+// The components of one point of a pair: after tc_score_cells left the hypothesis masks in `scratch`, every cell's
+// factors under the identities `ident` (total_chunks, G).  Lane l takes cells l, l + nl, ...; lane 0 adds the lanes'
+// sums in lane order, so a point's doubles do not depend on how many points share the cells.
 template <typename Lanes>
-TC_HD void ti_score_pair(const TiScoreIn& in, TiScoreShared& sh, unsigned* scratch, double* out /* 5 */, int* err,
-                         Lanes lanes) {
+TC_HD void ti_score_point(const TiScoreIn& in, const signed char* ident, TiScoreShared& sh, const unsigned* scratch,
+                          double* out /* 5 */, int* err, Lanes lanes) {
     const TcScoreIn& ci = in.cells;
     const int nl = lanes.nl, ncell = ci.ncell, G = ci.G;
     const unsigned gmask = G >= 32 ? 0xffffffffu : ((1u << G) - 1u);
-    tc_score_cells(ci, sh, scratch, lanes);
-    // ---- the components over the cells, per lane (lane l takes cells l, l + nl, ...)
+    // ---- the components over the cells, per lane
     lanes([&](int lane) {
         double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
         for (int i = lane; i < ncell; i += nl) {
@@ -105,7 +115,7 @@ TC_HD void ti_score_pair(const TiScoreIn& in, TiScoreShared& sh, unsigned* scrat
             }
             const double dur = ci.cell_dur[i];
             int n[5];
-            ti_cell_counts(h, rm, in.ident + (long)c * G, n);
+            ti_cell_counts(h, rm, ident + (long)c * G, n);
 #pragma unroll
             for (int q = 0; q < 5; ++q) acc[q] += dur * n[q];
         }
@@ -125,4 +135,30 @@ TC_HD void ti_score_pair(const TiScoreIn& in, TiScoreShared& sh, unsigned* scrat
             out[q] = s;
         }
     });
+}
+
+// One (trial, file) pair at `points` points: the cells once (the toggle and prefix-XOR phases depend on the masks
+// alone), then the components of every point in turn.  in.ident is point 0's identities; point j's lie j *
+// ident_stride bytes further and its five sums j * out_stride doubles further.
+template <typename Lanes>
+TC_HD void ti_score_pair(const TiScoreIn& in, int points, long long ident_stride, long long out_stride, TiScoreShared& sh,
+                         unsigned* scratch, double* out, int* err, Lanes lanes) {
+    tc_score_cells(in.cells, sh, scratch, lanes);
+    for (int j = 0; j < points; ++j)
+        ti_score_point(in, in.ident + j * ident_stride, sh, scratch, out + j * out_stride, err, lanes);
+}
+
+// The chain of a naming call: chain = (t * points + j) * n_files + n.  Point j reads plane j / (points / planes) of the
+// stored match (planes divides points: the entry points check it) and threshold delta_id[t * points + j].
+struct TiChain {
+    int t, j, n, plane;
+};
+TC_HD TiChain ti_chain(long long chain, int points, int planes, int n_files) {
+    const long long tj = chain / n_files;
+    TiChain c;
+    c.n = (int)(chain - tj * n_files);
+    c.t = (int)(tj / points);
+    c.j = (int)(tj - (long long)c.t * points);
+    c.plane = c.j / (points / planes);
+    return c;
 }

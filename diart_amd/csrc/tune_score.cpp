@@ -21,6 +21,8 @@
 //                        the text tune_name_kernel compiles (tune_ident_core.h)
 //   dz_tune_ident_score  identification error rate components of every pair: dz_tune_score's cells, the labels compared
 //                        as they are;  dz_tune_ident_score_core: the same from the text of tune_ident_score_kernel
+//   dz_tune_name_sweep_host, dz_tune_ident_score_sweep_core   the two at several (plane, threshold) points per trial
+//                        (DESIGN.md 4.23); the one-point entries are their points = 1 call
 #include "tune_core.h"
 #include "tune_ident_core.h"
 
@@ -642,6 +644,69 @@ extern "C" int dz_tune_vad_replay_tails(const dz_tune_desc* d, const double* tau
 // ---------------------------------------------------------------------------------------------------------
 // Tuning delta_id
 // ---------------------------------------------------------------------------------------------------------
+extern "C" int dz_tune_name_sweep_host(int trials, int points, int planes, int n_files, int total_chunks, int k_local,
+                                       int max_speakers, int voiceprints, const int* file_chunk_off,
+                                       const signed char* assign, const int* status, const int* match_index,
+                                       const float* match_distance, const signed char* vp_ref, const double* delta_id,
+                                       signed char* ident, int* hold, int num_threads) {
+    if (!file_chunk_off || !assign || !status || !match_index || !match_distance || !vp_ref || !delta_id || !ident) {
+        dz_set_error("dz_tune_name_sweep_host: NULL argument");
+        return 2;
+    }
+    if (trials < 1 || n_files < 1 || total_chunks < n_files || k_local < 1 || k_local > TC_KMAX || max_speakers < 1 ||
+        max_speakers > TC_GMAX || voiceprints < 1) {
+        dz_set_error("dz_tune_name_sweep_host: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at "
+                     "most %d / %d), %d voiceprints)",
+                     trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints);
+        return 2;
+    }
+    if (points < 1 || points > TI_MAX_POINTS || planes < 1 || planes > TI_MAX_PLANES || points % planes != 0) {
+        dz_set_error("dz_tune_name_sweep_host: %d points (1 .. %d) in %d planes (1 .. %d, a divisor of the points)", points,
+                     TI_MAX_POINTS, planes, TI_MAX_PLANES);
+        return 2;
+    }
+    const int N = n_files, K = k_local, G = max_speakers, V = voiceprints;
+    const long long chains = (long long)trials * points * N;
+    if (chains >= (1ll << 31)) {
+        dz_set_error("dz_tune_name_sweep_host: %lld chains in one call; evaluate fewer trials per batch", chains);
+        return 2;
+    }
+    each_item((int)chains, num_threads, [&](int, int chain) {
+        const TiChain ch = ti_chain(chain, points, planes, N);
+        const int n = ch.n;
+        const int c0 = file_chunk_off[n], c1 = file_chunk_off[n + 1];
+        const int st = status[(size_t)ch.t * N + n];
+        const int stop = st < 0 ? c1 : std::min(c0 + st, c1);
+        const size_t tj = (size_t)ch.t * points + ch.j;
+        const double delta = delta_id[tj];
+        const signed char* A = assign + (size_t)ch.t * total_chunks * K;
+        const int* MI = match_index + (size_t)ch.plane * total_chunks * K;
+        const float* MD = match_distance + (size_t)ch.plane * total_chunks * K;
+        signed char* I = ident + tj * total_chunks * G;
+        int* H = hold ? hold + tj * total_chunks * G : nullptr;
+        float best_d[TC_GMAX];
+        int best_e[TC_GMAX];
+        for (int g = 0; g < G; ++g) {
+            best_d[g] = INFINITY;
+            best_e[g] = -1;
+        }
+        for (int c = c0; c < c1; ++c) {
+            if (c < stop)
+                for (int g = 0; g < G; ++g)
+                    ti_update(best_d[g], best_e[g], g, A + (size_t)c * K, MI + (size_t)c * K, MD + (size_t)c * K, K, delta);
+            for (int g = 0; g < G; ++g) {
+                const int h = ti_hold(best_d[g], best_e[g], g, G, [&](int g2, float* d2, int* e2) {
+                    *d2 = best_d[g2];
+                    *e2 = best_e[g2];
+                });
+                I[(size_t)c * G + g] = ti_identity(h, vp_ref + (size_t)n * V, V);
+                if (H) H[(size_t)c * G + g] = h;
+            }
+        }
+    });
+    return 0;
+}
+
 extern "C" int dz_tune_name_host(int trials, int n_files, int total_chunks, int k_local, int max_speakers, int voiceprints,
                                  const int* file_chunk_off, const signed char* assign, const int* status,
                                  const int* match_index, const float* match_distance, const signed char* vp_ref,
@@ -657,36 +722,8 @@ extern "C" int dz_tune_name_host(int trials, int n_files, int total_chunks, int 
                      trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints);
         return 2;
     }
-    const int N = n_files, K = k_local, G = max_speakers, V = voiceprints, pairs = trials * N;
-    each_item(pairs, num_threads, [&](int, int pair) {
-        const int t = pair / N, n = pair - t * N;
-        const int c0 = file_chunk_off[n], c1 = file_chunk_off[n + 1];
-        const int stop = status[pair] < 0 ? c1 : std::min(c0 + status[pair], c1);
-        const signed char* A = assign + (size_t)t * total_chunks * K;
-        signed char* I = ident + (size_t)t * total_chunks * G;
-        int* H = hold ? hold + (size_t)t * total_chunks * G : nullptr;
-        float best_d[TC_GMAX];
-        int best_e[TC_GMAX];
-        for (int g = 0; g < G; ++g) {
-            best_d[g] = INFINITY;
-            best_e[g] = -1;
-        }
-        for (int c = c0; c < c1; ++c) {
-            if (c < stop)
-                for (int g = 0; g < G; ++g)
-                    ti_update(best_d[g], best_e[g], g, A + (size_t)c * K, match_index + (size_t)c * K,
-                              match_distance + (size_t)c * K, K, delta_id[t]);
-            for (int g = 0; g < G; ++g) {
-                const int h = ti_hold(best_d[g], best_e[g], g, G, [&](int g2, float* d2, int* e2) {
-                    *d2 = best_d[g2];
-                    *e2 = best_e[g2];
-                });
-                I[(size_t)c * G + g] = ti_identity(h, vp_ref + (size_t)n * V, V);
-                if (H) H[(size_t)c * G + g] = h;
-            }
-        }
-    });
-    return 0;
+    return dz_tune_name_sweep_host(trials, 1, 1, n_files, total_chunks, k_local, max_speakers, voiceprints, file_chunk_off,
+                                   assign, status, match_index, match_distance, vp_ref, delta_id, ident, hold, num_threads);
 }
 
 extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
@@ -740,6 +777,57 @@ extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits
     return 0;
 }
 
+// Both entries below: `who` is the entry the caller used, which every refusal and failure names.
+static int ident_score_core(const char* who, int trials, int points, int n_files, const unsigned* bits,
+                            const signed char* ident, int total_rows, int total_chunks, const int* file_chunk_off,
+                            const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
+                            const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step, int max_cells,
+                            int max_speakers, double collar, int lanes, int score_blocks, double* out, int num_threads) {
+    if (!bits || !ident || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off || !cell_dur || !cell_ref ||
+        !cell_step || !out) {
+        dz_set_error("%s: NULL argument", who);
+        return 2;
+    }
+    if (trials < 1 || n_files < 1 || total_rows < 1 || total_chunks < n_files || max_speakers < 1 || max_speakers > TC_GMAX ||
+        max_cells < 0 || lanes < 1 || lanes > TC_SCORE_LANES || score_blocks < 1) {
+        dz_set_error("%s: bad arguments (%d trials, at most %d speakers, %d lanes)", who, trials, TC_GMAX, TC_SCORE_LANES);
+        return 2;
+    }
+    if (points < 1 || points > TI_MAX_POINTS) {
+        dz_set_error("%s: %d points (1 .. %d)", who, points, TI_MAX_POINTS);
+        return 2;
+    }
+    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
+                              cell_dur, cell_ref, max_cells, max_speakers, collar};
+    const long long plane = (long long)total_chunks * max_speakers;   // one point's identities of one trial
+    const int rc = score_core<TiScoreShared>(
+        call, score_blocks, num_threads,
+        [&](const TcScoreIn& cells, TiScoreShared& sh, unsigned* slice, long long pair, int t, int cell0, int* err) {
+            const int n = (int)(pair - (long long)t * n_files);
+            const TiScoreIn in = {cells, ident + (size_t)t * points * plane, cell_step + cell0};
+            ti_score_pair(in, points, plane, (long long)n_files * 5, sh, slice, out + ((size_t)t * points * n_files + n) * 5,
+                          err, LanesInTurn{lanes});
+        });
+    if (rc) {
+        dz_set_error(rc == TC_SCORE_ERR_ARGS ? "%s: a file has more scoring cells than a scratch slice holds"
+                                             : "%s: a speech turn or a step does not lie on the file's scoring cells", who);
+        return rc;
+    }
+    return 0;
+}
+
+extern "C" int dz_tune_ident_score_sweep_core(int trials, int points, int n_files, const unsigned* bits,
+                                              const signed char* ident, int total_rows, int total_chunks,
+                                              const int* file_chunk_off, const int* row_off, const double* mids,
+                                              const int* mid_cell, const int* file_cell_off, const double* cell_dur,
+                                              const unsigned long long* cell_ref, const int* cell_step, int max_cells,
+                                              int max_speakers, double collar, int lanes, int score_blocks, double* out,
+                                              int num_threads) {
+    return ident_score_core("dz_tune_ident_score_sweep_core", trials, points, n_files, bits, ident, total_rows, total_chunks,
+                            file_chunk_off, row_off, mids, mid_cell, file_cell_off, cell_dur, cell_ref, cell_step, max_cells,
+                            max_speakers, collar, lanes, score_blocks, out, num_threads);
+}
+
 extern "C" int dz_tune_ident_score_core(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
                                         int total_chunks, const int* file_chunk_off, const int* row_off, const double* mids,
                                         const int* mid_cell, const int* file_cell_off, const double* cell_dur,
@@ -756,18 +844,7 @@ extern "C" int dz_tune_ident_score_core(int trials, int n_files, const unsigned*
         dz_set_error("dz_tune_ident_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
         return 2;
     }
-    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
-                              cell_dur, cell_ref, max_cells, max_speakers, collar};
-    const int rc = score_core<TiScoreShared>(
-        call, score_blocks, num_threads,
-        [&](const TcScoreIn& cells, TiScoreShared& sh, unsigned* slice, long long pair, int t, int cell0, int* err) {
-            const TiScoreIn in = {cells, ident + (size_t)t * total_chunks * max_speakers, cell_step + cell0};
-            ti_score_pair(in, sh, slice, out + (size_t)pair * 5, err, LanesInTurn{lanes});
-        });
-    if (rc) {
-        dz_set_error(rc == TC_SCORE_ERR_ARGS ? "dz_tune_ident_score_core: a file has more scoring cells than a scratch slice holds"
-                                             : "dz_tune_ident_score: a speech turn or a step does not lie on the file's scoring cells");
-        return rc;
-    }
-    return 0;
+    return ident_score_core("dz_tune_ident_score_core", trials, 1, n_files, bits, ident, total_rows, total_chunks,
+                            file_chunk_off, row_off, mids, mid_cell, file_cell_off, cell_dur, cell_ref, cell_step, max_cells,
+                            max_speakers, collar, lanes, score_blocks, out, num_threads);
 }

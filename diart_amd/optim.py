@@ -39,7 +39,7 @@ import ctypes as C
 import json
 import re
 from pathlib import Path
-from typing import Dict, List, NamedTuple, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -343,18 +343,33 @@ class TuneCache(_ReplayCache):
                 raise ValueError(f"{path} holds a {str(z['kind'])}, not a TuneCache (SpeakerDiarization)")
             return cls._stored(z)
 
-    def with_gallery(self, gallery, device=None) -> "IdentTuneCache":
+    def with_gallery(self, gallery, device=None, normalised: bool = False, top_n=None) -> "IdentTuneCache":
         """This cache with the match of every cached embedding against ``gallery`` (a ``SpeakerGallery``): an
         ``IdentTuneCache``, which tunes ``delta_id`` beside the three.  The files, the plan and the device copies are
         shared, not copied.  The match is ``gallery.match`` on the GPU when there is one (``device``: which), else
-        ``functional.gallery_match``'s float64 statement rounded to float32.  A gallery with a cohort is refused: the
-        live engines match it by the normalised distance, while ``DeltaId``'s range, the replays and the stored
-        ``match_distance`` are all for raw distances."""
-        if getattr(gallery, "cohort", None) is not None:
-            raise ValueError("TuneCache.with_gallery: the gallery has a cohort, so the live engines match it by the "
-                             "normalised distance, and delta_id is tuned on raw distances only; tune gallery."
-                             "with_cohort(None), or set the normalised threshold by hand")
-        return IdentTuneCache(self, gallery, device=device)
+        ``functional.gallery_match``'s float64 statement rounded to float32.  A gallery with a cohort is refused
+        without ``normalised=True``: the live engines match it by the normalised distance, while ``DeltaId``'s range
+        and a raw cache's ``match_distance`` are for raw distances.
+
+        ``normalised=True`` (a gallery with a cohort): the stored match is the normalised one, a signed ``dn``, in one
+        PLANE per value of ``top_n`` (None: the gallery's own; else 1 to 8 distinct integers in 1 .. the cohort's rows).
+        Plane p is ``gallery.with_cohort(gallery.cohort, top_ns[p]).match_normalised(emb)`` on the GPU, the kernels
+        the live engines run (one device copy at a time), or ``functional.gallery_match_normalised``'s float64 statement
+        rounded to float32 without one."""
+        cohort = getattr(gallery, "cohort", None)
+        if not normalised:
+            if top_n is not None:
+                raise ValueError("TuneCache.with_gallery: top_n= chooses the planes of the normalised match; it needs "
+                                 "normalised=True")
+            if cohort is not None:
+                raise ValueError("TuneCache.with_gallery: the gallery has a cohort, so the live engines match it by the "
+                                 "normalised distance, and delta_id is tuned on raw distances only; tune gallery."
+                                 "with_cohort(None), or tune the normalised threshold with normalised=True")
+            return IdentTuneCache(self, gallery, device=device)
+        if cohort is None:
+            raise ValueError("TuneCache.with_gallery(normalised=True): the gallery has no cohort to normalise against "
+                             "(SpeakerGallery(..., cohort=...) or with_cohort)")
+        return IdentTuneCache(self, gallery, device=device, top_ns=_check_top_ns(top_n, gallery, "TuneCache.with_gallery"))
 
     # ------------------------------------------------------------------------------------------ trial-independent parts
     def _reference_bits(self, f: dict) -> Dict[object, int]:
@@ -571,6 +586,33 @@ class TuneCache(_ReplayCache):
 
 
 _RESERVED_LABEL = re.compile(r"speaker\d+")          # gallery.py: what unnamed speakers are called
+MAX_PLANES, MAX_POINTS = 8, 256                      # tune_ident_core.h: TI_MAX_PLANES, TI_MAX_POINTS
+
+
+def _check_top_ns(top_n, gallery, who: str) -> Tuple[int, ...]:
+    """The planes of a normalised cache: ``(gallery.top_n,)`` for None, else 1 to 8 distinct integers under
+    ``gallery.check_cohort``'s rule."""
+    from .gallery import check_cohort
+    if top_n is None:
+        return (int(gallery.top_n),)
+    values = list(np.atleast_1d(np.asarray(top_n, dtype=object)).tolist())
+    if not 1 <= len(values) <= MAX_PLANES:
+        raise ValueError(f"{who}: top_n= of {len(values)} values (1 .. {MAX_PLANES} planes)")
+    out = tuple(check_cohort(gallery.cohort, v, gallery.dimension, who)[1] for v in values)
+    if len(set(out)) != len(out):
+        raise ValueError(f"{who}: top_n={list(out)} repeats a value; every plane is matched and stored once")
+    return out
+
+
+class SweepResult(NamedTuple):
+    """``IdentTuneCache.evaluate_sweep``: entry ``[t, p, q]`` is ``evaluate``'s for clustering trial t with threshold
+    ``delta_id[q]`` on the plane of ``top_n[p]``."""
+    rate: np.ndarray          # (T, P, Q), NaN where a chain of the trial stopped
+    components: np.ndarray    # (T, P, Q, 5)
+    per_file: np.ndarray      # (T, P, Q, N, 5)
+    status: np.ndarray        # (T, N)
+    top_n: np.ndarray         # (P,) int64; empty for a raw cache (its one plane has no top_n)
+    delta_id: np.ndarray      # (Q,)
 
 
 class IdentTuneCache(TuneCache):
@@ -587,7 +629,14 @@ class IdentTuneCache(TuneCache):
     also owns what lies before its ``b_c``, the last what lies behind).  It is scored by
     ``metrics.IdentificationErrorRate``: labels compared as they are.  This needs the steps' grids sorted by time
     (``sorted_steps``); a cache without is refused on every backend.  A reference label of the form ``speaker<digits>``
-    is refused, as the gallery refuses such names."""
+    is refused, as the gallery refuses such names.
+
+    A NORMALISED cache (``TuneCache.with_gallery(gallery, normalised=True, top_n=...)``, a gallery with a cohort) stores
+    the cohort-normalised match instead, a signed ``dn``, once per ``top_n``: ``plane_index`` / ``plane_distance
+    (P, chunks, K)``, with ``match_index`` / ``match_distance`` plane 0, and ``normalised``, ``top_ns``, ``cohort``.  Its
+    thresholds are any finite value and the rule is ``SpeakerNames(..., signed=True)``.  A raw cache has one plane and
+    ``top_ns == ()``.  ``evaluate_sweep`` scores every clustering trial at many (plane, threshold) points for little
+    more than one replay."""
 
     KIND = "IdentTuneCache"
     NAME_BLOCKS = 8192          # resident naming chains: 256 CUs x 32 one-wave workgroups
@@ -595,7 +644,7 @@ class IdentTuneCache(TuneCache):
     _IDENT_ERRORS = {4: "a speech turn or a step does not lie on the file's scoring cells",
                      2: "a file has more scoring cells than a scratch slice holds"}
 
-    def __init__(self, cache: TuneCache, gallery, device=None, match=None):
+    def __init__(self, cache: TuneCache, gallery, device=None, match=None, top_ns: Tuple[int, ...] = ()):
         if not isinstance(cache, TuneCache):
             raise ValueError(f"IdentTuneCache takes a TuneCache, got a {type(cache).__name__}")
         if gallery.dimension != cache.D:
@@ -609,8 +658,15 @@ class IdentTuneCache(TuneCache):
         self.__dict__.update(cache.__dict__)                 # the files, the plan, the device copies: shared
         self.names = tuple(gallery.names)
         self.voiceprints = gallery.voiceprints
+        self.top_ns = tuple(int(n) for n in top_ns)
+        self.normalised = bool(self.top_ns)
+        self.cohort = gallery.cohort if self.normalised else None
+        if self.normalised and self.cohort is None:
+            raise ValueError("IdentTuneCache: a normalised match (top_ns=) needs a gallery with a cohort")
         total = int(self.chunk_off[-1])
-        if match is None:
+        if match is not None:
+            index, distance = match
+        elif not self.normalised:
             if torch.cuda.is_available():
                 if device is not None:
                     gallery._resolve(device)
@@ -619,11 +675,25 @@ class IdentTuneCache(TuneCache):
                 from .functional import gallery_match
                 index, distance, _ = gallery_match(self.emb, gallery.voiceprints)
         else:
-            index, distance = match
-        self.match_index = np.ascontiguousarray(index, dtype=np.int32).reshape(total, self.K)
-        self.match_distance = np.ascontiguousarray(distance, dtype=np.float32).reshape(total, self.K)
+            index, distance = [], []
+            for n in self.top_ns:                            # one device copy of the gallery at a time
+                if torch.cuda.is_available():
+                    g = gallery.with_cohort(self.cohort, n)
+                    if device is not None:
+                        g._resolve(device)
+                    i, d, _ = g.match_normalised(self.emb)
+                    del g
+                else:
+                    from .functional import gallery_match_normalised
+                    i, d, _ = gallery_match_normalised(self.emb, gallery.voiceprints, self.cohort, n)
+                index.append(i)
+                distance.append(d)
+        P = max(1, len(self.top_ns))
+        self.plane_index = np.ascontiguousarray(index, dtype=np.int32).reshape(P, total, self.K)
+        self.plane_distance = np.ascontiguousarray(distance, dtype=np.float32).reshape(P, total, self.K)
+        self.match_index, self.match_distance = self.plane_index[0], self.plane_distance[0]     # (views: plane 0)
         V = len(self.names)
-        if ((self.match_index < -1) | (self.match_index >= V)).any():
+        if ((self.plane_index < -1) | (self.plane_index >= V)).any():
             raise ValueError(f"IdentTuneCache: a stored match names a voiceprint outside 0 .. {V - 1}")
         self.vp_ref = np.full((self.N, V), -1, dtype=np.int8)
         for n, labels in enumerate(self.ref_labels):
@@ -649,16 +719,21 @@ class IdentTuneCache(TuneCache):
 
     @classmethod
     def collect(cls, pipeline_class, base_config, speech_path, reference_path, batch_size: int = 32, gallery=None,
-                device=None) -> "IdentTuneCache":
+                device=None, normalised: bool = False, top_n=None) -> "IdentTuneCache":
         if gallery is None:
             raise ValueError("IdentTuneCache.collect needs gallery= (a SpeakerGallery)")
         return TuneCache.collect(pipeline_class, base_config, speech_path, reference_path, batch_size).with_gallery(
-            gallery, device)
+            gallery, device, normalised=normalised, top_n=top_n)
 
     def save(self, path) -> None:
+        """A raw cache writes the keys it always wrote; a normalised one adds its cohort, ``top_ns`` and planes (and
+        keeps ``match_index`` / ``match_distance``, plane 0)."""
         out = self._payload()
         out.update(kind=np.array(self.KIND), gallery_names=np.asarray(self.names, dtype=np.str_),
                    gallery_voiceprints=self.voiceprints, match_index=self.match_index, match_distance=self.match_distance)
+        if self.normalised:
+            out.update(gallery_cohort=self.cohort, top_ns=np.asarray(self.top_ns, dtype=np.int64),
+                       plane_index=self.plane_index, plane_distance=self.plane_distance)
         with open(path, "wb") as fh:
             np.savez(fh, **out)
 
@@ -670,25 +745,65 @@ class IdentTuneCache(TuneCache):
             if kind != cls.KIND:
                 holds = "TuneCache (SpeakerDiarization)" if kind is None else kind
                 raise ValueError(f"{path} holds a {holds}, not an IdentTuneCache (SpeakerDiarization with a gallery)")
-            gallery = SpeakerGallery([str(n) for n in z["gallery_names"]], z["gallery_voiceprints"])
+            names = [str(n) for n in z["gallery_names"]]
+            if "top_ns" in z.files:
+                top_ns = tuple(int(n) for n in z["top_ns"])
+                gallery = SpeakerGallery(names, z["gallery_voiceprints"], cohort=z["gallery_cohort"], top_n=top_ns[0])
+                return cls(cls._stored(z), gallery, match=(z["plane_index"], z["plane_distance"]), top_ns=top_ns)
+            gallery = SpeakerGallery(names, z["gallery_voiceprints"])
             return cls(cls._stored(z), gallery, match=(z["match_index"], z["match_distance"]))
 
     # ------------------------------------------------------------------------------------------ replay
     @property
     def bytes_per_trial(self) -> int:
         """``TuneCache.bytes_per_trial`` plus a trial's names: one byte per (chunk, global speaker)."""
-        return TuneCache.bytes_per_trial.fget(self) + int(self.chunk_off[-1]) * self.G
+        return self.sweep_bytes_per_trial(1)
 
-    @staticmethod
-    def _hparams4(hparams) -> np.ndarray:
+    def sweep_bytes_per_trial(self, points: int) -> int:
+        """``TuneCache.bytes_per_trial`` plus one plane of identities (``chunks * G`` bytes) per point of a sweep."""
+        return TuneCache.bytes_per_trial.fget(self) + int(points) * int(self.chunk_off[-1]) * self.G
+
+    def _check_delta(self, delta: np.ndarray, what: str) -> None:
+        """Any finite threshold on a normalised cache (``dn`` is signed); a finite distance >= 0 on a raw one."""
+        bad = np.flatnonzero(~np.isfinite(delta) | ((delta < 0) & (not self.normalised)))
+        if bad.size:
+            raise ValueError(f"{what} {int(bad[0])}: delta_id={float(delta[bad[0]])!r} "
+                             f"({'a finite threshold' if self.normalised else 'a finite distance >= 0'})")
+
+    def _hparams4(self, hparams) -> np.ndarray:
         hp = np.ascontiguousarray(np.atleast_2d(np.asarray(hparams, dtype=np.float64)))
         if hp.ndim != 2 or hp.shape[1] != 4 or hp.shape[0] < 1:
             raise ValueError(f"hparams (T, 4) = (tau_active, rho_update, delta_new, delta_id) per trial expected, got "
                              f"{hp.shape}")
-        bad = np.flatnonzero(~np.isfinite(hp[:, 3]) | (hp[:, 3] < 0))
-        if bad.size:
-            raise ValueError(f"trial {int(bad[0])}: delta_id={hp[bad[0], 3]!r} (a finite distance >= 0)")
+        self._check_delta(hp[:, 3], "trial")
         return hp
+
+    def _planes(self, top_n, who: str, several: bool = False) -> List[int]:
+        """The planes a call names: ``top_n=None`` is plane 0 (``several``: every plane); a value (``several``: or a
+        sequence of distinct values) must be among ``top_ns``."""
+        if top_n is None:
+            return list(range(self.plane_index.shape[0])) if several else [0]
+        values = np.atleast_1d(np.asarray(top_n, dtype=object)).tolist()
+        if not self.normalised:
+            raise ValueError(f"{who}: top_n={top_n!r} on a raw cache, which has one plane and no top_n (top_n=None)")
+        if not several and len(values) != 1:
+            raise ValueError(f"{who}: top_n={top_n!r}: one plane per call (one of {list(self.top_ns)})")
+        for v in values:
+            if isinstance(v, bool) or v not in self.top_ns:
+                raise ValueError(f"{who}: top_n={v!r} is no plane of this cache (top_ns = {list(self.top_ns)})")
+        if not 1 <= len(values) <= MAX_PLANES or len(set(values)) != len(values):
+            raise ValueError(f"{who}: top_n={top_n!r}: 1 .. {MAX_PLANES} distinct planes")
+        return [self.top_ns.index(v) for v in values]
+
+    def delta_range(self) -> Tuple[float, float]:
+        """The lowest and the highest finite stored distance over all planes of a normalised cache: a threshold
+        outside changes no name.  A raw cache answers ``DeltaId``'s range."""
+        if not self.normalised:
+            return float(base.DeltaId.low), float(base.DeltaId.high)
+        d = self.plane_distance[np.isfinite(self.plane_distance)]
+        if d.size == 0:
+            raise ValueError("IdentTuneCache.delta_range: no stored distance is finite")
+        return float(d.min()), float(d.max())
 
     def _check_steps(self) -> None:
         if not self.sorted_steps:
@@ -699,80 +814,122 @@ class IdentTuneCache(TuneCache):
         key = str(device)
         if key not in self._ident_dev:
             self._ident_dev[key] = {name: torch.from_numpy(getattr(self, name)).to(device)
-                                    for name in ("match_index", "match_distance", "vp_ref", "cell_step")}
+                                    for name in ("plane_index", "plane_distance", "vp_ref", "cell_step")}
         return self._ident_dev[key]
 
-    def _names_gpu(self, assign: torch.Tensor, status: torch.Tensor, delta_id: np.ndarray, want_hold: bool = False):
-        """``(ident (T, chunks, G) int8, hold (T, chunks, G) int32 or None)`` on the device: tune_name_kernel, enqueued."""
+    @staticmethod
+    def _take_planes(index, distance, planes: List[int]):
+        """``(planes, chunks, K)`` contiguous: the whole store, one plane of it in place, or a gathered copy."""
+        if planes == list(range(index.shape[0])):
+            return index, distance
+        if len(planes) == 1:
+            return index[planes[0]:planes[0] + 1], distance[planes[0]:planes[0] + 1]
+        if isinstance(index, torch.Tensor):
+            sel = torch.as_tensor(planes, device=index.device)
+            return index.index_select(0, sel).contiguous(), distance.index_select(0, sel).contiguous()
+        return np.ascontiguousarray(index[planes]), np.ascontiguousarray(distance[planes])
+
+    def _names_gpu(self, assign: torch.Tensor, status: torch.Tensor, delta_id: np.ndarray, want_hold: bool = False,
+                   planes: Sequence[int] = (0,)):
+        """``(ident, hold or None)`` on the device: tune_name_kernel, enqueued.  ``delta_id (T,)``: one point on
+        ``planes[0]`` -> ``(T, chunks, G)`` int8 / int32.  ``delta_id (T, J)``: the sweep, J points plane-major over
+        ``planes`` -> ``(T, J, chunks, G)``."""
         device = assign.device
         t, i = self._device(device)[0], self._ident_device(device)
         T, total = assign.shape[0], int(self.chunk_off[-1])
-        d_delta = torch.from_numpy(np.ascontiguousarray(delta_id)).to(device)
-        ident = torch.empty((T, total, self.G), dtype=torch.int8, device=device)
-        hold = torch.empty((T, total, self.G), dtype=torch.int32, device=device) if want_hold else None
-        _lib.check(_lib.load().dz_tune_name(_lib.context(device.index), T, self.N, total, self.K, self.G, len(self.names),
-                                            t["chunk_off"].data_ptr(), assign.data_ptr(), status.data_ptr(),
-                                            i["match_index"].data_ptr(), i["match_distance"].data_ptr(),
-                                            i["vp_ref"].data_ptr(), d_delta.data_ptr(), ident.data_ptr(),
-                                            None if hold is None else hold.data_ptr(), self.NAME_BLOCKS,
-                                            torch.cuda.current_stream(device).cuda_stream), "dz_tune_name")
+        delta_id = np.ascontiguousarray(delta_id, dtype=np.float64)
+        d_delta = torch.from_numpy(delta_id).to(device)
+        shape = (T,) + delta_id.shape[1:] + (total, self.G)
+        ident = torch.empty(shape, dtype=torch.int8, device=device)
+        hold = torch.empty(shape, dtype=torch.int32, device=device) if want_hold else None
+        index, distance = self._take_planes(i["plane_index"], i["plane_distance"], list(planes))
+        tail = (t["chunk_off"].data_ptr(), assign.data_ptr(), status.data_ptr(), index.data_ptr(), distance.data_ptr(),
+                i["vp_ref"].data_ptr(), d_delta.data_ptr(), ident.data_ptr(), None if hold is None else hold.data_ptr(),
+                self.NAME_BLOCKS, torch.cuda.current_stream(device).cuda_stream)
+        if delta_id.ndim == 1:
+            _lib.check(_lib.load().dz_tune_name(_lib.context(device.index), T, self.N, total, self.K, self.G, len(self.names),
+                                                *tail), "dz_tune_name")
+        else:
+            _lib.check(_lib.load().dz_tune_name_sweep(_lib.context(device.index), T, delta_id.shape[1], len(planes), self.N,
+                                                      total, self.K, self.G, len(self.names), *tail), "dz_tune_name_sweep")
         return ident, hold
 
-    def _names_host(self, assign: np.ndarray, status: np.ndarray, delta_id: np.ndarray, want_hold: bool, num_threads: int):
+    def _names_host(self, assign: np.ndarray, status: np.ndarray, delta_id: np.ndarray, want_hold: bool, num_threads: int,
+                    planes: Sequence[int] = (0,)):
+        """``_names_gpu`` on host threads: ``dz_tune_name_host`` for ``delta_id (T,)``, ``dz_tune_name_sweep_host`` for
+        ``delta_id (T, J)``."""
         T, total = assign.shape[0], int(self.chunk_off[-1])
-        delta_id = np.ascontiguousarray(delta_id)
-        ident = np.empty((T, total, self.G), dtype=np.int8)
-        hold = np.empty((T, total, self.G), dtype=np.int32) if want_hold else None
-        _lib.check(_lib.load().dz_tune_name_host(T, self.N, total, self.K, self.G, len(self.names), self.chunk_off.ctypes.data,
-                                                 assign.ctypes.data, status.ctypes.data, self.match_index.ctypes.data,
-                                                 self.match_distance.ctypes.data, self.vp_ref.ctypes.data,
-                                                 delta_id.ctypes.data, ident.ctypes.data,
-                                                 None if hold is None else hold.ctypes.data, int(num_threads)),
-                   "dz_tune_name_host")
+        delta_id = np.ascontiguousarray(delta_id, dtype=np.float64)
+        shape = (T,) + delta_id.shape[1:] + (total, self.G)
+        ident = np.empty(shape, dtype=np.int8)
+        hold = np.empty(shape, dtype=np.int32) if want_hold else None
+        index, distance = self._take_planes(self.plane_index, self.plane_distance, list(planes))
+        tail = (self.chunk_off.ctypes.data, assign.ctypes.data, status.ctypes.data, index.ctypes.data, distance.ctypes.data,
+                self.vp_ref.ctypes.data, delta_id.ctypes.data, ident.ctypes.data,
+                None if hold is None else hold.ctypes.data, int(num_threads))
+        if delta_id.ndim == 1:
+            _lib.check(_lib.load().dz_tune_name_host(T, self.N, total, self.K, self.G, len(self.names), *tail),
+                       "dz_tune_name_host")
+        else:
+            _lib.check(_lib.load().dz_tune_name_sweep_host(T, delta_id.shape[1], len(planes), self.N, total, self.K, self.G,
+                                                           len(self.names), *tail), "dz_tune_name_sweep_host")
         return ident, hold
 
-    def replay_names(self, hparams, backend: Optional[str] = None, num_threads: int = 8):
+    def replay_names(self, hparams, backend: Optional[str] = None, num_threads: int = 8, top_n=None):
         """``(assign, status, bits, hold (T, chunks, G) int32)``: ``TuneCache.replay`` of the first three columns of
         ``hparams (T, 4)``, and the voiceprint whose name every global speaker carries in every step under the
-        trial's ``delta_id`` (-1: none).  ``backend``: "gpu" | "host" | "core"; the naming rule has one text, which
-        "host" and "core" both run on host threads."""
+        trial's ``delta_id`` (-1: none) on the plane of ``top_n`` (None: plane 0).  ``backend``: "gpu" | "host" |
+        "core"; the naming rule has one text, which "host" and "core" both run on host threads."""
         hp = self._hparams4(hparams)
+        planes = self._planes(top_n, "IdentTuneCache.replay_names")
         backend = backend or self.default_backend()
         if backend == "gpu":
             a, s, b = self._replay_gpu(np.ascontiguousarray(hp[:, :3]))
-            _, hold = self._names_gpu(a, s, hp[:, 3], want_hold=True)
+            _, hold = self._names_gpu(a, s, hp[:, 3], want_hold=True, planes=planes)
             torch.cuda.synchronize(a.device)
             return a.cpu().numpy(), s.cpu().numpy(), b.cpu().numpy().view(np.uint32), hold.cpu().numpy()
         a, s, b = TuneCache.replay(self, hp[:, :3], backend, num_threads)
-        return a, s, b, self._names_host(a, s, hp[:, 3], True, num_threads)[1]
+        return a, s, b, self._names_host(a, s, hp[:, 3], True, num_threads, planes)[1]
 
     def _ident_score_gpu(self, bits: torch.Tensor, ident: torch.Tensor):
+        """``(out, err)`` on the device: tune_ident_score_kernel, enqueued.  ``ident (T, chunks, G)`` -> ``out
+        (T, N, 5)``; ``ident (T, J, chunks, G)``, the sweep -> ``out (T, J, N, 5)``."""
         device = bits.device
         t, i = self._device(device)[0], self._ident_device(device)
         T = bits.shape[0]
         blocks = max(1, min(T * self.N, self.IDENT_BLOCKS))
-        out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device)
+        out = torch.empty(tuple(ident.shape[:-2]) + (self.N, 5), dtype=torch.float64, device=device)
         scratch = torch.empty((blocks, self.max_cells + 1), dtype=torch.int32, device=device)
         err = torch.empty(1, dtype=torch.int32, device=device)
-        _lib.check(_lib.load().dz_tune_ident_score_gpu(
-            _lib.context(device.index), T, self.N, bits.data_ptr(), ident.data_ptr(), self.total_rows, int(self.chunk_off[-1]),
-            t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
-            t["file_cell_off"].data_ptr(), t["cell_dur"].data_ptr(), t["cell_ref"].data_ptr(), i["cell_step"].data_ptr(),
-            self.max_cells, self.G, PATCH_COLLAR, out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(),
-            torch.cuda.current_stream(device).cuda_stream), "dz_tune_ident_score_gpu")
+        tail = (bits.data_ptr(), ident.data_ptr(), self.total_rows, int(self.chunk_off[-1]),
+                t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
+                t["file_cell_off"].data_ptr(), t["cell_dur"].data_ptr(), t["cell_ref"].data_ptr(), i["cell_step"].data_ptr(),
+                self.max_cells, self.G, PATCH_COLLAR, out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(),
+                torch.cuda.current_stream(device).cuda_stream)
+        if ident.dim() == 3:
+            _lib.check(_lib.load().dz_tune_ident_score_gpu(_lib.context(device.index), T, self.N, *tail),
+                       "dz_tune_ident_score_gpu")
+        else:
+            _lib.check(_lib.load().dz_tune_ident_score_sweep_gpu(_lib.context(device.index), T, ident.shape[1], self.N, *tail),
+                       "dz_tune_ident_score_sweep_gpu")
         return out, err
 
     def _ident_score_host(self, bits: np.ndarray, ident: np.ndarray, core: bool, num_threads: int) -> np.ndarray:
+        """``_ident_score_gpu`` on host threads.  ``core``: the kernel's text (``ident`` of one point or of a sweep);
+        else ``dz_tune_ident_score``, the sequential text, one point."""
         bits = np.ascontiguousarray(bits, dtype=np.uint32)
         T, total = bits.shape[0], int(self.chunk_off[-1])
-        out = np.zeros((T, self.N, 5), dtype=np.float64)
+        out = np.zeros(ident.shape[:-2] + (self.N, 5), dtype=np.float64)
         lib, p = _lib.load(), lambda name: getattr(self, name).ctypes.data
         if core:
-            _lib.check(lib.dz_tune_ident_score_core(T, self.N, bits.ctypes.data, ident.ctypes.data, self.total_rows, total,
-                                                    p("chunk_off"), p("row_off"), p("mids"), p("mid_cell"), p("file_cell_off"),
-                                                    p("cell_dur"), p("cell_ref"), p("cell_step"), self.max_cells, self.G,
-                                                    PATCH_COLLAR, self.SCORE_LANES, self.IDENT_BLOCKS, out.ctypes.data,
-                                                    int(num_threads)), "dz_tune_ident_score_core")
+            tail = (bits.ctypes.data, ident.ctypes.data, self.total_rows, total, p("chunk_off"), p("row_off"), p("mids"),
+                    p("mid_cell"), p("file_cell_off"), p("cell_dur"), p("cell_ref"), p("cell_step"), self.max_cells, self.G,
+                    PATCH_COLLAR, self.SCORE_LANES, self.IDENT_BLOCKS, out.ctypes.data, int(num_threads))
+            if ident.ndim == 3:
+                _lib.check(lib.dz_tune_ident_score_core(T, self.N, *tail), "dz_tune_ident_score_core")
+            else:
+                _lib.check(lib.dz_tune_ident_score_sweep_core(T, ident.shape[1], self.N, *tail),
+                           "dz_tune_ident_score_sweep_core")
         else:
             _lib.check(lib.dz_tune_ident_score(T, self.N, bits.ctypes.data, ident.ctypes.data, self.total_rows, total,
                                                p("file_row_off"), p("chunk_off"), p("step_rows"), p("mids"), p("mid_cell"),
@@ -780,14 +937,23 @@ class IdentTuneCache(TuneCache):
                                                PATCH_COLLAR, out.ctypes.data, int(num_threads)), "dz_tune_ident_score")
         return out
 
+    def _ident_fetch(self, out: torch.Tensor, err: torch.Tensor) -> np.ndarray:
+        rc = int(err.cpu()[0])
+        if rc:
+            who = "dz_tune_ident_score_gpu" if out.dim() == 3 else "dz_tune_ident_score_sweep_gpu"
+            raise _lib.DiartAmdError(f"{who} failed (code {rc}): {self._IDENT_ERRORS.get(rc, 'unknown')}")
+        return out.cpu().numpy()
+
     def evaluate(self, hparams, backend: Optional[str] = None, memory_budget: int = 1 << 30,
-                 num_threads: int = 8) -> TuneResult:
+                 num_threads: int = 8, top_n=None) -> TuneResult:
         """The identification error rate of every trial of ``hparams (T, 4)`` = (tau_active, rho_update, delta_new,
         delta_id), trials in batches whose results fit ``memory_budget`` bytes (``bytes_per_trial`` each).  Scored
         where it is replayed: ``backend="gpu"`` leaves ``T x N x 5`` doubles and the statuses; "host": the clustering
         and the tail through their handles, the names and the score on host threads; "core": the kernels' text on host
-        threads.  A trial whose chain stopped has rate NaN."""
+        threads.  A trial whose chain stopped has rate NaN.  ``top_n``: the plane of a normalised cache that the call
+        is matched on (None: plane 0)."""
         hp = self._hparams4(hparams)
+        planes = self._planes(top_n, "IdentTuneCache.evaluate")
         backend = backend or self.default_backend()
         if backend not in ("gpu", "host", "core"):
             raise ValueError(f"backend '{backend}': gpu, host or core")
@@ -798,23 +964,117 @@ class IdentTuneCache(TuneCache):
             h3, delta = np.ascontiguousarray(hp[a:a + per_batch, :3]), hp[a:a + per_batch, 3]
             if backend == "gpu":
                 assign, st, bits = self._replay_gpu(h3)
-                ident, _ = self._names_gpu(assign, st, delta)
-                out, err = self._ident_score_gpu(bits, ident)
-                rc = int(err.cpu()[0])
-                if rc:
-                    raise _lib.DiartAmdError(f"dz_tune_ident_score_gpu failed (code {rc}): "
-                                             f"{self._IDENT_ERRORS.get(rc, 'unknown')}")
-                per_file.append(out.cpu().numpy())
+                ident, _ = self._names_gpu(assign, st, delta, planes=planes)
+                per_file.append(self._ident_fetch(*self._ident_score_gpu(bits, ident)))
                 status.append(st.cpu().numpy())
                 continue
             assign, st, bits = TuneCache.replay(self, h3, backend, num_threads)
-            ident, _ = self._names_host(assign, st, delta, False, num_threads)
+            ident, _ = self._names_host(assign, st, delta, False, num_threads, planes)
             per_file.append(self._ident_score_host(bits, ident, backend == "core", num_threads))
             status.append(st)
         per_file, status = np.concatenate(per_file), np.concatenate(status)
         comp = per_file.sum(axis=1)
         rate = np.where((status >= 0).any(axis=1), np.nan, _rates(comp))
         return TuneResult(rate, comp, per_file, status)
+
+    def _sweep_args(self, hparams, delta_id, top_n, who: str):
+        hp = self._hparams(hparams)
+        delta = np.ascontiguousarray(np.atleast_1d(np.asarray(delta_id, dtype=np.float64)))
+        if delta.ndim != 1:
+            raise ValueError(f"{who}: delta_id (Q,) thresholds expected, got {delta.shape}")
+        if top_n is not None and not self.normalised:
+            raise ValueError(f"{who}: top_n={top_n!r} on a raw cache, which has one plane and no top_n (top_n=None)")
+        planes = self._planes(top_n, who, several=True)
+        points = len(planes) * delta.shape[0]
+        if not 1 <= points <= MAX_POINTS:
+            raise ValueError(f"{who}: {len(planes)} planes x {delta.shape[0]} thresholds = {points} points (1 .. {MAX_POINTS})")
+        self._check_delta(delta, "point")
+        return hp, delta, planes
+
+    def replay_names_sweep(self, hparams, delta_id, top_n=None, backend: Optional[str] = None, num_threads: int = 8):
+        """``(assign, status, bits, hold (T, P, Q, chunks, G) int32)``: ``replay_names`` of every clustering trial of
+        ``hparams (T, 3)`` at every point of ``evaluate_sweep``."""
+        hp, delta, planes = self._sweep_args(hparams, delta_id, top_n, "IdentTuneCache.replay_names_sweep")
+        backend = backend or self.default_backend()
+        T, P, Q = hp.shape[0], len(planes), delta.shape[0]
+        thr = np.tile(delta, (T, P))                           # (T, P * Q): plane-major, the same for every trial
+        shape = (T, P, Q, int(self.chunk_off[-1]), self.G)
+        if backend == "gpu":
+            a, s, b = self._replay_gpu(hp)
+            _, hold = self._names_gpu(a, s, thr, want_hold=True, planes=planes)
+            torch.cuda.synchronize(a.device)
+            return a.cpu().numpy(), s.cpu().numpy(), b.cpu().numpy().view(np.uint32), hold.cpu().numpy().reshape(shape)
+        a, s, b = TuneCache.replay(self, hp, backend, num_threads)
+        if backend == "core":
+            return a, s, b, self._names_host(a, s, thr, True, num_threads, planes)[1].reshape(shape)
+        hold = np.empty(shape, dtype=np.int32)
+        for p, plane in enumerate(planes):
+            for q in range(Q):
+                hold[:, p, q] = self._names_host(a, s, np.full(T, delta[q]), True, num_threads, [plane])[1]
+        return a, s, b, hold
+
+    def evaluate_sweep(self, hparams, delta_id, top_n=None, backend: Optional[str] = None, memory_budget: int = 1 << 30,
+                       num_threads: int = 8) -> SweepResult:
+        """Every clustering trial of ``hparams (T, 3)`` = (tau_active, rho_update, delta_new) scored at every point of
+        ``top_n (P,)`` x ``delta_id (Q,)``: entry ``[t, p, q]`` of every array is what ``evaluate`` returns for the
+        trial ``hparams[t] + [delta_id[q]]`` on the plane of ``top_n[p]``.  The names depend on the clustering through
+        its assignments only and the scoring cells on its masks only, so a trial is replayed ONCE: the naming kernel
+        walks one chain per (trial, point, file), the scoring kernel builds a pair's cells once and adds every point's
+        components from them.  ``top_n=None``: every plane of the cache (a raw cache has one and
+        takes None only).  ``P * Q``: 1 .. 256 points, plane-major.  ``backend``: "gpu" and "core" run that text;
+        "host" is the loop over the points of ``dz_tune_name_host`` and ``dz_tune_ident_score``, the yardstick.
+        A trial's results take ``sweep_bytes_per_trial(P * Q)`` bytes, most of them identities; ``memory_budget`` is
+        split: three quarters hold the replays' results of a batch of trials, one quarter the identities of a slice of
+        that batch.  No result depends on the batches."""
+        who = "IdentTuneCache.evaluate_sweep"
+        hp, delta, planes = self._sweep_args(hparams, delta_id, top_n, who)
+        backend = backend or self.default_backend()
+        if backend not in ("gpu", "host", "core"):
+            raise ValueError(f"backend '{backend}': gpu, host or core")
+        self._check_steps()
+        P, Q = len(planes), delta.shape[0]
+        # Two levels of batches.  The clustering replay is latency-bound (a batch of 64 trials costs little more than a
+        # batch of one), and the identities of a sweep are by far the largest result: so three quarters of the budget
+        # go to the replays' results, in batches as large as they allow, and one quarter to the identities, which are
+        # named and scored in slices of each replayed batch.
+        J = P * Q
+        per_batch = max(1, (3 * int(memory_budget) // 4) // max(1, TuneCache.bytes_per_trial.fget(self)))
+        per_slice = max(1, (int(memory_budget) // 4) // max(1, J * int(self.chunk_off[-1]) * self.G))
+        per_file, status = [], []
+        for a in range(0, hp.shape[0], per_batch):
+            h3 = np.ascontiguousarray(hp[a:a + per_batch])
+            T = h3.shape[0]
+            thr = np.tile(delta, (min(T, per_slice), P))           # (slice, P * Q): plane-major, the same for every trial
+            slices = [slice(b, min(b + per_slice, T)) for b in range(0, T, per_slice)]
+            if backend == "gpu":
+                assign, st, bits = self._replay_gpu(h3)
+                outs = []
+                for sl in slices:
+                    ident, _ = self._names_gpu(assign[sl], st[sl], thr[:sl.stop - sl.start], planes=planes)
+                    outs.append(self._ident_score_gpu(bits[sl], ident))
+                    del ident
+                per_file += [self._ident_fetch(out, err) for out, err in outs]
+                status.append(st.cpu().numpy())
+                continue
+            assign, st, bits = TuneCache.replay(self, h3, backend, num_threads)
+            for sl in slices:
+                n = sl.stop - sl.start
+                if backend == "core":
+                    ident, _ = self._names_host(assign[sl], st[sl], thr[:n], False, num_threads, planes)
+                    per_file.append(self._ident_score_host(bits[sl], ident, True, num_threads))
+                    continue
+                out = np.empty((n, J, self.N, 5), dtype=np.float64)
+                for j in range(J):
+                    ident, _ = self._names_host(assign[sl], st[sl], thr[:n, j], False, num_threads, [planes[j // Q]])
+                    out[:, j] = self._ident_score_host(bits[sl], ident, False, num_threads)
+                per_file.append(out)
+            status.append(st)
+        per_file, status = np.concatenate(per_file), np.concatenate(status)
+        per_file = per_file.reshape(hp.shape[0], P, Q, self.N, 5)
+        comp = per_file.sum(axis=3)
+        rate = np.where((status >= 0).any(axis=1)[:, None, None], np.nan, _rates(comp.reshape(-1, 5)).reshape(comp.shape[:3]))
+        tops = np.asarray([self.top_ns[p] for p in planes] if self.normalised else [], dtype=np.int64)
+        return SweepResult(rate, comp, per_file, status, tops, delta)
 
     def score(self, *args, **kw):
         raise TypeError("IdentTuneCache scores names, not an optimal mapping: evaluate(hparams (T, 4)); the diarization "
@@ -1282,6 +1542,9 @@ def trial_config(base_config, values: Dict[str, float]):
     return cfg
 
 
+_MATCH_DEFAULTS = dict(sweep=None, top_n=None, normalised=False)     # Optimizer: a study file without these keys
+
+
 class Optimizer:
     """The reference's ``Optimizer`` (``optim.py:17-141``) on a ``TuneCache``: same constructor, ``objective`` value
     (the metric in percent), ``__call__(num_iter, show_progress)``, ``best_performance`` and ``best_hparams``.  optuna
@@ -1299,14 +1562,36 @@ class Optimizer:
     ``delta_id`` is tuned beside the three (``blocks.base.DeltaId``), the cache is an ``IdentTuneCache`` (a ``TuneCache``
     is matched against the gallery on first use), the metric is the ``IdentificationErrorRate`` and ``delta_id=`` is
     required: the value of the kick-start trial, and of every trial when ``DeltaId`` is not among ``hparams``.  There is
-    no default."""
+    no default.  ``normalised=True`` (a gallery with a cohort): the match is the cohort-normalised one, ``delta_id`` is a
+    signed threshold, a ``TuneCache`` is matched with ``with_gallery(gallery, normalised=True, top_n=top_n)`` and
+    ``base.DeltaId`` is sampled over ``cache.delta_range()`` (a ``HyperParameter("delta_id", lo, hi)`` of the caller's
+    is taken as given).  ``sweep=Q``: ``delta_id`` is not sampled; every sampled clustering trial is scored by
+    ``IdentTuneCache.evaluate_sweep`` on every plane at the constructor's ``delta_id`` followed by Q equally spaced
+    interior values of ``cache.delta_range()``, its value is the best finite point (ties: the lowest point index) and
+    its stored ``params`` gain the winner's ``delta_id`` and, with more than one plane, ``top_n``.  The planes of a study
+    are those of a matched cache, else ``top_n=``, else the gallery's own; more than one needs ``sweep=``; the study file
+    records them (with ``sweep`` and ``normalised``) and is continued with the same only."""
 
     def __init__(self, pipeline_class: type, speech_path, reference_path, study_or_path, batch_size: int = 32,
                  hparams: Optional[Sequence[base.HyperParameter]] = None, base_config=None,
                  do_kickstart_hparams: bool = True, metric=None, direction: str = "minimize", sampler: str = "random",
                  seed: int = 0, trials_per_batch: int = 256, cache=None, backend: Optional[str] = None,
-                 scoring: Optional[str] = None, gallery=None, delta_id=None):
+                 scoring: Optional[str] = None, gallery=None, delta_id=None, normalised: bool = False, top_n=None,
+                 sweep: Optional[int] = None):
         self.kind = _replay_kind(pipeline_class)
+        self.normalised, self.top_n, self.sweep = bool(normalised), None, None
+        if gallery is None:
+            for name, given in (("normalised", bool(normalised)), ("top_n", top_n is not None), ("sweep", sweep is not None)):
+                if given:
+                    raise ValueError(f"{name}= is about the match against gallery=, which is not given")
+        if top_n is not None:
+            if not normalised:
+                raise ValueError("top_n= chooses the planes of the normalised match; it needs normalised=True")
+            self.top_n = list(_check_top_ns(top_n, gallery, "Optimizer(gallery=...)"))
+        if sweep is not None:
+            if isinstance(sweep, bool) or not isinstance(sweep, (int, np.integer)) or sweep < 1:
+                raise ValueError(f"sweep={sweep!r}: the number of thresholds per trial, an integer of at least 1")
+            self.sweep = int(sweep)
         track = self.kind != "dia"                 # a track pipeline: tau_active alone, scored where it is replayed
         if scoring not in (None, "host", "device"):
             raise ValueError(f"scoring '{scoring}': host or device")
@@ -1319,7 +1604,9 @@ class Optimizer:
                 raise ValueError("scoring: with gallery= the trials are scored where they are replayed (backend), like the "
                                  "track pipelines")
             from .gallery import check_delta_id
-            self.delta_id = check_delta_id(delta_id, "Optimizer(gallery=...)")
+            if self.normalised and getattr(gallery, "cohort", None) is None:
+                raise ValueError("normalised=True: gallery= has no cohort to normalise against")
+            self.delta_id = check_delta_id(delta_id, "Optimizer(gallery=...)", signed=self.normalised)
             self.kind = "ident"
         elif delta_id is not None:
             raise ValueError("delta_id= is the identification distance of gallery=, which is not given")
@@ -1336,12 +1623,27 @@ class Optimizer:
             pass                                   # matched against the gallery on first use (the cache property)
         elif gallery is not None and isinstance(cache, IdentTuneCache) and cache.names != tuple(gallery.names):
             raise ValueError("cache: this IdentTuneCache was matched against another gallery (other names) than gallery=")
+        elif gallery is not None and isinstance(cache, IdentTuneCache) and cache.normalised != self.normalised:
+            raise ValueError(f"cache: this IdentTuneCache holds the {'normalised' if cache.normalised else 'raw'} match, "
+                             f"and normalised={self.normalised}")
+        elif gallery is not None and isinstance(cache, IdentTuneCache) and self.top_n is not None and \
+                list(cache.top_ns) != self.top_n:
+            raise ValueError(f"cache: this IdentTuneCache holds the planes top_ns = {list(cache.top_ns)}, and "
+                             f"top_n={self.top_n}")
         elif gallery is None and isinstance(cache, IdentTuneCache):
             raise ValueError("cache: an IdentTuneCache is tuned with gallery= and delta_id=; the TuneCache it was made "
                              "from tunes the diarization error rate")
         elif cache is not None and not isinstance(cache, self.cache_class):
             raise ValueError(f"pipeline class {pipeline_class.__name__}: cache must be a {self.cache_class.__name__}, "
                              f"got a {type(cache).__name__}")
+        # the planes of the study: those of a matched cache, else top_n=, else the gallery's own (a raw match has none);
+        # they are what the study file records, so a study cannot be continued on other planes unnoticed
+        if self.normalised:
+            self.top_n = (list(cache.top_ns) if isinstance(cache, IdentTuneCache) else
+                          self.top_n if self.top_n is not None else [int(gallery.top_n)])
+            if len(self.top_n) > 1 and self.sweep is None:
+                raise ValueError(f"top_n={self.top_n}: a trial without sweep= is scored on one plane; several planes are "
+                                 "compared by sweep=")
         self.pipeline_class = pipeline_class
         self.speech_path, self.reference_path, self.batch_size = speech_path, reference_path, batch_size
         wanted = {"dia": DiarizationErrorRate, "ident": IdentificationErrorRate, "vad": DetectionErrorRate,
@@ -1365,8 +1667,15 @@ class Optimizer:
         if self.base_config is None:
             self.base_config = pipeline_class.get_config_class()()
             self.do_kickstart_hparams = False
-        default = list(pipeline_class.hyper_parameters()) + ([base.DeltaId] if gallery is not None else [])
+        default = list(pipeline_class.hyper_parameters()) + ([base.DeltaId] if gallery is not None and self.sweep is None
+                                                             else [])
         self.hparams = list(default if hparams is None else hparams)
+        if self.sweep is not None and any(p.name == "delta_id" for p in self.hparams):
+            raise ValueError(f"hyper-parameter delta_id (DeltaId) with sweep={self.sweep}: the sweep covers delta_id at "
+                             "every trial, so it is not sampled; leave it out of hparams=")
+        if self.sweep is not None and self.direction != "minimize":
+            raise ValueError("sweep= keeps every trial's lowest point: direction='minimize'")
+        self._space: Optional[List[base.HyperParameter]] = None
         possible = vars(self.base_config)
         if not track and (hasattr(self.base_config, "tau_offset") or any(p.name == "tau_offset" for p in self.hparams)):
             from .blocks.diarization import refuse_tau_offset
@@ -1403,18 +1712,57 @@ class Optimizer:
                 raise ValueError(f"{self.study_file} holds a study of {stored.get('hparams')} ({stored.get('direction')}), "
                                  f"not of {names} ({self.direction}): its trials cannot be continued with other "
                                  "hyper-parameters or the other direction")
+            for key, mine in self._match_keys().items():           # (a study without them: the defaults)
+                if stored.get(key, _MATCH_DEFAULTS[key]) != mine:
+                    raise ValueError(f"{self.study_file} holds a study with {key}={stored.get(key, _MATCH_DEFAULTS[key])!r}, "
+                                     f"not {key}={mine!r}: its trials cannot be continued with another {key}")
             self.trials = stored["trials"]
         self._cache = cache
 
     @property
     def cache(self):
         if self._cache is None:
-            kw = {} if self.gallery is None else dict(gallery=self.gallery)
+            kw = {} if self.gallery is None else dict(gallery=self.gallery, normalised=self.normalised, top_n=self.top_n)
             self._cache = self.cache_class.collect(self.pipeline_class, self.base_config, self.speech_path, self.reference_path,
                                             self.batch_size, **kw)
         if self.gallery is not None and type(self._cache) is TuneCache:
-            self._cache = self._cache.with_gallery(self.gallery)
+            self._cache = self._cache.with_gallery(self.gallery, normalised=self.normalised, top_n=self.top_n)
         return self._cache
+
+    def _match_keys(self) -> dict:
+        """What the study file records about the match: a study continues with the same values only."""
+        return dict(sweep=self.sweep, top_n=self.top_n, normalised=self.normalised)
+
+    def _ranges(self) -> List[base.HyperParameter]:
+        """``hparams`` as they are sampled: ``base.DeltaId`` itself stands for the range of the stored normalised
+        distances of a normalised cache (its own (0, 2) is for raw distances)."""
+        if self._space is None:
+            self._space = [base.HyperParameter("delta_id", *self.cache.delta_range())
+                           if p is base.DeltaId and self.normalised else p for p in self.hparams]
+        return self._space
+
+    def sweep_thresholds(self) -> np.ndarray:
+        """The thresholds of every trial of a ``sweep=Q`` study: the constructor's ``delta_id``, then Q equally spaced
+        interior values of ``cache.delta_range()``."""
+        lo, hi = self.cache.delta_range()
+        return np.concatenate([[self.delta_id], np.linspace(lo, hi, self.sweep + 2)[1:-1]])
+
+    def objective_sweep(self, params: Sequence[Dict[str, float]]):
+        """``(values, winners)`` of a ``sweep=Q`` study: the metric in percent at every trial's best finite point (NaN
+        where no point is finite), and what that point adds to the trial's parameters."""
+        hp = np.array([[float(p.get(name, self._base_value(name))) for name in TUNABLE] for p in params], dtype=np.float64)
+        result = self.cache.evaluate_sweep(hp, self.sweep_thresholds(), backend=self.backend)
+        T, P, Q = result.rate.shape
+        flat = result.rate.reshape(T, P * Q)
+        best = np.argmin(np.where(np.isnan(flat), np.inf, flat), axis=1)          # (the first among equals)
+        values = 100.0 * flat[np.arange(T), best]
+        winners = []
+        for j in best:
+            won = dict(delta_id=float(result.delta_id[j % Q]))
+            if P > 1:
+                won["top_n"] = int(result.top_n[j // Q])
+            winners.append(won)
+        return values, winners
 
     def _complete(self) -> List[dict]:
         return [t for t in self.trials if t["value"] is not None]
@@ -1485,18 +1833,27 @@ class Optimizer:
         side = 1
         while (side + 1) ** len(self.hparams) <= total:
             side += 1
-        axes = [np.linspace(p.low, p.high, side + 2)[1:-1] for p in self.hparams]
+        axes = [np.linspace(p.low, p.high, side + 2)[1:-1] for p in self._ranges()]
         mesh = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, len(self.hparams))
         return [{p.name: float(v) for p, v in zip(self.hparams, row)} for row in mesh]
 
     def _random(self, number: int) -> Dict[str, float]:
         """The draw of trial ``number`` depends on (seed, number) only, so a resumed study continues the sequence."""
         rng = np.random.default_rng([self.seed, number])
-        return {p.name: float(rng.uniform(p.low, p.high)) for p in self.hparams}
+        return {p.name: float(rng.uniform(p.low, p.high)) for p in self._ranges()}
+
+    def _sampled(self, params: Dict[str, float]) -> Dict[str, float]:
+        """A stored trial's sampled keys: a sweep adds the winning point's ``delta_id`` and ``top_n`` to them."""
+        if self.sweep is None:
+            return params
+        names = {p.name for p in self.hparams}
+        return {k: v for k, v in params.items() if k in names}
 
     def _store(self) -> None:
         self.study_path.mkdir(parents=True, exist_ok=True)
         payload = dict(direction=self.direction, hparams=[p.name for p in self.hparams], trials=self.trials)
+        if self._match_keys() != _MATCH_DEFAULTS:              # (a study without them keeps the keys it always had)
+            payload.update(self._match_keys())
         tmp = self.study_file.with_suffix(".json.tmp")
         tmp.write_text(json.dumps(payload, indent=1))
         tmp.replace(self.study_file)
@@ -1505,17 +1862,21 @@ class Optimizer:
         queue: List[Dict[str, float]] = []
         if self.do_kickstart_hparams:
             kick = {p.name: float(self._base_value(p.name)) for p in self.hparams}
-            if not any(t["params"] == kick for t in self.trials):
+            if not any(self._sampled(t["params"]) == kick for t in self.trials):
                 queue.append(kick)
         if self.sampler == "grid":
-            stored = [t["params"] for t in self.trials]
+            stored = [self._sampled(t["params"]) for t in self.trials]
             queue += [p for p in self._grid(int(num_iter)) if p not in stored and p not in queue]
         else:
             first = len(self.trials)
             queue += [self._random(first + j) for j in range(len(queue), int(num_iter))]
         for a in range(0, len(queue), self.trials_per_batch):
             batch = queue[a:a + self.trials_per_batch]
-            values = self.objective(batch)
+            if self.sweep is not None:
+                values, winners = self.objective_sweep(batch)
+                batch = [{**params, **won} if not np.isnan(v) else params for params, won, v in zip(batch, winners, values)]
+            else:
+                values = self.objective(batch)
             for params, v in zip(batch, values):
                 self.trials.append(dict(number=len(self.trials), params=params, value=None if np.isnan(v) else float(v)))
             self._store()

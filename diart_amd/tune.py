@@ -10,7 +10,10 @@ that pipeline (``optim.OsdTuneCache``, the same arguments ignored) against the o
 ``--gallery FILE --delta-id VALUE`` (``SpeakerDiarization`` only) tunes ``delta_id``, the distance under which a speaker
 takes the name of a voiceprint of the ``SpeakerGallery`` in FILE, beside the three, against the identification error rate
 (``optim.IdentTuneCache``): the RTTM labels are then compared with the gallery's names as they are.  ``--delta-id`` has no
-default: it is the kick-start trial's value and, when ``--hparams`` leaves ``delta_id`` out, every trial's."""
+default: it is the kick-start trial's value and, when ``--hparams`` leaves ``delta_id`` out, every trial's.
+``--normalised`` tunes the threshold of the cohort-normalised match instead (the gallery file holds a cohort;
+``--top-n N [N ...]``: one stored match per value), and ``--sweep Q`` scores every clustering trial at ``--delta-id``
+and Q further thresholds on every plane for the price of one replay, keeping the trial's best point."""
 from __future__ import annotations
 
 import argparse
@@ -70,6 +73,15 @@ def parser() -> argparse.ArgumentParser:
                     help="A SpeakerGallery file (.npz): tune delta_id too, against the identification error rate")
     ap.add_argument("--delta-id", type=float, default=None,
                     help="Base value of delta_id; required with --gallery, there is no default")
+    ap.add_argument("--normalised", action="store_true",
+                    help="With --gallery: tune the threshold of the cohort-normalised match (the gallery file must hold a "
+                         "cohort); --delta-id is then a signed threshold")
+    ap.add_argument("--top-n", nargs="+", type=int, default=None, metavar="N",
+                    help="With --normalised: the top_n of the normalised match, one plane of the cache per value (1 to 8; "
+                         "several need --sweep). Defaults to the gallery's own")
+    ap.add_argument("--sweep", type=int, default=None, metavar="Q",
+                    help="With --gallery: do not sample delta_id; score every trial at --delta-id and Q equally spaced "
+                         "thresholds on every plane, and keep its best point")
     ap.add_argument("--objective", default="der", choices=("der", "fmeasure"),
                     help="der: minimise the pipeline's error rate (the default); fmeasure: maximise the detection "
                          "F-measure (--pipeline OverlappedSpeechDetection only)")
@@ -92,6 +104,9 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
         raise SystemExit(f"--objective fmeasure is the detection F-measure of OverlappedSpeechDetection; --pipeline "
                          f"{args.pipeline} is tuned on its error rate (--objective der)")
     gallery = None
+    normalised, top_n, sweep = (getattr(args, name, None) for name in ("normalised", "top_n", "sweep"))
+    if args.gallery is None and (normalised or top_n is not None or sweep is not None):
+        raise SystemExit("--normalised, --top-n and --sweep are about the match against --gallery, which is not given")
     if args.gallery is not None or args.delta_id is not None:
         if vad:
             raise SystemExit(f"--gallery names the speakers of SpeakerDiarization; --pipeline {args.pipeline} has none")
@@ -136,8 +151,12 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
         possible = possible + [TauOffset, MinDurationOn, MinDurationOff]
     if gallery is not None:
         from .blocks.base import DeltaId
-        possible, cache_class = possible + [DeltaId], IdentTuneCache
-        default = [hp.name for hp in possible]
+        cache_class = IdentTuneCache
+        if sweep is None:                                     # (a sweep covers delta_id at every trial)
+            possible = possible + [DeltaId]
+            default = [hp.name for hp in possible]
+        elif "delta_id" in (args.hparams or []):
+            raise SystemExit("--sweep covers delta_id at every trial: leave delta_id out of --hparams")
     names = args.hparams or default
     hparams = [hp for hp in (HyperParameter.from_name(name) for name in names) if hp in possible]
     if not hparams:
@@ -148,7 +167,7 @@ def run(args: argparse.Namespace, models=None) -> Optimizer:
         cache = cache_class.load(args.cache)
     objective = dict(metric=OverlapDetectionFMeasure(), direction="maximize") if args.objective == "fmeasure" else {}
     if gallery is not None:
-        objective = dict(gallery=gallery, delta_id=args.delta_id)
+        objective = dict(gallery=gallery, delta_id=args.delta_id, normalised=bool(normalised), top_n=top_n, sweep=sweep)
     opt = Optimizer(pipeline_class, args.root, args.reference, Path(args.output).expanduser(),
                     batch_size=args.batch_size, hparams=hparams, base_config=base_config, sampler=args.sampler,
                     seed=args.seed, trials_per_batch=args.trials_per_batch, cache=cache,

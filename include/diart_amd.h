@@ -1259,6 +1259,38 @@ int dz_tune_ident_score_core(int trials, int n_files, const unsigned* bits, cons
                              const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
                              int max_cells, int max_speakers, double collar, int lanes, int score_blocks,
                              double* out, int num_threads);
+/* The sweep: one clustering trial named and scored at `points` (plane, threshold) points, 1 .. 256,
+ * plane-major: point j reads plane j / (points / planes) of match_index / match_distance (planes, chunks, k_local),
+ * 1 .. 8 planes that divide the points, and threshold delta_id[t * points + j] of delta_id (T, points).  ident
+ * (T, points, chunks, max_speakers), hold likewise or NULL, out (T, points, N, 5).  dz_tune_name_sweep: one
+ * wavefront per (trial, point, file) chain; dz_tune_ident_score_sweep_gpu: one workgroup per (trial, file) pair,
+ * the cells' masks once and then every point's components in turn, each point's doubles those of the one-point
+ * call.  dz_tune_name and dz_tune_ident_score_gpu (and the two host forms) are these with points = planes = 1.
+ * Refused with 2 before anything runs: what the one-point entries refuse, points outside 1 .. 256, planes outside
+ * 1 .. 8 or not dividing the points.                                                                        */
+int dz_tune_name_sweep(dz_ctx* ctx, int trials, int points, int planes, int n_files, int total_chunks, int k_local,
+                       int max_speakers, int voiceprints, const int* d_file_chunk_off, const signed char* d_assign,
+                       const int* d_status, const int* d_match_index, const float* d_match_distance,
+                       const signed char* d_vp_ref, const double* d_delta_id, signed char* d_ident, int* d_hold,
+                       int name_blocks, void* stream);
+int dz_tune_name_sweep_host(int trials, int points, int planes, int n_files, int total_chunks, int k_local,
+                            int max_speakers, int voiceprints, const int* file_chunk_off, const signed char* assign,
+                            const int* status, const int* match_index, const float* match_distance,
+                            const signed char* vp_ref, const double* delta_id, signed char* ident, int* hold,
+                            int num_threads);
+int dz_tune_ident_score_sweep_gpu(dz_ctx* ctx, int trials, int points, int n_files, const unsigned* d_bits,
+                                  const signed char* d_ident, int total_rows, int total_chunks,
+                                  const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
+                                  const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
+                                  const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
+                                  int max_speakers, double collar, double* d_out, unsigned* d_scratch,
+                                  int score_blocks, int* d_err, void* stream);
+int dz_tune_ident_score_sweep_core(int trials, int points, int n_files, const unsigned* bits, const signed char* ident,
+                                   int total_rows, int total_chunks, const int* file_chunk_off, const int* row_off,
+                                   const double* mids, const int* mid_cell, const int* file_cell_off,
+                                   const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
+                                   int max_cells, int max_speakers, double collar, int lanes, int score_blocks,
+                                   double* out, int num_threads);
 
 /* sizeof() of the five structs that cross this boundary, in declaration order
  * (dz_sincnet_weights, dz_seg_weights, dz_emb_weights, dz_ecapa_weights, dz_convgemm_desc): a
