@@ -292,6 +292,12 @@ SIGNATURES = {
                                                 vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, vp, vp]),
     "dz_tune_ident_score_sweep_core": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
                                                  vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, C.c_int]),
+    "dz_agglo_work_bytes": (C.c_longlong, [C.c_int, vp]),
+    "dz_agglo_linkage": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_longlong, vp]),
+    "dz_agglo_linkage_host": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int]),
+    "dz_agglo_cut": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, c_int_p]),
+    "dz_offline_assign": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "dz_offline_reconstruct": (C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_double, vp, vp, C.c_int]),
     "dz_rows_repeat": (C.c_int, [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, c_int_p]),
     "dz_gallery_create": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "dz_gallery_destroy": (C.c_int, [vp]),

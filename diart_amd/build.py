@@ -19,13 +19,15 @@ LIB_EXPERIMENTS = HERE / "libdiart_amd_exp.so"
 SOURCES = ["api.hip", "seg_api.hip", "xvec_api.hip", "kernel_api.hip", "ecapa_api.hip", "k_front.hip", "k_convgemm.hip", "k_gemm_f32.hip", "k_gemm_split.hip", "k_gemm_pre.hip",
            "k_mlp_head.hip", "k_conv_pool.hip", "k_lstm.hip", "k_lstm_mfma.hip", "k_pool.hip",
            "k_ecapa.hip", "ecm_api.hip", "k_ecapa_mel.hip", "sbx_api.hip", "titanet_api.hip", "k_titanet.hip", "sbr_api.hip", "k_sb_resnet.hip", "wespeaker_api.hip", "k_wespeaker.hip", "k_conv2d.hip", "k_resample.hip", "k_volume.hip", "k_rows_repeat.hip", "k_gather.hip", "resample_api.hip", "ring.hip", "cluster.cpp", "tail.cpp", "hostpool.cpp", "filebatch.cpp", "k_tune.hip", "k_tune_vad.hip", "k_tune_score.hip", "k_tune_ident.hip", "tune_score.cpp",
-           "gallery_api.hip", "k_gallery.hip", "k_cohort.hip"]
+           "gallery_api.hip", "k_gallery.hip", "k_cohort.hip", "k_agglo.hip", "agglo.cpp"]
 # -DDZ_EXPERIMENTS only (csrc/dz_common.h "build flavours"): the never-default GEMM generations
 EXPERIMENT_SOURCES = ["experiments/k_gemm_g2.hip", "experiments/k_gemm_g3.hip"]
 ARCH = "gfx950"
 # per-source flags.  k_lstm_mfma.hip: the cell update beside the recurrence's MFMAs stays plain f32 instructions (hipcc's
 # SLP vectoriser would pack adjacent adds / multiplies into v_pk_*_f32, which cost more beside MFMAs than the two they replace)
-EXTRA_FLAGS = {"k_lstm_mfma.hip": ["-fno-slp-vectorize"]}
+# k_agglo.hip / agglo.cpp: merge order is decided by comparing nearly equal float64 distances, so the host and the device
+# must round alike: no fused multiply-add where the text has a multiply and an add (csrc/agglo_core.h)
+EXTRA_FLAGS = {"k_lstm_mfma.hip": ["-fno-slp-vectorize"], "k_agglo.hip": ["-ffp-contract=off"], "agglo.cpp": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:
@@ -48,7 +50,7 @@ def build(force: bool = False, verbose: bool = False, experiments: bool = False)
     hipcc = _hipcc()
     objdir = HERE / "build" / ("exp" if experiments else "ship")
     objdir.mkdir(parents=True, exist_ok=True)
-    headers = [CSRC / "dz_common.h", CSRC / "dz_embed.h", CSRC / "dz_sincnet.h", CSRC / "hostpool.h", CSRC / "tune_core.h", CSRC / "tune_ident_core.h", CSRC / "clu_core.h", CSRC / "tail_core.h", HERE.parent / "include" / "diart_amd.h",
+    headers = [CSRC / "dz_common.h", CSRC / "dz_embed.h", CSRC / "dz_sincnet.h", CSRC / "hostpool.h", CSRC / "tune_core.h", CSRC / "tune_ident_core.h", CSRC / "clu_core.h", CSRC / "tail_core.h", CSRC / "agglo_core.h", HERE.parent / "include" / "diart_amd.h",
                HERE.parent / "include" / "diart_amd_experiments.h"]
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", f"-I{CSRC}"]
     sources, lib = list(SOURCES), LIB

@@ -9,6 +9,10 @@ which is no tensor function at all: the rule of the track pipelines' minimum dur
 bookkeeping at the end of a file.  Inputs may live on the host
 (the reference runs these on CPU tensors) or on the GPU; the result comes back on the device
 of the input.  There is no torch fallback: without ``libdiart_amd.so`` and a GPU they raise.
+
+``linkage_centroid`` and ``cut_linkage`` are the clustering of the whole-file mode (``offline.py``):
+a CUDA tensor runs the HIP kernels of ``csrc/k_agglo.hip``, a host array the same text compiled for the host, which is
+the library's own code and no fallback to another implementation.
 """
 from __future__ import annotations
 
@@ -435,3 +439,160 @@ def min_duration(annotation, min_duration_on: float = 0.0, min_duration_off: flo
         if not (segment.end - segment.start < on):
             out[segment, track] = label
     return out
+
+
+# ---------------------------------------------------------------------------------------------- whole-file clustering
+LINKAGE_MAX_DIM = 1024               # AG_DMAX (csrc/agglo_core.h)
+LINKAGE_MAX_FILES = 1024             # files of one dz_agglo_linkage call
+LINKAGE_MEMORY_BUDGET = 4 << 30      # bytes of distance matrices (8 N^2 per file) one call may hold: N <= 23 170
+# backend=None on a machine with a GPU: a file of fewer rows runs on the host.  Measured (profiles/r36a_offline.json, D =
+# 256): one core takes 1.5 ms at N = 256 and 6.0 ms at 512, the GPU call 2.6 ms and 5.3 ms (about 10 us per merge, a
+# dependent chain inside one workgroup): the host wins up to 256 rows, the GPU from 512 on.
+LINKAGE_GPU_MIN_ROWS = 512
+
+
+def _linkage_groups(counts, memory_budget: int):
+    """Files whose float64 distance matrices fit the budget together share a call, in order; a file that does not fit
+    it alone is refused by name."""
+    groups, cur, used = [], [], 0
+    for i, n in enumerate(counts):
+        need = 8 * int(n) * int(n)
+        if need > memory_budget:
+            raise ValueError(f"file {i}: the distance matrix of {n} rows takes {need} bytes, above memory_budget = "
+                             f"{memory_budget}; whole-file clustering needs 8 N^2 bytes per file")
+        if cur and (used + need > memory_budget or len(cur) == LINKAGE_MAX_FILES):
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += need
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def linkage_unit_rows(rows, backend: Optional[str] = None, device: Optional[torch.device] = None,
+                      memory_budget: int = LINKAGE_MEMORY_BUDGET, num_threads: int = 8):
+    """Centroid linkage of every file of ``rows`` — ``(N_f, D)`` float64 arrays (or CUDA tensors) of finite unit rows,
+    which the caller has checked — as a list of ``(max(N_f - 1, 0), 4)`` float64 arrays in scipy's ``linkage`` layout.
+    ``backend="gpu"``: ``dz_agglo_linkage`` (``csrc/k_agglo.hip``); ``"core"``: the same text on host threads
+    (``dz_agglo_linkage_host``); ``None``: on a machine with a GPU the files of at least ``LINKAGE_GPU_MIN_ROWS`` rows on
+    the GPU and the smaller ones on the host (the two give the same ``Z`` bit for bit), else the host."""
+    import numpy as np
+    if backend not in ("gpu", "core", None):
+        raise ValueError(f"backend must be 'gpu', 'core' or None, got {backend!r}")
+    if not rows:
+        return []
+    dims = {int(x.shape[1]) for x in rows}
+    if len(dims) != 1:
+        raise ValueError(f"the files of one call share their dimension, got {sorted(dims)}")
+    D = dims.pop()
+    if not 1 <= D <= LINKAGE_MAX_DIM:
+        raise ValueError(f"dimension {D} outside [1, {LINKAGE_MAX_DIM}]")
+    counts = [int(x.shape[0]) for x in rows]
+    groups = _linkage_groups(counts, int(memory_budget))          # refusals come before the GPU is touched
+    if backend is None and torch.cuda.is_available():
+        out = [None] * len(rows)
+        for where, part in (("gpu", [i for i, n in enumerate(counts) if n >= LINKAGE_GPU_MIN_ROWS]),
+                            ("core", [i for i, n in enumerate(counts) if n < LINKAGE_GPU_MIN_ROWS])):
+            for i, Z in zip(part, linkage_unit_rows([rows[i] for i in part], where, device, memory_budget, num_threads)):
+                out[i] = Z
+        return out
+    backend = backend or "core"
+    lib = _lib.load()
+    out = [None] * len(rows)
+    dev = _gpu(device) if backend == "gpu" else None
+    for group in groups:
+        off = np.concatenate([[0], np.cumsum([counts[i] for i in group])]).astype(np.int32)
+        nz = int(sum(max(counts[i] - 1, 0) for i in group))
+        if backend == "gpu":
+            x = torch.cat([(rows[i] if isinstance(rows[i], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rows[i])))
+                           .to(dev, torch.float64) for i in group]).contiguous()
+            Z = torch.zeros((max(nz, 1), 4), dtype=torch.float64, device=dev)
+            status = torch.zeros(len(group), dtype=torch.int32, device=dev)
+            need = lib.dz_agglo_work_bytes(len(group), off.ctypes.data)
+            if need < 0:
+                _lib.check(2, "dz_agglo_work_bytes")
+            work = torch.empty(int(need), dtype=torch.uint8, device=dev)
+            _lib.check(lib.dz_agglo_linkage(_lib.context(dev.index), len(group), off.ctypes.data, x.data_ptr(), D,
+                                            Z.data_ptr(), status.data_ptr(), work.data_ptr(), int(need),
+                                            torch.cuda.current_stream(dev).cuda_stream), "dz_agglo_linkage")
+            Zh, st = Z.cpu().numpy(), status.cpu().numpy()        # the one synchronising copy of the call
+            del work
+        else:
+            x = np.ascontiguousarray(np.concatenate([np.asarray(rows[i].cpu() if isinstance(rows[i], torch.Tensor) else rows[i],
+                                                                dtype=np.float64).reshape(counts[i], D) for i in group]))
+            Zh, st = np.zeros((max(nz, 1), 4), dtype=np.float64), np.zeros(len(group), dtype=np.int32)
+            _lib.check(lib.dz_agglo_linkage_host(len(group), off.ctypes.data, x.ctypes.data, D, Zh.ctypes.data,
+                                                 st.ctypes.data, int(num_threads)), "dz_agglo_linkage_host")
+        if (st != -1).any():
+            bad = int(np.flatnonzero(st != -1)[0])
+            raise _lib.DiartAmdError(f"linkage of file {group[bad]} stopped at merge {int(st[bad])}: an index failed its "
+                                     "range check (rows that are not finite?)")
+        z0 = 0
+        for i in group:
+            m = max(counts[i] - 1, 0)
+            out[i] = Zh[z0:z0 + m].copy()
+            z0 += m
+    return out
+
+
+def linkage_centroid(x, memory_budget: int = LINKAGE_MEMORY_BUDGET, num_threads: int = 8):
+    """``scipy.cluster.hierarchy.linkage(x / |x|, "centroid")`` in float64: the dendrogram ``Z`` ``(N - 1, 4)`` of the
+    rows of ``x`` ``(N, D)``, each scaled to unit length — ``(smaller id, larger id, height, size)`` per merge, the
+    merge at step t getting id ``N + t``.  A CUDA tensor runs the HIP kernels (``csrc/k_agglo.hip``); a CPU tensor or a
+    numpy array runs the same text on the host.  A list of such arrays is clustered in one call and returns a list.
+    ``N`` = 0 or 1 gives an empty ``Z``.  Refused: a non-finite or zero row, ``D`` above 1 024, a matrix (``8 N^2``
+    bytes) above ``memory_budget``."""
+    import numpy as np
+    many = isinstance(x, (list, tuple))
+    xs = list(x) if many else [x]
+    gpu = [isinstance(a, torch.Tensor) and a.is_cuda for a in xs]
+    if any(gpu) and not all(gpu):
+        raise ValueError("the files of one call live on one side: all CUDA tensors, or all host arrays")
+    unit = []
+    for i, a in enumerate(xs):
+        if a.ndim != 2:
+            raise ValueError(f"file {i}: rows (N, D) expected, got shape {tuple(a.shape)}")
+        if a.shape[1] > LINKAGE_MAX_DIM or a.shape[1] < 1:
+            raise ValueError(f"file {i}: dimension {a.shape[1]} outside [1, {LINKAGE_MAX_DIM}]")
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            a = a.to(torch.float64)
+            norm = a.norm(dim=1, keepdim=True)
+            ok = bool((torch.isfinite(a).all() & torch.isfinite(norm).all() & (norm > 0).all()).item())
+        else:
+            a = np.asarray(a.detach().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+            with np.errstate(invalid="ignore", over="ignore"):
+                norm = np.sqrt((a * a).sum(axis=1, keepdims=True))
+            ok = bool(np.isfinite(a).all() and np.isfinite(norm).all() and (norm > 0).all())
+        if not ok:
+            raise ValueError(f"file {i}: a row is not finite or has zero norm; linkage_centroid takes rows it can scale to "
+                             "unit length")
+        unit.append(a / norm if a.shape[0] else a)
+    Z = linkage_unit_rows(unit, "gpu" if any(gpu) else "core", xs[0].device if any(gpu) else None, memory_budget,
+                          num_threads)
+    return Z if many else Z[0]
+
+
+def cut_linkage(Z, threshold: float, min_cluster_size: int = 1, max_speakers: Optional[int] = None, n: Optional[int] = None):
+    """``fcluster(Z, threshold, "distance")`` followed by the whole-file mode's choice of clusters: a flat cluster is a
+    maximal subtree whose merge heights are all ``<= threshold``; kept are those with at least ``min_cluster_size``
+    leaves, at most ``max_speakers`` of them by size (ties: the one whose first leaf comes first), the largest one when
+    none qualifies, numbered ``0 .. G - 1`` by their first leaf.  Returns ``(labels, G)``: per leaf its kept cluster
+    or -1.  ``n``: the leaves, ``len(Z) + 1`` unless given (an empty ``Z`` stands for one leaf, or for none)."""
+    import math
+    import numpy as np
+    if not math.isfinite(float(threshold)):
+        raise ValueError(f"threshold must be finite, got {threshold}")
+    if int(min_cluster_size) < 1:
+        raise ValueError(f"min_cluster_size must be at least 1, got {min_cluster_size}")
+    if max_speakers is not None and int(max_speakers) < 1:
+        raise ValueError(f"max_speakers must be at least 1, got {max_speakers}")
+    Z = np.ascontiguousarray(Z, dtype=np.float64).reshape(-1, 4)
+    n = Z.shape[0] + 1 if n is None else int(n)
+    if n != Z.shape[0] + 1 and not (n == 0 and Z.shape[0] == 0):
+        raise ValueError(f"{Z.shape[0]} merges are no dendrogram over {n} leaves")
+    labels, G = np.full(max(n, 1), -1, dtype=np.int32), _lib.C.c_int(0)
+    _lib.check(_lib.load().dz_agglo_cut(Z.ctypes.data, n, float(threshold), int(min_cluster_size),
+                                        2 ** 31 - 1 if max_speakers is None else int(max_speakers), labels.ctypes.data,
+                                        _lib.C.byref(G)), "dz_agglo_cut")
+    return labels[:n], int(G.value)

@@ -103,41 +103,48 @@ class _ReplayCache:
         model outputs of a batch of chunks as numpy arrays (the first one ``(batch, frames, ...)``); per file their
         concatenation over the chunks, the window starts, ``finalise``'s frame resolution, the shift, the reference."""
         from .features import load_rttm
-        from .inference import file_blocks, read_wav, resample_file, rolling_windows
         speech_path, reference_path = Path(speech_path).expanduser(), Path(reference_path).expanduser()
         assert speech_path.is_dir(), "Speech path must be a directory"
         assert reference_path.is_dir(), "Reference path must be a directory"
-        cfg = pipeline.config
         files = []
         for fp in sorted(p for p in speech_path.iterdir() if p.suffix.lower() == ".wav"):
-            waveform, sr = read_wav(fp)
-            padding = cfg.get_padding(len(waveform) / sr)
-            if sr != cfg.sample_rate:
-                if getattr(getattr(cfg, "device", None), "type", None) != "cuda":
-                    raise ValueError(f"{fp} has sample rate {sr}, the pipeline's is {cfg.sample_rate} and the pipeline "
-                                     "has no GPU device to resample on; resample the file first")
-                waveform, sr = resample_file(waveform, sr, cfg.sample_rate, cfg.device), cfg.sample_rate
-            outs, starts, res, batch = [], [], [], []
-
-            def flush():
-                arrays = outputs(batch)
-                outs.append(arrays)
-                starts.extend(w.extent.start for w in batch)
-                res.extend([batch[0].extent.duration / arrays[0].shape[1]] * len(batch))     # finalise's seg_resolution
-                batch.clear()
-
-            for window in rolling_windows(file_blocks(waveform, sr, padding, cfg.step), cfg.duration, cfg.step, sr):
-                batch.append(window)
-                if len(batch) == max(1, int(batch_size)):
-                    flush()
-            if batch:
-                flush()
-            if not outs:
-                raise ValueError(f"{fp} is shorter than one chunk")
-            files.append(dict(uri=fp.stem, outputs=[np.concatenate(a) for a in zip(*outs)], starts=np.array(starts),
-                              res=np.array(res), shift=-padding[0],
-                              reference=load_rttm(reference_path / f"{fp.stem}.rttm").popitem()[1]))
+            f = _ReplayCache._collect_file(pipeline, fp, batch_size, outputs)
+            f["reference"] = load_rttm(reference_path / f"{fp.stem}.rttm").popitem()[1]
+            files.append(f)
         return files
+
+    @staticmethod
+    def _collect_file(pipeline, fp, batch_size: int, outputs) -> dict:
+        """One WAV of ``_collect_files``, without its reference (``offline.OfflineDiarization`` collects a file alone)."""
+        from .inference import file_blocks, read_wav, resample_file, rolling_windows
+        fp = Path(fp)
+        cfg = pipeline.config
+        waveform, sr = read_wav(fp)
+        padding = cfg.get_padding(len(waveform) / sr)
+        if sr != cfg.sample_rate:
+            if getattr(getattr(cfg, "device", None), "type", None) != "cuda":
+                raise ValueError(f"{fp} has sample rate {sr}, the pipeline's is {cfg.sample_rate} and the pipeline "
+                                 "has no GPU device to resample on; resample the file first")
+            waveform, sr = resample_file(waveform, sr, cfg.sample_rate, cfg.device), cfg.sample_rate
+        outs, starts, res, batch = [], [], [], []
+
+        def flush():
+            arrays = outputs(batch)
+            outs.append(arrays)
+            starts.extend(w.extent.start for w in batch)
+            res.extend([batch[0].extent.duration / arrays[0].shape[1]] * len(batch))     # finalise's seg_resolution
+            batch.clear()
+
+        for window in rolling_windows(file_blocks(waveform, sr, padding, cfg.step), cfg.duration, cfg.step, sr):
+            batch.append(window)
+            if len(batch) == max(1, int(batch_size)):
+                flush()
+        if batch:
+            flush()
+        if not outs:
+            raise ValueError(f"{fp} is shorter than one chunk")
+        return dict(uri=fp.stem, outputs=[np.concatenate(a) for a in zip(*outs)], starts=np.array(starts),
+                    res=np.array(res), shift=-padding[0])
 
     def _prepare_plan(self) -> None:
         lib = _lib.load()
@@ -238,6 +245,17 @@ class _ReplayCache:
         return ann.support(PATCH_COLLAR)
 
 
+def _diarization_outputs(pipeline):
+    """``outputs(batch)`` of ``_collect_files`` for ``SpeakerDiarization``: the model half's scores and embeddings of a
+    batch of chunks as float32 arrays."""
+    def outputs(batch):
+        s, e = pipeline.model_outputs(batch)
+        s = s.detach().cpu().numpy().astype(np.float32, copy=False)
+        e = e.detach().cpu().numpy().astype(np.float32, copy=False)
+        return s, (e if e.ndim == 3 else e[None])
+    return outputs
+
+
 def _rates(comp: np.ndarray) -> np.ndarray:
     """``_Accumulating._rate`` of ``(T, 5)`` components."""
     err = comp[:, 2] + comp[:, 3] + comp[:, 4]
@@ -300,14 +318,7 @@ class TuneCache(_ReplayCache):
             raise ValueError(f"max_speakers = {base_config.max_speakers}: the replay keeps one 32-bit mask per frame, "
                              f"at most {MAX_SPEAKERS} speakers")
         pipeline = pipeline_class(base_config)
-
-        def outputs(batch):
-            s, e = pipeline.model_outputs(batch)
-            s = s.detach().cpu().numpy().astype(np.float32, copy=False)
-            e = e.detach().cpu().numpy().astype(np.float32, copy=False)
-            return s, (e if e.ndim == 3 else e[None])
-
-        files = cls._collect_files(pipeline, speech_path, reference_path, batch_size, outputs)
+        files = cls._collect_files(pipeline, speech_path, reference_path, batch_size, _diarization_outputs(pipeline))
         for f in files:
             f["seg"], f["emb"] = f.pop("outputs")
         return cls(files, pipeline.config)

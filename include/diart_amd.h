@@ -1292,6 +1292,49 @@ int dz_tune_ident_score_sweep_core(int trials, int points, int n_files, const un
                                    int max_cells, int max_speakers, double collar, int lanes, int score_blocks,
                                    double* out, int num_threads);
 
+/* Whole-file diarization: centroid-linkage agglomerative clustering of unit rows in float64, and
+ * what follows the dendrogram.  A call clusters n_files files: file f owns rows rows_off[f] .. rows_off[f + 1] - 1 of
+ * x (rows, D) float64 (rows_off: HOST memory, n_files + 1 ascending ints from 0) and max(n - 1, 0) rows of Z, the
+ * files' rows one after another: Z[t] = (smaller id, larger id, height, size), scipy's linkage(x, "centroid")
+ * layout.  status (n_files): -1, or the merge at which an index read from memory failed its range check (that
+ * file's Z is unfinished).  Rows are expected finite and of unit length (the caller checks).
+ * dz_agglo_linkage: x, Z, status and the workspace in device memory, work_bytes >= dz_agglo_work_bytes(n_files,
+ * rows_off) (8 n^2 bytes per file and a few arrays per row; -1: bad arguments); enqueued on `stream`, which it
+ * waits for once before the first kernel; nothing is read back.  dz_agglo_linkage_host: the same from host memory,
+ * compiled from the text of the kernels (csrc/agglo_core.h), files on num_threads host threads.
+ * Refused with 2 before anything runs: a NULL pointer, n_files outside 1 .. 1024, D outside 1 .. 1024, a rows_off
+ * that does not ascend from 0, a workspace that is too small.                                                  */
+long long dz_agglo_work_bytes(int n_files, const int* rows_off);
+int dz_agglo_linkage(dz_ctx* ctx, int n_files, const int* rows_off, const double* d_x, int D, double* d_Z,
+                     int* d_status, void* d_work, long long work_bytes, void* stream);
+int dz_agglo_linkage_host(int n_files, const int* rows_off, const double* x, int D, double* Z, int* status,
+                          int num_threads);
+/* scipy's fcluster(Z, threshold, "distance") over n leaves (a flat cluster is a maximal subtree whose merge heights
+ * are all <= threshold), then the kept clusters: those with at least min_cluster_size leaves, at most max_speakers
+ * of them by size (ties: the one whose first leaf comes first), the largest one when none qualifies; numbered
+ * 0 .. G - 1 by their first leaf.  labels (n): the kept cluster of each leaf, or -1; *n_kept = G.  n = 0: G = 0;
+ * n = 1: one cluster.  2: a NULL pointer, a threshold that is not finite, min_cluster_size or max_speakers below 1,
+ * a Z that is no dendrogram over n leaves.  1 (this entry, dz_offline_assign, dz_offline_reconstruct,
+ * dz_agglo_linkage_host): no memory.                                                                            */
+int dz_agglo_cut(const double* Z, int n, double threshold, int min_cluster_size, int max_speakers, int* labels,
+                 int* n_kept);
+/* x (rows, D) unit rows; train (n_train): the rows that were clustered, labels (n_train): dz_agglo_cut's.  Cluster
+ * g's centroid (centroids (n_kept, D), written) is the mean of its own train rows; assign (rows): the cluster at
+ * the lowest cosine distance 1 - x.c / |c| (ties: the lowest).                                                  */
+int dz_offline_assign(const double* x, int rows, int D, const int* train, const int* labels, int n_train,
+                      int n_kept, int* assign, double* centroids);
+/* The timeline of n_files files from their clustered chunks, files on num_threads host threads.  Per file f:
+ * seg[f] (chunks[f], F, K) scores, assign[f] (chunks[f], K) the cluster of each local speaker or -1, offset[f]
+ * (chunks[f]) the output frame of each chunk's first frame, n_kept[f] clusters, frames[f] output frames ->
+ * active[f] (frames[f], n_kept[f]) bytes.  A chunk with a non-finite score takes no part.  A[t][g] = sum over the
+ * chunks covering t of the max score of the local speakers assigned to g (0: none); count[t] = min(rint(mean over
+ * those chunks of the local speakers above tau_active), G), half to even; g is on at t when it is among the
+ * count[t] largest of A[t] (stable: the lower g first) and A[t][g] > 0.  2: a NULL pointer, a chunk that leaves
+ * the output frames, an assignment outside the clusters.                                                        */
+int dz_offline_reconstruct(int n_files, const float* const* seg, const int* const* assign, const int* const* offset,
+                           const int* chunks, int F, int K, const int* n_kept, double tau_active, const int* frames,
+                           unsigned char* const* active, int num_threads);
+
 /* sizeof() of the five structs that cross this boundary, in declaration order
  * (dz_sincnet_weights, dz_seg_weights, dz_emb_weights, dz_ecapa_weights, dz_convgemm_desc): a
  * binding checks its own mirror of the layouts against the library it loaded.            */
