@@ -20,8 +20,8 @@ void dz_set_error(const char* fmt, ...);
 
 namespace {
 
-// One file's linkage: x (n, D) -> Z (n - 1, 4).  The slots, the selection and the repairs are agglo_merge_kernel's,
-// played by one thread.
+// One file's linkage: x (n, D) -> Z (n - 1, 4).  The distance matrix is built here; the slots, the selection and the
+// repairs are agglo_core.h's merge loop, the text agglo_merge_kernel runs, on a team of one lane.
 int linkage_one(const double* x, int n, int D, double* Z) {
     if (n < 2) return AG_OK;
     std::vector<double> mat((size_t)n * n), nn_val(n);
@@ -50,58 +50,14 @@ int linkage_one(const double* x, int n, int D, double* Z) {
             mat[(size_t)r * n + c] = mat[(size_t)c * n + r] = s;
         }
     }
-    auto scan = [&](int k) {
-        double best = INFINITY;
-        int bidx = AG_NONE;
-        for (int m = k + 1; m < n; ++m)
-            if (active[m]) ag_take(mat[(size_t)k * n + m], m, best, bidx);
-        nn_val[k] = best;
-        nn_idx[k] = bidx == AG_NONE ? -1 : bidx;
-    };
+    const AgSlots s = {nn_val.data(), nn_idx.data(), size.data(), id.data(), active.data(), stale.data(), mat.data(), Z};
     for (int k = 0; k < n; ++k) {
         id[k] = k;
-        scan(k);
+        ag_scan(s, k, n, AgOneLane{});
     }
-    for (int t = 0; t < n - 1; ++t) {
-        double best;
-        int i;
-        for (int tries = 0;; ++tries) {
-            best = INFINITY;
-            i = AG_NONE;
-            for (int k = 0; k < n; ++k) ag_take(nn_val[k], k, best, i);
-            if (i < 0 || i >= n || tries > n) return t;
-            if (!stale[i]) break;
-            scan(i);
-            stale[i] = 0;
-        }
-        const int j = nn_idx[i];
-        if (!ag_pair_ok(i, j, best, n, active.data())) return t;
-        const int ni = size[i], nj = size[j];
-        ag_z_row(Z + (size_t)t * 4, id[i], id[j], best, ni + nj);
-        size[j] = ni + nj;
-        id[j] = n + t;
-        active[i] = 0;
-        nn_val[i] = INFINITY;
-        nn_idx[i] = -1;
-        stale[i] = 0;
-        for (int k = 0; k < n; ++k) {
-            if (k == i || k == j || !active[k]) continue;
-            const double nd = ag_lance_williams(mat[(size_t)i * n + k], mat[(size_t)j * n + k], best, ni, nj);
-            mat[(size_t)j * n + k] = nd;
-            mat[(size_t)k * n + j] = nd;
-            if (k < j) ag_repair(nd, i, j, &nn_val[k], &nn_idx[k], &stale[k]);
-        }
-        scan(j);
-        stale[j] = 0;
-    }
-    return AG_OK;
-}
-
-bool offsets_ok(int n_files, const int* rows_off) {
-    if (rows_off[0] != 0) return false;
-    for (int f = 0; f < n_files; ++f)
-        if (rows_off[f + 1] < rows_off[f]) return false;
-    return true;
+    bool bad = false;
+    const int t = ag_merge_steps(s, n, 0, n - 1, &bad, AgOneLane{});
+    return bad ? t : AG_OK;
 }
 
 }  // namespace
@@ -116,7 +72,7 @@ extern "C" int dz_agglo_linkage_host(int n_files, const int* rows_off, const dou
         dz_set_error("dz_agglo_linkage_host: dimension %d outside [1, %d]", D, AG_DMAX);
         return 2;
     }
-    if (!offsets_ok(n_files, rows_off)) {
+    if (!ag_offsets_ok(n_files, rows_off)) {
         dz_set_error("dz_agglo_linkage_host: rows_off is no ascending list from 0");
         return 2;
     }

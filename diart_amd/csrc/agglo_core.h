@@ -1,6 +1,7 @@
 // Centroid-linkage agglomerative clustering of unit rows, float64: the ONE text of its arithmetic and decisions.
 // k_agglo.hip (the kernels behind dz_agglo_linkage) and agglo.cpp (dz_agglo_linkage_host, backend="core") compile it,
-// so the host and the device round alike and cannot disagree at a tie.  DESIGN.md 4.24.
+// so the host and the device round alike and cannot disagree at a tie: the leaf functions, then the merge loop itself
+// (ag_scan, ag_merge_steps), which both sides run through a team of lanes.  DESIGN.md 4.24.
 //
 // The state of one file of n rows lives in n SLOTS:
 //   mat     (n, n)  squared Euclidean distances between the centroids of the slots' clusters, both halves kept
@@ -88,4 +89,103 @@ AG_HD void ag_repair(double nd, int i, int j, double* nn_val, int* nn_idx, int* 
         *nn_val = nd;
         *nn_idx = j;
     }
+}
+
+// rows_off (n_files + 1): file f owns rows rows_off[f] .. rows_off[f + 1] - 1 -- an ascending list from 0
+AG_HD bool ag_offsets_ok(int n_files, const int* rows_off) {
+    bool ok = rows_off[0] == 0;
+    for (int f = 0; f < n_files; ++f) ok = ok && rows_off[f + 1] >= rows_off[f];
+    return ok;
+}
+
+// The merge loop, run by a TEAM of lanes on the state of one file (above) and its Z:
+struct AgSlots {
+    double* nn_val;
+    int *nn_idx, *size, *id, *active, *stale;
+    double *mat, *z;
+};
+// A team is a policy: lane() of lanes() (lane l takes elements l, l + lanes(), ... of a list; lane 0 writes what one
+// lane writes), barrier(), and lowest(v, idx): the lowest (value, index) of the lanes' pairs, in every lane (it may hold
+// barriers: all lanes call it).  The device's team is a workgroup (k_agglo.hip), the host's is AgOneLane.  They decide
+// alike because `lowest` is a lexicographic minimum -- lower value, then lower index, NaN never wins (ag_take) -- which
+// is exact, associative and commutative: however the list is dealt to the lanes, the result is the pair one lane finds
+// walking it alone.  Everything else is per element k, from values no lane writes in the same phase.  This is the only
+// reason one text can serve both.
+struct AgOneLane {
+    AG_HD int lane() const { return 0; }
+    AG_HD int lanes() const { return 1; }
+    AG_HD void barrier() const {}
+    AG_HD void lowest(double&, int&) const {}
+};
+
+// Row k scanned by the team: its nearest active slot above it, written by lane 0, and the row is exact again.  Call
+// from all lanes; the entry is visible to them after the next barrier.
+template <typename Team>
+AG_HD void ag_scan(const AgSlots& s, int k, int n, Team team) {
+    const double* row = s.mat + (long long)k * n;
+    double best = INFINITY;
+    int bidx = AG_NONE;
+    for (int m = k + 1 + team.lane(); m < n; m += team.lanes())
+        if (s.active[m]) ag_take(row[m], m, best, bidx);
+    team.lowest(best, bidx);
+    if (team.lane() == 0) {
+        s.nn_val[k] = best;
+        s.nn_idx[k] = bidx == AG_NONE ? -1 : bidx;
+        s.stale[k] = 0;
+    }
+}
+
+// Merges t, t + 1, ... of a file of n >= 2 slots: at most nsteps of them, up to the last one (n - 2).  Returns the next
+// merge.  *bad: an index failed its range check at the merge returned, and the file ends there.
+// Every value a branch below depends on is the same in all lanes of the team (read after a barrier from memory that no
+// lane writes before the next one), so every barrier is reached by all of them.
+template <typename Team>
+AG_HD int ag_merge_steps(const AgSlots& s, int n, int t, int nsteps, bool* bad_out, Team team) {
+    const int lane = team.lane(), nl = team.lanes();
+    bool bad = false;
+    for (int it = 0; it < nsteps && t < n - 1; ++it, ++t) {
+        // the lowest (nn_val, i) whose row is exact
+        double dij;
+        int i;
+        for (int tries = 0;; ++tries) {
+            dij = INFINITY;
+            i = AG_NONE;
+            for (int k = lane; k < n; k += nl) ag_take(s.nn_val[k], k, dij, i);
+            team.lowest(dij, i);
+            bad = i < 0 || i >= n || tries > n;
+            if (bad || !s.stale[i]) break;
+            ag_scan(s, i, n, team);
+            team.barrier();
+        }
+        const int j = bad ? -1 : s.nn_idx[i];
+        bad = bad || !ag_pair_ok(i, j, dij, n, s.active);
+        if (bad) break;
+        const int ni = s.size[i], nj = s.size[j], id_i = s.id[i], id_j = s.id[j];
+        team.barrier();                           // everyone has read slot i and j's state
+        if (lane == 0) {
+            ag_z_row(s.z + (long long)t * 4, id_i, id_j, dij, ni + nj);
+            s.size[j] = ni + nj;
+            s.id[j] = n + t;
+            s.active[i] = 0;
+            s.nn_val[i] = INFINITY;
+            s.nn_idx[i] = -1;
+            s.stale[i] = 0;
+        }
+        team.barrier();
+        // Lance-Williams on row and column j, and the entries of the rows below j
+        const double* row_i = s.mat + (long long)i * n;
+        double* row_j = s.mat + (long long)j * n;
+        for (int k = lane; k < n; k += nl) {
+            if (k == i || k == j || !s.active[k]) continue;
+            const double nd = ag_lance_williams(row_i[k], row_j[k], dij, ni, nj);
+            row_j[k] = nd;
+            s.mat[(long long)k * n + j] = nd;
+            if (k < j) ag_repair(nd, i, j, &s.nn_val[k], &s.nn_idx[k], &s.stale[k]);
+        }
+        team.barrier();
+        ag_scan(s, j, n, team);
+        team.barrier();
+    }
+    *bad_out = bad;
+    return t;
 }

@@ -5,9 +5,9 @@
 //                          the rows' terms added in ascending k whatever the tile (one sequential chain per output)
 //   agglo_nn_init_kernel   one wavefront per row: its nearest slot above it, and the slot's initial state
 //   agglo_merge_kernel     ONE workgroup per file runs that file's merges one after another, `nsteps` of them per
-//                          launch, the state in device memory between launches.  A merge is: the lowest (nn_val, i)
-//                          over the list, its row scanned again while it is stale -> the Z row -> Lance-Williams on
-//                          row and column j -> ag_repair on the rows below j -> row j scanned.
+//                          launch, the state in device memory between launches.  The merges are agglo_core.h's
+//                          ag_merge_steps, the loop the host runs too, on the kernel's team (AgBlockTeam: 1 024
+//                          lanes, __syncthreads(), ag_block_min); the kernel keeps the entry checks and the last store.
 // No workgroup waits for another one: a file's merges are ordered inside its own workgroup by __syncthreads(), the
 // launches by the stream.  The host reads nothing back between launches.  There is no atomic of any kind.
 // Every index read from device memory is range-checked before it indexes anything: a failed check ends the file with
@@ -139,88 +139,32 @@ __device__ __forceinline__ void ag_block_min(double& best, int& bidx, double* s_
     __syncthreads();                              // s_val / s_idx are free again
 }
 
-// row k scanned by the whole workgroup: its nearest active slot above it, written by thread 0.  Call from all threads;
-// the entry is visible to them after the next barrier.
-__device__ __forceinline__ void ag_block_scan(const double* row, const int* active, int k, int n,
-                                              double* nn_val, int* nn_idx, int* stale, double* s_val, int* s_idx) {
-    double best = INFINITY;
-    int bidx = AG_NONE;
-    for (int m = k + 1 + (int)threadIdx.x; m < n; m += AG_MERGE_THREADS)
-        if (active[m]) ag_take(row[m], m, best, bidx);
-    ag_block_min(best, bidx, s_val, s_idx);
-    if (threadIdx.x == 0) {
-        nn_val[k] = best;
-        nn_idx[k] = bidx == AG_NONE ? -1 : bidx;
-        stale[k] = 0;
-    }
-}
+// the team of agglo_core.h's merge loop on the device: the workgroup's AG_MERGE_THREADS threads
+struct AgBlockTeam {
+    double* s_val;     // AG_MERGE_WAVES each, LDS
+    int* s_idx;
+    __device__ int lane() const { return (int)threadIdx.x; }
+    __device__ int lanes() const { return AG_MERGE_THREADS; }
+    __device__ void barrier() const { __syncthreads(); }
+    __device__ void lowest(double& v, int& idx) const { ag_block_min(v, idx, s_val, s_idx); }
+};
 
 __global__ __launch_bounds__(AG_MERGE_THREADS) void agglo_merge_kernel(
     const AgFile* __restrict__ files, int* step, double* g_nn_val, int* g_nn_idx,
     int* g_size, int* g_id, int* g_active, int* g_stale,
     double* g_mat, double* g_z, int* status, int nsteps) {
     const AgFile f = files[blockIdx.x];
-    const int n = f.n, tid = threadIdx.x;
+    const int n = f.n;
     if (n < 2 || status[blockIdx.x] != AG_OK) return;          // the whole workgroup
     int t = step[blockIdx.x];
     if (t < 0 || t >= n - 1) return;                           // a finished file does nothing
-    double* nn_val = g_nn_val + f.row0;
-    int* nn_idx = g_nn_idx + f.row0;
-    int* size = g_size + f.row0;
-    int* id = g_id + f.row0;
-    int* active = g_active + f.row0;
-    int* stale = g_stale + f.row0;
-    double* mat = g_mat + f.mat;
-    double* z = g_z + f.z * 4;
+    const AgSlots s = {g_nn_val + f.row0, g_nn_idx + f.row0, g_size + f.row0, g_id + f.row0,
+                       g_active + f.row0, g_stale + f.row0, g_mat + f.mat,    g_z + f.z * 4};
     __shared__ double s_val[AG_MERGE_WAVES];
     __shared__ int s_idx[AG_MERGE_WAVES];
     bool bad = false;
-    // every value a branch below depends on is the same in all threads of the workgroup (read after a barrier from
-    // memory that no thread writes before the next one), so every barrier is reached by all of them
-    for (int it = 0; it < nsteps && t < n - 1; ++it, ++t) {
-        // the lowest (nn_val, i) whose row is exact
-        double dij;
-        int i;
-        for (int tries = 0;; ++tries) {
-            dij = INFINITY;
-            i = AG_NONE;
-            for (int k = tid; k < n; k += AG_MERGE_THREADS) ag_take(nn_val[k], k, dij, i);
-            ag_block_min(dij, i, s_val, s_idx);
-            bad = i < 0 || i >= n || tries > n;
-            if (bad || !stale[i]) break;
-            ag_block_scan(mat + (long long)i * n, active, i, n, nn_val, nn_idx, stale, s_val, s_idx);
-            __syncthreads();
-        }
-        const int j = bad ? -1 : nn_idx[i];
-        bad = bad || !ag_pair_ok(i, j, dij, n, active);
-        if (bad) break;
-        const int ni = size[i], nj = size[j], id_i = id[i], id_j = id[j];
-        __syncthreads();                          // everyone has read slot i and j's state
-        if (tid == 0) {
-            ag_z_row(z + (long long)t * 4, id_i, id_j, dij, ni + nj);
-            size[j] = ni + nj;
-            id[j] = n + t;
-            active[i] = 0;
-            nn_val[i] = INFINITY;
-            nn_idx[i] = -1;
-            stale[i] = 0;
-        }
-        __syncthreads();
-        // Lance-Williams on row and column j, and the entries of the rows below j
-        const double* row_i = mat + (long long)i * n;
-        double* row_j = mat + (long long)j * n;
-        for (int k = tid; k < n; k += AG_MERGE_THREADS) {
-            if (k == i || k == j || !active[k]) continue;
-            const double nd = ag_lance_williams(row_i[k], row_j[k], dij, ni, nj);
-            row_j[k] = nd;
-            mat[(long long)k * n + j] = nd;
-            if (k < j) ag_repair(nd, i, j, &nn_val[k], &nn_idx[k], &stale[k]);
-        }
-        __syncthreads();
-        ag_block_scan(row_j, active, j, n, nn_val, nn_idx, stale, s_val, s_idx);
-        __syncthreads();
-    }
-    if (tid == 0) {
+    t = ag_merge_steps(s, n, t, nsteps, &bad, AgBlockTeam{s_val, s_idx});
+    if (threadIdx.x == 0) {
         step[blockIdx.x] = t;
         if (bad) status[blockIdx.x] = t;
     }
@@ -232,11 +176,10 @@ struct AgLayout {
 
 // the workspace of a call; false when rows_off is no ascending list from 0
 bool ag_layout(int n_files, const int* rows_off, AgLayout& L, std::vector<AgFile>* desc) {
-    if (rows_off[0] != 0) return false;
+    if (!ag_offsets_ok(n_files, rows_off)) return false;
     long long mat = 0, z = 0;
     for (int f = 0; f < n_files; ++f) {
         const long long n = (long long)rows_off[f + 1] - rows_off[f];
-        if (n < 0) return false;
         if (desc) desc->push_back(AgFile{mat, z, rows_off[f], (int)n});
         mat += n * n;
         z += n > 1 ? n - 1 : 0;

@@ -242,6 +242,33 @@ def e_bits(stats, e):
     return stats[0][e].tobytes() + stats[1][e].tobytes()
 
 
+# ------------------------------------------------------------------------- the two tile kernels give the same d
+@pytest.mark.parametrize("aligned", [True, False])
+@pytest.mark.parametrize("D", [64, 192])
+def test_cohort_tile_and_gallery_tile_give_the_same_d(gpu, D, aligned):
+    """A cohort equal to the gallery's own voiceprints, top_n = 1: a row's cohort mean is the float64 mean of its ONE
+    smallest distance to a member, a division by 1.0 that rounds back to the same float32, so it must be the row's
+    smallest raw distance to a voiceprint bit for bit.  The first comes from ``cohort_tile_kernel``'s distances, the
+    second from ``gallery_tile_kernel``'s fold: the two copies of the tile's loop must leave the same accumulator bits,
+    which is what 4.20's error bound and determinism argument rest on.  E = M = 129 (two gallery tiles, the second with
+    one member), R = 65 (two row tiles, the second with one row), the aligned and the single-float loads, one unusable
+    row."""
+    E = 129
+    x, g, _, _, _ = case(D, 129)
+    x, g = x.clone(), g[:E]
+    x[3] = 0.0                                                         # of zero norm: NaN on both sides
+    gallery = SpeakerGallery(names_of(E), g, gpu, cohort=g, top_n=1)
+    dx = x.to(gpu) if aligned else strided(x.to(gpu), gpu, pad=3, offset=1)
+    assert (dx.data_ptr() % 16 == 0 and dx.stride(0) % 4 == 0) == aligned
+    mean = gallery.cohort_stats(dx)[0].cpu().numpy()
+    dist = gallery.match(dx)[1].cpu().numpy()
+    assert mean.dtype == dist.dtype == np.float32 and mean.shape == dist.shape == (R,)
+    assert np.isnan(mean[3]) and np.isnan(dist[3])
+    usable = np.arange(R) != 3
+    assert np.isfinite(mean[usable]).all() and np.isfinite(dist[usable]).all()
+    assert np.array_equal(mean.view(np.uint32), dist.view(np.uint32))
+
+
 # -------------------------------------------------------------------------------------------------------- unusable rows
 def test_unusable_rows_get_nan_and_touch_nobody(gpu):
     x, g, c, _, _ = case(64, 129)
