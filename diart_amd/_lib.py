@@ -116,6 +116,13 @@ class TuneDesc(C.Structure):
         (n, C.c_int) for n in ("N", "F", "K", "D", "G", "nwin", "total_chunks", "total_rows")]
 
 
+class TuneCells(C.Structure):
+    POINTERS = ("file_chunk_off", "file_row_off", "row_off", "step_rows", "mids", "mid_cell", "file_cell_off", "cell_dur",
+                "cell_ref", "cell_step", "dur_prefix", "ref_prefix")
+    _fields_ = [(n, vp) for n in POINTERS] + [
+        (n, C.c_int) for n in ("n_files", "total_rows", "total_chunks", "max_cells", "max_speakers")] + [("collar", C.c_double)]
+
+
 # name -> (restype, argtypes); must list every function of include/diart_amd.h
 SIGNATURES = {
     "dz_last_error": (C.c_char_p, []),
@@ -252,46 +259,24 @@ SIGNATURES = {
     "dz_tune_replay": (C.c_int, [vp, C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     "dz_tune_replay_host": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp,
                                       C.c_int, C.c_int]),
-    "dz_tune_score": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp,
-                                C.c_int]),
-    "dz_tune_score_gpu": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int,
-                                    C.c_double, vp, vp, C.c_int, vp, vp]),
-    "dz_tune_score_core": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double,
-                                     C.c_int, C.c_int, vp, C.c_int]),
+    "dz_tune_cells_abi_size": (C.c_int, []),
+    "dz_tune_score": (C.c_int, [C.POINTER(TuneCells), C.c_int, vp, vp, C.c_int]),
+    "dz_tune_score_gpu": (C.c_int, [vp, C.POINTER(TuneCells), C.c_int, vp, vp, vp, C.c_int, vp, vp]),
+    "dz_tune_score_core": (C.c_int, [C.POINTER(TuneCells), C.c_int, vp, C.c_int, C.c_int, vp, C.c_int]),
     "dz_tune_vad_rows": (C.c_int, [vp, C.POINTER(TuneDesc), vp, vp]),
-    "dz_tune_vad_score": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp,
-                                    vp]),
-    "dz_tune_vad_host": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp,
+    "dz_tune_vad_score": (C.c_int, [vp, C.POINTER(TuneCells), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "dz_tune_vad_host": (C.c_int, [C.POINTER(TuneDesc), C.POINTER(TuneCells), C.c_int, vp, C.c_int, vp, vp, C.c_int, vp,
                                    C.c_int]),
-    "dz_tune_vad_score_hyst": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp,
-                                         vp, vp]),
-    "dz_tune_vad_host_hyst": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int,
-                                        vp, C.c_int]),
-    "dz_tune_vad_score_dur": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp,
-                                        vp, vp]),
-    "dz_tune_vad_host_dur": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int,
-                                       vp, C.c_int]),
-    "dz_tune_track_score_dur": (C.c_int, [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp,
-                                          C.c_int]),
+    "dz_tune_track_score_dur": (C.c_int, [C.POINTER(TuneCells), C.c_int, vp, vp, vp, C.c_int]),
     "dz_tune_vad_replay_tails": (C.c_int, [C.POINTER(TuneDesc), vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.c_int]),
-    "dz_tune_name": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                               C.c_int, vp]),
-    "dz_tune_name_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                    C.c_int]),
-    "dz_tune_ident_score": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                      C.c_int, C.c_double, vp, C.c_int]),
-    "dz_tune_ident_score_gpu": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
-                                          C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, vp, vp]),
-    "dz_tune_ident_score_core": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
-                                           C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, C.c_int]),
-    "dz_tune_name_sweep": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
-                                     vp, vp, vp, vp, vp, vp, C.c_int, vp]),
-    "dz_tune_name_sweep_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp,
-                                          vp, vp, vp, vp, vp, vp, C.c_int]),
-    "dz_tune_ident_score_sweep_gpu": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
-                                                vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int, vp, vp]),
-    "dz_tune_ident_score_sweep_core": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
-                                                 vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, C.c_int]),
+    # (the naming entries score nothing and take no dz_tune_cells: their arrays are a trial's, loose as in the header)
+    "dz_tune_name": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp, C.c_int, vp]),
+    "dz_tune_name_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, C.c_int]),
+    "dz_tune_ident_score": (C.c_int, [C.POINTER(TuneCells), C.c_int, vp, vp, vp, C.c_int]),
+    "dz_tune_ident_score_gpu": (C.c_int, [vp, C.POINTER(TuneCells), C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]),
+    "dz_tune_ident_score_core": (C.c_int, [C.POINTER(TuneCells), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int]),
     "dz_agglo_work_bytes": (C.c_longlong, [C.c_int, vp]),
     "dz_agglo_linkage": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_longlong, vp]),
     "dz_agglo_linkage_host": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int]),
@@ -408,10 +393,11 @@ def load() -> C.CDLL:
             raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: struct sizes "
                                 f"{list(sizes)} (library) vs {mine} (this binding); rebuild it")
         for name, struct in (("dz_wsp", WspWeights), ("dz_sbx", SbxWeights), ("dz_ttn", TtnWeights),
-                             ("dz_sbr", SbrWeights), ("dz_ecm", EcmWeights), ("dz_tune", TuneDesc)):
+                             ("dz_sbr", SbrWeights), ("dz_ecm", EcmWeights), ("dz_tune", TuneDesc),
+                             ("dz_tune_cells", TuneCells)):
             size = getattr(lib, f"{name}_abi_size")()
             if size != C.sizeof(struct):
-                what = "dz_tune_desc" if struct is TuneDesc else f"{name}_weights"
+                what = {TuneDesc: "dz_tune_desc", TuneCells: "dz_tune_cells"}.get(struct, f"{name}_weights")
                 raise DiartAmdError(f"{_LIB_PATH} was built from a different include/diart_amd.h: sizeof({what}) "
                                     f"{size} (library) vs {C.sizeof(struct)} (this binding); rebuild it")
         _lib = lib

@@ -1,4 +1,4 @@
-// Tuning delta_id by replay (dz_tune_name, dz_tune_ident_score_gpu and their sweeps): the names
+// Tuning delta_id by replay (dz_tune_name and dz_tune_ident_score_gpu): the names
 // a gallery gives the global speakers of every trial, and the identification error rate of every (trial, file) pair,
 // from the assignments and masks that dz_tune_replay left on the device -- at one (plane, threshold) point per trial, or
 // at up to 256 of them for the price of one clustering replay.
@@ -16,7 +16,7 @@
 //                             that owns it, popcounts, five sums per lane added in lane order by lane 0.  No assignment
 //                             problem, no co-occurrence sweep, 15 KB of LDS.
 //
-// The one-point entries are the sweep's with points = planes = 1: one text.  Both kernels are latency-sized (a chain is
+// One point is points = planes = 1 of the same entries.  Both kernels are latency-sized (a chain is
 // a dependent walk; a pair is a few thousand cells).  Vector stores only, no floating-point atomics: two calls give
 // the same doubles.  The arithmetic is tune_ident_core.h's, which the host compiles too.  No contraction, as in
 // k_tune.hip.
@@ -86,23 +86,23 @@ __global__ __launch_bounds__(TC_SCORE_LANES) void tune_ident_score_kernel(
 
 }  // namespace
 
-extern "C" int dz_tune_name_sweep(dz_ctx* ctx, int trials, int points, int planes, int n_files, int total_chunks,
+extern "C" int dz_tune_name(dz_ctx* ctx, int trials, int points, int planes, int n_files, int total_chunks,
                                   int k_local, int max_speakers, int voiceprints, const int* d_file_chunk_off,
                                   const signed char* d_assign, const int* d_status, const int* d_match_index,
                                   const float* d_match_distance, const signed char* d_vp_ref, const double* d_delta_id,
                                   signed char* d_ident, int* d_hold, int name_blocks, void* stream) {
     DZ_REQUIRE(ctx && d_file_chunk_off && d_assign && d_status && d_match_index && d_match_distance && d_vp_ref &&
-                   d_delta_id && d_ident, "dz_tune_name_sweep: NULL argument");
+                   d_delta_id && d_ident, "dz_tune_name: NULL argument");
     DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_chunks >= n_files && k_local >= 1 && k_local <= TC_KMAX &&
                    max_speakers >= 1 && max_speakers <= TC_GMAX && voiceprints >= 1 && name_blocks >= 1,
-               "dz_tune_name_sweep: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at most %d / "
+               "dz_tune_name: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at most %d / "
                "%d), %d voiceprints, %d workgroups)",
                trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints, name_blocks);
     DZ_REQUIRE(points >= 1 && points <= TI_MAX_POINTS && planes >= 1 && planes <= TI_MAX_PLANES && points % planes == 0,
-               "dz_tune_name_sweep: %d points (1 .. %d) in %d planes (1 .. %d, a divisor of the points)", points,
+               "dz_tune_name: %d points (1 .. %d) in %d planes (1 .. %d, a divisor of the points)", points,
                TI_MAX_POINTS, planes, TI_MAX_PLANES);
     const long long chains = (long long)trials * points * n_files;
-    DZ_REQUIRE(chains < (1ll << 31), "dz_tune_name_sweep: %lld chains in one call; evaluate fewer trials per batch", chains);
+    DZ_REQUIRE(chains < (1ll << 31), "dz_tune_name: %lld chains in one call; evaluate fewer trials per batch", chains);
     DZ_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)(chains < name_blocks ? chains : name_blocks);
@@ -113,69 +113,29 @@ extern "C" int dz_tune_name_sweep(dz_ctx* ctx, int trials, int points, int plane
     return 0;
 }
 
-extern "C" int dz_tune_name(dz_ctx* ctx, int trials, int n_files, int total_chunks, int k_local, int max_speakers,
-                            int voiceprints, const int* d_file_chunk_off, const signed char* d_assign, const int* d_status,
-                            const int* d_match_index, const float* d_match_distance, const signed char* d_vp_ref,
-                            const double* d_delta_id, signed char* d_ident, int* d_hold, int name_blocks, void* stream) {
-    DZ_REQUIRE(ctx && d_file_chunk_off && d_assign && d_status && d_match_index && d_match_distance && d_vp_ref &&
-                   d_delta_id && d_ident, "dz_tune_name: NULL argument");
-    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_chunks >= n_files && k_local >= 1 && k_local <= TC_KMAX &&
-                   max_speakers >= 1 && max_speakers <= TC_GMAX && voiceprints >= 1 && name_blocks >= 1,
-               "dz_tune_name: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at most %d / %d), "
-               "%d voiceprints, %d workgroups)",
-               trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints, name_blocks);
-    return dz_tune_name_sweep(ctx, trials, 1, 1, n_files, total_chunks, k_local, max_speakers, voiceprints, d_file_chunk_off,
-                              d_assign, d_status, d_match_index, d_match_distance, d_vp_ref, d_delta_id, d_ident, d_hold,
-                              name_blocks, stream);
-}
-
-extern "C" int dz_tune_ident_score_sweep_gpu(dz_ctx* ctx, int trials, int points, int n_files, const unsigned* d_bits,
-                                             const signed char* d_ident, int total_rows, int total_chunks,
-                                             const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                                             const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
-                                             const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
-                                             int max_speakers, double collar, double* d_out, unsigned* d_scratch,
-                                             int score_blocks, int* d_err, void* stream) {
-    DZ_REQUIRE(ctx && d_bits && d_ident && d_file_chunk_off && d_row_off && d_mids && d_mid_cell && d_file_cell_off &&
-                   d_cell_dur && d_cell_ref && d_cell_step && d_out && d_scratch && d_err,
-               "dz_tune_ident_score_sweep_gpu: NULL argument");
-    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_rows >= 1 && total_chunks >= n_files && max_cells >= 0 &&
-                   score_blocks >= 1 && max_speakers >= 1 && max_speakers <= TC_GMAX,
-               "dz_tune_ident_score_sweep_gpu: bad arguments (%d trials, %d files, %d rows, %d chunks, %d cells per slice, %d "
+extern "C" int dz_tune_ident_score_gpu(dz_ctx* ctx, const dz_tune_cells* d_cells, int trials, int points,
+                                       const unsigned* d_bits, const signed char* d_ident, double* d_out,
+                                       unsigned* d_scratch, int score_blocks, int* d_err, void* stream) {
+    const char* missing = tc_cells_missing(d_cells, TC_CELLS_KERNEL | TC_CELLS_CELL_STEP);
+    DZ_REQUIRE(!missing && ctx && d_bits && d_ident && d_out && d_scratch && d_err,
+               "dz_tune_ident_score_gpu: NULL argument (%s)", missing ? missing : "an array of the call");
+    const dz_tune_cells& c = *d_cells;
+    DZ_REQUIRE(trials >= 1 && c.n_files >= 1 && c.total_rows >= 1 && c.total_chunks >= c.n_files && c.max_cells >= 0 &&
+                   score_blocks >= 1 && c.max_speakers >= 1 && c.max_speakers <= TC_GMAX,
+               "dz_tune_ident_score_gpu: bad arguments (%d trials, %d files, %d rows, %d chunks, %d cells per slice, %d "
                "slices, %d speakers (at most %d))",
-               trials, n_files, total_rows, total_chunks, max_cells, score_blocks, max_speakers, TC_GMAX);
-    DZ_REQUIRE(points >= 1 && points <= TI_MAX_POINTS, "dz_tune_ident_score_sweep_gpu: %d points (1 .. %d)", points,
-               TI_MAX_POINTS);
-    const long long pairs = (long long)trials * n_files;
+               trials, c.n_files, c.total_rows, c.total_chunks, c.max_cells, score_blocks, c.max_speakers, TC_GMAX);
+    DZ_REQUIRE(points >= 1 && points <= TI_MAX_POINTS, "dz_tune_ident_score_gpu: %d points (1 .. %d)", points, TI_MAX_POINTS);
+    const long long pairs = (long long)trials * c.n_files;
     DZ_REQUIRE(pairs * points < (1ll << 31),
-               "dz_tune_ident_score_sweep_gpu: %lld pairs x %d points in one call; evaluate fewer trials per batch", pairs, points);
+               "dz_tune_ident_score_gpu: %lld pairs x %d points in one call; evaluate fewer trials per batch", pairs, points);
     DZ_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     DZ_HIP(hipMemsetAsync(d_err, 0, sizeof(int), st));
     const int grid = (int)(pairs < score_blocks ? pairs : score_blocks);
-    DZ_LAUNCH(tune_ident_score_kernel, dim3(grid), dim3(TC_SCORE_LANES), 0, st, d_bits, d_ident, trials, points, n_files,
-              total_rows, total_chunks, d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_cell_dur, d_cell_ref,
-              d_cell_step, max_cells, max_speakers, collar, d_out, d_scratch, d_err);
+    DZ_LAUNCH(tune_ident_score_kernel, dim3(grid), dim3(TC_SCORE_LANES), 0, st, d_bits, d_ident, trials, points, c.n_files,
+              c.total_rows, c.total_chunks, c.file_chunk_off, c.row_off, c.mids, c.mid_cell, c.file_cell_off, c.cell_dur,
+              c.cell_ref, c.cell_step, c.max_cells, c.max_speakers, c.collar, d_out, d_scratch, d_err);
     DZ_HIP(hipGetLastError());
     return 0;
-}
-
-extern "C" int dz_tune_ident_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits,
-                                       const signed char* d_ident, int total_rows, int total_chunks,
-                                       const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                                       const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
-                                       const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
-                                       int max_speakers, double collar, double* d_out, unsigned* d_scratch, int score_blocks,
-                                       int* d_err, void* stream) {
-    DZ_REQUIRE(ctx && d_bits && d_ident && d_file_chunk_off && d_row_off && d_mids && d_mid_cell && d_file_cell_off &&
-                   d_cell_dur && d_cell_ref && d_cell_step && d_out && d_scratch && d_err,
-               "dz_tune_ident_score_gpu: NULL argument");
-    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_rows >= 1 && total_chunks >= n_files && max_cells >= 0 &&
-                   score_blocks >= 1 && max_speakers >= 1 && max_speakers <= TC_GMAX,
-               "dz_tune_ident_score_gpu: bad arguments (%d trials, %d files, %d rows, %d chunks, %d cells per slice, %d slices, "
-               "%d speakers (at most %d))",
-               trials, n_files, total_rows, total_chunks, max_cells, score_blocks, max_speakers, TC_GMAX);
-    return dz_tune_ident_score_sweep_gpu(ctx, trials, 1, n_files, d_bits, d_ident, total_rows, total_chunks, d_file_chunk_off,
-                                         d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_cell_dur, d_cell_ref, d_cell_step,
-                                         max_cells, max_speakers, collar, d_out, d_scratch, score_blocks, d_err, stream);
 }

@@ -39,26 +39,25 @@ __global__ __launch_bounds__(TC_SCORE_LANES) void tune_score_kernel(
 
 }  // namespace
 
-extern "C" int dz_tune_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits, int total_rows,
-                                 const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                                 const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
-                                 const unsigned long long* d_cell_ref, int max_cells, int max_speakers, double collar,
+extern "C" int dz_tune_score_gpu(dz_ctx* ctx, const dz_tune_cells* d_cells, int trials, const unsigned* d_bits,
                                  double* d_out, unsigned* d_scratch, int score_blocks, int* d_err, void* stream) {
-    DZ_REQUIRE(ctx && d_bits && d_file_chunk_off && d_row_off && d_mids && d_mid_cell && d_file_cell_off && d_cell_dur &&
-                   d_cell_ref && d_out && d_scratch && d_err, "dz_tune_score_gpu: NULL argument");
-    DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_rows >= 1 && max_cells >= 0 && score_blocks >= 1 && max_speakers >= 1 &&
-                   max_speakers <= TC_GMAX,
+    const char* missing = tc_cells_missing(d_cells, TC_CELLS_KERNEL);
+    DZ_REQUIRE(!missing && ctx && d_bits && d_out && d_scratch && d_err, "dz_tune_score_gpu: NULL argument (%s)",
+               missing ? missing : "an array of the call");
+    const dz_tune_cells& c = *d_cells;
+    DZ_REQUIRE(trials >= 1 && c.n_files >= 1 && c.total_rows >= 1 && c.max_cells >= 0 && score_blocks >= 1 &&
+                   c.max_speakers >= 1 && c.max_speakers <= TC_GMAX,
                "dz_tune_score_gpu: bad arguments (%d trials, %d files, %d rows, %d cells per slice, %d slices, %d speakers)",
-               trials, n_files, total_rows, max_cells, score_blocks, max_speakers);
-    const long long pairs = (long long)trials * n_files;
+               trials, c.n_files, c.total_rows, c.max_cells, score_blocks, c.max_speakers);
+    const long long pairs = (long long)trials * c.n_files;
     DZ_REQUIRE(pairs < (1ll << 31), "dz_tune_score_gpu: %lld pairs in one call; evaluate fewer trials per batch", pairs);
     DZ_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     DZ_HIP(hipMemsetAsync(d_err, 0, sizeof(int), st));
     const int grid = (int)(pairs < score_blocks ? pairs : score_blocks);
-    DZ_LAUNCH(tune_score_kernel, dim3(grid), dim3(TC_SCORE_LANES), 0, st, d_bits, trials, n_files, total_rows,
-              d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_cell_dur, d_cell_ref, max_cells, max_speakers,
-              collar, d_out, d_scratch, d_err);
+    DZ_LAUNCH(tune_score_kernel, dim3(grid), dim3(TC_SCORE_LANES), 0, st, d_bits, trials, c.n_files, c.total_rows,
+              c.file_chunk_off, c.row_off, c.mids, c.mid_cell, c.file_cell_off, c.cell_dur, c.cell_ref, c.max_cells,
+              c.max_speakers, c.collar, d_out, d_scratch, d_err);
     DZ_HIP(hipGetLastError());
     return 0;
 }

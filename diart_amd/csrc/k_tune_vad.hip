@@ -27,9 +27,7 @@
 //   tune_vad_bits_kernel          one thread per (trial, row): agg > tau as the uint32 masks of the diarization replay
 //                                 (VadTuneCache.replay with taus (T,); the tests compare them with the host's)
 //
-// The arithmetic is tune_core.h's, which the host compiles too (dz_tune_vad_host, dz_tune_vad_host_hyst,
-// dz_tune_vad_host_dur).  No
-// contraction, as in k_tune.hip.
+// The arithmetic is tune_core.h's, which the host compiles too (dz_tune_vad_host).  No contraction, as in k_tune.hip.
 #pragma clang fp contract(off)
 #include "dz_common.h"
 #define TC_KERNEL_UNIT 1   // tune_core.h: TcDeviceLanes
@@ -74,15 +72,17 @@ __global__ __launch_bounds__(TC_TRACK_LANES) void tune_vad_score_kernel(
                   Rule::stateful && bits ? bits + (size_t)t * total_rows : nullptr, TcDeviceLanes{TC_TRACK_LANES});
 }
 
-// What dz_tune_vad_score, dz_tune_vad_score_hyst and dz_tune_vad_score_dur (`name`) share: the checks and the launches.  The stateful rule
-// takes its masks from the pair kernel; the stateless one keeps them one thread per (trial, row).
+// The checks and the launches of dz_tune_vad_score under one rule.  The stateful rules take their masks from the pair
+// kernel; the stateless one keeps them one thread per (trial, row).
 template <typename Rule>
-int track_score(const char* name, dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                const double* d_taus, const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                const int* d_mid_cell, const int* d_file_cell_off, const double* d_dur_prefix, const double* d_ref_prefix,
-                double collar, double* d_out, unsigned* d_bits, void* stream) {
-    DZ_REQUIRE(ctx && d_agg && d_taus && d_file_chunk_off && d_row_off && d_mids && d_mid_cell && d_file_cell_off &&
-                   d_dur_prefix && d_ref_prefix && (d_out || d_bits), "%s: NULL argument", name);
+int track_score(dz_ctx* ctx, const dz_tune_cells* d_cells, int trials, const double* d_agg, const double* d_taus,
+                double* d_out, unsigned* d_bits, void* stream) {
+    const char* name = "dz_tune_vad_score";
+    const char* missing = tc_cells_missing(d_cells, TC_CELLS_TRACK);
+    DZ_REQUIRE(!missing && ctx && d_agg && d_taus && (d_out || d_bits), "%s: NULL argument (%s)", name,
+               missing ? missing : "an array of the call");
+    const dz_tune_cells& c = *d_cells;
+    const int n_files = c.n_files, total_rows = c.total_rows;
     DZ_REQUIRE(trials >= 1 && n_files >= 1 && total_rows >= 1, "%s: empty shape (%d trials, %d files, %d rows)", name, trials,
                n_files, total_rows);
     const long long pairs = (long long)trials * n_files, rows = (long long)trials * total_rows;
@@ -96,8 +96,8 @@ int track_score(const char* name, dz_ctx* ctx, int trials, int n_files, int tota
     hipStream_t st = (hipStream_t)stream;
     if (d_out || pair_bits) {
         DZ_LAUNCH(tune_vad_score_kernel<Rule>, dim3((unsigned)pairs), dim3(TC_TRACK_LANES), 0, st, d_agg, d_taus, n_files,
-                  total_rows, d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix, d_ref_prefix,
-                  collar, d_out, pair_bits);
+                  total_rows, c.file_chunk_off, c.row_off, c.mids, c.mid_cell, c.file_cell_off, c.dur_prefix, c.ref_prefix,
+                  c.collar, d_out, pair_bits);
         DZ_HIP(hipGetLastError());
     }
     if (d_bits && !pair_bits) {
@@ -125,44 +125,27 @@ extern "C" int dz_tune_vad_rows(dz_ctx* ctx, const dz_tune_desc* d, double* d_ag
     return 0;
 }
 
-extern "C" int dz_tune_vad_score(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                                 const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
-                                 const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
-                                 const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
-                                 unsigned* d_bits, void* stream) {
-    return track_score<TcPlainRule>("dz_tune_vad_score", ctx, trials, n_files, total_rows, d_agg, d_taus, d_file_chunk_off,
-                                    d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix, d_ref_prefix, collar, d_out,
-                                    d_bits, stream);
-}
-
-// With hysteresis: d_taus (T, 2) = (tau_active, tau_offset) per trial; everything else is dz_tune_vad_score's.
-extern "C" int dz_tune_vad_score_hyst(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                                      const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
-                                      const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
-                                      const double* d_dur_prefix, const double* d_ref_prefix, double collar,
-                                      double* d_out, unsigned* d_bits, void* stream) {
-    return track_score<TcHystRule>("dz_tune_vad_score_hyst", ctx, trials, n_files, total_rows, d_agg, d_taus,
-                                   d_file_chunk_off, d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix, d_ref_prefix,
-                                   collar, d_out, d_bits, stream);
-}
-
-// With minimum durations: d_taus (T, 4) = (tau_active, tau_offset, min_duration_on, min_duration_off)
-// per trial, and `taus` the same values in host memory: the device form cannot read d_taus, and a duration that is
-// negative or not finite is refused here, before the device is touched.  Everything else is dz_tune_vad_score_hyst's.
-extern "C" int dz_tune_vad_score_dur(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                                     const double* taus, const double* d_taus, const int* d_file_chunk_off,
-                                     const int* d_row_off, const double* d_mids, const int* d_mid_cell,
-                                     const int* d_file_cell_off, const double* d_dur_prefix, const double* d_ref_prefix,
-                                     double collar, double* d_out, unsigned* d_bits, void* stream) {
-    DZ_REQUIRE(taus, "dz_tune_vad_score_dur: NULL argument");
-    DZ_REQUIRE(trials >= 1, "dz_tune_vad_score_dur: empty shape (%d trials)", trials);
+// `cols`, the columns of d_taus, selects the rule.  With minimum durations (cols = 4) `taus_host` holds
+// the same trials in host memory: the device form cannot read d_taus, and a duration that is negative or not finite is
+// refused here, before the context, the descriptor or any device pointer is looked at.
+extern "C" int dz_tune_vad_score(dz_ctx* ctx, const dz_tune_cells* d_cells, int cols, int trials, const double* d_agg,
+                                 const double* taus_host, const double* d_taus, double* d_out, unsigned* d_bits,
+                                 void* stream) {
+    switch (cols) {
+        case 1: return track_score<TcPlainRule>(ctx, d_cells, trials, d_agg, d_taus, d_out, d_bits, stream);
+        case 2: return track_score<TcHystRule>(ctx, d_cells, trials, d_agg, d_taus, d_out, d_bits, stream);
+        case 4: break;
+        default:
+            DZ_REQUIRE(false, "dz_tune_vad_score: taus of %d columns (1: tau_active; 2: and tau_offset; 4: and the two minimum "
+                              "durations)", cols);
+    }
+    DZ_REQUIRE(taus_host, "dz_tune_vad_score: NULL argument (taus_host, which 4 columns need)");
+    DZ_REQUIRE(trials >= 1, "dz_tune_vad_score: empty shape (%d trials)", trials);
     for (int t = 0; t < trials; ++t)
         for (int k = 2; k < 4; ++k) {
-            const double v = taus[4 * (size_t)t + k];
-            DZ_REQUIRE(v >= 0.0 && v <= 1.7976931348623157e308, "dz_tune_vad_score_dur: %s of trial %d is %g, not a finite number >= 0",
+            const double v = taus_host[4 * (size_t)t + k];
+            DZ_REQUIRE(v >= 0.0 && v <= 1.7976931348623157e308, "dz_tune_vad_score: %s of trial %d is %g, not a finite number >= 0",
                        k == 2 ? "min_duration_on" : "min_duration_off", t, v);
         }
-    return track_score<TcDurRule>("dz_tune_vad_score_dur", ctx, trials, n_files, total_rows, d_agg, d_taus, d_file_chunk_off,
-                                  d_row_off, d_mids, d_mid_cell, d_file_cell_off, d_dur_prefix, d_ref_prefix, collar, d_out,
-                                  d_bits, stream);
+    return track_score<TcDurRule>(ctx, d_cells, trials, d_agg, d_taus, d_out, d_bits, stream);
 }

@@ -8,7 +8,7 @@
 // compile this text: k_tune.hip for the kernels, tune_score.cpp for backend="core", which tests/test_tune_host.py
 // holds against dz_clu_step + dz_tail_step.  The track pipelines' half (tc_vad_row and tc_track_pair<Rule>, behind the
 // replay: one pair routine for the single threshold and for hysteresis, whose lanes' state maps are DESIGN.md 4.21) is
-// k_tune_vad.hip's and dz_tune_vad_host's / dz_tune_vad_host_hyst's in the same way, and the scoring of the diarization
+// k_tune_vad.hip's and dz_tune_vad_host's in the same way, and the scoring of the diarization
 // masks (tc_score_*, at the end) is k_tune_score.hip's and dz_tune_score_core's.  Three things are said once for all
 // of them: how lanes share a range (tc_lane_steps), how workgroups share the pairs of a scoring call (tc_score_pairs),
 // and what a phase over the lanes is on the device (TcDeviceLanes; the host's LanesInTurn is tune_score.cpp's).
@@ -690,6 +690,37 @@ TC_HD void tc_score_pairs(const TcScoreCall& c, int block, int blocks, bool rais
                               c.cell_ref + cell0, c.file_chunk_off[n], c.file_chunk_off[n + 1], ncell, c.max_speakers, c.collar};
         score(pair, t, cell0, in);
     }
+}
+
+// dz_tune_cells, the geometry as it crosses the C boundary (host side of every entry, device pointers or host ones).
+// The members an entry reads, one bit per pointer in declaration order, and the sets that several entries share.
+enum : unsigned {
+    TC_CELLS_FILE_CHUNK_OFF = 1u << 0, TC_CELLS_FILE_ROW_OFF = 1u << 1, TC_CELLS_ROW_OFF = 1u << 2,
+    TC_CELLS_STEP_ROWS = 1u << 3, TC_CELLS_MIDS = 1u << 4, TC_CELLS_MID_CELL = 1u << 5, TC_CELLS_FILE_CELL_OFF = 1u << 6,
+    TC_CELLS_CELL_DUR = 1u << 7, TC_CELLS_CELL_REF = 1u << 8, TC_CELLS_CELL_STEP = 1u << 9, TC_CELLS_DUR_PREFIX = 1u << 10,
+    TC_CELLS_REF_PREFIX = 1u << 11,
+    TC_CELLS_GRID = TC_CELLS_MIDS | TC_CELLS_MID_CELL | TC_CELLS_FILE_CELL_OFF,
+    TC_CELLS_REFERENCE = TC_CELLS_CELL_DUR | TC_CELLS_CELL_REF,
+    TC_CELLS_SEQUENTIAL = TC_CELLS_FILE_ROW_OFF | TC_CELLS_FILE_CHUNK_OFF | TC_CELLS_STEP_ROWS | TC_CELLS_GRID | TC_CELLS_REFERENCE,
+    TC_CELLS_KERNEL = TC_CELLS_FILE_CHUNK_OFF | TC_CELLS_ROW_OFF | TC_CELLS_GRID | TC_CELLS_REFERENCE,
+    TC_CELLS_TRACK_PAIR = TC_CELLS_GRID | TC_CELLS_DUR_PREFIX | TC_CELLS_REF_PREFIX,
+    TC_CELLS_TRACK = TC_CELLS_FILE_CHUNK_OFF | TC_CELLS_ROW_OFF | TC_CELLS_TRACK_PAIR,
+};
+// The first of the `need`ed members that is NULL, by name (the descriptor itself when there is none), or nullptr.
+inline const char* tc_cells_missing(const dz_tune_cells* c, unsigned need) {
+    if (!c) return "cells";
+    const void* const ptr[12] = {c->file_chunk_off, c->file_row_off, c->row_off,   c->step_rows, c->mids,       c->mid_cell,
+                                 c->file_cell_off,  c->cell_dur,     c->cell_ref,  c->cell_step, c->dur_prefix, c->ref_prefix};
+    static const char* const name[12] = {"cells->file_chunk_off", "cells->file_row_off", "cells->row_off",    "cells->step_rows",
+                                         "cells->mids",           "cells->mid_cell",     "cells->file_cell_off", "cells->cell_dur",
+                                         "cells->cell_ref",       "cells->cell_step",    "cells->dur_prefix", "cells->ref_prefix"};
+    for (int i = 0; i < 12; ++i)
+        if (((need >> i) & 1u) && !ptr[i]) return name[i];
+    return nullptr;
+}
+inline TcScoreCall tc_score_call(const dz_tune_cells& c, const unsigned* bits, int trials) {
+    return {bits,       trials,          c.n_files,  c.total_rows, c.file_chunk_off, c.row_off,      c.mids,
+            c.mid_cell, c.file_cell_off, c.cell_dur, c.cell_ref,   c.max_cells,      c.max_speakers, c.collar};
 }
 
 #if defined(TC_KERNEL_UNIT)   // the kernels' translation units define it before this header: threadIdx, the barrier

@@ -14,15 +14,15 @@
 //                        workgroup played one after the other: scoring="device" on backend="core"
 //   dz_tune_vad_host     VoiceActivityDetection: the aggregated speech scores, the masks and (backend="core") the
 //                        scoring of k_tune_vad.hip, from the text those kernels compile; OverlappedSpeechDetection
-//                        too (both track pipelines: another track, other reference prefix sums)
-//   dz_tune_vad_host_hyst     the same with an offset threshold (hysteresis): one implementation, another row rule;
+//                        too (both track pipelines: another track, other reference prefix sums).  With an offset
+//                        threshold (hysteresis) and with minimum durations: one implementation, another row rule
 //   dz_tune_vad_replay_tails  its yardstick: the masks through dz_tail_create + dz_tail_set_offset + dz_tail_step
-//   dz_tune_name_host    the names a gallery gives the global speakers of every (trial, file) chain, step by step, from
-//                        the text tune_name_kernel compiles (tune_ident_core.h)
+//   dz_tune_name_host    the names a gallery gives the global speakers of every (trial, point, file) chain, step by step,
+//                        from the text tune_name_kernel compiles (tune_ident_core.h)
 //   dz_tune_ident_score  identification error rate components of every pair: dz_tune_score's cells, the labels compared
-//                        as they are;  dz_tune_ident_score_core: the same from the text of tune_ident_score_kernel
-//   dz_tune_name_sweep_host, dz_tune_ident_score_sweep_core   the two at several (plane, threshold) points per trial
-//                        (DESIGN.md 4.23); the one-point entries are their points = 1 call
+//                        as they are;  dz_tune_ident_score_core: the same from the text of tune_ident_score_kernel, at
+//                        several (plane, threshold) points per trial
+// The scoring geometry reaches every entry as one descriptor, dz_tune_cells (include/diart_amd.h).
 #include "tune_core.h"
 #include "tune_ident_core.h"
 
@@ -95,16 +95,17 @@ struct ScoreScratch {
 // The hypothesis mask of every scoring cell of file n from one trial's masks B (dz_tune_score and
 // dz_tune_ident_score): Binarize's turns per step and speaker, Annotation.support(collar) per speaker, then the cells
 // each merged turn covers.  Returns 4 when a turn does not start and end on the file's cells.
-int hyp_cells(ScoreScratch& sc, const unsigned* B, int n, const int* file_row_off, const int* file_chunk_off,
-              const int* step_rows, const double* mids, const int* mid_cell, int ncell, int G, double collar) {
+int hyp_cells(ScoreScratch& sc, const unsigned* B, int n, const dz_tune_cells& cells, int ncell) {
+    const int G = cells.max_speakers;
+    const double collar = cells.collar;
     int rc = 0;
     for (int g = 0; g < G; ++g) sc.turns[g].clear();
     // ---- Binarize (tail_edge_walk): per step and speaker, [middle(onset), middle(first inactive row))
-    int p = file_row_off[n];
-    for (int c = file_chunk_off[n]; c < file_chunk_off[n + 1]; ++c) {
-        const int rows = step_rows[c];
-        const double* mid = mids + (size_t)p + c;      // rows + 1 values
-        const int* cell = mid_cell + (size_t)p + c;
+    int p = cells.file_row_off[n];
+    for (int c = cells.file_chunk_off[n]; c < cells.file_chunk_off[n + 1]; ++c) {
+        const int rows = cells.step_rows[c];
+        const double* mid = cells.mids + (size_t)p + c;      // rows + 1 values
+        const int* cell = cells.mid_cell + (size_t)p + c;
         unsigned any = 0;
         for (int r = 0; r < rows; ++r) any |= B[p + r];
         for (unsigned m = any; m; m &= m - 1) {
@@ -149,7 +150,20 @@ int hyp_cells(ScoreScratch& sc, const unsigned* B, int n, const int* file_row_of
     return rc;
 }
 
+// What every entry that takes the scoring geometry refuses first: a NULL among the members it reads (`need`,
+// tune_core.h) or among its own arrays (`rest`: all of them non-NULL).  `who` is the entry.
+int check_cells(const char* who, const dz_tune_cells* cells, unsigned need, bool rest) {
+    const char* missing = tc_cells_missing(cells, need);
+    if (missing || !rest) {
+        dz_set_error("%s: NULL argument (%s)", who, missing ? missing : "an array of the call");
+        return 2;
+    }
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int dz_tune_cells_abi_size(void) { return (int)sizeof(dz_tune_cells); }
 
 extern "C" int dz_tune_plan(int chunks, int frames, double step, double latency, const double* starts,
                             const double* resolution, int* plan, double* t0_out, double* res_out) {
@@ -290,16 +304,16 @@ extern "C" int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams,
     return f.code;
 }
 
-extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_row_off,
-                             const int* file_chunk_off, const int* step_rows, const double* mids, const int* mid_cell,
-                             const int* file_cell_off, const double* cell_dur, const unsigned long long* cell_ref,
-                             int max_speakers, double collar, double* out, int num_threads) {
-    if (trials < 1 || n_files < 1 || !bits || !file_row_off || !file_chunk_off || !step_rows || !mids || !mid_cell ||
-        !file_cell_off || !cell_dur || !cell_ref || !out || max_speakers < 1 || max_speakers > TC_GMAX) {
+extern "C" int dz_tune_score(const dz_tune_cells* cells, int trials, const unsigned* bits, double* out, int num_threads) {
+    if (check_cells("dz_tune_score", cells, TC_CELLS_SEQUENTIAL, bits && out)) return 2;
+    if (trials < 1 || cells->n_files < 1 || cells->max_speakers < 1 || cells->max_speakers > TC_GMAX) {
         dz_set_error("dz_tune_score: bad arguments");
         return 2;
     }
-    const int N = n_files, G = max_speakers, pairs = trials * N;
+    const int N = cells->n_files, G = cells->max_speakers, pairs = trials * N;
+    const int* file_cell_off = cells->file_cell_off;
+    const double* cell_dur = cells->cell_dur;
+    const unsigned long long* cell_ref = cells->cell_ref;
     const int nt = dz_host_threads(num_threads, pairs);
     std::vector<ScoreScratch> scratch(nt);
     std::vector<int> rcs(nt, 0);
@@ -307,9 +321,7 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
         const int t = pair / N, n = pair - t * N;
         ScoreScratch& sc = scratch[w];
         const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
-        if (hyp_cells(sc, bits + (size_t)t * total_rows, n, file_row_off, file_chunk_off, step_rows, mids, mid_cell, ncell, G,
-                      collar))
-            rcs[w] = 4;
+        if (hyp_cells(sc, bits + (size_t)t * cells->total_rows, n, *cells, ncell)) rcs[w] = 4;
         // ---- the components over the cells
         double total = 0.0, missed = 0.0, fa = 0.0, both = 0.0;
         double cooc[TC_GMAX][64];
@@ -372,20 +384,16 @@ extern "C" int dz_tune_score(int trials, int n_files, const unsigned* bits, int 
 
 // dz_tune_score's components from the text of tune_score_kernel (tune_core.h: tc_score_pair), on host memory
 // (score_core above).
-extern "C" int dz_tune_score_core(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
-                                  const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
-                                  const double* cell_dur, const unsigned long long* cell_ref, int max_cells, int max_speakers,
-                                  double collar, int lanes, int score_blocks, double* out, int num_threads) {
-    if (trials < 1 || n_files < 1 || !bits || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off ||
-        !cell_dur || !cell_ref || !out || max_speakers < 1 || max_speakers > TC_GMAX || max_cells < 0 || lanes < 1 ||
-        lanes > TC_SCORE_LANES || score_blocks < 1) {
+extern "C" int dz_tune_score_core(const dz_tune_cells* cells, int trials, const unsigned* bits, int lanes, int score_blocks,
+                                  double* out, int num_threads) {
+    if (check_cells("dz_tune_score_core", cells, TC_CELLS_KERNEL, bits && out)) return 2;
+    if (trials < 1 || cells->n_files < 1 || cells->max_speakers < 1 || cells->max_speakers > TC_GMAX || cells->max_cells < 0 ||
+        lanes < 1 || lanes > TC_SCORE_LANES || score_blocks < 1) {
         dz_set_error("dz_tune_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
         return 2;
     }
-    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
-                              cell_dur, cell_ref, max_cells, max_speakers, collar};
     const int rc = score_core<TcScoreShared>(
-        call, score_blocks, num_threads,
+        tc_score_call(*cells, bits, trials), score_blocks, num_threads,
         [&](const TcScoreIn& in, TcScoreShared& sh, unsigned* slice, long long pair, int, int, int* err) {
             tc_score_pair(in, sh, slice, out + (size_t)pair * 5, err, LanesInTurn{lanes});
         });
@@ -398,25 +406,25 @@ extern "C" int dz_tune_score_core(int trials, int n_files, const unsigned* bits,
     return 0;
 }
 
-// The track pipelines on the host, from the text k_tune_vad.hip compiles; what dz_tune_vad_host
-// (TcPlainRule: taus (T,)) and dz_tune_vad_host_hyst (TcHystRule: taus (T, 2) = (tau_active, tau_offset)) share, `name`
-// the one that was called.  agg (total_rows) once; then the pairs as tune_vad_score_kernel<Rule> runs them
+// The track pipelines on the host, from the text k_tune_vad.hip compiles, under the rule
+// dz_tune_vad_host's `cols` selects.  agg (total_rows) once; then the pairs as tune_vad_score_kernel<Rule> runs them
 // (tc_track_pair), `lanes` lanes of a workgroup played one after the other: the components where `out` is given
 // (backend="core"; backend="host" scores the bits with dz_tune_score instead, the yardstick of the device scoring) and,
-// under the stateful rule, the masks, which come from the lanes' state maps.  The stateless masks are agg > tau row by
+// under the stateful rules, the masks, which come from the lanes' state maps.  The stateless masks are agg > tau row by
 // row, as on the device.
 namespace {
 template <typename Rule>
-int track_host(const char* name, const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-               const double* mids, const int* mid_cell, const int* file_cell_off, const double* dur_prefix,
-               const double* ref_prefix, double collar, int lanes, double* out, int num_threads) {
+int track_host(const dz_tune_desc* d, const dz_tune_cells* cells, const double* taus, int trials, double* agg,
+               unsigned* bits, int lanes, double* out, int num_threads) {
+    const char* name = "dz_tune_vad_host";
     const bool pair_call = Rule::stateful || out;   // (whether anything goes through tc_track_pair)
     if (!d || !taus || !agg || trials < 1 || !d->seg || !d->chunk_off || !d->plan || !d->row_off || !d->row_chunk ||
         !d->hamming || d->K != 1 || d->N < 1 || d->F < 1 || d->nwin < 1 || d->total_rows < 1 || lanes > TC_TRACK_LANES ||
-        (pair_call && (!mids || !mid_cell || !file_cell_off || !dur_prefix || !ref_prefix || lanes < 1))) {
+        (pair_call && lanes < 1)) {
         dz_set_error("%s: bad arguments (one track per chunk, 1 .. %d lanes expected)", name, TC_TRACK_LANES);
         return 2;
     }
+    if (pair_call && check_cells(name, cells, TC_CELLS_TRACK_PAIR, true)) return 2;
     if constexpr (Rule::stateful) {
         const int cols = Rule::durations ? 4 : 2;
         for (int t = 0; t < trials; ++t) {
@@ -447,14 +455,15 @@ int track_host(const char* name, const dz_tune_desc* d, const double* taus, int 
             for (int p = 0; p < rows; ++p) B[p] = rule(agg[p], false) ? 1u : 0u;
         });
     if (!out && !pair_bits) return 0;
+    const int* file_cell_off = cells->file_cell_off;
     each_item(trials * N, num_threads, [&](int, int pair) {
         const int t = pair / N, n = pair - t * N;
         const size_t pre = (size_t)file_cell_off[n] + n;
         std::vector<TcTrackSharedOf<Rule>> sh(1);
         // LDS starts with whatever was there: nothing in it may be read before this pair has written it
         std::memset(sh.data(), (pair & 1) ? 0x7f : 0xff, sizeof(sh[0]));
-        const TcTrackIn in = {agg, d->row_off, mids, mid_cell, dur_prefix + pre, ref_prefix + pre, d->chunk_off[n],
-                              d->chunk_off[n + 1], file_cell_off[n + 1] - file_cell_off[n], collar};
+        const TcTrackIn in = {agg, d->row_off, cells->mids, cells->mid_cell, cells->dur_prefix + pre, cells->ref_prefix + pre,
+                              d->chunk_off[n], d->chunk_off[n + 1], file_cell_off[n + 1] - file_cell_off[n], cells->collar};
         tc_track_pair(in, Rule::of(taus, t), sh[0], out ? out + (size_t)pair * 5 : nullptr,
                       pair_bits ? pair_bits + (size_t)t * rows : nullptr, LanesInTurn{lanes});
     });
@@ -462,30 +471,15 @@ int track_host(const char* name, const dz_tune_desc* d, const double* taus, int 
 }
 }  // namespace
 
-extern "C" int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-                                const double* mids, const int* mid_cell, const int* file_cell_off,
-                                const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
-                                int num_threads) {
-    return track_host<TcPlainRule>("dz_tune_vad_host", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off, dur_prefix,
-                                   ref_prefix, collar, lanes, out, num_threads);
-}
-
-extern "C" int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-                                     const double* mids, const int* mid_cell, const int* file_cell_off,
-                                     const double* dur_prefix, const double* ref_prefix, double collar, int lanes,
-                                     double* out, int num_threads) {
-    return track_host<TcHystRule>("dz_tune_vad_host_hyst", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off,
-                                  dur_prefix, ref_prefix, collar, lanes, out, num_threads);
-}
-
-// Minimum durations: taus (T, 4) = (tau_active, tau_offset, min_duration_on, min_duration_off), the
-// text of tune_vad_score_kernel<TcDurRule>.  backend="core".
-extern "C" int dz_tune_vad_host_dur(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-                                    const double* mids, const int* mid_cell, const int* file_cell_off,
-                                    const double* dur_prefix, const double* ref_prefix, double collar, int lanes,
-                                    double* out, int num_threads) {
-    return track_host<TcDurRule>("dz_tune_vad_host_dur", d, taus, trials, agg, bits, mids, mid_cell, file_cell_off,
-                                 dur_prefix, ref_prefix, collar, lanes, out, num_threads);
+extern "C" int dz_tune_vad_host(const dz_tune_desc* d, const dz_tune_cells* cells, int cols, const double* taus, int trials,
+                                double* agg, unsigned* bits, int lanes, double* out, int num_threads) {
+    switch (cols) {
+        case 1: return track_host<TcPlainRule>(d, cells, taus, trials, agg, bits, lanes, out, num_threads);
+        case 2: return track_host<TcHystRule>(d, cells, taus, trials, agg, bits, lanes, out, num_threads);
+        case 4: return track_host<TcDurRule>(d, cells, taus, trials, agg, bits, lanes, out, num_threads);
+    }
+    dz_set_error("dz_tune_vad_host: taus of %d columns (1: tau_active; 2: and tau_offset; 4: and the two minimum durations)", cols);
+    return 2;
 }
 
 // The same components from an independent sequential text, behind masks that were made elsewhere (backend="host": the
@@ -493,16 +487,10 @@ extern "C" int dz_tune_vad_host_dur(const dz_tune_desc* d, const double* taus, i
 // from the masks, sorted by start; Annotation.support(max(collar, min_duration_off)); the spans shorter than
 // min_duration_on dropped; the cells of the others summed one by one, from cell_dur and cell_ref and not from prefix
 // sums.  bits (T, total_rows), bit 0; taus (T, 4), of which the two durations are read; out (T, N, 5).
-extern "C" int dz_tune_track_score_dur(int trials, int n_files, const unsigned* bits, int total_rows,
-                                       const int* file_chunk_off, const int* row_off, const double* mids,
-                                       const int* mid_cell, const int* file_cell_off, const double* cell_dur,
-                                       const unsigned long long* cell_ref, const double* taus, double collar, double* out,
-                                       int num_threads) {
-    if (!bits || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off || !cell_dur || !cell_ref || !taus ||
-        !out) {
-        dz_set_error("dz_tune_track_score_dur: NULL argument");
-        return 2;
-    }
+extern "C" int dz_tune_track_score_dur(const dz_tune_cells* cells, int trials, const unsigned* bits, const double* taus,
+                                       double* out, int num_threads) {
+    if (check_cells("dz_tune_track_score_dur", cells, TC_CELLS_KERNEL, bits && taus && out)) return 2;
+    const int n_files = cells->n_files, total_rows = cells->total_rows;
     if (trials < 1 || n_files < 1 || total_rows < 1) {
         dz_set_error("dz_tune_track_score_dur: empty shape (%d trials, %d files, %d rows)", trials, n_files, total_rows);
         return 2;
@@ -516,6 +504,10 @@ extern "C" int dz_tune_track_score_dur(int trials, int n_files, const unsigned* 
                 return 2;
             }
         }
+    const int *file_chunk_off = cells->file_chunk_off, *row_off = cells->row_off, *mid_cell = cells->mid_cell,
+              *file_cell_off = cells->file_cell_off;
+    const double *mids = cells->mids, *cell_dur = cells->cell_dur, collar = cells->collar;
+    const unsigned long long* cell_ref = cells->cell_ref;
     const dz_host_failure f = dz_host_parallel_rc(trials * n_files, dz_host_threads(num_threads, trials * n_files), [&](int, int pair) {
         const int t = pair / n_files, n = pair - t * n_files;
         const unsigned* B = bits + (size_t)t * total_rows;
@@ -644,31 +636,31 @@ extern "C" int dz_tune_vad_replay_tails(const dz_tune_desc* d, const double* tau
 // ---------------------------------------------------------------------------------------------------------
 // Tuning delta_id
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int dz_tune_name_sweep_host(int trials, int points, int planes, int n_files, int total_chunks, int k_local,
+extern "C" int dz_tune_name_host(int trials, int points, int planes, int n_files, int total_chunks, int k_local,
                                        int max_speakers, int voiceprints, const int* file_chunk_off,
                                        const signed char* assign, const int* status, const int* match_index,
                                        const float* match_distance, const signed char* vp_ref, const double* delta_id,
                                        signed char* ident, int* hold, int num_threads) {
     if (!file_chunk_off || !assign || !status || !match_index || !match_distance || !vp_ref || !delta_id || !ident) {
-        dz_set_error("dz_tune_name_sweep_host: NULL argument");
+        dz_set_error("dz_tune_name_host: NULL argument");
         return 2;
     }
     if (trials < 1 || n_files < 1 || total_chunks < n_files || k_local < 1 || k_local > TC_KMAX || max_speakers < 1 ||
         max_speakers > TC_GMAX || voiceprints < 1) {
-        dz_set_error("dz_tune_name_sweep_host: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at "
+        dz_set_error("dz_tune_name_host: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at "
                      "most %d / %d), %d voiceprints)",
                      trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints);
         return 2;
     }
     if (points < 1 || points > TI_MAX_POINTS || planes < 1 || planes > TI_MAX_PLANES || points % planes != 0) {
-        dz_set_error("dz_tune_name_sweep_host: %d points (1 .. %d) in %d planes (1 .. %d, a divisor of the points)", points,
+        dz_set_error("dz_tune_name_host: %d points (1 .. %d) in %d planes (1 .. %d, a divisor of the points)", points,
                      TI_MAX_POINTS, planes, TI_MAX_PLANES);
         return 2;
     }
     const int N = n_files, K = k_local, G = max_speakers, V = voiceprints;
     const long long chains = (long long)trials * points * N;
     if (chains >= (1ll << 31)) {
-        dz_set_error("dz_tune_name_sweep_host: %lld chains in one call; evaluate fewer trials per batch", chains);
+        dz_set_error("dz_tune_name_host: %lld chains in one call; evaluate fewer trials per batch", chains);
         return 2;
     }
     each_item((int)chains, num_threads, [&](int, int chain) {
@@ -707,41 +699,17 @@ extern "C" int dz_tune_name_sweep_host(int trials, int points, int planes, int n
     return 0;
 }
 
-extern "C" int dz_tune_name_host(int trials, int n_files, int total_chunks, int k_local, int max_speakers, int voiceprints,
-                                 const int* file_chunk_off, const signed char* assign, const int* status,
-                                 const int* match_index, const float* match_distance, const signed char* vp_ref,
-                                 const double* delta_id, signed char* ident, int* hold, int num_threads) {
-    if (!file_chunk_off || !assign || !status || !match_index || !match_distance || !vp_ref || !delta_id || !ident) {
-        dz_set_error("dz_tune_name_host: NULL argument");
-        return 2;
-    }
-    if (trials < 1 || n_files < 1 || total_chunks < n_files || k_local < 1 || k_local > TC_KMAX || max_speakers < 1 ||
-        max_speakers > TC_GMAX || voiceprints < 1) {
-        dz_set_error("dz_tune_name_host: bad arguments (%d trials, %d files, %d chunks, %d local / %d global speakers (at most "
-                     "%d / %d), %d voiceprints)",
-                     trials, n_files, total_chunks, k_local, max_speakers, TC_KMAX, TC_GMAX, voiceprints);
-        return 2;
-    }
-    return dz_tune_name_sweep_host(trials, 1, 1, n_files, total_chunks, k_local, max_speakers, voiceprints, file_chunk_off,
-                                   assign, status, match_index, match_distance, vp_ref, delta_id, ident, hold, num_threads);
-}
-
-extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
-                                   int total_chunks, const int* file_row_off, const int* file_chunk_off,
-                                   const int* step_rows, const double* mids, const int* mid_cell, const int* file_cell_off,
-                                   const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
-                                   int max_speakers, double collar, double* out, int num_threads) {
-    if (!bits || !ident || !file_row_off || !file_chunk_off || !step_rows || !mids || !mid_cell || !file_cell_off ||
-        !cell_dur || !cell_ref || !cell_step || !out) {
-        dz_set_error("dz_tune_ident_score: NULL argument");
-        return 2;
-    }
-    if (trials < 1 || n_files < 1 || total_rows < 1 || total_chunks < n_files || max_speakers < 1 || max_speakers > TC_GMAX) {
+extern "C" int dz_tune_ident_score(const dz_tune_cells* cells, int trials, const unsigned* bits, const signed char* ident,
+                                   double* out, int num_threads) {
+    if (check_cells("dz_tune_ident_score", cells, TC_CELLS_SEQUENTIAL | TC_CELLS_CELL_STEP, bits && ident && out)) return 2;
+    const int N = cells->n_files, G = cells->max_speakers, total_chunks = cells->total_chunks;
+    if (trials < 1 || N < 1 || cells->total_rows < 1 || total_chunks < N || G < 1 || G > TC_GMAX) {
         dz_set_error("dz_tune_ident_score: bad arguments (%d trials, %d files, %d rows, %d chunks, %d speakers (at most %d))",
-                     trials, n_files, total_rows, total_chunks, max_speakers, TC_GMAX);
+                     trials, N, cells->total_rows, total_chunks, G, TC_GMAX);
         return 2;
     }
-    const int N = n_files, G = max_speakers, pairs = trials * N;
+    const int pairs = trials * N;
+    const int *file_cell_off = cells->file_cell_off, *file_chunk_off = cells->file_chunk_off;
     const int nt = dz_host_threads(num_threads, pairs);
     std::vector<ScoreScratch> scratch(nt);
     std::vector<int> rcs(nt, 0);
@@ -749,24 +717,22 @@ extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits
         const int t = pair / N, n = pair - t * N;
         ScoreScratch& sc = scratch[w];
         const int cell0 = file_cell_off[n], ncell = file_cell_off[n + 1] - cell0;
-        if (hyp_cells(sc, bits + (size_t)t * total_rows, n, file_row_off, file_chunk_off, step_rows, mids, mid_cell, ncell, G,
-                      collar))
-            rcs[w] = 4;
+        if (hyp_cells(sc, bits + (size_t)t * cells->total_rows, n, *cells, ncell)) rcs[w] = 4;
         const signed char* I = ident + (size_t)t * total_chunks * G;
         double* o = out + (size_t)pair * 5;   // metrics.COMPONENTS order
         for (int q = 0; q < 5; ++q) o[q] = 0.0;
         for (int i = 0; i < ncell; ++i) {
             const unsigned h = sc.hyp[i];
-            const unsigned long long rm = cell_ref[cell0 + i];
+            const unsigned long long rm = cells->cell_ref[cell0 + i];
             if (!h && !rm) continue;
-            const int c = cell_step[cell0 + i];
+            const int c = cells->cell_step[cell0 + i];
             if (c < file_chunk_off[n] || c >= file_chunk_off[n + 1]) {
                 rcs[w] = 4;
                 continue;
             }
             int cnt[5];
             ti_cell_counts(h, rm, I + (size_t)c * G, cnt);
-            for (int q = 0; q < 5; ++q) o[q] += cell_dur[cell0 + i] * cnt[q];
+            for (int q = 0; q < 5; ++q) o[q] += cells->cell_dur[cell0 + i] * cnt[q];
         }
     });
     for (int w = 0; w < nt; ++w)
@@ -777,19 +743,14 @@ extern "C" int dz_tune_ident_score(int trials, int n_files, const unsigned* bits
     return 0;
 }
 
-// Both entries below: `who` is the entry the caller used, which every refusal and failure names.
-static int ident_score_core(const char* who, int trials, int points, int n_files, const unsigned* bits,
-                            const signed char* ident, int total_rows, int total_chunks, const int* file_chunk_off,
-                            const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
-                            const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step, int max_cells,
-                            int max_speakers, double collar, int lanes, int score_blocks, double* out, int num_threads) {
-    if (!bits || !ident || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off || !cell_dur || !cell_ref ||
-        !cell_step || !out) {
-        dz_set_error("%s: NULL argument", who);
-        return 2;
-    }
-    if (trials < 1 || n_files < 1 || total_rows < 1 || total_chunks < n_files || max_speakers < 1 || max_speakers > TC_GMAX ||
-        max_cells < 0 || lanes < 1 || lanes > TC_SCORE_LANES || score_blocks < 1) {
+extern "C" int dz_tune_ident_score_core(const dz_tune_cells* cells, int trials, int points, const unsigned* bits,
+                                        const signed char* ident, int lanes, int score_blocks, double* out,
+                                        int num_threads) {
+    const char* who = "dz_tune_ident_score_core";
+    if (check_cells(who, cells, TC_CELLS_KERNEL | TC_CELLS_CELL_STEP, bits && ident && out)) return 2;
+    const int n_files = cells->n_files, max_speakers = cells->max_speakers;
+    if (trials < 1 || n_files < 1 || cells->total_rows < 1 || cells->total_chunks < n_files || max_speakers < 1 ||
+        max_speakers > TC_GMAX || cells->max_cells < 0 || lanes < 1 || lanes > TC_SCORE_LANES || score_blocks < 1) {
         dz_set_error("%s: bad arguments (%d trials, at most %d speakers, %d lanes)", who, trials, TC_GMAX, TC_SCORE_LANES);
         return 2;
     }
@@ -797,14 +758,12 @@ static int ident_score_core(const char* who, int trials, int points, int n_files
         dz_set_error("%s: %d points (1 .. %d)", who, points, TI_MAX_POINTS);
         return 2;
     }
-    const TcScoreCall call = {bits, trials, n_files, total_rows, file_chunk_off, row_off, mids, mid_cell, file_cell_off,
-                              cell_dur, cell_ref, max_cells, max_speakers, collar};
-    const long long plane = (long long)total_chunks * max_speakers;   // one point's identities of one trial
+    const long long plane = (long long)cells->total_chunks * max_speakers;   // one point's identities of one trial
     const int rc = score_core<TiScoreShared>(
-        call, score_blocks, num_threads,
-        [&](const TcScoreIn& cells, TiScoreShared& sh, unsigned* slice, long long pair, int t, int cell0, int* err) {
+        tc_score_call(*cells, bits, trials), score_blocks, num_threads,
+        [&](const TcScoreIn& in_cells, TiScoreShared& sh, unsigned* slice, long long pair, int t, int cell0, int* err) {
             const int n = (int)(pair - (long long)t * n_files);
-            const TiScoreIn in = {cells, ident + (size_t)t * points * plane, cell_step + cell0};
+            const TiScoreIn in = {in_cells, ident + (size_t)t * points * plane, cells->cell_step + cell0};
             ti_score_pair(in, points, plane, (long long)n_files * 5, sh, slice, out + ((size_t)t * points * n_files + n) * 5,
                           err, LanesInTurn{lanes});
         });
@@ -814,37 +773,4 @@ static int ident_score_core(const char* who, int trials, int points, int n_files
         return rc;
     }
     return 0;
-}
-
-extern "C" int dz_tune_ident_score_sweep_core(int trials, int points, int n_files, const unsigned* bits,
-                                              const signed char* ident, int total_rows, int total_chunks,
-                                              const int* file_chunk_off, const int* row_off, const double* mids,
-                                              const int* mid_cell, const int* file_cell_off, const double* cell_dur,
-                                              const unsigned long long* cell_ref, const int* cell_step, int max_cells,
-                                              int max_speakers, double collar, int lanes, int score_blocks, double* out,
-                                              int num_threads) {
-    return ident_score_core("dz_tune_ident_score_sweep_core", trials, points, n_files, bits, ident, total_rows, total_chunks,
-                            file_chunk_off, row_off, mids, mid_cell, file_cell_off, cell_dur, cell_ref, cell_step, max_cells,
-                            max_speakers, collar, lanes, score_blocks, out, num_threads);
-}
-
-extern "C" int dz_tune_ident_score_core(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
-                                        int total_chunks, const int* file_chunk_off, const int* row_off, const double* mids,
-                                        const int* mid_cell, const int* file_cell_off, const double* cell_dur,
-                                        const unsigned long long* cell_ref, const int* cell_step, int max_cells,
-                                        int max_speakers, double collar, int lanes, int score_blocks, double* out,
-                                        int num_threads) {
-    if (!bits || !ident || !file_chunk_off || !row_off || !mids || !mid_cell || !file_cell_off || !cell_dur || !cell_ref ||
-        !cell_step || !out) {
-        dz_set_error("dz_tune_ident_score_core: NULL argument");
-        return 2;
-    }
-    if (trials < 1 || n_files < 1 || total_rows < 1 || total_chunks < n_files || max_speakers < 1 || max_speakers > TC_GMAX ||
-        max_cells < 0 || lanes < 1 || lanes > TC_SCORE_LANES || score_blocks < 1) {
-        dz_set_error("dz_tune_ident_score_core: bad arguments (at most %d speakers, %d lanes)", TC_GMAX, TC_SCORE_LANES);
-        return 2;
-    }
-    return ident_score_core("dz_tune_ident_score_core", trials, 1, n_files, bits, ident, total_rows, total_chunks,
-                            file_chunk_off, row_off, mids, mid_cell, file_cell_off, cell_dur, cell_ref, cell_step, max_cells,
-                            max_speakers, collar, lanes, score_blocks, out, num_threads);
 }

@@ -219,15 +219,34 @@ class _ReplayCache:
     def default_backend() -> str:
         return "gpu" if torch.cuda.is_available() else "host"
 
-    def _score_bits(self, bits: np.ndarray, max_speakers: int, num_threads: int) -> np.ndarray:
+    def _cells(self, ptr) -> _lib.TuneCells:
+        """The scoring geometry as the descriptor the entry points take (``dz_tune_cells``): ``ptr(name)`` is the address
+        of the cache's array ``name``, or None for one this cache does not have (which no entry it calls reads).  One
+        hypothesis label for a cache without ``G`` (the track caches)."""
+        c = _lib.TuneCells()
+        for name in _lib.TuneCells.POINTERS:
+            setattr(c, name, ptr("chunk_off" if name == "file_chunk_off" else name))
+        c.n_files, c.total_rows, c.total_chunks = self.N, self.total_rows, int(self.chunk_off[-1])
+        c.max_cells, c.max_speakers, c.collar = self.max_cells, getattr(self, "G", 1), PATCH_COLLAR
+        return c
+
+    def _host_cells(self) -> _lib.TuneCells:
+        """``_cells`` over the cache's own arrays, built once and kept beside the arrays it points into: it is built
+        again when one of them is no longer the cache's (an array replaced, or one this cache gained, as ``cell_step``)."""
+        names = ["chunk_off" if n == "file_chunk_off" else n for n in _lib.TuneCells.POINTERS]
+        arrays = [getattr(self, n, None) for n in names]
+        kept = self.__dict__.get("_cells_host")
+        if kept is None or any(a is not b for a, b in zip(kept[1], arrays)):
+            at = dict(zip(names, arrays))
+            kept = self._cells_host = (self._cells(lambda n: None if at[n] is None else at[n].ctypes.data), arrays)
+        return kept[0]
+
+    def _score_bits(self, bits: np.ndarray, num_threads: int) -> np.ndarray:
         bits = np.ascontiguousarray(bits, dtype=np.uint32)
         T = bits.shape[0]
         out = np.zeros((T, self.N, 5), dtype=np.float64)
-        _lib.check(_lib.load().dz_tune_score(T, self.N, bits.ctypes.data, self.total_rows, self.file_row_off.ctypes.data,
-                                             self.chunk_off.ctypes.data, self.step_rows.ctypes.data, self.mids.ctypes.data,
-                                             self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
-                                             self.cell_dur.ctypes.data, self.cell_ref.ctypes.data, max_speakers, PATCH_COLLAR,
-                                             out.ctypes.data, int(num_threads)), "dz_tune_score")
+        _lib.check(_lib.load().dz_tune_score(C.byref(self._host_cells()), T, bits.ctypes.data, out.ctypes.data,
+                                             int(num_threads)), "dz_tune_score")
         return out
 
     def _hypothesis(self, bits_row: np.ndarray, n: int, speakers: int, label) -> Annotation:
@@ -457,7 +476,8 @@ class TuneCache(_ReplayCache):
                        for name in ("seg", "emb", "pre_max", "pre_mean", "pre_flags", "chunk_off", "plan", "row_off",
                                     "row_chunk", "hamming", "mids", "mid_cell", "file_cell_off", "cell_dur")}
             tensors["cell_ref"] = torch.from_numpy(self.cell_ref.view(np.int64)).to(device)      # (the 64 bits as they are)
-            self._dev[key] = (tensors, self._desc(lambda name: tensors[name].data_ptr()))
+            ptr = lambda name: tensors[name].data_ptr() if name in tensors else None
+            self._dev[key] = (tensors, self._desc(ptr), self._cells(ptr))
         return self._dev[key]
 
     WORK_BLOCKS = 2048          # resident chains: 256 CUs x 8 one-wave workgroups
@@ -466,7 +486,7 @@ class TuneCache(_ReplayCache):
         if not torch.cuda.is_available():
             raise _lib.DiartAmdError("backend='gpu' needs a GPU; backend='host' replays on the host")
         device = device or torch.device("cuda", torch.cuda.current_device())
-        _, desc = self._device(device)
+        desc = self._device(device)[1]
         T, total = hp.shape[0], int(self.chunk_off[-1])
         d_hp = torch.from_numpy(hp).to(device)
         if into is not None:                     # (measurements: one phase on the arrays of an earlier call)
@@ -500,17 +520,14 @@ class TuneCache(_ReplayCache):
     def _score_gpu(self, bits: torch.Tensor, score_blocks: Optional[int] = None):
         """``(out (T, N, 5) float64, err (1,) int32)`` on the device of ``bits (T, rows)``: tune_score_kernel, enqueued."""
         device = bits.device
-        t, _ = self._device(device)
+        cells = self._device(device)[2]
         T = bits.shape[0]
         blocks = max(1, min(T * self.N, int(score_blocks or self.SCORE_BLOCKS)))
         out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device)
         scratch = torch.empty((blocks, self.max_cells + 1), dtype=torch.int32, device=device)
         err = torch.empty(1, dtype=torch.int32, device=device)
-        _lib.check(_lib.load().dz_tune_score_gpu(_lib.context(device.index), T, self.N, bits.data_ptr(), self.total_rows,
-                                                 t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(),
-                                                 t["mid_cell"].data_ptr(), t["file_cell_off"].data_ptr(),
-                                                 t["cell_dur"].data_ptr(), t["cell_ref"].data_ptr(), self.max_cells, self.G,
-                                                 PATCH_COLLAR, out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(),
+        _lib.check(_lib.load().dz_tune_score_gpu(_lib.context(device.index), C.byref(cells), T, bits.data_ptr(), out.data_ptr(),
+                                                 scratch.data_ptr(), blocks, err.data_ptr(),
                                                  torch.cuda.current_stream(device).cuda_stream), "dz_tune_score_gpu")
         return out, err
 
@@ -524,11 +541,8 @@ class TuneCache(_ReplayCache):
         bits = np.ascontiguousarray(bits, dtype=np.uint32)
         T = bits.shape[0]
         out = np.zeros((T, self.N, 5), dtype=np.float64)
-        _lib.check(_lib.load().dz_tune_score_core(T, self.N, bits.ctypes.data, self.total_rows, self.chunk_off.ctypes.data,
-                                                  self.row_off.ctypes.data, self.mids.ctypes.data, self.mid_cell.ctypes.data,
-                                                  self.file_cell_off.ctypes.data, self.cell_dur.ctypes.data,
-                                                  self.cell_ref.ctypes.data, self.max_cells, self.G, PATCH_COLLAR,
-                                                  self.SCORE_LANES, int(score_blocks or self.SCORE_BLOCKS), out.ctypes.data,
+        _lib.check(_lib.load().dz_tune_score_core(C.byref(self._host_cells()), T, bits.ctypes.data, self.SCORE_LANES,
+                                                  int(score_blocks or self.SCORE_BLOCKS), out.ctypes.data,
                                                   int(num_threads)), "dz_tune_score_core")
         return out
 
@@ -543,7 +557,7 @@ class TuneCache(_ReplayCache):
         if self._check_scoring(scoring, backend or "host") == "host":
             if isinstance(bits, torch.Tensor):
                 bits = bits.cpu().numpy().view(np.uint32)
-            return self._score_bits(bits, self.G, num_threads)
+            return self._score_bits(bits, num_threads)
         self._check_sorted("scoring 'device'", "scoring='host'")
         if backend == "core":
             if isinstance(bits, torch.Tensor):
@@ -822,10 +836,15 @@ class IdentTuneCache(TuneCache):
                              "output grids of this cache's steps are not sorted by time")
 
     def _ident_device(self, device: torch.device):
+        """``(tensors, cells)``: what this cache adds to the TuneCache's device copies, and the TuneCache's descriptor of
+        the scoring geometry with ``cell_step`` in it."""
         key = str(device)
         if key not in self._ident_dev:
-            self._ident_dev[key] = {name: torch.from_numpy(getattr(self, name)).to(device)
-                                    for name in ("plane_index", "plane_distance", "vp_ref", "cell_step")}
+            tensors = {name: torch.from_numpy(getattr(self, name)).to(device)
+                       for name in ("plane_index", "plane_distance", "vp_ref", "cell_step")}
+            cells = _lib.TuneCells.from_buffer_copy(self._device(device)[2])
+            cells.cell_step = tensors["cell_step"].data_ptr()
+            self._ident_dev[key] = (tensors, cells)
         return self._ident_dev[key]
 
     @staticmethod
@@ -846,7 +865,7 @@ class IdentTuneCache(TuneCache):
         ``planes[0]`` -> ``(T, chunks, G)`` int8 / int32.  ``delta_id (T, J)``: the sweep, J points plane-major over
         ``planes`` -> ``(T, J, chunks, G)``."""
         device = assign.device
-        t, i = self._device(device)[0], self._ident_device(device)
+        t, i = self._device(device)[0], self._ident_device(device)[0]
         T, total = assign.shape[0], int(self.chunk_off[-1])
         delta_id = np.ascontiguousarray(delta_id, dtype=np.float64)
         d_delta = torch.from_numpy(delta_id).to(device)
@@ -854,36 +873,27 @@ class IdentTuneCache(TuneCache):
         ident = torch.empty(shape, dtype=torch.int8, device=device)
         hold = torch.empty(shape, dtype=torch.int32, device=device) if want_hold else None
         index, distance = self._take_planes(i["plane_index"], i["plane_distance"], list(planes))
-        tail = (t["chunk_off"].data_ptr(), assign.data_ptr(), status.data_ptr(), index.data_ptr(), distance.data_ptr(),
-                i["vp_ref"].data_ptr(), d_delta.data_ptr(), ident.data_ptr(), None if hold is None else hold.data_ptr(),
-                self.NAME_BLOCKS, torch.cuda.current_stream(device).cuda_stream)
-        if delta_id.ndim == 1:
-            _lib.check(_lib.load().dz_tune_name(_lib.context(device.index), T, self.N, total, self.K, self.G, len(self.names),
-                                                *tail), "dz_tune_name")
-        else:
-            _lib.check(_lib.load().dz_tune_name_sweep(_lib.context(device.index), T, delta_id.shape[1], len(planes), self.N,
-                                                      total, self.K, self.G, len(self.names), *tail), "dz_tune_name_sweep")
+        _lib.check(_lib.load().dz_tune_name(
+            _lib.context(device.index), T, delta_id.size // T, len(planes), self.N, total, self.K, self.G, len(self.names),
+            t["chunk_off"].data_ptr(), assign.data_ptr(), status.data_ptr(), index.data_ptr(), distance.data_ptr(),
+            i["vp_ref"].data_ptr(), d_delta.data_ptr(), ident.data_ptr(), None if hold is None else hold.data_ptr(),
+            self.NAME_BLOCKS, torch.cuda.current_stream(device).cuda_stream), "dz_tune_name")
         return ident, hold
 
     def _names_host(self, assign: np.ndarray, status: np.ndarray, delta_id: np.ndarray, want_hold: bool, num_threads: int,
                     planes: Sequence[int] = (0,)):
-        """``_names_gpu`` on host threads: ``dz_tune_name_host`` for ``delta_id (T,)``, ``dz_tune_name_sweep_host`` for
-        ``delta_id (T, J)``."""
+        """``_names_gpu`` on host threads: ``dz_tune_name_host``."""
         T, total = assign.shape[0], int(self.chunk_off[-1])
         delta_id = np.ascontiguousarray(delta_id, dtype=np.float64)
         shape = (T,) + delta_id.shape[1:] + (total, self.G)
         ident = np.empty(shape, dtype=np.int8)
         hold = np.empty(shape, dtype=np.int32) if want_hold else None
         index, distance = self._take_planes(self.plane_index, self.plane_distance, list(planes))
-        tail = (self.chunk_off.ctypes.data, assign.ctypes.data, status.ctypes.data, index.ctypes.data, distance.ctypes.data,
-                self.vp_ref.ctypes.data, delta_id.ctypes.data, ident.ctypes.data,
-                None if hold is None else hold.ctypes.data, int(num_threads))
-        if delta_id.ndim == 1:
-            _lib.check(_lib.load().dz_tune_name_host(T, self.N, total, self.K, self.G, len(self.names), *tail),
-                       "dz_tune_name_host")
-        else:
-            _lib.check(_lib.load().dz_tune_name_sweep_host(T, delta_id.shape[1], len(planes), self.N, total, self.K, self.G,
-                                                           len(self.names), *tail), "dz_tune_name_sweep_host")
+        _lib.check(_lib.load().dz_tune_name_host(
+            T, delta_id.size // T, len(planes), self.N, total, self.K, self.G, len(self.names), self.chunk_off.ctypes.data,
+            assign.ctypes.data, status.ctypes.data, index.ctypes.data, distance.ctypes.data, self.vp_ref.ctypes.data,
+            delta_id.ctypes.data, ident.ctypes.data, None if hold is None else hold.ctypes.data, int(num_threads)),
+            "dz_tune_name_host")
         return ident, hold
 
     def replay_names(self, hparams, backend: Optional[str] = None, num_threads: int = 8, top_n=None):
@@ -906,53 +916,43 @@ class IdentTuneCache(TuneCache):
         """``(out, err)`` on the device: tune_ident_score_kernel, enqueued.  ``ident (T, chunks, G)`` -> ``out
         (T, N, 5)``; ``ident (T, J, chunks, G)``, the sweep -> ``out (T, J, N, 5)``."""
         device = bits.device
-        t, i = self._device(device)[0], self._ident_device(device)
+        cells = self._ident_device(device)[1]
         T = bits.shape[0]
         blocks = max(1, min(T * self.N, self.IDENT_BLOCKS))
         out = torch.empty(tuple(ident.shape[:-2]) + (self.N, 5), dtype=torch.float64, device=device)
         scratch = torch.empty((blocks, self.max_cells + 1), dtype=torch.int32, device=device)
         err = torch.empty(1, dtype=torch.int32, device=device)
-        tail = (bits.data_ptr(), ident.data_ptr(), self.total_rows, int(self.chunk_off[-1]),
-                t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
-                t["file_cell_off"].data_ptr(), t["cell_dur"].data_ptr(), t["cell_ref"].data_ptr(), i["cell_step"].data_ptr(),
-                self.max_cells, self.G, PATCH_COLLAR, out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(),
-                torch.cuda.current_stream(device).cuda_stream)
-        if ident.dim() == 3:
-            _lib.check(_lib.load().dz_tune_ident_score_gpu(_lib.context(device.index), T, self.N, *tail),
-                       "dz_tune_ident_score_gpu")
-        else:
-            _lib.check(_lib.load().dz_tune_ident_score_sweep_gpu(_lib.context(device.index), T, ident.shape[1], self.N, *tail),
-                       "dz_tune_ident_score_sweep_gpu")
+        _lib.check(_lib.load().dz_tune_ident_score_gpu(
+            _lib.context(device.index), C.byref(cells), T, self._points(ident), bits.data_ptr(), ident.data_ptr(),
+            out.data_ptr(), scratch.data_ptr(), blocks, err.data_ptr(), torch.cuda.current_stream(device).cuda_stream),
+            "dz_tune_ident_score_gpu")
         return out, err
+
+    @staticmethod
+    def _points(ident) -> int:
+        """The points of ``ident (T, chunks, G)`` (one) or ``(T, J, chunks, G)``."""
+        return 1 if len(ident.shape) == 3 else int(ident.shape[1])
 
     def _ident_score_host(self, bits: np.ndarray, ident: np.ndarray, core: bool, num_threads: int) -> np.ndarray:
         """``_ident_score_gpu`` on host threads.  ``core``: the kernel's text (``ident`` of one point or of a sweep);
         else ``dz_tune_ident_score``, the sequential text, one point."""
         bits = np.ascontiguousarray(bits, dtype=np.uint32)
-        T, total = bits.shape[0], int(self.chunk_off[-1])
+        T = bits.shape[0]
         out = np.zeros(ident.shape[:-2] + (self.N, 5), dtype=np.float64)
-        lib, p = _lib.load(), lambda name: getattr(self, name).ctypes.data
+        lib, cells = _lib.load(), C.byref(self._host_cells())
         if core:
-            tail = (bits.ctypes.data, ident.ctypes.data, self.total_rows, total, p("chunk_off"), p("row_off"), p("mids"),
-                    p("mid_cell"), p("file_cell_off"), p("cell_dur"), p("cell_ref"), p("cell_step"), self.max_cells, self.G,
-                    PATCH_COLLAR, self.SCORE_LANES, self.IDENT_BLOCKS, out.ctypes.data, int(num_threads))
-            if ident.ndim == 3:
-                _lib.check(lib.dz_tune_ident_score_core(T, self.N, *tail), "dz_tune_ident_score_core")
-            else:
-                _lib.check(lib.dz_tune_ident_score_sweep_core(T, ident.shape[1], self.N, *tail),
-                           "dz_tune_ident_score_sweep_core")
+            _lib.check(lib.dz_tune_ident_score_core(cells, T, self._points(ident), bits.ctypes.data, ident.ctypes.data,
+                                                    self.SCORE_LANES, self.IDENT_BLOCKS, out.ctypes.data, int(num_threads)),
+                       "dz_tune_ident_score_core")
         else:
-            _lib.check(lib.dz_tune_ident_score(T, self.N, bits.ctypes.data, ident.ctypes.data, self.total_rows, total,
-                                               p("file_row_off"), p("chunk_off"), p("step_rows"), p("mids"), p("mid_cell"),
-                                               p("file_cell_off"), p("cell_dur"), p("cell_ref"), p("cell_step"), self.G,
-                                               PATCH_COLLAR, out.ctypes.data, int(num_threads)), "dz_tune_ident_score")
+            _lib.check(lib.dz_tune_ident_score(cells, T, bits.ctypes.data, ident.ctypes.data, out.ctypes.data,
+                                               int(num_threads)), "dz_tune_ident_score")
         return out
 
     def _ident_fetch(self, out: torch.Tensor, err: torch.Tensor) -> np.ndarray:
         rc = int(err.cpu()[0])
         if rc:
-            who = "dz_tune_ident_score_gpu" if out.dim() == 3 else "dz_tune_ident_score_sweep_gpu"
-            raise _lib.DiartAmdError(f"{who} failed (code {rc}): {self._IDENT_ERRORS.get(rc, 'unknown')}")
+            raise _lib.DiartAmdError(f"dz_tune_ident_score_gpu failed (code {rc}): {self._IDENT_ERRORS.get(rc, 'unknown')}")
         return out.cpu().numpy()
 
     def evaluate(self, hparams, backend: Optional[str] = None, memory_budget: int = 1 << 30,
@@ -1284,9 +1284,9 @@ class _TrackTuneCache(_ReplayCache):
         return np.ascontiguousarray(t)
 
     def _host(self, taus: np.ndarray, bits: bool, components: bool, num_threads: int, core: bool = True):
-        """``(agg, bits, components)`` on host threads, from the kernels' text: ``dz_tune_vad_host`` for ``taus (T,)``,
-        ``dz_tune_vad_host_hyst`` — the lanes' state maps included — for ``taus (T, 2)``, ``dz_tune_vad_host_dur`` — the
-        lanes' span summaries too — for ``taus (T, 4)``.  ``core=False`` with ``(T, 2)`` or ``(T, 4)`` (backend="host"):
+        """``(agg, bits, components)`` on host threads, from the kernels' text: ``dz_tune_vad_host`` under the rule of
+        the columns of ``taus`` — ``(T,)``; ``(T, 2)``, the lanes' state maps included; ``(T, 4)``, the lanes' span
+        summaries too.  ``core=False`` with ``(T, 2)`` or ``(T, 4)`` (backend="host"):
         the masks come from an independent text instead — one ``dz_tail`` handle with ``dz_tail_set_offset`` per (trial,
         file), fed the track step by step, which reads the first two columns — and there are no components."""
         T = taus.shape[0]
@@ -1299,13 +1299,10 @@ class _TrackTuneCache(_ReplayCache):
         d = self._desc(lambda name: getattr(self, name).ctypes.data)
         ptr = lambda a: None if a is None else a.ctypes.data
         lib = _lib.load()
-        name = ("dz_tune_vad_host" if taus.ndim == 1 or not core else
-                "dz_tune_vad_host_dur" if taus.shape[1] == 4 else "dz_tune_vad_host_hyst")
         thresholds = np.ascontiguousarray(taus[:, 0]) if tails else taus          # (the aggregation reads none of them)
-        _lib.check(getattr(lib, name)(C.byref(d), thresholds.ctypes.data, T, agg.ctypes.data, None if tails else ptr(b),
-                                      self.mids.ctypes.data, self.mid_cell.ctypes.data, self.file_cell_off.ctypes.data,
-                                      self.dur_prefix.ctypes.data, self.ref_prefix.ctypes.data, PATCH_COLLAR,
-                                      self.SCORE_LANES, ptr(out), int(num_threads)), name)
+        _lib.check(lib.dz_tune_vad_host(C.byref(d), C.byref(self._host_cells()), thresholds.size // T, thresholds.ctypes.data,
+                                        T, agg.ctypes.data, None if tails else ptr(b), self.SCORE_LANES, ptr(out),
+                                        int(num_threads)), "dz_tune_vad_host")
         if tails and bits:
             starts = np.ascontiguousarray(self.starts, dtype=np.float64)
             res = np.ascontiguousarray(self.res, dtype=np.float64)
@@ -1322,40 +1319,29 @@ class _TrackTuneCache(_ReplayCache):
                        for name in ("seg", "chunk_off", "plan", "row_off", "row_chunk", "hamming", "mids", "mid_cell",
                                     "file_cell_off", "dur_prefix", "ref_prefix")}
             tensors["agg"] = torch.empty(self.total_rows, dtype=torch.float64, device=device)
-            desc = self._desc(lambda name: tensors[name].data_ptr())
+            ptr = lambda name: tensors[name].data_ptr() if name in tensors else None
+            desc = self._desc(ptr)
             _lib.check(_lib.load().dz_tune_vad_rows(_lib.context(device.index), C.byref(desc), tensors["agg"].data_ptr(),
                                                     torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_rows")
-            self._dev[key] = (tensors, desc)
+            self._dev[key] = (tensors, desc, self._cells(ptr))
         return self._dev[key]
 
     def _gpu(self, taus: np.ndarray, bits: bool, components: bool, device: Optional[torch.device] = None):
         if not torch.cuda.is_available():
             raise _lib.DiartAmdError("backend='gpu' needs a GPU; backend='host' replays on the host")
         device = device or torch.device("cuda", torch.cuda.current_device())
-        t, _ = self._device(device)
+        t, _, cells = self._device(device)
         T = taus.shape[0]
         d_taus = torch.from_numpy(taus).to(device)
         b = torch.empty((T, self.total_rows), dtype=torch.int32, device=device) if bits else None
         out = torch.empty((T, self.N, 5), dtype=torch.float64, device=device) if components else None
         ptr = lambda a: None if a is None else a.data_ptr()
-        if taus.ndim == 2 and taus.shape[1] == 4:
-            # (T, 4): the third instantiation, which takes the trials in host memory too and checks the durations there
-            _lib.check(_lib.load().dz_tune_vad_score_dur(
-                _lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(), taus.ctypes.data,
-                d_taus.data_ptr(), t["chunk_off"].data_ptr(), t["row_off"].data_ptr(), t["mids"].data_ptr(),
-                t["mid_cell"].data_ptr(), t["file_cell_off"].data_ptr(), t["dur_prefix"].data_ptr(),
-                t["ref_prefix"].data_ptr(), PATCH_COLLAR, ptr(out), ptr(b), torch.cuda.current_stream(device).cuda_stream),
-                "dz_tune_vad_score_dur")
-            return t["agg"], b, out
-        # (T, 2): the stateful instantiation of tune_vad_score_kernel, one workgroup per (trial, file) for the masks too
-        entry, name = ((_lib.load().dz_tune_vad_score_hyst, "dz_tune_vad_score_hyst") if taus.ndim == 2 else
-                       (_lib.load().dz_tune_vad_score, "dz_tune_vad_score"))
-        _lib.check(entry(_lib.context(device.index), T, self.N, self.total_rows, t["agg"].data_ptr(),
-                         d_taus.data_ptr(), t["chunk_off"].data_ptr(), t["row_off"].data_ptr(),
-                         t["mids"].data_ptr(), t["mid_cell"].data_ptr(),
-                         t["file_cell_off"].data_ptr(), t["dur_prefix"].data_ptr(),
-                         t["ref_prefix"].data_ptr(), PATCH_COLLAR, ptr(out), ptr(b),
-                         torch.cuda.current_stream(device).cuda_stream), name)
+        # the columns select the instantiation of tune_vad_score_kernel; (T, 4) is checked in host memory too (the other
+        # rules take no host pointer: `ndarray.ctypes` costs a microsecond between the upload and the launch)
+        cols = taus.size // T
+        _lib.check(_lib.load().dz_tune_vad_score(_lib.context(device.index), C.byref(cells), cols, T, t["agg"].data_ptr(),
+                                                 taus.ctypes.data if cols == 4 else None, d_taus.data_ptr(), ptr(out), ptr(b),
+                                                 torch.cuda.current_stream(device).cuda_stream), "dz_tune_vad_score")
         return t["agg"], b, out
 
     def replay(self, taus, backend: Optional[str] = None, num_threads: int = 8):
@@ -1382,7 +1368,7 @@ class _TrackTuneCache(_ReplayCache):
     def score(self, bits: np.ndarray, num_threads: int = 8) -> np.ndarray:
         """``(T, N, 5)`` detection error rate components of the masks of ``replay``, by ``dz_tune_score`` with one
         hypothesis speaker on the collapsed reference cells."""
-        return self._score_bits(bits, 1, num_threads)
+        return self._score_bits(bits, num_threads)
 
     def evaluate(self, taus, backend: Optional[str] = None, memory_budget: int = 1 << 30,
                  num_threads: int = 8) -> TuneResult:
@@ -1423,12 +1409,9 @@ class _TrackTuneCache(_ReplayCache):
         bits = np.ascontiguousarray(bits, dtype=np.uint32)
         taus = np.ascontiguousarray(taus, dtype=np.float64)
         out = np.zeros((bits.shape[0], self.N, 5), dtype=np.float64)
-        _lib.check(_lib.load().dz_tune_track_score_dur(bits.shape[0], self.N, bits.ctypes.data, self.total_rows,
-                                                       self.chunk_off.ctypes.data, self.row_off.ctypes.data,
-                                                       self.mids.ctypes.data, self.mid_cell.ctypes.data,
-                                                       self.file_cell_off.ctypes.data, self.cell_dur.ctypes.data,
-                                                       self.cell_ref.ctypes.data, taus.ctypes.data, PATCH_COLLAR,
-                                                       out.ctypes.data, int(num_threads)), "dz_tune_track_score_dur")
+        _lib.check(_lib.load().dz_tune_track_score_dur(C.byref(self._host_cells()), bits.shape[0], bits.ctypes.data,
+                                                       taus.ctypes.data, out.ctypes.data, int(num_threads)),
+                   "dz_tune_track_score_dur")
         return out
 
     def hypothesis(self, bits_row: np.ndarray, n: int, min_duration_on: float = 0.0,

@@ -1089,118 +1089,109 @@ int dz_tune_replay(dz_ctx* ctx, const dz_tune_desc* d, const double* d_hparams, 
 int dz_tune_replay_host(const dz_tune_desc* d, const double* hparams, int trials, double step, double latency,
                         const double* starts, const double* resolution, signed char* assign, int* status,
                         unsigned* bits, int use_core, int num_threads);
-/* Diarization error rate components (collar 0, overlap included) of every (trial, file) pair from the packed
- * frame masks, without building annotations: speech turns as Binarize forms them, same-speaker turns closer
- * than `collar` merged as Annotation.support does, then total / correct / false alarm / missed detection /
- * confusion over the file's scoring cells under the optimal one-to-one mapping.
- *   file_row_off, file_chunk_off, file_cell_off (N + 1); step_rows (chunks)
+/* The scoring geometry of a cache, the other half of a trial: where the files' steps, rows and frame middles lie and
+ * the scoring cells they are scored on.  The same for every trial and computed once; every pointer is host memory for
+ * the host entries and device memory for the device entries, as with dz_tune_desc.
+ *   file_chunk_off, file_row_off, file_cell_off (N + 1): the steps, packed rows and cells of file n
+ *   row_off (chunks + 1), step_rows (chunks): the packed rows of every step, as a prefix sum and as counts
  *   mids (total_rows + chunks): per step its rows + 1 frame middles, timestamp shift added; mid_cell: the cell
  *       that starts at that time
- *   cell_dur, cell_ref (cells): duration and bit mask of the reference speakers of every cell
- * out (T, N, 5).                                                                                        */
-int dz_tune_score(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_row_off,
-                  const int* file_chunk_off, const int* step_rows, const double* mids, const int* mid_cell,
-                  const int* file_cell_off, const double* cell_dur, const unsigned long long* cell_ref,
-                  int max_speakers, double collar, double* out, int num_threads);
+ *   cell_dur, cell_ref (cells): duration and bit mask of the reference speakers of every cell; cell_step (cells): the
+ *       step (chunk of the cache) that owns it (step c owns the cells from its first frame middle to the next step's)
+ *   dur_prefix, ref_prefix (cells + N): per file its cells + 1 prefix sums of cell_dur and of cell_dur where the
+ *       reference is active (file n starts at file_cell_off[n] + n)
+ *   max_cells: the cells of the largest file; collar: same-speaker turns closer than it are merged
+ * An entry reads the members its comment lists ("cells:") and no other: those may be NULL or 0.  A NULL among the
+ * listed pointers is refused with 2 and a message that names the entry and the member.                             */
+typedef struct dz_tune_cells {
+    const int* file_chunk_off;
+    const int* file_row_off;
+    const int* row_off;
+    const int* step_rows;
+    const double* mids;
+    const int* mid_cell;
+    const int* file_cell_off;
+    const double* cell_dur;
+    const unsigned long long* cell_ref;
+    const int* cell_step;
+    const double* dur_prefix;
+    const double* ref_prefix;
+    int n_files, total_rows, total_chunks, max_cells, max_speakers;
+    double collar;
+} dz_tune_cells;
+int dz_tune_cells_abi_size(void);
+/* Diarization error rate components (collar 0, overlap included) of every (trial, file) pair from the packed
+ * frame masks bits (T, total_rows), without building annotations: speech turns as Binarize forms them, same-speaker
+ * turns closer than `collar` merged as Annotation.support does, then total / correct / false alarm / missed detection /
+ * confusion over the file's scoring cells under the optimal one-to-one mapping.  out (T, N, 5).
+ * cells: file_row_off, file_chunk_off, step_rows, mids, mid_cell, file_cell_off, cell_dur, cell_ref; n_files,
+ * total_rows, max_speakers, collar.                                                                      */
+int dz_tune_score(const dz_tune_cells* cells, int trials, const unsigned* bits, double* out, int num_threads);
 /* dz_tune_score on the device: d_bits (T, total_rows) as dz_tune_replay wrote them stay there, and d_out
  * (T, N, 5) is all that a call leaves.  One workgroup per (trial, file) pair, score_blocks of them resident,
- * each on its own slice of d_scratch (score_blocks, max_cells + 1) uint32, max_cells = the cells of the
- * largest file; row_off (chunks + 1) is the prefix sum of step_rows, the other arrays are dz_tune_score's,
- * in device memory, the steps of a file sorted by time.  What differs from dz_tune_score is the order in
+ * each on its own slice of d_scratch (score_blocks, max_cells + 1) uint32; the steps of a file sorted by time.
+ * What differs from dz_tune_score is the order in
  * which the durations are summed (per lane, the lanes in order: the same doubles on every call).  d_err: one
  * int, 0 after the call, or dz_tune_score's return code (4 = a turn off the file's cells, 3 = the assignment
  * problem failed, 2 = a file with more than max_cells cells) of some pair; d_out is then not to be used.
- * Enqueued on `stream`, no synchronisation.                                                              */
-int dz_tune_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits, int total_rows,
-                      const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                      const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
-                      const unsigned long long* d_cell_ref, int max_cells, int max_speakers, double collar,
-                      double* d_out, unsigned* d_scratch, int score_blocks, int* d_err, void* stream);
+ * Enqueued on `stream`, no synchronisation.
+ * cells (the "kernel set"): file_chunk_off, row_off, mids, mid_cell, file_cell_off, cell_dur, cell_ref; n_files,
+ * total_rows, max_cells, max_speakers, collar.                                                            */
+int dz_tune_score_gpu(dz_ctx* ctx, const dz_tune_cells* d_cells, int trials, const unsigned* d_bits, double* d_out,
+                      unsigned* d_scratch, int score_blocks, int* d_err, void* stream);
 /* The same from host memory, compiled from the text of the kernel: the `lanes` (at most 256) lanes of a
  * workgroup played in order, "workgroup" b of score_blocks taking pairs b, b + score_blocks, ... on one
- * scratch slice, workgroups on num_threads host threads.  Returns dz_tune_score's codes.                */
-int dz_tune_score_core(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
-                       const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
-                       const double* cell_dur, const unsigned long long* cell_ref, int max_cells,
-                       int max_speakers, double collar, int lanes, int score_blocks, double* out,
-                       int num_threads);
+ * scratch slice, workgroups on num_threads host threads.  Returns dz_tune_score's codes.  cells: the kernel set. */
+int dz_tune_score_core(const dz_tune_cells* cells, int trials, const unsigned* bits, int lanes, int score_blocks,
+                       double* out, int num_threads);
 /* Tuning VoiceActivityDetection (tau_active alone): one track per chunk, so dz_tune_desc has k_local = 1,
  * seg (chunks, frames) = the max over the local speakers, and emb / pre_* unused (may be NULL).  The
  * aggregated speech score of a packed output row does not depend on tau: dz_tune_vad_rows writes
  * d_agg (total_rows) doubles once per cache (the value dz_tune_replay compares with tau when the one
  * local speaker of every buffer is mapped).  Device memory throughout, enqueued on `stream`.
- * The three dz_tune_vad_* calls serve both track pipelines: for OverlappedSpeechDetection seg is the
+ * The dz_tune_vad_* calls serve both track pipelines: for OverlappedSpeechDetection seg is the
  * second largest over the local speakers and ref_prefix sums the cells where two different reference
  * speakers are active; nothing in the arithmetic knows which of the two it is given.                   */
 int dz_tune_vad_rows(dz_ctx* ctx, const dz_tune_desc* d, double* d_agg, void* stream);
-/* T trials (d_taus (T)) x N files from d_agg: row r is speech when agg > tau; the turns, their merging and the
- * scoring cells are dz_tune_score's for one hypothesis label against a reference collapsed to one label
- * (detection error rate: the confusion is 0).  One workgroup per (trial, file); d_out (T, N, 5) is all that a
- * trial leaves.  file_chunk_off, file_cell_off (N + 1), row_off (chunks + 1), mids / mid_cell as in
- * dz_tune_score, sorted by time over the steps of a file; dur_prefix / ref_prefix (cells + N): per file its
- * cells + 1 prefix sums of cell_dur and of cell_dur where the reference is active (file n starts at
- * file_cell_off[n] + n).  d_bits (T, total_rows), if not NULL: agg > tau as 0 / 1 masks; d_out may be NULL
- * then.                                                                                                   */
-int dz_tune_vad_score(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                      const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
-                      const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
-                      const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
-                      unsigned* d_bits, void* stream);
-/* The same from host memory, compiled from the text of the kernels: agg (total_rows); bits (T, total_rows)
- * if not NULL; out (T, N, 5) if not NULL, the workgroup's `lanes` lanes played in order (the other
- * arguments may be NULL where out is).  lanes is at most 256, the workgroup of the kernel and the bound of
- * every sibling *_core entry point (the Python side only ever passes 256); more returns 2.                */
-int dz_tune_vad_host(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-                     const double* mids, const int* mid_cell, const int* file_cell_off,
-                     const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
-                     int num_threads);
-/* The track pipelines with hysteresis: d_taus / taus are (T, 2) = (tau_active, tau_offset) per trial,
- * a row is on when agg > tau_active while the track is off and > tau_offset while it is on (dz_tail_set_offset's rule),
- * the state off at every file's first step and carried across its steps.  All other arguments are those of
- * dz_tune_vad_score / dz_tune_vad_host, and so is the implementation (one pair routine, tc_track_pair in
- * csrc/tune_core.h, under another row rule: with tau_offset == tau_active these calls return the doubles of those).
- * (The device form bounds trials x files below 2^31; dz_tune_vad_score also bounds trials x total_rows, the grid of
- * its one-thread-per-row mask kernel, which the hysteresis form never launches.)
- * One workgroup per (trial, file) for the components and for the masks: the
- * lanes compose the state maps of their steps before they walk them, so every row's `on` is the sequential rule's.
- * The host form needs mids .. ref_prefix and lanes (1 .. 256) for the masks too, and returns 2 for a non-finite
- * tau_offset; the device form cannot read d_taus: its callers check them first.                                     */
-int dz_tune_vad_score_hyst(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                           const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
-                           const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
-                           const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
-                           unsigned* d_bits, void* stream);
-int dz_tune_vad_host_hyst(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-                          const double* mids, const int* mid_cell, const int* file_cell_off,
-                          const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
-                          int num_threads);
-/* The track pipelines with minimum durations, where a whole file is known: d_taus / taus are (T, 4) =
- * (tau_active, tau_offset, min_duration_on, min_duration_off) per trial.  The rows and the masks are the hysteresis
- * form's (no hysteresis: tau_offset == tau_active) — the masks are taken BEFORE the durations act; a filled gap is no
- * row.  The file's turns are merged with the collar max(collar, min_duration_off) (Annotation.support), then a merged
- * span counts unless end - start < min_duration_on, strictly, both from `mids`.  The same pair routine under a third
- * rule (TcDurRule): every lane leaves a summary of its steps, one lane composes the summaries in lane order.
- * dz_tune_vad_score_dur takes the trials twice: `taus` in host memory, which it checks before the device is touched,
- * and d_taus; its other arguments are dz_tune_vad_score_hyst's, and dz_tune_vad_host_dur's are dz_tune_vad_host_hyst's.
- * All three return 2, with a message that names the function, for a NULL pointer, trials < 1 and a duration that is
- * negative or not finite.                                                                                            */
-int dz_tune_vad_score_dur(dz_ctx* ctx, int trials, int n_files, int total_rows, const double* d_agg,
-                          const double* taus, const double* d_taus, const int* d_file_chunk_off, const int* d_row_off,
-                          const double* d_mids, const int* d_mid_cell, const int* d_file_cell_off,
-                          const double* d_dur_prefix, const double* d_ref_prefix, double collar, double* d_out,
-                          unsigned* d_bits, void* stream);
-int dz_tune_vad_host_dur(const dz_tune_desc* d, const double* taus, int trials, double* agg, unsigned* bits,
-                         const double* mids, const int* mid_cell, const int* file_cell_off,
-                         const double* dur_prefix, const double* ref_prefix, double collar, int lanes, double* out,
-                         int num_threads);
-/* The components of the same trials from an independent sequential text, behind masks made elsewhere: one host thread
+/* T trials x N files from d_agg under the row rule that `cols`, the columns of d_taus (T, cols), selects (any other
+ * value returns 2); one pair routine (tc_track_pair in csrc/tune_core.h) under three rules:
+ *   cols = 1  (tau_active): row r is speech when agg > tau.
+ *   cols = 2  (tau_active, tau_offset), hysteresis: a row is on when agg > tau_active while the track
+ *             is off and > tau_offset while it is on (dz_tail_set_offset's rule), the state off at every file's first
+ *             step and carried across its steps; the lanes compose the state maps of their steps before they walk
+ *             them, so every row's `on` is the sequential rule's.  With tau_offset == tau_active: the doubles of cols = 1.
+ *   cols = 4  (tau_active, tau_offset, min_duration_on, min_duration_off), minimum durations where a whole file is
+ *             known: the rows and the masks are those of cols = 2 — the masks are taken BEFORE the
+ *             durations act; a filled gap is no row.  The file's turns are merged with the collar max(collar,
+ *             min_duration_off) (Annotation.support), then a merged span counts unless end - start < min_duration_on,
+ *             strictly, both from `mids`: every lane leaves a summary of its steps, one lane composes the summaries in
+ *             lane order.  With zero durations: the doubles of cols = 2.
+ * The turns, their merging and the scoring cells are dz_tune_score's for one hypothesis label against a reference
+ * collapsed to one label (detection error rate: the confusion is 0).  One workgroup per (trial, file); d_out (T, N, 5)
+ * is all that a trial leaves.  d_bits (T, total_rows), if not NULL: the rows as 0 / 1 masks (cols = 1: from a kernel
+ * of one thread per row, which bounds trials x total_rows as well as trials x files); d_out may be NULL then.
+ * taus_host: the trials in host memory, required for cols = 4 and ignored otherwise: the device form cannot read
+ * d_taus, and a duration that is negative or not finite is refused before the context or any device pointer is looked
+ * at (the callers check tau_offset).  Also refused with 2: a NULL pointer, trials < 1.
+ * cells (the "track set"): file_chunk_off, row_off, mids, mid_cell, file_cell_off, dur_prefix, ref_prefix; n_files,
+ * total_rows, collar.                                                                                             */
+int dz_tune_vad_score(dz_ctx* ctx, const dz_tune_cells* d_cells, int cols, int trials, const double* d_agg,
+                      const double* taus_host, const double* d_taus, double* d_out, unsigned* d_bits, void* stream);
+/* The same from host memory, compiled from the text of the kernels: taus (T, cols); agg (total_rows), written; bits
+ * (T, total_rows) if not NULL; out (T, N, 5) if not NULL, the workgroup's `lanes` lanes played in order.  lanes is at
+ * most 256, the workgroup of the kernel and the bound of every sibling *_core entry point (the Python side only ever
+ * passes 256); more returns 2, and so does a non-finite tau_offset.  The steps and rows are d's (chunk_off, row_off).
+ * cells: mids, mid_cell, file_cell_off, dur_prefix, ref_prefix; collar — for out, and under cols = 2 and 4 for the
+ * masks too (with lanes 1 .. 256); cols = 1 with out NULL reads nothing of cells, which may be NULL then.          */
+int dz_tune_vad_host(const dz_tune_desc* d, const dz_tune_cells* cells, int cols, const double* taus, int trials,
+                     double* agg, unsigned* bits, int lanes, double* out, int num_threads);
+/* The components of cols = 4 trials from an independent sequential text, behind masks made elsewhere: one host thread
  * per (trial, file) walks the file's turns from bits (T, total_rows; bit 0) in order, merges, drops and sums the
- * cells one by one (cell_dur, cell_ref as in dz_tune_score).  Of taus (T, 4) the two durations are read.  Returns 4
- * when a turn does not start and end on the file's cells.                                                           */
-int dz_tune_track_score_dur(int trials, int n_files, const unsigned* bits, int total_rows, const int* file_chunk_off,
-                            const int* row_off, const double* mids, const int* mid_cell, const int* file_cell_off,
-                            const double* cell_dur, const unsigned long long* cell_ref, const double* taus,
-                            double collar, double* out, int num_threads);
+ * cells one by one.  Of taus (T, 4) the two durations are read.  Returns 4 when a turn does not start and end on the
+ * file's cells.  cells: file_chunk_off, row_off, mids, mid_cell, file_cell_off, cell_dur, cell_ref; n_files,
+ * total_rows, collar.                                                                                              */
+int dz_tune_track_score_dur(const dz_tune_cells* cells, int trials, const unsigned* bits, const double* taus,
+                            double* out, int num_threads);
 /* The masks of the same trials from an independent text: one dz_tail handle per (trial, file) with dz_tail_set_offset,
  * fed the file's track step by step (starts, resolution (chunks), step, latency as dz_tail_step gets them), the
  * masks read back from the turns it returns.  bits (T, total_rows).                                                  */
@@ -1213,84 +1204,49 @@ int dz_tune_vad_replay_tails(const dz_tune_desc* d, const double* taus, int tria
  * name of its voiceprint unless another speaker holds the same one with a lower best distance (ties: the lower
  * g).  match_index / match_distance (chunks, k_local): the stored match of every embedding row against the
  * gallery (-1 / NaN: none), the same for every trial; vp_ref (N, voiceprints) int8: the reference bit of file n
- * whose label is voiceprint v's name, or -1; delta_id (T).  ident (T, chunks, max_speakers) int8: the reference
+ * whose label is voiceprint v's name, or -1.  ident int8: the reference
  * bit of the name speaker g carries in that step, or -1 (no name, or a name no reference label of the file has);
- * hold (T, chunks, max_speakers) int32, if not NULL: the voiceprint itself, or -1.  A chain takes nothing from
- * its status chunk on.  dz_tune_name: device memory, one wavefront per (trial, file) chain, name_blocks
- * workgroups resident; enqueued on `stream`, no synchronisation.  Refused with 2 before anything runs: a NULL
- * pointer (d_hold excepted), trials < 1, max_speakers > 32, voiceprints < 1.                              */
-int dz_tune_name(dz_ctx* ctx, int trials, int n_files, int total_chunks, int k_local, int max_speakers,
-                 int voiceprints, const int* d_file_chunk_off, const signed char* d_assign, const int* d_status,
-                 const int* d_match_index, const float* d_match_distance, const signed char* d_vp_ref,
-                 const double* d_delta_id, signed char* d_ident, int* d_hold, int name_blocks, void* stream);
+ * hold int32, if not NULL: the voiceprint itself, or -1.  A chain takes nothing from its status chunk on.
+ * One clustering trial is named (and scored, below) at `points` (plane, threshold) points, 1 .. 256, plane-major
+ * (the sweep): point j reads plane j / (points / planes) of match_index / match_distance (planes,
+ * chunks, k_local), 1 .. 8 planes that divide the points, and threshold delta_id[t * points + j] of delta_id
+ * (T, points).  ident (T, points, chunks, max_speakers), hold likewise.  One point is points = planes = 1.
+ * dz_tune_name: device memory, one wavefront per (trial, point, file) chain, name_blocks workgroups resident; enqueued
+ * on `stream`, no synchronisation.  Refused with 2 before anything runs: a NULL pointer (d_hold excepted), trials < 1,
+ * max_speakers > 32, voiceprints < 1, points outside 1 .. 256, planes outside 1 .. 8 or not dividing the points. */
+int dz_tune_name(dz_ctx* ctx, int trials, int points, int planes, int n_files, int total_chunks, int k_local,
+                 int max_speakers, int voiceprints, const int* d_file_chunk_off, const signed char* d_assign,
+                 const int* d_status, const int* d_match_index, const float* d_match_distance,
+                 const signed char* d_vp_ref, const double* d_delta_id, signed char* d_ident, int* d_hold,
+                 int name_blocks, void* stream);
 /* The same from host memory, compiled from the text of the kernel, chains on num_threads host threads.     */
-int dz_tune_name_host(int trials, int n_files, int total_chunks, int k_local, int max_speakers, int voiceprints,
-                      const int* file_chunk_off, const signed char* assign, const int* status,
+int dz_tune_name_host(int trials, int points, int planes, int n_files, int total_chunks, int k_local, int max_speakers,
+                      int voiceprints, const int* file_chunk_off, const signed char* assign, const int* status,
                       const int* match_index, const float* match_distance, const signed char* vp_ref,
                       const double* delta_id, signed char* ident, int* hold, int num_threads);
-/* Identification error rate components of every (trial, file) pair: dz_tune_score's turns, merging and cells,
- * but the labels are compared as they are (no mapping).  cell_step (cells): the step (chunk of the cache) that
- * owns each cell (step c owns the cells from its first frame middle to the next step's); a set bit g of a cell's
- * hypothesis mask stands for ident[step][g].  Per cell with Nref reference labels, Nhyp hypothesis labels and
- * Nboth in both: total += dur Nref, correct += dur Nboth, false alarm += dur max(0, Nhyp - Nref),
+/* Identification error rate components of every (trial, file) pair at one point: dz_tune_score's turns, merging and
+ * cells, but the labels are compared as they are (no mapping).  A set bit g of a cell's hypothesis mask stands for
+ * ident[cell_step][g], ident (T, chunks, max_speakers).  Per cell with Nref reference labels, Nhyp hypothesis labels
+ * and Nboth in both: total += dur Nref, correct += dur Nboth, false alarm += dur max(0, Nhyp - Nref),
  * missed detection += dur max(0, Nref - Nhyp), confusion += dur (min(Nref, Nhyp) - Nboth).  out (T, N, 5).
- * 4 = a turn or a step off the file's cells.                                                              */
-int dz_tune_ident_score(int trials, int n_files, const unsigned* bits, const signed char* ident, int total_rows,
-                        int total_chunks, const int* file_row_off, const int* file_chunk_off,
-                        const int* step_rows, const double* mids, const int* mid_cell, const int* file_cell_off,
-                        const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
-                        int max_speakers, double collar, double* out, int num_threads);
-/* dz_tune_ident_score on the device, as dz_tune_score_gpu is dz_tune_score's: one workgroup per pair,
- * score_blocks of them resident on their slices of d_scratch (score_blocks, max_cells + 1) uint32; the sums
- * per lane, the lanes in order (the same doubles on every call).  d_err: one int, 0 after the call, or 4 / 2 as
- * dz_tune_score_gpu.  Enqueued on `stream`, no synchronisation.                                            */
-int dz_tune_ident_score_gpu(dz_ctx* ctx, int trials, int n_files, const unsigned* d_bits,
-                            const signed char* d_ident, int total_rows, int total_chunks,
-                            const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                            const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
-                            const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
-                            int max_speakers, double collar, double* d_out, unsigned* d_scratch, int score_blocks,
+ * 4 = a turn or a step off the file's cells.  The independent sequential text: the yardstick of the two below.
+ * cells: dz_tune_score's and cell_step, total_chunks.                                                       */
+int dz_tune_ident_score(const dz_tune_cells* cells, int trials, const unsigned* bits, const signed char* ident,
+                        double* out, int num_threads);
+/* The same on the device at every point of dz_tune_name's ident (T, points, chunks, max_speakers), as dz_tune_score_gpu
+ * is dz_tune_score's: one workgroup per (trial, file) pair, score_blocks of them resident on their slices of d_scratch
+ * (score_blocks, max_cells + 1) uint32; the cells' masks once and then every point's components in turn, the sums per
+ * lane, the lanes in order (the same doubles on every call, and each point's those of a call with that point alone).
+ * d_out (T, points, N, 5).  d_err: one int, 0 after the call, or 4 / 2 as dz_tune_score_gpu.  Enqueued on `stream`, no
+ * synchronisation.  Refused with 2 before anything runs: a NULL pointer, trials < 1, points outside 1 .. 256.
+ * cells: the kernel set and cell_step, total_chunks.                                                        */
+int dz_tune_ident_score_gpu(dz_ctx* ctx, const dz_tune_cells* d_cells, int trials, int points, const unsigned* d_bits,
+                            const signed char* d_ident, double* d_out, unsigned* d_scratch, int score_blocks,
                             int* d_err, void* stream);
 /* The same from host memory, compiled from the text of the kernel (the lanes of a workgroup played in order,
  * as dz_tune_score_core).                                                                                  */
-int dz_tune_ident_score_core(int trials, int n_files, const unsigned* bits, const signed char* ident,
-                             int total_rows, int total_chunks, const int* file_chunk_off, const int* row_off,
-                             const double* mids, const int* mid_cell, const int* file_cell_off,
-                             const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
-                             int max_cells, int max_speakers, double collar, int lanes, int score_blocks,
-                             double* out, int num_threads);
-/* The sweep: one clustering trial named and scored at `points` (plane, threshold) points, 1 .. 256,
- * plane-major: point j reads plane j / (points / planes) of match_index / match_distance (planes, chunks, k_local),
- * 1 .. 8 planes that divide the points, and threshold delta_id[t * points + j] of delta_id (T, points).  ident
- * (T, points, chunks, max_speakers), hold likewise or NULL, out (T, points, N, 5).  dz_tune_name_sweep: one
- * wavefront per (trial, point, file) chain; dz_tune_ident_score_sweep_gpu: one workgroup per (trial, file) pair,
- * the cells' masks once and then every point's components in turn, each point's doubles those of the one-point
- * call.  dz_tune_name and dz_tune_ident_score_gpu (and the two host forms) are these with points = planes = 1.
- * Refused with 2 before anything runs: what the one-point entries refuse, points outside 1 .. 256, planes outside
- * 1 .. 8 or not dividing the points.                                                                        */
-int dz_tune_name_sweep(dz_ctx* ctx, int trials, int points, int planes, int n_files, int total_chunks, int k_local,
-                       int max_speakers, int voiceprints, const int* d_file_chunk_off, const signed char* d_assign,
-                       const int* d_status, const int* d_match_index, const float* d_match_distance,
-                       const signed char* d_vp_ref, const double* d_delta_id, signed char* d_ident, int* d_hold,
-                       int name_blocks, void* stream);
-int dz_tune_name_sweep_host(int trials, int points, int planes, int n_files, int total_chunks, int k_local,
-                            int max_speakers, int voiceprints, const int* file_chunk_off, const signed char* assign,
-                            const int* status, const int* match_index, const float* match_distance,
-                            const signed char* vp_ref, const double* delta_id, signed char* ident, int* hold,
-                            int num_threads);
-int dz_tune_ident_score_sweep_gpu(dz_ctx* ctx, int trials, int points, int n_files, const unsigned* d_bits,
-                                  const signed char* d_ident, int total_rows, int total_chunks,
-                                  const int* d_file_chunk_off, const int* d_row_off, const double* d_mids,
-                                  const int* d_mid_cell, const int* d_file_cell_off, const double* d_cell_dur,
-                                  const unsigned long long* d_cell_ref, const int* d_cell_step, int max_cells,
-                                  int max_speakers, double collar, double* d_out, unsigned* d_scratch,
-                                  int score_blocks, int* d_err, void* stream);
-int dz_tune_ident_score_sweep_core(int trials, int points, int n_files, const unsigned* bits, const signed char* ident,
-                                   int total_rows, int total_chunks, const int* file_chunk_off, const int* row_off,
-                                   const double* mids, const int* mid_cell, const int* file_cell_off,
-                                   const double* cell_dur, const unsigned long long* cell_ref, const int* cell_step,
-                                   int max_cells, int max_speakers, double collar, int lanes, int score_blocks,
-                                   double* out, int num_threads);
+int dz_tune_ident_score_core(const dz_tune_cells* cells, int trials, int points, const unsigned* bits,
+                             const signed char* ident, int lanes, int score_blocks, double* out, int num_threads);
 
 /* Whole-file diarization: centroid-linkage agglomerative clustering of unit rows in float64, and
  * what follows the dendrogram.  A call clusters n_files files: file f owns rows rows_off[f] .. rows_off[f + 1] - 1 of

@@ -217,30 +217,30 @@ void run_track(unsigned seed, int threads) {
     for (int t = 0; t < T; ++t) pairs[t][0] = pairs[t][1] = taus[t];
     std::vector<double> agg(total_rows), agg2(total_rows), out((size_t)T * N * 5), out2(out.size());
     std::vector<unsigned> bits((size_t)T * total_rows), bits2(bits.size());
+    dz_tune_cells cells = {};   // what the track entry reads; the rest stays NULL
+    cells.mids = mids.data();
+    cells.mid_cell = mid_cell.data();
+    cells.file_cell_off = file_cell_off.data();
+    cells.dur_prefix = dur_prefix.data();
+    cells.ref_prefix = ref_prefix.data();
+    cells.collar = 0.05;
     for (int lanes : {1, 3, 256}) {
-        CHECK(dz_tune_vad_host(&d, taus, T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
-                               dur_prefix.data(), ref_prefix.data(), 0.05, lanes, out.data(), threads) == 0);
-        CHECK(dz_tune_vad_host_hyst(&d, &pairs[0][0], T, agg2.data(), bits2.data(), mids.data(), mid_cell.data(),
-                                    file_cell_off.data(), dur_prefix.data(), ref_prefix.data(), 0.05, lanes, out2.data(),
-                                    threads) == 0);
+        CHECK(dz_tune_vad_host(&d, &cells, 1, taus, T, agg.data(), bits.data(), lanes, out.data(), threads) == 0);
+        CHECK(dz_tune_vad_host(&d, &cells, 2, &pairs[0][0], T, agg2.data(), bits2.data(), lanes, out2.data(), threads) == 0);
         CHECK(memcmp(agg.data(), agg2.data(), sizeof(double) * agg.size()) == 0);
         CHECK(memcmp(bits.data(), bits2.data(), sizeof(unsigned) * bits.size()) == 0);
         CHECK(memcmp(out.data(), out2.data(), sizeof(double) * out.size()) == 0);
         for (unsigned b : bits) CHECK(b <= 1u);
         for (double v : out) CHECK(std::isfinite(v));
-        // the masks alone, the components alone (the stateless masks need none of the scoring arrays)
-        CHECK(dz_tune_vad_host(&d, taus, T, agg.data(), bits.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0.05, lanes,
-                               nullptr, threads) == 0);
-        CHECK(dz_tune_vad_host_hyst(&d, &pairs[0][0], T, agg2.data(), bits2.data(), mids.data(), mid_cell.data(),
-                                    file_cell_off.data(), dur_prefix.data(), ref_prefix.data(), 0.05, lanes, nullptr, threads) == 0);
+        // the masks alone, the components alone (the stateless masks need no scoring geometry at all)
+        CHECK(dz_tune_vad_host(&d, nullptr, 1, taus, T, agg.data(), bits.data(), lanes, nullptr, threads) == 0);
+        CHECK(dz_tune_vad_host(&d, &cells, 2, &pairs[0][0], T, agg2.data(), bits2.data(), lanes, nullptr, threads) == 0);
         CHECK(memcmp(bits.data(), bits2.data(), sizeof(unsigned) * bits.size()) == 0);
-        CHECK(dz_tune_vad_host_hyst(&d, &pairs[0][0], T, agg2.data(), nullptr, mids.data(), mid_cell.data(),
-                                    file_cell_off.data(), dur_prefix.data(), ref_prefix.data(), 0.05, lanes, out2.data(),
-                                    threads) == 0);
+        CHECK(dz_tune_vad_host(&d, &cells, 2, &pairs[0][0], T, agg2.data(), nullptr, lanes, out2.data(), threads) == 0);
         CHECK(memcmp(out.data(), out2.data(), sizeof(double) * out.size()) == 0);
     }
-    CHECK(dz_tune_vad_host(&d, taus, T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
-                           dur_prefix.data(), ref_prefix.data(), 0.05, 257, out.data(), threads) == 2);
+    CHECK(dz_tune_vad_host(&d, &cells, 1, taus, T, agg.data(), bits.data(), 257, out.data(), threads) == 2);
+    CHECK(dz_tune_vad_host(&d, &cells, 3, taus, T, agg.data(), bits.data(), 256, out.data(), threads) == 2);
 }
 
 void run_lsap(unsigned seed) {

@@ -1,5 +1,6 @@
-// The minimum-duration scoring of the track tuners on the host (csrc/tune_score.cpp: dz_tune_vad_host_dur, the text of
-// tune_vad_score_kernel<TcDurRule> with its lanes played in order, and dz_tune_track_score_dur, the sequential text)
+// The minimum-duration scoring of the track tuners on the host (csrc/tune_score.cpp: dz_tune_vad_host with four columns,
+// the text of tune_vad_score_kernel<TcDurRule> with its lanes played in order, and dz_tune_track_score_dur, the
+// sequential text)
 // on a generated cache, for AddressSanitizer + UBSan (tests/test_min_duration_host.py compiles this file with g++
 // together with the host sources and runs it).  Files of 1, 9, 70 and 300 chunks: at 256 lanes one step per lane with
 // empty lanes behind, and two steps per lane; tracks of slow waves with flat stretches, so that spans cross many lanes;
@@ -116,6 +117,17 @@ int main() {
     d.row_chunk = row_chunk.data();
     d.hamming = hamming.data();
     d.N = N, d.F = F, d.K = 1, d.D = 1, d.G = 1, d.nwin = nwin, d.total_chunks = chunks, d.total_rows = total_rows;
+    dz_tune_cells cells = {};   // (the members neither entry reads stay NULL)
+    cells.file_chunk_off = chunk_off.data();
+    cells.row_off = row_off.data();
+    cells.mids = mids.data();
+    cells.mid_cell = mid_cell.data();
+    cells.file_cell_off = file_cell_off.data();
+    cells.cell_dur = cell_dur.data();
+    cells.cell_ref = cell_ref.data();
+    cells.dur_prefix = dur_prefix.data();
+    cells.ref_prefix = ref_prefix.data();
+    cells.n_files = N, cells.total_rows = total_rows, cells.total_chunks = chunks, cells.max_speakers = 1, cells.collar = collar;
 
     const double durations[][2] = {{0.0, 0.0}, {0.2, 0.0}, {0.0, 0.3}, {1.1, 0.9}, {2.4, 0.07}, {1e4, 0.0}, {0.0, 1e4}, {0.4, 3.3}};
     const int T = (int)(sizeof(durations) / sizeof(durations[0]));
@@ -129,9 +141,8 @@ int main() {
     const int lanes[] = {256, 7, 1};
     for (int li = 0; li < 3; ++li) {
         std::fill(out.begin(), out.end(), -1.0);
-        if (dz_tune_vad_host_dur(&d, taus.data(), T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
-                                 dur_prefix.data(), ref_prefix.data(), collar, lanes[li], out.data(), li == 0 ? 3 : 1))
-            return fail("dz_tune_vad_host_dur", lanes[li]);
+        if (dz_tune_vad_host(&d, &cells, 4, taus.data(), T, agg.data(), bits.data(), lanes[li], out.data(), li == 0 ? 3 : 1))
+            return fail("dz_tune_vad_host, four columns", lanes[li]);
         if (li == 0) {
             first = out;
             bits0 = bits;
@@ -142,8 +153,7 @@ int main() {
             if (!(std::fabs(out[i] - first[i]) <= bar)) return fail("components differ between lane counts", lanes[li], (int)i);
         }
     }
-    if (dz_tune_track_score_dur(T, N, bits0.data(), total_rows, chunk_off.data(), row_off.data(), mids.data(), mid_cell.data(),
-                                file_cell_off.data(), cell_dur.data(), cell_ref.data(), taus.data(), collar, seq.data(), 3))
+    if (dz_tune_track_score_dur(&cells, T, bits0.data(), taus.data(), seq.data(), 3))
         return fail("dz_tune_track_score_dur");
     double hyp = 0.0;
     for (size_t i = 0; i < seq.size(); ++i) {
@@ -155,20 +165,15 @@ int main() {
     // the refusals: status 2 before anything is read
     std::vector<double> bad = taus;
     bad[2] = -0.1;
-    if (dz_tune_vad_host_dur(&d, bad.data(), T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
-                             dur_prefix.data(), ref_prefix.data(), collar, 256, out.data(), 1) != 2)
+    if (dz_tune_vad_host(&d, &cells, 4, bad.data(), T, agg.data(), bits.data(), 256, out.data(), 1) != 2)
         return fail("a negative duration passed");
     bad[2] = 0.0, bad[7] = NAN;
-    if (dz_tune_track_score_dur(T, N, bits0.data(), total_rows, chunk_off.data(), row_off.data(), mids.data(), mid_cell.data(),
-                                file_cell_off.data(), cell_dur.data(), cell_ref.data(), bad.data(), collar, seq.data(), 1) != 2)
+    if (dz_tune_track_score_dur(&cells, T, bits0.data(), bad.data(), seq.data(), 1) != 2)
         return fail("a NaN duration passed");
-    if (dz_tune_vad_host_dur(&d, taus.data(), T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
-                             dur_prefix.data(), ref_prefix.data(), collar, 257, out.data(), 1) != 2)
+    if (dz_tune_vad_host(&d, &cells, 4, taus.data(), T, agg.data(), bits.data(), 257, out.data(), 1) != 2)
         return fail("257 lanes passed");
-    if (dz_tune_vad_host_dur(&d, nullptr, T, agg.data(), bits.data(), mids.data(), mid_cell.data(), file_cell_off.data(),
-                             dur_prefix.data(), ref_prefix.data(), collar, 256, out.data(), 1) != 2 ||
-        dz_tune_track_score_dur(0, N, bits0.data(), total_rows, chunk_off.data(), row_off.data(), mids.data(), mid_cell.data(),
-                                file_cell_off.data(), cell_dur.data(), cell_ref.data(), taus.data(), collar, seq.data(), 1) != 2)
+    if (dz_tune_vad_host(&d, &cells, 4, nullptr, T, agg.data(), bits.data(), 256, out.data(), 1) != 2 ||
+        dz_tune_track_score_dur(&cells, 0, bits0.data(), taus.data(), seq.data(), 1) != 2)
         return fail("NULL or T < 1 passed");
     std::printf("min_duration_sanitize ok: %d trials x %d files, %d rows, hypothesis %.1f s\n", T, N, total_rows, hyp);
     return 0;

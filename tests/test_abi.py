@@ -65,6 +65,22 @@ def test_struct_layouts_match_the_library():
     mine = [C.sizeof(t) for t in (_lib.SincNetWeights, _lib.SegWeights, _lib.EmbWeights,
                                   _lib.EcapaWeights, _lib.ConvGemmDesc)]
     assert list(sizes) == mine and all(v > 0 for v in mine)
+    # the two halves of a tuning trial, each behind a size function of its own
+    assert lib.dz_tune_abi_size() == C.sizeof(_lib.TuneDesc) > 0
+    assert lib.dz_tune_cells_abi_size() == C.sizeof(_lib.TuneCells) == 12 * C.sizeof(C.c_void_p) + 5 * 4 + 4 + 8
+    header = (ROOT / "include" / "diart_amd.h").read_text()
+    body = re.search(r"typedef struct dz_tune_cells \{(.*?)\} dz_tune_cells;", header, flags=re.S).group(1)
+    members = re.findall(r"(\w+)\s*[;,]", body)
+    assert members == [name for name, _ in _lib.TuneCells._fields_], members
+
+
+def test_load_refuses_a_library_with_another_dz_tune_cells(monkeypatch):
+    """A library built from a header whose dz_tune_cells differs fails at load, with the message every stale struct gets."""
+    monkeypatch.setattr(_lib, "_lib", None)
+    stale = type("TuneCells", (C.Structure,), {"_fields_": _lib.TuneCells._fields_[:-1], "POINTERS": _lib.TuneCells.POINTERS})
+    monkeypatch.setattr(_lib, "TuneCells", stale)
+    with pytest.raises(_lib.DiartAmdError, match=r"built from a different include/diart_amd.h: sizeof\(dz_tune_cells\)"):
+        _lib.load()
 
 
 def test_header_is_plain_c_and_links_without_python(tmp_path):

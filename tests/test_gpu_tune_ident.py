@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import tune_cases as tc  # noqa: E402
+import tune_cells_cases as cc  # noqa: E402
 import tune_ident_cases as ic  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -109,15 +110,14 @@ def test_entry_points_refuse_before_the_gpu_is_touched(gpu, case):
     lib, ctx = _lib.load(), _lib.context(gpu.index)
     one = torch.zeros(64, dtype=torch.int32, device=gpu).data_ptr()
 
-    def name(T=1, G=5, V=6, assign=one):
-        return lib.dz_tune_name(ctx, T, 1, 1, 3, G, V, one, assign, one, one, one, one, one, one, None, 64, None)
+    def name(T=1, G=5, V=6, assign=one):                                 # one point: points = planes = 1
+        return lib.dz_tune_name(ctx, T, 1, 1, 1, 1, 3, G, V, one, assign, one, one, one, one, one, one, None, 64, None)
 
     for kw in (dict(T=0), dict(G=33), dict(V=0), dict(assign=None)):
         assert name(**kw) == 2 and "dz_tune_name" in lib.dz_last_error().decode(), kw
 
     def score(T=1, G=5, bits=one):
-        return lib.dz_tune_ident_score_gpu(ctx, T, 1, bits, one, 1, 1, one, one, one, one, one, one, one, one, 1, G, 0.05, one,
-                                           one, 1, one, None)
+        return lib.dz_tune_ident_score_gpu(ctx, cc.ref(cc.filled(one, G)), T, 1, bits, one, one, one, 1, one, None)
 
     for kw in (dict(T=0), dict(G=33), dict(bits=None)):
         assert score(**kw) == 2 and "dz_tune_ident_score_gpu" in lib.dz_last_error().decode(), kw

@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import tune_cases as tc  # noqa: E402
+import tune_cells_cases as cc  # noqa: E402
 import tune_ident_cases as ic  # noqa: E402
 import tune_sweep_cases as sc  # noqa: E402
 
@@ -106,17 +107,16 @@ def test_entry_points_refuse_before_the_gpu_is_touched(gpu, case):
     one = torch.zeros(64, dtype=torch.int32, device=gpu).data_ptr()
 
     def name(T=1, J=10, P=2, G=5, ptr=one):
-        return lib.dz_tune_name_sweep(ctx, T, J, P, 1, 1, 3, G, 6, one, ptr, one, one, one, one, one, one, None, 64, None)
+        return lib.dz_tune_name(ctx, T, J, P, 1, 1, 3, G, 6, one, ptr, one, one, one, one, one, one, None, 64, None)
 
     for kw in (dict(T=0), dict(J=0), dict(J=257), dict(P=0), dict(P=9), dict(J=10, P=3), dict(G=33), dict(ptr=None)):
-        assert name(**kw) == 2 and "dz_tune_name_sweep:" in lib.dz_last_error().decode(), kw
+        assert name(**kw) == 2 and "dz_tune_name:" in lib.dz_last_error().decode(), kw
 
     def score(T=1, J=10, G=5, ptr=one):
-        return lib.dz_tune_ident_score_sweep_gpu(ctx, T, J, 1, ptr, one, 1, 1, one, one, one, one, one, one, one, one, 1, G,
-                                                 0.05, one, one, 1, one, None)
+        return lib.dz_tune_ident_score_gpu(ctx, cc.ref(cc.filled(one, G)), T, J, ptr, one, one, one, 1, one, None)
 
     for kw in (dict(T=0), dict(J=0), dict(J=257), dict(G=33), dict(ptr=None)):
-        assert score(**kw) == 2 and "dz_tune_ident_score_sweep_gpu" in lib.dz_last_error().decode(), kw
+        assert score(**kw) == 2 and "dz_tune_ident_score_gpu" in lib.dz_last_error().decode(), kw
 
 
 def test_optimizer_sweep(gpu, case, tmp_path):

@@ -362,13 +362,11 @@ def test_refusals(tmp_path):
     import ctypes as C
     d = cache._desc(lambda name: getattr(cache, name).ctypes.data)
     agg, bits = np.empty(cache.total_rows), np.empty((1, cache.total_rows), dtype=np.uint32)
-    assert lib.dz_tune_vad_host_hyst(C.byref(d), taus.ctypes.data, 1, agg.ctypes.data, bits.ctypes.data,
-                                     cache.mids.ctypes.data, cache.mid_cell.ctypes.data, cache.file_cell_off.ctypes.data,
-                                     cache.dur_prefix.ctypes.data, cache.ref_prefix.ctypes.data, 0.05, 256, None, 1) == 2
-    assert "dz_tune_vad_host_hyst" in lib.dz_last_error().decode()
-    assert lib.dz_tune_vad_host(C.byref(d), np.array([0.6]).ctypes.data, 1, agg.ctypes.data, bits.ctypes.data,
-                                cache.mids.ctypes.data, cache.mid_cell.ctypes.data, cache.file_cell_off.ctypes.data,
-                                cache.dur_prefix.ctypes.data, cache.ref_prefix.ctypes.data, 0.05, 257, None, 1) == 2   # lanes
+    cells = C.byref(cache._host_cells())
+    assert lib.dz_tune_vad_host(C.byref(d), cells, 2, taus.ctypes.data, 1, agg.ctypes.data, bits.ctypes.data, 256, None, 1) == 2
+    assert "dz_tune_vad_host: tau_offset" in lib.dz_last_error().decode()
+    assert lib.dz_tune_vad_host(C.byref(d), cells, 1, np.array([0.6]).ctypes.data, 1, agg.ctypes.data, bits.ctypes.data,
+                                257, None, 1) == 2   # lanes
     assert "dz_tune_vad_host:" in lib.dz_last_error().decode()
     assert lib.dz_tune_vad_replay_tails(C.byref(d), taus.ctypes.data, 1, 0.5, 2.5, cache.starts.ctypes.data,
                                         cache.res.ctypes.data, bits.ctypes.data, 1) == 2

@@ -213,26 +213,24 @@ def test_refusals(tmp_path):
     out = np.zeros((1, cache.N, 5))
     p = lambda a: a.ctypes.data
 
+    cells = C.byref(cache._host_cells())
+
     def host_dur(taus, trials=1, lanes=256, desc=d):
-        return lib.dz_tune_vad_host_dur(None if desc is None else C.byref(desc), None if taus is None else p(taus), trials,
-                                        p(agg), p(bits), p(cache.mids), p(cache.mid_cell), p(cache.file_cell_off),
-                                        p(cache.dur_prefix), p(cache.ref_prefix), 0.05, lanes, p(out), 1)
+        return lib.dz_tune_vad_host(None if desc is None else C.byref(desc), cells, 4, None if taus is None else p(taus),
+                                    trials, p(agg), p(bits), lanes, p(out), 1)
 
     def track_dur(taus, trials=1, masks=bits):
-        return lib.dz_tune_track_score_dur(trials, cache.N, None if masks is None else p(masks), cache.total_rows,
-                                           p(cache.chunk_off), p(cache.row_off), p(cache.mids), p(cache.mid_cell),
-                                           p(cache.file_cell_off), p(cache.cell_dur), p(cache.cell_ref),
-                                           None if taus is None else p(taus), 0.05, p(out), 1)
+        return lib.dz_tune_track_score_dur(cells, trials, None if masks is None else p(masks),
+                                           None if taus is None else p(taus), p(out), 1)
 
     def score_dur(taus, trials=1, ctx=None):
         # without a context the call is refused before the device is touched: this runs on a machine without a GPU
-        return lib.dz_tune_vad_score_dur(ctx, trials, cache.N, cache.total_rows, None, None if taus is None else p(taus),
-                                         None, None, None, None, None, None, None, None, 0.05, None, None, None)
+        return lib.dz_tune_vad_score(ctx, None, 4, trials, None, None if taus is None else p(taus), None, None, None, None)
 
     good = np.array([[0.6, 0.4, 0.1, 0.2]])
     assert host_dur(good) == 0 and track_dur(good) == 0
-    for call, name in ((host_dur, "dz_tune_vad_host_dur"), (track_dur, "dz_tune_track_score_dur"),
-                       (score_dur, "dz_tune_vad_score_dur")):
+    for call, name in ((host_dur, "dz_tune_vad_host"), (track_dur, "dz_tune_track_score_dur"),
+                       (score_dur, "dz_tune_vad_score")):
         for column in (2, 3):
             for bad in (np.nan, np.inf, -np.inf, -1e-300):
                 quad = good.copy()
@@ -243,10 +241,10 @@ def test_refusals(tmp_path):
         assert call(None) == 2 and name in lib.dz_last_error().decode()
         assert call(good, trials=0) == 2 and name in lib.dz_last_error().decode()
         assert call(good, trials=-3) == 2 and name in lib.dz_last_error().decode()
-    assert score_dur(good) == 2 and "dz_tune_vad_score_dur: NULL" in lib.dz_last_error().decode()     # (no context)
-    assert host_dur(good, desc=None) == 2 and "dz_tune_vad_host_dur" in lib.dz_last_error().decode()
+    assert score_dur(good) == 2 and "dz_tune_vad_score: NULL" in lib.dz_last_error().decode()     # (no context)
+    assert host_dur(good, desc=None) == 2 and "dz_tune_vad_host:" in lib.dz_last_error().decode()
     assert track_dur(good, masks=None) == 2 and "dz_tune_track_score_dur: NULL" in lib.dz_last_error().decode()
-    assert host_dur(good, lanes=257) == 2 and "dz_tune_vad_host_dur" in lib.dz_last_error().decode()
+    assert host_dur(good, lanes=257) == 2 and "dz_tune_vad_host:" in lib.dz_last_error().decode()
     assert host_dur(np.array([[0.6, np.nan, 0.0, 0.0]])) == 2 and "tau_offset" in lib.dz_last_error().decode()
     # the configurations, the accumulator, the file batch
     for kind in ("vad", "osd"):
@@ -477,7 +475,7 @@ def test_accumulator_and_benchmark_loop(tmp_path):
 # ---------------------------------------------------------------------------------------------------- 6. sanitizers
 def test_host_texts_are_clean_under_asan_and_ubsan(tmp_path):
     """tests/native/min_duration_sanitize.cpp, a program of its own, compiled with g++ -fsanitize=address,undefined
-    together with the host sources: dz_tune_vad_host_dur and dz_tune_track_score_dur on a generated cache.  No Python
+    together with the host sources: dz_tune_vad_host (four columns) and dz_tune_track_score_dur on a generated cache.  No Python
     runs under the sanitizer."""
     cxx = shutil.which("g++")
     if cxx is None:

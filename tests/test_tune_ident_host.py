@@ -2,6 +2,7 @@
 gallery.SpeakerNames in Python, its components against metrics.IdentificationErrorRate on the named hypothesis, the
 metric on a hand-made example, the file format, the refusals, Optimizer and the command line.  The cases are
 tests/tune_ident_cases.py's."""
+import ctypes as C
 import json
 import sys
 from pathlib import Path
@@ -226,9 +227,14 @@ def test_c_entry_points_refuse_before_anything_runs(case):
     bits = np.zeros((1, cache.total_rows), dtype=np.uint32)
     out = np.zeros((1, 3, 5))
 
-    def name_host(T=1, G=5, V=6, assign_ptr=p(assign)):
-        return lib.dz_tune_name_host(T, 3, total, 3, G, V, p(cache.chunk_off), assign_ptr, p(status), p(cache.match_index),
-                                     p(cache.match_distance), p(cache.vp_ref), p(delta), p(ident), None, 1)
+    def cells(G):
+        c = _lib.TuneCells.from_buffer_copy(cache._host_cells())
+        c.max_speakers = G
+        return C.byref(c)
+
+    def name_host(T=1, G=5, V=6, assign_ptr=p(assign)):                  # one point: points = planes = 1
+        return lib.dz_tune_name_host(T, 1, 1, 3, total, 3, G, V, p(cache.chunk_off), assign_ptr, p(status),
+                                     p(cache.match_index), p(cache.match_distance), p(cache.vp_ref), p(delta), p(ident), None, 1)
 
     assert name_host() == 0                                              # (hold may be NULL)
     for kw in (dict(T=0), dict(G=33), dict(V=0), dict(assign_ptr=None)):
@@ -236,14 +242,8 @@ def test_c_entry_points_refuse_before_anything_runs(case):
 
     def score(fn, T=1, G=5, bits_ptr=p(bits)):
         if fn == "dz_tune_ident_score":
-            return lib.dz_tune_ident_score(T, 3, bits_ptr, p(ident), cache.total_rows, total, p(cache.file_row_off),
-                                           p(cache.chunk_off), p(cache.step_rows), p(cache.mids), p(cache.mid_cell),
-                                           p(cache.file_cell_off), p(cache.cell_dur), p(cache.cell_ref), p(cache.cell_step), G,
-                                           0.05, p(out), 1)
-        return lib.dz_tune_ident_score_core(T, 3, bits_ptr, p(ident), cache.total_rows, total, p(cache.chunk_off),
-                                            p(cache.row_off), p(cache.mids), p(cache.mid_cell), p(cache.file_cell_off),
-                                            p(cache.cell_dur), p(cache.cell_ref), p(cache.cell_step), cache.max_cells, G, 0.05,
-                                            256, 4, p(out), 1)
+            return lib.dz_tune_ident_score(cells(G), T, bits_ptr, p(ident), p(out), 1)
+        return lib.dz_tune_ident_score_core(cells(G), T, 1, bits_ptr, p(ident), 256, 4, p(out), 1)
 
     for fn in ("dz_tune_ident_score", "dz_tune_ident_score_core"):
         assert score(fn) == 0
@@ -252,13 +252,10 @@ def test_c_entry_points_refuse_before_anything_runs(case):
     # the device entry points: every pointer here is host memory or NULL, so they must refuse before touching it
     for kw in (dict(T=0), dict(G=33), dict(V=0), dict(T=1)):
         T, G, V = kw.get("T", 1), kw.get("G", 5), kw.get("V", 6)
-        rc = lib.dz_tune_name(None, T, 3, total, 3, G, V, p(cache.chunk_off), p(assign), p(status), p(cache.match_index),
+        rc = lib.dz_tune_name(None, T, 1, 1, 3, total, 3, G, V, p(cache.chunk_off), p(assign), p(status), p(cache.match_index),
                               p(cache.match_distance), p(cache.vp_ref), p(delta), p(ident), None, 64, None)
         assert rc == 2 and "dz_tune_name" in last_error(), kw
-    rc = lib.dz_tune_ident_score_gpu(None, 1, 3, p(bits), p(ident), cache.total_rows, total, p(cache.chunk_off),
-                                     p(cache.row_off), p(cache.mids), p(cache.mid_cell), p(cache.file_cell_off),
-                                     p(cache.cell_dur), p(cache.cell_ref), p(cache.cell_step), cache.max_cells, 5, 0.05, p(out),
-                                     None, 4, None, None)
+    rc = lib.dz_tune_ident_score_gpu(None, cells(5), 1, 1, p(bits), p(ident), p(out), None, 4, None, None)
     assert rc == 2 and "dz_tune_ident_score_gpu" in last_error()
 
 

@@ -3,6 +3,7 @@ normalised IdentTuneCache are the float64 statement's, the sweep's names are gal
 Python, evaluate_sweep is evaluate point by point (backend "core": bit for bit; "host", the loop of the sequential
 text: within 1e-9 x the pair's total) and metrics.IdentificationErrorRate on the named hypothesis, and the Optimizer
 keeps every trial's best point."""
+import ctypes as C
 import json
 import sys
 import types
@@ -264,40 +265,38 @@ def test_c_entry_points_refuse_before_anything_runs(case):
     out = np.zeros((1, 256, 3, 5))
     bad = (dict(T=0), dict(J=0), dict(J=257), dict(P=0), dict(P=9), dict(J=10, P=3), dict(G=33), dict(ptr=None))
 
+    def cells(G=5, max_cells=cache.max_cells):
+        c = _lib.TuneCells.from_buffer_copy(cache._host_cells())
+        c.max_speakers, c.max_cells = G, max_cells
+        return C.byref(c)
+
     def name(fn, T=1, J=10, P=2, G=5, ptr=p(assign)):
         args = (T, J, P, 3, total, 3, G, 6, p(cache.chunk_off), ptr, p(status), p(cache.plane_index),
                 p(cache.plane_distance), p(cache.vp_ref), p(delta), p(ident), None)
-        if fn == "dz_tune_name_sweep":
-            return lib.dz_tune_name_sweep(None, *args, 64, None)
-        return lib.dz_tune_name_sweep_host(*args, 1)
+        if fn == "dz_tune_name":
+            return lib.dz_tune_name(None, *args, 64, None)
+        return lib.dz_tune_name_host(*args, 1)
 
-    def score(fn, T=1, J=10, G=5, ptr=p(bits), **_):
-        args = (T, J, 3, ptr, p(ident), cache.total_rows, total, p(cache.chunk_off), p(cache.row_off), p(cache.mids),
-                p(cache.mid_cell), p(cache.file_cell_off), p(cache.cell_dur), p(cache.cell_ref), p(cache.cell_step),
-                cache.max_cells, G, 0.05)
-        if fn == "dz_tune_ident_score_sweep_gpu":
-            return lib.dz_tune_ident_score_sweep_gpu(None, *args, p(out), p(bits), 4, p(status), None)
-        return lib.dz_tune_ident_score_sweep_core(*args, 256, 4, p(out), 1)
+    def score(fn, T=1, J=10, G=5, ptr=p(bits), max_cells=cache.max_cells, **_):
+        if fn == "dz_tune_ident_score_gpu":
+            return lib.dz_tune_ident_score_gpu(None, cells(G), T, J, ptr, p(ident), p(out), p(bits), 4, p(status), None)
+        return lib.dz_tune_ident_score_core(cells(G, max_cells), T, J, ptr, p(ident), 256, 4, p(out), 1)
 
-    assert name("dz_tune_name_sweep_host") == 0 and name("dz_tune_name_sweep_host", J=256, P=1) == 0
-    assert score("dz_tune_ident_score_sweep_core") == 0 and score("dz_tune_ident_score_sweep_core", J=256) == 0
+    assert name("dz_tune_name_host") == 0 and name("dz_tune_name_host", J=256, P=1) == 0
+    assert score("dz_tune_ident_score_core") == 0 and score("dz_tune_ident_score_core", J=256) == 0
     for kw in bad:
-        assert name("dz_tune_name_sweep_host", **kw) == 2 and "dz_tune_name_sweep_host" in last_error(), kw
+        assert name("dz_tune_name_host", **kw) == 2 and "dz_tune_name_host" in last_error(), kw
         if "P" in kw:
             continue                                                      # (the scoring entries take no planes)
-        assert score("dz_tune_ident_score_sweep_core", **kw) == 2 and "dz_tune_ident_score_sweep_core" in last_error(), kw
-    # a failure while it runs names the entry too: a scratch slice smaller than a file's cells
-    args = (1, 10, 3, p(bits), p(ident), cache.total_rows, total, p(cache.chunk_off), p(cache.row_off), p(cache.mids),
-            p(cache.mid_cell), p(cache.file_cell_off), p(cache.cell_dur), p(cache.cell_ref), p(cache.cell_step), 1, 5, 0.05,
-            256, 4, p(out), 1)
-    assert lib.dz_tune_ident_score_sweep_core(*args) == 2
-    assert "dz_tune_ident_score_sweep_core: a file has more scoring cells" in last_error()
-    assert lib.dz_tune_ident_score_core(*args[:1], *args[2:]) == 2
-    assert "dz_tune_ident_score_core: a file has more scoring cells" in last_error()
+        assert score("dz_tune_ident_score_core", **kw) == 2 and "dz_tune_ident_score_core" in last_error(), kw
+    # a failure while it runs names the entry too: a scratch slice smaller than a file's cells, at ten points and at one
+    for points in (10, 1):
+        assert score("dz_tune_ident_score_core", J=points, max_cells=1) == 2
+        assert "dz_tune_ident_score_core: a file has more scoring cells" in last_error()
     # the device entries: without a GPU there is no context, and a NULL one is all that can be refused here; their other
     # refusals are held on the GPU (tests/test_gpu_tune_sweep.py), with a live context
-    assert name("dz_tune_name_sweep") == 2 and "dz_tune_name_sweep: NULL argument" in last_error()
-    assert score("dz_tune_ident_score_sweep_gpu") == 2 and "dz_tune_ident_score_sweep_gpu: NULL argument" in last_error()
+    assert name("dz_tune_name") == 2 and "dz_tune_name: NULL argument" in last_error()
+    assert score("dz_tune_ident_score_gpu") == 2 and "dz_tune_ident_score_gpu: NULL argument" in last_error()
 
 
 def _optimizer(tmp_path, cache, **kw):

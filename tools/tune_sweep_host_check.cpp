@@ -1,5 +1,6 @@
-// A stand-alone check of the sweep's host entry points for sanitizer builds: dz_tune_name_sweep_host
-// and dz_tune_ident_score_sweep_core on a seeded case, each against the loop of the one-point entry it generalises.
+// A stand-alone check of the sweep's host entry points for sanitizer builds: dz_tune_name_host and
+// dz_tune_ident_score_core at several points on a seeded case, each against the loop of its own points = 1 calls, and
+// the components against dz_tune_ident_score, the sequential text, within 1e-9 x the pair's total.
 // No GPU, no Python.  Build it with the host sources it needs, for example
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Idiart_amd/csrc \
@@ -55,18 +56,18 @@ int main() {
     const size_t plane = (size_t)total * G;
     std::vector<signed char> ident((size_t)T * J * plane, 99), ident1((size_t)T * plane);
     std::vector<int> hold((size_t)T * J * plane, 99), hold1((size_t)T * plane);
-    if (dz_tune_name_sweep_host(T, J, P, N, total, K, G, V, chunk_off, assign.data(), status.data(), index.data(), dist.data(),
-                                vp_ref.data(), thr.data(), ident.data(), hold.data(), 3)) {
-        std::printf("dz_tune_name_sweep_host failed: %s\n", dz_last_error());
+    if (dz_tune_name_host(T, J, P, N, total, K, G, V, chunk_off, assign.data(), status.data(), index.data(), dist.data(),
+                          vp_ref.data(), thr.data(), ident.data(), hold.data(), 3)) {
+        std::printf("dz_tune_name_host at %d points failed: %s\n", J, dz_last_error());
         return 1;
     }
     int named = 0;
     for (int j = 0; j < J; ++j) {
         std::vector<double> d1(T, thresholds[j % Q]);
         const size_t off = (size_t)(j / Q) * total * K;
-        if (dz_tune_name_host(T, N, total, K, G, V, chunk_off, assign.data(), status.data(), index.data() + off,
+        if (dz_tune_name_host(T, 1, 1, N, total, K, G, V, chunk_off, assign.data(), status.data(), index.data() + off,
                               dist.data() + off, vp_ref.data(), d1.data(), ident1.data(), hold1.data(), 1)) {
-            std::printf("dz_tune_name_host failed: %s\n", dz_last_error());
+            std::printf("dz_tune_name_host at one point failed: %s\n", dz_last_error());
             return 1;
         }
         for (int t = 0; t < T; ++t)
@@ -81,7 +82,7 @@ int main() {
     }
 
     // ---- the score: steps that follow each other, cell i of a file is [0.1 i, 0.1 (i + 1))
-    std::vector<int> row_off(total + 1), mid_cell, file_cell_off(N + 1, 0), cell_step;
+    std::vector<int> row_off(total + 1), step_rows(total, R), mid_cell, file_cell_off(N + 1, 0), cell_step;
     std::vector<double> mids, cell_dur;
     std::vector<unsigned long long> cell_ref;
     for (int c = 0; c <= total; ++c) row_off[c] = c * R;
@@ -103,21 +104,32 @@ int main() {
     const int max_cells = 7 * R;
     std::vector<unsigned> bits((size_t)T * rows);
     for (auto& b : bits) b = (unsigned)draw(0, 31) & (unsigned)draw(0, 31);
-    std::vector<double> out((size_t)T * J * N * 5, -1.0), out1((size_t)T * N * 5);
-    if (dz_tune_ident_score_sweep_core(T, J, N, bits.data(), ident.data(), rows, total, chunk_off, row_off.data(), mids.data(),
-                                       mid_cell.data(), file_cell_off.data(), cell_dur.data(), cell_ref.data(),
-                                       cell_step.data(), max_cells, G, 0.15, lanes, blocks, out.data(), 2)) {
-        std::printf("dz_tune_ident_score_sweep_core failed: %s\n", dz_last_error());
+    std::vector<double> out((size_t)T * J * N * 5, -1.0), out1((size_t)T * N * 5), seq((size_t)T * N * 5);
+    const int file_row_off[N + 1] = {0, chunk_off[1] * R, rows};
+    dz_tune_cells cells = {};   // (the track tuners' prefix sums stay NULL: nothing here reads them)
+    cells.file_chunk_off = chunk_off;
+    cells.file_row_off = file_row_off;
+    cells.row_off = row_off.data();
+    cells.step_rows = step_rows.data();
+    cells.mids = mids.data();
+    cells.mid_cell = mid_cell.data();
+    cells.file_cell_off = file_cell_off.data();
+    cells.cell_dur = cell_dur.data();
+    cells.cell_ref = cell_ref.data();
+    cells.cell_step = cell_step.data();
+    cells.n_files = N, cells.total_rows = rows, cells.total_chunks = total, cells.max_cells = max_cells;
+    cells.max_speakers = G, cells.collar = 0.15;
+    if (dz_tune_ident_score_core(&cells, T, J, bits.data(), ident.data(), lanes, blocks, out.data(), 2)) {
+        std::printf("dz_tune_ident_score_core at %d points failed: %s\n", J, dz_last_error());
         return 1;
     }
     double correct = 0.0;
     for (int j = 0; j < J; ++j) {
         for (int t = 0; t < T; ++t)
             std::memcpy(ident1.data() + t * plane, ident.data() + ((size_t)t * J + j) * plane, plane);
-        if (dz_tune_ident_score_core(T, N, bits.data(), ident1.data(), rows, total, chunk_off, row_off.data(), mids.data(),
-                                     mid_cell.data(), file_cell_off.data(), cell_dur.data(), cell_ref.data(),
-                                     cell_step.data(), max_cells, G, 0.15, lanes, blocks, out1.data(), 1)) {
-            std::printf("dz_tune_ident_score_core failed: %s\n", dz_last_error());
+        if (dz_tune_ident_score_core(&cells, T, 1, bits.data(), ident1.data(), lanes, blocks, out1.data(), 1) ||
+            dz_tune_ident_score(&cells, T, bits.data(), ident1.data(), seq.data(), 2)) {
+            std::printf("dz_tune_ident_score_core at one point or dz_tune_ident_score failed: %s\n", dz_last_error());
             return 1;
         }
         for (int t = 0; t < T; ++t)
@@ -127,23 +139,25 @@ int main() {
                     std::printf("components differ at trial %d point %d entry %d: %.17g, %.17g\n", t, j, i, a, b);
                     return 1;
                 }
+                const double total_s = seq[(size_t)t * N * 5 + i / 5 * 5], c = seq[(size_t)t * N * 5 + i];
+                if (!(std::fabs(a - c) <= 1e-9 * (total_s > 1.0 ? total_s : 1.0))) {
+                    std::printf("the sequential text differs at trial %d point %d entry %d: %.17g, %.17g\n", t, j, i, a, c);
+                    return 1;
+                }
                 if (i % 5 == 1) correct += a;
             }
     }
     // ---- the refusals touch nothing
-    const int refused = dz_tune_name_sweep_host(T, 257, P, N, total, K, G, V, chunk_off, assign.data(), status.data(),
-                                                index.data(), dist.data(), vp_ref.data(), thr.data(), ident.data(), nullptr, 1) +
-                        dz_tune_name_sweep_host(T, J, 4, N, total, K, G, V, chunk_off, assign.data(), status.data(),
-                                                index.data(), dist.data(), vp_ref.data(), thr.data(), ident.data(), nullptr, 1) +
-                        dz_tune_ident_score_sweep_core(T, 0, N, bits.data(), ident.data(), rows, total, chunk_off, row_off.data(),
-                                                       mids.data(), mid_cell.data(), file_cell_off.data(), cell_dur.data(),
-                                                       cell_ref.data(), cell_step.data(), max_cells, G, 0.15, lanes, blocks,
-                                                       out.data(), 1);
+    const int refused = dz_tune_name_host(T, 257, P, N, total, K, G, V, chunk_off, assign.data(), status.data(), index.data(),
+                                          dist.data(), vp_ref.data(), thr.data(), ident.data(), nullptr, 1) +
+                        dz_tune_name_host(T, J, 4, N, total, K, G, V, chunk_off, assign.data(), status.data(), index.data(),
+                                          dist.data(), vp_ref.data(), thr.data(), ident.data(), nullptr, 1) +
+                        dz_tune_ident_score_core(&cells, T, 0, bits.data(), ident.data(), lanes, blocks, out.data(), 1);
     if (refused != 6 || named == 0 || !(correct > 0.0)) {
         std::printf("refusals %d (6 expected), %d named slots, correct %.3f s\n", refused, named, correct);
         return 1;
     }
-    std::printf("%d trials x %d points: names and components of the sweep equal the one-point entries' (%d named slots, "
+    std::printf("%d trials x %d points: names and components of the sweep equal the one-point calls' (%d named slots, "
                 "%.1f s correct); 3 refusals\n", T, J, named, correct);
     return 0;
 }

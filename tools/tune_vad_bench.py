@@ -255,7 +255,7 @@ def main():
                         cells=int(cache.file_cell_off[-1]), sorted_steps=cache.sorted_steps)
     # ---- the rows kernel: once per cache and device (the upload of the cache's arrays is in the first figure only)
     t = time.perf_counter()
-    tensors, desc = cache._device(device)
+    tensors, desc, _ = cache._device(device)
     torch.cuda.synchronize(device)
     out["upload_and_rows_ms"] = 1e3 * (time.perf_counter() - t)
     lib, ctx = _lib.load(), _lib.context(device.index)
