@@ -156,6 +156,7 @@ SIGNATURES = {
     "dz_seg_use_wave_stats": (C.c_int, [vp, vp]),
     "dz_emb_use_wave_stats": (C.c_int, [vp, vp]),
     "dz_emb_pool": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "dz_emb_peek": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dz_emb_destroy": (C.c_int, [vp]),
     "dz_ecapa_frames_for": (C.c_int, [C.c_int]),
     "dz_ecapa_create": (C.c_int, [vp, C.POINTER(EcapaWeights), C.c_int, C.c_int, C.POINTER(vp)]),

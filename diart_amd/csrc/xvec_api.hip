@@ -18,6 +18,8 @@ struct dz_emb {
     // stops after tdnn4 and leaves tdnn5 to the call that brings the pooling weights
     int pending_B;            // > 0: frames of that many chunks are waiting at tdnn4's output
     const float* pending_in;  // tdnn4's planes
+    int lastB, last_rows;     // chunks of the last dz_emb_frames, rows of the last pooling (0: none yet): dz_emb_peek
+    int info[16];             // dz_emb_peek's record (buffer 8), filled by the peek itself
 };
 static const int kTdnnTaps[5] = {5, 3, 3, 1, 1};
 static const int kTdnnDil[5] = {1, 2, 3, 1, 1};
@@ -63,6 +65,7 @@ extern "C" int dz_emb_create(dz_ctx* ctx, const dz_emb_weights* w, int max_batch
     e->ctx = ctx; e->w = *w; e->g = g; e->Bm = max_batch; e->arena = nullptr; e->ext_stats = nullptr; e->cur_stats = nullptr;
     e->ext_conv0_B = 0;
     e->pending_B = 0; e->pending_in = nullptr;
+    e->lastB = e->last_rows = 0;
     e->pre = w->tw_split[0] && w->tw_split[1] && w->tw_split[2] &&
              w->tw_split[3] && w->tw_split[4];
     int t = g.P2;
@@ -111,6 +114,7 @@ static int emb_frames(dz_emb* e, const float* d_wave, long long stride, int B, h
     if ((rc = run_sincnet(w.sinc, e->g, e->ss, d_wave, stride, B, st, src, ext, pair))) return rc;
     e->cur_stats = ext ? ext : e->ss.stats;
     e->pending_B = 0;
+    e->lastB = B; e->last_rows = 0;
     // e->pre: tdnn1 writes its output as f16 (hi, lo) planes (same bytes, same buffers), tdnn2..5 run
     // on k_gemm_pre.hip, tdnn5 writes the f32 features the statistics pooling reads
     if (src == SINC_OUT_NORM_ON_LOAD) {      // tdnn1 normalises on load with per-chunk statistics, so it runs per chunk
@@ -175,6 +179,7 @@ static int emb_head(dz_emb* e, const float* d_weights, int Fw, int rows, int row
                                        e->pooled, kPoolLd, st)))
             return rc;
     }
+    e->last_rows = rows;
     // M = rows is tiny (3 per chunk): split K 16 ways so 128 workgroups share the 3008-deep
     // contraction, then reduce the partials in fixed order (+ L2 normalisation) in one pass
     const dz_layer lin = {e->w.emb_w, e->w.emb_b, nullptr, nullptr, nullptr};
@@ -245,6 +250,39 @@ extern "C" int dz_emb_pool(dz_emb* e, const float* d_weights, int batch, int num
     DzRangeScope range_scope(e->ctx->oflag_dev);
     return emb_head(e, d_weights, weight_frames, batch * num_speakers, num_speakers, normalize,
                     d_out, (hipStream_t)stream);
+}
+
+// Read-only views of the handle's buffers as the last call left them (parity tests): no copy, no launch.  The buffers
+// and the record are described at the declaration (include/diart_amd.h).
+extern "C" int dz_emb_peek(dz_emb* e, int which, const void** d_ptr, long long* count, int* frames) {
+    DZ_REQUIRE(e && d_ptr && count, "dz_emb_peek: NULL argument");
+    const SincOut src = sinc_out_source(e->w.sinc, e->pre, e->w.tw0_split_kb);
+    const long long B = e->lastB, rows = B * e->g.P2;
+    const bool x5_valid = B > 0 && e->pending_B == 0;
+    int fr = e->g.P2;
+    switch (which) {
+        case 0: *d_ptr = src == SINC_OUT_NORM_ON_LOAD ? e->ss.y2 : e->ss.y2s; *count = rows * 64; break;
+        case 1: *d_ptr = e->a; *count = rows * 512; fr = e->T[2]; break;
+        case 2: *d_ptr = e->b; *count = rows * 512; fr = e->T[3]; break;
+        case 3: *d_ptr = x5_valid ? e->x5 : nullptr; *count = x5_valid ? rows * 1536 : 0; fr = e->T[4]; break;
+        case 4: *d_ptr = e->pooled; *count = (long long)e->last_rows * kPoolLd; fr = e->T[4]; break;
+        case 5: *d_ptr = e->ss.sc2; *count = B * 64; break;
+        case 6: *d_ptr = e->ss.sh2; *count = B * 64; break;
+        case 7: *d_ptr = e->ss.part2; *count = B * e->g.nt2 * 64 * 2; break;
+        case 8: {
+            const int form = src == SINC_OUT_PLANES ? 0 : src == SINC_OUT_F32 ? 1 : sinc_fused_norm(e->w.sinc) ? 3 : 2;
+            const int rec[16] = {form, e->pre ? 1 : 0, e->lastB, e->pending_B, x5_valid ? 1 : 0, e->last_rows, e->g.P2,
+                                 e->T[0], e->T[1], e->T[2], e->T[3], e->T[4], e->g.nt2, kPoolLd, 0, 0};
+            memcpy(e->info, rec, sizeof(rec));
+            *d_ptr = e->info; *count = 16;
+            break;
+        }
+        default:
+            dz_set_error("dz_emb_peek: unknown buffer %d", which);
+            return 2;
+    }
+    if (frames) *frames = fr;
+    return 0;
 }
 
 #ifdef DZ_EXPERIMENTS

@@ -430,6 +430,16 @@ class HipEmbedding(_HipTrunkEmbedding):
     def _pack(self, device):
         return PackedEmbedding(self._state, device, precision=self.precision, weight_interp=self.weight_interp)
 
+    PEEK_RECORD = ("form", "planes", "batch", "pending", "x5_valid", "pooled_rows", "P2", "T1", "T2", "T3", "T4", "T5",
+                   "nt2", "pooled_ld")
+
+    def peek_record(self, num_samples: int, handle=None) -> Dict[str, int]:
+        """The record of ``dz_emb_peek`` (buffer 8, host memory) by name: what the buffers of the last call hold and
+        in which form; no copy, no synchronisation.  ``handle``: one this model created for someone else."""
+        ptr, cnt, _ = self._peek_raw(handle or self._handles[num_samples][0], 8)
+        rec = (C.c_int * cnt).from_address(ptr.value)
+        return dict(zip(self.PEEK_RECORD, rec))
+
 
 class _HipGroupsEmbedding(_HipSpeakerEmbedding):
     """ECAPA-TDNN and the speechbrain x-vector: the same batch geometry, hence the same groups forward."""

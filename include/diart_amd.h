@@ -225,6 +225,26 @@ int dz_emb_use_wave_stats(dz_emb* emb, const float* d_moments);
 int dz_emb_frames(dz_emb* emb, const float* d_wave, long long wave_stride, int batch, void* stream);
 int dz_emb_pool(dz_emb* emb, const float* d_weights, int batch, int num_speakers,
                 int weight_frames, int normalize, float* d_out, void* stream);
+/* pointer + element count of a buffer of the handle as the LAST call left it (parity tests): a view, no copy and no
+ * launch.  B = chunks of the last dz_emb_frames / forward, P2 = frames per chunk at the SincNet's output = the row
+ * pitch of every activation; rows t >= the layer's valid frame count of a chunk are never read and hold anything.
+ * Counts are in 4-byte elements; "planes" = the two kb-major f16 planes (hi, lo * 2^11) of [B * P2 rows][n],
+ * [2][n / 32][B * P2][32], which take the same bytes as the f32 rows.
+ *   0  the last SincNet stage as tdnn1 consumes it, (B * P2, 64), channels 60 .. 63 padding; the record's `form`:
+ *        0 normalised planes  1 normalised f32 rows  2 raw y2, scale / shift (5, 6) applied on load
+ *        3 raw y2, normalised on load from the tile partials (7)
+ *   1  tdnn3's output, 2  tdnn4's output: (B * P2, 512), planes when the record says so, else f32 rows (tdnn1's and
+ *        tdnn2's outputs are overwritten by then)
+ *   3  tdnn5's output (B * P2, 1536) f32 rows — only where tdnn5 ran on its own; while the frames are pending at
+ *        tdnn4's output (tdnn5 runs inside the pooling call) there is none: *d_ptr = NULL, *count = 0
+ *   4  pooled (rows of the last pooling, ld): mean at columns 0 .. 1499, std at 1500 .. 2999
+ *   5, 6  InstanceNorm scale / shift of the last SincNet stage (B, 64), written in form 2 only
+ *   7  tile partials of the last SincNet stage (B, nt2, 64, 2)
+ *   8  the record, 16 ints in HOST memory (valid until the next call on the handle): form, planes (0 / 1), B,
+ *        pending chunks, tdnn5 valid (0 / 1), rows of the last pooling, P2, T[0 .. 4] (valid frames behind tdnn1 ..
+ *        tdnn5), nt2, ld of pooled, 0, 0
+ * *frames receives the valid frames per chunk of that buffer (P2, T[2], T[3], T[4]).                            */
+int dz_emb_peek(dz_emb* emb, int which, const void** d_ptr, long long* count, int* frames);
 int dz_emb_destroy(dz_emb* emb);
 
 /* ---- ECAPA-TDNN embedding (BASELINE.json config 3): replaces the callable behind
